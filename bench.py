@@ -171,6 +171,36 @@ def roofline_of(rep, prof_steps):
                          for e in fams[:int(os.environ.get("BENCH_TOPK", "8"))]]}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, eng):
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy (float32) - both networks' parameters and
+    optimiser state (the engine's checkpoints: `model.<param>`, `model.<param>.<exp_avg|exp_avg_sq>`, `cdae.<param>`,
+    `cdae.<param>.<square_avg|momentum_buffer>`) and the step's logged values (`cdae_loss`, `model_losses` = [model_loss, recon, prior],
+    `cdae_std` = the per-image noise levels of the cDAE update).  The inputs are seeded, so two builds run with the same arguments
+    can be compared array for array."""
+    import numpy as np
+    arrays = {}
+    for prefix, module, ck in (("model", eng.model, eng.model_checkpoint()), ("cdae", eng.cdae, eng.cdae_checkpoint())):
+        for k, t in ck["state_dict"].items():
+            arrays[f"{prefix}.{k}"] = t
+        names = [n for n, _ in module.named_parameters()]
+        for i, st in ck["optimizer"]["state"].items():
+            for k, t in st.items():
+                if torch.is_tensor(t):
+                    arrays[f"{prefix}.{names[i]}.{k}"] = t
+    arrays.update(cdae_loss=eng.loss_c, model_losses=eng.losses_m, cdae_std=eng.std_b)
+    host = {k: t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy() for k, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_CAP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_CAP_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(host), "bytes": total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -178,7 +208,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--prof-steps", type=int, default=5, help="instrumented steps for the live roofline numbers")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (parameters, optimiser state, losses) as DIR/<name>.npy "
+                         "(rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- process environment FIRST: HSA / RCCL read these when the runtime initialises, i.e. at the first call that touches the GPU
     # (torch.cuda.set_device below) - a default set after that point never takes effect in this process
@@ -315,6 +350,8 @@ def main():
                                                           "allreduce": "ardae_dp_allreduce_mean, captured in the step graphs"},
                        "dp_fallback": dp_fallback, "env": env_report}
     stats = eng.stats()
+    # the last timed step's outputs: taken before the instrumented steps below, which go on training
+    dumped = dump_outputs(args.dump_outputs, eng) if args.dump_outputs and rank == 0 else None
 
     # ---- live per-kernel timing (HIP events on the launch stream), separate from the throughput region
     roofline = None
@@ -362,6 +399,8 @@ def main():
             "ranks": rank_report,
             "roofline": roofline,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (contract)
             out["cpu_baseline"] = cpu_baseline()
             out["speedup_vs_cpu_baseline"] = steps_per_s / out["cpu_baseline"]["value"]

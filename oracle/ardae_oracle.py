@@ -809,17 +809,19 @@ def _grads_of(loss, p):
     return {n: g for n, g in zip(names, gs)}
 
 
-def cdae_update_grads(mc, cc, tc, pm, pc, x, noise):
+def cdae_update_grads(mc, cc, tc, pm, pc, x, noise, latents=None):
     """cDAE phase up to (not including) the optimiser step  (ivae_ardae.py:713-771).
-    Returns loss, grads dict (None for tensors the loss does not reach), std [B,1,1]."""
+    Returns loss, grads dict (None for tensors the loss does not reach), std [B,1,1].
+    latents: optional (latent_mean, latent) used in place of the encoder's (tests feed the reference's: u = std_scale (z - z0)
+    amplifies last-bit differences of the encoder between machines)."""
     B = x.size(0)
     with torch.no_grad():
-        z0 = encode(mc, pm, x, zero_noise(mc, B, x, noise.get("z0_raw")), 1)          # latent_mean (and the context for lt0)
+        z0 = encode(mc, pm, x, zero_noise(mc, B, x, noise.get("z0_raw")), 1) if latents is None else latents[0]   # latent_mean (and the context for lt0)
         if mc.clipped and tc.ctx_type == "lt0":      # the reference's two encode(x, std=0) calls draw separately (ivae_ardae.py:741,748)
             ctx = encode(mc, pm, x, zero_noise(mc, B, x, noise.get("ctx_raw")), 1)
         else:
             ctx = z0 if tc.ctx_type == "lt0" else cdae_context(mc, tc, pm, x, noise.get("ctx_raw")).unsqueeze(1)
-        latent = encode(mc, pm, x, sampler_noise(mc, noise, "sampler"), tc.nz_cdae)
+        latent = encode(mc, pm, x, sampler_noise(mc, noise, "sampler"), tc.nz_cdae) if latents is None else latents[1]
         u, std = latent_stats(latent, z0, tc.std_scale, tc.delta)
         stdmat = std * noise["sigma"]
         u_exp = u.unsqueeze(2).expand(B, tc.nz_cdae, tc.nstd, mc.z_dim).reshape(B, tc.nz_cdae * tc.nstd, mc.z_dim)

@@ -91,6 +91,14 @@ def test_oracle_step_matches_reference_fixture(golden_dir, name):
         closs, gc, std = O.cdae_update_grads(mc, cc, tc, pm, pc, xc, noise)
         assert abs(float(closs) - float(fx[pre + "cdae_loss"])) / float(fx[pre + "cdae_loss"]) < tol
         assert rel_l2(std, torch.tensor(fx[pre + "std"])) < tol
+        # the encoder outputs the reference saw; the cDAE gradients are compared from THEM: u = std_scale (z - z0) turns last-bit
+        # differences of the encoder (another CPU / BLAS sums in another order) into ~5e-3 of the gradients' cancelling row sums
+        z0_ref, latent_ref = torch.tensor(fx[pre + "z0"]), torch.tensor(fx[pre + "latent"])
+        z0 = O.encode(mc, pm, xc, O.zero_noise(mc, xc.size(0), xc, noise.get("z0_raw")), 1)
+        latent = O.encode(mc, pm, xc, O.sampler_noise(mc, noise, "sampler"), tc.nz_cdae)
+        assert z0.shape == z0_ref.shape and latent.shape == latent_ref.shape
+        assert rel_l2(z0, z0_ref) < tol and rel_l2(latent, latent_ref) < tol
+        _, gc, _ = O.cdae_update_grads(mc, cc, tc, pm, pc, xc, noise, latents=(z0_ref, latent_ref))
         for n, _ in O.cdae_param_spec(cc):
             if pre + "cdae_grads/" + n + "/none" in fx:
                 assert gc[n] is None
