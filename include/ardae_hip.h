@@ -165,6 +165,16 @@ int ardae_philox_normal_at(float* out, int64_t n, uint64_t seed, uint64_t offset
                            void* stream);
 int ardae_adam_ref_step_dev(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
                             double beta1, double beta2, double eps, const void* state, void* stream);
+/* Weight averaging of the model parameters: --m-weight-avg swa | polyak (torchcontrib.optim.SWA / Polyak around the model
+ * optimiser, ivae_ardae.py:158-164,559-565, freq 1).  t = model-optimiser steps done, the current one included: state.adam_step
+ * when state is non-NULL (read on the device: a captured step replays correctly), else the argument t.  origin = the t of the
+ * first averaging step (start + 1).  t < origin: avg is not written; t == origin: avg = p (a copy); t > origin, k = t - origin:
+ *   avg = avg + (p - avg) * w,  w = fp32(1 / (k + 1)) (SWA) | fp32(1 - decay) (Polyak), each operation rounded separately.
+ * avg and p must not overlap; float4 accesses where both share their offset inside 16 bytes, scalar ones otherwise. */
+#define ARDAE_WEIGHT_AVG_SWA 0
+#define ARDAE_WEIGHT_AVG_POLYAK 1
+int ardae_weight_avg(float* avg, const float* p, int64_t n, int kind, double decay, int64_t origin, const void* state, int64_t t,
+                     void* stream);
 /* torch.optim.RMSprop(lr, momentum) as built at ivae_ardae.py:625-626 (alpha .99, eps 1e-8, not centred) */
 int ardae_rmsprop_step(float* p, const float* g, float* square_avg, float* momentum_buffer, int64_t n, double lr,
                        double alpha, double eps, double momentum, void* stream);

@@ -101,6 +101,10 @@ int ardae_adam_ref_step_dev(float* p, const float* g, float* exp_avg, float* exp
                             double beta1, double beta2, double eps, const void* state, void* stream) {
   return launch_adam_ref_dev(p, g, exp_avg, exp_avg_sq, max_exp_avg_sq, n, beta1, beta2, eps, state, (hipStream_t)stream);
 }
+int ardae_weight_avg(float* avg, const float* p, int64_t n, int kind, double decay, int64_t origin, const void* state, int64_t t,
+                     void* stream) {
+  return launch_weight_avg(avg, p, n, kind, decay, origin, state, t, (hipStream_t)stream);
+}
 int ardae_rmsprop_step(float* p, const float* g, float* square_avg, float* momentum_buffer, int64_t n, double lr,
                        double alpha, double eps, double momentum, void* stream) {
   return launch_rmsprop(p, g, square_avg, momentum_buffer, n, lr, alpha, eps, momentum, (hipStream_t)stream);

@@ -47,6 +47,9 @@ int launch_bernoulli(const float* p, int64_t rows, int cols, float* out, uint64_
 // utils/optim.py:86-106 (old-style Adam: eps added before the bias correction)
 int launch_adam_ref(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, double lr, double beta1, double beta2,
                     double eps, int step, hipStream_t st);
+// --m-weight-avg swa | polyak (ivae_ardae.py:559-565): see ardae_weight_avg in ardae_hip.h; state null = host t
+int launch_weight_avg(float* avg, const float* p, int64_t n, int kind, double decay, int64_t origin, const void* state, int64_t t,
+                      hipStream_t st);
 // torch.optim.RMSprop(lr, momentum) as constructed at ivae_ardae.py:625-626 (alpha, eps defaults; not centred)
 int launch_rmsprop(float* p, const float* g, float* sq, float* buf, int64_t n, double lr, double alpha, double eps,
                    double momentum, hipStream_t st);

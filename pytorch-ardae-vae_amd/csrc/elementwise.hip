@@ -422,6 +422,50 @@ __global__ void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ 
   }
 }
 
+// Weight averaging of the model parameters (torchcontrib.optim.SWA / Polyak around the model optimiser, ivae_ardae.py:559-565,
+// freq 1).  t = model-optimiser steps done, the current one included (StepState::adam_step while the step is applied, or t_host);
+// k = t - origin = earlier averaging steps.  t < origin: nothing is written;  k == 0: avg = p (a copy, not arithmetic);  else
+//   avg = avg + (p - avg) * w,   w = fp32(1 / (k + 1)) (SWA) | fp32(1 - decay) (Polyak)
+// with the three operations rounded one by one: torch's avg.add_((p - avg) * w) bit for bit.  (hipcc contracts a * b + c to an FMA by
+// default, __fmul_rn / __fadd_rn included; the fused form is up to a few ulps away from torch's where p - avg nearly cancels avg.)
+__device__ __forceinline__ float weight_avg1(float a, float q, float w, bool first) {
+#pragma clang fp contract(off)
+  return first ? q : a + (q - a) * w;
+}
+
+__global__ __launch_bounds__(256) void weight_avg_kernel(float* __restrict__ avg, const float* __restrict__ p, int64_t n, int kind,
+                                                         float w_polyak, int64_t origin, const StepState* state, int64_t t_host) {
+  const int64_t t = state ? state->adam_step : t_host;
+  if (t < origin) return;
+  const int64_t k = t - origin;
+  const bool first = k == 0;
+  const float w = kind == ARDAE_WEIGHT_AVG_SWA ? (float)(1.0 / (double)(k + 1)) : w_polyak;
+  // float4 body between a scalar head (the elements before avg's first 16-byte boundary) and a scalar tail; when p sits at another
+  // offset inside its 16 bytes than avg (module-path runs), no float4 pair exists and every element takes the scalar path
+  const uintptr_t ma = reinterpret_cast<uintptr_t>(avg) & 15, mp = reinterpret_cast<uintptr_t>(p) & 15;
+  int64_t head = n, nvec = 0;
+  if (ma == mp) {
+    head = (int64_t)((16 - ma) & 15) / 4;
+    if (head > n) head = n;
+    nvec = (n - head) / 4;
+  }
+  const int64_t tail0 = head + 4 * nvec;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  f32x4* __restrict__ av = reinterpret_cast<f32x4*>(avg + head);
+  const f32x4* __restrict__ pv = reinterpret_cast<const f32x4*>(p + head);
+  for (int64_t i = tid; i < nvec; i += stride) {
+    const f32x4 q = pv[i];
+    f32x4 a = first ? q : av[i];
+    a.x = weight_avg1(a.x, q.x, w, first);
+    a.y = weight_avg1(a.y, q.y, w, first);
+    a.z = weight_avg1(a.z, q.z, w, first);
+    a.w = weight_avg1(a.w, q.w, w, first);
+    av[i] = a;
+  }
+  for (int64_t i = tid; i < head; i += stride) avg[i] = weight_avg1(avg[i], p[i], w, first);
+  for (int64_t i = tail0 + tid; i < n; i += stride) avg[i] = weight_avg1(avg[i], p[i], w, first);
+}
+
 __global__ void axpy_kernel(const float* __restrict__ x, int64_t n, float alpha, float* __restrict__ y) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] += alpha * x[i];
 }
@@ -723,6 +767,18 @@ int launch_rmsprop(float* p, const float* g, float* sq, float* buf, int64_t n, d
   ARDAE_CHECK_ARG(p && g && sq && n > 0 && (momentum <= 0.0 || buf), "rmsprop: bad arguments");
   hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_for(n)), dim3(256), 0, st, p, g, sq, buf, n, (float)lr, (float)alpha, (float)eps,
                      (float)momentum);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_weight_avg(float* avg, const float* p, int64_t n, int kind, double decay, int64_t origin, const void* state, int64_t t,
+                      hipStream_t st) {
+  ARDAE_CHECK_ARG(avg && p && n > 0 && origin >= 1, "weight_avg: bad arguments");
+  ARDAE_CHECK_ARG(kind == ARDAE_WEIGHT_AVG_SWA || (kind == ARDAE_WEIGHT_AVG_POLYAK && decay >= 0.0 && decay <= 1.0),
+                  "weight_avg: kind must be ARDAE_WEIGHT_AVG_SWA or ARDAE_WEIGHT_AVG_POLYAK (0 <= decay <= 1)");
+  ARDAE_CHECK_ARG((const char*)avg + n * 4 <= (const char*)p || (const char*)p + n * 4 <= (const char*)avg, "weight_avg: avg and p overlap");
+  hipLaunchKernelGGL(weight_avg_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, avg, p, n, kind, (float)(1.0 - decay), origin,
+                     (const StepState*)state, t);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }

@@ -5,6 +5,7 @@ engine's Philox stream (or is injected for parity tests), losses stay on the dev
 Data parallel: the image batch is sharded over ranks, parameters are replicated, and the two flat gradient
 buffers are all-reduced (RCCL over xGMI via torch.distributed backend "nccl") before their optimiser steps.
 """
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -14,6 +15,7 @@ import torch
 from . import _lib as L
 from . import dist
 from . import rng
+from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
 
 @dataclass
@@ -35,6 +37,19 @@ class TrainConfig:
     d_beta1: float = 0.5          # --d-beta1 (cDAE Adam / amsgrad)
     cdae_ctx_type: str = "lt0"    # --cdae-ctx-type: "lt0" (context = encode(x, std=0)) | "hidden1a" (aux models: encoder hiddens) | "data"
     ctx_data_center: bool = True  # "data": the image as 2x - 1 when 'mnist' is in --dataset (ivae_ardae.py:731-734,810-813), x itself otherwise
+    m_weight_avg: str = "none"    # --m-weight-avg none | swa | polyak (ivae_ardae.py:158-164,559-565): an average of the model's weights,
+    m_weight_avg_start: int = 1000    # updated at every model step t > --m-weight-avg-start (rules: optim.py, "Weight averaging")
+    m_weight_avg_decay: float = 0.998  # --m-weight-avg-decay (Polyak)
+    m_weight_avg_freq: int = 1    # torchcontrib's polyak_freq / swa_freq: the script always passes 1, nothing else is implemented
+
+    def __post_init__(self):
+        if self.m_weight_avg != "none" and self.m_weight_avg not in WEIGHT_AVG_KINDS:
+            raise NotImplementedError(f"unknown weight averaging: {self.m_weight_avg}")           # like ivae_ardae.py:555-556 for optimisers
+        if int(self.m_weight_avg_freq) != 1:
+            raise NotImplementedError(f"m_weight_avg_freq {self.m_weight_avg_freq}: only 1 is implemented (ivae_ardae.py:561,563 always pass 1)")
+        if int(self.m_weight_avg_start) < 0 or not 0.0 <= float(self.m_weight_avg_decay) <= 1.0:
+            raise ValueError(f"m_weight_avg_start must be >= 0 and m_weight_avg_decay in [0, 1] (got {self.m_weight_avg_start}, "
+                             f"{self.m_weight_avg_decay})")
 
 
 def annealing_func(val_init, val_fin, val_annealing, step):
@@ -197,6 +212,13 @@ class ArdaeEngine:
         # --m-optimizer / --d-optimizer (ivae_ardae.py:545-556,612-622); the model's RMSprop is built with d_momentum there (:553)
         self.opt_m = _FlatOpt(cfg.m_optimizer, model._flat, model._flat.numel(), cfg.m_lr, cfg.m_beta1, cfg.d_momentum, state=self.state)
         self.opt_c = _FlatOpt(cfg.d_optimizer, cdae._flat, self.n_c, cfg.d_lr, cfg.d_beta1, cfg.d_momentum)
+        # --m-weight-avg (ivae_ardae.py:559-565): the averaged model weights, a buffer laid out like model._flat (replicated over the ranks,
+        # updated from the all-reduced weights) that `ardae_weight_avg` updates in the model-update unit.  _avg_origin: the t of the first
+        # averaging step (start + 1 unless a checkpoint says otherwise); _avg_swap: None, or whether use_averaged() swapped the buffers
+        self.wavg = None if cfg.m_weight_avg == "none" else cfg.m_weight_avg
+        self.avg = torch.zeros_like(model._flat) if self.wavg else None
+        self._avg_origin = int(cfg.m_weight_avg_start) + 1
+        self._avg_swap = None
         if graph not in (True, False, "auto"):
             raise ValueError(f"graph must be True, False or 'auto', got {graph!r}")
         self.use_graph = bool(graph) and L.debug_knob("ARDAE_GRAPH", "1") != "0"
@@ -416,6 +438,7 @@ class ArdaeEngine:
     # ------------------------------------------------------------------------------------------------------------
     def cdae_phase(self, x, noise=None, apply_update=True):
         """ivae_ardae.py:713-779 (one cDAE update).  noise: optional dict(sampler [N,nd], sigma [B,nz,1], eps [N,z])."""
+        self._require_trained("cdae_phase()")
         self._cdae_grads(x, noise)
         if self.dp:
             self._allreduce(self.grads_c[:self.n_c])
@@ -497,6 +520,7 @@ class ArdaeEngine:
 
     def vae_forward_part(self, x, noise=None, beta=None, draw=None):
         """ivae_ardae.py:781-827: everything of the VAE update that does not involve the cDAE (forward, ELBO pieces, z0, u)."""
+        self._require_trained("vae_forward_part()")
         self._check_batch(x, "vae_forward_part")
         cfg, lib, st = self.cfg, self.lib, L.stream_ptr()
         beta = cfg.beta if beta is None else beta
@@ -527,6 +551,7 @@ class ArdaeEngine:
 
     def vae_backward_part(self, x, nv, beta=None, apply_update=True):
         """ivae_ardae.py:829-846: entropy gradient through the (updated) cDAE, backward, Adam."""
+        self._require_trained("vae_backward_part()")
         self._vae_backward_grads(x, nv, beta)
         if self.dp:
             self._allreduce(self.grads_m)
@@ -556,6 +581,11 @@ class ArdaeEngine:
 
     def _model_update(self):
         self.opt_m.apply(self.lib, self.grads_m, self._in_step)   # in a step: t and the bias corrections come from the device step state
+        if self.avg is not None:
+            # t from the device block (not yet advanced: it still holds this step's t), so a replayed graph averages at the right steps
+            L.check(self.lib.ardae_weight_avg(L.ptr(self.avg), L.ptr(self.model._flat), self.avg.numel(), WEIGHT_AVG_KINDS[self.wavg],
+                                              float(self.cfg.m_weight_avg_decay), self._avg_origin, ctypes.c_void_p(self.state.data_ptr()), 0,
+                                              L.stream_ptr()), "ardae_weight_avg")
         if not self._in_step:
             self.step_count += 1
             self.opt_m.steps = self.step_count
@@ -613,6 +643,7 @@ class ArdaeEngine:
     def step(self, x_cdae, x_vae, noise=None, beta=None):
         """One iteration of the reference loop: num_cdae_updates cDAE updates (each on its own batch in the reference; the
         caller passes a list of batches when num_cdae_updates > 1) followed by one VAE update."""
+        self._require_trained("step()")
         many = isinstance(x_cdae, (list, tuple))
         xs = list(x_cdae) if many else [x_cdae] * self.cfg.num_cdae_updates
         for x in xs:
@@ -708,9 +739,19 @@ class ArdaeEngine:
         return out
 
     def model_checkpoint(self):
+        """With --m-weight-avg the optimiser entry takes the wrapper layout of optim.py ("Weight averaging"): the inner optimiser's state
+        under "opt_state", the averaged weights per parameter, n_avg / step_counter in the param group.  Refused while the averaged
+        weights are in (the reference saves after use_sgd())."""
+        self._require_trained("model_checkpoint()")
         nparams = len(list(self.model.named_parameters()))
+        opt = {"state": self._opt_state(self.model, self.opt_m), "param_groups": [self.opt_m.param_group(nparams)]}
+        if self.avg is not None:
+            n_avg = self._n_avg()
+            opt["param_groups"][0].update(n_avg=n_avg, step_counter=self.step_count)
+            bufs = dict(enumerate(v.clone() for v in self._per_param(self.model, self.avg, self.avg.numel()))) if n_avg else {}
+            opt = wrap_state_dict(opt, self.wavg, bufs)
         return {"state_dict": {k: t.clone() for k, t in self.model.state_dict().items()},
-                "optimizer": {"state": self._opt_state(self.model, self.opt_m), "param_groups": [self.opt_m.param_group(nparams)]},
+                "optimizer": opt,
                 # state_version 2 (round 3 on): the device step block describes the COMING step (the last launch of a step advances it)
                 "engine": {"state_version": 2, "step_count": self.step_count, "cdae_steps": self.opt_c.steps, "rng_seed": rng.get_state()["seed"],
                            "rng_host_offset": rng.get_state()["offset"], "step_state": self.state.cpu().clone()}}
@@ -749,12 +790,17 @@ class ArdaeEngine:
         return steps.pop() if steps else 0
 
     def load_checkpoints(self, model_ckpt, cdae_ckpt):
-        """Inverse of model_checkpoint() / cdae_checkpoint(); also accepts files written by the reference loop."""
+        """Inverse of model_checkpoint() / cdae_checkpoint(); also accepts files written by the reference loop.  The model's optimiser
+        entry may be plain or in the weight-averaging wrapper layout: an engine without averaging drops a wrapped file's buffer, an engine
+        with averaging starts a fresh average at the next step when the file has none (a plain file loaded past the start)."""
+        self._require_trained("load_checkpoints()")
+        m_opt, w_kind, w_bufs = unwrap_state_dict(model_ckpt["optimizer"])
+        if self.avg is not None and w_kind is not None and w_kind != self.wavg:
+            raise ValueError(f"model checkpoint: holds a {w_kind!r} average, but this engine was built with m_weight_avg={self.wavg!r}")
         self.model.load_state_dict(model_ckpt["state_dict"])
         self.cdae.load_state_dict(cdae_ckpt["state_dict"])
         eng = model_ckpt.get("engine")
-        m_steps = self._load_opt_state(self.model, self.opt_m, model_ckpt["optimizer"]["state"], "model checkpoint",
-                                       model_ckpt["optimizer"].get("param_groups"))
+        m_steps = self._load_opt_state(self.model, self.opt_m, m_opt["state"], "model checkpoint", m_opt.get("param_groups"))
         c_steps = self._load_opt_state(self.cdae, self.opt_c, cdae_ckpt["optimizer"]["state"], "cdae checkpoint",
                                        cdae_ckpt["optimizer"].get("param_groups"))
         # optimisers without per-parameter state (SGD) carry no step count: the engine's own record, if the file has one
@@ -775,10 +821,84 @@ class ArdaeEngine:
             self.opt_m.advance(self.lib, self.RNG_STRIDE)
         self.opt_c.state.zero_()
         self.opt_c.state[1] = self.opt_c.steps
-        self._graph = None      # parameters were rewritten outside of the captured step
+        if self.avg is not None:
+            self._load_average(m_opt, w_kind, w_bufs)
+        self._graph = None      # parameters were rewritten outside of the captured step (and the averaging origin is a kernel argument)
         if self._log is not None:
             self._log.resync()   # the log's iteration numbers come from the device t: first unreported iteration = step_count + 1
         self.repack()
+
+    # ------------------------------------------------------------------------------------------------------------
+    # Weight averaging (--m-weight-avg, ivae_ardae.py:559-565,644-673)
+    def _n_avg(self):
+        """Averaging steps done so far (torchcontrib's n_avg)."""
+        return max(0, self.step_count - self._avg_origin + 1)
+
+    def _load_average(self, m_opt, w_kind, w_bufs):
+        groups = m_opt.get("param_groups") or [{}]
+        n_avg = int(groups[0].get("n_avg", 0)) if w_kind is not None else 0
+        views = self._per_param(self.model, self.avg, self.avg.numel())
+        if n_avg > self.step_count:
+            raise ValueError(f"model checkpoint: {n_avg} averaging steps recorded after only {self.step_count} optimiser steps")
+        if n_avg > 0:
+            missing = [i for i in range(len(views)) if i not in w_bufs]
+            if missing:
+                raise ValueError(f"model checkpoint: {n_avg} averaging steps recorded, but no averaged weights for parameters {missing}")
+            with torch.no_grad():
+                for i, v in enumerate(views):
+                    v.copy_(w_bufs[i])
+            self._avg_origin = self.step_count + 1 - n_avg
+        else:       # no average in the file: averaging starts at start + 1, or at the next step if the file is already past it
+            self._avg_origin = max(int(self.cfg.m_weight_avg_start), self.step_count) + 1
+
+    def _require_trained(self, what):
+        if self._avg_swap is not None:
+            raise RuntimeError(f"ArdaeEngine.{what} while the averaged weights are in: call use_trained() first")
+
+    def _swap_average(self):
+        with torch.no_grad():
+            tmp = self.model._flat.clone()
+            self.model._flat.copy_(self.avg)
+            self.avg.copy_(tmp)
+            for p in self.model.parameters():
+                torch.autograd.graph.increment_version(p)
+        self.model.mark_dirty()          # the module path (model.logprob, ...) re-packs its weight image at its next use
+        self._pack_model()               # ... and so does the engine's
+
+    def use_averaged(self):
+        """ivae_ardae.py:646-647 (model_optimizer.use_buf()): the averaged weights into model._flat, in place (the captured graphs keep
+        their pointers), so that model.logprob(...) evaluates them.  Before the first averaging step there is no average and the raw
+        weights stay.  step(), the phase calls and the checkpoints are refused until use_trained()."""
+        if self.avg is None:
+            raise RuntimeError("use_averaged(): this engine was built with m_weight_avg='none'")
+        if self._avg_swap is not None:
+            return
+        self._avg_swap = self._n_avg() > 0
+        if self._avg_swap:
+            self._swap_average()
+
+    def use_trained(self):
+        """ivae_ardae.py:671-672 (model_optimizer.use_sgd()): the raw weights back, bit for bit."""
+        if self._avg_swap is None:
+            return
+        if self._avg_swap:
+            self._swap_average()
+        self._avg_swap = None
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """with engine.averaged_weights(): ll = model.logprob(x) - use_averaged() ... use_trained()."""
+        self.use_averaged()
+        try:
+            yield self.model
+        finally:
+            self.use_trained()
+
+    def averaged_params(self):
+        """The averaged weights as a flat tensor in named_parameters() order (None before the first averaging step)."""
+        if self.avg is None or self._n_avg() == 0:
+            return None
+        return self.model._flat if self._avg_swap else self.avg
 
     def stats(self):
         """Host copy of the logged scalars of ivae_ardae.py:756-758,774,837-841 (this is the only synchronising call)."""

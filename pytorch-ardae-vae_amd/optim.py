@@ -174,3 +174,200 @@ class RMSprop(_FlatStateOptimizer):
             for p in active:
                 _bump(p)
         return loss
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Weight averaging of the model parameters: --m-weight-avg polyak | swa (ivae_ardae.py:158-164,559-565,646-647,671-672, where the
+# model optimiser is wrapped in torchcontrib.optim.Polyak / SWA).  torchcontrib is a VCS dependency that is not importable here, so its
+# rules are restated as this project's definition, after upstream torchcontrib's SWA in automatic mode with freq 1 (the only freq the
+# script passes):
+#   t = steps of the wrapped optimiser, the current one included; averaging happens at every step with t > start;
+#   k = t - (start + 1) = earlier averaging steps
+#   SWA:    avg += (p - avg) * (1 / (k + 1))                    (k = 0: avg = p exactly)
+#   Polyak: k = 0: avg = p exactly;  k > 0: avg += (p - avg) * (1 - decay)
+#   w is rounded to fp32 and the update keeps the order avg + (p - avg) * w (kernel: ardae_weight_avg).  Before the first averaging
+#   step there is no buffer: use_buf() then leaves the raw weights in place, as torchcontrib's swap does when it finds none.
+# Checkpoint layout: upstream SWA.state_dict() with parameter INDICES as keys (upstream uses id(tensor), which does not survive a file):
+#   {"opt_state": <inner optimizer's state>, "swa_state" | "polyak_state": {idx: {"swa_buffer" | "polyak_buffer": tensor}},
+#    "param_groups": <inner optimizer's groups, each with "n_avg" (averaging steps done) and "step_counter" (t)>}
+# The Polyak key names are an assumption (the fork that adds Polyak is not available to compare against).
+WEIGHT_AVG_KINDS = {"swa": 0, "polyak": 1}      # ARDAE_WEIGHT_AVG_SWA / ARDAE_WEIGHT_AVG_POLYAK
+
+
+def weight_avg_keys(kind):
+    """("<kind>_state", "<kind>_buffer"): the two key names of the wrapper layout."""
+    return f"{kind}_state", f"{kind}_buffer"
+
+
+def wrap_state_dict(inner, kind, buffers):
+    """A torch.optim state_dict ({"state", "param_groups"}, groups already carrying n_avg / step_counter) and the averaged buffers
+    {param index: tensor} -> the wrapper layout above."""
+    if kind not in WEIGHT_AVG_KINDS:
+        raise NotImplementedError(f"unknown weight averaging: {kind}")
+    skey, bkey = weight_avg_keys(kind)
+    return {"opt_state": inner["state"], skey: {int(i): {bkey: b} for i, b in buffers.items()}, "param_groups": inner["param_groups"]}
+
+
+def unwrap_state_dict(sd):
+    """Inverse of wrap_state_dict: (inner torch.optim state_dict, kind, {param index: buffer}).  A plain optimiser state_dict passes
+    through as (sd, None, {})."""
+    if "opt_state" not in sd:
+        return sd, None, {}
+    kinds = [k for k in WEIGHT_AVG_KINDS if weight_avg_keys(k)[0] in sd]
+    if len(kinds) != 1:
+        raise ValueError(f"wrapped optimiser state with {'no' if not kinds else 'more than one'} averaging state ({sorted(sd)})")
+    kind = kinds[0]
+    skey, bkey = weight_avg_keys(kind)
+    bufs = {int(i): st[bkey] for i, st in sd[skey].items() if st.get(bkey) is not None}
+    return {"state": sd["opt_state"], "param_groups": sd["param_groups"]}, kind, bufs
+
+
+class _WeightAverage:
+    """torchcontrib.optim.SWA / Polyak (automatic mode, freq 1) around an optimiser over this package's modules (net.Adam, net.RMSprop,
+    or any torch optimiser).  The buffers of a param group are views of one allocation laid out like the parameters, so a run of
+    parameters that are adjacent in memory (a module's flat buffer) is averaged by ONE `ardae_weight_avg` launch."""
+
+    def __init__(self, optimizer, kind, start, freq, decay=None):
+        if kind not in WEIGHT_AVG_KINDS:
+            raise NotImplementedError(f"unknown weight averaging: {kind}")
+        if freq != 1:
+            raise NotImplementedError(f"{kind} freq {freq}: only freq 1 is implemented (ivae_ardae.py:561,563 always passes 1)")
+        if start is None or int(start) < 0:
+            raise ValueError(f"{kind} start must be an int >= 0 (manual mode is not implemented), got {start!r}")
+        if decay is not None and not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"invalid Polyak decay: {decay}")
+        self.optimizer, self.kind, self.start = optimizer, kind, int(start)
+        self.decay = 0.0 if decay is None else float(decay)
+        self.state = {}             # param -> {"<kind>_buffer": tensor}
+        self._swapped = None        # inside use_buf(): the parameters whose values were swapped with their buffers
+        for group in self.param_groups:
+            group.setdefault("n_avg", 0)
+            group.setdefault("step_counter", 0)
+
+    @property
+    def param_groups(self):
+        return self.optimizer.param_groups
+
+    @property
+    def defaults(self):
+        return self.optimizer.defaults
+
+    def zero_grad(self, set_to_none=True):
+        self.optimizer.zero_grad(set_to_none=set_to_none)
+
+    def _buffer(self, p):
+        return self.state.get(p, {}).get(weight_avg_keys(self.kind)[1])
+
+    def _alloc(self, params):
+        """Buffers for `params` as views of one allocation whose 16-byte phase matches the first parameter's (float4 path)."""
+        bkey = weight_avg_keys(self.kind)[1]
+        need = [p for p in params if self._buffer(p) is None]
+        if not need:
+            return
+        total = sum(p.numel() for p in need)
+        raw = torch.zeros(total + 3, device=need[0].device, dtype=torch.float32)
+        off = ((need[0].data_ptr() - raw.data_ptr()) // 4) % 4
+        for p in need:
+            self.state.setdefault(p, {})[bkey] = raw[off:off + p.numel()].view_as(p)
+            off += p.numel()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if self._swapped is not None:
+            raise RuntimeError(f"{type(self).__name__}.step() while the averaged weights are in: call use_sgd() first")
+        loss = self.optimizer.step(closure)
+        lib = L.lib()
+        for group in self.param_groups:
+            group["step_counter"] += 1
+            t = group["step_counter"]
+            if t <= self.start:
+                continue
+            params = list(group["params"])
+            self._alloc(params)
+            origin = t - group["n_avg"]          # k = t - origin = averaging steps already in the buffers
+            for run in _runs([(p.data, self._buffer(p)) for p in params]):
+                n = sum(x.numel() for x in run[0])
+                L.check(lib.ardae_weight_avg(L.ptr(run[1][0]), L.ptr(run[0][0]), n, WEIGHT_AVG_KINDS[self.kind], self.decay, origin, None, t,
+                                             L.stream_ptr()), "ardae_weight_avg")
+            group["n_avg"] += 1
+        return loss
+
+    @torch.no_grad()
+    def _swap(self, params):
+        for p in params:
+            buf = self._buffer(p)
+            tmp = p.data.clone()
+            p.data.copy_(buf)
+            buf.copy_(tmp)
+            _bump(p)                 # the owning module re-packs its weight image at its next use
+
+    def use_buf(self):
+        """ivae_ardae.py:646-647: the averaged weights into the parameters (in place); parameters without a buffer (no averaging step
+        yet) keep their raw values."""
+        if self._swapped is not None:
+            return
+        self._swapped = [p for g in self.param_groups for p in g["params"] if self._buffer(p) is not None]
+        self._swap(self._swapped)
+
+    def use_sgd(self):
+        """ivae_ardae.py:671-672: the raw weights back, bit for bit."""
+        if self._swapped is None:
+            return
+        self._swap(self._swapped)
+        self._swapped = None
+
+    def state_dict(self):
+        if self._swapped is not None:
+            raise RuntimeError(f"{type(self).__name__}.state_dict() while the averaged weights are in: call use_sgd() first")
+        bufs, i = {}, 0
+        for g in self.param_groups:
+            for p in g["params"]:
+                if self._buffer(p) is not None:
+                    bufs[i] = self._buffer(p)
+                i += 1
+        return wrap_state_dict(self.optimizer.state_dict(), self.kind, bufs)
+
+    def load_state_dict(self, state_dict):
+        """The wrapper layout (this wrapper's or the fused engine's model_checkpoint()['optimizer']) or a plain optimiser state_dict; a
+        plain one past `start` starts a fresh average at the next step."""
+        if self._swapped is not None:
+            raise RuntimeError(f"{type(self).__name__}.load_state_dict() while the averaged weights are in: call use_sgd() first")
+        inner, kind, bufs = unwrap_state_dict(state_dict)
+        if kind is not None and kind != self.kind:
+            raise ValueError(f"the state holds a {kind!r} average, this wrapper is {self.kind!r}")
+        self.optimizer.load_state_dict(inner)
+        self.state = {}
+        i = 0
+        for group in self.param_groups:
+            steps = [int(st["step"]) for p in group["params"] for st in (self.optimizer.state.get(p, {}),) if "step" in st]
+            group.setdefault("step_counter", max(steps) if steps else 0)
+            if kind is None:
+                group["n_avg"] = 0
+            group.setdefault("n_avg", 0)
+            params = list(group["params"])
+            mine = [p for k, p in enumerate(params, i) if k in bufs]
+            if group["n_avg"] and len(mine) != len(params):
+                raise ValueError(f"{self.kind} state: {group['n_avg']} averaging steps recorded but buffers for {len(mine)} of {len(params)} parameters")
+            self._alloc(mine)
+            with torch.no_grad():
+                for k, p in enumerate(params, i):
+                    if k in bufs:
+                        self._buffer(p).copy_(bufs[k])
+            i += len(params)
+
+
+class Polyak(_WeightAverage):
+    """torchcontrib.optim.Polyak(optimizer, polyak_start, polyak_freq=1, polyak_decay) as built at ivae_ardae.py:561 (decay default:
+    the script's --m-weight-avg-decay default)."""
+
+    def __init__(self, optimizer, polyak_start, polyak_freq=1, polyak_decay=0.998):
+        super().__init__(optimizer, "polyak", polyak_start, polyak_freq, polyak_decay)
+
+
+class SWA(_WeightAverage):
+    """torchcontrib.optim.SWA(optimizer, swa_start, swa_freq=1) as built at ivae_ardae.py:563 (no swa_lr: the script passes none)."""
+
+    def __init__(self, optimizer, swa_start, swa_freq=1, swa_lr=None):
+        if swa_lr is not None:
+            raise NotImplementedError("swa_lr (SWA's learning-rate schedule) is never used by ivae_ardae.py and is not implemented")
+        super().__init__(optimizer, "swa", swa_start, swa_freq)
