@@ -17,8 +17,10 @@ from ardae_amd import _lib as L
 pytestmark = pytest.mark.gpu
 
 
-def run_batch(specs, seed):
-    """specs: list of (M, O, I, npairs, want_bias, want_rowscale)."""
+def run_batch(specs, seed, beta=0.0, pad=0):
+    """specs: list of (M, O, I, npairs, want_bias, want_rowscale).  beta != 0: the outputs are prefilled and must come back as
+    beta * prefill + sum (the accumulating form every model backward passes its grads_beta through); pad > 0: G and X are column
+    blocks of wider matrices (ldG = O + pad, ldX = I + pad)."""
     g = torch.Generator(device="cuda").manual_seed(seed)
     lib = L.lib()
     probs = (L.WgradProblem * len(specs))()
@@ -26,10 +28,10 @@ def run_batch(specs, seed):
     for k, (M, O, I, npairs, wb, wr) in enumerate(specs):
         p = probs[k]
         p.M, p.O, p.I, p.npairs = M, O, I, npairs
-        Gs = [torch.randn(M, O, device="cuda", generator=g) for _ in range(npairs)]
-        Xs = [torch.randn(M, I, device="cuda", generator=g) for _ in range(npairs)]
+        Gs = [torch.randn(M, O + pad, device="cuda", generator=g)[:, :O] for _ in range(npairs)]
+        Xs = [torch.randn(M, I + pad, device="cuda", generator=g)[:, pad:] for _ in range(npairs)]
         for q in range(npairs):
-            p.G[q], p.ldG[q], p.X[q], p.ldX[q] = Gs[q].data_ptr(), O, Xs[q].data_ptr(), I
+            p.G[q], p.ldG[q], p.X[q], p.ldX[q] = Gs[q].data_ptr(), O + pad, Xs[q].data_ptr(), I + pad
         sig = torch.randn(M, device="cuda", generator=g)
         p.bias_pair = npairs - 1 if (wb or wr) else -1
         p.rowscale = sig.data_ptr() if wr else None
@@ -41,16 +43,28 @@ def run_batch(specs, seed):
         p.out, p.ldout = out.data_ptr(), I + 3
         p.out_bias = ob.data_ptr() if wb else None
         p.out_rowscale, p.ld_rowscale = (ors[:, 2:].data_ptr(), 5) if wr else (None, 0)
-        p.beta = 0.0
-        keep += Gs + Xs + [sig, part, pvec, out, ob, ors]
+        p.beta = beta
         dW = sum(Gs[q].double().T @ Xs[q].double() for q in range(npairs))
         Gb = Gs[p.bias_pair].double() if p.bias_pair >= 0 else None
-        refs.append((out, ob, ors, dW, Gb.sum(0) if wb else None, (sig.double()[:, None] * Gb).sum(0) if wr else None, I))
+        bsum = Gb.sum(0) if wb else None
+        rsum = (sig.double()[:, None] * Gb).sum(0) if wr else None
+        if beta != 0.0:
+            out[:, :I] = torch.randn(O, I, device="cuda", generator=g) * dW.abs().max().float()
+            dW = dW + beta * out[:, :I].double()
+            if wb:
+                ob.copy_(torch.randn(O, device="cuda", generator=g) * bsum.abs().max().float())
+                bsum = bsum + beta * ob.double()
+            if wr:
+                ors[:, 2] = torch.randn(O, device="cuda", generator=g) * rsum.abs().max().float()
+                rsum = rsum + beta * ors[:, 2].double()
+        keep += Gs + Xs + [sig, part, pvec, out, ob, ors]
+        refs.append((out, ob, ors, dW, bsum, rsum, I))
     L.check(lib.ardae_wgrad_batch(probs, len(specs), L.stream_ptr()), "ardae_wgrad_batch")
     torch.cuda.synchronize()
     for out, ob, ors, dW, bsum, rsum, I in refs:
         assert float((out[:, :I].double() - dW).abs().max() / dW.abs().max()) < 1e-5
         assert torch.isnan(out[:, I:]).all()                              # nothing written outside the [O, I] view
+        assert torch.isnan(ors[:, :2]).all() and torch.isnan(ors[:, 3:]).all()
         if bsum is not None:
             assert float((ob.double() - bsum).abs().max() / bsum.abs().max()) < 1e-5
         if rsum is not None:
@@ -82,6 +96,27 @@ def test_wgrad_many_tiles_several_launches():
     run_batch([(4096, 1024, 1024, 2, True, True), (4096, 1024, 1024, 1, True, False), (4096, 1024, 1024, 2, False, False),
                (4096, 512, 512, 2, True, False), (4096, 1024, 32, 2, True, False)], seed=5)
     run_batch([(32768, 256, 2, 2, True, False), (32768, 512, 512, 1, True, False)], seed=6)
+
+
+@pytest.mark.parametrize("beta", [1.0, 0.5])
+def test_wgrad_batch_accumulates_with_beta(beta):
+    """out = beta * out + sum, for the matrix, the bias sums and the sigma column, on each kernel behind the entry point: the 256 x 256
+    x9 tiles, the 256 x 32 wide geometry, the generic kernel (M > 1024, ragged) and the per-image one (M <= 1024)."""
+    lib = L.lib()
+    specs = [(4096, 256, 256, 2, True, True), (4096, 256, 32, 1, True, False), (3000, 96, 130, 2, True, True), (600, 80, 70, 1, True, True)]
+    lib.ardae_profile_enable(1)
+    run_batch(specs, seed=7, beta=beta)
+    names = [e["name"] for e in L.profile_report(max_entries=64)]
+    lib.ardae_profile_enable(0)
+    for k in ("wgrad_x9_kernel", "wgrad_wide", "wgrad_kernel", "wgrad_small_kernel"):
+        assert any(n.startswith(k) for n in names), (k, names)
+
+
+def test_wgrad_batch_strided_operands_with_beta():
+    """ldG > O and ldX > I (G and X column blocks of wider matrices, as the models' concatenated-input layers pass them), with beta = 1:
+    the generic and the per-image kernels (a padded leading dimension that keeps 16-byte rows may also take the tiled kernels)."""
+    run_batch([(3000, 96, 130, 2, True, True), (600, 80, 70, 1, True, False), (4096, 256, 256, 1, True, False)], seed=8, beta=1.0, pad=4)
+    run_batch([(3000, 96, 130, 2, True, True), (600, 80, 70, 1, True, False)], seed=9, beta=0.0, pad=3)
 
 
 # ---- wgrad_x9_kernel: fp32 products formed EXACTLY from three bf16 pieces per operand on the BF16 matrix cores (round 4)
