@@ -10,9 +10,11 @@ dynamically-binarised images generated on the device.  One step = the loop body 
 (ivae_ardae.py:707-846): one cDAE update (RMSprop) + one VAE update (Adam), nothing skipped.  With N GPUs the image
 batch is sharded (512/N per rank, strong scaling), gradients all-reduced over RCCL.
 
-Prints ONE JSON line on rank 0 (contract in the task description) including
-  roofline     -- the dominant kernel, timed live with HIP events on the launch stream in a second, instrumented pass
-  cpu_baseline -- the oracle's restatement of the same step timed on this box's host cores (bounded sample)
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run does only what that line's headline needs: set up,
+warm up, time the steps, write --dump-outputs, print.  With --full it also measures
+  roofline     -- the dominant kernel, timed live with HIP events on the launch stream in a second, instrumented pass (--prof-steps)
+  cpu_baseline -- the oracle's restatement of the same step timed on the host's cores (bounded sample; N = 1 only, --no-cpu-baseline skips it)
+  collectives  -- with N GPUs, the latency of the step's two gradient all-reduces, timed on their own after the steps
 """
 import argparse
 import json
@@ -206,8 +208,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--prof-steps", type=int, default=5, help="instrumented steps for the live roofline numbers")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the live roofline, the CPU baseline and the "
+                         "collectives' latencies (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--prof-steps", type=int, default=5, help="with --full: instrumented steps for the live roofline numbers")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (parameters, optimiser state, losses) as DIR/<name>.npy "
                          "(rank 0)")
@@ -327,20 +332,22 @@ def main():
         t = mine.clone()
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
-        from ardae_amd import dist as D
-        reduce_ = eng.comm.allreduce_mean_ if eng.comm is not None else D.allreduce_mean_      # the call the step itself makes
-        lat = {}
-        for name, buf in (("cdae_grads", eng.grads_c[:eng.n_c]), ("model_grads", eng.grads_m)):
-            scratch = buf.clone()
-            for _ in range(3):
-                reduce_(scratch)
-            torch.cuda.synchronize(); torch.distributed.barrier()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(20):
-                reduce_(scratch)
-            e1.record(); torch.cuda.synchronize()
-            lat[name] = {"bytes": scratch.numel() * 4, "us_per_allreduce_mean": 1e3 * e0.elapsed_time(e1) / 20}
+        lat = None
+        if args.full:
+            from ardae_amd import dist as D
+            reduce_ = eng.comm.allreduce_mean_ if eng.comm is not None else D.allreduce_mean_      # the call the step itself makes
+            lat = {}
+            for name, buf in (("cdae_grads", eng.grads_c[:eng.n_c]), ("model_grads", eng.grads_m)):
+                scratch = buf.clone()
+                for _ in range(3):
+                    reduce_(scratch)
+                torch.cuda.synchronize(); torch.distributed.barrier()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    reduce_(scratch)
+                e1.record(); torch.cuda.synchronize()
+                lat[name] = {"bytes": scratch.numel() * 4, "us_per_allreduce_mean": 1e3 * e0.elapsed_time(e1) / 20}
         seen = eng.comm.query() if eng.comm is not None else None
         rank_report = {"ms_per_step_by_rank": [1e3 * float(x) / args.steps for x in every], "collectives": lat,
                        "plan": eng.plan_summary(),
@@ -353,10 +360,10 @@ def main():
     # the last timed step's outputs: taken before the instrumented steps below, which go on training
     dumped = dump_outputs(args.dump_outputs, eng) if args.dump_outputs and rank == 0 else None
 
-    # ---- live per-kernel timing (HIP events on the launch stream), separate from the throughput region
+    # ---- --full: live per-kernel timing (HIP events on the launch stream), separate from the throughput region
     roofline = None
     rep = None
-    if args.prof_steps > 0:
+    if args.full and args.prof_steps > 0:
         # every rank runs the instrumented steps (they contain the gradient all-reduces); rank 0 reports its own kernels
         graph_was = eng.use_graph
         eng.use_graph = False                 # the per-kernel HIP events need individual launches
@@ -377,7 +384,7 @@ def main():
         executed = roofline["executed_tflop_per_step"] * 1e12 * world if roofline else None      # rank 0's kernels x ranks (equal shards)
         out = {
             "metric": f"AR-DAE-VAE train-steps/sec (batch {GLOBAL_B}, nz_cdae {NZ}) on dbMNIST", "value": steps_per_s, "unit": "train-steps/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("BASELINE config #2" if GLOBAL_B == 512 else f"EXPERIMENT (BENCH_GLOBAL_B={GLOBAL_B}): BASELINE config #2's networks") +
                                    f": MNISTIPVAE mlp z=32 h=256 + cDAE mlp-grad h=256 L=3, global batch {GLOBAL_B}, "
@@ -401,7 +408,7 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (contract)
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (contract)
             out["cpu_baseline"] = cpu_baseline()
             out["speedup_vs_cpu_baseline"] = steps_per_s / out["cpu_baseline"]["value"]
         print(json.dumps(out))

@@ -6,9 +6,9 @@ R="${GRAFT_REPO_ROOT:?}"
 O="$R/gpurun_out/r03_art"
 rm -rf "$O"; mkdir -p "$O"
 cd "$R"
-python bench.py --steps 100 --warmup 20 > "$O/bench_default.json" 2> "$O/bench_default.err"
+python bench.py --full --steps 100 --warmup 20 > "$O/bench_default.json" 2> "$O/bench_default.err"
 for gb in 256 128 64; do
-  BENCH_GLOBAL_B=$gb python bench.py --steps 200 --warmup 20 --no-cpu-baseline > "$O/bench_b$gb.json" 2> "$O/bench_b$gb.err"
+  BENCH_GLOBAL_B=$gb python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > "$O/bench_b$gb.json" 2> "$O/bench_b$gb.err"
 done
 cd /tmp && export TMPDIR=/tmp
 BENCH_GLOBAL_B=64 rocprofv3 --kernel-trace --output-format csv -d "$O/tr_b64" -- python3 "$R/bench.py" --steps 60 --warmup 10 --prof-steps 0 --no-cpu-baseline > "$O/tr_b64.json" 2> "$O/tr_b64.err"

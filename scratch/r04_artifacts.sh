@@ -4,11 +4,11 @@ set -u
 R="${GRAFT_REPO_ROOT:?}"
 cd "$R"
 O="$R/gpurun_out/r04_art"; rm -rf "$O"; mkdir -p "$O"
-python bench.py --steps 100 --warmup 20 > "$O/bench_default.json" 2> "$O/bench_default.err"
+python bench.py --full --steps 100 --warmup 20 > "$O/bench_default.json" 2> "$O/bench_default.err"
 echo "bench default done"
 export ARDAE_DEBUG_KNOBS=1
 for gb in 256 128 64; do
-  BENCH_GLOBAL_B=$gb python bench.py --steps 200 --warmup 20 --no-cpu-baseline > "$O/bench_b$gb.json" 2> "$O/bench_b$gb.err"
+  BENCH_GLOBAL_B=$gb python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > "$O/bench_b$gb.json" 2> "$O/bench_b$gb.err"
 done
 echo "shards done"
 python scratch/bench_configs.py 1 2 4 5 6 7 8 9 10 > "$R/gpurun_out/r04_configs.txt" 2> "$O/configs.err"

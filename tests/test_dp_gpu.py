@@ -227,7 +227,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     env.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)          # bench.py must provide it itself - before anything touches the GPU
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240, cwd=root)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -265,7 +265,7 @@ def test_bench_one_rank_rccl_end_to_end(tmp_path):
     env.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240, cwd=root)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
