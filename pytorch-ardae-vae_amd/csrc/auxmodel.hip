@@ -20,8 +20,7 @@
 
 #include "auxmodel.h"
 #include "elementwise.h"
-#include "linear.h"
-#include "wgrad.h"
+#include "host_util.h"
 
 namespace ardae {
 namespace {
@@ -90,17 +89,6 @@ struct AuxPacked {
   }
 };
 
-struct Bump {
-  float* base; size_t cap; size_t off = 0; bool ok = true;
-  Bump(float* b, size_t c) : base(b), cap(c) {}
-  float* take(size_t n) {
-    size_t o = off; off += (n + 63) & ~size_t(63);
-    if (off > cap) { ok = false; return base; }
-    return base + o;
-  }
-};
-size_t al64(size_t n) { return (n + 63) & ~size_t(63); }
-
 struct AuxWs {
   float *xs, *mu0, *lv0, *rb, *z0, *mu, *lv, *z, *zero;
   float *lv0r, *lvr;                    // the heads' raw outputs when a log-variance clip is on (lv0 / lv then hold the clipped values)
@@ -113,30 +101,6 @@ struct AuxWs {
 };
 
 int wgrad_nprob(const AuxLayout& P) { return 1 + (P.toy ? 1 : 0) + P.nl + 2 + P.nl + 1 + 2 + P.nl; }
-
-// R: stage rows (B nz, toy: B q); N: z / decoder rows (= R, toy: R q)
-size_t wgrad_scratch(const AuxLayout& P, int B, int R, int N, std::vector<int>* splits_out) {
-  // problem order must match aux_model_vae_backward
-  std::vector<int> sp;
-  size_t tot = 0;
-  const int nprob = wgrad_nprob(P);
-  auto one = [&](int M, int O, int I) {
-    const int s = wgrad_splits(M, O, I, nprob);
-    sp.push_back(s);
-    tot += al64((size_t)s * O * I) + al64((size_t)s * 2 * O);
-  };
-  one(N, P.D, P.h);                                                  // logit head (toy: mean head)
-  if (P.toy) one(N, P.D, P.h);                                       // toy: logvar head
-  for (int l = 0; l < P.nl; ++l) one(N, P.h, l == 0 ? P.zd : P.h);   // decoder
-  one(R, P.zd, P.h); one(R, P.zd, P.h);                              // mean, logvar
-  for (int l = P.nl - 1; l >= 1; --l) one(R, P.h, P.h);              // encoder layers 2..n
-  one(R, P.h, P.nd);                                                 // first encoder layer, z0 half (+ bias)
-  one(B, P.h, P.D);                                                  // first encoder layer, image half
-  one(B, P.nd, P.h); one(B, P.nd, P.h);                              // mean0, logvar0
-  for (int l = 0; l < P.nl; ++l) one(B, P.h, l == 0 ? P.D : P.h);    // aux main
-  if (splits_out) *splits_out = sp;
-  return tot;
-}
 
 // mode 0: sampler only; 1: + decoder, losses, backward, weight gradients
 void carve(const AuxLayout& P, Bump& ws, int B, int nz, int mode, AuxWs& W) {
@@ -165,14 +129,38 @@ void carve(const AuxLayout& P, Bump& ws, int B, int nz, int mode, AuxWs& W) {
   for (int l = 1; l <= P.nl; ++l) { W.ddec[l] = ws.take(N * h); W.dt[l] = ws.take(R * h); W.de[l] = ws.take((size_t)B * h); }
 }
 
+// every weight-gradient problem of aux_model_vae_backward, with its scratch taken from ws
+// (rows: B images, R = B stage(nz) stage rows, N = B nz z / decoder rows; toy: the heads' gradients are the sums over a stage row's q z's)
+void aux_wgrads(const AuxLayout& P, const AuxWs& W, int B, int nz, WgradList& wl, Bump& ws) {
+  const int R = B * P.stage(nz), N = B * nz, h = P.h, nl = P.nl;
+  const float* dmu = P.toy ? W.dmu_s : W.dz;
+  const float* dlv = P.toy ? W.dlv_s : W.dlv;
+  wl.push(N, P.D, h, W.dox, W.dcd[nl], h, wl.g(P.logit.w), h, wl.g(P.logit.b));                       // logit head (toy: mean head)
+  if (P.toy) wl.push(N, P.D, h, W.dox2, W.dcd[nl], h, wl.g(P.logvarx.w), h, wl.g(P.logvarx.b));      // toy: logvar head
+  for (int l = 1; l <= nl; ++l)                                                                      // decoder
+    wl.push(N, h, P.dec[l - 1].in, W.ddec[l], l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, wl.g(P.dec[l - 1].w), P.dec[l - 1].in, wl.g(P.dec[l - 1].b));
+  wl.push(R, P.zd, h, dmu, W.t[nl], h, wl.g(P.mean.w), h, wl.g(P.mean.b));
+  wl.push(R, P.zd, h, dlv, W.t[nl], h, wl.g(P.logvar.w), h, wl.g(P.logvar.b));
+  for (int l = nl; l >= 2; --l) wl.push(R, h, h, W.dt[l], W.t[l - 1], h, wl.g(P.ef[l - 1].w), h, wl.g(P.ef[l - 1].b));   // encoder layers n..2
+  wl.push(R, h, P.nd, W.dt[1], W.z0, P.nd, wl.g(P.ef[0].w + P.D), P.ef[0].in, wl.g(P.ef[0].b));        // first encoder layer, z0 half (+ bias)
+  wl.push(B, h, P.D, W.drb, W.xs, P.D, wl.g(P.ef[0].w), P.ef[0].in, nullptr);                         // first encoder layer, image half
+  wl.push(B, P.nd, h, W.dmu0, W.e[nl], h, wl.g(P.mean0.w), h, wl.g(P.mean0.b));
+  wl.push(B, P.nd, h, W.dlv0, W.e[nl], h, wl.g(P.logvar0.w), h, wl.g(P.logvar0.b));
+  for (int l = 1; l <= nl; ++l)                                                                      // aux main
+    wl.push(B, h, P.am[l - 1].in, W.de[l], l == 1 ? W.xs : W.e[l - 1], l == 1 ? P.D : h, wl.g(P.am[l - 1].w), P.am[l - 1].in, wl.g(P.am[l - 1].b));
+  wl.assign(ws, wgrad_nprob(P));
+}
+
 size_t workspace_floats(const AuxLayout& P, int B, int nz, int mode) {
-  // dry run of carve() on a null arena
-  Bump ws(nullptr, ~size_t(0));
+  // dry run of carve() and the weight-gradient list on a null arena
+  Bump ws;
   AuxWs W;
   carve(P, ws, B, nz, mode == 0 ? 0 : 1, W);
-  size_t t = ws.off;
-  if (mode != 0) t += wgrad_scratch(P, B, B * P.stage(nz), B * nz, nullptr);
-  return t;
+  if (mode != 0) {
+    WgradList wl(nullptr);
+    aux_wgrads(P, W, B, nz, wl, ws);
+  }
+  return ws.off;
 }
 
 // out[r][c] = mu[g][c] + exp(lv[g][c] / 2) * eps[r][c],  g = r / rows_per_group  (models/ivae/auxmnist.py:33-41)
@@ -250,12 +238,6 @@ int launch_reparam_bwd(const float* dz, const float* z, const float* mu, int64_t
 }
 
 namespace {
-int lin1(int epi, int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a, hipStream_t st) {
-  a.M = M; a.Nout = Nout; a.nsrc = 1; a.act = act;
-  a.src[0].x = x; a.src[0].ld = ldx; a.src[0].K = K; a.src[0].wp = wp;
-  return launch_linear(a, epi, st);
-}
-
 // the sampler on R = B nz rows; noise [R, nd + zd] (never null here); fills every forward field of W
 // (toy: R = B q stage rows, z on B q q rows; noise = [eps0: R x nd | eps: R q x zd])
 int sampler_fwd(const AuxLayout& P, const AuxPacked& K, const float* params, const float* packed, const float* x, const float* noise, int B,
@@ -484,37 +466,11 @@ int aux_model_vae_backward(const ardae_model_desc& d, const float* params, const
     LinArgs A{}; A.S = W.e[l - 1]; A.ldS = h; A.Y = W.de[l - 1]; A.ldY = h;
     ARDAE_TRY(lin1(EPI_DACT, act, B, h, W.de[l], h, h, packed + K.am_b[l - 1], A, st));
   }
-  // weight gradients: one batched launch (order == wgrad_scratch)
-  std::vector<int> splits;
-  wgrad_scratch(P, B, R, N, &splits);
-  std::vector<WgradProblem> probs;
-  auto push = [&](int M, int O, int I, const float* G, const float* X, int ldX, float* out, int ldout, float* out_bias) {
-    WgradProblem p;
-    memset(&p, 0, sizeof(p));
-    p.M = M; p.O = O; p.I = I; p.npairs = 1;
-    p.G[0] = G; p.ldG[0] = O; p.X[0] = X; p.ldX[0] = ldX;
-    p.bias_pair = out_bias ? 0 : -1;
-    p.splits = splits[probs.size()];
-    p.partial = ws.take((size_t)p.splits * O * I);
-    p.partial_vec = ws.take((size_t)p.splits * 2 * O);
-    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.beta = grads_beta;
-    probs.push_back(p);
-  };
-  push(N, P.D, h, W.dox, W.dcd[nl], h, grads + P.logit.w, h, grads + P.logit.b);
-  if (P.toy) push(N, P.D, h, W.dox2, W.dcd[nl], h, grads + P.logvarx.w, h, grads + P.logvarx.b);
-  for (int l = 1; l <= nl; ++l)
-    push(N, h, P.dec[l - 1].in, W.ddec[l], l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, grads + P.dec[l - 1].w, P.dec[l - 1].in, grads + P.dec[l - 1].b);
-  push(R, P.zd, h, dmu, W.t[nl], h, grads + P.mean.w, h, grads + P.mean.b);
-  push(R, P.zd, h, dlv, W.t[nl], h, grads + P.logvar.w, h, grads + P.logvar.b);
-  for (int l = nl; l >= 2; --l) push(R, h, h, W.dt[l], W.t[l - 1], h, grads + P.ef[l - 1].w, h, grads + P.ef[l - 1].b);
-  push(R, h, P.nd, W.dt[1], W.z0, P.nd, grads + P.ef[0].w + P.D, P.ef[0].in, grads + P.ef[0].b);
-  push(B, h, P.D, W.drb, W.xs, P.D, grads + P.ef[0].w, P.ef[0].in, nullptr);
-  push(B, P.nd, h, W.dmu0, W.e[nl], h, grads + P.mean0.w, h, grads + P.mean0.b);
-  push(B, P.nd, h, W.dlv0, W.e[nl], h, grads + P.logvar0.w, h, grads + P.logvar0.b);
-  for (int l = 1; l <= nl; ++l)
-    push(B, h, P.am[l - 1].in, W.de[l], l == 1 ? W.xs : W.e[l - 1], l == 1 ? P.D : h, grads + P.am[l - 1].w, P.am[l - 1].in, grads + P.am[l - 1].b);
+  // weight gradients: one batched launch
+  WgradList wl(grads, grads_beta);
+  aux_wgrads(P, W, B, nz, wl, ws);
   ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_backward: workspace too small");
-  return launch_wgrad_batch(probs.data(), (int)probs.size(), st);
+  return wl.launch(st);
 }
 
 }  // namespace ardae

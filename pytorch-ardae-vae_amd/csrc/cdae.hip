@@ -16,14 +16,13 @@
 //                qhat_L = qbar_L; qhat_{l-1} = qbar_{l-1} + (qhat_l W_l) (.) s(h_{l-1});
 //                phat_L = pbar_L + (qhat_1 W1a) (.) s(a_L); phat_{l-1} = pbar_{l-1} + (phat_l A_l) (.) s(a_{l-1})
 //                ctx branch: Qsum_b = sum_{i in b} qhat_1[i]  (reduce over S BEFORE the ctx chain), chat_L = (Qsum W1c) (.) s(c_L) ...
-//   weight gradients (one batched launch): see the problem list in cdae_loss_grads_impl().
+//   weight gradients (one batched launch): see cdae_wgrads().
 #include <vector>
 
 #include "ardae_hip.h"
 #include "common.h"
 #include "elementwise.h"
-#include "linear.h"
-#include "wgrad.h"
+#include "host_util.h"
 
 namespace ardae {
 namespace {
@@ -89,16 +88,6 @@ struct PackedLayout {
   }
 };
 
-struct Bump {
-  float* base; size_t cap; size_t off = 0; bool ok = true;
-  Bump(float* b, size_t c) : base(b), cap(c) {}
-  float* take(size_t n) {
-    size_t o = off; off += (n + 63) & ~size_t(63);
-    if (off > cap) { ok = false; return base; }
-    return base + o;
-  }
-};
-
 int desc_ok(const ardae_cdae_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "cdae: desc is NULL");
   ARDAE_CHECK_ARG(d->kind == 0 || d->kind == 1, "cdae: kind must be 0 (mlp-grad) or 1 (mlp-res)");
@@ -110,43 +99,76 @@ int desc_ok(const ardae_cdae_desc* d) {
   return 0;
 }
 
-size_t wgrad_scratch(const CdaeLayout& P, int B, int S, std::vector<int>* splits_out) {
-  // problem order must match cdae_loss_grads_impl
-  const int N = B * S;
-  const int nprob = 3 * P.L + 1;
-  size_t tot = 0;
-  std::vector<int> sp;
-  auto one = [&](int M, int O, int I) {
-    const int s = wgrad_splits(M, O, I, nprob);
-    sp.push_back(s);
-    tot += (((size_t)s * O * I) + 63) & ~size_t(63);
-    tot += (((size_t)s * 2 * O) + 63) & ~size_t(63);
-  };
-  for (int l = 0; l < P.L; ++l) one(N, P.h, P.inp[l].in);         // inp A_l
-  one(N, P.h, P.h);                                               // W1a (+ d_1, w1s)
-  one(B, P.h, P.h);                                               // W1c
-  for (int l = 1; l < P.L; ++l) one(N, P.h, P.h);                 // W_l
-  if (P.kind == 1) one(N, P.z, P.h);                              // dae.fc
-  for (int l = 0; l < P.L; ++l) one(B, P.h, P.ctx[l].in);         // ctx C_l
-  if (splits_out) *splits_out = sp;
-  return tot;
+// the workspace of cdae_impl: forward / score-pass buffers, then (need_grads) the double backward's
+struct CdaeWs {
+  std::vector<float*> cL, a, hh, e, r, tau, taup, pbar, qbar, chat;   // [l], l = 1..L; cL / chat: [B, h], the rest [N, h]
+  float *cb, *gbar, *gbuf, *tile_loss, *chain_cnt, *Qsum, *cs_taup;
+  int ltiles, ctiles;
+};
+
+void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, CdaeWs& W) {
+  const int N = B * S, h = P.h, L = P.L, z = P.z;
+  const size_t Bh = (size_t)B * h, Nh = (size_t)N * h;
+  for (auto* v : {&W.cL, &W.a, &W.hh, &W.e, &W.r, &W.tau, &W.taup, &W.pbar, &W.qbar, &W.chat}) v->assign(L + 1, nullptr);
+  for (int l = 1; l <= L; ++l) W.cL[l] = ws.take(Bh);
+  W.cb = ws.take(Bh);
+  for (int l = 1; l <= L; ++l) { W.a[l] = ws.take(Nh); W.hh[l] = ws.take(Nh); W.e[l] = ws.take(Nh); W.r[l] = ws.take(Nh); }
+  if (need_grads)
+    for (int l = 1; l <= L; ++l) { W.tau[l] = ws.take(Nh); W.taup[l] = ws.take(Nh); W.pbar[l] = ws.take(Nh); W.qbar[l] = ws.take(Nh); }
+  W.gbar = ws.take((size_t)N * z);
+  W.gbuf = ws.take((size_t)N * z);
+  W.ltiles = linear_row_tiles(N, z) * linear_col_panels(N, z);
+  W.tile_loss = ws.take(W.ltiles);
+  W.chain_cnt = ws.take((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));   // row-block counters of the per-image chain launch (score pass)
+  W.Qsum = W.cs_taup = nullptr;
+  W.ctiles = linear_row_tiles(N, h);
+  if (!need_grads) return;
+  W.Qsum = ws.take(Bh);
+  for (int l = 1; l <= L; ++l) W.chat[l] = ws.take(Bh);
+  W.cs_taup = ws.take((size_t)W.ctiles * h);                                            // colsum of tau'_L
 }
 
-size_t workspace_floats(const CdaeLayout& P, int B, int S, bool need_grads) {
-  const size_t N = (size_t)B * S, h = P.h;
-  auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  size_t t = 0;
-  t += (size_t)(P.L) * al((size_t)B * h) + al((size_t)B * h);            // c_l, cb
-  t += (size_t)(need_grads ? 8 : 4) * P.L * al(N * h);                   // a,hh,e,r (+ tau,taup,pbar,qbar)
-  t += 2 * al(N * P.z);                                                  // gbar, g
-  t += al((size_t)linear_row_tiles((int)N, P.z) * linear_col_panels((int)N, P.z));
-  t += al((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));                                          // row-block counters of the per-image chain launch (score pass)
-  if (need_grads) {
-    t += al((size_t)B * h) + (size_t)P.L * al((size_t)B * h);            // Qsum, chat_l
-    t += al((size_t)linear_row_tiles((int)N, P.h) * h);                  // colsum of tau'_L
-    t += wgrad_scratch(P, B, S, nullptr);
+// every weight-gradient problem of the update (one batched launch), with its scratch taken from ws
+// (qhat_l / phat_l live in qbar_l / pbar_l: the backward overwrites them in place)
+void cdae_wgrads(const CdaeLayout& P, const CdaeWs& W, const float* xbar, const float* sigma, const float* ctx, int B, int S, WgradList& wl, Bump& ws) {
+  const int N = B * S, h = P.h, L = P.L, z = P.z;
+  const std::vector<float*>&a = W.a, &hh = W.hh, &e = W.e, &r = W.r, &tau = W.tau, &taup = W.taup, &qhat = W.qbar, &phat = W.pbar;
+  const int ld1 = 2 * h + 1;
+  const size_t gW1 = P.neg[0].w;
+  if (P.kind == 0) {
+    for (int l = 1; l <= L; ++l)   // inp A_l: r_l (x) tau_{l-1}  +  phat_l (x) a_{l-1}   (tau_0 = gbar, a_0 = xbar)
+      wl.push2(N, h, P.inp[l - 1].in, r[l], l == 1 ? W.gbar : tau[l - 1], l == 1 ? z : h, phat[l], l == 1 ? xbar : a[l - 1], l == 1 ? z : h, 1,
+               nullptr, wl.g(P.inp[l - 1].w), P.inp[l - 1].in, wl.g(P.inp[l - 1].b), nullptr, 0);
+    wl.push2(N, h, h, e[1], tau[L], h, qhat[1], a[L], h, 1, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + 2 * h), ld1);        // W1a, d_1, w1s
+    wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + h), ld1, nullptr, nullptr, 0);                 // W1c
+    for (int l = 2; l <= L; ++l)   // W_l: e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}
+      wl.push2(N, h, h, e[l], taup[l - 1], h, qhat[l], hh[l - 1], h, 1, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
+  } else {
+    for (int l = 1; l <= L; ++l)
+      wl.push2(N, h, P.inp[l - 1].in, phat[l], l == 1 ? xbar : a[l - 1], l == 1 ? z : h, nullptr, nullptr, 0, 0, nullptr,
+               wl.g(P.inp[l - 1].w), P.inp[l - 1].in, wl.g(P.inp[l - 1].b), nullptr, 0);
+    wl.push2(N, h, h, qhat[1], a[L], h, nullptr, nullptr, 0, 0, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + 2 * h), ld1);
+    wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + h), ld1, nullptr, nullptr, 0);
+    for (int l = 2; l <= L; ++l)
+      wl.push2(N, h, h, qhat[l], hh[l - 1], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
+    wl.push2(N, z, h, W.gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[L].w), h, wl.g(P.neg[L].b), nullptr, 0);   // dae.fc
   }
-  return t;
+  for (int l = 1; l <= L; ++l)     // ctx C_l: chat_l (x) c_{l-1}
+    wl.push2(B, h, P.ctx[l - 1].in, W.chat[l], l == 1 ? ctx : W.cL[l - 1], l == 1 ? P.c : h, nullptr, nullptr, 0, 0, nullptr,
+             wl.g(P.ctx[l - 1].w), P.ctx[l - 1].in, wl.g(P.ctx[l - 1].b), nullptr, 0);
+  wl.assign(ws, 3 * L + 1);
+}
+
+// dry run of cdae_carve() and the weight-gradient list on a null arena
+size_t workspace_floats(const CdaeLayout& P, int B, int S, bool need_grads) {
+  Bump ws;
+  CdaeWs W;
+  cdae_carve(P, ws, B, S, need_grads, W);
+  if (need_grads) {
+    WgradList wl(nullptr);
+    cdae_wgrads(P, W, nullptr, nullptr, nullptr, B, S, wl, ws);
+  }
+  return ws.off;
 }
 
 int cdae_pack_impl(const CdaeLayout& P, const PackedLayout& K, const float* params, float* packed, hipStream_t st) {
@@ -220,13 +242,6 @@ struct LayerRun {
   }
 };
 
-// where cdae_impl's workspace layout puts a_1 [N, h] (behind c_1..c_L and the per-image bias block, [B, h] each)
-float* cdae_a1_slot(const CdaeLayout& P, int B, float* workspace) {
-  Bump ws(workspace, ~size_t(0));
-  for (int l = 0; l <= P.L; ++l) ws.take((size_t)B * P.h);
-  return ws.take(1);
-}
-
 int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma,
               const float* eps, const float* ctx, int B, int S, float* workspace, size_t ws_floats, float* loss, float* grads,
               float* score_out, bool need_grads, hipStream_t st, bool a1_ready = false) {
@@ -238,21 +253,16 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   const CdaeLayout P(*d);
   const PackedLayout K(P);
   const int N = B * S, h = P.h, L = P.L, z = P.z, act = P.act;
-  ARDAE_CHECK_ARG(ws_floats >= workspace_floats(P, B, S, need_grads), "cdae: workspace too small (%zu < %zu floats)", ws_floats,
-                  workspace_floats(P, B, S, need_grads));
+  // the whole arena up front: the buffers, then (need_grads) the weight-gradient list with its scratch
   Bump ws(workspace, ws_floats);
-  const size_t Bh = (size_t)B * h, Nh = (size_t)N * h;
-  std::vector<float*> cL(L + 1), a(L + 1), hh(L + 1), e(L + 1), r(L + 1), tau(L + 1), taup(L + 1), pbar(L + 1), qbar(L + 1), chat(L + 1);
-  for (int l = 1; l <= L; ++l) cL[l] = ws.take(Bh);
-  float* cb = ws.take(Bh);
-  for (int l = 1; l <= L; ++l) { a[l] = ws.take(Nh); hh[l] = ws.take(Nh); e[l] = ws.take(Nh); r[l] = ws.take(Nh); }
-  if (need_grads)
-    for (int l = 1; l <= L; ++l) { tau[l] = ws.take(Nh); taup[l] = ws.take(Nh); pbar[l] = ws.take(Nh); qbar[l] = ws.take(Nh); }
-  float* gbar = ws.take((size_t)N * z);
-  float* gbuf = ws.take((size_t)N * z);
-  const int ltiles = linear_row_tiles(N, z) * linear_col_panels(N, z);
-  float* tile_loss = ws.take(ltiles);
-  float* chain_cnt = ws.take((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));
+  CdaeWs W;
+  cdae_carve(P, ws, B, S, need_grads, W);
+  WgradList wl(grads);
+  if (need_grads) cdae_wgrads(P, W, xbar, sigma, ctx, B, S, wl, ws);
+  ARDAE_CHECK_ARG(ws.ok, "cdae: workspace too small (%zu < %zu floats)", ws_floats, ws.off);
+  const std::vector<float*>&cL = W.cL, &a = W.a, &hh = W.hh, &e = W.e, &r = W.r, &tau = W.tau, &taup = W.taup, &pbar = W.pbar, &qbar = W.qbar, &chat = W.chat;
+  float *cb = W.cb, *gbar = W.gbar, *gbuf = W.gbuf, *tile_loss = W.tile_loss, *chain_cnt = W.chain_cnt, *Qsum = W.Qsum, *cs_taup = W.cs_taup;
+  const int ltiles = W.ltiles, ctiles = W.ctiles;
   float* g = score_out ? score_out : gbuf;
 
   const float* W1s = packed + K.w1s;
@@ -283,7 +293,6 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     { LinArgs A{}; A.Y = g; A.ldY = z; add(lin_args(ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A), EPI_ACT, level++); }
     return launch_linear_small_chain(pr.data(), ep.data(), lv.data(), (int)pr.size(), chain_cnt, st);
   }
-  ARDAE_CHECK_ARG(!a1_ready || a[1] == cdae_a1_slot(P, B, workspace), "cdae: a_1 slot moved (workspace layout and cdae_a1_slot disagree)");
   const bool few_rows = !a1_ready && linear_small_eligible(inp_layer(1), EPI_ACT);
   auto ctx_bias = [&]() {  // per-image bias of the first energy layer: cb = W1c c_L + d_1
     LinArgs A{}; A.bias = params + P.neg[0].b; A.Y = cb; A.ldY = h;
@@ -353,11 +362,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   ARDAE_TRY(launch_sum_scale(tile_loss, ltiles, inv_nz, loss, st));
 
   // -------------------------------------------------------------------- backward
-  float* Qsum = ws.take(Bh);
-  for (int l = 1; l <= L; ++l) chat[l] = ws.take(Bh);
-  const int ctiles = linear_row_tiles(N, h);
-  float* cs_taup = ws.take((size_t)ctiles * h);
-  std::vector<float*>&qhat = qbar, &phat = pbar;   // in-place: qhat_l overwrites qbar_l, phat_l overwrites pbar_l
+  const std::vector<float*>&qhat = qbar, &phat = pbar;   // in-place: qhat_l overwrites qbar_l, phat_l overwrites pbar_l
   if (P.kind == 0) {
     // forward-mode chain through the score pass
     {
@@ -423,50 +428,8 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     ARDAE_TRY(lin(EPI_DACT, act, B, h, chat[l], h, h, packed + K.ctx_b[l - 1], A, st));
   }
 
-  // -------------------------------------------------------------------- weight gradients: one batched launch
-  std::vector<int> splits;
-  wgrad_scratch(P, B, S, &splits);
-  std::vector<WgradProblem> probs;
-  auto push = [&](int M, int O, int I, const float* G0, const float* X0, int ldX0, const float* G1, const float* X1, int ldX1,
-                  int bias_pair, const float* rowscale, float* out, int ldout, float* out_bias, float* out_rs, int ld_rs) {
-    WgradProblem p;
-    memset(&p, 0, sizeof(p));
-    p.M = M; p.O = O; p.I = I;
-    p.npairs = G1 ? 2 : 1;
-    p.G[0] = G0; p.ldG[0] = O; p.X[0] = X0; p.ldX[0] = ldX0;
-    p.G[1] = G1; p.ldG[1] = O; p.X[1] = X1; p.ldX[1] = ldX1;
-    p.bias_pair = bias_pair; p.rowscale = rowscale;
-    p.splits = splits[probs.size()];
-    p.partial = ws.take((size_t)p.splits * O * I);
-    p.partial_vec = ws.take((size_t)p.splits * 2 * O);
-    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.out_rowscale = out_rs; p.ld_rowscale = ld_rs; p.beta = 0.f;
-    probs.push_back(p);
-  };
-  const int ld1 = 2 * h + 1;
-  float* gW1 = grads + P.neg[0].w;
-  if (P.kind == 0) {
-    for (int l = 1; l <= L; ++l)   // inp A_l: r_l (x) tau_{l-1}  +  phat_l (x) a_{l-1}   (tau_0 = gbar, a_0 = xbar)
-      push(N, h, P.inp[l - 1].in, r[l], l == 1 ? gbar : tau[l - 1], l == 1 ? z : h, phat[l], l == 1 ? xbar : a[l - 1], l == 1 ? z : h, 1,
-           nullptr, grads + P.inp[l - 1].w, P.inp[l - 1].in, grads + P.inp[l - 1].b, nullptr, 0);
-    push(N, h, h, e[1], tau[L], h, qhat[1], a[L], h, 1, sigma, gW1, ld1, grads + P.neg[0].b, gW1 + 2 * h, ld1);        // W1a, d_1, w1s
-    push(B, h, h, Qsum, cL[L], h, nullptr, nullptr, 0, -1, nullptr, gW1 + h, ld1, nullptr, nullptr, 0);                 // W1c
-    for (int l = 2; l <= L; ++l)   // W_l: e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}
-      push(N, h, h, e[l], taup[l - 1], h, qhat[l], hh[l - 1], h, 1, nullptr, grads + P.neg[l - 1].w, h, grads + P.neg[l - 1].b, nullptr, 0);
-  } else {
-    for (int l = 1; l <= L; ++l)
-      push(N, h, P.inp[l - 1].in, phat[l], l == 1 ? xbar : a[l - 1], l == 1 ? z : h, nullptr, nullptr, 0, 0, nullptr,
-           grads + P.inp[l - 1].w, P.inp[l - 1].in, grads + P.inp[l - 1].b, nullptr, 0);
-    push(N, h, h, qhat[1], a[L], h, nullptr, nullptr, 0, 0, sigma, gW1, ld1, grads + P.neg[0].b, gW1 + 2 * h, ld1);
-    push(B, h, h, Qsum, cL[L], h, nullptr, nullptr, 0, -1, nullptr, gW1 + h, ld1, nullptr, nullptr, 0);
-    for (int l = 2; l <= L; ++l)
-      push(N, h, h, qhat[l], hh[l - 1], h, nullptr, nullptr, 0, 0, nullptr, grads + P.neg[l - 1].w, h, grads + P.neg[l - 1].b, nullptr, 0);
-    push(N, z, h, gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, grads + P.neg[L].w, h, grads + P.neg[L].b, nullptr, 0);   // dae.fc
-  }
-  for (int l = 1; l <= L; ++l)     // ctx C_l: chat_l (x) c_{l-1}
-    push(B, h, P.ctx[l - 1].in, chat[l], l == 1 ? ctx : cL[l - 1], l == 1 ? P.c : h, nullptr, nullptr, 0, 0, nullptr,
-         grads + P.ctx[l - 1].w, P.ctx[l - 1].in, grads + P.ctx[l - 1].b, nullptr, 0);
-  ARDAE_CHECK_ARG(ws.ok, "cdae: internal workspace accounting error");
-  return launch_wgrad_batch(probs.data(), (int)probs.size(), st);
+  // -------------------------------------------------------------------- weight gradients: one batched launch (cdae_wgrads)
+  return wl.launch(st);
 }
 
 }  // namespace
@@ -515,8 +478,11 @@ int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params,
   const CdaeLayout P(*d);
   const PackedLayout K(P);
   ARDAE_CHECK_ARG(ws_floats >= workspace_floats(P, B, nz, true), "cdae_perturb_loss_grads: workspace too small");
+  Bump ws(workspace, ws_floats);
+  CdaeWs W;
+  cdae_carve(P, ws, B, nz, true, W);   // the kernel below leaves a_1 where cdae_impl reads it
   ARDAE_TRY(launch_latent_perturb_draw_fwd(latent, z0, B, nz, P.z, std_scale, delta, seed, offset_xi, offset_eps, state, first_row, xbar, sigma,
-                                           eps_out, std_b, packed + K.inp_f[0], params + P.inp[0].b, P.h, P.act, cdae_a1_slot(P, B, workspace),
+                                           eps_out, std_b, packed + K.inp_f[0], params + P.inp[0].b, P.h, P.act, W.a[1],
                                            (hipStream_t)stream));
   return cdae_impl(d, params, packed, xbar, sigma, eps_out, ctx, B, nz, workspace, ws_floats, loss, grads, nullptr, true, (hipStream_t)stream,
                    true);

@@ -12,8 +12,7 @@
 #include "auxmodel.h"
 #include "convmodel.h"
 #include "elementwise.h"
-#include "linear.h"
-#include "wgrad.h"
+#include "host_util.h"
 
 namespace ardae {
 namespace {
@@ -73,28 +72,10 @@ __global__ void col2im_s2_kernel(const float* __restrict__ cols, int IH, int IW,
   out[e] = v;
 }
 
-// [B, HW, C] (NHWC rows) <-> [B, C*HW] (PyTorch's .view(B,-1) of NCHW)
-__global__ void nhwc_to_nchw_kernel(const float* __restrict__ in, int HW, int C, float* __restrict__ out, int64_t total, int reverse) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int c = (int)(e % C);
-  const int hw = (int)((e / C) % HW);
-  const int64_t b = e / ((int64_t)C * HW);
-  const int64_t nchw = (b * C + c) * HW + hw;
-  if (reverse) out[e] = in[nchw]; else out[nchw] = in[e];
-}
-
-__global__ void mul_dact_kernel(const float* __restrict__ x, const float* __restrict__ S, int act, float* __restrict__ y, int64_t n) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) y[e] = x[e] * act_d1_rt(act, S[e]);
-}
-
 __global__ void fill_kernel(float* __restrict__ p, float v, int64_t n) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) p[e] = v;
 }
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // ------------------------------------------------------------------------------------------------ layout
 struct Lin { size_t w, b; int out, in; };   // weight viewed as [out, in] (convs: [O, C*25]; deconvs: [in_ch, out_ch*25])
@@ -115,8 +96,6 @@ struct ConvLayout {
   }
 };
 
-size_t al64(size_t n) { return (n + 63) & ~size_t(63); }
-
 struct ConvPacked {
   size_t conv_f[3], conv_b[3], fc4i_f, fc4i_b, fc4n_f, fc5_f, fc5_b, dfc_f[2], dfc_b[2], dcv_f[3], dcv_b[3], total;
   ConvPacked() : total(0) {}
@@ -130,12 +109,6 @@ struct ConvPacked {
     for (int i = 0; i < 3; ++i) { dcv_f[i] = take(packed_floats(P.dcv[i].in, P.dcv[i].out)); dcv_b[i] = take(packed_floats(P.dcv[i].out, P.dcv[i].in)); }
     total = off;
   }
-};
-
-struct Bump {
-  float* base; size_t cap; size_t off = 0; bool ok = true;
-  Bump(float* b, size_t c) : base(b), cap(c) {}
-  float* take(size_t n) { size_t o = off; off += al64(n); if (off > cap) { ok = false; return base; } return base + o; }
 };
 
 // spatial sizes: encoder 28 -> 14 -> 7 -> 4; decoder grids 4 -> 8 (7 valid) -> 15 -> 28 (of 29)
@@ -177,37 +150,6 @@ void carve(const ConvLayout& P, Bump& ws, int B, int nz, int mode, ConvWs& W) {
   W.ones = ws.take(R * 784);
 }
 
-constexpr int N_WGRAD = 18;   // problems of one backward (see conv_vae_backward)
-
-size_t wgrad_scratch(const ConvLayout& P, int B, int R, std::vector<int>* out) {
-  std::vector<int> sp; size_t tot = 0;
-  auto one = [&](int M, int O, int I) { const int s = wgrad_splits(M, O, I, N_WGRAD); sp.push_back(s); tot += al64((size_t)s * O * I) + al64((size_t)s * 2 * O); };
-  one(R * 225, 16, 25); one(R * 784, 1, 1);          // deconv3 weight, bias
-  one(R * 64, 32, 400); one(R * 225, 16, 1);         // deconv2
-  one(R * 16, 32, 800); one(R * 64, 32, 1);          // deconv1
-  one(R, 512, 300); one(R, 300, P.zd);               // decoder fc
-  one(R, P.zd, 800); one(R, 800, P.nd); one(B, 800, 512);   // fc5, fc4 noise half (+bias), fc4 image half
-  one(B * 16, 32, 800); one(B * 49, 32, 400); one(B * 196, 16, 25);   // conv3, conv2, conv1
-  if (out) *out = sp;
-  return tot;
-}
-
-size_t conv_workspace(const ConvLayout& P, int B, int nz, int mode) {
-  // run the carve on a null arena to count
-  Bump b(nullptr, ~size_t(0));
-  ConvWs W;
-  carve(P, b, B, nz, mode, W);
-  size_t t = b.off + al64((size_t)B * nz * P.nd);    // + zero-noise buffer for encode(std=0)
-  if (mode == 1) t += wgrad_scratch(P, B, B * nz, nullptr);
-  return t;
-}
-
-int lin1(int epi, int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a, hipStream_t st) {
-  a.M = M; a.Nout = Nout; a.nsrc = 1; a.act = act;
-  a.src[0].x = x; a.src[0].ld = ldx; a.src[0].K = K; a.src[0].wp = wp;
-  return launch_linear(a, epi, st);
-}
-
 int im2col(const float* x, int Bn, int H, int Wd, int C, int OH, int OW, float* cols, hipStream_t st) {
   const int64_t total = (int64_t)Bn * OH * OW * C * 25;
   hipLaunchKernelGGL(im2col_s2_kernel, dim3(nblk(total)), dim3(256), 0, st, x, H, Wd, C, OH, OW, cols, total);
@@ -221,13 +163,6 @@ int col2im(const float* cols, int Bn, int IH, int IW, int O, int OH, int OW, int
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
-int transpose_hw_c(const float* in, int Bn, int HW, int C, float* out, bool to_nchw, hipStream_t st) {
-  const int64_t total = (int64_t)Bn * HW * C;
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblk(total)), dim3(256), 0, st, in, HW, C, out, total, to_nchw ? 0 : 1);
-  ARDAE_LAUNCH_CHECK();
-  return 0;
-}
-
 // conv trunk 1 -> 16 -> 32 -> 32 (k5 s2 p2, 28 -> 14 -> 7 -> 4) on the rescaled images x2 [B, 784]: fills cols / hcv and the
 // NCHW-flattened output inp [B, 512] (shared by ConvIPVAE and the two trunks of the hierarchical conv model)
 int trunk_fwd(const Lin* conv, const size_t* conv_f, const float* params, const float* packed, const float* x2, float* const* cols,
@@ -240,18 +175,14 @@ int trunk_fwd(const Lin* conv, const size_t* conv_f, const float* params, const 
     ARDAE_TRY(lin1(EPI_ACT, act, B * OH * OH, ECH[i + 1], cols[i], Kc, Kc, packed + conv_f[i], A, st));
     cur = hcv[i];
   }
-  return transpose_hw_c(hcv[2], B, 16, 32, inp, true, st);                      // h3.view(B,-1) of NCHW
+  return launch_nhwc_nchw(hcv[2], B, 16, 32, inp, false, st);                      // h3.view(B,-1) of NCHW
 }
 
 // backward of the trunk from d(inp) [B, 512] (NCHW-flat): dh3 / dh2 / dh1 = d(pre-activation) of conv3 / conv2 / conv1 (NHWC rows)
 int trunk_bwd(const size_t* conv_b, const float* packed, const float* dinp, float* dinp_t, float* const* hcv, float* dh3, float* dcols3,
               float* dh2, float* dcols2, float* dh1, int B, int act, hipStream_t st) {
-  ARDAE_TRY(transpose_hw_c(dinp, B, 16, 32, dinp_t, false, st));               // NCHW-flat -> NHWC rows
-  {
-    const int64_t n = (int64_t)B * 512;
-    hipLaunchKernelGGL(mul_dact_kernel, dim3(nblk(n)), dim3(256), 0, st, dinp_t, hcv[2], act, dh3, n);
-    ARDAE_LAUNCH_CHECK();
-  }
+  ARDAE_TRY(launch_nhwc_nchw(dinp, B, 16, 32, dinp_t, true, st));                // NCHW-flat -> NHWC rows
+  ARDAE_TRY(launch_mul_dact(dinp_t, hcv[2], act, dh3, (int64_t)B * 512, st));
   { LinArgs A{}; A.Y = dcols3; A.ldY = 800;                                     // conv3 backward-data: dcols = dpre . W3
     ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B * 16, 800, dh3, 32, 32, packed + conv_b[2], A, st)); }
   ARDAE_TRY(col2im(dcols3, B, 4, 4, 32, 7, 7, 7, 7, nullptr, act, hcv[1], dh2, st));
@@ -286,7 +217,7 @@ int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* param
   const int act = P.act;
   { LinArgs A{}; A.bias = params + P.dfc[0].b; A.Y = W.d1; A.ldY = 300; ARDAE_TRY(lin1(EPI_ACT, act, R, 300, z, P.zd, P.zd, packed + K.dfc_f[0], A, st)); }
   { LinArgs A{}; A.bias = params + P.dfc[1].b; A.Y = W.d2; A.ldY = 512; ARDAE_TRY(lin1(EPI_ACT, act, R, 512, W.d1, 300, 300, packed + K.dfc_f[1], A, st)); }
-  ARDAE_TRY(transpose_hw_c(W.d2, R, 16, 32, W.g0, false, st));                  // h1.view(R,32,4,4) -> NHWC rows
+  ARDAE_TRY(launch_nhwc_nchw(W.d2, R, 16, 32, W.g0, true, st));                  // h1.view(R,32,4,4) -> NHWC rows
   // deconv1 32->32: 4x4 -> 7x7, activation, zero-pad to 8x8
   { LinArgs A{}; A.Y = W.c1; A.ldY = 800; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R * 16, 800, W.g0, 32, 32, packed + K.dcv_f[0], A, st)); }
   ARDAE_TRY(col2im(W.c1, R, 4, 4, 32, 8, 8, 7, 7, params + P.dcv[0].b, act, nullptr, W.u1, st));
@@ -317,7 +248,7 @@ int conv_decoder_bwd(const ConvLayout& P, const ConvPacked& K, const float* pack
   ARDAE_TRY(im2col(W.dp1, R, 8, 8, 32, 4, 4, W.dc1, st));
   { LinArgs A{}; A.S = W.g0; A.ldS = 32; A.Y = W.dg0; A.ldY = 32;               // g0 is the (permuted) activated output of decode.fc
     ARDAE_TRY(lin1(EPI_DACT, act, R * 16, 32, W.dc1, 800, 800, packed + K.dcv_b[0], A, st)); }
-  ARDAE_TRY(transpose_hw_c(W.dg0, R, 16, 32, W.dd2, true, st));                 // -> d(pre) of decode.fc.fc  [R,512]
+  ARDAE_TRY(launch_nhwc_nchw(W.dg0, R, 16, 32, W.dd2, false, st));               // -> d(pre) of decode.fc.fc  [R,512]
   { LinArgs A{}; A.S = W.d1; A.ldS = 300; A.Y = W.dd1; A.ldY = 300;
     ARDAE_TRY(lin1(EPI_DACT, act, R, 300, W.dd2, 512, 512, packed + K.dfc_b[1], A, st)); }
   { LinArgs A{}; A.S = W.dzq; A.ldS = P.zd; A.Q = W.dzq; A.ldQ = P.zd; A.Y = W.dz; A.ldY = P.zd;   // + prior + injected seed
@@ -325,18 +256,44 @@ int conv_decoder_bwd(const ConvLayout& P, const ConvPacked& K, const float* pack
   return 0;
 }
 
-// the decoder's eight weight-gradient problems (order == wgrad_scratch)
-template <class PUSH>
-void conv_decoder_wgrads(const ConvLayout& P, ConvWs& W, int R, float* grads, PUSH&& push) {
+// wgrad_splits hint of the conv backward: a tuning value, not the problem count (the list below has 14)
+constexpr int CONV_WGRAD_HINT = 18;
+
+// the decoder's eight weight-gradient problems (shared with the hierarchical conv model)
+void conv_decoder_wgrads(const ConvLayout& P, const ConvWs& W, int R, WgradList& wl) {
   // ConvTranspose2d: dW[in][out*25] = sum_rows input[row][in] * dcols[row][out*25]; its bias = sum of the output gradient
-  push(R * 225, 16, 25, W.u2, W.dc3, grads + P.dcv[2].w, 25, nullptr);
-  push(R * 784, 1, 1, W.dlogit, W.ones, grads + P.dcv[2].b, 1, nullptr);
-  push(R * 64, 32, 400, W.u1, W.dc2, grads + P.dcv[1].w, 400, nullptr);
-  push(R * 225, 16, 1, W.dp2, W.ones, grads + P.dcv[1].b, 1, nullptr);
-  push(R * 16, 32, 800, W.g0, W.dc1, grads + P.dcv[0].w, 800, nullptr);
-  push(R * 64, 32, 1, W.dp1, W.ones, grads + P.dcv[0].b, 1, nullptr);
-  push(R, 512, 300, W.dd2, W.d1, grads + P.dfc[1].w, 300, grads + P.dfc[1].b);
-  push(R, 300, P.zd, W.dd1, W.z, grads + P.dfc[0].w, P.zd, grads + P.dfc[0].b);
+  wl.push(R * 225, 16, 25, W.u2, W.dc3, 25, wl.g(P.dcv[2].w), 25, nullptr);
+  wl.push(R * 784, 1, 1, W.dlogit, W.ones, 1, wl.g(P.dcv[2].b), 1, nullptr);
+  wl.push(R * 64, 32, 400, W.u1, W.dc2, 400, wl.g(P.dcv[1].w), 400, nullptr);
+  wl.push(R * 225, 16, 1, W.dp2, W.ones, 1, wl.g(P.dcv[1].b), 1, nullptr);
+  wl.push(R * 16, 32, 800, W.g0, W.dc1, 800, wl.g(P.dcv[0].w), 800, nullptr);
+  wl.push(R * 64, 32, 1, W.dp1, W.ones, 1, wl.g(P.dcv[0].b), 1, nullptr);
+  wl.push(R, 512, 300, W.dd2, W.d1, 300, wl.g(P.dfc[1].w), 300, wl.g(P.dfc[1].b));
+  wl.push(R, 300, P.zd, W.dd1, W.z, P.zd, wl.g(P.dfc[0].w), P.zd, wl.g(P.dfc[0].b));
+}
+
+// every weight-gradient problem of conv_model_vae_backward, with its scratch taken from ws
+void conv_wgrads(const ConvLayout& P, const ConvWs& W, int B, int R, const float* noise, WgradList& wl, Bump& ws) {
+  conv_decoder_wgrads(P, W, R, wl);
+  wl.push(R, P.zd, 800, W.dz, W.t1, 800, wl.g(P.fc5.w), 800, wl.g(P.fc5.b));
+  wl.push(R, 800, P.nd, W.dt1, noise, P.nd, wl.g(P.fc4.w + 512), 512 + P.nd, wl.g(P.fc4.b));   // fc4 noise half (+ bias)
+  wl.push(B, 800, 512, W.drb, W.inp, 512, wl.g(P.fc4.w), 512 + P.nd, nullptr);                  // fc4 image half
+  wl.push(B * 16, 32, 800, W.dh3, W.cols[2], 800, wl.g(P.conv[2].w), 800, wl.g(P.conv[2].b));
+  wl.push(B * 49, 32, 400, W.dh2, W.cols[1], 400, wl.g(P.conv[1].w), 400, wl.g(P.conv[1].b));
+  wl.push(B * 196, 16, 25, W.dh1, W.cols[0], 25, wl.g(P.conv[0].w), 25, wl.g(P.conv[0].b));
+  wl.assign(ws, CONV_WGRAD_HINT);
+}
+
+size_t conv_workspace(const ConvLayout& P, int B, int nz, int mode) {
+  // run the carve (and the weight-gradient list) on a null arena to count
+  Bump ws;
+  ConvWs W;
+  carve(P, ws, B, nz, mode, W);
+  if (mode == 1) {
+    WgradList wl(nullptr);
+    conv_wgrads(P, W, B, B * nz, nullptr, wl, ws);
+  }
+  return ws.off + al64((size_t)B * nz * P.nd);    // + zero-noise buffer for encode(std=0)
 }
 
 }  // namespace
@@ -438,31 +395,11 @@ int conv_model_vae_backward(const ardae_model_desc& d, const float* params, cons
   { LinArgs A{}; A.Y = W.dinp; A.ldY = 512;
     ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 512, W.drb, 800, 800, packed + K.fc4i_b, A, st)); }
   ARDAE_TRY(trunk_bwd(K.conv_b, packed, W.dinp, W.dinp_t, W.hcv, W.dh3, W.dcols3, W.dh2, W.dcols2, W.dh1, B, act, st));
-  // ---- weight gradients (order must match wgrad_scratch)
-  std::vector<int> splits;
-  wgrad_scratch(P, B, R, &splits);
-  std::vector<WgradProblem> probs;
-  auto push = [&](int M, int O, int I, const float* G, const float* X, float* out, int ldout, float* out_bias) {
-    WgradProblem p;
-    memset(&p, 0, sizeof(p));
-    p.M = M; p.O = O; p.I = I; p.npairs = 1;
-    p.G[0] = G; p.ldG[0] = O; p.X[0] = X; p.ldX[0] = I;
-    p.bias_pair = out_bias ? 0 : -1;
-    p.splits = splits[probs.size()];
-    p.partial = ws.take((size_t)p.splits * O * I);
-    p.partial_vec = ws.take((size_t)p.splits * 2 * O);
-    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.beta = grads_beta;
-    probs.push_back(p);
-  };
-  conv_decoder_wgrads(P, W, R, grads, push);
-  push(R, P.zd, 800, W.dz, W.t1, grads + P.fc5.w, 800, grads + P.fc5.b);
-  push(R, 800, P.nd, W.dt1, noise, grads + P.fc4.w + 512, 512 + P.nd, grads + P.fc4.b);
-  push(B, 800, 512, W.drb, W.inp, grads + P.fc4.w, 512 + P.nd, nullptr);
-  push(B * 16, 32, 800, W.dh3, W.cols[2], grads + P.conv[2].w, 800, grads + P.conv[2].b);
-  push(B * 49, 32, 400, W.dh2, W.cols[1], grads + P.conv[1].w, 400, grads + P.conv[1].b);
-  push(B * 196, 16, 25, W.dh1, W.cols[0], grads + P.conv[0].w, 25, grads + P.conv[0].b);
+  // ---- weight gradients: one batched launch
+  WgradList wl(grads, grads_beta);
+  conv_wgrads(P, W, B, R, noise, wl, ws);
   ARDAE_CHECK_ARG(ws.ok, "conv_model_vae_backward: workspace too small");
-  return launch_wgrad_batch(probs.data(), (int)probs.size(), st);
+  return wl.launch(st);
 }
 
 
@@ -556,28 +493,38 @@ void aux_carve(const AuxConvLayout& P, Bump& ws, int B, int nz, int mode, AuxCon
   }
 }
 
-constexpr int AUX_N_WGRAD = 21;   // 8 decoder + 13 sampler problems, launched as two batches (20 per batch at most)
+// wgrad_splits hint of the hierarchical conv backward, and the size of its first batch: the 21 problems go out as 10 + 11
+constexpr int AUX_WGRAD_HINT = 10;
 
-size_t aux_wgrad_scratch(const AuxConvLayout& P, int B, int R, std::vector<int>* out) {
-  std::vector<int> sp; size_t tot = 0;
-  auto one = [&](int M, int O, int I) { const int s = wgrad_splits(M, O, I, AUX_N_WGRAD / 2); sp.push_back(s); tot += al64((size_t)s * O * I) + al64((size_t)s * 2 * O); };
-  one(R * 225, 16, 25); one(R * 784, 1, 1); one(R * 64, 32, 400); one(R * 225, 16, 1); one(R * 16, 32, 800); one(R * 64, 32, 1);
-  one(R, 512, 300); one(R, 300, P.zd);                                              // decoder (as ConvIPVAE)
-  one(R, P.zd, 800); one(R, P.zd, 800); one(R, 800, P.nd); one(B, 800, 512);       // mean, logvar, fc z0 half (+bias), fc image half
-  one(B * 16, 32, 800); one(B * 49, 32, 400); one(B * 196, 16, 25);                // encoder trunk
-  one(B, P.nd, 800); one(B, P.nd, 800); one(B, 800, 512);                          // mean0, logvar0, aux fc
-  one(B * 16, 32, 800); one(B * 49, 32, 400); one(B * 196, 16, 25);                // aux trunk
-  if (out) *out = sp;
-  return tot;
+// every weight-gradient problem of auxconv_model_vae_backward, with its scratch taken from ws
+void auxconv_wgrads(const AuxConvLayout& P, const AuxConvWs& W, int B, int R, WgradList& wl, Bump& ws) {
+  const ConvWs& D = W.D;
+  conv_decoder_wgrads(P.dec, D, R, wl);                                                             // decoder (as ConvIPVAE)
+  wl.push(R, P.zd, 800, D.dz, D.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
+  wl.push(R, P.zd, 800, W.dlv, D.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
+  wl.push(R, 800, P.nd, W.dt1, W.z0, P.nd, wl.g(P.efc.w + 512), 512 + P.nd, wl.g(P.efc.b));         // fc z0 half (+ bias)
+  wl.push(B, 800, 512, W.drb, W.einp, 512, wl.g(P.efc.w), 512 + P.nd, nullptr);                     // fc image half
+  wl.push(B * 16, 32, 800, W.dh3[1], W.ecols[2], 800, wl.g(P.econv[2].w), 800, wl.g(P.econv[2].b));  // encoder trunk
+  wl.push(B * 49, 32, 400, W.dh2[1], W.ecols[1], 400, wl.g(P.econv[1].w), 400, wl.g(P.econv[1].b));
+  wl.push(B * 196, 16, 25, W.dh1[1], W.ecols[0], 25, wl.g(P.econv[0].w), 25, wl.g(P.econv[0].b));
+  wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
+  wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
+  wl.push(B, 800, 512, W.dh4a, W.ainp, 512, wl.g(P.afc.w), 512, wl.g(P.afc.b));
+  wl.push(B * 16, 32, 800, W.dh3[0], W.acols[2], 800, wl.g(P.aconv[2].w), 800, wl.g(P.aconv[2].b));  // aux trunk
+  wl.push(B * 49, 32, 400, W.dh2[0], W.acols[1], 400, wl.g(P.aconv[1].w), 400, wl.g(P.aconv[1].b));
+  wl.push(B * 196, 16, 25, W.dh1[0], W.acols[0], 25, wl.g(P.aconv[0].w), 25, wl.g(P.aconv[0].b));
+  wl.assign(ws, AUX_WGRAD_HINT);
 }
 
 size_t aux_workspace(const AuxConvLayout& P, int B, int nz, int mode) {
-  Bump b(nullptr, ~size_t(0));
+  Bump ws;
   AuxConvWs W;
-  aux_carve(P, b, B, nz, mode, W);
-  size_t t = b.off;
-  if (mode == 1) t += aux_wgrad_scratch(P, B, B * nz, nullptr);
-  return t;
+  aux_carve(P, ws, B, nz, mode, W);
+  if (mode == 1) {
+    WgradList wl(nullptr);
+    auxconv_wgrads(P, W, B, B * nz, wl, ws);
+  }
+  return ws.off;
 }
 
 // keep_hidden = false (forward-only encodes of the cDAE phase): the [R, 800] hidden rows need not exist
@@ -737,40 +684,12 @@ int auxconv_model_vae_backward(const ardae_model_desc& d, const float* params, c
   { LinArgs A{}; A.Y = W.dinp_a; A.ldY = 512;
     ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, A, st)); }
   ARDAE_TRY(trunk_bwd(K.aconv_b, packed, W.dinp_a, W.dinp_t, W.ahcv, W.dh3[0], W.dcols3[0], W.dh2[0], W.dcols2[0], W.dh1[0], B, act, st));
-  // ---- weight gradients: 8 decoder + 14 sampler problems in two batches (order == aux_wgrad_scratch)
-  std::vector<int> splits;
-  aux_wgrad_scratch(P, B, R, &splits);
-  std::vector<WgradProblem> probs;
-  auto push = [&](int M, int O, int I, const float* G, const float* X, float* out, int ldout, float* out_bias) {
-    WgradProblem p;
-    memset(&p, 0, sizeof(p));
-    p.M = M; p.O = O; p.I = I; p.npairs = 1;
-    p.G[0] = G; p.ldG[0] = O; p.X[0] = X; p.ldX[0] = I;
-    p.bias_pair = out_bias ? 0 : -1;
-    p.splits = splits[probs.size()];
-    p.partial = ws.take((size_t)p.splits * O * I);
-    p.partial_vec = ws.take((size_t)p.splits * 2 * O);
-    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.beta = grads_beta;
-    probs.push_back(p);
-  };
-  conv_decoder_wgrads(P.dec, D, R, grads, push);
-  push(R, P.zd, 800, D.dz, D.t1, grads + P.mean.w, 800, grads + P.mean.b);
-  push(R, P.zd, 800, W.dlv, D.t1, grads + P.logvar.w, 800, grads + P.logvar.b);
-  push(R, 800, P.nd, W.dt1, W.z0, grads + P.efc.w + 512, 512 + P.nd, grads + P.efc.b);
-  push(B, 800, 512, W.drb, W.einp, grads + P.efc.w, 512 + P.nd, nullptr);
-  push(B * 16, 32, 800, W.dh3[1], W.ecols[2], grads + P.econv[2].w, 800, grads + P.econv[2].b);
-  push(B * 49, 32, 400, W.dh2[1], W.ecols[1], grads + P.econv[1].w, 400, grads + P.econv[1].b);
-  push(B * 196, 16, 25, W.dh1[1], W.ecols[0], grads + P.econv[0].w, 25, grads + P.econv[0].b);
-  push(B, P.nd, 800, W.dmu0, W.h4a, grads + P.mean0.w, 800, grads + P.mean0.b);
-  push(B, P.nd, 800, W.dlv0, W.h4a, grads + P.logvar0.w, 800, grads + P.logvar0.b);
-  push(B, 800, 512, W.dh4a, W.ainp, grads + P.afc.w, 512, grads + P.afc.b);
-  push(B * 16, 32, 800, W.dh3[0], W.acols[2], grads + P.aconv[2].w, 800, grads + P.aconv[2].b);
-  push(B * 49, 32, 400, W.dh2[0], W.acols[1], grads + P.aconv[1].w, 400, grads + P.aconv[1].b);
-  push(B * 196, 16, 25, W.dh1[0], W.acols[0], grads + P.aconv[0].w, 25, grads + P.aconv[0].b);
-  ARDAE_CHECK_ARG(ws.ok, "auxconv_model_vae_backward: workspace too small (%zu floats needed so far, %zu given, %zu problems)", ws.off, wsf, probs.size());
-  ARDAE_CHECK_ARG((int)probs.size() == AUX_N_WGRAD, "auxconv_model_vae_backward: internal problem count");
-  ARDAE_TRY(launch_wgrad_batch(probs.data(), AUX_N_WGRAD / 2, st));
-  return launch_wgrad_batch(probs.data() + AUX_N_WGRAD / 2, AUX_N_WGRAD - AUX_N_WGRAD / 2, st);
+  // ---- weight gradients, launched as two batches
+  WgradList wl(grads, grads_beta);
+  auxconv_wgrads(P, W, B, R, wl, ws);
+  ARDAE_CHECK_ARG(ws.ok, "auxconv_model_vae_backward: workspace too small (%zu floats needed, %zu given, %zu problems)", ws.off, wsf, wl.probs.size());
+  ARDAE_TRY(wl.launch(st, AUX_WGRAD_HINT));
+  return wl.launch(st);
 }
 
 }  // namespace ardae

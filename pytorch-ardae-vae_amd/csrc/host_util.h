@@ -1,0 +1,113 @@
+// Host-side helpers shared by the model families (model / convmodel / auxmodel / resmodel .hip) and cdae.hip: the bump
+// allocator that carves a workspace arena, one-/two-source linear launches, and the list of weight-gradient problems a
+// backward pass hands to launch_wgrad_batch.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "linear.h"
+#include "wgrad.h"
+
+namespace ardae {
+
+inline size_t al64(size_t n) { return (n + 63) & ~size_t(63); }
+inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Carves 64-float-aligned pieces out of an arena.  With a null base it only counts (the sizing pass of every
+// *_workspace_floats): take() returns nullptr and `off` ends up as the floats a real arena needs.
+struct Bump {
+  float* base; size_t cap; size_t off = 0; bool ok = true;
+  Bump(float* b, size_t c) : base(b), cap(c) {}
+  Bump() : base(nullptr), cap(~size_t(0) >> 2) {}   // sizing pass
+  float* take(size_t n) {
+    size_t o = off; off += al64(n);
+    if (off > cap) { ok = false; return base; }
+    return base ? base + o : nullptr;
+  }
+};
+
+// one linear launch, one or two sources
+inline int lin1(int epi, int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a, hipStream_t st) {
+  a.M = M; a.Nout = Nout; a.nsrc = 1; a.act = act;
+  a.src[0].x = x; a.src[0].ld = ldx; a.src[0].K = K; a.src[0].wp = wp;
+  return launch_linear(a, epi, st);
+}
+inline int lin2(int epi, int act, int M, int Nout, const float* x0, int ld0, int K0, const float* wp0, const float* x1, int ld1, int K1, const float* wp1,
+                LinArgs a, hipStream_t st) {
+  a.M = M; a.Nout = Nout; a.nsrc = 2; a.act = act;
+  a.src[0].x = x0; a.src[0].ld = ld0; a.src[0].K = K0; a.src[0].wp = wp0;
+  a.src[1].x = x1; a.src[1].ld = ld1; a.src[1].K = K1; a.src[1].wp = wp1;
+  return launch_linear(a, epi, st);
+}
+
+// The weight-gradient problems of one backward, written ONCE per family: the backward pushes them with its real buffers,
+// assigns their scratch out of the arena and launches; *_workspace_floats runs the same code over a sizing Bump with null
+// buffers (nothing is dereferenced) and reads the arena offset.
+struct WgradList {
+  std::vector<WgradProblem> probs;
+  float* grads;      // flat gradient buffer (null in a sizing pass)
+  float beta;        // out = beta * out + sum, for every problem pushed
+  size_t next = 0;   // first problem not launched yet
+  explicit WgradList(float* grads_, float beta_ = 0.f) : grads(grads_), beta(beta_) {}
+  float* g(size_t off) const { return grads ? grads + off : nullptr; }
+
+  // dW[O, I] = G[M, O]^T X[M, I] (+ the bias gradient, G's column sums, where out_bias is given)
+  WgradProblem& push(int M, int O, int I, const float* G, const float* X, int ldX, float* out, int ldout, float* out_bias) {
+    WgradProblem p;
+    memset(&p, 0, sizeof(p));
+    p.M = M; p.O = O; p.I = I; p.npairs = 1;
+    p.G[0] = G; p.ldG[0] = O; p.X[0] = X; p.ldX[0] = ldX;
+    p.bias_pair = out_bias ? 0 : -1;
+    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.beta = beta;
+    return add(p);
+  }
+  // the cDAE's form: a second (G, X) pair (G1 null: none), the pair whose G gives the bias gradient (-1: none), a row scale
+  WgradProblem& push2(int M, int O, int I, const float* G0, const float* X0, int ldX0, const float* G1, const float* X1, int ldX1, int bias_pair,
+                      const float* rowscale, float* out, int ldout, float* out_bias, float* out_rs, int ld_rs) {
+    WgradProblem p;
+    memset(&p, 0, sizeof(p));
+    p.M = M; p.O = O; p.I = I;
+    p.npairs = G1 ? 2 : 1;
+    p.G[0] = G0; p.ldG[0] = O; p.X[0] = X0; p.ldX[0] = ldX0;
+    p.G[1] = G1; p.ldG[1] = O; p.X[1] = X1; p.ldX[1] = ldX1;
+    p.bias_pair = bias_pair; p.rowscale = rowscale;
+    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.out_rowscale = out_rs; p.ld_rowscale = ld_rs; p.beta = beta;
+    return add(p);
+  }
+  WgradProblem& add(const WgradProblem& p) {
+    if (probs.empty()) probs.reserve(WGRAD_MAX_PROBLEMS + 2);   // one allocation per list
+    probs.push_back(p);
+    return probs.back();
+  }
+  size_t pending() const { return probs.size() - next; }
+  // splits (wgrad_splits with the family's hint) and scratch for the next n pending problems, in list order
+  void assign(Bump& ws, int hint, size_t n = ~size_t(0)) {
+    const size_t end = next + std::min(n, pending());
+    for (size_t i = next; i < end; ++i) {
+      WgradProblem& p = probs[i];
+      p.splits = wgrad_splits(p.M, p.O, p.I, hint);
+      p.partial = ws.take((size_t)p.splits * p.O * p.I);
+      p.partial_vec = ws.take((size_t)p.splits * 2 * p.O);
+    }
+  }
+  // launches the next n pending problems (default: all of them), WGRAD_MAX_PROBLEMS per batch at most; a caller that wants
+  // a batch boundary elsewhere names it through n
+  int launch(hipStream_t st, size_t n = ~size_t(0)) {
+    const size_t end = next + std::min(n, pending());
+    while (next < end) {
+      const size_t m = std::min<size_t>(end - next, WGRAD_MAX_PROBLEMS);
+      ARDAE_TRY(launch_wgrad_batch(probs.data() + next, (int)m, st));
+      next += m;
+    }
+    return 0;
+  }
+};
+
+// y = x * act'(S)  (S = saved post-activation); y may alias x
+int launch_mul_dact(const float* x, const float* S, int act, float* y, int64_t n, hipStream_t st);
+// [B, HW, C] (NHWC rows) <-> [B, C*HW] (PyTorch's .view(B, -1) of NCHW); to_nhwc: `in` is the NCHW side
+int launch_nhwc_nchw(const float* in, int B, int HW, int C, float* out, bool to_nhwc, hipStream_t st);
+
+}  // namespace ardae

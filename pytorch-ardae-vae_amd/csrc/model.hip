@@ -16,8 +16,7 @@
 #include "convmodel.h"
 #include "resmodel.h"
 #include "elementwise.h"
-#include "linear.h"
-#include "wgrad.h"
+#include "host_util.h"
 
 namespace ardae {
 namespace {
@@ -78,16 +77,6 @@ struct ModelPacked {
   }
 };
 
-struct Bump {
-  float* base; size_t cap; size_t off = 0; bool ok = true;
-  Bump(float* b, size_t c) : base(b), cap(c) {}
-  float* take(size_t n) {
-    size_t o = off; off += (n + 63) & ~size_t(63);
-    if (off > cap) { ok = false; return base; }
-    return base + o;
-  }
-};
-
 int desc_ok(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "model: desc is NULL");
   ARDAE_CHECK_ARG(d->kind >= 0 && d->kind <= 7,
@@ -130,40 +119,6 @@ struct ModelWs {
   float *dzq, *dz, *drb;
 };
 
-size_t al64(size_t n) { return (n + 63) & ~size_t(63); }
-
-size_t wgrad_scratch(const ModelLayout& P, int B, int R, std::vector<int>* splits_out) {
-  std::vector<int> sp;
-  size_t tot = 0;
-  const int nprob = (int)(P.heads.size() + P.dec.size() + 2 * P.stack.size() + P.inp.size());
-  auto one = [&](int M, int O, int I) {
-    const int s = wgrad_splits(M, O, I, nprob);
-    sp.push_back(s);
-    tot += al64((size_t)s * O * I) + al64((size_t)s * 2 * O);
-  };
-  for (auto& l : P.heads) one(R, l.out, l.in);
-  for (auto& l : P.dec) one(R, l.out, l.in);
-  for (size_t i = 0; i < P.stack.size(); ++i) {
-    one(i == 0 ? B : R, P.stack[i].out, P.h);              // hidden part
-    if (P.stack_noise[i]) one(R, P.stack[i].out, P.nd);    // noise part
-  }
-  for (auto& l : P.inp) one(B, l.out, l.in);
-  if (splits_out) *splits_out = sp;
-  return tot;
-}
-
-size_t workspace_floats(const ModelLayout& P, int B, int nz, int mode) {
-  const size_t R = (size_t)B * nz, h = P.h;
-  size_t t = al64((size_t)B * P.D) + P.inp.size() * al64((size_t)B * h) + al64((size_t)B * h);
-  t += (P.stack.size() - 1) * al64(R * h) + al64(R * P.zd);
-  if (mode == 0) return t;
-  t += P.dec.size() * al64(R * h) + P.heads.size() * al64(R * P.D) + 2 * al64(R);
-  t += P.heads.size() * al64(R * P.D) + P.dec.size() * al64(R * h) + (P.stack.size() - 1) * al64(R * h) + P.inp.size() * al64((size_t)B * h);
-  t += 2 * al64(R * P.zd) + al64((size_t)B * h);
-  t += wgrad_scratch(P, B, (int)R, nullptr);
-  return t;
-}
-
 void carve(const ModelLayout& P, Bump& ws, int B, int nz, int mode, ModelWs& W) {
   const size_t R = (size_t)B * nz, h = P.h;
   W.x2 = ws.take((size_t)B * P.D);
@@ -188,10 +143,38 @@ void carve(const ModelLayout& P, Bump& ws, int B, int nz, int mode, ModelWs& W) 
   W.dzq = ws.take(R * P.zd); W.dz = ws.take(R * P.zd); W.drb = ws.take((size_t)B * h);
 }
 
-int lin1(int epi, int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a, hipStream_t st) {
-  a.M = M; a.Nout = Nout; a.nsrc = 1; a.act = act;
-  a.src[0].x = x; a.src[0].ld = ldx; a.src[0].K = K; a.src[0].wp = wp;
-  return launch_linear(a, epi, st);
+// every weight-gradient problem of the backward, with its scratch taken from ws (x: the images; noise: the sampler's draw)
+void model_wgrads(const ModelLayout& P, const ModelWs& W, const float* x, const float* noise, int B, int R, WgradList& wl, Bump& ws) {
+  const int h = P.h;
+  const size_t ns = P.stack.size(), ndec = P.dec.size(), ninp = P.inp.size(), nh = P.heads.size();
+  const float* x_in = P.kind == 0 ? W.x2 : x;
+  for (size_t k = 0; k < nh; ++k) wl.push(R, P.D, h, W.dox[k], W.dcd[ndec], h, wl.g(P.heads[k].w), h, wl.g(P.heads[k].b));
+  for (size_t l = 1; l <= ndec; ++l)
+    wl.push(R, h, P.dec[l - 1].in, W.ddec[l], l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, wl.g(P.dec[l - 1].w), P.dec[l - 1].in,
+            wl.g(P.dec[l - 1].b));
+  for (size_t i = 0; i < ns; ++i) {
+    const Lin& L = P.stack[i];
+    const float* G = (i == ns - 1) ? W.dz : W.dt[i + 1];
+    if (i == 0) wl.push(B, L.out, h, W.drb, W.e[ninp], h, wl.g(L.w), L.in, nullptr);        // per-image hidden part
+    else wl.push(R, L.out, h, G, W.t[i], h, wl.g(L.w), L.in, P.stack_noise[i] ? nullptr : wl.g(L.b));
+    if (P.stack_noise[i]) wl.push(R, L.out, P.nd, G, noise, P.nd, wl.g(L.w + h), L.in, wl.g(L.b));   // noise part (+ bias)
+  }
+  for (size_t l = 1; l <= ninp; ++l)
+    wl.push(B, h, P.inp[l - 1].in, W.de[l], l == 1 ? x_in : W.e[l - 1], l == 1 ? P.D : h, wl.g(P.inp[l - 1].w), P.inp[l - 1].in,
+            wl.g(P.inp[l - 1].b));
+  wl.assign(ws, (int)(nh + ndec + 2 * ns + ninp));   // the hint counts a noise part for every stack layer
+}
+
+// dry run of carve() and the weight-gradient list on a null arena (mode 0: the sampler's buffers only)
+size_t workspace_floats(const ModelLayout& P, int B, int nz, int mode) {
+  Bump ws;
+  ModelWs W;
+  carve(P, ws, B, nz, mode, W);
+  if (mode != 0) {
+    WgradList wl(nullptr);
+    model_wgrads(P, W, nullptr, nullptr, B, B * nz, wl, ws);
+  }
+  return ws.off;
 }
 
 // sampler trunk (once per image): inp_encode on B rows, then rb = inp . S_1[:, :h]^T + b_S1.  Fills W.e, W.rb.
@@ -551,39 +534,11 @@ static int vae_backward_impl(const ardae_model_desc* d, const float* params, con
     LinArgs A{}; A.S = W.e[l - 1]; A.ldS = h; A.Y = W.de[l - 1]; A.ldY = h;
     ARDAE_TRY(lin1(EPI_DACT, act, B, h, W.de[l], h, h, packed + K.inp_b[l - 1], A, st));
   }
-  // weight gradients: one batched launch (problem order must match wgrad_scratch)
-  std::vector<int> splits;
-  wgrad_scratch(P, B, R, &splits);
-  std::vector<WgradProblem> probs;
-  auto push = [&](int M, int O, int I, const float* G, const float* X, int ldX, float* out, int ldout, float* out_bias) {
-    WgradProblem p;
-    memset(&p, 0, sizeof(p));
-    p.M = M; p.O = O; p.I = I; p.npairs = 1;
-    p.G[0] = G; p.ldG[0] = O; p.X[0] = X; p.ldX[0] = ldX;
-    p.bias_pair = out_bias ? 0 : -1;
-    p.splits = splits[probs.size()];
-    p.partial = ws.take((size_t)p.splits * O * I);
-    p.partial_vec = ws.take((size_t)p.splits * 2 * O);
-    p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.beta = grads_beta;
-    probs.push_back(p);
-  };
-  const float* x_in = P.kind == 0 ? W.x2 : x;
-  for (size_t k = 0; k < nh; ++k) push(R, P.D, h, W.dox[k], W.dcd[ndec], h, grads + P.heads[k].w, h, grads + P.heads[k].b);
-  for (size_t l = 1; l <= ndec; ++l)
-    push(R, h, P.dec[l - 1].in, W.ddec[l], l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, grads + P.dec[l - 1].w, P.dec[l - 1].in,
-         grads + P.dec[l - 1].b);
-  for (size_t i = 0; i < ns; ++i) {
-    const Lin& L = P.stack[i];
-    const float* G = (i == ns - 1) ? W.dz : W.dt[i + 1];
-    if (i == 0) push(B, L.out, h, W.drb, W.e[ninp], h, grads + L.w, L.in, nullptr);        // per-image hidden part
-    else push(R, L.out, h, G, W.t[i], h, grads + L.w, L.in, P.stack_noise[i] ? nullptr : grads + L.b);
-    if (P.stack_noise[i]) push(R, L.out, P.nd, G, noise, P.nd, grads + L.w + h, L.in, grads + L.b);   // noise part (+ bias)
-  }
-  for (size_t l = 1; l <= ninp; ++l)
-    push(B, h, P.inp[l - 1].in, W.de[l], l == 1 ? x_in : W.e[l - 1], l == 1 ? P.D : h, grads + P.inp[l - 1].w, P.inp[l - 1].in,
-         grads + P.inp[l - 1].b);
+  // weight gradients: one batched launch
+  WgradList wl(grads, grads_beta);
+  model_wgrads(P, W, x, noise, B, R, wl, ws);
   ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
-  return launch_wgrad_batch(probs.data(), (int)probs.size(), st);
+  return wl.launch(st);
 }
 
 int ardae_model_vae_backward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,

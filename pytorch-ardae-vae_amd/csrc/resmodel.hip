@@ -19,15 +19,11 @@
 #include "auxmodel.h"
 #include "common.h"
 #include "elementwise.h"
-#include "linear.h"
+#include "host_util.h"
 #include "resmodel.h"
-#include "wgrad.h"
 
 namespace ardae {
 namespace {
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
-size_t al64(size_t n) { return (n + 63) & ~size_t(63); }
 
 // ------------------------------------------------------------------------------------------------ kernels
 // weff[o][:] = scale[o] * dir[o][:] * inv,  inv = norm ? 1 / ||dir[o][:]|| : 1   (one workgroup per output row)
@@ -149,11 +145,6 @@ __global__ void act_inplace_kernel(float* __restrict__ x, int act, int64_t n) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) x[e] = act_fwd_rt(act, x[e]);
 }
-// y = x * act'(S)  (S = saved post-activation)
-__global__ void mul_dact_kernel(const float* __restrict__ x, const float* __restrict__ S, int act, float* __restrict__ y, int64_t n) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) y[e] = x[e] * act_d1_rt(act, S[e]);
-}
 
 // bilinear x2 upsampling, align_corners=True (nn.Upsample in models/vae/resconv.py:96-106), NHWC; src = o (IH-1)/(OH-1)
 __device__ __forceinline__ void up_src(int o, int IH, int OH, int& i0, int& i1, float& f) {
@@ -217,16 +208,6 @@ __global__ void crop_pad_kernel(const float* __restrict__ x, int HS, int HD, int
   const int w = (int)(pix % HD), h = (int)((pix / HD) % HD);
   const int64_t b = pix / ((int64_t)HD * HD);
   y[e] = (h < HS && w < HS) ? x[((b * HS + h) * HS + w) * C + c] : 0.f;
-}
-// [B, HW, C] (NHWC rows) <-> [B, C*HW] (PyTorch's .view(B, -1) of NCHW)
-__global__ void nhwc_nchw_kernel(const float* __restrict__ in, int HW, int C, float* __restrict__ out, int64_t total, int to_nhwc) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int c = (int)(e % C);
-  const int hw = (int)((e / C) % HW);
-  const int64_t b = e / ((int64_t)C * HW);
-  const int64_t nchw = (b * C + c) * HW + hw;
-  if (to_nhwc) out[e] = in[nchw]; else out[nchw] = in[e];
 }
 // NormalDistribution.clip_logvar 'spm4' (models/reparam.py:30-31): y = softplus(x + 4) - 4; backward: dx = dy * sigmoid(x + 4)
 // identity != 0 (the clipped class of ivae/auxresconv2.py:71-72 builds its heads WITHOUT the clip): y = x, dx = dy
@@ -373,16 +354,6 @@ struct ResPacked {
   }
 };
 
-struct Bump {
-  float* base; size_t cap; size_t off = 0; bool ok = true;
-  Bump(float* b, size_t c) : base(b), cap(c) {}
-  float* take(size_t n) {
-    size_t o = off; off += al64(n);
-    if (off > cap) { ok = false; return base; }
-    return base ? base + o : nullptr;
-  }
-};
-
 int res_desc_ok(const ardae_model_desc& d) {
   ARDAE_CHECK_ARG(d.input_dim == 784 && d.noise_dim >= 1 && d.z_dim >= 1 && d.h_dim >= 1, "model: the residual-conv models are hard-wired to 28x28x1 inputs");
   ARDAE_CHECK_ARG(d.act == ACT_ELU, "model: the residual-conv models use ELU (--model-nonlin elu; models/ivae/auxresconv.py:69 asserts it)");
@@ -395,20 +366,6 @@ int res_desc_ok(const ardae_model_desc& d) {
     ARDAE_CHECK_ARG(ht == HEAD_MLP || 512 + d.noise_dim != d.h_dim, "model: ResConvIPVAE with c_dim + noise_dim == h_dim (identity skip over the concat input) is not built");
   }
   return 0;
-}
-
-// one linear launch, one or two sources
-int lin1(int epi, int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a, hipStream_t st) {
-  a.M = M; a.Nout = Nout; a.nsrc = 1; a.act = act;
-  a.src[0].x = x; a.src[0].ld = ldx; a.src[0].K = K; a.src[0].wp = wp;
-  return launch_linear(a, epi, st);
-}
-int lin2(int epi, int act, int M, int Nout, const float* x0, int ld0, int K0, const float* wp0, const float* x1, int ld1, int K1, const float* wp1,
-         LinArgs a, hipStream_t st) {
-  a.M = M; a.Nout = Nout; a.nsrc = 2; a.act = act;
-  a.src[0].x = x0; a.src[0].ld = ld0; a.src[0].K = K0; a.src[0].wp = wp0;
-  a.src[1].x = x1; a.src[1].ld = ld1; a.src[1].K = K1; a.src[1].wp = wp1;
-  return launch_linear(a, epi, st);
 }
 
 // saved activations of one block
@@ -455,34 +412,16 @@ struct BwdScratch { float *g, *dh, *dcols; };
 struct WnGrad { float* dW; float* db; float beta; };   // beta: accumulate into the destination (plain operators write the gradient buffer itself)
 struct BlkGrad { WnGrad a, h, s; };
 
-void push_wgrad(std::vector<WgradProblem>& probs, std::vector<std::pair<size_t, size_t>>& need, int M, int O, int I, const float* G, const float* X, int ldX,
-                float* out, int ldout, float* out_bias) {
-  WgradProblem p;
-  memset(&p, 0, sizeof(p));
-  p.M = M; p.O = O; p.I = I; p.npairs = 1;
-  p.G[0] = G; p.ldG[0] = O; p.X[0] = X; p.ldX[0] = ldX;
-  p.bias_pair = out_bias ? 0 : -1;
-  p.out = out; p.ldout = ldout; p.out_bias = out_bias; p.beta = 0.f;
-  probs.push_back(p);
-  (void)need;
-}
-// assign splits + scratch and launch (at most ARDAE_WGRAD_MAX_PROBLEMS per batch)
-int flush_wgrad(std::vector<WgradProblem>& probs, float* scratch, size_t scratch_floats, hipStream_t st) {
-  size_t i0 = 0;
-  while (i0 < probs.size()) {
-    const size_t n = std::min<size_t>(probs.size() - i0, ARDAE_WGRAD_MAX_PROBLEMS);
+// assign splits + scratch (the scratch is reused from batch to batch; the batch size is the wgrad_splits hint) and launch,
+// at most ARDAE_WGRAD_MAX_PROBLEMS per batch
+int flush_wgrad(WgradList& wl, float* scratch, size_t scratch_floats, hipStream_t st) {
+  while (wl.pending()) {
+    const size_t n = std::min<size_t>(wl.pending(), ARDAE_WGRAD_MAX_PROBLEMS);
     Bump ws(scratch, scratch_floats);
-    for (size_t i = i0; i < i0 + n; ++i) {
-      WgradProblem& p = probs[i];
-      p.splits = wgrad_splits(p.M, p.O, p.I, (int)n);
-      p.partial = ws.take((size_t)p.splits * p.O * p.I);
-      p.partial_vec = ws.take((size_t)p.splits * 2 * p.O);
-    }
+    wl.assign(ws, (int)n, n);
     ARDAE_CHECK_ARG(ws.ok, "res model: weight-gradient scratch too small");
-    ARDAE_TRY(launch_wgrad_batch(probs.data() + i0, (int)n, st));
-    i0 += n;
+    ARDAE_TRY(wl.launch(st, n));
   }
-  probs.clear();
   return 0;
 }
 size_t wgrad_scratch_floats(int M, int O, int I) {
@@ -499,7 +438,7 @@ int blk_bwd(const Blk& b, const BlkPk& k, const float* packed, const float* x, i
   const int64_t nout = (int64_t)R * b.Cout;
   const float* g = d_out;
   if (act_out != ACT_NONE) {
-    RES_LAUNCH(mul_dact_kernel, nout, d_out, u.out, act_out, sc.g, nout);
+    ARDAE_TRY(launch_mul_dact(d_out, u.out, act_out, sc.g, nout, st));
     g = sc.g;
   }
   const float* cx = b.conv ? u.colsx : x;
@@ -514,12 +453,11 @@ int blk_bwd(const Blk& b, const BlkPk& k, const float* packed, const float* x, i
     ARDAE_TRY(lin1(EPI_DACT, ACT_RELU, R, b.Cout, g, b.Cout, b.Cout, packed + k.h.b, A, st));
   }
   // weight gradients of the three operators (their bias gradients: column sums of d hmid / g; b_h1 and b_01 share g's)
-  std::vector<WgradProblem> probs;
-  std::vector<std::pair<size_t, size_t>> dummy;
-  push_wgrad(probs, dummy, R, b.Cout, b.h.I, g, ch, b.h.I, gr.h.dW, b.h.I, gr.h.db);
-  push_wgrad(probs, dummy, R, b.Cout, b.s.I, g, cx, b.s.I, gr.s.dW, b.s.I, gr.s.db);
-  push_wgrad(probs, dummy, R, b.Cout, b.a.I, sc.dh, cx, b.a.I, gr.a.dW, b.a.I, gr.a.db);
-  ARDAE_TRY(flush_wgrad(probs, wscratch, wscratch_floats, st));
+  WgradList wl(nullptr);
+  wl.push(R, b.Cout, b.h.I, g, ch, b.h.I, gr.h.dW, b.h.I, gr.h.db);
+  wl.push(R, b.Cout, b.s.I, g, cx, b.s.I, gr.s.dW, b.s.I, gr.s.db);
+  wl.push(R, b.Cout, b.a.I, sc.dh, cx, b.a.I, gr.a.dW, b.a.I, gr.a.db);
+  ARDAE_TRY(flush_wgrad(wl, wscratch, wscratch_floats, st));
   if (!d_x) return 0;
   // d x = W_01^T g + W_0h^T d hmid
   if (b.conv) {
@@ -626,7 +564,7 @@ void res_carve(const ResLayout& P, Bump& ws, int B, int nz, int mode, ResWs& W) 
 }
 
 size_t res_workspace(const ResLayout& P, int B, int nz, int mode) {
-  Bump ws(nullptr, ~size_t(0) >> 2);
+  Bump ws;
   ResWs W;
   res_carve(P, ws, B, nz, mode, W);
   return ws.off;
@@ -641,7 +579,7 @@ int trunk_fwd(const ResLayout& P, const ResPacked& K, const float* params, const
     ARDAE_TRY(blk_fwd(P.trunk[i], K.trunk[i], params, packed, cur, B, ACT_ELU, W.tb[i], st));
     cur = W.tb[i].out;
   }
-  RES_LAUNCH(nhwc_nchw_kernel, (int64_t)B * 512, cur, 16, 32, W.flat, (int64_t)B * 512, 0);
+  ARDAE_TRY(launch_nhwc_nchw(cur, B, 16, 32, W.flat, false, st));
   return blk_fwd(P.trunk[5], K.trunk[5], params, packed, W.flat, B, ACT_ELU, W.tb[5], st);
 }
 
@@ -717,7 +655,7 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
 int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* z, int R, ResWs& W, float* logits, hipStream_t st) {
   ARDAE_TRY(blk_fwd(P.dec[0], K.dec[0], params, packed, z, R, ACT_ELU, W.db[0], st));
   ARDAE_TRY(blk_fwd(P.dec[1], K.dec[1], params, packed, W.db[0].out, R, ACT_ELU, W.db[1], st));
-  RES_LAUNCH(nhwc_nchw_kernel, (int64_t)R * 512, W.db[1].out, 16, 32, W.d4, (int64_t)R * 512, 1);          // view(-1, 32, 4, 4) -> NHWC
+  ARDAE_TRY(launch_nhwc_nchw(W.db[1].out, R, 16, 32, W.d4, true, st));                                    // view(-1, 32, 4, 4) -> NHWC
   RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 64 * 32, W.d4, 4, 32, W.u8, (int64_t)R * 64 * 32);
   ARDAE_TRY(blk_fwd(P.dec[2], K.dec[2], params, packed, W.u8, R, ACT_ELU, W.db[2], st));
   ARDAE_TRY(blk_fwd(P.dec[3], K.dec[3], params, packed, W.db[2].out, R, ACT_ELU, W.db[3], st));
@@ -899,19 +837,16 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
   ARDAE_TRY(blk_bwd(P.dec[3], K.dec[3], packed, W.db[2].out, R, ACT_ELU, W.db[3], W.dbuf, W.da, W.sc, gd[3], W.wscratch, W.wscratch_floats, st));
   ARDAE_TRY(blk_bwd(P.dec[2], K.dec[2], packed, W.u8, R, ACT_ELU, W.db[2], W.da, W.dbuf, W.sc, gd[2], W.wscratch, W.wscratch_floats, st));            // -> d u8
   RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 16 * 32, W.dbuf, 4, 32, W.da, (int64_t)R * 16 * 32);                                                 // -> d d4 (NHWC)
-  RES_LAUNCH(nhwc_nchw_kernel, (int64_t)R * 512, W.da, 16, 32, W.dbuf, (int64_t)R * 512, 0);                                                          // -> NCHW-flat [R,512]
+  ARDAE_TRY(launch_nhwc_nchw(W.da, R, 16, 32, W.dbuf, false, st));                                                                                    // -> NCHW-flat [R,512]
   ARDAE_TRY(blk_bwd(P.dec[1], K.dec[1], packed, W.db[0].out, R, ACT_ELU, W.db[1], W.dbuf, W.da, W.sc, gd[1], W.wscratch, W.wscratch_floats, st));
   ARDAE_TRY(blk_bwd(P.dec[0], K.dec[0], packed, W.z, R, ACT_ELU, W.db[0], W.da, W.dbuf, W.sc, gd[0], W.wscratch, W.wscratch_floats, st));             // -> dz (decoder part) [R,zd]
   ARDAE_TRY(launch_axpy(W.dbuf, (int64_t)R * P.zd, 1.f, W.dzq, st));                                                                                 // dz total in W.dzq
   // ---- sampler backward -> W.dinp [B, cdim]
-  std::vector<WgradProblem> probs;
-  std::vector<std::pair<size_t, size_t>> dummy;
-  std::vector<WnBwdItem> plain;     // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
+  WgradList wl(grads);              // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
   if (P.kind == 5) {
     // encode.fc backwards, operator by operator: g = dL/d(output of the operator) [R, out]
     auto pw = [&](int M, int O, int I, const float* G, const float* X, int ldX, const WnGrad& g, int col0, int ldout, bool bias) {
-      push_wgrad(probs, dummy, M, O, I, G, X, ldX, g.dW + col0, ldout, bias ? g.db : nullptr);
-      probs.back().beta = g.beta;
+      wl.push(M, O, I, G, X, ldX, g.dW + col0, ldout, bias ? g.db : nullptr).beta = g.beta;
     };
     float* g = W.dzq;
     float* pp[2] = {W.dR0, W.dR1};
@@ -922,7 +857,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
       const float* out = i + 1 == (int)P.head.size() ? W.z : u.out;
       const float* x = i == 0 ? nullptr : W.hb[i - 1].out;        // the operator's input (post-activation output of its predecessor)
       float* dx = pp[i & 1];
-      if (o.act != ACT_NONE) RES_LAUNCH(mul_dact_kernel, (int64_t)R * o.out, g, out, o.act, g, (int64_t)R * o.out);
+      if (o.act != ACT_NONE) ARDAE_TRY(launch_mul_dact(g, out, o.act, g, (int64_t)R * o.out, st));
       if (o.res) {
         const Blk& b = o.b; const BlkPk& k = hk.k;
         const BlkGrad gr = gm.blk(b, k);
@@ -937,13 +872,13 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
           pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gr.s, 0, I0, false);                       // image columns of W_01
           pw(R, o.out, P.nd, dh, noise, P.nd, gr.a, P.cdim, I0, true);
           pw(B, o.out, P.cdim, W.dB1, W.inp, P.cdim, gr.a, 0, I0, false);
-          ARDAE_TRY(flush_wgrad(probs, W.wscratch, W.wscratch_floats, st));
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
           LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
           ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.s_bi, W.dB1, o.out, o.out, packed + k.a_bi, A, st));
         } else {
           if (!b.same) pw(R, o.out, o.in, g, x, o.in, gr.s, 0, o.in, true);
           pw(R, o.out, o.in, dh, x, o.in, gr.a, 0, o.in, true);
-          ARDAE_TRY(flush_wgrad(probs, W.wscratch, W.wscratch_floats, st));
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
           LinArgs A{}; A.Y = dx; A.ldY = o.in;
           if (!b.same) {
             ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.s.b, dh, o.out, o.out, packed + k.a.b, A, st));
@@ -959,12 +894,12 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
           ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rba [B, out]
           pw(R, o.out, P.nd, g, noise, P.nd, gl, P.cdim, l.in, true);
           pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gl, 0, l.in, false);
-          ARDAE_TRY(flush_wgrad(probs, W.wscratch, W.wscratch_floats, st));
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
           LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
           ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, A, st));
         } else {
           pw(R, o.out, o.in, g, x, o.in, gl, 0, l.in, true);
-          ARDAE_TRY(flush_wgrad(probs, W.wscratch, W.wscratch_floats, st));
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
           LinArgs A{}; A.Y = dx; A.ldY = o.in;
           ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, A, st));
         }
@@ -974,8 +909,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
   } else {
     const int ldn = P.nd + P.zd;
     auto plain_wgrad = [&](int M, const Lin& l, const float* G, const float* X, int ldX, int col0, int I, bool bias) {
-      push_wgrad(probs, dummy, M, l.out, I, G, X, ldX, grads + l.w + col0, l.in, bias ? grads + l.b : nullptr);
-      probs.back().beta = grads_beta;
+      wl.push(M, l.out, I, G, X, ldX, grads + l.w + col0, l.in, bias ? grads + l.b : nullptr).beta = grads_beta;
     };
     // z = mu + exp(lv/2) eps,  lv = spm4(lvr)
     float* dlv = W.sc.g;           // [R, zd]
@@ -985,7 +919,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
     plain_wgrad(R, P.lv, dlv, W.hh, P.cdim, 0, P.cdim, true);
     float* dhh = W.dR0;            // [R, cdim]
     { LinArgs A{}; A.Y = dhh; A.ldY = P.cdim; ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, P.cdim, W.dzq, P.zd, P.zd, packed + K.mu.b, dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
-    RES_LAUNCH(mul_dact_kernel, (int64_t)R * P.cdim, dhh, W.hh, (int)ACT_ELU, dhh, (int64_t)R * P.cdim);
+    ARDAE_TRY(launch_mul_dact(dhh, W.hh, ACT_ELU, dhh, (int64_t)R * P.cdim, st));
     ARDAE_TRY(launch_segment_sum(dhh, P.cdim, B, nz, P.cdim, 1.f, W.dB0, P.cdim, st));      // d rbh [B, cdim]
     plain_wgrad(R, P.efc, dhh, W.z0, P.nd, P.cdim, P.nd, true);                              // z0 columns + bias
     plain_wgrad(B, P.efc, W.dB0, W.inp, P.cdim, 0, P.cdim, false);                           // image columns
@@ -999,7 +933,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
     RES_LAUNCH(spm4_kernel, (int64_t)B * P.nd, W.lv0r, (const float*)W.dB2, W.dB2, (int64_t)B * P.nd, (int)P.clipped);
     plain_wgrad(B, P.mu0, W.dB1, W.inp, P.cdim, 0, P.cdim, true);
     plain_wgrad(B, P.lv0, W.dB2, W.inp, P.cdim, 0, P.cdim, true);
-    ARDAE_TRY(flush_wgrad(probs, W.wscratch, W.wscratch_floats, st));
+    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
     // d inp = d rbh W_fc[:, :cdim] + d mu0 W_mu0 + d lv0r W_lv0
     float* part = W.dflat;         // [B, cdim] scratch (cdim <= 512)
     { LinArgs A{}; A.Y = part; A.ldY = P.cdim;
@@ -1008,12 +942,11 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
       ARDAE_TRY(lin1(EPI_DACT, ACT_NONE, B, P.cdim, W.dB2, P.nd, P.nd, packed + K.lv0.b, A, st)); }
     (void)ldn;
   }
-  (void)plain;
   // ---- trunk backward
   std::vector<BlkGrad> gt(P.trunk.size());
   for (size_t i = 0; i < P.trunk.size(); ++i) gt[i] = gm.blk(P.trunk[i], K.trunk[i]);
   ARDAE_TRY(blk_bwd(P.trunk[5], K.trunk[5], packed, W.flat, B, ACT_ELU, W.tb[5], W.dinp, W.dflat, W.sc, gt[5], W.wscratch, W.wscratch_floats, st));
-  RES_LAUNCH(nhwc_nchw_kernel, (int64_t)B * 512, W.dflat, 16, 32, W.da, (int64_t)B * 512, 1);        // NCHW-flat gradient -> NHWC [B,4,4,32]
+  ARDAE_TRY(launch_nhwc_nchw(W.dflat, B, 16, 32, W.da, true, st));                                  // NCHW-flat gradient -> NHWC [B,4,4,32]
   float *cur = W.da, *nxt = W.dbuf;
   for (int i = 4; i >= 0; --i) {
     const float* xin = i == 0 ? W.x2 : W.tb[i - 1].out;
