@@ -10,9 +10,9 @@ size_t aux_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int 
 int aux_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st);
 // noise [B*nz, noise_dim + z_dim] (rows [eps0 | eps]) or null = zeros; hidden_out [B, 2 h] (nz == 1) or null
 int aux_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st);
+                     float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float* raw0);
 int aux_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                     float* out0, hipStream_t st, float* out1 = nullptr);
+                     float* out0, hipStream_t st, float* out1);
 int aux_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                           float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st);
 int aux_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,

@@ -25,13 +25,6 @@
 namespace ardae {
 namespace {
 
-#define PACK_PUSH(W_, ldw_, nout_, k_, tr_, out_) pack_items__.push_back(PackItem{W_, ldw_, nout_, k_, (tr_) ? 1 : 0, out_})
-
-struct Lin {
-  size_t w, b;
-  int out, in;
-};
-
 struct AuxLayout {
   int D, nd, h, zd, nl, act;
   int clip0, clip1;               // NormalDistribution.clip_logvar codes of the z0 / z heads (ardae_hip.h: ARDAE_MODEL_CLIP_*), 0 = none
@@ -50,10 +43,7 @@ struct AuxLayout {
       : D(d.input_dim), nd(d.noise_dim), h(d.h_dim), zd(d.z_dim), nl(d.n_layers), act(d.act),
         clip0((d.flags >> ARDAE_MODEL_CLIP_Z0_SHIFT) & 15), clip1((d.flags >> ARDAE_MODEL_CLIP_Z_SHIFT) & 15), toy(d.kind == 7) {
     size_t off = 0;
-    auto one = [&](int out, int in) {
-      Lin l; l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += out;
-      return l;
-    };
+    auto one = [&](int out, int in) { return next_lin(off, out, in); };
     for (int l = 0; l < nl; ++l) am.push_back(one(h, l == 0 ? D : h));
     mean0 = one(nd, h); logvar0 = one(nd, h);
     for (int l = 0; l < nl; ++l) ef.push_back(one(h, l == 0 ? D + nd : h));
@@ -68,25 +58,21 @@ struct AuxLayout {
 struct AuxPacked {
   std::vector<size_t> am_f, am_b, ef_f, ef_b, dec_f, dec_b;   // ef_f[0] / ef_b[0]: the z0 half of the first encoder layer
   size_t efx_f, mean0_f, mean0_b, logvar0_f, logvar0_b, mean_f, mean_b, logvar_f, logvar_b, logit_f, logit_b, logvarx_f = 0, logvarx_b = 0;
-  size_t total = 0;
-  explicit AuxPacked(const AuxLayout& P) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-    for (auto& l : P.am) { am_f.push_back(take(packed_floats(l.out, l.in))); am_b.push_back(take(packed_floats(l.in, l.out))); }
-    mean0_f = take(packed_floats(P.nd, P.h)); mean0_b = take(packed_floats(P.h, P.nd));
-    logvar0_f = take(packed_floats(P.nd, P.h)); logvar0_b = take(packed_floats(P.h, P.nd));
-    efx_f = take(packed_floats(P.h, P.D));
-    for (int l = 0; l < P.nl; ++l) {
-      const int in = l == 0 ? P.nd : P.h;
-      ef_f.push_back(take(packed_floats(P.h, in))); ef_b.push_back(take(packed_floats(in, P.h)));
-    }
-    mean_f = take(packed_floats(P.zd, P.h)); mean_b = take(packed_floats(P.h, P.zd));
-    logvar_f = take(packed_floats(P.zd, P.h)); logvar_b = take(packed_floats(P.h, P.zd));
-    for (auto& l : P.dec) { dec_f.push_back(take(packed_floats(l.out, l.in))); dec_b.push_back(take(packed_floats(l.in, l.out))); }
-    logit_f = take(packed_floats(P.D, P.h)); logit_b = take(packed_floats(P.h, P.D));
-    if (P.toy) { logvarx_f = take(packed_floats(P.D, P.h)); logvarx_b = take(packed_floats(P.h, P.D)); }
-    total = off;
+  AuxPacked(const AuxLayout& P, PackList& pl) {
+    const size_t nl = P.nl;
+    am_f.resize(nl); am_b.resize(nl); ef_f.resize(nl); ef_b.resize(nl); dec_f.resize(nl); dec_b.resize(nl);
+    for (size_t l = 0; l < nl; ++l) pl.pair(P.am[l], am_f[l], am_b[l]);
+    pl.pair(P.mean0, mean0_f, mean0_b); pl.pair(P.logvar0, logvar0_f, logvar0_b);
+    const Lin& e0 = P.ef[0];                                            // [h, D + nd]: image half (forward only) | z0 half
+    efx_f = pl.panel(e0.w, e0.in, P.h, P.D, false);
+    pl.pair(e0, ef_f[0], ef_b[0], P.D, P.nd);
+    for (size_t l = 1; l < nl; ++l) pl.pair(P.ef[l], ef_f[l], ef_b[l]);
+    pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
+    for (size_t l = 0; l < nl; ++l) pl.pair(P.dec[l], dec_f[l], dec_b[l]);
+    pl.pair(P.logit, logit_f, logit_b);
+    if (P.toy) pl.pair(P.logvarx, logvarx_f, logvarx_b);
   }
+  explicit AuxPacked(const AuxLayout& P, PackList&& sizing = PackList()) : AuxPacked(P, sizing) {}   // offsets only
 };
 
 struct AuxWs {
@@ -290,7 +276,11 @@ const float* noise_or_zero(const AuxLayout& P, const float* noise, int B, int nz
 }  // namespace
 
 size_t aux_model_param_floats(const ardae_model_desc& d) { return AuxLayout(d).total; }
-size_t aux_model_packed_floats(const ardae_model_desc& d) { return AuxPacked(AuxLayout(d)).total; }
+size_t aux_model_packed_floats(const ardae_model_desc& d) {
+  PackList pl;
+  AuxPacked(AuxLayout(d), pl);
+  return pl.total();
+}
 size_t aux_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   const AuxLayout P(d);
   if (mode == 2) return (size_t)P.nl * al64((size_t)B * nz * P.h);   // decode only
@@ -298,29 +288,13 @@ size_t aux_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int 
 }
 
 int aux_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  const AuxLayout P(d);
-  const AuxPacked K(P);
-  std::vector<PackItem> pack_items__;
-  auto both = [&](const Lin& l, size_t f, size_t b) {
-    PACK_PUSH(params + l.w, l.in, l.out, l.in, false, packed + f);
-    PACK_PUSH(params + l.w, l.in, l.in, l.out, true, packed + b);
-  };
-  for (int l = 0; l < P.nl; ++l) both(P.am[l], K.am_f[l], K.am_b[l]);
-  both(P.mean0, K.mean0_f, K.mean0_b); both(P.logvar0, K.logvar0_f, K.logvar0_b);
-  const Lin& e0 = P.ef[0];                                            // [h, D + nd]: image half | z0 half
-  PACK_PUSH(params + e0.w, e0.in, P.h, P.D, false, packed + K.efx_f);
-  PACK_PUSH(params + e0.w + P.D, e0.in, P.h, P.nd, false, packed + K.ef_f[0]);
-  PACK_PUSH(params + e0.w + P.D, e0.in, P.nd, P.h, true, packed + K.ef_b[0]);
-  for (int l = 1; l < P.nl; ++l) both(P.ef[l], K.ef_f[l], K.ef_b[l]);
-  both(P.mean, K.mean_f, K.mean_b); both(P.logvar, K.logvar_f, K.logvar_b);
-  for (int l = 0; l < P.nl; ++l) both(P.dec[l], K.dec_f[l], K.dec_b[l]);
-  both(P.logit, K.logit_f, K.logit_b);
-  if (P.toy) both(P.logvarx, K.logvarx_f, K.logvarx_b);
-  return launch_pack_batch(pack_items__.data(), (int)pack_items__.size(), st);
+  PackList pl(params, packed);
+  AuxPacked(AuxLayout(d), pl);
+  return pl.launch(st);
 }
 
 int aux_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st) {
+                     float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
   const AuxLayout P(d);
   const AuxPacked K(P);
   Bump ws(workspace, wsf);
@@ -341,27 +315,33 @@ int aux_model_encode(const ardae_model_desc& d, const float* params, const float
   return 0;
 }
 
+// decoder on R rows: the hidden layers into hid[1 .. nl], then the logit head (toy: mean and logvar heads) into out0 (, out1)
+static int decoder_fwd(const AuxLayout& P, const AuxPacked& K, const float* params, const float* packed, const float* z, int R, float* const* hid,
+                       float* out0, float* out1, hipStream_t st) {
+  const int h = P.h;
+  for (int l = 1; l <= P.nl; ++l) {
+    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = hid[l]; A.ldY = h;
+    ARDAE_TRY(lin1(EPI_ACT, P.act, R, h, l == 1 ? z : hid[l - 1], l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
+  }
+  LinArgs A{}; A.bias = params + P.logit.b; A.Y = out0; A.ldY = P.D;
+  ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, hid[P.nl], h, h, packed + K.logit_f, A, st));
+  if (P.toy) {
+    LinArgs A2{}; A2.bias = params + P.logvarx.b; A2.Y = out1; A2.ldY = P.D;
+    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, hid[P.nl], h, h, packed + K.logvarx_f, A2, st));
+  }
+  return 0;
+}
+
 int aux_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
                      float* out0, hipStream_t st, float* out1) {
   const AuxLayout P(d);
   const AuxPacked K(P);
   Bump ws(workspace, wsf);
-  const float* cur = z;
-  for (int l = 1; l <= P.nl; ++l) {
-    float* nxt = ws.take((size_t)R * P.h);
-    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = nxt; A.ldY = P.h;
-    ARDAE_TRY(lin1(EPI_ACT, P.act, R, P.h, cur, l == 1 ? P.zd : P.h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
-    cur = nxt;
-  }
+  std::vector<float*> hid(P.nl + 1, nullptr);
+  for (int l = 1; l <= P.nl; ++l) hid[l] = ws.take((size_t)R * P.h);
   ARDAE_CHECK_ARG(ws.ok, "aux_model_decode: workspace too small");
-  LinArgs A{}; A.bias = params + P.logit.b; A.Y = out0; A.ldY = P.D;
-  ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, cur, P.h, P.h, packed + K.logit_f, A, st));
-  if (P.toy) {
-    ARDAE_CHECK_ARG(out1, "aux_model_decode: the Gaussian decoder returns mean (out0) and logvar (out1)");
-    LinArgs A2{}; A2.bias = params + P.logvarx.b; A2.Y = out1; A2.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, cur, P.h, P.h, packed + K.logvarx_f, A2, st));
-  }
-  return 0;
+  ARDAE_CHECK_ARG(!P.toy || out1, "aux_model_decode: the Gaussian decoder returns mean (out0) and logvar (out1)");
+  return decoder_fwd(P, K, params, packed, z, R, hid.data(), out0, out1, st);
 }
 
 int aux_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
@@ -373,21 +353,10 @@ int aux_model_vae_forward(const ardae_model_desc& d, const float* params, const 
   carve(P, ws, B, nz, 1, W);
   ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_forward: workspace too small");
   ARDAE_CHECK_ARG(!P.toy || P.stage(nz) * P.stage(nz) == nz, "aux_model_vae_forward: ToyAuxIPVAE needs a square nz (got %d)", nz);
-  const int R = B * nz, h = P.h;      // z / decoder rows
+  const int R = B * nz;      // z / decoder rows
   ARDAE_TRY(sampler_fwd(P, K, params, packed, x, noise, B, nz, W, st));
   ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
-  for (int l = 1; l <= P.nl; ++l) {
-    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = W.dcd[l]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, P.act, R, h, l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
-  }
-  {
-    LinArgs A{}; A.bias = params + P.logit.b; A.Y = W.o; A.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, W.dcd[P.nl], h, h, packed + K.logit_f, A, st));
-  }
-  if (P.toy) {
-    LinArgs A{}; A.bias = params + P.logvarx.b; A.Y = W.o2; A.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, W.dcd[P.nl], h, h, packed + K.logvarx_f, A, st));
-  }
+  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, R, W.dcd.data(), W.o, W.o2, st));
   ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.o, W.o2, x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
   return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
 }

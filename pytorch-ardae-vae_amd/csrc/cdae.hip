@@ -27,15 +27,6 @@
 namespace ardae {
 namespace {
 
-// collect pack requests; flushed with one launch by PACK_FLUSH
-#define PACK_PUSH(W_, ldw_, nout_, k_, tr_, out_) pack_items__.push_back(PackItem{W_, ldw_, nout_, k_, (tr_) ? 1 : 0, out_})
-#define PACK_FLUSH(st_) ARDAE_TRY(launch_pack_batch(pack_items__.data(), (int)pack_items__.size(), st_))
-
-struct Lin {
-  size_t w, b;   // offsets (floats) into the flat parameter buffer
-  int out, in;
-};
-
 struct CdaeLayout {
   int kind, z, c, h, L, act;
   std::vector<Lin> ctx, inp, neg;   // ctx/inp: L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae)
@@ -44,10 +35,7 @@ struct CdaeLayout {
 
   explicit CdaeLayout(const ardae_cdae_desc& d) : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act) {
     size_t off = 0;
-    auto add = [&](std::vector<Lin>& v, int out, int in) {
-      Lin l; l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += out;
-      v.push_back(l);
-    };
+    auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
     for (int l = 0; l < L; ++l) add(ctx, h, l == 0 ? c : h);
     for (int l = 0; l < L; ++l) add(inp, h, l == 0 ? z : h);
     for (int l = 0; l < L; ++l) add(neg, h, l == 0 ? 2 * h + 1 : h);
@@ -61,31 +49,19 @@ struct PackedLayout {
   std::vector<size_t> ctx_f, ctx_b, inp_f, inp_b, neg_f, neg_b;   // neg_*[0] unused (W1 is split below)
   size_t w1a_f, w1a_b, w1c_f, w1c_b, w1s;
   size_t fc_f, fc_b;   // res kind only (dae.fc [z,h])
-  size_t total = 0;
-  explicit PackedLayout(const CdaeLayout& P) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-    for (int l = 0; l < P.L; ++l) {
-      ctx_f.push_back(take(packed_floats(P.ctx[l].out, P.ctx[l].in)));
-      ctx_b.push_back(take(packed_floats(P.ctx[l].in, P.ctx[l].out)));
-      inp_f.push_back(take(packed_floats(P.inp[l].out, P.inp[l].in)));
-      inp_b.push_back(take(packed_floats(P.inp[l].in, P.inp[l].out)));
-    }
-    neg_f.assign(P.L, 0); neg_b.assign(P.L, 0);
-    w1a_f = take(packed_floats(P.h, P.h)); w1a_b = take(packed_floats(P.h, P.h));
-    w1c_f = take(packed_floats(P.h, P.h)); w1c_b = take(packed_floats(P.h, P.h));
-    w1s = take(P.h);
-    for (int l = 1; l < P.L; ++l) {
-      neg_f[l] = take(packed_floats(P.h, P.h));
-      neg_b[l] = take(packed_floats(P.h, P.h));
-    }
+  PackedLayout(const CdaeLayout& P, PackList& pl) {
+    const size_t L = P.L;
+    ctx_f.resize(L); ctx_b.resize(L); inp_f.resize(L); inp_b.resize(L); neg_f.assign(L, 0); neg_b.assign(L, 0);
+    for (size_t l = 0; l < L; ++l) { pl.pair(P.ctx[l], ctx_f[l], ctx_b[l]); pl.pair(P.inp[l], inp_f[l], inp_b[l]); }
+    const Lin& W1 = P.neg[0];                        // [h, 2h + 1] = [W1a | W1c | w1s]
+    pl.pair(W1, w1a_f, w1a_b, 0, P.h);
+    pl.pair(W1, w1c_f, w1c_b, P.h, P.h);
+    w1s = pl.take(P.h);                              // the sigma column, gathered by cdae_pack_impl
+    for (size_t l = 1; l < L; ++l) pl.pair(P.neg[l], neg_f[l], neg_b[l]);
     fc_f = fc_b = 0;
-    if (P.kind == 1) {
-      fc_f = take(packed_floats(P.z, P.h));
-      fc_b = take(packed_floats(P.h, P.z));
-    }
-    total = off;
+    if (P.kind == 1) pl.pair(P.neg[L], fc_f, fc_b);
   }
+  explicit PackedLayout(const CdaeLayout& P, PackList&& sizing = PackList()) : PackedLayout(P, sizing) {}   // offsets only
 };
 
 int desc_ok(const ardae_cdae_desc* d) {
@@ -171,41 +147,18 @@ size_t workspace_floats(const CdaeLayout& P, int B, int S, bool need_grads) {
   return ws.off;
 }
 
-int cdae_pack_impl(const CdaeLayout& P, const PackedLayout& K, const float* params, float* packed, hipStream_t st) {
-  std::vector<PackItem> pack_items__;
-  for (int l = 0; l < P.L; ++l) {
-    PACK_PUSH(params + P.ctx[l].w, P.ctx[l].in, P.ctx[l].out, P.ctx[l].in, false, packed + K.ctx_f[l]);
-    PACK_PUSH(params + P.ctx[l].w, P.ctx[l].in, P.ctx[l].in, P.ctx[l].out, true, packed + K.ctx_b[l]);
-    PACK_PUSH(params + P.inp[l].w, P.inp[l].in, P.inp[l].out, P.inp[l].in, false, packed + K.inp_f[l]);
-    PACK_PUSH(params + P.inp[l].w, P.inp[l].in, P.inp[l].in, P.inp[l].out, true, packed + K.inp_b[l]);
-  }
-  const float* W1 = params + P.neg[0].w;
-  const int ld1 = 2 * P.h + 1;
-  PACK_PUSH(W1, ld1, P.h, P.h, false, packed + K.w1a_f);
-  PACK_PUSH(W1, ld1, P.h, P.h, true, packed + K.w1a_b);
-  PACK_PUSH(W1 + P.h, ld1, P.h, P.h, false, packed + K.w1c_f);
-  PACK_PUSH(W1 + P.h, ld1, P.h, P.h, true, packed + K.w1c_b);
-  ARDAE_TRY(launch_gather_strided(W1 + 2 * P.h, ld1, P.h, packed + K.w1s, st));
-  for (int l = 1; l < P.L; ++l) {
-    PACK_PUSH(params + P.neg[l].w, P.h, P.h, P.h, false, packed + K.neg_f[l]);
-    PACK_PUSH(params + P.neg[l].w, P.h, P.h, P.h, true, packed + K.neg_b[l]);
-  }
-  if (P.kind == 1) {
-    PACK_PUSH(params + P.neg[P.L].w, P.h, P.z, P.h, false, packed + K.fc_f);
-    PACK_PUSH(params + P.neg[P.L].w, P.h, P.h, P.z, true, packed + K.fc_b);
-  }
-  PACK_FLUSH(st);
-  return 0;
+int cdae_pack_impl(const CdaeLayout& P, const float* params, float* packed, hipStream_t st) {
+  PackList pl(params, packed);
+  const PackedLayout K(P, pl);
+  ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + 2 * P.h, P.neg[0].in, P.h, packed + K.w1s, st));
+  return pl.launch(st);
 }
 
-// one fused Linear launch with a single source
+// the arguments of one fused Linear launch with a single source (lin1 of host_util.h, without the launch)
 LinArgs lin_args(int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a) {
   a.M = M; a.Nout = Nout; a.nsrc = 1; a.act = act;
   a.src[0].x = x; a.src[0].ld = ldx; a.src[0].K = K; a.src[0].wp = wp;
   return a;
-}
-int lin(int epi, int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a, hipStream_t st) {
-  return launch_linear(lin_args(act, M, Nout, x, ldx, K, wp, a), epi, st);
 }
 
 // A run of consecutive N-row layers of one epilogue kind, each reading its predecessor's output: the longest prefixes that
@@ -296,7 +249,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   const bool few_rows = !a1_ready && linear_small_eligible(inp_layer(1), EPI_ACT);
   auto ctx_bias = [&]() {  // per-image bias of the first energy layer: cb = W1c c_L + d_1
     LinArgs A{}; A.bias = params + P.neg[0].b; A.Y = cb; A.ldY = h;
-    return lin(EPI_ACT, ACT_NONE, B, h, cL[L], h, h, packed + K.w1c_f, A, st);
+    return lin1(EPI_ACT, ACT_NONE, B, h, cL[L], h, h, packed + K.w1c_f, A, st);
   };
   LayerRun run(EPI_ACT, st);      // the forward N-row layers: A_1 (2) .. A_L, then W_1 .. W_L
   if (few_rows) {
@@ -345,19 +298,19 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     }
     if (!need_grads) {   // glogprob: g = r_1 A_1
       LinArgs A{}; A.Y = g; A.ldY = z;
-      return lin(EPI_ACT, ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A, st);
+      return lin1(EPI_ACT, ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A, st);
     }
     LinArgs A{}; A.sigma = sigma; A.eps = eps; A.ldeps = z; A.scale = inv_nz; A.Y = g; A.ldY = z; A.Y2 = gbar; A.ldY2 = z;
     A.tile_loss = tile_loss;
-    ARDAE_TRY(lin(EPI_DAE_LOSS, ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A, st));
+    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A, st));
   } else {
     if (!need_grads) {
       LinArgs A{}; A.bias = params + P.neg[L].b; A.Y = g; A.ldY = z;
-      return lin(EPI_ACT, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st);
+      return lin1(EPI_ACT, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st);
     }
     LinArgs A{}; A.bias = params + P.neg[L].b; A.sigma = sigma; A.eps = eps; A.ldeps = z; A.scale = inv_nz; A.Y = g; A.ldY = z;
     A.Y2 = gbar; A.ldY2 = z; A.tile_loss = tile_loss;
-    ARDAE_TRY(lin(EPI_DAE_LOSS, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st));
+    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st));
   }
   ARDAE_TRY(launch_sum_scale(tile_loss, ltiles, inv_nz, loss, st));
 
@@ -402,30 +355,30 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     // direct-score variant: a single ordinary backward from gbar
     {
       LinArgs A{}; A.S = hh[L]; A.ldS = h; A.Y = qhat[L]; A.ldY = h;
-      ARDAE_TRY(lin(EPI_DACT, act, N, h, gbar, z, z, packed + K.fc_b, A, st));
+      ARDAE_TRY(lin1(EPI_DACT, act, N, h, gbar, z, z, packed + K.fc_b, A, st));
     }
     for (int l = L; l >= 2; --l) {
       LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = qhat[l - 1]; A.ldY = h;
-      ARDAE_TRY(lin(EPI_DACT, act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A, st));
+      ARDAE_TRY(lin1(EPI_DACT, act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A, st));
     }
     {
       LinArgs A{}; A.S = a[L]; A.ldS = h; A.Y = phat[L]; A.ldY = h;
-      ARDAE_TRY(lin(EPI_DACT, act, N, h, qhat[1], h, h, packed + K.w1a_b, A, st));
+      ARDAE_TRY(lin1(EPI_DACT, act, N, h, qhat[1], h, h, packed + K.w1a_b, A, st));
     }
     for (int l = L; l >= 2; --l) {
       LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = phat[l - 1]; A.ldY = h;
-      ARDAE_TRY(lin(EPI_DACT, act, N, h, phat[l], h, h, packed + K.inp_b[l - 1], A, st));
+      ARDAE_TRY(lin1(EPI_DACT, act, N, h, phat[l], h, h, packed + K.inp_b[l - 1], A, st));
     }
   }
   // ctx branch: reduce over the S samples of each image first, then B-row back-prop
   ARDAE_TRY(launch_segment_sum(qhat[1], h, B, S, h, 1.0f, Qsum, h, st));
   {
     LinArgs A{}; A.S = cL[L]; A.ldS = h; A.Y = chat[L]; A.ldY = h;
-    ARDAE_TRY(lin(EPI_DACT, act, B, h, Qsum, h, h, packed + K.w1c_b, A, st));
+    ARDAE_TRY(lin1(EPI_DACT, act, B, h, Qsum, h, h, packed + K.w1c_b, A, st));
   }
   for (int l = L; l >= 2; --l) {
     LinArgs A{}; A.S = cL[l - 1]; A.ldS = h; A.Y = chat[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin(EPI_DACT, act, B, h, chat[l], h, h, packed + K.ctx_b[l - 1], A, st));
+    ARDAE_TRY(lin1(EPI_DACT, act, B, h, chat[l], h, h, packed + K.ctx_b[l - 1], A, st));
   }
 
   // -------------------------------------------------------------------- weight gradients: one batched launch (cdae_wgrads)
@@ -445,7 +398,9 @@ size_t ardae_cdae_param_floats(const ardae_cdae_desc* d) {
 }
 size_t ardae_cdae_packed_floats(const ardae_cdae_desc* d) {
   if (desc_ok(d) != 0) return 0;
-  return PackedLayout(CdaeLayout(*d)).total;
+  PackList pl;
+  PackedLayout(CdaeLayout(*d), pl);
+  return pl.total();
 }
 size_t ardae_cdae_workspace_floats(const ardae_cdae_desc* d, int B, int S, int need_grads) {
   if (desc_ok(d) != 0 || B <= 0 || S <= 0) return 0;
@@ -454,8 +409,7 @@ size_t ardae_cdae_workspace_floats(const ardae_cdae_desc* d, int B, int S, int n
 int ardae_cdae_pack(const ardae_cdae_desc* d, const float* params, float* packed, void* stream) {
   ARDAE_TRY(desc_ok(d));
   ARDAE_CHECK_ARG(params && packed, "cdae_pack: null pointer");
-  const CdaeLayout P(*d);
-  return cdae_pack_impl(P, PackedLayout(P), params, packed, (hipStream_t)stream);
+  return cdae_pack_impl(CdaeLayout(*d), params, packed, (hipStream_t)stream);
 }
 int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar,
                           const float* sigma, const float* eps, const float* ctx, int B, int S, float* workspace,

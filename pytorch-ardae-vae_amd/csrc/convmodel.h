@@ -8,10 +8,11 @@ size_t conv_model_param_floats(const ardae_model_desc& d);
 size_t conv_model_packed_floats(const ardae_model_desc& d);
 size_t conv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode);
 int conv_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st);
+// (every family has the same eight signatures, csrc/model.hip: hidden_out / raw0 / out1 are NULL where a family has no such thing)
 int conv_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                      int nz, float* workspace, size_t wsf, float* z_out, hipStream_t st);
+                      int nz, float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float* raw0);
 int conv_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace,
-                      size_t wsf, float* out0, hipStream_t st);
+                      size_t wsf, float* out0, hipStream_t st, float* out1);
 int conv_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                            int nz, float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st);
 int conv_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
@@ -23,9 +24,9 @@ size_t auxconv_model_packed_floats(const ardae_model_desc& d);
 size_t auxconv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode);
 int auxconv_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st);
 int auxconv_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                         float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st);
+                         float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float* raw0);
 int auxconv_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                         float* out0, hipStream_t st);
+                         float* out0, hipStream_t st, float* out1);
 int auxconv_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                               int nz, float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st);
 int auxconv_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,

@@ -17,10 +17,6 @@
 namespace ardae {
 namespace {
 
-// collect pack requests; flushed with one launch by PACK_FLUSH
-#define PACK_PUSH(W_, ldw_, nout_, k_, tr_, out_) pack_items__.push_back(PackItem{W_, ldw_, nout_, k_, (tr_) ? 1 : 0, out_})
-#define PACK_FLUSH(st_) ARDAE_TRY(launch_pack_batch(pack_items__.data(), (int)pack_items__.size(), st_))
-
 // ------------------------------------------------------------------------------------------------ data-movement kernels
 // cols[(b*OH+oh)*OW+ow][c*25+kh*5+kw] = x[b][2oh-2+kh][2ow-2+kw][c]  (0 outside H x W); x is NHWC [B,H,W,C]
 __global__ void im2col_s2_kernel(const float* __restrict__ x, int H, int W, int C, int OH, int OW, float* __restrict__ cols, int64_t total) {
@@ -78,8 +74,7 @@ __global__ void fill_kernel(float* __restrict__ p, float v, int64_t n) {
 }
 
 // ------------------------------------------------------------------------------------------------ layout
-struct Lin { size_t w, b; int out, in; };   // weight viewed as [out, in] (convs: [O, C*25]; deconvs: [in_ch, out_ch*25])
-
+// a Lin's weight is viewed as [out, in] (convs: [O, C*25]; deconvs: [in_ch, out_ch*25], with out_ch bias entries)
 struct ConvLayout {
   int nd, zd, act;
   Lin conv[3], fc4, fc5, dfc[2], dcv[3];
@@ -87,7 +82,7 @@ struct ConvLayout {
   ConvLayout() : nd(0), zd(0), act(0), total(0) {}     // decoder-only view filled by AuxConvLayout
   explicit ConvLayout(const ardae_model_desc& d) : nd(d.noise_dim), zd(d.z_dim), act(d.act) {
     size_t off = 0;
-    auto add = [&](Lin& l, int out, int in, int nbias) { l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += nbias; };
+    auto add = [&](Lin& l, int out, int in, int nbias) { l = next_lin(off, out, in, nbias); };
     add(conv[0], 16, 1 * 25, 16); add(conv[1], 32, 16 * 25, 32); add(conv[2], 32, 32 * 25, 32);
     add(fc4, 800, 512 + nd, 800); add(fc5, zd, 800, zd);
     add(dfc[0], 300, zd, 300); add(dfc[1], 512, 300, 512);
@@ -97,17 +92,23 @@ struct ConvLayout {
 };
 
 struct ConvPacked {
-  size_t conv_f[3], conv_b[3], fc4i_f, fc4i_b, fc4n_f, fc5_f, fc5_b, dfc_f[2], dfc_b[2], dcv_f[3], dcv_b[3], total;
-  ConvPacked() : total(0) {}
-  explicit ConvPacked(const ConvLayout& P) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += al64(n); return o; };
-    for (int i = 0; i < 3; ++i) { conv_f[i] = take(packed_floats(P.conv[i].out, P.conv[i].in)); conv_b[i] = take(packed_floats(P.conv[i].in, P.conv[i].out)); }
-    fc4i_f = take(packed_floats(800, 512)); fc4i_b = take(packed_floats(512, 800)); fc4n_f = take(packed_floats(800, P.nd));
-    fc5_f = take(packed_floats(P.zd, 800)); fc5_b = take(packed_floats(800, P.zd));
-    for (int i = 0; i < 2; ++i) { dfc_f[i] = take(packed_floats(P.dfc[i].out, P.dfc[i].in)); dfc_b[i] = take(packed_floats(P.dfc[i].in, P.dfc[i].out)); }
-    for (int i = 0; i < 3; ++i) { dcv_f[i] = take(packed_floats(P.dcv[i].in, P.dcv[i].out)); dcv_b[i] = take(packed_floats(P.dcv[i].out, P.dcv[i].in)); }
-    total = off;
+  size_t conv_f[3], conv_b[3], fc4i_f, fc4i_b, fc4n_f, fc5_f, fc5_b, dfc_f[2], dfc_b[2], dcv_f[3], dcv_b[3];
+  ConvPacked() {}     // decoder-only view filled by AuxConvPacked
+  ConvPacked(const ConvLayout& P, PackList& pl) {
+    for (int i = 0; i < 3; ++i) pl.pair(P.conv[i], conv_f[i], conv_b[i]);
+    pl.pair(P.fc4, fc4i_f, fc4i_b, 0, 512);                            // [800, 512 + nd]: image half both ways, noise half forward
+    fc4n_f = pl.panel(P.fc4.w + 512, P.fc4.in, 800, P.nd, false);
+    pl.pair(P.fc5, fc5_f, fc5_b);
+    decoder_panels(P, pl);
+  }
+  explicit ConvPacked(const ConvLayout& P, PackList&& sizing = PackList()) : ConvPacked(P, sizing) {}   // offsets only
+  // the decoder's five operators (shared with the hierarchical conv model, which reserves them at its own offsets)
+  void decoder_panels(const ConvLayout& P, PackList& pl) {
+    for (int i = 0; i < 2; ++i) pl.pair(P.dfc[i], dfc_f[i], dfc_b[i]);
+    for (int i = 0; i < 3; ++i) {   // ConvTranspose2d weight [in, out*25]: forward = X . W (transposed pack), backward-data = dC . W^T (natural)
+      dcv_f[i] = pl.panel(P.dcv[i].w, P.dcv[i].in, P.dcv[i].in, P.dcv[i].out, true);
+      dcv_b[i] = pl.panel(P.dcv[i].w, P.dcv[i].in, P.dcv[i].out, P.dcv[i].in, false);
+    }
   }
 };
 
@@ -300,33 +301,18 @@ size_t conv_workspace(const ConvLayout& P, int B, int nz, int mode) {
 
 // ------------------------------------------------------------------------------------------------ entry points (kind == 2)
 size_t conv_model_param_floats(const ardae_model_desc& d) { return ConvLayout(d).total; }
-size_t conv_model_packed_floats(const ardae_model_desc& d) { return ConvPacked(ConvLayout(d)).total; }
-size_t conv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return conv_workspace(ConvLayout(d), B, nz, mode); }
+size_t conv_model_packed_floats(const ardae_model_desc& d) {
+  PackList pl;
+  ConvPacked(ConvLayout(d), pl);
+  return pl.total();
+}
+// mode 3 (encode_pair: two encode passes over one workspace) is mode 0
+size_t conv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return conv_workspace(ConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
 
 int conv_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  std::vector<PackItem> pack_items__;
-  const ConvLayout P(d);
-  const ConvPacked K(P);
-  for (int i = 0; i < 3; ++i) {
-    PACK_PUSH(params + P.conv[i].w, P.conv[i].in, P.conv[i].out, P.conv[i].in, false, packed + K.conv_f[i]);
-    PACK_PUSH(params + P.conv[i].w, P.conv[i].in, P.conv[i].in, P.conv[i].out, true, packed + K.conv_b[i]);
-  }
-  const int ld4 = 512 + P.nd;
-  PACK_PUSH(params + P.fc4.w, ld4, 800, 512, false, packed + K.fc4i_f);
-  PACK_PUSH(params + P.fc4.w, ld4, 512, 800, true, packed + K.fc4i_b);
-  PACK_PUSH(params + P.fc4.w + 512, ld4, 800, P.nd, false, packed + K.fc4n_f);
-  PACK_PUSH(params + P.fc5.w, 800, P.zd, 800, false, packed + K.fc5_f);
-  PACK_PUSH(params + P.fc5.w, 800, 800, P.zd, true, packed + K.fc5_b);
-  for (int i = 0; i < 2; ++i) {
-    PACK_PUSH(params + P.dfc[i].w, P.dfc[i].in, P.dfc[i].out, P.dfc[i].in, false, packed + K.dfc_f[i]);
-    PACK_PUSH(params + P.dfc[i].w, P.dfc[i].in, P.dfc[i].in, P.dfc[i].out, true, packed + K.dfc_b[i]);
-  }
-  for (int i = 0; i < 3; ++i) {   // ConvTranspose2d weight [in, out*25]: forward = X . W (transposed pack), backward-data = dC . W^T (natural)
-    PACK_PUSH(params + P.dcv[i].w, P.dcv[i].in, P.dcv[i].in, P.dcv[i].out, true, packed + K.dcv_f[i]);
-    PACK_PUSH(params + P.dcv[i].w, P.dcv[i].in, P.dcv[i].out, P.dcv[i].in, false, packed + K.dcv_b[i]);
-  }
-  PACK_FLUSH(st);
-  return 0;
+  PackList pl(params, packed);
+  ConvPacked(ConvLayout(d), pl);
+  return pl.launch(st);
 }
 
 static const float* zero_noise(Bump& ws, const ConvLayout& P, int B, int nz, hipStream_t st) {
@@ -336,7 +322,7 @@ static const float* zero_noise(Bump& ws, const ConvLayout& P, int B, int nz, hip
 }
 
 int conv_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                      int nz, float* workspace, size_t wsf, float* z_out, hipStream_t st) {
+                      int nz, float* workspace, size_t wsf, float* z_out, float*, hipStream_t st, const float*) {
   const ConvLayout P(d);
   const ConvPacked K(P);
   Bump ws(workspace, wsf);
@@ -348,7 +334,7 @@ int conv_model_encode(const ardae_model_desc& d, const float* params, const floa
 }
 
 int conv_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace,
-                      size_t wsf, float* out0, hipStream_t st) {
+                      size_t wsf, float* out0, hipStream_t st, float*) {
   const ConvLayout P(d);
   const ConvPacked K(P);
   Bump ws(workspace, wsf);
@@ -419,7 +405,7 @@ struct AuxConvLayout {
   size_t total;
   explicit AuxConvLayout(const ardae_model_desc& d) : nd(d.noise_dim), zd(d.z_dim), act(d.act) {
     size_t off = 0;
-    auto add = [&](Lin& l, int out, int in, int nbias) { l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += nbias; };
+    auto add = [&](Lin& l, int out, int in, int nbias) { l = next_lin(off, out, in, nbias); };
     add(aconv[0], 16, 25, 16); add(aconv[1], 32, 400, 32); add(aconv[2], 32, 800, 32);
     add(afc, 800, 512, 800); add(mean0, nd, 800, nd); add(logvar0, nd, 800, nd);
     add(econv[0], 16, 25, 16); add(econv[1], 32, 400, 32); add(econv[2], 32, 800, 32);
@@ -433,24 +419,18 @@ struct AuxConvLayout {
 
 struct AuxConvPacked {
   size_t aconv_f[3], aconv_b[3], afc_f, afc_b, mean0_f, mean0_b, logvar0_f, logvar0_b, econv_f[3], econv_b[3], efci_f, efci_b, efcn_f, efcn_b,
-      mean_f, mean_b, logvar_f, logvar_b, total;
+      mean_f, mean_b, logvar_f, logvar_b;
   ConvPacked dec;
-  explicit AuxConvPacked(const AuxConvLayout& P) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += al64(n); return o; };
-    for (int i = 0; i < 3; ++i) { aconv_f[i] = take(packed_floats(P.aconv[i].out, P.aconv[i].in)); aconv_b[i] = take(packed_floats(P.aconv[i].in, P.aconv[i].out)); }
-    afc_f = take(packed_floats(800, 512)); afc_b = take(packed_floats(512, 800));
-    mean0_f = take(packed_floats(P.nd, 800)); mean0_b = take(packed_floats(800, P.nd));
-    logvar0_f = take(packed_floats(P.nd, 800)); logvar0_b = take(packed_floats(800, P.nd));
-    for (int i = 0; i < 3; ++i) { econv_f[i] = take(packed_floats(P.econv[i].out, P.econv[i].in)); econv_b[i] = take(packed_floats(P.econv[i].in, P.econv[i].out)); }
-    efci_f = take(packed_floats(800, 512)); efci_b = take(packed_floats(512, 800));
-    efcn_f = take(packed_floats(800, P.nd)); efcn_b = take(packed_floats(P.nd, 800));
-    mean_f = take(packed_floats(P.zd, 800)); mean_b = take(packed_floats(800, P.zd));
-    logvar_f = take(packed_floats(P.zd, 800)); logvar_b = take(packed_floats(800, P.zd));
-    for (int i = 0; i < 2; ++i) { dec.dfc_f[i] = take(packed_floats(P.dec.dfc[i].out, P.dec.dfc[i].in)); dec.dfc_b[i] = take(packed_floats(P.dec.dfc[i].in, P.dec.dfc[i].out)); }
-    for (int i = 0; i < 3; ++i) { dec.dcv_f[i] = take(packed_floats(P.dec.dcv[i].in, P.dec.dcv[i].out)); dec.dcv_b[i] = take(packed_floats(P.dec.dcv[i].out, P.dec.dcv[i].in)); }
-    total = off;
+  AuxConvPacked(const AuxConvLayout& P, PackList& pl) {
+    for (int i = 0; i < 3; ++i) pl.pair(P.aconv[i], aconv_f[i], aconv_b[i]);
+    pl.pair(P.afc, afc_f, afc_b); pl.pair(P.mean0, mean0_f, mean0_b); pl.pair(P.logvar0, logvar0_f, logvar0_b);
+    for (int i = 0; i < 3; ++i) pl.pair(P.econv[i], econv_f[i], econv_b[i]);
+    pl.pair(P.efc, efci_f, efci_b, 0, 512);                            // [800, 512 + nd]: image half | z0 half
+    pl.pair(P.efc, efcn_f, efcn_b, 512, P.nd);
+    pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
+    dec.decoder_panels(P.dec, pl);
   }
+  explicit AuxConvPacked(const AuxConvLayout& P, PackList&& sizing = PackList()) : AuxConvPacked(P, sizing) {}   // offsets only
 };
 
 struct AuxConvWs {
@@ -563,36 +543,21 @@ int aux_sampler_fwd(const AuxConvLayout& P, const AuxConvPacked& K, const float*
 }  // namespace
 
 size_t auxconv_model_param_floats(const ardae_model_desc& d) { return AuxConvLayout(d).total; }
-size_t auxconv_model_packed_floats(const ardae_model_desc& d) { return AuxConvPacked(AuxConvLayout(d)).total; }
+size_t auxconv_model_packed_floats(const ardae_model_desc& d) {
+  PackList pl;
+  AuxConvPacked(AuxConvLayout(d), pl);
+  return pl.total();
+}
 size_t auxconv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return aux_workspace(AuxConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
 
 int auxconv_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  std::vector<PackItem> pack_items__;
-  const AuxConvLayout P(d);
-  const AuxConvPacked K(P);
-  auto both = [&](const Lin& l, size_t f, size_t b) {
-    PACK_PUSH(params + l.w, l.in, l.out, l.in, false, packed + f);
-    PACK_PUSH(params + l.w, l.in, l.in, l.out, true, packed + b);
-  };
-  for (int i = 0; i < 3; ++i) { both(P.aconv[i], K.aconv_f[i], K.aconv_b[i]); both(P.econv[i], K.econv_f[i], K.econv_b[i]); }
-  both(P.afc, K.afc_f, K.afc_b); both(P.mean0, K.mean0_f, K.mean0_b); both(P.logvar0, K.logvar0_f, K.logvar0_b);
-  const int lde = 512 + P.nd;
-  PACK_PUSH(params + P.efc.w, lde, 800, 512, false, packed + K.efci_f);
-  PACK_PUSH(params + P.efc.w, lde, 512, 800, true, packed + K.efci_b);
-  PACK_PUSH(params + P.efc.w + 512, lde, 800, P.nd, false, packed + K.efcn_f);
-  PACK_PUSH(params + P.efc.w + 512, lde, P.nd, 800, true, packed + K.efcn_b);
-  both(P.mean, K.mean_f, K.mean_b); both(P.logvar, K.logvar_f, K.logvar_b);
-  for (int i = 0; i < 2; ++i) both(P.dec.dfc[i], K.dec.dfc_f[i], K.dec.dfc_b[i]);
-  for (int i = 0; i < 3; ++i) {   // ConvTranspose2d weight [in, out*25] (see conv_model_pack)
-    PACK_PUSH(params + P.dec.dcv[i].w, P.dec.dcv[i].in, P.dec.dcv[i].in, P.dec.dcv[i].out, true, packed + K.dec.dcv_f[i]);
-    PACK_PUSH(params + P.dec.dcv[i].w, P.dec.dcv[i].in, P.dec.dcv[i].out, P.dec.dcv[i].in, false, packed + K.dec.dcv_b[i]);
-  }
-  PACK_FLUSH(st);
-  return 0;
+  PackList pl(params, packed);
+  AuxConvPacked(AuxConvLayout(d), pl);
+  return pl.launch(st);
 }
 
 int auxconv_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                         float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st) {
+                         float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
   const AuxConvLayout P(d);
   const AuxConvPacked K(P);
   Bump ws(workspace, wsf);
@@ -615,7 +580,7 @@ int auxconv_model_encode(const ardae_model_desc& d, const float* params, const f
 }
 
 int auxconv_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                         float* out0, hipStream_t st) {
+                         float* out0, hipStream_t st, float*) {
   const AuxConvLayout P(d);
   const AuxConvPacked K(P);
   Bump ws(workspace, wsf);

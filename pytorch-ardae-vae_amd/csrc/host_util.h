@@ -1,6 +1,6 @@
 // Host-side helpers shared by the model families (model / convmodel / auxmodel / resmodel .hip) and cdae.hip: the bump
 // allocator that carves a workspace arena, one-/two-source linear launches, and the list of weight-gradient problems a
-// backward pass hands to launch_wgrad_batch.
+// backward pass hands to launch_wgrad_batch, and the list of weight panels a network's packed buffer is made of.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -41,6 +41,46 @@ inline int lin2(int epi, int act, int M, int Nout, const float* x0, int ld0, int
   a.src[1].x = x1; a.src[1].ld = ld1; a.src[1].K = K1; a.src[1].wp = wp1;
   return launch_linear(a, epi, st);
 }
+
+// A Linear in the flat parameter buffer: weight [out, in] at w, bias at b (offsets in floats)
+struct Lin { size_t w, b; int out, in; };
+// the next Linear at parameter offset `off` (advanced past the weight and nbias bias entries; default: one per output)
+inline Lin next_lin(size_t& off, int out, int in, int nbias = -1) {
+  Lin l; l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += nbias < 0 ? out : nbias;
+  return l;
+}
+
+// The panels of a packed-weight buffer, written ONCE per network: the constructor of a family's *Packed struct reserves
+// every panel through this list and keeps the returned offsets.  Over the real (params, packed) pointers each reservation
+// also records the pack_batch item that fills it, and launch() packs them all; over null pointers (the sizing pass of
+// *_packed_floats and of every entry point that only needs the offsets) it only counts, and total() is the buffer's size.
+struct PackList {
+  std::vector<PackItem> items;
+  const float* params; float* packed;
+  size_t off = 0;
+  PackList() : params(nullptr), packed(nullptr) {}   // sizing pass
+  PackList(const float* params_, float* packed_) : params(params_), packed(packed_) {}
+  // a raw reservation (filled by something other than the pack launch)
+  size_t take(size_t n) { size_t o = off; off += al64(n); return o; }
+  // the panel of W[nout, k] (transpose: of W[k, nout]^T) with leading dimension ldw; W starts src floats into params, or
+  // (src_in_packed: a weight composed there by an earlier launch on the same stream) into the packed buffer itself
+  size_t panel(size_t src, int ldw, int nout, int k, bool transpose, bool src_in_packed = false) {
+    const size_t o = take(packed_floats(nout, k));
+    if (packed) {
+      if (items.empty()) items.reserve(PACK_BATCH_MAX);   // one allocation for all but the residual-conv lists
+      items.push_back(PackItem{(src_in_packed ? packed : params) + src, ldw, nout, k, transpose ? 1 : 0, packed + o});
+    }
+    return o;
+  }
+  // the common pair: the forward panel of l's columns [col0, col0 + k) (default: all of them), then its transpose
+  void pair(const Lin& l, size_t& f, size_t& b, int col0 = 0, int k = 0) {
+    if (k == 0) k = l.in;
+    f = panel(l.w + col0, l.in, l.out, k, false);
+    b = panel(l.w + col0, l.in, k, l.out, true);
+  }
+  size_t total() const { return off; }
+  int launch(hipStream_t st) { return launch_pack_batch(items.data(), (int)items.size(), st); }
+};
 
 // The weight-gradient problems of one backward, written ONCE per family: the backward pushes them with its real buffers,
 // assigns their scratch out of the arena and launches; *_workspace_floats runs the same code over a sizing Bump with null

@@ -21,15 +21,6 @@
 namespace ardae {
 namespace {
 
-// collect pack requests; flushed with one launch by PACK_FLUSH
-#define PACK_PUSH(W_, ldw_, nout_, k_, tr_, out_) pack_items__.push_back(PackItem{W_, ldw_, nout_, k_, (tr_) ? 1 : 0, out_})
-#define PACK_FLUSH(st_) ARDAE_TRY(launch_pack_batch(pack_items__.data(), (int)pack_items__.size(), st_))
-
-struct Lin {
-  size_t w, b;
-  int out, in;
-};
-
 struct ModelLayout {
   int kind, D, nd, h, zd, nl, act;
   std::vector<Lin> inp, stack, dec, heads;
@@ -38,10 +29,7 @@ struct ModelLayout {
   explicit ModelLayout(const ardae_model_desc& d)
       : kind(d.kind), D(d.input_dim), nd(d.noise_dim), h(d.h_dim), zd(d.z_dim), nl(d.n_layers), act(d.act) {
     size_t off = 0;
-    auto add = [&](std::vector<Lin>& v, int out, int in) {
-      Lin l; l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += out;
-      v.push_back(l);
-    };
+    auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
     const int n_inp = kind == 0 ? nl + 2 : nl;
     for (int l = 0; l < n_inp; ++l) add(inp, h, l == 0 ? D : h);
     if (kind == 0) {
@@ -59,22 +47,26 @@ struct ModelLayout {
   }
 };
 
+// offsets into the packed buffer, reserved (and, over a real PackList, filled) in this order
 struct ModelPacked {
   std::vector<size_t> inp_f, inp_b, sh_f, sh_b, sn_f, dec_f, dec_b, head_f, head_b;
-  size_t total = 0;
-  explicit ModelPacked(const ModelLayout& P) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-    for (auto& l : P.inp) { inp_f.push_back(take(packed_floats(l.out, l.in))); inp_b.push_back(take(packed_floats(l.in, l.out))); }
-    for (size_t i = 0; i < P.stack.size(); ++i) {
-      sh_f.push_back(take(packed_floats(P.stack[i].out, P.h)));
-      sh_b.push_back(take(packed_floats(P.h, P.stack[i].out)));
-      sn_f.push_back(P.stack_noise[i] ? take(packed_floats(P.stack[i].out, P.nd)) : 0);
+  ModelPacked(const ModelLayout& P, PackList& pl) {
+    auto pairs = [&](const std::vector<Lin>& v, std::vector<size_t>& f, std::vector<size_t>& b) {
+      f.resize(v.size()); b.resize(v.size());
+      for (size_t i = 0; i < v.size(); ++i) pl.pair(v[i], f[i], b[i]);
+    };
+    pairs(P.inp, inp_f, inp_b);
+    const size_t ns = P.stack.size();
+    sh_f.resize(ns); sh_b.resize(ns); sn_f.assign(ns, 0);
+    for (size_t i = 0; i < ns; ++i) {           // [out, h | nd]: hidden columns both ways, noise columns forward
+      const Lin& l = P.stack[i];
+      pl.pair(l, sh_f[i], sh_b[i], 0, P.h);
+      if (P.stack_noise[i]) sn_f[i] = pl.panel(l.w + P.h, l.in, l.out, P.nd, false);
     }
-    for (auto& l : P.dec) { dec_f.push_back(take(packed_floats(l.out, l.in))); dec_b.push_back(take(packed_floats(l.in, l.out))); }
-    for (auto& l : P.heads) { head_f.push_back(take(packed_floats(l.out, l.in))); head_b.push_back(take(packed_floats(l.in, l.out))); }
-    total = off;
+    pairs(P.dec, dec_f, dec_b);
+    pairs(P.heads, head_f, head_b);
   }
+  explicit ModelPacked(const ModelLayout& P, PackList&& sizing = PackList()) : ModelPacked(P, sizing) {}   // offsets only
 };
 
 int desc_ok(const ardae_model_desc* d) {
@@ -246,97 +238,31 @@ size_t encode_pair_extra(const ModelLayout& P, int B) {
   return (P.stack.size() - 1) * al64((size_t)B * P.h) + al64((size_t)B * P.nd);
 }
 
-}  // namespace
-}  // namespace ardae
-
-using namespace ardae;
-
-extern "C" {
-
-size_t ardae_model_param_floats(const ardae_model_desc* d) {
-  if (desc_ok(d)) return 0;
-  if ((d->kind == 5 || d->kind == 6)) return res_model_param_floats(*d);
-  if (d->kind == 4) return auxconv_model_param_floats(*d);
-  if ((d->kind == 3 || d->kind == 7)) return aux_model_param_floats(*d);
-  return d->kind == 2 ? conv_model_param_floats(*d) : ModelLayout(*d).total;
+// ------------------------------------------------------------------------------------------------ kinds 0 / 1 as a family
+size_t mlp_param_floats(const ardae_model_desc& d) { return ModelLayout(d).total; }
+size_t mlp_packed_floats(const ardae_model_desc& d) {
+  PackList pl;
+  ModelPacked(ModelLayout(d), pl);
+  return pl.total();
 }
-size_t ardae_model_packed_floats(const ardae_model_desc* d) {
-  if (desc_ok(d)) return 0;
-  if ((d->kind == 5 || d->kind == 6)) return res_model_packed_floats(*d);
-  if (d->kind == 4) return auxconv_model_packed_floats(*d);
-  if ((d->kind == 3 || d->kind == 7)) return aux_model_packed_floats(*d);
-  return d->kind == 2 ? conv_model_packed_floats(*d) : ModelPacked(ModelLayout(*d)).total;
-}
-size_t ardae_model_workspace_floats(const ardae_model_desc* d, int B, int nz, int mode) {
-  if (desc_ok(d) || B <= 0 || nz <= 0) return 0;
-  if ((d->kind == 5 || d->kind == 6)) return res_model_workspace_floats(*d, B, nz, mode);
-  if (d->kind == 4) return auxconv_model_workspace_floats(*d, B, nz, mode);
-  if ((d->kind == 3 || d->kind == 7)) return aux_model_workspace_floats(*d, B, nz, mode);
-  if (d->kind == 2) return conv_model_workspace_floats(*d, B, nz, mode == 3 ? 0 : mode);
-  const ModelLayout P(*d);
+size_t mlp_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+  const ModelLayout P(d);
   if (mode == 2) return P.dec.size() * al64((size_t)B * nz * P.h);
   if (mode == 3) return workspace_floats(P, B, nz, 0) + encode_pair_extra(P, B);   // ardae_model_encode_pair
   return workspace_floats(P, B, nz, mode) + (size_t)al64((size_t)B * nz * P.nd);   // + a zero-noise buffer for encode(std=0)
 }
 
-int ardae_model_pack(const ardae_model_desc* d, const float* params, float* packed, void* stream) {
-  ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(params && packed, "model_pack: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if ((d->kind == 5 || d->kind == 6)) return res_model_pack(*d, params, packed, st);
-  if (d->kind == 4) return auxconv_model_pack(*d, params, packed, st);
-  if ((d->kind == 3 || d->kind == 7)) return aux_model_pack(*d, params, packed, st);
-  if (d->kind == 2) return conv_model_pack(*d, params, packed, st);
-  std::vector<PackItem> pack_items__;
-  const ModelLayout P(*d);
-  const ModelPacked K(P);
-  for (size_t l = 0; l < P.inp.size(); ++l) {
-    PACK_PUSH(params + P.inp[l].w, P.inp[l].in, P.inp[l].out, P.inp[l].in, false, packed + K.inp_f[l]);
-    PACK_PUSH(params + P.inp[l].w, P.inp[l].in, P.inp[l].in, P.inp[l].out, true, packed + K.inp_b[l]);
-  }
-  for (size_t i = 0; i < P.stack.size(); ++i) {
-    const Lin& l = P.stack[i];
-    PACK_PUSH(params + l.w, l.in, l.out, P.h, false, packed + K.sh_f[i]);
-    PACK_PUSH(params + l.w, l.in, P.h, l.out, true, packed + K.sh_b[i]);
-    if (P.stack_noise[i]) PACK_PUSH(params + l.w + P.h, l.in, l.out, P.nd, false, packed + K.sn_f[i]);
-  }
-  for (size_t l = 0; l < P.dec.size(); ++l) {
-    PACK_PUSH(params + P.dec[l].w, P.dec[l].in, P.dec[l].out, P.dec[l].in, false, packed + K.dec_f[l]);
-    PACK_PUSH(params + P.dec[l].w, P.dec[l].in, P.dec[l].in, P.dec[l].out, true, packed + K.dec_b[l]);
-  }
-  for (size_t k = 0; k < P.heads.size(); ++k) {
-    PACK_PUSH(params + P.heads[k].w, P.heads[k].in, P.heads[k].out, P.heads[k].in, false, packed + K.head_f[k]);
-    PACK_PUSH(params + P.heads[k].w, P.heads[k].in, P.heads[k].in, P.heads[k].out, true, packed + K.head_b[k]);
-  }
-  PACK_FLUSH(st);
-  return 0;
+int mlp_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
+  PackList pl(params, packed);
+  ModelPacked(ModelLayout(d), pl);
+  return pl.launch(st);
 }
 
-static int model_common(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, int nz,
-                        float* workspace, size_t wsf, int mode) {
-  ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(params && packed && x && workspace, "model: null pointer argument");
-  ARDAE_CHECK_ARG(B > 0 && nz > 0 && (int64_t)B * nz < (int64_t)1 << 30, "model: bad batch (B=%d nz=%d)", B, nz);
-  const size_t need = ardae_model_workspace_floats(d, B, nz, mode);
-  ARDAE_CHECK_ARG(wsf >= need, "model: workspace too small (%zu < %zu floats)", wsf, need);
-  return 0;
-}
-
-int ardae_model_encode(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
-                       int B, int nz, float* workspace, size_t workspace_floats_, float* z_out, void* stream) {
-  ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 0));
-  ARDAE_CHECK_ARG(z_out, "model_encode: z_out is NULL");
-  hipStream_t st = (hipStream_t)stream;
-  if ((d->kind == 5 || d->kind == 6)) return res_model_encode(*d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, nullptr, st);
-  if ((d->kind == 3 || d->kind == 7)) {
-    ARDAE_TRY(aux_model_encode(*d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, nullptr, st));
-    return 0;
-  }
-  if (d->kind == 4) return auxconv_model_encode(*d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, nullptr, st);
-  if (d->kind == 2) return conv_model_encode(*d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, st);
-  const ModelLayout P(*d);
+int mlp_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+               float* workspace, size_t wsf, float* z_out, float*, hipStream_t st, const float*) {
+  const ModelLayout P(d);
   const ModelPacked K(P);
-  Bump ws(workspace, workspace_floats_);
+  Bump ws(workspace, wsf);
   ModelWs W;
   carve(P, ws, B, nz, 0, W);
   const float* nz_ptr = noise;
@@ -346,139 +272,46 @@ int ardae_model_encode(const ardae_model_desc* d, const float* params, const flo
     nz_ptr = zero;
   }
   ARDAE_CHECK_ARG(ws.ok, "model_encode: internal workspace accounting error");
-  ARDAE_TRY(encode_fwd(P, K, params, packed, x, nz_ptr, B, nz, W, z_out, false, st));
-  return 0;
+  return encode_fwd(P, K, params, packed, x, nz_ptr, B, nz, W, z_out, false, st);
 }
 
-int ardae_model_encode_pair(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
-                            int B, int nz, float* workspace, size_t workspace_floats_, float* z0_out, float* z_out, int phase,
-                            void* stream) {
-  ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(phase >= 0 && phase <= 2, "model_encode_pair: phase must be 0 (all), 1 (trunk + z0) or 2 (N-row stack)");
-  ARDAE_CHECK_ARG(params && packed && x && (noise || phase == 1) && workspace && z0_out && z_out, "model_encode_pair: null pointer argument");
-  ARDAE_CHECK_ARG(B > 0 && nz > 0 && (int64_t)B * nz < (int64_t)1 << 30, "model_encode_pair: bad batch (B=%d nz=%d)", B, nz);
-  ARDAE_CHECK_ARG(workspace_floats_ >= ardae_model_workspace_floats(d, B, nz, 3), "model_encode_pair: workspace too small");
-  if (d->kind >= 2) {   // conv / aux samplers: two passes over the same workspace
-    if (phase != 2) ARDAE_TRY(ardae_model_encode(d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, stream));
-    if (phase == 1) return 0;
-    return ardae_model_encode(d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, stream);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const ModelLayout P(*d);
-  const ModelPacked K(P);
-  Bump ws(workspace, workspace_floats_);
-  ModelWs W;
-  carve(P, ws, B, nz, 0, W);
-  std::vector<float*> t0(P.stack.size(), nullptr);
-  for (size_t i = 1; i < P.stack.size(); ++i) t0[i] = ws.take((size_t)B * P.h);
-  float* zero = ws.take((size_t)B * P.nd);
-  ARDAE_CHECK_ARG(ws.ok, "model_encode_pair: internal workspace accounting error");
-  if (phase != 2) {
-    ARDAE_TRY(launch_fill(zero, (size_t)B * P.nd, 0.f, st));
-    ARDAE_TRY(encode_trunk(P, K, params, packed, x, B, W, st));
-    ARDAE_TRY(encode_stack(P, K, params, packed, zero, B, 1, W.rb, t0, z0_out, false, st));    // encode(x, std=0): the draw is multiplied by 0
-  }
-  if (phase != 1) ARDAE_TRY(encode_stack(P, K, params, packed, noise, B, nz, W.rb, W.t, z_out, false, st));   // forward_hidden(x, nz); W.rb from phase 1
-  return 0;
-}
-
-int ardae_model_encode_hidden_raw(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* raw0, int B,
-                                  float* workspace, size_t workspace_floats_, float* z0_out, float* hidden_out, void* stream) {
-  ARDAE_TRY(model_common(d, params, packed, x, B, 1, workspace, workspace_floats_, 0));
-  ARDAE_CHECK_ARG(d->kind == 6 && (d->flags & ARDAE_MODEL_CLIPPED), "model_encode_hidden_raw: the clipped aux-resconv class only (kind 6 + ARDAE_MODEL_CLIPPED)");
-  ARDAE_CHECK_ARG(z0_out || hidden_out, "model_encode_hidden_raw: nothing to return");
-  return res_model_encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, (hipStream_t)stream, raw0);
-}
-int ardae_model_encode_hidden(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, float* workspace,
-                              size_t workspace_floats_, float* z0_out, float* hidden_out, void* stream) {
-  ARDAE_TRY(model_common(d, params, packed, x, B, 1, workspace, workspace_floats_, 0));
-  ARDAE_CHECK_ARG((d->kind == 3 || d->kind == 7) || d->kind == 4 || d->kind == 6, "model_encode_hidden: the hidden1a context exists for the aux models only (kinds 3, 4, 6, 7)");
-  ARDAE_CHECK_ARG(hidden_out, "model_encode_hidden: hidden_out is NULL");
-  hipStream_t st = (hipStream_t)stream;
-  if (d->kind == 6) return res_model_encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, st);   // z0_out may be NULL
-  if (d->kind == 4) ARDAE_TRY(auxconv_model_encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, st));
-  else ARDAE_TRY(aux_model_encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, st));
-  return 0;
-}
-
-int ardae_model_decode(const ardae_model_desc* d, const float* params, const float* packed, const float* z, int R, float* workspace,
-                       size_t workspace_floats_, float* out0, float* out1, void* stream) {
-  ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(params && packed && z && workspace && out0 && R > 0, "model_decode: bad arguments");
-  if ((d->kind == 5 || d->kind == 6)) {
-    ARDAE_CHECK_ARG(workspace_floats_ >= res_model_workspace_floats(*d, R, 1, 2), "model_decode: workspace too small");
-    return res_model_decode(*d, params, packed, z, R, workspace, workspace_floats_, out0, (hipStream_t)stream);
-  }
-  if (d->kind == 2) {
-    ARDAE_CHECK_ARG(workspace_floats_ >= conv_model_workspace_floats(*d, R, 1, 2), "model_decode: workspace too small");
-    return conv_model_decode(*d, params, packed, z, R, workspace, workspace_floats_, out0, (hipStream_t)stream);
-  }
-  if (d->kind == 4) {
-    ARDAE_CHECK_ARG(workspace_floats_ >= auxconv_model_workspace_floats(*d, R, 1, 2), "model_decode: workspace too small");
-    return auxconv_model_decode(*d, params, packed, z, R, workspace, workspace_floats_, out0, (hipStream_t)stream);
-  }
-  if ((d->kind == 3 || d->kind == 7)) {
-    ARDAE_CHECK_ARG(workspace_floats_ >= aux_model_workspace_floats(*d, R, 1, 2), "model_decode: workspace too small");
-    ARDAE_TRY(aux_model_decode(*d, params, packed, z, R, workspace, workspace_floats_, out0, (hipStream_t)stream, out1));
-    return 0;
-  }
-  const ModelLayout P(*d);
-  const ModelPacked K(P);
-  ARDAE_CHECK_ARG(P.kind == 0 || out1, "model_decode: the Gaussian decoder needs out1 (logvar)");
-  ARDAE_CHECK_ARG(workspace_floats_ >= P.dec.size() * al64((size_t)R * P.h), "model_decode: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  Bump ws(workspace, workspace_floats_);
+// decoder on R rows: the hidden layers into hid[1 .. n_dec], then the head(s) into out[0] (, out[1])
+int decoder_fwd(const ModelLayout& P, const ModelPacked& K, const float* params, const float* packed, const float* z, int R, float* const* hid,
+                float* const* out, hipStream_t st) {
   const int h = P.h;
-  const float* cur = z;
   for (size_t l = 1; l <= P.dec.size(); ++l) {
-    float* nxt = ws.take((size_t)R * h);
-    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = nxt; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, P.act, R, h, cur, l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
-    cur = nxt;
+    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = hid[l]; A.ldY = h;
+    ARDAE_TRY(lin1(EPI_ACT, P.act, R, h, l == 1 ? z : hid[l - 1], l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
   }
   for (size_t k = 0; k < P.heads.size(); ++k) {
-    LinArgs A{}; A.bias = params + P.heads[k].b; A.Y = k == 0 ? out0 : out1; A.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, cur, h, h, packed + K.head_f[k], A, st));
+    LinArgs A{}; A.bias = params + P.heads[k].b; A.Y = out[k]; A.ldY = P.D;
+    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, hid[P.dec.size()], h, h, packed + K.head_f[k], A, st));
   }
   return 0;
 }
 
-int ardae_model_loss_rows(const ardae_model_desc* d, const float* out0, const float* out1, const float* x, const float* z, int rows,
-                          int nz, float* recon_row, float* prior_row, void* stream) {
-  ARDAE_TRY(desc_ok(d));
-  return launch_vae_loss(d->kind == 1 || d->kind == 7 ? 1 : 0, out0, out1, x, z, rows, nz, d->input_dim, d->z_dim, 1.f, 0, 0.f, nullptr, recon_row, prior_row, nullptr,
-                         nullptr, nullptr, (hipStream_t)stream);
+int mlp_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
+               float* out0, hipStream_t st, float* out1) {
+  const ModelLayout P(d);
+  const ModelPacked K(P);
+  Bump ws(workspace, wsf);
+  std::vector<float*> hid(P.dec.size() + 1, nullptr);
+  for (size_t l = 1; l <= P.dec.size(); ++l) hid[l] = ws.take((size_t)R * P.h);
+  float* const out[2] = {out0, out1};
+  return decoder_fwd(P, K, params, packed, z, R, hid.data(), out, st);
 }
 
-int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
-                            int B, int nz, float beta, float* workspace, size_t workspace_floats_, float* z_out, float* losses,
-                            void* stream) {
-  ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
-  ARDAE_CHECK_ARG(noise && z_out && losses, "model_vae_forward: null pointer argument");
-  hipStream_t st = (hipStream_t)stream;
-  if ((d->kind == 5 || d->kind == 6)) return res_model_vae_forward(*d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, st);
-  if ((d->kind == 3 || d->kind == 7)) {
-    ARDAE_TRY(aux_model_vae_forward(*d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, st));
-    return 0;
-  }
-  if (d->kind == 4) return auxconv_model_vae_forward(*d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, st);
-  if (d->kind == 2) return conv_model_vae_forward(*d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, st);
-  const ModelLayout P(*d);
+int mlp_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                    float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+  const ModelLayout P(d);
   const ModelPacked K(P);
-  Bump ws(workspace, workspace_floats_);
+  Bump ws(workspace, wsf);
   ModelWs W;
   carve(P, ws, B, nz, 1, W);
   ARDAE_CHECK_ARG(ws.ok, "model_vae_forward: internal workspace accounting error");
-  const int R = B * nz, h = P.h, act = P.act;
+  const int R = B * nz;
   ARDAE_TRY(encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, true, st));
-  for (size_t l = 1; l <= P.dec.size(); ++l) {
-    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = W.dcd[l]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, act, R, h, l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
-  }
-  for (size_t k = 0; k < P.heads.size(); ++k) {
-    LinArgs A{}; A.bias = params + P.heads[k].b; A.Y = W.o[k]; A.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, W.dcd[P.dec.size()], h, h, packed + K.head_f[k], A, st));
-  }
+  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, R, W.dcd.data(), W.o.data(), st));
   ARDAE_TRY(launch_vae_loss(P.kind, W.o[0], P.kind == 1 ? W.o[1] : nullptr, x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row,
                             W.pri_row, nullptr, nullptr, nullptr, st));
   return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
@@ -487,10 +320,10 @@ int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, cons
 // phases: 1 = loss gradients + decoder backward up to dz (needs nothing from the cDAE), 2 = entropy seed + sampler backward +
 // weight gradients, 3 = both.  With phases == 3 the (pre-scaled) seed enters through the loss kernel; with phases == 2 it is
 // added to dz as seed_scale * dz_extra.
-static int vae_backward_impl(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
-                             int B, int nz, float beta, float dloss, const float* dz_extra, float seed_scale, float* workspace,
-                             size_t workspace_floats_, float* grads, float grads_beta, int phases, hipStream_t st) {
-  const ModelLayout P(*d);
+int vae_backward_impl(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise,
+                      int B, int nz, float beta, float dloss, const float* dz_extra, float seed_scale, float* workspace,
+                      size_t workspace_floats_, float* grads, float grads_beta, int phases, hipStream_t st) {
+  const ModelLayout P(d);
   const ModelPacked K(P);
   Bump ws(workspace, workspace_floats_);
   ModelWs W;
@@ -541,25 +374,158 @@ static int vae_backward_impl(const ardae_model_desc* d, const float* params, con
   return wl.launch(st);
 }
 
+int mlp_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                     float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
+                     hipStream_t st) {
+  return vae_backward_impl(d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, 1.f, workspace, wsf, grads, grads_beta, 3, st);
+}
+
+// ------------------------------------------------------------------------------------------------ the families, by kind
+// (encode: hidden_out / raw0 and decode: out1 are NULL for the families that have no such output / input)
+struct Family {
+  size_t (*param_floats)(const ardae_model_desc&);
+  size_t (*packed_floats)(const ardae_model_desc&);
+  size_t (*workspace_floats)(const ardae_model_desc&, int B, int nz, int mode);   // mode 2: decode only, 3: encode_pair
+  int (*pack)(const ardae_model_desc&, const float* params, float* packed, hipStream_t);
+  int (*encode)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t, const float* raw0);
+  int (*decode)(const ardae_model_desc&, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
+                float* out0, hipStream_t, float* out1);
+  int (*vae_forward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                     float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
+  int (*vae_backward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                      float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
+};
+const Family MLP = {mlp_param_floats, mlp_packed_floats, mlp_workspace_floats, mlp_pack, mlp_encode, mlp_decode, mlp_vae_forward, mlp_vae_backward};
+const Family CONV = {conv_model_param_floats, conv_model_packed_floats, conv_model_workspace_floats, conv_model_pack, conv_model_encode,
+                     conv_model_decode, conv_model_vae_forward, conv_model_vae_backward};
+const Family AUX = {aux_model_param_floats, aux_model_packed_floats, aux_model_workspace_floats, aux_model_pack, aux_model_encode,
+                    aux_model_decode, aux_model_vae_forward, aux_model_vae_backward};
+const Family AUXCONV = {auxconv_model_param_floats, auxconv_model_packed_floats, auxconv_model_workspace_floats, auxconv_model_pack,
+                        auxconv_model_encode, auxconv_model_decode, auxconv_model_vae_forward, auxconv_model_vae_backward};
+const Family RES = {res_model_param_floats, res_model_packed_floats, res_model_workspace_floats, res_model_pack, res_model_encode,
+                    res_model_decode, res_model_vae_forward, res_model_vae_backward};
+// desc_ok() has checked the kind
+const Family& family(const ardae_model_desc* d) {
+  static const Family* const by_kind[8] = {&MLP, &MLP, &CONV, &AUX, &AUXCONV, &RES, &RES, &AUX};
+  return *by_kind[d->kind];
+}
+
+}  // namespace
+}  // namespace ardae
+
+using namespace ardae;
+
+extern "C" {
+
+size_t ardae_model_param_floats(const ardae_model_desc* d) { return desc_ok(d) ? 0 : family(d).param_floats(*d); }
+size_t ardae_model_packed_floats(const ardae_model_desc* d) { return desc_ok(d) ? 0 : family(d).packed_floats(*d); }
+size_t ardae_model_workspace_floats(const ardae_model_desc* d, int B, int nz, int mode) {
+  if (desc_ok(d) || B <= 0 || nz <= 0) return 0;
+  return family(d).workspace_floats(*d, B, nz, mode);
+}
+
+int ardae_model_pack(const ardae_model_desc* d, const float* params, float* packed, void* stream) {
+  ARDAE_TRY(desc_ok(d));
+  ARDAE_CHECK_ARG(params && packed, "model_pack: null pointer");
+  return family(d).pack(*d, params, packed, (hipStream_t)stream);
+}
+
+static int model_common(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, int nz,
+                        float* workspace, size_t wsf, int mode) {
+  ARDAE_TRY(desc_ok(d));
+  ARDAE_CHECK_ARG(params && packed && x && workspace, "model: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && nz > 0 && (int64_t)B * nz < (int64_t)1 << 30, "model: bad batch (B=%d nz=%d)", B, nz);
+  const size_t need = ardae_model_workspace_floats(d, B, nz, mode);
+  ARDAE_CHECK_ARG(wsf >= need, "model: workspace too small (%zu < %zu floats)", wsf, need);
+  return 0;
+}
+
+int ardae_model_encode(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                       int B, int nz, float* workspace, size_t workspace_floats_, float* z_out, void* stream) {
+  ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 0));
+  ARDAE_CHECK_ARG(z_out, "model_encode: z_out is NULL");
+  return family(d).encode(*d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, nullptr, (hipStream_t)stream, nullptr);
+}
+
+int ardae_model_encode_pair(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                            int B, int nz, float* workspace, size_t workspace_floats_, float* z0_out, float* z_out, int phase,
+                            void* stream) {
+  ARDAE_TRY(desc_ok(d));
+  ARDAE_CHECK_ARG(phase >= 0 && phase <= 2, "model_encode_pair: phase must be 0 (all), 1 (trunk + z0) or 2 (N-row stack)");
+  ARDAE_CHECK_ARG(params && packed && x && (noise || phase == 1) && workspace && z0_out && z_out, "model_encode_pair: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && nz > 0 && (int64_t)B * nz < (int64_t)1 << 30, "model_encode_pair: bad batch (B=%d nz=%d)", B, nz);
+  ARDAE_CHECK_ARG(workspace_floats_ >= ardae_model_workspace_floats(d, B, nz, 3), "model_encode_pair: workspace too small");
+  if (d->kind >= 2) {   // conv / aux samplers: two passes over the same workspace
+    if (phase != 2) ARDAE_TRY(ardae_model_encode(d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, stream));
+    if (phase == 1) return 0;
+    return ardae_model_encode(d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, stream);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const ModelLayout P(*d);
+  const ModelPacked K(P);
+  Bump ws(workspace, workspace_floats_);
+  ModelWs W;
+  carve(P, ws, B, nz, 0, W);
+  std::vector<float*> t0(P.stack.size(), nullptr);
+  for (size_t i = 1; i < P.stack.size(); ++i) t0[i] = ws.take((size_t)B * P.h);
+  float* zero = ws.take((size_t)B * P.nd);
+  ARDAE_CHECK_ARG(ws.ok, "model_encode_pair: internal workspace accounting error");
+  if (phase != 2) {
+    ARDAE_TRY(launch_fill(zero, (size_t)B * P.nd, 0.f, st));
+    ARDAE_TRY(encode_trunk(P, K, params, packed, x, B, W, st));
+    ARDAE_TRY(encode_stack(P, K, params, packed, zero, B, 1, W.rb, t0, z0_out, false, st));    // encode(x, std=0): the draw is multiplied by 0
+  }
+  if (phase != 1) ARDAE_TRY(encode_stack(P, K, params, packed, noise, B, nz, W.rb, W.t, z_out, false, st));   // forward_hidden(x, nz); W.rb from phase 1
+  return 0;
+}
+
+int ardae_model_encode_hidden_raw(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* raw0, int B,
+                                  float* workspace, size_t workspace_floats_, float* z0_out, float* hidden_out, void* stream) {
+  ARDAE_TRY(model_common(d, params, packed, x, B, 1, workspace, workspace_floats_, 0));
+  ARDAE_CHECK_ARG(d->kind == 6 && (d->flags & ARDAE_MODEL_CLIPPED), "model_encode_hidden_raw: the clipped aux-resconv class only (kind 6 + ARDAE_MODEL_CLIPPED)");
+  ARDAE_CHECK_ARG(z0_out || hidden_out, "model_encode_hidden_raw: nothing to return");
+  return family(d).encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, (hipStream_t)stream, raw0);
+}
+int ardae_model_encode_hidden(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, float* workspace,
+                              size_t workspace_floats_, float* z0_out, float* hidden_out, void* stream) {
+  ARDAE_TRY(model_common(d, params, packed, x, B, 1, workspace, workspace_floats_, 0));
+  ARDAE_CHECK_ARG((d->kind == 3 || d->kind == 7) || d->kind == 4 || d->kind == 6, "model_encode_hidden: the hidden1a context exists for the aux models only (kinds 3, 4, 6, 7)");
+  ARDAE_CHECK_ARG(hidden_out, "model_encode_hidden: hidden_out is NULL");
+  return family(d).encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, (hipStream_t)stream, nullptr);   // z0_out may be NULL
+}
+
+int ardae_model_decode(const ardae_model_desc* d, const float* params, const float* packed, const float* z, int R, float* workspace,
+                       size_t workspace_floats_, float* out0, float* out1, void* stream) {
+  ARDAE_TRY(desc_ok(d));
+  ARDAE_CHECK_ARG(params && packed && z && workspace && out0 && R > 0, "model_decode: bad arguments");
+  ARDAE_CHECK_ARG(d->kind != 1 || out1, "model_decode: the Gaussian decoder needs out1 (logvar)");
+  ARDAE_CHECK_ARG(workspace_floats_ >= family(d).workspace_floats(*d, R, 1, 2), "model_decode: workspace too small");
+  return family(d).decode(*d, params, packed, z, R, workspace, workspace_floats_, out0, (hipStream_t)stream, out1);
+}
+
+int ardae_model_loss_rows(const ardae_model_desc* d, const float* out0, const float* out1, const float* x, const float* z, int rows,
+                          int nz, float* recon_row, float* prior_row, void* stream) {
+  ARDAE_TRY(desc_ok(d));
+  return launch_vae_loss(d->kind == 1 || d->kind == 7 ? 1 : 0, out0, out1, x, z, rows, nz, d->input_dim, d->z_dim, 1.f, 0, 0.f, nullptr, recon_row, prior_row, nullptr,
+                         nullptr, nullptr, (hipStream_t)stream);
+}
+
+int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                            int B, int nz, float beta, float* workspace, size_t workspace_floats_, float* z_out, float* losses,
+                            void* stream) {
+  ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
+  ARDAE_CHECK_ARG(noise && z_out && losses, "model_vae_forward: null pointer argument");
+  return family(d).vae_forward(*d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, (hipStream_t)stream);
+}
+
 int ardae_model_vae_backward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
                              int B, int nz, float beta, float dloss, const float* dz_extra, float* workspace,
                              size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise && grads, "model_vae_backward: null pointer argument");
-  hipStream_t st = (hipStream_t)stream;
-  if ((d->kind == 5 || d->kind == 6)) {
-    return res_model_vae_backward(*d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta, st);
-  }
-  if (d->kind == 2) {
-    return conv_model_vae_backward(*d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta, st);
-  }
-  if (d->kind == 4) {
-    return auxconv_model_vae_backward(*d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta, st);
-  }
-  if ((d->kind == 3 || d->kind == 7)) {
-    return aux_model_vae_backward(*d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta, st);
-  }
-  return vae_backward_impl(d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, 1.f, workspace, workspace_floats_, grads, grads_beta, 3, st);
+  return family(d).vae_backward(*d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta,
+                                (hipStream_t)stream);
 }
 
 int ardae_model_vae_backward_decoder(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
@@ -568,7 +534,7 @@ int ardae_model_vae_backward_decoder(const ardae_model_desc* d, const float* par
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise, "model_vae_backward_decoder: null pointer argument");
   ARDAE_CHECK_ARG(d->kind < 2, "model_vae_backward_decoder: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
-  return vae_backward_impl(d, params, packed, x, noise, B, nz, beta, dloss, nullptr, 0.f, workspace, workspace_floats_, nullptr, 0.f, 1,
+  return vae_backward_impl(*d, params, packed, x, noise, B, nz, beta, dloss, nullptr, 0.f, workspace, workspace_floats_, nullptr, 0.f, 1,
                            (hipStream_t)stream);
 }
 
@@ -578,7 +544,7 @@ int ardae_model_vae_backward_sampler(const ardae_model_desc* d, const float* par
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise && grads, "model_vae_backward_sampler: null pointer argument");
   ARDAE_CHECK_ARG(d->kind < 2, "model_vae_backward_sampler: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
-  return vae_backward_impl(d, params, packed, x, noise, B, nz, 0.f, 0.f, dz_extra, seed_scale, workspace, workspace_floats_, grads,
+  return vae_backward_impl(*d, params, packed, x, noise, B, nz, 0.f, 0.f, dz_extra, seed_scale, workspace, workspace_floats_, grads,
                            grads_beta, 2, (hipStream_t)stream);
 }
 

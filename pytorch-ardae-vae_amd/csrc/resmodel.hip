@@ -229,7 +229,6 @@ __global__ void spm4_kernel(const float* __restrict__ x, const float* __restrict
 // ------------------------------------------------------------------------------------------------ layout
 // plain: the operator is an nn.Linear (weight at `dir`, no scale, effective weight = weight): ResMLP(layer='linear')
 struct WN { size_t dir, scale, bias; int O, I; bool norm; bool plain; };          // flat-parameter offsets; I = fan-in (C*9 for a conv)
-struct Lin { size_t w, b; int out, in; };
 struct Blk { WN a, h, s; bool conv; int Cin, Cout, stride, Hin, Hout; bool same; };   // a = *_0h, h = *_h1, s = *_01 (skip; absent when same: identity)
 // One operator of ResConvIPVAE's sampler head `encode.fc` (models/ivae/resconv.py:101-116) on the B nz rows: a ResLinear (inner ReLU) or a
 // plain Linear, reading [trunk output | noise] (concat: the first one) or its predecessor's output, with ELU behind it or not
@@ -263,7 +262,7 @@ struct ResLayout {
       if (same) { b.s = b.h; b.s.O = 0; } else b.s = wn(Cout, I, norm, plain);
       return b;
     };
-    auto lin = [&](int out, int in) { Lin l; l.out = out; l.in = in; l.w = off; off += (size_t)out * in; l.b = off; off += out; return l; };
+    auto lin = [&](int out, int in) { return next_lin(off, out, in); };
     trunk.push_back(block(16, 1, true, 2, 28, true));    // 28 -> 14
     trunk.push_back(block(16, 16, true, 1, 14, true));
     trunk.push_back(block(32, 16, true, 2, 14, true));   // 14 -> 7
@@ -318,26 +317,32 @@ struct ResPacked {
   struct HeadPk { BlkPk k; LinPk lk; };
   std::vector<HeadPk> head;
   LinPk mu0, lv0, efc, mu, lv;
-  size_t total = 0;
-  explicit ResPacked(const ResLayout& P) {
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += al64(n); return o; };
-    auto wn = [&](const WN& w) { WNPk k; k.weff = take((size_t)w.O * w.I); k.inv = take(w.O); k.f = take(packed_floats(w.O, w.I)); k.b = take(packed_floats(w.I, w.O)); return k; };
+  ResPacked(const ResLayout& P, PackList& pl) {
+    // an operator's panels are packed from its effective weight: composed into the packed buffer at k.weff by res_model_pack's
+    // compose launch (weight norm), or the parameter itself (plain nn.Linear operator, whose weff / inv stay unused)
+    auto wn_panel = [&](const WN& w, const WNPk& k, int col0, int nout, int kk, bool tr) {
+      return pl.panel((w.plain ? w.dir : k.weff) + col0, w.I, nout, kk, tr, !w.plain);
+    };
+    auto wn = [&](const WN& w) {
+      WNPk k; k.weff = pl.take((size_t)w.O * w.I); k.inv = pl.take(w.O);
+      k.f = wn_panel(w, k, 0, w.O, w.I, false); k.b = wn_panel(w, k, 0, w.I, w.O, true);
+      return k;
+    };
     auto blk = [&](const Blk& b, int split) {
-      BlkPk k; k.a = wn(b.a); k.h = wn(b.h); k.s = b.same ? k.h : wn(b.s); k.bsum = take(b.Cout);
+      BlkPk k; k.a = wn(b.a); k.h = wn(b.h); k.s = b.same ? k.h : wn(b.s); k.bsum = pl.take(b.Cout);
       k.a_fi = k.a_fn = k.a_bi = k.s_fi = k.s_fn = k.s_bi = 0;
       if (split) {   // concat input [image part (split columns) | noise part]  (a concat block always has its projected skip: cdim + nd != Cout)
         const int nn = b.a.I - split;
-        k.a_fi = take(packed_floats(b.a.O, split)); k.a_fn = take(packed_floats(b.a.O, nn)); k.a_bi = take(packed_floats(split, b.a.O));
-        k.s_fi = take(packed_floats(b.s.O, split)); k.s_fn = take(packed_floats(b.s.O, nn)); k.s_bi = take(packed_floats(split, b.s.O));
+        k.a_fi = wn_panel(b.a, k.a, 0, b.a.O, split, false); k.a_fn = wn_panel(b.a, k.a, split, b.a.O, nn, false); k.a_bi = wn_panel(b.a, k.a, 0, split, b.a.O, true);
+        k.s_fi = wn_panel(b.s, k.s, 0, b.s.O, split, false); k.s_fn = wn_panel(b.s, k.s, split, b.s.O, nn, false); k.s_bi = wn_panel(b.s, k.s, 0, split, b.s.O, true);
       }
       return k;
     };
     auto lin = [&](const Lin& l, int split) {
-      LinPk k; k.f = take(packed_floats(l.out, l.in)); k.b = take(packed_floats(l.in, l.out)); k.fi = k.fn = k.bi = k.bn = 0;
+      LinPk k; pl.pair(l, k.f, k.b); k.fi = k.fn = k.bi = k.bn = 0;
       if (split) {
-        k.fi = take(packed_floats(l.out, split)); k.fn = take(packed_floats(l.out, l.in - split));
-        k.bi = take(packed_floats(split, l.out)); k.bn = take(packed_floats(l.in - split, l.out));
+        k.fi = pl.panel(l.w, l.in, l.out, split, false); k.fn = pl.panel(l.w + split, l.in, l.out, l.in - split, false);
+        k.bi = pl.panel(l.w, l.in, split, l.out, true); k.bn = pl.panel(l.w + split, l.in, l.in - split, l.out, true);
       }
       return k;
     };
@@ -350,8 +355,8 @@ struct ResPacked {
       }
     } else { mu0 = lin(P.mu0, 0); lv0 = lin(P.lv0, 0); efc = lin(P.efc, P.cdim); mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
     for (auto& b : P.dec) dec.push_back(blk(b, 0));
-    total = off;
   }
+  explicit ResPacked(const ResLayout& P, PackList&& sizing = PackList()) : ResPacked(P, sizing) {}   // offsets only
 };
 
 int res_desc_ok(const ardae_model_desc& d) {
@@ -697,7 +702,12 @@ struct GradMap {
 
 // ================================================================================================ entry points
 size_t res_model_param_floats(const ardae_model_desc& d) { return res_desc_ok(d) ? 0 : ResLayout(d).total; }
-size_t res_model_packed_floats(const ardae_model_desc& d) { return res_desc_ok(d) ? 0 : ResPacked(ResLayout(d)).total; }
+size_t res_model_packed_floats(const ardae_model_desc& d) {
+  if (res_desc_ok(d)) return 0;
+  PackList pl;
+  ResPacked(ResLayout(d), pl);
+  return pl.total();
+}
 size_t res_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   if (res_desc_ok(d)) return 0;
   return res_workspace(ResLayout(d), B, nz, mode == 3 ? 0 : mode);
@@ -706,52 +716,24 @@ size_t res_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int 
 int res_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
   ARDAE_TRY(res_desc_ok(d));
   const ResLayout P(d);
-  const ResPacked K(P);
-  std::vector<PackItem> items;
+  PackList pl(params, packed);
+  const ResPacked K(P, pl);
+  // what the panels are packed FROM: the weight-normalised operators' effective weights and every projected-skip block's bias sum,
+  // composed into the packed buffer ahead of the pack launch
   std::vector<WnComposeItem> comp;
-  // effective weight of an operator: composed into the packed buffer (weight norm), or the parameter itself (plain nn.Linear operator)
-  auto weff = [&](const WN& w, const WNPk& k) -> const float* { return w.plain ? params + w.dir : packed + k.weff; };
-  auto wn = [&](const WN& w, const WNPk& k) -> int {
+  auto wn = [&](const WN& w, const WNPk& k) {
     if (!w.plain) comp.push_back(WnComposeItem{params + w.dir, params + w.scale, packed + k.weff, packed + k.inv, w.O, w.I, w.norm ? 1 : 0, nullptr, nullptr});
-    items.push_back(PackItem{weff(w, k), w.I, w.O, w.I, 0, packed + k.f});
-    items.push_back(PackItem{weff(w, k), w.I, w.I, w.O, 1, packed + k.b});
-    return 0;
   };
-  auto blk = [&](const Blk& b, const BlkPk& k, int split) -> int {
-    ARDAE_TRY(wn(b.a, k.a)); ARDAE_TRY(wn(b.h, k.h));
-    if (b.same) return 0;          // identity skip: no third operator, the block's bias is b_h1
-    ARDAE_TRY(wn(b.s, k.s));
-    // bsum = b_h + b_s rides in the same launch
-    comp.push_back(WnComposeItem{nullptr, nullptr, packed + k.bsum, nullptr, b.Cout, 0, 0, params + b.h.bias, params + b.s.bias});
-    if (split) {
-      const int nn = b.a.I - split;
-      items.push_back(PackItem{weff(b.a, k.a), b.a.I, b.a.O, split, 0, packed + k.a_fi});
-      items.push_back(PackItem{weff(b.a, k.a) + split, b.a.I, b.a.O, nn, 0, packed + k.a_fn});
-      items.push_back(PackItem{weff(b.a, k.a), b.a.I, split, b.a.O, 1, packed + k.a_bi});
-      items.push_back(PackItem{weff(b.s, k.s), b.s.I, b.s.O, split, 0, packed + k.s_fi});
-      items.push_back(PackItem{weff(b.s, k.s) + split, b.s.I, b.s.O, nn, 0, packed + k.s_fn});
-      items.push_back(PackItem{weff(b.s, k.s), b.s.I, split, b.s.O, 1, packed + k.s_bi});
-    }
-    return 0;
+  auto blk = [&](const Blk& b, const BlkPk& k) {
+    wn(b.a, k.a); wn(b.h, k.h);
+    if (b.same) return;          // identity skip: no third operator, the block's bias is b_h1
+    wn(b.s, k.s);
+    comp.push_back(WnComposeItem{nullptr, nullptr, packed + k.bsum, nullptr, b.Cout, 0, 0, params + b.h.bias, params + b.s.bias});   // bsum = b_h + b_s
   };
-  auto lin = [&](const Lin& l, const LinPk& k, int split) {
-    items.push_back(PackItem{params + l.w, l.in, l.out, l.in, 0, packed + k.f});
-    items.push_back(PackItem{params + l.w, l.in, l.in, l.out, 1, packed + k.b});
-    if (split) {
-      items.push_back(PackItem{params + l.w, l.in, l.out, split, 0, packed + k.fi});
-      items.push_back(PackItem{params + l.w + split, l.in, l.out, l.in - split, 0, packed + k.fn});
-      items.push_back(PackItem{params + l.w, l.in, split, l.out, 1, packed + k.bi});
-      items.push_back(PackItem{params + l.w + split, l.in, l.in - split, l.out, 1, packed + k.bn});
-    }
-  };
-  for (size_t i = 0; i < P.trunk.size(); ++i) ARDAE_TRY(blk(P.trunk[i], K.trunk[i], 0));
-  if (P.kind == 5) {
-    for (size_t i = 0; i < P.head.size(); ++i) {
-      const HeadOp& o = P.head[i];
-      if (o.res) ARDAE_TRY(blk(o.b, K.head[i].k, o.concat ? P.cdim : 0)); else lin(o.l, K.head[i].lk, o.concat ? P.cdim : 0);
-    }
-  } else { lin(P.mu0, K.mu0, 0); lin(P.lv0, K.lv0, 0); lin(P.efc, K.efc, P.cdim); lin(P.mu, K.mu, 0); lin(P.lv, K.lv, 0); }
-  for (size_t i = 0; i < P.dec.size(); ++i) ARDAE_TRY(blk(P.dec[i], K.dec[i], 0));
+  for (size_t i = 0; i < P.trunk.size(); ++i) blk(P.trunk[i], K.trunk[i]);
+  for (size_t i = 0; i < P.head.size(); ++i)
+    if (P.head[i].res) blk(P.head[i].b, K.head[i].k);
+  for (size_t i = 0; i < P.dec.size(); ++i) blk(P.dec[i], K.dec[i]);
   for (size_t i0 = 0; i0 < comp.size(); i0 += WNC_MAX) {
     WnComposeBatch cb;
     cb.n = (int)std::min<size_t>(WNC_MAX, comp.size() - i0);
@@ -763,7 +745,7 @@ int res_model_pack(const ardae_model_desc& d, const float* params, float* packed
     hipLaunchKernelGGL(wn_compose_batch_kernel, dim3(maxo, cb.n), dim3(256), 0, st, cb);
     ARDAE_LAUNCH_CHECK();
   }
-  return launch_pack_batch(items.data(), (int)items.size(), st);
+  return pl.launch(st);
 }
 
 int res_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
@@ -784,7 +766,7 @@ int res_model_encode(const ardae_model_desc& d, const float* params, const float
 }
 
 int res_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                     float* out0, hipStream_t st) {
+                     float* out0, hipStream_t st, float*) {
   const ResLayout P(d);
   const ResPacked K(P);
   Bump ws(workspace, wsf);

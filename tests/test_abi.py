@@ -38,33 +38,57 @@ def test_abi_version_and_error_channel():
         L.check(lib.ardae_pack_weight(None, 0, 0, 0, 0, None, None))
 
 
-@pytest.mark.parametrize("kind,args", [("mnist", (784, 100, 256, 32, 2)), ("toy", (2, 10, 256, 2, 2)), ("mnist", (24, 10, 64, 8, 2)),
-                                       ("conv", (784, 100, 800, 32, 1)), ("auxmnist", (784, 100, 300, 32, 2)), ("auxmnist", (24, 10, 48, 8, 3)), ("auxconv", (784, 100, 800, 32, 1)),
-                                       ("resconv", (784, 100, 512, 32, 1)), ("auxresconv", (784, 100, 450, 32, 1))])
-def test_model_layout_matches_c_side(kind, args):
+# packed floats and workspace floats at (B, nz) = (8, 16) for modes 0 .. 3, as the C side gave them before the packed buffers were laid
+# out from one pack list (the packed-buffer and workspace layouts are part of no interface, but a change of either is a change of every offset)
+MODEL_SIZES = [("mnist", (784, 100, 256, 32, 2), 2, 0, 1656832, [66176, 1735232, 98304, 56256]),
+               ("toy", (2, 10, 256, 2, 2), 2, 0, 584192, [73280, 692864, 65536, 76224]),
+               ("mnist", (24, 10, 64, 8, 2), 2, 0, 62464, [13248, 124160, 24576, 12608]),
+               ("conv", (784, 100, 800, 32, 1), 2, 0, 1450752, [476224, 16308992, 7104448, 476224]),
+               ("auxmnist", (784, 100, 300, 32, 2), 2, 0, 2099200, [134016, 2191488, 76800, 134016]),
+               ("auxmnist", (24, 10, 48, 8, 3), 2, 0, 58368, [27072, 130176, 18432, 27072]),
+               ("auxconv", (784, 100, 800, 32, 1), 2, 0, 2873600, [853632, 18387072, 7481856, 853632]),
+               ("resconv", (784, 100, 512, 32, 1), 3, 0, 10086208, [1506112, 77025792, 48908288, 1506112]),
+               ("auxresconv", (784, 100, 450, 32, 1), 3, 0, 6869312, [1446592, 76021632, 48892416, 1446592]),
+               ("auxtoy", (2, 2, 64, 2, 1), 4, 0, 23552, [4032, 28608, 8192, 4032]),
+               # both log-variance clip codes set (z0 head 'hard', z head 'spm4'): two more workspace buffers, same parameters and panels
+               ("auxmnist", (784, 100, 300, 32, 2), 2, (1 << L.MODEL_CLIP_Z0_SHIFT) | (6 << L.MODEL_CLIP_Z_SHIFT), 2099200, [138944, 2196416, 76800, 138944])]
+# kind 5 at (784, 100, 512, 32, nl): (packed floats, workspace floats at (4, 8), mode 1) per sampler head and nl = 1, 2, 3
+RESCONV_HEAD_SIZES = {"res-wn-mlp": [(10086208, 22831104), (11660608, 23456000), (13235008, 24080896)],
+                      "mlp": [(7447104, 22141504), (7971392, 22453376), (8495680, 22765248)],
+                      "res-mlp": [(10086208, 22829184), (11660608, 23452928), (13235008, 24076672)],
+                      "res-wn-mlp-lin": [(10017344, 22810240), (11591744, 23435136), (13166144, 24060032)],
+                      "res-mlp-lin": [(10017344, 22808512), (11591744, 23432256), (13166144, 24056000)]}
+
+
+@pytest.mark.parametrize("kind,args,act,flags,packed,workspace", MODEL_SIZES, ids=[f"{r[0]}-args{i}" for i, r in enumerate(MODEL_SIZES)])
+def test_model_layout_matches_c_side(kind, args, act, flags, packed, workspace):
     spec = layout.model_spec(kind, *args)
     _, total = layout.offsets(spec)
-    d = L.ModelDesc({"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6}[kind], *args,
-                    3 if "resconv" in kind else 2)
+    d = L.ModelDesc({"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7}[kind], *args, act, flags)
     if kind == "resconv":       # every sampler head of ivae_ardae.py's --model resconv* choices, one to three hidden layers
         for et, code in layout.RESCONV_HEADS.items():
             for nl in (1, 2, 3):
                 _, tot = layout.offsets(layout.model_spec(kind, *args[:4], nl, enc_type=et))
                 dd = L.ModelDesc(5, *args[:4], nl, 3, code << L.MODEL_HEAD_SHIFT)
                 assert L.lib().ardae_model_param_floats(ctypes.byref(dd)) == tot, (et, nl)
-                assert L.lib().ardae_model_workspace_floats(ctypes.byref(dd), 4, 8, 1) > 0
+                assert (L.lib().ardae_model_packed_floats(ctypes.byref(dd)),
+                        L.lib().ardae_model_workspace_floats(ctypes.byref(dd), 4, 8, 1)) == RESCONV_HEAD_SIZES[et][nl - 1], (et, nl)
     assert L.lib().ardae_model_param_floats(ctypes.byref(d)) == total
-    assert L.lib().ardae_model_packed_floats(ctypes.byref(d)) > total
-    assert L.lib().ardae_model_workspace_floats(ctypes.byref(d), 8, 16, 1) > 0
+    assert L.lib().ardae_model_packed_floats(ctypes.byref(d)) == packed > total
+    assert [L.lib().ardae_model_workspace_floats(ctypes.byref(d), 8, 16, mode) for mode in range(4)] == workspace
 
 
-@pytest.mark.parametrize("kind,args", [("grad", (32, 32, 256, 3)), ("res", (32, 32, 1024, 6)), ("grad", (2, 2, 256, 3)), ("grad", (32, 32, 512, 4))])
-def test_cdae_layout_matches_c_side(kind, args):
+# packed floats and workspace floats at (B, S) = (4, 8) without / with gradients, recorded like MODEL_SIZES
+@pytest.mark.parametrize("kind,args,packed,workspace", [("grad", (32, 32, 256, 3), 1081600, (104576, 753024)), ("res", (32, 32, 1024, 6), 35849216, (817280, 19596480)),
+                                                        ("grad", (2, 2, 256, 3), 1069312, (102656, 735744)), ("grad", (32, 32, 512, 4), 5833216, (274560, 3477120))],
+                         ids=["grad-args0", "res-args1", "grad-args2", "grad-args3"])
+def test_cdae_layout_matches_c_side(kind, args, packed, workspace):
     spec = layout.cdae_spec(kind, *args)
     _, total = layout.offsets(spec)
     d = L.CdaeDesc(0 if kind == "grad" else 1, *args, 2)
     assert L.lib().ardae_cdae_param_floats(ctypes.byref(d)) == total
-    assert L.lib().ardae_cdae_workspace_floats(ctypes.byref(d), 4, 8, 1) > L.lib().ardae_cdae_workspace_floats(ctypes.byref(d), 4, 8, 0) > 0
+    assert L.lib().ardae_cdae_packed_floats(ctypes.byref(d)) == packed
+    assert tuple(L.lib().ardae_cdae_workspace_floats(ctypes.byref(d), 4, 8, g) for g in (0, 1)) == workspace
 
 
 def test_survey_parameter_counts():
