@@ -1,15 +1,15 @@
-"""ctypes binding of libardae_hip.so (C ABI: include/ardae_hip.h).
+"""ctypes binding of libardae_hip.so, derived from the C ABI's only description: include/ardae_hip.h.
 
-The HIP library is the product: there is no CPU or eager-PyTorch fallback.  Importing this module
-without a built library raises; calling into it without a GPU raises from the HIP runtime.
+The HIP library is the product: there is no CPU or eager-PyTorch fallback.  Importing this module parses the header (no library, no
+GPU needed); `lib()` raises without a built library; calling into it without a GPU raises from the HIP runtime.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARDAE_LIB") or os.path.join(_HERE, "libardae_hip.so")   # ARDAE_LIB: experiment builds
-
-c_float_p = ctypes.POINTER(ctypes.c_float)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ardae_hip.h")
 
 
 def debug_knob(name, default=None):
@@ -20,168 +20,121 @@ def debug_knob(name, default=None):
     return os.environ.get(name, default)
 
 
-class LinSrc(ctypes.Structure):
-    _fields_ = [("x", ctypes.c_void_p), ("ld", ctypes.c_int), ("K", ctypes.c_int), ("wp", ctypes.c_void_p)]
+# ---------------------------------------------------------------------------------------------------------------
+# The header parser.  It reads THIS header, not C: enum blocks, integer #defines, `typedef struct X { ... } X;` and prototypes over
+# the types below.  Anything else is an error that names the declaration - never a loosely bound symbol.
+# ---------------------------------------------------------------------------------------------------------------
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
+_DATA_POINTEES = ("float", "int64_t", "void", "unsigned long long")      # pointers that are bound as c_void_p
+_TYPE = r"(?:const\s+)?(unsigned long long|\w+)\s*"
+_DECL = re.compile(r"\s*(?:enum\s*\{(?P<enum>[^{}]*)\}|typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<fields>[^{}]*)\}\s*(?P<alias>\w+)|(?P<proto>[^;{}]+?))\s*;")
 
 
-class LinearArgs(ctypes.Structure):
-    _fields_ = [
-        ("M", ctypes.c_int), ("Nout", ctypes.c_int),
-        ("nsrc", ctypes.c_int),
-        ("src", LinSrc * 2),
-        ("act", ctypes.c_int),
-        ("bias", ctypes.c_void_p),
-        ("rowbias", ctypes.c_void_p), ("rowbias_ld", ctypes.c_int), ("rows_per_group", ctypes.c_int),
-        ("rowscale", ctypes.c_void_p), ("rowscale_w", ctypes.c_void_p),
-        ("S", ctypes.c_void_p), ("ldS", ctypes.c_int),
-        ("R", ctypes.c_void_p), ("ldR", ctypes.c_int),
-        ("Q", ctypes.c_void_p), ("ldQ", ctypes.c_int),
-        ("sigma", ctypes.c_void_p),
-        ("eps", ctypes.c_void_p), ("ldeps", ctypes.c_int),
-        ("scale", ctypes.c_float),
-        ("Y", ctypes.c_void_p), ("ldY", ctypes.c_int),
-        ("Y2", ctypes.c_void_p), ("ldY2", ctypes.c_int),
-        ("colsum", ctypes.c_void_p),
-        ("tile_loss", ctypes.c_void_p),
-    ]
+def _int(expr, where):
+    m = re.fullmatch(r"(\w+)(?:\s*<<\s*(\w+))?", expr.strip())
+    try:
+        return int(m.group(1), 0) << int(m.group(2) or "0", 0)
+    except (AttributeError, ValueError):
+        raise ValueError(f"ardae_hip.h: {where}: not an integer constant: {expr.strip()!r}") from None
 
 
-class WgradProblem(ctypes.Structure):
-    _fields_ = [
-        ("M", ctypes.c_int), ("O", ctypes.c_int), ("I", ctypes.c_int), ("npairs", ctypes.c_int),
-        ("G", ctypes.c_void_p * 2), ("ldG", ctypes.c_int * 2),
-        ("X", ctypes.c_void_p * 2), ("ldX", ctypes.c_int * 2),
-        ("bias_pair", ctypes.c_int),
-        ("rowscale", ctypes.c_void_p),
-        ("splits", ctypes.c_int),
-        ("partial", ctypes.c_void_p),
-        ("partial_vec", ctypes.c_void_p),
-        ("out", ctypes.c_void_p), ("ldout", ctypes.c_int),
-        ("out_bias", ctypes.c_void_p),
-        ("out_rowscale", ctypes.c_void_p), ("ld_rowscale", ctypes.c_int),
-        ("beta", ctypes.c_float),
-    ]
+def _struct(tag, body, structs):
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        m = re.fullmatch(_TYPE + r"(\*?)\s*(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)", decl)
+        if m is None or (m.group(2) and "," in m.group(3)):
+            raise ValueError(f"ardae_hip.h: struct {tag}: cannot split the field declaration {decl!r}")
+        base, star, names = m.groups()
+        if star:
+            ctype = ctypes.c_void_p if base in _DATA_POINTEES else None
+        else:
+            ctype = ctypes.c_char if base == "char" else _SCALARS.get(base) or structs.get(base)
+        if ctype is None:
+            raise ValueError(f"ardae_hip.h: struct {tag}: unknown type in the field declaration {decl!r}")
+        fields += [(name, ctype * int(dim) if dim else ctype) for name, dim in re.findall(r"(\w+)(?:\[(\d+)\])?", names)]
+    # ardae_linear_args -> LinearArgs
+    return type("".join(w.title() for w in tag.split("_")[1:]), (ctypes.Structure,), {"_fields_": fields})
 
 
-class CdaeDesc(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int), ("input_dim", ctypes.c_int), ("context_dim", ctypes.c_int),
-                ("h_dim", ctypes.c_int), ("n_layers", ctypes.c_int), ("act", ctypes.c_int)]
+def _prototype(text, structs):
+    """-> name, restype, [(parameter name, ctypes type, pointee or None)]"""
+    m = re.fullmatch(_TYPE + r"(\*?)\s*(\w+)\s*\((.*)\)", text, re.S)
+    if m is None:
+        raise ValueError(f"ardae_hip.h: cannot split the declaration {' '.join(text.split())!r}")
+    rbase, rptr, name, plist = m.groups()
+    restype = ctypes.c_char_p if (rbase, rptr) == ("char", "*") else None if rptr else _SCALARS.get(rbase)
+    if restype is None:
+        raise ValueError(f"ardae_hip.h: {name}: unknown return type {rbase + rptr!r}")
+    params = []
+    for p in ([] if plist.strip() == "void" else plist.split(",")):
+        pm = re.fullmatch(_TYPE + r"(\*{0,2})\s*(\w+)", p.strip())
+        if pm is None:
+            raise ValueError(f"ardae_hip.h: {name}: cannot split the parameter {' '.join(p.split())!r}")
+        base, stars, pname = pm.groups()
+        if not stars:
+            ctype = _SCALARS.get(base)
+        elif base in structs and stars == "*":
+            ctype = ctypes.POINTER(structs[base])
+        elif (base, stars) in (("void", "**"), ("int", "*")):
+            ctype = ctypes.POINTER(ctypes.c_void_p if base == "void" else ctypes.c_int)
+        else:
+            ctype = ctypes.c_void_p if stars == "*" and base in _DATA_POINTEES else None
+        if ctype is None:
+            raise ValueError(f"ardae_hip.h: {name}: unknown type in the parameter {' '.join(p.split())!r}")
+        params.append((pname, ctype, base + stars[1:] if stars else None))
+    return name, restype, params
 
 
-class ProfileEntry(ctypes.Structure):
-    _fields_ = [("name", ctypes.c_char * 96), ("calls", ctypes.c_int), ("total_ms", ctypes.c_double), ("flops", ctypes.c_double),
-                ("bytes", ctypes.c_double)]
+def parse_header(text):
+    """-> (constants {name: int}, structs {C name: ctypes.Structure class, in declaration order}, prototypes {name: (restype, params)})"""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)            # the extern "C" braces
+    consts = {n: _int(v, f"#define {n}") for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    structs, protos, pos = {}, {}, 0
+    while text[pos:].strip():
+        m = _DECL.match(text, pos)
+        if m is None:
+            raise ValueError(f"ardae_hip.h: cannot split the declaration starting at {' '.join(text[pos:].split())[:80]!r}")
+        pos = m.end()
+        if m.group("enum") is not None:
+            for item in filter(None, (i.strip() for i in m.group("enum").split(","))):
+                n, _, v = item.partition("=")           # (an enumerator without a value is refused: the header numbers all of them)
+                consts[n.strip()] = _int(v, f"enum constant {n.strip()}")
+        elif m.group("tag"):
+            if m.group("tag") != m.group("alias"):
+                raise ValueError(f"ardae_hip.h: struct {m.group('tag')} is given the other name {m.group('alias')}")
+            structs[m.group("tag")] = _struct(m.group("tag"), m.group("fields"), structs)
+        else:
+            name, restype, params = _prototype(m.group("proto"), structs)
+            protos[name] = (restype, params)
+    return consts, structs, protos
 
 
-class ModelDesc(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int), ("input_dim", ctypes.c_int), ("noise_dim", ctypes.c_int), ("h_dim", ctypes.c_int),
-                ("z_dim", ctypes.c_int), ("n_layers", ctypes.c_int), ("act", ctypes.c_int), ("flags", ctypes.c_int)]
+with open(HEADER_PATH) as _f:
+    CONSTANTS, STRUCTS, PROTOTYPES = parse_header(_f.read())
 
+LinSrc, LinearArgs, WgradProblem, CdaeDesc, ModelDesc, ProfileEntry = (STRUCTS["ardae_" + n] for n in (
+    "lin_src", "linear_args", "wgrad_problem", "cdae_desc", "model_desc", "profile_entry"))
+# every symbol include/ardae_hip.h declares: name -> (restype, argtypes)
+EXPORTS = {name: (res, [ctype for _, ctype, _ in params]) for name, (res, params) in PROTOTYPES.items()}
 
-MODEL_NO_CENTER = 1      # ardae_model_desc.flags (residual-conv kinds: do_center=False)
-MODEL_HEAD_SHIFT = 1     # kind 5: sampler-head type in flags bits 1-3 (layout.RESCONV_HEADS)
-MODEL_CLIPPED = 16       # kind 6: MNISTResConvAuxIPVAEClipped (no 'spm4' clip, z0 keeps an unscaled eps0)
-# kinds 3 / 7: NormalDistribution.clip_logvar of the z0 / z heads (models/reparam.py:17-41; flags bits 8-11 / 12-15)
+MODEL_NO_CENTER = CONSTANTS["ARDAE_MODEL_NO_CENTER"]      # ardae_model_desc.flags (residual-conv kinds: do_center=False)
+MODEL_HEAD_SHIFT = CONSTANTS["ARDAE_MODEL_HEAD_SHIFT"]    # kind 5: sampler-head type in flags bits 1-3 (layout.RESCONV_HEADS)
+MODEL_CLIPPED = CONSTANTS["ARDAE_MODEL_CLIPPED"]          # kind 6: MNISTResConvAuxIPVAEClipped (no 'spm4' clip, z0 keeps an unscaled eps0)
+# kinds 3 / 7: NormalDistribution.clip_logvar of the z0 / z heads (models/reparam.py:17-41; flags bits 8-11 / 12-15); the header gives
+# these codes in a comment only
 LOGVAR_CLIP = {None: 0, "none": 0, "hard": 1, "softplus": 2, "spm10": 3, "spm6": 4, "spm5": 5, "spm4": 6, "spm3": 7, "spm2": 8, "tanh": 9, "2tanh": 10}
-MODEL_CLIP_Z0_SHIFT, MODEL_CLIP_Z_SHIFT = 8, 12
-
+MODEL_CLIP_Z0_SHIFT, MODEL_CLIP_Z_SHIFT = CONSTANTS["ARDAE_MODEL_CLIP_Z0_SHIFT"], CONSTANTS["ARDAE_MODEL_CLIP_Z_SHIFT"]
 
 # utils/models.py:14-32 (get_nonlinear_func): all seven names; 'csoftplus' = log(exp(x) + 1) is softplus (evaluated in its accurate form)
-ACT = {"none": 0, None: 0, "relu": 1, "softplus": 2, "csoftplus": 2, "elu": 3, "tanh": 4, "leaky_relu": 5, "swish": 6}
-LOG_RECORD_FLOATS = 16
-EPI_ACT, EPI_DACT, EPI_CHAIN, EPI_DAE_LOSS = 0, 1, 2, 3
-
-# every symbol include/ardae_hip.h declares (checked by tests/test_abi.py)
-EXPORTS = {
-    "ardae_last_error": (ctypes.c_char_p, []),
-    "ardae_abi_version": (ctypes.c_int, []),
-    "ardae_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "ardae_linear_row_tiles": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "ardae_linear_col_panels": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "ardae_pack_weight": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_linear": (ctypes.c_int, [ctypes.POINTER(LinearArgs), ctypes.c_int, ctypes.c_void_p]),
-    "ardae_linear_chain_eligible": (ctypes.c_int, [ctypes.POINTER(LinearArgs), ctypes.c_int, ctypes.c_int]),
-    "ardae_linear_chain": (ctypes.c_int, [ctypes.POINTER(LinearArgs), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "ardae_linear_wide_layers_eligible": (ctypes.c_int, [ctypes.POINTER(LinearArgs), ctypes.c_int, ctypes.c_int]),
-    "ardae_linear_wide_layers": (ctypes.c_int, [ctypes.POINTER(LinearArgs), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "ardae_wgrad_splits": (ctypes.c_int, [ctypes.c_int] * 4),
-    "ardae_wgrad_batch": (ctypes.c_int, [ctypes.POINTER(WgradProblem), ctypes.c_int, ctypes.c_void_p]),
-    "ardae_latent_perturb": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_void_p] * 4),
-    "ardae_latent_perturb_nstd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_void_p] * 4),
-    "ardae_latent_perturb_draw_ok": (ctypes.c_int, [ctypes.c_int] * 3),
-    "ardae_latent_perturb_draw": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_uint64] * 3 +
-                                  [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 5),
-    "ardae_cdae_perturb_fused_ok": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
-    "ardae_cdae_perturb_loss_grads": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 2 + [ctypes.c_float] * 2 + [ctypes.c_uint64] * 3 +
-                                      [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3),
-    "ardae_center_scale": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 2),
-    "ardae_philox_normal": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]),
-    "ardae_philox_uniform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]),
-    "ardae_bernoulli": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-                                       ctypes.c_uint64, ctypes.c_void_p]),
-    "ardae_step_state_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
-    "ardae_philox_normal_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
-    "ardae_philox_normal_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                               ctypes.c_void_p]),
-    "ardae_adam_ref_step_dev": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_adam_ref_step": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_void_p]),
-    "ardae_weight_avg": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p,
-                                         ctypes.c_int64, ctypes.c_void_p]),
-    "ardae_rmsprop_step": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
-    "ardae_sgd_step": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_double, ctypes.c_void_p]),
-    "ardae_cdae_param_floats": (ctypes.c_size_t, [ctypes.POINTER(CdaeDesc)]),
-    "ardae_cdae_packed_floats": (ctypes.c_size_t, [ctypes.POINTER(CdaeDesc)]),
-    "ardae_cdae_workspace_floats": (ctypes.c_size_t, [ctypes.POINTER(CdaeDesc), ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ardae_cdae_pack": (ctypes.c_int, [ctypes.POINTER(CdaeDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_cdae_loss_grads": (ctypes.c_int, [ctypes.POINTER(CdaeDesc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 4),
-    "ardae_model_param_floats": (ctypes.c_size_t, [ctypes.POINTER(ModelDesc)]),
-    "ardae_model_packed_floats": (ctypes.c_size_t, [ctypes.POINTER(ModelDesc)]),
-    "ardae_model_workspace_floats": (ctypes.c_size_t, [ctypes.POINTER(ModelDesc), ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ardae_model_pack": (ctypes.c_int, [ctypes.POINTER(ModelDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_model_encode": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_model_encode_pair": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    "ardae_model_encode_hidden": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_model_encode_hidden_raw": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_model_decode": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_model_loss_rows": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_model_vae_forward": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p]),
-    "ardae_model_vae_backward": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]),
-    "ardae_model_vae_backward_decoder": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                                         ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "ardae_model_vae_backward_sampler": (ctypes.c_int, [ctypes.POINTER(ModelDesc)] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int,
-                                                         ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
-                                                         ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]),
-    "ardae_relaxed_bernoulli": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p]),
-    "ardae_gaussian_sample": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_cholesky_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_log_scalars": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_int, ctypes.c_void_p]),
-    "ardae_gather_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
-    "ardae_profile_enable": (ctypes.c_int, [ctypes.c_int]),
-    "ardae_debug_stamp": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    "ardae_profile_report": (ctypes.c_int, [ctypes.POINTER(ProfileEntry), ctypes.c_int]),
-    "ardae_dp_backend": (ctypes.c_char_p, []),
-    "ardae_dp_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
-    "ardae_dp_comm_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "ardae_dp_comm_query": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 3),
-    "ardae_dp_comm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
-    "ardae_dp_allreduce_mean": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "ardae_cdae_score": (ctypes.c_int, [ctypes.POINTER(CdaeDesc)] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 2),
-}
+ACT = {name: CONSTANTS["ARDAE_ACT_" + code] for name, code in (
+    ("none", "NONE"), (None, "NONE"), ("relu", "RELU"), ("softplus", "SOFTPLUS"), ("csoftplus", "SOFTPLUS"), ("elu", "ELU"), ("tanh", "TANH"),
+    ("leaky_relu", "LEAKY_RELU"), ("swish", "SWISH"))}
+LOG_RECORD_FLOATS = CONSTANTS["ARDAE_LOG_RECORD_FLOATS"]
+EPI_ACT, EPI_DACT, EPI_CHAIN, EPI_DAE_LOSS = (CONSTANTS["ARDAE_EPI_" + n] for n in ("ACT", "DACT", "CHAIN", "DAE_LOSS"))
+WEIGHT_AVG_SWA, WEIGHT_AVG_POLYAK = CONSTANTS["ARDAE_WEIGHT_AVG_SWA"], CONSTANTS["ARDAE_WEIGHT_AVG_POLYAK"]
 
 _lib = None
 
@@ -211,15 +164,23 @@ def check(rc, what="ardae call"):
         raise RuntimeError(f"{what}: HIP error {rc}: {msg}")
 
 
+_dtypes = {}      # "float32" -> torch.float32, filled at first use (torch stays a lazy import)
+
+
+def _device_ptr(t, dtype):
+    want = _dtypes.get(dtype)
+    if want is None:
+        import torch
+        want = _dtypes[dtype] = getattr(torch, dtype)
+    if not (t.is_cuda and t.dtype == want):
+        raise TypeError(f"expected a {dtype} tensor on the GPU, got {t.dtype} on {t.device}")
+    return t.data_ptr()
+
+
 def ptr(t):
     """Device pointer of an fp32 CUDA(HIP) tensor (or None).  Layout is the caller's business (strided views are passed with their
     leading dimension); the engine validates its batches in ArdaeEngine._check_batch."""
-    if t is None:
-        return None
-    import torch
-    if not (t.is_cuda and t.dtype == torch.float32):
-        raise TypeError(f"expected a float32 tensor on the GPU, got {t.dtype} on {t.device}")
-    return ctypes.c_void_p(t.data_ptr())
+    return None if t is None else ctypes.c_void_p(_device_ptr(t, "float32"))
 
 
 def stream_ptr():
@@ -227,9 +188,50 @@ def stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# call("ardae_X", ...) / query("ardae_X", ...): tensors, descs and numbers in the header's parameter order.  Only data pointers need
+# a conversion of their own (None and ctypes objects pass; `argtypes` converts numbers and takes a struct, or a c_int / c_void_p
+# out-parameter, by reference where the parameter is a pointer to one).  One plan per entry point, made here once.
+# ---------------------------------------------------------------------------------------------------------------
+def _typed(dtype):
+    return lambda t: _device_ptr(t, dtype) if hasattr(t, "data_ptr") else t
+
+
+_CONVERT = {"float": _typed("float32"), "int64_t": _typed("int64"),
+            # the step state block, stamp slots, the host-side RCCL id: no dtype or device rule
+            "void": lambda t: t.data_ptr() if hasattr(t, "data_ptr") else t}
+_CONVERT["unsigned long long"] = _CONVERT["void"]
+# name -> (per-parameter converter or None, whether the last parameter is `stream`)
+_PLANS = {name: (tuple(_CONVERT.get(pointee) for _, _, pointee in params), bool(params) and params[-1][0] == "stream")
+          for name, (_, params) in PROTOTYPES.items()}
+
+
+def _invoke(name, args):
+    plan, has_stream = _PLANS[name]
+    missing = len(plan) - len(args)
+    if missing and not (missing == 1 and has_stream):
+        raise TypeError(f"{name} takes {len(plan)} arguments{' (the trailing stream is optional)' if has_stream else ''}, got {len(args)}")
+    argv = [a if conv is None else conv(a) for conv, a in zip(plan, args)]
+    if missing:
+        import torch
+        argv.append(torch.cuda.current_stream().cuda_stream)
+    return getattr(_lib or lib(), name)(*argv)
+
+
+def call(name, *args):
+    """An entry point that returns a status: ValueError (status < 0) / RuntimeError (> 0) carrying its name and the library's message.
+    A trailing `stream` parameter may be left out: PyTorch's current stream."""
+    check(_invoke(name, args), name)
+
+
+def query(name, *args):
+    """An entry point that returns a value (*_floats, *_ok, *_eligible, ardae_wgrad_splits, ...)."""
+    return _invoke(name, args)
+
+
 def profile_report(max_entries=64):
     """Per-kernel (name, calls, total_ms, flops, bytes) since ardae_profile_enable(1); synchronises and clears the log."""
     buf = (ProfileEntry * max_entries)()
-    n = lib().ardae_profile_report(buf, max_entries)
+    n = query("ardae_profile_report", buf, max_entries)
     return [dict(name=buf[i].name.decode(), calls=buf[i].calls, total_ms=buf[i].total_ms, flops=buf[i].flops, bytes=buf[i].bytes)
             for i in range(min(n, max_entries))]

@@ -7,6 +7,15 @@
 #include "linear.h"
 #include "wgrad.h"
 
+// The struct layout the ctypes binding derives from the header, as THIS compiler lays it out: the same numbers are asserted
+// for the derived classes in tests/test_abi.py::test_struct_layout_matches_the_compiler (written down twice on purpose).
+static_assert(sizeof(ardae_lin_src) == 24, "ardae_lin_src");
+static_assert(sizeof(ardae_linear_args) == 232 && offsetof(ardae_linear_args, tile_loss) == 224, "ardae_linear_args");
+static_assert(sizeof(ardae_wgrad_problem) == 144 && offsetof(ardae_wgrad_problem, beta) == 140, "ardae_wgrad_problem");
+static_assert(sizeof(ardae_cdae_desc) == 24, "ardae_cdae_desc");
+static_assert(sizeof(ardae_model_desc) == 32, "ardae_model_desc");
+static_assert(sizeof(ardae_profile_entry) == 128, "ardae_profile_entry");
+
 namespace ardae {
 static thread_local char g_last_error[512] = "";
 void set_last_error(const char* fmt, ...) {

@@ -7,7 +7,6 @@
                          the same number of points per mixture component, labels 0..24 in grid order)
 Both draw from the library's Philox stream (`rng.manual_seed`), like the engine's noise.
 """
-import ctypes
 import math
 
 import torch
@@ -24,8 +23,7 @@ def dynamic_binarize(probs, out=None):
     out = torch.empty_like(p2) if out is None else out
     # ardae_bernoulli takes one probability per column; a full [B, D] table is B*D columns of a single row
     st = rng.get_state()
-    L.check(L.lib().ardae_bernoulli(L.ptr(p2), 1, p2.numel(), L.ptr(out), ctypes.c_uint64(st["seed"]), ctypes.c_uint64(rng._next_offset()),
-                                    L.stream_ptr()), "ardae_bernoulli")
+    L.call("ardae_bernoulli", p2, 1, p2.numel(), out, st["seed"], rng._next_offset())
     return out.view_as(probs)
 
 
@@ -67,8 +65,7 @@ class StaticBinarizedSource:
         p = ((torch.rand(input_dim, generator=g) < 0.2).float() * 0.6 + 0.03).to(device)
         table = torch.empty(num_rows, input_dim, device=device)
         st = rng.get_state()
-        L.check(L.lib().ardae_bernoulli(L.ptr(p), num_rows, input_dim, L.ptr(table), ctypes.c_uint64(st["seed"]), ctypes.c_uint64(rng._next_offset()),
-                                        L.stream_ptr()), "ardae_bernoulli")
+        L.call("ardae_bernoulli", p, num_rows, input_dim, table, st["seed"], rng._next_offset())
         return cls(table, seed)
 
     @classmethod
@@ -89,6 +86,5 @@ class StaticBinarizedSource:
         self._pos += batch_size
         self.last_indices = idx
         out = torch.empty(batch_size, self.table.size(1), device=self.table.device) if out is None else out
-        L.check(L.lib().ardae_gather_rows(L.ptr(self.table), ctypes.c_void_p(idx.data_ptr()), batch_size, self.table.size(1), L.ptr(out),
-                                          L.stream_ptr()), "ardae_gather_rows")
+        L.call("ardae_gather_rows", self.table, idx, batch_size, self.table.size(1), out)
         return out

@@ -62,11 +62,10 @@ class DpComm:
     def __init__(self, group=None):
         from . import _lib as L
         self._L, self._h = L, ctypes.c_void_p()
-        lib = L.lib()
         self.world, self.rank = world_size(group), rank(group)
         uid = torch.zeros(128, dtype=torch.uint8)
         if self.rank == 0:
-            L.check(lib.ardae_dp_unique_id(ctypes.c_void_p(uid.data_ptr())), "ardae_dp_unique_id")
+            L.call("ardae_dp_unique_id", uid)
         if self.world > 1:
             backend = str(torch.distributed.get_backend(group))
             if "gloo" in backend:
@@ -75,23 +74,23 @@ class DpComm:
                 d = uid.cuda()
                 torch.distributed.broadcast(d, src=torch.distributed.get_global_rank(group, 0) if group is not None else 0, group=group)
                 uid = d.cpu()
-        L.check(lib.ardae_dp_comm_create(ctypes.c_void_p(uid.data_ptr()), self.world, self.rank, ctypes.byref(self._h)), "ardae_dp_comm_create")
-        self.backend = lib.ardae_dp_backend().decode()
+        L.call("ardae_dp_comm_create", uid, self.world, self.rank, self._h)         # comm_out: argtypes passes the handle by reference
+        self.backend = L.query("ardae_dp_backend").decode()
 
     def query(self):
         """(ranks, rank, device) as RCCL reports them."""
         n, r, d = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        self._L.check(self._L.lib().ardae_dp_comm_query(self._h, ctypes.byref(n), ctypes.byref(r), ctypes.byref(d)), "ardae_dp_comm_query")
+        self._L.call("ardae_dp_comm_query", self._h, n, r, d)
         return n.value, r.value, d.value
 
     def allreduce_mean_(self, flat):
         """In-place mean over the ranks on the current stream (capturable)."""
         if not flat.is_contiguous():
             raise ValueError("the gradient buffer must be contiguous")
-        self._L.check(self._L.lib().ardae_dp_allreduce_mean(self._h, self._L.ptr(flat), flat.numel(), self._L.stream_ptr()), "ardae_dp_allreduce_mean")
+        self._L.call("ardae_dp_allreduce_mean", self._h, flat, flat.numel())
         return flat
 
     def close(self):
         if self._h:
-            self._L.check(self._L.lib().ardae_dp_comm_destroy(self._h), "ardae_dp_comm_destroy")
+            self._L.call("ardae_dp_comm_destroy", self._h)
             self._h = ctypes.c_void_p()

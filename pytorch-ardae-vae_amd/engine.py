@@ -6,7 +6,6 @@ Data parallel: the image batch is sharded over ranks, parameters are
 buffers are all-reduced (RCCL over xGMI via torch.distributed backend "nccl") before their optimiser steps.
 """
 import contextlib
-import ctypes
 import os
 from dataclasses import dataclass
 
@@ -81,22 +80,19 @@ class _FlatOpt:
     def adam(self):
         return self.kind in ("adam", "amsgrad")
 
-    def advance(self, lib, rng_inc=0):
-        L.check(lib.ardae_step_state_advance(ctypes.c_void_p(self.state.data_ptr()), ctypes.c_uint64(rng_inc), self.lr, self.beta1, 0.999,
-                                             L.stream_ptr()), "ardae_step_state_advance")
+    def advance(self, rng_inc=0):
+        L.call("ardae_step_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999)
 
-    def apply(self, lib, grads, in_step):
-        st, p, g = L.stream_ptr(), L.ptr(self.flat), L.ptr(grads)
+    def apply(self, grads, in_step):
+        p, g = self.flat, grads
         if self.kind == "sgd":
-            L.check(lib.ardae_sgd_step(p, g, self.n, self.lr, st), "ardae_sgd_step")
+            L.call("ardae_sgd_step", p, g, self.n, self.lr)
         elif self.kind == "rmsprop":
-            L.check(lib.ardae_rmsprop_step(p, g, L.ptr(self.a), L.ptr(self.b), self.n, self.lr, 0.99, 1e-8, self.momentum, st), "ardae_rmsprop_step")
+            L.call("ardae_rmsprop_step", p, g, self.a, self.b, self.n, self.lr, 0.99, 1e-8, self.momentum)
         elif in_step:      # t and the bias corrections come from the device block (advanced inside the step)
-            L.check(lib.ardae_adam_ref_step_dev(p, g, L.ptr(self.a), L.ptr(self.b), L.ptr(self.c) if self.c is not None else None, self.n,
-                                                self.beta1, 0.999, 1e-8, ctypes.c_void_p(self.state.data_ptr()), st), "ardae_adam_ref_step_dev")
+            L.call("ardae_adam_ref_step_dev", p, g, self.a, self.b, self.c, self.n, self.beta1, 0.999, 1e-8, self.state)
         else:
-            L.check(lib.ardae_adam_ref_step(p, g, L.ptr(self.a), L.ptr(self.b), L.ptr(self.c) if self.c is not None else None, self.n,
-                                            self.lr, self.beta1, 0.999, 1e-8, self.steps + 1, st), "ardae_adam_ref_step")
+            L.call("ardae_adam_ref_step", p, g, self.a, self.b, self.c, self.n, self.lr, self.beta1, 0.999, 1e-8, self.steps + 1)
 
     # torch.optim.Optimizer.state_dict() pieces (per-parameter views of the flat buffers)
     def state_names(self):
@@ -141,7 +137,6 @@ class ArdaeEngine:
         self.model, self.cdae, self.cfg = model, cdae, cfg
         self.B = int(batch_size)                       # per-rank image batch
         self.dev = model._flat.device
-        self.lib = L.lib()
         self.pg = process_group
         self.world = dist.world_size(process_group)
         self.rank = dist.rank(process_group)
@@ -182,15 +177,14 @@ class ArdaeEngine:
         if int(cdae.context_dim) != ctx_dim:
             raise ValueError(f"cdae.context_dim = {cdae.context_dim}, but the {cfg.cdae_ctx_type} context has {ctx_dim} columns")
         f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
-        lib = self.lib
         S = nzc * int(cfg.nstd_cdae)            # rows per image of the cDAE update (ivae_ardae.py:759-767)
-        ws_floats = max(lib.ardae_cdae_workspace_floats(ctypes.byref(cd), B, S, 1),
-                        lib.ardae_model_workspace_floats(ctypes.byref(md), B, nzc, 3))
+        ws_floats = max(L.query("ardae_cdae_workspace_floats", cd, B, S, 1),
+                        L.query("ardae_model_workspace_floats", md, B, nzc, 3))
         self.ws = f(ws_floats)
-        self.ws_vae = f(lib.ardae_model_workspace_floats(ctypes.byref(md), B, nzm, 1))
-        self.ws_small = f(max(lib.ardae_cdae_workspace_floats(ctypes.byref(cd), B, nzm, 0),
-                              lib.ardae_model_workspace_floats(ctypes.byref(md), B, 1, 0)))
-        self.ws_small_v = f(lib.ardae_model_workspace_floats(ctypes.byref(md), B, 1, 0))   # VAE-side encode(std=0): may run beside the cDAE phase
+        self.ws_vae = f(L.query("ardae_model_workspace_floats", md, B, nzm, 1))
+        self.ws_small = f(max(L.query("ardae_cdae_workspace_floats", cd, B, nzm, 0),
+                              L.query("ardae_model_workspace_floats", md, B, 1, 0)))
+        self.ws_small_v = f(L.query("ardae_model_workspace_floats", md, B, 1, 0))   # VAE-side encode(std=0): may run beside the cDAE phase
         self.z0, self.latent = f(B, z), f(N, z)
         self.noise_s, self.xi, self.eps = f(model._noise_numel(B, nzc)), f(B * S), f(B * S, z)
         self.xbar, self.sigma, self.std_b = f(B * S, z), f(B * S), f(B)
@@ -237,7 +231,7 @@ class ArdaeEngine:
         self._cap_stream = torch.cuda.Stream(device=self.dev)
         self._stamps = None                             # diagnostics: see enable_stamps()
         self._log = None                                # scalar log channel (scalar_log.ScalarLog), one more launch at the end of the step
-        self.opt_m.advance(self.lib, self.RNG_STRIDE)   # the step state always describes the COMING step (t = 1, first Philox block)
+        self.opt_m.advance(self.RNG_STRIDE)   # the step state always describes the COMING step (t = 1, first Philox block)
         self.repack()
 
     def attach_log(self, log):
@@ -252,10 +246,10 @@ class ArdaeEngine:
         self.pk_c = self.cdae._packed_weights()
 
     def _pack_model(self):
-        L.check(self.lib.ardae_model_pack(ctypes.byref(self.model._desc), L.ptr(self.model._flat), L.ptr(self.pk_m), L.stream_ptr()))
+        L.call("ardae_model_pack", self.model._desc, self.model._flat, self.pk_m)
 
     def _pack_cdae(self):
-        L.check(self.lib.ardae_cdae_pack(ctypes.byref(self.cdae._desc), L.ptr(self.cdae._flat), L.ptr(self.pk_c), L.stream_ptr()))
+        L.call("ardae_cdae_pack", self.cdae._desc, self.cdae._flat, self.pk_c)
 
     def _check_batch(self, x, what):
         """The kernels read exactly B * input_dim contiguous floats from each batch pointer: anything else (a ragged last batch
@@ -273,22 +267,16 @@ class ArdaeEngine:
             raise ValueError(f"{what}: expected a tensor on {self.dev}, got one on {x.device}")
 
     def _encode(self, x, noise, nz, out, ws):
-        L.check(self.lib.ardae_model_encode(ctypes.byref(self.model._desc), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x),
-                                            L.ptr(noise) if noise is not None else None, self.B, nz, L.ptr(ws), ws.numel(),
-                                            L.ptr(out), L.stream_ptr()), "ardae_model_encode")
+        L.call("ardae_model_encode", self.model._desc, self.model._flat, self.pk_m, x, noise, self.B, nz, ws, ws.numel(), out)
 
     def _hidden(self, x, z0_out, out, ws, raws=None):
         """The std = 0 pass of an aux sampler: latent mean z0 AND the hidden1a context in one go.  raws [2, B, z0_dim] (clipped class):
         two passes - the context with draw 0, the latent mean with draw 1."""
         if self.clipped:
-            md, st = self.model._desc, L.stream_ptr()
             for k, (zo, ho) in enumerate(((None, out), (z0_out, None))):
-                L.check(self.lib.ardae_model_encode_hidden_raw(ctypes.byref(md), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), L.ptr(raws[k]), self.B,
-                                                               L.ptr(ws), ws.numel(), None if zo is None else L.ptr(zo), None if ho is None else L.ptr(ho), st),
-                        "ardae_model_encode_hidden_raw")
+                L.call("ardae_model_encode_hidden_raw", self.model._desc, self.model._flat, self.pk_m, x, raws[k], self.B, ws, ws.numel(), zo, ho)
             return
-        L.check(self.lib.ardae_model_encode_hidden(ctypes.byref(self.model._desc), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), self.B,
-                                                   L.ptr(ws), ws.numel(), L.ptr(z0_out), L.ptr(out), L.stream_ptr()), "ardae_model_encode_hidden")
+        L.call("ardae_model_encode_hidden", self.model._desc, self.model._flat, self.pk_m, x, self.B, ws, ws.numel(), z0_out, out)
 
     # ------------------------------------------------------------------------------------------------------------
     # The step as a plan.  A segment is ("run", name, stream, deps, fn) or ("allreduce", tensor); `_units` merges neighbouring
@@ -323,7 +311,7 @@ class ArdaeEngine:
             self._model_update()
             if self._log is not None:
                 self._log.record(cfg.beta if beta is None else beta)
-            self.opt_m.advance(self.lib, self.RNG_STRIDE)       # for the NEXT step: Philox base += stride, model optimiser's t += 1
+            self.opt_m.advance(self.RNG_STRIDE)       # for the NEXT step: Philox base += stride, model optimiser's t += 1
         segs.append(("run", "model_update", "main", (), model_update))
         if self._stamps is not None:
             def wrap(name, fn):
@@ -431,8 +419,7 @@ class ArdaeEngine:
             k = draw
         if k >= self.RNG_STRIDE:
             raise RuntimeError("more Philox draws in one step than RNG_STRIDE reserves")
-        L.check(self.lib.ardae_philox_normal_at(L.ptr(out), out.numel(), ctypes.c_uint64(rng.get_state()["seed"]), ctypes.c_uint64(k),
-                                                ctypes.c_void_p(self.state.data_ptr()), ctypes.c_uint64(first), L.stream_ptr()), "ardae_philox_normal_at")
+        L.call("ardae_philox_normal_at", out, out.numel(), rng.get_state()["seed"], k, self.state, first)
         return out
 
     # ------------------------------------------------------------------------------------------------------------
@@ -449,12 +436,12 @@ class ArdaeEngine:
         """ivae_ardae.py:713-776: sampler on N rows, latent statistics, perturbation, cDAE loss and its gradients (local shard).
         draw0: index of the first of this update's three Philox draws inside the step."""
         self._check_batch(x, "cdae_phase")
-        cfg, lib, st = self.cfg, self.lib, L.stream_ptr()
+        cfg = self.cfg
         B, nz, z = self.B, cfg.nz_cdae, self.model.z_dim
         nstd = int(cfg.nstd_cdae)
         # inside a step the sigma- and eps-draws are made by the perturbation kernel itself where the shape allows (same Philox
         # keying as the separate draws: same numbers, two launches less)
-        fused = (not noise) and self._in_step and draw0 is not None and self.fused_draws and bool(lib.ardae_latent_perturb_draw_ok(nz, nstd, z))
+        fused = (not noise) and self._in_step and draw0 is not None and self.fused_draws and bool(L.query("ardae_latent_perturb_draw_ok", nz, nstd, z))
         if noise:
             ns, xi, eps = noise["sampler"], noise["sigma"].reshape(-1), noise["eps"]
         else:
@@ -474,40 +461,31 @@ class ArdaeEngine:
             self._encode(x, ns, nz, self.latent, self.ws)
         else:
             # context == latent_mean == encode(x, std=0) (lt0) and forward_hidden(x, nz) share the per-image trunk: one pass
-            L.check(lib.ardae_model_encode_pair(ctypes.byref(self.model._desc), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), L.ptr(ns), B, nz,
-                                                L.ptr(self.ws), self.ws.numel(), L.ptr(self.z0), L.ptr(self.latent), 0, st),
-                    "ardae_model_encode_pair")
+            L.call("ardae_model_encode_pair", self.model._desc, self.model._flat, self.pk_m, x, ns, B, nz, self.ws, self.ws.numel(), self.z0,
+                   self.latent, 0)
         if self.data_ctx:
             self._data_context(x, self.ctx_c)
         self._stamp("  sampler done")
-        if fused and self.fused_first_layer and bool(lib.ardae_cdae_perturb_fused_ok(ctypes.byref(self.cdae._desc), nz, nstd)):
+        if fused and self.fused_first_layer and bool(L.query("ardae_cdae_perturb_fused_ok", self.cdae._desc, nz, nstd)):
             # north star's "fused per-sample Gaussian-perturb + sigma-scaling + DAE-forward kernel", then the cDAE from its second layer on
-            L.check(lib.ardae_cdae_perturb_loss_grads(ctypes.byref(self.cdae._desc), L.ptr(self.cdae._flat), L.ptr(self.pk_c), L.ptr(self.latent),
-                                                      L.ptr(self.z0), L.ptr(self.ctx_c), B, nz, cfg.std_scale, cfg.delta,
-                                                      ctypes.c_uint64(rng.get_state()["seed"]), ctypes.c_uint64(d[1]), ctypes.c_uint64(d[2]),
-                                                      ctypes.c_void_p(self.state.data_ptr()), ctypes.c_uint64(self.rank * B * nz),
-                                                      L.ptr(self.xbar), L.ptr(self.sigma), L.ptr(eps), L.ptr(self.std_b), L.ptr(self.ws),
-                                                      self.ws.numel(), L.ptr(self.loss_c), L.ptr(self.grads_c), st),
-                    "ardae_cdae_perturb_loss_grads")
+            L.call("ardae_cdae_perturb_loss_grads", self.cdae._desc, self.cdae._flat, self.pk_c, self.latent, self.z0, self.ctx_c, B, nz,
+                   cfg.std_scale, cfg.delta, rng.get_state()["seed"], d[1], d[2], self.state, self.rank * B * nz, self.xbar, self.sigma, eps,
+                   self.std_b, self.ws, self.ws.numel(), self.loss_c, self.grads_c)
             return
         if fused:
-            L.check(lib.ardae_latent_perturb_draw(L.ptr(self.latent), L.ptr(self.z0), B, nz, z, cfg.std_scale, cfg.delta,
-                                                  ctypes.c_uint64(rng.get_state()["seed"]), ctypes.c_uint64(d[1]), ctypes.c_uint64(d[2]),
-                                                  ctypes.c_void_p(self.state.data_ptr()), ctypes.c_uint64(self.rank * B * nz),
-                                                  L.ptr(self.xbar), L.ptr(self.sigma), L.ptr(eps), L.ptr(self.std_b), st),
-                    "ardae_latent_perturb_draw")
+            L.call("ardae_latent_perturb_draw", self.latent, self.z0, B, nz, z, cfg.std_scale, cfg.delta, rng.get_state()["seed"], d[1], d[2],
+                   self.state, self.rank * B * nz, self.xbar, self.sigma, eps, self.std_b)
         else:
-            L.check(lib.ardae_latent_perturb_nstd(L.ptr(self.latent), L.ptr(self.z0), L.ptr(xi), L.ptr(eps), B, nz, nstd, z, cfg.std_scale, cfg.delta,
-                                                  L.ptr(self.xbar), L.ptr(self.sigma), L.ptr(self.std_b), st), "ardae_latent_perturb_nstd")
-        L.check(lib.ardae_cdae_loss_grads(ctypes.byref(self.cdae._desc), L.ptr(self.cdae._flat), L.ptr(self.pk_c), L.ptr(self.xbar),
-                                          L.ptr(self.sigma), L.ptr(eps), L.ptr(self.ctx_c), B, nz * nstd, L.ptr(self.ws), self.ws.numel(),
-                                          L.ptr(self.loss_c), L.ptr(self.grads_c), None, st), "ardae_cdae_loss_grads")
+            L.call("ardae_latent_perturb_nstd", self.latent, self.z0, xi, eps, B, nz, nstd, z, cfg.std_scale, cfg.delta, self.xbar, self.sigma,
+                   self.std_b)
+        L.call("ardae_cdae_loss_grads", self.cdae._desc, self.cdae._flat, self.pk_c, self.xbar, self.sigma, eps, self.ctx_c, B, nz * nstd,
+               self.ws, self.ws.numel(), self.loss_c, self.grads_c, None)
 
     def _cdae_update(self):
         """ivae_ardae.py:777-779: the cDAE optimiser's step on the (rank-averaged) gradients, then the weight re-pack."""
         if self._in_step and self.opt_c.adam:
-            self.opt_c.advance(self.lib)           # the cDAE's own Adam block: t advances once per cDAE update
-        self.opt_c.apply(self.lib, self.grads_c, self._in_step)
+            self.opt_c.advance()           # the cDAE's own Adam block: t advances once per cDAE update
+        self.opt_c.apply(self.grads_c, self._in_step)
         if not self._in_step:
             self.opt_c.steps += 1
         self._pack_cdae()
@@ -515,20 +493,18 @@ class ArdaeEngine:
     def _data_context(self, x, out):
         """--cdae-ctx-type data: the flattened image, centred to 2x - 1 for the MNIST family (ivae_ardae.py:730-734,809-813)."""
         D = int(self.model.input_dim)
-        L.check(self.lib.ardae_center_scale(L.ptr(x), L.ptr(self._ctx_half), self.B, 1, D, 2.0 if self.cfg.ctx_data_center else 1.0, L.ptr(out),
-                                            L.stream_ptr()), "ardae_center_scale")
+        L.call("ardae_center_scale", x, self._ctx_half, self.B, 1, D, 2.0 if self.cfg.ctx_data_center else 1.0, out)
 
     def vae_forward_part(self, x, noise=None, beta=None, draw=None):
         """ivae_ardae.py:781-827: everything of the VAE update that does not involve the cDAE (forward, ELBO pieces, z0, u)."""
         self._require_trained("vae_forward_part()")
         self._check_batch(x, "vae_forward_part")
-        cfg, lib, st = self.cfg, self.lib, L.stream_ptr()
+        cfg = self.cfg
         beta = cfg.beta if beta is None else beta
         B, nz, md = self.B, cfg.nz_model, self.model._desc
         nv = noise["vae"] if noise else self._normal(self.noise_v, draw)
-        L.check(lib.ardae_model_vae_forward(ctypes.byref(md), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), L.ptr(nv), B, nz,
-                                            float(beta), L.ptr(self.ws_vae), self.ws_vae.numel(), L.ptr(self.zv), L.ptr(self.losses_m), st),
-                "ardae_model_vae_forward")
+        L.call("ardae_model_vae_forward", md, self.model._flat, self.pk_m, x, nv, B, nz, float(beta), self.ws_vae, self.ws_vae.numel(), self.zv,
+               self.losses_m)
         if self.hidden_ctx:      # context and latent mean of the VAE batch: one std = 0 pass (ivae_ardae.py:815-817,826)
             raws = None
             if self.clipped:
@@ -541,12 +517,11 @@ class ArdaeEngine:
             self._encode(x, None, 1, self.z0v, self.ws_small_v)
         if self.data_ctx:
             self._data_context(x, self.ctx_v)
-        L.check(lib.ardae_center_scale(L.ptr(self.zv), L.ptr(self.z0v), B, nz, self.model.z_dim, cfg.std_scale, L.ptr(self.u), st))
+        L.call("ardae_center_scale", self.zv, self.z0v, B, nz, self.model.z_dim, cfg.std_scale, self.u)
         if self.split_backward:
             # model_loss.backward() through the decoder down to dL/dz (ivae_ardae.py:804) needs nothing from the cDAE either
-            L.check(lib.ardae_model_vae_backward_decoder(ctypes.byref(md), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), L.ptr(nv), B, nz,
-                                                         float(beta), 1.0, L.ptr(self.ws_vae), self.ws_vae.numel(), st),
-                    "ardae_model_vae_backward_decoder")
+            L.call("ardae_model_vae_backward_decoder", md, self.model._flat, self.pk_m, x, nv, B, nz, float(beta), 1.0, self.ws_vae,
+                   self.ws_vae.numel())
         return nv
 
     def vae_backward_part(self, x, nv, beta=None, apply_update=True):
@@ -560,36 +535,32 @@ class ArdaeEngine:
 
     def _vae_backward_grads(self, x, nv, beta=None):
         self._check_batch(x, "vae_backward_part")
-        cfg, lib, st = self.cfg, self.lib, L.stream_ptr()
+        cfg = self.cfg
         beta = cfg.beta if beta is None else beta
         B, nz, md = self.B, cfg.nz_model, self.model._desc
-        L.check(lib.ardae_cdae_score(ctypes.byref(self.cdae._desc), L.ptr(self.cdae._flat), L.ptr(self.pk_c), L.ptr(self.u),
-                                     L.ptr(self.sigma0), L.ptr(self.ctx_v), B, nz, L.ptr(self.ws_small), self.ws_small.numel(),
-                                     L.ptr(self.g), st), "ardae_cdae_score")
+        L.call("ardae_cdae_score", self.cdae._desc, self.cdae._flat, self.pk_c, self.u, self.sigma0, self.ctx_v, B, nz, self.ws_small,
+               self.ws_small.numel(), self.g)
         # seed of (s (z - z0)).backward(beta g / (B nz)) w.r.t. z  (ivae_ardae.py:834); B is the per-rank batch because the
         # ranks' gradients are averaged afterwards (mean over ranks of 1/B_local == 1/B_global sum)
         seed_scale = dist.entropy_seed_scale(cfg.std_scale, beta, B, nz)
         if self.split_backward:      # the decoder half already ran in vae_forward_part
-            L.check(lib.ardae_model_vae_backward_sampler(ctypes.byref(md), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), L.ptr(nv), B, nz,
-                                                         L.ptr(self.g), float(seed_scale), L.ptr(self.ws_vae), self.ws_vae.numel(),
-                                                         L.ptr(self.grads_m), 0.0, st), "ardae_model_vae_backward_sampler")
+            L.call("ardae_model_vae_backward_sampler", md, self.model._flat, self.pk_m, x, nv, B, nz, self.g, float(seed_scale), self.ws_vae,
+                   self.ws_vae.numel(), self.grads_m, 0.0)
         else:
             self.g.mul_(seed_scale)
-            L.check(lib.ardae_model_vae_backward(ctypes.byref(md), L.ptr(self.model._flat), L.ptr(self.pk_m), L.ptr(x), L.ptr(nv), B, nz,
-                                                 float(beta), 1.0, L.ptr(self.g), L.ptr(self.ws_vae), self.ws_vae.numel(), L.ptr(self.grads_m),
-                                                 0.0, st), "ardae_model_vae_backward")
+            L.call("ardae_model_vae_backward", md, self.model._flat, self.pk_m, x, nv, B, nz, float(beta), 1.0, self.g, self.ws_vae,
+                   self.ws_vae.numel(), self.grads_m, 0.0)
 
     def _model_update(self):
-        self.opt_m.apply(self.lib, self.grads_m, self._in_step)   # in a step: t and the bias corrections come from the device step state
+        self.opt_m.apply(self.grads_m, self._in_step)   # in a step: t and the bias corrections come from the device step state
         if self.avg is not None:
             # t from the device block (not yet advanced: it still holds this step's t), so a replayed graph averages at the right steps
-            L.check(self.lib.ardae_weight_avg(L.ptr(self.avg), L.ptr(self.model._flat), self.avg.numel(), WEIGHT_AVG_KINDS[self.wavg],
-                                              float(self.cfg.m_weight_avg_decay), self._avg_origin, ctypes.c_void_p(self.state.data_ptr()), 0,
-                                              L.stream_ptr()), "ardae_weight_avg")
+            L.call("ardae_weight_avg", self.avg, self.model._flat, self.avg.numel(), WEIGHT_AVG_KINDS[self.wavg], float(self.cfg.m_weight_avg_decay),
+                   self._avg_origin, self.state, 0)
         if not self._in_step:
             self.step_count += 1
             self.opt_m.steps = self.step_count
-            self.opt_m.advance(self.lib, self.RNG_STRIDE)   # phase calls made directly keep the device block (t of the coming step) in step
+            self.opt_m.advance(self.RNG_STRIDE)   # phase calls made directly keep the device block (t of the coming step) in step
         self._pack_model()
 
     def vae_phase(self, x, noise=None, beta=None, apply_update=True):
@@ -625,7 +596,7 @@ class ArdaeEngine:
             return
         if name not in st["names"]:
             st["names"].append(name)
-        L.check(self.lib.ardae_debug_stamp(ctypes.c_void_p(st["buf"].data_ptr()), st["names"].index(name), L.stream_ptr()), "ardae_debug_stamp")
+        L.call("ardae_debug_stamp", st["buf"], st["names"].index(name))
 
     def read_stamps(self):
         st = self._stamps
@@ -656,9 +627,7 @@ class ArdaeEngine:
         if self.use_graph and noise is None:
             b = float(self.cfg.beta if beta is None else beta)
             # static copies of the batches (one per DISTINCT batch object: --num-cdae-updates k on one tensor shares its copy)
-            if self._xc is None or len(self._xc) != len(xs):
-                flat = lambda: torch.empty(self.B, self.model.input_dim, device=self.dev, dtype=torch.float32)
-                self._xc, self._xv, self._graph = [flat() for _ in xs], flat(), None
+            self._static_batches(len(xs))
             for buf, x in zip(self._xc, xs):      # batches were validated above: B x input_dim contiguous floats, whatever their view shape
                 if x is not buf:
                     buf.copy_(x.view(self.B, -1))
@@ -700,11 +669,14 @@ class ArdaeEngine:
         """The engine's static batch buffers ([B, input_dim] each: one per cDAE update, and the VAE batch's): a producer that
         already works on the device (dynamic binarisation, a gather from a resident table) writes the next batches THERE and
         passes the same tensors to step(), which then has nothing to copy."""
-        n = self.cfg.num_cdae_updates if n_cdae is None else int(n_cdae)
+        self._static_batches(self.cfg.num_cdae_updates if n_cdae is None else int(n_cdae))
+        return list(self._xc), self._xv
+
+    def _static_batches(self, n):
+        """Make sure there are n cDAE batch buffers and the VAE one; new buffers invalidate a captured step."""
         if self._xc is None or len(self._xc) != n:
             flat = lambda: torch.empty(self.B, self.model.input_dim, device=self.dev, dtype=torch.float32)
             self._xc, self._xv, self._graph = [flat() for _ in range(n)], flat(), None
-        return list(self._xc), self._xv
 
     def _count_step(self, n_cdae_updates):
         self.step_count += 1
@@ -813,12 +785,12 @@ class ArdaeEngine:
             if int(eng.get("state_version", 1)) < 2:
                 # written before round 3: the block still described the step just DONE (t == step_count, that step's Philox offsets) -
                 # advance it once, or Adam's t would lag by one for good and the first resumed step would repeat the last step's noise
-                self.opt_m.advance(self.lib, self.RNG_STRIDE)
+                self.opt_m.advance(self.RNG_STRIDE)
         else:                   # written by the reference / the module path: the optimisers' t, and Philox offsets this run has not used yet
             self.state.zero_()      # (a resumed run with an unchanged seed would otherwise replay the draws of steps 1..step_count)
             self.state[0] = self.RNG_STRIDE * self.step_count
             self.state[1] = self.step_count
-            self.opt_m.advance(self.lib, self.RNG_STRIDE)
+            self.opt_m.advance(self.RNG_STRIDE)
         self.opt_c.state.zero_()
         self.opt_c.state[1] = self.opt_c.steps
         if self.avg is not None:

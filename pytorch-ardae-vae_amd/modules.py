@@ -8,7 +8,6 @@ names and argument meaning, same exception types.  Parameters are `nn.Parameter`
 (the layout the C ABI consumes); forward/backward are `torch.autograd.Function`s that call the ABI.  There is no
 PyTorch fallback: on a CPU tensor or without the built library these modules raise.
 """
-import ctypes
 import math
 import weakref
 
@@ -118,6 +117,19 @@ class FlatParamModule(nn.Module):
     def _ws(self, nfloats):
         return torch.empty(nfloats, device=self._flat.device, dtype=torch.float32)
 
+    _packed_floats_fn = _pack_fn = None      # the network family's two entry points (ardae_cdae_* | ardae_model_*)
+
+    def _packed_weights(self):
+        """MFMA-lane-linear image of the current weights (policy: _pack_is_current; the fused engine keeps its own image and re-packs
+        right after its own optimiser kernels)."""
+        if self._pack_is_current():
+            return self._packed
+        if self._packed is None:
+            self._packed = self._ws(L.query(self._packed_floats_fn, self._desc))
+        L.call(self._pack_fn, self._desc, self._flat, self._packed)
+        self._note_packed()
+        return self._packed
+
 
 def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
@@ -136,14 +148,11 @@ class _CdaeLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mod, xbar, sigma, eps, context, B, S, *params):
-        lib = L.lib()
         d = mod._desc
-        ws = mod._ws(lib.ardae_cdae_workspace_floats(ctypes.byref(d), B, S, 1))
+        ws = mod._ws(L.query("ardae_cdae_workspace_floats", d, B, S, 1))
         loss = torch.empty(1, device=xbar.device)
         grads = torch.zeros_like(mod._flat)
-        L.check(lib.ardae_cdae_loss_grads(ctypes.byref(d), L.ptr(mod._flat), L.ptr(mod._packed_weights()), L.ptr(xbar), L.ptr(sigma),
-                                          L.ptr(eps), L.ptr(context), B, S, L.ptr(ws), ws.numel(), L.ptr(loss), L.ptr(grads), None,
-                                          L.stream_ptr()), "ardae_cdae_loss_grads")
+        L.call("ardae_cdae_loss_grads", d, mod._flat, mod._packed_weights(), xbar, sigma, eps, context, B, S, ws, ws.numel(), loss, grads, None)
         ctx.mod, ctx.grads = mod, grads
         return loss.reshape(())
 
@@ -162,6 +171,7 @@ class _CdaeLossFn(torch.autograd.Function):
 
 class ConditionalARDAE(FlatParamModule):
     _kind = None
+    _packed_floats_fn, _pack_fn = "ardae_cdae_packed_floats", "ardae_cdae_pack"
 
     def __init__(self, input_dim=2, h_dim=128, context_dim=2, std=0.01, num_hidden_layers=1, nonlinearity="tanh",
                  noise_type="gaussian", enc_input=True, enc_ctx=True, std_method="default"):
@@ -179,18 +189,6 @@ class ConditionalARDAE(FlatParamModule):
         self._build_params(layout.cdae_spec(self._kind, input_dim, context_dim, h_dim, num_hidden_layers))
         self._no_grad_names = {"neglogprob.fc.bias"} if self._kind == "grad" else set()
         self._default_init()
-
-    def _packed_weights(self):
-        """MFMA-lane-linear image of the current weights (policy: FlatParamModule._pack_is_current; the fused engine keeps its own
-        image and re-packs right after its own optimiser kernels)."""
-        if self._pack_is_current():
-            return self._packed
-        lib = L.lib()
-        if self._packed is None:
-            self._packed = self._ws(lib.ardae_cdae_packed_floats(ctypes.byref(self._desc)))
-        L.check(lib.ardae_cdae_pack(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed), L.stream_ptr()), "ardae_cdae_pack")
-        self._note_packed()
-        return self._packed
 
     def _prep(self, input, context, std):
         assert input.dim() == 3      # bsz x ssz x x_dim   (graddae/mlp.py:402)
@@ -219,11 +217,9 @@ class ConditionalARDAE(FlatParamModule):
 
     def glogprob(self, input, context, std=None, scale=None):
         B, S, x, c, s = self._prep(input, context, std)
-        lib = L.lib()
-        ws = self._ws(lib.ardae_cdae_workspace_floats(ctypes.byref(self._desc), B, S, 0))
+        ws = self._ws(L.query("ardae_cdae_workspace_floats", self._desc, B, S, 0))
         out = torch.empty(B * S, self.input_dim, device=x.device)
-        L.check(lib.ardae_cdae_score(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed_weights()), L.ptr(x), L.ptr(s),
-                                     L.ptr(c), B, S, L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()), "ardae_cdae_score")
+        L.call("ardae_cdae_score", self._desc, self._flat, self._packed_weights(), x, s, c, B, S, ws, ws.numel(), out)
         return out.view(B, S, self.input_dim)
 
 
@@ -249,29 +245,25 @@ def normal_energy_func(x, mu=0., logvar=0.):
 class _VaeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x, noise, beta, nz, *params):
-        lib = L.lib()
         d = mod._desc
         B = x.size(0)
-        ws = mod._ws(lib.ardae_model_workspace_floats(ctypes.byref(d), B, nz, 1))
+        ws = mod._ws(L.query("ardae_model_workspace_floats", d, B, nz, 1))
         z = torch.empty(B * nz, mod.z_dim, device=x.device)
         losses = torch.empty(3, device=x.device)
-        L.check(lib.ardae_model_vae_forward(ctypes.byref(d), L.ptr(mod._flat), L.ptr(mod._packed_weights()), L.ptr(x), L.ptr(noise), B, nz,
-                                            float(beta), L.ptr(ws), ws.numel(), L.ptr(z), L.ptr(losses), L.stream_ptr()),
-                "ardae_model_vae_forward")
+        L.call("ardae_model_vae_forward", d, mod._flat, mod._packed_weights(), x, noise, B, nz, float(beta), ws, ws.numel(), z, losses)
         ctx.mod, ctx.ws, ctx.x, ctx.noise, ctx.beta, ctx.nz = mod, ws, x, noise, float(beta), nz
         ctx.mark_non_differentiable(losses)
         return z.view(B, nz, mod.z_dim), losses[0].clone(), losses
 
     @staticmethod
     def backward(ctx, dz, dloss, _dlosses):
-        mod, lib = ctx.mod, L.lib()
+        mod = ctx.mod
         B = ctx.x.size(0)
         grads = torch.empty_like(mod._flat)
         dl = float(dloss) if dloss is not None else 0.0
         dzc = _f32c(dz).view(B * ctx.nz, mod.z_dim) if dz is not None else None
-        L.check(lib.ardae_model_vae_backward(ctypes.byref(mod._desc), L.ptr(mod._flat), L.ptr(mod._packed_weights()), L.ptr(ctx.x),
-                                             L.ptr(ctx.noise), B, ctx.nz, ctx.beta, dl, L.ptr(dzc), L.ptr(ctx.ws), ctx.ws.numel(),
-                                             L.ptr(grads), 0.0, L.stream_ptr()), "ardae_model_vae_backward")
+        L.call("ardae_model_vae_backward", mod._desc, mod._flat, mod._packed_weights(), ctx.x, ctx.noise, B, ctx.nz, ctx.beta, dl, dzc, ctx.ws,
+               ctx.ws.numel(), grads, 0.0)
         out = []
         for name, _ in mod.named_parameters():
             off, n, shape = mod._offs[name]
@@ -281,6 +273,7 @@ class _VaeFn(torch.autograd.Function):
 
 class ImplicitPosteriorVAE(FlatParamModule):
     _kind = None
+    _packed_floats_fn, _pack_fn = "ardae_model_packed_floats", "ardae_model_pack"
     _enc_types = ("concat",)
     return_samples = True        # forward() also returns the decoder sample / mean the reference's visualisation code reads
 
@@ -349,17 +342,6 @@ class ImplicitPosteriorVAE(FlatParamModule):
             if self.init == "gaussian":                   # ivae/mnist.py:158-159
                 p["encode.fc.fc.weight"].normal_()
 
-    def _packed_weights(self):
-        """See ConditionalARDAE._packed_weights."""
-        if self._pack_is_current():
-            return self._packed
-        lib = L.lib()
-        if self._packed is None:
-            self._packed = self._ws(lib.ardae_model_packed_floats(ctypes.byref(self._desc)))
-        L.check(lib.ardae_model_pack(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed), L.stream_ptr()), "ardae_model_pack")
-        self._note_packed()
-        return self._packed
-
     def _set_logvar_clips(self, clip_z0_logvar, clip_z_logvar):
         """clip_z0_logvar / clip_z_logvar of the hierarchical MLP models (ivae/auxmnist.py:144-161: 'none' -> None; the choices are
         NormalDistribution.clip_logvar's, models/reparam.py:17-41; any other name leaves the log-variance as it is there, and is refused here)."""
@@ -377,20 +359,15 @@ class ImplicitPosteriorVAE(FlatParamModule):
     def _sample(self, x, nz, std, noise):
         """z = f(x, std*eps) without autograd (the reference loop detaches every use: ivae_ardae.py:735,748-750)."""
         B = x.size(0)
-        if noise is None and std is not None and float(std) == 0.0:
-            nptr = None                                   # encode(x, std=0): the draw is multiplied by zero
-        else:
+        if not (noise is None and std is not None and float(std) == 0.0):      # encode(x, std=0): the draw is multiplied by zero (NULL)
             if noise is None:
                 noise = rng.normal((self._noise_numel(B, nz),), x.device)
                 if std is not None:
                     noise = noise * float(std)
             noise = self._noise_rows(noise, B * nz)
-            nptr = L.ptr(noise)
-        lib = L.lib()
-        ws = self._ws(lib.ardae_model_workspace_floats(ctypes.byref(self._desc), B, nz, 0))
+        ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, B, nz, 0))
         z = torch.empty(B * nz, self.z_dim, device=x.device)
-        L.check(lib.ardae_model_encode(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed_weights()), L.ptr(x), nptr, B, nz,
-                                       L.ptr(ws), ws.numel(), L.ptr(z), L.stream_ptr()), "ardae_model_encode")
+        L.call("ardae_model_encode", self._desc, self._flat, self._packed_weights(), x, noise, B, nz, ws, ws.numel(), z)
         return z.view(B, nz, self.z_dim)
 
     def _noise_numel(self, B, nz):
@@ -411,11 +388,10 @@ class ImplicitPosteriorVAE(FlatParamModule):
         if self._kind not in AUX_KINDS:
             raise NotImplementedError("hidden contexts exist for the aux models only")
         x = self._x(input)
-        B, lib = x.size(0), L.lib()
-        ws = self._ws(lib.ardae_model_workspace_floats(ctypes.byref(self._desc), B, 1, 0))
+        B = x.size(0)
+        ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, B, 1, 0))
         hid = torch.empty(B, self.hidden_dim, device=x.device)
-        L.check(lib.ardae_model_encode_hidden(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed_weights()), L.ptr(x), B, L.ptr(ws),
-                                              ws.numel(), None, L.ptr(hid), L.stream_ptr()), "ardae_model_encode_hidden")
+        L.call("ardae_model_encode_hidden", self._desc, self._flat, self._packed_weights(), x, B, ws, ws.numel(), None, hid)
         return hid
 
     def _decoder_sample(self, z_rows, dec_noise=None):
@@ -424,17 +400,15 @@ class ImplicitPosteriorVAE(FlatParamModule):
         Gaussian decoder returns mu + exp(logvar/2) eps and mu (reparam.py:42-51, ivae/toy.py:725-737,858).  dec_noise injects
         the draw (uniform [R, D] resp. normal [R, D]); default: the library's Philox stream."""
         out = self.decode_params(z_rows)
-        R, lib = out[0].size(0), L.lib()
+        R = out[0].size(0)
         sample = torch.empty_like(out[0])
         if self._kind in GAUSSIAN_DECODERS:
             e = _f32c(dec_noise).view(R, self.input_dim) if dec_noise is not None else rng.normal((R, self.input_dim), out[0].device)
-            L.check(lib.ardae_gaussian_sample(L.ptr(out[0]), L.ptr(out[1]), L.ptr(e), out[0].numel(), L.ptr(sample), L.stream_ptr()),
-                    "ardae_gaussian_sample")
+            L.call("ardae_gaussian_sample", out[0], out[1], e, out[0].numel(), sample)
             return sample, out[0]
         u = _f32c(dec_noise).view(R, self.input_dim) if dec_noise is not None else rng.uniform((R, self.input_dim), out[0].device)
         mean = torch.empty_like(out[0])
-        L.check(lib.ardae_relaxed_bernoulli(L.ptr(out[0]), L.ptr(u), out[0].numel(), 1.0, L.ptr(sample), L.ptr(mean), L.stream_ptr()),
-                "ardae_relaxed_bernoulli")
+        L.call("ardae_relaxed_bernoulli", out[0], u, out[0].numel(), 1.0, sample, mean)
         return sample, mean
 
     def forward(self, input, beta=1.0, eta=0.0, lmbd=0.0, std=None, nz=1, noise=None, dec_noise=None):
@@ -463,12 +437,11 @@ class ImplicitPosteriorVAE(FlatParamModule):
         """Decoder heads for z [R, z_dim] -> (logits,) or (mean, logvar)."""
         self._require_gpu(z)
         z = _f32c(z).view(-1, self.z_dim)
-        R, lib = z.size(0), L.lib()
-        ws = self._ws(lib.ardae_model_workspace_floats(ctypes.byref(self._desc), R, 1, 2))
+        R = z.size(0)
+        ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, R, 1, 2))
         o0 = torch.empty(R, self.input_dim, device=z.device)
         o1 = torch.empty(R, self.input_dim, device=z.device) if self._kind in GAUSSIAN_DECODERS else None
-        L.check(lib.ardae_model_decode(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed_weights()), L.ptr(z), R, L.ptr(ws),
-                                       ws.numel(), L.ptr(o0), L.ptr(o1), L.stream_ptr()), "ardae_model_decode")
+        L.call("ardae_model_decode", self._desc, self._flat, self._packed_weights(), z, R, ws, ws.numel(), o0, o1)
         return (o0,) if o1 is None else (o0, o1)
 
     def generate(self, batch_size=1, z=None, dec_noise=None):
@@ -504,7 +477,7 @@ class ImplicitPosteriorVAE(FlatParamModule):
             cov = cov.contiguous()
             if zd <= 64:
                 Lc = torch.empty_like(cov)                    # all B factorisations in one launch (MultivariateNormal's, ivae/mnist.py:397)
-                L.check(L.lib().ardae_cholesky_batched(L.ptr(cov), B, zd, L.ptr(Lc), L.stream_ptr()), "ardae_cholesky_batched")
+                L.call("ardae_cholesky_batched", cov, B, zd, Lc)
             else:
                 # the LDS-resident kernel holds one z x z matrix per workgroup (z <= 64, every shipped recipe has z 32); larger latent
                 # spaces factorise on the device through the library solver MultivariateNormal itself would use - evaluation only
@@ -519,8 +492,7 @@ class ImplicitPosteriorVAE(FlatParamModule):
             logq = -0.5 * (e ** 2).sum(2) - torch.log(torch.diagonal(Lc, dim1=1, dim2=2)).sum(1, keepdim=True) - 0.5 * zd * math.log(2 * math.pi)
             out = self.decode_params(newz.view(B * k, zd))
             rec = torch.empty(B * k, device=x.device); pri = torch.empty(B * k, device=x.device)
-            L.check(L.lib().ardae_model_loss_rows(ctypes.byref(self._desc), L.ptr(out[0]), L.ptr(out[1]) if len(out) > 1 else None, L.ptr(x),
-                                                  L.ptr(newz), B * k, k, L.ptr(rec), L.ptr(pri), L.stream_ptr()), "ardae_model_loss_rows")
+            L.call("ardae_model_loss_rows", self._desc, out[0], out[1] if len(out) > 1 else None, x, newz, B * k, k, rec, pri)
             lw = -rec.view(B, k) - pri.view(B, k) - logq
             m, _ = lw.max(1, keepdim=True)
             return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).mean()
@@ -659,13 +631,12 @@ class MNISTResConvAuxIPVAEClipped(MNISTResConvAuxIPVAE):
         super().__init__(*a, **k)
 
     def _std0(self, x, raw0, want_hidden):
-        B, lib = x.size(0), L.lib()
+        B = x.size(0)
         raw = _f32c(raw0).view(B, -1)[:, :self.z0_dim].contiguous() if raw0 is not None else rng.normal((B, self.z0_dim), x.device)
-        ws = self._ws(lib.ardae_model_workspace_floats(ctypes.byref(self._desc), B, 1, 0))
+        ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, B, 1, 0))
         out = torch.empty(B, self.hidden_dim if want_hidden else self.z_dim, device=x.device)
-        L.check(lib.ardae_model_encode_hidden_raw(ctypes.byref(self._desc), L.ptr(self._flat), L.ptr(self._packed_weights()), L.ptr(x), L.ptr(raw), B,
-                                                  L.ptr(ws), ws.numel(), None if want_hidden else L.ptr(out), L.ptr(out) if want_hidden else None,
-                                                  L.stream_ptr()), "ardae_model_encode_hidden_raw")
+        L.call("ardae_model_encode_hidden_raw", self._desc, self._flat, self._packed_weights(), x, raw, B, ws, ws.numel(),
+               None if want_hidden else out, out if want_hidden else None)
         return out
 
     def _sample(self, x, nz, std, noise):

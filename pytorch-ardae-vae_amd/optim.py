@@ -90,7 +90,6 @@ class Adam(_FlatStateOptimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        lib = L.lib()
         for group in self.param_groups:
             active = [p for p in group["params"] if p.grad is not None]
             if not active:
@@ -118,10 +117,9 @@ class Adam(_FlatStateOptimizer):
                     end += 1
                 for run in _runs(tuples[start:end]):
                     n = sum(t.numel() for t in run[0])
-                    vmax = L.ptr(run[4][0]) if group["amsgrad"] else None
-                    L.check(lib.ardae_adam_ref_step(L.ptr(run[0][0]), L.ptr(run[1][0]), L.ptr(run[2][0]), L.ptr(run[3][0]), vmax, n,
-                                                    float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]),
-                                                    float(group["eps"]), int(steps[start]), L.stream_ptr()), "ardae_adam_ref_step")
+                    vmax = run[4][0] if group["amsgrad"] else None
+                    L.call("ardae_adam_ref_step", run[0][0], run[1][0], run[2][0], run[3][0], vmax, n, float(group["lr"]),
+                           float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), int(steps[start]))
                 start = end
             for p in active:
                 _bump(p)
@@ -148,7 +146,6 @@ class RMSprop(_FlatStateOptimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        lib = L.lib()
         for group in self.param_groups:
             active = [p for p in group["params"] if p.grad is not None]
             if not active:
@@ -167,10 +164,9 @@ class RMSprop(_FlatStateOptimizer):
                 tuples.append((p.data, g, st["square_avg"]) + ((st["momentum_buffer"],) if group["momentum"] > 0 else ()))
             for run in _runs(tuples):
                 n = sum(t.numel() for t in run[0])
-                buf = L.ptr(run[3][0]) if group["momentum"] > 0 else None
-                L.check(lib.ardae_rmsprop_step(L.ptr(run[0][0]), L.ptr(run[1][0]), L.ptr(run[2][0]), buf, n, float(group["lr"]),
-                                               float(group["alpha"]), float(group["eps"]), float(group["momentum"]), L.stream_ptr()),
-                        "ardae_rmsprop_step")
+                buf = run[3][0] if group["momentum"] > 0 else None
+                L.call("ardae_rmsprop_step", run[0][0], run[1][0], run[2][0], buf, n, float(group["lr"]), float(group["alpha"]),
+                       float(group["eps"]), float(group["momentum"]))
             for p in active:
                 _bump(p)
         return loss
@@ -191,7 +187,7 @@ class RMSprop(_FlatStateOptimizer):
 #   {"opt_state": <inner optimizer's state>, "swa_state" | "polyak_state": {idx: {"swa_buffer" | "polyak_buffer": tensor}},
 #    "param_groups": <inner optimizer's groups, each with "n_avg" (averaging steps done) and "step_counter" (t)>}
 # The Polyak key names are an assumption (the fork that adds Polyak is not available to compare against).
-WEIGHT_AVG_KINDS = {"swa": 0, "polyak": 1}      # ARDAE_WEIGHT_AVG_SWA / ARDAE_WEIGHT_AVG_POLYAK
+WEIGHT_AVG_KINDS = {"swa": L.WEIGHT_AVG_SWA, "polyak": L.WEIGHT_AVG_POLYAK}
 
 
 def weight_avg_keys(kind):
@@ -276,7 +272,6 @@ class _WeightAverage:
         if self._swapped is not None:
             raise RuntimeError(f"{type(self).__name__}.step() while the averaged weights are in: call use_sgd() first")
         loss = self.optimizer.step(closure)
-        lib = L.lib()
         for group in self.param_groups:
             group["step_counter"] += 1
             t = group["step_counter"]
@@ -287,8 +282,7 @@ class _WeightAverage:
             origin = t - group["n_avg"]          # k = t - origin = averaging steps already in the buffers
             for run in _runs([(p.data, self._buffer(p)) for p in params]):
                 n = sum(x.numel() for x in run[0])
-                L.check(lib.ardae_weight_avg(L.ptr(run[1][0]), L.ptr(run[0][0]), n, WEIGHT_AVG_KINDS[self.kind], self.decay, origin, None, t,
-                                             L.stream_ptr()), "ardae_weight_avg")
+                L.call("ardae_weight_avg", run[1][0], run[0][0], n, WEIGHT_AVG_KINDS[self.kind], self.decay, origin, None, t)
             group["n_avg"] += 1
         return loss
 

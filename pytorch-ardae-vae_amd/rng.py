@@ -10,8 +10,6 @@ Two consumers share one seed and must never share a Philox word: the fused engin
 `data.dynamic_binarize`, `model.generate/logprob`, the drop-in modules' noise) use `HOST_STREAM | n` with the top bit of
 the 64-bit offset set.  The host counter `n` is part of the engine checkpoint (engine.py::model_checkpoint).
 """
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -42,13 +40,11 @@ def normal(shape, device, out=None, first_element=0):
     """first_element: this tensor is the slice [first_element, first_element + numel) of a larger draw (data parallelism:
     rank r of R equal shards passes r * numel and gets the numbers a single process would have generated there)."""
     t = out if out is not None else torch.empty(shape, device=device, dtype=torch.float32)
-    L.check(L.lib().ardae_philox_normal_at(L.ptr(t), t.numel(), ctypes.c_uint64(_state["seed"]), ctypes.c_uint64(_next_offset()), None,
-                                           ctypes.c_uint64(first_element), L.stream_ptr()), "ardae_philox_normal_at")
+    L.call("ardae_philox_normal_at", t, t.numel(), _state["seed"], _next_offset(), None, first_element)
     return t
 
 
 def uniform(shape, device, out=None):
     t = out if out is not None else torch.empty(shape, device=device, dtype=torch.float32)
-    L.check(L.lib().ardae_philox_uniform(L.ptr(t), t.numel(), ctypes.c_uint64(_state["seed"]), ctypes.c_uint64(_next_offset()),
-                                         L.stream_ptr()), "ardae_philox_uniform")
+    L.call("ardae_philox_uniform", t, t.numel(), _state["seed"], _next_offset())
     return t

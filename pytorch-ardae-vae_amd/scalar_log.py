@@ -42,8 +42,7 @@ class ScalarLog:
     def record(self, beta):
         """Called by the engine as the last launch of a step (on the step's stream)."""
         e = self.eng
-        L.check(e.lib.ardae_log_scalars(L.ptr(e.loss_c), L.ptr(e.losses_m), L.ptr(e.std_b), e.B, float(beta), float(e.cfg.d_lr),
-                                        e.state.data_ptr(), L.ptr(self.ring), self.capacity, L.stream_ptr()), "ardae_log_scalars")
+        L.call("ardae_log_scalars", e.loss_c, e.losses_m, e.std_b, e.B, float(beta), float(e.cfg.d_lr), e.state, self.ring, self.capacity)
 
     def drain(self):
         """Records of the steps finished since the last drain (oldest first); appends them to log.txt / scalars.jsonl."""

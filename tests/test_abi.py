@@ -8,6 +8,7 @@ import pytest
 import ardae_amd
 from ardae_amd import _lib as L
 from ardae_amd import layout
+from ardae_amd.modules import KIND_IDS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -26,6 +27,154 @@ def test_header_symbols_are_exported_and_bound():
         assert hasattr(h, s), f"{s} declared in include/ardae_hip.h but not exported by libardae_hip.so"
         assert s in L.EXPORTS, f"{s} has no ctypes binding in _lib.EXPORTS"
     assert sorted(L.EXPORTS) == syms
+
+
+# ---- the binding is DERIVED from the header (ardae_amd/_lib.py::parse_header), so the header cannot vouch for it: what follows pins the
+# derivation against the compiler, against signatures and constants written out here, and against inputs the parser must refuse
+vp, i32, i64, u64, f32, f64, usize = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double,
+                                      ctypes.c_size_t)
+
+
+def test_struct_layout_matches_the_compiler():
+    """The same literals as the static_asserts of csrc/api.hip: sizes of the six structs, offsets of the last fields of the two big ones."""
+    sizes = {"ardae_lin_src": 24, "ardae_linear_args": 232, "ardae_wgrad_problem": 144, "ardae_cdae_desc": 24, "ardae_model_desc": 32,
+             "ardae_profile_entry": 128}
+    assert list(L.STRUCTS) == list(sizes)                                   # declaration order: ardae_lin_src before its user
+    assert {n: ctypes.sizeof(c) for n, c in L.STRUCTS.items()} == sizes
+    assert (L.LinearArgs.tile_loss.offset, L.WgradProblem.beta.offset) == (224, 140)
+    assert [L.STRUCTS[n] for n in sizes] == [L.LinSrc, L.LinearArgs, L.WgradProblem, L.CdaeDesc, L.ModelDesc, L.ProfileEntry]
+    # one field of every declaration form the header uses: `int M, Nout;`, two declarations on a line, arrays, a nested struct by value
+    assert [f[0] for f in L.LinearArgs._fields_[:4]] == ["M", "Nout", "nsrc", "src"] and L.LinearArgs.src.size == 2 * 24
+    assert (L.LinearArgs.S.offset + 8, L.LinearArgs.S.size) == (L.LinearArgs.ldS.offset, 8)
+    assert (L.WgradProblem.G.size, L.WgradProblem.ldG.size, L.ProfileEntry.name.size, L.ProfileEntry.calls.offset) == (16, 8, 96, 96)
+    assert [f[0] for f in L.ModelDesc._fields_] == ["kind", "input_dim", "noise_dim", "h_dim", "z_dim", "n_layers", "act", "flags"]
+
+
+SIGNATURES = {      # every scalar type, data pointers, a struct pointer, an out-parameter; one (name, type) per parameter, in order
+    "ardae_adam_ref_step": (i32, [("p", vp), ("g", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("max_exp_avg_sq", vp), ("n", i64), ("lr", f64),
+                                  ("beta1", f64), ("beta2", f64), ("eps", f64), ("step", i32), ("stream", vp)]),
+    "ardae_weight_avg": (i32, [("avg", vp), ("p", vp), ("n", i64), ("kind", i32), ("decay", f64), ("origin", i64), ("state", vp), ("t", i64),
+                               ("stream", vp)]),
+    "ardae_cdae_perturb_loss_grads": (i32, [("d", ctypes.POINTER(L.CdaeDesc)), ("params", vp), ("packed", vp), ("latent", vp), ("z0", vp),
+                                            ("ctx", vp), ("B", i32), ("nz", i32), ("std_scale", f32), ("delta", f32), ("seed", u64),
+                                            ("offset_xi", u64), ("offset_eps", u64), ("state", vp), ("first_row", u64), ("xbar", vp),
+                                            ("sigma", vp), ("eps_out", vp), ("std_b", vp), ("workspace", vp), ("workspace_floats", usize),
+                                            ("loss", vp), ("grads", vp), ("stream", vp)]),
+    "ardae_dp_comm_create": (i32, [("host_id", vp), ("nranks", i32), ("rank", i32), ("comm_out", ctypes.POINTER(vp))]),
+    "ardae_gather_rows": (i32, [("table", vp), ("idx", vp), ("B", i32), ("D", i32), ("out", vp), ("stream", vp)]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SIGNATURES))
+def test_derived_signature_matches_the_literal_one(name):
+    restype, params = SIGNATURES[name]
+    assert L.EXPORTS[name] == (restype, [t for _, t in params])
+    assert [p[0] for p in L.PROTOTYPES[name][1]] == [n for n, _ in params]
+    fn = getattr(L.lib(), name)
+    assert fn.restype is restype and list(fn.argtypes) == [t for _, t in params]
+
+
+def test_other_return_types_and_out_parameters():
+    assert L.EXPORTS["ardae_last_error"] == (ctypes.c_char_p, []) and L.EXPORTS["ardae_dp_backend"] == (ctypes.c_char_p, [])
+    assert L.EXPORTS["ardae_cdae_workspace_floats"] == (usize, [ctypes.POINTER(L.CdaeDesc), i32, i32, i32])
+    assert L.EXPORTS["ardae_dp_comm_query"] == (i32, [vp] + [ctypes.POINTER(i32)] * 3)
+    assert L.EXPORTS["ardae_cdae_perturb_fused_ok"] == (i32, [ctypes.POINTER(L.CdaeDesc), i32, i32])
+    assert L.EXPORTS["ardae_profile_report"] == (i32, [ctypes.POINTER(L.ProfileEntry), i32])
+    assert L.EXPORTS["ardae_debug_stamp"] == (i32, [vp, i32, vp])
+    pointees = lambda name: [p[2] for p in L.PROTOTYPES[name][1]]
+    assert pointees("ardae_gather_rows") == ["float", "int64_t", None, None, "float", "void"]
+    assert pointees("ardae_debug_stamp") == ["unsigned long long", None, "void"]
+
+
+def test_derived_constants_have_todays_values():
+    from ardae_amd import optim
+    assert L.ACT == {"none": 0, None: 0, "relu": 1, "softplus": 2, "csoftplus": 2, "elu": 3, "tanh": 4, "leaky_relu": 5, "swish": 6}
+    assert (L.EPI_ACT, L.EPI_DACT, L.EPI_CHAIN, L.EPI_DAE_LOSS) == (0, 1, 2, 3)
+    assert (L.MODEL_NO_CENTER, L.MODEL_HEAD_SHIFT, L.MODEL_CLIPPED, L.MODEL_CLIP_Z0_SHIFT, L.MODEL_CLIP_Z_SHIFT) == (1, 1, 16, 8, 12)
+    assert L.LOG_RECORD_FLOATS == 16
+    assert optim.WEIGHT_AVG_KINDS == {"swa": 0, "polyak": 1}
+    # the two expressions among the header's enumerators, and a #define
+    assert (L.CONSTANTS["ARDAE_MODEL_HEAD_MASK"], L.CONSTANTS["ARDAE_MODEL_CLIP_MASK"], L.CONSTANTS["ARDAE_WGRAD_MAX_PROBLEMS"]) == (14, 0xff00, 20)
+
+
+GOOD_HEADER = """#define ARDAE_N 3
+enum { ARDAE_A = 0, ARDAE_B = 1 << 4 };
+typedef struct ardae_s { int a, b; const float* p[2]; } ardae_s;
+int ardae_f(const ardae_s* s, float* y, /* a comment */ void* stream);
+"""
+
+
+def test_parser_reads_what_the_header_uses():
+    consts, structs, protos = L.parse_header(GOOD_HEADER)
+    assert consts == {"ARDAE_N": 3, "ARDAE_A": 0, "ARDAE_B": 16}
+    assert ctypes.sizeof(structs["ardae_s"]) == 24 and structs["ardae_s"].__name__ == "S"
+    assert protos == {"ardae_f": (i32, [("s", ctypes.POINTER(structs["ardae_s"]), "ardae_s"), ("y", vp, "float"), ("stream", vp, "void")])}
+
+
+BAD_DECLARATIONS = [
+    ("int ardae_g(long double x);", "ardae_g"),                                       # an unknown type ...
+    ("int ardae_g(int n, short k);", "ardae_g.*short k"),
+    ("long ardae_g(int n);", "ardae_g"),                                              # ... also as the result
+    ("int ardae_g(ardae_t* t);", "ardae_g.*ardae_t"),                                 # a pointer to an undeclared struct is not a void*
+    ("int ardae_g(char** names);", "ardae_g"),
+    ("int ardae_g(int (*callback)(int), int n);", "ardae_g"),                         # a function pointer
+    ("typedef struct ardae_t { int a b; } ardae_t;", "ardae_t.*int a b"),              # fields it cannot split
+    ("typedef struct ardae_t { void (*f)(void); } ardae_t;", "ardae_t"),
+    ("typedef struct ardae_t { float* x, y; } ardae_t;", "ardae_t"),
+    ("typedef struct ardae_t { long double x; } ardae_t;", "ardae_t"),
+    ("typedef struct ardae_t { int a; } ardae_u;", "ardae_t"),
+    ("enum { ARDAE_C = 1 + 1 };", "ARDAE_C"),
+    ("int ardae_g(int n) { return n; }", "ardae_g"),                                  # not a declaration of this header's kind
+    ("#define ARDAE_X 1.5", "ARDAE_X"),
+]
+
+
+@pytest.mark.parametrize("decl,names", BAD_DECLARATIONS, ids=[f"bad{i}" for i in range(len(BAD_DECLARATIONS))])
+def test_parser_refuses_what_it_does_not_recognise(decl, names):
+    """It raises and names the declaration; a symbol is never bound loosely (to c_void_p) or skipped."""
+    with pytest.raises(ValueError, match=names):
+        L.parse_header(GOOD_HEADER + decl + "\nint ardae_h(int n);\n")
+
+
+def test_call_helper_checks_arguments_before_anything_runs(monkeypatch):
+    """The converter's refusals, on CPU tensors: every check runs before the stream is fetched and before the library is entered."""
+    import types
+    import torch
+    fetched = []
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda: fetched.append(1) or types.SimpleNamespace(cuda_stream=0))
+    f32, i64t = torch.zeros(4, 2), torch.zeros(4, dtype=torch.int64)
+    with pytest.raises(TypeError, match="expected a float32 tensor on the GPU, got torch.float64 on cpu"):
+        L.call("ardae_gather_rows", f32.double(), None, 4, 2, None)
+    with pytest.raises(TypeError, match="expected a float32 tensor on the GPU, got torch.float32 on cpu"):      # right dtype, wrong device
+        L.call("ardae_gather_rows", f32, None, 4, 2, None)
+    with pytest.raises(TypeError, match="expected a int64 tensor on the GPU, got torch.int32"):
+        L.call("ardae_gather_rows", None, i64t.int(), 4, 2, None)
+    with pytest.raises(TypeError, match="expected a int64 tensor on the GPU, got torch.int64 on cpu"):
+        L.call("ardae_gather_rows", None, i64t, 4, 2, None)
+    with pytest.raises(TypeError, match="ardae_gather_rows takes 6 arguments"):
+        L.call("ardae_gather_rows", None, None, 4, 2, None, None, None)                  # one too many
+    with pytest.raises(TypeError, match="ardae_gather_rows takes 6 arguments"):
+        L.call("ardae_gather_rows", None, None, 4, 2)                                    # two too few
+    with pytest.raises(TypeError, match="ardae_cdae_param_floats takes 1 arguments, got 0"):
+        L.query("ardae_cdae_param_floats")                                               # no stream parameter: nothing is optional
+    with pytest.raises(ctypes.ArgumentError, match="CdaeDesc"):
+        L.query("ardae_cdae_param_floats", L.ModelDesc())                                # the wrong struct: argtypes holds a typed pointer
+    assert not fetched
+    # a missing trailing stream is NOT an error: the call goes through (to the library's own validation, which runs before any HIP call),
+    # and its error carries the entry point's name
+    with pytest.raises(ValueError, match="^ardae_pack_weight: "):
+        L.call("ardae_pack_weight", None, 0, 0, 0, 0, None)
+    assert fetched == [1]
+    with pytest.raises(ValueError, match="^ardae_pack_weight: "):
+        L.call("ardae_pack_weight", None, 0, 0, 0, 0, None, None)                        # ... and so does an explicit one
+    assert fetched == [1]
+    # values: a struct goes by reference, tensors without a dtype rule (the host-side RCCL id) go as their address, numbers as they are
+    cd = L.CdaeDesc(0, 8, 8, 64, 3, 2)
+    assert L.query("ardae_cdae_param_floats", cd) == L.lib().ardae_cdae_param_floats(ctypes.byref(cd)) > 0
+    assert L.query("ardae_cdae_workspace_floats", cd, 4, 8, 1) == L.lib().ardae_cdae_workspace_floats(ctypes.byref(cd), 4, 8, 1) > 0
+    assert L.query("ardae_abi_version") == 1
+    with pytest.raises(ValueError, match="^ardae_dp_comm_create: "):
+        L.call("ardae_dp_comm_create", torch.zeros(128, dtype=torch.uint8), 0, 0, ctypes.c_void_p())      # nranks 0
 
 
 def test_abi_version_and_error_channel():
@@ -64,7 +213,7 @@ RESCONV_HEAD_SIZES = {"res-wn-mlp": [(10086208, 22831104), (11660608, 23456000),
 def test_model_layout_matches_c_side(kind, args, act, flags, packed, workspace):
     spec = layout.model_spec(kind, *args)
     _, total = layout.offsets(spec)
-    d = L.ModelDesc({"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7}[kind], *args, act, flags)
+    d = L.ModelDesc(KIND_IDS[kind], *args, act, flags)
     if kind == "resconv":       # every sampler head of ivae_ardae.py's --model resconv* choices, one to three hidden layers
         for et, code in layout.RESCONV_HEADS.items():
             for nl in (1, 2, 3):
