@@ -185,9 +185,10 @@ int ardae_sgd_step(float* p, const float* g, int64_t n, double lr, void* stream)
  * Parameters live in ONE flat fp32 buffer in the reference's named_parameters() order
  * (ctx_encode.layers.*, ctx_encode.fc, inp_encode.*, neglogprob.* | dae.*), each tensor [out,in] row-major. */
 typedef struct ardae_cdae_desc {
-  int kind;        /* 0 = mlp-grad (MLPGradCARDAE: score = input-gradient of an energy MLP), 1 = mlp-res (direct score) */
+  int kind;        /* 0 = mlp-grad (MLPGradCARDAE: score = input-gradient of an energy MLP), 1 = mlp-res (direct score);
+                    * 2 / 3 = the same two WITHOUT a context (MLPGradARDAE / MLPResARDAE, see "unconditional AR-DAE" below) */
   int input_dim;   /* z */
-  int context_dim; /* c */
+  int context_dim; /* c  (kinds 0 / 1: >= 1; kinds 2 / 3: 0) */
   int h_dim;
   int n_layers;    /* --cdae-n-layers */
   int act;         /* any ARDAE_ACT_* but NONE (with a piecewise linear one mlp-grad's second-order terms are zero)  */
@@ -220,6 +221,32 @@ int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params,
 int ardae_cdae_score(const ardae_cdae_desc* d, const float* params, const float* packed, const float* x,
                      const float* sigma, const float* ctx, int B, int S, float* workspace, size_t workspace_floats,
                      float* score_out, void* stream);
+
+/* ---- unconditional AR-DAE (models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167): ardae_cdae_desc.kind 2 / 3 -------------
+ * The score network on [x_bar | sigma] alone: MLP(input_dim + 1, h, 1) whose input-gradient is the score (kind 2, MLPGradARDAE)
+ * or MLP(input_dim + 1, h, input_dim) that is the score (kind 3, MLPResARDAE).  context_dim must be 0.  Parameters in the
+ * reference's named_parameters() order: neglogprob.layers.{0..L-1}.{weight,bias}, neglogprob.fc.* (kind 2) / main.layers.*,
+ * main.fc.* (kind 3); layers.0.weight is [h, d + 1] = [W1x | w1s].  ardae_cdae_param_floats / packed_floats / workspace_floats /
+ * pack / loss_grads / score take these kinds with ctx == NULL (anything else is an argument error) and N = B * S rows in any
+ * factorisation; kind 2 leaves neglogprob.fc.bias's gradient untouched like kind 0.
+ *
+ * ardae_dae_perturb: add_gaussian_noise on a broadcast batch (graddae/mlp.py:21-23 after the notebooks'
+ * x.unsqueeze(1).expand(B, nsigma, d)): xbar[(b, j)] = fma(sigma[(b, j)], eps[(b, j)], x[b]); the broadcast is never written. */
+int ardae_dae_perturb(const float* x /* [B, d] */, const float* sigma /* [B*nsigma] */, const float* eps /* [B*nsigma, d] */,
+                      int B, int nsigma, int d, float* xbar, void* stream);
+/* Draw + perturbation + first layer in ONE kernel over 64-row tiles of the N = B * nsigma rows, then ardae_cdae_loss_grads from
+ * layer 2 on.  Row r of the call = element first_row + r of the global sigma draw (seed, offset_sigma [+ state.rng_offset]) and
+ * elements (first_row + r) d ... of the eps draw, keyed exactly like ardae_philox_normal_at (first_row a multiple of 4):
+ * sigma = delta * n (one multiply), xbar = fma(sigma, eps, x[b]); xbar, sigma, eps_out are written as the three separate launches
+ * would, and h_1 = act(W1x xbar + sigma w1s + d_1) goes into the workspace slot ardae_cdae_loss_grads reads.
+ * ardae_dae_perturb_fused_ok: 1 if (d, h, L, act, nsigma) qualifies (kind 2 / 3, input_dim <= 8, h_dim 64 | 128 | 256,
+ * n_layers >= 2, nsigma >= 1; any N - a last partial tile is masked); otherwise: ardae_philox_normal_at x 2, sigma *= delta,
+ * ardae_dae_perturb, ardae_cdae_loss_grads. */
+int ardae_dae_perturb_fused_ok(const ardae_cdae_desc* d, int nsigma);
+int ardae_dae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* x, int B, int nsigma,
+                                 float delta, uint64_t seed, uint64_t offset_sigma, uint64_t offset_eps, const void* state,
+                                 uint64_t first_row, float* xbar, float* sigma, float* eps_out, float* workspace,
+                                 size_t workspace_floats, float* loss, float* grads, void* stream);
 
 
 /* ---- K2/K8: implicit-posterior VAE (models/ivae/mnist.py, models/ivae/toy.py enc_type='concat') ---------------

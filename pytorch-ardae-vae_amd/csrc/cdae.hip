@@ -66,8 +66,10 @@ struct PackedLayout {
 
 int desc_ok(const ardae_cdae_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "cdae: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind == 0 || d->kind == 1, "cdae: kind must be 0 (mlp-grad) or 1 (mlp-res)");
-  ARDAE_CHECK_ARG(d->input_dim >= 1 && d->context_dim >= 1 && d->h_dim >= 1 && d->n_layers >= 1, "cdae: bad dimensions");
+  ARDAE_CHECK_ARG(d->kind >= 0 && d->kind <= 3, "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad) or 3 (unconditional res)");
+  ARDAE_CHECK_ARG(d->kind >= 2 || d->context_dim >= 1, "cdae: kinds 0 / 1 need context_dim >= 1 (got %d)", d->context_dim);
+  ARDAE_CHECK_ARG(d->kind < 2 || d->context_dim == 0, "cdae: kinds 2 / 3 have no context: context_dim must be 0 (got %d)", d->context_dim);
+  ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->n_layers >= 1, "cdae: bad dimensions");
   ARDAE_CHECK_ARG(d->n_layers <= 6, "cdae: n_layers <= 6 supported (3L+1 gradient problems per batch)");
   // every activation of get_nonlinear_func; with a piecewise linear one mlp-grad's second-order terms vanish, as
   // they do under autograd in the reference
@@ -385,7 +387,214 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   return wl.launch(st);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Unconditional AR-DAE (kinds 2 / 3; models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167): the update above with the context
+// branch and the input encoder removed, a_L -> xbar, W1a -> W1x [h, d], [W1c c_L + d_1](b) -> d_1:
+//   energy MLP : h_1 = act(W1x xbar + sigma w1s + d_1), h_l = act(W_l h_{l-1} + d_l), E = w.h_L + d_f
+//   score      : e_L = -w (.) s(h_L); e_{l-1} = (e_l W_l) (.) s(h_{l-1}); g = e_1 W1x
+//   loss       : rho = sigma g + eps; loss = sum rho^2 / (N d); gbar = 2 sigma rho / (N d)
+//   forward-mode chain: eb_1 = gbar W1x^T; tau'_l = eb_l (.) s(h_l); qbar_l = eb_l (.) e_l (.) (1 - s(h_l)); eb_{l+1} = tau'_l W_{l+1}^T
+//   backward   : qhat_L = qbar_L; qhat_{l-1} = qbar_{l-1} + (qhat_l W_l) (.) s(h_{l-1})
+//   gradients  : W1x = e_1 (x) gbar + qhat_1 (x) xbar, w1s = sum_i sigma_i qhat_1[i], d_1 = colsum qhat_1,
+//                W_l = e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}, d_l = colsum qhat_l, w = -colsum tau'_L; d_f: none (left untouched)
+// Kind 3 (direct score, g = fc(h_L)): one ordinary backward from gbar.
+struct DaeLayout {
+  int kind, z, h, L, act;
+  std::vector<Lin> neg;   // L hidden + fc (neglogprob.* | main.*); neg[0] is [h, d + 1] = [W1x | w1s]
+  size_t total = 0;
+  bool grad() const { return kind == 2; }
+  explicit DaeLayout(const ardae_cdae_desc& d) : kind(d.kind), z(d.input_dim), h(d.h_dim), L(d.n_layers), act(d.act) {
+    size_t off = 0;
+    for (int l = 0; l < L; ++l) neg.push_back(next_lin(off, h, l == 0 ? z + 1 : h));
+    neg.push_back(next_lin(off, grad() ? 1 : z, h));
+    total = off;
+  }
+};
+
+struct DaePacked {
+  std::vector<size_t> neg_f, neg_b;   // [0] unused (W1 is split below)
+  size_t w1x_f, w1x_b, w1s, fc_f, fc_b;
+  DaePacked(const DaeLayout& P, PackList& pl) {
+    neg_f.assign(P.L, 0); neg_b.assign(P.L, 0);
+    pl.pair(P.neg[0], w1x_f, w1x_b, 0, P.z);
+    w1s = pl.take(P.h);                              // the sigma column, gathered by dae_pack_impl
+    for (int l = 1; l < P.L; ++l) pl.pair(P.neg[l], neg_f[l], neg_b[l]);
+    fc_f = fc_b = 0;
+    if (!P.grad()) pl.pair(P.neg[P.L], fc_f, fc_b);
+  }
+  explicit DaePacked(const DaeLayout& P, PackList&& sizing = PackList()) : DaePacked(P, sizing) {}   // offsets only
+};
+
+struct DaeWs {
+  std::vector<float*> hh, e, taup, qbar;   // [l], l = 1..L, [N, h] each (kind 3: hh and qbar only)
+  float *gbar, *gbuf, *tile_loss, *cs_taup;
+  int ltiles, ctiles;
+};
+
+void dae_carve(const DaeLayout& P, Bump& ws, int N, bool need_grads, DaeWs& W) {
+  const int h = P.h, L = P.L, z = P.z;
+  const size_t Nh = (size_t)N * h;
+  for (auto* v : {&W.hh, &W.e, &W.taup, &W.qbar}) v->assign(L + 1, nullptr);
+  for (int l = 1; l <= L; ++l) { W.hh[l] = ws.take(Nh); if (P.grad()) W.e[l] = ws.take(Nh); }
+  if (need_grads)
+    for (int l = 1; l <= L; ++l) { if (P.grad()) W.taup[l] = ws.take(Nh); W.qbar[l] = ws.take(Nh); }
+  W.gbar = ws.take((size_t)N * z);
+  W.gbuf = ws.take((size_t)N * z);
+  W.ltiles = linear_row_tiles(N, z) * linear_col_panels(N, z);
+  W.tile_loss = ws.take(W.ltiles);
+  W.ctiles = linear_row_tiles(N, h);
+  W.cs_taup = need_grads && P.grad() ? ws.take((size_t)W.ctiles * h) : nullptr;
+}
+
+void dae_wgrads(const DaeLayout& P, const DaeWs& W, const float* xbar, const float* sigma, int N, WgradList& wl, Bump& ws) {
+  const int h = P.h, L = P.L, z = P.z, ld1 = z + 1;
+  const std::vector<float*>&hh = W.hh, &e = W.e, &taup = W.taup, &qhat = W.qbar;
+  const size_t gW1 = P.neg[0].w;
+  if (P.grad()) {
+    wl.push2(N, h, z, e[1], W.gbar, z, qhat[1], xbar, z, 1, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + z), ld1);   // W1x, d_1, w1s
+    for (int l = 2; l <= L; ++l)
+      wl.push2(N, h, h, e[l], taup[l - 1], h, qhat[l], hh[l - 1], h, 1, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
+  } else {
+    wl.push2(N, h, z, qhat[1], xbar, z, nullptr, nullptr, 0, 0, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + z), ld1);
+    for (int l = 2; l <= L; ++l)
+      wl.push2(N, h, h, qhat[l], hh[l - 1], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
+    wl.push2(N, z, h, W.gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[L].w), h, wl.g(P.neg[L].b), nullptr, 0);   // main.fc
+  }
+  wl.assign(ws, L + 1);
+}
+
+size_t dae_workspace_floats(const DaeLayout& P, int N, bool need_grads) {
+  Bump ws;
+  DaeWs W;
+  dae_carve(P, ws, N, need_grads, W);
+  if (need_grads) {
+    WgradList wl(nullptr);
+    dae_wgrads(P, W, nullptr, nullptr, N, wl, ws);
+  }
+  return ws.off;
+}
+
+int dae_pack_impl(const DaeLayout& P, const float* params, float* packed, hipStream_t st) {
+  PackList pl(params, packed);
+  const DaePacked K(P, pl);
+  ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + P.z, P.neg[0].in, P.h, packed + K.w1s, st));
+  return pl.launch(st);
+}
+
+// h1_ready: the fused front end (dae_perturb.hip) has written h_1 into W.hh[1]
+int dae_impl(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma, const float* eps,
+             const float* ctx, int B, int S, float* workspace, size_t ws_floats, float* loss, float* grads, float* score_out, bool need_grads,
+             hipStream_t st, bool h1_ready = false) {
+  ARDAE_CHECK_ARG(ctx == nullptr, "cdae: kinds 2 / 3 take no context: ctx must be NULL");
+  ARDAE_CHECK_ARG(params && packed && xbar && sigma && workspace, "cdae: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S < (int64_t)1 << 30, "cdae: bad batch (B=%d, S=%d)", B, S);
+  ARDAE_CHECK_ARG(!need_grads || (eps && loss && grads), "cdae: loss/grads/eps must be given");
+  ARDAE_CHECK_ARG(need_grads || score_out, "cdae: score_out is NULL");
+  const DaeLayout P(*d);
+  const DaePacked K(P);
+  const int N = B * S, h = P.h, L = P.L, z = P.z, act = P.act;
+  Bump ws(workspace, ws_floats);
+  DaeWs W;
+  dae_carve(P, ws, N, need_grads, W);
+  WgradList wl(grads);
+  if (need_grads) dae_wgrads(P, W, xbar, sigma, N, wl, ws);
+  ARDAE_CHECK_ARG(ws.ok, "cdae: workspace too small (%zu < %zu floats)", ws_floats, ws.off);
+  const std::vector<float*>&hh = W.hh, &e = W.e, &taup = W.taup, &qbar = W.qbar;
+  float* g = score_out ? score_out : W.gbuf;
+  const float* wfc = params + P.neg[L].w;   // grad kind: w [1, h]
+  // ------------------------------------------------------------------ forward
+  {
+    LayerRun run(EPI_ACT, st);
+    for (int l = h1_ready ? 2 : 1; l <= L; ++l) {
+      LinArgs A{}; A.Y = hh[l]; A.ldY = h; A.bias = params + P.neg[l - 1].b;
+      if (l == 1) { A.rowscale = sigma; A.rowscale_w = packed + K.w1s; }
+      if (P.grad() && l == L) { A.Y2 = e[L]; A.ldY2 = h; A.R = wfc; }   // e_L = -w (.) s(h_L)
+      if (l == 1) run.add(act, N, h, xbar, z, z, packed + K.w1x_f, A);
+      else run.add(act, N, h, hh[l - 1], h, h, packed + K.neg_f[l - 1], A);
+    }
+    ARDAE_TRY(run.flush());
+  }
+  const float inv_nz = 1.0f / ((float)N * (float)z);
+  LinArgs LA{}; LA.sigma = sigma; LA.eps = eps; LA.ldeps = z; LA.scale = inv_nz; LA.Y = g; LA.ldY = z; LA.Y2 = W.gbar; LA.ldY2 = z;
+  LA.tile_loss = W.tile_loss;
+  if (P.grad()) {
+    // ---------------------------------------------------------------- score pass (input-gradient of the energy)
+    LayerRun run(EPI_DACT, st);
+    for (int l = L; l >= 2; --l) {
+      LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = e[l - 1]; A.ldY = h;
+      run.add(act, N, h, e[l], h, h, packed + K.neg_b[l - 1], A);
+    }
+    ARDAE_TRY(run.flush());
+    if (!need_grads) {   // glogprob: g = e_1 W1x
+      LinArgs A{}; A.Y = g; A.ldY = z;
+      return lin1(EPI_ACT, ACT_NONE, N, z, e[1], h, h, packed + K.w1x_b, A, st);
+    }
+    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, e[1], h, h, packed + K.w1x_b, LA, st));
+  } else {
+    if (!need_grads) {
+      LinArgs A{}; A.bias = params + P.neg[L].b; A.Y = g; A.ldY = z;
+      return lin1(EPI_ACT, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st);
+    }
+    LA.bias = params + P.neg[L].b;
+    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, LA, st));
+  }
+  ARDAE_TRY(launch_sum_scale(W.tile_loss, W.ltiles, inv_nz, loss, st));
+
+  // -------------------------------------------------------------------- backward
+  const std::vector<float*>& qhat = qbar;   // in place
+  if (P.grad()) {
+    {
+      LayerRun run(EPI_CHAIN, st);   // forward-mode chain through the score pass
+      for (int l = 1; l <= L; ++l) {
+        LinArgs A{}; A.S = hh[l]; A.ldS = h; A.R = e[l]; A.ldR = h; A.Y = taup[l]; A.ldY = h; A.Y2 = qbar[l]; A.ldY2 = h;
+        if (l == L) A.colsum = W.cs_taup;
+        if (l == 1) run.add(act, N, h, W.gbar, z, z, packed + K.w1x_f, A);
+        else run.add(act, N, h, taup[l - 1], h, h, packed + K.neg_f[l - 1], A);
+      }
+      ARDAE_TRY(run.flush());
+    }
+    // wbar = -colsum(tau'_L)  -> grads of neglogprob.fc.weight [1, h]
+    ARDAE_TRY(launch_segment_sum(W.cs_taup, h, 1, W.ctiles, h, -1.0f, grads + P.neg[L].w, h, st));
+    LayerRun run(EPI_DACT, st);      // ordinary backward of the energy chain, seeded by the qbar_l
+    for (int l = L; l >= 2; --l) {
+      LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Q = qbar[l - 1]; A.ldQ = h; A.Y = qhat[l - 1]; A.ldY = h;
+      run.add(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A);
+    }
+    ARDAE_TRY(run.flush());
+  } else {
+    {
+      LinArgs A{}; A.S = hh[L]; A.ldS = h; A.Y = qhat[L]; A.ldY = h;
+      ARDAE_TRY(lin1(EPI_DACT, act, N, h, W.gbar, z, z, packed + K.fc_b, A, st));
+    }
+    LayerRun run(EPI_DACT, st);
+    for (int l = L; l >= 2; --l) {
+      LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = qhat[l - 1]; A.ldY = h;
+      run.add(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A);
+    }
+    ARDAE_TRY(run.flush());
+  }
+  return wl.launch(st);
+}
+
+inline bool uncond(const ardae_cdae_desc* d) { return d->kind >= 2; }
+
 }  // namespace
+
+// what dae_perturb.hip needs of the unconditional layout: where W1 / d_1 live, and the workspace slot of h_1
+int dae_front_slots(const ardae_cdae_desc* d, int N, size_t ws_floats, size_t* w1, size_t* b1, size_t* h1_off) {
+  ARDAE_TRY(desc_ok(d));
+  ARDAE_CHECK_ARG(uncond(d), "dae_perturb_loss_grads: kind must be 2 or 3");
+  const DaeLayout P(*d);
+  ARDAE_CHECK_ARG(ws_floats >= dae_workspace_floats(P, N, true), "dae_perturb_loss_grads: workspace too small (%zu < %zu floats)", ws_floats,
+                  dae_workspace_floats(P, N, true));
+  *w1 = P.neg[0].w; *b1 = P.neg[0].b; *h1_off = 0;   // dae_carve takes hh[1] first
+  return 0;
+}
+int dae_loss_grads_from_h1(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma, const float* eps,
+                           int N, float* workspace, size_t ws_floats, float* loss, float* grads, hipStream_t st) {
+  return dae_impl(d, params, packed, xbar, sigma, eps, nullptr, N, 1, workspace, ws_floats, loss, grads, nullptr, true, st, true);
+}
+
 }  // namespace ardae
 
 using namespace ardae;
@@ -394,31 +603,37 @@ extern "C" {
 
 size_t ardae_cdae_param_floats(const ardae_cdae_desc* d) {
   if (desc_ok(d) != 0) return 0;
+  if (uncond(d)) return DaeLayout(*d).total;
   return CdaeLayout(*d).total;
 }
 size_t ardae_cdae_packed_floats(const ardae_cdae_desc* d) {
   if (desc_ok(d) != 0) return 0;
   PackList pl;
-  PackedLayout(CdaeLayout(*d), pl);
+  if (uncond(d)) DaePacked(DaeLayout(*d), pl);
+  else PackedLayout(CdaeLayout(*d), pl);
   return pl.total();
 }
 size_t ardae_cdae_workspace_floats(const ardae_cdae_desc* d, int B, int S, int need_grads) {
   if (desc_ok(d) != 0 || B <= 0 || S <= 0) return 0;
+  if (uncond(d)) return dae_workspace_floats(DaeLayout(*d), B * S, need_grads != 0);
   return workspace_floats(CdaeLayout(*d), B, S, need_grads != 0);
 }
 int ardae_cdae_pack(const ardae_cdae_desc* d, const float* params, float* packed, void* stream) {
   ARDAE_TRY(desc_ok(d));
   ARDAE_CHECK_ARG(params && packed, "cdae_pack: null pointer");
+  if (uncond(d)) return dae_pack_impl(DaeLayout(*d), params, packed, (hipStream_t)stream);
   return cdae_pack_impl(CdaeLayout(*d), params, packed, (hipStream_t)stream);
 }
 int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar,
                           const float* sigma, const float* eps, const float* ctx, int B, int S, float* workspace,
                           size_t workspace_floats, float* loss, float* grads, float* score_out, void* stream) {
+  ARDAE_TRY(desc_ok(d));
+  if (uncond(d)) return dae_impl(d, params, packed, xbar, sigma, eps, ctx, B, S, workspace, workspace_floats, loss, grads, score_out, true, (hipStream_t)stream);
   return cdae_impl(d, params, packed, xbar, sigma, eps, ctx, B, S, workspace, workspace_floats, loss, grads, score_out, true,
                    (hipStream_t)stream);
 }
 int ardae_cdae_perturb_fused_ok(const ardae_cdae_desc* d, int nz, int nstd) {
-  if (desc_ok(d) != 0) return 0;
+  if (desc_ok(d) != 0 || uncond(d)) return 0;
   const CdaeLayout P(*d);
   return nstd == 1 && P.inp[0].in == P.z && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
 }
@@ -443,6 +658,8 @@ int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params,
 }
 int ardae_cdae_score(const ardae_cdae_desc* d, const float* params, const float* packed, const float* x, const float* sigma,
                      const float* ctx, int B, int S, float* workspace, size_t workspace_floats, float* score_out, void* stream) {
+  ARDAE_TRY(desc_ok(d));
+  if (uncond(d)) return dae_impl(d, params, packed, x, sigma, nullptr, ctx, B, S, workspace, workspace_floats, nullptr, nullptr, score_out, false, (hipStream_t)stream);
   return cdae_impl(d, params, packed, x, sigma, nullptr, ctx, B, S, workspace, workspace_floats, nullptr, nullptr, score_out, false,
                    (hipStream_t)stream);
 }

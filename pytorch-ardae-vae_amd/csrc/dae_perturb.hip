@@ -1,0 +1,165 @@
+// Front end of the unconditional AR-DAE update (ardae_cdae_desc.kind 2 / 3): the perturbation of a broadcast batch, and the same with
+// its two draws and the score network's first layer in one kernel.
+//
+// Reference: the training cells of notebooks/ardae_toy.ipynb / ardae_fit.ipynb (x.unsqueeze(1).expand(B, nsigma, d).contiguous(),
+// std = delta * randn) and add_gaussian_noise (models/graddae/mlp.py:21-23).  Row (b, j) reads x[b]: the broadcast is never written.
+#include <algorithm>
+
+#include "ardae_hip.h"
+#include "common.h"
+#include "philox.h"
+#include "profile.h"
+
+namespace ardae {
+
+// cdae.hip
+int dae_front_slots(const ardae_cdae_desc* d, int N, size_t ws_floats, size_t* w1, size_t* b1, size_t* h1_off);
+int dae_loss_grads_from_h1(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma, const float* eps,
+                           int N, float* workspace, size_t ws_floats, float* loss, float* grads, hipStream_t st);
+
+namespace {
+
+constexpr int DP_ROWS = 64;   // rows per workgroup of the fused kernel
+constexpr int DP_DMAX = 8;    // widest input it takes as plain FMAs
+
+__global__ __launch_bounds__(256) void dae_perturb_kernel(const float* __restrict__ x, const float* __restrict__ sigma, const float* __restrict__ eps,
+                                                          int64_t n, int nsigma, int d, float* __restrict__ xbar) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = e / d;
+    const int k = (int)(e - row * d);
+    xbar[e] = __builtin_fmaf(sigma[row], eps[e], x[(row / nsigma) * d + k]);
+  }
+}
+
+// One workgroup per tile of 64 rows.  Phase 1: the tile's Philox counters (16 d of the eps draw, 16 of the sigma draw: at most 144 of the
+// 256 threads hold one), then sigma = delta n, xbar = fma(sigma, eps, x[b]) - written out, and kept in LDS.  Phase 2: h_1 =
+// act(W1x xbar + sigma w1s + d_1): K = d + 1 <= 9, so the layer is nothing but its N x h store.  A lane owns FOUR consecutive columns (its
+// 4 (d + 2) weights stay in registers) and h / 4 lanes cover a row, so every store instruction of a wave is 64 x 16 bytes = 1 KiB of
+// consecutive addresses - one full row at h 256, two at h 128, four at h 64; the row's d + 1 inputs are LDS broadcasts.  The dot product
+// is a chain of FMAs in ascending k from 0 (the order the FP32 MFMA of the stand-alone layer adds in), then + d_1, then fma(sigma, w1s, .).
+// Rows at or beyond N (a last partial tile) draw like the others and write nothing.
+__global__ __launch_bounds__(256) void dae_perturb_fwd_kernel(const float* __restrict__ x, int N, int nsigma, int d, float delta, uint64_t seed,
+                                                              uint64_t off_sigma, uint64_t off_eps, const StepState* __restrict__ state,
+                                                              uint64_t first_row, float* __restrict__ xbar, float* __restrict__ sigma,
+                                                              float* __restrict__ eps_out, const float* __restrict__ W1,
+                                                              const float* __restrict__ b1, int h, int act, float* __restrict__ h1) {
+  __shared__ __attribute__((aligned(16))) float neps[DP_ROWS * DP_DMAX];
+  __shared__ __attribute__((aligned(16))) float nsig[DP_ROWS];
+  __shared__ float xb[DP_ROWS * DP_DMAX];
+  __shared__ float sg[DP_ROWS];
+  const int t = threadIdx.x;
+  const int row0 = blockIdx.x * DP_ROWS;
+  const uint64_t base_off = state ? state->rng_offset : 0;
+  const uint64_t r_first = first_row + (uint64_t)row0;   // a multiple of 4
+  if (t < 16 * d) {
+    float v[4];
+    philox_normal4(seed, off_eps + base_off, ((r_first * (uint64_t)d) >> 2) + (uint64_t)t, v);
+    *reinterpret_cast<f32x4*>(neps + 4 * t) = f32x4{v[0], v[1], v[2], v[3]};
+  } else if (t < 16 * d + 16) {
+    const int c = t - 16 * d;
+    float v[4];
+    philox_normal4(seed, off_sigma + base_off, (r_first >> 2) + (uint64_t)c, v);
+    *reinterpret_cast<f32x4*>(nsig + 4 * c) = f32x4{v[0], v[1], v[2], v[3]};
+  }
+  __syncthreads();
+  for (int e = t; e < DP_ROWS * d; e += 256) {
+    const int r = e / d, k = e - r * d;
+    const int row = row0 + r;
+    float s = 0.f, xv = 0.f;
+    if (row < N) {
+      s = delta * nsig[r];
+      const float ep = neps[e];
+      xv = __builtin_fmaf(s, ep, x[(size_t)(row / nsigma) * d + k]);
+      xbar[(size_t)row * d + k] = xv;
+      eps_out[(size_t)row * d + k] = ep;
+      if (k == 0) sigma[row] = s;
+    }
+    xb[e] = xv;
+    if (k == 0) sg[r] = s;
+  }
+  __syncthreads();
+  const int lane = t & 63, wave = t >> 6;
+  const int lpr = h >> 2, rpw = 64 / lpr;          // lanes per row, rows per wave store
+  const int lc = lane % lpr, lr = lane / lpr, c0 = 4 * lc;
+  float w[4][DP_DMAX], ws[4], bs[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float* wr = W1 + (size_t)(c0 + j) * (d + 1);
+#pragma unroll
+    for (int k = 0; k < DP_DMAX; ++k) w[j][k] = k < d ? wr[k] : 0.f;
+    ws[j] = wr[d];
+    bs[j] = b1[c0 + j];
+  }
+  for (int r = wave * (DP_ROWS / 4) + lr; r < (wave + 1) * (DP_ROWS / 4); r += rpw) {
+    const int row = row0 + r;
+    if (row >= N) break;
+    const float s = sg[r];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < DP_DMAX; ++k)
+      if (k < d) {
+        const float xv = xb[r * d + k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(xv, w[j][k], acc[j]);
+      }
+    f32x4 y;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = act_fwd_rt(act, __builtin_fmaf(s, ws[j], acc[j] + bs[j]));
+    *reinterpret_cast<f32x4*>(h1 + (size_t)row * h + c0) = y;
+  }
+}
+
+bool fused_shape_ok(const ardae_cdae_desc* d, int nsigma) {
+  return d && (d->kind == 2 || d->kind == 3) && d->context_dim == 0 && d->input_dim >= 1 && d->input_dim <= DP_DMAX &&
+         (d->h_dim == 64 || d->h_dim == 128 || d->h_dim == 256) && d->n_layers >= 2 && d->n_layers <= 6 && d->act > ACT_NONE &&
+         d->act <= ACT_LAST && nsigma >= 1;
+}
+
+}  // namespace
+}  // namespace ardae
+
+using namespace ardae;
+
+extern "C" {
+
+int ardae_dae_perturb(const float* x, const float* sigma, const float* eps, int B, int nsigma, int d, float* xbar, void* stream) {
+  ARDAE_CHECK_ARG(x && sigma && eps && xbar, "dae_perturb: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && nsigma > 0 && d > 0 && (int64_t)B * nsigma * d < (int64_t)1 << 31, "dae_perturb: bad batch (B=%d, nsigma=%d, d=%d)", B,
+                  nsigma, d);
+  const int64_t n = (int64_t)B * nsigma * d;
+  const hipStream_t st = (hipStream_t)stream;
+  prof_begin(st, "dae_perturb_kernel", 2.0 * (double)n, 4.0 * (2.0 * (double)n + (double)B * nsigma + (double)B * d));
+  hipLaunchKernelGGL(dae_perturb_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, x, sigma, eps, n, nsigma, d,
+                     xbar);
+  prof_end(st);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int ardae_dae_perturb_fused_ok(const ardae_cdae_desc* d, int nsigma) { return fused_shape_ok(d, nsigma) ? 1 : 0; }
+
+int ardae_dae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* x, int B, int nsigma,
+                                 float delta, uint64_t seed, uint64_t offset_sigma, uint64_t offset_eps, const void* state,
+                                 uint64_t first_row, float* xbar, float* sigma, float* eps_out, float* workspace,
+                                 size_t workspace_floats, float* loss, float* grads, void* stream) {
+  ARDAE_CHECK_ARG(d != nullptr, "dae_perturb_loss_grads: desc is NULL");
+  ARDAE_CHECK_ARG(B > 0 && nsigma > 0 && (int64_t)B * nsigma < (int64_t)1 << 30, "dae_perturb_loss_grads: bad batch (B=%d, nsigma=%d)", B, nsigma);
+  ARDAE_CHECK_ARG(fused_shape_ok(d, nsigma),
+                  "dae_perturb_loss_grads: shape not eligible (ardae_dae_perturb_fused_ok): use ardae_philox_normal_at + ardae_dae_perturb + "
+                  "ardae_cdae_loss_grads");
+  ARDAE_CHECK_ARG(params && packed && x && xbar && sigma && eps_out && workspace && loss && grads, "dae_perturb_loss_grads: null pointer argument");
+  ARDAE_CHECK_ARG((first_row & 3) == 0, "dae_perturb_loss_grads: first_row must be a multiple of 4 (one Philox counter = 4 normals)");
+  const int N = B * nsigma, h = d->h_dim, z = d->input_dim;
+  size_t w1, b1, h1_off;
+  ARDAE_TRY(dae_front_slots(d, N, workspace_floats, &w1, &b1, &h1_off));
+  const hipStream_t st = (hipStream_t)stream;
+  prof_begin(st, "dae_perturb_fwd_kernel", 2.0 * (double)N * h * (z + 1), 4.0 * ((double)N * h + (double)N * (2 * z + 1) + (double)B * z));
+  hipLaunchKernelGGL(dae_perturb_fwd_kernel, dim3((unsigned)ceil_div(N, DP_ROWS)), dim3(256), 0, st, x, N, nsigma, z, delta, seed, offset_sigma,
+                     offset_eps, (const StepState*)state, first_row, xbar, sigma, eps_out, params + w1, params + b1, h, d->act,
+                     workspace + h1_off);
+  prof_end(st);
+  ARDAE_LAUNCH_CHECK();
+  return dae_loss_grads_from_h1(d, params, packed, xbar, sigma, eps_out, N, workspace, workspace_floats, loss, grads, st);
+}
+
+}  // extern "C"

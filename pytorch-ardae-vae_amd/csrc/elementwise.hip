@@ -1,61 +1,11 @@
 // Bandwidth-bound helper kernels (gfx950).  See elementwise.h for the operator definitions + reference lines.
 #include "elementwise.h"
 #include "linear.h"
+#include "philox.h"
 
 namespace ardae {
 namespace {
 
-// ------------------------------------------------------------------------------------------ Philox4x32-10
-struct Philox {
-  uint32_t c[4];
-  uint32_t k[2];
-};
-__device__ __forceinline__ void philox_round(Philox& s) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  const uint32_t hi0 = __umulhi(M0, s.c[0]), lo0 = M0 * s.c[0];
-  const uint32_t hi1 = __umulhi(M1, s.c[2]), lo1 = M1 * s.c[2];
-  const uint32_t n0 = hi1 ^ s.c[1] ^ s.k[0], n1 = lo1, n2 = hi0 ^ s.c[3] ^ s.k[1], n3 = lo0;
-  s.c[0] = n0; s.c[1] = n1; s.c[2] = n2; s.c[3] = n3;
-  s.k[0] += 0x9E3779B9u;
-  s.k[1] += 0xBB67AE85u;
-}
-__device__ __forceinline__ void philox4(uint64_t seed, uint64_t offset, uint64_t idx, uint32_t out[4]) {
-  Philox s;
-  s.c[0] = (uint32_t)idx; s.c[1] = (uint32_t)(idx >> 32);
-  s.c[2] = (uint32_t)offset; s.c[3] = (uint32_t)(offset >> 32);
-  s.k[0] = (uint32_t)seed; s.k[1] = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) philox_round(s);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) out[i] = s.c[i];
-}
-__device__ __forceinline__ float u01_open(uint32_t x) { return ((x >> 8) + 1u) * (1.0f / 16777216.0f); }  // (0,1]
-// the four standard normals of Philox counter `idx` (Box-Muller on the two word pairs): the ONE definition every draw uses -
-// the stand-alone kernel and the draws fused into their consumers give the same numbers for the same (seed, offset, element)
-__device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t offset, uint64_t idx, float v[4]) {
-  uint32_t r[4];
-  philox4(seed, offset, idx, r);
-  // Box-Muller on the hardware transcendental units (round 4): v_log_f32 is log2, v_sin_f32 / v_cos_f32 take their argument in
-  // REVOLUTIONS, so sin(2 pi u) is one instruction with no range reduction.  ~12 vector-ALU instructions per pair instead of the ~150
-  // of logf + sincosf (the draws fused into latent_perturb_reg_kernel made that kernel issue-bound: SQ_WAIT_INST_ANY = a third of its
-  // wave cycles).  Absolute accuracy ~1e-6 - these are noise samples; what matters is that EVERY draw uses this one definition.
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float rad = __builtin_amdgcn_sqrtf(-1.38629436111989062f * __builtin_amdgcn_logf(u01_open(r[2 * h])));      // sqrt(-2 ln u)
-    const float rev = u01_open(r[2 * h + 1]);
-    v[2 * h] = rad * __builtin_amdgcn_cosf(rev);
-    v[2 * h + 1] = rad * __builtin_amdgcn_sinf(rev);
-  }
-}
-
-// Device-resident step state (ardae_step_state_advance): lets a captured HIP graph replay the step with fresh noise and
-// the right Adam bias correction - kernel arguments are frozen at capture, this block is not.
-struct StepState {
-  uint64_t rng_offset;     // base offset of this step's Philox draws
-  int64_t adam_step;       // t of utils/optim.py:84
-  float adam_step_size;    // lr / (1 - beta1^t)
-  float adam_sqrt_bc2;     // sqrt(1 - beta2^t)
-};
 
 __global__ void step_state_advance_kernel(StepState* s, uint64_t rng_inc, double lr, double beta1, double beta2) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;

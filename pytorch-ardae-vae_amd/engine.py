@@ -876,3 +876,160 @@ class ArdaeEngine:
         """Host copy of the logged scalars of ivae_ardae.py:756-758,774,837-841 (this is the only synchronising call)."""
         v = torch.cat([self.loss_c, self.losses_m, self.std_b.mean().reshape(1), self.std_b.max().reshape(1), self.std_b.min().reshape(1)]).tolist()
         return dict(cdae_loss=v[0], model_loss=v[1], recon=v[2], prior=v[3], std_mean=v[4], std_max=v[5], std_min=v[6])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Unconditional AR-DAE: the score-estimator half of notebooks/ardae_toy.ipynb / ardae_fit.ipynb
+# ---------------------------------------------------------------------------------------------------------------
+@dataclass
+class ScoreConfig:
+    """Constants of the notebooks' AR-DAE update (ardae_toy.ipynb: delta 1, num_sigma 10, lr 5e-3; ardae_fit.ipynb: lr 1e-3)."""
+    delta: float = 1.0            # sigma = delta * randn per row
+    nsigma: int = 10              # noise levels per sample (`num_sigma`): a batch of B samples is B * nsigma rows
+    lr: float = 1e-3
+    optimizer: str = "rmsprop"    # sgd | adam | amsgrad | rmsprop (_FlatOpt).  "adam" is the reference's VENDORED Adam (utils/optim.py:
+    beta1: float = 0.5            # epsilon before the bias correction), not the torch.optim.Adam the notebooks construct; for that one
+    momentum: float = 0.5         # use the module path (MLPGradARDAE + torch.optim.Adam).  rmsprop and sgd coincide with torch's.
+
+
+class ArdaeScoreEngine:
+    """One AR-DAE update of an unconditional score network (`net.MLPGradARDAE` / `net.MLPResARDAE`) as ONE captured unit:
+    advance the step state, draw sigma and eps, perturb the broadcast batch, loss and gradients on B * nsigma rows, optimiser,
+    re-pack.  The rules are ArdaeEngine's: `step()` is captured at its third call and replayed afterwards (replayed == eager bit for
+    bit), `noise={'sigma' [B * nsigma], 'eps' [B * nsigma, d]}` runs the same launches eagerly on injected draws, batches are
+    validated before any pointer reaches a kernel, in-step Philox offsets are RNG_STRIDE * step + {0 (sigma), 1 (eps)} - below
+    rng.HOST_STREAM.  One stream, one linear graph; there is no data parallelism here.
+
+    The sampler of ardae_fit.ipynb stays the caller's torch module; its entropy gradient is
+    `output.backward(engine.score(output.detach()) / B)`."""
+
+    RNG_STRIDE = ArdaeEngine.RNG_STRIDE
+
+    def __init__(self, dae, cfg: ScoreConfig, batch_size, graph=True):
+        dae._require_gpu()
+        if int(dae._desc.kind) not in (2, 3):
+            raise TypeError("ArdaeScoreEngine drives the unconditional networks (net.MLPGradARDAE / net.MLPResARDAE)")
+        if int(cfg.nsigma) < 1 or int(batch_size) < 1:
+            raise ValueError(f"nsigma and batch_size must be positive (got {cfg.nsigma}, {batch_size})")
+        self.dae, self.cfg = dae, cfg
+        self.B, self.S, self.d = int(batch_size), int(cfg.nsigma), int(dae.input_dim)
+        self.N = self.B * self.S
+        self.dev = dae._flat.device
+        f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
+        self.ws = f(L.query("ardae_cdae_workspace_floats", dae._desc, self.N, 1, 1))
+        self.xbar, self.sigma, self.eps, self.nrm = f(self.N, self.d), f(self.N), f(self.N, self.d), f(self.N)
+        self._zero = torch.zeros(self.N, device=self.dev)
+        self.loss = f(1)
+        self.grads = torch.zeros_like(dae._flat)
+        self.n_grad = dae._flat.numel() - (1 if dae._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
+        self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        self.opt = _FlatOpt(cfg.optimizer, dae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state)
+        if graph not in (True, False):
+            raise ValueError(f"graph must be True or False, got {graph!r}")
+        self.use_graph = bool(graph) and L.debug_knob("ARDAE_GRAPH", "1") != "0"
+        self.fused_front = L.debug_knob("ARDAE_FUSED_DAE_FRONT", "1") != "0" and bool(L.query("ardae_dae_perturb_fused_ok", dae._desc, self.S))
+        self._graph, self._x, self._calls = None, None, 0
+        self._cap_stream = torch.cuda.Stream(device=self.dev)
+        self._score_ws = {}
+        self.step_count = 0
+        self.opt.advance(self.RNG_STRIDE)      # the step state always describes the COMING step
+        self.repack()
+
+    def repack(self):
+        self.dae._packed = None
+        self.pk = self.dae._packed_weights()
+
+    def _check_batch(self, x, what):
+        """Exactly B * input_dim contiguous fp32 values on the engine's device (ArdaeEngine._check_batch's rules)."""
+        if not torch.is_tensor(x):
+            raise TypeError(f"{what}: expected a tensor, got {type(x).__name__}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{what}: expected a float32 tensor, got {x.dtype}")
+        if x.dim() < 2 or x.size(0) != self.B or x.numel() != self.B * self.d:
+            raise ValueError(f"{what}: expected {self.B} samples of {self.d} values (the engine was built with batch_size={self.B}), "
+                             f"got shape {tuple(x.shape)}")
+        if not x.is_contiguous():
+            raise ValueError(f"{what}: the batch must be contiguous (got strides {tuple(x.stride())}); call .contiguous()")
+        if not x.is_cuda or x.device != self.dev:
+            raise ValueError(f"{what}: expected a tensor on {self.dev}, got one on {x.device}")
+
+    def _body(self, x, noise):
+        d, seed = self.dae._desc, rng.get_state()["seed"]
+        if noise is None and self.fused_front:
+            L.call("ardae_dae_perturb_loss_grads", d, self.dae._flat, self.pk, x, self.B, self.S, float(self.cfg.delta), seed, 0, 1, self.state, 0,
+                   self.xbar, self.sigma, self.eps, self.ws, self.ws.numel(), self.loss, self.grads)
+        else:
+            if noise is None:
+                L.call("ardae_philox_normal_at", self.nrm, self.N, seed, 0, self.state, 0)
+                L.call("ardae_center_scale", self.nrm, self._zero, self.N, 1, 1, float(self.cfg.delta), self.sigma)     # sigma = delta * n
+                L.call("ardae_philox_normal_at", self.eps, self.N * self.d, seed, 1, self.state, 0)
+                sigma, eps = self.sigma, self.eps
+            else:
+                sigma, eps = noise["sigma"], noise["eps"]
+            L.call("ardae_dae_perturb", x, sigma, eps, self.B, self.S, self.d, self.xbar)
+            L.call("ardae_cdae_loss_grads", d, self.dae._flat, self.pk, self.xbar, sigma, eps, None, self.N, 1, self.ws, self.ws.numel(), self.loss,
+                   self.grads, None)
+        self.opt.apply(self.grads, True)      # Adam's t and bias corrections come from the device block
+        L.call("ardae_cdae_pack", d, self.dae._flat, self.pk)
+        self.opt.advance(self.RNG_STRIDE)     # for the NEXT step: Philox base += stride, t += 1
+
+    def step(self, x, noise=None):
+        """One AR-DAE update on the B samples x [B, d] (each used with nsigma noise levels)."""
+        self._check_batch(x, "step(x)")
+        if noise is not None:
+            sg, ep = noise["sigma"], noise["eps"]
+            for t, n, nm in ((sg, self.N, "sigma"), (ep, self.N * self.d, "eps")):
+                if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == n):
+                    raise ValueError(f"step(noise): {nm} must be a contiguous float32 tensor of {n} values on {self.dev}")
+            # into the engine's own buffers: the launches (and stats()) then read what a drawn step would have left there
+            self.sigma.copy_(sg.reshape(-1))
+            self.eps.copy_(ep.reshape(self.N, self.d))
+            self._body(x, {"sigma": self.sigma, "eps": self.eps})
+        elif not self.use_graph:
+            self._body(x, None)
+        else:
+            if self._x is None:
+                self._x = torch.empty(self.B, self.d, device=self.dev, dtype=torch.float32)
+            if x is not self._x:
+                self._x.copy_(x.view(self.B, self.d))
+            if self._graph is not None:
+                self._graph.replay()
+            elif self._calls < 2:               # the first two calls eagerly: every kernel is loaded outside of a capture
+                self._body(self._x, None)
+            else:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=self._cap_stream):
+                    self._body(self._x, None)
+                g.replay()                      # a capture runs nothing
+                self._graph = g
+        self._calls += 1
+        self.step_count += 1
+        self.opt.steps = self.step_count
+        for p in self.dae.parameters():         # the module path re-packs at its next use
+            torch.autograd.graph.increment_version(p)
+
+    def input_buffer(self):
+        """The static batch buffer [B, d]: a sampler that writes its batch there and passes the same tensor to step() saves the copy."""
+        if self._x is None:
+            self._x = torch.empty(self.B, self.d, device=self.dev, dtype=torch.float32)
+        return self._x
+
+    def score(self, x, sigma=None):
+        """glogprob(x, sigma) with the engine's weight image: x [R, d] (any R), sigma [R] / [R, 1] or None = zeros."""
+        if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.size(1) == self.d):
+            raise ValueError(f"score(x): expected a contiguous float32 [R, {self.d}] tensor on {self.dev}")
+        R = x.size(0)
+        s = torch.zeros(R, device=self.dev) if sigma is None else sigma.detach().to(torch.float32).reshape(-1).contiguous()
+        if s.numel() != R:
+            raise ValueError(f"score(sigma): {s.numel()} entries for {R} rows")
+        ws = self._score_ws.get(R)
+        if ws is None:
+            ws = self._score_ws[R] = torch.empty(L.query("ardae_cdae_workspace_floats", self.dae._desc, R, 1, 0), device=self.dev)
+        out = torch.empty(R, self.d, device=self.dev)
+        L.call("ardae_cdae_score", self.dae._desc, self.dae._flat, self.pk, x.detach(), s, None, R, 1, ws, ws.numel(), out)
+        return out
+
+    def stats(self):
+        """Host copy of the last step's loss and mean |sigma| (the only synchronising call)."""
+        v = torch.cat([self.loss, self.sigma.abs().mean().reshape(1)]).tolist()
+        return dict(loss=v[0], sigma_abs_mean=v[1])

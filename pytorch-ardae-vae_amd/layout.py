@@ -1,8 +1,8 @@
 """Parameter names / shapes / flat-buffer offsets, identical to the reference's `named_parameters()` order.
 
 Reference: models/layers.py:477-515 (MLP: `layers.{i}.{weight,bias}`, `fc.{weight,bias}`), :681-724 (ContextConcatMLP),
-models/ivae/mnist.py:123-199, models/ivae/toy.py:154-194,694-737, models/graddae/mlp.py:342-378,
-models/resdae/mlp.py:287-326.  The C++ side (csrc/cdae.hip, csrc/model.hip) computes the same offsets; the ABI
+models/ivae/mnist.py:123-199, models/ivae/toy.py:154-194,694-737, models/graddae/mlp.py:137,342-378,
+models/resdae/mlp.py:111,287-326.  The C++ side (csrc/cdae.hip, csrc/model.hip) computes the same offsets; the ABI
 test checks `ardae_*_param_floats` against these totals.
 """
 import math
@@ -113,6 +113,16 @@ def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):
     else:
         raise NotImplementedError(kind)
     return s
+
+
+def dae_spec(kind, input_dim, h_dim, n_layers):
+    """The unconditional AR-DAE (models/graddae/mlp.py:137, models/resdae/mlp.py:111): one MLP on [x_bar | sigma]; `layers.0.weight`
+    is [h, d + 1] = [W1x | w1s].  ardae_cdae_desc.kind 2 ('grad') / 3 ('res')."""
+    if kind == "grad":
+        return _mlp("neglogprob.", input_dim + 1, h_dim, 1, n_layers)
+    if kind == "res":
+        return _mlp("main.", input_dim + 1, h_dim, input_dim, n_layers)
+    raise NotImplementedError(kind)
 
 
 def offsets(spec):

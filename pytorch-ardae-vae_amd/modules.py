@@ -2,6 +2,7 @@
 
     net.MNISTIPVAE / net.ToyIPVAE        <- models/ivae/mnist.py:201-301, models/ivae/toy.py:739-873 (enc_type='concat')
     net.MLPGradCARDAE / net.MLPResCARDAE <- models/graddae/mlp.py:341-483, models/resdae/mlp.py:286-413
+    net.MLPGradARDAE / net.MLPResARDAE   <- models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167
 
 Same constructor kwargs, same `state_dict()` keys and `[out, in]` layouts (reference checkpoints load), same method
 names and argument meaning, same exception types.  Parameters are `nn.Parameter` views into ONE flat fp32 buffer
@@ -230,6 +231,100 @@ class MLPGradCARDAE(ConditionalARDAE):
 
 class MLPResCARDAE(ConditionalARDAE):
     """models/resdae/mlp.py::ConditionalARDAE (`--cdae mlp-res`)."""
+    _kind = "res"
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# unconditional AR-DAE (the score estimator of notebooks/ardae_toy.ipynb / ardae_fit.ipynb)
+# ---------------------------------------------------------------------------------------------------------------
+class _DaeLossFn(torch.autograd.Function):
+    """forward = ARDAE.forward's loss; the double backward runs in the same ABI call, so backward() only scales."""
+
+    @staticmethod
+    def forward(ctx, mod, xbar, sigma, eps, N, *params):
+        d = mod._desc
+        ws = mod._ws(L.query("ardae_cdae_workspace_floats", d, N, 1, 1))
+        loss = torch.empty(1, device=xbar.device)
+        grads = torch.zeros_like(mod._flat)
+        L.call("ardae_cdae_loss_grads", d, mod._flat, mod._packed_weights(), xbar, sigma, eps, None, N, 1, ws, ws.numel(), loss, grads, None)
+        ctx.mod, ctx.grads = mod, grads
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        mod = ctx.mod
+        out = []
+        for name, p in mod.named_parameters():
+            if name in mod._no_grad_names:
+                out.append(None)      # the reference leaves .grad = None here: the energy's offset does not reach its input-gradient
+                continue
+            off, n, shape = mod._offs[name]
+            out.append(ctx.grads[off:off + n].view(shape) * gloss)
+        return (None,) * 5 + tuple(out)
+
+
+class ARDAE(FlatParamModule):
+    """models/graddae/mlp.py:118-207 / models/resdae/mlp.py:92-167: the AR-DAE score network on [x_bar | sigma], no context."""
+    _kind = None
+    _packed_floats_fn, _pack_fn = "ardae_cdae_packed_floats", "ardae_cdae_pack"
+
+    def __init__(self, input_dim=2, h_dim=1000, std=0.1, num_hidden_layers=1, nonlinearity="tanh", noise_type="gaussian"):
+        super().__init__()
+        if noise_type != "gaussian":
+            raise NotImplementedError            # uniform / laplace (graddae/mlp.py:143-146) are not on the path
+        if nonlinearity not in L.ACT or nonlinearity in ("none", None):
+            raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
+        if num_hidden_layers < 1:
+            raise NotImplementedError("num_hidden_layers >= 1 (a score network without a hidden layer is linear in [x | sigma])")
+        self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
+        self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
+        self._desc = L.CdaeDesc(2 if self._kind == "grad" else 3, input_dim, 0, h_dim, num_hidden_layers, L.ACT[nonlinearity])
+        self._build_params(layout.dae_spec(self._kind, input_dim, h_dim, num_hidden_layers))
+        self._no_grad_names = {"neglogprob.fc.bias"} if self._kind == "grad" else set()
+        self._default_init()
+
+    def _prep(self, input, std):
+        self._require_gpu(input, std if torch.is_tensor(std) else None)
+        batch_size = input.size(0)
+        x = _f32c(input).view(-1, self.input_dim)
+        if std is None:
+            std = x.new_zeros(batch_size, 1)                # graddae/mlp.py:159-160
+        else:
+            assert torch.is_tensor(std)
+        s = _f32c(std).reshape(-1)
+        if s.numel() != x.size(0):
+            raise ValueError(f"std has {s.numel()} entries for {x.size(0)} rows")
+        return x, s
+
+    def forward(self, input, std=None, eps=None):
+        """-> (None, loss) like the reference.  `eps` injects the Gaussian perturbation draw ([N, input_dim]); default: the library's
+        Philox stream."""
+        x, s = self._prep(input, std)
+        N = x.size(0)
+        if eps is None:
+            eps = rng.normal((N, self.input_dim), x.device)
+        eps = _f32c(eps).view(N, self.input_dim)
+        xbar = torch.empty_like(x)
+        L.call("ardae_dae_perturb", x, s, eps, N, 1, self.input_dim, xbar)      # add_gaussian_noise (graddae/mlp.py:21-23)
+        loss = _DaeLossFn.apply(self, xbar, s, eps, N, *self.parameters())
+        return None, loss
+
+    def glogprob(self, input, std=None):
+        x, s = self._prep(input, std)
+        N = x.size(0)
+        ws = self._ws(L.query("ardae_cdae_workspace_floats", self._desc, N, 1, 0))
+        out = torch.empty(N, self.input_dim, device=x.device)
+        L.call("ardae_cdae_score", self._desc, self._flat, self._packed_weights(), x, s, None, N, 1, ws, ws.numel(), out)
+        return out
+
+
+class MLPGradARDAE(ARDAE):
+    """models/graddae/mlp.py::ARDAE (exported as MLPGradARDAE, models/__init__.py:11): score = input-gradient of an energy MLP."""
+    _kind = "grad"
+
+
+class MLPResARDAE(ARDAE):
+    """models/resdae/mlp.py::ARDAE (exported as MLPResARDAE, models/__init__.py:6): the MLP's output is the score."""
     _kind = "res"
 
 

@@ -1,0 +1,208 @@
+"""Unconditional AR-DAE score networks (ardae_cdae_desc.kind 2 / 3): layout, argument validation, module surface, and the float64
+restatement of the two networks that the GPU tests lean on - pinned here to the reference's fp64 fixtures.  No GPU needed."""
+import ctypes
+import glob
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ardae_amd as net
+from ardae_amd import _lib as L
+from ardae_amd import layout
+
+KIND_ID = {"grad": 2, "res": 3}
+# parameter counts of the reference classes, (d, h, L) -> (grad, res)
+REFERENCE_COUNTS = {(2, 256, 3): (132865, 133122), (32, 256, 3): (140545, 148512), (2, 64, 3): (8641, 8706), (3, 100, 2): (10701, 10903)}
+
+
+def fixtures(golden_dir, kind=None):
+    names = sorted(glob.glob(os.path.join(golden_dir, f"ardae_uncond_{kind or '*'}_n*.npz")))
+    assert len(names) == (5 if kind else 10)
+    return names
+
+
+def load(path):
+    return dict(np.load(path))
+
+
+def state_dict_of(fx):
+    return {k[3:]: torch.tensor(v) for k, v in fx.items() if k.startswith("sd/")}
+
+
+# ---- the test-side oracle: the two networks restated (models/layers.py:477-515 MLP on [x_bar | sigma]) ----------------------------
+ACTS = {"relu": torch.relu, "softplus": torch.nn.functional.softplus, "elu": torch.nn.functional.elu, "tanh": torch.tanh,
+        "leaky_relu": lambda t: torch.nn.functional.leaky_relu(t, 0.2), "swish": lambda t: t * torch.sigmoid(t)}
+
+
+def mlp(p, prefix, hdn, act):
+    n = len([k for k in p if k.startswith(prefix + "layers.") and k.endswith("weight")])
+    for i in range(n):
+        hdn = ACTS[act](hdn @ p[f"{prefix}layers.{i}.weight"].t() + p[f"{prefix}layers.{i}.bias"])
+    return hdn @ p[prefix + "fc.weight"].t() + p[prefix + "fc.bias"]
+
+
+def score(kind, p, act, x, std, create_graph=False):
+    if kind == "res":
+        return mlp(p, "main.", torch.cat([x, std], 1), act)
+    x = x if x.requires_grad else x.clone().requires_grad_(True)
+    logprob = -mlp(p, "neglogprob.", torch.cat([x, std], 1), act).sum()
+    return torch.autograd.grad(logprob, x, create_graph=create_graph)[0]
+
+
+def loss_and_grads(kind, p, act, x, std, eps):
+    """-> loss, {name: grad or None}, with p's tensors as leaves"""
+    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
+    xbar = (x + std * eps).requires_grad_(True)
+    loss = torch.nn.functional.mse_loss(std * score(kind, p, act, xbar, std, create_graph=True), -eps)
+    return loss.detach(), dict(zip(p, torch.autograd.grad(loss, list(p.values()), allow_unused=True)))
+
+
+def rel(a, b):
+    a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
+    return float((a - b).norm() / (b.norm() + 1e-300))
+
+
+# ---- 1. layout ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["grad", "res"])
+def test_layout_totals_match_c_side_and_reference_counts(kind):
+    for (d, h, nl), counts in REFERENCE_COUNTS.items():
+        total = layout.offsets(layout.dae_spec(kind, d, h, nl))[1]
+        desc = L.CdaeDesc(KIND_ID[kind], d, 0, h, nl, L.ACT["softplus"])
+        assert total == L.query("ardae_cdae_param_floats", desc) == counts[kind == "res"]
+        assert L.query("ardae_cdae_packed_floats", desc) > total
+        assert L.query("ardae_cdae_workspace_floats", desc, 16, 4, 1) > L.query("ardae_cdae_workspace_floats", desc, 16, 4, 0) > 0
+        assert L.query("ardae_cdae_workspace_floats", desc, 16, 4, 1) == L.query("ardae_cdae_workspace_floats", desc, 64, 1, 1)    # N = B S in any factorisation
+
+
+def test_layout_names_and_shapes_are_the_fixtures(golden_dir):
+    for path in fixtures(golden_dir):
+        fx = load(path)
+        (_, d, h, nl), kind = (int(v) for v in fx["shape"]), str(fx["kind"])
+        sd = state_dict_of(fx)
+        assert [(n, tuple(s)) for n, s in layout.dae_spec(kind, d, h, nl)] == [(k, tuple(v.shape)) for k, v in sd.items()], path
+
+
+# ---- 2. validation before any HIP call ---------------------------------------------------------------------------------------------
+def test_argument_validation_of_the_unconditional_entry_points():
+    lib = L.lib()
+    one, big = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40)      # any non-null address: validation must fail before it is dereferenced
+
+    def fails(rc, fragment):
+        assert rc < 0
+        assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
+
+    ok = L.CdaeDesc(2, 2, 0, 64, 3, 2)
+    ref = ctypes.byref
+    for bad, fragment in ((L.CdaeDesc(2, 2, 1, 64, 3, 2), "context_dim must be 0"), (L.CdaeDesc(3, 2, 2, 64, 3, 2), "context_dim must be 0"),
+                          (L.CdaeDesc(0, 2, 0, 64, 3, 2), "context_dim >= 1"), (L.CdaeDesc(1, 2, 0, 64, 3, 2), "context_dim >= 1"),
+                          (L.CdaeDesc(4, 2, 0, 64, 3, 2), "kind must be")):
+        assert lib.ardae_cdae_param_floats(ref(bad)) == lib.ardae_cdae_packed_floats(ref(bad)) == lib.ardae_cdae_workspace_floats(ref(bad), 4, 8, 1) == 0
+        fails(lib.ardae_cdae_pack(ref(bad), one, one, None), fragment)
+        fails(lib.ardae_cdae_loss_grads(ref(bad), one, one, one, one, one, None, 4, 8, one, big, one, one, None, None), fragment)
+        fails(lib.ardae_cdae_score(ref(bad), one, one, one, one, None, 4, 8, one, big, one, None), fragment)
+        assert lib.ardae_dae_perturb_fused_ok(ref(bad), 10) == 0
+    # a context pointer is an error for the unconditional kinds, not ignored
+    fails(lib.ardae_cdae_loss_grads(ref(ok), one, one, one, one, one, one, 4, 8, one, big, one, one, None, None), "ctx must be NULL")
+    fails(lib.ardae_cdae_score(ref(ok), one, one, one, one, one, 4, 8, one, big, one, None), "ctx must be NULL")
+    fails(lib.ardae_cdae_loss_grads(ref(ok), one, one, None, one, one, None, 4, 8, one, big, one, one, None, None), "null pointer")
+    fails(lib.ardae_cdae_loss_grads(ref(ok), one, one, one, one, one, None, 0, 8, one, big, one, one, None, None), "bad batch")
+    fails(lib.ardae_cdae_loss_grads(ref(ok), one, one, one, one, one, None, 4, 8, one, ctypes.c_size_t(16), one, one, None, None), "workspace too small")
+    # the perturbation and the fused front end
+    fails(lib.ardae_dae_perturb(None, one, one, 4, 8, 2, one, None), "null pointer")
+    fails(lib.ardae_dae_perturb(one, one, one, 0, 8, 2, one, None), "bad batch")
+    fails(lib.ardae_dae_perturb(one, one, one, 4, 0, 2, one, None), "bad batch")
+    fused = lambda desc, x, B, ns, first, ws: lib.ardae_dae_perturb_loss_grads(ref(desc), one, one, x, B, ns, 1.0, 7, 0, 1, None, first, one, one, one, one,
+                                                                                ws, one, one, None)
+    fails(fused(ok, None, 4, 8, 0, big), "null pointer")
+    fails(fused(ok, one, 0, 8, 0, big), "bad batch")
+    fails(fused(ok, one, 4, 0, 0, big), "bad batch")
+    fails(fused(ok, one, 4, 8, 2, big), "first_row must be a multiple of 4")
+    fails(fused(ok, one, 4, 8, 0, ctypes.c_size_t(16)), "workspace too small")
+    fails(fused(L.CdaeDesc(2, 3, 0, 100, 2, 3), one, 4, 8, 0, big), "not eligible")
+    fails(fused(L.CdaeDesc(0, 2, 2, 64, 3, 2), one, 4, 8, 0, big), "not eligible")
+
+
+def test_fused_front_end_eligibility_answers_without_a_device():
+    okq = lambda kind, d, h, nl, act, ns: L.query("ardae_dae_perturb_fused_ok", L.CdaeDesc(kind, d, 0, h, nl, L.ACT[act]), ns)
+    for kind in (2, 3):
+        assert okq(kind, 2, 256, 3, "softplus", 10) == 1      # ardae_fit.ipynb: 1024 x 10 rows, h 256
+        assert okq(kind, 2, 128, 3, "softplus", 10) == 1      # ardae_toy.ipynb: 256 x 10 rows, h 128
+        assert okq(kind, 3, 100, 2, "elu", 10) == 0           # h is not 64 | 128 | 256
+        assert okq(kind, 32, 256, 3, "softplus", 10) == 0     # d > 8
+        assert okq(kind, 2, 64, 1, "relu", 10) == 0           # a single layer also seeds the score pass
+        assert okq(kind, 2, 256, 3, "softplus", 0) == 0
+    assert L.query("ardae_dae_perturb_fused_ok", L.CdaeDesc(0, 2, 2, 256, 3, 2), 10) == 0
+    assert L.query("ardae_cdae_perturb_fused_ok", L.CdaeDesc(2, 8, 0, 256, 3, 2), 256, 1) == 0   # the conditional front end refuses kinds 2 / 3
+
+
+# ---- 3. modules --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cls,names", [(net.MLPGradARDAE, ["neglogprob.layers.0.weight", "neglogprob.layers.0.bias", "neglogprob.fc.weight", "neglogprob.fc.bias"]),
+                                       (net.MLPResARDAE, ["main.layers.0.weight", "main.layers.0.bias", "main.fc.weight", "main.fc.bias"])])
+def test_module_defaults_are_the_references(cls, names):
+    m = cls()
+    assert (m.input_dim, m.h_dim, m.std, m.num_hidden_layers, m.nonlinearity, m.noise_type) == (2, 1000, 0.1, 1, "tanh", "gaussian")
+    assert [n for n, _ in m.named_parameters()] == names
+    assert m.state_dict()[names[0]].shape == (1000, 3)
+    assert int(m._desc.kind) == (2 if cls is net.MLPGradARDAE else 3) and int(m._desc.context_dim) == 0
+    with pytest.raises(NotImplementedError):
+        cls(noise_type="laplace")
+    with pytest.raises(NotImplementedError):
+        cls(nonlinearity="gelu")
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        cls(h_dim=16)(torch.zeros(4, 2), torch.zeros(4, 1))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        cls(h_dim=16).glogprob(torch.zeros(4, 2))
+
+
+def test_load_state_dict_keeps_flat_views(golden_dir):
+    for path in fixtures(golden_dir):
+        fx = load(path)
+        (_, d, h, nl), kind = (int(v) for v in fx["shape"]), str(fx["kind"])
+        m = (net.MLPGradARDAE if kind == "grad" else net.MLPResARDAE)(input_dim=d, h_dim=h, num_hidden_layers=nl, nonlinearity=str(fx["act"]))
+        sd = state_dict_of(fx)
+        m.load_state_dict(sd)
+        off = 0
+        for n, p in m.named_parameters():
+            assert p.data_ptr() == m.flat_params().data_ptr() + 4 * off and torch.equal(p, sd[n])
+            off += p.numel()
+        assert off == m.flat_params().numel() == L.query("ardae_cdae_param_floats", m._desc)
+
+
+def test_score_engine_refuses_other_networks_and_bad_batches():
+    import types
+    from ardae_amd.engine import ArdaeScoreEngine
+    eng = types.SimpleNamespace(B=4, d=2, dev=torch.device("cuda", 0))
+    check = lambda x: ArdaeScoreEngine._check_batch(eng, x, "step(x)")
+    with pytest.raises(ValueError, match="on cuda:0"):
+        check(torch.zeros(4, 2))                      # host batch
+    with pytest.raises(ValueError, match="batch_size=4"):
+        check(torch.zeros(3, 2))
+    with pytest.raises(ValueError, match="batch_size=4"):
+        check(torch.zeros(4, 3))
+    with pytest.raises(ValueError, match="contiguous"):
+        check(torch.zeros(4, 4)[:, ::2])
+    with pytest.raises(ValueError, match="float32"):
+        check(torch.zeros(4, 2).double())
+    with pytest.raises(TypeError):
+        check([[0.0, 0.0]] * 4)
+    assert ArdaeScoreEngine.RNG_STRIDE * 1000 + 1 < net.rng.HOST_STREAM
+
+
+# ---- 4. the float64 restatement reproduces every fp64 fixture ----------------------------------------------------------------------
+def test_restatement_reproduces_the_fp64_fixtures(golden_dir):
+    for path in fixtures(golden_dir):
+        fx = load(path)
+        kind, act = str(fx["kind"]), str(fx["act"])
+        p = {k: v.double() for k, v in state_dict_of(fx).items()}
+        x, std, eps = (torch.tensor(fx[k]).double() for k in ("x", "std", "eps"))
+        loss, grads = loss_and_grads(kind, p, act, x, std, eps)
+        assert abs(float(loss) - float(fx["loss64"])) <= 1e-12 * abs(float(fx["loss64"])), path
+        for n, g in grads.items():
+            if f"g64/{n}/none" in fx:
+                assert g is None, (path, n)
+            else:
+                assert rel(g, fx["g64/" + n]) <= 1e-12, (path, n, rel(g, fx["g64/" + n]))
+        assert rel(score(kind, p, act, x, torch.zeros_like(std)), fx["glog0_64"]) <= 1e-12, path
+        assert rel(score(kind, p, act, x, std), fx["glog_64"]) <= 1e-12, path
