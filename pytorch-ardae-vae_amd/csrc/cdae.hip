@@ -1,5 +1,5 @@
-// Conditional AR-DAE update on gfx950: forward, score pass, DAE loss, double backward and weight gradients,
-// orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
+// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1) and unconditional (kind 2 / 3): forward, score pass, DAE loss,
+// double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
 //
 // Maths: SURVEY.md Appendix A (closed form of models/graddae/mlp.py:400-444 under autograd), notation below.
 //   rows i=1..N (N = B*S), image b(i) = i / S
@@ -17,6 +17,13 @@
 //                phat_L = pbar_L + (qhat_1 W1a) (.) s(a_L); phat_{l-1} = pbar_{l-1} + (phat_l A_l) (.) s(a_{l-1})
 //                ctx branch: Qsum_b = sum_{i in b} qhat_1[i]  (reduce over S BEFORE the ctx chain), chat_L = (Qsum W1c) (.) s(c_L) ...
 //   weight gradients (one batched launch): see cdae_wgrads().
+//   res kinds (1 / 3: direct score, g = fc(h_L) + d_f): no score pass and no forward-mode chain, one ordinary backward from gbar.
+//
+// The unconditional kinds (models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167) are the special case without the two encoders:
+// the energy MLP reads the input itself, a_L := xbar, so W1a [h, h] becomes W1x [h, z] and the per-image bias [W1c c_L + d_1](b) the
+// plain d_1.  Every line above that names A_l, C_l, a_l (l < L), c_l, r_l, tau_l, pbar_l, phat_l or Qsum drops out:
+//   g = e_1 W1x;  eb_1 = gbar W1x^T;  W1x's gradient = e_1 (x) gbar + qhat_1 (x) xbar.
+// In the code: `cond` marks what exists for kinds 0 / 1 only, `grad` what the energy kinds (0 / 2) add to the res kinds.
 #include <vector>
 
 #include "ardae_hip.h"
@@ -29,37 +36,45 @@ namespace {
 
 struct CdaeLayout {
   int kind, z, c, h, L, act;
-  std::vector<Lin> ctx, inp, neg;   // ctx/inp: L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae)
+  bool cond, grad;
+  std::vector<Lin> ctx, inp, neg;   // ctx/inp (cond): L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae / main)
   size_t total = 0;
-  int out_dim() const { return kind == 0 ? 1 : z; }
+  // W1 = neg[0] is [W1a | W1c | w1s] (cond) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then the sigma column
+  int k1() const { return cond ? h : z; }
+  int sigma_col() const { return cond ? 2 * h : z; }
 
-  explicit CdaeLayout(const ardae_cdae_desc& d) : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act) {
+  explicit CdaeLayout(const ardae_cdae_desc& d)
+      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(d.kind < 2), grad(d.kind == 0 || d.kind == 2) {
     size_t off = 0;
     auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
-    for (int l = 0; l < L; ++l) add(ctx, h, l == 0 ? c : h);
-    for (int l = 0; l < L; ++l) add(inp, h, l == 0 ? z : h);
-    for (int l = 0; l < L; ++l) add(neg, h, l == 0 ? 2 * h + 1 : h);
-    add(neg, out_dim(), h);
+    if (cond) {
+      for (int l = 0; l < L; ++l) add(ctx, h, l == 0 ? c : h);
+      for (int l = 0; l < L; ++l) add(inp, h, l == 0 ? z : h);
+    }
+    for (int l = 0; l < L; ++l) add(neg, h, l == 0 ? sigma_col() + 1 : h);
+    add(neg, grad ? 1 : z, h);
     total = off;
   }
 };
 
 // offsets into the packed-weight buffer
 struct PackedLayout {
-  std::vector<size_t> ctx_f, ctx_b, inp_f, inp_b, neg_f, neg_b;   // neg_*[0] unused (W1 is split below)
-  size_t w1a_f, w1a_b, w1c_f, w1c_b, w1s;
-  size_t fc_f, fc_b;   // res kind only (dae.fc [z,h])
+  std::vector<size_t> ctx_f, ctx_b, inp_f, inp_b, neg_f, neg_b;   // ctx / inp: cond only; neg_*[0] unused (W1 is split below)
+  size_t w1_f, w1_b, w1c_f, w1c_b, w1s;                           // w1: W1's N-row panel (W1a | W1x); w1c: cond only
+  size_t fc_f, fc_b;   // res kinds only (dae.fc / main.fc [z,h])
   PackedLayout(const CdaeLayout& P, PackList& pl) {
     const size_t L = P.L;
-    ctx_f.resize(L); ctx_b.resize(L); inp_f.resize(L); inp_b.resize(L); neg_f.assign(L, 0); neg_b.assign(L, 0);
-    for (size_t l = 0; l < L; ++l) { pl.pair(P.ctx[l], ctx_f[l], ctx_b[l]); pl.pair(P.inp[l], inp_f[l], inp_b[l]); }
-    const Lin& W1 = P.neg[0];                        // [h, 2h + 1] = [W1a | W1c | w1s]
-    pl.pair(W1, w1a_f, w1a_b, 0, P.h);
-    pl.pair(W1, w1c_f, w1c_b, P.h, P.h);
+    for (auto* v : {&ctx_f, &ctx_b, &inp_f, &inp_b, &neg_f, &neg_b}) v->assign(L, 0);
+    if (P.cond)
+      for (size_t l = 0; l < L; ++l) { pl.pair(P.ctx[l], ctx_f[l], ctx_b[l]); pl.pair(P.inp[l], inp_f[l], inp_b[l]); }
+    const Lin& W1 = P.neg[0];
+    pl.pair(W1, w1_f, w1_b, 0, P.k1());
+    w1c_f = w1c_b = 0;
+    if (P.cond) pl.pair(W1, w1c_f, w1c_b, P.h, P.h);
     w1s = pl.take(P.h);                              // the sigma column, gathered by cdae_pack_impl
     for (size_t l = 1; l < L; ++l) pl.pair(P.neg[l], neg_f[l], neg_b[l]);
     fc_f = fc_b = 0;
-    if (P.kind == 1) pl.pair(P.neg[L], fc_f, fc_b);
+    if (!P.grad) pl.pair(P.neg[L], fc_f, fc_b);
   }
   explicit PackedLayout(const CdaeLayout& P, PackList&& sizing = PackList()) : PackedLayout(P, sizing) {}   // offsets only
 };
@@ -84,26 +99,43 @@ struct CdaeWs {
   int ltiles, ctiles;
 };
 
+// The conditional kinds take every buffer whichever of the two reads it (kind 1 leaves e, r, tau, tau', pbar and cs_taup unused); the
+// unconditional kinds take what they read, so hh[1] is the arena's first piece (the fused front end of dae_perturb.hip fills it).
 void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, CdaeWs& W) {
   const int N = B * S, h = P.h, L = P.L, z = P.z;
   const size_t Bh = (size_t)B * h, Nh = (size_t)N * h;
+  const bool cond = P.cond, score = P.cond || P.grad;
   for (auto* v : {&W.cL, &W.a, &W.hh, &W.e, &W.r, &W.tau, &W.taup, &W.pbar, &W.qbar, &W.chat}) v->assign(L + 1, nullptr);
-  for (int l = 1; l <= L; ++l) W.cL[l] = ws.take(Bh);
-  W.cb = ws.take(Bh);
-  for (int l = 1; l <= L; ++l) { W.a[l] = ws.take(Nh); W.hh[l] = ws.take(Nh); W.e[l] = ws.take(Nh); W.r[l] = ws.take(Nh); }
+  W.cb = W.chain_cnt = W.Qsum = W.cs_taup = nullptr;
+  if (cond) {
+    for (int l = 1; l <= L; ++l) W.cL[l] = ws.take(Bh);
+    W.cb = ws.take(Bh);
+  }
+  for (int l = 1; l <= L; ++l) {
+    if (cond) W.a[l] = ws.take(Nh);
+    W.hh[l] = ws.take(Nh);
+    if (score) W.e[l] = ws.take(Nh);
+    if (cond) W.r[l] = ws.take(Nh);
+  }
   if (need_grads)
-    for (int l = 1; l <= L; ++l) { W.tau[l] = ws.take(Nh); W.taup[l] = ws.take(Nh); W.pbar[l] = ws.take(Nh); W.qbar[l] = ws.take(Nh); }
+    for (int l = 1; l <= L; ++l) {
+      if (cond) W.tau[l] = ws.take(Nh);
+      if (score) W.taup[l] = ws.take(Nh);
+      if (cond) W.pbar[l] = ws.take(Nh);
+      W.qbar[l] = ws.take(Nh);
+    }
   W.gbar = ws.take((size_t)N * z);
   W.gbuf = ws.take((size_t)N * z);
   W.ltiles = linear_row_tiles(N, z) * linear_col_panels(N, z);
   W.tile_loss = ws.take(W.ltiles);
-  W.chain_cnt = ws.take((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));   // row-block counters of the per-image chain launch (score pass)
-  W.Qsum = W.cs_taup = nullptr;
+  if (cond) W.chain_cnt = ws.take((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));   // row-block counters of the per-image chain launch (score pass)
   W.ctiles = linear_row_tiles(N, h);
   if (!need_grads) return;
-  W.Qsum = ws.take(Bh);
-  for (int l = 1; l <= L; ++l) W.chat[l] = ws.take(Bh);
-  W.cs_taup = ws.take((size_t)W.ctiles * h);                                            // colsum of tau'_L
+  if (cond) {
+    W.Qsum = ws.take(Bh);
+    for (int l = 1; l <= L; ++l) W.chat[l] = ws.take(Bh);
+  }
+  if (score) W.cs_taup = ws.take((size_t)W.ctiles * h);                                           // colsum of tau'_L
 }
 
 // every weight-gradient problem of the update (one batched launch), with its scratch taken from ws
@@ -111,30 +143,30 @@ void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, Cd
 void cdae_wgrads(const CdaeLayout& P, const CdaeWs& W, const float* xbar, const float* sigma, const float* ctx, int B, int S, WgradList& wl, Bump& ws) {
   const int N = B * S, h = P.h, L = P.L, z = P.z;
   const std::vector<float*>&a = W.a, &hh = W.hh, &e = W.e, &r = W.r, &tau = W.tau, &taup = W.taup, &qhat = W.qbar, &phat = W.pbar;
-  const int ld1 = 2 * h + 1;
+  const int ld1 = P.neg[0].in;
   const size_t gW1 = P.neg[0].w;
-  if (P.kind == 0) {
+  // One N-row layer's weight [h, I] and bias.  grad kinds: s (x) t of the score pass + ghat (x) x of the backward; res kinds: the second term
+  // alone; the bias gradient is ghat's column sums.  first: W1's N-row panel, which also yields w1s = sum_i sigma_i ghat[i]
+  auto push = [&](const Lin& lin, int I, const float* s, const float* t, const float* ghat, const float* x, bool first) {
+    const float* rs = first ? sigma : nullptr;
+    float* out_rs = first ? wl.g(gW1 + P.sigma_col()) : nullptr;
+    const int ld = first ? ld1 : I, ld_rs = first ? ld1 : 0;
+    if (P.grad) wl.push2(N, h, I, s, t, I, ghat, x, I, 1, rs, wl.g(lin.w), ld, wl.g(lin.b), out_rs, ld_rs);
+    else wl.push2(N, h, I, ghat, x, I, nullptr, nullptr, 0, 0, rs, wl.g(lin.w), ld, wl.g(lin.b), out_rs, ld_rs);
+  };
+  if (P.cond)
     for (int l = 1; l <= L; ++l)   // inp A_l: r_l (x) tau_{l-1}  +  phat_l (x) a_{l-1}   (tau_0 = gbar, a_0 = xbar)
-      wl.push2(N, h, P.inp[l - 1].in, r[l], l == 1 ? W.gbar : tau[l - 1], l == 1 ? z : h, phat[l], l == 1 ? xbar : a[l - 1], l == 1 ? z : h, 1,
-               nullptr, wl.g(P.inp[l - 1].w), P.inp[l - 1].in, wl.g(P.inp[l - 1].b), nullptr, 0);
-    wl.push2(N, h, h, e[1], tau[L], h, qhat[1], a[L], h, 1, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + 2 * h), ld1);        // W1a, d_1, w1s
-    wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + h), ld1, nullptr, nullptr, 0);                 // W1c
-    for (int l = 2; l <= L; ++l)   // W_l: e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}
-      wl.push2(N, h, h, e[l], taup[l - 1], h, qhat[l], hh[l - 1], h, 1, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
-  } else {
-    for (int l = 1; l <= L; ++l)
-      wl.push2(N, h, P.inp[l - 1].in, phat[l], l == 1 ? xbar : a[l - 1], l == 1 ? z : h, nullptr, nullptr, 0, 0, nullptr,
-               wl.g(P.inp[l - 1].w), P.inp[l - 1].in, wl.g(P.inp[l - 1].b), nullptr, 0);
-    wl.push2(N, h, h, qhat[1], a[L], h, nullptr, nullptr, 0, 0, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + 2 * h), ld1);
-    wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + h), ld1, nullptr, nullptr, 0);
-    for (int l = 2; l <= L; ++l)
-      wl.push2(N, h, h, qhat[l], hh[l - 1], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
-    wl.push2(N, z, h, W.gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[L].w), h, wl.g(P.neg[L].b), nullptr, 0);   // dae.fc
-  }
-  for (int l = 1; l <= L; ++l)     // ctx C_l: chat_l (x) c_{l-1}
-    wl.push2(B, h, P.ctx[l - 1].in, W.chat[l], l == 1 ? ctx : W.cL[l - 1], l == 1 ? P.c : h, nullptr, nullptr, 0, 0, nullptr,
-             wl.g(P.ctx[l - 1].w), P.ctx[l - 1].in, wl.g(P.ctx[l - 1].b), nullptr, 0);
-  wl.assign(ws, 3 * L + 1);
+      push(P.inp[l - 1], l == 1 ? z : h, r[l], l == 1 ? W.gbar : tau[l - 1], phat[l], l == 1 ? xbar : a[l - 1], false);
+  push(P.neg[0], P.k1(), e[1], P.cond ? tau[L] : W.gbar, qhat[1], P.cond ? a[L] : xbar, true);                                  // W1a | W1x, d_1, w1s
+  if (P.cond) wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + h), ld1, nullptr, nullptr, 0);   // W1c
+  for (int l = 2; l <= L; ++l)     // W_l: e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}
+    push(P.neg[l - 1], h, e[l], taup[l - 1], qhat[l], hh[l - 1], false);
+  if (!P.grad) wl.push2(N, z, h, W.gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[L].w), h, wl.g(P.neg[L].b), nullptr, 0);   // dae.fc / main.fc
+  if (P.cond)
+    for (int l = 1; l <= L; ++l)   // ctx C_l: chat_l (x) c_{l-1}
+      wl.push2(B, h, P.ctx[l - 1].in, W.chat[l], l == 1 ? ctx : W.cL[l - 1], l == 1 ? P.c : h, nullptr, nullptr, 0, 0, nullptr,
+               wl.g(P.ctx[l - 1].w), P.ctx[l - 1].in, wl.g(P.ctx[l - 1].b), nullptr, 0);
+  wl.assign(ws, P.cond ? 3 * L + 1 : L + 1);   // the split hint: the list's length (res kinds keep their grad sibling's)
 }
 
 // dry run of cdae_carve() and the weight-gradient list on a null arena
@@ -152,7 +184,7 @@ size_t workspace_floats(const CdaeLayout& P, int B, int S, bool need_grads) {
 int cdae_pack_impl(const CdaeLayout& P, const float* params, float* packed, hipStream_t st) {
   PackList pl(params, packed);
   const PackedLayout K(P, pl);
-  ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + 2 * P.h, P.neg[0].in, P.h, packed + K.w1s, st));
+  ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + P.sigma_col(), P.neg[0].in, P.h, packed + K.w1s, st));
   return pl.launch(st);
 }
 
@@ -165,16 +197,18 @@ LinArgs lin_args(int act, int M, int Nout, const float* x, int ldx, int K, const
 
 // A run of consecutive N-row layers of one epilogue kind, each reading its predecessor's output: the longest prefixes that
 // qualify go out as ONE launch each (linear_chain.hip: the small-shard regime), the rest layer by layer.
+// one_by_one: no grouping, every layer is a launch of its own (kind 1's backward: moving it onto grouped launches is a change of its own, to be measured).
 struct LayerRun {
   int epi;
   hipStream_t st;
+  bool one_by_one;
   std::vector<LinArgs> v;
-  LayerRun(int epi_, hipStream_t st_) : epi(epi_), st(st_) {}
-  void add(int act, int M, int Nout, const float* x, int ldx, int K, const float* wp, LinArgs a) { v.push_back(lin_args(act, M, Nout, x, ldx, K, wp, a)); }
+  LayerRun(int epi_, hipStream_t st_, bool one_by_one_ = false) : epi(epi_), st(st_), one_by_one(one_by_one_) {}
+  void add(const LinArgs& a) { v.push_back(a); }
   int flush() {
     size_t i = 0;
     while (i < v.size()) {
-      size_t n = v.size() - i;
+      size_t n = one_by_one ? 1 : v.size() - i;
       while (n >= 2 && !linear_chain_eligible(v.data() + i, (int)n, epi)) --n;
       if (n >= 2) {
         ARDAE_TRY(launch_linear_chain(v.data() + i, (int)n, epi, st));
@@ -182,7 +216,7 @@ struct LayerRun {
         continue;
       }
       // many tiles per workgroup: the same run layer-major in the weight-stationary kernel (one launch, the slab loaded once per layer)
-      size_t m = std::min<size_t>(v.size() - i, 6);
+      size_t m = one_by_one ? 1 : std::min<size_t>(v.size() - i, 6);
       while (m >= 2 && !linear_wide_layers_eligible(v.data() + i, (int)m, epi)) --m;
       if (m >= 2) {
         ARDAE_TRY(launch_linear_wide_layers(v.data() + i, (int)m, epi, st));
@@ -197,17 +231,20 @@ struct LayerRun {
   }
 };
 
+// first_ready: a fused front end has written the first N-row layer's output where the carve puts it (a_1 when cond, else h_1)
 int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma,
               const float* eps, const float* ctx, int B, int S, float* workspace, size_t ws_floats, float* loss, float* grads,
-              float* score_out, bool need_grads, hipStream_t st, bool a1_ready = false) {
+              float* score_out, bool need_grads, hipStream_t st, bool first_ready = false) {
   ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(params && packed && xbar && sigma && ctx && workspace, "cdae: null pointer argument");
+  const CdaeLayout P(*d);
+  const bool cond = P.cond, grad = P.grad;
+  ARDAE_CHECK_ARG(cond || ctx == nullptr, "cdae: kinds 2 / 3 take no context: ctx must be NULL");
+  ARDAE_CHECK_ARG(params && packed && xbar && sigma && (ctx || !cond) && workspace, "cdae: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S < (int64_t)1 << 30, "cdae: bad batch (B=%d, S=%d)", B, S);
   ARDAE_CHECK_ARG(!need_grads || (eps && loss && grads), "cdae: loss/grads/eps must be given");
   ARDAE_CHECK_ARG(need_grads || score_out, "cdae: score_out is NULL");
-  const CdaeLayout P(*d);
   const PackedLayout K(P);
-  const int N = B * S, h = P.h, L = P.L, z = P.z, act = P.act;
+  const int N = B * S, h = P.h, L = P.L, z = P.z, act = P.act, k1 = P.k1();
   // the whole arena up front: the buffers, then (need_grads) the weight-gradient list with its scratch
   Bump ws(workspace, ws_floats);
   CdaeWs W;
@@ -216,17 +253,43 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   if (need_grads) cdae_wgrads(P, W, xbar, sigma, ctx, B, S, wl, ws);
   ARDAE_CHECK_ARG(ws.ok, "cdae: workspace too small (%zu < %zu floats)", ws_floats, ws.off);
   const std::vector<float*>&cL = W.cL, &a = W.a, &hh = W.hh, &e = W.e, &r = W.r, &tau = W.tau, &taup = W.taup, &pbar = W.pbar, &qbar = W.qbar, &chat = W.chat;
-  float *cb = W.cb, *gbar = W.gbar, *gbuf = W.gbuf, *tile_loss = W.tile_loss, *chain_cnt = W.chain_cnt, *Qsum = W.Qsum, *cs_taup = W.cs_taup;
-  const int ltiles = W.ltiles, ctiles = W.ctiles;
-  float* g = score_out ? score_out : gbuf;
+  float *cb = W.cb, *gbar = W.gbar, *Qsum = W.Qsum, *cs_taup = W.cs_taup;
+  float* g = score_out ? score_out : W.gbuf;
+  const float* x1 = cond ? a[L] : xbar;        // the energy MLP's input rows [N, k1]
+  const float* wfc = params + P.neg[L].w;      // grad kinds: w [1,h]
 
-  const float* W1s = packed + K.w1s;
-  // ------------------------------------------------------------------ forward: ctx (B rows, once per image) and inp (N rows)
+  // ------------------------------------------------------------------ the layers of the forward and of the score pass
   auto ctx_layer = [&](int l) { LinArgs A{}; A.bias = params + P.ctx[l - 1].b; A.Y = cL[l]; A.ldY = h;
                                 return lin_args(act, B, h, l == 1 ? ctx : cL[l - 1], l == 1 ? P.c : h, P.ctx[l - 1].in, packed + K.ctx_f[l - 1], A); };
   auto inp_layer = [&](int l) { LinArgs A{}; A.bias = params + P.inp[l - 1].b; A.Y = a[l]; A.ldY = h;
                                 return lin_args(act, N, h, l == 1 ? xbar : a[l - 1], l == 1 ? z : h, P.inp[l - 1].in, packed + K.inp_f[l - 1], A); };
-  const float* wfc0 = params + P.neg[L].w;
+  auto ctx_bias = [&]() {  // per-image bias of the first energy layer: cb = W1c c_L + d_1
+    LinArgs A{}; A.bias = params + P.neg[0].b; A.Y = cb; A.ldY = h;
+    return lin_args(ACT_NONE, B, h, cL[L], h, h, packed + K.w1c_f, A);
+  };
+  auto energy_layer = [&](int l) {
+    LinArgs A{}; A.Y = hh[l]; A.ldY = h;
+    if (l == 1) { A.rowscale = sigma; A.rowscale_w = packed + K.w1s; }
+    if (l == 1 && cond) { A.rowbias = cb; A.rowbias_ld = h; A.rows_per_group = S; } else A.bias = params + P.neg[l - 1].b;
+    if (grad && l == L) { A.Y2 = e[L]; A.ldY2 = h; A.R = wfc; }   // e_L = -w (.) s(h_L)
+    return l == 1 ? lin_args(act, N, h, x1, k1, k1, packed + K.w1_f, A) : lin_args(act, N, h, hh[l - 1], h, h, packed + K.neg_f[l - 1], A);
+  };
+  auto e_layer = [&](int l) {   // e_{l-1} from e_l, l = L..2
+    LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = e[l - 1]; A.ldY = h;
+    return lin_args(act, N, h, e[l], h, h, packed + K.neg_b[l - 1], A);
+  };
+  auto r_layer = [&](int l) {   // r_{l-1} from r_l, l = L+1..2, with r_{L+1} W := e_1 W1a
+    LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = r[l - 1]; A.ldY = h;
+    return l > L ? lin_args(act, N, h, e[1], h, h, packed + K.w1_b, A) : lin_args(act, N, h, r[l], h, h, packed + K.inp_b[l - 1], A);
+  };
+  auto g_layer = [&](LinArgs A) {   // the score g [N, z]: the last link of the score pass (r_1 A_1 | e_1 W1x), or fc(h_L) of the res kinds
+    A.Y = g; A.ldY = z;
+    if (grad) return lin_args(ACT_NONE, N, z, cond ? r[1] : e[1], h, h, packed + (cond ? K.inp_b[0] : K.w1_b), A);
+    A.bias = params + P.neg[L].b;
+    return lin_args(ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A);
+  };
+
+  // ------------------------------------------------------------------ forward: ctx (B rows, once per image), inp and energy (N rows)
   if (!need_grads && P.kind == 0 && N == B && linear_small_eligible(inp_layer(1), EPI_ACT)) {
     // The sigma = 0 score pass of the VAE update (glogprob on B rows, models/graddae/mlp.py:446-483): 4 L + 2 per-image problems, every one
     // a link of a dependent chain - ONE launch walks them level by level (linear_small_chain_kernel): [ctx_l | inp_l] l = 1..L, the
@@ -235,364 +298,114 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     int level = 0;
     auto add = [&](const LinArgs& A, int epi, int lev) { pr.push_back(A); ep.push_back(epi); lv.push_back(lev); };
     for (int l = 1; l <= L; ++l, ++level) { add(ctx_layer(l), EPI_ACT, level); add(inp_layer(l), EPI_ACT, level); }
-    { LinArgs A{}; A.bias = params + P.neg[0].b; A.Y = cb; A.ldY = h; add(lin_args(ACT_NONE, B, h, cL[L], h, h, packed + K.w1c_f, A), EPI_ACT, level++); }
-    for (int l = 1; l <= L; ++l) {
-      LinArgs A{}; A.Y = hh[l]; A.ldY = h;
-      if (l == 1) { A.rowbias = cb; A.rowbias_ld = h; A.rows_per_group = S; A.rowscale = sigma; A.rowscale_w = W1s; } else A.bias = params + P.neg[l - 1].b;
-      if (l == L) { A.Y2 = e[L]; A.ldY2 = h; A.R = wfc0; }
-      add(lin_args(act, N, h, l == 1 ? a[L] : hh[l - 1], h, h, l == 1 ? packed + K.w1a_f : packed + K.neg_f[l - 1], A), EPI_ACT, level++);
-    }
-    for (int l = L; l >= 2; --l) { LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = e[l - 1]; A.ldY = h; add(lin_args(act, N, h, e[l], h, h, packed + K.neg_b[l - 1], A), EPI_DACT, level++); }
-    { LinArgs A{}; A.S = a[L]; A.ldS = h; A.Y = r[L]; A.ldY = h; add(lin_args(act, N, h, e[1], h, h, packed + K.w1a_b, A), EPI_DACT, level++); }
-    for (int l = L; l >= 2; --l) { LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = r[l - 1]; A.ldY = h; add(lin_args(act, N, h, r[l], h, h, packed + K.inp_b[l - 1], A), EPI_DACT, level++); }
-    { LinArgs A{}; A.Y = g; A.ldY = z; add(lin_args(ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A), EPI_ACT, level++); }
-    return launch_linear_small_chain(pr.data(), ep.data(), lv.data(), (int)pr.size(), chain_cnt, st);
+    add(ctx_bias(), EPI_ACT, level++);
+    for (int l = 1; l <= L; ++l) add(energy_layer(l), EPI_ACT, level++);
+    for (int l = L; l >= 2; --l) add(e_layer(l), EPI_DACT, level++);
+    for (int l = L + 1; l >= 2; --l) add(r_layer(l), EPI_DACT, level++);
+    add(g_layer(LinArgs{}), EPI_ACT, level++);
+    return launch_linear_small_chain(pr.data(), ep.data(), lv.data(), (int)pr.size(), W.chain_cnt, st);
   }
-  const bool few_rows = !a1_ready && linear_small_eligible(inp_layer(1), EPI_ACT);
-  auto ctx_bias = [&]() {  // per-image bias of the first energy layer: cb = W1c c_L + d_1
-    LinArgs A{}; A.bias = params + P.neg[0].b; A.Y = cb; A.ldY = h;
-    return lin1(EPI_ACT, ACT_NONE, B, h, cL[L], h, h, packed + K.w1c_f, A, st);
-  };
-  LayerRun run(EPI_ACT, st);      // the forward N-row layers: A_1 (2) .. A_L, then W_1 .. W_L
-  if (few_rows) {
-    // few rows: the two encoders are independent chains of per-image launches - level l of both in ONE launch
-    for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear_pair(ctx_layer(l), inp_layer(l), EPI_ACT, st));
-    ARDAE_TRY(ctx_bias());
-  } else {
-    // the whole per-image branch FIRST (context encoder, then the bias it contributes to the first energy layer): the N-row forward
-    // layers of both networks then form ONE run (round 4: one multi-layer launch instead of two with a per-image launch between them)
-    for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear(ctx_layer(l), EPI_ACT, st));
-    ARDAE_TRY(ctx_bias());
-    for (int l = a1_ready ? 2 : 1; l <= L; ++l) run.v.push_back(inp_layer(l));   // a1_ready: the perturbation kernel has written a_1
-  }
-  const float* wfc = params + P.neg[L].w;   // grad kind: w [1,h]
   {
-    for (int l = 1; l <= L; ++l) {
-      LinArgs A{}; A.Y = hh[l]; A.ldY = h;
-      if (l == 1) {
-        A.rowbias = cb; A.rowbias_ld = h; A.rows_per_group = S; A.rowscale = sigma; A.rowscale_w = W1s;
-      } else {
-        A.bias = params + P.neg[l - 1].b;
-      }
-      if (P.kind == 0 && l == L) { A.Y2 = e[L]; A.ldY2 = h; A.R = wfc; }   // e_L = -w (.) s(h_L)
-      run.add(act, N, h, l == 1 ? a[L] : hh[l - 1], h, h, l == 1 ? packed + K.w1a_f : packed + K.neg_f[l - 1], A);
+    LayerRun run(EPI_ACT, st);      // the forward N-row layers: A_1 (2) .. A_L, then W_1 (2) .. W_L
+    if (cond && !first_ready && linear_small_eligible(inp_layer(1), EPI_ACT)) {
+      // few rows: the two encoders are independent chains of per-image launches - level l of both in ONE launch
+      for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear_pair(ctx_layer(l), inp_layer(l), EPI_ACT, st));
+      ARDAE_TRY(launch_linear(ctx_bias(), EPI_ACT, st));
+    } else if (cond) {
+      // the whole per-image branch FIRST (context encoder, then the bias it contributes to the first energy layer): the N-row forward
+      // layers of both networks then form ONE run (round 4: one multi-layer launch instead of two with a per-image launch between them)
+      for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear(ctx_layer(l), EPI_ACT, st));
+      ARDAE_TRY(launch_linear(ctx_bias(), EPI_ACT, st));
+      for (int l = first_ready ? 2 : 1; l <= L; ++l) run.add(inp_layer(l));
     }
+    for (int l = !cond && first_ready ? 2 : 1; l <= L; ++l) run.add(energy_layer(l));
     ARDAE_TRY(run.flush());
   }
-  const float inv_nz = 1.0f / ((float)N * (float)z);
-  if (P.kind == 0) {
-    // ---------------------------------------------------------------- score pass (input-gradient of the energy)
-    {
-      LayerRun run(EPI_DACT, st);
-      for (int l = L; l >= 2; --l) {
-        LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = e[l - 1]; A.ldY = h;
-        run.add(act, N, h, e[l], h, h, packed + K.neg_b[l - 1], A);
-      }
-      {
-        LinArgs A{}; A.S = a[L]; A.ldS = h; A.Y = r[L]; A.ldY = h;
-        run.add(act, N, h, e[1], h, h, packed + K.w1a_b, A);
-      }
-      for (int l = L; l >= 2; --l) {
-        LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = r[l - 1]; A.ldY = h;
-        run.add(act, N, h, r[l], h, h, packed + K.inp_b[l - 1], A);
-      }
-      ARDAE_TRY(run.flush());
-    }
-    if (!need_grads) {   // glogprob: g = r_1 A_1
-      LinArgs A{}; A.Y = g; A.ldY = z;
-      return lin1(EPI_ACT, ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A, st);
-    }
-    LinArgs A{}; A.sigma = sigma; A.eps = eps; A.ldeps = z; A.scale = inv_nz; A.Y = g; A.ldY = z; A.Y2 = gbar; A.ldY2 = z;
-    A.tile_loss = tile_loss;
-    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, r[1], h, h, packed + K.inp_b[0], A, st));
-  } else {
-    if (!need_grads) {
-      LinArgs A{}; A.bias = params + P.neg[L].b; A.Y = g; A.ldY = z;
-      return lin1(EPI_ACT, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st);
-    }
-    LinArgs A{}; A.bias = params + P.neg[L].b; A.sigma = sigma; A.eps = eps; A.ldeps = z; A.scale = inv_nz; A.Y = g; A.ldY = z;
-    A.Y2 = gbar; A.ldY2 = z; A.tile_loss = tile_loss;
-    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st));
+  if (grad) {
+    // ------------------------------------------------------------------ score pass (input-gradient of the energy)
+    LayerRun run(EPI_DACT, st);
+    for (int l = L; l >= 2; --l) run.add(e_layer(l));
+    if (cond) for (int l = L + 1; l >= 2; --l) run.add(r_layer(l));
+    ARDAE_TRY(run.flush());
   }
-  ARDAE_TRY(launch_sum_scale(tile_loss, ltiles, inv_nz, loss, st));
+  if (!need_grads) return launch_linear(g_layer(LinArgs{}), EPI_ACT, st);   // glogprob
+  const float inv_nz = 1.0f / ((float)N * (float)z);
+  {
+    LinArgs A{}; A.sigma = sigma; A.eps = eps; A.ldeps = z; A.scale = inv_nz; A.Y2 = gbar; A.ldY2 = z; A.tile_loss = W.tile_loss;
+    ARDAE_TRY(launch_linear(g_layer(A), EPI_DAE_LOSS, st));
+  }
+  ARDAE_TRY(launch_sum_scale(W.tile_loss, W.ltiles, inv_nz, loss, st));
 
   // -------------------------------------------------------------------- backward
   const std::vector<float*>&qhat = qbar, &phat = pbar;   // in-place: qhat_l overwrites qbar_l, phat_l overwrites pbar_l
-  if (P.kind == 0) {
+  if (grad) {
     // forward-mode chain through the score pass
-    {
-      LayerRun run(EPI_CHAIN, st);
+    LayerRun run(EPI_CHAIN, st);
+    if (cond)
       for (int l = 1; l <= L; ++l) {
         LinArgs A{}; A.S = a[l]; A.ldS = h; A.R = r[l]; A.ldR = h; A.Y = tau[l]; A.ldY = h; A.Y2 = pbar[l]; A.ldY2 = h;
-        if (l == 1) run.add(act, N, h, gbar, z, z, packed + K.inp_f[0], A);
-        else run.add(act, N, h, tau[l - 1], h, h, packed + K.inp_f[l - 1], A);
+        run.add(l == 1 ? lin_args(act, N, h, gbar, z, z, packed + K.inp_f[0], A) : lin_args(act, N, h, tau[l - 1], h, h, packed + K.inp_f[l - 1], A));
       }
-      for (int l = 1; l <= L; ++l) {
-        LinArgs A{}; A.S = hh[l]; A.ldS = h; A.R = e[l]; A.ldR = h; A.Y = taup[l]; A.ldY = h; A.Y2 = qbar[l]; A.ldY2 = h;
-        if (l == L) A.colsum = cs_taup;
-        run.add(act, N, h, l == 1 ? tau[L] : taup[l - 1], h, h, l == 1 ? packed + K.w1a_f : packed + K.neg_f[l - 1], A);
-      }
-      ARDAE_TRY(run.flush());
+    for (int l = 1; l <= L; ++l) {
+      LinArgs A{}; A.S = hh[l]; A.ldS = h; A.R = e[l]; A.ldR = h; A.Y = taup[l]; A.ldY = h; A.Y2 = qbar[l]; A.ldY2 = h;
+      if (l == L) A.colsum = cs_taup;
+      run.add(l == 1 ? lin_args(act, N, h, cond ? tau[L] : gbar, k1, k1, packed + K.w1_f, A) : lin_args(act, N, h, taup[l - 1], h, h, packed + K.neg_f[l - 1], A));
     }
+    ARDAE_TRY(run.flush());
     // wbar = -colsum(tau'_L)  -> grads of neglogprob.fc.weight [1,h]
-    ARDAE_TRY(launch_segment_sum(cs_taup, h, 1, ctiles, h, -1.0f, grads + P.neg[L].w, h, st));
-    // ordinary backward of the energy chain, seeded ONLY by the qbar_l
-    {
-      LayerRun run(EPI_DACT, st);
-      for (int l = L; l >= 2; --l) {
-        LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Q = qbar[l - 1]; A.ldQ = h; A.Y = qhat[l - 1]; A.ldY = h;
-        run.add(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A);
-      }
-      {
-        LinArgs A{}; A.S = a[L]; A.ldS = h; A.Q = pbar[L]; A.ldQ = h; A.Y = phat[L]; A.ldY = h;
-        run.add(act, N, h, qhat[1], h, h, packed + K.w1a_b, A);
-      }
-      for (int l = L; l >= 2; --l) {
-        LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Q = pbar[l - 1]; A.ldQ = h; A.Y = phat[l - 1]; A.ldY = h;
-        run.add(act, N, h, phat[l], h, h, packed + K.inp_b[l - 1], A);
-      }
-      ARDAE_TRY(run.flush());
-    }
+    ARDAE_TRY(launch_segment_sum(cs_taup, h, 1, W.ctiles, h, -1.0f, grads + P.neg[L].w, h, st));
   } else {
-    // direct-score variant: a single ordinary backward from gbar
-    {
-      LinArgs A{}; A.S = hh[L]; A.ldS = h; A.Y = qhat[L]; A.ldY = h;
-      ARDAE_TRY(lin1(EPI_DACT, act, N, h, gbar, z, z, packed + K.fc_b, A, st));
-    }
+    // direct-score variant: the backward starts from gbar
+    LinArgs A{}; A.S = hh[L]; A.ldS = h; A.Y = qhat[L]; A.ldY = h;
+    ARDAE_TRY(lin1(EPI_DACT, act, N, h, gbar, z, z, packed + K.fc_b, A, st));
+  }
+  {
+    // ordinary backward of the energy chain and (cond) the input encoder; the grad kinds seed every layer with its qbar_l / pbar_l
+    LayerRun run(EPI_DACT, st, P.kind == 1);
     for (int l = L; l >= 2; --l) {
       LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = qhat[l - 1]; A.ldY = h;
-      ARDAE_TRY(lin1(EPI_DACT, act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A, st));
+      if (grad) { A.Q = qbar[l - 1]; A.ldQ = h; }
+      run.add(lin_args(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A));
     }
-    {
-      LinArgs A{}; A.S = a[L]; A.ldS = h; A.Y = phat[L]; A.ldY = h;
-      ARDAE_TRY(lin1(EPI_DACT, act, N, h, qhat[1], h, h, packed + K.w1a_b, A, st));
-    }
-    for (int l = L; l >= 2; --l) {
-      LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = phat[l - 1]; A.ldY = h;
-      ARDAE_TRY(lin1(EPI_DACT, act, N, h, phat[l], h, h, packed + K.inp_b[l - 1], A, st));
-    }
+    if (cond)
+      for (int l = L + 1; l >= 2; --l) {   // phat_{l-1} from phat_l, with phat_{L+1} A := qhat_1 W1a
+        LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = phat[l - 1]; A.ldY = h;
+        if (grad) { A.Q = pbar[l - 1]; A.ldQ = h; }
+        run.add(l > L ? lin_args(act, N, h, qhat[1], h, h, packed + K.w1_b, A) : lin_args(act, N, h, phat[l], h, h, packed + K.inp_b[l - 1], A));
+      }
+    ARDAE_TRY(run.flush());
   }
-  // ctx branch: reduce over the S samples of each image first, then B-row back-prop
-  ARDAE_TRY(launch_segment_sum(qhat[1], h, B, S, h, 1.0f, Qsum, h, st));
-  {
-    LinArgs A{}; A.S = cL[L]; A.ldS = h; A.Y = chat[L]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, B, h, Qsum, h, h, packed + K.w1c_b, A, st));
-  }
-  for (int l = L; l >= 2; --l) {
-    LinArgs A{}; A.S = cL[l - 1]; A.ldS = h; A.Y = chat[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, B, h, chat[l], h, h, packed + K.ctx_b[l - 1], A, st));
+  if (cond) {
+    // ctx branch: reduce over the S samples of each image first, then B-row back-prop
+    ARDAE_TRY(launch_segment_sum(qhat[1], h, B, S, h, 1.0f, Qsum, h, st));
+    for (int l = L + 1; l >= 2; --l) {     // chat_{l-1} from chat_l, with chat_{L+1} C := Qsum W1c
+      LinArgs A{}; A.S = cL[l - 1]; A.ldS = h; A.Y = chat[l - 1]; A.ldY = h;
+      ARDAE_TRY(lin1(EPI_DACT, act, B, h, l > L ? Qsum : chat[l], h, h, packed + (l > L ? K.w1c_b : K.ctx_b[l - 1]), A, st));
+    }
   }
 
   // -------------------------------------------------------------------- weight gradients: one batched launch (cdae_wgrads)
   return wl.launch(st);
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------
-// Unconditional AR-DAE (kinds 2 / 3; models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167): the update above with the context
-// branch and the input encoder removed, a_L -> xbar, W1a -> W1x [h, d], [W1c c_L + d_1](b) -> d_1:
-//   energy MLP : h_1 = act(W1x xbar + sigma w1s + d_1), h_l = act(W_l h_{l-1} + d_l), E = w.h_L + d_f
-//   score      : e_L = -w (.) s(h_L); e_{l-1} = (e_l W_l) (.) s(h_{l-1}); g = e_1 W1x
-//   loss       : rho = sigma g + eps; loss = sum rho^2 / (N d); gbar = 2 sigma rho / (N d)
-//   forward-mode chain: eb_1 = gbar W1x^T; tau'_l = eb_l (.) s(h_l); qbar_l = eb_l (.) e_l (.) (1 - s(h_l)); eb_{l+1} = tau'_l W_{l+1}^T
-//   backward   : qhat_L = qbar_L; qhat_{l-1} = qbar_{l-1} + (qhat_l W_l) (.) s(h_{l-1})
-//   gradients  : W1x = e_1 (x) gbar + qhat_1 (x) xbar, w1s = sum_i sigma_i qhat_1[i], d_1 = colsum qhat_1,
-//                W_l = e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}, d_l = colsum qhat_l, w = -colsum tau'_L; d_f: none (left untouched)
-// Kind 3 (direct score, g = fc(h_L)): one ordinary backward from gbar.
-struct DaeLayout {
-  int kind, z, h, L, act;
-  std::vector<Lin> neg;   // L hidden + fc (neglogprob.* | main.*); neg[0] is [h, d + 1] = [W1x | w1s]
-  size_t total = 0;
-  bool grad() const { return kind == 2; }
-  explicit DaeLayout(const ardae_cdae_desc& d) : kind(d.kind), z(d.input_dim), h(d.h_dim), L(d.n_layers), act(d.act) {
-    size_t off = 0;
-    for (int l = 0; l < L; ++l) neg.push_back(next_lin(off, h, l == 0 ? z + 1 : h));
-    neg.push_back(next_lin(off, grad() ? 1 : z, h));
-    total = off;
-  }
-};
-
-struct DaePacked {
-  std::vector<size_t> neg_f, neg_b;   // [0] unused (W1 is split below)
-  size_t w1x_f, w1x_b, w1s, fc_f, fc_b;
-  DaePacked(const DaeLayout& P, PackList& pl) {
-    neg_f.assign(P.L, 0); neg_b.assign(P.L, 0);
-    pl.pair(P.neg[0], w1x_f, w1x_b, 0, P.z);
-    w1s = pl.take(P.h);                              // the sigma column, gathered by dae_pack_impl
-    for (int l = 1; l < P.L; ++l) pl.pair(P.neg[l], neg_f[l], neg_b[l]);
-    fc_f = fc_b = 0;
-    if (!P.grad()) pl.pair(P.neg[P.L], fc_f, fc_b);
-  }
-  explicit DaePacked(const DaeLayout& P, PackList&& sizing = PackList()) : DaePacked(P, sizing) {}   // offsets only
-};
-
-struct DaeWs {
-  std::vector<float*> hh, e, taup, qbar;   // [l], l = 1..L, [N, h] each (kind 3: hh and qbar only)
-  float *gbar, *gbuf, *tile_loss, *cs_taup;
-  int ltiles, ctiles;
-};
-
-void dae_carve(const DaeLayout& P, Bump& ws, int N, bool need_grads, DaeWs& W) {
-  const int h = P.h, L = P.L, z = P.z;
-  const size_t Nh = (size_t)N * h;
-  for (auto* v : {&W.hh, &W.e, &W.taup, &W.qbar}) v->assign(L + 1, nullptr);
-  for (int l = 1; l <= L; ++l) { W.hh[l] = ws.take(Nh); if (P.grad()) W.e[l] = ws.take(Nh); }
-  if (need_grads)
-    for (int l = 1; l <= L; ++l) { if (P.grad()) W.taup[l] = ws.take(Nh); W.qbar[l] = ws.take(Nh); }
-  W.gbar = ws.take((size_t)N * z);
-  W.gbuf = ws.take((size_t)N * z);
-  W.ltiles = linear_row_tiles(N, z) * linear_col_panels(N, z);
-  W.tile_loss = ws.take(W.ltiles);
-  W.ctiles = linear_row_tiles(N, h);
-  W.cs_taup = need_grads && P.grad() ? ws.take((size_t)W.ctiles * h) : nullptr;
-}
-
-void dae_wgrads(const DaeLayout& P, const DaeWs& W, const float* xbar, const float* sigma, int N, WgradList& wl, Bump& ws) {
-  const int h = P.h, L = P.L, z = P.z, ld1 = z + 1;
-  const std::vector<float*>&hh = W.hh, &e = W.e, &taup = W.taup, &qhat = W.qbar;
-  const size_t gW1 = P.neg[0].w;
-  if (P.grad()) {
-    wl.push2(N, h, z, e[1], W.gbar, z, qhat[1], xbar, z, 1, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + z), ld1);   // W1x, d_1, w1s
-    for (int l = 2; l <= L; ++l)
-      wl.push2(N, h, h, e[l], taup[l - 1], h, qhat[l], hh[l - 1], h, 1, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
-  } else {
-    wl.push2(N, h, z, qhat[1], xbar, z, nullptr, nullptr, 0, 0, sigma, wl.g(gW1), ld1, wl.g(P.neg[0].b), wl.g(gW1 + z), ld1);
-    for (int l = 2; l <= L; ++l)
-      wl.push2(N, h, h, qhat[l], hh[l - 1], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[l - 1].w), h, wl.g(P.neg[l - 1].b), nullptr, 0);
-    wl.push2(N, z, h, W.gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[L].w), h, wl.g(P.neg[L].b), nullptr, 0);   // main.fc
-  }
-  wl.assign(ws, L + 1);
-}
-
-size_t dae_workspace_floats(const DaeLayout& P, int N, bool need_grads) {
-  Bump ws;
-  DaeWs W;
-  dae_carve(P, ws, N, need_grads, W);
-  if (need_grads) {
-    WgradList wl(nullptr);
-    dae_wgrads(P, W, nullptr, nullptr, N, wl, ws);
-  }
-  return ws.off;
-}
-
-int dae_pack_impl(const DaeLayout& P, const float* params, float* packed, hipStream_t st) {
-  PackList pl(params, packed);
-  const DaePacked K(P, pl);
-  ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + P.z, P.neg[0].in, P.h, packed + K.w1s, st));
-  return pl.launch(st);
-}
-
-// h1_ready: the fused front end (dae_perturb.hip) has written h_1 into W.hh[1]
-int dae_impl(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma, const float* eps,
-             const float* ctx, int B, int S, float* workspace, size_t ws_floats, float* loss, float* grads, float* score_out, bool need_grads,
-             hipStream_t st, bool h1_ready = false) {
-  ARDAE_CHECK_ARG(ctx == nullptr, "cdae: kinds 2 / 3 take no context: ctx must be NULL");
-  ARDAE_CHECK_ARG(params && packed && xbar && sigma && workspace, "cdae: null pointer argument");
-  ARDAE_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S < (int64_t)1 << 30, "cdae: bad batch (B=%d, S=%d)", B, S);
-  ARDAE_CHECK_ARG(!need_grads || (eps && loss && grads), "cdae: loss/grads/eps must be given");
-  ARDAE_CHECK_ARG(need_grads || score_out, "cdae: score_out is NULL");
-  const DaeLayout P(*d);
-  const DaePacked K(P);
-  const int N = B * S, h = P.h, L = P.L, z = P.z, act = P.act;
-  Bump ws(workspace, ws_floats);
-  DaeWs W;
-  dae_carve(P, ws, N, need_grads, W);
-  WgradList wl(grads);
-  if (need_grads) dae_wgrads(P, W, xbar, sigma, N, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "cdae: workspace too small (%zu < %zu floats)", ws_floats, ws.off);
-  const std::vector<float*>&hh = W.hh, &e = W.e, &taup = W.taup, &qbar = W.qbar;
-  float* g = score_out ? score_out : W.gbuf;
-  const float* wfc = params + P.neg[L].w;   // grad kind: w [1, h]
-  // ------------------------------------------------------------------ forward
-  {
-    LayerRun run(EPI_ACT, st);
-    for (int l = h1_ready ? 2 : 1; l <= L; ++l) {
-      LinArgs A{}; A.Y = hh[l]; A.ldY = h; A.bias = params + P.neg[l - 1].b;
-      if (l == 1) { A.rowscale = sigma; A.rowscale_w = packed + K.w1s; }
-      if (P.grad() && l == L) { A.Y2 = e[L]; A.ldY2 = h; A.R = wfc; }   // e_L = -w (.) s(h_L)
-      if (l == 1) run.add(act, N, h, xbar, z, z, packed + K.w1x_f, A);
-      else run.add(act, N, h, hh[l - 1], h, h, packed + K.neg_f[l - 1], A);
-    }
-    ARDAE_TRY(run.flush());
-  }
-  const float inv_nz = 1.0f / ((float)N * (float)z);
-  LinArgs LA{}; LA.sigma = sigma; LA.eps = eps; LA.ldeps = z; LA.scale = inv_nz; LA.Y = g; LA.ldY = z; LA.Y2 = W.gbar; LA.ldY2 = z;
-  LA.tile_loss = W.tile_loss;
-  if (P.grad()) {
-    // ---------------------------------------------------------------- score pass (input-gradient of the energy)
-    LayerRun run(EPI_DACT, st);
-    for (int l = L; l >= 2; --l) {
-      LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = e[l - 1]; A.ldY = h;
-      run.add(act, N, h, e[l], h, h, packed + K.neg_b[l - 1], A);
-    }
-    ARDAE_TRY(run.flush());
-    if (!need_grads) {   // glogprob: g = e_1 W1x
-      LinArgs A{}; A.Y = g; A.ldY = z;
-      return lin1(EPI_ACT, ACT_NONE, N, z, e[1], h, h, packed + K.w1x_b, A, st);
-    }
-    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, e[1], h, h, packed + K.w1x_b, LA, st));
-  } else {
-    if (!need_grads) {
-      LinArgs A{}; A.bias = params + P.neg[L].b; A.Y = g; A.ldY = z;
-      return lin1(EPI_ACT, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A, st);
-    }
-    LA.bias = params + P.neg[L].b;
-    ARDAE_TRY(lin1(EPI_DAE_LOSS, ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, LA, st));
-  }
-  ARDAE_TRY(launch_sum_scale(W.tile_loss, W.ltiles, inv_nz, loss, st));
-
-  // -------------------------------------------------------------------- backward
-  const std::vector<float*>& qhat = qbar;   // in place
-  if (P.grad()) {
-    {
-      LayerRun run(EPI_CHAIN, st);   // forward-mode chain through the score pass
-      for (int l = 1; l <= L; ++l) {
-        LinArgs A{}; A.S = hh[l]; A.ldS = h; A.R = e[l]; A.ldR = h; A.Y = taup[l]; A.ldY = h; A.Y2 = qbar[l]; A.ldY2 = h;
-        if (l == L) A.colsum = W.cs_taup;
-        if (l == 1) run.add(act, N, h, W.gbar, z, z, packed + K.w1x_f, A);
-        else run.add(act, N, h, taup[l - 1], h, h, packed + K.neg_f[l - 1], A);
-      }
-      ARDAE_TRY(run.flush());
-    }
-    // wbar = -colsum(tau'_L)  -> grads of neglogprob.fc.weight [1, h]
-    ARDAE_TRY(launch_segment_sum(W.cs_taup, h, 1, W.ctiles, h, -1.0f, grads + P.neg[L].w, h, st));
-    LayerRun run(EPI_DACT, st);      // ordinary backward of the energy chain, seeded by the qbar_l
-    for (int l = L; l >= 2; --l) {
-      LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Q = qbar[l - 1]; A.ldQ = h; A.Y = qhat[l - 1]; A.ldY = h;
-      run.add(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A);
-    }
-    ARDAE_TRY(run.flush());
-  } else {
-    {
-      LinArgs A{}; A.S = hh[L]; A.ldS = h; A.Y = qhat[L]; A.ldY = h;
-      ARDAE_TRY(lin1(EPI_DACT, act, N, h, W.gbar, z, z, packed + K.fc_b, A, st));
-    }
-    LayerRun run(EPI_DACT, st);
-    for (int l = L; l >= 2; --l) {
-      LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = qhat[l - 1]; A.ldY = h;
-      run.add(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A);
-    }
-    ARDAE_TRY(run.flush());
-  }
-  return wl.launch(st);
-}
-
-inline bool uncond(const ardae_cdae_desc* d) { return d->kind >= 2; }
-
 }  // namespace
 
-// what dae_perturb.hip needs of the unconditional layout: where W1 / d_1 live, and the workspace slot of h_1
-int dae_front_slots(const ardae_cdae_desc* d, int N, size_t ws_floats, size_t* w1, size_t* b1, size_t* h1_off) {
+// what the fused front end of dae_perturb.hip needs of an unconditional network: where W1 / d_1 live, and the carved h_1 it writes
+int dae_front_slots(const ardae_cdae_desc* d, int N, float* workspace, size_t ws_floats, size_t* w1, size_t* b1, float** h1) {
   ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(uncond(d), "dae_perturb_loss_grads: kind must be 2 or 3");
-  const DaeLayout P(*d);
-  ARDAE_CHECK_ARG(ws_floats >= dae_workspace_floats(P, N, true), "dae_perturb_loss_grads: workspace too small (%zu < %zu floats)", ws_floats,
-                  dae_workspace_floats(P, N, true));
-  *w1 = P.neg[0].w; *b1 = P.neg[0].b; *h1_off = 0;   // dae_carve takes hh[1] first
+  ARDAE_CHECK_ARG(d->kind >= 2, "dae_perturb_loss_grads: kind must be 2 or 3");
+  const CdaeLayout P(*d);
+  const size_t need = workspace_floats(P, N, 1, true);
+  ARDAE_CHECK_ARG(ws_floats >= need, "dae_perturb_loss_grads: workspace too small (%zu < %zu floats)", ws_floats, need);
+  Bump ws(workspace, ws_floats);
+  CdaeWs W;
+  cdae_carve(P, ws, N, 1, true, W);
+  *w1 = P.neg[0].w; *b1 = P.neg[0].b; *h1 = W.hh[1];
   return 0;
 }
 int dae_loss_grads_from_h1(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma, const float* eps,
                            int N, float* workspace, size_t ws_floats, float* loss, float* grads, hipStream_t st) {
-  return dae_impl(d, params, packed, xbar, sigma, eps, nullptr, N, 1, workspace, ws_floats, loss, grads, nullptr, true, st, true);
+  return cdae_impl(d, params, packed, xbar, sigma, eps, nullptr, N, 1, workspace, ws_floats, loss, grads, nullptr, true, st, true);
 }
 
 }  // namespace ardae
@@ -603,39 +416,33 @@ extern "C" {
 
 size_t ardae_cdae_param_floats(const ardae_cdae_desc* d) {
   if (desc_ok(d) != 0) return 0;
-  if (uncond(d)) return DaeLayout(*d).total;
   return CdaeLayout(*d).total;
 }
 size_t ardae_cdae_packed_floats(const ardae_cdae_desc* d) {
   if (desc_ok(d) != 0) return 0;
   PackList pl;
-  if (uncond(d)) DaePacked(DaeLayout(*d), pl);
-  else PackedLayout(CdaeLayout(*d), pl);
+  PackedLayout(CdaeLayout(*d), pl);
   return pl.total();
 }
 size_t ardae_cdae_workspace_floats(const ardae_cdae_desc* d, int B, int S, int need_grads) {
   if (desc_ok(d) != 0 || B <= 0 || S <= 0) return 0;
-  if (uncond(d)) return dae_workspace_floats(DaeLayout(*d), B * S, need_grads != 0);
   return workspace_floats(CdaeLayout(*d), B, S, need_grads != 0);
 }
 int ardae_cdae_pack(const ardae_cdae_desc* d, const float* params, float* packed, void* stream) {
   ARDAE_TRY(desc_ok(d));
   ARDAE_CHECK_ARG(params && packed, "cdae_pack: null pointer");
-  if (uncond(d)) return dae_pack_impl(DaeLayout(*d), params, packed, (hipStream_t)stream);
   return cdae_pack_impl(CdaeLayout(*d), params, packed, (hipStream_t)stream);
 }
 int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar,
                           const float* sigma, const float* eps, const float* ctx, int B, int S, float* workspace,
                           size_t workspace_floats, float* loss, float* grads, float* score_out, void* stream) {
-  ARDAE_TRY(desc_ok(d));
-  if (uncond(d)) return dae_impl(d, params, packed, xbar, sigma, eps, ctx, B, S, workspace, workspace_floats, loss, grads, score_out, true, (hipStream_t)stream);
   return cdae_impl(d, params, packed, xbar, sigma, eps, ctx, B, S, workspace, workspace_floats, loss, grads, score_out, true,
                    (hipStream_t)stream);
 }
 int ardae_cdae_perturb_fused_ok(const ardae_cdae_desc* d, int nz, int nstd) {
-  if (desc_ok(d) != 0 || uncond(d)) return 0;
-  const CdaeLayout P(*d);
-  return nstd == 1 && P.inp[0].in == P.z && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
+  if (desc_ok(d) != 0) return 0;
+  const CdaeLayout P(*d);   // the fused draw + A_1 kernel is the conditional kinds'
+  return P.cond && nstd == 1 && P.inp[0].in == P.z && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
 }
 int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* latent, const float* z0,
                                   const float* ctx, int B, int nz, float std_scale, float delta, uint64_t seed, uint64_t offset_xi,
@@ -658,8 +465,6 @@ int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params,
 }
 int ardae_cdae_score(const ardae_cdae_desc* d, const float* params, const float* packed, const float* x, const float* sigma,
                      const float* ctx, int B, int S, float* workspace, size_t workspace_floats, float* score_out, void* stream) {
-  ARDAE_TRY(desc_ok(d));
-  if (uncond(d)) return dae_impl(d, params, packed, x, sigma, nullptr, ctx, B, S, workspace, workspace_floats, nullptr, nullptr, score_out, false, (hipStream_t)stream);
   return cdae_impl(d, params, packed, x, sigma, nullptr, ctx, B, S, workspace, workspace_floats, nullptr, nullptr, score_out, false,
                    (hipStream_t)stream);
 }

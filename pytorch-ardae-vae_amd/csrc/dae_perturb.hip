@@ -13,7 +13,7 @@
 namespace ardae {
 
 // cdae.hip
-int dae_front_slots(const ardae_cdae_desc* d, int N, size_t ws_floats, size_t* w1, size_t* b1, size_t* h1_off);
+int dae_front_slots(const ardae_cdae_desc* d, int N, float* workspace, size_t ws_floats, size_t* w1, size_t* b1, float** h1);
 int dae_loss_grads_from_h1(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma, const float* eps,
                            int N, float* workspace, size_t ws_floats, float* loss, float* grads, hipStream_t st);
 
@@ -150,13 +150,14 @@ int ardae_dae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, 
   ARDAE_CHECK_ARG(params && packed && x && xbar && sigma && eps_out && workspace && loss && grads, "dae_perturb_loss_grads: null pointer argument");
   ARDAE_CHECK_ARG((first_row & 3) == 0, "dae_perturb_loss_grads: first_row must be a multiple of 4 (one Philox counter = 4 normals)");
   const int N = B * nsigma, h = d->h_dim, z = d->input_dim;
-  size_t w1, b1, h1_off;
-  ARDAE_TRY(dae_front_slots(d, N, workspace_floats, &w1, &b1, &h1_off));
+  size_t w1, b1;
+  float* h1;
+  ARDAE_TRY(dae_front_slots(d, N, workspace, workspace_floats, &w1, &b1, &h1));
   const hipStream_t st = (hipStream_t)stream;
   prof_begin(st, "dae_perturb_fwd_kernel", 2.0 * (double)N * h * (z + 1), 4.0 * ((double)N * h + (double)N * (2 * z + 1) + (double)B * z));
   hipLaunchKernelGGL(dae_perturb_fwd_kernel, dim3((unsigned)ceil_div(N, DP_ROWS)), dim3(256), 0, st, x, N, nsigma, z, delta, seed, offset_sigma,
                      offset_eps, (const StepState*)state, first_row, xbar, sigma, eps_out, params + w1, params + b1, h, d->act,
-                     workspace + h1_off);
+                     h1);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
   return dae_loss_grads_from_h1(d, params, packed, xbar, sigma, eps_out, N, workspace, workspace_floats, loss, grads, st);

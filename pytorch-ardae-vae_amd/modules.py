@@ -142,10 +142,11 @@ GAUSSIAN_DECODERS = ("toy", "auxtoy")                                           
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# conditional AR-DAE
+# AR-DAE score networks: conditional (the cDAE of ivae_ardae.py) and unconditional (notebooks/ardae_toy.ipynb / ardae_fit.ipynb)
 # ---------------------------------------------------------------------------------------------------------------
-class _CdaeLossFn(torch.autograd.Function):
-    """forward = ConditionalARDAE.forward's loss; the double backward runs in the same ABI call, so backward() only scales."""
+class _ArdaeLossFn(torch.autograd.Function):
+    """forward = the loss of ConditionalARDAE.forward / ARDAE.forward (context None, S = 1); the double backward runs in the same ABI
+    call, so backward() only scales."""
 
     @staticmethod
     def forward(ctx, mod, xbar, sigma, eps, context, B, S, *params):
@@ -163,33 +164,46 @@ class _CdaeLossFn(torch.autograd.Function):
         out = []
         for name, p in mod.named_parameters():
             if name in mod._no_grad_names:
-                out.append(None)      # the reference leaves .grad = None here
+                out.append(None)      # the reference leaves .grad = None here (SURVEY App. A.8): the energy's offset does not reach its input-gradient
                 continue
             off, n, shape = mod._offs[name]
             out.append(ctx.grads[off:off + n].view(shape) * gloss)
         return (None,) * 7 + tuple(out)
 
 
-class ConditionalARDAE(FlatParamModule):
-    _kind = None
+class _ScoreNet(FlatParamModule):
+    """What ConditionalARDAE and ARDAE share: the constructor checks, the ardae_cdae_desc and the parameter buffer."""
+    _kind = None                 # "grad" | "res": the leaf classes
     _packed_floats_fn, _pack_fn = "ardae_cdae_packed_floats", "ardae_cdae_pack"
 
+    @staticmethod
+    def _check(noise_type, nonlinearity, also=None):
+        if noise_type != "gaussian":
+            raise NotImplementedError            # uniform / laplace (graddae/mlp.py:143-146,392-393) are not on the path
+        if also:
+            raise NotImplementedError(also)
+        if nonlinearity not in L.ACT or nonlinearity in ("none", None):
+            raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
+
+    def _build_net(self, first_kind, spec, input_dim, context_dim, h_dim, std, num_hidden_layers, nonlinearity, noise_type):
+        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional); its res sibling is the next."""
+        self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
+        self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
+        self._desc = L.CdaeDesc(first_kind if self._kind == "grad" else first_kind + 1, input_dim, context_dim, h_dim, num_hidden_layers, L.ACT[nonlinearity])
+        self._build_params(spec)
+        self._no_grad_names = {"neglogprob.fc.bias"} if self._kind == "grad" else set()
+        self._default_init()
+
+
+class ConditionalARDAE(_ScoreNet):
     def __init__(self, input_dim=2, h_dim=128, context_dim=2, std=0.01, num_hidden_layers=1, nonlinearity="tanh",
                  noise_type="gaussian", enc_input=True, enc_ctx=True, std_method="default"):
         super().__init__()
-        if noise_type != "gaussian":
-            raise NotImplementedError            # reference: graddae/mlp.py:392-393 for unknown types; only gaussian is on the path
-        if not (enc_input and enc_ctx):
-            raise NotImplementedError("enc_input=enc_ctx=True is the only configuration ivae_ardae.py:583-606 constructs")
-        if nonlinearity not in L.ACT or nonlinearity in ("none", None):
-            raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
-        self.input_dim, self.h_dim, self.context_dim, self.std = input_dim, h_dim, context_dim, std
-        self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
-        self.enc_input, self.enc_ctx = enc_input, enc_ctx
-        self._desc = L.CdaeDesc(0 if self._kind == "grad" else 1, input_dim, context_dim, h_dim, num_hidden_layers, L.ACT[nonlinearity])
-        self._build_params(layout.cdae_spec(self._kind, input_dim, context_dim, h_dim, num_hidden_layers))
-        self._no_grad_names = {"neglogprob.fc.bias"} if self._kind == "grad" else set()
-        self._default_init()
+        self._check(noise_type, nonlinearity, None if enc_input and enc_ctx else
+                    "enc_input=enc_ctx=True is the only configuration ivae_ardae.py:583-606 constructs")
+        self.context_dim, self.enc_input, self.enc_ctx = context_dim, enc_input, enc_ctx
+        self._build_net(0, layout.cdae_spec(self._kind, input_dim, context_dim, h_dim, num_hidden_layers), input_dim, context_dim, h_dim, std,
+                        num_hidden_layers, nonlinearity, noise_type)
 
     def _prep(self, input, context, std):
         assert input.dim() == 3      # bsz x ssz x x_dim   (graddae/mlp.py:402)
@@ -213,7 +227,7 @@ class ConditionalARDAE(FlatParamModule):
             eps = rng.normal((B * S, self.input_dim), x.device)
         eps = _f32c(eps).view(B * S, self.input_dim)
         xbar = torch.addcmul(x, s[:, None], eps)         # add_gaussian_noise (graddae/mlp.py:21-23)
-        loss = _CdaeLossFn.apply(self, xbar, s, eps, c, B, S, *self.parameters())
+        loss = _ArdaeLossFn.apply(self, xbar, s, eps, c, B, S, *self.parameters())
         return None, loss
 
     def glogprob(self, input, context, std=None, scale=None):
@@ -234,54 +248,16 @@ class MLPResCARDAE(ConditionalARDAE):
     _kind = "res"
 
 
-# ---------------------------------------------------------------------------------------------------------------
-# unconditional AR-DAE (the score estimator of notebooks/ardae_toy.ipynb / ardae_fit.ipynb)
-# ---------------------------------------------------------------------------------------------------------------
-class _DaeLossFn(torch.autograd.Function):
-    """forward = ARDAE.forward's loss; the double backward runs in the same ABI call, so backward() only scales."""
-
-    @staticmethod
-    def forward(ctx, mod, xbar, sigma, eps, N, *params):
-        d = mod._desc
-        ws = mod._ws(L.query("ardae_cdae_workspace_floats", d, N, 1, 1))
-        loss = torch.empty(1, device=xbar.device)
-        grads = torch.zeros_like(mod._flat)
-        L.call("ardae_cdae_loss_grads", d, mod._flat, mod._packed_weights(), xbar, sigma, eps, None, N, 1, ws, ws.numel(), loss, grads, None)
-        ctx.mod, ctx.grads = mod, grads
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, gloss):
-        mod = ctx.mod
-        out = []
-        for name, p in mod.named_parameters():
-            if name in mod._no_grad_names:
-                out.append(None)      # the reference leaves .grad = None here: the energy's offset does not reach its input-gradient
-                continue
-            off, n, shape = mod._offs[name]
-            out.append(ctx.grads[off:off + n].view(shape) * gloss)
-        return (None,) * 5 + tuple(out)
-
-
-class ARDAE(FlatParamModule):
+class ARDAE(_ScoreNet):
     """models/graddae/mlp.py:118-207 / models/resdae/mlp.py:92-167: the AR-DAE score network on [x_bar | sigma], no context."""
-    _kind = None
-    _packed_floats_fn, _pack_fn = "ardae_cdae_packed_floats", "ardae_cdae_pack"
 
     def __init__(self, input_dim=2, h_dim=1000, std=0.1, num_hidden_layers=1, nonlinearity="tanh", noise_type="gaussian"):
         super().__init__()
-        if noise_type != "gaussian":
-            raise NotImplementedError            # uniform / laplace (graddae/mlp.py:143-146) are not on the path
-        if nonlinearity not in L.ACT or nonlinearity in ("none", None):
-            raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
+        self._check(noise_type, nonlinearity)
         if num_hidden_layers < 1:
             raise NotImplementedError("num_hidden_layers >= 1 (a score network without a hidden layer is linear in [x | sigma])")
-        self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
-        self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
-        self._desc = L.CdaeDesc(2 if self._kind == "grad" else 3, input_dim, 0, h_dim, num_hidden_layers, L.ACT[nonlinearity])
-        self._build_params(layout.dae_spec(self._kind, input_dim, h_dim, num_hidden_layers))
-        self._no_grad_names = {"neglogprob.fc.bias"} if self._kind == "grad" else set()
-        self._default_init()
+        self._build_net(2, layout.dae_spec(self._kind, input_dim, h_dim, num_hidden_layers), input_dim, 0, h_dim, std, num_hidden_layers,
+                        nonlinearity, noise_type)
 
     def _prep(self, input, std):
         self._require_gpu(input, std if torch.is_tensor(std) else None)
@@ -306,7 +282,7 @@ class ARDAE(FlatParamModule):
         eps = _f32c(eps).view(N, self.input_dim)
         xbar = torch.empty_like(x)
         L.call("ardae_dae_perturb", x, s, eps, N, 1, self.input_dim, xbar)      # add_gaussian_noise (graddae/mlp.py:21-23)
-        loss = _DaeLossFn.apply(self, xbar, s, eps, N, *self.parameters())
+        loss = _ArdaeLossFn.apply(self, xbar, s, eps, None, N, 1, *self.parameters())
         return None, loss
 
     def glogprob(self, input, std=None):

@@ -240,6 +240,28 @@ def test_cdae_layout_matches_c_side(kind, args, packed, workspace):
     assert tuple(L.lib().ardae_cdae_workspace_floats(ctypes.byref(d), 4, 8, g) for g in (0, 1)) == workspace
 
 
+# the unconditional kinds (2 / 3): parameter floats, packed floats and workspace floats at (B, S) = (4, 8) without / with gradients, recorded like
+# MODEL_SIZES (these kinds share the layout, workspace and gradient-list code of kinds 0 / 1: what they do NOT take of it is pinned here)
+DAE_SIZES = [("grad", (2, 64, 2), 4481, 10816, (8384, 21120)), ("grad", (2, 64, 3), 8641, 19008, (12480, 33536)),
+             ("grad", (2, 256, 2), 67073, 141568, (32960, 133056)), ("grad", (2, 256, 3), 132865, 272640, (49344, 231872)),
+             ("grad", (32, 64, 2), 6401, 12352, (10304, 24960)), ("grad", (32, 64, 3), 10561, 20544, (14400, 37376)),
+             ("grad", (32, 256, 2), 74753, 147712, (34880, 142656)), ("grad", (32, 256, 3), 140545, 278784, (51264, 241472)),
+             ("res", (2, 64, 2), 4546, 13376, (4288, 13056)), ("res", (2, 64, 3), 8706, 21568, (6336, 21376)),
+             ("res", (2, 256, 2), 67330, 151808, (16576, 100608)), ("res", (2, 256, 3), 133122, 282880, (24768, 183040)),
+             ("res", (32, 64, 2), 8416, 16448, (6208, 18816)), ("res", (32, 64, 3), 12576, 24640, (8256, 27136)),
+             ("res", (32, 256, 2), 82720, 164096, (18496, 117888)), ("res", (32, 256, 3), 148512, 295168, (26688, 200320))]
+
+
+@pytest.mark.parametrize("kind,args,params,packed,workspace", DAE_SIZES, ids=[f"{r[0]}-d{r[1][0]}-h{r[1][1]}-L{r[1][2]}" for r in DAE_SIZES])
+def test_dae_layout_matches_c_side(kind, args, params, packed, workspace):
+    d_in, h, nl = args
+    _, total = layout.offsets(layout.dae_spec(kind, d_in, h, nl))
+    d = L.CdaeDesc(2 if kind == "grad" else 3, d_in, 0, h, nl, 2)
+    assert L.lib().ardae_cdae_param_floats(ctypes.byref(d)) == total == params
+    assert L.lib().ardae_cdae_packed_floats(ctypes.byref(d)) == packed
+    assert tuple(L.lib().ardae_cdae_workspace_floats(ctypes.byref(d), 4, 8, g) for g in (0, 1)) == workspace
+
+
 def test_survey_parameter_counts():
     """839 472 / 543 489 (cfg #2), 271 386 / 528 129 (cfg #1), 2 923 521 (cfg #4 cDAE), 17 943 584 (cfg #5 cDAE)."""
     tot = lambda spec: layout.offsets(spec)[1]
