@@ -20,7 +20,7 @@
 
 #include "auxmodel.h"
 #include "elementwise.h"
-#include "host_util.h"
+#include "mlp.h"
 
 namespace ardae {
 namespace {
@@ -30,7 +30,7 @@ struct AuxLayout {
   int clip0, clip1;               // NormalDistribution.clip_logvar codes of the z0 / z heads (ardae_hip.h: ARDAE_MODEL_CLIP_*), 0 = none
   bool toy;                       // kind 7
   std::vector<Lin> am, ef, dec;   // aux_encode.main, encode.fc, decode.main: nl Linear each (nl - 1 hidden + fc, all followed by act)
-  Lin mean0, logvar0, mean, logvar, logit, logvarx;   // logit: decode.reparam.logit_fn, or (toy) mean_fn followed by logvarx = logvar_fn
+  Lin mean0, logvar0, mean, logvar, heads[2];         // heads: decode.reparam.logit_fn, or (toy) mean_fn, logvar_fn
   size_t total = 0;
   // stage rows per image of a call with nz rows per image: nz, or (toy) q = sqrt(nz)
   int stage(int nz) const {
@@ -49,28 +49,24 @@ struct AuxLayout {
     for (int l = 0; l < nl; ++l) ef.push_back(one(h, l == 0 ? D + nd : h));
     mean = one(zd, h); logvar = one(zd, h);
     for (int l = 0; l < nl; ++l) dec.push_back(one(h, l == 0 ? zd : h));
-    logit = one(D, h);
-    if (toy) logvarx = one(D, h);
+    heads[0] = one(D, h);
+    if (toy) heads[1] = one(D, h);
     total = off;
   }
 };
 
 struct AuxPacked {
-  std::vector<size_t> am_f, am_b, ef_f, ef_b, dec_f, dec_b;   // ef_f[0] / ef_b[0]: the z0 half of the first encoder layer
-  size_t efx_f, mean0_f, mean0_b, logvar0_f, logvar0_b, mean_f, mean_b, logvar_f, logvar_b, logit_f, logit_b, logvarx_f = 0, logvarx_b = 0;
-  AuxPacked(const AuxLayout& P, PackList& pl) {
-    const size_t nl = P.nl;
-    am_f.resize(nl); am_b.resize(nl); ef_f.resize(nl); ef_b.resize(nl); dec_f.resize(nl); dec_b.resize(nl);
-    for (size_t l = 0; l < nl; ++l) pl.pair(P.am[l], am_f[l], am_b[l]);
+  MlpStack am, ef;   // ef: the encoder's layers 2 .. nl (the first one is a row bias plus its z0 half: efx_f, ef0_f / ef0_b)
+  MlpDecoder dec;
+  size_t efx_f, ef0_f, ef0_b, mean0_f, mean0_b, logvar0_f, logvar0_b, mean_f, mean_b, logvar_f, logvar_b;
+  AuxPacked(const AuxLayout& P, PackList& pl) : am(P.am.data(), P.nl, pl) {
     pl.pair(P.mean0, mean0_f, mean0_b); pl.pair(P.logvar0, logvar0_f, logvar0_b);
     const Lin& e0 = P.ef[0];                                            // [h, D + nd]: image half (forward only) | z0 half
     efx_f = pl.panel(e0.w, e0.in, P.h, P.D, false);
-    pl.pair(e0, ef_f[0], ef_b[0], P.D, P.nd);
-    for (size_t l = 1; l < nl; ++l) pl.pair(P.ef[l], ef_f[l], ef_b[l]);
+    pl.pair(e0, ef0_f, ef0_b, P.D, P.nd);
+    ef = MlpStack(P.ef.data() + 1, P.nl - 1, pl);
     pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
-    for (size_t l = 0; l < nl; ++l) pl.pair(P.dec[l], dec_f[l], dec_b[l]);
-    pl.pair(P.logit, logit_f, logit_b);
-    if (P.toy) pl.pair(P.logvarx, logvarx_f, logvarx_b);
+    dec = MlpDecoder(P.dec.data(), P.nl, P.heads, P.toy ? 2 : 1, pl);
   }
   explicit AuxPacked(const AuxLayout& P, PackList&& sizing = PackList()) : AuxPacked(P, sizing) {}   // offsets only
 };
@@ -78,22 +74,22 @@ struct AuxPacked {
 struct AuxWs {
   float *xs, *mu0, *lv0, *rb, *z0, *mu, *lv, *z, *zero;
   float *lv0r, *lvr;                    // the heads' raw outputs when a log-variance clip is on (lv0 / lv then hold the clipped values)
-  std::vector<float*> e, t, dcd;        // e[l] [B,h] (l = 1..nl), t[i] [R,h], dcd[l] [R,h]
-  float *o, *o2, *rec_row, *pri_row;    // decoder logits (toy: mean, o2 = logvar) and row losses
+  std::vector<float*> e, t;             // e[l] [B,h] (l = 1..nl), t[l] [R,h]
+  MlpDecoder::Bufs D;                   // the decoder's, forward and backward (toy: o[0] = mean, o[1] = logvar)
+  float *rec_row, *pri_row;             // row losses
   // backward
-  float *dox, *dox2, *dzq, *dz, *dlv, *dz0, *dlv0r, *drb, *dmu0, *dlv0;
+  float *dlv, *dz0, *dlv0r, *drb, *dmu0, *dlv0;
   float *dmu_s, *dlv_s;                 // toy: dz / dlv summed over the q z's of a stage row, [R, zd]
-  std::vector<float*> ddec, dt, de;
+  std::vector<float*> dt, de;
 };
 
 int wgrad_nprob(const AuxLayout& P) { return 1 + (P.toy ? 1 : 0) + P.nl + 2 + P.nl + 1 + 2 + P.nl; }
 
 // mode 0: sampler only; 1: + decoder, losses, backward, weight gradients
-void carve(const AuxLayout& P, Bump& ws, int B, int nz, int mode, AuxWs& W) {
+void carve(const AuxLayout& P, const AuxPacked& K, Bump& ws, int B, int nz, int mode, AuxWs& W) {
   const size_t R = (size_t)B * P.stage(nz), N = (size_t)B * nz, h = P.h;
   W.xs = ws.take((size_t)B * P.D);
-  W.e.assign(P.nl + 1, nullptr);
-  for (int l = 1; l <= P.nl; ++l) W.e[l] = ws.take((size_t)B * h);
+  K.am.carve(ws, B, W.e);
   W.mu0 = ws.take((size_t)B * P.nd); W.lv0 = ws.take((size_t)B * P.nd); W.rb = ws.take((size_t)B * h);
   W.z0 = ws.take(R * P.nd);
   W.t.assign(P.nl + 1, nullptr);
@@ -103,28 +99,25 @@ void carve(const AuxLayout& P, Bump& ws, int B, int nz, int mode, AuxWs& W) {
   W.lv0r = P.clip0 ? ws.take((size_t)B * P.nd) : W.lv0;
   W.lvr = P.clip1 ? ws.take(R * P.zd) : W.lv;
   if (mode == 0) return;
-  W.dcd.assign(P.nl + 1, nullptr);
-  for (int l = 1; l <= P.nl; ++l) W.dcd[l] = ws.take(N * h);
-  W.o = ws.take(N * P.D); W.o2 = P.toy ? ws.take(N * P.D) : nullptr; W.rec_row = ws.take(N); W.pri_row = ws.take(N);
-  W.dox = ws.take(N * P.D); W.dox2 = P.toy ? ws.take(N * P.D) : nullptr;
-  W.dzq = ws.take(N * P.zd); W.dz = ws.take(N * P.zd); W.dlv = ws.take(N * P.zd);
+  K.dec.carve(ws, N, true, W.D);
+  W.rec_row = ws.take(N); W.pri_row = ws.take(N);
+  W.dlv = ws.take(N * P.zd);
   W.dmu_s = P.toy ? ws.take(R * P.zd) : nullptr; W.dlv_s = P.toy ? ws.take(R * P.zd) : nullptr;
   W.dz0 = ws.take(R * P.nd); W.dlv0r = ws.take(R * P.nd);
   W.drb = ws.take((size_t)B * h); W.dmu0 = ws.take((size_t)B * P.nd); W.dlv0 = ws.take((size_t)B * P.nd);
-  W.ddec.assign(P.nl + 1, nullptr); W.dt.assign(P.nl + 1, nullptr); W.de.assign(P.nl + 1, nullptr);
-  for (int l = 1; l <= P.nl; ++l) { W.ddec[l] = ws.take(N * h); W.dt[l] = ws.take(R * h); W.de[l] = ws.take((size_t)B * h); }
+  W.dt.assign(P.nl + 1, nullptr);
+  for (int l = 1; l <= P.nl; ++l) W.dt[l] = ws.take(R * h);
+  K.am.carve(ws, B, W.de);
 }
+using AuxEntry = Entry<AuxLayout, AuxPacked, AuxWs>;
 
 // every weight-gradient problem of aux_model_vae_backward, with its scratch taken from ws
 // (rows: B images, R = B stage(nz) stage rows, N = B nz z / decoder rows; toy: the heads' gradients are the sums over a stage row's q z's)
-void aux_wgrads(const AuxLayout& P, const AuxWs& W, int B, int nz, WgradList& wl, Bump& ws) {
+void aux_wgrads(const AuxLayout& P, const AuxPacked& K, const AuxWs& W, int B, int nz, WgradList& wl, Bump& ws) {
   const int R = B * P.stage(nz), N = B * nz, h = P.h, nl = P.nl;
-  const float* dmu = P.toy ? W.dmu_s : W.dz;
+  const float* dmu = P.toy ? W.dmu_s : W.D.dz;
   const float* dlv = P.toy ? W.dlv_s : W.dlv;
-  wl.push(N, P.D, h, W.dox, W.dcd[nl], h, wl.g(P.logit.w), h, wl.g(P.logit.b));                       // logit head (toy: mean head)
-  if (P.toy) wl.push(N, P.D, h, W.dox2, W.dcd[nl], h, wl.g(P.logvarx.w), h, wl.g(P.logvarx.b));      // toy: logvar head
-  for (int l = 1; l <= nl; ++l)                                                                      // decoder
-    wl.push(N, h, P.dec[l - 1].in, W.ddec[l], l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, wl.g(P.dec[l - 1].w), P.dec[l - 1].in, wl.g(P.dec[l - 1].b));
+  K.dec.wgrads(wl, N, W.z, W.D);                                                                     // decoder: head(s), then its layers
   wl.push(R, P.zd, h, dmu, W.t[nl], h, wl.g(P.mean.w), h, wl.g(P.mean.b));
   wl.push(R, P.zd, h, dlv, W.t[nl], h, wl.g(P.logvar.w), h, wl.g(P.logvar.b));
   for (int l = nl; l >= 2; --l) wl.push(R, h, h, W.dt[l], W.t[l - 1], h, wl.g(P.ef[l - 1].w), h, wl.g(P.ef[l - 1].b));   // encoder layers n..2
@@ -132,19 +125,19 @@ void aux_wgrads(const AuxLayout& P, const AuxWs& W, int B, int nz, WgradList& wl
   wl.push(B, h, P.D, W.drb, W.xs, P.D, wl.g(P.ef[0].w), P.ef[0].in, nullptr);                         // first encoder layer, image half
   wl.push(B, P.nd, h, W.dmu0, W.e[nl], h, wl.g(P.mean0.w), h, wl.g(P.mean0.b));
   wl.push(B, P.nd, h, W.dlv0, W.e[nl], h, wl.g(P.logvar0.w), h, wl.g(P.logvar0.b));
-  for (int l = 1; l <= nl; ++l)                                                                      // aux main
-    wl.push(B, h, P.am[l - 1].in, W.de[l], l == 1 ? W.xs : W.e[l - 1], l == 1 ? P.D : h, wl.g(P.am[l - 1].w), P.am[l - 1].in, wl.g(P.am[l - 1].b));
+  K.am.wgrads(wl, B, W.xs, W.e.data(), W.de.data());                                                 // aux main
   wl.assign(ws, wgrad_nprob(P));
 }
 
 size_t workspace_floats(const AuxLayout& P, int B, int nz, int mode) {
   // dry run of carve() and the weight-gradient list on a null arena
+  const AuxPacked K(P);
   Bump ws;
   AuxWs W;
-  carve(P, ws, B, nz, mode == 0 ? 0 : 1, W);
+  carve(P, K, ws, B, nz, mode == 0 ? 0 : 1, W);
   if (mode != 0) {
     WgradList wl(nullptr);
-    aux_wgrads(P, W, B, nz, wl, ws);
+    aux_wgrads(P, K, W, B, nz, wl, ws);
   }
   return ws.off;
 }
@@ -234,78 +227,39 @@ int sampler_fwd(const AuxLayout& P, const AuxPacked& K, const float* params, con
   const float* eps = P.toy ? noise + (size_t)R * P.nd : noise + P.nd;
   if (P.toy) ARDAE_TRY(launch_copy(x, (int64_t)B * P.D, W.xs, st));      // no rescale (models/vae/auxtoy.py: the `x = 2*x - 1` lines are gone)
   else ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.xs, st));
-  for (int l = 1; l <= nl; ++l) {
-    LinArgs A{}; A.bias = params + P.am[l - 1].b; A.Y = W.e[l]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, act, B, h, l == 1 ? W.xs : W.e[l - 1], l == 1 ? P.D : h, P.am[l - 1].in, packed + K.am_f[l - 1], A, st));
-  }
-  {
-    LinArgs A{}; A.bias = params + P.mean0.b; A.Y = W.mu0; A.ldY = P.nd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.nd, W.e[nl], h, h, packed + K.mean0_f, A, st));
-    LinArgs A2{}; A2.bias = params + P.logvar0.b; A2.Y = W.lv0r; A2.ldY = P.nd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.nd, W.e[nl], h, h, packed + K.logvar0_f, A2, st));
-    ARDAE_TRY(launch_logvar_clip(W.lv0r, nullptr, W.lv0, (int64_t)B * P.nd, P.clip0, st));
-    LinArgs A3{}; A3.bias = params + P.ef[0].b; A3.Y = W.rb; A3.ldY = h;   // image half of the first encoder layer (+ its bias)
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, h, W.xs, P.D, P.D, packed + K.efx_f, A3, st));
-  }
+  ARDAE_TRY(K.am.fwd(params, packed, act, B, W.xs, W.e.data(), st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.e[nl], h, h, packed + K.mean0_f, params + P.mean0.b, W.mu0, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.e[nl], h, h, packed + K.logvar0_f, params + P.logvar0.b, W.lv0r, st));
+  ARDAE_TRY(launch_logvar_clip(W.lv0r, nullptr, W.lv0, (int64_t)B * P.nd, P.clip0, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, h, W.xs, P.D, P.D, packed + K.efx_f, params + P.ef[0].b, W.rb, st));   // image half of the first encoder layer (+ its bias)
   ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, noise, ld0, R, P.nd, nz, W.z0, st));
-  for (int l = 1; l <= nl; ++l) {
-    LinArgs A{}; A.Y = W.t[l]; A.ldY = h;
-    if (l == 1) { A.rowbias = W.rb; A.rowbias_ld = h; A.rows_per_group = nz; }
-    else A.bias = params + P.ef[l - 1].b;
-    ARDAE_TRY(lin1(EPI_ACT, act, R, h, l == 1 ? W.z0 : W.t[l - 1], l == 1 ? P.nd : h, l == 1 ? P.nd : h, packed + K.ef_f[l - 1], A, st));
+  {  // first encoder layer: the z0 half on the stage rows, the image half as a row bias
+    LinArgs A{}; A.Y = W.t[1]; A.ldY = h; A.rowbias = W.rb; A.rowbias_ld = h; A.rows_per_group = nz;
+    ARDAE_TRY(lin1(EPI_ACT, act, R, h, W.z0, P.nd, P.nd, packed + K.ef0_f, A, st));
   }
-  {
-    LinArgs A{}; A.bias = params + P.mean.b; A.Y = W.mu; A.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.t[nl], h, h, packed + K.mean_f, A, st));
-    LinArgs A2{}; A2.bias = params + P.logvar.b; A2.Y = W.lvr; A2.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.t[nl], h, h, packed + K.logvar_f, A2, st));
-    ARDAE_TRY(launch_logvar_clip(W.lvr, nullptr, W.lv, (int64_t)R * P.zd, P.clip1, st));
-  }
+  ARDAE_TRY(K.ef.fwd(params, packed, act, R, W.t[1], W.t.data() + 1, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.t[nl], h, h, packed + K.mean_f, params + P.mean.b, W.mu, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.t[nl], h, h, packed + K.logvar_f, params + P.logvar.b, W.lvr, st));
+  ARDAE_TRY(launch_logvar_clip(W.lvr, nullptr, W.lv, (int64_t)R * P.zd, P.clip1, st));
   if (P.toy) return launch_reparam_fwd(W.mu, W.lv, eps, lde, (int64_t)R * nz, P.zd, nz, W.z, st);      // q z's per stage row
   return launch_reparam_fwd(W.mu, W.lv, eps, lde, R, P.zd, 1, W.z, st);
 }
 
-// noise of a call with nz rows per image, or the zero block of a std = 0 pass
-const float* noise_or_zero(const AuxLayout& P, const float* noise, int B, int nz, AuxWs& W, hipStream_t st, int& rc) {
-  rc = 0;
-  if (noise) return noise;
-  if (rc == 0) rc = launch_fill(W.zero, (size_t)B * P.stage(nz) * P.nd + (size_t)B * nz * P.zd, 0.f, st);
-  return W.zero;
-}
-
-}  // namespace
-
-size_t aux_model_param_floats(const ardae_model_desc& d) { return AuxLayout(d).total; }
-size_t aux_model_packed_floats(const ardae_model_desc& d) {
-  PackList pl;
-  AuxPacked(AuxLayout(d), pl);
-  return pl.total();
-}
-size_t aux_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+// ------------------------------------------------------------------------------------------------ entry points (kinds 3 / 7)
+size_t aux_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   const AuxLayout P(d);
-  if (mode == 2) return (size_t)P.nl * al64((size_t)B * nz * P.h);   // decode only
+  if (mode == 2) return AuxPacked(P).dec.decode_floats((size_t)B * nz);   // decode only
   return workspace_floats(P, B, nz, mode == 3 ? 0 : mode);
 }
 
-int aux_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  PackList pl(params, packed);
-  AuxPacked(AuxLayout(d), pl);
-  return pl.launch(st);
-}
-
-int aux_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
-  const AuxLayout P(d);
-  const AuxPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxWs W;
-  carve(P, ws, B, nz, 0, W);
+int aux_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+               float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
+  AuxEntry entry(d, workspace, wsf, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "aux_model_encode: workspace too small");
-  int rc;
   ARDAE_CHECK_ARG(!P.toy || P.stage(nz) * P.stage(nz) == nz, "aux_model_encode: ToyAuxIPVAE draws q z0's x q z's per image - nz (%d) must be a square", nz);
-  const float* nz_ptr = noise_or_zero(P, noise, B, nz, W, st, rc);
-  ARDAE_TRY(rc);
-  ARDAE_TRY(sampler_fwd(P, K, params, packed, x, nz_ptr, B, nz, W, st));
+  ARDAE_TRY(noise_or_zero(noise, W.zero, (size_t)B * P.stage(nz) * P.nd + (size_t)B * nz * P.zd, st));
+  ARDAE_TRY(sampler_fwd(P, K, params, packed, x, noise, B, nz, W, st));
   if (z_out) ARDAE_TRY(launch_copy(W.z, (size_t)B * nz * P.zd, z_out, st));
   if (hidden_out) {   // forward_hidden of the ENCODER (ivae/auxmnist.py:125-132, nz == 1): cat(h0, h)
     ARDAE_CHECK_ARG(nz == 1, "aux_model_encode: the hidden context is defined for nz == 1");
@@ -315,131 +269,70 @@ int aux_model_encode(const ardae_model_desc& d, const float* params, const float
   return 0;
 }
 
-// decoder on R rows: the hidden layers into hid[1 .. nl], then the logit head (toy: mean and logvar heads) into out0 (, out1)
-static int decoder_fwd(const AuxLayout& P, const AuxPacked& K, const float* params, const float* packed, const float* z, int R, float* const* hid,
-                       float* out0, float* out1, hipStream_t st) {
-  const int h = P.h;
-  for (int l = 1; l <= P.nl; ++l) {
-    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = hid[l]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, P.act, R, h, l == 1 ? z : hid[l - 1], l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
-  }
-  LinArgs A{}; A.bias = params + P.logit.b; A.Y = out0; A.ldY = P.D;
-  ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, hid[P.nl], h, h, packed + K.logit_f, A, st));
-  if (P.toy) {
-    LinArgs A2{}; A2.bias = params + P.logvarx.b; A2.Y = out1; A2.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, hid[P.nl], h, h, packed + K.logvarx_f, A2, st));
-  }
-  return 0;
-}
-
-int aux_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                     float* out0, hipStream_t st, float* out1) {
-  const AuxLayout P(d);
-  const AuxPacked K(P);
-  Bump ws(workspace, wsf);
-  std::vector<float*> hid(P.nl + 1, nullptr);
-  for (int l = 1; l <= P.nl; ++l) hid[l] = ws.take((size_t)R * P.h);
-  ARDAE_CHECK_ARG(ws.ok, "aux_model_decode: workspace too small");
-  ARDAE_CHECK_ARG(!P.toy || out1, "aux_model_decode: the Gaussian decoder returns mean (out0) and logvar (out1)");
-  return decoder_fwd(P, K, params, packed, z, R, hid.data(), out0, out1, st);
-}
-
-int aux_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                          float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  const AuxLayout P(d);
-  const AuxPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxWs W;
-  carve(P, ws, B, nz, 1, W);
+int aux_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                    float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+  AuxEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_forward: workspace too small");
   ARDAE_CHECK_ARG(!P.toy || P.stage(nz) * P.stage(nz) == nz, "aux_model_vae_forward: ToyAuxIPVAE needs a square nz (got %d)", nz);
   const int R = B * nz;      // z / decoder rows
   ARDAE_TRY(sampler_fwd(P, K, params, packed, x, noise, B, nz, W, st));
   ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
-  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, R, W.dcd.data(), W.o, W.o2, st));
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.o, W.o2, x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
+  ARDAE_TRY(K.dec.fwd(params, packed, P.act, R, W.z, W.D.hid.data(), W.D.o, st));
+  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
   return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
 }
 
-int aux_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                           float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
-                           hipStream_t st) {
+int aux_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                     float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
+                     hipStream_t st) {
   (void)noise;
-  const AuxLayout P(d);
-  const AuxPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxWs W;
-  carve(P, ws, B, nz, 1, W);
+  AuxEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   const int N = B * nz;                                   // z / decoder rows
   const int nzs = P.stage(nz);                            // samples per image at the stage level (toy: q)
   const int R = B * nzs, h = P.h, act = P.act, nl = P.nl;
   const float gscale = dloss / (float)N;
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.o, W.o2, x, W.z, N, nz, P.D, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.dox, W.dox2, W.dzq, st));
-  // decoder backward
-  if (P.toy) {      // two heads (mean_fn, logvar_fn) back into the last hidden layer
-    LinArgs A{}; A.M = N; A.Nout = h; A.nsrc = 2; A.act = act; A.S = W.dcd[nl]; A.ldS = h; A.Y = W.ddec[nl]; A.ldY = h;
-    A.src[0].x = W.dox; A.src[0].ld = P.D; A.src[0].K = P.D; A.src[0].wp = packed + K.logit_b;
-    A.src[1].x = W.dox2; A.src[1].ld = P.D; A.src[1].K = P.D; A.src[1].wp = packed + K.logvarx_b;
-    ARDAE_TRY(launch_linear(A, EPI_DACT, st));
-  } else {
-    LinArgs A{}; A.S = W.dcd[nl]; A.ldS = h; A.Y = W.ddec[nl]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, N, h, W.dox, P.D, P.D, packed + K.logit_b, A, st));
-  }
-  for (int l = nl; l >= 2; --l) {
-    LinArgs A{}; A.S = W.dcd[l - 1]; A.ldS = h; A.Y = W.ddec[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, N, h, W.ddec[l], h, h, packed + K.dec_b[l - 1], A, st));
-  }
-  {  // dz = ddec_1 . D_1 + (prior + injected seed)
-    LinArgs A{}; A.S = W.dzq; A.ldS = P.zd; A.Q = W.dzq; A.ldQ = P.zd; A.Y = W.dz; A.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_DACT, ACT_NONE, N, P.zd, W.ddec[1], h, h, packed + K.dec_b[0], A, st));
-  }
+  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, N, nz, P.D, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.D.dox[0],
+                            W.D.dox[1], W.D.dzq, st));
+  ARDAE_TRY(K.dec.bwd(packed, act, N, W.D, st));
   // second reparameterisation: dmu = dz, dlv = dz (z - mu) / 2; both heads back into h = t_n
   // (toy: q z's share a stage row's mu / lv: their dz and dlv are summed over the q rows first)
-  ARDAE_TRY(launch_reparam_bwd(W.dz, W.z, W.mu, N, P.zd, P.toy ? nzs : 1, W.dlv, st));
-  const float* dmu = W.dz;
-  const float* dlv = W.dlv;
+  ARDAE_TRY(launch_reparam_bwd(W.D.dz, W.z, W.mu, N, P.zd, P.toy ? nzs : 1, W.dlv, st));
+  const float* dmu = W.D.dz;
+  float* dlv = W.dlv;
   if (P.toy) {
-    ARDAE_TRY(launch_segment_sum(W.dz, P.zd, R, nzs, P.zd, 1.0f, W.dmu_s, P.zd, st));
+    ARDAE_TRY(launch_segment_sum(W.D.dz, P.zd, R, nzs, P.zd, 1.0f, W.dmu_s, P.zd, st));
     ARDAE_TRY(launch_segment_sum(W.dlv, P.zd, R, nzs, P.zd, 1.0f, W.dlv_s, P.zd, st));
     dmu = W.dmu_s; dlv = W.dlv_s;
   }
   // through the z head's log-variance clip: d lv_raw = d lv c'(lv_raw) (in place; one value per stage row)
-  ARDAE_TRY(launch_logvar_clip(W.lvr, dlv, const_cast<float*>(dlv), (int64_t)R * P.zd, P.clip1, st));
-  {
-    LinArgs A{}; A.M = R; A.Nout = h; A.nsrc = 2; A.act = act; A.S = W.t[nl]; A.ldS = h; A.Y = W.dt[nl]; A.ldY = h;
-    A.src[0].x = dmu; A.src[0].ld = P.zd; A.src[0].K = P.zd; A.src[0].wp = packed + K.mean_b;
-    A.src[1].x = dlv; A.src[1].ld = P.zd; A.src[1].K = P.zd; A.src[1].wp = packed + K.logvar_b;
-    ARDAE_TRY(launch_linear(A, EPI_DACT, st));
-  }
-  for (int l = nl; l >= 2; --l) {
-    LinArgs A{}; A.S = W.t[l - 1]; A.ldS = h; A.Y = W.dt[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, R, h, W.dt[l], h, h, packed + K.ef_b[l - 1], A, st));
-  }
-  {  // dz0 = dt_1 Wz  (no activation between z0 and the layer)
-    LinArgs A{}; A.Y = W.dz0; A.ldY = P.nd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.nd, W.dt[1], h, h, packed + K.ef_b[0], A, st));
-  }
+  ARDAE_TRY(launch_logvar_clip(W.lvr, dlv, dlv, (int64_t)R * P.zd, P.clip1, st));
+  ARDAE_TRY(dense_bwd2(act, R, h, dmu, packed + K.mean_b, dlv, packed + K.logvar_b, P.zd, W.t[nl], W.dt[nl], st));
+  ARDAE_TRY(K.ef.bwd(packed, act, R, W.t.data() + 1, W.dt.data() + 1, st));                             // dt_n .. dt_2
+  if (nl >= 2) ARDAE_TRY(dense_bwd(act, R, h, W.dt[2], h, packed + K.ef.b[0], W.t[1], W.dt[1], st));    // ... and into the first layer's output
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, W.dt[1], h, h, packed + K.ef0_b, nullptr, W.dz0, st));          // dz0 = dt_1 Wz  (no activation between z0 and the layer)
   ARDAE_TRY(launch_segment_sum(W.dt[1], h, B, nzs, h, 1.0f, W.drb, h, st));
   // first reparameterisation, reduced over the nz samples of each image
   ARDAE_TRY(launch_reparam_bwd(W.dz0, W.z0, W.mu0, R, P.nd, nzs, W.dlv0r, st));
   ARDAE_TRY(launch_segment_sum(W.dz0, P.nd, B, nzs, P.nd, 1.0f, W.dmu0, P.nd, st));
   ARDAE_TRY(launch_segment_sum(W.dlv0r, P.nd, B, nzs, P.nd, 1.0f, W.dlv0, P.nd, st));
   ARDAE_TRY(launch_logvar_clip(W.lv0r, W.dlv0, W.dlv0, (int64_t)B * P.nd, P.clip0, st));      // ... and through the z0 head's
-  {
-    LinArgs A{}; A.M = B; A.Nout = h; A.nsrc = 2; A.act = act; A.S = W.e[nl]; A.ldS = h; A.Y = W.de[nl]; A.ldY = h;
-    A.src[0].x = W.dmu0; A.src[0].ld = P.nd; A.src[0].K = P.nd; A.src[0].wp = packed + K.mean0_b;
-    A.src[1].x = W.dlv0; A.src[1].ld = P.nd; A.src[1].K = P.nd; A.src[1].wp = packed + K.logvar0_b;
-    ARDAE_TRY(launch_linear(A, EPI_DACT, st));
-  }
-  for (int l = nl; l >= 2; --l) {
-    LinArgs A{}; A.S = W.e[l - 1]; A.ldS = h; A.Y = W.de[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, B, h, W.de[l], h, h, packed + K.am_b[l - 1], A, st));
-  }
+  ARDAE_TRY(dense_bwd2(act, B, h, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.e[nl], W.de[nl], st));
+  ARDAE_TRY(K.am.bwd(packed, act, B, W.e.data(), W.de.data(), st));
   // weight gradients: one batched launch
   WgradList wl(grads, grads_beta);
-  aux_wgrads(P, W, B, nz, wl, ws);
+  aux_wgrads(P, K, W, B, nz, wl, ws);
   ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_backward: workspace too small");
   return wl.launch(st);
 }
+
+}  // namespace
+
+// (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
+#ifndef __HIP_DEVICE_COMPILE__
+const Family AUX_FAMILY = {family_param_floats<AuxLayout, AuxPacked>, family_packed_floats<AuxLayout, AuxPacked>, aux_workspace_floats,
+                           family_pack<AuxLayout, AuxPacked>, aux_encode, mlp_decode<AuxLayout, AuxPacked>, aux_vae_forward, aux_vae_backward};
+#endif
 
 }  // namespace ardae

@@ -11,8 +11,6 @@
 #include "common.h"
 #include "auxmodel.h"
 #include "convmodel.h"
-#include "elementwise.h"
-#include "host_util.h"
 
 namespace ardae {
 namespace {
@@ -68,11 +66,6 @@ __global__ void col2im_s2_kernel(const float* __restrict__ cols, int IH, int IW,
   out[e] = v;
 }
 
-__global__ void fill_kernel(float* __restrict__ p, float v, int64_t n) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) p[e] = v;
-}
-
 // ------------------------------------------------------------------------------------------------ layout
 // a Lin's weight is viewed as [out, in] (convs: [O, C*25]; deconvs: [in_ch, out_ch*25], with out_ch bias entries)
 struct ConvLayout {
@@ -125,7 +118,7 @@ struct ConvWs {
 constexpr int EH[4] = {28, 14, 7, 4};      // encoder spatial sizes
 constexpr int ECH[4] = {1, 16, 32, 32};    // encoder channels
 
-void carve(const ConvLayout& P, Bump& ws, int B, int nz, int mode, ConvWs& W) {
+void carve(const ConvLayout& P, const ConvPacked&, Bump& ws, int B, int nz, int mode, ConvWs& W) {
   const size_t R = (size_t)B * nz;
   W.x2 = ws.take((size_t)B * 784);
   for (int i = 0; i < 3; ++i) {
@@ -150,6 +143,7 @@ void carve(const ConvLayout& P, Bump& ws, int B, int nz, int mode, ConvWs& W) {
   W.dcols2 = ws.take((size_t)B * 49 * 400); W.dh1 = ws.take((size_t)B * 196 * 16);
   W.ones = ws.take(R * 784);
 }
+using ConvEntry = Entry<ConvLayout, ConvPacked, ConvWs>;
 
 int im2col(const float* x, int Bn, int H, int Wd, int C, int OH, int OW, float* cols, hipStream_t st) {
   const int64_t total = (int64_t)Bn * OH * OW * C * 25;
@@ -172,8 +166,7 @@ int trunk_fwd(const Lin* conv, const size_t* conv_f, const float* params, const 
   for (int i = 0; i < 3; ++i) {                                                 // conv_i = im2col + Linear([O, C*25]) + act
     const int OH = EH[i + 1], Kc = ECH[i] * 25;
     ARDAE_TRY(im2col(cur, B, EH[i], EH[i], ECH[i], OH, OH, cols[i], st));
-    LinArgs A{}; A.bias = params + conv[i].b; A.Y = hcv[i]; A.ldY = ECH[i + 1];
-    ARDAE_TRY(lin1(EPI_ACT, act, B * OH * OH, ECH[i + 1], cols[i], Kc, Kc, packed + conv_f[i], A, st));
+    ARDAE_TRY(dense_fwd(act, B * OH * OH, ECH[i + 1], cols[i], Kc, Kc, packed + conv_f[i], params + conv[i].b, hcv[i], st));
     cur = hcv[i];
   }
   return launch_nhwc_nchw(hcv[2], B, 16, 32, inp, false, st);                      // h3.view(B,-1) of NCHW
@@ -184,11 +177,9 @@ int trunk_bwd(const size_t* conv_b, const float* packed, const float* dinp, floa
               float* dh2, float* dcols2, float* dh1, int B, int act, hipStream_t st) {
   ARDAE_TRY(launch_nhwc_nchw(dinp, B, 16, 32, dinp_t, true, st));                // NCHW-flat -> NHWC rows
   ARDAE_TRY(launch_mul_dact(dinp_t, hcv[2], act, dh3, (int64_t)B * 512, st));
-  { LinArgs A{}; A.Y = dcols3; A.ldY = 800;                                     // conv3 backward-data: dcols = dpre . W3
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B * 16, 800, dh3, 32, 32, packed + conv_b[2], A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B * 16, 800, dh3, 32, 32, packed + conv_b[2], nullptr, dcols3, st));   // conv3 backward-data: dcols = dpre . W3
   ARDAE_TRY(col2im(dcols3, B, 4, 4, 32, 7, 7, 7, 7, nullptr, act, hcv[1], dh2, st));
-  { LinArgs A{}; A.Y = dcols2; A.ldY = 400;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B * 49, 400, dh2, 32, 32, packed + conv_b[1], A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B * 49, 400, dh2, 32, 32, packed + conv_b[1], nullptr, dcols2, st));
   return col2im(dcols2, B, 7, 7, 16, 14, 14, 14, 14, nullptr, act, hcv[0], dh1, st);
 }
 
@@ -197,18 +188,12 @@ int conv_encode_fwd(const ConvLayout& P, const ConvPacked& K, const float* param
   const int R = B * nz, act = P.act;
   ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // ivae/conv.py:81
   ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.cols, W.hcv, W.inp, B, act, st));
-  {
-    LinArgs A{}; A.bias = params + P.fc4.b; A.Y = W.rb; A.ldY = 800;            // image half of fc4, once per image
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, A, st));
-  }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, params + P.fc4.b, W.rb, st));   // image half of fc4, once per image
   {
     LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.t1; A.ldY = 800;
     ARDAE_TRY(lin1(EPI_ACT, act, R, 800, noise, P.nd, P.nd, packed + K.fc4n_f, A, st));
   }
-  {
-    LinArgs A{}; A.bias = params + P.fc5.b; A.Y = W.z; A.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, A, st));
-  }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, params + P.fc5.b, W.z, st));
   if (z_out) ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
   return 0;
 }
@@ -216,17 +201,17 @@ int conv_encode_fwd(const ConvLayout& P, const ConvPacked& K, const float* param
 int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
                     hipStream_t st) {
   const int act = P.act;
-  { LinArgs A{}; A.bias = params + P.dfc[0].b; A.Y = W.d1; A.ldY = 300; ARDAE_TRY(lin1(EPI_ACT, act, R, 300, z, P.zd, P.zd, packed + K.dfc_f[0], A, st)); }
-  { LinArgs A{}; A.bias = params + P.dfc[1].b; A.Y = W.d2; A.ldY = 512; ARDAE_TRY(lin1(EPI_ACT, act, R, 512, W.d1, 300, 300, packed + K.dfc_f[1], A, st)); }
+  ARDAE_TRY(dense_fwd(act, R, 300, z, P.zd, P.zd, packed + K.dfc_f[0], params + P.dfc[0].b, W.d1, st));
+  ARDAE_TRY(dense_fwd(act, R, 512, W.d1, 300, 300, packed + K.dfc_f[1], params + P.dfc[1].b, W.d2, st));
   ARDAE_TRY(launch_nhwc_nchw(W.d2, R, 16, 32, W.g0, true, st));                  // h1.view(R,32,4,4) -> NHWC rows
   // deconv1 32->32: 4x4 -> 7x7, activation, zero-pad to 8x8
-  { LinArgs A{}; A.Y = W.c1; A.ldY = 800; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R * 16, 800, W.g0, 32, 32, packed + K.dcv_f[0], A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R * 16, 800, W.g0, 32, 32, packed + K.dcv_f[0], nullptr, W.c1, st));
   ARDAE_TRY(col2im(W.c1, R, 4, 4, 32, 8, 8, 7, 7, params + P.dcv[0].b, act, nullptr, W.u1, st));
   // deconv2 32->16: 8x8 -> 15x15, activation
-  { LinArgs A{}; A.Y = W.c2; A.ldY = 400; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R * 64, 400, W.u1, 32, 32, packed + K.dcv_f[1], A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R * 64, 400, W.u1, 32, 32, packed + K.dcv_f[1], nullptr, W.c2, st));
   ARDAE_TRY(col2im(W.c2, R, 8, 8, 16, 15, 15, 15, 15, params + P.dcv[1].b, act, nullptr, W.u2, st));
   // logit deconv 16->1: 15x15 -> 29x29, cropped to 28x28
-  { LinArgs A{}; A.Y = W.c3; A.ldY = 25; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R * 225, 25, W.u2, 16, 16, packed + K.dcv_f[2], A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R * 225, 25, W.u2, 16, 16, packed + K.dcv_f[2], nullptr, W.c3, st));
   ARDAE_TRY(col2im(W.c3, R, 15, 15, 1, 28, 28, 28, 28, params + P.dcv[2].b, ACT_NONE, nullptr, W.logit, st));
   return 0;
 }
@@ -234,27 +219,17 @@ int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* param
 // decoder backward from W.dlogit (and W.dzq = prior + seed part of dL/dz): fills dc3/dp2/dc2/dp1/dc1/dg0/dd2/dd1 and W.dz
 int conv_decoder_bwd(const ConvLayout& P, const ConvPacked& K, const float* packed, ConvWs& W, int R, hipStream_t st) {
   const int act = P.act;
-  {
-    const int64_t n = (int64_t)R * 784;
-    hipLaunchKernelGGL(fill_kernel, dim3(nblk(n)), dim3(256), 0, st, W.ones, 1.0f, n);
-    ARDAE_LAUNCH_CHECK();
-  }
+  ARDAE_TRY(launch_fill(W.ones, (int64_t)R * 784, 1.0f, st));
   // ---- decoder backward.  d(cols) of a transposed conv = im2col of the output gradient over the deconv's INPUT grid.
   ARDAE_TRY(im2col(W.dlogit, R, 28, 28, 1, 15, 15, W.dc3, st));                 // cropped row/col 28 has no gradient
-  { LinArgs A{}; A.S = W.u2; A.ldS = 16; A.Y = W.dp2; A.ldY = 16;               // dpre2 = (dc3 . W3^T) (.) act'(u2)
-    ARDAE_TRY(lin1(EPI_DACT, act, R * 225, 16, W.dc3, 25, 25, packed + K.dcv_b[2], A, st)); }
+  ARDAE_TRY(dense_bwd(act, R * 225, 16, W.dc3, 25, packed + K.dcv_b[2], W.u2, W.dp2, st));   // dpre2 = (dc3 . W3^T) (.) act'(u2)
   ARDAE_TRY(im2col(W.dp2, R, 15, 15, 16, 8, 8, W.dc2, st));
-  { LinArgs A{}; A.S = W.u1; A.ldS = 32; A.Y = W.dp1; A.ldY = 32;               // zero at the padded positions: act'(0) = 0
-    ARDAE_TRY(lin1(EPI_DACT, act, R * 64, 32, W.dc2, 400, 400, packed + K.dcv_b[1], A, st)); }
+  ARDAE_TRY(dense_bwd(act, R * 64, 32, W.dc2, 400, packed + K.dcv_b[1], W.u1, W.dp1, st));   // zero at the padded positions: act'(0) = 0
   ARDAE_TRY(im2col(W.dp1, R, 8, 8, 32, 4, 4, W.dc1, st));
-  { LinArgs A{}; A.S = W.g0; A.ldS = 32; A.Y = W.dg0; A.ldY = 32;               // g0 is the (permuted) activated output of decode.fc
-    ARDAE_TRY(lin1(EPI_DACT, act, R * 16, 32, W.dc1, 800, 800, packed + K.dcv_b[0], A, st)); }
+  ARDAE_TRY(dense_bwd(act, R * 16, 32, W.dc1, 800, packed + K.dcv_b[0], W.g0, W.dg0, st));   // g0 is the (permuted) activated output of decode.fc
   ARDAE_TRY(launch_nhwc_nchw(W.dg0, R, 16, 32, W.dd2, false, st));               // -> d(pre) of decode.fc.fc  [R,512]
-  { LinArgs A{}; A.S = W.d1; A.ldS = 300; A.Y = W.dd1; A.ldY = 300;
-    ARDAE_TRY(lin1(EPI_DACT, act, R, 300, W.dd2, 512, 512, packed + K.dfc_b[1], A, st)); }
-  { LinArgs A{}; A.S = W.dzq; A.ldS = P.zd; A.Q = W.dzq; A.ldQ = P.zd; A.Y = W.dz; A.ldY = P.zd;   // + prior + injected seed
-    ARDAE_TRY(lin1(EPI_DACT, ACT_NONE, R, P.zd, W.dd1, 300, 300, packed + K.dfc_b[0], A, st)); }
-  return 0;
+  ARDAE_TRY(dense_bwd(act, R, 300, W.dd2, 512, packed + K.dfc_b[1], W.d1, W.dd1, st));
+  return dense_bwd(ACT_NONE, R, P.zd, W.dd1, 300, packed + K.dfc_b[0], W.dzq, W.dz, st, W.dzq);   // + prior + injected seed
 }
 
 // wgrad_splits hint of the conv backward: a tuning value, not the problem count (the list below has 14)
@@ -289,7 +264,7 @@ size_t conv_workspace(const ConvLayout& P, int B, int nz, int mode) {
   // run the carve (and the weight-gradient list) on a null arena to count
   Bump ws;
   ConvWs W;
-  carve(P, ws, B, nz, mode, W);
+  carve(P, ConvPacked(P), ws, B, nz, mode, W);
   if (mode == 1) {
     WgradList wl(nullptr);
     conv_wgrads(P, W, B, B * nz, nullptr, wl, ws);
@@ -297,62 +272,34 @@ size_t conv_workspace(const ConvLayout& P, int B, int nz, int mode) {
   return ws.off + al64((size_t)B * nz * P.nd);    // + zero-noise buffer for encode(std=0)
 }
 
-}  // namespace
-
 // ------------------------------------------------------------------------------------------------ entry points (kind == 2)
-size_t conv_model_param_floats(const ardae_model_desc& d) { return ConvLayout(d).total; }
-size_t conv_model_packed_floats(const ardae_model_desc& d) {
-  PackList pl;
-  ConvPacked(ConvLayout(d), pl);
-  return pl.total();
-}
 // mode 3 (encode_pair: two encode passes over one workspace) is mode 0
-size_t conv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return conv_workspace(ConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
+size_t conv_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return conv_workspace(ConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
 
-int conv_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  PackList pl(params, packed);
-  ConvPacked(ConvLayout(d), pl);
-  return pl.launch(st);
-}
-
-static const float* zero_noise(Bump& ws, const ConvLayout& P, int B, int nz, hipStream_t st) {
-  float* zero = ws.take((size_t)B * nz * P.nd);
-  if (launch_fill(zero, (size_t)B * nz * P.nd, 0.f, st) != 0) return nullptr;
-  return zero;
-}
-
-int conv_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
+int conv_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                       int nz, float* workspace, size_t wsf, float* z_out, float*, hipStream_t st, const float*) {
-  const ConvLayout P(d);
-  const ConvPacked K(P);
-  Bump ws(workspace, wsf);
-  ConvWs W;
-  carve(P, ws, B, nz, 0, W);
-  const float* nptr = noise ? noise : zero_noise(ws, P, B, nz, st);
+  ConvEntry entry(d, workspace, wsf, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
+  float* zero = noise ? nullptr : ws.take((size_t)B * nz * P.nd);
   ARDAE_CHECK_ARG(ws.ok, "conv_model_encode: workspace too small");
-  return conv_encode_fwd(P, K, params, packed, x, nptr, B, nz, W, z_out, st);
+  ARDAE_TRY(noise_or_zero(noise, zero, (size_t)B * nz * P.nd, st));
+  return conv_encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, st);
 }
 
-int conv_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace,
+int conv_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace,
                       size_t wsf, float* out0, hipStream_t st, float*) {
-  const ConvLayout P(d);
-  const ConvPacked K(P);
-  Bump ws(workspace, wsf);
-  ConvWs W;
-  carve(P, ws, R, 1, 2, W);
+  ConvEntry entry(d, workspace, wsf, R, 1, 2);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "conv_model_decode: workspace too small");
   ARDAE_TRY(conv_decode_fwd(P, K, params, packed, z, R, W, st));
   ARDAE_TRY(launch_copy(W.logit, (size_t)R * 784, out0, st));
   return 0;
 }
 
-int conv_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
+int conv_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                            int nz, float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  const ConvLayout P(d);
-  const ConvPacked K(P);
-  Bump ws(workspace, wsf);
-  ConvWs W;
-  carve(P, ws, B, nz, 1, W);
+  ConvEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "conv_model_vae_forward: workspace too small");
   const int R = B * nz;
   ARDAE_TRY(conv_encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, st));
@@ -361,25 +308,20 @@ int conv_model_vae_forward(const ardae_model_desc& d, const float* params, const
   return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
 }
 
-int conv_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
+int conv_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                             int nz, float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
                             float grads_beta, hipStream_t st) {
-  const ConvLayout P(d);
-  const ConvPacked K(P);
-  Bump ws(workspace, wsf);
-  ConvWs W;
-  carve(P, ws, B, nz, 1, W);
+  ConvEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   const int R = B * nz, act = P.act;
   const float gscale = dloss / (float)R;
   ARDAE_TRY(launch_vae_loss(0, W.logit, nullptr, x, W.z, R, nz, 784, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.dlogit, nullptr,
                             W.dzq, st));
   ARDAE_TRY(conv_decoder_bwd(P, K, packed, W, R, st));
   // ---- sampler backward
-  { LinArgs A{}; A.S = W.t1; A.ldS = 800; A.Y = W.dt1; A.ldY = 800;
-    ARDAE_TRY(lin1(EPI_DACT, act, R, 800, W.dz, P.zd, P.zd, packed + K.fc5_b, A, st)); }
+  ARDAE_TRY(dense_bwd(act, R, 800, W.dz, P.zd, packed + K.fc5_b, W.t1, W.dt1, st));
   ARDAE_TRY(launch_segment_sum(W.dt1, 800, B, nz, 800, 1.0f, W.drb, 800, st));
-  { LinArgs A{}; A.Y = W.dinp; A.ldY = 512;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 512, W.drb, 800, 800, packed + K.fc4i_b, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.drb, 800, 800, packed + K.fc4i_b, nullptr, W.dinp, st));
   ARDAE_TRY(trunk_bwd(K.conv_b, packed, W.dinp, W.dinp_t, W.hcv, W.dh3, W.dcols3, W.dh2, W.dcols2, W.dh1, B, act, st));
   // ---- weight gradients: one batched launch
   WgradList wl(grads, grads_beta);
@@ -396,8 +338,6 @@ int conv_model_vae_backward(const ardae_model_desc& d, const float* params, cons
 //   per sample:  z0 = mu0[b] + exp(lv0[b]/2) eps0;  h4 = act(Fn z0 + rb[b]);  mu = M h4 + m; lv = L h4 + l;  z = mu + exp(lv/2) eps
 // Noise layout as for kind 3: one [R, noise_dim + z_dim] tensor per sampler call.  hidden1a context = cat(h4a, h4) [B, 1600].
 // =====================================================================================================================
-namespace {
-
 struct AuxConvLayout {
   int nd, zd, act;
   Lin aconv[3], afc, mean0, logvar0, econv[3], efc, mean, logvar;
@@ -441,7 +381,7 @@ struct AuxConvWs {
   float *dh3[2], *dcols3[2], *dh2[2], *dcols2[2], *dh1[2];    // [0] = aux trunk, [1] = encoder trunk
 };
 
-void aux_carve(const AuxConvLayout& P, Bump& ws, int B, int nz, int mode, AuxConvWs& W) {
+void carve(const AuxConvLayout& P, const AuxConvPacked&, Bump& ws, int B, int nz, int mode, AuxConvWs& W) {
   const size_t R = (size_t)B * nz;
   ConvWs& D = W.D;
   D.x2 = ws.take((size_t)B * 784);
@@ -472,6 +412,7 @@ void aux_carve(const AuxConvLayout& P, Bump& ws, int B, int nz, int mode, AuxCon
     W.dcols2[k] = ws.take((size_t)B * 49 * 400); W.dh1[k] = ws.take((size_t)B * 196 * 16);
   }
 }
+using AuxConvEntry = Entry<AuxConvLayout, AuxConvPacked, AuxConvWs>;
 
 // wgrad_splits hint of the hierarchical conv backward, and the size of its first batch: the 21 problems go out as 10 + 11
 constexpr int AUX_WGRAD_HINT = 10;
@@ -499,7 +440,7 @@ void auxconv_wgrads(const AuxConvLayout& P, const AuxConvWs& W, int B, int R, Wg
 size_t aux_workspace(const AuxConvLayout& P, int B, int nz, int mode) {
   Bump ws;
   AuxConvWs W;
-  aux_carve(P, ws, B, nz, mode, W);
+  carve(P, AuxConvPacked(P), ws, B, nz, mode, W);
   if (mode == 1) {
     WgradList wl(nullptr);
     auxconv_wgrads(P, W, B, B * nz, wl, ws);
@@ -513,16 +454,12 @@ int aux_sampler_fwd(const AuxConvLayout& P, const AuxConvPacked& K, const float*
   const int R = B * nz, act = P.act, ldn = P.nd + P.zd;
   ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.D.x2, st));
   ARDAE_TRY(trunk_fwd(P.aconv, K.aconv_f, params, packed, W.D.x2, W.acols, W.ahcv, W.ainp, B, act, st));
-  { LinArgs A{}; A.bias = params + P.afc.b; A.Y = W.h4a; A.ldY = 800;
-    ARDAE_TRY(lin1(EPI_ACT, act, B, 800, W.ainp, 512, 512, packed + K.afc_f, A, st)); }
-  { LinArgs A{}; A.bias = params + P.mean0.b; A.Y = W.mu0; A.ldY = P.nd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.mean0_f, A, st)); }
-  { LinArgs A{}; A.bias = params + P.logvar0.b; A.Y = W.lv0; A.ldY = P.nd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.logvar0_f, A, st)); }
+  ARDAE_TRY(dense_fwd(act, B, 800, W.ainp, 512, 512, packed + K.afc_f, params + P.afc.b, W.h4a, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.mean0_f, params + P.mean0.b, W.mu0, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.logvar0_f, params + P.logvar0.b, W.lv0, st));
   ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, noise, ldn, R, P.nd, nz, W.z0, st));
   ARDAE_TRY(trunk_fwd(P.econv, K.econv_f, params, packed, W.D.x2, W.ecols, W.ehcv, W.einp, B, act, st));
-  { LinArgs A{}; A.bias = params + P.efc.b; A.Y = W.rb; A.ldY = 800;               // image half of the encoder's fc, once per image
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 800, W.einp, 512, 512, packed + K.efci_f, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.einp, 512, 512, packed + K.efci_f, params + P.efc.b, W.rb, st));   // image half of the encoder's fc, once per image
   if (!keep_hidden) {    // z0 -> 800 -> (mean | logvar) in one launch, hidden rows on chip (linear_shortk.hip::sampler_tail_kernel)
     LinArgs A{}; A.M = R; A.Nout = 800; A.act = act; A.nsrc = 1; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz;
     A.src[0].x = W.z0; A.src[0].ld = P.nd; A.src[0].K = P.nd; A.src[0].wp = packed + K.efcn_f;
@@ -533,43 +470,20 @@ int aux_sampler_fwd(const AuxConvLayout& P, const AuxConvPacked& K, const float*
   }
   { LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.D.t1; A.ldY = 800;
     ARDAE_TRY(lin1(EPI_ACT, act, R, 800, W.z0, P.nd, P.nd, packed + K.efcn_f, A, st)); }
-  { LinArgs A{}; A.bias = params + P.mean.b; A.Y = W.mu; A.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.D.t1, 800, 800, packed + K.mean_f, A, st)); }
-  { LinArgs A{}; A.bias = params + P.logvar.b; A.Y = W.lv; A.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.D.t1, 800, 800, packed + K.logvar_f, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.D.t1, 800, 800, packed + K.mean_f, params + P.mean.b, W.mu, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.D.t1, 800, 800, packed + K.logvar_f, params + P.logvar.b, W.lv, st));
   return launch_reparam_fwd(W.mu, W.lv, noise + P.nd, ldn, R, P.zd, 1, W.D.z, st);
 }
 
-}  // namespace
+size_t auxconv_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return aux_workspace(AuxConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
 
-size_t auxconv_model_param_floats(const ardae_model_desc& d) { return AuxConvLayout(d).total; }
-size_t auxconv_model_packed_floats(const ardae_model_desc& d) {
-  PackList pl;
-  AuxConvPacked(AuxConvLayout(d), pl);
-  return pl.total();
-}
-size_t auxconv_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return aux_workspace(AuxConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
-
-int auxconv_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  PackList pl(params, packed);
-  AuxConvPacked(AuxConvLayout(d), pl);
-  return pl.launch(st);
-}
-
-int auxconv_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+int auxconv_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                          float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
-  const AuxConvLayout P(d);
-  const AuxConvPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxConvWs W;
-  aux_carve(P, ws, B, nz, 0, W);
+  AuxConvEntry entry(d, workspace, wsf, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "auxconv_model_encode: workspace too small");
-  const float* nptr = noise;
-  if (!noise) {
-    ARDAE_TRY(launch_fill(W.zero, (size_t)B * nz * (P.nd + P.zd), 0.f, st));
-    nptr = W.zero;
-  }
-  ARDAE_TRY(aux_sampler_fwd(P, K, params, packed, x, nptr, B, nz, W, hidden_out != nullptr, st));
+  ARDAE_TRY(noise_or_zero(noise, W.zero, (size_t)B * nz * (P.nd + P.zd), st));
+  ARDAE_TRY(aux_sampler_fwd(P, K, params, packed, x, noise, B, nz, W, hidden_out != nullptr, st));
   if (z_out) ARDAE_TRY(launch_copy(W.D.z, (size_t)B * nz * P.zd, z_out, st));
   if (hidden_out) {
     ARDAE_CHECK_ARG(nz == 1, "auxconv_model_encode: the hidden context is defined for nz == 1");
@@ -579,26 +493,20 @@ int auxconv_model_encode(const ardae_model_desc& d, const float* params, const f
   return 0;
 }
 
-int auxconv_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
+int auxconv_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
                          float* out0, hipStream_t st, float*) {
-  const AuxConvLayout P(d);
-  const AuxConvPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxConvWs W;
-  aux_carve(P, ws, R, 1, 2, W);
+  AuxConvEntry entry(d, workspace, wsf, R, 1, 2);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "auxconv_model_decode: workspace too small");
   ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, z, R, W.D, st));
   ARDAE_TRY(launch_copy(W.D.logit, (size_t)R * 784, out0, st));
   return 0;
 }
 
-int auxconv_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
+int auxconv_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                               int nz, float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  const AuxConvLayout P(d);
-  const AuxConvPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxConvWs W;
-  aux_carve(P, ws, B, nz, 1, W);
+  AuxConvEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "auxconv_model_vae_forward: workspace too small");
   const int R = B * nz;
   ARDAE_TRY(aux_sampler_fwd(P, K, params, packed, x, noise, B, nz, W, true, st));
@@ -608,15 +516,12 @@ int auxconv_model_vae_forward(const ardae_model_desc& d, const float* params, co
   return launch_vae_loss_finalize(W.D.rec_row, W.D.pri_row, R, beta, losses, st);
 }
 
-int auxconv_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
+int auxconv_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
                                int nz, float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
                                float grads_beta, hipStream_t st) {
   (void)noise;
-  const AuxConvLayout P(d);
-  const AuxConvPacked K(P);
-  Bump ws(workspace, wsf);
-  AuxConvWs W;
-  aux_carve(P, ws, B, nz, 1, W);
+  AuxConvEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ConvWs& D = W.D;
   const int R = B * nz, act = P.act;
   const float gscale = dloss / (float)R;
@@ -624,30 +529,17 @@ int auxconv_model_vae_backward(const ardae_model_desc& d, const float* params, c
   ARDAE_TRY(conv_decoder_bwd(P.dec, K.dec, packed, D, R, st));
   // second reparameterisation and the encoder's fc
   ARDAE_TRY(launch_reparam_bwd(D.dz, D.z, W.mu, R, P.zd, 1, W.dlv, st));
-  {
-    LinArgs A{}; A.M = R; A.Nout = 800; A.nsrc = 2; A.act = act; A.S = D.t1; A.ldS = 800; A.Y = W.dt1; A.ldY = 800;
-    A.src[0].x = D.dz; A.src[0].ld = P.zd; A.src[0].K = P.zd; A.src[0].wp = packed + K.mean_b;
-    A.src[1].x = W.dlv; A.src[1].ld = P.zd; A.src[1].K = P.zd; A.src[1].wp = packed + K.logvar_b;
-    ARDAE_TRY(launch_linear(A, EPI_DACT, st));
-  }
-  { LinArgs A{}; A.Y = W.dz0; A.ldY = P.nd;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.nd, W.dt1, 800, 800, packed + K.efcn_b, A, st)); }
+  ARDAE_TRY(dense_bwd2(act, R, 800, D.dz, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, D.t1, W.dt1, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, W.dt1, 800, 800, packed + K.efcn_b, nullptr, W.dz0, st));
   ARDAE_TRY(launch_segment_sum(W.dt1, 800, B, nz, 800, 1.0f, W.drb, 800, st));
-  { LinArgs A{}; A.Y = W.dinp_e; A.ldY = 512;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 512, W.drb, 800, 800, packed + K.efci_b, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.drb, 800, 800, packed + K.efci_b, nullptr, W.dinp_e, st));
   ARDAE_TRY(trunk_bwd(K.econv_b, packed, W.dinp_e, W.dinp_t, W.ehcv, W.dh3[1], W.dcols3[1], W.dh2[1], W.dcols2[1], W.dh1[1], B, act, st));
   // first reparameterisation, reduced over the nz samples of each image, and the aux encoder
   ARDAE_TRY(launch_reparam_bwd(W.dz0, W.z0, W.mu0, R, P.nd, nz, W.dlv0r, st));
   ARDAE_TRY(launch_segment_sum(W.dz0, P.nd, B, nz, P.nd, 1.0f, W.dmu0, P.nd, st));
   ARDAE_TRY(launch_segment_sum(W.dlv0r, P.nd, B, nz, P.nd, 1.0f, W.dlv0, P.nd, st));
-  {
-    LinArgs A{}; A.M = B; A.Nout = 800; A.nsrc = 2; A.act = act; A.S = W.h4a; A.ldS = 800; A.Y = W.dh4a; A.ldY = 800;
-    A.src[0].x = W.dmu0; A.src[0].ld = P.nd; A.src[0].K = P.nd; A.src[0].wp = packed + K.mean0_b;
-    A.src[1].x = W.dlv0; A.src[1].ld = P.nd; A.src[1].K = P.nd; A.src[1].wp = packed + K.logvar0_b;
-    ARDAE_TRY(launch_linear(A, EPI_DACT, st));
-  }
-  { LinArgs A{}; A.Y = W.dinp_a; A.ldY = 512;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, A, st)); }
+  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.dinp_a, st));
   ARDAE_TRY(trunk_bwd(K.aconv_b, packed, W.dinp_a, W.dinp_t, W.ahcv, W.dh3[0], W.dcols3[0], W.dh2[0], W.dcols2[0], W.dh1[0], B, act, st));
   // ---- weight gradients, launched as two batches
   WgradList wl(grads, grads_beta);
@@ -656,5 +548,15 @@ int auxconv_model_vae_backward(const ardae_model_desc& d, const float* params, c
   ARDAE_TRY(wl.launch(st, AUX_WGRAD_HINT));
   return wl.launch(st);
 }
+
+}  // namespace
+
+// (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
+#ifndef __HIP_DEVICE_COMPILE__
+const Family CONV_FAMILY = {family_param_floats<ConvLayout, ConvPacked>, family_packed_floats<ConvLayout, ConvPacked>, conv_workspace_floats,
+                            family_pack<ConvLayout, ConvPacked>, conv_encode, conv_decode, conv_vae_forward, conv_vae_backward};
+const Family AUXCONV_FAMILY = {family_param_floats<AuxConvLayout, AuxConvPacked>, family_packed_floats<AuxConvLayout, AuxConvPacked>, auxconv_workspace_floats,
+                               family_pack<AuxConvLayout, AuxConvPacked>, auxconv_encode, auxconv_decode, auxconv_vae_forward, auxconv_vae_backward};
+#endif
 
 }  // namespace ardae

@@ -1,12 +1,15 @@
 // Host-side helpers shared by the model families (model / convmodel / auxmodel / resmodel .hip) and cdae.hip: the bump
-// allocator that carves a workspace arena, one-/two-source linear launches, and the list of weight-gradient problems a
-// backward pass hands to launch_wgrad_batch, and the list of weight panels a network's packed buffer is made of.
+// allocator that carves a workspace arena, one-/two-source linear launches and the dense-layer calls written with them, the
+// list of weight-gradient problems a backward pass hands to launch_wgrad_batch, the list of weight panels a network's packed
+// buffer is made of, and what every model family is made of (the Family table row, its sizing / pack triple, the prologue of
+// an entry point).
 #pragma once
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "common.h"
+#include "elementwise.h"
 #include "linear.h"
 #include "wgrad.h"
 
@@ -40,6 +43,25 @@ inline int lin2(int epi, int act, int M, int Nout, const float* x0, int ld0, int
   a.src[0].x = x0; a.src[0].ld = ld0; a.src[0].K = K0; a.src[0].wp = wp0;
   a.src[1].x = x1; a.src[1].ld = ld1; a.src[1].K = K1; a.src[1].wp = wp1;
   return launch_linear(a, epi, st);
+}
+
+// The dense layers of the model families (wp: the packed panel of the operator; every buffer is dense, ld = its column count):
+//   y [M, n] = act(x [M, K] W^T + bias)   (bias null: none - with ACT_NONE also the backward-data product g W of a layer
+//   whose input has no activation in front)
+inline int dense_fwd(int act, int M, int n, const float* x, int ldx, int K, const float* wp, const float* bias, float* y, hipStream_t st) {
+  LinArgs A{}; A.bias = bias; A.Y = y; A.ldY = n;
+  return lin1(EPI_ACT, act, M, n, x, ldx, K, wp, A, st);
+}
+//   y [M, n] = (g [M, K] W) (.) act'(S) (+ Q)   (S: the saved post-activation [M, n]; with ACT_NONE act' == 1 and S is only a placeholder)
+inline int dense_bwd(int act, int M, int n, const float* g, int K, const float* wp, const float* S, float* y, hipStream_t st, const float* Q = nullptr) {
+  LinArgs A{}; A.S = S; A.ldS = n; A.Q = Q; A.ldQ = Q ? n : 0; A.Y = y; A.ldY = n;
+  return lin1(EPI_DACT, act, M, n, g, K, K, wp, A, st);
+}
+//   y [M, n] = (g0 [M, K] W0 + g1 [M, K] W1) (.) act'(S): two heads back into the layer both read
+inline int dense_bwd2(int act, int M, int n, const float* g0, const float* wp0, const float* g1, const float* wp1, int K, const float* S, float* y,
+                      hipStream_t st) {
+  LinArgs A{}; A.S = S; A.ldS = n; A.Y = y; A.ldY = n;
+  return lin2(EPI_DACT, act, M, n, g0, K, K, wp0, g1, K, K, wp1, A, st);
 }
 
 // A Linear in the flat parameter buffer: weight [out, in] at w, bias at b (offsets in floats)
@@ -142,6 +164,56 @@ struct WgradList {
       next += m;
     }
     return 0;
+  }
+};
+
+// the caller's noise, or (null: a std = 0 pass, the reference multiplies its draw by 0) the n floats at `zero`, filled with zeros
+inline int noise_or_zero(const float*& noise, float* zero, size_t n, hipStream_t st) {
+  if (noise) return 0;
+  noise = zero;
+  return launch_fill(zero, (int64_t)n, 0.f, st);
+}
+
+// ------------------------------------------------------------------------------------------------ the model families
+// One row of csrc/model.hip's table by kind (encode: hidden_out / raw0 and decode: out1 are NULL for the families that have no
+// such output / input).  Each family file defines its own.
+struct Family {
+  size_t (*param_floats)(const ardae_model_desc&);
+  size_t (*packed_floats)(const ardae_model_desc&);
+  size_t (*workspace_floats)(const ardae_model_desc&, int B, int nz, int mode);   // mode 2: decode only, 3: encode_pair
+  int (*pack)(const ardae_model_desc&, const float* params, float* packed, hipStream_t);
+  int (*encode)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t, const float* raw0);
+  int (*decode)(const ardae_model_desc&, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
+                float* out0, hipStream_t, float* out1);
+  int (*vae_forward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                     float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
+  int (*vae_backward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                      float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
+};
+
+// A family is a Layout (the Linears' offsets in the flat parameter buffer, from the desc) and a Packed (the panels' offsets in the
+// packed buffer, reserved on a PackList).  Where the pack launch is all a family's pack does, these three are its first members:
+template <class Layout, class Packed> size_t family_param_floats(const ardae_model_desc& d) { return Layout(d).total; }
+template <class Layout, class Packed> size_t family_packed_floats(const ardae_model_desc& d) {
+  const Layout P(d);
+  PackList pl;
+  const Packed K(P, pl);
+  return pl.total();
+}
+template <class Layout, class Packed> int family_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
+  const Layout P(d);
+  PackList pl(params, packed);
+  const Packed K(P, pl);
+  return pl.launch(st);
+}
+
+// What every entry point opens with: the layout, the panel offsets, the arena, and the buffers the family's carve(P, ws, ..., W)
+// takes out of it.  `auto& [P, K, ws, W] = entry;` names them.
+template <class Layout, class Packed, class Ws> struct Entry {
+  const Layout P; const Packed K; Bump ws; Ws W;
+  template <class... CarveArgs> Entry(const ardae_model_desc& d, float* workspace, size_t wsf, CarveArgs... args) : P(d), K(P), ws(workspace, wsf) {
+    carve(P, K, ws, args..., W);
   }
 };
 

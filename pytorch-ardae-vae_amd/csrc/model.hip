@@ -16,7 +16,7 @@
 #include "convmodel.h"
 #include "resmodel.h"
 #include "elementwise.h"
-#include "host_util.h"
+#include "mlp.h"
 
 namespace ardae {
 namespace {
@@ -49,13 +49,10 @@ struct ModelLayout {
 
 // offsets into the packed buffer, reserved (and, over a real PackList, filled) in this order
 struct ModelPacked {
-  std::vector<size_t> inp_f, inp_b, sh_f, sh_b, sn_f, dec_f, dec_b, head_f, head_b;
-  ModelPacked(const ModelLayout& P, PackList& pl) {
-    auto pairs = [&](const std::vector<Lin>& v, std::vector<size_t>& f, std::vector<size_t>& b) {
-      f.resize(v.size()); b.resize(v.size());
-      for (size_t i = 0; i < v.size(); ++i) pl.pair(v[i], f[i], b[i]);
-    };
-    pairs(P.inp, inp_f, inp_b);
+  MlpStack inp;
+  std::vector<size_t> sh_f, sh_b, sn_f;
+  MlpDecoder dec;
+  ModelPacked(const ModelLayout& P, PackList& pl) : inp(P.inp.data(), P.inp.size(), pl) {
     const size_t ns = P.stack.size();
     sh_f.resize(ns); sh_b.resize(ns); sn_f.assign(ns, 0);
     for (size_t i = 0; i < ns; ++i) {           // [out, h | nd]: hidden columns both ways, noise columns forward
@@ -63,8 +60,7 @@ struct ModelPacked {
       pl.pair(l, sh_f[i], sh_b[i], 0, P.h);
       if (P.stack_noise[i]) sn_f[i] = pl.panel(l.w + P.h, l.in, l.out, P.nd, false);
     }
-    pairs(P.dec, dec_f, dec_b);
-    pairs(P.heads, head_f, head_b);
+    dec = MlpDecoder(P.dec.data(), P.dec.size(), P.heads.data(), (int)P.heads.size(), pl);
   }
   explicit ModelPacked(const ModelLayout& P, PackList&& sizing = PackList()) : ModelPacked(P, sizing) {}   // offsets only
 };
@@ -103,68 +99,56 @@ struct ModelWs {
   float* rb;                // per-image part of the first stack layer (+ its bias) [B,h]
   std::vector<float*> t;    // t[i], i = 1..n_stack-1    [R,h]
   float* z;                 // sampler output            [R,zd]
-  std::vector<float*> dcd;  // dcd[l], l = 1..n_dec      [R,h]
-  std::vector<float*> o;    // heads                     [R,D]
+  MlpDecoder::Bufs D;       // the decoder's, forward and backward
   float *rec_row, *pri_row;
   // backward only
-  std::vector<float*> dox, ddec, dt, de;
-  float *dzq, *dz, *drb;
+  std::vector<float*> dt, de;
+  float* drb;
 };
 
-void carve(const ModelLayout& P, Bump& ws, int B, int nz, int mode, ModelWs& W) {
+void carve(const ModelLayout& P, const ModelPacked& K, Bump& ws, int B, int nz, int mode, ModelWs& W) {
   const size_t R = (size_t)B * nz, h = P.h;
   W.x2 = ws.take((size_t)B * P.D);
-  W.e.assign(P.inp.size() + 1, nullptr);
-  for (size_t l = 1; l <= P.inp.size(); ++l) W.e[l] = ws.take((size_t)B * h);
+  K.inp.carve(ws, B, W.e);
   W.rb = ws.take((size_t)B * h);
   W.t.assign(P.stack.size(), nullptr);
   for (size_t i = 1; i < P.stack.size(); ++i) W.t[i] = ws.take(R * h);
   W.z = ws.take(R * P.zd);
   if (mode == 0) return;
-  W.dcd.assign(P.dec.size() + 1, nullptr);
-  for (size_t l = 1; l <= P.dec.size(); ++l) W.dcd[l] = ws.take(R * h);
-  for (size_t k = 0; k < P.heads.size(); ++k) W.o.push_back(ws.take(R * P.D));
+  K.dec.carve(ws, R, true, W.D);
   W.rec_row = ws.take(R); W.pri_row = ws.take(R);
-  for (size_t k = 0; k < P.heads.size(); ++k) W.dox.push_back(ws.take(R * P.D));
-  W.ddec.assign(P.dec.size() + 1, nullptr);
-  for (size_t l = 1; l <= P.dec.size(); ++l) W.ddec[l] = ws.take(R * h);
   W.dt.assign(P.stack.size(), nullptr);
   for (size_t i = 1; i < P.stack.size(); ++i) W.dt[i] = ws.take(R * h);
-  W.de.assign(P.inp.size() + 1, nullptr);
-  for (size_t l = 1; l <= P.inp.size(); ++l) W.de[l] = ws.take((size_t)B * h);
-  W.dzq = ws.take(R * P.zd); W.dz = ws.take(R * P.zd); W.drb = ws.take((size_t)B * h);
+  K.inp.carve(ws, B, W.de);
+  W.drb = ws.take((size_t)B * h);
 }
+using MlpEntry = Entry<ModelLayout, ModelPacked, ModelWs>;
 
 // every weight-gradient problem of the backward, with its scratch taken from ws (x: the images; noise: the sampler's draw)
-void model_wgrads(const ModelLayout& P, const ModelWs& W, const float* x, const float* noise, int B, int R, WgradList& wl, Bump& ws) {
+void model_wgrads(const ModelLayout& P, const ModelPacked& K, const ModelWs& W, const float* x, const float* noise, int B, int R, WgradList& wl, Bump& ws) {
   const int h = P.h;
-  const size_t ns = P.stack.size(), ndec = P.dec.size(), ninp = P.inp.size(), nh = P.heads.size();
-  const float* x_in = P.kind == 0 ? W.x2 : x;
-  for (size_t k = 0; k < nh; ++k) wl.push(R, P.D, h, W.dox[k], W.dcd[ndec], h, wl.g(P.heads[k].w), h, wl.g(P.heads[k].b));
-  for (size_t l = 1; l <= ndec; ++l)
-    wl.push(R, h, P.dec[l - 1].in, W.ddec[l], l == 1 ? W.z : W.dcd[l - 1], l == 1 ? P.zd : h, wl.g(P.dec[l - 1].w), P.dec[l - 1].in,
-            wl.g(P.dec[l - 1].b));
+  const size_t ns = P.stack.size();
+  K.dec.wgrads(wl, R, W.z, W.D);
   for (size_t i = 0; i < ns; ++i) {
     const Lin& L = P.stack[i];
-    const float* G = (i == ns - 1) ? W.dz : W.dt[i + 1];
-    if (i == 0) wl.push(B, L.out, h, W.drb, W.e[ninp], h, wl.g(L.w), L.in, nullptr);        // per-image hidden part
+    const float* G = (i == ns - 1) ? W.D.dz : W.dt[i + 1];
+    if (i == 0) wl.push(B, L.out, h, W.drb, W.e[P.inp.size()], h, wl.g(L.w), L.in, nullptr);        // per-image hidden part
     else wl.push(R, L.out, h, G, W.t[i], h, wl.g(L.w), L.in, P.stack_noise[i] ? nullptr : wl.g(L.b));
     if (P.stack_noise[i]) wl.push(R, L.out, P.nd, G, noise, P.nd, wl.g(L.w + h), L.in, wl.g(L.b));   // noise part (+ bias)
   }
-  for (size_t l = 1; l <= ninp; ++l)
-    wl.push(B, h, P.inp[l - 1].in, W.de[l], l == 1 ? x_in : W.e[l - 1], l == 1 ? P.D : h, wl.g(P.inp[l - 1].w), P.inp[l - 1].in,
-            wl.g(P.inp[l - 1].b));
-  wl.assign(ws, (int)(nh + ndec + 2 * ns + ninp));   // the hint counts a noise part for every stack layer
+  K.inp.wgrads(wl, B, P.kind == 0 ? W.x2 : x, W.e.data(), W.de.data());
+  wl.assign(ws, (int)(P.heads.size() + P.dec.size() + 2 * ns + P.inp.size()));   // the hint counts a noise part for every stack layer
 }
 
 // dry run of carve() and the weight-gradient list on a null arena (mode 0: the sampler's buffers only)
 size_t workspace_floats(const ModelLayout& P, int B, int nz, int mode) {
+  const ModelPacked K(P);
   Bump ws;
   ModelWs W;
-  carve(P, ws, B, nz, mode, W);
+  carve(P, K, ws, B, nz, mode, W);
   if (mode != 0) {
     WgradList wl(nullptr);
-    model_wgrads(P, W, nullptr, nullptr, B, B * nz, wl, ws);
+    model_wgrads(P, K, W, nullptr, nullptr, B, B * nz, wl, ws);
   }
   return ws.off;
 }
@@ -172,18 +156,14 @@ size_t workspace_floats(const ModelLayout& P, int B, int nz, int mode) {
 // sampler trunk (once per image): inp_encode on B rows, then rb = inp . S_1[:, :h]^T + b_S1.  Fills W.e, W.rb.
 int encode_trunk(const ModelLayout& P, const ModelPacked& K, const float* params, const float* packed, const float* x, int B,
                  ModelWs& W, hipStream_t st) {
-  const int h = P.h, act = P.act;
+  const int h = P.h;
   const float* x_in = x;
   if (P.kind == 0) {
     ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.x2, st));
     x_in = W.x2;
   }
-  for (size_t l = 1; l <= P.inp.size(); ++l) {
-    LinArgs A{}; A.bias = params + P.inp[l - 1].b; A.Y = W.e[l]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, act, B, h, l == 1 ? x_in : W.e[l - 1], l == 1 ? P.D : h, P.inp[l - 1].in, packed + K.inp_f[l - 1], A, st));
-  }
-  LinArgs A{}; A.bias = params + P.stack[0].b; A.Y = W.rb; A.ldY = h;
-  return lin1(EPI_ACT, ACT_NONE, B, P.stack[0].out, W.e[P.inp.size()], h, h, packed + K.sh_f[0], A, st);
+  ARDAE_TRY(K.inp.fwd(params, packed, P.act, B, x_in, W.e.data(), st));
+  return dense_fwd(ACT_NONE, B, h, W.e[P.inp.size()], h, h, packed + K.sh_f[0], params + P.stack[0].b, W.rb, st);
 }
 
 // sampler stack on R = B*nz rows: layer 0 takes the per-image rb plus its noise part, the last layer writes zdst [R, zd]
@@ -239,81 +219,32 @@ size_t encode_pair_extra(const ModelLayout& P, int B) {
 }
 
 // ------------------------------------------------------------------------------------------------ kinds 0 / 1 as a family
-size_t mlp_param_floats(const ardae_model_desc& d) { return ModelLayout(d).total; }
-size_t mlp_packed_floats(const ardae_model_desc& d) {
-  PackList pl;
-  ModelPacked(ModelLayout(d), pl);
-  return pl.total();
-}
 size_t mlp_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   const ModelLayout P(d);
-  if (mode == 2) return P.dec.size() * al64((size_t)B * nz * P.h);
+  if (mode == 2) return ModelPacked(P).dec.decode_floats((size_t)B * nz);
   if (mode == 3) return workspace_floats(P, B, nz, 0) + encode_pair_extra(P, B);   // ardae_model_encode_pair
   return workspace_floats(P, B, nz, mode) + (size_t)al64((size_t)B * nz * P.nd);   // + a zero-noise buffer for encode(std=0)
 }
 
-int mlp_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  PackList pl(params, packed);
-  ModelPacked(ModelLayout(d), pl);
-  return pl.launch(st);
-}
-
 int mlp_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                float* workspace, size_t wsf, float* z_out, float*, hipStream_t st, const float*) {
-  const ModelLayout P(d);
-  const ModelPacked K(P);
-  Bump ws(workspace, wsf);
-  ModelWs W;
-  carve(P, ws, B, nz, 0, W);
-  const float* nz_ptr = noise;
-  if (!noise) {   // encode(x, std=0): the reference multiplies its draw by 0
-    float* zero = ws.take((size_t)B * nz * P.nd);
-    ARDAE_TRY(launch_fill(zero, (size_t)B * nz * P.nd, 0.f, st));
-    nz_ptr = zero;
-  }
+  MlpEntry entry(d, workspace, wsf, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
+  float* zero = noise ? nullptr : ws.take((size_t)B * nz * P.nd);
   ARDAE_CHECK_ARG(ws.ok, "model_encode: internal workspace accounting error");
-  return encode_fwd(P, K, params, packed, x, nz_ptr, B, nz, W, z_out, false, st);
-}
-
-// decoder on R rows: the hidden layers into hid[1 .. n_dec], then the head(s) into out[0] (, out[1])
-int decoder_fwd(const ModelLayout& P, const ModelPacked& K, const float* params, const float* packed, const float* z, int R, float* const* hid,
-                float* const* out, hipStream_t st) {
-  const int h = P.h;
-  for (size_t l = 1; l <= P.dec.size(); ++l) {
-    LinArgs A{}; A.bias = params + P.dec[l - 1].b; A.Y = hid[l]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_ACT, P.act, R, h, l == 1 ? z : hid[l - 1], l == 1 ? P.zd : h, P.dec[l - 1].in, packed + K.dec_f[l - 1], A, st));
-  }
-  for (size_t k = 0; k < P.heads.size(); ++k) {
-    LinArgs A{}; A.bias = params + P.heads[k].b; A.Y = out[k]; A.ldY = P.D;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.D, hid[P.dec.size()], h, h, packed + K.head_f[k], A, st));
-  }
-  return 0;
-}
-
-int mlp_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-               float* out0, hipStream_t st, float* out1) {
-  const ModelLayout P(d);
-  const ModelPacked K(P);
-  Bump ws(workspace, wsf);
-  std::vector<float*> hid(P.dec.size() + 1, nullptr);
-  for (size_t l = 1; l <= P.dec.size(); ++l) hid[l] = ws.take((size_t)R * P.h);
-  float* const out[2] = {out0, out1};
-  return decoder_fwd(P, K, params, packed, z, R, hid.data(), out, st);
+  ARDAE_TRY(noise_or_zero(noise, zero, (size_t)B * nz * P.nd, st));
+  return encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, false, st);
 }
 
 int mlp_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                     float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  const ModelLayout P(d);
-  const ModelPacked K(P);
-  Bump ws(workspace, wsf);
-  ModelWs W;
-  carve(P, ws, B, nz, 1, W);
+  MlpEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "model_vae_forward: internal workspace accounting error");
   const int R = B * nz;
   ARDAE_TRY(encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, true, st));
-  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, R, W.dcd.data(), W.o.data(), st));
-  ARDAE_TRY(launch_vae_loss(P.kind, W.o[0], P.kind == 1 ? W.o[1] : nullptr, x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row,
-                            W.pri_row, nullptr, nullptr, nullptr, st));
+  ARDAE_TRY(K.dec.fwd(params, packed, P.act, R, W.z, W.D.hid.data(), W.D.o, st));
+  ARDAE_TRY(launch_vae_loss(P.kind, W.D.o[0], W.D.o[1], x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
   return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
 }
 
@@ -323,53 +254,27 @@ int mlp_vae_forward(const ardae_model_desc& d, const float* params, const float*
 int vae_backward_impl(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise,
                       int B, int nz, float beta, float dloss, const float* dz_extra, float seed_scale, float* workspace,
                       size_t workspace_floats_, float* grads, float grads_beta, int phases, hipStream_t st) {
-  const ModelLayout P(d);
-  const ModelPacked K(P);
-  Bump ws(workspace, workspace_floats_);
-  ModelWs W;
-  carve(P, ws, B, nz, 1, W);
+  MlpEntry entry(d, workspace, workspace_floats_, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   const int R = B * nz, h = P.h, act = P.act;
-  const size_t ns = P.stack.size(), ndec = P.dec.size(), ninp = P.inp.size(), nh = P.heads.size();
+  const size_t ns = P.stack.size(), ninp = P.inp.size();
   const float gscale = dloss / (float)R;
   if (phases & 1) {
-  ARDAE_TRY(launch_vae_loss(P.kind, W.o[0], P.kind == 1 ? W.o[1] : nullptr, x, W.z, R, nz, P.D, P.zd, beta, 1, gscale,
-                            phases == 3 ? dz_extra : nullptr, W.rec_row, W.pri_row, W.dox[0], P.kind == 1 ? W.dox[1] : nullptr, W.dzq, st));
-  // decoder backward
-  {
-    LinArgs A{}; A.S = W.dcd[ndec]; A.ldS = h; A.Y = W.ddec[ndec]; A.ldY = h; A.M = R; A.Nout = h; A.act = act; A.nsrc = (int)nh;
-    for (size_t k = 0; k < nh; ++k) { A.src[k].x = W.dox[k]; A.src[k].ld = P.D; A.src[k].K = P.D; A.src[k].wp = packed + K.head_b[k]; }
-    ARDAE_TRY(launch_linear(A, EPI_DACT, st));
-  }
-  for (size_t l = ndec; l >= 2; --l) {
-    LinArgs A{}; A.S = W.dcd[l - 1]; A.ldS = h; A.Y = W.ddec[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, R, h, W.ddec[l], h, h, packed + K.dec_b[l - 1], A, st));
-  }
-  {  // dz = ddec_1 . D_1 + (prior + injected seed)      (act NONE: act' == 1, S is only a placeholder)
-    LinArgs A{}; A.S = W.dzq; A.ldS = P.zd; A.Q = W.dzq; A.ldQ = P.zd; A.Y = W.dz; A.ldY = P.zd;
-    ARDAE_TRY(lin1(EPI_DACT, ACT_NONE, R, P.zd, W.ddec[1], h, h, packed + K.dec_b[0], A, st));
-  }
+    ARDAE_TRY(launch_vae_loss(P.kind, W.D.o[0], W.D.o[1], x, W.z, R, nz, P.D, P.zd, beta, 1, gscale, phases == 3 ? dz_extra : nullptr, W.rec_row, W.pri_row,
+                              W.D.dox[0], W.D.dox[1], W.D.dzq, st));
+    ARDAE_TRY(K.dec.bwd(packed, act, R, W.D, st));
   }
   if (!(phases & 2)) return 0;
-  if (phases == 2 && dz_extra) ARDAE_TRY(launch_axpy(dz_extra, (int64_t)R * P.zd, seed_scale, W.dz, st));   // + the entropy seed
+  if (phases == 2 && dz_extra) ARDAE_TRY(launch_axpy(dz_extra, (int64_t)R * P.zd, seed_scale, W.D.dz, st));   // + the entropy seed
   // sampler backward
-  for (size_t i = ns - 1; i >= 1; --i) {
-    LinArgs A{}; A.S = W.t[i]; A.ldS = h; A.Y = W.dt[i]; A.ldY = h;
-    const float* src = (i == ns - 1) ? W.dz : W.dt[i + 1];
-    const int kk = P.stack[i].out;
-    ARDAE_TRY(lin1(EPI_DACT, act, R, h, src, kk, kk, packed + K.sh_b[i], A, st));
-  }
+  for (size_t i = ns - 1; i >= 1; --i)
+    ARDAE_TRY(dense_bwd(act, R, h, (i == ns - 1) ? W.D.dz : W.dt[i + 1], P.stack[i].out, packed + K.sh_b[i], W.t[i], W.dt[i], st));
   ARDAE_TRY(launch_segment_sum(W.dt[1], h, B, nz, h, 1.0f, W.drb, h, st));
-  {
-    LinArgs A{}; A.S = W.e[ninp]; A.ldS = h; A.Y = W.de[ninp]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, B, h, W.drb, h, h, packed + K.sh_b[0], A, st));
-  }
-  for (size_t l = ninp; l >= 2; --l) {
-    LinArgs A{}; A.S = W.e[l - 1]; A.ldS = h; A.Y = W.de[l - 1]; A.ldY = h;
-    ARDAE_TRY(lin1(EPI_DACT, act, B, h, W.de[l], h, h, packed + K.inp_b[l - 1], A, st));
-  }
+  ARDAE_TRY(dense_bwd(act, B, h, W.drb, h, packed + K.sh_b[0], W.e[ninp], W.de[ninp], st));
+  ARDAE_TRY(K.inp.bwd(packed, act, B, W.e.data(), W.de.data(), st));
   // weight gradients: one batched launch
   WgradList wl(grads, grads_beta);
-  model_wgrads(P, W, x, noise, B, R, wl, ws);
+  model_wgrads(P, K, W, x, noise, B, R, wl, ws);
   ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
   return wl.launch(st);
 }
@@ -380,34 +285,13 @@ int mlp_vae_backward(const ardae_model_desc& d, const float* params, const float
   return vae_backward_impl(d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, 1.f, workspace, wsf, grads, grads_beta, 3, st);
 }
 
+const Family MLP_FAMILY = {family_param_floats<ModelLayout, ModelPacked>, family_packed_floats<ModelLayout, ModelPacked>, mlp_workspace_floats,
+                           family_pack<ModelLayout, ModelPacked>, mlp_encode, mlp_decode<ModelLayout, ModelPacked>, mlp_vae_forward, mlp_vae_backward};
+
 // ------------------------------------------------------------------------------------------------ the families, by kind
-// (encode: hidden_out / raw0 and decode: out1 are NULL for the families that have no such output / input)
-struct Family {
-  size_t (*param_floats)(const ardae_model_desc&);
-  size_t (*packed_floats)(const ardae_model_desc&);
-  size_t (*workspace_floats)(const ardae_model_desc&, int B, int nz, int mode);   // mode 2: decode only, 3: encode_pair
-  int (*pack)(const ardae_model_desc&, const float* params, float* packed, hipStream_t);
-  int (*encode)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t, const float* raw0);
-  int (*decode)(const ardae_model_desc&, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                float* out0, hipStream_t, float* out1);
-  int (*vae_forward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
-  int (*vae_backward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                      float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
-};
-const Family MLP = {mlp_param_floats, mlp_packed_floats, mlp_workspace_floats, mlp_pack, mlp_encode, mlp_decode, mlp_vae_forward, mlp_vae_backward};
-const Family CONV = {conv_model_param_floats, conv_model_packed_floats, conv_model_workspace_floats, conv_model_pack, conv_model_encode,
-                     conv_model_decode, conv_model_vae_forward, conv_model_vae_backward};
-const Family AUX = {aux_model_param_floats, aux_model_packed_floats, aux_model_workspace_floats, aux_model_pack, aux_model_encode,
-                    aux_model_decode, aux_model_vae_forward, aux_model_vae_backward};
-const Family AUXCONV = {auxconv_model_param_floats, auxconv_model_packed_floats, auxconv_model_workspace_floats, auxconv_model_pack,
-                        auxconv_model_encode, auxconv_model_decode, auxconv_model_vae_forward, auxconv_model_vae_backward};
-const Family RES = {res_model_param_floats, res_model_packed_floats, res_model_workspace_floats, res_model_pack, res_model_encode,
-                    res_model_decode, res_model_vae_forward, res_model_vae_backward};
 // desc_ok() has checked the kind
 const Family& family(const ardae_model_desc* d) {
-  static const Family* const by_kind[8] = {&MLP, &MLP, &CONV, &AUX, &AUXCONV, &RES, &RES, &AUX};
+  static const Family* const by_kind[8] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY};
   return *by_kind[d->kind];
 }
 
@@ -462,11 +346,8 @@ int ardae_model_encode_pair(const ardae_model_desc* d, const float* params, cons
     return ardae_model_encode(d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, stream);
   }
   hipStream_t st = (hipStream_t)stream;
-  const ModelLayout P(*d);
-  const ModelPacked K(P);
-  Bump ws(workspace, workspace_floats_);
-  ModelWs W;
-  carve(P, ws, B, nz, 0, W);
+  MlpEntry entry(*d, workspace, workspace_floats_, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
   std::vector<float*> t0(P.stack.size(), nullptr);
   for (size_t i = 1; i < P.stack.size(); ++i) t0[i] = ws.take((size_t)B * P.h);
   float* zero = ws.take((size_t)B * P.nd);

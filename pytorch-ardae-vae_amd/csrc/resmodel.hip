@@ -18,8 +18,6 @@
 #include "ardae_hip.h"
 #include "auxmodel.h"
 #include "common.h"
-#include "elementwise.h"
-#include "host_util.h"
 #include "resmodel.h"
 
 namespace ardae {
@@ -318,7 +316,7 @@ struct ResPacked {
   std::vector<HeadPk> head;
   LinPk mu0, lv0, efc, mu, lv;
   ResPacked(const ResLayout& P, PackList& pl) {
-    // an operator's panels are packed from its effective weight: composed into the packed buffer at k.weff by res_model_pack's
+    // an operator's panels are packed from its effective weight: composed into the packed buffer at k.weff by res_pack's
     // compose launch (weight norm), or the parameter itself (plain nn.Linear operator, whose weff / inv stay unused)
     auto wn_panel = [&](const WN& w, const WNPk& k, int col0, int nout, int kk, bool tr) {
       return pl.panel((w.plain ? w.dir : k.weff) + col0, w.I, nout, kk, tr, !w.plain);
@@ -393,11 +391,8 @@ int blk_fwd(const Blk& b, const BlkPk& k, const float* params, const float* pack
     RES_LAUNCH(im2col3_kernel, (int64_t)R * b.a.I, x, b.Hin, b.Hin, b.Cin, b.Hout, b.Hout, b.stride, u.colsx, (int64_t)R * b.a.I);
     cx = u.colsx;
   }
-  {
-    LinArgs A{}; A.bias = params + b.a.bias; A.Y = u.hmid; A.ldY = b.Cout;
-    // conv blocks: ELU as the epilogue activation (their Cout <= 32 columns run on the generic kernel either way)
-    ARDAE_TRY(lin1(EPI_ACT, b.conv ? ACT_ELU : ACT_RELU, R, b.Cout, cx, b.a.I, b.a.I, packed + k.a.f, A, st));
-  }
+  // conv blocks: ELU as the epilogue activation (their Cout <= 32 columns run on the generic kernel either way)
+  ARDAE_TRY(dense_fwd(b.conv ? ACT_ELU : ACT_RELU, R, b.Cout, cx, b.a.I, b.a.I, packed + k.a.f, params + b.a.bias, u.hmid, st));
   const float* ch = u.hmid;
   if (b.conv) {
     RES_LAUNCH(im2col3_kernel, (int64_t)R * b.h.I, u.hmid, b.Hout, b.Hout, b.Cout, b.Hout, b.Hout, 1, u.colsh, (int64_t)R * b.h.I);
@@ -450,12 +445,10 @@ int blk_bwd(const Blk& b, const BlkPk& k, const float* packed, const float* x, i
   const float* ch = b.conv ? u.colsh : u.hmid;
   // d hmid
   if (b.conv) {
-    LinArgs A{}; A.Y = sc.dcols; A.ldY = b.h.I;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, b.h.I, g, b.Cout, b.Cout, packed + k.h.b, A, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, R, b.h.I, g, b.Cout, b.Cout, packed + k.h.b, nullptr, sc.dcols, st));
     RES_LAUNCH(col2im3_kernel, nout, sc.dcols, b.Hout, b.Hout, b.Cout, b.Hout, b.Hout, 1, sc.dh, nout, (const float*)u.hmid, (int)ACT_ELU);
   } else {
-    LinArgs A{}; A.S = u.hmid; A.ldS = b.Cout; A.Y = sc.dh; A.ldY = b.Cout;
-    ARDAE_TRY(lin1(EPI_DACT, ACT_RELU, R, b.Cout, g, b.Cout, b.Cout, packed + k.h.b, A, st));
+    ARDAE_TRY(dense_bwd(ACT_RELU, R, b.Cout, g, b.Cout, packed + k.h.b, u.hmid, sc.dh, st));
   }
   // weight gradients of the three operators (their bias gradients: column sums of d hmid / g; b_h1 and b_01 share g's)
   WgradList wl(nullptr);
@@ -497,7 +490,7 @@ struct ResWs {
 size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 // mode 0: encode (trunk + sampler forward), 1: vae forward + backward, 2: decode only (B = rows, nz = 1)
-void res_carve(const ResLayout& P, Bump& ws, int B, int nz, int mode, ResWs& W) {
+void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mode, ResWs& W) {
   const size_t R = (size_t)B * nz;
   const bool enc = mode != 2, dec = mode != 0, bwd = mode == 1;
   if (enc) {
@@ -571,9 +564,10 @@ void res_carve(const ResLayout& P, Bump& ws, int B, int nz, int mode, ResWs& W) 
 size_t res_workspace(const ResLayout& P, int B, int nz, int mode) {
   Bump ws;
   ResWs W;
-  res_carve(P, ws, B, nz, mode, W);
+  carve(P, ResPacked(P), ws, B, nz, mode, W);
   return ws.off;
 }
+using ResEntry = Entry<ResLayout, ResPacked, ResWs>;
 
 // ------------------------------------------------------------------------------------------------ forward pieces
 int trunk_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* x, int B, ResWs& W, hipStream_t st) {
@@ -605,32 +599,30 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
         const Blk& b = o.b; const BlkPk& k = hk.k;
         if (o.concat) {
           // rba = W0h[:, :c] inp + b0h, rbs = W01[:, :c] inp + (bh1 + b01)
-          { LinArgs A{}; A.bias = params + b.a.bias; A.Y = u.rba; A.ldY = o.out; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.a_fi, A, st)); }
-          { LinArgs A{}; A.bias = packed + k.bsum; A.Y = u.rbs; A.ldY = o.out; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.s_fi, A, st)); }
+          ARDAE_TRY(dense_fwd(ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.a_fi, params + b.a.bias, u.rba, st));
+          ARDAE_TRY(dense_fwd(ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.s_fi, packed + k.bsum, u.rbs, st));
           { LinArgs A{}; A.rowbias = u.rba; A.rowbias_ld = o.out; A.rows_per_group = nz; A.Y = u.hmid; A.ldY = o.out;
             ARDAE_TRY(lin1(EPI_ACT, ACT_RELU, R, o.out, noise, P.nd, P.nd, packed + k.a_fn, A, st)); }
           { LinArgs A{}; A.rowbias = u.rbs; A.rowbias_ld = o.out; A.rows_per_group = nz; A.Y = out; A.ldY = o.out;
             ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.out, u.hmid, o.out, o.out, packed + k.h.f, noise, P.nd, P.nd, packed + k.s_fn, A, st)); }
         } else {
-          { LinArgs A{}; A.bias = params + b.a.bias; A.Y = u.hmid; A.ldY = o.out; ARDAE_TRY(lin1(EPI_ACT, ACT_RELU, R, o.out, x, o.in, o.in, packed + k.a.f, A, st)); }
+          ARDAE_TRY(dense_fwd(ACT_RELU, R, o.out, x, o.in, o.in, packed + k.a.f, params + b.a.bias, u.hmid, st));
           if (!b.same) {
             LinArgs A{}; A.bias = packed + k.bsum; A.Y = out; A.ldY = o.out;
             ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.out, u.hmid, o.out, o.out, packed + k.h.f, x, o.in, o.in, packed + k.s.f, A, st));
           } else {   // identity skip (ResLinear(same_dim=True), models/layers.py:82-84)
-            LinArgs A{}; A.bias = params + b.h.bias; A.Y = out; A.ldY = o.out;
-            ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.out, u.hmid, o.out, o.out, packed + k.h.f, A, st));
+            ARDAE_TRY(dense_fwd(ACT_NONE, R, o.out, u.hmid, o.out, o.out, packed + k.h.f, params + b.h.bias, out, st));
             ARDAE_TRY(launch_axpy(x, (int64_t)R * o.out, 1.f, out, st));
           }
         }
       } else {
         const Lin& l = o.l; const LinPk& k = hk.lk;
         if (o.concat) {
-          { LinArgs A{}; A.bias = params + l.b; A.Y = u.rba; A.ldY = o.out; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.fi, A, st)); }
+          ARDAE_TRY(dense_fwd(ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.fi, params + l.b, u.rba, st));
           { LinArgs A{}; A.rowbias = u.rba; A.rowbias_ld = o.out; A.rows_per_group = nz; A.Y = out; A.ldY = o.out;
             ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.out, noise, P.nd, P.nd, packed + k.fn, A, st)); }
         } else {
-          LinArgs A{}; A.bias = params + l.b; A.Y = out; A.ldY = o.out;
-          ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.out, x, o.in, o.in, packed + k.f, A, st));
+          ARDAE_TRY(dense_fwd(ACT_NONE, R, o.out, x, o.in, o.in, packed + k.f, params + l.b, out, st));
         }
       }
       if (o.act != ACT_NONE) RES_LAUNCH(act_inplace_kernel, (int64_t)R * o.out, out, o.act, (int64_t)R * o.out);
@@ -639,19 +631,19 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
     return 0;
   }
   const int ldn = P.nd + P.zd;
-  { LinArgs A{}; A.bias = params + P.mu0.b; A.Y = W.mu0; A.ldY = P.nd; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, A, st)); }
-  { LinArgs A{}; A.bias = params + P.lv0.b; A.Y = W.lv0r; A.ldY = P.nd; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, W.mu0, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, W.lv0r, st));
   RES_LAUNCH(spm4_kernel, (int64_t)B * P.nd, W.lv0r, (const float*)nullptr, W.lv0, (int64_t)B * P.nd, (int)P.clipped);
   // clipped: z0 = mu0 + (std exp(lv0 / 2) + 1) eps0; the std = 0 pass (noise = zeros) takes its unscaled draw from raw0 (none: z0 = mu0)
   if (P.clipped && !(std0 && !raw0)) ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, noise, ldn, R, P.nd, nz, W.z0, st, 1.f, std0 ? raw0 : nullptr, P.nd));
   else ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, noise, ldn, R, P.nd, nz, W.z0, st));
-  { LinArgs A{}; A.bias = params + P.efc.b; A.Y = W.rbh; A.ldY = P.cdim; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.cdim, W.inp, P.cdim, P.cdim, packed + K.efc.fi, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.inp, P.cdim, P.cdim, packed + K.efc.fi, params + P.efc.b, W.rbh, st));
   { LinArgs A{}; A.rowbias = W.rbh; A.rowbias_ld = P.cdim; A.rows_per_group = nz; A.Y = W.hh; A.ldY = P.cdim;
     ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.cdim, W.z0, P.nd, P.nd, packed + K.efc.fn, A, st)); }
   RES_LAUNCH(act_inplace_kernel, (int64_t)R * P.cdim, W.hh, (int)ACT_ELU, (int64_t)R * P.cdim);
   if (hidden_out) ARDAE_TRY(launch_copy(W.hh, (size_t)R * P.cdim, hidden_out, st));
-  { LinArgs A{}; A.bias = params + P.mu.b; A.Y = W.mu; A.ldY = P.zd; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.hh, P.cdim, P.cdim, packed + K.mu.f, A, st)); }
-  { LinArgs A{}; A.bias = params + P.lv.b; A.Y = W.lvr; A.ldY = P.zd; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.zd, W.hh, P.cdim, P.cdim, packed + K.lv.f, A, st)); }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.hh, P.cdim, P.cdim, packed + K.mu.f, params + P.mu.b, W.mu, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.hh, P.cdim, P.cdim, packed + K.lv.f, params + P.lv.b, W.lvr, st));
   RES_LAUNCH(spm4_kernel, (int64_t)R * P.zd, W.lvr, (const float*)nullptr, W.lv, (int64_t)R * P.zd, (int)P.clipped);
   return launch_reparam_fwd(W.mu, W.lv, noise + P.nd, ldn, R, P.zd, 1, z_out, st);
 }
@@ -674,13 +666,6 @@ int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
   return 0;
 }
 
-const float* noise_or_zero(const ResLayout& P, const float* noise, int R, ResWs& W, hipStream_t st, int& rc) {
-  rc = 0;
-  if (noise) return noise;
-  if (rc == 0) rc = launch_fill(W.zero, (size_t)R * (P.nd + P.zd), 0.f, st);
-  return W.zero;
-}
-
 // gradient destinations of a WN operator inside the dweff / dbias scratch
 struct GradMap {
   const ResLayout& P; float* dweff; float* dbias; size_t boff = 0;
@@ -698,22 +683,20 @@ struct GradMap {
   BlkGrad blk(const Blk& b, const BlkPk& k) { BlkGrad g; g.a = wn(b.a, k.a); g.h = wn(b.h, k.h); g.s = b.same ? g.h : wn(b.s, k.s); return g; }
 };
 
-}  // namespace
-
 // ================================================================================================ entry points
-size_t res_model_param_floats(const ardae_model_desc& d) { return res_desc_ok(d) ? 0 : ResLayout(d).total; }
-size_t res_model_packed_floats(const ardae_model_desc& d) {
+size_t res_param_floats(const ardae_model_desc& d) { return res_desc_ok(d) ? 0 : ResLayout(d).total; }
+size_t res_packed_floats(const ardae_model_desc& d) {
   if (res_desc_ok(d)) return 0;
   PackList pl;
   ResPacked(ResLayout(d), pl);
   return pl.total();
 }
-size_t res_model_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+size_t res_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   if (res_desc_ok(d)) return 0;
   return res_workspace(ResLayout(d), B, nz, mode == 3 ? 0 : mode);
 }
 
-int res_model_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
+int res_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
   ARDAE_TRY(res_desc_ok(d));
   const ResLayout P(d);
   PackList pl(params, packed);
@@ -748,41 +731,31 @@ int res_model_pack(const ardae_model_desc& d, const float* params, float* packed
   return pl.launch(st);
 }
 
-int res_model_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+int res_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                      float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float* raw0) {
-  const ResLayout P(d);
-  const ResPacked K(P);
-  Bump ws(workspace, wsf);
-  ResWs W;
-  res_carve(P, ws, B, nz, 0, W);
+  ResEntry entry(d, workspace, wsf, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "res model encode: workspace too small");
   ARDAE_CHECK_ARG(!hidden_out || (P.kind == 6 && nz == 1), "res model: the hidden1a context is the aux model's h at nz = 1");
-  int rc;
-  const float* nzp = noise_or_zero(P, noise, B * nz, W, st, rc);
-  ARDAE_TRY(rc);
+  const float* nzp = noise;
+  ARDAE_TRY(noise_or_zero(nzp, W.zero, (size_t)B * nz * (P.nd + P.zd), st));
   ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
   ARDAE_CHECK_ARG(!raw0 || (P.clipped && !noise), "res model: raw0 is the clipped class's unscaled eps0 of a std = 0 pass (noise NULL)");
   return sampler_fwd(P, K, params, packed, nzp, B, nz, W, z_out ? z_out : W.z, hidden_out, st, raw0, noise == nullptr);
 }
 
-int res_model_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
+int res_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
                      float* out0, hipStream_t st, float*) {
-  const ResLayout P(d);
-  const ResPacked K(P);
-  Bump ws(workspace, wsf);
-  ResWs W;
-  res_carve(P, ws, R, 1, 2, W);
+  ResEntry entry(d, workspace, wsf, R, 1, 2);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "res model decode: workspace too small");
   return decoder_fwd(P, K, params, packed, z, R, W, out0, st);
 }
 
-int res_model_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+int res_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                           float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  const ResLayout P(d);
-  const ResPacked K(P);
-  Bump ws(workspace, wsf);
-  ResWs W;
-  res_carve(P, ws, B, nz, 1, W);
+  ResEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "res model vae_forward: workspace too small");
   const int R = B * nz;
   ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
@@ -793,13 +766,10 @@ int res_model_vae_forward(const ardae_model_desc& d, const float* params, const 
   return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
 }
 
-int res_model_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+int res_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                            float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  const ResLayout P(d);
-  const ResPacked K(P);
-  Bump ws(workspace, wsf);
-  ResWs W;
-  res_carve(P, ws, B, nz, 1, W);
+  ResEntry entry(d, workspace, wsf, B, nz, 1);
+  auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "res model vae_backward: workspace too small");
   const int R = B * nz;
   const float gscale = dloss / (float)R;
@@ -844,7 +814,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
         const Blk& b = o.b; const BlkPk& k = hk.k;
         const BlkGrad gr = gm.blk(b, k);
         float* dh = W.sc.dh;       // [R, out]: d hmid = (g W_h1) relu'(hmid)
-        { LinArgs A{}; A.S = u.hmid; A.ldS = o.out; A.Y = dh; A.ldY = o.out; ARDAE_TRY(lin1(EPI_DACT, ACT_RELU, R, o.out, g, o.out, o.out, packed + k.h.b, A, st)); }
+        ARDAE_TRY(dense_bwd(ACT_RELU, R, o.out, g, o.out, packed + k.h.b, u.hmid, dh, st));
         pw(R, o.out, o.out, g, u.hmid, o.out, gr.h, 0, o.out, true);
         if (o.concat) {
           const int I0 = P.cdim + P.nd;
@@ -861,11 +831,11 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
           if (!b.same) pw(R, o.out, o.in, g, x, o.in, gr.s, 0, o.in, true);
           pw(R, o.out, o.in, dh, x, o.in, gr.a, 0, o.in, true);
           ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          LinArgs A{}; A.Y = dx; A.ldY = o.in;
           if (!b.same) {
+            LinArgs A{}; A.Y = dx; A.ldY = o.in;
             ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.s.b, dh, o.out, o.out, packed + k.a.b, A, st));
           } else {   // identity skip: dx = dh W_0h + g
-            ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.in, dh, o.out, o.out, packed + k.a.b, A, st));
+            ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, dh, o.out, o.out, packed + k.a.b, nullptr, dx, st));
             ARDAE_TRY(launch_axpy(g, (int64_t)R * o.in, 1.f, dx, st));
           }
         }
@@ -877,13 +847,11 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
           pw(R, o.out, P.nd, g, noise, P.nd, gl, P.cdim, l.in, true);
           pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gl, 0, l.in, false);
           ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
-          ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, A, st));
+          ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, nullptr, W.dinp, st));
         } else {
           pw(R, o.out, o.in, g, x, o.in, gl, 0, l.in, true);
           ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          LinArgs A{}; A.Y = dx; A.ldY = o.in;
-          ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, A, st));
+          ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, nullptr, dx, st));
         }
       }
       g = dx;
@@ -906,7 +874,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
     plain_wgrad(R, P.efc, dhh, W.z0, P.nd, P.cdim, P.nd, true);                              // z0 columns + bias
     plain_wgrad(B, P.efc, W.dB0, W.inp, P.cdim, 0, P.cdim, false);                           // image columns
     float* dz0 = W.dR1;            // [R, nd] = dhh W_fc[:, cdim:]
-    { LinArgs A{}; A.Y = dz0; A.ldY = P.nd; ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.nd, dhh, P.cdim, P.cdim, packed + K.efc.bn, A, st)); }
+    ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, dhh, P.cdim, P.cdim, packed + K.efc.bn, nullptr, dz0, st));
     // z0 = mu0[b] + exp(lv0[b] / 2) eps0,  lv0 = spm4(lv0r): reduce over the nz rows of an image first
     float* dlv0_rows = W.sc.dh;    // [R, nd]
     ARDAE_TRY(launch_reparam_bwd(dz0, W.z0, W.mu0, R, P.nd, nz, dlv0_rows, st, P.clipped ? 1.f : 0.f, noise, ldn));
@@ -920,9 +888,7 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
     float* part = W.dflat;         // [B, cdim] scratch (cdim <= 512)
     { LinArgs A{}; A.Y = part; A.ldY = P.cdim;
       ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, P.cdim, P.cdim, packed + K.efc.bi, W.dB1, P.nd, P.nd, packed + K.mu0.b, A, st)); }
-    { LinArgs A{}; A.S = part; A.ldS = P.cdim; A.Q = part; A.ldQ = P.cdim; A.Y = W.dinp; A.ldY = P.cdim;       // V * 1 + Q
-      ARDAE_TRY(lin1(EPI_DACT, ACT_NONE, B, P.cdim, W.dB2, P.nd, P.nd, packed + K.lv0.b, A, st)); }
-    (void)ldn;
+    ARDAE_TRY(dense_bwd(ACT_NONE, B, P.cdim, W.dB2, P.nd, packed + K.lv0.b, part, W.dinp, st, part));       // V * 1 + Q
   }
   // ---- trunk backward
   std::vector<BlkGrad> gt(P.trunk.size());
@@ -946,5 +912,12 @@ int res_model_vae_backward(const ardae_model_desc& d, const float* params, const
   }
   return 0;
 }
+
+}  // namespace
+
+// (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
+#ifndef __HIP_DEVICE_COMPILE__
+const Family RES_FAMILY = {res_param_floats, res_packed_floats, res_workspace_floats, res_pack, res_encode, res_decode, res_vae_forward, res_vae_backward};
+#endif
 
 }  // namespace ardae

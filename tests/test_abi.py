@@ -200,7 +200,16 @@ MODEL_SIZES = [("mnist", (784, 100, 256, 32, 2), 2, 0, 1656832, [66176, 1735232,
                ("auxresconv", (784, 100, 450, 32, 1), 3, 0, 6869312, [1446592, 76021632, 48892416, 1446592]),
                ("auxtoy", (2, 2, 64, 2, 1), 4, 0, 23552, [4032, 28608, 8192, 4032]),
                # both log-variance clip codes set (z0 head 'hard', z head 'spm4'): two more workspace buffers, same parameters and panels
-               ("auxmnist", (784, 100, 300, 32, 2), 2, (1 << L.MODEL_CLIP_Z0_SHIFT) | (6 << L.MODEL_CLIP_Z_SHIFT), 2099200, [138944, 2196416, 76800, 138944])]
+               ("auxmnist", (784, 100, 300, 32, 2), 2, (1 << L.MODEL_CLIP_Z0_SHIFT) | (6 << L.MODEL_CLIP_Z_SHIFT), 2099200, [138944, 2196416, 76800, 138944]),
+               # the ends of the MLP families' layer loops, num_hidden_layers 1 and 4 (auxtoy at 1 is the row above): recorded from a build of
+               # the commit BEFORE the stacks and the decoder of these four kinds were written once (csrc/mlp.h), not from that code
+               ("mnist", (24, 10, 64, 8, 1), 2, 0, 46080, [12736, 94080, 16384, 12096]),
+               ("mnist", (24, 10, 64, 8, 4), 2, 0, 95232, [14272, 184320, 40960, 13632]),
+               ("toy", (2, 10, 64, 2, 1), 2, 0, 22528, [10816, 45824, 8192, 10176]),
+               ("toy", (2, 10, 64, 2, 4), 2, 0, 99328, [36928, 215168, 32768, 37824]),
+               ("auxmnist", (24, 10, 48, 8, 1), 2, 0, 21504, [14016, 55424, 6144, 14016]),
+               ("auxmnist", (24, 10, 48, 8, 4), 2, 0, 76800, [33600, 167552, 24576, 33600]),
+               ("auxtoy", (2, 2, 64, 2, 4), 4, 0, 97280, [11712, 143808, 32768, 11712])]
 # kind 5 at (784, 100, 512, 32, nl): (packed floats, workspace floats at (4, 8), mode 1) per sampler head and nl = 1, 2, 3
 RESCONV_HEAD_SIZES = {"res-wn-mlp": [(10086208, 22831104), (11660608, 23456000), (13235008, 24080896)],
                       "mlp": [(7447104, 22141504), (7971392, 22453376), (8495680, 22765248)],

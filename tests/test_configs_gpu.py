@@ -33,8 +33,8 @@ def test_cdae_update_workload_shape_vs_oracle(cfg, B, S):
     cdae_vs_oracle(kind, B, S, z, h, L)
 
 
-def _step_vs_oracle(mc, cc, B, nz, p_pix):
-    tc = O.TrainCfg(nz_cdae=nz)
+def _step_vs_oracle(mc, cc, B, nz, p_pix, cdae_ctx_type="lt0"):
+    tc = O.TrainCfg(nz_cdae=nz, ctx_type=cdae_ctx_type)
     pm = O.init_params(O.model_param_spec(mc), 0, O.model_init_special(mc))
     pc = O.init_params(O.cdae_param_spec(cc), 1)
     gen = torch.Generator().manual_seed(23)
@@ -45,8 +45,13 @@ def _step_vs_oracle(mc, cc, B, nz, p_pix):
     model.load_state_dict(pm); cdae.load_state_dict(pc)
     model, cdae = model.to("cuda"), cdae.to("cuda")
     before_c, before_m = cdae.flat_params().clone().cpu(), model.flat_params().clone().cpu()
-    eng = net.ArdaeEngine(model, cdae, net.TrainConfig(nz_cdae=nz), batch_size=B)
-    eng.step(x1.cuda(), x2.cuda(), noise={k: v.cuda().contiguous() for k, v in noise.items()})
+    eng = net.ArdaeEngine(model, cdae, net.TrainConfig(nz_cdae=nz, cdae_ctx_type=cdae_ctx_type), batch_size=B)
+    eng_noise = {k: v for k, v in noise.items() if not k.endswith("_z")}
+    for k in ("sampler", "vae"):        # aux models: the engine takes the two draws of a sampler call as one tensor, rows [eps0 | eps]
+        if k + "_z" in noise:           # (ToyAuxIPVAE: eps0 [B q, nd] and eps [B q q, z] as two blocks, one after the other)
+            e0, e = noise[k], noise[k + "_z"]
+            eng_noise[k] = torch.cat([e0.reshape(-1), e.reshape(-1)]) if mc.kind == "auxtoy" else torch.cat([e0, e], 1)
+    eng.step(x1.cuda(), x2.cuda(), noise={k: v.cuda().contiguous() for k, v in eng_noise.items()})
     got = eng.stats()
     rm, rc = {k: v.clone() for k, v in pm.items()}, {k: v.clone() for k, v in pc.items()}
     ref = O.train_step(mc, cc, tc, rm, rc, {}, {}, x1, x2, noise)
@@ -68,6 +73,25 @@ def test_engine_step_cfg4_vs_oracle():
 def test_engine_step_cfg5_vs_oracle():
     """Config #5: MNISTIPVAE(input_dim=3072) + mlp-res h 1024 L 6, 8 images x 1024 samples = 8192 rows, one whole step."""
     _step_vs_oracle(O.ModelCfg("mnist", 3072, 100, 256, 32, 2, "softplus"), O.CdaeCfg("res", 32, 32, 1024, 6), 8, 1024, 0.5)
+
+
+# the four MLP model kinds at the ends of their layer loops (every other MLP-family fixture has two hidden layers): one layer, where
+# each stack is its first layer only and no backward loop runs, and three, where the backward loops take more than one step
+MLP_DEPTH_CASES = {
+    "mnist": (("mnist", 24, 10, 64, 8, "softplus"), ("grad", 8, 8, 64, 3), 8),
+    "toy": (("toy", 2, 10, 64, 2, "softplus"), ("grad", 2, 2, 64, 3), 8),
+    "auxmnist": (("auxmnist", 24, 10, 48, 8, "softplus"), ("grad", 8, 96, 64, 3), 8),
+    "auxtoy": (("auxtoy", 2, 2, 32, 2, "tanh"), ("grad", 2, 64, 64, 3), 16),
+}
+
+
+@pytest.mark.parametrize("n_layers", [1, 3])
+@pytest.mark.parametrize("kind", list(MLP_DEPTH_CASES))
+def test_engine_step_mlp_depth_vs_oracle(kind, n_layers):
+    """One whole engine step of the four MLP model kinds with 1 and 3 hidden layers, 4 images, against the live oracle."""
+    (name, *dims, nonlin), cc, nz = MLP_DEPTH_CASES[kind]
+    mc = O.ModelCfg(name, *dims, n_layers, nonlin)
+    _step_vs_oracle(mc, O.CdaeCfg(*cc), 4, nz, 0.5, cdae_ctx_type="hidden1a" if mc.kind in O.AUX_KINDS else "lt0")
 
 
 @pytest.mark.parametrize("cfg,B,S", [(CFG4_CDAE, 256, 512), (CFG5_CDAE, 256, 1024)], ids=["cfg4", "cfg5"])
