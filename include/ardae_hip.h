@@ -248,6 +248,62 @@ int ardae_dae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, 
                                  uint64_t first_row, float* xbar, float* sigma, float* eps_out, float* workspace,
                                  size_t workspace_floats, float* loss, float* grads, void* stream);
 
+/* ---- energy-function fitting (notebooks/ardae_fit.ipynb): energies, the implicit generator, torch.optim.Adam + StepLR -------------
+ * One iteration of the notebook: num_dae_updates AR-DAE updates, each on a fresh sample of the generator, then one generator update
+ * whose output gradient is (alpha dE/dx + score(x, sigma = 0)) / B.  What changes from iteration to iteration (the Philox base
+ * offset, Adam's t and bias corrections, the StepLR learning rate, the annealed energy weight alpha) lives in the FIT STATE, a device
+ * block of ARDAE_FIT_STATE_BYTES: its first ARDAE_STEP_STATE_BYTES are the step state (ardae_philox_normal_at / *_dev consumers read
+ * it as such), then f32 alpha, f32 lr of the COMING iteration, then f32 alpha, f32 lr of the iteration just done.  Zero-initialise. */
+#define ARDAE_FIT_STATE_BYTES 48
+/* utils/energy.py: regularization_func alone (any d), energy_func1..4 (each with regularization_func; x is [R, 2]) and
+ * normal_energy_func(x, mu, logvar) (any d) */
+enum { ARDAE_ENERGY_REG = 0, ARDAE_ENERGY_1 = 1, ARDAE_ENERGY_2 = 2, ARDAE_ENERGY_3 = 3, ARDAE_ENERGY_4 = 4, ARDAE_ENERGY_NORMAL = 5 };
+/* energy[r] = E(x[r]) and grad[r] = dE/dx (x[r]) - what autograd returns for the reference's function - for x [R, d]; either output
+ * may be NULL.  Evaluated in double per row and rounded once.  mu / logvar: ARDAE_ENERGY_NORMAL only.  Kinds 1 - 4 refuse d != 2. */
+int ardae_energy(int kind, const float* x, int R, int d, float mu, float logvar, float* energy, float* grad, void* stream);
+/* The generator's output seed of one iteration: seed[r] = (alpha * dE/dx (x[r]) + score[r]) / R, three separately rounded fp32
+ * operations on the fp32 gradient of ardae_energy, and mean_energy[0] = mean_r E(x[r]) (a two-stage sum in a fixed order, in double:
+ * no atomics).  alpha: the fit state's (coming iteration) when fit_state is non-NULL, else the argument.  partial: scratch of
+ * ardae_energy_partial_floats(R) floats. */
+size_t ardae_energy_partial_floats(int R);
+int ardae_energy_seed(int kind, const float* x, const float* score, int R, int d, float mu, float logvar, float alpha,
+                      const void* fit_state, float* seed, float* mean_energy, float* partial, void* stream);
+/* The implicit generator (ardae_fit.ipynb `Generator.main`): Linear(z_dim, h) -> act -> [Linear(h, h) -> act] x (n_layers - 1) ->
+ * Linear(h, out_dim).  Parameters in ONE flat buffer in named_parameters() order (main.0.weight, main.0.bias, main.2.weight, ...),
+ * each weight [out, in] row-major.  n_layers 1 .. 16, act any ARDAE_ACT_* but NONE.
+ * forward: x_out [B, out_dim] from z [B, z_dim]; the hidden layers stay in `workspace` for the backward call (same B).
+ * backward: grads (flat, parameter layout, OVERWRITTEN) = d <dx, x_out> / d params from the seed dx [B, out_dim], every weight
+ * gradient in one ardae_wgrad_batch. */
+size_t ardae_gen_param_floats(int z_dim, int h_dim, int n_layers, int out_dim, int act);
+size_t ardae_gen_packed_floats(int z_dim, int h_dim, int n_layers, int out_dim, int act);
+size_t ardae_gen_workspace_floats(int z_dim, int h_dim, int n_layers, int out_dim, int act, int B);
+int ardae_gen_pack(int z_dim, int h_dim, int n_layers, int out_dim, int act, const float* params, float* packed, void* stream);
+int ardae_gen_forward(int z_dim, int h_dim, int n_layers, int out_dim, int act, const float* params, const float* packed, const float* z,
+                      int B, float* workspace, size_t workspace_floats, float* x_out, void* stream);
+int ardae_gen_backward(int z_dim, int h_dim, int n_layers, int out_dim, int act, const float* params, const float* packed, const float* z,
+                       const float* dx, int B, float* workspace, size_t workspace_floats, float* grads, void* stream);
+/* Draw + first layer in ONE kernel over 64-row tiles: z [B, z_dim] = the draw (seed, offset [+ state.rng_offset]) keyed exactly like
+ * ardae_philox_normal_at on B * z_dim elements (written out: the first layer's weight gradient reads it) and h_1 = act(W_1 z + b_1)
+ * into the workspace slot ardae_gen_forward would fill; then ardae_gen_forward from layer 2 on.  ardae_gen_draw_fused_ok: 1 if
+ * z_dim <= 16 and h_dim is 64, 128 or 256; otherwise ardae_philox_normal_at + ardae_gen_forward. */
+int ardae_gen_draw_fused_ok(int z_dim, int h_dim, int n_layers, int out_dim, int act);
+int ardae_gen_draw_forward(int z_dim, int h_dim, int n_layers, int out_dim, int act, const float* params, const float* packed, int B,
+                           uint64_t seed, uint64_t offset, const void* state, float* z_out, float* workspace, size_t workspace_floats,
+                           float* x_out, void* stream);
+/* torch.optim.Adam (no amsgrad, no weight decay): m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g;
+ * p -= step_size * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)) - epsilon AFTER the bias correction, unlike ardae_adam_ref_step.
+ * step_size = lr / (1 - beta1^t) and sqrt(1 - beta2^t) come from the head of the fit (or step) state. */
+int ardae_adam_torch_step_dev(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1, double beta2,
+                              double eps, const void* state, void* stream);
+/* Advance the fit state to the next iteration (last node of an iteration): the iteration just done keeps its alpha / lr in the
+ * second pair, rng_offset += rng_inc, t += 1, and for iteration i = t - 1, in double:
+ *   lr_i = max(lr_min, lr0 * lr_gamma^(i / lr_step_size))   the notebook's StepLR (utils/lr_scheduler.py), stepped after the optimiser
+ *   step_size = lr_i / (1 - beta1^t), sqrt(1 - beta2^t)     torch.optim.Adam's coefficients
+ *   alpha_i = alpha_init + (alpha_fin - alpha_init) / alpha_annealing * min(alpha_annealing, i)   (utils/msc.py:53-55;
+ *             alpha_annealing < 0: None, alpha_fin) */
+int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, double beta1, double beta2, int64_t lr_step_size,
+                            double lr_gamma, double lr_min, double alpha_init, double alpha_fin, int64_t alpha_annealing, void* stream);
+
 
 /* ---- K2/K8: implicit-posterior VAE (models/ivae/mnist.py, models/ivae/toy.py enc_type='concat') ---------------
  * Parameters: ONE flat fp32 buffer in the reference's named_parameters() order

@@ -7,6 +7,7 @@
 
 #include "ardae_hip.h"
 #include "common.h"
+#include "front_layer.h"
 #include "philox.h"
 #include "profile.h"
 
@@ -19,7 +20,7 @@ int dae_loss_grads_from_h1(const ardae_cdae_desc* d, const float* params, const 
 
 namespace {
 
-constexpr int DP_ROWS = 64;   // rows per workgroup of the fused kernel
+constexpr int DP_ROWS = FRONT_ROWS;   // rows per workgroup of the fused kernel
 constexpr int DP_DMAX = 8;    // widest input it takes as plain FMAs
 
 __global__ __launch_bounds__(256) void dae_perturb_kernel(const float* __restrict__ x, const float* __restrict__ sigma, const float* __restrict__ eps,
@@ -33,10 +34,7 @@ __global__ __launch_bounds__(256) void dae_perturb_kernel(const float* __restric
 
 // One workgroup per tile of 64 rows.  Phase 1: the tile's Philox counters (16 d of the eps draw, 16 of the sigma draw: at most 144 of the
 // 256 threads hold one), then sigma = delta n, xbar = fma(sigma, eps, x[b]) - written out, and kept in LDS.  Phase 2: h_1 =
-// act(W1x xbar + sigma w1s + d_1): K = d + 1 <= 9, so the layer is nothing but its N x h store.  A lane owns FOUR consecutive columns (its
-// 4 (d + 2) weights stay in registers) and h / 4 lanes cover a row, so every store instruction of a wave is 64 x 16 bytes = 1 KiB of
-// consecutive addresses - one full row at h 256, two at h 128, four at h 64; the row's d + 1 inputs are LDS broadcasts.  The dot product
-// is a chain of FMAs in ascending k from 0 (the order the FP32 MFMA of the stand-alone layer adds in), then + d_1, then fma(sigma, w1s, .).
+// act(W1x xbar + sigma w1s + d_1), front_layer.h::front_first_layer (shared with the generator's front end, generator.hip).
 // Rows at or beyond N (a last partial tile) draw like the others and write nothing.
 __global__ __launch_bounds__(256) void dae_perturb_fwd_kernel(const float* __restrict__ x, int N, int nsigma, int d, float delta, uint64_t seed,
                                                               uint64_t off_sigma, uint64_t off_eps, const StepState* __restrict__ state,
@@ -78,35 +76,7 @@ __global__ __launch_bounds__(256) void dae_perturb_fwd_kernel(const float* __res
     if (k == 0) sg[r] = s;
   }
   __syncthreads();
-  const int lane = t & 63, wave = t >> 6;
-  const int lpr = h >> 2, rpw = 64 / lpr;          // lanes per row, rows per wave store
-  const int lc = lane % lpr, lr = lane / lpr, c0 = 4 * lc;
-  float w[4][DP_DMAX], ws[4], bs[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float* wr = W1 + (size_t)(c0 + j) * (d + 1);
-#pragma unroll
-    for (int k = 0; k < DP_DMAX; ++k) w[j][k] = k < d ? wr[k] : 0.f;
-    ws[j] = wr[d];
-    bs[j] = b1[c0 + j];
-  }
-  for (int r = wave * (DP_ROWS / 4) + lr; r < (wave + 1) * (DP_ROWS / 4); r += rpw) {
-    const int row = row0 + r;
-    if (row >= N) break;
-    const float s = sg[r];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < DP_DMAX; ++k)
-      if (k < d) {
-        const float xv = xb[r * d + k];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(xv, w[j][k], acc[j]);
-      }
-    f32x4 y;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = act_fwd_rt(act, __builtin_fmaf(s, ws[j], acc[j] + bs[j]));
-    *reinterpret_cast<f32x4*>(h1 + (size_t)row * h + c0) = y;
-  }
+  front_first_layer<DP_DMAX, true>(xb, sg, d, row0, N, W1, d + 1, b1, h, act, h1);
 }
 
 bool fused_shape_ok(const ardae_cdae_desc* d, int nsigma) {

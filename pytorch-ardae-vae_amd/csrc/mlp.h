@@ -18,9 +18,9 @@ struct MlpStack {
   }
   size_t n() const { return lin.size(); }
 
-  // a[l] = act(a[l - 1] W_l^T + b_l), l = 1 .. n, on M rows
-  int fwd(const float* params, const float* packed, int act, int M, const float* x, float* const* a, hipStream_t st) const {
-    for (size_t l = 1; l <= n(); ++l) {
+  // a[l] = act(a[l - 1] W_l^T + b_l), l = first .. n, on M rows  (first > 1: a[first - 1] is already there)
+  int fwd(const float* params, const float* packed, int act, int M, const float* x, float* const* a, hipStream_t st, size_t first = 1) const {
+    for (size_t l = first; l <= n(); ++l) {
       const Lin& L = lin[l - 1];
       ARDAE_TRY(dense_fwd(act, M, L.out, l == 1 ? x : a[l - 1], L.in, L.in, packed + f[l - 1], params + L.b, a[l], st));
     }

@@ -57,4 +57,13 @@ struct StepState {
   float adam_sqrt_bc2;     // sqrt(1 - beta2^t)
 };
 
+// The fit state (ardae_fit_state_advance): a step state whose Adam coefficients follow the StepLR schedule, and behind it the
+// energy weight and learning rate of the coming iteration and of the one just done (the logged pair).
+struct FitState {
+  StepState step;
+  uint64_t reserved;           // the step state block is 32 bytes (ARDAE_STEP_STATE_BYTES), 24 of them used
+  float alpha, lr;             // the coming iteration's
+  float alpha_done, lr_done;   // the last finished iteration's
+};
+
 }  // namespace ardae

@@ -900,8 +900,8 @@ class ArdaeScoreEngine:
     validated before any pointer reaches a kernel, in-step Philox offsets are RNG_STRIDE * step + {0 (sigma), 1 (eps)} - below
     rng.HOST_STREAM.  One stream, one linear graph; there is no data parallelism here.
 
-    The sampler of ardae_fit.ipynb stays the caller's torch module; its entropy gradient is
-    `output.backward(engine.score(output.detach()) / B)`."""
+    A sampler that stays the caller's torch module takes its entropy gradient as `output.backward(engine.score(output.detach()) / B)`;
+    the whole iteration of ardae_fit.ipynb on the device - generator, energy, this update - is `ArdaeFitEngine` (fit.py)."""
 
     RNG_STRIDE = ArdaeEngine.RNG_STRIDE
 
@@ -1003,6 +1003,10 @@ class ArdaeScoreEngine:
                 g.replay()                      # a capture runs nothing
                 self._graph = g
         self._calls += 1
+        self._count_step()
+
+    def _count_step(self):
+        """Host-side bookkeeping of one update (`_body` itself only launches: ArdaeFitEngine runs it inside its own captured iteration)."""
         self.step_count += 1
         self.opt.steps = self.step_count
         for p in self.dae.parameters():         # the module path re-packs at its next use

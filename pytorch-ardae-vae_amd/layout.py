@@ -125,6 +125,15 @@ def dae_spec(kind, input_dim, h_dim, n_layers):
     raise NotImplementedError(kind)
 
 
+def gen_spec(input_dim, hidden_dim, z_dim, n_layers):
+    """The implicit generator of notebooks/ardae_fit.ipynb: `main = nn.Sequential(Linear, act, Linear, act, ..., Linear)` - the Linears sit
+    at the even indices, main.{0, 2, ..., 2 n_layers}."""
+    s = []
+    for i in range(n_layers):
+        s += [(f"main.{2 * i}.weight", (hidden_dim, z_dim if i == 0 else hidden_dim)), (f"main.{2 * i}.bias", (hidden_dim,))]
+    return s + [(f"main.{2 * n_layers}.weight", (input_dim, hidden_dim)), (f"main.{2 * n_layers}.bias", (input_dim,))]
+
+
 def offsets(spec):
     out, off = {}, 0
     for name, shape in spec:

@@ -305,6 +305,81 @@ class MLPResARDAE(ARDAE):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# The implicit generator of notebooks/ardae_fit.ipynb
+# ---------------------------------------------------------------------------------------------------------------
+class _GenFn(torch.autograd.Function):
+    """x = main(z) through ardae_gen_forward; backward = ardae_gen_backward on the incoming seed (the workspace keeps the hidden layers, so
+    the notebook's two backward calls through one forward - retain_graph=True - both work)."""
+
+    @staticmethod
+    def forward(ctx, mod, z, *params):
+        B = z.size(0)
+        ws = mod._ws(L.query("ardae_gen_workspace_floats", *mod._net, B))
+        x = torch.empty(B, mod.input_dim, device=z.device, dtype=torch.float32)
+        L.call("ardae_gen_forward", *mod._net, mod._flat, mod._packed_weights(), z, B, ws, ws.numel(), x)
+        ctx.mod, ctx.z, ctx.ws = mod, z, ws
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        mod = ctx.mod
+        grads = torch.zeros_like(mod._flat)
+        L.call("ardae_gen_backward", *mod._net, mod._flat, mod._packed_weights(), ctx.z, _f32c(dx), ctx.z.size(0), ctx.ws, ctx.ws.numel(), grads)
+        return (None, None) + tuple(grads[off:off + n].view(shape) for off, n, shape in (mod._offs[name] for name, _ in mod.named_parameters()))
+
+
+class Generator(FlatParamModule):
+    """notebooks/ardae_fit.ipynb `Generator`: main = Linear(z_dim, h) -> act -> [Linear(h, h) -> act] x (num_hidden_layers - 1) ->
+    Linear(h, input_dim); the notebook's is num_hidden_layers=3, nonlinearity='relu'.  state_dict() keys are the nn.Sequential's,
+    main.{0, 2, 4, ...}.{weight, bias}.  `energy_func`: what `loss` averages (the notebook reads a global; default net.energy.energy_func4,
+    the notebook's choice)."""
+
+    def _packed_weights(self):
+        if self._pack_is_current():
+            return self._packed
+        if self._packed is None:
+            self._packed = self._ws(L.query("ardae_gen_packed_floats", *self._net))
+        L.call("ardae_gen_pack", *self._net, self._flat, self._packed)
+        self._note_packed()
+        return self._packed
+
+    def __init__(self, input_dim=2, hidden_dim=64, z_dim=2, num_hidden_layers=3, nonlinearity="relu", energy_func=None):
+        super().__init__()
+        if nonlinearity not in L.ACT or nonlinearity in ("none", None):
+            raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
+        if not (int(input_dim) >= 1 and int(hidden_dim) >= 1 and int(z_dim) >= 1 and 1 <= int(num_hidden_layers) <= 16):
+            raise ValueError(f"Generator: dimensions must be positive and 1 <= num_hidden_layers <= 16 (got input_dim={input_dim}, hidden_dim={hidden_dim}, "
+                             f"z_dim={z_dim}, num_hidden_layers={num_hidden_layers})")
+        self.input_dim, self.hidden_dim, self.z_dim = int(input_dim), int(hidden_dim), int(z_dim)
+        self.num_hidden_layers, self.nonlinearity = int(num_hidden_layers), nonlinearity
+        if energy_func is None:
+            from . import energy
+            energy_func = energy.energy_func4
+        self.energy_func = energy_func
+        # the network as the ABI takes it: z_dim, h_dim, n_layers, out_dim, act
+        self._net = (self.z_dim, self.hidden_dim, self.num_hidden_layers, self.input_dim, L.ACT[nonlinearity])
+        self._build_params(layout.gen_spec(self.input_dim, self.hidden_dim, self.z_dim, self.num_hidden_layers))
+        self._default_init()
+
+    def sample_noise(self, batch_size):
+        """[batch_size, z_dim] standard normals from the library's host Philox stream."""
+        self._require_gpu()
+        return rng.normal((int(batch_size), self.z_dim), self._flat.device)
+
+    def loss(self, x):
+        return torch.mean(self.energy_func(x))
+
+    def forward(self, batch_size=None, z=None):
+        """-> (x, loss) like the notebook's.  `z` injects the noise batch ([B, z_dim]); default: sample_noise(batch_size or 128)."""
+        self._require_gpu(z)
+        if z is None:
+            z = self.sample_noise(128 if batch_size is None else batch_size)
+        z = _f32c(z).view(-1, self.z_dim)
+        x = _GenFn.apply(self, z, *self.parameters())
+        return x, self.loss(x)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # implicit-posterior VAE
 # ---------------------------------------------------------------------------------------------------------------
 def normal_energy_func(x, mu=0., logvar=0.):
