@@ -6,7 +6,6 @@ Data parallel: the image batch is sharded over ranks, parameters are
 buffers are all-reduced (RCCL over xGMI via torch.distributed backend "nccl") before their optimiser steps.
 """
 import contextlib
-import os
 from dataclasses import dataclass
 
 import torch
@@ -14,6 +13,7 @@ import torch
 from . import _lib as L
 from . import dist
 from . import rng
+from .engine_common import CaptureLadder, _FlatOpt, bump_versions, capture_linear, check_batch, check_tensor, rebuild_step_state  # noqa: F401
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
 
@@ -56,61 +56,6 @@ def annealing_func(val_init, val_fin, val_annealing, step):
     if val_annealing is None:
         return float(val_fin)
     return float(val_init + (val_fin - val_init) / float(val_annealing) * float(min(val_annealing, step)))
-
-
-class _FlatOpt:
-    """One network's optimiser on its flat parameter / gradient buffers: torch.optim.SGD(lr), the reference's vendored Adam (amsgrad
-    optional; utils/optim.py:49-108) or torch.optim.RMSprop(momentum) - the four choices of --m-optimizer / --d-optimizer.  `n`: floats
-    that receive gradients (the cDAE's trailing neglogprob.fc.bias does not and keeps no state).  Adam's t and bias corrections live in a
-    32-byte device block (`ardae_step_state_advance`) so that a captured step can be replayed."""
-    KINDS = ("sgd", "adam", "amsgrad", "rmsprop")
-
-    def __init__(self, kind, flat, n, lr, beta1, momentum, state=None):
-        if kind not in self.KINDS:
-            raise NotImplementedError(f"unknown optimizer: {kind}")                     # ivae_ardae.py:555-556,621-622
-        self.kind, self.flat, self.n, self.lr, self.beta1, self.momentum = kind, flat, int(n), float(lr), float(beta1), float(momentum)
-        z = lambda: torch.zeros_like(flat)
-        self.a = None if kind == "sgd" else z()                                         # exp_avg | square_avg
-        self.b = None if kind == "sgd" else z()                                         # exp_avg_sq | momentum_buffer
-        self.c = z() if kind == "amsgrad" else None                                     # max_exp_avg_sq
-        self.steps = 0
-        self.state = state if state is not None else torch.zeros(4, dtype=torch.int64, device=flat.device)
-
-    @property
-    def adam(self):
-        return self.kind in ("adam", "amsgrad")
-
-    def advance(self, rng_inc=0):
-        L.call("ardae_step_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999)
-
-    def apply(self, grads, in_step):
-        p, g = self.flat, grads
-        if self.kind == "sgd":
-            L.call("ardae_sgd_step", p, g, self.n, self.lr)
-        elif self.kind == "rmsprop":
-            L.call("ardae_rmsprop_step", p, g, self.a, self.b, self.n, self.lr, 0.99, 1e-8, self.momentum)
-        elif in_step:      # t and the bias corrections come from the device block (advanced inside the step)
-            L.call("ardae_adam_ref_step_dev", p, g, self.a, self.b, self.c, self.n, self.beta1, 0.999, 1e-8, self.state)
-        else:
-            L.call("ardae_adam_ref_step", p, g, self.a, self.b, self.c, self.n, self.lr, self.beta1, 0.999, 1e-8, self.steps + 1)
-
-    # torch.optim.Optimizer.state_dict() pieces (per-parameter views of the flat buffers)
-    def state_names(self):
-        return {"sgd": (), "adam": ("exp_avg", "exp_avg_sq"), "amsgrad": ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
-                "rmsprop": ("square_avg", "momentum_buffer")}[self.kind]
-
-    def buffers(self):
-        return [t for t in (self.a, self.b, self.c) if t is not None]
-
-    def param_group(self, nparams):
-        if self.kind == "sgd":
-            g = {"lr": self.lr, "momentum": 0, "dampening": 0, "weight_decay": 0, "nesterov": False}
-        elif self.adam:
-            g = {"lr": self.lr, "betas": (self.beta1, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": self.kind == "amsgrad"}
-        else:
-            g = {"lr": self.lr, "momentum": self.momentum, "alpha": 0.99, "eps": 1e-8, "centered": False, "weight_decay": 0}
-        g["params"] = list(range(nparams))
-        return g
 
 
 class ArdaeEngine:
@@ -252,19 +197,7 @@ class ArdaeEngine:
         L.call("ardae_cdae_pack", self.cdae._desc, self.cdae._flat, self.pk_c)
 
     def _check_batch(self, x, what):
-        """The kernels read exactly B * input_dim contiguous floats from each batch pointer: anything else (a ragged last batch
-        of a loader without drop_last, a strided view, a host tensor) must be refused here, not read out of bounds."""
-        if not torch.is_tensor(x):
-            raise TypeError(f"{what}: expected a tensor, got {type(x).__name__}")
-        if x.dtype != torch.float32:
-            raise ValueError(f"{what}: expected a float32 tensor, got {x.dtype}")
-        if x.dim() < 2 or x.size(0) != self.B or x.numel() != self.B * self.model.input_dim:
-            raise ValueError(f"{what}: expected {self.B} images of {self.model.input_dim} values (the engine was built with batch_size={self.B}; "
-                             f"use drop_last or pad the last batch), got shape {tuple(x.shape)}")
-        if not x.is_contiguous():
-            raise ValueError(f"{what}: the batch must be contiguous (got strides {tuple(x.stride())}); call .contiguous()")
-        if not x.is_cuda or x.device != self.dev:
-            raise ValueError(f"{what}: expected a tensor on {self.dev}, got one on {x.device}")
+        check_batch(x, what, self.dev, self.B, self.model.input_dim, "images")
 
     def _encode(self, x, noise, nz, out, ws):
         L.call("ardae_model_encode", self.model._desc, self.model._flat, self.pk_m, x, noise, self.B, nz, ws, ws.numel(), out)
@@ -378,14 +311,9 @@ class ArdaeEngine:
             if sname != "main" and not waits:        # a side unit without explicit dependencies still follows what main has queued
                 st.wait_stream(main)
             if capture:
-                g = torch.cuda.CUDAGraph()
-                # (captured on a stream of its own - the default stream cannot capture -, replayed on the unit's stream)
-                with torch.cuda.graph(g, stream=self._cap_stream):
-                    for fn in fns:
-                        fn()
-                out.append(g)
+                out.append(capture_linear(fns, self._cap_stream))       # replayed on the unit's stream
                 with torch.cuda.stream(st):
-                    g.replay()
+                    out[-1].replay()
             elif graphs is not None:
                 if st is main:
                     graphs[k].replay()
@@ -689,38 +617,16 @@ class ArdaeEngine:
     # resp. 'step' / 'square_avg' / 'momentum_buffer', and 'param_groups'), so that files written by the reference loop, by the
     # drop-in modules + net.Adam / net.RMSprop, and by the fused engine are interchangeable.  The caller adds its own
     # bookkeeping keys ('epoch', 'batch_idx', 'best_val_loss', ...) exactly as the reference does.
-    def _per_param(self, module, flat, n_used):
-        out, off = [], 0
-        for name, p in module.named_parameters():
-            k = p.numel()
-            out.append(flat[off:off + k].view_as(p) if off + k <= n_used else None)
-            off += k
-        return out
-
-    def _opt_state(self, module, opt):
-        """torch.optim state_dict()['state'] of one network: {param index: {'step', <buffers of the optimiser>}}; parameters without
-        gradients (the cDAE's trailing bias) and optimisers without state (SGD) contribute nothing."""
-        if not opt.steps or opt.kind == "sgd":
-            return {}
-        views = [self._per_param(module, t, opt.n) for t in opt.buffers()]
-        names = opt.state_names()
-        out = {}
-        for i in range(len(views[0])):
-            if views[0][i] is not None:
-                out[i] = dict({"step": opt.steps}, **{nm: v[i].clone() for nm, v in zip(names, views)})
-        return out
-
     def model_checkpoint(self):
         """With --m-weight-avg the optimiser entry takes the wrapper layout of optim.py ("Weight averaging"): the inner optimiser's state
         under "opt_state", the averaged weights per parameter, n_avg / step_counter in the param group.  Refused while the averaged
         weights are in (the reference saves after use_sgd())."""
         self._require_trained("model_checkpoint()")
-        nparams = len(list(self.model.named_parameters()))
-        opt = {"state": self._opt_state(self.model, self.opt_m), "param_groups": [self.opt_m.param_group(nparams)]}
+        opt = self.opt_m.state_dict(self.model)
         if self.avg is not None:
             n_avg = self._n_avg()
             opt["param_groups"][0].update(n_avg=n_avg, step_counter=self.step_count)
-            bufs = dict(enumerate(v.clone() for v in self._per_param(self.model, self.avg, self.avg.numel()))) if n_avg else {}
+            bufs = dict(enumerate(v.clone() for v in self.model.param_views(self.avg))) if n_avg else {}
             opt = wrap_state_dict(opt, self.wavg, bufs)
         return {"state_dict": {k: t.clone() for k, t in self.model.state_dict().items()},
                 "optimizer": opt,
@@ -729,37 +635,7 @@ class ArdaeEngine:
                            "rng_host_offset": rng.get_state()["offset"], "step_state": self.state.cpu().clone()}}
 
     def cdae_checkpoint(self):
-        nparams = len(list(self.cdae.named_parameters()))
-        return {"state_dict": {k: t.clone() for k, t in self.cdae.state_dict().items()},
-                "optimizer": {"state": self._opt_state(self.cdae, self.opt_c), "param_groups": [self.opt_c.param_group(nparams)]}}
-
-    @staticmethod
-    def _kind_of_group(group):
-        """Which optimiser wrote this torch.optim param_group (utils.Adam / torch.optim.RMSprop / torch.optim.SGD layouts)."""
-        if "betas" in group:
-            return "amsgrad" if group.get("amsgrad") else "adam"
-        return "rmsprop" if "alpha" in group else "sgd"
-
-    def _load_opt_state(self, module, opt, state, what, groups=None):
-        if groups:
-            wrote = self._kind_of_group(groups[0])
-            if wrote != opt.kind:
-                raise ValueError(f"{what}: written by optimiser {wrote!r}, but this engine was built with {opt.kind!r} for that network")
-        for t in opt.buffers():
-            t.zero_()
-        steps = {int(st["step"]) for st in state.values()}
-        if len(steps) > 1:
-            raise ValueError(f"the fused engine keeps one step count per network ({what}: {sorted(steps)})")
-        names = opt.state_names()
-        if state and not all(nm in next(iter(state.values())) for nm in names[:1]):
-            raise ValueError(f"{what}: the checkpoint's optimiser state does not belong to {opt.kind!r} (engine built with TrainConfig."
-                             f"{'m' if opt is self.opt_m else 'd'}_optimizer={opt.kind!r})")
-        with torch.no_grad():
-            for nm, buf in zip(names, opt.buffers()):
-                for i, t in enumerate(self._per_param(module, buf, opt.n)):
-                    if t is not None and i in state and state[i].get(nm) is not None:
-                        t.copy_(state[i][nm])
-        return steps.pop() if steps else 0
+        return {"state_dict": {k: t.clone() for k, t in self.cdae.state_dict().items()}, "optimizer": self.opt_c.state_dict(self.cdae)}
 
     def load_checkpoints(self, model_ckpt, cdae_ckpt):
         """Inverse of model_checkpoint() / cdae_checkpoint(); also accepts files written by the reference loop.  The model's optimiser
@@ -772,9 +648,8 @@ class ArdaeEngine:
         self.model.load_state_dict(model_ckpt["state_dict"])
         self.cdae.load_state_dict(cdae_ckpt["state_dict"])
         eng = model_ckpt.get("engine")
-        m_steps = self._load_opt_state(self.model, self.opt_m, m_opt["state"], "model checkpoint", m_opt.get("param_groups"))
-        c_steps = self._load_opt_state(self.cdae, self.opt_c, cdae_ckpt["optimizer"]["state"], "cdae checkpoint",
-                                       cdae_ckpt["optimizer"].get("param_groups"))
+        m_steps = self.opt_m.load_state_dict(self.model, m_opt, "model checkpoint")
+        c_steps = self.opt_c.load_state_dict(self.cdae, cdae_ckpt["optimizer"], "cdae checkpoint")
         # optimisers without per-parameter state (SGD) carry no step count: the engine's own record, if the file has one
         self.step_count = m_steps if (m_steps or eng is None) else int(eng["step_count"])
         self.opt_m.steps = self.step_count
@@ -787,10 +662,8 @@ class ArdaeEngine:
                 # advance it once, or Adam's t would lag by one for good and the first resumed step would repeat the last step's noise
                 self.opt_m.advance(self.RNG_STRIDE)
         else:                   # written by the reference / the module path: the optimisers' t, and Philox offsets this run has not used yet
-            self.state.zero_()      # (a resumed run with an unchanged seed would otherwise replay the draws of steps 1..step_count)
-            self.state[0] = self.RNG_STRIDE * self.step_count
-            self.state[1] = self.step_count
-            self.opt_m.advance(self.RNG_STRIDE)
+            # (a resumed run with an unchanged seed would otherwise replay the draws of steps 1..step_count)
+            rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt_m.advance(self.RNG_STRIDE))
         self.opt_c.state.zero_()
         self.opt_c.state[1] = self.opt_c.steps
         if self.avg is not None:
@@ -809,7 +682,7 @@ class ArdaeEngine:
     def _load_average(self, m_opt, w_kind, w_bufs):
         groups = m_opt.get("param_groups") or [{}]
         n_avg = int(groups[0].get("n_avg", 0)) if w_kind is not None else 0
-        views = self._per_param(self.model, self.avg, self.avg.numel())
+        views = self.model.param_views(self.avg)
         if n_avg > self.step_count:
             raise ValueError(f"model checkpoint: {n_avg} averaging steps recorded after only {self.step_count} optimiser steps")
         if n_avg > 0:
@@ -832,8 +705,7 @@ class ArdaeEngine:
             tmp = self.model._flat.clone()
             self.model._flat.copy_(self.avg)
             self.avg.copy_(tmp)
-            for p in self.model.parameters():
-                torch.autograd.graph.increment_version(p)
+        bump_versions(self.model)
         self.model.mark_dirty()          # the module path (model.logprob, ...) re-packs its weight image at its next use
         self._pack_model()               # ... and so does the engine's
 
@@ -924,12 +796,9 @@ class ArdaeScoreEngine:
         self.n_grad = dae._flat.numel() - (1 if dae._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
         self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.opt = _FlatOpt(cfg.optimizer, dae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state)
-        if graph not in (True, False):
-            raise ValueError(f"graph must be True or False, got {graph!r}")
-        self.use_graph = bool(graph) and L.debug_knob("ARDAE_GRAPH", "1") != "0"
+        self._ladder = CaptureLadder(self.dev, graph)
         self.fused_front = L.debug_knob("ARDAE_FUSED_DAE_FRONT", "1") != "0" and bool(L.query("ardae_dae_perturb_fused_ok", dae._desc, self.S))
-        self._graph, self._x, self._calls = None, None, 0
-        self._cap_stream = torch.cuda.Stream(device=self.dev)
+        self._x = None
         self._score_ws = {}
         self.step_count = 0
         self.opt.advance(self.RNG_STRIDE)      # the step state always describes the COMING step
@@ -939,19 +808,11 @@ class ArdaeScoreEngine:
         self.dae._packed = None
         self.pk = self.dae._packed_weights()
 
+    _graph = property(lambda self: self._ladder.graph)          # None until the step has been captured
+    use_graph = property(lambda self: self._ladder.on, lambda self, on: setattr(self._ladder, "on", bool(on)))
+
     def _check_batch(self, x, what):
-        """Exactly B * input_dim contiguous fp32 values on the engine's device (ArdaeEngine._check_batch's rules)."""
-        if not torch.is_tensor(x):
-            raise TypeError(f"{what}: expected a tensor, got {type(x).__name__}")
-        if x.dtype != torch.float32:
-            raise ValueError(f"{what}: expected a float32 tensor, got {x.dtype}")
-        if x.dim() < 2 or x.size(0) != self.B or x.numel() != self.B * self.d:
-            raise ValueError(f"{what}: expected {self.B} samples of {self.d} values (the engine was built with batch_size={self.B}), "
-                             f"got shape {tuple(x.shape)}")
-        if not x.is_contiguous():
-            raise ValueError(f"{what}: the batch must be contiguous (got strides {tuple(x.stride())}); call .contiguous()")
-        if not x.is_cuda or x.device != self.dev:
-            raise ValueError(f"{what}: expected a tensor on {self.dev}, got one on {x.device}")
+        check_batch(x, what, self.dev, self.B, self.d)
 
     def _body(self, x, noise):
         d, seed = self.dae._desc, rng.get_state()["seed"]
@@ -977,40 +838,22 @@ class ArdaeScoreEngine:
         """One AR-DAE update on the B samples x [B, d] (each used with nsigma noise levels)."""
         self._check_batch(x, "step(x)")
         if noise is not None:
-            sg, ep = noise["sigma"], noise["eps"]
-            for t, n, nm in ((sg, self.N, "sigma"), (ep, self.N * self.d, "eps")):
-                if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == n):
-                    raise ValueError(f"step(noise): {nm} must be a contiguous float32 tensor of {n} values on {self.dev}")
+            check_tensor(noise["sigma"], "step(noise): sigma", self.dev, numel=self.N)
+            check_tensor(noise["eps"], "step(noise): eps", self.dev, numel=self.N * self.d)
             # into the engine's own buffers: the launches (and stats()) then read what a drawn step would have left there
-            self.sigma.copy_(sg.reshape(-1))
-            self.eps.copy_(ep.reshape(self.N, self.d))
-            self._body(x, {"sigma": self.sigma, "eps": self.eps})
-        elif not self.use_graph:
-            self._body(x, None)
-        else:
-            if self._x is None:
-                self._x = torch.empty(self.B, self.d, device=self.dev, dtype=torch.float32)
-            if x is not self._x:
-                self._x.copy_(x.view(self.B, self.d))
-            if self._graph is not None:
-                self._graph.replay()
-            elif self._calls < 2:               # the first two calls eagerly: every kernel is loaded outside of a capture
-                self._body(self._x, None)
-            else:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=self._cap_stream):
-                    self._body(self._x, None)
-                g.replay()                      # a capture runs nothing
-                self._graph = g
-        self._calls += 1
+            self.sigma.copy_(noise["sigma"].reshape(-1))
+            self.eps.copy_(noise["eps"].reshape(self.N, self.d))
+            noise = {"sigma": self.sigma, "eps": self.eps}
+        elif self.use_graph and x is not self._x:
+            x = self.input_buffer().copy_(x.view(self.B, self.d))      # the static batch buffer the captured launches read
+        self._ladder.run(lambda: self._body(x, noise), eager=noise is not None)
         self._count_step()
 
     def _count_step(self):
         """Host-side bookkeeping of one update (`_body` itself only launches: ArdaeFitEngine runs it inside its own captured iteration)."""
         self.step_count += 1
         self.opt.steps = self.step_count
-        for p in self.dae.parameters():         # the module path re-packs at its next use
-            torch.autograd.graph.increment_version(p)
+        bump_versions(self.dae)
 
     def input_buffer(self):
         """The static batch buffer [B, d]: a sampler that writes its batch there and passes the same tensor to step() saves the copy."""
@@ -1020,8 +863,7 @@ class ArdaeScoreEngine:
 
     def score(self, x, sigma=None):
         """glogprob(x, sigma) with the engine's weight image: x [R, d] (any R), sigma [R] / [R, 1] or None = zeros."""
-        if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.size(1) == self.d):
-            raise ValueError(f"score(x): expected a contiguous float32 [R, {self.d}] tensor on {self.dev}")
+        check_tensor(x, "score(x)", self.dev, shape=(None, self.d))
         R = x.size(0)
         s = torch.zeros(R, device=self.dev) if sigma is None else sigma.detach().to(torch.float32).reshape(-1).contiguous()
         if s.numel() != R:
@@ -1037,3 +879,28 @@ class ArdaeScoreEngine:
         """Host copy of the last step's loss and mean |sigma| (the only synchronising call)."""
         v = torch.cat([self.loss, self.sigma.abs().mean().reshape(1)]).tolist()
         return dict(loss=v[0], sigma_abs_mean=v[1])
+
+    # ------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """The network, its optimiser in torch.optim's layout, and the step count, step-state block and RNG state: everything a resumed
+        run needs to continue bit-identically."""
+        return {"dae": {k: v.clone() for k, v in self.dae.state_dict().items()},
+                "optimizer": self.opt.state_dict(self.dae),
+                "engine": {"step_count": self.step_count, "rng_seed": rng.get_state()["seed"], "rng_host_offset": rng.get_state()["offset"],
+                           "step_state": self.state.cpu().clone()}}
+
+    def load_state_dict(self, sd, default_steps=0):
+        """Inverse of state_dict().  Without the "engine" entry (a checkpoint assembled from torch objects) the step count is the optimiser
+        state's (default_steps where that is empty: SGD) and the block is rebuilt for it: the run continues with Philox offsets it has not used."""
+        self.dae.load_state_dict(sd["dae"])
+        steps = self.opt.load_state_dict(self.dae, sd["optimizer"], "AR-DAE checkpoint")
+        eng = sd.get("engine")
+        self.step_count = self.opt.steps = int(eng["step_count"]) if eng is not None else (steps or int(default_steps))
+        if eng is not None:
+            rng.manual_seed(eng["rng_seed"], eng["rng_host_offset"])
+            self.state.copy_(eng["step_state"].to(self.dev))
+        else:
+            rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt.advance(self.RNG_STRIDE))
+        self._ladder.reset()                    # parameters were rewritten outside of the captured step
+        bump_versions(self.dae)
+        self.repack()

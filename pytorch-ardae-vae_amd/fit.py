@@ -14,6 +14,7 @@ from . import _lib as L
 from . import energy as E
 from . import rng
 from .engine import ArdaeScoreEngine, ScoreConfig, annealing_func
+from .engine_common import CaptureLadder, bump_versions, check_tensor, rebuild_step_state
 from .modules import Generator
 
 FIT_STATE_WORDS = L.CONSTANTS["ARDAE_FIT_STATE_BYTES"] // 8          # the block as int64 words; floats 8 .. 11 are its tail
@@ -83,8 +84,6 @@ class ArdaeFitEngine:
         if not isinstance(generator, Generator):
             raise TypeError("ArdaeFitEngine drives net.Generator")
         generator._require_gpu()
-        if graph not in (True, False):
-            raise ValueError(f"graph must be True or False, got {graph!r}")
         if int(batch_size) < 1:
             raise ValueError(f"batch_size must be positive, got {batch_size}")
         self.gen, self.dae, self.cfg = generator, dae, cfg
@@ -100,6 +99,7 @@ class ArdaeFitEngine:
         self.dev = generator._flat.device
         if self.score.dev != self.dev:
             raise ValueError(f"generator on {self.dev}, score network on {self.score.dev}")
+        self._ladder = CaptureLadder(self.dev, graph)
         self.net = generator._net
         f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
         B, d = self.B, self.d
@@ -113,14 +113,14 @@ class ArdaeFitEngine:
         self.grads = torch.zeros_like(generator._flat)
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(generator._flat), torch.zeros_like(generator._flat)
         self.state = torch.zeros(FIT_STATE_WORDS, dtype=torch.int64, device=self.dev)
-        self.use_graph = bool(graph) and L.debug_knob("ARDAE_GRAPH", "1") != "0"
         self.fused_front = L.debug_knob("ARDAE_FUSED_GEN_FRONT", "1") != "0" and bool(L.query("ardae_gen_draw_fused_ok", *self.net))
-        self._graph, self._calls = None, 0
-        self._cap_stream = torch.cuda.Stream(device=self.dev)
         self._sample_ws = {}
         self.step_count = 0
         self._advance()                # the fit state always describes the COMING iteration
         self.repack()
+
+    _graph = property(lambda self: self._ladder.graph)          # None until the iteration has been captured
+    use_graph = property(lambda self: self._ladder.on, lambda self, on: setattr(self._ladder, "on", bool(on)))
 
     # ------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -183,34 +183,17 @@ class ArdaeFitEngine:
         if not isinstance(noise, dict) or set(noise) != set(want):
             raise ValueError(f"step(noise): expected a dict with the keys {sorted(want)}")
         for k, shape in want.items():
-            t = noise[k]
-            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and t.device == self.dev and t.is_contiguous()
-                    and tuple(t.shape) == shape):
-                raise ValueError(f"step(noise): {k} must be a contiguous float32 tensor of shape {list(shape)} on {self.dev}")
+            check_tensor(noise[k], f"step(noise): {k}", self.dev, shape=shape)
 
     def step(self, noise=None):
         """One iteration of ardae_fit.ipynb."""
         if noise is not None:
             self._check_noise(noise)
-            self._body(noise)
-        elif not self.use_graph:
-            self._body(None)
-        elif self._graph is not None:
-            self._graph.replay()
-        elif self._calls < 2:                   # the first two calls eagerly: every kernel is loaded outside of a capture
-            self._body(None)
-        else:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self._cap_stream):
-                self._body(None)
-            g.replay()                          # a capture runs nothing
-            self._graph = g
-        self._calls += 1
+        self._ladder.run(lambda: self._body(noise), eager=noise is not None)
         self.step_count += 1
         for _ in range(self.U):
             self.score._count_step()
-        for p in self.gen.parameters():         # the module path re-packs at its next use
-            torch.autograd.graph.increment_version(p)
+        bump_versions(self.gen)
 
     def sample(self, n):
         """n generator samples [n, input_dim] with the current weights; draws from the host Philox stream, touches no training state."""
@@ -232,43 +215,27 @@ class ArdaeFitEngine:
         return dict(model_loss=v[0], dae_loss=v[1], alpha=v[2], lr=v[3])
 
     # ------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _per_param(module, flat):
-        return [flat[off:off + n].view(shape) for off, n, shape in (module._offs[name] for name, _ in module.named_parameters())]
-
     def state_dict(self):
         """Generator, torch.optim.Adam's state_dict() layout for it plus the schedule's last_epoch, the AR-DAE and its optimiser, and the
         RNG state: everything a resumed run needs to continue bit-identically."""
-        c, t, sc = self.cfg, self.step_count, self.score
-        nparams = len(list(self.gen.named_parameters()))
-        adam = {}
-        if t:
-            for i, (m, v) in enumerate(zip(self._per_param(self.gen, self.exp_avg), self._per_param(self.gen, self.exp_avg_sq))):
-                adam[i] = {"step": torch.tensor(float(t)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        c, t, dae = self.cfg, self.step_count, self.score.state_dict()
+        views = list(zip(self.gen.param_views(self.exp_avg), self.gen.param_views(self.exp_avg_sq)))
+        adam = {i: {"step": torch.tensor(float(t)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()} for i, (m, v) in enumerate(views)} if t else {}
         group = {"lr": step_lr(c, t), "betas": (float(c.m_beta1), 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "initial_lr": float(c.lr), "params": list(range(nparams))}
-        dae_state = {}
-        if sc.opt.steps and sc.opt.kind != "sgd":
-            names = sc.opt.state_names()
-            views = [self._per_param(self.dae, b) for b in sc.opt.buffers()]
-            for i, (name, _) in enumerate(self.dae.named_parameters()):
-                if name not in self.dae._no_grad_names:
-                    dae_state[i] = dict({"step": sc.opt.steps}, **{nm: v[i].clone() for nm, v in zip(names, views)})
+                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "initial_lr": float(c.lr), "params": list(range(len(views)))}
         return {"generator": {k: v.clone() for k, v in self.gen.state_dict().items()},
                 "optimizer": {"state": adam, "param_groups": [group]},
                 "scheduler": {"step_size": int(c.lr_step_size), "gamma": float(c.lr_gamma), "min_lr": float(c.lr_min), "base_lrs": [float(c.lr)],
                               "last_epoch": t, "_last_lr": [step_lr(c, t)]},
-                "dae": {k: v.clone() for k, v in self.dae.state_dict().items()},
-                "dae_optimizer": {"state": dae_state, "param_groups": [sc.opt.param_group(len(list(self.dae.named_parameters())))]},
-                "engine": {"step_count": t, "dae_steps": sc.step_count, "rng_seed": rng.get_state()["seed"], "rng_host_offset": rng.get_state()["offset"],
-                           "fit_state": self.state.cpu().clone(), "dae_step_state": sc.state.cpu().clone()}}
+                "dae": dae["dae"], "dae_optimizer": dae["optimizer"],
+                "engine": {"step_count": t, "dae_steps": dae["engine"]["step_count"], "rng_seed": dae["engine"]["rng_seed"],
+                           "rng_host_offset": dae["engine"]["rng_host_offset"], "fit_state": self.state.cpu().clone(),
+                           "dae_step_state": dae["engine"]["step_state"]}}
 
     def load_state_dict(self, sd):
         """Inverse of state_dict().  Without the "engine" entry (a checkpoint assembled from torch objects) the iteration count is the
         schedule's last_epoch and the device blocks are rebuilt for it: the run continues with Philox offsets it has not used."""
-        sc = self.score
         self.gen.load_state_dict(sd["generator"])
-        self.dae.load_state_dict(sd["dae"])
         eng = sd.get("engine")
         t = int(sd["scheduler"]["last_epoch"]) if eng is None else int(eng["step_count"])
         steps = {int(st["step"]) for st in sd["optimizer"]["state"].values()}
@@ -277,33 +244,20 @@ class ArdaeFitEngine:
         with torch.no_grad():
             for buf, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
                 buf.zero_()
-                for i, v in enumerate(self._per_param(self.gen, buf)):
+                for i, v in enumerate(self.gen.param_views(buf)):
                     if i in sd["optimizer"]["state"]:
                         v.copy_(sd["optimizer"]["state"][i][key])
-            dstate = sd["dae_optimizer"]["state"]
-            for buf, key in zip(sc.opt.buffers(), sc.opt.state_names()):
-                buf.zero_()
-                for i, v in enumerate(self._per_param(self.dae, buf)):
-                    if i in dstate:
-                        if key not in dstate[i]:
-                            raise ValueError(f"the AR-DAE's optimiser state does not belong to {sc.opt.kind!r} (no {key!r})")
-                        v.copy_(dstate[i][key])
-        dsteps = {int(st["step"]) for st in sd["dae_optimizer"]["state"].values()}
-        if len(dsteps) > 1:
-            raise ValueError(f"the AR-DAE's optimiser state holds several step counts ({sorted(dsteps)})")
-        self.step_count = t
-        sc.step_count = sc.opt.steps = int(eng["dae_steps"]) if eng is not None else (dsteps.pop() if dsteps else t * self.U)
+        # the AR-DAE half is the score engine's own checkpoint under this dictionary's keys (it restores the RNG state too)
+        dae = {"dae": sd["dae"], "optimizer": sd["dae_optimizer"]}
         if eng is not None:
-            rng.manual_seed(eng["rng_seed"], eng["rng_host_offset"])
+            dae["engine"] = {"step_count": eng["dae_steps"], "rng_seed": eng["rng_seed"], "rng_host_offset": eng["rng_host_offset"],
+                             "step_state": eng["dae_step_state"]}
+        self.score.load_state_dict(dae, default_steps=t * self.U)
+        self.step_count = t
+        if eng is not None:
             self.state.copy_(eng["fit_state"].to(self.dev))
-            sc.state.copy_(eng["dae_step_state"].to(self.dev))
         else:
-            for block, n, adv in ((self.state, t, self._advance), (sc.state, sc.step_count, lambda: sc.opt.advance(self.RNG_STRIDE))):
-                block.zero_()
-                block[0], block[1] = self.RNG_STRIDE * n, n
-                adv()
-        self._graph, self._calls = None, 0       # parameters were rewritten outside of the captured iteration
-        for m in (self.gen, self.dae):
-            for p in m.parameters():
-                torch.autograd.graph.increment_version(p)
+            rebuild_step_state(self.state, t, self.RNG_STRIDE, self._advance)
+        self._ladder.reset()                     # parameters were rewritten outside of the captured iteration
+        bump_versions(self.gen)
         self.repack()

@@ -42,6 +42,8 @@ class _EncodeBox(_Box):
 
 
 class FlatParamModule(nn.Module):
+    _no_grad_names = frozenset()     # parameters that receive no gradient (and keep no optimiser state)
+
     def _build_params(self, spec, boxes=None):
         boxes = boxes or {}
         self._spec = spec
@@ -95,6 +97,12 @@ class FlatParamModule(nn.Module):
     def flat_params(self):
         return self._flat
 
+    def param_views(self, flat, grads_only=False):
+        """A buffer laid out like `_flat` (gradients, optimiser state, an average) as per-parameter views in named_parameters() order;
+        grads_only: None in the place of a parameter that receives no gradient."""
+        return [None if grads_only and name in self._no_grad_names else flat[off:off + n].view(shape)
+                for name, (off, n, shape) in ((name, self._offs[name]) for name, _ in self.named_parameters())]
+
     def _default_init(self):
         """nn.Linear's default init (kaiming_uniform(a=sqrt 5) == U(+-1/sqrt(fan_in)) for weight and bias)."""
         spec = dict(self._spec)
@@ -118,7 +126,8 @@ class FlatParamModule(nn.Module):
     def _ws(self, nfloats):
         return torch.empty(nfloats, device=self._flat.device, dtype=torch.float32)
 
-    _packed_floats_fn = _pack_fn = None      # the network family's two entry points (ardae_cdae_* | ardae_model_*)
+    _packed_floats_fn = _pack_fn = None      # the network family's two entry points (ardae_cdae_* | ardae_model_* | ardae_gen_*), which
+    _abi = None                              # take the network as `*self._abi`: (descriptor,), the generator's five integers
 
     def _packed_weights(self):
         """MFMA-lane-linear image of the current weights (policy: _pack_is_current; the fused engine keeps its own image and re-packs
@@ -126,8 +135,8 @@ class FlatParamModule(nn.Module):
         if self._pack_is_current():
             return self._packed
         if self._packed is None:
-            self._packed = self._ws(L.query(self._packed_floats_fn, self._desc))
-        L.call(self._pack_fn, self._desc, self._flat, self._packed)
+            self._packed = self._ws(L.query(self._packed_floats_fn, *self._abi))
+        L.call(self._pack_fn, *self._abi, self._flat, self._packed)
         self._note_packed()
         return self._packed
 
@@ -160,15 +169,8 @@ class _ArdaeLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss):
-        mod = ctx.mod
-        out = []
-        for name, p in mod.named_parameters():
-            if name in mod._no_grad_names:
-                out.append(None)      # the reference leaves .grad = None here: the energy's offset does not reach its input-gradient
-                continue
-            off, n, shape = mod._offs[name]
-            out.append(ctx.grads[off:off + n].view(shape) * gloss)
-        return (None,) * 7 + tuple(out)
+        # (no gradient: the reference leaves .grad = None there - the energy's offset does not reach its input-gradient)
+        return (None,) * 7 + tuple(None if g is None else g * gloss for g in ctx.mod.param_views(ctx.grads, grads_only=True))
 
 
 class _ScoreNet(FlatParamModule):
@@ -190,8 +192,10 @@ class _ScoreNet(FlatParamModule):
         self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
         self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
         self._desc = L.CdaeDesc(first_kind if self._kind == "grad" else first_kind + 1, input_dim, context_dim, h_dim, num_hidden_layers, L.ACT[nonlinearity])
+        self._abi = (self._desc,)
         self._build_params(spec)
-        self._no_grad_names = {"neglogprob.fc.bias"} if self._kind == "grad" else set()
+        if self._kind == "grad":
+            self._no_grad_names = frozenset({"neglogprob.fc.bias"})
         self._default_init()
 
 
@@ -325,7 +329,7 @@ class _GenFn(torch.autograd.Function):
         mod = ctx.mod
         grads = torch.zeros_like(mod._flat)
         L.call("ardae_gen_backward", *mod._net, mod._flat, mod._packed_weights(), ctx.z, _f32c(dx), ctx.z.size(0), ctx.ws, ctx.ws.numel(), grads)
-        return (None, None) + tuple(grads[off:off + n].view(shape) for off, n, shape in (mod._offs[name] for name, _ in mod.named_parameters()))
+        return (None, None) + tuple(mod.param_views(grads))
 
 
 class Generator(FlatParamModule):
@@ -334,14 +338,7 @@ class Generator(FlatParamModule):
     main.{0, 2, 4, ...}.{weight, bias}.  `energy_func`: what `loss` averages (the notebook reads a global; default net.energy.energy_func4,
     the notebook's choice)."""
 
-    def _packed_weights(self):
-        if self._pack_is_current():
-            return self._packed
-        if self._packed is None:
-            self._packed = self._ws(L.query("ardae_gen_packed_floats", *self._net))
-        L.call("ardae_gen_pack", *self._net, self._flat, self._packed)
-        self._note_packed()
-        return self._packed
+    _packed_floats_fn, _pack_fn = "ardae_gen_packed_floats", "ardae_gen_pack"
 
     def __init__(self, input_dim=2, hidden_dim=64, z_dim=2, num_hidden_layers=3, nonlinearity="relu", energy_func=None):
         super().__init__()
@@ -357,7 +354,7 @@ class Generator(FlatParamModule):
             energy_func = energy.energy_func4
         self.energy_func = energy_func
         # the network as the ABI takes it: z_dim, h_dim, n_layers, out_dim, act
-        self._net = (self.z_dim, self.hidden_dim, self.num_hidden_layers, self.input_dim, L.ACT[nonlinearity])
+        self._net = self._abi = (self.z_dim, self.hidden_dim, self.num_hidden_layers, self.input_dim, L.ACT[nonlinearity])
         self._build_params(layout.gen_spec(self.input_dim, self.hidden_dim, self.z_dim, self.num_hidden_layers))
         self._default_init()
 
@@ -410,11 +407,7 @@ class _VaeFn(torch.autograd.Function):
         dzc = _f32c(dz).view(B * ctx.nz, mod.z_dim) if dz is not None else None
         L.call("ardae_model_vae_backward", mod._desc, mod._flat, mod._packed_weights(), ctx.x, ctx.noise, B, ctx.nz, ctx.beta, dl, dzc, ctx.ws,
                ctx.ws.numel(), grads, 0.0)
-        out = []
-        for name, _ in mod.named_parameters():
-            off, n, shape = mod._offs[name]
-            out.append(grads[off:off + n].view(shape))
-        return (None,) * 5 + tuple(out)
+        return (None,) * 5 + tuple(mod.param_views(grads))
 
 
 class ImplicitPosteriorVAE(FlatParamModule):
@@ -438,6 +431,7 @@ class ImplicitPosteriorVAE(FlatParamModule):
         flags = L.MODEL_NO_CENTER if self._kind in ("resconv", "auxresconv") and not getattr(self, "do_center", True) else 0
         flags |= getattr(self, "_flag_extra", 0)
         self._desc = L.ModelDesc(KIND_IDS[self._kind], input_dim, noise_dim, h_dim, z_dim, num_hidden_layers, L.ACT[nonlinearity], flags)
+        self._abi = (self._desc,)
         # floats per row of a sampler draw: the aux models take two draws per call, laid out side by side [eps0 | eps]
         self._noise_width = noise_dim + z_dim if self._kind in AUX_KINDS else noise_dim
         # columns of the `hidden1a` cDAE context (ivae_ardae.py:572-580): cat(h0, h) for the MLP / conv aux models, h alone for auxresconv

@@ -206,3 +206,92 @@ def test_restatement_reproduces_the_fp64_fixtures(golden_dir):
                 assert rel(g, fx["g64/" + n]) <= 1e-12, (path, n, rel(g, fx["g64/" + n]))
         assert rel(score(kind, p, act, x, torch.zeros_like(std)), fx["glog0_64"]) <= 1e-12, path
         assert rel(score(kind, p, act, x, std), fx["glog_64"]) <= 1e-12, path
+
+
+# ---- 5. host logic the engines share (engine_common.py): per-parameter views, the optimiser's checkpoint ---------------------------
+def test_param_views_alias_the_parameters_and_name_the_tensor_without_gradient():
+    mods = [net.MLPGradARDAE(input_dim=3, h_dim=16, num_hidden_layers=2, nonlinearity="elu"),
+            net.MLPGradCARDAE(input_dim=4, context_dim=4, h_dim=16, num_hidden_layers=2, nonlinearity="softplus"),
+            net.MLPResCARDAE(input_dim=4, context_dim=4, h_dim=16, num_hidden_layers=2, nonlinearity="softplus"),
+            net.Generator(hidden_dim=16, z_dim=3, num_hidden_layers=2),
+            net.MNISTIPVAE(input_dim=24, noise_dim=6, h_dim=16, z_dim=4, num_hidden_layers=1, nonlinearity="softplus", enc_type="concat")]
+    for m in mods:
+        flat, params = m.flat_params(), list(m.named_parameters())
+        views = m.param_views(flat)
+        assert len(views) == len(params) and sum(v.numel() for v in views) == flat.numel()
+        for v, (name, p) in zip(views, params):
+            assert v.data_ptr() == p.data_ptr() and v.shape == p.shape, name
+        other = torch.zeros_like(flat)                      # any buffer of that layout, not the parameters alone
+        assert [v.data_ptr() - other.data_ptr() for v in m.param_views(other)] == [v.data_ptr() - flat.data_ptr() for v in views]
+        grad_kind = isinstance(m, (net.MLPGradARDAE, net.MLPGradCARDAE))
+        assert set(m._no_grad_names) == ({"neglogprob.fc.bias"} if grad_kind else set())
+        masked = m.param_views(flat, grads_only=True)
+        assert [v is None for v in masked] == [name in m._no_grad_names for name, _ in params]
+        assert all(v is None or v.data_ptr() == w.data_ptr() for v, w in zip(masked, views))
+        if grad_kind:
+            # it is the LAST tensor of the layout: "the first numel - 1 floats" (_FlatOpt.n, a kernel argument) and the name set say the same
+            assert params[-1][0] == "neglogprob.fc.bias" and m._offs["neglogprob.fc.bias"][:2] == (flat.numel() - 1, 1)
+            assert sum(v.numel() for v in masked if v is not None) == flat.numel() - 1
+
+
+def _flat_opt(kind, seed=0):
+    from ardae_amd.engine import _FlatOpt
+    torch.manual_seed(seed)
+    m = net.MLPGradARDAE(input_dim=3, h_dim=16, num_hidden_layers=2, nonlinearity="elu")
+    return m, _FlatOpt(kind, m.flat_params(), m.flat_params().numel() - 1, 1e-3, 0.5, 0.5)        # construction launches nothing
+
+
+def _filled(kind):
+    m, opt = _flat_opt(kind)
+    opt.steps = 3
+    for k, b in enumerate(opt.buffers()):
+        b.copy_(torch.arange(b.numel()) + 10000.0 * (k + 1))
+    return m, opt
+
+
+@pytest.mark.parametrize("kind", ["sgd", "rmsprop", "adam", "amsgrad"])
+def test_flat_opt_state_dict_has_torchs_layout_and_round_trips(kind):
+    m, opt = _filled(kind)
+    assert opt.n == m.flat_params().numel() - len(m._no_grad_names)
+    sd = opt.state_dict(m)
+    assert list(sd) == ["state", "param_groups"]
+    params = [p for _, p in m.named_parameters()]
+    ref = {"sgd": lambda: torch.optim.SGD(params, lr=1e-3), "rmsprop": lambda: torch.optim.RMSprop(params, lr=1e-3, momentum=0.5),
+           "adam": lambda: torch.optim.Adam(params, lr=1e-3, betas=(0.5, 0.999)),
+           "amsgrad": lambda: torch.optim.Adam(params, lr=1e-3, betas=(0.5, 0.999), amsgrad=True)}[kind]()
+    g = torch.Generator().manual_seed(1)
+    for name, p in m.named_parameters():
+        p.grad = None if name in m._no_grad_names else torch.randn(p.shape, generator=g)
+    ref.step()
+    want = ref.state_dict()
+    assert list(sd["state"]) == list(want["state"]) == ([] if kind == "sgd" else list(range(len(params) - 1)))      # no entry for the bias
+    for i, st in sd["state"].items():
+        assert list(st) == list(want["state"][i]) == ["step"] + list(opt.state_names())
+        assert st["step"] == 3 and all(st[k].shape == params[i].shape for k in opt.state_names())
+    assert set(sd["param_groups"][0]) <= set(want["param_groups"][0]) and sd["param_groups"][0]["params"] == want["param_groups"][0]["params"]
+    assert len(sd["param_groups"]) == len(want["param_groups"]) == 1
+    # into a second optimiser over a fresh module
+    m2, opt2 = _flat_opt(kind, seed=1)
+    for b in opt2.buffers():
+        b.fill_(-1.0)
+    assert opt2.load_state_dict(m2, sd, "checkpoint") == (0 if kind == "sgd" else 3)
+    assert len(opt2.buffers()) == len(opt.buffers()) == len(opt.state_names())
+    for a, b in zip(opt.buffers(), opt2.buffers()):
+        assert torch.equal(a[:opt.n], b[:opt.n]) and float(b[opt.n:].abs().sum()) == 0.0      # the bias keeps no state
+    assert opt2.state_dict(m2)["state"] == {} and opt2.steps == 0                                    # the step count is the caller's to set
+    opt2.steps = 3
+    again = opt2.state_dict(m2)
+    assert all(torch.equal(again["state"][i][k], sd["state"][i][k]) for i in sd["state"] for k in opt.state_names())
+
+
+def test_flat_opt_refuses_foreign_and_inconsistent_state():
+    m, rms = _filled("rmsprop")
+    sd = rms.state_dict(m)
+    _, adam = _flat_opt("adam")
+    with pytest.raises(ValueError, match="written by optimiser 'rmsprop', but this engine was built with 'adam'"):
+        adam.load_state_dict(m, sd, "checkpoint")
+    with pytest.raises(ValueError, match="does not belong to 'adam'"):
+        adam.load_state_dict(m, {"state": sd["state"]}, "checkpoint")                                 # no param_groups: the state's own keys
+    sd["state"][1]["step"] = 4
+    with pytest.raises(ValueError, match=r"one step count per network \(checkpoint: \[3, 4\]\)"):
+        rms.load_state_dict(m, sd, "checkpoint")

@@ -379,6 +379,60 @@ def test_engine_refuses_bad_batches():
         net.ArdaeScoreEngine(fresh_module("grad", 2, 64, 3, "softplus"), net.ScoreConfig(optimizer="lbfgs"), 32)
 
 
+def test_engine_refuses_noise_on_another_device():
+    """Injected noise is validated like a batch: a tensor on the host or on another GPU is refused before anything is launched."""
+    B, ns, d = 30, 4, 3
+    eng = net.ArdaeScoreEngine(fresh_module("grad", d, 64, 2, "elu"), net.ScoreConfig(nsigma=ns), B)
+    before = [eng.dae.flat_params().clone(), eng.state.clone(), eng.sigma.clone()] + [b.clone() for b in eng.opt.buffers()]
+    x, eps = torch.zeros(B, d, device="cuda:0"), torch.zeros(B * ns, d, device="cuda:0")
+    for other in ["cpu"] + (["cuda:1"] if torch.cuda.device_count() > 1 else []):
+        with pytest.raises(ValueError, match="sigma must be"):
+            eng.step(x, noise={"sigma": torch.zeros(B * ns, device=other), "eps": eps})
+        with pytest.raises(ValueError, match="eps must be"):
+            eng.step(x, noise={"sigma": torch.zeros(B * ns, device="cuda:0"), "eps": eps.to(other)})
+    after = [eng.dae.flat_params(), eng.state, eng.sigma] + eng.opt.buffers()
+    assert eng.step_count == 0 and all(torch.equal(a, b) for a, b in zip(before, after)), "a refused call reached the device"
+
+
+@pytest.mark.parametrize("kind,optimizer", [("grad", "rmsprop"), ("grad", "amsgrad"), ("res", "adam")])
+def test_score_engine_resumes_bit_identically(kind, optimizer):
+    """state_dict() after step 4 into a fresh engine under another library seed: steps 5 - 8 (eager, eager, captured, replayed there) leave
+    what the uninterrupted run leaves.  B 30 x 4 levels, d 3, h 64: the trailing bias without gradient (grad), three optimiser buffers
+    (amsgrad), a partial 64-row tile and the fused front end."""
+    B, ns, d, h, nl, act = 30, 4, 3, 64, 2, "elu"
+    cfg = net.ScoreConfig(delta=1.0, nsigma=ns, lr=1e-3, optimizer=optimizer)
+    xs = [torch.randn(B, d, generator=torch.Generator().manual_seed(s)).cuda() for s in range(8)]
+    runs, sd = [], None
+    for resumed in (False, True):
+        net.manual_seed(77)
+        eng = net.ArdaeScoreEngine(fresh_module(kind, d, h, nl, act), cfg, B)
+        assert eng.fused_front
+        losses = []
+        for i, x in enumerate(xs):
+            if resumed and i == 4:
+                sd = eng.state_dict()
+                net.manual_seed(1)                                 # the checkpoint, not the process, carries the RNG state
+                eng = net.ArdaeScoreEngine(fresh_module(kind, d, h, nl, act, seed=5), cfg, B, graph=True)
+                eng.load_state_dict(sd)
+                assert eng._graph is None and (eng.step_count, eng.opt.steps) == (4, 4)
+            eng.step(x)
+            losses.append(eng.loss.clone())
+        torch.cuda.synchronize()
+        assert eng._graph is not None
+        runs.append([eng.dae.flat_params().clone(), eng.state.clone(), eng.sigma.clone(), torch.cat(losses)[4:]] + [b.clone() for b in eng.opt.buffers()])
+    assert len(runs[0]) == len(runs[1]) == 4 + len(eng.opt.state_names())
+    assert all(torch.equal(a, b) for a, b in zip(*runs)), "the resumed run drifted"
+    assert torch.isfinite(runs[0][3]).all() and len(set(runs[0][3].tolist())) == 4
+    # a checkpoint assembled from torch objects has no "engine" entry: the block is rebuilt for the coming step, n = 4 steps done
+    assert list(sd) == ["dae", "optimizer", "engine"] and [int(st["step"]) for st in sd["optimizer"]["state"].values()] == [4] * len(sd["optimizer"]["state"])
+    del sd["engine"]
+    new = net.ArdaeScoreEngine(fresh_module(kind, d, h, nl, act, seed=5), cfg, B)
+    new.load_state_dict(sd)
+    assert new.step_count == 4 and new.state[:2].tolist() == [16 * 5, 5]
+    new.step(xs[4])
+    assert np.isfinite(new.stats()["loss"]) and new.state[:2].tolist() == [16 * 6, 6]
+
+
 # ---- 10. quality: device seeds against the reference's seeds ----------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["grad", "res"])
 def test_training_quality_against_the_reference_seeds(golden_dir, kind):
