@@ -165,6 +165,19 @@ int ardae_philox_normal_at(float* out, int64_t n, uint64_t seed, uint64_t offset
                            void* stream);
 int ardae_adam_ref_step_dev(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
                             double beta1, double beta2, double eps, const void* state, void* stream);
+/* The TRAIN STATE: the step state with the KL weight of the coming step in its last 8 bytes - f32 beta (bytes 24..27), f32 seed_scale
+ * (bytes 28..31), which no step-state consumer reads - so that a captured step replays through --beta-annealing (ivae_ardae.py:704).
+ * `ardae_train_state_advance` does what ardae_step_state_advance does and then, for the new t and i = t - 1 (the reference's zero-based
+ * i_ep), in double, every operation rounded on its own and in this order (utils/msc.py:53-55, the host's Python arithmetic bit for bit):
+ *   beta = beta_annealing < 0 ? beta_fin : beta_init + (beta_fin - beta_init) / beta_annealing * min(beta_annealing, i)
+ *   seed_scale = std_scale * beta / seed_rows      the factor of the entropy seed, ivae_ardae.py:834 (seed_rows = B * nz of the VAE batch)
+ * each rounded to float once.  beta_annealing == 0 and seed_rows <= 0 are argument errors.  The `_dev` twins of the entry points that
+ * take `float beta` / `float seed_scale` (ardae_model_vae_forward_dev, ..., ardae_log_scalars_dev) take the block in its place; the
+ * kernels are the value forms' own, reading the float through a pointer. */
+int ardae_train_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double beta_init, double beta_fin,
+                              int64_t beta_annealing, double std_scale, int64_t seed_rows, void* stream);
+/* g[i] *= state.seed_scale, i < n: the entropy seed of the single-call backward (ardae_model_vae_backward_dev takes dz_extra scaled) */
+int ardae_seed_scale_dev(float* g, int64_t n, const void* state, void* stream);
 /* Weight averaging of the model parameters: --m-weight-avg swa | polyak (torchcontrib.optim.SWA / Polyak around the model
  * optimiser, ivae_ardae.py:158-164,559-565, freq 1).  t = model-optimiser steps done, the current one included: state.adam_step
  * when state is non-NULL (read on the device: a captured step replays correctly), else the argument t.  origin = the t of the
@@ -377,6 +390,9 @@ int ardae_model_encode_pair(const ardae_model_desc* d, const float* params, cons
 int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
                             const float* noise, int B, int nz, float beta, float* workspace, size_t workspace_floats,
                             float* z_out, float* losses, void* stream);
+int ardae_model_vae_forward_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                const float* noise, int B, int nz, const void* state, float* workspace, size_t workspace_floats,
+                                float* z_out, float* losses, void* stream);
 /* Aux models (kinds 3 and 4): the std = 0 pass of the sampler, returning the latent mean z0 [B, z] (may be NULL) AND the encoder hiddens
  * cat(h0, h) [B, 2 h] that --cdae-ctx-type hidden1a uses as the cDAE context (ivae_ardae.py:737-739, ivae/auxmnist.py:125-132).
  * Workspace: mode 0 with nz = 1. */
@@ -400,6 +416,9 @@ int ardae_model_loss_rows(const ardae_model_desc* d, const float* out0, const fl
 int ardae_model_vae_backward(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
                              const float* noise, int B, int nz, float beta, float dloss, const float* dz_extra,
                              float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
+int ardae_model_vae_backward_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                 const float* noise, int B, int nz, const void* state, float dloss, const float* dz_extra,
+                                 float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
 /* The same backward in two calls, for callers that compute the entropy seed late (ivae_ardae.py:829-834: it needs the UPDATED
  * cDAE): _decoder = model_loss.backward() through the decoder down to dL/dz (:804; needs only the vae_forward workspace, so it
  * can run beside the cDAE update), _sampler = dL/dz += seed_scale * dz_extra (:834), back-propagation through the sampler and
@@ -410,6 +429,12 @@ int ardae_model_vae_backward_decoder(const ardae_model_desc* d, const float* par
 int ardae_model_vae_backward_sampler(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
                                      const float* noise, int B, int nz, const float* dz_extra, float seed_scale,
                                      float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
+int ardae_model_vae_backward_decoder_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                         const float* noise, int B, int nz, const void* state, float dloss, float* workspace,
+                                         size_t workspace_floats, void* stream);
+int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                         const float* noise, int B, int nz, const float* dz_extra, const void* state,
+                                         float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
 
 
 /* ---- evaluation / visualisation side of the model surface (csrc/eval_kernels.hip) ----------------------------
@@ -436,6 +461,9 @@ int ardae_cholesky_batched(const float* A, int batch, int n, float* L, void* str
 #define ARDAE_LOG_RECORD_FLOATS 16
 int ardae_log_scalars(const float* cdae_loss, const float* model_losses, const float* std_b, int B, float beta, float d_lr,
                       const void* state, float* ring, int capacity, void* stream);
+/* record [4] = beta_state's beta (a train state; `state` stays the block whose t numbers the record - the engine passes one block twice) */
+int ardae_log_scalars_dev(const float* cdae_loss, const float* model_losses, const float* std_b, int B, const void* beta_state, float d_lr,
+                          const void* state, float* ring, int capacity, void* stream);
 /* out[b, :] = table[idx[b], :]: a batch of a statically binarised set (fixed pre-drawn rows, datasets/sbmnist.py:34-60) by
  * int64 row indices, all on the device */
 int ardae_gather_rows(const float* table, const int64_t* idx, int B, int D, float* out, void* stream);

@@ -100,6 +100,15 @@ int ardae_adam_ref_step(float* p, const float* g, float* exp_avg, float* exp_avg
 int ardae_step_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, void* stream) {
   return launch_step_state_advance(state, rng_inc, lr, beta1, beta2, (hipStream_t)stream);
 }
+int ardae_train_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double beta_init, double beta_fin,
+                              int64_t beta_annealing, double std_scale, int64_t seed_rows, void* stream) {
+  return launch_train_state_advance(state, rng_inc, lr, beta1, beta2, beta_init, beta_fin, beta_annealing, std_scale, seed_rows,
+                                    (hipStream_t)stream);
+}
+int ardae_seed_scale_dev(float* g, int64_t n, const void* state, void* stream) {
+  ARDAE_CHECK_ARG(state, "seed_scale_dev: state is NULL");
+  return launch_scale(g, n, train_state_seed_scale(state), (hipStream_t)stream);
+}
 int ardae_philox_normal_dev(float* out, int64_t n, uint64_t seed, const void* state, uint64_t offset_add, void* stream) {
   return launch_philox_normal_dev(out, n, seed, state, offset_add, (hipStream_t)stream);
 }

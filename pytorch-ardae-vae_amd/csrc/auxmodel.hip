@@ -270,7 +270,7 @@ int aux_encode(const ardae_model_desc& d, const float* params, const float* pack
 }
 
 int aux_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                    float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+                    DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
   AuxEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_forward: workspace too small");
@@ -284,7 +284,7 @@ int aux_vae_forward(const ardae_model_desc& d, const float* params, const float*
 }
 
 int aux_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
+                     DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
                      hipStream_t st) {
   (void)noise;
   AuxEntry entry(d, workspace, wsf, B, nz, 1);

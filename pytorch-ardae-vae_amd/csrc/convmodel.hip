@@ -297,7 +297,7 @@ int conv_decode(const ardae_model_desc& d, const float* params, const float* pac
 }
 
 int conv_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                           int nz, float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+                           int nz, DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
   ConvEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "conv_model_vae_forward: workspace too small");
@@ -309,7 +309,7 @@ int conv_vae_forward(const ardae_model_desc& d, const float* params, const float
 }
 
 int conv_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                            int nz, float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
+                            int nz, DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
                             float grads_beta, hipStream_t st) {
   ConvEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
@@ -504,7 +504,7 @@ int auxconv_decode(const ardae_model_desc& d, const float* params, const float* 
 }
 
 int auxconv_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                              int nz, float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+                              int nz, DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
   AuxConvEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "auxconv_model_vae_forward: workspace too small");
@@ -517,7 +517,7 @@ int auxconv_vae_forward(const ardae_model_desc& d, const float* params, const fl
 }
 
 int auxconv_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                               int nz, float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
+                               int nz, DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
                                float grads_beta, hipStream_t st) {
   (void)noise;
   AuxConvEntry entry(d, workspace, wsf, B, nz, 1);

@@ -5,6 +5,18 @@
 
 namespace ardae {
 
+// A float kernel argument that may live in device memory instead: the train state's beta / seed_scale (ardae_train_state_advance),
+// which a replayed graph must read afresh.  p non-null: the kernel loads *p (one wave-uniform load) and goes on as with v.
+struct DevFloat {
+  float v;
+  const float* p;
+  DevFloat(float v_) : v(v_), p(nullptr) {}
+  explicit DevFloat(const float* p_) : v(0.f), p(p_) {}
+};
+// the two floats of the train state block (null state: an argument error at the entry point, never dereferenced here)
+DevFloat train_state_beta(const void* state);
+DevFloat train_state_seed_scale(const void* state);
+
 // ivae_ardae.py:753-761 + models/graddae/mlp.py:21-23:
 //   u = s (z - z0[b]);  std_b = delta * mean_d( std_unbiased_over_nz(u[:, d]) );
 //   sigma[b, i] = std_b * xi[b, i];  xbar = u + sigma * eps
@@ -39,6 +51,9 @@ int launch_philox_normal_dev(float* out, int64_t n, uint64_t seed, const void* s
 // elements [first_element, first_element + n) of the draw (seed, offset [+ state]); state may be null
 int launch_philox_normal_at(float* out, int64_t n, uint64_t seed, uint64_t offset, const void* state, uint64_t first_element, hipStream_t st);
 int launch_step_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, hipStream_t st);
+// the same, then beta and the entropy-seed factor of the coming step: see ardae_train_state_advance in ardae_hip.h
+int launch_train_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double beta_init, double beta_fin,
+                               int64_t beta_annealing, double std_scale, int64_t seed_rows, hipStream_t st);
 int launch_adam_ref_dev(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, double beta1, double beta2, double eps,
                         const void* state, hipStream_t st);
 int launch_philox_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st);
@@ -55,7 +70,9 @@ int launch_rmsprop(float* p, const float* g, float* sq, float* buf, int64_t n, d
                    double momentum, hipStream_t st);
 
 // y += alpha*x (the entropy-gradient seed of ivae_ardae.py:834 added to dL/dz)
-int launch_axpy(const float* x, int64_t n, float alpha, float* y, hipStream_t st);
+int launch_axpy(const float* x, int64_t n, DevFloat alpha, float* y, hipStream_t st);
+// y *= alpha (the entropy seed of the single-call backward, scaled before it enters the loss kernel)
+int launch_scale(float* y, int64_t n, DevFloat alpha, hipStream_t st);
 // y[i] = v;  y = x;  y[r][c] = x[r][c] (row strides ldx / ldy) - kernels instead of hipMemsetAsync / hipMemcpyAsync / hipMemcpy2DAsync: as
 // graph nodes those are not ordered against their neighbour kernels when a linear graph goes out as one AQL batch (elementwise.hip)
 int launch_fill(float* y, int64_t n, float v, hipStream_t st);
@@ -69,9 +86,9 @@ int launch_affine(const float* x, int64_t n, float alpha, float beta, float* y, 
 //   pri = .5 sum_d (z^2 + log 2pi) (utils/energy.py:69-77);  dzq = gscale*beta*z + dz_extra
 // x is [rows/nz, D] (row r belongs to image r/nz).
 int launch_vae_loss(int kind, const float* o0, const float* o1, const float* x, const float* z, int rows, int nz, int D, int zd,
-                    float beta, int write_grads, float gscale, const float* dz_extra, float* rec_row, float* pri_row, float* do0,
+                    DevFloat beta, int write_grads, float gscale, const float* dz_extra, float* rec_row, float* pri_row, float* do0,
                     float* do1, float* dzq, hipStream_t st);
 // losses[0] = mean(rec + beta*pri), losses[1] = mean(rec), losses[2] = mean(pri)
-int launch_vae_loss_finalize(const float* rec_row, const float* pri_row, int rows, float beta, float* losses, hipStream_t st);
+int launch_vae_loss_finalize(const float* rec_row, const float* pri_row, int rows, DevFloat beta, float* losses, hipStream_t st);
 
 }  // namespace ardae

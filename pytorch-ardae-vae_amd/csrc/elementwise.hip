@@ -6,15 +6,39 @@
 namespace ardae {
 namespace {
 
-
-__global__ void step_state_advance_kernel(StepState* s, uint64_t rng_inc, double lr, double beta1, double beta2) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+// rng_offset += rng_inc, t += 1 and Adam's two coefficients for the new t; returns t
+__device__ __forceinline__ int64_t step_state_advance1(StepState* s, uint64_t rng_inc, double lr, double beta1, double beta2) {
   s->rng_offset += rng_inc;
   const int64_t t = s->adam_step + 1;
   s->adam_step = t;
   const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);   // host formula of launch_adam_ref, in double
   s->adam_step_size = (float)(lr / bc1);
   s->adam_sqrt_bc2 = (float)sqrt(bc2);
+  return t;
+}
+
+__global__ void step_state_advance_kernel(StepState* s, uint64_t rng_inc, double lr, double beta1, double beta2) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  step_state_advance1(s, rng_inc, lr, beta1, beta2);
+}
+
+// beta and the entropy-seed factor of step t (0-based i = t - 1, the reference's i_ep) as the host forms them: utils/msc.py:53-55 and
+// dist.entropy_seed_scale, every operation rounded to double on its own (a contracted multiply-add would differ from Python's in
+// the last bit), each result rounded to float once
+__global__ void train_state_advance_kernel(TrainState* s, uint64_t rng_inc, double lr, double beta1, double beta2, double beta_init,
+                                           double beta_fin, int64_t beta_annealing, double std_scale, int64_t seed_rows) {
+#pragma clang fp contract(off)
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t i = step_state_advance1(&s->step, rng_inc, lr, beta1, beta2) - 1;
+  double beta = beta_fin;
+  if (beta_annealing >= 0) {
+    const double slope = (beta_fin - beta_init) / (double)beta_annealing;
+    const double ramp = slope * (double)(i < beta_annealing ? i : beta_annealing);
+    beta = beta_init + ramp;
+  }
+  const double scaled = std_scale * beta;
+  s->beta = (float)beta;
+  s->seed_scale = (float)(scaled / (double)seed_rows);
 }
 
 // q0: first counter of this launch - a rank that owns rows [r0, r1) of a draw generates elements [first, first + n) of the
@@ -416,8 +440,26 @@ __global__ __launch_bounds__(256) void weight_avg_kernel(float* __restrict__ avg
   for (int64_t i = tail0 + tid; i < n; i += stride) avg[i] = weight_avg1(avg[i], p[i], w, first);
 }
 
-__global__ void axpy_kernel(const float* __restrict__ x, int64_t n, float alpha, float* __restrict__ y) {
+__global__ void axpy_kernel(const float* __restrict__ x, int64_t n, float alpha, const float* __restrict__ alpha_dev, float* __restrict__ y) {
+  if (alpha_dev) alpha = *alpha_dev;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] += alpha * x[i];
+}
+
+// y *= alpha: float4 body between a scalar head (up to y's first 16-byte boundary) and a scalar tail
+__global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ y, int64_t n, float alpha, const float* __restrict__ alpha_dev) {
+  if (alpha_dev) alpha = *alpha_dev;
+  int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(y) & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const int64_t nvec = (n - head) / 4, tail0 = head + 4 * nvec;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  f32x4* __restrict__ yv = reinterpret_cast<f32x4*>(y + head);
+  for (int64_t i = tid; i < nvec; i += stride) {
+    f32x4 v = yv[i];
+    v.x *= alpha; v.y *= alpha; v.z *= alpha; v.w *= alpha;
+    yv[i] = v;
+  }
+  for (int64_t i = tid; i < head; i += stride) y[i] *= alpha;
+  for (int64_t i = tail0 + tid; i < n; i += stride) y[i] *= alpha;
 }
 
 // The library issues no hipMemsetAsync / hipMemcpyAsync: as nodes of a captured graph they are not ordered against the
@@ -451,10 +493,12 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 template <int KIND>
 __global__ __launch_bounds__(256) void vae_loss_kernel(const float* __restrict__ o0, const float* __restrict__ o1,
                                                        const float* __restrict__ x, const float* __restrict__ z, int nz, int D, int zd,
-                                                       float beta, int write_grads, float gscale, const float* __restrict__ dz_extra,
-                                                       float* __restrict__ rec_row, float* __restrict__ pri_row, float* __restrict__ do0,
-                                                       float* __restrict__ do1, float* __restrict__ dzq) {
+                                                       float beta, const float* __restrict__ beta_dev, int write_grads, float gscale,
+                                                       const float* __restrict__ dz_extra, float* __restrict__ rec_row,
+                                                       float* __restrict__ pri_row, float* __restrict__ do0, float* __restrict__ do1,
+                                                       float* __restrict__ dzq) {
   __shared__ float red[4];
+  if (beta_dev) beta = *beta_dev;
   const int r = blockIdx.x;
   const float* xr = x + (size_t)(r / nz) * D;
   const size_t base = (size_t)r * D;
@@ -495,8 +539,10 @@ __global__ __launch_bounds__(256) void vae_loss_kernel(const float* __restrict__
 }
 
 __global__ __launch_bounds__(256) void vae_loss_finalize_kernel(const float* __restrict__ rec_row, const float* __restrict__ pri_row,
-                                                                int rows, float beta, float* __restrict__ losses) {
+                                                                int rows, float beta, const float* __restrict__ beta_dev,
+                                                                float* __restrict__ losses) {
   __shared__ float red[4];
+  if (beta_dev) beta = *beta_dev;
   float a = 0.f, b = 0.f;
   for (int i = threadIdx.x; i < rows; i += 256) {
     a += rec_row[i];
@@ -677,6 +723,19 @@ int launch_step_state_advance(void* state, uint64_t rng_inc, double lr, double b
   return 0;
 }
 
+int launch_train_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double beta_init, double beta_fin,
+                               int64_t beta_annealing, double std_scale, int64_t seed_rows, hipStream_t st) {
+  ARDAE_CHECK_ARG(state, "train_state_advance: null state");
+  ARDAE_CHECK_ARG(beta_annealing != 0 && seed_rows > 0, "train_state_advance: beta_annealing must be positive (or negative: no annealing) and seed_rows positive");
+  hipLaunchKernelGGL(train_state_advance_kernel, dim3(1), dim3(64), 0, st, (TrainState*)state, rng_inc, lr, beta1, beta2, beta_init, beta_fin,
+                     beta_annealing, std_scale, seed_rows);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+DevFloat train_state_beta(const void* state) { return DevFloat(&((const TrainState*)state)->beta); }
+DevFloat train_state_seed_scale(const void* state) { return DevFloat(&((const TrainState*)state)->seed_scale); }
+
 int launch_philox_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st) {
   ARDAE_CHECK_ARG(out && n > 0, "philox_uniform: bad arguments");
   const int64_t q = (n + 3) / 4;
@@ -733,9 +792,16 @@ int launch_weight_avg(float* avg, const float* p, int64_t n, int kind, double de
   return 0;
 }
 
-int launch_axpy(const float* x, int64_t n, float alpha, float* y, hipStream_t st) {
+int launch_axpy(const float* x, int64_t n, DevFloat alpha, float* y, hipStream_t st) {
   ARDAE_CHECK_ARG(x && y && n > 0, "axpy: bad arguments");
-  hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, alpha, y);
+  hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, alpha.v, alpha.p, y);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_scale(float* y, int64_t n, DevFloat alpha, hipStream_t st) {
+  ARDAE_CHECK_ARG(y && n > 0, "scale: bad arguments");
+  hipLaunchKernelGGL(scale_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, y, n, alpha.v, alpha.p);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
@@ -764,24 +830,24 @@ int launch_affine(const float* x, int64_t n, float alpha, float beta, float* y, 
 }
 
 int launch_vae_loss(int kind, const float* o0, const float* o1, const float* x, const float* z, int rows, int nz, int D, int zd,
-                    float beta, int write_grads, float gscale, const float* dz_extra, float* rec_row, float* pri_row, float* do0,
+                    DevFloat beta, int write_grads, float gscale, const float* dz_extra, float* rec_row, float* pri_row, float* do0,
                     float* do1, float* dzq, hipStream_t st) {
   ARDAE_CHECK_ARG(o0 && x && z && rec_row && pri_row && rows > 0 && nz > 0 && D > 0 && zd > 0, "vae_loss: bad arguments");
   ARDAE_CHECK_ARG(kind == 0 || (kind == 1 && o1), "vae_loss: kind 1 needs the logvar head");
   ARDAE_CHECK_ARG(!write_grads || (do0 && dzq && (kind == 0 || do1)), "vae_loss: gradient outputs missing");
   if (kind == 0)
-    hipLaunchKernelGGL(vae_loss_kernel<0>, dim3(rows), dim3(256), 0, st, o0, o1, x, z, nz, D, zd, beta, write_grads, gscale, dz_extra,
+    hipLaunchKernelGGL(vae_loss_kernel<0>, dim3(rows), dim3(256), 0, st, o0, o1, x, z, nz, D, zd, beta.v, beta.p, write_grads, gscale, dz_extra,
                        rec_row, pri_row, do0, do1, dzq);
   else
-    hipLaunchKernelGGL(vae_loss_kernel<1>, dim3(rows), dim3(256), 0, st, o0, o1, x, z, nz, D, zd, beta, write_grads, gscale, dz_extra,
+    hipLaunchKernelGGL(vae_loss_kernel<1>, dim3(rows), dim3(256), 0, st, o0, o1, x, z, nz, D, zd, beta.v, beta.p, write_grads, gscale, dz_extra,
                        rec_row, pri_row, do0, do1, dzq);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_vae_loss_finalize(const float* rec_row, const float* pri_row, int rows, float beta, float* losses, hipStream_t st) {
+int launch_vae_loss_finalize(const float* rec_row, const float* pri_row, int rows, DevFloat beta, float* losses, hipStream_t st) {
   ARDAE_CHECK_ARG(rec_row && pri_row && losses && rows > 0, "vae_loss_finalize: bad arguments");
-  hipLaunchKernelGGL(vae_loss_finalize_kernel, dim3(1), dim3(256), 0, st, rec_row, pri_row, rows, beta, losses);
+  hipLaunchKernelGGL(vae_loss_finalize_kernel, dim3(1), dim3(256), 0, st, rec_row, pri_row, rows, beta.v, beta.p, losses);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }

@@ -6,6 +6,7 @@
 //                                        factorises cov per image; here all images in one launch (z_dim <= 64)
 #include "ardae_hip.h"
 #include "common.h"
+#include "elementwise.h"
 
 namespace ardae {
 namespace {
@@ -103,8 +104,9 @@ struct StepStateView {     // layout of the device step state (elementwise.hip::
 
 // One record of ARDAE_LOG_RECORD_FLOATS floats per step into ring slot (iter - 1) % capacity; iter = the step state's Adam t.
 __global__ __launch_bounds__(256) void log_scalars_kernel(const float* __restrict__ cdae_loss, const float* __restrict__ model_losses,
-                                                          const float* __restrict__ std_b, int B, float beta, float d_lr,
-                                                          const StepStateView* __restrict__ state, float* __restrict__ ring, int capacity) {
+                                                          const float* __restrict__ std_b, int B, float beta, const float* __restrict__ beta_dev,
+                                                          float d_lr, const StepStateView* __restrict__ state, float* __restrict__ ring,
+                                                          int capacity) {
   __shared__ float s_sum[256], s_max[256], s_min[256];
   const int t = threadIdx.x;
   float sm = 0.f, mx = -INFINITY, mn = INFINITY;
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void log_scalars_kernel(const float* __restric
   float* r = ring + (size_t)((iter - 1) % capacity) * ARDAE_LOG_RECORD_FLOATS;
   r[0] = __int_as_float((int)(iter & 0x7fffffff));
   r[1] = model_losses[0]; r[2] = model_losses[1]; r[3] = model_losses[2];
-  r[4] = beta;
+  r[4] = beta_dev ? *beta_dev : beta;
   r[5] = cdae_loss[0];
   r[6] = s_sum[0] / (float)B; r[7] = s_max[0]; r[8] = s_min[0];
   r[9] = d_lr;
@@ -142,13 +144,22 @@ __global__ void gather_rows_kernel(const float* __restrict__ table, const int64_
 
 extern "C" {
 
-int ardae_log_scalars(const float* cdae_loss, const float* model_losses, const float* std_b, int B, float beta, float d_lr,
-                      const void* state, float* ring, int capacity, void* stream) {
+static int log_scalars(const float* cdae_loss, const float* model_losses, const float* std_b, int B, ardae::DevFloat beta, float d_lr,
+                       const void* state, float* ring, int capacity, void* stream) {
   ARDAE_CHECK_ARG(cdae_loss && model_losses && std_b && state && ring && B > 0 && capacity > 0, "log_scalars: bad arguments");
-  hipLaunchKernelGGL(log_scalars_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, cdae_loss, model_losses, std_b, B, beta, d_lr,
+  hipLaunchKernelGGL(log_scalars_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, cdae_loss, model_losses, std_b, B, beta.v, beta.p, d_lr,
                      (const StepStateView*)state, ring, capacity);
   ARDAE_LAUNCH_CHECK();
   return 0;
+}
+int ardae_log_scalars(const float* cdae_loss, const float* model_losses, const float* std_b, int B, float beta, float d_lr,
+                      const void* state, float* ring, int capacity, void* stream) {
+  return log_scalars(cdae_loss, model_losses, std_b, B, beta, d_lr, state, ring, capacity, stream);
+}
+int ardae_log_scalars_dev(const float* cdae_loss, const float* model_losses, const float* std_b, int B, const void* beta_state, float d_lr,
+                          const void* state, float* ring, int capacity, void* stream) {
+  ARDAE_CHECK_ARG(beta_state, "log_scalars_dev: beta_state is NULL");
+  return log_scalars(cdae_loss, model_losses, std_b, B, ardae::train_state_beta(beta_state), d_lr, state, ring, capacity, stream);
 }
 
 int ardae_gather_rows(const float* table, const int64_t* idx, int B, int D, float* out, void* stream) {

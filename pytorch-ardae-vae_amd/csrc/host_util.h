@@ -187,9 +187,9 @@ struct Family {
   int (*decode)(const ardae_model_desc&, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
                 float* out0, hipStream_t, float* out1);
   int (*vae_forward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
+                     DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
   int (*vae_backward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                      float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
+                      DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
 };
 
 // A family is a Layout (the Linears' offsets in the flat parameter buffer, from the desc) and a Packed (the panels' offsets in the

@@ -237,7 +237,7 @@ int mlp_encode(const ardae_model_desc& d, const float* params, const float* pack
 }
 
 int mlp_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                    float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+                    DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
   MlpEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "model_vae_forward: internal workspace accounting error");
@@ -252,7 +252,7 @@ int mlp_vae_forward(const ardae_model_desc& d, const float* params, const float*
 // weight gradients, 3 = both.  With phases == 3 the (pre-scaled) seed enters through the loss kernel; with phases == 2 it is
 // added to dz as seed_scale * dz_extra.
 int vae_backward_impl(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise,
-                      int B, int nz, float beta, float dloss, const float* dz_extra, float seed_scale, float* workspace,
+                      int B, int nz, DevFloat beta, float dloss, const float* dz_extra, DevFloat seed_scale, float* workspace,
                       size_t workspace_floats_, float* grads, float grads_beta, int phases, hipStream_t st) {
   MlpEntry entry(d, workspace, workspace_floats_, B, nz, 1);
   auto& [P, K, ws, W] = entry;
@@ -280,7 +280,7 @@ int vae_backward_impl(const ardae_model_desc& d, const float* params, const floa
 }
 
 int mlp_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
+                     DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
                      hipStream_t st) {
   return vae_backward_impl(d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, 1.f, workspace, wsf, grads, grads_beta, 3, st);
 }
@@ -392,26 +392,26 @@ int ardae_model_loss_rows(const ardae_model_desc* d, const float* out0, const fl
                          nullptr, nullptr, (hipStream_t)stream);
 }
 
-int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
-                            int B, int nz, float beta, float* workspace, size_t workspace_floats_, float* z_out, float* losses,
-                            void* stream) {
+// The four entry points that take beta or the seed factor, each written once: the ABI's value form passes the float, its _dev twin
+// the train state's slot (DevFloat).
+static int vae_forward_entry(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise, int B,
+                             int nz, DevFloat beta, float* workspace, size_t workspace_floats_, float* z_out, float* losses, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise && z_out && losses, "model_vae_forward: null pointer argument");
   return family(d).vae_forward(*d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, (hipStream_t)stream);
 }
 
-int ardae_model_vae_backward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
-                             int B, int nz, float beta, float dloss, const float* dz_extra, float* workspace,
-                             size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
+static int vae_backward_entry(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise, int B,
+                              int nz, DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t workspace_floats_,
+                              float* grads, float grads_beta, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise && grads, "model_vae_backward: null pointer argument");
   return family(d).vae_backward(*d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta,
                                 (hipStream_t)stream);
 }
 
-int ardae_model_vae_backward_decoder(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
-                                     const float* noise, int B, int nz, float beta, float dloss, float* workspace,
-                                     size_t workspace_floats_, void* stream) {
+static int vae_backward_decoder_entry(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                                      int B, int nz, DevFloat beta, float dloss, float* workspace, size_t workspace_floats_, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise, "model_vae_backward_decoder: null pointer argument");
   ARDAE_CHECK_ARG(d->kind < 2, "model_vae_backward_decoder: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
@@ -419,14 +419,65 @@ int ardae_model_vae_backward_decoder(const ardae_model_desc* d, const float* par
                            (hipStream_t)stream);
 }
 
-int ardae_model_vae_backward_sampler(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
-                                     const float* noise, int B, int nz, const float* dz_extra, float seed_scale, float* workspace,
-                                     size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
+static int vae_backward_sampler_entry(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                                      int B, int nz, const float* dz_extra, DevFloat seed_scale, float* workspace, size_t workspace_floats_,
+                                      float* grads, float grads_beta, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise && grads, "model_vae_backward_sampler: null pointer argument");
   ARDAE_CHECK_ARG(d->kind < 2, "model_vae_backward_sampler: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
   return vae_backward_impl(*d, params, packed, x, noise, B, nz, 0.f, 0.f, dz_extra, seed_scale, workspace, workspace_floats_, grads,
                            grads_beta, 2, (hipStream_t)stream);
+}
+
+int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                            int B, int nz, float beta, float* workspace, size_t workspace_floats_, float* z_out, float* losses,
+                            void* stream) {
+  return vae_forward_entry(d, params, packed, x, noise, B, nz, beta, workspace, workspace_floats_, z_out, losses, stream);
+}
+int ardae_model_vae_forward_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                                int B, int nz, const void* state, float* workspace, size_t workspace_floats_, float* z_out, float* losses,
+                                void* stream) {
+  ARDAE_CHECK_ARG(state, "model_vae_forward_dev: state is NULL");
+  return vae_forward_entry(d, params, packed, x, noise, B, nz, train_state_beta(state), workspace, workspace_floats_, z_out, losses, stream);
+}
+
+int ardae_model_vae_backward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                             int B, int nz, float beta, float dloss, const float* dz_extra, float* workspace,
+                             size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
+  return vae_backward_entry(d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, workspace, workspace_floats_, grads, grads_beta, stream);
+}
+int ardae_model_vae_backward_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
+                                 int B, int nz, const void* state, float dloss, const float* dz_extra, float* workspace,
+                                 size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
+  ARDAE_CHECK_ARG(state, "model_vae_backward_dev: state is NULL");
+  return vae_backward_entry(d, params, packed, x, noise, B, nz, train_state_beta(state), dloss, dz_extra, workspace, workspace_floats_, grads,
+                            grads_beta, stream);
+}
+
+int ardae_model_vae_backward_decoder(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                     const float* noise, int B, int nz, float beta, float dloss, float* workspace,
+                                     size_t workspace_floats_, void* stream) {
+  return vae_backward_decoder_entry(d, params, packed, x, noise, B, nz, beta, dloss, workspace, workspace_floats_, stream);
+}
+int ardae_model_vae_backward_decoder_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                         const float* noise, int B, int nz, const void* state, float dloss, float* workspace,
+                                         size_t workspace_floats_, void* stream) {
+  ARDAE_CHECK_ARG(state, "model_vae_backward_decoder_dev: state is NULL");
+  return vae_backward_decoder_entry(d, params, packed, x, noise, B, nz, train_state_beta(state), dloss, workspace, workspace_floats_, stream);
+}
+
+int ardae_model_vae_backward_sampler(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                     const float* noise, int B, int nz, const float* dz_extra, float seed_scale, float* workspace,
+                                     size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
+  return vae_backward_sampler_entry(d, params, packed, x, noise, B, nz, dz_extra, seed_scale, workspace, workspace_floats_, grads, grads_beta,
+                                    stream);
+}
+int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x,
+                                         const float* noise, int B, int nz, const float* dz_extra, const void* state, float* workspace,
+                                         size_t workspace_floats_, float* grads, float grads_beta, void* stream) {
+  ARDAE_CHECK_ARG(state, "model_vae_backward_sampler_dev: state is NULL");
+  return vae_backward_sampler_entry(d, params, packed, x, noise, B, nz, dz_extra, train_state_seed_scale(state), workspace, workspace_floats_,
+                                    grads, grads_beta, stream);
 }
 
 }  // extern "C"

@@ -57,6 +57,15 @@ struct StepState {
   float adam_sqrt_bc2;     // sqrt(1 - beta2^t)
 };
 
+// The train state (ardae_train_state_advance): the step state with the KL weight and the entropy-seed factor of the coming step in
+// the block's last 8 bytes (FitState::reserved; no step-state consumer reads them).
+struct TrainState {
+  StepState step;
+  float beta;              // annealing_func(beta_init, beta_fin, beta_annealing, t - 1)
+  float seed_scale;        // std_scale * beta / seed_rows
+};
+static_assert(sizeof(TrainState) == 32, "the train state fills ARDAE_STEP_STATE_BYTES");
+
 // The fit state (ardae_fit_state_advance): a step state whose Adam coefficients follow the StepLR schedule, and behind it the
 // energy weight and learning rate of the coming iteration and of the one just done (the logged pair).
 struct FitState {

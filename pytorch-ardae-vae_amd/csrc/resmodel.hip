@@ -753,7 +753,7 @@ int res_decode(const ardae_model_desc& d, const float* params, const float* pack
 }
 
 int res_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                          float beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
+                          DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
   ResEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "res model vae_forward: workspace too small");
@@ -767,7 +767,7 @@ int res_vae_forward(const ardae_model_desc& d, const float* params, const float*
 }
 
 int res_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                           float beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
+                           DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
   ResEntry entry(d, workspace, wsf, B, nz, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "res model vae_backward: workspace too small");

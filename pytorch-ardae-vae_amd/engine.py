@@ -26,7 +26,10 @@ class TrainConfig:
     nstd_cdae: int = 1            # --train-nstd-cdae: noise levels (sigma, eps pairs) per sample row of the cDAE update
     nz_model: int = 1             # --train-nz-model
     num_cdae_updates: int = 1     # --num-cdae-updates
-    beta: float = 1.0             # --beta-fin (no annealing in the shipped recipes)
+    beta: float = 1.0             # --beta-fin: the KL weight, or its final value under a schedule
+    beta_init: float = None       # --beta-init / --beta-annealing (ivae_ardae.py:202-203,704; the resconv recipes of run_vae_sbmnist.sh and
+    beta_annealing: int = None    # run_vae_dbmnist.sh pass 0.0001 / 50000): beta rises linearly from beta_init over that many steps, computed on
+                                  # the device (ardae_train_state_advance).  None, 0 or anything below 1: no schedule (the other recipes pass 0)
     m_lr: float = 1e-4            # --m-lr, Adam betas (m_beta1, 0.999)
     m_beta1: float = 0.5
     d_lr: float = 1e-4            # --d-lr, RMSprop momentum d_momentum
@@ -49,6 +52,16 @@ class TrainConfig:
         if int(self.m_weight_avg_start) < 0 or not 0.0 <= float(self.m_weight_avg_decay) <= 1.0:
             raise ValueError(f"m_weight_avg_start must be >= 0 and m_weight_avg_decay in [0, 1] (got {self.m_weight_avg_start}, "
                              f"{self.m_weight_avg_decay})")
+        if self.beta_annealing is not None and int(self.beta_annealing) != self.beta_annealing:
+            raise ValueError(f"beta_annealing must be a whole number of steps or None (got {self.beta_annealing!r})")
+        if self.beta_init is None and self.beta_annealing is not None and self.beta_annealing >= 1:
+            raise ValueError(f"beta_annealing={self.beta_annealing} needs beta_init (--beta-init)")
+
+    def beta_schedule(self):
+        """(beta_init, beta_fin, beta_annealing) of `annealing_func`, or None: ivae_ardae.py:202-203 drops a --beta-annealing below 1."""
+        if self.beta_annealing is None or self.beta_annealing < 1:
+            return None
+        return float(self.beta_init), float(self.beta), int(self.beta_annealing)
 
 
 def annealing_func(val_init, val_fin, val_annealing, step):
@@ -59,10 +72,14 @@ def annealing_func(val_init, val_fin, val_annealing, step):
 
 
 class ArdaeEngine:
-    """`graph=True` (default): `step()` captures the iteration at its third call and replays it afterwards.  What changes from
+    """`graph=True` (default): `step()` captures the iteration once beta - a kernel argument - has stood still for two steps (a constant
+    beta: at the third call) and replays it afterwards.  What changes from
     step to step lives in device memory: a 32-byte step state (Philox base offset, Adam's t and bias corrections,
     `ardae_step_state_advance`) and the static image buffers the caller's batches are copied into.  Noise injection (parity
-    tests) runs the same launches eagerly.
+    tests) runs the same launches eagerly.  With a beta schedule (`TrainConfig.beta_init` / `beta_annealing`) the block also carries
+    the coming step's beta and entropy-seed factor (`ardae_train_state_advance`), every consumer reads them there (the `_dev` entry
+    points), nothing of beta is frozen into the launches, and the ladder is: first call eager, second call captured, replays from
+    then on, while beta moves; `beta=` is then refused.
 
     A step is a PLAN of units (`_plan` / `_units`): stretches of launches on ONE stream each, ordered by events between
     them, with the gradient all-reduces (world > 1) as eager items in between.  Every unit is captured as its own LINEAR HIP
@@ -148,8 +165,12 @@ class ArdaeEngine:
         self.step_count = 0
         # device-resident step state (Philox base offset + the model optimiser's Adam block) + graph bookkeeping
         self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        # --beta-annealing: slot 3 of the block holds the coming step's beta and seed factor.  seed_rows is the PER-RANK B * nz_model, as
+        # in _vae_backward_grads; every rank computes the same beta from the same t (no collective)
+        self.sched = cfg.beta_schedule()
+        train = None if self.sched is None else self.sched + (float(cfg.std_scale), B * nzm)
         # --m-optimizer / --d-optimizer (ivae_ardae.py:545-556,612-622); the model's RMSprop is built with d_momentum there (:553)
-        self.opt_m = _FlatOpt(cfg.m_optimizer, model._flat, model._flat.numel(), cfg.m_lr, cfg.m_beta1, cfg.d_momentum, state=self.state)
+        self.opt_m = _FlatOpt(cfg.m_optimizer, model._flat, model._flat.numel(), cfg.m_lr, cfg.m_beta1, cfg.d_momentum, state=self.state, train=train)
         self.opt_c = _FlatOpt(cfg.d_optimizer, cdae._flat, self.n_c, cfg.d_lr, cfg.d_beta1, cfg.d_momentum)
         # --m-weight-avg (ivae_ardae.py:559-565): the averaged model weights, a buffer laid out like model._flat (replicated over the ranks,
         # updated from the all-reduced weights) that `ardae_weight_avg` updates in the model-update unit.  _avg_origin: the t of the first
@@ -182,6 +203,24 @@ class ArdaeEngine:
     def attach_log(self, log):
         """Append `log.record(beta)` to every step (a new launch: a captured step graph is rebuilt)."""
         self._log, self._graph = log, None
+
+    def _beta_arg(self, beta):
+        """The beta of a step or phase call: the caller's or cfg.beta as a float, or - with a schedule - None: the device block's."""
+        if self.sched is None:
+            return float(self.cfg.beta if beta is None else beta)
+        if beta is not None:
+            raise ValueError(f"beta={beta!r}: this engine computes beta on the device (TrainConfig(beta_init={self.cfg.beta_init}, "
+                             f"beta_annealing={self.cfg.beta_annealing})); a second source is refused")
+        return None
+
+    def _refresh_train_state(self):
+        """Slot 3 of a block that was loaded or rebuilt, recomputed from its t: step the block back by one and advance it again (the same t,
+        Philox offset and Adam coefficients; beta and the seed factor of THIS engine's schedule).  A file written before the schedule
+        existed, by the reference loop or under another schedule thereby resumes at annealing_func(beta_init, beta, beta_annealing, step_count)."""
+        if self.sched is not None:
+            self.state[0] -= self.RNG_STRIDE
+            self.state[1] -= 1
+            self.opt_m.advance(self.RNG_STRIDE)
 
     # ------------------------------------------------------------------------------------------------------------
     def repack(self):
@@ -243,7 +282,7 @@ class ArdaeEngine:
         def model_update():
             self._model_update()
             if self._log is not None:
-                self._log.record(cfg.beta if beta is None else beta)
+                self._log.record(self._beta_arg(beta))
             self.opt_m.advance(self.RNG_STRIDE)       # for the NEXT step: Philox base += stride, model optimiser's t += 1
         segs.append(("run", "model_update", "main", (), model_update))
         if self._stamps is not None:
@@ -428,11 +467,12 @@ class ArdaeEngine:
         self._require_trained("vae_forward_part()")
         self._check_batch(x, "vae_forward_part")
         cfg = self.cfg
-        beta = cfg.beta if beta is None else beta
+        beta = self._beta_arg(beta)
+        dev = "_dev" if beta is None else ""        # the twins that read beta / the seed factor from the block
         B, nz, md = self.B, cfg.nz_model, self.model._desc
         nv = noise["vae"] if noise else self._normal(self.noise_v, draw)
-        L.call("ardae_model_vae_forward", md, self.model._flat, self.pk_m, x, nv, B, nz, float(beta), self.ws_vae, self.ws_vae.numel(), self.zv,
-               self.losses_m)
+        L.call("ardae_model_vae_forward" + dev, md, self.model._flat, self.pk_m, x, nv, B, nz, self.state if dev else beta, self.ws_vae,
+               self.ws_vae.numel(), self.zv, self.losses_m)
         if self.hidden_ctx:      # context and latent mean of the VAE batch: one std = 0 pass (ivae_ardae.py:815-817,826)
             raws = None
             if self.clipped:
@@ -448,8 +488,8 @@ class ArdaeEngine:
         L.call("ardae_center_scale", self.zv, self.z0v, B, nz, self.model.z_dim, cfg.std_scale, self.u)
         if self.split_backward:
             # model_loss.backward() through the decoder down to dL/dz (ivae_ardae.py:804) needs nothing from the cDAE either
-            L.call("ardae_model_vae_backward_decoder", md, self.model._flat, self.pk_m, x, nv, B, nz, float(beta), 1.0, self.ws_vae,
-                   self.ws_vae.numel())
+            L.call("ardae_model_vae_backward_decoder" + dev, md, self.model._flat, self.pk_m, x, nv, B, nz, self.state if dev else beta, 1.0,
+                   self.ws_vae, self.ws_vae.numel())
         return nv
 
     def vae_backward_part(self, x, nv, beta=None, apply_update=True):
@@ -464,20 +504,25 @@ class ArdaeEngine:
     def _vae_backward_grads(self, x, nv, beta=None):
         self._check_batch(x, "vae_backward_part")
         cfg = self.cfg
-        beta = cfg.beta if beta is None else beta
+        beta = self._beta_arg(beta)
+        dev = "_dev" if beta is None else ""
         B, nz, md = self.B, cfg.nz_model, self.model._desc
         L.call("ardae_cdae_score", self.cdae._desc, self.cdae._flat, self.pk_c, self.u, self.sigma0, self.ctx_v, B, nz, self.ws_small,
                self.ws_small.numel(), self.g)
         # seed of (s (z - z0)).backward(beta g / (B nz)) w.r.t. z  (ivae_ardae.py:834); B is the per-rank batch because the
         # ranks' gradients are averaged afterwards (mean over ranks of 1/B_local == 1/B_global sum)
-        seed_scale = dist.entropy_seed_scale(cfg.std_scale, beta, B, nz)
+        # (with a schedule the block holds this very factor: ardae_train_state_advance forms it in the same order)
+        seed_scale = self.state if dev else float(dist.entropy_seed_scale(cfg.std_scale, beta, B, nz))
         if self.split_backward:      # the decoder half already ran in vae_forward_part
-            L.call("ardae_model_vae_backward_sampler", md, self.model._flat, self.pk_m, x, nv, B, nz, self.g, float(seed_scale), self.ws_vae,
+            L.call("ardae_model_vae_backward_sampler" + dev, md, self.model._flat, self.pk_m, x, nv, B, nz, self.g, seed_scale, self.ws_vae,
                    self.ws_vae.numel(), self.grads_m, 0.0)
         else:
-            self.g.mul_(seed_scale)
-            L.call("ardae_model_vae_backward", md, self.model._flat, self.pk_m, x, nv, B, nz, float(beta), 1.0, self.g, self.ws_vae,
-                   self.ws_vae.numel(), self.grads_m, 0.0)
+            if dev:
+                L.call("ardae_seed_scale_dev", self.g, self.g.numel(), self.state)
+            else:
+                self.g.mul_(seed_scale)
+            L.call("ardae_model_vae_backward" + dev, md, self.model._flat, self.pk_m, x, nv, B, nz, self.state if dev else beta, 1.0, self.g,
+                   self.ws_vae, self.ws_vae.numel(), self.grads_m, 0.0)
 
     def _model_update(self):
         self.opt_m.apply(self.grads_m, self._in_step)   # in a step: t and the bias corrections come from the device step state
@@ -541,7 +586,8 @@ class ArdaeEngine:
 
     def step(self, x_cdae, x_vae, noise=None, beta=None):
         """One iteration of the reference loop: num_cdae_updates cDAE updates (each on its own batch in the reference; the
-        caller passes a list of batches when num_cdae_updates > 1) followed by one VAE update."""
+        caller passes a list of batches when num_cdae_updates > 1) followed by one VAE update.  beta: this step's KL weight (default
+        cfg.beta) - refused when the engine computes it on the device (TrainConfig.beta_init / beta_annealing)."""
         self._require_trained("step()")
         many = isinstance(x_cdae, (list, tuple))
         xs = list(x_cdae) if many else [x_cdae] * self.cfg.num_cdae_updates
@@ -552,8 +598,8 @@ class ArdaeEngine:
             raise ValueError("at most %d cDAE updates per step (Philox offsets reserved per step)" % ((self.RNG_STRIDE - 1) // 3))
         if self.clipped and len(xs) > 3:
             raise ValueError("at most 3 cDAE updates per step with MNISTResConvAuxIPVAEClipped (its std = 0 draws use Philox offsets 9 .. 12)")
+        b = self._beta_arg(beta)      # None: the device schedule's - nothing of beta is frozen into the launches
         if self.use_graph and noise is None:
-            b = float(self.cfg.beta if beta is None else beta)
             # static copies of the batches (one per DISTINCT batch object: --num-cdae-updates k on one tensor shares its copy)
             self._static_batches(len(xs))
             for buf, x in zip(self._xc, xs):      # batches were validated above: B x input_dim contiguous floats, whatever their view shape
@@ -562,13 +608,14 @@ class ArdaeEngine:
             if x_vae is not self._xv:
                 self._xv.copy_(x_vae.view(self.B, -1))
             key = (b, tuple(tuple(x.shape) for x in self._xc), tuple(self._xv.shape))
-            # beta annealing (utils/msc.py:53-55) changes a frozen kernel argument every step: capture only once beta has stood
-            # still for two steps, run eagerly while it moves (a capture per step would cost far more than replay saves)
+            # beta annealing fed by the caller (utils/msc.py:53-55) changes a frozen kernel argument every step: capture only once beta has stood
+            # still for two steps, run eagerly while it moves (a capture per step would cost far more than replay saves).  A device
+            # schedule moves nothing the graph holds: the second step is captured
             self._beta_stable = self._beta_stable + 1 if b == self._last_beta else 0
             self._last_beta = b
             if self._graph is not None and self._graph_key == key:
                 self._replay()
-            elif self._warmed and self._beta_stable < 2:
+            elif self._warmed and b is not None and self._beta_stable < 2:
                 self._step_body(self._xc, self._xv, None, b)
             elif not self._warmed:
                 # first iteration of this engine eagerly: every kernel gets loaded outside of a capture
@@ -590,7 +637,7 @@ class ArdaeEngine:
                     self._graph, self._graph_key = g, key
             self._count_step(len(xs))
             return
-        self._step_body(xs, x_vae, noise, beta)
+        self._step_body(xs, x_vae, noise, b)
         self._count_step(len(xs))
 
     def input_buffers(self, n_cdae=None):
@@ -664,6 +711,7 @@ class ArdaeEngine:
         else:                   # written by the reference / the module path: the optimisers' t, and Philox offsets this run has not used yet
             # (a resumed run with an unchanged seed would otherwise replay the draws of steps 1..step_count)
             rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt_m.advance(self.RNG_STRIDE))
+        self._refresh_train_state()     # whatever the file's block says of beta, this engine's schedule at the block's t holds
         self.opt_c.state.zero_()
         self.opt_c.state[1] = self.opt_c.steps
         if self.avg is not None:

@@ -85,10 +85,12 @@ class _FlatOpt:
     """One network's optimiser on its flat parameter / gradient buffers: torch.optim.SGD(lr), the reference's vendored Adam (amsgrad
     optional; utils/optim.py:49-108) or torch.optim.RMSprop(momentum) - the four choices of --m-optimizer / --d-optimizer.  `n`: floats
     that receive gradients (a grad-kind score network's trailing neglogprob.fc.bias does not and keeps no state).  Adam's t and bias
-    corrections live in a 32-byte device block (`ardae_step_state_advance`) so that a captured step can be replayed."""
+    corrections live in a 32-byte device block (`ardae_step_state_advance`) so that a captured step can be replayed.  `train`:
+    (beta_init, beta_fin, beta_annealing, std_scale, seed_rows) of a beta schedule - the block is then advanced by
+    `ardae_train_state_advance`, which also writes the coming step's beta and entropy-seed factor into its last 8 bytes."""
     KINDS = ("sgd", "adam", "amsgrad", "rmsprop")
 
-    def __init__(self, kind, flat, n, lr, beta1, momentum, state=None):
+    def __init__(self, kind, flat, n, lr, beta1, momentum, state=None, train=None):
         if kind not in self.KINDS:
             raise NotImplementedError(f"unknown optimizer: {kind}")                     # ivae_ardae.py:555-556,621-622
         self.kind, self.flat, self.n, self.lr, self.beta1, self.momentum = kind, flat, int(n), float(lr), float(beta1), float(momentum)
@@ -96,7 +98,7 @@ class _FlatOpt:
         self.a = None if kind == "sgd" else z()                                         # exp_avg | square_avg
         self.b = None if kind == "sgd" else z()                                         # exp_avg_sq | momentum_buffer
         self.c = z() if kind == "amsgrad" else None                                     # max_exp_avg_sq
-        self.steps = 0
+        self.steps, self.train = 0, train
         self.state = state if state is not None else torch.zeros(4, dtype=torch.int64, device=flat.device)
 
     @property
@@ -104,7 +106,10 @@ class _FlatOpt:
         return self.kind in ("adam", "amsgrad")
 
     def advance(self, rng_inc=0):
-        L.call("ardae_step_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999)
+        if self.train is not None:
+            L.call("ardae_train_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999, *self.train)
+        else:
+            L.call("ardae_step_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999)
 
     def apply(self, grads, in_step):
         p, g = self.flat, grads

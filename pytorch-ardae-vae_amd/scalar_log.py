@@ -40,9 +40,12 @@ class ScalarLog:
         self._next = self.eng.step_count + 1
 
     def record(self, beta):
-        """Called by the engine as the last launch of a step (on the step's stream)."""
+        """Called by the engine as the last launch of a step (on the step's stream).  beta None: the step block's (a device schedule)."""
         e = self.eng
-        L.call("ardae_log_scalars", e.loss_c, e.losses_m, e.std_b, e.B, float(beta), float(e.cfg.d_lr), e.state, self.ring, self.capacity)
+        if beta is None:
+            L.call("ardae_log_scalars_dev", e.loss_c, e.losses_m, e.std_b, e.B, e.state, float(e.cfg.d_lr), e.state, self.ring, self.capacity)
+        else:
+            L.call("ardae_log_scalars", e.loss_c, e.losses_m, e.std_b, e.B, float(beta), float(e.cfg.d_lr), e.state, self.ring, self.capacity)
 
     def drain(self):
         """Records of the steps finished since the last drain (oldest first); appends them to log.txt / scalars.jsonl."""
