@@ -199,9 +199,11 @@ int ardae_sgd_step(float* p, const float* g, int64_t n, double lr, void* stream)
  * (ctx_encode.layers.*, ctx_encode.fc, inp_encode.*, neglogprob.* | dae.*), each tensor [out,in] row-major. */
 typedef struct ardae_cdae_desc {
   int kind;        /* 0 = mlp-grad (MLPGradCARDAE: score = input-gradient of an energy MLP), 1 = mlp-res (direct score);
-                    * 2 / 3 = the same two WITHOUT a context (MLPGradARDAE / MLPResARDAE, see "unconditional AR-DAE" below) */
+                    * 2 / 3 = the same two WITHOUT a context (MLPGradARDAE / MLPResARDAE, see "unconditional AR-DAE" below);
+                    * 6 / 7 = the plain DAEs, without a context and without the sigma input (MLPGradDAE / MLPResDAE, see "plain DAE"
+                    * below).  4 and 5 are not kinds */
   int input_dim;   /* z */
-  int context_dim; /* c  (kinds 0 / 1: >= 1; kinds 2 / 3: 0) */
+  int context_dim; /* c  (kinds 0 / 1: >= 1; kinds 2 / 3 / 6 / 7: 0) */
   int h_dim;
   int n_layers;    /* --cdae-n-layers */
   int act;         /* any ARDAE_ACT_* but NONE (with a piecewise linear one mlp-grad's second-order terms are zero)  */
@@ -260,6 +262,33 @@ int ardae_dae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, 
                                  float delta, uint64_t seed, uint64_t offset_sigma, uint64_t offset_eps, const void* state,
                                  uint64_t first_row, float* xbar, float* sigma, float* eps_out, float* workspace,
                                  size_t workspace_floats, float* loss, float* grads, void* stream);
+
+/* ---- plain DAE (models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90; notebooks/dae_toy.ipynb): ardae_cdae_desc.kind 6 / 7 ------
+ * The score network that is NOT amortised over the noise level: MLP(input_dim, h, 1) on x_bar alone whose input-gradient is the
+ * score (kind 6, MLPGradDAE, graddae/mlp.py:57,88-92) or MLP(input_dim, h, input_dim) that is the score (kind 7, MLPResDAE,
+ * resdae/mlp.py:45,73).  context_dim must be 0 and ctx NULL, as for kinds 2 / 3.  Parameters in named_parameters() order:
+ * neglogprob.layers.{0..L-1}.{weight,bias}, neglogprob.fc.* (kind 6) / main.layers.*, main.fc.* (kind 7); layers.0.weight is
+ * [h, d] - there is no sigma column.  ardae_cdae_param_floats / packed_floats / workspace_floats / pack / loss_grads / score take
+ * these kinds, N = B * S rows in any factorisation; the update is the one of kinds 2 / 3 with every sigma-column term removed.  The
+ * loss is unchanged, mean((sigma[r] g + eps)^2) with a per-row sigma [N] (graddae/mlp.py:96: `std * glogprob` broadcasts a float or
+ * a tensor alike); ardae_cdae_score ignores `sigma` (NULL allowed), as DAE.glogprob ignores std (graddae/mlp.py:101-116).  Kind 6
+ * leaves neglogprob.fc.bias's gradient untouched like kinds 0 / 2.
+ *
+ * ardae_dae_noise_perturb: add_gaussian_noise (graddae/mlp.py:21-23) with ONE noise level on a broadcast batch:
+ * xbar[(b, j)] = fma(s, eps[(b, j)], x[b]) and sigma_out[r] = s for all N = B * nsigma rows, where s is the f32 in bytes 24..27 of
+ * the block `dae_state` (ardae_dae_state_advance) when that is non-NULL, else the argument `sigma`.  The update is then
+ * ardae_philox_normal_at (eps), ardae_dae_noise_perturb, ardae_cdae_loss_grads; a fused draw + perturbation + first-layer kernel like
+ * ardae_dae_perturb_loss_grads' was built and measured, and did not pay. */
+int ardae_dae_noise_perturb(const float* x /* [B, d] */, const float* eps /* [B*nsigma, d] */, int B, int nsigma, int d, float sigma,
+                            const void* dae_state, float* xbar, float* sigma_out /* [B*nsigma] */, void* stream);
+/* The DAE STATE: the step state with the noise level of the coming step as f32 in bytes 24..27 (the train state's beta slot; bytes
+ * 28..31 stay zero), so that a captured step replays through the notebook's sigma annealing (dae_toy.ipynb's training cell).
+ * `ardae_dae_state_advance` does what ardae_step_state_advance does and then, for the new t and i = t - 1 (the notebook's i_ep), in
+ * double, every operation rounded on its own and in the notebook's order, rounded to float once:
+ *   perc = min((i + 1) / (double)sigma_annealing, 1.0);  sigma = sigma_max * (1 - perc) + sigma_min * perc
+ * sigma_annealing <= 0: the constant sigma_min. */
+int ardae_dae_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double sigma_max, double sigma_min,
+                            int64_t sigma_annealing, void* stream);
 
 /* ---- energy-function fitting (notebooks/ardae_fit.ipynb): energies, the implicit generator, torch.optim.Adam + StepLR -------------
  * One iteration of the notebook: num_dae_updates AR-DAE updates, each on a fresh sample of the generator, then one generator update

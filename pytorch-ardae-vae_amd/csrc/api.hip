@@ -105,6 +105,10 @@ int ardae_train_state_advance(void* state, uint64_t rng_inc, double lr, double b
   return launch_train_state_advance(state, rng_inc, lr, beta1, beta2, beta_init, beta_fin, beta_annealing, std_scale, seed_rows,
                                     (hipStream_t)stream);
 }
+int ardae_dae_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double sigma_max, double sigma_min,
+                            int64_t sigma_annealing, void* stream) {
+  return launch_dae_state_advance(state, rng_inc, lr, beta1, beta2, sigma_max, sigma_min, sigma_annealing, (hipStream_t)stream);
+}
 int ardae_seed_scale_dev(float* g, int64_t n, const void* state, void* stream) {
   ARDAE_CHECK_ARG(state, "seed_scale_dev: state is NULL");
   return launch_scale(g, n, train_state_seed_scale(state), (hipStream_t)stream);

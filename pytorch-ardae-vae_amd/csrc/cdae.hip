@@ -1,4 +1,4 @@
-// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1) and unconditional (kind 2 / 3): forward, score pass, DAE loss,
+// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1), unconditional (kind 2 / 3) and plain DAE (kind 6 / 7): forward, score pass, DAE loss,
 // double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
 //
 // Maths: SURVEY.md Appendix A (closed form of models/graddae/mlp.py:400-444 under autograd), notation below.
@@ -23,7 +23,10 @@
 // the energy MLP reads the input itself, a_L := xbar, so W1a [h, h] becomes W1x [h, z] and the per-image bias [W1c c_L + d_1](b) the
 // plain d_1.  Every line above that names A_l, C_l, a_l (l < L), c_l, r_l, tau_l, pbar_l, phat_l or Qsum drops out:
 //   g = e_1 W1x;  eb_1 = gbar W1x^T;  W1x's gradient = e_1 (x) gbar + qhat_1 (x) xbar.
-// In the code: `cond` marks what exists for kinds 0 / 1 only, `grad` what the energy kinds (0 / 2) add to the res kinds.
+// The plain DAEs (kinds 6 / 7; models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90) are the unconditional kinds whose network does not see
+// sigma: W1 = W1x [h, z], no w1s, h_1 = sp(W1x xbar + d_1).  The loss keeps its per-row sigma.
+// In the code: `cond` marks what exists for kinds 0 / 1 only, `grad` what the energy kinds (0 / 2 / 6) add to the res kinds, `has_sigma`
+// the sigma column of W1 (every kind but 6 / 7).
 #include <vector>
 
 #include "ardae_hip.h"
@@ -36,22 +39,22 @@ namespace {
 
 struct CdaeLayout {
   int kind, z, c, h, L, act;
-  bool cond, grad;
+  bool cond, grad, has_sigma;
   std::vector<Lin> ctx, inp, neg;   // ctx/inp (cond): L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae / main)
   size_t total = 0;
-  // W1 = neg[0] is [W1a | W1c | w1s] (cond) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then the sigma column
+  // W1 = neg[0] is [W1a | W1c | w1s] (cond) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then (has_sigma) the sigma column
   int k1() const { return cond ? h : z; }
   int sigma_col() const { return cond ? 2 * h : z; }
 
   explicit CdaeLayout(const ardae_cdae_desc& d)
-      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(d.kind < 2), grad(d.kind == 0 || d.kind == 2) {
+      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(d.kind < 2), grad(d.kind % 2 == 0), has_sigma(d.kind < 6) {
     size_t off = 0;
     auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
     if (cond) {
       for (int l = 0; l < L; ++l) add(ctx, h, l == 0 ? c : h);
       for (int l = 0; l < L; ++l) add(inp, h, l == 0 ? z : h);
     }
-    for (int l = 0; l < L; ++l) add(neg, h, l == 0 ? sigma_col() + 1 : h);
+    for (int l = 0; l < L; ++l) add(neg, h, l == 0 ? sigma_col() + (has_sigma ? 1 : 0) : h);
     add(neg, grad ? 1 : z, h);
     total = off;
   }
@@ -60,7 +63,7 @@ struct CdaeLayout {
 // offsets into the packed-weight buffer
 struct PackedLayout {
   std::vector<size_t> ctx_f, ctx_b, inp_f, inp_b, neg_f, neg_b;   // ctx / inp: cond only; neg_*[0] unused (W1 is split below)
-  size_t w1_f, w1_b, w1c_f, w1c_b, w1s;                           // w1: W1's N-row panel (W1a | W1x); w1c: cond only
+  size_t w1_f, w1_b, w1c_f, w1c_b, w1s;                           // w1: W1's N-row panel (W1a | W1x); w1c: cond only; w1s: has_sigma only
   size_t fc_f, fc_b;   // res kinds only (dae.fc / main.fc [z,h])
   PackedLayout(const CdaeLayout& P, PackList& pl) {
     const size_t L = P.L;
@@ -71,7 +74,7 @@ struct PackedLayout {
     pl.pair(W1, w1_f, w1_b, 0, P.k1());
     w1c_f = w1c_b = 0;
     if (P.cond) pl.pair(W1, w1c_f, w1c_b, P.h, P.h);
-    w1s = pl.take(P.h);                              // the sigma column, gathered by cdae_pack_impl
+    w1s = P.has_sigma ? pl.take(P.h) : 0;            // the sigma column, gathered by cdae_pack_impl
     for (size_t l = 1; l < L; ++l) pl.pair(P.neg[l], neg_f[l], neg_b[l]);
     fc_f = fc_b = 0;
     if (!P.grad) pl.pair(P.neg[L], fc_f, fc_b);
@@ -81,7 +84,8 @@ struct PackedLayout {
 
 int desc_ok(const ardae_cdae_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "cdae: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind >= 0 && d->kind <= 3, "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad) or 3 (unconditional res)");
+  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7,
+                  "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad), 3 (unconditional res), 6 (plain DAE grad) or 7 (plain DAE res)");
   ARDAE_CHECK_ARG(d->kind >= 2 || d->context_dim >= 1, "cdae: kinds 0 / 1 need context_dim >= 1 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(d->kind < 2 || d->context_dim == 0, "cdae: kinds 2 / 3 have no context: context_dim must be 0 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->n_layers >= 1, "cdae: bad dimensions");
@@ -146,11 +150,12 @@ void cdae_wgrads(const CdaeLayout& P, const CdaeWs& W, const float* xbar, const 
   const int ld1 = P.neg[0].in;
   const size_t gW1 = P.neg[0].w;
   // One N-row layer's weight [h, I] and bias.  grad kinds: s (x) t of the score pass + ghat (x) x of the backward; res kinds: the second term
-  // alone; the bias gradient is ghat's column sums.  first: W1's N-row panel, which also yields w1s = sum_i sigma_i ghat[i]
+  // alone; the bias gradient is ghat's column sums.  first: W1's N-row panel, which (has_sigma) also yields w1s = sum_i sigma_i ghat[i]
   auto push = [&](const Lin& lin, int I, const float* s, const float* t, const float* ghat, const float* x, bool first) {
-    const float* rs = first ? sigma : nullptr;
-    float* out_rs = first ? wl.g(gW1 + P.sigma_col()) : nullptr;
-    const int ld = first ? ld1 : I, ld_rs = first ? ld1 : 0;
+    const bool scol = first && P.has_sigma;
+    const float* rs = scol ? sigma : nullptr;
+    float* out_rs = scol ? wl.g(gW1 + P.sigma_col()) : nullptr;
+    const int ld = first ? ld1 : I, ld_rs = scol ? ld1 : 0;
     if (P.grad) wl.push2(N, h, I, s, t, I, ghat, x, I, 1, rs, wl.g(lin.w), ld, wl.g(lin.b), out_rs, ld_rs);
     else wl.push2(N, h, I, ghat, x, I, nullptr, nullptr, 0, 0, rs, wl.g(lin.w), ld, wl.g(lin.b), out_rs, ld_rs);
   };
@@ -184,7 +189,7 @@ size_t workspace_floats(const CdaeLayout& P, int B, int S, bool need_grads) {
 int cdae_pack_impl(const CdaeLayout& P, const float* params, float* packed, hipStream_t st) {
   PackList pl(params, packed);
   const PackedLayout K(P, pl);
-  ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + P.sigma_col(), P.neg[0].in, P.h, packed + K.w1s, st));
+  if (P.has_sigma) ARDAE_TRY(launch_gather_strided(params + P.neg[0].w + P.sigma_col(), P.neg[0].in, P.h, packed + K.w1s, st));
   return pl.launch(st);
 }
 
@@ -239,7 +244,8 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   const CdaeLayout P(*d);
   const bool cond = P.cond, grad = P.grad;
   ARDAE_CHECK_ARG(cond || ctx == nullptr, "cdae: kinds 2 / 3 take no context: ctx must be NULL");
-  ARDAE_CHECK_ARG(params && packed && xbar && sigma && (ctx || !cond) && workspace, "cdae: null pointer argument");
+  // the plain DAEs' score does not read sigma (DAE.glogprob ignores std); their loss layer does
+  ARDAE_CHECK_ARG(params && packed && xbar && (sigma || (!P.has_sigma && !need_grads)) && (ctx || !cond) && workspace, "cdae: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S < (int64_t)1 << 30, "cdae: bad batch (B=%d, S=%d)", B, S);
   ARDAE_CHECK_ARG(!need_grads || (eps && loss && grads), "cdae: loss/grads/eps must be given");
   ARDAE_CHECK_ARG(need_grads || score_out, "cdae: score_out is NULL");
@@ -269,7 +275,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   };
   auto energy_layer = [&](int l) {
     LinArgs A{}; A.Y = hh[l]; A.ldY = h;
-    if (l == 1) { A.rowscale = sigma; A.rowscale_w = packed + K.w1s; }
+    if (l == 1 && P.has_sigma) { A.rowscale = sigma; A.rowscale_w = packed + K.w1s; }
     if (l == 1 && cond) { A.rowbias = cb; A.rowbias_ld = h; A.rows_per_group = S; } else A.bias = params + P.neg[l - 1].b;
     if (grad && l == L) { A.Y2 = e[L]; A.ldY2 = h; A.R = wfc; }   // e_L = -w (.) s(h_L)
     return l == 1 ? lin_args(act, N, h, x1, k1, k1, packed + K.w1_f, A) : lin_args(act, N, h, hh[l - 1], h, h, packed + K.neg_f[l - 1], A);
@@ -393,7 +399,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
 // what the fused front end of dae_perturb.hip needs of an unconditional network: where W1 / d_1 live, and the carved h_1 it writes
 int dae_front_slots(const ardae_cdae_desc* d, int N, float* workspace, size_t ws_floats, size_t* w1, size_t* b1, float** h1) {
   ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(d->kind >= 2, "dae_perturb_loss_grads: kind must be 2 or 3");
+  ARDAE_CHECK_ARG(d->kind >= 2, "dae_perturb_loss_grads: the network must be unconditional");
   const CdaeLayout P(*d);
   const size_t need = workspace_floats(P, N, 1, true);
   ARDAE_CHECK_ARG(ws_floats >= need, "dae_perturb_loss_grads: workspace too small (%zu < %zu floats)", ws_floats, need);

@@ -1,5 +1,6 @@
 // Front end of the unconditional AR-DAE update (ardae_cdae_desc.kind 2 / 3): the perturbation of a broadcast batch, and the same with
-// its two draws and the score network's first layer in one kernel.
+// its two draws and the score network's first layer in one kernel.  And the plain DAE's perturbation (kind 6 / 7, notebooks/dae_toy.ipynb):
+// one noise level for the whole batch, a value or the DAE state's.
 //
 // Reference: the training cells of notebooks/ardae_toy.ipynb / ardae_fit.ipynb (x.unsqueeze(1).expand(B, nsigma, d).contiguous(),
 // std = delta * randn) and add_gaussian_noise (models/graddae/mlp.py:21-23).  Row (b, j) reads x[b]: the broadcast is never written.
@@ -7,6 +8,7 @@
 
 #include "ardae_hip.h"
 #include "common.h"
+#include "elementwise.h"
 #include "front_layer.h"
 #include "philox.h"
 #include "profile.h"
@@ -29,6 +31,19 @@ __global__ __launch_bounds__(256) void dae_perturb_kernel(const float* __restric
     const int64_t row = e / d;
     const int k = (int)(e - row * d);
     xbar[e] = __builtin_fmaf(sigma[row], eps[e], x[(row / nsigma) * d + k]);
+  }
+}
+
+// The plain DAE's perturbation: one noise level s for every row (sp non-null: the device block's, one wave-uniform load)
+__global__ __launch_bounds__(256) void dae_noise_perturb_kernel(const float* __restrict__ x, const float* __restrict__ eps, int64_t n, int nsigma, int d,
+                                                                float sv, const float* __restrict__ sp, float* __restrict__ xbar,
+                                                                float* __restrict__ sigma_out) {
+  const float s = sp ? *sp : sv;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = e / d;
+    const int k = (int)(e - row * d);
+    xbar[e] = __builtin_fmaf(s, eps[e], x[(row / nsigma) * d + k]);
+    if (k == 0) sigma_out[row] = s;
   }
 }
 
@@ -131,6 +146,22 @@ int ardae_dae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, 
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
   return dae_loss_grads_from_h1(d, params, packed, xbar, sigma, eps_out, N, workspace, workspace_floats, loss, grads, st);
+}
+
+int ardae_dae_noise_perturb(const float* x, const float* eps, int B, int nsigma, int d, float sigma, const void* dae_state, float* xbar,
+                            float* sigma_out, void* stream) {
+  ARDAE_CHECK_ARG(x && eps && xbar && sigma_out, "dae_noise_perturb: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && nsigma > 0 && d > 0 && (int64_t)B * nsigma * d < (int64_t)1 << 31, "dae_noise_perturb: bad batch (B=%d, nsigma=%d, d=%d)", B,
+                  nsigma, d);
+  const int64_t n = (int64_t)B * nsigma * d;
+  const hipStream_t st = (hipStream_t)stream;
+  const DevFloat s = dae_state ? dae_state_sigma(dae_state) : DevFloat(sigma);
+  prof_begin(st, "dae_noise_perturb_kernel", 2.0 * (double)n, 4.0 * (2.0 * (double)n + (double)B * nsigma + (double)B * d));
+  hipLaunchKernelGGL(dae_noise_perturb_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, x, eps, n, nsigma, d, s.v,
+                     s.p, xbar, sigma_out);
+  prof_end(st);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // extern "C"

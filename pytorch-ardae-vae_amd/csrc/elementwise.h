@@ -54,6 +54,10 @@ int launch_step_state_advance(void* state, uint64_t rng_inc, double lr, double b
 // the same, then beta and the entropy-seed factor of the coming step: see ardae_train_state_advance in ardae_hip.h
 int launch_train_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double beta_init, double beta_fin,
                                int64_t beta_annealing, double std_scale, int64_t seed_rows, hipStream_t st);
+// the same, then the noise level of the coming step: see ardae_dae_state_advance in ardae_hip.h
+int launch_dae_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double sigma_max, double sigma_min,
+                             int64_t sigma_annealing, hipStream_t st);
+DevFloat dae_state_sigma(const void* state);
 int launch_adam_ref_dev(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, double beta1, double beta2, double eps,
                         const void* state, hipStream_t st);
 int launch_philox_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st);

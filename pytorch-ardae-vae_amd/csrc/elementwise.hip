@@ -41,6 +41,24 @@ __global__ void train_state_advance_kernel(TrainState* s, uint64_t rng_inc, doub
   s->seed_scale = (float)(scaled / (double)seed_rows);
 }
 
+// the noise level of step t (0-based i = t - 1, the notebook's i_ep) as notebooks/dae_toy.ipynb's training cell forms it in Python:
+// every operation rounded to double on its own, the result rounded to float once (what torch does with the Python float)
+__global__ void dae_state_advance_kernel(DaeState* s, uint64_t rng_inc, double lr, double beta1, double beta2, double sigma_max,
+                                         double sigma_min, int64_t sigma_annealing) {
+#pragma clang fp contract(off)
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t i = step_state_advance1(&s->step, rng_inc, lr, beta1, beta2) - 1;
+  double sigma = sigma_min;
+  if (sigma_annealing > 0) {
+    const double frac = (double)(i + 1) / (double)sigma_annealing;
+    const double perc = frac < 1.0 ? frac : 1.0;
+    const double hi = sigma_max * (1.0 - perc), lo = sigma_min * perc;
+    sigma = hi + lo;
+  }
+  s->sigma = (float)sigma;
+  s->pad = 0.f;
+}
+
 // q0: first counter of this launch - a rank that owns rows [r0, r1) of a draw generates elements [first, first + n) of the
 // GLOBAL draw (first = 4 q0), so the numbers do not depend on how the rows are partitioned over ranks
 __global__ void philox_normal_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset, const StepState* state, uint64_t q0) {
@@ -733,8 +751,18 @@ int launch_train_state_advance(void* state, uint64_t rng_inc, double lr, double 
   return 0;
 }
 
+int launch_dae_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double sigma_max, double sigma_min,
+                             int64_t sigma_annealing, hipStream_t st) {
+  ARDAE_CHECK_ARG(state, "dae_state_advance: null state");
+  hipLaunchKernelGGL(dae_state_advance_kernel, dim3(1), dim3(64), 0, st, (DaeState*)state, rng_inc, lr, beta1, beta2, sigma_max, sigma_min,
+                     sigma_annealing);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
 DevFloat train_state_beta(const void* state) { return DevFloat(&((const TrainState*)state)->beta); }
 DevFloat train_state_seed_scale(const void* state) { return DevFloat(&((const TrainState*)state)->seed_scale); }
+DevFloat dae_state_sigma(const void* state) { return DevFloat(&((const DaeState*)state)->sigma); }
 
 int launch_philox_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st) {
   ARDAE_CHECK_ARG(out && n > 0, "philox_uniform: bad arguments");

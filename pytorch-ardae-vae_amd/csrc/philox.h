@@ -68,6 +68,15 @@ struct TrainState {
 };
 static_assert(sizeof(TrainState) == 32, "the train state fills ARDAE_STEP_STATE_BYTES");
 
+// The DAE state (ardae_dae_state_advance): the step state with the noise level of the coming step of notebooks/dae_toy.ipynb in the
+// train state's beta slot.
+struct DaeState {
+  StepState step;
+  float sigma;             // sigma_max (1 - perc) + sigma_min perc, perc = min(t / sigma_annealing, 1)
+  float pad;
+};
+static_assert(sizeof(DaeState) == 32, "the DAE state fills ARDAE_STEP_STATE_BYTES");
+
 // The fit state (ardae_fit_state_advance): a step state whose Adam coefficients follow the StepLR schedule, and behind it the
 // energy weight and learning rate of the coming iteration and of the one just done (the logged pair).
 struct FitState {

@@ -8,6 +8,7 @@ buffers are all-reduced (RCCL over xGMI via torch.distributed backend "nccl") be
 import contextlib
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -812,6 +813,33 @@ class ScoreConfig:
     momentum: float = 0.5         # use the module path (MLPGradARDAE + torch.optim.Adam).  rmsprop and sgd coincide with torch's.
 
 
+@dataclass
+class DaeConfig:
+    """Constants of notebooks/dae_toy.ipynb's training cell: one noise level per step, annealed linearly from sigma_max to sigma_min over
+    sigma_annealing steps and computed on the device (ardae_dae_state_advance); torch.optim.Adam(lr=0.005)."""
+    sigma_max: float = 5.0
+    sigma_min: float = 0.05
+    sigma_annealing: int = 4000   # steps of the ramp; 0 or below: the constant sigma_min
+    nsigma: int = 10              # `num_sigma`: a batch of B samples is B * nsigma rows (each with its own eps)
+    lr: float = 5e-3
+    optimizer: str = "adam_torch"  # torch.optim.Adam, the notebook's (_FlatOpt; sgd | adam | amsgrad | rmsprop as for ScoreConfig)
+    beta1: float = 0.9
+    momentum: float = 0.0
+
+    def __post_init__(self):
+        if int(self.sigma_annealing) != self.sigma_annealing:
+            raise ValueError(f"sigma_annealing must be a whole number of steps (got {self.sigma_annealing!r})")
+
+
+def dae_sigma(sigma_max, sigma_min, sigma_annealing, step):
+    """The noise level of 0-based step `step` (the notebook's i_ep), in the notebook's operation order; numpy.float32 of it is what
+    ardae_dae_state_advance writes for t = step + 1."""
+    if sigma_annealing <= 0:
+        return float(sigma_min)
+    perc = min((step + 1) / float(sigma_annealing), 1.0)
+    return sigma_max * (1 - perc) + sigma_min * perc
+
+
 class ArdaeScoreEngine:
     """One AR-DAE update of an unconditional score network (`net.MLPGradARDAE` / `net.MLPResARDAE`) as ONE captured unit:
     advance the step state, draw sigma and eps, perturb the broadcast batch, loss and gradients on B * nsigma rows, optimiser,
@@ -820,6 +848,11 @@ class ArdaeScoreEngine:
     validated before any pointer reaches a kernel, in-step Philox offsets are RNG_STRIDE * step + {0 (sigma), 1 (eps)} - below
     rng.HOST_STREAM.  One stream, one linear graph; there is no data parallelism here.
 
+    With a plain DAE (`net.MLPGradDAE` / `net.MLPResDAE`) and a `DaeConfig` the same engine runs notebooks/dae_toy.ipynb's update: no
+    sigma draw - the step's one noise level is read from the device block, where `ardae_dae_state_advance` leaves the annealed value -
+    so `noise` is {'eps'} alone, the in-step Philox offset RNG_STRIDE * step + 1 (eps; slot 0 stays unused), and `stats()` reports
+    `loss` and `sigma`.
+
     A sampler that stays the caller's torch module takes its entropy gradient as `output.backward(engine.score(output.detach()) / B)`;
     the whole iteration of ardae_fit.ipynb on the device - generator, energy, this update - is `ArdaeFitEngine` (fit.py)."""
 
@@ -827,8 +860,14 @@ class ArdaeScoreEngine:
 
     def __init__(self, dae, cfg: ScoreConfig, batch_size, graph=True):
         dae._require_gpu()
-        if int(dae._desc.kind) not in (2, 3):
-            raise TypeError("ArdaeScoreEngine drives the unconditional networks (net.MLPGradARDAE / net.MLPResARDAE)")
+        kind = int(dae._desc.kind)
+        if kind not in (2, 3, 6, 7):
+            raise TypeError("ArdaeScoreEngine drives the unconditional networks (net.MLPGradARDAE / net.MLPResARDAE with a ScoreConfig, "
+                            "net.MLPGradDAE / net.MLPResDAE with a DaeConfig)")
+        self.plain = kind >= 6
+        if not isinstance(cfg, DaeConfig if self.plain else ScoreConfig):
+            raise TypeError(f"{type(dae).__name__} takes a {'DaeConfig' if self.plain else 'ScoreConfig'}, not a {type(cfg).__name__}: ScoreConfig "
+                            "(a sigma draw per row) belongs to the AR-DAE networks, DaeConfig (one annealed sigma per step) to the plain DAEs")
         if int(cfg.nsigma) < 1 or int(batch_size) < 1:
             raise ValueError(f"nsigma and batch_size must be positive (got {cfg.nsigma}, {batch_size})")
         self.dae, self.cfg = dae, cfg
@@ -843,9 +882,11 @@ class ArdaeScoreEngine:
         self.grads = torch.zeros_like(dae._flat)
         self.n_grad = dae._flat.numel() - (1 if dae._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
         self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.opt = _FlatOpt(cfg.optimizer, dae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state)
+        self.sched = (float(cfg.sigma_max), float(cfg.sigma_min), int(cfg.sigma_annealing)) if self.plain else None
+        self.opt = _FlatOpt(cfg.optimizer, dae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state, dae=self.sched)
         self._ladder = CaptureLadder(self.dev, graph)
-        self.fused_front = L.debug_knob("ARDAE_FUSED_DAE_FRONT", "1") != "0" and bool(L.query("ardae_dae_perturb_fused_ok", dae._desc, self.S))
+        self.fused_front = (not self.plain and L.debug_knob("ARDAE_FUSED_DAE_FRONT", "1") != "0"       # (the plain DAEs have no fused front end)
+                            and bool(L.query("ardae_dae_perturb_fused_ok", dae._desc, self.S)))
         self._x = None
         self._score_ws = {}
         self.step_count = 0
@@ -864,7 +905,13 @@ class ArdaeScoreEngine:
 
     def _body(self, x, noise):
         d, seed = self.dae._desc, rng.get_state()["seed"]
-        if noise is None and self.fused_front:
+        if self.plain:             # sigma: the device block's in every form of the step
+            if noise is None:
+                L.call("ardae_philox_normal_at", self.eps, self.N * self.d, seed, 1, self.state, 0)
+            L.call("ardae_dae_noise_perturb", x, self.eps, self.B, self.S, self.d, 0.0, self.state, self.xbar, self.sigma)
+            L.call("ardae_cdae_loss_grads", d, self.dae._flat, self.pk, self.xbar, self.sigma, self.eps, None, self.N, 1, self.ws, self.ws.numel(),
+                   self.loss, self.grads, None)
+        elif noise is None and self.fused_front:
             L.call("ardae_dae_perturb_loss_grads", d, self.dae._flat, self.pk, x, self.B, self.S, float(self.cfg.delta), seed, 0, 1, self.state, 0,
                    self.xbar, self.sigma, self.eps, self.ws, self.ws.numel(), self.loss, self.grads)
         else:
@@ -882,14 +929,20 @@ class ArdaeScoreEngine:
         L.call("ardae_cdae_pack", d, self.dae._flat, self.pk)
         self.opt.advance(self.RNG_STRIDE)     # for the NEXT step: Philox base += stride, t += 1
 
-    def step(self, x, noise=None):
+    def step(self, x, noise=None, sigma=None):
         """One AR-DAE update on the B samples x [B, d] (each used with nsigma noise levels)."""
+        if sigma is not None:
+            raise ValueError(f"sigma={sigma!r}: " + (f"this engine computes sigma on the device (DaeConfig(sigma_max={self.cfg.sigma_max}, sigma_min="
+                             f"{self.cfg.sigma_min}, sigma_annealing={self.cfg.sigma_annealing})); a second source is refused" if self.plain else
+                             "the AR-DAE update draws its noise levels; inject them through noise={'sigma', 'eps'}"))
         self._check_batch(x, "step(x)")
         if noise is not None:
-            check_tensor(noise["sigma"], "step(noise): sigma", self.dev, numel=self.N)
+            if not self.plain:
+                check_tensor(noise["sigma"], "step(noise): sigma", self.dev, numel=self.N)
             check_tensor(noise["eps"], "step(noise): eps", self.dev, numel=self.N * self.d)
             # into the engine's own buffers: the launches (and stats()) then read what a drawn step would have left there
-            self.sigma.copy_(noise["sigma"].reshape(-1))
+            if not self.plain:
+                self.sigma.copy_(noise["sigma"].reshape(-1))
             self.eps.copy_(noise["eps"].reshape(self.N, self.d))
             noise = {"sigma": self.sigma, "eps": self.eps}
         elif self.use_graph and x is not self._x:
@@ -924,7 +977,11 @@ class ArdaeScoreEngine:
         return out
 
     def stats(self):
-        """Host copy of the last step's loss and mean |sigma| (the only synchronising call)."""
+        """Host copy of the last step's loss and mean |sigma| (the only synchronising call); a plain DAE: its loss and the finished step's
+        sigma, recomputed on the host from the step count (nothing is read back for it)."""
+        if self.plain:
+            sigma = float(np.float32(dae_sigma(*self.sched, self.step_count - 1))) if self.step_count else float("nan")
+            return dict(loss=float(self.loss), sigma=sigma)
         v = torch.cat([self.loss, self.sigma.abs().mean().reshape(1)]).tolist()
         return dict(loss=v[0], sigma_abs_mean=v[1])
 
@@ -949,6 +1006,12 @@ class ArdaeScoreEngine:
             self.state.copy_(eng["step_state"].to(self.dev))
         else:
             rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt.advance(self.RNG_STRIDE))
+        if self.plain and eng is not None:
+            # bytes 24..27 recomputed from t (ArdaeEngine._refresh_train_state): step the block back by one and advance it again, so that a
+            # file written under another schedule resumes at THIS engine's sigma
+            self.state[0] -= self.RNG_STRIDE
+            self.state[1] -= 1
+            self.opt.advance(self.RNG_STRIDE)
         self._ladder.reset()                    # parameters were rewritten outside of the captured step
         bump_versions(self.dae)
         self.repack()

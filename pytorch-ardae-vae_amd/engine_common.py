@@ -87,10 +87,13 @@ class _FlatOpt:
     that receive gradients (a grad-kind score network's trailing neglogprob.fc.bias does not and keeps no state).  Adam's t and bias
     corrections live in a 32-byte device block (`ardae_step_state_advance`) so that a captured step can be replayed.  `train`:
     (beta_init, beta_fin, beta_annealing, std_scale, seed_rows) of a beta schedule - the block is then advanced by
-    `ardae_train_state_advance`, which also writes the coming step's beta and entropy-seed factor into its last 8 bytes."""
-    KINDS = ("sgd", "adam", "amsgrad", "rmsprop")
+    `ardae_train_state_advance`, which also writes the coming step's beta and entropy-seed factor into its last 8 bytes.  `dae`:
+    (sigma_max, sigma_min, sigma_annealing) of notebooks/dae_toy.ipynb's noise schedule - the block is advanced by
+    `ardae_dae_state_advance`, which writes the coming step's sigma there.  'adam_torch' is torch.optim.Adam (epsilon after the bias
+    correction; `ardae_adam_torch_step_dev`): it reads the device block, so it runs inside an engine's step only."""
+    KINDS = ("sgd", "adam", "amsgrad", "rmsprop", "adam_torch")
 
-    def __init__(self, kind, flat, n, lr, beta1, momentum, state=None, train=None):
+    def __init__(self, kind, flat, n, lr, beta1, momentum, state=None, train=None, dae=None):
         if kind not in self.KINDS:
             raise NotImplementedError(f"unknown optimizer: {kind}")                     # ivae_ardae.py:555-556,621-622
         self.kind, self.flat, self.n, self.lr, self.beta1, self.momentum = kind, flat, int(n), float(lr), float(beta1), float(momentum)
@@ -98,16 +101,18 @@ class _FlatOpt:
         self.a = None if kind == "sgd" else z()                                         # exp_avg | square_avg
         self.b = None if kind == "sgd" else z()                                         # exp_avg_sq | momentum_buffer
         self.c = z() if kind == "amsgrad" else None                                     # max_exp_avg_sq
-        self.steps, self.train = 0, train
+        self.steps, self.train, self.dae = 0, train, dae
         self.state = state if state is not None else torch.zeros(4, dtype=torch.int64, device=flat.device)
 
     @property
     def adam(self):
-        return self.kind in ("adam", "amsgrad")
+        return self.kind in ("adam", "amsgrad", "adam_torch")
 
     def advance(self, rng_inc=0):
         if self.train is not None:
             L.call("ardae_train_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999, *self.train)
+        elif self.dae is not None:
+            L.call("ardae_dae_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999, *self.dae)
         else:
             L.call("ardae_step_state_advance", self.state, rng_inc, self.lr, self.beta1, 0.999)
 
@@ -117,6 +122,10 @@ class _FlatOpt:
             L.call("ardae_sgd_step", p, g, self.n, self.lr)
         elif self.kind == "rmsprop":
             L.call("ardae_rmsprop_step", p, g, self.a, self.b, self.n, self.lr, 0.99, 1e-8, self.momentum)
+        elif self.kind == "adam_torch":
+            if not in_step:
+                raise NotImplementedError("adam_torch takes t and its bias corrections from the device block: it runs inside an engine's step")
+            L.call("ardae_adam_torch_step_dev", p, g, self.a, self.b, self.n, self.beta1, 0.999, 1e-8, self.state)
         elif in_step:      # t and the bias corrections come from the device block (advanced inside the step)
             L.call("ardae_adam_ref_step_dev", p, g, self.a, self.b, self.c, self.n, self.beta1, 0.999, 1e-8, self.state)
         else:
@@ -125,7 +134,7 @@ class _FlatOpt:
     # torch.optim.Optimizer.state_dict() layout (per-parameter views of the flat buffers), so that files written by the reference loop, by
     # the drop-in modules + net.Adam / net.RMSprop, and by the engines are interchangeable
     def state_names(self):
-        return {"sgd": (), "adam": ("exp_avg", "exp_avg_sq"), "amsgrad": ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
+        return {"sgd": (), "adam": ("exp_avg", "exp_avg_sq"), "adam_torch": ("exp_avg", "exp_avg_sq"), "amsgrad": ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
                 "rmsprop": ("square_avg", "momentum_buffer")}[self.kind]
 
     def buffers(self):
@@ -162,7 +171,8 @@ class _FlatOpt:
     def load_state_dict(self, module, sd, what):
         """Inverse of state_dict(), also for what torch.optim and the reference's optimisers write.  -> the step count found (0: empty state)."""
         state, groups = sd["state"], sd.get("param_groups")
-        if groups and self._kind_of_group(groups[0]) != self.kind:
+        # (torch.optim.Adam and the vendored Adam write the same param_group: either file loads into 'adam' and 'adam_torch')
+        if groups and self._kind_of_group(groups[0]) != ("adam" if self.kind == "adam_torch" else self.kind):
             raise ValueError(f"{what}: written by optimiser {self._kind_of_group(groups[0])!r}, but this engine was built with {self.kind!r} for that network")
         for t in self.buffers():
             t.zero_()

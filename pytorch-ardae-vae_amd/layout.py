@@ -1,8 +1,8 @@
 """Parameter names / shapes / flat-buffer offsets, identical to the reference's `named_parameters()` order.
 
 Reference: models/layers.py:477-515 (MLP: `layers.{i}.{weight,bias}`, `fc.{weight,bias}`), :681-724 (ContextConcatMLP),
-models/ivae/mnist.py:123-199, models/ivae/toy.py:154-194,694-737, models/graddae/mlp.py:137,342-378,
-models/resdae/mlp.py:111,287-326.  The C++ side (csrc/cdae.hip, csrc/model.hip) computes the same offsets; the ABI
+models/ivae/mnist.py:123-199, models/ivae/toy.py:154-194,694-737, models/graddae/mlp.py:57,137,342-378,
+models/resdae/mlp.py:45,111,287-326.  The C++ side (csrc/cdae.hip, csrc/model.hip) computes the same offsets; the ABI
 test checks `ardae_*_param_floats` against these totals.
 """
 import math
@@ -122,6 +122,16 @@ def dae_spec(kind, input_dim, h_dim, n_layers):
         return _mlp("neglogprob.", input_dim + 1, h_dim, 1, n_layers)
     if kind == "res":
         return _mlp("main.", input_dim + 1, h_dim, input_dim, n_layers)
+    raise NotImplementedError(kind)
+
+
+def dae_plain_spec(kind, input_dim, h_dim, n_layers):
+    """The plain DAE of notebooks/dae_toy.ipynb (models/graddae/mlp.py:57, models/resdae/mlp.py:45): one MLP on x_bar alone;
+    `layers.0.weight` is [h, d], there is no sigma column.  ardae_cdae_desc.kind 6 ('grad') / 7 ('res')."""
+    if kind == "grad":
+        return _mlp("neglogprob.", input_dim, h_dim, 1, n_layers)
+    if kind == "res":
+        return _mlp("main.", input_dim, h_dim, input_dim, n_layers)
     raise NotImplementedError(kind)
 
 

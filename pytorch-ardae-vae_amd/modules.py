@@ -3,6 +3,7 @@
     net.MNISTIPVAE / net.ToyIPVAE        <- models/ivae/mnist.py:201-301, models/ivae/toy.py:739-873 (enc_type='concat')
     net.MLPGradCARDAE / net.MLPResCARDAE <- models/graddae/mlp.py:341-483, models/resdae/mlp.py:286-413
     net.MLPGradARDAE / net.MLPResARDAE   <- models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167
+    net.MLPGradDAE / net.MLPResDAE       <- models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90
 
 Same constructor kwargs, same `state_dict()` keys and `[out, in]` layouts (reference checkpoints load), same method
 names and argument meaning, same exception types.  Parameters are `nn.Parameter` views into ONE flat fp32 buffer
@@ -188,7 +189,7 @@ class _ScoreNet(FlatParamModule):
             raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
 
     def _build_net(self, first_kind, spec, input_dim, context_dim, h_dim, std, num_hidden_layers, nonlinearity, noise_type):
-        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional); its res sibling is the next."""
+        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional, 6 plain DAE); its res sibling is the next."""
         self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
         self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
         self._desc = L.CdaeDesc(first_kind if self._kind == "grad" else first_kind + 1, input_dim, context_dim, h_dim, num_hidden_layers, L.ACT[nonlinearity])
@@ -305,6 +306,61 @@ class MLPGradARDAE(ARDAE):
 
 class MLPResARDAE(ARDAE):
     """models/resdae/mlp.py::ARDAE (exported as MLPResARDAE, models/__init__.py:6): the MLP's output is the score."""
+    _kind = "res"
+
+
+class DAE(_ScoreNet):
+    """models/graddae/mlp.py:39-116 / models/resdae/mlp.py:27-90: the plain denoising autoencoder of notebooks/dae_toy.ipynb, a score network
+    on x_bar alone - one noise level per call (`std`, default `self.std`), not an input of the network."""
+
+    def __init__(self, input_dim=2, h_dim=1000, std=0.1, num_hidden_layers=1, nonlinearity="tanh", noise_type="gaussian"):
+        super().__init__()
+        self._check(noise_type, nonlinearity)
+        if num_hidden_layers < 1:
+            raise NotImplementedError("num_hidden_layers >= 1 (a score network without a hidden layer is linear in x)")
+        self._build_net(6, layout.dae_plain_spec(self._kind, input_dim, h_dim, num_hidden_layers), input_dim, 0, h_dim, std, num_hidden_layers,
+                        nonlinearity, noise_type)
+
+    def _rows(self, input):
+        self._require_gpu(input)
+        return _f32c(input).view(-1, self.input_dim)
+
+    def forward(self, input, std=None, eps=None):
+        """-> (None, loss) like the reference.  `std`: None (self.std), a Python number, or a tensor that broadcasts to [N, 1]
+        (graddae/mlp.py:77,96).  `eps` injects the Gaussian perturbation draw ([N, input_dim]); default: the library's Philox stream."""
+        x = self._rows(input)
+        N = x.size(0)
+        std = self.std if std is None else std
+        if torch.is_tensor(std):
+            self._require_gpu(std)
+            s = torch.broadcast_to(_f32c(std), (N, 1)).reshape(-1).contiguous()
+        else:
+            s = torch.full((N,), float(std), device=x.device, dtype=torch.float32)
+        if eps is None:
+            eps = rng.normal((N, self.input_dim), x.device)
+        eps = _f32c(eps).view(N, self.input_dim)
+        xbar = torch.empty_like(x)
+        L.call("ardae_dae_perturb", x, s, eps, N, 1, self.input_dim, xbar)      # add_gaussian_noise (graddae/mlp.py:21-23)
+        loss = _ArdaeLossFn.apply(self, xbar, s, eps, None, N, 1, *self.parameters())
+        return None, loss
+
+    def glogprob(self, input, std=None):
+        """The score at `input`; `std` is accepted and ignored, as in the reference (graddae/mlp.py:101-116)."""
+        x = self._rows(input)
+        N = x.size(0)
+        ws = self._ws(L.query("ardae_cdae_workspace_floats", self._desc, N, 1, 0))
+        out = torch.empty(N, self.input_dim, device=x.device)
+        L.call("ardae_cdae_score", self._desc, self._flat, self._packed_weights(), x, None, None, N, 1, ws, ws.numel(), out)
+        return out
+
+
+class MLPGradDAE(DAE):
+    """models/graddae/mlp.py::DAE (exported as MLPGradDAE, models/__init__.py): score = input-gradient of an energy MLP on x_bar."""
+    _kind = "grad"
+
+
+class MLPResDAE(DAE):
+    """models/resdae/mlp.py::DAE (exported as MLPResDAE, models/__init__.py): the MLP's output is the score."""
     _kind = "res"
 
 
