@@ -479,6 +479,22 @@ int ardae_gaussian_sample(const float* mu, const float* logvar, const float* eps
  * MultivariateNormal(mu, cov) of the IWAE proposal (ivae/mnist.py:397-406).  Not positive definite -> NaNs in that factor. */
 int ardae_cholesky_batched(const float* A, int batch, int n, float* L, void* stream);
 
+/* ---- IWAE evaluation (csrc/iwae.hip): the proposal of logprob_w_cov_gaussian_posterior (ivae/mnist.py:378-437) in one launch ---
+ * Per image b (one workgroup each, z <= 64): mu = column mean of zs[b] [ke, z]; cov = centred zc^T zc / (ke - 1) + jitter I
+ * (utils/stat.py:127-158; the aux models pass jitter 1e-5, ivae/auxmnist.py:321, the others 0); L = the lower Cholesky factor of cov (the
+ * factorisation of ardae_cholesky_batched); for each of the k proposal samples newz[b, j] = mu + L e_j and
+ * logq[b, j] = -0.5 sum e_j^2 - sum_i log L_ii - 0.5 z log 2 pi.  e = prop_noise [B, k, z], or, when prop_noise is NULL, drawn in the
+ * kernel: element first_element + (b k + j) z + i of the draw (seed, offset), the numbers ardae_philox_normal_at(out, B k z, seed,
+ * offset, NULL, first_element) would write (first_element a multiple of 4; a caller that walks a set in chunks passes the chunk's first
+ * image times k z and gets draws that do not depend on the chunking).  eps_out [B, k, z] (the e used), mu [B, z], chol [B, z, z] may be
+ * NULL.  A covariance that is not positive definite gives NaN in that image's newz and logq (and in chol, as ardae_cholesky_batched
+ * does), and touches no other image.  An image's outputs do not depend on B or on its place in the launch. */
+int ardae_iwae_proposal(const float* zs, const float* prop_noise, int B, int ke, int k, int z, float jitter, uint64_t seed, uint64_t offset,
+                        uint64_t first_element, float* newz, float* logq, float* eps_out, float* mu, float* chol, void* stream);
+/* out[b] = log(mean_j exp(lw_j - max_j lw) + 1e-10) + max_j lw with lw_j = -recon[b, j] - prior[b, j] - logq[b, j]
+ * (ivae/mnist.py:427-436); recon / prior / logq [B, k] (ardae_model_loss_rows' rows), fixed reduction order, NaN rows give NaN. */
+int ardae_iwae_reduce(const float* recon, const float* prior, const float* logq, int B, int k, float* out, void* stream);
+
 
 /* ---- scalar log channel + static-binarised batches ------------------------------------------------
  * The scalars the reference logs per --log-interval (ivae_ardae.py:850-906; five .item() synchronisations per step there,

@@ -9,6 +9,8 @@ Fused path:
     ArdaeScoreEngine, DaeConfig -- the same engine on a plain DAE (MLPGradDAE / MLPResDAE) with notebooks/dae_toy.ipynb's annealed noise level
     ArdaeFitEngine, FitConfig, Generator, energy -- a whole iteration of notebooks/ardae_fit.ipynb (implicit generator fitted to an energy function, the
                                  AR-DAE score as its entropy gradient) as one captured unit; utils/energy.py's functions on the device
+    IwaeEvaluator, ArdaeEngine.evaluate_iws -- evaluate_iws of the recipes: the IWAE bound of a whole set in large chunks, the proposal fused into one
+                                 kernel, one host synchronisation per set
     ScalarLog                 -- the reference's per-step scalars through a device ring buffer (no host sync in the step)
 The compute is libardae_hip.so (hand-written HIP for gfx950, C ABI in include/ardae_hip.h); there is no fallback.
 """
@@ -22,4 +24,5 @@ from .modules import (MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVA
 from .optim import Adam, RMSprop, Polyak, SWA  # noqa: F401
 from .engine import ArdaeEngine, ArdaeScoreEngine, DaeConfig, ScoreConfig, TrainConfig, annealing_func, dae_sigma  # noqa: F401
 from .fit import ArdaeFitEngine, FitConfig  # noqa: F401
+from .iwae import IwaeEvaluator, plan_chunks  # noqa: F401
 from .scalar_log import ScalarLog  # noqa: F401

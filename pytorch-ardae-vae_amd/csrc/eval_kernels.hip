@@ -5,6 +5,7 @@
 //   * batched Cholesky factorisation     the proposal of the IWAE evaluator: MultivariateNormal(mu, cov) at ivae/mnist.py:397-406
 //                                        factorises cov per image; here all images in one launch (z_dim <= 64)
 #include "ardae_hip.h"
+#include "cholesky.h"
 #include "common.h"
 #include "elementwise.h"
 
@@ -33,26 +34,17 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mu, const float
   sample[i] = mu[i] + expf(0.5f * logvar[i]) * eps[i];
 }
 
-// One 64-thread workgroup per matrix, right-looking, matrix in LDS; thread i owns row i.  A not positive definite gives NaN
+// One 64-thread workgroup per matrix, matrix in LDS, factorised by cholesky_lds (cholesky.h).  A not positive definite gives NaN
 // on and below the failing pivot (the caller checks, as torch.linalg.cholesky would raise).
 __global__ __launch_bounds__(64) void cholesky_kernel(const float* __restrict__ A, int n, float* __restrict__ Lout) {
-  __shared__ float a[64][65];
+  __shared__ float a[CHOL_MAX][CHOL_PITCH];
   const int i = threadIdx.x;
   const float* Ab = A + (size_t)blockIdx.x * n * n;
   float* Lb = Lout + (size_t)blockIdx.x * n * n;
   if (i < n)
     for (int j = 0; j < n; ++j) a[i][j] = Ab[(size_t)i * n + j];
   __syncthreads();
-  for (int k = 0; k < n; ++k) {
-    const float d = sqrtf(a[k][k]);
-    __syncthreads();
-    if (i == k) a[k][k] = d;
-    if (i > k && i < n) a[i][k] = a[i][k] / d;
-    __syncthreads();
-    if (i > k && i < n)
-      for (int j = k + 1; j <= i; ++j) a[i][j] -= a[i][k] * a[j][k];
-    __syncthreads();
-  }
+  cholesky_lds(a, n, i);
   if (i < n)
     for (int j = 0; j < n; ++j) Lb[(size_t)i * n + j] = j <= i ? a[i][j] : 0.f;
 }

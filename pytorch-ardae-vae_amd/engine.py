@@ -14,6 +14,7 @@ import torch
 from . import _lib as L
 from . import dist
 from . import rng
+from .iwae import IwaeEvaluator
 from .engine_common import CaptureLadder, _FlatOpt, bump_versions, capture_linear, check_batch, check_tensor, rebuild_step_state  # noqa: F401
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
@@ -180,6 +181,7 @@ class ArdaeEngine:
         self.avg = torch.zeros_like(model._flat) if self.wavg else None
         self._avg_origin = int(cfg.m_weight_avg_start) + 1
         self._avg_swap = None
+        self._iwae = None                               # evaluate_iws' evaluator: ((sample size, budget), IwaeEvaluator)
         if graph not in (True, False, "auto"):
             raise ValueError(f"graph must be True, False or 'auto', got {graph!r}")
         self.use_graph = bool(graph) and L.debug_knob("ARDAE_GRAPH", "1") != "0"
@@ -786,6 +788,21 @@ class ArdaeEngine:
             yield self.model
         finally:
             self.use_trained()
+
+    def evaluate_iws(self, x_all, sample_size, enc_noise=None, prop_noise=None, max_workspace_floats=None):
+        """evaluate_iws (ivae_ardae.py:644-673): the mean IWAE-`sample_size` bound over x_all [N, ...] on the device, one host
+        synchronisation (iwae.IwaeEvaluator).  With weight averaging it evaluates the averaged weights (:646-647) and puts the trained
+        ones back bit for bit (:671-672); between use_averaged() and use_trained() it evaluates what is in.  Under data parallelism the
+        calling rank evaluates all of x_all; there is no collective.  The evaluator and its buffers are kept for the next call."""
+        key = (int(sample_size), max_workspace_floats)
+        if self._iwae is None or self._iwae[0] != key:
+            kw = {} if max_workspace_floats is None else {"max_workspace_floats": max_workspace_floats}
+            self._iwae = (key, IwaeEvaluator(self.model, sample_size, **kw))
+        ev = self._iwae[1]
+        if self.wavg is None or self._avg_swap is not None:
+            return ev.evaluate(x_all, enc_noise, prop_noise)
+        with self.averaged_weights():
+            return ev.evaluate(x_all, enc_noise, prop_noise)
 
     def averaged_params(self):
         """The averaged weights as a flat tensor in named_parameters() order (None before the first averaging step)."""
