@@ -495,6 +495,27 @@ int ardae_iwae_proposal(const float* zs, const float* prop_noise, int B, int ke,
  * (ivae/mnist.py:427-436); recon / prior / logq [B, k] (ardae_model_loss_rows' rows), fixed reduction order, NaN rows give NaN. */
 int ardae_iwae_reduce(const float* recon, const float* prior, const float* logq, int B, int k, float* out, void* stream);
 
+/* ---- posterior diagnostics (csrc/diag.hip): the compute of the loop's `''' visualize '''` block (ivae_ardae.py:952-1111) ---------
+ * ardae_philox_normal_scaled_at: the numbers of ardae_philox_normal_at (same keying, first_element a multiple of 4), element e multiplied
+ * in fp32 by scale[((first_element + e) / width) % nslots] - a [rows, nslots, width] draw whose slot s carries the noise level scale[s], so
+ * that ONE sampler call with nz = nslots does model.encode(x, std=s) for every s (ivae_ardae.py:992-999,1001).  Bit-equal to the plain draw
+ * followed by `noise * float(std)`; a slot whose scale is exactly 0 is +0.0f.  scale: device, [nslots]. */
+int ardae_philox_normal_scaled_at(float* out, int64_t n, uint64_t seed, uint64_t offset, const void* state, uint64_t first_element, int width,
+                                  int nslots, const float* scale, void* stream);
+/* logvar[b, c] = log(var_r z[b, r, c] + eps), the unbiased variance over an image's nz sampler rows: torch.log(torch.var(latent, dim=1)
+ * + 1e-10) of ivae_ardae.py:956-957.  z [B, nz, zd].  Mean first, then the centred squares, in fp64 and in an order that depends on
+ * (nz, zd) only: no atomics, and an image's output does not depend on B or on its place in the launch.  nz == 1 gives NaN, as torch does. */
+int ardae_sample_logvar(const float* z, int B, int nz, int zd, float eps, float* logvar, void* stream);
+/* counts[s] += np.histogram2d(x_s, y_s, range=[[lo, hi], [lo, hi]], bins=bins)[0] for the nslots point sets
+ * (x_s, y_s)[i] = (pts[i row_stride + s slot_stride + col_x], pts[i row_stride + s slot_stride + col_y]), i < n
+ * (get_2d_histogram_plot, utils/visualization.py:193-204).  counts [nslots, bins, bins], first index x; it is ADDED to: zero it once per
+ * set.  Edges are np.linspace's doubles (k (hi - lo) / bins + lo, product and sum rounded apart; hi for k = bins), a float32 value v
+ * belongs to bin k when edge[k] <= v < edge[k + 1] compared in double, v == hi to the last bin; values outside, +-inf and NaN are dropped.
+ * bins <= 128 (one 32-bit table per workgroup in LDS, flushed with 64-bit atomic adds; integer sums: the result does not depend on their
+ * order). */
+int ardae_hist2d(const float* pts, int64_t n, int64_t row_stride, int nslots, int64_t slot_stride, int col_x, int col_y, double lo, double hi,
+                 int bins, int64_t* counts, void* stream);
+
 
 /* ---- scalar log channel + static-binarised batches ------------------------------------------------
  * The scalars the reference logs per --log-interval (ivae_ardae.py:850-906; five .item() synchronisations per step there,

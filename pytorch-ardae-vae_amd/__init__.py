@@ -11,6 +11,9 @@ Fused path:
                                  AR-DAE score as its entropy gradient) as one captured unit; utils/energy.py's functions on the device
     IwaeEvaluator, ArdaeEngine.evaluate_iws -- evaluate_iws of the recipes: the IWAE bound of a whole set in large chunks, the proposal fused into one
                                  kernel, one host synchronisation per set
+    PosteriorDiagnostics, ArdaeEngine.diagnostics -- the visualisation block's numbers (ivae_ardae.py:952-1111): 2-D histograms of the latents at
+                                 every noise level from one sampler pass, the data-recon-gen histograms of the 2-D problems, log var q(z); all on
+                                 the device, one host synchronisation per pass
     ScalarLog                 -- the reference's per-step scalars through a device ring buffer (no host sync in the step)
 The compute is libardae_hip.so (hand-written HIP for gfx950, C ABI in include/ardae_hip.h); there is no fallback.
 """
@@ -25,4 +28,5 @@ from .optim import Adam, RMSprop, Polyak, SWA  # noqa: F401
 from .engine import ArdaeEngine, ArdaeScoreEngine, DaeConfig, ScoreConfig, TrainConfig, annealing_func, dae_sigma  # noqa: F401
 from .fit import ArdaeFitEngine, FitConfig  # noqa: F401
 from .iwae import IwaeEvaluator, plan_chunks  # noqa: F401
+from .diagnostics import PosteriorDiagnostics  # noqa: F401
 from .scalar_log import ScalarLog  # noqa: F401

@@ -15,6 +15,7 @@ from . import _lib as L
 from . import dist
 from . import rng
 from .iwae import IwaeEvaluator
+from .diagnostics import PosteriorDiagnostics
 from .engine_common import CaptureLadder, _FlatOpt, bump_versions, capture_linear, check_batch, check_tensor, rebuild_step_state  # noqa: F401
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
@@ -182,6 +183,7 @@ class ArdaeEngine:
         self._avg_origin = int(cfg.m_weight_avg_start) + 1
         self._avg_swap = None
         self._iwae = None                               # evaluate_iws' evaluator: ((sample size, budget), IwaeEvaluator)
+        self._diag = None                               # diagnostics' PosteriorDiagnostics, with its buffers
         if graph not in (True, False, "auto"):
             raise ValueError(f"graph must be True, False or 'auto', got {graph!r}")
         self.use_graph = bool(graph) and L.debug_knob("ARDAE_GRAPH", "1") != "0"
@@ -803,6 +805,15 @@ class ArdaeEngine:
             return ev.evaluate(x_all, enc_noise, prop_noise)
         with self.averaged_weights():
             return ev.evaluate(x_all, enc_noise, prop_noise)
+
+    def diagnostics(self, x_all, x_batch=None):
+        """The visualisation block (ivae_ardae.py:952-1111) on the device: diagnostics.PosteriorDiagnostics.run on the engine's model with the
+        weights that are in - the LIVE ones, as the reference's block reads them (the averaged weights are swapped in for evaluate_iws only).
+        x_batch: the images of log var q(z) (the reference takes the last training batch; default: the first batch_size images of x_all).
+        Rank-local, no collective; it consumes host-stream Philox offsets and nothing of the step's state."""
+        if self._diag is None:
+            self._diag = PosteriorDiagnostics(self.model)
+        return self._diag.run(x_all, x_all[:self.B] if x_batch is None else x_batch)
 
     def averaged_params(self):
         """The averaged weights as a flat tensor in named_parameters() order (None before the first averaging step)."""

@@ -42,16 +42,16 @@ def plan_chunks(N, rows_per_image, floats_per_image, budget):
     return [(s, min(s + C, N)) for s in range(0, N, C)]
 
 
-def _check(t, what, shape):
+def _check(t, what, shape, who="IwaeEvaluator"):
     """float32, contiguous, on the device, `shape` (leading dimension and element count) - in this order, before anything is launched."""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError(f"IwaeEvaluator: {what}: expected a float32 tensor on the GPU, got {getattr(t, 'dtype', type(t))}")
+        raise TypeError(f"{who}: {what}: expected a float32 tensor on the GPU, got {getattr(t, 'dtype', type(t))}")
     if not t.is_contiguous():
-        raise ValueError(f"IwaeEvaluator: {what} must be contiguous (chunks are passed as slices of it)")
+        raise ValueError(f"{who}: {what} must be contiguous (chunks are passed as slices of it)")
     if not t.is_cuda:
-        raise TypeError(f"IwaeEvaluator: {what}: expected a float32 tensor on the GPU, got {t.dtype} on {t.device}")
+        raise TypeError(f"{who}: {what}: expected a float32 tensor on the GPU, got {t.dtype} on {t.device}")
     if t.dim() < 1 or t.size(0) != shape[0] or t.numel() != shape[0] * shape[1] * shape[2]:
-        raise ValueError(f"IwaeEvaluator: {what} must be {list(shape)}, got {list(t.shape)}")
+        raise ValueError(f"{who}: {what} must be {list(shape)}, got {list(t.shape)}")
     return t
 
 
