@@ -376,7 +376,7 @@ int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, doubl
  *                        noise of such a call = [eps0: B q x noise_dim | eps: B q q x z_dim], two consecutive blocks; hidden1a context
  *                        cat(h0, h) [B, 2 h_dim] */
 typedef struct ardae_model_desc {
-  int kind;
+  int kind;     /* 0 .. 7 above; 8 / 9: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0) */
   int input_dim, noise_dim, h_dim, z_dim;
   int n_layers; /* --model-n-layers */
   int act;      /* any ARDAE_ACT_* but NONE; kinds 5 / 6: ARDAE_ACT_ELU */
@@ -465,6 +465,59 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
                                          const float* noise, int B, int nz, const float* dz_extra, const void* state,
                                          float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
 
+
+/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, models/vae/toy.py; csrc/vaemodel.hip): ardae_model_desc.kind 8 / 9 ------
+ * The second trainer of the reference: an encoder MLP with a Gaussian head and its analytic KL, no sampler noise, no score network.
+ *   kind 8 (MNISTVAE, `vae.py --model mnist`): encode.main.{layers.0..n_layers-2, fc}, encode.reparam.{mean_fn, logvar_fn}, decode.main.{layers.*, fc},
+ *                        decode.reparam.logit_fn; Bernoulli decoder, x rescaled to 2x - 1 inside the encoder (vae/mnist.py:54)
+ *   kind 9 (ToyVAE, `vae.py --model toy`): the same without the rescale, decode.reparam.{mean_fn, logvar_fn}: Gaussian decoder
+ * noise_dim must be 0 and flags 0; n_layers 1 .. 4.  ardae_model_param_floats / packed_floats / workspace_floats (nz = 1; mode 0: encode_stats, 1: forward +
+ * backward, 2: decode) / pack / decode / loss_rows take these kinds; ardae_model_encode and ardae_model_vae_* refuse them (there is no sampler).
+ *
+ * ardae_vae_forward: mu = M h + m, lv = L h + l on the encoder's last hidden rows h, z = mu + exp(lv / 2) eps,
+ *   kld_b = -0.5 sum_c (1 + lv - mu^2 - exp(lv)) (utils/vae.py:78-92), the decoder and the row reconstruction loss;
+ *   losses[3] = {mean_b(recon_b + beta kld_b), mean recon, mean kld} as VAE.forward returns them (unscaled: loss_scale enters the backward only).
+ *   x [B, input_dim]; eps [B, z_dim], or NULL: drawn in the head kernel - element i = element i of the draw (seed, offset [+ state.rng_offset]),
+ *   keyed exactly like ardae_philox_normal_at(out, B z_dim, seed, offset, state, 0).  z_out [B, z_dim]; eps_out [B, z_dim] (the eps used; may be
+ *   NULL).  Activations stay in `workspace` for the backward call.  The _dev twins read beta from the train state block `beta_state`.
+ * ardae_vae_backward: grads = grads_beta * grads + d/dparams [loss_scale * loss] from the workspace of the matching forward.  With c = loss_scale / B the
+ *   head is closed form: dmu = dz + c beta mu, dlv = dz (z - mu) / 2 + c beta (exp(lv) - 1) / 2 (one element-wise launch); every weight gradient
+ *   goes out as one ardae_wgrad_batch problem list.
+ * ardae_vae_encode_stats: mu, lv [B, z_dim] without a draw (the encoder call of logprob and of the latent plots).  Workspace: mode 0.
+ * ardae_vae_head: the head alone on hidden rows hid [B, h_dim] -> mu, lv, z_out [B, z_dim], kld [B], eps_out (may be NULL with variant 1).
+ *   variant 1: gauss_head_kernel, ONE launch over 8-row tiles (a masked last row tile, any h_dim; every product sum over ascending k from a
+ *   zero accumulator, the bias added after, each row's KL terms added in ascending column order: a row's bits do not depend on B);
+ *   variant 2: the unfused launches (two narrow linears, the draw, the reparameterisation, the KL rows); variant 0: what ardae_vae_forward runs - the
+ *   fused kernel where ardae_vae_head_fused_ok, unless ARDAE_VAE_HEAD_UNFUSED=1 is set under ARDAE_DEBUG_KNOBS=1.  ardae_vae_head_fused_ok: 1 where
+ *   z_dim <= 64 and the rows of both head matrices start on 16 bytes (h_dim a multiple of 4 and both parameter offsets multiples of 4 floats: the
+ *   recipe's 300 -> 2 x 32); variant 1 runs for any z_dim <= 64, reading float by float where that does not hold (the toy recipe's z_dim 2, where it only
+ *   ties with the unfused launches, which are the default there).
+ * ardae_vae_kld_rows: kld[b] = -0.5 sum_c (1 + lv - mu^2 - exp(lv)) from mu, lv [B, z], the terms in double and added over ascending c - the row values
+ *   of the head, for callers that hold the statistics (the ELBO rows of the evaluator). */
+int ardae_vae_head_fused_ok(const ardae_model_desc* d);
+int ardae_vae_kld_rows(const float* mu, const float* lv, int B, int z, float* kld, void* stream);
+int ardae_vae_head(const ardae_model_desc* d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
+                   uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z_out, float* eps_out, float* kld, void* stream);
+int ardae_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* eps, int B, float beta,
+                      float loss_scale, uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t workspace_floats, float* z_out,
+                      float* eps_out, float* losses, void* stream);
+int ardae_vae_forward_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* eps, int B,
+                          const void* beta_state, float loss_scale, uint64_t seed, uint64_t offset, const void* state, float* workspace,
+                          size_t workspace_floats, float* z_out, float* eps_out, float* losses, void* stream);
+int ardae_vae_backward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, float beta, float loss_scale,
+                       float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
+int ardae_vae_backward_dev(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, const void* beta_state,
+                           float loss_scale, float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
+int ardae_vae_encode_stats(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, float* workspace,
+                           size_t workspace_floats, float* mu_out, float* lv_out, void* stream);
+/* Importance-weighted evaluation under the analytic posterior (VAE.logprob, vae/mnist.py:179-220): for each of B images k samples
+ * z = mu + exp(lv / 2) eps and their log-density logq = sum_c -0.5 ((z - mu)^2 / exp(lv) + lv + log 2 pi) (utils/stat.py:65-85), one launch, each
+ * sample's sum in double over ascending c.  mu, lv [B, z]; eps [B, k, z], or NULL: element i = element first_element + i of the draw (seed, offset),
+ * the numbers ardae_philox_normal_at(out, B k z, seed, offset, NULL, first_element) would write (first_element a multiple of 4: a caller that walks
+ * a set in chunks passes the chunk's first image times k z).  z_out [B, k, z], logq [B, k], eps_out [B, k, z] or NULL.  z <= 64.  The prior, the
+ * decoder, the row losses and the log-mean-exp are ardae_model_decode, ardae_model_loss_rows and ardae_iwae_reduce. */
+int ardae_vae_iwae_draw(const float* mu, const float* lv, const float* eps, int B, int k, int z, uint64_t seed, uint64_t offset,
+                        uint64_t first_element, float* z_out, float* logq, float* eps_out, void* stream);
 
 /* ---- evaluation / visualisation side of the model surface (csrc/eval_kernels.hip) ----------------------------
  * Decoder samples that ImplicitPosteriorVAE.forward / .generate return next to the losses (ivae/mnist.py:188-199,300,316):

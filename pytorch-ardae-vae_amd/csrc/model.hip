@@ -15,6 +15,7 @@
 #include "auxmodel.h"
 #include "convmodel.h"
 #include "resmodel.h"
+#include "vaemodel.h"
 #include "elementwise.h"
 #include "mlp.h"
 
@@ -67,9 +68,10 @@ struct ModelPacked {
 
 int desc_ok(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "model: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind >= 0 && d->kind <= 7,
-                  "model: kind must be 0 (MNISTIPVAE), 1 (ToyIPVAE concat), 2 (ConvIPVAE), 3 (MNISTAuxIPVAE), 4 (MNISTConvAuxIPVAE), 5 (ResConvIPVAE) or "
-                  "6 (MNISTResConvAuxIPVAE) or 7 (ToyAuxIPVAE)");
+  ARDAE_CHECK_ARG(d->kind >= 0 && d->kind <= 9,
+                  "model: kind must be 0 (MNISTIPVAE), 1 (ToyIPVAE concat), 2 (ConvIPVAE), 3 (MNISTAuxIPVAE), 4 (MNISTConvAuxIPVAE), 5 (ResConvIPVAE), "
+                  "6 (MNISTResConvAuxIPVAE), 7 (ToyAuxIPVAE), 8 (MNISTVAE) or 9 (ToyVAE)");
+  if (d->kind >= 8) return vae_desc_check(d);      // the Gaussian-posterior baselines: no noise input, no flags
   ARDAE_CHECK_ARG((d->flags & ~(ARDAE_MODEL_NO_CENTER | ARDAE_MODEL_HEAD_MASK | ARDAE_MODEL_CLIPPED | ARDAE_MODEL_CLIP_MASK)) == 0 &&
                       ((d->kind == 5 || d->kind == 6) ? (d->flags & ARDAE_MODEL_CLIP_MASK) == 0
                                                       : ((d->kind == 3 || d->kind == 7) ? (d->flags & ~ARDAE_MODEL_CLIP_MASK) == 0 : d->flags == 0)),
@@ -291,7 +293,8 @@ const Family MLP_FAMILY = {family_param_floats<ModelLayout, ModelPacked>, family
 // ------------------------------------------------------------------------------------------------ the families, by kind
 // desc_ok() has checked the kind
 const Family& family(const ardae_model_desc* d) {
-  static const Family* const by_kind[8] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY};
+  static const Family* const by_kind[10] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY,
+                                            &VAE_FAMILY, &VAE_FAMILY};
   return *by_kind[d->kind];
 }
 
@@ -388,7 +391,7 @@ int ardae_model_decode(const ardae_model_desc* d, const float* params, const flo
 int ardae_model_loss_rows(const ardae_model_desc* d, const float* out0, const float* out1, const float* x, const float* z, int rows,
                           int nz, float* recon_row, float* prior_row, void* stream) {
   ARDAE_TRY(desc_ok(d));
-  return launch_vae_loss(d->kind == 1 || d->kind == 7 ? 1 : 0, out0, out1, x, z, rows, nz, d->input_dim, d->z_dim, 1.f, 0, 0.f, nullptr, recon_row, prior_row, nullptr,
+  return launch_vae_loss(d->kind == 1 || d->kind == 7 || d->kind == 9 ? 1 : 0, out0, out1, x, z, rows, nz, d->input_dim, d->z_dim, 1.f, 0, 0.f, nullptr, recon_row, prior_row, nullptr,
                          nullptr, nullptr, (hipStream_t)stream);
 }
 

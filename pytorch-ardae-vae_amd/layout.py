@@ -103,6 +103,22 @@ def model_spec(kind, input_dim, noise_dim, h_dim, z_dim, n_layers, enc_type="res
     return s
 
 
+def vae_spec(kind, input_dim, h_dim, z_dim, n_layers):
+    """The Gaussian-posterior baselines of vae.py (models/vae/mnist.py:28-122 'mnist', models/vae/toy.py:21-120 'toy'): encoder and decoder are
+    MLP(..., num_hidden_layers - 1, use_nonlinearity_output=True) - n_layers Linear -> act each - with NormalDistributionLinear /
+    BernoulliDistributionLinear heads.  ardae_model_desc.kind 8 ('mnist') / 9 ('toy')."""
+    if kind not in ("mnist", "toy"):
+        raise NotImplementedError(kind)
+    s = _mlp("encode.main.", input_dim, h_dim, h_dim, n_layers - 1)
+    s += [("encode.reparam.mean_fn.weight", (z_dim, h_dim)), ("encode.reparam.mean_fn.bias", (z_dim,)),
+          ("encode.reparam.logvar_fn.weight", (z_dim, h_dim)), ("encode.reparam.logvar_fn.bias", (z_dim,))]
+    s += _mlp("decode.main.", z_dim, h_dim, h_dim, n_layers - 1)
+    if kind == "mnist":
+        return s + [("decode.reparam.logit_fn.weight", (input_dim, h_dim)), ("decode.reparam.logit_fn.bias", (input_dim,))]
+    return s + [("decode.reparam.mean_fn.weight", (input_dim, h_dim)), ("decode.reparam.mean_fn.bias", (input_dim,)),
+                ("decode.reparam.logvar_fn.weight", (input_dim, h_dim)), ("decode.reparam.logvar_fn.bias", (input_dim,))]
+
+
 def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):
     s = _mlp("ctx_encode.", context_dim, h_dim, h_dim, n_layers - 1)
     s += _mlp("inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)

@@ -4,6 +4,7 @@
     net.MLPGradCARDAE / net.MLPResCARDAE <- models/graddae/mlp.py:341-483, models/resdae/mlp.py:286-413
     net.MLPGradARDAE / net.MLPResARDAE   <- models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167
     net.MLPGradDAE / net.MLPResDAE       <- models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90
+    net.MNISTVAE / net.ToyVAE            <- models/vae/mnist.py:99-220, models/vae/toy.py:99-213 (the Gaussian-posterior baselines of vae.py)
 
 Same constructor kwargs, same `state_dict()` keys and `[out, in]` layouts (reference checkpoints load), same method
 names and argument meaning, same exception types.  Parameters are `nn.Parameter` views into ONE flat fp32 buffer
@@ -146,9 +147,10 @@ def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
-KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7}     # ardae_model_desc.kind
+KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7,      # ardae_model_desc.kind
+            "vae_mnist": 8, "vae_toy": 9}                                                                    # (vae.py's baselines: GaussianVAE below)
 AUX_KINDS = ("auxmnist", "auxconv", "auxresconv", "auxtoy")                                                 # hierarchical samplers
-GAUSSIAN_DECODERS = ("toy", "auxtoy")                                                                        # decode.reparam.{mean_fn, logvar_fn}
+GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -859,3 +861,175 @@ class ToyIPVAE(ImplicitPosteriorVAE):
         if enc_type != "concat":
             raise NotImplementedError(f"enc_type {enc_type!r}: only 'concat' is on the BASELINE path (SURVEY 2 #5)")
         super().__init__(energy_func, input_dim, noise_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, init, enc_type)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Gaussian-posterior VAE baselines (vae.py)
+# ---------------------------------------------------------------------------------------------------------------
+class _GaussVaeFn(torch.autograd.Function):
+    """VAE.forward through ardae_vae_forward; backward = ardae_vae_backward with the incoming d loss as loss_scale (the workspace keeps
+    the activations).  Only `loss` carries a gradient: z, mu and logvar are returned detached, as nothing in vae.py differentiates them."""
+
+    @staticmethod
+    def forward(ctx, mod, x, eps, beta, *params):
+        d, B = mod._desc, x.size(0)
+        ws = mod._ws(L.query("ardae_model_workspace_floats", d, B, 1, 1))
+        z, eps_out = torch.empty(B, mod.z_dim, device=x.device), torch.empty(B, mod.z_dim, device=x.device)
+        losses = torch.empty(3, device=x.device)
+        seed, offset = rng.get_state()["seed"], (rng._next_offset() if eps is None else 0)
+        L.call("ardae_vae_forward", d, mod._flat, mod._packed_weights(), x, eps, B, float(beta), 1.0, seed, offset, None, ws, ws.numel(), z, eps_out,
+               losses)
+        ctx.mod, ctx.ws, ctx.x, ctx.beta = mod, ws, x, float(beta)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(z, eps_out, losses)
+        return losses[0].clone(), z, eps_out, losses
+
+    @staticmethod
+    def backward(ctx, dloss, *_unused):
+        mod = ctx.mod
+        grads = torch.empty_like(mod._flat)
+        L.call("ardae_vae_backward", mod._desc, mod._flat, mod._packed_weights(), ctx.x, ctx.x.size(0), ctx.beta, 0.0 if dloss is None else float(dloss),
+               ctx.ws, ctx.ws.numel(), grads, 0.0)
+        return (None,) * 4 + tuple(mod.param_views(grads))
+
+
+class _GaussEncodeBox(_Box):
+    """`model.encode(x)` -> (z, mu, logvar) like Encoder.forward (vae/mnist.py:49-63), without autograd; `eps` injects the draw."""
+
+    def forward(self, x, eps=None):
+        o = self._owner_ref()
+        mu, lv = o.encode_stats(x)
+        e = rng.normal(tuple(mu.shape), mu.device) if eps is None else _f32c(eps).view_as(mu)
+        z = torch.empty_like(mu)
+        L.call("ardae_gaussian_sample", mu, lv, e, mu.numel(), z)
+        return z, mu, lv
+
+    def sample(self, mu, logvar, eps=None):
+        """NormalDistributionLinear.sample_gaussian (models/reparam.py:42-51)."""
+        e = rng.normal(tuple(mu.shape), mu.device) if eps is None else _f32c(eps).view_as(mu)
+        z = torch.empty_like(mu)
+        L.call("ardae_gaussian_sample", _f32c(mu), _f32c(logvar), e, mu.numel(), z)
+        return z
+
+
+class GaussianVAE(FlatParamModule):
+    """What MNISTVAE and ToyVAE share: ardae_model_desc kinds 8 / 9, an encoder MLP with a Gaussian head and its analytic KL, the decoders
+    of the implicit models.  There is no CPU path."""
+    _kind = None                 # "vae_mnist" | "vae_toy"
+    _packed_floats_fn, _pack_fn = "ardae_model_packed_floats", "ardae_model_pack"
+    return_samples = True        # forward() also returns the decoder sample / mean (one extra decoder pass); False: (None, None)
+    noise_dim = 0
+
+    def _build(self, energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers):
+        if energy_func is not normal_energy_func:
+            raise NotImplementedError("only utils.normal_energy_func is implemented on the HIP path")
+        if nonlinearity not in L.ACT or nonlinearity in ("none", None):
+            raise NotImplementedError(f"nonlinearity {nonlinearity!r}")
+        if not (int(input_dim) >= 1 and int(h_dim) >= 1 and int(z_dim) >= 1 and 1 <= int(num_hidden_layers) <= 4):
+            raise ValueError(f"{type(self).__name__}: dimensions must be positive and 1 <= num_hidden_layers <= 4 (got input_dim={input_dim}, "
+                             f"h_dim={h_dim}, z_dim={z_dim}, num_hidden_layers={num_hidden_layers})")
+        self.energy_func = energy_func
+        self.input_dim, self.h_dim, self.z_dim = int(input_dim), int(h_dim), int(z_dim)
+        self.latent_dim = self.z_dim
+        self.nonlinearity, self.num_hidden_layers = nonlinearity, int(num_hidden_layers)
+        self._desc = L.ModelDesc(KIND_IDS[self._kind], self.input_dim, 0, self.h_dim, self.z_dim, self.num_hidden_layers, L.ACT[nonlinearity], 0)
+        self._abi = (self._desc,)
+        self._build_params(layout.vae_spec(self._kind[len("vae_"):], self.input_dim, self.h_dim, self.z_dim, self.num_hidden_layers),
+                           {"encode": _GaussEncodeBox})
+        object.__setattr__(self.encode, "_owner_ref", weakref.ref(self))
+        self.reset_parameters()
+
+    _x = ImplicitPosteriorVAE._x
+    decode_params = ImplicitPosteriorVAE.decode_params
+    _decoder_sample = ImplicitPosteriorVAE._decoder_sample
+
+    def generate(self, batch_size=1, z=None, dec_noise=None):
+        """-> (x_sample, decoder mean, z) with z ~ N(0, I) (vae/mnist.py:164-177, vae/toy.py:154-167).  z / dec_noise inject the draws."""
+        self._require_gpu(z, dec_noise)
+        return ImplicitPosteriorVAE.generate(self, batch_size, z, dec_noise)
+
+    def encode_stats(self, input):
+        """(mu, logvar) [B, z_dim] of q(z | x), no draw (ardae_vae_encode_stats)."""
+        x = self._x(input)
+        B = x.size(0)
+        ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, B, 1, 0))
+        mu, lv = torch.empty(B, self.z_dim, device=x.device), torch.empty(B, self.z_dim, device=x.device)
+        L.call("ardae_vae_encode_stats", self._desc, self._flat, self._packed_weights(), x, B, ws, ws.numel(), mu, lv)
+        return mu, lv
+
+    def forward(self, input, beta=1.0, eps=None, dec_noise=None):
+        """-> (x_sample, decoder mean, z, loss, recon.detach(), kld.detach()) like the reference (vae/mnist.py:142-162).  `eps` [B, z_dim]
+        injects the posterior draw (default: drawn in the head kernel from the library's host Philox stream), `dec_noise` the decoder's."""
+        x = self._x(input)
+        B = x.size(0)
+        if eps is not None:
+            self._require_gpu(eps)
+            eps = _f32c(eps).view(B, self.z_dim)
+        loss, z, _, losses = _GaussVaeFn.apply(self, x, eps, beta, *self.parameters())
+        xs, xm = (None, None)
+        if self.return_samples:
+            with torch.no_grad():
+                xs, xm = self._decoder_sample(z, dec_noise)
+        return xs, xm, z, loss, losses[1].detach(), losses[2].detach()
+
+    def logprob_rows(self, input, sample_size=128, eps=None):
+        """The IWAE-`sample_size` bound of every image under the analytic posterior, [B] on the device (VAE.logprob before its mean,
+        vae/mnist.py:179-217): encoder statistics, ardae_vae_iwae_draw (samples and log q in one launch), decoder, row losses,
+        log-mean-exp.  eps [B, sample_size, z_dim] injects the draws."""
+        x = self._x(input)
+        B, k, zd = x.size(0), int(sample_size), self.z_dim
+        if zd > 64:
+            raise NotImplementedError(f"{type(self).__name__}.logprob: z_dim {zd} > 64: ardae_vae_iwae_draw takes latent widths up to 64")
+        with torch.no_grad():
+            mu, lv = self.encode_stats(x)
+            if eps is not None:
+                self._require_gpu(eps)
+                eps = _f32c(eps).view(B, k, zd)
+            z, logq = torch.empty(B * k, zd, device=x.device), torch.empty(B * k, device=x.device)
+            L.call("ardae_vae_iwae_draw", mu, lv, eps, B, k, zd, rng.get_state()["seed"], rng._next_offset() if eps is None else 0, 0, z, logq, None)
+            out = self.decode_params(z)
+            rec, pri, res = torch.empty(B * k, device=x.device), torch.empty(B * k, device=x.device), torch.empty(B, device=x.device)
+            L.call("ardae_model_loss_rows", self._desc, out[0], out[1] if len(out) > 1 else None, x, z, B * k, k, rec, pri)
+            L.call("ardae_iwae_reduce", rec, pri, logq, B, k, res)
+        return res
+
+    def logprob(self, input, sample_size=128, z=None, eps=None):
+        """VAE.logprob (vae/mnist.py:179-220; the reference ignores `z` too)."""
+        return self.logprob_rows(input, sample_size, eps).mean()
+
+
+class MNISTVAE(GaussianVAE):
+    """models/vae/mnist.py::VAE (`vae.py --model mnist`, the "# mlp" baseline of run_vae_dbmnist.sh): x -> 2x - 1 inside the encoder, Bernoulli decoder."""
+    _kind = "vae_mnist"
+
+    def __init__(self, energy_func=normal_energy_func, input_dim=784, h_dim=300, z_dim=32, nonlinearity="softplus", num_hidden_layers=2,
+                 do_xavier=False, do_m5bias=False):
+        super().__init__()
+        self.do_xavier, self.do_m5bias = do_xavier, do_m5bias
+        self._build(energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers)
+
+    def reset_parameters(self):
+        self._default_init()
+        with torch.no_grad():
+            p = dict(self.named_parameters())
+            if self.do_xavier:                              # self.apply(weight_init): xavier-uniform W, zero b (vae/mnist.py:16-21,125-127)
+                for t in p.values():
+                    nn.init.xavier_uniform_(t) if t.dim() == 2 else t.zero_()
+            if self.do_m5bias:                              # vae/mnist.py:128-129
+                p["decode.reparam.logit_fn.bias"].fill_(-5.0)
+
+
+class ToyVAE(GaussianVAE):
+    """models/vae/toy.py::VAE (`vae.py --model toy`): no rescale, Gaussian decoder (decode.reparam.{mean_fn, logvar_fn})."""
+    _kind = "vae_toy"
+
+    def __init__(self, energy_func=normal_energy_func, input_dim=2, h_dim=64, z_dim=2, nonlinearity="softplus", num_hidden_layers=1, init="gaussian"):
+        super().__init__()
+        self.init = init
+        self._build(energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers)
+
+    def reset_parameters(self):
+        self._default_init()
+        if self.init == "gaussian":                         # Decoder.reset_parameters (vae/toy.py:75-81)
+            with torch.no_grad():
+                dict(self.named_parameters())["decode.reparam.mean_fn.weight"].normal_()
