@@ -376,7 +376,8 @@ int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, doubl
  *                        noise of such a call = [eps0: B q x noise_dim | eps: B q q x z_dim], two consecutive blocks; hidden1a context
  *                        cat(h0, h) [B, 2 h_dim] */
 typedef struct ardae_model_desc {
-  int kind;     /* 0 .. 7 above; 8 / 9: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0) */
+  int kind;     /* 0 .. 7 above; 8 / 9 / 11: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0).
+                 * 10 is not a kind */
   int input_dim, noise_dim, h_dim, z_dim;
   int n_layers; /* --model-n-layers */
   int act;      /* any ARDAE_ACT_* but NONE; kinds 5 / 6: ARDAE_ACT_ELU */
@@ -466,12 +467,16 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
                                          float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
 
 
-/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, models/vae/toy.py; csrc/vaemodel.hip): ardae_model_desc.kind 8 / 9 ------
+/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, toy.py, conv.py; csrc/vaemodel.hip, csrc/convvae.hip): ardae_model_desc.kind 8 / 9 / 11 ------
  * The second trainer of the reference: an encoder MLP with a Gaussian head and its analytic KL, no sampler noise, no score network.
  *   kind 8 (MNISTVAE, `vae.py --model mnist`): encode.main.{layers.0..n_layers-2, fc}, encode.reparam.{mean_fn, logvar_fn}, decode.main.{layers.*, fc},
  *                        decode.reparam.logit_fn; Bernoulli decoder, x rescaled to 2x - 1 inside the encoder (vae/mnist.py:54)
  *   kind 9 (ToyVAE, `vae.py --model toy`): the same without the rescale, decode.reparam.{mean_fn, logvar_fn}: Gaussian decoder
- * noise_dim must be 0 and flags 0; n_layers 1 .. 4.  ardae_model_param_floats / packed_floats / workspace_floats (nz = 1; mode 0: encode_stats, 1: forward +
+ *   kind 11 (MNISTConvVAE, `vae.py --model conv`, models/vae/conv.py; 28 x 28 x 1 only): encode.conv{1,2,3} (the trunk of kind 2 on 2x - 1), encode.fc
+ *                        512 -> 800, encode.reparam.{mean_fn, logvar_fn} [z_dim, 800], then kind 2's decoder: decode.fc.{layers.0, fc}, decode.deconv{1,2},
+ *                        decode.reparam.logit_fn.  input_dim 784, h_dim 800 (the fc width, as kind 4 records it), n_layers 1, z_dim >= 1; every entry
+ *                        point below takes it, with the same workspace modes.  10 is not a kind.
+ * noise_dim must be 0 and flags 0; n_layers 1 .. 4 (kind 11: 1).  ardae_model_param_floats / packed_floats / workspace_floats (nz = 1; mode 0: encode_stats, 1: forward +
  * backward, 2: decode) / pack / decode / loss_rows take these kinds; ardae_model_encode and ardae_model_vae_* refuse them (there is no sampler).
  *
  * ardae_vae_forward: mu = M h + m, lv = L h + l on the encoder's last hidden rows h, z = mu + exp(lv / 2) eps,
@@ -491,7 +496,10 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
  *   fused kernel where ardae_vae_head_fused_ok, unless ARDAE_VAE_HEAD_UNFUSED=1 is set under ARDAE_DEBUG_KNOBS=1.  ardae_vae_head_fused_ok: 1 where
  *   z_dim <= 64 and the rows of both head matrices start on 16 bytes (h_dim a multiple of 4 and both parameter offsets multiples of 4 floats: the
  *   recipe's 300 -> 2 x 32); variant 1 runs for any z_dim <= 64, reading float by float where that does not hold (the toy recipe's z_dim 2, where it only
- *   ties with the unfused launches, which are the default there).
+ *   ties with the unfused launches, which are the default there).  Kind 11: on its 800-wide hidden rows gauss_head_kernel loses to the unfused
+ *   launches (51.0 against 19.8 us at 128 x 800 -> 2 x 32), so that kind's variant 1 is another fused head: the two products on the MFMA linears, then ONE
+ *   launch for the draw, the reparameterisation and the KL rows (three launches, every output equal to variant 2's bit for bit); ardae_vae_head_fused_ok is 1
+ *   for it wherever z_dim <= 64.
  * ardae_vae_kld_rows: kld[b] = -0.5 sum_c (1 + lv - mu^2 - exp(lv)) from mu, lv [B, z], the terms in double and added over ascending c - the row values
  *   of the head, for callers that hold the statistics (the ELBO rows of the evaluator). */
 int ardae_vae_head_fused_ok(const ardae_model_desc* d);

@@ -66,84 +66,15 @@ __global__ void col2im_s2_kernel(const float* __restrict__ cols, int IH, int IW,
   out[e] = v;
 }
 
-// ------------------------------------------------------------------------------------------------ layout
-// a Lin's weight is viewed as [out, in] (convs: [O, C*25]; deconvs: [in_ch, out_ch*25], with out_ch bias entries)
-struct ConvLayout {
-  int nd, zd, act;
-  Lin conv[3], fc4, fc5, dfc[2], dcv[3];
-  size_t total;
-  ConvLayout() : nd(0), zd(0), act(0), total(0) {}     // decoder-only view filled by AuxConvLayout
-  explicit ConvLayout(const ardae_model_desc& d) : nd(d.noise_dim), zd(d.z_dim), act(d.act) {
-    size_t off = 0;
-    auto add = [&](Lin& l, int out, int in, int nbias) { l = next_lin(off, out, in, nbias); };
-    add(conv[0], 16, 1 * 25, 16); add(conv[1], 32, 16 * 25, 32); add(conv[2], 32, 32 * 25, 32);
-    add(fc4, 800, 512 + nd, 800); add(fc5, zd, 800, zd);
-    add(dfc[0], 300, zd, 300); add(dfc[1], 512, 300, 512);
-    add(dcv[0], 32, 32 * 25, 32); add(dcv[1], 32, 16 * 25, 16); add(dcv[2], 16, 1 * 25, 1);
-    total = off;
-  }
-};
-
-struct ConvPacked {
-  size_t conv_f[3], conv_b[3], fc4i_f, fc4i_b, fc4n_f, fc5_f, fc5_b, dfc_f[2], dfc_b[2], dcv_f[3], dcv_b[3];
-  ConvPacked() {}     // decoder-only view filled by AuxConvPacked
-  ConvPacked(const ConvLayout& P, PackList& pl) {
-    for (int i = 0; i < 3; ++i) pl.pair(P.conv[i], conv_f[i], conv_b[i]);
-    pl.pair(P.fc4, fc4i_f, fc4i_b, 0, 512);                            // [800, 512 + nd]: image half both ways, noise half forward
-    fc4n_f = pl.panel(P.fc4.w + 512, P.fc4.in, 800, P.nd, false);
-    pl.pair(P.fc5, fc5_f, fc5_b);
-    decoder_panels(P, pl);
-  }
-  explicit ConvPacked(const ConvLayout& P, PackList&& sizing = PackList()) : ConvPacked(P, sizing) {}   // offsets only
-  // the decoder's five operators (shared with the hierarchical conv model, which reserves them at its own offsets)
-  void decoder_panels(const ConvLayout& P, PackList& pl) {
-    for (int i = 0; i < 2; ++i) pl.pair(P.dfc[i], dfc_f[i], dfc_b[i]);
-    for (int i = 0; i < 3; ++i) {   // ConvTranspose2d weight [in, out*25]: forward = X . W (transposed pack), backward-data = dC . W^T (natural)
-      dcv_f[i] = pl.panel(P.dcv[i].w, P.dcv[i].in, P.dcv[i].in, P.dcv[i].out, true);
-      dcv_b[i] = pl.panel(P.dcv[i].w, P.dcv[i].in, P.dcv[i].out, P.dcv[i].in, false);
-    }
-  }
-};
-
-// spatial sizes: encoder 28 -> 14 -> 7 -> 4; decoder grids 4 -> 8 (7 valid) -> 15 -> 28 (of 29)
-struct ConvWs {
-  // encoder (B rows)
-  float *x2, *cols[3], *hcv[3], *inp, *rb, *t1, *z;
-  // decoder (R rows)
-  float *d1, *d2, *g0, *c1, *u1, *c2, *u2, *c3, *logit, *rec_row, *pri_row;
-  // backward
-  float *dlogit, *dc3, *dp2, *dc2, *dp1, *dc1, *dg0, *dd2, *dd1, *dzq, *dz, *dt1, *drb, *dinp, *dinp_t, *dh3, *dcols3, *dh2, *dcols2, *dh1, *ones;
-};
-
-constexpr int EH[4] = {28, 14, 7, 4};      // encoder spatial sizes
-constexpr int ECH[4] = {1, 16, 32, 32};    // encoder channels
-
-void carve(const ConvLayout& P, const ConvPacked&, Bump& ws, int B, int nz, int mode, ConvWs& W) {
-  const size_t R = (size_t)B * nz;
-  W.x2 = ws.take((size_t)B * 784);
-  for (int i = 0; i < 3; ++i) {
-    W.cols[i] = ws.take((size_t)B * EH[i + 1] * EH[i + 1] * ECH[i] * 25);
-    W.hcv[i] = ws.take((size_t)B * EH[i + 1] * EH[i + 1] * ECH[i + 1]);
-  }
-  W.inp = ws.take((size_t)B * 512); W.rb = ws.take((size_t)B * 800);
-  W.t1 = ws.take(R * 800); W.z = ws.take(R * P.zd);
-  if (mode == 0) return;
-  W.d1 = ws.take(R * 300); W.d2 = ws.take(R * 512); W.g0 = ws.take(R * 512);
-  W.c1 = ws.take(R * 16 * 800); W.u1 = ws.take(R * 64 * 32);
-  W.c2 = ws.take(R * 64 * 400); W.u2 = ws.take(R * 225 * 16);
-  W.c3 = ws.take(R * 225 * 25); W.logit = ws.take(R * 784);
-  W.rec_row = ws.take(R); W.pri_row = ws.take(R);
-  if (mode == 2) return;
-  W.dlogit = ws.take(R * 784); W.dc3 = ws.take(R * 225 * 25); W.dp2 = ws.take(R * 225 * 16);
-  W.dc2 = ws.take(R * 64 * 400); W.dp1 = ws.take(R * 64 * 32); W.dc1 = ws.take(R * 16 * 800);
-  W.dg0 = ws.take(R * 512); W.dd2 = ws.take(R * 512); W.dd1 = ws.take(R * 300);
-  W.dzq = ws.take(R * P.zd); W.dz = ws.take(R * P.zd); W.dt1 = ws.take(R * 800);
-  W.drb = ws.take((size_t)B * 800); W.dinp = ws.take((size_t)B * 512); W.dinp_t = ws.take((size_t)B * 512);
-  W.dh3 = ws.take((size_t)B * 512); W.dcols3 = ws.take((size_t)B * 16 * 800); W.dh2 = ws.take((size_t)B * 49 * 32);
-  W.dcols2 = ws.take((size_t)B * 49 * 400); W.dh1 = ws.take((size_t)B * 196 * 16);
-  W.ones = ws.take(R * 784);
+// x[b][oh][ow][c] = 0 where oh >= VH or ow >= VW; x is NHWC [B, OH, OW, C]: the gradient at zero-padded positions, which a
+// dense_bwd has multiplied by act'(0) - 0 for relu and softplus, not for the other activations
+__global__ void zero_pad_kernel(float* __restrict__ x, int OH, int OW, int VH, int VW, int C, int64_t total) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int64_t pix = e / C;
+  const int ow = (int)(pix % OW), oh = (int)((pix / OW) % OH);
+  if (oh >= VH || ow >= VW) x[e] = 0.f;
 }
-using ConvEntry = Entry<ConvLayout, ConvPacked, ConvWs>;
 
 int im2col(const float* x, int Bn, int H, int Wd, int C, int OH, int OW, float* cols, hipStream_t st) {
   const int64_t total = (int64_t)Bn * OH * OW * C * 25;
@@ -158,8 +89,33 @@ int col2im(const float* cols, int Bn, int IH, int IW, int O, int OH, int OW, int
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ shared with csrc/convvae.hip (convmodel.h)
+void conv_trunk_carve(Bump& ws, size_t B, ConvWs& W) {
+  W.x2 = ws.take(B * 784);
+  for (int i = 0; i < 3; ++i) {
+    W.cols[i] = ws.take(B * EH[i + 1] * EH[i + 1] * ECH[i] * 25);
+    W.hcv[i] = ws.take(B * EH[i + 1] * EH[i + 1] * ECH[i + 1]);
+  }
+  W.inp = ws.take(B * 512);
+}
+
+void conv_decoder_carve(Bump& ws, size_t R, int zd, bool decode_only, ConvWs& W) {
+  W.d1 = ws.take(R * 300); W.d2 = ws.take(R * 512); W.g0 = ws.take(R * 512);
+  W.c1 = ws.take(R * 16 * 800); W.u1 = ws.take(R * 64 * 32);
+  W.c2 = ws.take(R * 64 * 400); W.u2 = ws.take(R * 225 * 16);
+  W.c3 = ws.take(R * 225 * 25); W.logit = ws.take(R * 784);
+  W.rec_row = ws.take(R); W.pri_row = ws.take(R);
+  if (decode_only) return;
+  W.dlogit = ws.take(R * 784); W.dc3 = ws.take(R * 225 * 25); W.dp2 = ws.take(R * 225 * 16);
+  W.dc2 = ws.take(R * 64 * 400); W.dp1 = ws.take(R * 64 * 32); W.dc1 = ws.take(R * 16 * 800);
+  W.dg0 = ws.take(R * 512); W.dd2 = ws.take(R * 512); W.dd1 = ws.take(R * 300);
+  W.dzq = ws.take(R * zd); W.dz = ws.take(R * zd); W.ones = ws.take(R * 784);
+}
+
 // conv trunk 1 -> 16 -> 32 -> 32 (k5 s2 p2, 28 -> 14 -> 7 -> 4) on the rescaled images x2 [B, 784]: fills cols / hcv and the
-// NCHW-flattened output inp [B, 512] (shared by ConvIPVAE and the two trunks of the hierarchical conv model)
+// NCHW-flattened output inp [B, 512] (shared by ConvIPVAE, the two trunks of the hierarchical conv model and the conv baseline)
 int trunk_fwd(const Lin* conv, const size_t* conv_f, const float* params, const float* packed, const float* x2, float* const* cols,
               float* const* hcv, float* inp, int B, int act, hipStream_t st) {
   const float* cur = x2;
@@ -181,21 +137,6 @@ int trunk_bwd(const size_t* conv_b, const float* packed, const float* dinp, floa
   ARDAE_TRY(col2im(dcols3, B, 4, 4, 32, 7, 7, 7, 7, nullptr, act, hcv[1], dh2, st));
   ARDAE_TRY(dense_fwd(ACT_NONE, B * 49, 400, dh2, 32, 32, packed + conv_b[1], nullptr, dcols2, st));
   return col2im(dcols2, B, 7, 7, 16, 14, 14, 14, 14, nullptr, act, hcv[0], dh1, st);
-}
-
-int conv_encode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* x, const float* noise,
-                    int B, int nz, ConvWs& W, float* z_out, hipStream_t st) {
-  const int R = B * nz, act = P.act;
-  ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // ivae/conv.py:81
-  ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.cols, W.hcv, W.inp, B, act, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, params + P.fc4.b, W.rb, st));   // image half of fc4, once per image
-  {
-    LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.t1; A.ldY = 800;
-    ARDAE_TRY(lin1(EPI_ACT, act, R, 800, noise, P.nd, P.nd, packed + K.fc4n_f, A, st));
-  }
-  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, params + P.fc5.b, W.z, st));
-  if (z_out) ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
-  return 0;
 }
 
 int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
@@ -224,7 +165,12 @@ int conv_decoder_bwd(const ConvLayout& P, const ConvPacked& K, const float* pack
   ARDAE_TRY(im2col(W.dlogit, R, 28, 28, 1, 15, 15, W.dc3, st));                 // cropped row/col 28 has no gradient
   ARDAE_TRY(dense_bwd(act, R * 225, 16, W.dc3, 25, packed + K.dcv_b[2], W.u2, W.dp2, st));   // dpre2 = (dc3 . W3^T) (.) act'(u2)
   ARDAE_TRY(im2col(W.dp2, R, 15, 15, 16, 8, 8, W.dc2, st));
-  ARDAE_TRY(dense_bwd(act, R * 64, 32, W.dc2, 400, packed + K.dcv_b[1], W.u1, W.dp1, st));   // zero at the padded positions: act'(0) = 0
+  ARDAE_TRY(dense_bwd(act, R * 64, 32, W.dc2, 400, packed + K.dcv_b[1], W.u1, W.dp1, st));   // zero at the padded positions where act'(0) = 0
+  if (act != ACT_RELU && act != ACT_SOFTPLUS) {      // ZeroPad2d passes no gradient: elu, tanh, leaky_relu and swish have act'(0) != 0
+    const int64_t total = (int64_t)R * 64 * 32;
+    hipLaunchKernelGGL(zero_pad_kernel, dim3(nblk(total)), dim3(256), 0, st, W.dp1, 8, 8, 7, 7, 32, total);
+    ARDAE_LAUNCH_CHECK();
+  }
   ARDAE_TRY(im2col(W.dp1, R, 8, 8, 32, 4, 4, W.dc1, st));
   ARDAE_TRY(dense_bwd(act, R * 16, 32, W.dc1, 800, packed + K.dcv_b[0], W.g0, W.dg0, st));   // g0 is the (permuted) activated output of decode.fc
   ARDAE_TRY(launch_nhwc_nchw(W.dg0, R, 16, 32, W.dd2, false, st));               // -> d(pre) of decode.fc.fc  [R,512]
@@ -232,10 +178,7 @@ int conv_decoder_bwd(const ConvLayout& P, const ConvPacked& K, const float* pack
   return dense_bwd(ACT_NONE, R, P.zd, W.dd1, 300, packed + K.dfc_b[0], W.dzq, W.dz, st, W.dzq);   // + prior + injected seed
 }
 
-// wgrad_splits hint of the conv backward: a tuning value, not the problem count (the list below has 14)
-constexpr int CONV_WGRAD_HINT = 18;
-
-// the decoder's eight weight-gradient problems (shared with the hierarchical conv model)
+// the decoder's eight weight-gradient problems
 void conv_decoder_wgrads(const ConvLayout& P, const ConvWs& W, int R, WgradList& wl) {
   // ConvTranspose2d: dW[in][out*25] = sum_rows input[row][in] * dcols[row][out*25]; its bias = sum of the output gradient
   wl.push(R * 225, 16, 25, W.u2, W.dc3, 25, wl.g(P.dcv[2].w), 25, nullptr);
@@ -248,15 +191,55 @@ void conv_decoder_wgrads(const ConvLayout& P, const ConvWs& W, int R, WgradList&
   wl.push(R, 300, P.zd, W.dd1, W.z, P.zd, wl.g(P.dfc[0].w), P.zd, wl.g(P.dfc[0].b));
 }
 
+void conv_trunk_wgrads(const Lin* conv, float* const* cols, const float* dh3, const float* dh2, const float* dh1, int B, WgradList& wl) {
+  wl.push(B * 16, 32, 800, dh3, cols[2], 800, wl.g(conv[2].w), 800, wl.g(conv[2].b));
+  wl.push(B * 49, 32, 400, dh2, cols[1], 400, wl.g(conv[1].w), 400, wl.g(conv[1].b));
+  wl.push(B * 196, 16, 25, dh1, cols[0], 25, wl.g(conv[0].w), 25, wl.g(conv[0].b));
+}
+
+// ------------------------------------------------------------------------------------------------ ConvIPVAE (kind == 2)
+// (Entry finds carve() by argument-dependent lookup, and ConvLayout lives in namespace ardae: this overload does too, file-local)
+static void carve(const ConvLayout& P, const ConvPacked&, Bump& ws, int B, int nz, int mode, ConvWs& W) {
+  const size_t R = (size_t)B * nz;
+  conv_trunk_carve(ws, (size_t)B, W);
+  W.rb = ws.take((size_t)B * 800);
+  W.t1 = ws.take(R * 800); W.z = ws.take(R * P.zd);
+  if (mode == 0) return;
+  conv_decoder_carve(ws, R, P.zd, mode == 2, W);
+  if (mode == 2) return;
+  W.dt1 = ws.take(R * 800);
+  W.drb = ws.take((size_t)B * 800); W.dinp = ws.take((size_t)B * 512); W.dinp_t = ws.take((size_t)B * 512);
+  W.dh3 = ws.take((size_t)B * 512); W.dcols3 = ws.take((size_t)B * 16 * 800); W.dh2 = ws.take((size_t)B * 49 * 32);
+  W.dcols2 = ws.take((size_t)B * 49 * 400); W.dh1 = ws.take((size_t)B * 196 * 16);
+}
+
+namespace {
+
+using ConvEntry = Entry<ConvLayout, ConvPacked, ConvWs>;
+
+
+int conv_encode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* x, const float* noise,
+                    int B, int nz, ConvWs& W, float* z_out, hipStream_t st) {
+  const int R = B * nz, act = P.act;
+  ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // ivae/conv.py:81
+  ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.cols, W.hcv, W.inp, B, act, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, params + P.fc4.b, W.rb, st));   // image half of fc4, once per image
+  {
+    LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.t1; A.ldY = 800;
+    ARDAE_TRY(lin1(EPI_ACT, act, R, 800, noise, P.nd, P.nd, packed + K.fc4n_f, A, st));
+  }
+  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, params + P.fc5.b, W.z, st));
+  if (z_out) ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
+  return 0;
+}
+
 // every weight-gradient problem of conv_model_vae_backward, with its scratch taken from ws
 void conv_wgrads(const ConvLayout& P, const ConvWs& W, int B, int R, const float* noise, WgradList& wl, Bump& ws) {
   conv_decoder_wgrads(P, W, R, wl);
   wl.push(R, P.zd, 800, W.dz, W.t1, 800, wl.g(P.fc5.w), 800, wl.g(P.fc5.b));
   wl.push(R, 800, P.nd, W.dt1, noise, P.nd, wl.g(P.fc4.w + 512), 512 + P.nd, wl.g(P.fc4.b));   // fc4 noise half (+ bias)
   wl.push(B, 800, 512, W.drb, W.inp, 512, wl.g(P.fc4.w), 512 + P.nd, nullptr);                  // fc4 image half
-  wl.push(B * 16, 32, 800, W.dh3, W.cols[2], 800, wl.g(P.conv[2].w), 800, wl.g(P.conv[2].b));
-  wl.push(B * 49, 32, 400, W.dh2, W.cols[1], 400, wl.g(P.conv[1].w), 400, wl.g(P.conv[1].b));
-  wl.push(B * 196, 16, 25, W.dh1, W.cols[0], 25, wl.g(P.conv[0].w), 25, wl.g(P.conv[0].b));
+  conv_trunk_wgrads(P.conv, W.cols, W.dh3, W.dh2, W.dh1, B, wl);
   wl.assign(ws, CONV_WGRAD_HINT);
 }
 
@@ -351,8 +334,7 @@ struct AuxConvLayout {
     add(econv[0], 16, 25, 16); add(econv[1], 32, 400, 32); add(econv[2], 32, 800, 32);
     add(efc, 800, 512 + nd, 800); add(mean, zd, 800, zd); add(logvar, zd, 800, zd);
     dec.nd = nd; dec.zd = zd; dec.act = act;
-    add(dec.dfc[0], 300, zd, 300); add(dec.dfc[1], 512, 300, 512);
-    add(dec.dcv[0], 32, 32 * 25, 32); add(dec.dcv[1], 32, 16 * 25, 16); add(dec.dcv[2], 16, 25, 1);
+    dec.decoder(off);
     total = off;
   }
 };
@@ -394,16 +376,8 @@ void carve(const AuxConvLayout& P, const AuxConvPacked&, Bump& ws, int B, int nz
   W.z0 = ws.take(R * P.nd); D.t1 = ws.take(R * 800); W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); D.z = ws.take(R * P.zd);
   W.zero = ws.take(R * (P.nd + P.zd));
   if (mode == 0) return;
-  D.d1 = ws.take(R * 300); D.d2 = ws.take(R * 512); D.g0 = ws.take(R * 512);
-  D.c1 = ws.take(R * 16 * 800); D.u1 = ws.take(R * 64 * 32);
-  D.c2 = ws.take(R * 64 * 400); D.u2 = ws.take(R * 225 * 16);
-  D.c3 = ws.take(R * 225 * 25); D.logit = ws.take(R * 784);
-  D.rec_row = ws.take(R); D.pri_row = ws.take(R);
+  conv_decoder_carve(ws, R, P.zd, mode == 2, D);
   if (mode == 2) return;
-  D.dlogit = ws.take(R * 784); D.dc3 = ws.take(R * 225 * 25); D.dp2 = ws.take(R * 225 * 16);
-  D.dc2 = ws.take(R * 64 * 400); D.dp1 = ws.take(R * 64 * 32); D.dc1 = ws.take(R * 16 * 800);
-  D.dg0 = ws.take(R * 512); D.dd2 = ws.take(R * 512); D.dd1 = ws.take(R * 300);
-  D.dzq = ws.take(R * P.zd); D.dz = ws.take(R * P.zd); D.ones = ws.take(R * 784);
   W.dlv = ws.take(R * P.zd); W.dt1 = ws.take(R * 800); W.dz0 = ws.take(R * P.nd); W.dlv0r = ws.take(R * P.nd);
   W.drb = ws.take((size_t)B * 800); W.dmu0 = ws.take((size_t)B * P.nd); W.dlv0 = ws.take((size_t)B * P.nd); W.dh4a = ws.take((size_t)B * 800);
   W.dinp_a = ws.take((size_t)B * 512); W.dinp_e = ws.take((size_t)B * 512); W.dinp_t = ws.take((size_t)B * 512);
@@ -425,15 +399,11 @@ void auxconv_wgrads(const AuxConvLayout& P, const AuxConvWs& W, int B, int R, Wg
   wl.push(R, P.zd, 800, W.dlv, D.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
   wl.push(R, 800, P.nd, W.dt1, W.z0, P.nd, wl.g(P.efc.w + 512), 512 + P.nd, wl.g(P.efc.b));         // fc z0 half (+ bias)
   wl.push(B, 800, 512, W.drb, W.einp, 512, wl.g(P.efc.w), 512 + P.nd, nullptr);                     // fc image half
-  wl.push(B * 16, 32, 800, W.dh3[1], W.ecols[2], 800, wl.g(P.econv[2].w), 800, wl.g(P.econv[2].b));  // encoder trunk
-  wl.push(B * 49, 32, 400, W.dh2[1], W.ecols[1], 400, wl.g(P.econv[1].w), 400, wl.g(P.econv[1].b));
-  wl.push(B * 196, 16, 25, W.dh1[1], W.ecols[0], 25, wl.g(P.econv[0].w), 25, wl.g(P.econv[0].b));
+  conv_trunk_wgrads(P.econv, W.ecols, W.dh3[1], W.dh2[1], W.dh1[1], B, wl);                           // encoder trunk
   wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
   wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
   wl.push(B, 800, 512, W.dh4a, W.ainp, 512, wl.g(P.afc.w), 512, wl.g(P.afc.b));
-  wl.push(B * 16, 32, 800, W.dh3[0], W.acols[2], 800, wl.g(P.aconv[2].w), 800, wl.g(P.aconv[2].b));  // aux trunk
-  wl.push(B * 49, 32, 400, W.dh2[0], W.acols[1], 400, wl.g(P.aconv[1].w), 400, wl.g(P.aconv[1].b));
-  wl.push(B * 196, 16, 25, W.dh1[0], W.acols[0], 25, wl.g(P.aconv[0].w), 25, wl.g(P.aconv[0].b));
+  conv_trunk_wgrads(P.aconv, W.acols, W.dh3[0], W.dh2[0], W.dh1[0], B, wl);                           // aux trunk
   wl.assign(ws, AUX_WGRAD_HINT);
 }
 

@@ -1,0 +1,206 @@
+// The conv Gaussian-posterior baseline (vae.py --model conv; ardae_model_desc.kind 11: models/vae/conv.py::VAE), joined from pieces the other
+// families own - no kernel of its own:
+//
+//   per image (B rows):  x2 = 2x - 1;  h3 = trunk(x2) (conv 1 -> 16 -> 32 -> 32, k5 s2 p2: csrc/convmodel.hip);  hid = act(F h3 + f)  [B, 800]
+//                        mu, lv, z, kld: the Gaussian head on hid - two MFMA linears and one tail launch (head_fwd below; csrc/vaemodel.hip:
+//                        the draw keying and the KL in double of kinds 8 / 9)
+//                        logit = Decoder(z) (models/vae/conv.py:79-136, the decoder of kinds 2 / 4);  recon = BCE-with-logits over 784 pixels
+//   losses = {mean_b(recon_b + beta kld_b), mean recon, mean kld}    (vae/conv.py:170-201)
+// Backward (c = loss_scale / B): the reconstruction seed, the decoder down to dz, the head's closed form (dmu, dlv), both heads back into
+// hid, fc, the trunk; every weight gradient - the decoder's eight, the two heads, fc, the three convs - in one batch.
+#include "ardae_hip.h"
+#include "common.h"
+#include "convmodel.h"
+#include "convvae.h"
+#include "vaemodel.h"
+
+namespace ardae {
+namespace {
+
+struct ConvVaeLayout {
+  int zd, act;
+  Lin conv[3], fc, mean, logvar;   // encode.conv{1,2,3}, encode.fc [800, 512], encode.reparam.{mean_fn, logvar_fn} [zd, 800]
+  ConvLayout dec;                  // dfc / dcv only
+  size_t total;
+  explicit ConvVaeLayout(const ardae_model_desc& d) : zd(d.z_dim), act(d.act) {
+    size_t off = 0;
+    conv[0] = next_lin(off, 16, 1 * 25); conv[1] = next_lin(off, 32, 16 * 25); conv[2] = next_lin(off, 32, 32 * 25);
+    fc = next_lin(off, 800, 512); mean = next_lin(off, zd, 800); logvar = next_lin(off, zd, 800);
+    dec.zd = zd; dec.act = act;
+    dec.decoder(off);
+    total = off;
+  }
+};
+
+struct ConvVaePacked {
+  size_t conv_f[3], conv_b[3], fc_f, fc_b, mean_f, mean_b, logvar_f, logvar_b;
+  ConvPacked dec;
+  ConvVaePacked(const ConvVaeLayout& P, PackList& pl) {
+    for (int i = 0; i < 3; ++i) pl.pair(P.conv[i], conv_f[i], conv_b[i]);
+    pl.pair(P.fc, fc_f, fc_b); pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
+    dec.decoder_panels(P.dec, pl);
+  }
+  explicit ConvVaePacked(const ConvVaeLayout& P, PackList&& sizing = PackList()) : ConvVaePacked(P, sizing) {}   // offsets only
+};
+
+struct ConvVaeWs {
+  ConvWs C;                        // x2, the trunk's and the decoder's buffers; t1 = hid [B, 800], dt1 = its gradient, z, dzq / dz
+  float *mu, *lv, *eps, *kld, *dmu, *dlv;
+};
+
+// mode 0: the encoder up to hid (encode_stats writes mu, lv to the caller); 1: forward + backward; 2: the decoder's forward on B rows of z
+void carve(const ConvVaeLayout& P, const ConvVaePacked&, Bump& ws, int B, int mode, ConvVaeWs& W) {
+  const size_t b = (size_t)B;
+  ConvWs& C = W.C;
+  if (mode == 2) return conv_decoder_carve(ws, b, P.zd, true, C);
+  conv_trunk_carve(ws, b, C);
+  C.t1 = ws.take(b * 800);
+  if (mode == 0) return;
+  W.mu = ws.take(b * P.zd); W.lv = ws.take(b * P.zd); C.z = ws.take(b * P.zd); W.eps = ws.take(b * P.zd); W.kld = ws.take(b);
+  conv_decoder_carve(ws, b, P.zd, false, C);
+  W.dmu = ws.take(b * P.zd); W.dlv = ws.take(b * P.zd); C.dt1 = ws.take(b * 800);
+  C.dinp = ws.take(b * 512); C.dinp_t = ws.take(b * 512);
+  C.dh3 = ws.take(b * 512); C.dcols3 = ws.take(b * 16 * 800); C.dh2 = ws.take(b * 49 * 32);
+  C.dcols2 = ws.take(b * 49 * 400); C.dh1 = ws.take(b * 196 * 16);
+}
+using ConvVaeEntry = Entry<ConvVaeLayout, ConvVaePacked, ConvVaeWs>;
+
+GaussHead head_of(const ConvVaeLayout& P, const ConvVaePacked& K) { return GaussHead{800, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f}; }
+
+// every weight-gradient problem of the backward: the decoder's eight, the two heads, fc, the three convs
+void convvae_wgrads(const ConvVaeLayout& P, const ConvVaeWs& W, int B, WgradList& wl, Bump& ws) {
+  const ConvWs& C = W.C;
+  conv_decoder_wgrads(P.dec, C, B, wl);
+  wl.push(B, P.zd, 800, W.dmu, C.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
+  wl.push(B, P.zd, 800, W.dlv, C.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
+  wl.push(B, 800, 512, C.dt1, C.inp, 512, wl.g(P.fc.w), 512, wl.g(P.fc.b));
+  conv_trunk_wgrads(P.conv, C.cols, C.dh3, C.dh2, C.dh1, B, wl);
+  wl.assign(ws, CONV_WGRAD_HINT);
+}
+
+size_t convvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+  if (mode != 2 && (nz != 1 || mode == 3)) return 0;         // one draw per image; there is no sampler pair
+  const ConvVaeLayout P(d);
+  Bump ws;
+  ConvVaeWs W;
+  carve(P, ConvVaePacked(P), ws, mode == 2 ? B * nz : B, mode, W);
+  if (mode == 1) {
+    WgradList wl(nullptr);
+    convvae_wgrads(P, W, B, wl, ws);
+  }
+  return ws.off;
+}
+
+// x2 = 2x - 1, the trunk, hid = act(fc(h3))
+int encoder_fwd(const ConvVaeLayout& P, const ConvVaePacked& K, const float* params, const float* packed, const float* x, int B, ConvWs& C,
+                hipStream_t st) {
+  ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, C.x2, st));           // vae/conv.py:64
+  ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, C.x2, C.cols, C.hcv, C.inp, B, P.act, st));
+  return dense_fwd(P.act, B, 800, C.inp, 512, 512, packed + K.fc_f, params + P.fc.b, C.t1, st);
+}
+
+int convvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
+                   hipStream_t st, float*) {
+  ConvVaeEntry entry(d, workspace, wsf, R, 2);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
+  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, z, R, W.C, st));
+  return launch_copy(W.C.logit, (int64_t)R * 784, out0, st);
+}
+
+}  // namespace
+
+int convvae_desc_check(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 11 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
+  ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kind 11, got %d", d->flags);
+  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTConvVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
+  ARDAE_CHECK_ARG(d->h_dim == 800, "model: h_dim must be 800 for kind 11 (the width of encode.fc), got %d", d->h_dim);
+  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 11, got %d", d->n_layers);
+  ARDAE_CHECK_ARG(d->z_dim >= 1, "model: bad dimensions (z_dim %d)", d->z_dim);
+  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
+  return 0;
+}
+
+// The head at h = 800.  gauss_head_kernel (one serial 800-long FMA chain per output, 16 workgroups at 128 rows) loses here: 51.0 us against 19.8 us
+// for the five unfused launches at 128 x 800 -> 2 x 32.  So this family's fused variant keeps the two products on the MFMA
+// linears and fuses what is left - the draw, the reparameterisation and the KL rows - into ONE launch (gauss_head_tail): three launches in place
+// of five, and bit for bit the unfused head's outputs, whose launches and expressions it shares.  Where it is the default: z <= 64 (the tail's LDS).
+bool convvae_head_fused_ok(const ardae_model_desc& d) { return d.z_dim >= 1 && d.z_dim <= 64; }
+
+// variant 0: the library's choice (fused where convvae_head_fused_ok, unless the debug knob says otherwise), 1: fused, 2: unfused
+static int head_fwd(const ardae_model_desc& d, const GaussHead& H, const float* params, const float* packed, const float* hid, const float* eps, int B,
+                    uint64_t seed, uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld,
+                    hipStream_t st) {
+  if (variant == 0) {
+    const char* knob = debug_knob("ARDAE_VAE_HEAD_UNFUSED");
+    variant = (convvae_head_fused_ok(d) && !(knob && knob[0] == '1')) ? 1 : 2;
+  }
+  if (variant == 2) return gauss_head_fwd(H, false, params, packed, hid, eps, B, seed, offset, state, 2, mu, lv, z, eps_out, kld, st);
+  ARDAE_CHECK_ARG(gauss_head_fused_can(H), "vae_head: the fused head takes 1 <= z_dim <= 64 (got %d)", H.zd);
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.mean_f, params + H.mean.b, mu, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.logvar_f, params + H.logvar.b, lv, st));
+  return gauss_head_tail(mu, lv, eps, B, H.zd, seed, offset, state, z, eps_out, kld, st);
+}
+
+int convvae_head(const ardae_model_desc& d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
+                 uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld, hipStream_t st) {
+  const ConvVaeLayout P(d);
+  return head_fwd(d, head_of(P, ConvVaePacked(P)), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z, eps_out, kld, st);
+}
+
+int convvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
+                         float* mu_out, float* lv_out, hipStream_t st) {
+  ConvVaeEntry entry(d, workspace, wsf, B, 0);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
+  ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, W.C, st));
+  // the two heads write the caller's buffers themselves: no draw, no sample
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, W.C.t1, 800, 800, packed + K.mean_f, params + P.mean.b, mu_out, st));
+  return dense_fwd(ACT_NONE, B, P.zd, W.C.t1, 800, 800, packed + K.logvar_f, params + P.logvar.b, lv_out, st);
+}
+
+int convvae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, DevFloat beta,
+                    uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t wsf, float* z_out, float* eps_out, float* losses,
+                    hipStream_t st) {
+  ConvVaeEntry entry(d, workspace, wsf, B, 1);
+  auto& [P, K, ws, W] = entry;
+  ConvWs& C = W.C;
+  ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
+  ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, C, st));
+  ARDAE_TRY(head_fwd(d, head_of(P, K), params, packed, C.t1, eps, B, seed, offset, state, 0, W.mu, W.lv, C.z, W.eps, W.kld, st));
+  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, C.z, B, C, st));
+  ARDAE_TRY(launch_vae_loss(0, C.logit, nullptr, x, C.z, B, 1, 784, P.zd, 0.f, 0, 0.f, nullptr, C.rec_row, C.pri_row, nullptr, nullptr, nullptr, st));
+  ARDAE_TRY(launch_vae_loss_finalize(C.rec_row, W.kld, B, beta, losses, st));
+  ARDAE_TRY(launch_copy(C.z, (int64_t)B * P.zd, z_out, st));
+  if (eps_out) ARDAE_TRY(launch_copy(W.eps, (int64_t)B * P.zd, eps_out, st));
+  return 0;
+}
+
+int convvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
+                     float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
+  (void)params;
+  ConvVaeEntry entry(d, workspace, wsf, B, 1);
+  auto& [P, K, ws, W] = entry;
+  ConvWs& C = W.C;
+  const float c = loss_scale / (float)B;
+  // reconstruction gradients at the logits (the N(0, I) energy this kernel also knows is switched off: beta 0, no seed)
+  ARDAE_TRY(launch_vae_loss(0, C.logit, nullptr, x, C.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, C.rec_row, C.pri_row, C.dlogit, nullptr, C.dzq, st));
+  ARDAE_TRY(conv_decoder_bwd(P.dec, K.dec, packed, C, B, st));
+  ARDAE_TRY(gauss_head_seed(C.dz, C.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
+  ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, C.t1, C.dt1, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, C.dt1, 800, 800, packed + K.fc_b, nullptr, C.dinp, st));   // fc backward-data; the trunk applies conv3's act'
+  ARDAE_TRY(trunk_bwd(K.conv_b, packed, C.dinp, C.dinp_t, C.hcv, C.dh3, C.dcols3, C.dh2, C.dcols2, C.dh1, B, P.act, st));
+  WgradList wl(grads, grads_beta);
+  convvae_wgrads(P, W, B, wl, ws);
+  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+  return wl.launch(st);
+}
+
+// (host pass only, as in csrc/auxmodel.hip)
+#ifndef __HIP_DEVICE_COMPILE__
+const Family CONVVAE_FAMILY = {family_param_floats<ConvVaeLayout, ConvVaePacked>, family_packed_floats<ConvVaeLayout, ConvVaePacked>,
+                               convvae_workspace_floats, family_pack<ConvVaeLayout, ConvVaePacked>, vae_no_encode, convvae_decode, vae_no_forward,
+                               vae_no_backward};
+#endif
+
+}  // namespace ardae

@@ -23,6 +23,7 @@
 #include "elementwise.h"
 #include "mlp.h"
 #include "philox.h"
+#include "convvae.h"
 #include "vaemodel.h"
 
 namespace ardae {
@@ -200,6 +201,43 @@ __global__ __launch_bounds__(GH_THREADS) void gauss_head_kernel(const float* __r
   }
 }
 
+// The head's tail as ONE launch, for a family whose two products run on the MFMA linears (kind 11, csrc/convvae.hip): from mu, lv [B, zd] the
+// draw (keyed like ardae_philox_normal_at) or the injected eps, z and the row's KL - the expressions and the order of the three unfused launches
+// (ardae_philox_normal_at, reparam_fwd_kernel, gauss_kld_rows_kernel), so its outputs equal theirs bit for bit.  Tiles and LDS as gauss_head_kernel.
+__global__ __launch_bounds__(GH_THREADS) void gauss_head_tail_kernel(const float* __restrict__ mu, const float* __restrict__ lv, int B, int zd,
+                                                                     const float* __restrict__ eps_in, uint64_t seed, uint64_t offset,
+                                                                     const StepState* __restrict__ state, float* __restrict__ z_out,
+                                                                     float* __restrict__ eps_out, float* __restrict__ kld_out) {
+  __shared__ double kt[GH_ROWS][GH_ZMAX + 1];
+  const int t = threadIdx.x;
+  const int r0 = blockIdx.x * GH_ROWS;
+  const int nout = GH_ROWS * zd;
+  if (state) offset += state->rng_offset;
+#pragma unroll
+  for (int i = 0; i < GH_PER; ++i) {
+    const int o = t + i * GH_THREADS;
+    if (o < nout) {
+      const int r = o / zd, c = o - r * zd, gr = r0 + r;
+      double term = 0.0;
+      if (gr < B) {
+        const uint64_t g = (uint64_t)gr * zd + c;
+        const float m = mu[g], l = lv[g];
+        const float e = eps_in ? eps_in[g] : philox_normal_element(seed, offset, g);
+        z_out[g] = m + __expf(0.5f * l) * e;
+        if (eps_out) eps_out[g] = e;
+        term = kld_term(m, l);
+      }
+      kt[r][c] = term;
+    }
+  }
+  __syncthreads();
+  if (t < GH_ROWS && r0 + t < B) {
+    double s = 0.0;
+    for (int c = 0; c < zd; ++c) s += kt[t][c];      // ascending c
+    kld_out[r0 + t] = (float)(-0.5 * s);
+  }
+}
+
 // the unfused head's last launch: kld[r] from (mu, lv) [B, zd], one thread per row, the same terms in the same order
 __global__ void gauss_kld_rows_kernel(const float* __restrict__ mu, const float* __restrict__ lv, int B, int zd, float* __restrict__ kld) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -252,46 +290,85 @@ __global__ __launch_bounds__(IQ_THREADS) void vae_iwae_draw_kernel(const float* 
   }
 }
 
-// ------------------------------------------------------------------------------------------------ the head, fused or not
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ the head, fused or not (vaemodel.h)
 // what the fused kernel can compute at all (ardae_vae_head's variant 1) ...
-bool head_fused_can(const ardae_model_desc& d) { return d.z_dim >= 1 && d.z_dim <= GH_ZMAX && d.h_dim >= 1; }
-// ... and where it is the default: where the rows of both head matrices start on 16 bytes (h a multiple of 4 and both parameter offsets
+bool gauss_head_fused_can(const GaussHead& H) { return H.zd >= 1 && H.zd <= GH_ZMAX && H.h >= 1; }
+// ... and where it may be the default: where the rows of both head matrices start on 16 bytes (h a multiple of 4 and both parameter offsets
 // multiples of 4 floats - a z that is a multiple of 4, given such an h).  Elsewhere the kernel reads float by float and a narrow head
 // leaves most of a workgroup idle: at the toy recipe's z = 2 it only ties with the unfused launches, which run there.
-bool head_fused_ok(const ardae_model_desc& d) {
-  if (!head_fused_can(d) || (d.h_dim & 3)) return false;
-  const VaeLayout P(d);
-  return (P.mean.w & 3) == 0 && (P.logvar.w & 3) == 0;
-}
+bool gauss_head_fused_ok(const GaussHead& H) { return gauss_head_fused_can(H) && (H.h & 3) == 0 && (H.mean.w & 3) == 0 && (H.logvar.w & 3) == 0; }
 
-// variant 0: the library's choice (fused where it is taken, unless the debug knob says otherwise), 1: fused, 2: unfused
-int head_fwd(const ardae_model_desc& d, const VaeLayout& P, const VaePacked& K, const float* params, const float* packed, const float* hid,
-             const float* eps, int B, uint64_t seed, uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out,
-             float* kld, hipStream_t st) {
+// variant 0: the library's choice (fused where `fused_default`, unless the debug knob says otherwise), 1: fused, 2: unfused
+int gauss_head_fwd(const GaussHead& H, bool fused_default, const float* params, const float* packed, const float* hid, const float* eps, int B,
+                   uint64_t seed, uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld,
+                   hipStream_t st) {
   if (variant == 0) {
     const char* knob = debug_knob("ARDAE_VAE_HEAD_UNFUSED");
-    variant = (head_fused_ok(d) && !(knob && knob[0] == '1')) ? 1 : 2;
+    variant = (fused_default && !(knob && knob[0] == '1')) ? 1 : 2;
   }
   if (variant == 1) {
-    ARDAE_CHECK_ARG(head_fused_can(d), "vae_head: the fused head takes 1 <= z_dim <= %d (got %d)", GH_ZMAX, d.z_dim);
-    hipLaunchKernelGGL(gauss_head_kernel, dim3((unsigned)ceil_div(B, GH_ROWS)), dim3(GH_THREADS), 0, st, hid, B, P.h, P.zd, params + P.mean.w,
-                       params + P.mean.b, params + P.logvar.w, params + P.logvar.b, eps, seed, offset, (const StepState*)state, mu, lv, z, eps_out, kld);
+    ARDAE_CHECK_ARG(gauss_head_fused_can(H), "vae_head: the fused head takes 1 <= z_dim <= %d (got %d)", GH_ZMAX, H.zd);
+    hipLaunchKernelGGL(gauss_head_kernel, dim3((unsigned)ceil_div(B, GH_ROWS)), dim3(GH_THREADS), 0, st, hid, B, H.h, H.zd, params + H.mean.w,
+                       params + H.mean.b, params + H.logvar.w, params + H.logvar.b, eps, seed, offset, (const StepState*)state, mu, lv, z, eps_out, kld);
     ARDAE_LAUNCH_CHECK();
     return 0;
   }
   ARDAE_CHECK_ARG(eps || eps_out, "vae_head: the unfused head draws into eps_out (null pointer)");
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, hid, P.h, P.h, packed + K.mean_f, params + P.mean.b, mu, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, hid, P.h, P.h, packed + K.logvar_f, params + P.logvar.b, lv, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.mean_f, params + H.mean.b, mu, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.logvar_f, params + H.logvar.b, lv, st));
   if (!eps) {
-    ARDAE_TRY(launch_philox_normal_at(eps_out, (int64_t)B * P.zd, seed, offset, state, 0, st));
+    ARDAE_TRY(launch_philox_normal_at(eps_out, (int64_t)B * H.zd, seed, offset, state, 0, st));
     eps = eps_out;
   } else if (eps_out && eps_out != eps) {
-    ARDAE_TRY(launch_copy(eps, (int64_t)B * P.zd, eps_out, st));
+    ARDAE_TRY(launch_copy(eps, (int64_t)B * H.zd, eps_out, st));
   }
-  ARDAE_TRY(launch_reparam_fwd(mu, lv, eps, P.zd, B, P.zd, 1, z, st));
-  hipLaunchKernelGGL(gauss_kld_rows_kernel, dim3(nblk(B)), dim3(256), 0, st, mu, lv, B, P.zd, kld);
+  ARDAE_TRY(launch_reparam_fwd(mu, lv, eps, H.zd, B, H.zd, 1, z, st));
+  hipLaunchKernelGGL(gauss_kld_rows_kernel, dim3(nblk(B)), dim3(256), 0, st, mu, lv, B, H.zd, kld);
   ARDAE_LAUNCH_CHECK();
   return 0;
+}
+
+int gauss_head_tail(const float* mu, const float* lv, const float* eps, int B, int zd, uint64_t seed, uint64_t offset, const void* state, float* z,
+                    float* eps_out, float* kld, hipStream_t st) {
+  ARDAE_CHECK_ARG(zd >= 1 && zd <= GH_ZMAX, "vae_head: the fused head takes 1 <= z_dim <= %d (got %d)", GH_ZMAX, zd);
+  hipLaunchKernelGGL(gauss_head_tail_kernel, dim3((unsigned)ceil_div(B, GH_ROWS)), dim3(GH_THREADS), 0, st, mu, lv, B, zd, eps, seed, offset,
+                     (const StepState*)state, z, eps_out, kld);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int gauss_head_seed(const float* dz, const float* z, const float* mu, const float* lv, int64_t n, float c, DevFloat beta, float* dmu, float* dlv,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(gauss_head_seed_kernel, dim3(nblk(n)), dim3(256), 0, st, dz, z, mu, lv, n, c, beta.v, beta.p, dmu, dlv);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+// what ardae_model_encode / ardae_model_vae_* answer for the Gaussian-posterior kinds (Family members)
+int vae_no_encode(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, float*, size_t, float*, float*, hipStream_t,
+                  const float*) {
+  set_last_error("model_encode: kinds 8 / 9 / 11 have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
+  return -1;
+}
+int vae_no_forward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float*, size_t, float*, float*,
+                   hipStream_t) {
+  set_last_error("model_vae_forward: kinds 8 / 9 / 11 are driven by ardae_vae_forward");
+  return -1;
+}
+int vae_no_backward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float, const float*, float*,
+                    size_t, float*, float, hipStream_t) {
+  set_last_error("model_vae_backward: kinds 8 / 9 / 11 are driven by ardae_vae_backward");
+  return -1;
+}
+
+namespace {
+
+GaussHead head_of(const VaeLayout& P, const VaePacked& K) { return GaussHead{P.h, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f}; }
+bool head_fused_ok(const ardae_model_desc& d) {
+  const VaeLayout P(d);
+  return gauss_head_fused_ok(head_of(P, VaePacked(P)));
 }
 
 // xs (kind 8: 2x - 1) and the encoder stack; -> the stack's input
@@ -307,31 +384,20 @@ size_t vae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) 
   if (nz != 1 || mode == 3) return 0;         // one draw per image; there is no sampler pair
   return workspace_floats(P, B, mode);
 }
-int vae_no_encode(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, float*, size_t, float*, float*, hipStream_t,
-                  const float*) {
-  set_last_error("model_encode: kinds 8 / 9 have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
-  return -1;
-}
-int vae_no_forward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float*, size_t, float*, float*,
-                   hipStream_t) {
-  set_last_error("model_vae_forward: kinds 8 / 9 are driven by ardae_vae_forward");
-  return -1;
-}
-int vae_no_backward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float, const float*, float*,
-                    size_t, float*, float, hipStream_t) {
-  set_last_error("model_vae_backward: kinds 8 / 9 are driven by ardae_vae_backward");
-  return -1;
+// the kinds the ardae_vae_* entry points take, and their descriptor rules
+int vae_kind_check(const ardae_model_desc* d, const char* who) {
+  ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
+  ARDAE_CHECK_ARG(d->kind == 8 || d->kind == 9 || d->kind == 11, "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), got %d", who, d->kind);
+  return d->kind == 11 ? convvae_desc_check(d) : vae_desc_check(d);
 }
 
 // what every ardae_vae_* entry point checks before anything is launched
 int vae_common(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf, int mode,
                const char* who) {
-  ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
-  ARDAE_CHECK_ARG(d->kind == 8 || d->kind == 9, "%s: kind must be 8 (MNISTVAE) or 9 (ToyVAE), got %d", who, d->kind);
-  ARDAE_TRY(vae_desc_check(d));
+  ARDAE_TRY(vae_kind_check(d, who));
   ARDAE_CHECK_ARG(params && packed && x && workspace, "%s: null pointer argument", who);
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "%s: bad batch (B=%d)", who, B);
-  const size_t need = vae_workspace_floats(*d, B, 1, mode);
+  const size_t need = d->kind == 11 ? CONVVAE_FAMILY.workspace_floats(*d, B, 1, mode) : vae_workspace_floats(*d, B, 1, mode);
   ARDAE_CHECK_ARG(wsf >= need, "%s: workspace too small (%zu < %zu floats)", who, wsf, need);
   return 0;
 }
@@ -343,11 +409,13 @@ int vae_forward_entry(const ardae_model_desc* d, const float* params, const floa
   ARDAE_CHECK_ARG(z_out && losses, "vae_forward: null pointer argument (z_out, losses)");
   ARDAE_CHECK_ARG(std::isfinite(loss_scale), "vae_forward: loss_scale must be finite");
   hipStream_t st = (hipStream_t)stream;
+  if (d->kind == 11) return convvae_forward(*d, params, packed, x, eps, B, beta, seed, offset, state, workspace, wsf, z_out, eps_out, losses, st);
   VaeEntry entry(*d, workspace, wsf, B, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
   ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, W, st));
-  ARDAE_TRY(head_fwd(*d, P, K, params, packed, W.e[P.nl], eps, B, seed, offset, state, 0, W.mu, W.lv, W.z, W.eps, W.kld, st));
+  const GaussHead H = head_of(P, K);
+  ARDAE_TRY(gauss_head_fwd(H, gauss_head_fused_ok(H), params, packed, W.e[P.nl], eps, B, seed, offset, state, 0, W.mu, W.lv, W.z, W.eps, W.kld, st));
   ARDAE_TRY(K.dec.fwd(params, packed, P.act, B, W.z, W.D.hid.data(), W.D.o, st));
   ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, B, 1, P.D, P.zd, 0.f, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr,
                             nullptr, st));
@@ -363,6 +431,7 @@ int vae_backward_entry(const ardae_model_desc* d, const float* params, const flo
   ARDAE_CHECK_ARG(grads, "vae_backward: null pointer argument (grads)");
   ARDAE_CHECK_ARG(std::isfinite(loss_scale) && std::isfinite(grads_beta), "vae_backward: loss_scale and grads_beta must be finite");
   hipStream_t st = (hipStream_t)stream;
+  if (d->kind == 11) return convvae_backward(*d, params, packed, x, B, beta, loss_scale, workspace, wsf, grads, grads_beta, st);
   VaeEntry entry(*d, workspace, wsf, B, 1);
   auto& [P, K, ws, W] = entry;
   const float c = loss_scale / (float)B;
@@ -371,8 +440,7 @@ int vae_backward_entry(const ardae_model_desc* d, const float* params, const flo
   ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, B, 1, P.D, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.D.dox[0], W.D.dox[1],
                             W.D.dzq, st));
   ARDAE_TRY(K.dec.bwd(packed, P.act, B, W.D, st));
-  hipLaunchKernelGGL(gauss_head_seed_kernel, dim3(nblk(n)), dim3(256), 0, st, W.D.dz, W.z, W.mu, W.lv, n, c, beta.v, beta.p, W.dmu, W.dlv);
-  ARDAE_LAUNCH_CHECK();
+  ARDAE_TRY(gauss_head_seed(W.D.dz, W.z, W.mu, W.lv, n, c, beta, W.dmu, W.dlv, st));
   ARDAE_TRY(dense_bwd2(P.act, B, P.h, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.e[P.nl], W.de[P.nl], st));
   ARDAE_TRY(K.enc.bwd(packed, P.act, B, W.e.data(), W.de.data(), st));
   WgradList wl(grads, grads_beta);
@@ -404,7 +472,8 @@ using namespace ardae;
 extern "C" {
 
 int ardae_vae_head_fused_ok(const ardae_model_desc* d) {
-  return d && (d->kind == 8 || d->kind == 9) && vae_desc_check(d) == 0 && head_fused_ok(*d) ? 1 : 0;
+  if (!d || vae_kind_check(d, "vae_head_fused_ok") != 0) return 0;
+  return (d->kind == 11 ? convvae_head_fused_ok(*d) : head_fused_ok(*d)) ? 1 : 0;
 }
 
 int ardae_vae_kld_rows(const float* mu, const float* lv, int B, int z, float* kld, void* stream) {
@@ -417,15 +486,15 @@ int ardae_vae_kld_rows(const float* mu, const float* lv, int B, int z, float* kl
 
 int ardae_vae_head(const ardae_model_desc* d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
                    uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z_out, float* eps_out, float* kld, void* stream) {
-  ARDAE_CHECK_ARG(d != nullptr, "vae_head: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind == 8 || d->kind == 9, "vae_head: kind must be 8 (MNISTVAE) or 9 (ToyVAE), got %d", d->kind);
-  ARDAE_TRY(vae_desc_check(d));
+  ARDAE_TRY(vae_kind_check(d, "vae_head"));
   ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "vae_head: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
   ARDAE_CHECK_ARG(params && packed && hid && mu && lv && z_out && kld, "vae_head: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "vae_head: bad batch (B=%d)", B);
+  if (d->kind == 11) return convvae_head(*d, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
   const VaeLayout P(*d);
-  const VaePacked K(P);
-  return head_fwd(*d, P, K, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
+  const GaussHead H = head_of(P, VaePacked(P));
+  return gauss_head_fwd(H, gauss_head_fused_ok(H), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld,
+                        (hipStream_t)stream);
 }
 
 int ardae_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* eps, int B, float beta,
@@ -457,6 +526,7 @@ int ardae_vae_encode_stats(const ardae_model_desc* d, const float* params, const
   ARDAE_TRY(vae_common(d, params, packed, x, B, workspace, workspace_floats_, 0, "vae_encode_stats"));
   ARDAE_CHECK_ARG(mu_out && lv_out, "vae_encode_stats: null pointer argument (mu_out, lv_out)");
   hipStream_t st = (hipStream_t)stream;
+  if (d->kind == 11) return convvae_encode_stats(*d, params, packed, x, B, workspace, workspace_floats_, mu_out, lv_out, st);
   VaeEntry entry(*d, workspace, workspace_floats_, B, 0);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");

@@ -119,6 +119,21 @@ def vae_spec(kind, input_dim, h_dim, z_dim, n_layers):
                 ("decode.reparam.logvar_fn.weight", (input_dim, h_dim)), ("decode.reparam.logvar_fn.bias", (input_dim,))]
 
 
+def conv_vae_spec(z_dim):
+    """The conv Gaussian-posterior baseline of vae.py (models/vae/conv.py:29-168, `--model conv`; 28 x 28 x 1, fixed architecture): the conv
+    trunk of the 'conv' implicit model, `encode.fc` 512 -> 800, a NormalDistributionLinear head and that model's decoder.  ardae_model_desc.kind 11."""
+    s = [("encode.conv1.weight", (16, 1, 5, 5)), ("encode.conv1.bias", (16,)),
+         ("encode.conv2.weight", (32, 16, 5, 5)), ("encode.conv2.bias", (32,)),
+         ("encode.conv3.weight", (32, 32, 5, 5)), ("encode.conv3.bias", (32,)),
+         ("encode.fc.weight", (800, 512)), ("encode.fc.bias", (800,)),
+         ("encode.reparam.mean_fn.weight", (z_dim, 800)), ("encode.reparam.mean_fn.bias", (z_dim,)),
+         ("encode.reparam.logvar_fn.weight", (z_dim, 800)), ("encode.reparam.logvar_fn.bias", (z_dim,))]
+    s += _mlp("decode.fc.", z_dim, 300, 512, 1)
+    return s + [("decode.deconv1.weight", (32, 32, 5, 5)), ("decode.deconv1.bias", (32,)),
+                ("decode.deconv2.weight", (32, 16, 5, 5)), ("decode.deconv2.bias", (16,)),
+                ("decode.reparam.logit_fn.weight", (16, 1, 5, 5)), ("decode.reparam.logit_fn.bias", (1,))]
+
+
 def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):
     s = _mlp("ctx_encode.", context_dim, h_dim, h_dim, n_layers - 1)
     s += _mlp("inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)

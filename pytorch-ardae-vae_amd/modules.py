@@ -5,6 +5,7 @@
     net.MLPGradARDAE / net.MLPResARDAE   <- models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167
     net.MLPGradDAE / net.MLPResDAE       <- models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90
     net.MNISTVAE / net.ToyVAE            <- models/vae/mnist.py:99-220, models/vae/toy.py:99-213 (the Gaussian-posterior baselines of vae.py)
+    net.MNISTConvVAE                     <- models/vae/conv.py:138-260 (`vae.py --model conv`)
 
 Same constructor kwargs, same `state_dict()` keys and `[out, in]` layouts (reference checkpoints load), same method
 names and argument meaning, same exception types.  Parameters are `nn.Parameter` views into ONE flat fp32 buffer
@@ -148,7 +149,7 @@ def _f32c(t):
 
 
 KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7,      # ardae_model_desc.kind
-            "vae_mnist": 8, "vae_toy": 9}                                                                    # (vae.py's baselines: GaussianVAE below)
+            "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11}                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
 AUX_KINDS = ("auxmnist", "auxconv", "auxresconv", "auxtoy")                                                 # hierarchical samplers
 GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
 
@@ -913,12 +914,13 @@ class _GaussEncodeBox(_Box):
 
 
 class GaussianVAE(FlatParamModule):
-    """What MNISTVAE and ToyVAE share: ardae_model_desc kinds 8 / 9, an encoder MLP with a Gaussian head and its analytic KL, the decoders
-    of the implicit models.  There is no CPU path."""
-    _kind = None                 # "vae_mnist" | "vae_toy"
+    """What MNISTVAE, ToyVAE and MNISTConvVAE share: ardae_model_desc kinds 8 / 9 / 11, an encoder with a Gaussian head and its analytic KL, the
+    decoders of the implicit models.  A family is its `_kind` and its `_param_spec()`.  There is no CPU path."""
+    _kind = None                 # "vae_mnist" | "vae_toy" | "vae_conv"
     _packed_floats_fn, _pack_fn = "ardae_model_packed_floats", "ardae_model_pack"
     return_samples = True        # forward() also returns the decoder sample / mean (one extra decoder pass); False: (None, None)
     noise_dim = 0
+    _eval_groups = None          # GaussianIwaeEvaluator: (images per encoder / ELBO-decoder call, images per importance-sample decoder call); None: a chunk at once
 
     def _build(self, energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers):
         if energy_func is not normal_energy_func:
@@ -934,10 +936,13 @@ class GaussianVAE(FlatParamModule):
         self.nonlinearity, self.num_hidden_layers = nonlinearity, int(num_hidden_layers)
         self._desc = L.ModelDesc(KIND_IDS[self._kind], self.input_dim, 0, self.h_dim, self.z_dim, self.num_hidden_layers, L.ACT[nonlinearity], 0)
         self._abi = (self._desc,)
-        self._build_params(layout.vae_spec(self._kind[len("vae_"):], self.input_dim, self.h_dim, self.z_dim, self.num_hidden_layers),
-                           {"encode": _GaussEncodeBox})
+        self._build_params(self._param_spec(), {"encode": _GaussEncodeBox})
         object.__setattr__(self.encode, "_owner_ref", weakref.ref(self))
         self.reset_parameters()
+
+    def _param_spec(self):
+        """Names and shapes in named_parameters() order (the two MLP families; MNISTConvVAE has its own)."""
+        return layout.vae_spec(self._kind[len("vae_"):], self.input_dim, self.h_dim, self.z_dim, self.num_hidden_layers)
 
     _x = ImplicitPosteriorVAE._x
     decode_params = ImplicitPosteriorVAE.decode_params
@@ -1016,6 +1021,41 @@ class MNISTVAE(GaussianVAE):
                 for t in p.values():
                     nn.init.xavier_uniform_(t) if t.dim() == 2 else t.zero_()
             if self.do_m5bias:                              # vae/mnist.py:128-129
+                p["decode.reparam.logit_fn.bias"].fill_(-5.0)
+
+
+class MNISTConvVAE(GaussianVAE):
+    """models/vae/conv.py::VAE (`vae.py --model conv`, the "# conv" baseline of run_vae_dbmnist.sh): ConvIPVAE's trunk, `encode.fc` 512 -> 800 and a
+    Gaussian head; that model's decoder.  The reference's decoder only produces 28x28 outputs, so input_height=28 / input_channels=1 are required.
+    forward() takes x as [B, 784] or [B, 1, 28, 28] and returns the decoder sample / mean as [B, 784]."""
+    _kind = "vae_conv"
+    # Every (transposed) convolution here is a linear on rows = images x positions, and the library picks a linear's kernel by its row count;
+    # the kernels add in different orders, so a row's last bits depend on the images per call - in the trunk and `fc` as in the decoder.  The
+    # evaluator therefore calls the encoder and the ELBO pass's decoder on 64 images and the importance samples' decoder on 16 (at k = 256:
+    # 4096 decoded rows, 0.2 G floats of workspace), and cuts its chunks at multiples of 64: what it reports does not depend on the budget.
+    _eval_groups = (64, 16)
+
+    def __init__(self, energy_func=normal_energy_func, input_height=28, input_channels=1, z_dim=32, nonlinearity="softplus", do_xavier=False,
+                 do_m5bias=False):
+        if input_height != 28 or input_channels != 1:
+            raise NotImplementedError("MNISTConvVAE: the reference decoder (models/vae/conv.py:79-136) is hard-wired to 28x28x1")
+        super().__init__()
+        self.input_height, self.input_channels, self.do_xavier, self.do_m5bias = input_height, input_channels, do_xavier, do_m5bias
+        self._build(energy_func, input_height * input_height * input_channels, 800, z_dim, nonlinearity, 1)
+
+    def _param_spec(self):
+        return layout.conv_vae_spec(self.z_dim)
+
+    def reset_parameters(self):
+        self._default_init()
+        with torch.no_grad():
+            p = dict(self.named_parameters())
+            if self.do_xavier:                              # self.apply(weight_init): xavier-uniform on Conv2d / Linear, zero biases; ConvTranspose2d
+                for name, t in p.items():                   # keeps torch's default init (vae/conv.py:17-22,164-166)
+                    if "deconv" in name or "logit_fn" in name:
+                        continue
+                    nn.init.xavier_uniform_(t) if t.dim() >= 2 else t.zero_()
+            if self.do_m5bias:                              # vae/conv.py:167-168
                 p["decode.reparam.logit_fn.bias"].fill_(-5.0)
 
 

@@ -1,7 +1,7 @@
 """The Gaussian-posterior baselines of the reference's second trainer, vae.py, on the device: one iteration of its loop (vae.py:396-417)
 as one captured unit, and its evaluate_iws (vae.py:342-377) in large chunks.
 
-    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE
+    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE
     eng = net.VaeEngine(model, net.VaeConfig(lr=1e-3, beta_init=1e-4, beta_annealing=50000), batch_size=128)
     for x in loader: eng.step(x)
     elbo, logprob = eng.evaluate_iws(x_valid, sample_size=512)
@@ -70,23 +70,50 @@ class GaussianIwaeEvaluator:
     ardae_vae_iwae_draw, decoder, row losses, log-mean-exp.  Everything lands in [N] buffers, one row per image, which are reduced once
     at the end in an order that depends on N alone; there is no host read inside the walk.  Own draws take two Philox offsets per call
     from the host stream (the forward's, the importance samples'); a chunk reads its slice through `first_element`, so ELBO and bound do
-    not depend on the chunk length, to the bit.  Injected draws: fwd_eps [N, z], eps [N, k, z].  There is no covariance fit and no
-    Cholesky on this path (iwae.IwaeEvaluator is the implicit models')."""
+    not depend on the chunk length, to the bit - given that a row's bits do not depend on the rows per call, which holds for the MLP families'
+    layers.  Where it does not (MNISTConvVAE: the library picks the kernel of every conv-as-linear by the row count), the model names fixed
+    groups, `_eval_groups = (G, g)`: the encoder and the ELBO pass's decoder run on G images per call, the importance samples' decoder on g
+    images per call, and chunks are whole multiples of G - so every call sees the same rows under any budget.  Injected draws: fwd_eps
+    [N, z], eps [N, k, z].  There is no covariance fit and no Cholesky on this path (iwae.IwaeEvaluator is the implicit models')."""
 
     def __init__(self, model, sample_size, max_workspace_floats=1 << 28):
         if not isinstance(model, GaussianVAE):
-            raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE (the implicit models: net.IwaeEvaluator)")
+            raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE (the implicit models: net.IwaeEvaluator)")
         self.model, self.k, self.budget = model, int(sample_size), int(max_workspace_floats)
         if self.k < 1:
             raise ValueError(f"sample_size must be positive (got {sample_size})")
         if model.z_dim > MAX_Z:
             raise NotImplementedError(f"GaussianIwaeEvaluator: z_dim {model.z_dim} > {MAX_Z}: ardae_vae_iwae_draw takes latent widths up to {MAX_Z}")
         self.gaussian = model._kind == "vae_toy"
+        # images per encoder / ELBO-decoder call and per importance-sample decoder call (None: a chunk at once)
+        self.image_group, self.group = model._eval_groups or (None, None)
         self._bufs = None
 
     def _workspace_floats(self, c):
         d = self.model._desc
-        return max(L.query("ardae_model_workspace_floats", d, c, 1, 0), L.query("ardae_model_workspace_floats", d, c * self.k, 1, 2))
+        G, g = min(c, self.image_group or c), min(c, self.group or c)
+        return max(L.query("ardae_model_workspace_floats", d, G, 1, 0), L.query("ardae_model_workspace_floats", d, G, 1, 2),
+                   L.query("ardae_model_workspace_floats", d, g * self.k, 1, 2))
+
+    def _encode_stats(self, b, xc, c):
+        """b["mu"], b["lv"] [c, z_dim] of the chunk xc, `self.image_group` images per encoder call"""
+        m, zd = self.model, self.model.z_dim
+        G = self.image_group or c
+        for j in range(0, c, G):
+            n = min(G, c - j)
+            L.call("ardae_vae_encode_stats", m._desc, m._flat, m._packed_weights(), xc[j:j + n], n, b["ws"], b["ws"].numel(), b["mu"][j * zd:(j + n) * zd],
+                   b["lv"][j * zd:(j + n) * zd])
+
+    def _decode_rows(self, b, xc, z, c, rpi, rec, group):
+        """rec [c * rpi]: the reconstruction rows of z [c * rpi, z_dim] (rpi rows per image of xc [c, input_dim]), `group` images per decoder call"""
+        m, zd = self.model, self.model.z_dim
+        d, flat, packed, ws = m._desc, m._flat, m._packed_weights(), b["ws"]
+        g = group or c
+        for j in range(0, c, g):
+            n = min(g, c - j)
+            zj = z[j * rpi * zd:(j + n) * rpi * zd]
+            L.call("ardae_model_decode", d, flat, packed, zj, n * rpi, ws, ws.numel(), b["out0"], b["out1"])
+            L.call("ardae_model_loss_rows", d, b["out0"], b["out1"], xc[j:j + n], zj, n * rpi, rpi, rec[j * rpi:(j + n) * rpi], b["pri"][j * rpi:(j + n) * rpi])
 
     def floats_per_chunk(self, c):
         m, k = self.model, self.k
@@ -94,7 +121,15 @@ class GaussianIwaeEvaluator:
         return self._workspace_floats(c) + c * own
 
     def plan(self, N):
-        return plan_chunks(N, self.k, self.floats_per_chunk, self.budget)
+        chunks = plan_chunks(N, self.k, self.floats_per_chunk, self.budget)
+        G = self.image_group
+        if G is None or len(chunks) == 1:
+            return chunks
+        C = (chunks[0][1] - chunks[0][0]) // G * G      # whole groups: every call starts at a multiple of its group in any plan
+        if C == 0:
+            raise ValueError(f"GaussianIwaeEvaluator: the budget of {self.budget} floats is below one group of {G} images "
+                             f"({self.floats_per_chunk(G)} floats)")
+        return [(s, min(s + C, N)) for s in range(0, N, C)]
 
     def _buffers(self, c, device):
         if self._bufs is None or self._bufs["c"] < c or self._bufs["ws"].device != device:
@@ -128,7 +163,7 @@ class GaussianIwaeEvaluator:
             for i0, i1 in chunks:
                 c = i1 - i0
                 xc = x[i0:i1]
-                L.call("ardae_vae_encode_stats", d, flat, packed, xc, c, ws, ws.numel(), b["mu"], b["lv"])
+                self._encode_stats(b, xc, c)
                 # the forward at beta = 1 (vae.py:360), row by row
                 if fwd_eps is None:
                     L.call("ardae_philox_normal_at", b["feps"], c * zd, seed, fwd_offset, None, i0 * zd)
@@ -137,13 +172,11 @@ class GaussianIwaeEvaluator:
                     fe = fwd_eps.view(N, zd)[i0:i1]
                 L.call("ardae_vae_kld_rows", b["mu"], b["lv"], c, zd, kld[i0:i1])
                 L.call("ardae_gaussian_sample", b["mu"], b["lv"], fe, c * zd, b["fz"])
-                L.call("ardae_model_decode", d, flat, packed, b["fz"], c, ws, ws.numel(), b["out0"], b["out1"])
-                L.call("ardae_model_loss_rows", d, b["out0"], b["out1"], xc, b["fz"], c, 1, recon[i0:i1], b["pri"])
+                self._decode_rows(b, xc, b["fz"], c, 1, recon[i0:i1], self.image_group)
                 # model.logprob (vae.py:363)
                 L.call("ardae_vae_iwae_draw", b["mu"], b["lv"], None if eps is None else eps[i0:i1], c, k, zd, seed, iw_offset, i0 * k * zd, b["z"],
                        b["logq"], None)
-                L.call("ardae_model_decode", d, flat, packed, b["z"], c * k, ws, ws.numel(), b["out0"], b["out1"])
-                L.call("ardae_model_loss_rows", d, b["out0"], b["out1"], xc, b["z"], c * k, k, b["rec"], b["pri"])
+                self._decode_rows(b, xc, b["z"], c, k, b["rec"], self.group)
                 L.call("ardae_iwae_reduce", b["rec"], b["pri"], b["logq"], c, k, out[i0:i1])
         return recon, kld, out
 
@@ -168,7 +201,8 @@ class VaeEngine:
 
     def __init__(self, model, cfg: VaeConfig, batch_size, graph=True):
         if not isinstance(model, GaussianVAE):
-            raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE); the implicit models take net.ArdaeEngine")
+            raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE); the implicit models take "
+                            "net.ArdaeEngine")
         if not isinstance(cfg, VaeConfig):
             raise TypeError(f"VaeEngine takes a VaeConfig, not a {type(cfg).__name__}")
         model._require_gpu()

@@ -1,0 +1,338 @@
+"""The conv Gaussian-posterior baseline (ardae_model_desc.kind 11, the reference's `vae.py --model conv`): layout, initialisation, argument
+validation of kind 11 at every entry point, refusals of the module, and the float64 restatement of the family (F.conv2d / F.conv_transpose2d,
+padding and crop as models/vae/conv.py) that the GPU tests lean on - pinned here to the reference's float64 fixtures.  No GPU needed.
+
+The fixtures (tools/gen_vae_conv_golden.py) do not store the 703 405 parameters: `conv_params` regenerates them from the stored seed with the
+oracle's platform-independent initialiser, exactly as the tool did."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import ardae_amd as net
+from ardae_amd import _lib as L
+from ardae_amd import layout
+from oracle import ardae_oracle as O
+from test_ardae_uncond import ACTS, rel
+from test_vae_baseline import BETAS, adam_step, lin, load
+
+CASES = ("z32_b3", "z6_b5")
+D = 784
+TOL64 = 1e-9          # float64 restatement against the reference's float64 outputs: losses, full tensors and summaries
+
+
+def conv_params(z, seed, special, dtype=torch.float32):
+    """tools/gen_vae_conv_golden.py::conv_params: oracle.init_params on layout.conv_vae_spec(z); special: the init of do_xavier, do_m5bias"""
+    spec = layout.conv_vae_spec(z)
+    sp = None
+    if special:
+        sp = {n: (("xavier",) if n.endswith("weight") else ("zeros",)) for n, _ in spec if "deconv" not in n and "logit_fn" not in n}
+    p = O.init_params(spec, seed, sp, dtype)
+    if special:
+        p["decode.reparam.logit_fn.bias"].fill_(-5.0)
+    return p
+
+
+def fixture_params(fx, dtype=torch.float32):
+    """(the float64 runs of the tool start from the fp32 numbers, widened)"""
+    return {k: v.to(dtype) for k, v in conv_params(int(fx["shape"][1]), int(fx["seed"]), bool(int(fx["special"]))).items()}
+
+
+def summary(t):
+    t = t.detach().reshape(-1)
+    return torch.cat([torch.stack([t.norm(), t.sum()]), t[:8]])
+
+
+# ---- the test-side oracle: the family restated in plain torch ----------------------------------------------------------------------
+def encode(p, act, x):
+    """Encoder.forward up to the statistics (vae/conv.py:59-72)"""
+    a = ACTS[act]
+    hdn = (2 * x - 1).view(-1, 1, 28, 28)
+    for i in (1, 2, 3):
+        hdn = a(F.conv2d(hdn, p[f"encode.conv{i}.weight"], p[f"encode.conv{i}.bias"], stride=2, padding=2))
+    hdn = a(lin(p, "encode.fc", hdn.reshape(hdn.size(0), -1)))
+    return lin(p, "encode.reparam.mean_fn", hdn), lin(p, "encode.reparam.logvar_fn", hdn)
+
+
+def decode_logit(p, act, z):
+    """Decoder.forward's logits as [R, 784] (vae/conv.py:121-131): ZeroPad2d((0, 1, 0, 1)) after deconv1, the 29 x 29 output cropped to 28 x 28"""
+    a = ACTS[act]
+    hdn = a(lin(p, "decode.fc.fc", a(lin(p, "decode.fc.layers.0", z)))).view(-1, 32, 4, 4)
+    hdn = F.pad(a(F.conv_transpose2d(hdn, p["decode.deconv1.weight"], p["decode.deconv1.bias"], stride=2, padding=2)), (0, 1, 0, 1))
+    hdn = a(F.conv_transpose2d(hdn, p["decode.deconv2.weight"], p["decode.deconv2.bias"], stride=2, padding=2))
+    logit = F.conv_transpose2d(hdn, p["decode.reparam.logit_fn.weight"], p["decode.reparam.logit_fn.bias"], stride=2, padding=2)
+    return logit[:, :, :28, :28].reshape(-1, D)
+
+
+def recon_rows(p, act, x, z):
+    logit = decode_logit(p, act, z)
+    return F.binary_cross_entropy_with_logits(logit, x, reduction="none").sum(1), logit
+
+
+def forward(p, act, x, eps, beta):
+    """-> dict(mu, lv, z, mean, logit, loss, recon, kld): VAE.forward (vae/conv.py:170-201)"""
+    mu, lv = encode(p, act, x)
+    z = mu + torch.exp(0.5 * lv) * eps
+    kld = -0.5 * (1 + lv - mu ** 2 - lv.exp()).sum(1)
+    rec, logit = recon_rows(p, act, x, z)
+    return dict(mu=mu, lv=lv, z=z, mean=torch.sigmoid(logit), logit=logit, loss=(rec + beta * kld).mean(), recon=rec.mean(), kld=kld.mean())
+
+
+def loss_and_grads(p, act, x, eps, beta, scale):
+    """-> forward's dict (detached) and {name: d (scale * loss) / d p}"""
+    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
+    out = forward(p, act, x, eps, beta)
+    grads = dict(zip(p, torch.autograd.grad(scale * out["loss"], list(p.values()))))
+    return {k: v.detach() for k, v in out.items()}, grads
+
+
+def relaxed_sample(logit, u):
+    """BernoulliDistribution.sample_logistic_sigmoid at temperature 1 on the uniform draw u (models/reparam.py:111-120)"""
+    return torch.sigmoid(logit + torch.log(u + 1e-20) - torch.log(1 - u + 1e-20))
+
+
+def logprob_rows(p, act, x, eps):
+    """VAE.logprob before its mean (vae/conv.py:218-257) on injected draws eps [B, k, zd]"""
+    B, k, zd = eps.shape
+    mu, lv = encode(p, act, x)
+    mu, lv = mu[:, None, :], lv[:, None, :]
+    z = mu + torch.exp(0.5 * lv) * eps
+    c = math.log(2 * math.pi)
+    logq = (-0.5 * ((z - mu) ** 2 / lv.exp() + lv + c)).sum(2)
+    logprior = (-0.5 * (z ** 2 + c)).sum(2)
+    rec, _ = recon_rows(p, act, x[:, None, :].expand(B, k, D).reshape(B * k, D), z.reshape(B * k, zd))
+    lw = -rec.view(B, k) + logprior - logq
+    m = lw.max(1, keepdim=True)[0]
+    return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).view(B)
+
+
+def trajectory(fx):
+    """The fixture's loop restated in float64: yields (step, forward's dict, the parameters after the vendored Adam's step)"""
+    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
+                        beta_annealing=int(fx["cfg/beta_annealing"]))
+    p, st, act = fixture_params(fx, torch.float64), {}, str(fx["act"])
+    for s in range(int(fx["cfg/steps"])):
+        beta = cfg.beta_at(s)
+        assert beta == float(fx[f"{s}/beta"])
+        out, grads = loss_and_grads(p, act, torch.tensor(fx[f"{s}/x"]).double(), torch.tensor(fx[f"{s}/eps"]).double(), beta, 1.0 / D)
+        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
+        yield s, out, p
+
+
+# ---- 1. layout, initialisation -----------------------------------------------------------------------------------------------------
+def test_layout_is_the_reference_state_dict(golden_dir):
+    for name, z in (("vae_conv_z32_b3", 32), ("vae_conv_z6_b5", 6), ("vae_traj_conv", 32)):
+        fx = load(golden_dir, name)
+        assert int(fx["shape"][1]) == z
+        ref = [(str(n), tuple(int(v) for v in str(s).split(","))) for n, s in zip(fx["names"], fx["shapes"])]
+        spec = layout.conv_vae_spec(z)
+        assert [(n, tuple(s)) for n, s in spec] == ref
+        desc = L.ModelDesc(11, D, 0, 800, z, 1, L.ACT[str(fx["act"])], 0)
+        total = layout.offsets(spec)[1]
+        assert total == L.query("ardae_model_param_floats", desc) == sum(v.numel() for v in fixture_params(fx).values())
+        assert L.query("ardae_model_packed_floats", desc) > total
+        mod = net.MNISTConvVAE(z_dim=z, nonlinearity=str(fx["act"]))
+        assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == ref
+        assert (mod.input_dim, mod.h_dim, mod.latent_dim, mod.z_dim, mod.noise_dim) == (D, 800, z, z, 0)
+        sd = fixture_params(fx)
+        mod.load_state_dict(sd)
+        assert torch.equal(mod.flat_params(), torch.cat([v.reshape(-1) for v in sd.values()]))
+    counts = load(golden_dir, "vae_conv_param_counts")
+    d32 = L.ModelDesc(11, D, 0, 800, 32, 1, L.ACT["softplus"], 0)
+    assert layout.offsets(layout.conv_vae_spec(32))[1] == L.query("ardae_model_param_floats", d32) == int(counts["conv_32"])
+    sizes = [[L.query("ardae_model_workspace_floats", d32, b, 1, mode) for b in (1, 9, 70)] for mode in (0, 1, 2)]
+    for per_mode in sizes:
+        assert 0 < per_mode[0] < per_mode[1] < per_mode[2]
+    assert all(a < b for a, b in zip(sizes[0], sizes[1]))               # the training workspace holds the encoder's and more
+    with pytest.raises(NotImplementedError):
+        layout.vae_spec("conv", 784, 800, 32, 1)                         # the MLP families' spec stays theirs
+
+
+def test_initialisation_of_do_xavier_and_do_m5bias():
+    torch.manual_seed(0)
+    m = net.MNISTConvVAE(z_dim=8, do_xavier=True, do_m5bias=True)
+    p = {k: v.detach() for k, v in m.named_parameters()}
+    assert float(p["decode.reparam.logit_fn.bias"]) == -5.0
+    for k, v in p.items():
+        if "deconv" in k or "logit_fn" in k:
+            continue
+        if k.endswith("bias"):
+            assert float(v.abs().max()) == 0.0, k
+    for k, fan in (("encode.conv2.weight", (16 + 32) * 25), ("encode.fc.weight", 512 + 800), ("decode.fc.fc.weight", 300 + 512)):
+        bound = math.sqrt(6.0 / fan)                                    # xavier-uniform
+        assert 0.9 * bound < float(p[k].abs().max()) <= bound, k
+    # ConvTranspose2d keeps torch's default: U(+-1 / sqrt(fan_in)), fan_in = weight.size(1) * 25, biases not zeroed
+    for k, fan_in in (("decode.deconv1", 32 * 25), ("decode.deconv2", 16 * 25)):
+        bound = 1.0 / math.sqrt(fan_in)
+        assert 0.9 * bound < float(p[k + ".weight"].abs().max()) <= bound and 0.0 < float(p[k + ".bias"].abs().max()) <= bound, k
+    plain = {k: v.detach() for k, v in net.MNISTConvVAE(z_dim=8).named_parameters()}
+    assert float(plain["encode.fc.bias"].abs().max()) > 0.0 and float(plain["encode.fc.weight"].abs().max()) <= 1.0 / math.sqrt(512)
+    assert abs(float(plain["decode.reparam.logit_fn.bias"])) <= 1.0 / 5
+
+
+# ---- 2. the float64 restatement, pinned to the reference ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES)
+def test_restatement_is_the_reference_in_float64(golden_dir, case):
+    fx = load(golden_dir, f"vae_conv_{case}")
+    act = str(fx["act"])
+    p = fixture_params(fx, torch.float64)
+    x, eps, dec = (torch.tensor(fx[k]).double() for k in ("x", "eps", "dec_noise"))
+    for b, beta in BETAS.items():
+        out, grads = loss_and_grads(p, act, x, eps, beta, 1.0 / D)
+        for k in ("z", "mean", "loss", "recon", "kld"):
+            assert rel(out[k], fx[f"{b}/{k}_f64"]) <= TOL64, (b, k)
+        assert rel(relaxed_sample(out["logit"], dec), fx[f"{b}/x_sample_f64"]) <= TOL64
+        assert rel(out["mu"], fx["mu_f64"]) <= TOL64 and rel(out["lv"], fx["lv_f64"]) <= TOL64
+        full = {k[len(b) + 7:] for k in fx if k.startswith(f"{b}/g_f64/")}
+        summed = {k[len(b) + 8:] for k in fx if k.startswith(f"{b}/gs_f64/")}
+        assert full | summed == set(grads) and not full & summed
+        for k, g in grads.items():
+            assert (g.numel() <= 16384) == (k in full), k
+            if k in full:
+                assert rel(g, fx[f"{b}/g_f64/{k}"]) <= TOL64, (b, k)
+            else:
+                want = torch.tensor(fx[f"{b}/gs_f64/{k}"])
+                got = summary(g)
+                assert abs(float(got[0]) - float(want[0])) <= TOL64 * float(want[0]), (b, k)                 # L2 norm
+                assert abs(float(got[1]) - float(want[1])) <= TOL64 * float(want[0]) * math.sqrt(g.numel()), (b, k)   # the sum, on the scale of its terms
+                assert rel(got[2:], want[2:]) <= TOL64, (b, k)
+    lp = logprob_rows(p, act, x, torch.tensor(fx["lp/eps"]).double()).mean()
+    assert rel(lp, fx["lp/value_f64"]) <= TOL64
+    # the fp32 fixture is the same computation at fp32's precision
+    assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
+
+
+def test_restated_trajectory_is_the_reference_in_float64(golden_dir):
+    fx = load(golden_dir, "vae_traj_conv")
+    assert int(fx["special"]) == 1 and int(fx["cfg/steps"]) == 4                # the run starts from the do_xavier / do_m5bias init
+    for s, out, p in trajectory(fx):
+        for k in ("loss", "recon", "kld"):
+            assert rel(out[k], fx[f"{s}/{k}_f64"]) <= TOL64, (s, k)
+        for k, v in p.items():
+            want = torch.tensor(fx[f"{s}/ps_f64/{k}"])
+            got = summary(v)
+            assert abs(float(got[0]) - float(want[0])) <= TOL64 * float(want[0]), (s, k)
+            assert abs(float(got[1]) - float(want[1])) <= TOL64 * float(want[0]) * math.sqrt(v.numel()), (s, k)
+            assert rel(got[2:], want[2:]) <= TOL64, (s, k)
+    assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
+
+
+# ---- 3. validation before any HIP call ---------------------------------------------------------------------------------------------
+def test_argument_validation_of_kind_11_at_every_entry_point():
+    lib = L.lib()
+    one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
+    ref = ctypes.byref
+
+    def fails(rc, fragment):
+        assert rc < 0
+        assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
+
+    fwd = lambda d, x, B, wsf, z, losses: lib.ardae_vae_forward(ref(d), one, one, x, None, B, 1.0, 1.0, 7, 0, None, one, wsf, z, None, losses, None)
+    fwd_dev = lambda d, st: lib.ardae_vae_forward_dev(ref(d), one, one, one, None, 4, st, 1.0, 7, 0, None, one, big, one, None, one, None)
+    bwd = lambda d, B, wsf, g: lib.ardae_vae_backward(ref(d), one, one, one, B, 1.0, 1.0, one, wsf, g, 0.0, None)
+    bwd_dev = lambda d, st: lib.ardae_vae_backward_dev(ref(d), one, one, one, 4, st, 1.0, one, big, one, 0.0, None)
+    stats = lambda d, B, wsf, mu, lv: lib.ardae_vae_encode_stats(ref(d), one, one, one, B, one, wsf, mu, lv, None)
+    head = lambda d, B, variant, mu, eps_out=one: lib.ardae_vae_head(ref(d), one, one, one, None, B, 7, 0, None, variant, mu, one, one, eps_out, one, None)
+    desc = lambda **kw: L.ModelDesc(*[kw.get(k, v) for k, v in (("kind", 11), ("input_dim", 784), ("noise_dim", 0), ("h_dim", 800), ("z_dim", 32),
+                                                                  ("n_layers", 1), ("act", 2), ("flags", 0))])
+    ok = desc()
+    assert lib.ardae_model_param_floats(ref(ok)) == 703405 and lib.ardae_model_packed_floats(ref(ok)) > 703405
+    assert lib.ardae_model_workspace_floats(ref(ok), 4, 1, 1) > lib.ardae_model_workspace_floats(ref(ok), 4, 1, 0) > 0
+    assert lib.ardae_model_workspace_floats(ref(ok), 4, 1, 2) > 0
+    assert lib.ardae_model_workspace_floats(ref(ok), 4, 2, 1) == lib.ardae_model_workspace_floats(ref(ok), 4, 2, 0) == 0     # one draw per image
+    assert lib.ardae_model_workspace_floats(ref(ok), 4, 1, 3) == 0                                                            # no sampler pair
+    # this family's fused head (the two MFMA products + one tail launch) is the default wherever its tail runs: z <= 64 (README)
+    assert [lib.ardae_vae_head_fused_ok(ref(desc(z_dim=z))) for z in (32, 6, 64, 65)] == [1, 1, 1, 0]
+    # each descriptor rule
+    for bad, why in ((desc(input_dim=783), "input_dim 784"), (desc(h_dim=300), "h_dim must be 800"), (desc(n_layers=2), "n_layers must be 1"),
+                     (desc(noise_dim=3), "noise_dim must be 0"), (desc(flags=1), "flags must be 0"), (desc(z_dim=0), "bad dimensions"),
+                     (desc(act=0), "unknown activation"), (desc(act=99), "unknown activation")):
+        assert lib.ardae_model_param_floats(ref(bad)) == lib.ardae_model_packed_floats(ref(bad)) == 0
+        assert all(lib.ardae_model_workspace_floats(ref(bad), 4, 1, mode) == 0 for mode in (0, 1, 2))
+        assert lib.ardae_vae_head_fused_ok(ref(bad)) == 0
+        fails(lib.ardae_model_pack(ref(bad), one, one, None), why)
+        fails(lib.ardae_model_decode(ref(bad), one, one, one, 4, one, big, one, None, None), why)
+        fails(fwd(bad, one, 4, big, one, one), why)
+        fails(bwd(bad, 4, big, one), why)
+        fails(stats(bad, 4, big, one, one), why)
+        fails(head(bad, 4, 0, one), why)
+    fails(fwd(ok, one, 0, big, one, one), "bad batch")
+    fails(fwd(ok, one, -3, big, one, one), "bad batch")
+    fails(fwd(ok, one, 4, small, one, one), "workspace too small")
+    fails(fwd(ok, None, 4, big, one, one), "null pointer")
+    fails(fwd(ok, one, 4, big, None, one), "null pointer")
+    fails(fwd(ok, one, 4, big, one, None), "null pointer")
+    fails(fwd_dev(ok, None), "beta_state is NULL")
+    fails(bwd(ok, 0, big, one), "bad batch")
+    fails(bwd(ok, 4, small, one), "workspace too small")
+    fails(bwd(ok, 4, big, None), "null pointer")
+    fails(bwd_dev(ok, None), "beta_state is NULL")
+    fails(stats(ok, 0, big, one, one), "bad batch")
+    fails(stats(ok, 4, small, one, one), "workspace too small")
+    fails(stats(ok, 4, big, None, one), "null pointer")
+    fails(stats(ok, 4, big, one, None), "null pointer")
+    fails(head(ok, 0, 1, one), "bad batch")
+    fails(head(ok, 4, 3, one), "variant must be")
+    fails(head(ok, 4, 1, None), "null pointer")
+    fails(head(ok, 4, 2, one, eps_out=None), "null pointer")                               # the unfused head draws into eps_out
+    fails(head(desc(z_dim=65), 4, 1, one), "the fused head takes")
+    fails(lib.ardae_model_decode(ref(ok), one, one, one, 4, one, small, one, None, None), "workspace too small")
+    fails(lib.ardae_model_decode(ref(ok), one, one, None, 4, one, big, one, None, None), "bad arguments")
+    # the implicit models' calls refuse the family: there is no sampler
+    fails(lib.ardae_model_encode(ref(ok), one, one, one, None, 4, 1, one, big, one, None), "analytic posterior")
+    fails(lib.ardae_model_vae_forward(ref(ok), one, one, one, one, 4, 1, 1.0, one, big, one, one, None), "ardae_vae_forward")
+    fails(lib.ardae_model_vae_backward(ref(ok), one, one, one, one, 4, 1, 1.0, 1.0, None, one, big, one, 0.0, None), "ardae_vae_backward")
+    # 10 is still not a kind, anywhere; the messages name the third kind
+    bad = desc(kind=10)
+    assert lib.ardae_model_param_floats(ref(bad)) == lib.ardae_model_packed_floats(ref(bad)) == lib.ardae_model_workspace_floats(ref(bad), 4, 1, 1) == 0
+    assert lib.ardae_vae_head_fused_ok(ref(bad)) == 0
+    for rc in (lib.ardae_model_pack(ref(bad), one, one, None), lib.ardae_model_decode(ref(bad), one, one, one, 4, one, big, one, None, None),
+               lib.ardae_model_encode(ref(bad), one, one, one, None, 4, 1, one, big, one, None)):
+        fails(rc, "kind must be")
+        assert b"11 (MNISTConvVAE)" in lib.ardae_last_error()
+    for call in (lambda: fwd(bad, one, 4, big, one, one), lambda: bwd(bad, 4, big, one), lambda: stats(bad, 4, big, one, one), lambda: head(bad, 4, 0, one)):
+        fails(call(), "kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE)")
+
+
+# ---- 4. refusals on the module -----------------------------------------------------------------------------------------------------
+def test_module_surface_and_refusals():
+    with pytest.raises(NotImplementedError, match="28x28x1"):
+        net.MNISTConvVAE(input_height=32)
+    with pytest.raises(NotImplementedError, match="28x28x1"):
+        net.MNISTConvVAE(input_channels=2)
+    with pytest.raises(NotImplementedError, match="nonlinearity"):
+        net.MNISTConvVAE(nonlinearity="gelu")
+    with pytest.raises(NotImplementedError, match="normal_energy_func"):
+        net.MNISTConvVAE(energy_func=lambda z: z.sum(1))
+    m = net.MNISTConvVAE(z_dim=8)
+    assert isinstance(m, net.GaussianVAE) and m.return_samples and (m.input_height, m.input_channels, m.do_xavier, m.do_m5bias) == (28, 1, False, False)
+    for call in (lambda: m(torch.zeros(3, 784)), lambda: m(torch.zeros(3, 1, 28, 28)), lambda: m.logprob(torch.zeros(3, 784), sample_size=4),
+                 lambda: m.logprob_rows(torch.zeros(3, 784), 4), lambda: m.encode(torch.zeros(3, 784)), lambda: m.encode_stats(torch.zeros(3, 784)),
+                 lambda: m.generate(2)):
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            call()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        net.VaeEngine(m, net.VaeConfig(), batch_size=4)
+    with pytest.raises(TypeError, match="MNISTConvVAE"):
+        net.VaeEngine(net.ConvIPVAE(z_dim=8, noise_dim=4), net.VaeConfig(), batch_size=4)
+    with pytest.raises(TypeError, match="MNISTConvVAE"):
+        net.GaussianIwaeEvaluator(net.ConvIPVAE(z_dim=8, noise_dim=4), 16)
+    with pytest.raises(NotImplementedError, match="z_dim 65 > 64"):
+        net.GaussianIwaeEvaluator(net.MNISTConvVAE(z_dim=65), 16)
+    # the evaluator plans the recipe's evaluation at the default budget (this decoder keeps ~5e4 floats per decoded row, so the importance samples
+    # are decoded 16 images per call; the encoder runs on 64); chunks are whole groups of 64 images, and a budget below one group is refused
+    ev = net.GaussianIwaeEvaluator(net.MNISTConvVAE(z_dim=32), 256)
+    plan = ev.plan(2048)
+    assert plan[0][0] == 0 and plan[-1][1] == 2048 and all(a[1] == b[0] for a, b in zip(plan, plan[1:]))
+    assert (ev.image_group, ev.group) == (64, 16) and ev.floats_per_chunk(plan[0][1]) <= ev.budget
+    assert all((b - a) % 64 == 0 for a, b in plan[:-1]) and len(plan) > 1
+    small = net.GaussianIwaeEvaluator(ev.model, 256, max_workspace_floats=ev.floats_per_chunk(150))
+    assert [b - a for a, b in small.plan(300)] == [64, 64, 64, 64, 44]       # three equal chunks of 100 fit, cut down to whole groups
+    with pytest.raises(ValueError, match="one group of 64 images"):
+        net.GaussianIwaeEvaluator(ev.model, 256, max_workspace_floats=ev.floats_per_chunk(40)).plan(100)
+    assert net.GaussianIwaeEvaluator(ev.model, 256, max_workspace_floats=ev.floats_per_chunk(12)).plan(12) == [(0, 12)]
+    mlp = net.GaussianIwaeEvaluator(net.MNISTVAE(input_dim=12, h_dim=16, z_dim=4), 16)
+    assert (mlp.image_group, mlp.group) == (None, None)                     # the MLP families: a chunk per call, as before
