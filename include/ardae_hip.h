@@ -376,12 +376,12 @@ int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, doubl
  *                        noise of such a call = [eps0: B q x noise_dim | eps: B q q x z_dim], two consecutive blocks; hidden1a context
  *                        cat(h0, h) [B, 2 h_dim] */
 typedef struct ardae_model_desc {
-  int kind;     /* 0 .. 7 above; 8 / 9 / 11: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0).
+  int kind;     /* 0 .. 7 above; 8 / 9 / 11 / 12: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0).
                  * 10 is not a kind */
   int input_dim, noise_dim, h_dim, z_dim;
   int n_layers; /* --model-n-layers */
   int act;      /* any ARDAE_ACT_* but NONE; kinds 5 / 6: ARDAE_ACT_ELU */
-  int flags;    /* kinds 5 / 6: ARDAE_MODEL_NO_CENTER = do_center False (--model resconv-res / auxresconv: the trunk sees x, not 2x - 1;
+  int flags;    /* kinds 5 / 6 / 12: ARDAE_MODEL_NO_CENTER = do_center False (--model resconv-res / auxresconv: the trunk sees x, not 2x - 1;
                  * ivae/resconv.py:131-132, vae/auxresconv.py:56-58); 0 elsewhere */
 } ardae_model_desc;
 enum { ARDAE_MODEL_NO_CENTER = 1,
@@ -467,7 +467,8 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
                                          float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
 
 
-/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, toy.py, conv.py; csrc/vaemodel.hip, csrc/convvae.hip): ardae_model_desc.kind 8 / 9 / 11 ------
+/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, toy.py, conv.py, resconv.py; csrc/vaemodel.hip, csrc/convvae.hip, csrc/resmodel.hip):
+ * ardae_model_desc.kind 8 / 9 / 11 / 12 ------
  * The second trainer of the reference: an encoder MLP with a Gaussian head and its analytic KL, no sampler noise, no score network.
  *   kind 8 (MNISTVAE, `vae.py --model mnist`): encode.main.{layers.0..n_layers-2, fc}, encode.reparam.{mean_fn, logvar_fn}, decode.main.{layers.*, fc},
  *                        decode.reparam.logit_fn; Bernoulli decoder, x rescaled to 2x - 1 inside the encoder (vae/mnist.py:54)
@@ -476,7 +477,14 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
  *                        512 -> 800, encode.reparam.{mean_fn, logvar_fn} [z_dim, 800], then kind 2's decoder: decode.fc.{layers.0, fc}, decode.deconv{1,2},
  *                        decode.reparam.logit_fn.  input_dim 784, h_dim 800 (the fc width, as kind 4 records it), n_layers 1, z_dim >= 1; every entry
  *                        point below takes it, with the same workspace modes.  10 is not a kind.
- * noise_dim must be 0 and flags 0; n_layers 1 .. 4 (kind 11: 1).  ardae_model_param_floats / packed_floats / workspace_floats (nz = 1; mode 0: encode_stats, 1: forward +
+ *   kind 12 (MNISTResConvVAE, `vae.py --model resconv`, models/vae/resconv.py; 28 x 28 x 1 only): the weight-normalised residual trunk of kinds 5 / 6 as
+ *                        encode.enc.{0,2,4,6,8}.conv_{0h,h1,01}.{direction,scale,bias} and encode.enc.11.dot_* (512 -> c_dim), the plain Linears
+ *                        encode.reparam.{mean_fn, logvar_fn} [z_dim, c_dim] (no log-variance clip), then the decoder of kinds 5 / 6: decode.dec.{0,2}.dot_*,
+ *                        decode.dec.{6,8,12,14,17}.conv_*.  input_dim 784, h_dim = c_dim >= 1 (450 in the recipe), n_layers 1, act ARDAE_ACT_ELU, z_dim >= 1;
+ *                        flags 0 (do_center: the trunk sees 2x - 1) or ARDAE_MODEL_NO_CENTER (what vae.py passes).  ardae_model_pack composes the effective
+ *                        weights as for kinds 5 / 6.  Its decode-only workspace (mode 2) keeps ONE columns scratch for all blocks and, with the fused tail
+ *                        below, no buffer of the last stage: about a third of the floats per decoded row of kinds 5 / 6.
+ * noise_dim must be 0 and flags 0 (kind 12: 0 or ARDAE_MODEL_NO_CENTER); n_layers 1 .. 4 (kinds 11 / 12: 1).  ardae_model_param_floats / packed_floats / workspace_floats (nz = 1; mode 0: encode_stats, 1: forward +
  * backward, 2: decode) / pack / decode / loss_rows take these kinds; ardae_model_encode and ardae_model_vae_* refuse them (there is no sampler).
  *
  * ardae_vae_forward: mu = M h + m, lv = L h + l on the encoder's last hidden rows h, z = mu + exp(lv / 2) eps,
@@ -499,7 +507,8 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
  *   ties with the unfused launches, which are the default there).  Kind 11: on its 800-wide hidden rows gauss_head_kernel loses to the unfused
  *   launches (51.0 against 19.8 us at 128 x 800 -> 2 x 32), so that kind's variant 1 is another fused head: the two products on the MFMA linears, then ONE
  *   launch for the draw, the reparameterisation and the KL rows (three launches, every output equal to variant 2's bit for bit); ardae_vae_head_fused_ok is 1
- *   for it wherever z_dim <= 64.
+ *   for it wherever z_dim <= 64.  Kind 12: variant 1 is gauss_head_kernel, variant 2 the unfused launches, as for kind 8; its default is variant 2
+ *   (ardae_vae_head_fused_ok is 0: the recipe's c_dim 450 is no multiple of 4, and the kernel's float-by-float path loses there).
  * ardae_vae_kld_rows: kld[b] = -0.5 sum_c (1 + lv - mu^2 - exp(lv)) from mu, lv [B, z], the terms in double and added over ascending c - the row values
  *   of the head, for callers that hold the statistics (the ELBO rows of the evaluator). */
 int ardae_vae_head_fused_ok(const ardae_model_desc* d);
@@ -526,6 +535,21 @@ int ardae_vae_encode_stats(const ardae_model_desc* d, const float* params, const
  * decoder, the row losses and the log-mean-exp are ardae_model_decode, ardae_model_loss_rows and ardae_iwae_reduce. */
 int ardae_vae_iwae_draw(const float* mu, const float* lv, const float* eps, int B, int k, int z, uint64_t seed, uint64_t offset,
                         uint64_t first_element, float* z_out, float* logq, float* eps_out, void* stream);
+
+/* The last stage of the residual-conv decoder on its own (kind 12; csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
+ * -> bilinear x2 upsampling (align_corners) -> decode.dec.17 = ResConv2d(16 -> 1) -> logits [R, 784].  It reads the effective weights ardae_model_pack
+ * composed into `packed`.
+ *   variant 1: resconv_tail_kernel, ONE launch, a workgroup per image: the interpolation, hmid = ELU(conv3x3_0h(u28) + b) and
+ *              logit = conv3x3_h1(hmid) + conv3x3_01(u28) + (b_h1 + b_01) stay on chip; every sum runs in a fixed order inside the image's workgroup, so a
+ *              row's bits do not depend on R.  Needs no workspace (it may be NULL).
+ *   variant 2: the launches the training forward runs (upsample, im2col, linear, im2col, two-source linear); workspace:
+ *              ardae_resconv_tail_workspace_floats(d, R, 2) floats.
+ *   variant 0: what ardae_model_decode runs for kind 12: variant 1, unless ARDAE_RESCONV_TAIL_UNFUSED=1 is set under ARDAE_DEBUG_KNOBS=1 (then the mode-2
+ *              workspace of the kind grows by the last stage's buffers).
+ * ardae_resconv_tail_workspace_floats: the floats `variant` needs at R rows (0 for the fused kernel, and for bad arguments). */
+size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant);
+int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* y14, int R, int variant, float* workspace,
+                       size_t workspace_floats, float* logits, void* stream);
 
 /* ---- evaluation / visualisation side of the model surface (csrc/eval_kernels.hip) ----------------------------
  * Decoder samples that ImplicitPosteriorVAE.forward / .generate return next to the losses (ivae/mnist.py:188-199,300,316):

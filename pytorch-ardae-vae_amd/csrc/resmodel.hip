@@ -1,7 +1,10 @@
-// Weight-normalised residual-conv implicit-posterior VAEs on gfx950 (ardae_model_desc.kind 5 and 6):
+// Weight-normalised residual-conv VAEs on gfx950 (ardae_model_desc.kind 5, 6 and 12):
 //   kind 5  ResConvIPVAE           models/ivae/resconv.py:53-245 (`--model resconvct-res`: do_center, enc_type 'res-wn-mlp')
 //   kind 6  MNISTResConvAuxIPVAE   models/ivae/auxresconv.py:48-255 + models/vae/auxresconv.py:26-185 (`--model auxresconvct`)
-// both with the decoder of models/vae/resconv.py:79-136.  The shipped "implicit resconv" / "hierarchical resconv" recipes
+//   kind 12 MNISTResConvVAE        models/vae/resconv.py:26-241 (`vae.py --model resconv`): the same trunk (width c_dim = h_dim), a plain Gaussian head
+//                                  encode.reparam.{mean_fn, logvar_fn} on it (no clip, one draw per image, the analytic KL of kinds 8 / 9 / 11) - driven
+//                                  by the ardae_vae_* entry points (csrc/vaemodel.hip dispatches here), not by the sampler calls
+// all with the decoder of models/vae/resconv.py:79-136.  The shipped "implicit resconv" / "hierarchical resconv" recipes
 // (run_vae_dbmnist.sh) train them with ELU, an mlp-res cDAE, --std-scale 100.
 //
 // Every residual block (models/layers2.py:305-352, models/layers.py:66-85) is
@@ -19,6 +22,7 @@
 #include "auxmodel.h"
 #include "common.h"
 #include "resmodel.h"
+#include "vaemodel.h"
 
 namespace ardae {
 namespace {
@@ -218,6 +222,90 @@ __global__ void spm4_kernel(const float* __restrict__ x, const float* __restrict
   else y[e] = (u > 20.f ? u : log1pf(expf(u))) - 4.f;
 }
 
+// The decoder's last stage as ONE launch (kind 12's decode-only path; ardae_resconv_tail variant 1): upsample 14 -> 28 (up_src and the expression
+// of upsample2_fwd_kernel), then dec[6] = ResConv2d(16 -> 1):  hmid = ELU(conv3x3_a(u28) + b_a),  logit = conv3x3_h(hmid) + conv3x3_s(u28) + (b_h + b_s).
+// One workgroup per image; nothing but the 784 logits leaves the chip (the unfused launches write u28, two column matrices and hmid: ~134k floats a row).
+//   LDS: u28 as 16 channel planes of 30 x 30 (a zero halo: the padding taps read it), hmid as one such plane, the 2 x 144 + 9 effective weights: 64.3 KB,
+//        two workgroups a CU.  4-byte reads and every write bank on word % 32 and conflict within a 32-lane half: the planes are planar and a half-wave
+//        owns ONE image row (28 of its 32 lanes), so its reads are 28 consecutive words - no conflict; the weight reads are broadcasts.  The
+//        interpolation walks (pixel, channel) with the channel fastest: coalesced reads of the NHWC y14 (L2 / L1 resident, each value read by at most
+//        four outputs), and the plane stride 930 = 2 mod 32 puts a half-wave's 16 channels x 2 pixels on 32 different banks.
+//   Work: half-wave r < 7 owns rows r, r + 7, r + 14, r + 21, a lane one column position in them: a channel's 18 weights are read once for the four
+//        pixels, 72 FMAs against 36 + 18 LDS reads.  Each pixel's sums run over ascending (c, kh, kw) from zero, the biases added last, whatever R is:
+//        a row's bits do not depend on the rows of the call.
+constexpr int RT_THREADS = 256, RT_PIX = 4, RT_C = 16, RT_P = 30, RT_PLANE = RT_P * RT_P, RT_STRIDE = RT_PLANE + 30, RT_HALO = 4 * RT_P - 4;
+__global__ __launch_bounds__(RT_THREADS) void resconv_tail_kernel(const float* __restrict__ y14, const float* __restrict__ wa, const float* __restrict__ ba,
+                                                                  const float* __restrict__ wh, const float* __restrict__ wsk,
+                                                                  const float* __restrict__ bsum, float* __restrict__ logits) {
+  __shared__ float u[RT_C * RT_STRIDE];
+  __shared__ float hm[RT_PLANE];
+  __shared__ float w_a[RT_C * 9], w_s[RT_C * 9], w_h[12];
+  const int t = threadIdx.x;
+  const float* __restrict__ yb = y14 + (size_t)blockIdx.x * (196 * RT_C);
+  for (int i = t; i < RT_C * 9; i += RT_THREADS) { w_a[i] = wa[i]; w_s[i] = wsk[i]; }
+  if (t < 9) w_h[t] = wh[t];
+  // the zero halo of the 16 + 1 planes: top row, bottom row, then the two end cells of rows 1 .. 28
+  for (int i = t; i < (RT_C + 1) * RT_HALO; i += RT_THREADS) {
+    const int c = i / RT_HALO, j = i - c * RT_HALO;
+    int r, q;
+    if (j < RT_P) { r = 0; q = j; }
+    else if (j < 2 * RT_P) { r = RT_P - 1; q = j - RT_P; }
+    else { const int k = j - 2 * RT_P; r = 1 + (k >> 1); q = (k & 1) ? RT_P - 1 : 0; }
+    float* plane = c < RT_C ? u + c * RT_STRIDE : hm;
+    plane[r * RT_P + q] = 0.f;
+  }
+  for (int e = t; e < 784 * RT_C; e += RT_THREADS) {
+    const int c = e & (RT_C - 1), pix = e >> 4, ow = pix % 28, oh = pix / 28;
+    int h0, h1, w0, w1; float fh, fw;
+    up_src(oh, 14, 28, h0, h1, fh); up_src(ow, 14, 28, w0, w1, fw);
+    const float* xb = yb + c;
+    const float v00 = xb[(h0 * 14 + w0) * RT_C], v01 = xb[(h0 * 14 + w1) * RT_C], v10 = xb[(h1 * 14 + w0) * RT_C], v11 = xb[(h1 * 14 + w1) * RT_C];
+    u[c * RT_STRIDE + (oh + 1) * RT_P + ow + 1] = (1.f - fh) * ((1.f - fw) * v00 + fw * v01) + fh * ((1.f - fw) * v10 + fw * v11);
+  }
+  __syncthreads();
+  const int w = t & 31, hb = t >> 5;          // pixel i of the thread: (hb + 7 i, w); padded position of tap (kh, kw): (hb + 7 i + kh, w + kw)
+  const bool on = hb < 28 / RT_PIX && w < 28;
+  float aa[RT_PIX], as[RT_PIX];
+#pragma unroll
+  for (int i = 0; i < RT_PIX; ++i) aa[i] = as[i] = 0.f;
+  if (on) {
+#pragma unroll 2
+    for (int c = 0; c < RT_C; ++c) {
+      float ka[9], ks[9];
+#pragma unroll
+      for (int j = 0; j < 9; ++j) { ka[j] = w_a[c * 9 + j]; ks[j] = w_s[c * 9 + j]; }
+      const float* uc = u + c * RT_STRIDE + hb * RT_P + w;
+#pragma unroll
+      for (int i = 0; i < RT_PIX; ++i)
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) {
+            const float v = uc[(7 * i + kh) * RT_P + kw];
+            aa[i] = __builtin_fmaf(ka[kh * 3 + kw], v, aa[i]);
+            as[i] = __builtin_fmaf(ks[kh * 3 + kw], v, as[i]);
+          }
+    }
+    const float b = ba[0];
+#pragma unroll
+    for (int i = 0; i < RT_PIX; ++i) hm[(hb + 7 * i + 1) * RT_P + w + 1] = act_fwd_rt(ACT_ELU, aa[i] + b);
+  }
+  __syncthreads();
+  if (on) {
+    const float bs = bsum[0];
+    float* __restrict__ out = logits + (size_t)blockIdx.x * 784;
+#pragma unroll
+    for (int i = 0; i < RT_PIX; ++i) {
+      float o = 0.f;
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) o = __builtin_fmaf(w_h[kh * 3 + kw], hm[(hb + 7 * i + kh) * RT_P + w + kw], o);
+      out[(hb + 7 * i) * 28 + w] = (o + as[i]) + bs;
+    }
+  }
+}
+
 #define RES_LAUNCH(kernel, n, ...)                                                            \
   do {                                                                                        \
     hipLaunchKernelGGL(kernel, dim3(nblk(n)), dim3(256), 0, st, __VA_ARGS__);                 \
@@ -240,7 +328,7 @@ struct ResLayout {
   bool clipped;                  // kind 6 + ARDAE_MODEL_CLIPPED: MNISTResConvAuxIPVAEClipped (no 'spm4' clip, z0 keeps an unscaled eps0)
   std::vector<Blk> trunk, dec;   // trunk: 5 conv + ResLinear(512 -> cdim); dec: 2 ResLinear + 5 conv
   std::vector<HeadOp> head;      // kind 5: encode.fc (the shipped recipe: ResLinear(cdim + nd -> hdim), ELU, ResLinear(hdim -> zd), un-normalised WN operators)
-  Lin mu0, lv0, efc, mu, lv;     // kind 6: aux_encode.reparam.{mean,logvar}_fn, encode.fc.0, encode.reparam.{mean,logvar}_fn
+  Lin mu0{}, lv0{}, efc{}, mu{}, lv{};   // kind 6: aux_encode.reparam.{mean,logvar}_fn, encode.fc.0, encode.reparam.{mean,logvar}_fn; kind 12: the last two
   size_t total = 0;
 
   explicit ResLayout(const ardae_model_desc& d)
@@ -292,6 +380,8 @@ struct ResLayout {
         res_op(hdim, nl - 1 == 0 ? cin : hdim, plain, ACT_ELU, nl - 1 == 0);
         lin_op(zd, hdim, ACT_NONE, false);
       }
+    } else if (kind == 12) {
+      mu = lin(zd, cdim); lv = lin(zd, cdim);
     } else {
       mu0 = lin(nd, cdim); lv0 = lin(nd, cdim); efc = lin(cdim, cdim + nd); mu = lin(zd, cdim); lv = lin(zd, cdim);
     }
@@ -314,7 +404,7 @@ struct ResPacked {
   std::vector<BlkPk> trunk, dec;
   struct HeadPk { BlkPk k; LinPk lk; };
   std::vector<HeadPk> head;
-  LinPk mu0, lv0, efc, mu, lv;
+  LinPk mu0{}, lv0{}, efc{}, mu{}, lv{};
   ResPacked(const ResLayout& P, PackList& pl) {
     // an operator's panels are packed from its effective weight: composed into the packed buffer at k.weff by res_pack's
     // compose launch (weight norm), or the parameter itself (plain nn.Linear operator, whose weff / inv stay unused)
@@ -351,13 +441,15 @@ struct ResPacked {
         if (o.res) hp.k = blk(o.b, o.concat ? P.cdim : 0); else hp.lk = lin(o.l, o.concat ? P.cdim : 0);
         head.push_back(hp);
       }
-    } else { mu0 = lin(P.mu0, 0); lv0 = lin(P.lv0, 0); efc = lin(P.efc, P.cdim); mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
+    } else if (P.kind == 12) { mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
+    else { mu0 = lin(P.mu0, 0); lv0 = lin(P.lv0, 0); efc = lin(P.efc, P.cdim); mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
     for (auto& b : P.dec) dec.push_back(blk(b, 0));
   }
   explicit ResPacked(const ResLayout& P, PackList&& sizing = PackList()) : ResPacked(P, sizing) {}   // offsets only
 };
 
 int res_desc_ok(const ardae_model_desc& d) {
+  if (d.kind == 12) return resvae_desc_check(&d);
   ARDAE_CHECK_ARG(d.input_dim == 784 && d.noise_dim >= 1 && d.z_dim >= 1 && d.h_dim >= 1, "model: the residual-conv models are hard-wired to 28x28x1 inputs");
   ARDAE_CHECK_ARG(d.act == ACT_ELU, "model: the residual-conv models use ELU (--model-nonlin elu; models/ivae/auxresconv.py:69 asserts it)");
   ARDAE_CHECK_ARG(d.kind != 5 || (d.n_layers >= 1 && d.n_layers <= 4), "model: ResConvIPVAE takes --model-n-layers 1 .. 4");
@@ -405,6 +497,20 @@ int blk_fwd(const Blk& b, const BlkPk& k, const float* params, const float* pack
   ARDAE_TRY(lin2(EPI_ACT, act_epi, R, b.Cout, ch, b.h.I, b.h.I, packed + k.h.f, cx, b.a.I, b.s.I, packed + k.s.f, A, st));
   if (act_out != act_epi) RES_LAUNCH(act_inplace_kernel, (int64_t)R * b.Cout, u.out, act_out, (int64_t)R * b.Cout);
   return 0;
+}
+
+// upsample x2 + dec[6] on R images in one launch: y14 [R, 14, 14, 16] (dec[5]'s output after its ELU) -> logits [R, 784]
+int tail_fused(const Blk& b, const BlkPk& k, const float* params, const float* packed, const float* y14, int R, float* logits, hipStream_t st) {
+  hipLaunchKernelGGL(resconv_tail_kernel, dim3((unsigned)R), dim3(RT_THREADS), 0, st, y14, packed + k.a.weff, params + b.a.bias, packed + k.h.weff,
+                     packed + k.s.weff, packed + k.bsum, logits);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+// which tail the decode-only path of kind 12 runs (ardae_resconv_tail's variant 0): the fused kernel, unless ARDAE_RESCONV_TAIL_UNFUSED=1 under
+// ARDAE_DEBUG_KNOBS=1.  The mode-2 workspace of kind 12 is sized for the answer.
+bool tail_fused_default() {
+  const char* knob = debug_knob("ARDAE_RESCONV_TAIL_UNFUSED");
+  return !(knob && knob[0] == '1');
 }
 
 // scratch of one block's backward (reused from block to block) and the gradient destinations of its three operators
@@ -478,7 +584,8 @@ struct ResWs {
   float *zero;                                                      // zero noise for encode(std=0)
   struct HeadBuf { float *rba, *rbs, *hmid, *out; };                // kind 5, per head operator: per-image row biases [B,out] (concat), ResLinear hidden [R,out], output [R,out]
   std::vector<HeadBuf> hb; float* z;                                // z [R,zd]
-  float *mu0, *lv0r, *lv0, *z0, *rbh, *hh, *mu, *lvr, *lv;          // kind 6
+  float *mu0, *lv0r, *lv0, *z0, *rbh, *hh, *mu, *lvr, *lv;          // kind 6 (kind 12: mu, lv [B, zd])
+  float *eps, *kld, *dmu, *dlv;                                     // kind 12: the draw used, the KL rows [B], the head's backward seed
   // decoder (R images)
   std::vector<BlkBuf> db; float *d4, *u8, *c7, *u14, *u28;          // block buffers; NHWC 4x4x32, upsampled / cropped maps
   float *rec_row, *pri_row, *dlogit, *dzq;
@@ -499,8 +606,13 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
     for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.tb[i], bwd);
     W.flat = ws.take((size_t)B * 512);
     W.inp = W.tb.back().out;
-    W.zero = ws.take(R * (P.nd + P.zd));
-    if (P.kind == 5) {
+    if (P.kind != 12) W.zero = ws.take(R * (P.nd + P.zd));
+    if (P.kind == 12) {          // one draw per image (nz = 1); mode 0 ends at the trunk: encode_stats writes the caller's mu, lv
+      if (mode == 1) {
+        W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.z = ws.take(R * P.zd); W.eps = ws.take(R * P.zd); W.kld = ws.take(R);
+        W.dmu = ws.take(R * P.zd); W.dlv = ws.take(R * P.zd);
+      }
+    } else if (P.kind == 5) {
       W.hb.resize(P.head.size());
       for (size_t i = 0; i < P.head.size(); ++i) {
         const HeadOp& o = P.head[i];
@@ -516,7 +628,23 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
       W.z = ws.take(R * P.zd);
     }
   }
-  if (dec) {
+  if (dec && P.kind == 12 && mode == 2) {
+    // decode only, nothing is saved for a backward: ONE columns scratch (the widest block's) serves every conv block in turn, and with the fused
+    // tail neither u28 nor dec[6]'s buffers exist
+    const size_t nb = tail_fused_default() ? P.dec.size() - 1 : P.dec.size();
+    size_t cx = 0, ch = 0;
+    for (size_t i = 0; i < nb; ++i)
+      if (P.dec[i].conv) { cx = max_sz(cx, blk_rows(P.dec[i], (int)R) * P.dec[i].a.I); ch = max_sz(ch, blk_rows(P.dec[i], (int)R) * P.dec[i].h.I); }
+    float* colsx = ws.take(cx); float* colsh = ws.take(ch);
+    W.db.assign(P.dec.size(), BlkBuf{nullptr, nullptr, nullptr, nullptr});
+    for (size_t i = 0; i < nb; ++i) {
+      const Blk& b = P.dec[i];
+      W.db[i].colsx = b.conv ? colsx : nullptr; W.db[i].colsh = b.conv ? colsh : nullptr;
+      W.db[i].hmid = ws.take(blk_rows(b, (int)R) * b.Cout); W.db[i].out = ws.take(blk_rows(b, (int)R) * b.Cout);
+    }
+    W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32); W.c7 = ws.take(R * 49 * 32); W.u14 = ws.take(R * 196 * 32);
+    W.u28 = nb == P.dec.size() ? ws.take(R * 784 * 16) : nullptr;
+  } else if (dec) {
     W.db.resize(P.dec.size());
     for (size_t i = 0; i < P.dec.size(); ++i) blk_carve(P.dec[i], (int)R, ws, W.db[i], bwd);
     W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32); W.c7 = ws.take(R * 49 * 32); W.u14 = ws.take(R * 196 * 32); W.u28 = ws.take(R * 784 * 16);
@@ -554,8 +682,10 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
       if (o.concat) need += 2 * wgrad_scratch_floats(B, o.out, P.cdim);
       wsf = max_sz(wsf, need);
     }
-    wsf = max_sz(wsf, 2 * (wgrad_scratch_floats(Ri, P.hdim, P.hdim) + wgrad_scratch_floats(Ri, P.hdim, P.cdim + P.nd) + wgrad_scratch_floats(Ri, P.zd, P.hdim)) +
-                          3 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.hdim, P.cdim));
+    if (P.kind == 12) wsf = max_sz(wsf, 2 * wgrad_scratch_floats(Ri, P.zd, P.cdim));      // the two heads, one batch
+    else
+      wsf = max_sz(wsf, 2 * (wgrad_scratch_floats(Ri, P.hdim, P.hdim) + wgrad_scratch_floats(Ri, P.hdim, P.cdim + P.nd) + wgrad_scratch_floats(Ri, P.zd, P.hdim)) +
+                            3 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.hdim, P.cdim));
     W.wscratch_floats = wsf + 1024;
     W.wscratch = ws.take(W.wscratch_floats);
   }
@@ -649,7 +779,9 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
 }
 
 // decoder on R rows: z [R, zd] -> logits [R, 784]
-int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* z, int R, ResWs& W, float* logits, hipStream_t st) {
+// fused_tail (kind 12's decode-only path): the last upsampling and dec[6] as resconv_tail_kernel, which writes `logits` itself
+int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* z, int R, ResWs& W, float* logits, hipStream_t st,
+                bool fused_tail = false) {
   ARDAE_TRY(blk_fwd(P.dec[0], K.dec[0], params, packed, z, R, ACT_ELU, W.db[0], st));
   ARDAE_TRY(blk_fwd(P.dec[1], K.dec[1], params, packed, W.db[0].out, R, ACT_ELU, W.db[1], st));
   ARDAE_TRY(launch_nhwc_nchw(W.db[1].out, R, 16, 32, W.d4, true, st));                                    // view(-1, 32, 4, 4) -> NHWC
@@ -660,6 +792,7 @@ int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
   RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 196 * 32, W.c7, 7, 32, W.u14, (int64_t)R * 196 * 32);
   ARDAE_TRY(blk_fwd(P.dec[4], K.dec[4], params, packed, W.u14, R, ACT_ELU, W.db[4], st));
   ARDAE_TRY(blk_fwd(P.dec[5], K.dec[5], params, packed, W.db[4].out, R, ACT_ELU, W.db[5], st));
+  if (fused_tail) return tail_fused(P.dec[6], K.dec[6], params, packed, W.db[5].out, R, logits, st);
   RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, W.db[5].out, 14, 16, W.u28, (int64_t)R * 784 * 16);
   ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, W.u28, R, ACT_NONE, W.db[6], st));
   if (logits && logits != W.db[6].out) ARDAE_TRY(launch_copy(W.db[6].out, (size_t)R * 784, logits, st));
@@ -682,6 +815,53 @@ struct GradMap {
   }
   BlkGrad blk(const Blk& b, const BlkPk& k) { BlkGrad g; g.a = wn(b.a, k.a); g.h = wn(b.h, k.h); g.s = b.same ? g.h : wn(b.s, k.s); return g; }
 };
+
+// the decoder's backward on R rows from W.dlogit: every block's weight gradients into gm's scratch, dz (added to what the loss kernel left) in W.dzq
+int decoder_bwd(const ResLayout& P, const ResPacked& K, const float* packed, ResWs& W, int R, GradMap& gm, hipStream_t st) {
+  // ---- decoder backward (d_out ping-pongs between W.da and W.dbuf)
+  std::vector<BlkGrad> gd(P.dec.size());
+  for (size_t i = 0; i < P.dec.size(); ++i) gd[i] = gm.blk(P.dec[i], K.dec[i]);
+  ARDAE_TRY(blk_bwd(P.dec[6], K.dec[6], packed, W.u28, R, ACT_NONE, W.db[6], W.dlogit, W.da, W.sc, gd[6], W.wscratch, W.wscratch_floats, st));      // -> d u28 [R,28,28,16]
+  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 196 * 16, W.da, 14, 16, W.dbuf, (int64_t)R * 196 * 16);
+  ARDAE_TRY(blk_bwd(P.dec[5], K.dec[5], packed, W.db[4].out, R, ACT_ELU, W.db[5], W.dbuf, W.da, W.sc, gd[5], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(blk_bwd(P.dec[4], K.dec[4], packed, W.u14, R, ACT_ELU, W.db[4], W.da, W.dbuf, W.sc, gd[4], W.wscratch, W.wscratch_floats, st));          // -> d u14 [R,14,14,32]
+  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 49 * 32, W.dbuf, 7, 32, W.da, (int64_t)R * 49 * 32);                                                 // -> d c7
+  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 64 * 32, W.da, 7, 8, 32, W.dbuf, (int64_t)R * 64 * 32);                                                    // -> d (block 3 out) [R,8,8,32]
+  ARDAE_TRY(blk_bwd(P.dec[3], K.dec[3], packed, W.db[2].out, R, ACT_ELU, W.db[3], W.dbuf, W.da, W.sc, gd[3], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(blk_bwd(P.dec[2], K.dec[2], packed, W.u8, R, ACT_ELU, W.db[2], W.da, W.dbuf, W.sc, gd[2], W.wscratch, W.wscratch_floats, st));            // -> d u8
+  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 16 * 32, W.dbuf, 4, 32, W.da, (int64_t)R * 16 * 32);                                                 // -> d d4 (NHWC)
+  ARDAE_TRY(launch_nhwc_nchw(W.da, R, 16, 32, W.dbuf, false, st));                                                                                    // -> NCHW-flat [R,512]
+  ARDAE_TRY(blk_bwd(P.dec[1], K.dec[1], packed, W.db[0].out, R, ACT_ELU, W.db[1], W.dbuf, W.da, W.sc, gd[1], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(blk_bwd(P.dec[0], K.dec[0], packed, W.z, R, ACT_ELU, W.db[0], W.da, W.dbuf, W.sc, gd[0], W.wscratch, W.wscratch_floats, st));             // -> dz (decoder part) [R,zd]
+  ARDAE_TRY(launch_axpy(W.dbuf, (int64_t)R * P.zd, 1.f, W.dzq, st));                                                                                 // dz total in W.dzq
+  return 0;
+}
+
+// the trunk's backward on B images from W.dinp (the gradient at its output, after the ELU), then dL/dW -> dL/d(direction, scale) and the bias
+// gradients of every weight-normalised operator gm has handed out
+int trunk_wn_bwd(const ResLayout& P, const ResPacked& K, const float* packed, ResWs& W, int B, GradMap& gm, float grads_beta, hipStream_t st) {
+  // ---- trunk backward
+  std::vector<BlkGrad> gt(P.trunk.size());
+  for (size_t i = 0; i < P.trunk.size(); ++i) gt[i] = gm.blk(P.trunk[i], K.trunk[i]);
+  ARDAE_TRY(blk_bwd(P.trunk[5], K.trunk[5], packed, W.flat, B, ACT_ELU, W.tb[5], W.dinp, W.dflat, W.sc, gt[5], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(launch_nhwc_nchw(W.dflat, B, 16, 32, W.da, true, st));                                  // NCHW-flat gradient -> NHWC [B,4,4,32]
+  float *cur = W.da, *nxt = W.dbuf;
+  for (int i = 4; i >= 0; --i) {
+    const float* xin = i == 0 ? W.x2 : W.tb[i - 1].out;
+    ARDAE_TRY(blk_bwd(P.trunk[i], K.trunk[i], packed, xin, B, ACT_ELU, W.tb[i], cur, i == 0 ? nullptr : nxt, W.sc, gt[i], W.wscratch, W.wscratch_floats, st));
+    std::swap(cur, nxt);
+  }
+  // ---- dL/dW -> dL/d(direction, scale), bias gradients
+  for (size_t i0 = 0; i0 < gm.items.size(); i0 += WNB_MAX) {
+    WnBwdBatch bt;
+    bt.n = (int)std::min<size_t>(WNB_MAX, gm.items.size() - i0);
+    bt.beta = grads_beta;
+    for (int i = 0; i < bt.n; ++i) bt.it[i] = gm.items[i0 + i];
+    hipLaunchKernelGGL(wn_backward_kernel, dim3(32, bt.n), dim3(256), 0, st, bt);
+    ARDAE_LAUNCH_CHECK();
+  }
+  return 0;
+}
 
 // ================================================================================================ entry points
 size_t res_param_floats(const ardae_model_desc& d) { return res_desc_ok(d) ? 0 : ResLayout(d).total; }
@@ -777,22 +957,7 @@ int res_vae_backward(const ardae_model_desc& d, const float* params, const float
   gm.grads_beta = grads_beta;
   // loss gradients: d logits, dz = gscale beta z + dz_extra
   ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, R, nz, 784, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.dlogit, nullptr, W.dzq, st));
-  // ---- decoder backward (d_out ping-pongs between W.da and W.dbuf)
-  std::vector<BlkGrad> gd(P.dec.size());
-  for (size_t i = 0; i < P.dec.size(); ++i) gd[i] = gm.blk(P.dec[i], K.dec[i]);
-  ARDAE_TRY(blk_bwd(P.dec[6], K.dec[6], packed, W.u28, R, ACT_NONE, W.db[6], W.dlogit, W.da, W.sc, gd[6], W.wscratch, W.wscratch_floats, st));      // -> d u28 [R,28,28,16]
-  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 196 * 16, W.da, 14, 16, W.dbuf, (int64_t)R * 196 * 16);
-  ARDAE_TRY(blk_bwd(P.dec[5], K.dec[5], packed, W.db[4].out, R, ACT_ELU, W.db[5], W.dbuf, W.da, W.sc, gd[5], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(blk_bwd(P.dec[4], K.dec[4], packed, W.u14, R, ACT_ELU, W.db[4], W.da, W.dbuf, W.sc, gd[4], W.wscratch, W.wscratch_floats, st));          // -> d u14 [R,14,14,32]
-  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 49 * 32, W.dbuf, 7, 32, W.da, (int64_t)R * 49 * 32);                                                 // -> d c7
-  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 64 * 32, W.da, 7, 8, 32, W.dbuf, (int64_t)R * 64 * 32);                                                    // -> d (block 3 out) [R,8,8,32]
-  ARDAE_TRY(blk_bwd(P.dec[3], K.dec[3], packed, W.db[2].out, R, ACT_ELU, W.db[3], W.dbuf, W.da, W.sc, gd[3], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(blk_bwd(P.dec[2], K.dec[2], packed, W.u8, R, ACT_ELU, W.db[2], W.da, W.dbuf, W.sc, gd[2], W.wscratch, W.wscratch_floats, st));            // -> d u8
-  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 16 * 32, W.dbuf, 4, 32, W.da, (int64_t)R * 16 * 32);                                                 // -> d d4 (NHWC)
-  ARDAE_TRY(launch_nhwc_nchw(W.da, R, 16, 32, W.dbuf, false, st));                                                                                    // -> NCHW-flat [R,512]
-  ARDAE_TRY(blk_bwd(P.dec[1], K.dec[1], packed, W.db[0].out, R, ACT_ELU, W.db[1], W.dbuf, W.da, W.sc, gd[1], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(blk_bwd(P.dec[0], K.dec[0], packed, W.z, R, ACT_ELU, W.db[0], W.da, W.dbuf, W.sc, gd[0], W.wscratch, W.wscratch_floats, st));             // -> dz (decoder part) [R,zd]
-  ARDAE_TRY(launch_axpy(W.dbuf, (int64_t)R * P.zd, 1.f, W.dzq, st));                                                                                 // dz total in W.dzq
+  ARDAE_TRY(decoder_bwd(P, K, packed, W, R, gm, st));
   // ---- sampler backward -> W.dinp [B, cdim]
   WgradList wl(grads);              // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
   if (P.kind == 5) {
@@ -890,34 +1055,147 @@ int res_vae_backward(const ardae_model_desc& d, const float* params, const float
       ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, P.cdim, P.cdim, packed + K.efc.bi, W.dB1, P.nd, P.nd, packed + K.mu0.b, A, st)); }
     ARDAE_TRY(dense_bwd(ACT_NONE, B, P.cdim, W.dB2, P.nd, packed + K.lv0.b, part, W.dinp, st, part));       // V * 1 + Q
   }
-  // ---- trunk backward
-  std::vector<BlkGrad> gt(P.trunk.size());
-  for (size_t i = 0; i < P.trunk.size(); ++i) gt[i] = gm.blk(P.trunk[i], K.trunk[i]);
-  ARDAE_TRY(blk_bwd(P.trunk[5], K.trunk[5], packed, W.flat, B, ACT_ELU, W.tb[5], W.dinp, W.dflat, W.sc, gt[5], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(launch_nhwc_nchw(W.dflat, B, 16, 32, W.da, true, st));                                  // NCHW-flat gradient -> NHWC [B,4,4,32]
-  float *cur = W.da, *nxt = W.dbuf;
-  for (int i = 4; i >= 0; --i) {
-    const float* xin = i == 0 ? W.x2 : W.tb[i - 1].out;
-    ARDAE_TRY(blk_bwd(P.trunk[i], K.trunk[i], packed, xin, B, ACT_ELU, W.tb[i], cur, i == 0 ? nullptr : nxt, W.sc, gt[i], W.wscratch, W.wscratch_floats, st));
-    std::swap(cur, nxt);
-  }
-  // ---- dL/dW -> dL/d(direction, scale), bias gradients
-  for (size_t i0 = 0; i0 < gm.items.size(); i0 += WNB_MAX) {
-    WnBwdBatch bt;
-    bt.n = (int)std::min<size_t>(WNB_MAX, gm.items.size() - i0);
-    bt.beta = grads_beta;
-    for (int i = 0; i < bt.n; ++i) bt.it[i] = gm.items[i0 + i];
-    hipLaunchKernelGGL(wn_backward_kernel, dim3(32, bt.n), dim3(256), 0, st, bt);
-    ARDAE_LAUNCH_CHECK();
-  }
-  return 0;
+  return trunk_wn_bwd(P, K, packed, W, B, gm, grads_beta, st);
+}
+
+// ------------------------------------------------------------------------------------------------ kind 12: the Gaussian-posterior baseline
+GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f}; }
+
+// one draw per image; there is no sampler pair.  mode 2: B * nz decoded rows
+size_t resvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+  if (res_desc_ok(d)) return 0;
+  if (mode != 2 && (nz != 1 || mode == 3)) return 0;
+  return res_workspace(ResLayout(d), mode == 2 ? B * nz : B, 1, mode);
+}
+
+int resvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
+                  hipStream_t st, float*) {
+  ResEntry entry(d, workspace, wsf, R, 1, 2);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
+  return decoder_fwd(P, K, params, packed, z, R, W, out0, st, tail_fused_default());
 }
 
 }  // namespace
 
+int resvae_desc_check(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 12 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
+  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind 12, got %d", d->flags);
+  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTResConvVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
+  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 12, got %d", d->n_layers);
+  ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
+  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 12 takes ELU only (--model-nonlin elu; models/vae/resconv.py:145 asserts it), got activation %d", d->act);
+  return 0;
+}
+
+// The head at h = c_dim.  The recipe's 450 is no multiple of 4, so gauss_head_kernel reads its rows float by float there: measured at
+// 128 x 450 -> 2 x 32 it loses to the unfused launches (README), which are this kind's default; variant 1 stays callable.
+bool resvae_head_fused_ok(const ardae_model_desc&) { return false; }
+
+int resvae_head(const ardae_model_desc& d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
+                uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld, hipStream_t st) {
+  const ResLayout P(d);
+  return gauss_head_fwd(head_of(P, ResPacked(P)), resvae_head_fused_ok(d), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z, eps_out,
+                        kld, st);
+}
+
+int resvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
+                        float* mu_out, float* lv_out, hipStream_t st) {
+  ResEntry entry(d, workspace, wsf, B, 1, 0);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
+  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, W.inp, P.cdim, P.cdim, packed + K.mu.f, params + P.mu.b, mu_out, st));
+  return dense_fwd(ACT_NONE, B, P.zd, W.inp, P.cdim, P.cdim, packed + K.lv.f, params + P.lv.b, lv_out, st);
+}
+
+int resvae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, DevFloat beta,
+                   uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t wsf, float* z_out, float* eps_out, float* losses,
+                   hipStream_t st) {
+  ResEntry entry(d, workspace, wsf, B, 1, 1);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
+  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+  ARDAE_TRY(gauss_head_fwd(head_of(P, K), resvae_head_fused_ok(d), params, packed, W.inp, eps, B, seed, offset, state, 0, W.mu, W.lv, W.z, W.eps, W.kld, st));
+  // the training forward keeps the unfused tail: the backward reads the columns it saves
+  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, B, W, nullptr, st));
+  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
+  ARDAE_TRY(launch_vae_loss_finalize(W.rec_row, W.kld, B, beta, losses, st));
+  ARDAE_TRY(launch_copy(W.z, (int64_t)B * P.zd, z_out, st));
+  if (eps_out) ARDAE_TRY(launch_copy(W.eps, (int64_t)B * P.zd, eps_out, st));
+  return 0;
+}
+
+int resvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
+                    float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
+  ResEntry entry(d, workspace, wsf, B, 1, 1);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+  const float c = loss_scale / (float)B;
+  GradMap gm{P, W.dweff, W.dbias, 0, {}, params, packed, grads};
+  gm.grads_beta = grads_beta;
+  // reconstruction gradients at the logits (the N(0, I) energy this kernel also knows is switched off: beta 0, no seed - W.dzq starts at zero)
+  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.dlogit, nullptr, W.dzq, st));
+  ARDAE_TRY(decoder_bwd(P, K, packed, W, B, gm, st));
+  ARDAE_TRY(gauss_head_seed(W.dzq, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
+  // the two heads: plain Linears, their gradients go to the gradient buffer itself; then both back into the trunk's output rows
+  WgradList wl(grads, grads_beta);
+  wl.push(B, P.zd, P.cdim, W.dmu, W.inp, P.cdim, grads + P.mu.w, P.cdim, grads + P.mu.b);
+  wl.push(B, P.zd, P.cdim, W.dlv, W.inp, P.cdim, grads + P.lv.w, P.cdim, grads + P.lv.b);
+  ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+  { LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
+    ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dmu, P.zd, P.zd, packed + K.mu.b, W.dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
+  return trunk_wn_bwd(P, K, packed, W, B, gm, grads_beta, st);
+}
+
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
 #ifndef __HIP_DEVICE_COMPILE__
 const Family RES_FAMILY = {res_param_floats, res_packed_floats, res_workspace_floats, res_pack, res_encode, res_decode, res_vae_forward, res_vae_backward};
+const Family RESVAE_FAMILY = {res_param_floats, res_packed_floats, resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward,
+                              vae_no_backward};
 #endif
 
 }  // namespace ardae
+
+using namespace ardae;
+
+extern "C" {
+
+// floats of the buffers the unfused launches keep: u28 and dec[6]'s columns, hidden map and output
+size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant) {
+  if (!d || d->kind != 12 || resvae_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
+  if (variant == 1 || (variant == 0 && tail_fused_default())) return 0;
+  const ResLayout P(*d);
+  Bump ws;
+  BlkBuf u;
+  ws.take((size_t)R * 784 * 16);
+  blk_carve(P.dec[6], R, ws, u, false);
+  return ws.off;
+}
+
+int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* y14, int R, int variant, float* workspace,
+                       size_t workspace_floats, float* logits, void* stream) {
+  ARDAE_CHECK_ARG(d != nullptr, "resconv_tail: desc is NULL");
+  ARDAE_CHECK_ARG(d->kind == 12, "resconv_tail: kind must be 12 (MNISTResConvVAE), got %d", d->kind);
+  ARDAE_TRY(resvae_desc_check(d));
+  ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "resconv_tail: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
+  ARDAE_CHECK_ARG(params && packed && y14 && logits, "resconv_tail: null pointer argument");
+  ARDAE_CHECK_ARG(R > 0 && R < (1 << 20), "resconv_tail: bad batch (R=%d)", R);
+  if (variant == 0) variant = tail_fused_default() ? 1 : 2;
+  hipStream_t st = (hipStream_t)stream;
+  const ResLayout P(*d);
+  const ResPacked K(P);
+  if (variant == 1) return tail_fused(P.dec[6], K.dec[6], params, packed, y14, R, logits, st);
+  const size_t need = ardae_resconv_tail_workspace_floats(d, R, 2);
+  ARDAE_CHECK_ARG(workspace, "resconv_tail: null pointer argument (the unfused launches need a workspace)");
+  ARDAE_CHECK_ARG(workspace_floats >= need, "resconv_tail: workspace too small (%zu < %zu floats)", workspace_floats, need);
+  Bump ws(workspace, workspace_floats);
+  float* u28 = ws.take((size_t)R * 784 * 16);
+  BlkBuf u;
+  blk_carve(P.dec[6], R, ws, u, false);
+  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, y14, 14, 16, u28, (int64_t)R * 784 * 16);
+  ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, u28, R, ACT_NONE, u, st));
+  return launch_copy(u.out, (size_t)R * 784, logits, st);
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 #include "mlp.h"
 #include "philox.h"
 #include "convvae.h"
+#include "resmodel.h"
 #include "vaemodel.h"
 
 namespace ardae {
@@ -349,17 +350,17 @@ int gauss_head_seed(const float* dz, const float* z, const float* mu, const floa
 // what ardae_model_encode / ardae_model_vae_* answer for the Gaussian-posterior kinds (Family members)
 int vae_no_encode(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, float*, size_t, float*, float*, hipStream_t,
                   const float*) {
-  set_last_error("model_encode: kinds 8 / 9 / 11 have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
+  set_last_error("model_encode: kinds 8 / 9 / 11 / 12 have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
   return -1;
 }
 int vae_no_forward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float*, size_t, float*, float*,
                    hipStream_t) {
-  set_last_error("model_vae_forward: kinds 8 / 9 / 11 are driven by ardae_vae_forward");
+  set_last_error("model_vae_forward: kinds 8 / 9 / 11 / 12 are driven by ardae_vae_forward");
   return -1;
 }
 int vae_no_backward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float, const float*, float*,
                     size_t, float*, float, hipStream_t) {
-  set_last_error("model_vae_backward: kinds 8 / 9 / 11 are driven by ardae_vae_backward");
+  set_last_error("model_vae_backward: kinds 8 / 9 / 11 / 12 are driven by ardae_vae_backward");
   return -1;
 }
 
@@ -387,8 +388,9 @@ size_t vae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) 
 // the kinds the ardae_vae_* entry points take, and their descriptor rules
 int vae_kind_check(const ardae_model_desc* d, const char* who) {
   ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
-  ARDAE_CHECK_ARG(d->kind == 8 || d->kind == 9 || d->kind == 11, "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), got %d", who, d->kind);
-  return d->kind == 11 ? convvae_desc_check(d) : vae_desc_check(d);
+  ARDAE_CHECK_ARG(d->kind == 8 || d->kind == 9 || d->kind == 11 || d->kind == 12,
+                  "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), or 12 (MNISTResConvVAE), got %d", who, d->kind);
+  return d->kind == 12 ? resvae_desc_check(d) : d->kind == 11 ? convvae_desc_check(d) : vae_desc_check(d);
 }
 
 // what every ardae_vae_* entry point checks before anything is launched
@@ -397,7 +399,9 @@ int vae_common(const ardae_model_desc* d, const float* params, const float* pack
   ARDAE_TRY(vae_kind_check(d, who));
   ARDAE_CHECK_ARG(params && packed && x && workspace, "%s: null pointer argument", who);
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "%s: bad batch (B=%d)", who, B);
-  const size_t need = d->kind == 11 ? CONVVAE_FAMILY.workspace_floats(*d, B, 1, mode) : vae_workspace_floats(*d, B, 1, mode);
+  const size_t need = d->kind == 12   ? RESVAE_FAMILY.workspace_floats(*d, B, 1, mode)
+                      : d->kind == 11 ? CONVVAE_FAMILY.workspace_floats(*d, B, 1, mode)
+                                      : vae_workspace_floats(*d, B, 1, mode);
   ARDAE_CHECK_ARG(wsf >= need, "%s: workspace too small (%zu < %zu floats)", who, wsf, need);
   return 0;
 }
@@ -410,6 +414,7 @@ int vae_forward_entry(const ardae_model_desc* d, const float* params, const floa
   ARDAE_CHECK_ARG(std::isfinite(loss_scale), "vae_forward: loss_scale must be finite");
   hipStream_t st = (hipStream_t)stream;
   if (d->kind == 11) return convvae_forward(*d, params, packed, x, eps, B, beta, seed, offset, state, workspace, wsf, z_out, eps_out, losses, st);
+  if (d->kind == 12) return resvae_forward(*d, params, packed, x, eps, B, beta, seed, offset, state, workspace, wsf, z_out, eps_out, losses, st);
   VaeEntry entry(*d, workspace, wsf, B, 1);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
@@ -432,6 +437,7 @@ int vae_backward_entry(const ardae_model_desc* d, const float* params, const flo
   ARDAE_CHECK_ARG(std::isfinite(loss_scale) && std::isfinite(grads_beta), "vae_backward: loss_scale and grads_beta must be finite");
   hipStream_t st = (hipStream_t)stream;
   if (d->kind == 11) return convvae_backward(*d, params, packed, x, B, beta, loss_scale, workspace, wsf, grads, grads_beta, st);
+  if (d->kind == 12) return resvae_backward(*d, params, packed, x, B, beta, loss_scale, workspace, wsf, grads, grads_beta, st);
   VaeEntry entry(*d, workspace, wsf, B, 1);
   auto& [P, K, ws, W] = entry;
   const float c = loss_scale / (float)B;
@@ -473,7 +479,7 @@ extern "C" {
 
 int ardae_vae_head_fused_ok(const ardae_model_desc* d) {
   if (!d || vae_kind_check(d, "vae_head_fused_ok") != 0) return 0;
-  return (d->kind == 11 ? convvae_head_fused_ok(*d) : head_fused_ok(*d)) ? 1 : 0;
+  return (d->kind == 12 ? resvae_head_fused_ok(*d) : d->kind == 11 ? convvae_head_fused_ok(*d) : head_fused_ok(*d)) ? 1 : 0;
 }
 
 int ardae_vae_kld_rows(const float* mu, const float* lv, int B, int z, float* kld, void* stream) {
@@ -491,6 +497,7 @@ int ardae_vae_head(const ardae_model_desc* d, const float* params, const float* 
   ARDAE_CHECK_ARG(params && packed && hid && mu && lv && z_out && kld, "vae_head: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "vae_head: bad batch (B=%d)", B);
   if (d->kind == 11) return convvae_head(*d, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
+  if (d->kind == 12) return resvae_head(*d, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
   const VaeLayout P(*d);
   const GaussHead H = head_of(P, VaePacked(P));
   return gauss_head_fwd(H, gauss_head_fused_ok(H), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld,
@@ -527,6 +534,7 @@ int ardae_vae_encode_stats(const ardae_model_desc* d, const float* params, const
   ARDAE_CHECK_ARG(mu_out && lv_out, "vae_encode_stats: null pointer argument (mu_out, lv_out)");
   hipStream_t st = (hipStream_t)stream;
   if (d->kind == 11) return convvae_encode_stats(*d, params, packed, x, B, workspace, workspace_floats_, mu_out, lv_out, st);
+  if (d->kind == 12) return resvae_encode_stats(*d, params, packed, x, B, workspace, workspace_floats_, mu_out, lv_out, st);
   VaeEntry entry(*d, workspace, workspace_floats_, B, 0);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");

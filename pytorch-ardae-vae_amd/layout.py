@@ -16,6 +16,32 @@ def _mlp(prefix, din, dh, dout, n_hidden, extra_in=0):
     return spec
 
 
+def _res_block(prefix, out, inn, conv):
+    """A weight-normalised residual block (models/layers2.py:50-93,237-352; models/layers.py:25-85 inside ResMLP): three operators, each with
+    direction / scale / bias."""
+    def wn(pre):
+        o_in = out if pre.endswith("h1.") else inn
+        return [(pre + "direction", (out, o_in, 3, 3) if conv else (out, o_in)), (pre + "scale", (out,)), (pre + "bias", (out,))]
+    a, b, c = ("conv_0h.", "conv_h1.", "conv_01.") if conv else ("dot_0h.", "dot_h1.", "dot_01.")
+    return wn(prefix + a) + wn(prefix + b) + wn(prefix + c)
+
+
+def _resconv_trunk(tp, cdim):
+    """ResConv2d 1 -> 16 s2, 16 -> 16, 16 -> 32 s2, 32 -> 32, 32 -> 32 s2, then ResLinear(512 -> c_dim) under the prefix `tp`"""
+    s = []
+    for i, (o, inn) in zip((0, 2, 4, 6, 8), ((16, 1), (16, 16), (32, 16), (32, 32), (32, 32))):
+        s += _res_block(f"{tp}{i}.", o, inn, True)
+    return s + _res_block(f"{tp}11.", cdim, 512, False)
+
+
+def _resconv_decoder(z_dim, cdim):
+    """models/vae/resconv.py:87-106: two ResLinears, five ResConv2d"""
+    s = _res_block("decode.dec.0.", cdim, z_dim, False) + _res_block("decode.dec.2.", 512, cdim, False)
+    for i, (o, inn) in zip((6, 8, 12, 14, 17), ((32, 32), (32, 32), (16, 32), (16, 16), (1, 16))):
+        s += _res_block(f"decode.dec.{i}.", o, inn, True)
+    return s
+
+
 def model_spec(kind, input_dim, noise_dim, h_dim, z_dim, n_layers, enc_type="res-wn-mlp"):
     if kind == "mnist":
         s = _mlp("encode.inp_encode.", input_dim, h_dim, h_dim, n_layers + 1)
@@ -33,20 +59,9 @@ def model_spec(kind, input_dim, noise_dim, h_dim, z_dim, n_layers, enc_type="res
               ("decode.deconv2.weight", (32, 16, 5, 5)), ("decode.deconv2.bias", (16,)),
               ("decode.reparam.logit_fn.weight", (16, 1, 5, 5)), ("decode.reparam.logit_fn.bias", (1,))]
     elif kind in ("resconv", "auxresconv"):
-        # weight-normalised residual blocks (models/layers2.py:50-93,237-352; models/layers.py:25-85 inside ResMLP): three operators per
-        # block, each with direction / scale / bias; ivae/resconv.py:81-125, vae/auxresconv.py:36-63,94,149-153, vae/resconv.py:89-109
-        def wn(prefix, out, inn, conv):
-            return [(prefix + "direction", (out, inn, 3, 3) if conv else (out, inn)), (prefix + "scale", (out,)), (prefix + "bias", (out,))]
-
-        def block(prefix, out, inn, conv):
-            a, b, c = ("conv_0h.", "conv_h1.", "conv_01.") if conv else ("dot_0h.", "dot_h1.", "dot_01.")
-            return wn(prefix + a, out, inn, conv) + wn(prefix + b, out, out, conv) + wn(prefix + c, out, inn, conv)
+        # weight-normalised residual blocks (_res_block): ivae/resconv.py:81-125, vae/auxresconv.py:36-63,94,149-153, vae/resconv.py:89-109
         cdim = 512 if kind == "resconv" else h_dim
-        tp = "encode.inp_encode." if kind == "resconv" else "encode.inp_encode.enc."
-        s = []
-        for i, (o, inn) in zip((0, 2, 4, 6, 8), ((16, 1), (16, 16), (32, 16), (32, 32), (32, 32))):
-            s += block(f"{tp}{i}.", o, inn, True)
-        s += block(f"{tp}11.", cdim, 512, False)
+        s = _resconv_trunk("encode.inp_encode." if kind == "resconv" else "encode.inp_encode.enc.", cdim)
         if kind == "resconv":
             s += resconv_head_spec(enc_type, n_layers, cdim + noise_dim, h_dim, z_dim)
         else:
@@ -55,9 +70,7 @@ def model_spec(kind, input_dim, noise_dim, h_dim, z_dim, n_layers, enc_type="res
                   ("encode.encode.fc.0.weight", (cdim, cdim + noise_dim)), ("encode.encode.fc.0.bias", (cdim,)),
                   ("encode.encode.reparam.mean_fn.weight", (z_dim, cdim)), ("encode.encode.reparam.mean_fn.bias", (z_dim,)),
                   ("encode.encode.reparam.logvar_fn.weight", (z_dim, cdim)), ("encode.encode.reparam.logvar_fn.bias", (z_dim,))]
-        s += block("decode.dec.0.", cdim, z_dim, False) + block("decode.dec.2.", 512, cdim, False)
-        for i, (o, inn) in zip((6, 8, 12, 14, 17), ((32, 32), (32, 32), (16, 32), (16, 16), (1, 16))):
-            s += block(f"decode.dec.{i}.", o, inn, True)
+        s += _resconv_decoder(z_dim, cdim)
     elif kind == "toy":
         s = _mlp("encode.inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)
         s += _mlp("encode.fc.", h_dim, h_dim, z_dim, n_layers, extra_in=noise_dim)
@@ -132,6 +145,16 @@ def conv_vae_spec(z_dim):
     return s + [("decode.deconv1.weight", (32, 32, 5, 5)), ("decode.deconv1.bias", (32,)),
                 ("decode.deconv2.weight", (32, 16, 5, 5)), ("decode.deconv2.bias", (16,)),
                 ("decode.reparam.logit_fn.weight", (16, 1, 5, 5)), ("decode.reparam.logit_fn.bias", (1,))]
+
+
+def resconv_vae_spec(z_dim, c_dim):
+    """The residual-conv Gaussian-posterior baseline of vae.py (models/vae/resconv.py:26-148, `--model resconv`; 28 x 28 x 1): the weight-normalised
+    trunk of the 'auxresconv' implicit model as `encode.enc.*` (width c_dim), a NormalDistributionLinear head and that model's decoder.
+    ardae_model_desc.kind 12."""
+    return (_resconv_trunk("encode.enc.", c_dim)
+            + [("encode.reparam.mean_fn.weight", (z_dim, c_dim)), ("encode.reparam.mean_fn.bias", (z_dim,)),
+               ("encode.reparam.logvar_fn.weight", (z_dim, c_dim)), ("encode.reparam.logvar_fn.bias", (z_dim,))]
+            + _resconv_decoder(z_dim, c_dim))
 
 
 def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):

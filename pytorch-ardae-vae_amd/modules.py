@@ -6,6 +6,7 @@
     net.MLPGradDAE / net.MLPResDAE       <- models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90
     net.MNISTVAE / net.ToyVAE            <- models/vae/mnist.py:99-220, models/vae/toy.py:99-213 (the Gaussian-posterior baselines of vae.py)
     net.MNISTConvVAE                     <- models/vae/conv.py:138-260 (`vae.py --model conv`)
+    net.MNISTResConvVAE                  <- models/vae/resconv.py:122-240 (`vae.py --model resconv`)
 
 Same constructor kwargs, same `state_dict()` keys and `[out, in]` layouts (reference checkpoints load), same method
 names and argument meaning, same exception types.  Parameters are `nn.Parameter` views into ONE flat fp32 buffer
@@ -149,7 +150,7 @@ def _f32c(t):
 
 
 KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7,      # ardae_model_desc.kind
-            "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11}                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
+            "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11, "vae_resconv": 12}                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
 AUX_KINDS = ("auxmnist", "auxconv", "auxresconv", "auxtoy")                                                 # hierarchical samplers
 GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
 
@@ -469,6 +470,17 @@ class _VaeFn(torch.autograd.Function):
         return (None,) * 5 + tuple(mod.param_views(grads))
 
 
+def _weight_norm_init(spec, p):
+    """WNlinear / WNconv2d / WeightNormalizedLinear.reset_parameters (layers2.py:66-71,184-190, layers.py:40-45) on the weight-normalised operators
+    among the parameters p (under torch.no_grad()): direction and bias U(+-1/sqrt(in_features | in_channels)), scale 1."""
+    for name, t in p.items():
+        if name.endswith(".scale"):
+            t.fill_(1.0)
+        elif name.endswith(".direction") or (name[:-len("bias")] + "direction") in spec:
+            d = spec[name if name.endswith(".direction") else name[:-len("bias")] + "direction"]
+            t.uniform_(-1.0 / math.sqrt(d[1]), 1.0 / math.sqrt(d[1]))
+
+
 class ImplicitPosteriorVAE(FlatParamModule):
     _kind = None
     _packed_floats_fn, _pack_fn = "ardae_model_packed_floats", "ardae_model_pack"
@@ -505,15 +517,7 @@ class ImplicitPosteriorVAE(FlatParamModule):
         with torch.no_grad():
             p = dict(self.named_parameters())
             if self._kind in ("resconv", "auxresconv"):
-                # WNlinear / WNconv2d / WeightNormalizedLinear.reset_parameters (layers2.py:66-71,184-190, layers.py:40-45): direction and bias
-                # U(+-1/sqrt(in_features | in_channels)), scale 1; the plain nn.Linear layers of the aux sampler keep torch's default
-                spec = dict(self._spec)
-                for name, t in p.items():
-                    if name.endswith(".scale"):
-                        t.fill_(1.0)
-                    elif name.endswith(".direction") or (name[:-len("bias")] + "direction") in spec:
-                        d = spec[name if name.endswith(".direction") else name[:-len("bias")] + "direction"]
-                        t.uniform_(-1.0 / math.sqrt(d[1]), 1.0 / math.sqrt(d[1]))
+                _weight_norm_init(dict(self._spec), p)    # the plain nn.Linear layers of the aux sampler keep torch's default
                 return
             if self._kind == "auxmnist":                  # self.apply(weight_init) on the whole model (ivae/auxmnist.py:172-174)
                 if self.do_xavier:
@@ -914,15 +918,15 @@ class _GaussEncodeBox(_Box):
 
 
 class GaussianVAE(FlatParamModule):
-    """What MNISTVAE, ToyVAE and MNISTConvVAE share: ardae_model_desc kinds 8 / 9 / 11, an encoder with a Gaussian head and its analytic KL, the
+    """What MNISTVAE, ToyVAE, MNISTConvVAE and MNISTResConvVAE share: ardae_model_desc kinds 8 / 9 / 11 / 12, an encoder with a Gaussian head and its analytic KL, the
     decoders of the implicit models.  A family is its `_kind` and its `_param_spec()`.  There is no CPU path."""
-    _kind = None                 # "vae_mnist" | "vae_toy" | "vae_conv"
+    _kind = None                 # "vae_mnist" | "vae_toy" | "vae_conv" | "vae_resconv"
     _packed_floats_fn, _pack_fn = "ardae_model_packed_floats", "ardae_model_pack"
     return_samples = True        # forward() also returns the decoder sample / mean (one extra decoder pass); False: (None, None)
     noise_dim = 0
     _eval_groups = None          # GaussianIwaeEvaluator: (images per encoder / ELBO-decoder call, images per importance-sample decoder call); None: a chunk at once
 
-    def _build(self, energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers):
+    def _build(self, energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, flags=0):
         if energy_func is not normal_energy_func:
             raise NotImplementedError("only utils.normal_energy_func is implemented on the HIP path")
         if nonlinearity not in L.ACT or nonlinearity in ("none", None):
@@ -934,14 +938,14 @@ class GaussianVAE(FlatParamModule):
         self.input_dim, self.h_dim, self.z_dim = int(input_dim), int(h_dim), int(z_dim)
         self.latent_dim = self.z_dim
         self.nonlinearity, self.num_hidden_layers = nonlinearity, int(num_hidden_layers)
-        self._desc = L.ModelDesc(KIND_IDS[self._kind], self.input_dim, 0, self.h_dim, self.z_dim, self.num_hidden_layers, L.ACT[nonlinearity], 0)
+        self._desc = L.ModelDesc(KIND_IDS[self._kind], self.input_dim, 0, self.h_dim, self.z_dim, self.num_hidden_layers, L.ACT[nonlinearity], flags)
         self._abi = (self._desc,)
         self._build_params(self._param_spec(), {"encode": _GaussEncodeBox})
         object.__setattr__(self.encode, "_owner_ref", weakref.ref(self))
         self.reset_parameters()
 
     def _param_spec(self):
-        """Names and shapes in named_parameters() order (the two MLP families; MNISTConvVAE has its own)."""
+        """Names and shapes in named_parameters() order (the two MLP families; the conv families have their own)."""
         return layout.vae_spec(self._kind[len("vae_"):], self.input_dim, self.h_dim, self.z_dim, self.num_hidden_layers)
 
     _x = ImplicitPosteriorVAE._x
@@ -1057,6 +1061,42 @@ class MNISTConvVAE(GaussianVAE):
                     nn.init.xavier_uniform_(t) if t.dim() >= 2 else t.zero_()
             if self.do_m5bias:                              # vae/conv.py:167-168
                 p["decode.reparam.logit_fn.bias"].fill_(-5.0)
+
+
+class MNISTResConvVAE(GaussianVAE):
+    """models/vae/resconv.py::VAE (`vae.py --model resconv`, the "# resconv" baseline of run_vae_sbmnist.sh): the weight-normalised residual-conv trunk
+    of MNISTResConvAuxIPVAE (width c_dim) with a plain Gaussian head, and that model's decoder.  ELU only (vae/resconv.py:145), 28x28x1 only.
+    do_center=True feeds the trunk 2x - 1; vae.py builds `resconv` and `resconvct` alike with do_center=False (vae.py:171-193).
+    forward() takes x as [B, 784] or [B, 1, 28, 28] and returns the decoder sample / mean as [B, 784]."""
+    _kind = "vae_resconv"
+    # As for MNISTConvVAE every 3x3 convolution but the last stage is a linear on rows = images x positions whose kernel the library picks by the
+    # row count, so the evaluator runs fixed groups: the encoder and the ELBO pass's decoder on 64 images per call, the importance samples' decoder on
+    # 8.  The decode-only workspace of this kind (one columns scratch, the last stage fused) takes ~1.18e5 floats per decoded row against ~3.5e5 for
+    # the training carving: at k = 256 the 2048 rows of a call need 0.24 G floats, inside the default budget of 2^28; the training carving would
+    # allow 2 images.  Chunks are cut at multiples of 64.
+    _eval_groups = (64, 8)
+
+    def __init__(self, energy_func=normal_energy_func, input_height=28, input_channels=1, z_dim=32, c_dim=450, nonlinearity="elu", do_center=False,
+                 do_m5bias=False):
+        if input_height != 28 or input_channels != 1:
+            raise NotImplementedError("MNISTResConvVAE: the reference asserts 28x28x1 (models/vae/resconv.py:143-144)")
+        if nonlinearity != "elu":
+            raise NotImplementedError(f"MNISTResConvVAE: nonlinearity {nonlinearity!r}: the reference asserts 'elu' (models/vae/resconv.py:145)")
+        super().__init__()
+        self.input_height, self.input_channels, self.c_dim = input_height, input_channels, int(c_dim)
+        self.do_center, self.do_m5bias = bool(do_center), do_m5bias
+        self._build(energy_func, input_height * input_height * input_channels, c_dim, z_dim, nonlinearity, 1, 0 if do_center else L.MODEL_NO_CENTER)
+
+    def _param_spec(self):
+        return layout.resconv_vae_spec(self.z_dim, self.c_dim)
+
+    def reset_parameters(self):
+        self._default_init()                                # the two heads: nn.Linear's default
+        with torch.no_grad():
+            p = dict(self.named_parameters())
+            _weight_norm_init(dict(self._spec), p)
+            if self.do_m5bias:                              # vae/resconv.py:107-108
+                p["decode.dec.17.conv_01.bias"].normal_(-3.0, 0.0001)
 
 
 class ToyVAE(GaussianVAE):

@@ -1,7 +1,7 @@
 """The Gaussian-posterior baselines of the reference's second trainer, vae.py, on the device: one iteration of its loop (vae.py:396-417)
 as one captured unit, and its evaluate_iws (vae.py:342-377) in large chunks.
 
-    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE
+    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE
     eng = net.VaeEngine(model, net.VaeConfig(lr=1e-3, beta_init=1e-4, beta_annealing=50000), batch_size=128)
     for x in loader: eng.step(x)
     elbo, logprob = eng.evaluate_iws(x_valid, sample_size=512)
@@ -71,14 +71,15 @@ class GaussianIwaeEvaluator:
     at the end in an order that depends on N alone; there is no host read inside the walk.  Own draws take two Philox offsets per call
     from the host stream (the forward's, the importance samples'); a chunk reads its slice through `first_element`, so ELBO and bound do
     not depend on the chunk length, to the bit - given that a row's bits do not depend on the rows per call, which holds for the MLP families'
-    layers.  Where it does not (MNISTConvVAE: the library picks the kernel of every conv-as-linear by the row count), the model names fixed
+    layers.  Where it does not (MNISTConvVAE, MNISTResConvVAE: the library picks the kernel of every conv-as-linear by the row count), the model names fixed
     groups, `_eval_groups = (G, g)`: the encoder and the ELBO pass's decoder run on G images per call, the importance samples' decoder on g
     images per call, and chunks are whole multiples of G - so every call sees the same rows under any budget.  Injected draws: fwd_eps
     [N, z], eps [N, k, z].  There is no covariance fit and no Cholesky on this path (iwae.IwaeEvaluator is the implicit models')."""
 
     def __init__(self, model, sample_size, max_workspace_floats=1 << 28):
         if not isinstance(model, GaussianVAE):
-            raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE (the implicit models: net.IwaeEvaluator)")
+            raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE (the implicit models: "
+                            "net.IwaeEvaluator)")
         self.model, self.k, self.budget = model, int(sample_size), int(max_workspace_floats)
         if self.k < 1:
             raise ValueError(f"sample_size must be positive (got {sample_size})")
@@ -201,8 +202,8 @@ class VaeEngine:
 
     def __init__(self, model, cfg: VaeConfig, batch_size, graph=True):
         if not isinstance(model, GaussianVAE):
-            raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE); the implicit models take "
-                            "net.ArdaeEngine")
+            raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE); the "
+                            "implicit models take net.ArdaeEngine")
         if not isinstance(cfg, VaeConfig):
             raise TypeError(f"VaeEngine takes a VaeConfig, not a {type(cfg).__name__}")
         model._require_gpu()
