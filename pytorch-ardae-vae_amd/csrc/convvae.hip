@@ -1,9 +1,9 @@
 // The conv Gaussian-posterior baseline (vae.py --model conv; ardae_model_desc.kind 11: models/vae/conv.py::VAE), joined from pieces the other
-// families own - no kernel of its own:
+// families own - no kernel of its own, and of the algorithm only what ConvVaeTraits says (the rest is csrc/vaemodel.h's, shared by every Gaussian kind):
 //
 //   per image (B rows):  x2 = 2x - 1;  h3 = trunk(x2) (conv 1 -> 16 -> 32 -> 32, k5 s2 p2: csrc/convmodel.hip);  hid = act(F h3 + f)  [B, 800]
-//                        mu, lv, z, kld: the Gaussian head on hid - two MFMA linears and one tail launch (head_fwd below; csrc/vaemodel.hip:
-//                        the draw keying and the KL in double of kinds 8 / 9)
+//                        mu, lv, z, kld: the Gaussian head on hid - two MFMA linears and one tail launch (gauss_head_fwd's tail form,
+//                        csrc/vaemodel.hip: the draw keying and the KL in double of kinds 8 / 9)
 //                        logit = Decoder(z) (models/vae/conv.py:79-136, the decoder of kinds 2 / 4);  recon = BCE-with-logits over 784 pixels
 //   losses = {mean_b(recon_b + beta kld_b), mean recon, mean kld}    (vae/conv.py:170-201)
 // Backward (c = loss_scale / B): the reconstruction seed, the decoder down to dz, the head's closed form (dmu, dlv), both heads back into
@@ -65,8 +65,6 @@ void carve(const ConvVaeLayout& P, const ConvVaePacked&, Bump& ws, int B, int mo
 }
 using ConvVaeEntry = Entry<ConvVaeLayout, ConvVaePacked, ConvVaeWs>;
 
-GaussHead head_of(const ConvVaeLayout& P, const ConvVaePacked& K) { return GaussHead{800, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f}; }
-
 // every weight-gradient problem of the backward: the decoder's eight, the two heads, fc, the three convs
 void convvae_wgrads(const ConvVaeLayout& P, const ConvVaeWs& W, int B, WgradList& wl, Bump& ws) {
   const ConvWs& C = W.C;
@@ -91,14 +89,6 @@ size_t convvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mo
   return ws.off;
 }
 
-// x2 = 2x - 1, the trunk, hid = act(fc(h3))
-int encoder_fwd(const ConvVaeLayout& P, const ConvVaePacked& K, const float* params, const float* packed, const float* x, int B, ConvWs& C,
-                hipStream_t st) {
-  ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, C.x2, st));           // vae/conv.py:64
-  ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, C.x2, C.cols, C.hcv, C.inp, B, P.act, st));
-  return dense_fwd(P.act, B, 800, C.inp, 512, 512, packed + K.fc_f, params + P.fc.b, C.t1, st);
-}
-
 int convvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
                    hipStream_t st, float*) {
   ConvVaeEntry entry(d, workspace, wsf, R, 2);
@@ -108,8 +98,7 @@ int convvae_decode(const ardae_model_desc& d, const float* params, const float* 
   return launch_copy(W.C.logit, (int64_t)R * 784, out0, st);
 }
 
-}  // namespace
-
+// the descriptor rules of kind 11 (input_dim 784, h_dim 800, n_layers 1, noise_dim 0, flags 0, z_dim >= 1, any activation but NONE)
 int convvae_desc_check(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 11 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
   ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kind 11, got %d", d->flags);
@@ -121,86 +110,56 @@ int convvae_desc_check(const ardae_model_desc* d) {
   return 0;
 }
 
-// The head at h = 800.  gauss_head_kernel (one serial 800-long FMA chain per output, 16 workgroups at 128 rows) loses here: 51.0 us against 19.8 us
-// for the five unfused launches at 128 x 800 -> 2 x 32.  So this family's fused variant keeps the two products on the MFMA
-// linears and fuses what is left - the draw, the reparameterisation and the KL rows - into ONE launch (gauss_head_tail): three launches in place
-// of five, and bit for bit the unfused head's outputs, whose launches and expressions it shares.  Where it is the default: z <= 64 (the tail's LDS).
-bool convvae_head_fused_ok(const ardae_model_desc& d) { return d.z_dim >= 1 && d.z_dim <= 64; }
-
-// variant 0: the library's choice (fused where convvae_head_fused_ok, unless the debug knob says otherwise), 1: fused, 2: unfused
-static int head_fwd(const ardae_model_desc& d, const GaussHead& H, const float* params, const float* packed, const float* hid, const float* eps, int B,
-                    uint64_t seed, uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld,
-                    hipStream_t st) {
-  if (variant == 0) {
-    const char* knob = debug_knob("ARDAE_VAE_HEAD_UNFUSED");
-    variant = (convvae_head_fused_ok(d) && !(knob && knob[0] == '1')) ? 1 : 2;
+// What gauss_vae_forward / _backward / _encode_stats (csrc/vaemodel.h) need to know of this family.
+struct ConvVaeTraits {
+  using Layout = ConvVaeLayout; using Packed = ConvVaePacked; using Entry = ConvVaeEntry;
+  struct Grads { float* grads; float beta; };
+  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, mode); }
+  // The head at h = 800.  gauss_head_kernel (one serial 800-long FMA chain per output, 16 workgroups at 128 rows) loses here: 51.0 us against
+  // 19.8 us for the five unfused launches at 128 x 800 -> 2 x 32.  So this family's fused form is the tail form: the two
+  // products stay on the MFMA linears and what is left - the draw, the reparameterisation and the KL rows - is ONE launch: three launches in place
+  // of five, and bit for bit the unfused head's outputs, whose launches and expressions it shares.  Where it is the default: z <= 64 (the tail's LDS).
+  static GaussHead head_of(const ConvVaeLayout& P, const ConvVaePacked& K) {
+    return GaussHead{800, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f, true, P.zd >= 1 && P.zd <= 64};
   }
-  if (variant == 2) return gauss_head_fwd(H, false, params, packed, hid, eps, B, seed, offset, state, 2, mu, lv, z, eps_out, kld, st);
-  ARDAE_CHECK_ARG(gauss_head_fused_can(H), "vae_head: the fused head takes 1 <= z_dim <= 64 (got %d)", H.zd);
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.mean_f, params + H.mean.b, mu, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.logvar_f, params + H.logvar.b, lv, st));
-  return gauss_head_tail(mu, lv, eps, B, H.zd, seed, offset, state, z, eps_out, kld, st);
-}
+  static const float* hid(const ConvVaeWs& W) { return W.C.t1; }
+  static GaussBufs bufs(const ConvVaeWs& W) {
+    const ConvWs& C = W.C;
+    return {W.mu, W.lv, C.z, W.eps, W.kld, C.rec_row, C.pri_row, C.logit, nullptr, C.dlogit, nullptr, C.dzq, C.dz, W.dmu, W.dlv};
+  }
+  // x2 = 2x - 1, the trunk, hid = act(fc(h3))
+  static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
+    const ConvVaeLayout& P = e.P; const ConvVaePacked& K = e.K; ConvWs& C = e.W.C;
+    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, C.x2, st));           // vae/conv.py:64
+    ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, C.x2, C.cols, C.hcv, C.inp, B, P.act, st));
+    return dense_fwd(P.act, B, 800, C.inp, 512, 512, packed + K.fc_f, params + P.fc.b, C.t1, st);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
+    return conv_decode_fwd(e.P.dec, e.K.dec, params, packed, e.W.C.z, B, e.W.C, st);
+  }
+  static Grads grads_of(Entry&, const float*, const float*, float* grads, float grads_beta) { return {grads, grads_beta}; }
+  static int decoder_bwd(Entry& e, const float* packed, int B, Grads&, hipStream_t st) { return conv_decoder_bwd(e.P.dec, e.K.dec, packed, e.W.C, B, st); }
+  static int encoder_bwd(Entry& e, const float* packed, const float*, int B, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ConvWs& C = W.C;
+    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, C.t1, C.dt1, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, C.dt1, 800, 800, packed + K.fc_b, nullptr, C.dinp, st));   // fc backward-data; the trunk applies conv3's act'
+    ARDAE_TRY(trunk_bwd(K.conv_b, packed, C.dinp, C.dinp_t, C.hcv, C.dh3, C.dcols3, C.dh2, C.dcols2, C.dh1, B, P.act, st));
+    WgradList wl(g.grads, g.beta);
+    convvae_wgrads(P, W, B, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+    return wl.launch(st);
+  }
+};
 
-int convvae_head(const ardae_model_desc& d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
-                 uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld, hipStream_t st) {
-  const ConvVaeLayout P(d);
-  return head_fwd(d, head_of(P, ConvVaePacked(P)), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z, eps_out, kld, st);
-}
-
-int convvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
-                         float* mu_out, float* lv_out, hipStream_t st) {
-  ConvVaeEntry entry(d, workspace, wsf, B, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
-  ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, W.C, st));
-  // the two heads write the caller's buffers themselves: no draw, no sample
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, W.C.t1, 800, 800, packed + K.mean_f, params + P.mean.b, mu_out, st));
-  return dense_fwd(ACT_NONE, B, P.zd, W.C.t1, 800, 800, packed + K.logvar_f, params + P.logvar.b, lv_out, st);
-}
-
-int convvae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, DevFloat beta,
-                    uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t wsf, float* z_out, float* eps_out, float* losses,
-                    hipStream_t st) {
-  ConvVaeEntry entry(d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  ConvWs& C = W.C;
-  ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
-  ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, C, st));
-  ARDAE_TRY(head_fwd(d, head_of(P, K), params, packed, C.t1, eps, B, seed, offset, state, 0, W.mu, W.lv, C.z, W.eps, W.kld, st));
-  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, C.z, B, C, st));
-  ARDAE_TRY(launch_vae_loss(0, C.logit, nullptr, x, C.z, B, 1, 784, P.zd, 0.f, 0, 0.f, nullptr, C.rec_row, C.pri_row, nullptr, nullptr, nullptr, st));
-  ARDAE_TRY(launch_vae_loss_finalize(C.rec_row, W.kld, B, beta, losses, st));
-  ARDAE_TRY(launch_copy(C.z, (int64_t)B * P.zd, z_out, st));
-  if (eps_out) ARDAE_TRY(launch_copy(W.eps, (int64_t)B * P.zd, eps_out, st));
-  return 0;
-}
-
-int convvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
-                     float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  (void)params;
-  ConvVaeEntry entry(d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  ConvWs& C = W.C;
-  const float c = loss_scale / (float)B;
-  // reconstruction gradients at the logits (the N(0, I) energy this kernel also knows is switched off: beta 0, no seed)
-  ARDAE_TRY(launch_vae_loss(0, C.logit, nullptr, x, C.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, C.rec_row, C.pri_row, C.dlogit, nullptr, C.dzq, st));
-  ARDAE_TRY(conv_decoder_bwd(P.dec, K.dec, packed, C, B, st));
-  ARDAE_TRY(gauss_head_seed(C.dz, C.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
-  ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, C.t1, C.dt1, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, C.dt1, 800, 800, packed + K.fc_b, nullptr, C.dinp, st));   // fc backward-data; the trunk applies conv3's act'
-  ARDAE_TRY(trunk_bwd(K.conv_b, packed, C.dinp, C.dinp_t, C.hcv, C.dh3, C.dcols3, C.dh2, C.dcols2, C.dh1, B, P.act, st));
-  WgradList wl(grads, grads_beta);
-  convvae_wgrads(P, W, B, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  return wl.launch(st);
-}
+}  // namespace
 
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
+static const GaussFamily CONVVAE_GAUSS = gauss_family<ConvVaeTraits>(convvae_desc_check);
 const Family CONVVAE_FAMILY = {family_param_floats<ConvVaeLayout, ConvVaePacked>, family_packed_floats<ConvVaeLayout, ConvVaePacked>,
                                convvae_workspace_floats, family_pack<ConvVaeLayout, ConvVaePacked>, vae_no_encode, convvae_decode, vae_no_forward,
-                               vae_no_backward};
+                               vae_no_backward, &CONVVAE_GAUSS};
 #endif
 
 }  // namespace ardae

@@ -177,6 +177,7 @@ inline int noise_or_zero(const float*& noise, float* zero, size_t n, hipStream_t
 // ------------------------------------------------------------------------------------------------ the model families
 // One row of csrc/model.hip's table by kind (encode: hidden_out / raw0 and decode: out1 are NULL for the families that have no
 // such output / input).  Each family file defines its own.
+struct GaussFamily;   // csrc/vaemodel.h
 struct Family {
   size_t (*param_floats)(const ardae_model_desc&);
   size_t (*packed_floats)(const ardae_model_desc&);
@@ -190,7 +191,11 @@ struct Family {
                      DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
   int (*vae_backward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                       DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
+  const GaussFamily* gauss;   // the Gaussian-posterior kinds' descriptor rules and ardae_vae_* bodies; null for the implicit kinds
 };
+// the table (csrc/model.hip): the row of a kind, null where the number is not a kind; family(d) where the kind has been checked
+const Family* family_of(int kind);
+inline const Family& family(const ardae_model_desc* d) { return *family_of(d->kind); }
 
 // A family is a Layout (the Linears' offsets in the flat parameter buffer, from the desc) and a Packed (the panels' offsets in the
 // packed buffer, reserved on a PackList).  Where the pack launch is all a family's pack does, these three are its first members:

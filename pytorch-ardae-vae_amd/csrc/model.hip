@@ -69,12 +69,10 @@ struct ModelPacked {
 
 int desc_ok(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "model: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind >= 0 && d->kind <= 12 && d->kind != 10,
+  ARDAE_CHECK_ARG(family_of(d->kind) != nullptr,
                   "model: kind must be 0 (MNISTIPVAE), 1 (ToyIPVAE concat), 2 (ConvIPVAE), 3 (MNISTAuxIPVAE), 4 (MNISTConvAuxIPVAE), 5 (ResConvIPVAE), "
                   "6 (MNISTResConvAuxIPVAE), 7 (ToyAuxIPVAE), 8 (MNISTVAE), 9 (ToyVAE), 11 (MNISTConvVAE) or 12 (MNISTResConvVAE)");
-  if (d->kind == 12) return resvae_desc_check(d);
-  if (d->kind == 11) return convvae_desc_check(d);
-  if (d->kind >= 8) return vae_desc_check(d);      // the Gaussian-posterior baselines: no noise input, no flags
+  if (family(d).gauss) return family(d).gauss->desc_check(d);      // the Gaussian-posterior baselines: no noise input, their own rules
   ARDAE_CHECK_ARG((d->flags & ~(ARDAE_MODEL_NO_CENTER | ARDAE_MODEL_HEAD_MASK | ARDAE_MODEL_CLIPPED | ARDAE_MODEL_CLIP_MASK)) == 0 &&
                       ((d->kind == 5 || d->kind == 6) ? (d->flags & ARDAE_MODEL_CLIP_MASK) == 0
                                                       : ((d->kind == 3 || d->kind == 7) ? (d->flags & ~ARDAE_MODEL_CLIP_MASK) == 0 : d->flags == 0)),
@@ -294,14 +292,15 @@ const Family MLP_FAMILY = {family_param_floats<ModelLayout, ModelPacked>, family
                            family_pack<ModelLayout, ModelPacked>, mlp_encode, mlp_decode<ModelLayout, ModelPacked>, mlp_vae_forward, mlp_vae_backward};
 
 // ------------------------------------------------------------------------------------------------ the families, by kind
-// desc_ok() has checked the kind
-const Family& family(const ardae_model_desc* d) {
+}  // namespace
+
+// (host_util.h) the one table by kind; desc_ok() checks the kind against it
+const Family* family_of(int kind) {
   static const Family* const by_kind[13] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY,
                                             &VAE_FAMILY, &VAE_FAMILY, nullptr, &CONVVAE_FAMILY, &RESVAE_FAMILY};      // 10 is not a kind
-  return *by_kind[d->kind];
+  return kind >= 0 && kind <= 12 ? by_kind[kind] : nullptr;
 }
 
-}  // namespace
 }  // namespace ardae
 
 using namespace ardae;

@@ -448,6 +448,17 @@ struct ResPacked {
   explicit ResPacked(const ResLayout& P, PackList&& sizing = PackList()) : ResPacked(P, sizing) {}   // offsets only
 };
 
+// the descriptor rules of kind 12 (input_dim 784, noise_dim 0, h_dim = c_dim >= 1, z_dim >= 1, n_layers 1, ELU, flags within ARDAE_MODEL_NO_CENTER)
+int resvae_desc_check(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 12 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
+  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind 12, got %d", d->flags);
+  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTResConvVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
+  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 12, got %d", d->n_layers);
+  ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
+  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 12 takes ELU only (--model-nonlin elu; models/vae/resconv.py:145 asserts it), got activation %d", d->act);
+  return 0;
+}
+
 int res_desc_ok(const ardae_model_desc& d) {
   if (d.kind == 12) return resvae_desc_check(&d);
   ARDAE_CHECK_ARG(d.input_dim == 784 && d.noise_dim >= 1 && d.z_dim >= 1 && d.h_dim >= 1, "model: the residual-conv models are hard-wired to 28x28x1 inputs");
@@ -1059,8 +1070,6 @@ int res_vae_backward(const ardae_model_desc& d, const float* params, const float
 }
 
 // ------------------------------------------------------------------------------------------------ kind 12: the Gaussian-posterior baseline
-GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f}; }
-
 // one draw per image; there is no sampler pair.  mode 2: B * nz decoded rows
 size_t resvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   if (res_desc_ok(d)) return 0;
@@ -1076,83 +1085,52 @@ int resvae_decode(const ardae_model_desc& d, const float* params, const float* p
   return decoder_fwd(P, K, params, packed, z, R, W, out0, st, tail_fused_default());
 }
 
-}  // namespace
-
-int resvae_desc_check(const ardae_model_desc* d) {
-  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 12 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
-  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind 12, got %d", d->flags);
-  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTResConvVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
-  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 12, got %d", d->n_layers);
-  ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
-  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 12 takes ELU only (--model-nonlin elu; models/vae/resconv.py:145 asserts it), got activation %d", d->act);
-  return 0;
-}
-
-// The head at h = c_dim.  The recipe's 450 is no multiple of 4, so gauss_head_kernel reads its rows float by float there: measured at
-// 128 x 450 -> 2 x 32 it loses to the unfused launches (README), which are this kind's default; variant 1 stays callable.
-bool resvae_head_fused_ok(const ardae_model_desc&) { return false; }
-
-int resvae_head(const ardae_model_desc& d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
-                uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld, hipStream_t st) {
-  const ResLayout P(d);
-  return gauss_head_fwd(head_of(P, ResPacked(P)), resvae_head_fused_ok(d), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z, eps_out,
-                        kld, st);
-}
-
-int resvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
-                        float* mu_out, float* lv_out, hipStream_t st) {
-  ResEntry entry(d, workspace, wsf, B, 1, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
-  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, W.inp, P.cdim, P.cdim, packed + K.mu.f, params + P.mu.b, mu_out, st));
-  return dense_fwd(ACT_NONE, B, P.zd, W.inp, P.cdim, P.cdim, packed + K.lv.f, params + P.lv.b, lv_out, st);
-}
-
-int resvae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, DevFloat beta,
-                   uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t wsf, float* z_out, float* eps_out, float* losses,
-                   hipStream_t st) {
-  ResEntry entry(d, workspace, wsf, B, 1, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
-  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-  ARDAE_TRY(gauss_head_fwd(head_of(P, K), resvae_head_fused_ok(d), params, packed, W.inp, eps, B, seed, offset, state, 0, W.mu, W.lv, W.z, W.eps, W.kld, st));
+// What gauss_vae_forward / _backward / _encode_stats (csrc/vaemodel.h) need to know of kind 12.
+struct ResVaeTraits {
+  using Layout = ResLayout; using Packed = ResPacked; using Entry = ResEntry;
+  using Grads = GradMap;      // built before the decoder's backward, used again by the trunk's
+  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, 1, mode); }
+  // The head at h = c_dim.  The recipe's 450 is no multiple of 4, so gauss_head_kernel reads its rows float by float there: measured at
+  // 128 x 450 -> 2 x 32 it loses to the unfused launches (README), which are this kind's default; variant 1 stays callable.
+  static GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f, false, false}; }
+  static const float* hid(const ResWs& W) { return W.inp; }
+  static GaussBufs bufs(const ResWs& W) {      // the decoder's backward adds its dz to what the loss kernel left in dzq
+    return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dzq, W.dmu, W.dlv};
+  }
+  static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
+    return trunk_fwd(e.P, e.K, params, packed, x, B, e.W, st);
+  }
   // the training forward keeps the unfused tail: the backward reads the columns it saves
-  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, B, W, nullptr, st));
-  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
-  ARDAE_TRY(launch_vae_loss_finalize(W.rec_row, W.kld, B, beta, losses, st));
-  ARDAE_TRY(launch_copy(W.z, (int64_t)B * P.zd, z_out, st));
-  if (eps_out) ARDAE_TRY(launch_copy(W.eps, (int64_t)B * P.zd, eps_out, st));
-  return 0;
-}
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
+    return ardae::decoder_fwd(e.P, e.K, params, packed, e.W.z, B, e.W, nullptr, st);
+  }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* grads, float grads_beta) {
+    GradMap gm{e.P, e.W.dweff, e.W.dbias, 0, {}, params, packed, grads};
+    gm.grads_beta = grads_beta;
+    return gm;
+  }
+  static int decoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, B, gm, st); }
+  static int encoder_bwd(Entry& e, const float* packed, const float*, int B, GradMap& gm, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    // the two heads: plain Linears, their gradients go to the gradient buffer itself; then both back into the trunk's output rows
+    WgradList wl(gm.grads, gm.grads_beta);
+    wl.push(B, P.zd, P.cdim, W.dmu, W.inp, P.cdim, gm.grads + P.mu.w, P.cdim, gm.grads + P.mu.b);
+    wl.push(B, P.zd, P.cdim, W.dlv, W.inp, P.cdim, gm.grads + P.lv.w, P.cdim, gm.grads + P.lv.b);
+    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+    { LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
+      ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dmu, P.zd, P.zd, packed + K.mu.b, W.dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
+    return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
+  }
+};
 
-int resvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
-                    float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  ResEntry entry(d, workspace, wsf, B, 1, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  const float c = loss_scale / (float)B;
-  GradMap gm{P, W.dweff, W.dbias, 0, {}, params, packed, grads};
-  gm.grads_beta = grads_beta;
-  // reconstruction gradients at the logits (the N(0, I) energy this kernel also knows is switched off: beta 0, no seed - W.dzq starts at zero)
-  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.dlogit, nullptr, W.dzq, st));
-  ARDAE_TRY(decoder_bwd(P, K, packed, W, B, gm, st));
-  ARDAE_TRY(gauss_head_seed(W.dzq, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
-  // the two heads: plain Linears, their gradients go to the gradient buffer itself; then both back into the trunk's output rows
-  WgradList wl(grads, grads_beta);
-  wl.push(B, P.zd, P.cdim, W.dmu, W.inp, P.cdim, grads + P.mu.w, P.cdim, grads + P.mu.b);
-  wl.push(B, P.zd, P.cdim, W.dlv, W.inp, P.cdim, grads + P.lv.w, P.cdim, grads + P.lv.b);
-  ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-  { LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
-    ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dmu, P.zd, P.zd, packed + K.mu.b, W.dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
-  return trunk_wn_bwd(P, K, packed, W, B, gm, grads_beta, st);
-}
+}  // namespace
 
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
 #ifndef __HIP_DEVICE_COMPILE__
 const Family RES_FAMILY = {res_param_floats, res_packed_floats, res_workspace_floats, res_pack, res_encode, res_decode, res_vae_forward, res_vae_backward};
+static const GaussFamily RESVAE_GAUSS = gauss_family<ResVaeTraits>(resvae_desc_check);
 const Family RESVAE_FAMILY = {res_param_floats, res_packed_floats, resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward,
-                              vae_no_backward};
+                              vae_no_backward, &RESVAE_GAUSS};
 #endif
 
 }  // namespace ardae

@@ -1,5 +1,7 @@
 // Gaussian-posterior VAE baselines (vae.py; ardae_model_desc.kind 8: models/vae/mnist.py::VAE, 9: models/vae/toy.py::VAE), orchestrated
-// from the K1 / K6w kernels like csrc/model.hip, plus the one kernel the family adds: the fused Gaussian head.
+// from the K1 / K6w kernels like csrc/model.hip, plus the one kernel the family adds: the fused Gaussian head.  Also here, for every Gaussian kind
+// (11: csrc/convvae.hip, 12: csrc/resmodel.hip): the head's kernels and its one policy (gauss_head_fwd), and the ardae_vae_* entry points, which
+// validate and dispatch through the table's row (family(d).gauss); the algorithm they run is csrc/vaemodel.h's, over each family's traits.
 //
 //   per image (B rows):  xs = 2x - 1 (kind 8) | x (kind 9);  h = MLP_enc(xs)  (n_layers Linear -> act: layers.0 .. n-2, fc)
 //                        mu = M h + m;  lv = L h + l;  z = mu + exp(lv / 2) eps;  kld = -0.5 sum_c (1 + lv - mu^2 - exp(lv))   (utils/vae.py:78-92)
@@ -23,8 +25,6 @@
 #include "elementwise.h"
 #include "mlp.h"
 #include "philox.h"
-#include "convvae.h"
-#include "resmodel.h"
 #include "vaemodel.h"
 
 namespace ardae {
@@ -294,31 +294,36 @@ __global__ __launch_bounds__(IQ_THREADS) void vae_iwae_draw_kernel(const float* 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ the head, fused or not (vaemodel.h)
-// what the fused kernel can compute at all (ardae_vae_head's variant 1) ...
+// what the fused forms can compute at all (ardae_vae_head's variant 1) ...
 bool gauss_head_fused_can(const GaussHead& H) { return H.zd >= 1 && H.zd <= GH_ZMAX && H.h >= 1; }
-// ... and where it may be the default: where the rows of both head matrices start on 16 bytes (h a multiple of 4 and both parameter offsets
-// multiples of 4 floats - a z that is a multiple of 4, given such an h).  Elsewhere the kernel reads float by float and a narrow head
+// ... and where gauss_head_kernel may be the default: where the rows of both head matrices start on 16 bytes (h a multiple of 4 and both parameter
+// offsets multiples of 4 floats - a z that is a multiple of 4, given such an h).  Elsewhere the kernel reads float by float and a narrow head
 // leaves most of a workgroup idle: at the toy recipe's z = 2 it only ties with the unfused launches, which run there.
 bool gauss_head_fused_ok(const GaussHead& H) { return gauss_head_fused_can(H) && (H.h & 3) == 0 && (H.mean.w & 3) == 0 && (H.logvar.w & 3) == 0; }
 
-// variant 0: the library's choice (fused where `fused_default`, unless the debug knob says otherwise), 1: fused, 2: unfused
-int gauss_head_fwd(const GaussHead& H, bool fused_default, const float* params, const float* packed, const float* hid, const float* eps, int B,
-                   uint64_t seed, uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld,
-                   hipStream_t st) {
+// variant 0: the library's choice (fused where H.fused_default, unless the debug knob says otherwise), 1: fused, 2: unfused
+int gauss_head_fwd(const GaussHead& H, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
+                   uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld, hipStream_t st) {
   if (variant == 0) {
     const char* knob = debug_knob("ARDAE_VAE_HEAD_UNFUSED");
-    variant = (fused_default && !(knob && knob[0] == '1')) ? 1 : 2;
+    variant = (H.fused_default && !(knob && knob[0] == '1')) ? 1 : 2;
   }
-  if (variant == 1) {
-    ARDAE_CHECK_ARG(gauss_head_fused_can(H), "vae_head: the fused head takes 1 <= z_dim <= %d (got %d)", GH_ZMAX, H.zd);
+  if (variant == 1) ARDAE_CHECK_ARG(gauss_head_fused_can(H), "vae_head: the fused head takes 1 <= z_dim <= %d (got %d)", GH_ZMAX, H.zd);
+  else ARDAE_CHECK_ARG(eps || eps_out, "vae_head: the unfused head draws into eps_out (null pointer)");
+  if (variant == 1 && !H.tail) {
     hipLaunchKernelGGL(gauss_head_kernel, dim3((unsigned)ceil_div(B, GH_ROWS)), dim3(GH_THREADS), 0, st, hid, B, H.h, H.zd, params + H.mean.w,
                        params + H.mean.b, params + H.logvar.w, params + H.logvar.b, eps, seed, offset, (const StepState*)state, mu, lv, z, eps_out, kld);
     ARDAE_LAUNCH_CHECK();
     return 0;
   }
-  ARDAE_CHECK_ARG(eps || eps_out, "vae_head: the unfused head draws into eps_out (null pointer)");
   ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.mean_f, params + H.mean.b, mu, st));
   ARDAE_TRY(dense_fwd(ACT_NONE, B, H.zd, hid, H.h, H.h, packed + H.logvar_f, params + H.logvar.b, lv, st));
+  if (variant == 1) {      // the tail form: what is left after the two products, in one launch
+    hipLaunchKernelGGL(gauss_head_tail_kernel, dim3((unsigned)ceil_div(B, GH_ROWS)), dim3(GH_THREADS), 0, st, mu, lv, B, H.zd, eps, seed, offset,
+                       (const StepState*)state, z, eps_out, kld);
+    ARDAE_LAUNCH_CHECK();
+    return 0;
+  }
   if (!eps) {
     ARDAE_TRY(launch_philox_normal_at(eps_out, (int64_t)B * H.zd, seed, offset, state, 0, st));
     eps = eps_out;
@@ -331,15 +336,6 @@ int gauss_head_fwd(const GaussHead& H, bool fused_default, const float* params, 
   return 0;
 }
 
-int gauss_head_tail(const float* mu, const float* lv, const float* eps, int B, int zd, uint64_t seed, uint64_t offset, const void* state, float* z,
-                    float* eps_out, float* kld, hipStream_t st) {
-  ARDAE_CHECK_ARG(zd >= 1 && zd <= GH_ZMAX, "vae_head: the fused head takes 1 <= z_dim <= %d (got %d)", GH_ZMAX, zd);
-  hipLaunchKernelGGL(gauss_head_tail_kernel, dim3((unsigned)ceil_div(B, GH_ROWS)), dim3(GH_THREADS), 0, st, mu, lv, B, zd, eps, seed, offset,
-                     (const StepState*)state, z, eps_out, kld);
-  ARDAE_LAUNCH_CHECK();
-  return 0;
-}
-
 int gauss_head_seed(const float* dz, const float* z, const float* mu, const float* lv, int64_t n, float c, DevFloat beta, float* dmu, float* dlv,
                     hipStream_t st) {
   hipLaunchKernelGGL(gauss_head_seed_kernel, dim3(nblk(n)), dim3(256), 0, st, dz, z, mu, lv, n, c, beta.v, beta.p, dmu, dlv);
@@ -348,49 +344,87 @@ int gauss_head_seed(const float* dz, const float* z, const float* mu, const floa
 }
 
 // what ardae_model_encode / ardae_model_vae_* answer for the Gaussian-posterior kinds (Family members)
+#define GAUSS_KINDS "kinds 8 / 9 / 11 / 12"
 int vae_no_encode(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, float*, size_t, float*, float*, hipStream_t,
                   const float*) {
-  set_last_error("model_encode: kinds 8 / 9 / 11 / 12 have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
+  set_last_error("model_encode: " GAUSS_KINDS " have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
   return -1;
 }
 int vae_no_forward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float*, size_t, float*, float*,
                    hipStream_t) {
-  set_last_error("model_vae_forward: kinds 8 / 9 / 11 / 12 are driven by ardae_vae_forward");
+  set_last_error("model_vae_forward: " GAUSS_KINDS " are driven by ardae_vae_forward");
   return -1;
 }
 int vae_no_backward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float, const float*, float*,
                     size_t, float*, float, hipStream_t) {
-  set_last_error("model_vae_backward: kinds 8 / 9 / 11 / 12 are driven by ardae_vae_backward");
+  set_last_error("model_vae_backward: " GAUSS_KINDS " are driven by ardae_vae_backward");
   return -1;
 }
 
 namespace {
 
-GaussHead head_of(const VaeLayout& P, const VaePacked& K) { return GaussHead{P.h, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f}; }
-bool head_fused_ok(const ardae_model_desc& d) {
-  const VaeLayout P(d);
-  return gauss_head_fused_ok(head_of(P, VaePacked(P)));
-}
+// ------------------------------------------------------------------------------------------------ kinds 8 / 9: the traits and the family row
+struct VaeTraits {
+  using Layout = VaeLayout; using Packed = VaePacked; using Entry = VaeEntry;
+  struct Grads { float* grads; float beta; };
+  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, mode); }
+  static GaussHead head_of(const VaeLayout& P, const VaePacked& K) {
+    GaussHead H{P.h, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f, false, false};
+    H.fused_default = gauss_head_fused_ok(H);
+    return H;
+  }
+  static const float* hid(const VaeWs& W) { return W.e.back(); }
+  static GaussBufs bufs(const VaeWs& W) {
+    return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.D.o[0], W.D.o[1], W.D.dox[0], W.D.dox[1], W.D.dzq, W.D.dz, W.dmu, W.dlv};
+  }
+  // xs (kind 8: 2x - 1) and the encoder stack
+  static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    if (!P.toy) ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.xs, st));      // vae/mnist.py:54
+    return K.enc.fwd(params, packed, P.act, B, P.toy ? x : W.xs, W.e.data(), st);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
+    return e.K.dec.fwd(params, packed, e.P.act, B, e.W.z, e.W.D.hid.data(), e.W.D.o, st);
+  }
+  static Grads grads_of(Entry&, const float*, const float*, float* grads, float grads_beta) { return {grads, grads_beta}; }
+  static int decoder_bwd(Entry& e, const float* packed, int B, Grads&, hipStream_t st) { return e.K.dec.bwd(packed, e.P.act, B, e.W.D, st); }
+  static int encoder_bwd(Entry& e, const float* packed, const float* x, int B, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(dense_bwd2(P.act, B, P.h, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.e[P.nl], W.de[P.nl], st));
+    ARDAE_TRY(K.enc.bwd(packed, P.act, B, W.e.data(), W.de.data(), st));
+    WgradList wl(g.grads, g.beta);
+    vae_wgrads(P, K, W, x, B, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+    return wl.launch(st);
+  }
+};
 
-// xs (kind 8: 2x - 1) and the encoder stack; -> the stack's input
-int encoder_fwd(const VaeLayout& P, const VaePacked& K, const float* params, const float* packed, const float* x, int B, VaeWs& W, hipStream_t st) {
-  if (!P.toy) ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.xs, st));      // vae/mnist.py:54
-  return K.enc.fwd(params, packed, P.act, B, P.toy ? x : W.xs, W.e.data(), st);
-}
-
-// ------------------------------------------------------------------------------------------------ the family row (kinds 8 / 9)
 size_t vae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
   const VaeLayout P(d);
   if (mode == 2) return VaePacked(P).dec.decode_floats((size_t)B * nz);
   if (nz != 1 || mode == 3) return 0;         // one draw per image; there is no sampler pair
   return workspace_floats(P, B, mode);
 }
-// the kinds the ardae_vae_* entry points take, and their descriptor rules
+// the descriptor rules of kinds 8 / 9 (noise_dim 0, flags 0, 1 .. 4 layers, any activation but NONE)
+int vae_desc_check(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kinds 8 / 9 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
+  ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kinds 8 / 9, got %d", d->flags);
+  ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->z_dim >= 1 && d->n_layers >= 1 && d->n_layers <= 4, "model: bad dimensions");
+  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
+  return 0;
+}
+// (host pass only, as in csrc/auxmodel.hip)
+#ifndef __HIP_DEVICE_COMPILE__
+const GaussFamily VAE_GAUSS = gauss_family<VaeTraits>(vae_desc_check);
+#endif
+
+// ------------------------------------------------------------------------------------------------ the ardae_vae_* entry points, every Gaussian kind
+// the kinds they take (the rows of the table that have a GaussFamily), and the kind's descriptor rules
 int vae_kind_check(const ardae_model_desc* d, const char* who) {
   ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
-  ARDAE_CHECK_ARG(d->kind == 8 || d->kind == 9 || d->kind == 11 || d->kind == 12,
+  ARDAE_CHECK_ARG(family_of(d->kind) && family(d).gauss,
                   "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), or 12 (MNISTResConvVAE), got %d", who, d->kind);
-  return d->kind == 12 ? resvae_desc_check(d) : d->kind == 11 ? convvae_desc_check(d) : vae_desc_check(d);
+  return family(d).gauss->desc_check(d);
 }
 
 // what every ardae_vae_* entry point checks before anything is launched
@@ -399,9 +433,7 @@ int vae_common(const ardae_model_desc* d, const float* params, const float* pack
   ARDAE_TRY(vae_kind_check(d, who));
   ARDAE_CHECK_ARG(params && packed && x && workspace, "%s: null pointer argument", who);
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "%s: bad batch (B=%d)", who, B);
-  const size_t need = d->kind == 12   ? RESVAE_FAMILY.workspace_floats(*d, B, 1, mode)
-                      : d->kind == 11 ? CONVVAE_FAMILY.workspace_floats(*d, B, 1, mode)
-                                      : vae_workspace_floats(*d, B, 1, mode);
+  const size_t need = family(d).workspace_floats(*d, B, 1, mode);
   ARDAE_CHECK_ARG(wsf >= need, "%s: workspace too small (%zu < %zu floats)", who, wsf, need);
   return 0;
 }
@@ -412,22 +444,7 @@ int vae_forward_entry(const ardae_model_desc* d, const float* params, const floa
   ARDAE_TRY(vae_common(d, params, packed, x, B, workspace, wsf, 1, "vae_forward"));
   ARDAE_CHECK_ARG(z_out && losses, "vae_forward: null pointer argument (z_out, losses)");
   ARDAE_CHECK_ARG(std::isfinite(loss_scale), "vae_forward: loss_scale must be finite");
-  hipStream_t st = (hipStream_t)stream;
-  if (d->kind == 11) return convvae_forward(*d, params, packed, x, eps, B, beta, seed, offset, state, workspace, wsf, z_out, eps_out, losses, st);
-  if (d->kind == 12) return resvae_forward(*d, params, packed, x, eps, B, beta, seed, offset, state, workspace, wsf, z_out, eps_out, losses, st);
-  VaeEntry entry(*d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
-  ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, W, st));
-  const GaussHead H = head_of(P, K);
-  ARDAE_TRY(gauss_head_fwd(H, gauss_head_fused_ok(H), params, packed, W.e[P.nl], eps, B, seed, offset, state, 0, W.mu, W.lv, W.z, W.eps, W.kld, st));
-  ARDAE_TRY(K.dec.fwd(params, packed, P.act, B, W.z, W.D.hid.data(), W.D.o, st));
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, B, 1, P.D, P.zd, 0.f, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr,
-                            nullptr, st));
-  ARDAE_TRY(launch_vae_loss_finalize(W.rec_row, W.kld, B, beta, losses, st));
-  ARDAE_TRY(launch_copy(W.z, (int64_t)B * P.zd, z_out, st));
-  if (eps_out) ARDAE_TRY(launch_copy(W.eps, (int64_t)B * P.zd, eps_out, st));
-  return 0;
+  return family(d).gauss->forward(*d, params, packed, x, eps, B, beta, seed, offset, state, workspace, wsf, z_out, eps_out, losses, (hipStream_t)stream);
 }
 
 int vae_backward_entry(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
@@ -435,40 +452,16 @@ int vae_backward_entry(const ardae_model_desc* d, const float* params, const flo
   ARDAE_TRY(vae_common(d, params, packed, x, B, workspace, wsf, 1, "vae_backward"));
   ARDAE_CHECK_ARG(grads, "vae_backward: null pointer argument (grads)");
   ARDAE_CHECK_ARG(std::isfinite(loss_scale) && std::isfinite(grads_beta), "vae_backward: loss_scale and grads_beta must be finite");
-  hipStream_t st = (hipStream_t)stream;
-  if (d->kind == 11) return convvae_backward(*d, params, packed, x, B, beta, loss_scale, workspace, wsf, grads, grads_beta, st);
-  if (d->kind == 12) return resvae_backward(*d, params, packed, x, B, beta, loss_scale, workspace, wsf, grads, grads_beta, st);
-  VaeEntry entry(*d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  const float c = loss_scale / (float)B;
-  const int64_t n = (int64_t)B * P.zd;
-  // reconstruction gradients at the decoder heads (the N(0, I) energy this kernel also knows is switched off: beta 0, no seed)
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, B, 1, P.D, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.D.dox[0], W.D.dox[1],
-                            W.D.dzq, st));
-  ARDAE_TRY(K.dec.bwd(packed, P.act, B, W.D, st));
-  ARDAE_TRY(gauss_head_seed(W.D.dz, W.z, W.mu, W.lv, n, c, beta, W.dmu, W.dlv, st));
-  ARDAE_TRY(dense_bwd2(P.act, B, P.h, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.e[P.nl], W.de[P.nl], st));
-  ARDAE_TRY(K.enc.bwd(packed, P.act, B, W.e.data(), W.de.data(), st));
-  WgradList wl(grads, grads_beta);
-  vae_wgrads(P, K, W, x, B, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  return wl.launch(st);
+  return family(d).gauss->backward(*d, params, packed, x, B, beta, loss_scale, workspace, wsf, grads, grads_beta, (hipStream_t)stream);
 }
 
 }  // namespace
 
-int vae_desc_check(const ardae_model_desc* d) {
-  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kinds 8 / 9 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
-  ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kinds 8 / 9, got %d", d->flags);
-  ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->z_dim >= 1 && d->n_layers >= 1 && d->n_layers <= 4, "model: bad dimensions");
-  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
-  return 0;
-}
-
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
 const Family VAE_FAMILY = {family_param_floats<VaeLayout, VaePacked>, family_packed_floats<VaeLayout, VaePacked>, vae_workspace_floats,
-                           family_pack<VaeLayout, VaePacked>, vae_no_encode, mlp_decode<VaeLayout, VaePacked>, vae_no_forward, vae_no_backward};
+                           family_pack<VaeLayout, VaePacked>, vae_no_encode, mlp_decode<VaeLayout, VaePacked>, vae_no_forward, vae_no_backward,
+                           &VAE_GAUSS};
 #endif
 
 }  // namespace ardae
@@ -479,7 +472,7 @@ extern "C" {
 
 int ardae_vae_head_fused_ok(const ardae_model_desc* d) {
   if (!d || vae_kind_check(d, "vae_head_fused_ok") != 0) return 0;
-  return (d->kind == 12 ? resvae_head_fused_ok(*d) : d->kind == 11 ? convvae_head_fused_ok(*d) : head_fused_ok(*d)) ? 1 : 0;
+  return family(d).gauss->head_fused_ok(*d) ? 1 : 0;
 }
 
 int ardae_vae_kld_rows(const float* mu, const float* lv, int B, int z, float* kld, void* stream) {
@@ -496,12 +489,7 @@ int ardae_vae_head(const ardae_model_desc* d, const float* params, const float* 
   ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "vae_head: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
   ARDAE_CHECK_ARG(params && packed && hid && mu && lv && z_out && kld, "vae_head: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "vae_head: bad batch (B=%d)", B);
-  if (d->kind == 11) return convvae_head(*d, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
-  if (d->kind == 12) return resvae_head(*d, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
-  const VaeLayout P(*d);
-  const GaussHead H = head_of(P, VaePacked(P));
-  return gauss_head_fwd(H, gauss_head_fused_ok(H), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld,
-                        (hipStream_t)stream);
+  return family(d).gauss->head(*d, params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z_out, eps_out, kld, (hipStream_t)stream);
 }
 
 int ardae_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* eps, int B, float beta,
@@ -532,16 +520,7 @@ int ardae_vae_encode_stats(const ardae_model_desc* d, const float* params, const
                            size_t workspace_floats_, float* mu_out, float* lv_out, void* stream) {
   ARDAE_TRY(vae_common(d, params, packed, x, B, workspace, workspace_floats_, 0, "vae_encode_stats"));
   ARDAE_CHECK_ARG(mu_out && lv_out, "vae_encode_stats: null pointer argument (mu_out, lv_out)");
-  hipStream_t st = (hipStream_t)stream;
-  if (d->kind == 11) return convvae_encode_stats(*d, params, packed, x, B, workspace, workspace_floats_, mu_out, lv_out, st);
-  if (d->kind == 12) return resvae_encode_stats(*d, params, packed, x, B, workspace, workspace_floats_, mu_out, lv_out, st);
-  VaeEntry entry(*d, workspace, workspace_floats_, B, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
-  ARDAE_TRY(encoder_fwd(P, K, params, packed, x, B, W, st));
-  // the two heads write the caller's buffers themselves: no draw, no sample
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.zd, W.e[P.nl], P.h, P.h, packed + K.mean_f, params + P.mean.b, mu_out, st));
-  return dense_fwd(ACT_NONE, B, P.zd, W.e[P.nl], P.h, P.h, packed + K.logvar_f, params + P.logvar.b, lv_out, st);
+  return family(d).gauss->encode_stats(*d, params, packed, x, B, workspace, workspace_floats_, mu_out, lv_out, (hipStream_t)stream);
 }
 
 int ardae_vae_iwae_draw(const float* mu, const float* lv, const float* eps, int B, int k, int z, uint64_t seed, uint64_t offset,
