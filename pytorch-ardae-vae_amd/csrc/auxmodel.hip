@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "auxmodel.h"
+#include "ipmodel.h"
 #include "elementwise.h"
 #include "mlp.h"
 
@@ -110,37 +111,6 @@ void carve(const AuxLayout& P, const AuxPacked& K, Bump& ws, int B, int nz, int 
   K.am.carve(ws, B, W.de);
 }
 using AuxEntry = Entry<AuxLayout, AuxPacked, AuxWs>;
-
-// every weight-gradient problem of aux_model_vae_backward, with its scratch taken from ws
-// (rows: B images, R = B stage(nz) stage rows, N = B nz z / decoder rows; toy: the heads' gradients are the sums over a stage row's q z's)
-void aux_wgrads(const AuxLayout& P, const AuxPacked& K, const AuxWs& W, int B, int nz, WgradList& wl, Bump& ws) {
-  const int R = B * P.stage(nz), N = B * nz, h = P.h, nl = P.nl;
-  const float* dmu = P.toy ? W.dmu_s : W.D.dz;
-  const float* dlv = P.toy ? W.dlv_s : W.dlv;
-  K.dec.wgrads(wl, N, W.z, W.D);                                                                     // decoder: head(s), then its layers
-  wl.push(R, P.zd, h, dmu, W.t[nl], h, wl.g(P.mean.w), h, wl.g(P.mean.b));
-  wl.push(R, P.zd, h, dlv, W.t[nl], h, wl.g(P.logvar.w), h, wl.g(P.logvar.b));
-  for (int l = nl; l >= 2; --l) wl.push(R, h, h, W.dt[l], W.t[l - 1], h, wl.g(P.ef[l - 1].w), h, wl.g(P.ef[l - 1].b));   // encoder layers n..2
-  wl.push(R, h, P.nd, W.dt[1], W.z0, P.nd, wl.g(P.ef[0].w + P.D), P.ef[0].in, wl.g(P.ef[0].b));        // first encoder layer, z0 half (+ bias)
-  wl.push(B, h, P.D, W.drb, W.xs, P.D, wl.g(P.ef[0].w), P.ef[0].in, nullptr);                         // first encoder layer, image half
-  wl.push(B, P.nd, h, W.dmu0, W.e[nl], h, wl.g(P.mean0.w), h, wl.g(P.mean0.b));
-  wl.push(B, P.nd, h, W.dlv0, W.e[nl], h, wl.g(P.logvar0.w), h, wl.g(P.logvar0.b));
-  K.am.wgrads(wl, B, W.xs, W.e.data(), W.de.data());                                                 // aux main
-  wl.assign(ws, wgrad_nprob(P));
-}
-
-size_t workspace_floats(const AuxLayout& P, int B, int nz, int mode) {
-  // dry run of carve() and the weight-gradient list on a null arena
-  const AuxPacked K(P);
-  Bump ws;
-  AuxWs W;
-  carve(P, K, ws, B, nz, mode == 0 ? 0 : 1, W);
-  if (mode != 0) {
-    WgradList wl(nullptr);
-    aux_wgrads(P, K, W, B, nz, wl, ws);
-  }
-  return ws.off;
-}
 
 // out[r][c] = mu[g][c] + exp(lv[g][c] / 2) * eps[r][c],  g = r / rows_per_group  (models/ivae/auxmnist.py:33-41)
 __global__ void reparam_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv, int ld_stat, const float* __restrict__ eps,
@@ -245,94 +215,96 @@ int sampler_fwd(const AuxLayout& P, const AuxPacked& K, const float* params, con
   return launch_reparam_fwd(W.mu, W.lv, eps, lde, R, P.zd, 1, W.z, st);
 }
 
-// ------------------------------------------------------------------------------------------------ entry points (kinds 3 / 7)
-size_t aux_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  const AuxLayout P(d);
-  if (mode == 2) return AuxPacked(P).dec.decode_floats((size_t)B * nz);   // decode only
-  return workspace_floats(P, B, nz, mode == 3 ? 0 : mode);
-}
-
-int aux_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-               float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
-  AuxEntry entry(d, workspace, wsf, B, nz, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "aux_model_encode: workspace too small");
-  ARDAE_CHECK_ARG(!P.toy || P.stage(nz) * P.stage(nz) == nz, "aux_model_encode: ToyAuxIPVAE draws q z0's x q z's per image - nz (%d) must be a square", nz);
-  ARDAE_TRY(noise_or_zero(noise, W.zero, (size_t)B * P.stage(nz) * P.nd + (size_t)B * nz * P.zd, st));
-  ARDAE_TRY(sampler_fwd(P, K, params, packed, x, noise, B, nz, W, st));
-  if (z_out) ARDAE_TRY(launch_copy(W.z, (size_t)B * nz * P.zd, z_out, st));
-  if (hidden_out) {   // forward_hidden of the ENCODER (ivae/auxmnist.py:125-132, nz == 1): cat(h0, h)
-    ARDAE_CHECK_ARG(nz == 1, "aux_model_encode: the hidden context is defined for nz == 1");
-    ARDAE_TRY(launch_copy2d(W.e[P.nl], (size_t)P.h, hidden_out, 2 * (size_t)P.h, B, (size_t)P.h, st));
-    ARDAE_TRY(launch_copy2d(W.t[P.nl], (size_t)P.h, hidden_out + P.h, 2 * (size_t)P.h, B, (size_t)P.h, st));
+// ------------------------------------------------------------------------------------------------ kinds 3 / 7 as a family
+// What the shared algorithm (csrc/ipmodel.h) needs to know of the hierarchical MLP models.
+struct AuxTraits : IpTraitsBase {
+  using Layout = AuxLayout; using Packed = AuxPacked; using Ws = AuxWs; using Entry = AuxEntry;
+  [[maybe_unused]] static constexpr bool mlp_decoder = true;
+  static int desc_check(const ardae_model_desc* d) { return mlp_desc_check(d, ARDAE_MODEL_CLIP_MASK); }
+  static unsigned caps(const ardae_model_desc& d) { return CAP_HIDDEN | (d.kind == 7 ? CAP_GAUSS_DECODER : 0); }
+  static IpBufs bufs(const AuxWs& W) { return {W.z, W.D.o[0], W.D.o[1], W.D.dox[0], W.D.dox[1], W.D.dzq, W.D.dz, W.rec_row, W.pri_row}; }
+  // every weight-gradient problem of the backward, with its scratch taken from ws
+  // (rows: B images, R = B stage(nz) stage rows, N = B nz z / decoder rows; toy: the heads' gradients are the sums over a stage row's q z's)
+  static void wgrads(const AuxLayout& P, const AuxPacked& K, const AuxWs& W, const float*, const float*, int B, int nz, WgradList& wl, Bump& ws) {
+    const int R = B * P.stage(nz), N = B * nz, h = P.h, nl = P.nl;
+    const float* dmu = P.toy ? W.dmu_s : W.D.dz;
+    const float* dlv = P.toy ? W.dlv_s : W.dlv;
+    K.dec.wgrads(wl, N, W.z, W.D);                                                                     // decoder: head(s), then its layers
+    wl.push(R, P.zd, h, dmu, W.t[nl], h, wl.g(P.mean.w), h, wl.g(P.mean.b));
+    wl.push(R, P.zd, h, dlv, W.t[nl], h, wl.g(P.logvar.w), h, wl.g(P.logvar.b));
+    for (int l = nl; l >= 2; --l) wl.push(R, h, h, W.dt[l], W.t[l - 1], h, wl.g(P.ef[l - 1].w), h, wl.g(P.ef[l - 1].b));   // encoder layers n..2
+    wl.push(R, h, P.nd, W.dt[1], W.z0, P.nd, wl.g(P.ef[0].w + P.D), P.ef[0].in, wl.g(P.ef[0].b));        // first encoder layer, z0 half (+ bias)
+    wl.push(B, h, P.D, W.drb, W.xs, P.D, wl.g(P.ef[0].w), P.ef[0].in, nullptr);                         // first encoder layer, image half
+    wl.push(B, P.nd, h, W.dmu0, W.e[nl], h, wl.g(P.mean0.w), h, wl.g(P.mean0.b));
+    wl.push(B, P.nd, h, W.dlv0, W.e[nl], h, wl.g(P.logvar0.w), h, wl.g(P.logvar0.b));
+    K.am.wgrads(wl, B, W.xs, W.e.data(), W.de.data());                                                 // aux main
+    wl.assign(ws, wgrad_nprob(P));
   }
-  return 0;
-}
-
-int aux_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                    DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  AuxEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_forward: workspace too small");
-  ARDAE_CHECK_ARG(!P.toy || P.stage(nz) * P.stage(nz) == nz, "aux_model_vae_forward: ToyAuxIPVAE needs a square nz (got %d)", nz);
-  const int R = B * nz;      // z / decoder rows
-  ARDAE_TRY(sampler_fwd(P, K, params, packed, x, noise, B, nz, W, st));
-  ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
-  ARDAE_TRY(K.dec.fwd(params, packed, P.act, R, W.z, W.D.hid.data(), W.D.o, st));
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
-  return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
-}
-
-int aux_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
-                     hipStream_t st) {
-  (void)noise;
-  AuxEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  const int N = B * nz;                                   // z / decoder rows
-  const int nzs = P.stage(nz);                            // samples per image at the stage level (toy: q)
-  const int R = B * nzs, h = P.h, act = P.act, nl = P.nl;
-  const float gscale = dloss / (float)N;
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, N, nz, P.D, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.D.dox[0],
-                            W.D.dox[1], W.D.dzq, st));
-  ARDAE_TRY(K.dec.bwd(packed, act, N, W.D, st));
-  // second reparameterisation: dmu = dz, dlv = dz (z - mu) / 2; both heads back into h = t_n
-  // (toy: q z's share a stage row's mu / lv: their dz and dlv are summed over the q rows first)
-  ARDAE_TRY(launch_reparam_bwd(W.D.dz, W.z, W.mu, N, P.zd, P.toy ? nzs : 1, W.dlv, st));
-  const float* dmu = W.D.dz;
-  float* dlv = W.dlv;
-  if (P.toy) {
-    ARDAE_TRY(launch_segment_sum(W.D.dz, P.zd, R, nzs, P.zd, 1.0f, W.dmu_s, P.zd, st));
-    ARDAE_TRY(launch_segment_sum(W.dlv, P.zd, R, nzs, P.zd, 1.0f, W.dlv_s, P.zd, st));
-    dmu = W.dmu_s; dlv = W.dlv_s;
+  static size_t noise_floats(const AuxLayout& P, int B, int nz) { return (size_t)B * P.stage(nz) * P.nd + (size_t)B * nz * P.zd; }
+  static float* zero_noise(Entry& e, size_t) { return e.W.zero; }
+  static int rows_ok(const AuxLayout& P, int nz, bool encode) {
+    if (!P.toy || P.stage(nz) * P.stage(nz) == nz) return 0;
+    ARDAE_CHECK_ARG(!encode, "aux_model_encode: ToyAuxIPVAE draws q z0's x q z's per image - nz (%d) must be a square", nz);
+    ARDAE_CHECK_ARG(false, "aux_model_vae_forward: ToyAuxIPVAE needs a square nz (got %d)", nz);
+    return 0;
   }
-  // through the z head's log-variance clip: d lv_raw = d lv c'(lv_raw) (in place; one value per stage row)
-  ARDAE_TRY(launch_logvar_clip(W.lvr, dlv, dlv, (int64_t)R * P.zd, P.clip1, st));
-  ARDAE_TRY(dense_bwd2(act, R, h, dmu, packed + K.mean_b, dlv, packed + K.logvar_b, P.zd, W.t[nl], W.dt[nl], st));
-  ARDAE_TRY(K.ef.bwd(packed, act, R, W.t.data() + 1, W.dt.data() + 1, st));                             // dt_n .. dt_2
-  if (nl >= 2) ARDAE_TRY(dense_bwd(act, R, h, W.dt[2], h, packed + K.ef.b[0], W.t[1], W.dt[1], st));    // ... and into the first layer's output
-  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, W.dt[1], h, h, packed + K.ef0_b, nullptr, W.dz0, st));          // dz0 = dt_1 Wz  (no activation between z0 and the layer)
-  ARDAE_TRY(launch_segment_sum(W.dt[1], h, B, nzs, h, 1.0f, W.drb, h, st));
-  // first reparameterisation, reduced over the nz samples of each image
-  ARDAE_TRY(launch_reparam_bwd(W.dz0, W.z0, W.mu0, R, P.nd, nzs, W.dlv0r, st));
-  ARDAE_TRY(launch_segment_sum(W.dz0, P.nd, B, nzs, P.nd, 1.0f, W.dmu0, P.nd, st));
-  ARDAE_TRY(launch_segment_sum(W.dlv0r, P.nd, B, nzs, P.nd, 1.0f, W.dlv0, P.nd, st));
-  ARDAE_TRY(launch_logvar_clip(W.lv0r, W.dlv0, W.dlv0, (int64_t)B * P.nd, P.clip0, st));      // ... and through the z0 head's
-  ARDAE_TRY(dense_bwd2(act, B, h, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.e[nl], W.de[nl], st));
-  ARDAE_TRY(K.am.bwd(packed, act, B, W.e.data(), W.de.data(), st));
-  // weight gradients: one batched launch
-  WgradList wl(grads, grads_beta);
-  aux_wgrads(P, K, W, B, nz, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "aux_model_vae_backward: workspace too small");
-  return wl.launch(st);
-}
+  static int sampler_fwd(Entry& e, const float* params, const float* packed, const float* x, const float* noise, int B, int nz, const IpEncodeOut*,
+                         hipStream_t st) {
+    return ardae::sampler_fwd(e.P, e.K, params, packed, x, noise, B, nz, e.W, st);
+  }
+  // forward_hidden of the ENCODER (ivae/auxmnist.py:125-132, nz == 1): cat(h0, h)
+  static int hidden_copy(Entry& e, float* hidden_out, int B, hipStream_t st) {
+    const size_t h = (size_t)e.P.h;
+    ARDAE_TRY(launch_copy2d(e.W.e[e.P.nl], h, hidden_out, 2 * h, B, h, st));
+    return launch_copy2d(e.W.t[e.P.nl], h, hidden_out + h, 2 * h, B, h, st);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int N, hipStream_t st) {
+    return e.K.dec.fwd(params, packed, e.P.act, N, z, e.W.D.hid.data(), e.W.D.o, st);
+  }
+  static int decoder_bwd(Entry& e, const float* packed, int N, Grads&, hipStream_t st) { return e.K.dec.bwd(packed, e.P.act, N, e.W.D, st); }
+  // rows: N = B nz z / decoder rows, R = B nzs stage rows
+  static int sampler_bwd(Entry& e, const float*, const float* packed, const float*, const float*, int B, int nz, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int N = B * nz;
+    const int nzs = P.stage(nz);                            // samples per image at the stage level (toy: q)
+    const int R = B * nzs, h = P.h, act = P.act, nl = P.nl;
+    // second reparameterisation: dmu = dz, dlv = dz (z - mu) / 2; both heads back into h = t_n
+    // (toy: q z's share a stage row's mu / lv: their dz and dlv are summed over the q rows first)
+    ARDAE_TRY(launch_reparam_bwd(W.D.dz, W.z, W.mu, N, P.zd, P.toy ? nzs : 1, W.dlv, st));
+    const float* dmu = W.D.dz;
+    float* dlv = W.dlv;
+    if (P.toy) {
+      ARDAE_TRY(launch_segment_sum(W.D.dz, P.zd, R, nzs, P.zd, 1.0f, W.dmu_s, P.zd, st));
+      ARDAE_TRY(launch_segment_sum(W.dlv, P.zd, R, nzs, P.zd, 1.0f, W.dlv_s, P.zd, st));
+      dmu = W.dmu_s; dlv = W.dlv_s;
+    }
+    // through the z head's log-variance clip: d lv_raw = d lv c'(lv_raw) (in place; one value per stage row)
+    ARDAE_TRY(launch_logvar_clip(W.lvr, dlv, dlv, (int64_t)R * P.zd, P.clip1, st));
+    ARDAE_TRY(dense_bwd2(act, R, h, dmu, packed + K.mean_b, dlv, packed + K.logvar_b, P.zd, W.t[nl], W.dt[nl], st));
+    ARDAE_TRY(K.ef.bwd(packed, act, R, W.t.data() + 1, W.dt.data() + 1, st));                             // dt_n .. dt_2
+    if (nl >= 2) ARDAE_TRY(dense_bwd(act, R, h, W.dt[2], h, packed + K.ef.b[0], W.t[1], W.dt[1], st));    // ... and into the first layer's output
+    ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, W.dt[1], h, h, packed + K.ef0_b, nullptr, W.dz0, st));          // dz0 = dt_1 Wz  (no activation between z0 and the layer)
+    ARDAE_TRY(launch_segment_sum(W.dt[1], h, B, nzs, h, 1.0f, W.drb, h, st));
+    // first reparameterisation, reduced over the nz samples of each image
+    ARDAE_TRY(launch_reparam_bwd(W.dz0, W.z0, W.mu0, R, P.nd, nzs, W.dlv0r, st));
+    ARDAE_TRY(launch_segment_sum(W.dz0, P.nd, B, nzs, P.nd, 1.0f, W.dmu0, P.nd, st));
+    ARDAE_TRY(launch_segment_sum(W.dlv0r, P.nd, B, nzs, P.nd, 1.0f, W.dlv0, P.nd, st));
+    ARDAE_TRY(launch_logvar_clip(W.lv0r, W.dlv0, W.dlv0, (int64_t)B * P.nd, P.clip0, st));      // ... and through the z0 head's
+    ARDAE_TRY(dense_bwd2(act, B, h, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.e[nl], W.de[nl], st));
+    ARDAE_TRY(K.am.bwd(packed, act, B, W.e.data(), W.de.data(), st));
+    // weight gradients: one batched launch
+    WgradList wl(g.grads, g.beta);
+    wgrads(P, K, W, nullptr, nullptr, B, nz, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
+    return wl.launch(st);
+  }
+};
 
 }  // namespace
 
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
 #ifndef __HIP_DEVICE_COMPILE__
-const Family AUX_FAMILY = {family_param_floats<AuxLayout, AuxPacked>, family_packed_floats<AuxLayout, AuxPacked>, aux_workspace_floats,
-                           family_pack<AuxLayout, AuxPacked>, aux_encode, mlp_decode<AuxLayout, AuxPacked>, aux_vae_forward, aux_vae_backward};
+const Family AUX_FAMILY = ip_family<AuxTraits>();
 #endif
 
 }  // namespace ardae

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "auxmodel.h"
 #include "convmodel.h"
+#include "ipmodel.h"
 
 namespace ardae {
 namespace {
@@ -217,102 +218,64 @@ namespace {
 
 using ConvEntry = Entry<ConvLayout, ConvPacked, ConvWs>;
 
-
-int conv_encode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* x, const float* noise,
-                    int B, int nz, ConvWs& W, float* z_out, hipStream_t st) {
-  const int R = B * nz, act = P.act;
-  ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // ivae/conv.py:81
-  ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.cols, W.hcv, W.inp, B, act, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, params + P.fc4.b, W.rb, st));   // image half of fc4, once per image
-  {
-    LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.t1; A.ldY = 800;
-    ARDAE_TRY(lin1(EPI_ACT, act, R, 800, noise, P.nd, P.nd, packed + K.fc4n_f, A, st));
-  }
-  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, params + P.fc5.b, W.z, st));
-  if (z_out) ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
+// the descriptor rules of kinds 2 / 4
+int conv_desc_check(const ardae_model_desc* d) {
+  ARDAE_TRY(desc_flags_ok(d, 0));
+  ARDAE_CHECK_ARG(d->input_dim == 784 && d->noise_dim >= 1 && d->z_dim >= 1, "model: ConvIPVAE is hard-wired to 28x28x1 inputs (input_dim 784)");
+  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
   return 0;
 }
 
-// every weight-gradient problem of conv_model_vae_backward, with its scratch taken from ws
-void conv_wgrads(const ConvLayout& P, const ConvWs& W, int B, int R, const float* noise, WgradList& wl, Bump& ws) {
-  conv_decoder_wgrads(P, W, R, wl);
-  wl.push(R, P.zd, 800, W.dz, W.t1, 800, wl.g(P.fc5.w), 800, wl.g(P.fc5.b));
-  wl.push(R, 800, P.nd, W.dt1, noise, P.nd, wl.g(P.fc4.w + 512), 512 + P.nd, wl.g(P.fc4.b));   // fc4 noise half (+ bias)
-  wl.push(B, 800, 512, W.drb, W.inp, 512, wl.g(P.fc4.w), 512 + P.nd, nullptr);                  // fc4 image half
-  conv_trunk_wgrads(P.conv, W.cols, W.dh3, W.dh2, W.dh1, B, wl);
-  wl.assign(ws, CONV_WGRAD_HINT);
-}
-
-size_t conv_workspace(const ConvLayout& P, int B, int nz, int mode) {
-  // run the carve (and the weight-gradient list) on a null arena to count
-  Bump ws;
-  ConvWs W;
-  carve(P, ConvPacked(P), ws, B, nz, mode, W);
-  if (mode == 1) {
-    WgradList wl(nullptr);
-    conv_wgrads(P, W, B, B * nz, nullptr, wl, ws);
+// What the shared algorithm (csrc/ipmodel.h) needs to know of ConvIPVAE.
+struct ConvTraits : IpTraitsBase {
+  using Layout = ConvLayout; using Packed = ConvPacked; using Ws = ConvWs; using Entry = ConvEntry;
+  static int desc_check(const ardae_model_desc* d) { return conv_desc_check(d); }
+  static unsigned caps(const ardae_model_desc&) { return 0; }
+  static IpBufs bufs(const ConvWs& W) { return {W.z, W.logit, nullptr, W.dlogit, nullptr, W.dzq, W.dz, W.rec_row, W.pri_row}; }
+  // every weight-gradient problem of the backward, with its scratch taken from ws
+  static void wgrads(const ConvLayout& P, const ConvPacked&, const ConvWs& W, const float*, const float* noise, int B, int nz, WgradList& wl, Bump& ws) {
+    const int R = B * nz;
+    conv_decoder_wgrads(P, W, R, wl);
+    wl.push(R, P.zd, 800, W.dz, W.t1, 800, wl.g(P.fc5.w), 800, wl.g(P.fc5.b));
+    wl.push(R, 800, P.nd, W.dt1, noise, P.nd, wl.g(P.fc4.w + 512), 512 + P.nd, wl.g(P.fc4.b));   // fc4 noise half (+ bias)
+    wl.push(B, 800, 512, W.drb, W.inp, 512, wl.g(P.fc4.w), 512 + P.nd, nullptr);                  // fc4 image half
+    conv_trunk_wgrads(P.conv, W.cols, W.dh3, W.dh2, W.dh1, B, wl);
+    wl.assign(ws, CONV_WGRAD_HINT);
   }
-  return ws.off + al64((size_t)B * nz * P.nd);    // + zero-noise buffer for encode(std=0)
-}
-
-// ------------------------------------------------------------------------------------------------ entry points (kind == 2)
-// mode 3 (encode_pair: two encode passes over one workspace) is mode 0
-size_t conv_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return conv_workspace(ConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
-
-int conv_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                      int nz, float* workspace, size_t wsf, float* z_out, float*, hipStream_t st, const float*) {
-  ConvEntry entry(d, workspace, wsf, B, nz, 0);
-  auto& [P, K, ws, W] = entry;
-  float* zero = noise ? nullptr : ws.take((size_t)B * nz * P.nd);
-  ARDAE_CHECK_ARG(ws.ok, "conv_model_encode: workspace too small");
-  ARDAE_TRY(noise_or_zero(noise, zero, (size_t)B * nz * P.nd, st));
-  return conv_encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, st);
-}
-
-int conv_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace,
-                      size_t wsf, float* out0, hipStream_t st, float*) {
-  ConvEntry entry(d, workspace, wsf, R, 1, 2);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "conv_model_decode: workspace too small");
-  ARDAE_TRY(conv_decode_fwd(P, K, params, packed, z, R, W, st));
-  ARDAE_TRY(launch_copy(W.logit, (size_t)R * 784, out0, st));
-  return 0;
-}
-
-int conv_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                           int nz, DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  ConvEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "conv_model_vae_forward: workspace too small");
-  const int R = B * nz;
-  ARDAE_TRY(conv_encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, st));
-  ARDAE_TRY(conv_decode_fwd(P, K, params, packed, W.z, R, W, st));
-  ARDAE_TRY(launch_vae_loss(0, W.logit, nullptr, x, W.z, R, nz, 784, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
-  return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
-}
-
-int conv_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                            int nz, DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
-                            float grads_beta, hipStream_t st) {
-  ConvEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  const int R = B * nz, act = P.act;
-  const float gscale = dloss / (float)R;
-  ARDAE_TRY(launch_vae_loss(0, W.logit, nullptr, x, W.z, R, nz, 784, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.dlogit, nullptr,
-                            W.dzq, st));
-  ARDAE_TRY(conv_decoder_bwd(P, K, packed, W, R, st));
-  // ---- sampler backward
-  ARDAE_TRY(dense_bwd(act, R, 800, W.dz, P.zd, packed + K.fc5_b, W.t1, W.dt1, st));
-  ARDAE_TRY(launch_segment_sum(W.dt1, 800, B, nz, 800, 1.0f, W.drb, 800, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.drb, 800, 800, packed + K.fc4i_b, nullptr, W.dinp, st));
-  ARDAE_TRY(trunk_bwd(K.conv_b, packed, W.dinp, W.dinp_t, W.hcv, W.dh3, W.dcols3, W.dh2, W.dcols2, W.dh1, B, act, st));
-  // ---- weight gradients: one batched launch
-  WgradList wl(grads, grads_beta);
-  conv_wgrads(P, W, B, R, noise, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "conv_model_vae_backward: workspace too small");
-  return wl.launch(st);
-}
-
+  static size_t extra_floats(const ConvLayout& P, int B, int nz, int) { return al64((size_t)B * nz * P.nd); }    // a zero-noise buffer for encode(std=0)
+  static size_t noise_floats(const ConvLayout& P, int B, int nz) { return (size_t)B * nz * P.nd; }
+  static float* zero_noise(Entry& e, size_t n) { return e.ws.take(n); }
+  static int sampler_fwd(Entry& e, const float* params, const float* packed, const float* x, const float* noise, int B, int nz, const IpEncodeOut*,
+                         hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int R = B * nz, act = P.act;
+    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // ivae/conv.py:81
+    ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.cols, W.hcv, W.inp, B, act, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, params + P.fc4.b, W.rb, st));   // image half of fc4, once per image
+    {
+      LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.t1; A.ldY = 800;
+      ARDAE_TRY(lin1(EPI_ACT, act, R, 800, noise, P.nd, P.nd, packed + K.fc4n_f, A, st));
+    }
+    return dense_fwd(ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, params + P.fc5.b, W.z, st);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {
+    return conv_decode_fwd(e.P, e.K, params, packed, z, R, e.W, st);
+  }
+  static int decoder_bwd(Entry& e, const float* packed, int R, Grads&, hipStream_t st) { return conv_decoder_bwd(e.P, e.K, packed, e.W, R, st); }
+  static int sampler_bwd(Entry& e, const float*, const float* packed, const float*, const float* noise, int B, int nz, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int R = B * nz, act = P.act;
+    ARDAE_TRY(dense_bwd(act, R, 800, W.dz, P.zd, packed + K.fc5_b, W.t1, W.dt1, st));
+    ARDAE_TRY(launch_segment_sum(W.dt1, 800, B, nz, 800, 1.0f, W.drb, 800, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.drb, 800, 800, packed + K.fc4i_b, nullptr, W.dinp, st));
+    ARDAE_TRY(trunk_bwd(K.conv_b, packed, W.dinp, W.dinp_t, W.hcv, W.dh3, W.dcols3, W.dh2, W.dcols2, W.dh1, B, act, st));
+    // ---- weight gradients: one batched launch
+    WgradList wl(g.grads, g.beta);
+    wgrads(P, K, W, nullptr, noise, B, nz, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
+    return wl.launch(st);
+  }
+};
 
 // =====================================================================================================================
 // MNISTConvAuxIPVAE (`--model auxconv`, kind == 4): models/ivae/auxconv.py:48-126 - the hierarchical sampler of csrc/auxmodel.hip with
@@ -391,33 +354,6 @@ using AuxConvEntry = Entry<AuxConvLayout, AuxConvPacked, AuxConvWs>;
 // wgrad_splits hint of the hierarchical conv backward, and the size of its first batch: the 21 problems go out as 10 + 11
 constexpr int AUX_WGRAD_HINT = 10;
 
-// every weight-gradient problem of auxconv_model_vae_backward, with its scratch taken from ws
-void auxconv_wgrads(const AuxConvLayout& P, const AuxConvWs& W, int B, int R, WgradList& wl, Bump& ws) {
-  const ConvWs& D = W.D;
-  conv_decoder_wgrads(P.dec, D, R, wl);                                                             // decoder (as ConvIPVAE)
-  wl.push(R, P.zd, 800, D.dz, D.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
-  wl.push(R, P.zd, 800, W.dlv, D.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
-  wl.push(R, 800, P.nd, W.dt1, W.z0, P.nd, wl.g(P.efc.w + 512), 512 + P.nd, wl.g(P.efc.b));         // fc z0 half (+ bias)
-  wl.push(B, 800, 512, W.drb, W.einp, 512, wl.g(P.efc.w), 512 + P.nd, nullptr);                     // fc image half
-  conv_trunk_wgrads(P.econv, W.ecols, W.dh3[1], W.dh2[1], W.dh1[1], B, wl);                           // encoder trunk
-  wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
-  wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
-  wl.push(B, 800, 512, W.dh4a, W.ainp, 512, wl.g(P.afc.w), 512, wl.g(P.afc.b));
-  conv_trunk_wgrads(P.aconv, W.acols, W.dh3[0], W.dh2[0], W.dh1[0], B, wl);                           // aux trunk
-  wl.assign(ws, AUX_WGRAD_HINT);
-}
-
-size_t aux_workspace(const AuxConvLayout& P, int B, int nz, int mode) {
-  Bump ws;
-  AuxConvWs W;
-  carve(P, AuxConvPacked(P), ws, B, nz, mode, W);
-  if (mode == 1) {
-    WgradList wl(nullptr);
-    auxconv_wgrads(P, W, B, B * nz, wl, ws);
-  }
-  return ws.off;
-}
-
 // keep_hidden = false (forward-only encodes of the cDAE phase): the [R, 800] hidden rows need not exist
 int aux_sampler_fwd(const AuxConvLayout& P, const AuxConvPacked& K, const float* params, const float* packed, const float* x, const float* noise,
                     int B, int nz, AuxConvWs& W, bool keep_hidden, hipStream_t st) {
@@ -445,88 +381,79 @@ int aux_sampler_fwd(const AuxConvLayout& P, const AuxConvPacked& K, const float*
   return launch_reparam_fwd(W.mu, W.lv, noise + P.nd, ldn, R, P.zd, 1, W.D.z, st);
 }
 
-size_t auxconv_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) { return aux_workspace(AuxConvLayout(d), B, nz, mode == 3 ? 0 : mode); }
-
-int auxconv_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                         float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float*) {
-  AuxConvEntry entry(d, workspace, wsf, B, nz, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "auxconv_model_encode: workspace too small");
-  ARDAE_TRY(noise_or_zero(noise, W.zero, (size_t)B * nz * (P.nd + P.zd), st));
-  ARDAE_TRY(aux_sampler_fwd(P, K, params, packed, x, noise, B, nz, W, hidden_out != nullptr, st));
-  if (z_out) ARDAE_TRY(launch_copy(W.D.z, (size_t)B * nz * P.zd, z_out, st));
-  if (hidden_out) {
-    ARDAE_CHECK_ARG(nz == 1, "auxconv_model_encode: the hidden context is defined for nz == 1");
-    ARDAE_TRY(launch_copy2d(W.h4a, 800, hidden_out, 1600, B, 800, st));
-    ARDAE_TRY(launch_copy2d(W.D.t1, 800, hidden_out + 800, 1600, B, 800, st));
+// What the shared algorithm (csrc/ipmodel.h) needs to know of MNISTConvAuxIPVAE.
+struct AuxConvTraits : IpTraitsBase {
+  using Layout = AuxConvLayout; using Packed = AuxConvPacked; using Ws = AuxConvWs; using Entry = AuxConvEntry;
+  static int desc_check(const ardae_model_desc* d) { return conv_desc_check(d); }
+  static unsigned caps(const ardae_model_desc&) { return CAP_HIDDEN; }
+  static IpBufs bufs(const AuxConvWs& W) {
+    const ConvWs& D = W.D;
+    return {D.z, D.logit, nullptr, D.dlogit, nullptr, D.dzq, D.dz, D.rec_row, D.pri_row};
   }
-  return 0;
-}
-
-int auxconv_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                         float* out0, hipStream_t st, float*) {
-  AuxConvEntry entry(d, workspace, wsf, R, 1, 2);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "auxconv_model_decode: workspace too small");
-  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, z, R, W.D, st));
-  ARDAE_TRY(launch_copy(W.D.logit, (size_t)R * 784, out0, st));
-  return 0;
-}
-
-int auxconv_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                              int nz, DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  AuxConvEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "auxconv_model_vae_forward: workspace too small");
-  const int R = B * nz;
-  ARDAE_TRY(aux_sampler_fwd(P, K, params, packed, x, noise, B, nz, W, true, st));
-  ARDAE_TRY(launch_copy(W.D.z, (size_t)R * P.zd, z_out, st));
-  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, W.D.z, R, W.D, st));
-  ARDAE_TRY(launch_vae_loss(0, W.D.logit, nullptr, x, W.D.z, R, nz, 784, P.zd, beta, 0, 0.f, nullptr, W.D.rec_row, W.D.pri_row, nullptr, nullptr, nullptr, st));
-  return launch_vae_loss_finalize(W.D.rec_row, W.D.pri_row, R, beta, losses, st);
-}
-
-int auxconv_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B,
-                               int nz, DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads,
-                               float grads_beta, hipStream_t st) {
-  (void)noise;
-  AuxConvEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ConvWs& D = W.D;
-  const int R = B * nz, act = P.act;
-  const float gscale = dloss / (float)R;
-  ARDAE_TRY(launch_vae_loss(0, D.logit, nullptr, x, D.z, R, nz, 784, P.zd, beta, 1, gscale, dz_extra, D.rec_row, D.pri_row, D.dlogit, nullptr, D.dzq, st));
-  ARDAE_TRY(conv_decoder_bwd(P.dec, K.dec, packed, D, R, st));
-  // second reparameterisation and the encoder's fc
-  ARDAE_TRY(launch_reparam_bwd(D.dz, D.z, W.mu, R, P.zd, 1, W.dlv, st));
-  ARDAE_TRY(dense_bwd2(act, R, 800, D.dz, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, D.t1, W.dt1, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, W.dt1, 800, 800, packed + K.efcn_b, nullptr, W.dz0, st));
-  ARDAE_TRY(launch_segment_sum(W.dt1, 800, B, nz, 800, 1.0f, W.drb, 800, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.drb, 800, 800, packed + K.efci_b, nullptr, W.dinp_e, st));
-  ARDAE_TRY(trunk_bwd(K.econv_b, packed, W.dinp_e, W.dinp_t, W.ehcv, W.dh3[1], W.dcols3[1], W.dh2[1], W.dcols2[1], W.dh1[1], B, act, st));
-  // first reparameterisation, reduced over the nz samples of each image, and the aux encoder
-  ARDAE_TRY(launch_reparam_bwd(W.dz0, W.z0, W.mu0, R, P.nd, nz, W.dlv0r, st));
-  ARDAE_TRY(launch_segment_sum(W.dz0, P.nd, B, nz, P.nd, 1.0f, W.dmu0, P.nd, st));
-  ARDAE_TRY(launch_segment_sum(W.dlv0r, P.nd, B, nz, P.nd, 1.0f, W.dlv0, P.nd, st));
-  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.dinp_a, st));
-  ARDAE_TRY(trunk_bwd(K.aconv_b, packed, W.dinp_a, W.dinp_t, W.ahcv, W.dh3[0], W.dcols3[0], W.dh2[0], W.dcols2[0], W.dh1[0], B, act, st));
-  // ---- weight gradients, launched as two batches
-  WgradList wl(grads, grads_beta);
-  auxconv_wgrads(P, W, B, R, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "auxconv_model_vae_backward: workspace too small (%zu floats needed, %zu given, %zu problems)", ws.off, wsf, wl.probs.size());
-  ARDAE_TRY(wl.launch(st, AUX_WGRAD_HINT));
-  return wl.launch(st);
-}
+  // every weight-gradient problem of the backward, with its scratch taken from ws
+  static void wgrads(const AuxConvLayout& P, const AuxConvPacked&, const AuxConvWs& W, const float*, const float*, int B, int nz, WgradList& wl, Bump& ws) {
+    const int R = B * nz;
+    const ConvWs& D = W.D;
+    conv_decoder_wgrads(P.dec, D, R, wl);                                                             // decoder (as ConvIPVAE)
+    wl.push(R, P.zd, 800, D.dz, D.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
+    wl.push(R, P.zd, 800, W.dlv, D.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
+    wl.push(R, 800, P.nd, W.dt1, W.z0, P.nd, wl.g(P.efc.w + 512), 512 + P.nd, wl.g(P.efc.b));         // fc z0 half (+ bias)
+    wl.push(B, 800, 512, W.drb, W.einp, 512, wl.g(P.efc.w), 512 + P.nd, nullptr);                     // fc image half
+    conv_trunk_wgrads(P.econv, W.ecols, W.dh3[1], W.dh2[1], W.dh1[1], B, wl);                           // encoder trunk
+    wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
+    wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
+    wl.push(B, 800, 512, W.dh4a, W.ainp, 512, wl.g(P.afc.w), 512, wl.g(P.afc.b));
+    conv_trunk_wgrads(P.aconv, W.acols, W.dh3[0], W.dh2[0], W.dh1[0], B, wl);                           // aux trunk
+    wl.assign(ws, AUX_WGRAD_HINT);
+  }
+  static size_t noise_floats(const AuxConvLayout& P, int B, int nz) { return (size_t)B * nz * (P.nd + P.zd); }
+  static float* zero_noise(Entry& e, size_t) { return e.W.zero; }
+  // a forward-only pass keeps the [R, 800] hidden rows only where the hidden context is wanted
+  static int sampler_fwd(Entry& e, const float* params, const float* packed, const float* x, const float* noise, int B, int nz, const IpEncodeOut* enc,
+                         hipStream_t st) {
+    return aux_sampler_fwd(e.P, e.K, params, packed, x, noise, B, nz, e.W, !enc || enc->hidden_out != nullptr, st);
+  }
+  static int hidden_copy(Entry& e, float* hidden_out, int B, hipStream_t st) {      // cat(h4a, h4)
+    ARDAE_TRY(launch_copy2d(e.W.h4a, 800, hidden_out, 1600, B, 800, st));
+    return launch_copy2d(e.W.D.t1, 800, hidden_out + 800, 1600, B, 800, st);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {
+    return conv_decode_fwd(e.P.dec, e.K.dec, params, packed, z, R, e.W.D, st);
+  }
+  static int decoder_bwd(Entry& e, const float* packed, int R, Grads&, hipStream_t st) { return conv_decoder_bwd(e.P.dec, e.K.dec, packed, e.W.D, R, st); }
+  static int sampler_bwd(Entry& e, const float*, const float* packed, const float*, const float*, int B, int nz, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ConvWs& D = W.D;
+    const int R = B * nz, act = P.act;
+    // second reparameterisation and the encoder's fc
+    ARDAE_TRY(launch_reparam_bwd(D.dz, D.z, W.mu, R, P.zd, 1, W.dlv, st));
+    ARDAE_TRY(dense_bwd2(act, R, 800, D.dz, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, D.t1, W.dt1, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, W.dt1, 800, 800, packed + K.efcn_b, nullptr, W.dz0, st));
+    ARDAE_TRY(launch_segment_sum(W.dt1, 800, B, nz, 800, 1.0f, W.drb, 800, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.drb, 800, 800, packed + K.efci_b, nullptr, W.dinp_e, st));
+    ARDAE_TRY(trunk_bwd(K.econv_b, packed, W.dinp_e, W.dinp_t, W.ehcv, W.dh3[1], W.dcols3[1], W.dh2[1], W.dcols2[1], W.dh1[1], B, act, st));
+    // first reparameterisation, reduced over the nz samples of each image, and the aux encoder
+    ARDAE_TRY(launch_reparam_bwd(W.dz0, W.z0, W.mu0, R, P.nd, nz, W.dlv0r, st));
+    ARDAE_TRY(launch_segment_sum(W.dz0, P.nd, B, nz, P.nd, 1.0f, W.dmu0, P.nd, st));
+    ARDAE_TRY(launch_segment_sum(W.dlv0r, P.nd, B, nz, P.nd, 1.0f, W.dlv0, P.nd, st));
+    ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.dinp_a, st));
+    ARDAE_TRY(trunk_bwd(K.aconv_b, packed, W.dinp_a, W.dinp_t, W.ahcv, W.dh3[0], W.dcols3[0], W.dh2[0], W.dcols2[0], W.dh1[0], B, act, st));
+    // ---- weight gradients, launched as two batches
+    WgradList wl(g.grads, g.beta);
+    wgrads(P, K, W, nullptr, nullptr, B, nz, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
+    ARDAE_TRY(wl.launch(st, AUX_WGRAD_HINT));
+    return wl.launch(st);
+  }
+};
 
 }  // namespace
 
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
 #ifndef __HIP_DEVICE_COMPILE__
-const Family CONV_FAMILY = {family_param_floats<ConvLayout, ConvPacked>, family_packed_floats<ConvLayout, ConvPacked>, conv_workspace_floats,
-                            family_pack<ConvLayout, ConvPacked>, conv_encode, conv_decode, conv_vae_forward, conv_vae_backward};
-const Family AUXCONV_FAMILY = {family_param_floats<AuxConvLayout, AuxConvPacked>, family_packed_floats<AuxConvLayout, AuxConvPacked>, auxconv_workspace_floats,
-                               family_pack<AuxConvLayout, AuxConvPacked>, auxconv_encode, auxconv_decode, auxconv_vae_forward, auxconv_vae_backward};
+const Family CONV_FAMILY = ip_family<ConvTraits>();
+const Family AUXCONV_FAMILY = ip_family<AuxConvTraits>();
 #endif
 
 }  // namespace ardae

@@ -156,8 +156,8 @@ struct ConvVaeTraits {
 
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
-static const GaussFamily CONVVAE_GAUSS = gauss_family<ConvVaeTraits>(convvae_desc_check);
-const Family CONVVAE_FAMILY = {family_param_floats<ConvVaeLayout, ConvVaePacked>, family_packed_floats<ConvVaeLayout, ConvVaePacked>,
+static const GaussFamily CONVVAE_GAUSS = gauss_family<ConvVaeTraits>();
+const Family CONVVAE_FAMILY = {convvae_desc_check, no_caps, family_param_floats<ConvVaeLayout, ConvVaePacked>, family_packed_floats<ConvVaeLayout, ConvVaePacked>,
                                convvae_workspace_floats, family_pack<ConvVaeLayout, ConvVaePacked>, vae_no_encode, convvae_decode, vae_no_forward,
                                vae_no_backward, &CONVVAE_GAUSS};
 #endif

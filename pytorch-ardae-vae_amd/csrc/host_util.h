@@ -176,9 +176,15 @@ inline int noise_or_zero(const float*& noise, float* zero, size_t n, hipStream_t
 
 // ------------------------------------------------------------------------------------------------ the model families
 // One row of csrc/model.hip's table by kind (encode: hidden_out / raw0 and decode: out1 are NULL for the families that have no
-// such output / input).  Each family file defines its own.
+// such output / input).  Each family file defines its own.  The row carries everything the entry points decide by: they know no kind number.
 struct GaussFamily;   // csrc/vaemodel.h
+// what a descriptor of the family can do (a row may serve two kinds, so these are read per descriptor)
+enum { CAP_GAUSS_DECODER = 1,   // the decoder has mean and logvar heads: ardae_model_decode needs out1, ardae_model_loss_rows the Gaussian likelihood
+       CAP_HIDDEN = 2,          // ardae_model_encode_hidden: the hidden1a context
+       CAP_HIDDEN_RAW = 4 };    // ardae_model_encode_hidden_raw: the same with an unscaled eps0
 struct Family {
+  int (*desc_check)(const ardae_model_desc* d);    // the family's descriptor rules, next to its layout: 0, or -1 with the message set
+  unsigned (*caps)(const ardae_model_desc& d);     // CAP_*
   size_t (*param_floats)(const ardae_model_desc&);
   size_t (*packed_floats)(const ardae_model_desc&);
   size_t (*workspace_floats)(const ardae_model_desc&, int B, int nz, int mode);   // mode 2: decode only, 3: encode_pair
@@ -191,8 +197,26 @@ struct Family {
                      DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t);
   int (*vae_backward)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
                       DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
-  const GaussFamily* gauss;   // the Gaussian-posterior kinds' descriptor rules and ardae_vae_* bodies; null for the implicit kinds
+  const GaussFamily* gauss;   // the Gaussian-posterior kinds' ardae_vae_* bodies; null for the implicit kinds
+  // the fused ardae_model_encode_pair (phase as in the ABI); null: the entry point runs two passes of `encode` over the same workspace
+  int (*encode_pair)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                     float* workspace, size_t wsf, float* z0_out, float* z_out, int phase, hipStream_t);
+  // the two halves of vae_backward as calls of their own (decoder: loss gradients + decoder backward up to dz; sampler: dz += seed_scale
+  // dz_extra, then the sampler's backward and the weight gradients); null: the family has no split backward
+  int (*vae_backward_decoder)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                              DevFloat beta, float dloss, float* workspace, size_t wsf, hipStream_t);
+  int (*vae_backward_sampler)(const ardae_model_desc&, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                              const float* dz_extra, DevFloat seed_scale, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t);
 };
+inline unsigned no_caps(const ardae_model_desc&) { return 0; }
+// the flag rule of an implicit family's desc_check: nothing outside `allowed`, and known log-variance clip codes
+inline int desc_flags_ok(const ardae_model_desc* d, int allowed) {
+  ARDAE_CHECK_ARG((d->flags & ~allowed) == 0,
+                  "model: unknown flags %d (ARDAE_MODEL_NO_CENTER / the sampler-head bits / ARDAE_MODEL_CLIPPED: residual-conv kinds 5 / 6 only; "
+                  "the log-variance clip codes: kinds 3 / 7 only)", d->flags);
+  ARDAE_CHECK_ARG(((d->flags >> ARDAE_MODEL_CLIP_Z0_SHIFT) & 15) <= 10 && ((d->flags >> ARDAE_MODEL_CLIP_Z_SHIFT) & 15) <= 10, "model: unknown log-variance clip code");
+  return 0;
+}
 // the table (csrc/model.hip): the row of a kind, null where the number is not a kind; family(d) where the kind has been checked
 const Family* family_of(int kind);
 inline const Family& family(const ardae_model_desc* d) { return *family_of(d->kind); }
@@ -216,7 +240,7 @@ template <class Layout, class Packed> int family_pack(const ardae_model_desc& d,
 // What every entry point opens with: the layout, the panel offsets, the arena, and the buffers the family's carve(P, ws, ..., W)
 // takes out of it.  `auto& [P, K, ws, W] = entry;` names them.
 template <class Layout, class Packed, class Ws> struct Entry {
-  const Layout P; const Packed K; Bump ws; Ws W;
+  const Layout P; const Packed K; Bump ws; Ws W{};
   template <class... CarveArgs> Entry(const ardae_model_desc& d, float* workspace, size_t wsf, CarveArgs... args) : P(d), K(P), ws(workspace, wsf) {
     carve(P, K, ws, args..., W);
   }

@@ -95,7 +95,7 @@ struct MlpDecoder {
     stack.wgrads(wl, R, z, u.hid.data(), u.dhid.data());
   }
 
-  // ardae_model_decode: workspace floats (mode 2) and the call
+  // ardae_model_decode: workspace floats (mode 2) and the call (out1: the entry point has asked for it where nh == 2, CAP_GAUSS_DECODER)
   size_t decode_floats(size_t R) const {
     Bump ws;
     Bufs u;
@@ -108,11 +108,18 @@ struct MlpDecoder {
     Bufs u;
     carve(ws, (size_t)R, false, u);
     ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
-    ARDAE_CHECK_ARG(nh == 1 || out1, "aux_model_decode: the Gaussian decoder returns mean (out0) and logvar (out1)");
     float* const out[2] = {out0, out1};
     return fwd(params, packed, act, R, z, u.hid.data(), out, st);
   }
 };
+
+// the descriptor rules of the implicit MLP families (allowed: the flag bits the family knows)
+inline int mlp_desc_check(const ardae_model_desc* d, int allowed) {
+  ARDAE_TRY(desc_flags_ok(d, allowed));
+  ARDAE_CHECK_ARG(d->input_dim >= 1 && d->noise_dim >= 1 && d->h_dim >= 1 && d->z_dim >= 1 && d->n_layers >= 1 && d->n_layers <= 4, "model: bad dimensions");
+  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
+  return 0;
+}
 
 // the `decode` member of a Family whose Packed holds its MlpDecoder as `dec` (and whose Layout the activation as `act`)
 template <class Layout, class Packed>

@@ -17,6 +17,7 @@
 #include "convvae.h"
 #include "resmodel.h"
 #include "vaemodel.h"
+#include "ipmodel.h"
 #include "elementwise.h"
 #include "mlp.h"
 
@@ -67,34 +68,6 @@ struct ModelPacked {
   explicit ModelPacked(const ModelLayout& P, PackList&& sizing = PackList()) : ModelPacked(P, sizing) {}   // offsets only
 };
 
-int desc_ok(const ardae_model_desc* d) {
-  ARDAE_CHECK_ARG(d != nullptr, "model: desc is NULL");
-  ARDAE_CHECK_ARG(family_of(d->kind) != nullptr,
-                  "model: kind must be 0 (MNISTIPVAE), 1 (ToyIPVAE concat), 2 (ConvIPVAE), 3 (MNISTAuxIPVAE), 4 (MNISTConvAuxIPVAE), 5 (ResConvIPVAE), "
-                  "6 (MNISTResConvAuxIPVAE), 7 (ToyAuxIPVAE), 8 (MNISTVAE), 9 (ToyVAE), 11 (MNISTConvVAE) or 12 (MNISTResConvVAE)");
-  if (family(d).gauss) return family(d).gauss->desc_check(d);      // the Gaussian-posterior baselines: no noise input, their own rules
-  ARDAE_CHECK_ARG((d->flags & ~(ARDAE_MODEL_NO_CENTER | ARDAE_MODEL_HEAD_MASK | ARDAE_MODEL_CLIPPED | ARDAE_MODEL_CLIP_MASK)) == 0 &&
-                      ((d->kind == 5 || d->kind == 6) ? (d->flags & ARDAE_MODEL_CLIP_MASK) == 0
-                                                      : ((d->kind == 3 || d->kind == 7) ? (d->flags & ~ARDAE_MODEL_CLIP_MASK) == 0 : d->flags == 0)),
-                  "model: unknown flags %d (ARDAE_MODEL_NO_CENTER / the sampler-head bits / ARDAE_MODEL_CLIPPED: residual-conv kinds 5 / 6 only; "
-                  "the log-variance clip codes: kinds 3 / 7 only)", d->flags);
-  ARDAE_CHECK_ARG(((d->flags >> ARDAE_MODEL_CLIP_Z0_SHIFT) & 15) <= 10 && ((d->flags >> ARDAE_MODEL_CLIP_Z_SHIFT) & 15) <= 10, "model: unknown log-variance clip code");
-  if ((d->kind == 5 || d->kind == 6)) {
-    ARDAE_CHECK_ARG(d->input_dim == 784 && d->noise_dim >= 1 && d->z_dim >= 1 && d->h_dim >= 1 && d->act == ACT_ELU && (d->kind == 6 || (d->n_layers >= 1 && d->n_layers <= 4)),
-                    "model: the residual-conv models are 28x28x1, ELU, and (kind 5) 1 .. 4 hidden layers in the sampler head");
-    return 0;
-  }
-  if (d->kind == 2 || d->kind == 4) {
-    ARDAE_CHECK_ARG(d->input_dim == 784 && d->noise_dim >= 1 && d->z_dim >= 1, "model: ConvIPVAE is hard-wired to 28x28x1 inputs (input_dim 784)");
-    ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
-    return 0;
-  }
-  ARDAE_CHECK_ARG(d->input_dim >= 1 && d->noise_dim >= 1 && d->h_dim >= 1 && d->z_dim >= 1 && d->n_layers >= 1 && d->n_layers <= 4,
-                  "model: bad dimensions");
-  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
-  return 0;
-}
-
 // saved activations (in `workspace`, same carving in forward and backward)
 struct ModelWs {
   float* x2;
@@ -126,35 +99,6 @@ void carve(const ModelLayout& P, const ModelPacked& K, Bump& ws, int B, int nz, 
   W.drb = ws.take((size_t)B * h);
 }
 using MlpEntry = Entry<ModelLayout, ModelPacked, ModelWs>;
-
-// every weight-gradient problem of the backward, with its scratch taken from ws (x: the images; noise: the sampler's draw)
-void model_wgrads(const ModelLayout& P, const ModelPacked& K, const ModelWs& W, const float* x, const float* noise, int B, int R, WgradList& wl, Bump& ws) {
-  const int h = P.h;
-  const size_t ns = P.stack.size();
-  K.dec.wgrads(wl, R, W.z, W.D);
-  for (size_t i = 0; i < ns; ++i) {
-    const Lin& L = P.stack[i];
-    const float* G = (i == ns - 1) ? W.D.dz : W.dt[i + 1];
-    if (i == 0) wl.push(B, L.out, h, W.drb, W.e[P.inp.size()], h, wl.g(L.w), L.in, nullptr);        // per-image hidden part
-    else wl.push(R, L.out, h, G, W.t[i], h, wl.g(L.w), L.in, P.stack_noise[i] ? nullptr : wl.g(L.b));
-    if (P.stack_noise[i]) wl.push(R, L.out, P.nd, G, noise, P.nd, wl.g(L.w + h), L.in, wl.g(L.b));   // noise part (+ bias)
-  }
-  K.inp.wgrads(wl, B, P.kind == 0 ? W.x2 : x, W.e.data(), W.de.data());
-  wl.assign(ws, (int)(P.heads.size() + P.dec.size() + 2 * ns + P.inp.size()));   // the hint counts a noise part for every stack layer
-}
-
-// dry run of carve() and the weight-gradient list on a null arena (mode 0: the sampler's buffers only)
-size_t workspace_floats(const ModelLayout& P, int B, int nz, int mode) {
-  const ModelPacked K(P);
-  Bump ws;
-  ModelWs W;
-  carve(P, K, ws, B, nz, mode, W);
-  if (mode != 0) {
-    WgradList wl(nullptr);
-    model_wgrads(P, K, W, nullptr, nullptr, B, B * nz, wl, ws);
-  }
-  return ws.off;
-}
 
 // sampler trunk (once per image): inp_encode on B rows, then rb = inp . S_1[:, :h]^T + b_S1.  Fills W.e, W.rb.
 int encode_trunk(const ModelLayout& P, const ModelPacked& K, const float* params, const float* packed, const float* x, int B,
@@ -203,97 +147,94 @@ int encode_stack(const ModelLayout& P, const ModelPacked& K, const float* params
   return 0;
 }
 
-// sampler forward: fills W.e, W.rb, W.t, W.z (and copies z to z_out when given)
-int encode_fwd(const ModelLayout& P, const ModelPacked& K, const float* params, const float* packed, const float* x,
-               const float* noise, int B, int nz, ModelWs& W, float* z_out, bool keep_hidden, hipStream_t st) {
-  ARDAE_TRY(encode_trunk(P, K, params, packed, x, B, W, st));
-  if (z_out && !keep_hidden)     // forward-only: the last layer writes the caller's buffer itself (one launch less per encode)
-    return encode_stack(P, K, params, packed, noise, B, nz, W.rb, W.t, z_out, false, st);
-  ARDAE_TRY(encode_stack(P, K, params, packed, noise, B, nz, W.rb, W.t, W.z, keep_hidden, st));
-  if (z_out) {
-    ARDAE_TRY(launch_copy(W.z, (size_t)B * nz * P.zd, z_out, st));
+// ------------------------------------------------------------------------------------------------ kinds 0 / 1 as a family
+// What the shared algorithm (csrc/ipmodel.h) needs to know of the MLP models: one trunk, two stacks.
+struct MlpTraits : IpTraitsBase {
+  using Layout = ModelLayout; using Packed = ModelPacked; using Ws = ModelWs; using Entry = MlpEntry;
+  static constexpr bool mlp_decoder = true;
+  static constexpr bool direct_z = true;      // a forward-only encode: the last stack layer writes the caller's buffer itself (one launch less)
+  static int desc_check(const ardae_model_desc* d) { return mlp_desc_check(d, 0); }
+  static unsigned caps(const ardae_model_desc& d) { return d.kind == 1 ? CAP_GAUSS_DECODER : 0; }
+  static IpBufs bufs(const ModelWs& W) { return {W.z, W.D.o[0], W.D.o[1], W.D.dox[0], W.D.dox[1], W.D.dzq, W.D.dz, W.rec_row, W.pri_row}; }
+  // every weight-gradient problem of the backward, with its scratch taken from ws (x: the images; noise: the sampler's draw)
+  static void wgrads(const ModelLayout& P, const ModelPacked& K, const ModelWs& W, const float* x, const float* noise, int B, int nz, WgradList& wl, Bump& ws) {
+    const int R = B * nz, h = P.h;
+    const size_t ns = P.stack.size();
+    K.dec.wgrads(wl, R, W.z, W.D);
+    for (size_t i = 0; i < ns; ++i) {
+      const Lin& L = P.stack[i];
+      const float* G = (i == ns - 1) ? W.D.dz : W.dt[i + 1];
+      if (i == 0) wl.push(B, L.out, h, W.drb, W.e[P.inp.size()], h, wl.g(L.w), L.in, nullptr);        // per-image hidden part
+      else wl.push(R, L.out, h, G, W.t[i], h, wl.g(L.w), L.in, P.stack_noise[i] ? nullptr : wl.g(L.b));
+      if (P.stack_noise[i]) wl.push(R, L.out, P.nd, G, noise, P.nd, wl.g(L.w + h), L.in, wl.g(L.b));   // noise part (+ bias)
+    }
+    K.inp.wgrads(wl, B, P.kind == 0 ? W.x2 : x, W.e.data(), W.de.data());
+    wl.assign(ws, (int)(P.heads.size() + P.dec.size() + 2 * ns + P.inp.size()));   // the hint counts a noise part for every stack layer
   }
+  // beside the carve: a zero-noise buffer for encode(std=0), or (encode_pair) the zero-noise stack's hidden rows and its zero noise block (B rows each)
+  static size_t extra_floats(const ModelLayout& P, int B, int nz, int mode) {
+    if (mode == 3) return (P.stack.size() - 1) * al64((size_t)B * P.h) + al64((size_t)B * P.nd);
+    return al64((size_t)B * nz * P.nd);
+  }
+  static size_t noise_floats(const ModelLayout& P, int B, int nz) { return (size_t)B * nz * P.nd; }
+  static float* zero_noise(Entry& e, size_t n) { return e.ws.take(n); }
+  // fills W.e, W.rb, and (training forward) W.t, W.z
+  static int sampler_fwd(Entry& e, const float* params, const float* packed, const float* x, const float* noise, int B, int nz, const IpEncodeOut* enc,
+                         hipStream_t st) {
+    ARDAE_TRY(encode_trunk(e.P, e.K, params, packed, x, B, e.W, st));
+    return encode_stack(e.P, e.K, params, packed, noise, B, nz, e.W.rb, e.W.t, enc && enc->z_out ? enc->z_out : e.W.z, enc == nullptr, st);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {
+    return e.K.dec.fwd(params, packed, e.P.act, R, z, e.W.D.hid.data(), e.W.D.o, st);
+  }
+  static int decoder_bwd(Entry& e, const float* packed, int R, Grads&, hipStream_t st) { return e.K.dec.bwd(packed, e.P.act, R, e.W.D, st); }
+  static int sampler_bwd(Entry& e, const float*, const float* packed, const float* x, const float* noise, int B, int nz, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int R = B * nz, h = P.h, act = P.act;
+    const size_t ns = P.stack.size(), ninp = P.inp.size();
+    for (size_t i = ns - 1; i >= 1; --i)
+      ARDAE_TRY(dense_bwd(act, R, h, (i == ns - 1) ? W.D.dz : W.dt[i + 1], P.stack[i].out, packed + K.sh_b[i], W.t[i], W.dt[i], st));
+    ARDAE_TRY(launch_segment_sum(W.dt[1], h, B, nz, h, 1.0f, W.drb, h, st));
+    ARDAE_TRY(dense_bwd(act, B, h, W.drb, h, packed + K.sh_b[0], W.e[ninp], W.de[ninp], st));
+    ARDAE_TRY(K.inp.bwd(packed, act, B, W.e.data(), W.de.data(), st));
+    // weight gradients: one batched launch
+    WgradList wl(g.grads, g.beta);
+    wgrads(P, K, W, x, noise, B, nz, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
+    return wl.launch(st);
+  }
+};
+
+// ardae_model_encode_pair in one pass: z0 = encode(x, std=0) and z = forward_hidden(x, nz) share the per-image trunk
+int mlp_encode_pair(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
+                    float* workspace, size_t wsf, float* z0_out, float* z_out, int phase, hipStream_t st) {
+  MlpEntry entry(d, workspace, wsf, B, nz, 0);
+  auto& [P, K, ws, W] = entry;
+  std::vector<float*> t0(P.stack.size(), nullptr);
+  for (size_t i = 1; i < P.stack.size(); ++i) t0[i] = ws.take((size_t)B * P.h);
+  float* zero = ws.take((size_t)B * P.nd);
+  ARDAE_CHECK_ARG(ws.ok, "model_encode_pair: internal workspace accounting error");
+  if (phase != 2) {
+    ARDAE_TRY(launch_fill(zero, (size_t)B * P.nd, 0.f, st));
+    ARDAE_TRY(encode_trunk(P, K, params, packed, x, B, W, st));
+    ARDAE_TRY(encode_stack(P, K, params, packed, zero, B, 1, W.rb, t0, z0_out, false, st));    // encode(x, std=0): the draw is multiplied by 0
+  }
+  if (phase != 1) ARDAE_TRY(encode_stack(P, K, params, packed, noise, B, nz, W.rb, W.t, z_out, false, st));   // forward_hidden(x, nz); W.rb from phase 1
   return 0;
 }
 
-// extra floats of the encode_pair workspace: the zero-noise stack's hidden rows and its zero noise block (B rows each)
-size_t encode_pair_extra(const ModelLayout& P, int B) {
-  return (P.stack.size() - 1) * al64((size_t)B * P.h) + al64((size_t)B * P.nd);
+constexpr Family mlp_family() {
+  Family f = ip_family<MlpTraits>();
+  f.encode_pair = mlp_encode_pair;
+  f.vae_backward_decoder = ip_vae_backward_decoder<MlpTraits>;
+  f.vae_backward_sampler = ip_vae_backward_sampler<MlpTraits>;
+  return f;
 }
+const Family MLP_FAMILY = mlp_family();
 
-// ------------------------------------------------------------------------------------------------ kinds 0 / 1 as a family
-size_t mlp_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  const ModelLayout P(d);
-  if (mode == 2) return ModelPacked(P).dec.decode_floats((size_t)B * nz);
-  if (mode == 3) return workspace_floats(P, B, nz, 0) + encode_pair_extra(P, B);   // ardae_model_encode_pair
-  return workspace_floats(P, B, nz, mode) + (size_t)al64((size_t)B * nz * P.nd);   // + a zero-noise buffer for encode(std=0)
-}
-
-int mlp_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-               float* workspace, size_t wsf, float* z_out, float*, hipStream_t st, const float*) {
-  MlpEntry entry(d, workspace, wsf, B, nz, 0);
-  auto& [P, K, ws, W] = entry;
-  float* zero = noise ? nullptr : ws.take((size_t)B * nz * P.nd);
-  ARDAE_CHECK_ARG(ws.ok, "model_encode: internal workspace accounting error");
-  ARDAE_TRY(noise_or_zero(noise, zero, (size_t)B * nz * P.nd, st));
-  return encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, false, st);
-}
-
-int mlp_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                    DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  MlpEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "model_vae_forward: internal workspace accounting error");
-  const int R = B * nz;
-  ARDAE_TRY(encode_fwd(P, K, params, packed, x, noise, B, nz, W, z_out, true, st));
-  ARDAE_TRY(K.dec.fwd(params, packed, P.act, R, W.z, W.D.hid.data(), W.D.o, st));
-  ARDAE_TRY(launch_vae_loss(P.kind, W.D.o[0], W.D.o[1], x, W.z, R, nz, P.D, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
-  return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
-}
-
-// phases: 1 = loss gradients + decoder backward up to dz (needs nothing from the cDAE), 2 = entropy seed + sampler backward +
-// weight gradients, 3 = both.  With phases == 3 the (pre-scaled) seed enters through the loss kernel; with phases == 2 it is
-// added to dz as seed_scale * dz_extra.
-int vae_backward_impl(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise,
-                      int B, int nz, DevFloat beta, float dloss, const float* dz_extra, DevFloat seed_scale, float* workspace,
-                      size_t workspace_floats_, float* grads, float grads_beta, int phases, hipStream_t st) {
-  MlpEntry entry(d, workspace, workspace_floats_, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  const int R = B * nz, h = P.h, act = P.act;
-  const size_t ns = P.stack.size(), ninp = P.inp.size();
-  const float gscale = dloss / (float)R;
-  if (phases & 1) {
-    ARDAE_TRY(launch_vae_loss(P.kind, W.D.o[0], W.D.o[1], x, W.z, R, nz, P.D, P.zd, beta, 1, gscale, phases == 3 ? dz_extra : nullptr, W.rec_row, W.pri_row,
-                              W.D.dox[0], W.D.dox[1], W.D.dzq, st));
-    ARDAE_TRY(K.dec.bwd(packed, act, R, W.D, st));
-  }
-  if (!(phases & 2)) return 0;
-  if (phases == 2 && dz_extra) ARDAE_TRY(launch_axpy(dz_extra, (int64_t)R * P.zd, seed_scale, W.D.dz, st));   // + the entropy seed
-  // sampler backward
-  for (size_t i = ns - 1; i >= 1; --i)
-    ARDAE_TRY(dense_bwd(act, R, h, (i == ns - 1) ? W.D.dz : W.dt[i + 1], P.stack[i].out, packed + K.sh_b[i], W.t[i], W.dt[i], st));
-  ARDAE_TRY(launch_segment_sum(W.dt[1], h, B, nz, h, 1.0f, W.drb, h, st));
-  ARDAE_TRY(dense_bwd(act, B, h, W.drb, h, packed + K.sh_b[0], W.e[ninp], W.de[ninp], st));
-  ARDAE_TRY(K.inp.bwd(packed, act, B, W.e.data(), W.de.data(), st));
-  // weight gradients: one batched launch
-  WgradList wl(grads, grads_beta);
-  model_wgrads(P, K, W, x, noise, B, R, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "model_vae_backward: internal workspace accounting error");
-  return wl.launch(st);
-}
-
-int mlp_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta,
-                     hipStream_t st) {
-  return vae_backward_impl(d, params, packed, x, noise, B, nz, beta, dloss, dz_extra, 1.f, workspace, wsf, grads, grads_beta, 3, st);
-}
-
-const Family MLP_FAMILY = {family_param_floats<ModelLayout, ModelPacked>, family_packed_floats<ModelLayout, ModelPacked>, mlp_workspace_floats,
-                           family_pack<ModelLayout, ModelPacked>, mlp_encode, mlp_decode<ModelLayout, ModelPacked>, mlp_vae_forward, mlp_vae_backward};
-
-// ------------------------------------------------------------------------------------------------ the families, by kind
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ the families, by kind
 // (host_util.h) the one table by kind; desc_ok() checks the kind against it
 const Family* family_of(int kind) {
   static const Family* const by_kind[13] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY,
@@ -304,6 +245,15 @@ const Family* family_of(int kind) {
 }  // namespace ardae
 
 using namespace ardae;
+
+// the number is a kind, then the family's own rules
+static int desc_ok(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d != nullptr, "model: desc is NULL");
+  ARDAE_CHECK_ARG(family_of(d->kind) != nullptr,
+                  "model: kind must be 0 (MNISTIPVAE), 1 (ToyIPVAE concat), 2 (ConvIPVAE), 3 (MNISTAuxIPVAE), 4 (MNISTConvAuxIPVAE), 5 (ResConvIPVAE), "
+                  "6 (MNISTResConvAuxIPVAE), 7 (ToyAuxIPVAE), 8 (MNISTVAE), 9 (ToyVAE), 11 (MNISTConvVAE) or 12 (MNISTResConvVAE)");
+  return family(d).desc_check(d);
+}
 
 extern "C" {
 
@@ -345,38 +295,25 @@ int ardae_model_encode_pair(const ardae_model_desc* d, const float* params, cons
   ARDAE_CHECK_ARG(params && packed && x && (noise || phase == 1) && workspace && z0_out && z_out, "model_encode_pair: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && nz > 0 && (int64_t)B * nz < (int64_t)1 << 30, "model_encode_pair: bad batch (B=%d nz=%d)", B, nz);
   ARDAE_CHECK_ARG(workspace_floats_ >= ardae_model_workspace_floats(d, B, nz, 3), "model_encode_pair: workspace too small");
-  if (d->kind >= 2) {   // conv / aux samplers: two passes over the same workspace
-    if (phase != 2) ARDAE_TRY(ardae_model_encode(d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, stream));
-    if (phase == 1) return 0;
-    return ardae_model_encode(d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, stream);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  MlpEntry entry(*d, workspace, workspace_floats_, B, nz, 0);
-  auto& [P, K, ws, W] = entry;
-  std::vector<float*> t0(P.stack.size(), nullptr);
-  for (size_t i = 1; i < P.stack.size(); ++i) t0[i] = ws.take((size_t)B * P.h);
-  float* zero = ws.take((size_t)B * P.nd);
-  ARDAE_CHECK_ARG(ws.ok, "model_encode_pair: internal workspace accounting error");
-  if (phase != 2) {
-    ARDAE_TRY(launch_fill(zero, (size_t)B * P.nd, 0.f, st));
-    ARDAE_TRY(encode_trunk(P, K, params, packed, x, B, W, st));
-    ARDAE_TRY(encode_stack(P, K, params, packed, zero, B, 1, W.rb, t0, z0_out, false, st));    // encode(x, std=0): the draw is multiplied by 0
-  }
-  if (phase != 1) ARDAE_TRY(encode_stack(P, K, params, packed, noise, B, nz, W.rb, W.t, z_out, false, st));   // forward_hidden(x, nz); W.rb from phase 1
-  return 0;
+  if (family(d).encode_pair)
+    return family(d).encode_pair(*d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z0_out, z_out, phase, (hipStream_t)stream);
+  // no fused pair (conv / aux samplers): two passes over the same workspace
+  if (phase != 2) ARDAE_TRY(ardae_model_encode(d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, stream));
+  if (phase == 1) return 0;
+  return ardae_model_encode(d, params, packed, x, noise, B, nz, workspace, workspace_floats_, z_out, stream);
 }
 
 int ardae_model_encode_hidden_raw(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* raw0, int B,
                                   float* workspace, size_t workspace_floats_, float* z0_out, float* hidden_out, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, 1, workspace, workspace_floats_, 0));
-  ARDAE_CHECK_ARG(d->kind == 6 && (d->flags & ARDAE_MODEL_CLIPPED), "model_encode_hidden_raw: the clipped aux-resconv class only (kind 6 + ARDAE_MODEL_CLIPPED)");
+  ARDAE_CHECK_ARG(family(d).caps(*d) & CAP_HIDDEN_RAW, "model_encode_hidden_raw: the clipped aux-resconv class only (kind 6 + ARDAE_MODEL_CLIPPED)");
   ARDAE_CHECK_ARG(z0_out || hidden_out, "model_encode_hidden_raw: nothing to return");
   return family(d).encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, (hipStream_t)stream, raw0);
 }
 int ardae_model_encode_hidden(const ardae_model_desc* d, const float* params, const float* packed, const float* x, int B, float* workspace,
                               size_t workspace_floats_, float* z0_out, float* hidden_out, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, 1, workspace, workspace_floats_, 0));
-  ARDAE_CHECK_ARG((d->kind == 3 || d->kind == 7) || d->kind == 4 || d->kind == 6, "model_encode_hidden: the hidden1a context exists for the aux models only (kinds 3, 4, 6, 7)");
+  ARDAE_CHECK_ARG(family(d).caps(*d) & CAP_HIDDEN, "model_encode_hidden: the hidden1a context exists for the aux models only (kinds 3, 4, 6, 7)");
   ARDAE_CHECK_ARG(hidden_out, "model_encode_hidden: hidden_out is NULL");
   return family(d).encode(*d, params, packed, x, nullptr, B, 1, workspace, workspace_floats_, z0_out, hidden_out, (hipStream_t)stream, nullptr);   // z0_out may be NULL
 }
@@ -385,7 +322,7 @@ int ardae_model_decode(const ardae_model_desc* d, const float* params, const flo
                        size_t workspace_floats_, float* out0, float* out1, void* stream) {
   ARDAE_TRY(desc_ok(d));
   ARDAE_CHECK_ARG(params && packed && z && workspace && out0 && R > 0, "model_decode: bad arguments");
-  ARDAE_CHECK_ARG(d->kind != 1 || out1, "model_decode: the Gaussian decoder needs out1 (logvar)");
+  ARDAE_CHECK_ARG(!(family(d).caps(*d) & CAP_GAUSS_DECODER) || out1, "model_decode: the Gaussian decoder needs out1 (logvar)");
   ARDAE_CHECK_ARG(workspace_floats_ >= family(d).workspace_floats(*d, R, 1, 2), "model_decode: workspace too small");
   return family(d).decode(*d, params, packed, z, R, workspace, workspace_floats_, out0, (hipStream_t)stream, out1);
 }
@@ -393,7 +330,7 @@ int ardae_model_decode(const ardae_model_desc* d, const float* params, const flo
 int ardae_model_loss_rows(const ardae_model_desc* d, const float* out0, const float* out1, const float* x, const float* z, int rows,
                           int nz, float* recon_row, float* prior_row, void* stream) {
   ARDAE_TRY(desc_ok(d));
-  return launch_vae_loss(d->kind == 1 || d->kind == 7 || d->kind == 9 ? 1 : 0, out0, out1, x, z, rows, nz, d->input_dim, d->z_dim, 1.f, 0, 0.f, nullptr, recon_row, prior_row, nullptr,
+  return launch_vae_loss(family(d).caps(*d) & CAP_GAUSS_DECODER ? 1 : 0, out0, out1, x, z, rows, nz, d->input_dim, d->z_dim, 1.f, 0, 0.f, nullptr, recon_row, prior_row, nullptr,
                          nullptr, nullptr, (hipStream_t)stream);
 }
 
@@ -419,9 +356,8 @@ static int vae_backward_decoder_entry(const ardae_model_desc* d, const float* pa
                                       int B, int nz, DevFloat beta, float dloss, float* workspace, size_t workspace_floats_, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise, "model_vae_backward_decoder: null pointer argument");
-  ARDAE_CHECK_ARG(d->kind < 2, "model_vae_backward_decoder: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
-  return vae_backward_impl(*d, params, packed, x, noise, B, nz, beta, dloss, nullptr, 0.f, workspace, workspace_floats_, nullptr, 0.f, 1,
-                           (hipStream_t)stream);
+  ARDAE_CHECK_ARG(family(d).vae_backward_decoder, "model_vae_backward_decoder: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
+  return family(d).vae_backward_decoder(*d, params, packed, x, noise, B, nz, beta, dloss, workspace, workspace_floats_, (hipStream_t)stream);
 }
 
 static int vae_backward_sampler_entry(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,
@@ -429,9 +365,9 @@ static int vae_backward_sampler_entry(const ardae_model_desc* d, const float* pa
                                       float* grads, float grads_beta, void* stream) {
   ARDAE_TRY(model_common(d, params, packed, x, B, nz, workspace, workspace_floats_, 1));
   ARDAE_CHECK_ARG(noise && grads, "model_vae_backward_sampler: null pointer argument");
-  ARDAE_CHECK_ARG(d->kind < 2, "model_vae_backward_sampler: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
-  return vae_backward_impl(*d, params, packed, x, noise, B, nz, 0.f, 0.f, dz_extra, seed_scale, workspace, workspace_floats_, grads,
-                           grads_beta, 2, (hipStream_t)stream);
+  ARDAE_CHECK_ARG(family(d).vae_backward_sampler, "model_vae_backward_sampler: the conv model and the aux model have no split backward (use ardae_model_vae_backward)");
+  return family(d).vae_backward_sampler(*d, params, packed, x, noise, B, nz, dz_extra, seed_scale, workspace, workspace_floats_, grads, grads_beta,
+                                        (hipStream_t)stream);
 }
 
 int ardae_model_vae_forward(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* noise,

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "resmodel.h"
 #include "vaemodel.h"
+#include "ipmodel.h"
 
 namespace ardae {
 namespace {
@@ -459,18 +460,18 @@ int resvae_desc_check(const ardae_model_desc* d) {
   return 0;
 }
 
-int res_desc_ok(const ardae_model_desc& d) {
-  if (d.kind == 12) return resvae_desc_check(&d);
-  ARDAE_CHECK_ARG(d.input_dim == 784 && d.noise_dim >= 1 && d.z_dim >= 1 && d.h_dim >= 1, "model: the residual-conv models are hard-wired to 28x28x1 inputs");
-  ARDAE_CHECK_ARG(d.act == ACT_ELU, "model: the residual-conv models use ELU (--model-nonlin elu; models/ivae/auxresconv.py:69 asserts it)");
-  ARDAE_CHECK_ARG(d.kind != 5 || (d.n_layers >= 1 && d.n_layers <= 4), "model: ResConvIPVAE takes --model-n-layers 1 .. 4");
-  ARDAE_CHECK_ARG(d.kind != 5 || ((d.flags >> 1) & 7) <= HEAD_RES_MLP_LIN, "model: unknown sampler head %d (desc.flags bits 1-3)", (d.flags >> 1) & 7);
-  ARDAE_CHECK_ARG(d.kind == 5 || ((d.flags >> 1) & 7) == 0, "model: the sampler-head bits of desc.flags belong to kind 5");
-  ARDAE_CHECK_ARG(d.kind == 6 || !(d.flags & ARDAE_MODEL_CLIPPED), "model: ARDAE_MODEL_CLIPPED belongs to kind 6");
-  if (d.kind == 5) {   // a concat block needs its projected skip (same_dim would make the skip the 612-wide concat itself)
-    const int ht = (d.flags >> 1) & 7;
-    ARDAE_CHECK_ARG(ht == HEAD_MLP || 512 + d.noise_dim != d.h_dim, "model: ResConvIPVAE with c_dim + noise_dim == h_dim (identity skip over the concat input) is not built");
-  }
+// the descriptor rules of kinds 5 / 6
+int res_desc_check(const ardae_model_desc* d) {
+  ARDAE_TRY(desc_flags_ok(d, ARDAE_MODEL_NO_CENTER | ARDAE_MODEL_HEAD_MASK | ARDAE_MODEL_CLIPPED));
+  ARDAE_CHECK_ARG(d->input_dim == 784 && d->noise_dim >= 1 && d->z_dim >= 1 && d->h_dim >= 1 && d->act == ACT_ELU && (d->kind == 6 || (d->n_layers >= 1 && d->n_layers <= 4)),
+                  "model: the residual-conv models are 28x28x1, ELU, and (kind 5) 1 .. 4 hidden layers in the sampler head");
+  const int ht = (d->flags >> 1) & 7;
+  ARDAE_CHECK_ARG(d->kind != 5 || ht <= HEAD_RES_MLP_LIN, "model: unknown sampler head %d (desc.flags bits 1-3)", ht);
+  ARDAE_CHECK_ARG(d->kind == 5 || ht == 0, "model: the sampler-head bits of desc.flags belong to kind 5");
+  ARDAE_CHECK_ARG(d->kind == 6 || !(d->flags & ARDAE_MODEL_CLIPPED), "model: ARDAE_MODEL_CLIPPED belongs to kind 6");
+  // a concat block needs its projected skip (same_dim would make the skip the 612-wide concat itself)
+  ARDAE_CHECK_ARG(d->kind != 5 || ht == HEAD_MLP || 512 + d->noise_dim != d->h_dim,
+                  "model: ResConvIPVAE with c_dim + noise_dim == h_dim (identity skip over the concat input) is not built");
   return 0;
 }
 
@@ -702,12 +703,6 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
   }
 }
 
-size_t res_workspace(const ResLayout& P, int B, int nz, int mode) {
-  Bump ws;
-  ResWs W;
-  carve(P, ResPacked(P), ws, B, nz, mode, W);
-  return ws.off;
-}
 using ResEntry = Entry<ResLayout, ResPacked, ResWs>;
 
 // ------------------------------------------------------------------------------------------------ forward pieces
@@ -875,20 +870,7 @@ int trunk_wn_bwd(const ResLayout& P, const ResPacked& K, const float* packed, Re
 }
 
 // ================================================================================================ entry points
-size_t res_param_floats(const ardae_model_desc& d) { return res_desc_ok(d) ? 0 : ResLayout(d).total; }
-size_t res_packed_floats(const ardae_model_desc& d) {
-  if (res_desc_ok(d)) return 0;
-  PackList pl;
-  ResPacked(ResLayout(d), pl);
-  return pl.total();
-}
-size_t res_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  if (res_desc_ok(d)) return 0;
-  return res_workspace(ResLayout(d), B, nz, mode == 3 ? 0 : mode);
-}
-
 int res_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  ARDAE_TRY(res_desc_ok(d));
   const ResLayout P(d);
   PackList pl(params, packed);
   const ResPacked K(P, pl);
@@ -922,159 +904,154 @@ int res_pack(const ardae_model_desc& d, const float* params, float* packed, hipS
   return pl.launch(st);
 }
 
-int res_encode(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                     float* workspace, size_t wsf, float* z_out, float* hidden_out, hipStream_t st, const float* raw0) {
-  ResEntry entry(d, workspace, wsf, B, nz, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "res model encode: workspace too small");
-  ARDAE_CHECK_ARG(!hidden_out || (P.kind == 6 && nz == 1), "res model: the hidden1a context is the aux model's h at nz = 1");
-  const float* nzp = noise;
-  ARDAE_TRY(noise_or_zero(nzp, W.zero, (size_t)B * nz * (P.nd + P.zd), st));
-  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-  ARDAE_CHECK_ARG(!raw0 || (P.clipped && !noise), "res model: raw0 is the clipped class's unscaled eps0 of a std = 0 pass (noise NULL)");
-  return sampler_fwd(P, K, params, packed, nzp, B, nz, W, z_out ? z_out : W.z, hidden_out, st, raw0, noise == nullptr);
-}
-
-int res_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
-                     float* out0, hipStream_t st, float*) {
-  ResEntry entry(d, workspace, wsf, R, 1, 2);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "res model decode: workspace too small");
-  return decoder_fwd(P, K, params, packed, z, R, W, out0, st);
-}
-
-int res_vae_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                          DevFloat beta, float* workspace, size_t wsf, float* z_out, float* losses, hipStream_t st) {
-  ResEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "res model vae_forward: workspace too small");
-  const int R = B * nz;
-  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-  ARDAE_TRY(sampler_fwd(P, K, params, packed, noise, B, nz, W, W.z, nullptr, st));
-  ARDAE_TRY(launch_copy(W.z, (size_t)R * P.zd, z_out, st));
-  ARDAE_TRY(decoder_fwd(P, K, params, packed, W.z, R, W, nullptr, st));
-  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, R, nz, 784, P.zd, beta, 0, 0.f, nullptr, W.rec_row, W.pri_row, nullptr, nullptr, nullptr, st));
-  return launch_vae_loss_finalize(W.rec_row, W.pri_row, R, beta, losses, st);
-}
-
-int res_vae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* noise, int B, int nz,
-                           DevFloat beta, float dloss, const float* dz_extra, float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  ResEntry entry(d, workspace, wsf, B, nz, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "res model vae_backward: workspace too small");
-  const int R = B * nz;
-  const float gscale = dloss / (float)R;
-  GradMap gm{P, W.dweff, W.dbias, 0, {}, params, packed, grads};
+GradMap grad_map(ResEntry& e, const float* params, const float* packed, float* grads, float grads_beta) {
+  GradMap gm{e.P, e.W.dweff, e.W.dbias, 0, {}, params, packed, grads};
   gm.grads_beta = grads_beta;
-  // loss gradients: d logits, dz = gscale beta z + dz_extra
-  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, R, nz, 784, P.zd, beta, 1, gscale, dz_extra, W.rec_row, W.pri_row, W.dlogit, nullptr, W.dzq, st));
-  ARDAE_TRY(decoder_bwd(P, K, packed, W, R, gm, st));
-  // ---- sampler backward -> W.dinp [B, cdim]
-  WgradList wl(grads);              // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
-  if (P.kind == 5) {
-    // encode.fc backwards, operator by operator: g = dL/d(output of the operator) [R, out]
-    auto pw = [&](int M, int O, int I, const float* G, const float* X, int ldX, const WnGrad& g, int col0, int ldout, bool bias) {
-      wl.push(M, O, I, G, X, ldX, g.dW + col0, ldout, bias ? g.db : nullptr).beta = g.beta;
-    };
-    float* g = W.dzq;
-    float* pp[2] = {W.dR0, W.dR1};
-    for (int i = (int)P.head.size() - 1; i >= 0; --i) {
-      const HeadOp& o = P.head[i];
-      const ResPacked::HeadPk& hk = K.head[i];
-      const ResWs::HeadBuf& u = W.hb[i];
-      const float* out = i + 1 == (int)P.head.size() ? W.z : u.out;
-      const float* x = i == 0 ? nullptr : W.hb[i - 1].out;        // the operator's input (post-activation output of its predecessor)
-      float* dx = pp[i & 1];
-      if (o.act != ACT_NONE) ARDAE_TRY(launch_mul_dact(g, out, o.act, g, (int64_t)R * o.out, st));
-      if (o.res) {
-        const Blk& b = o.b; const BlkPk& k = hk.k;
-        const BlkGrad gr = gm.blk(b, k);
-        float* dh = W.sc.dh;       // [R, out]: d hmid = (g W_h1) relu'(hmid)
-        ARDAE_TRY(dense_bwd(ACT_RELU, R, o.out, g, o.out, packed + k.h.b, u.hmid, dh, st));
-        pw(R, o.out, o.out, g, u.hmid, o.out, gr.h, 0, o.out, true);
-        if (o.concat) {
-          const int I0 = P.cdim + P.nd;
-          ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rbs [B, out]
-          ARDAE_TRY(launch_segment_sum(dh, o.out, B, nz, o.out, 1.f, W.dB1, o.out, st));      // d rba [B, out]
-          pw(R, o.out, P.nd, g, noise, P.nd, gr.s, P.cdim, I0, true);                           // noise columns of W_01 (+ its bias)
-          pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gr.s, 0, I0, false);                       // image columns of W_01
-          pw(R, o.out, P.nd, dh, noise, P.nd, gr.a, P.cdim, I0, true);
-          pw(B, o.out, P.cdim, W.dB1, W.inp, P.cdim, gr.a, 0, I0, false);
-          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
-          ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.s_bi, W.dB1, o.out, o.out, packed + k.a_bi, A, st));
+  return gm;
+}
+
+// What the shared algorithm (csrc/ipmodel.h) needs to know of the residual-conv models (the weight gradients go out block by block through
+// flush_wgrad, their scratch carved up front: there is no list to size)
+struct ResTraits : IpTraitsBase {
+  using Layout = ResLayout; using Packed = ResPacked; using Ws = ResWs; using Entry = ResEntry;
+  using Grads = GradMap;      // built before the decoder's backward, used again by the sampler's and the trunk's
+  [[maybe_unused]] static constexpr bool direct_z = true;      // a forward-only encode: the last launch of the sampler writes the caller's buffer itself
+  static int desc_check(const ardae_model_desc* d) { return res_desc_check(d); }
+  // the hidden1a context is the aux model's h; the raw form belongs to its clipped class
+  static unsigned caps(const ardae_model_desc& d) { return d.kind != 6 ? 0 : (d.flags & ARDAE_MODEL_CLIPPED) ? CAP_HIDDEN | CAP_HIDDEN_RAW : CAP_HIDDEN; }
+  static IpBufs bufs(const ResWs& W) {      // the decoder's backward adds its dz to what the loss kernel left in dzq
+    return {W.z, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dzq, W.rec_row, W.pri_row};
+  }
+  static void wgrads(const ResLayout&, const ResPacked&, const ResWs&, const float*, const float*, int, int, WgradList&, Bump&) {}
+  static size_t noise_floats(const ResLayout& P, int B, int nz) { return (size_t)B * nz * (P.nd + P.zd); }
+  static float* zero_noise(Entry& e, size_t) { return e.W.zero; }
+  // (a forward-only pass copies the hidden context out in passing)
+  static int sampler_fwd(Entry& e, const float* params, const float* packed, const float* x, const float* noise, int B, int nz, const IpEncodeOut* enc,
+                         hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+    if (!enc) return ardae::sampler_fwd(P, K, params, packed, noise, B, nz, W, W.z, nullptr, st);
+    ARDAE_CHECK_ARG(!enc->raw0 || (P.clipped && enc->std0), "res model: raw0 is the clipped class's unscaled eps0 of a std = 0 pass (noise NULL)");
+    return ardae::sampler_fwd(P, K, params, packed, noise, B, nz, W, enc->z_out ? enc->z_out : W.z, enc->hidden_out, st, enc->raw0, enc->std0);
+  }
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {
+    return ardae::decoder_fwd(e.P, e.K, params, packed, z, R, e.W, nullptr, st);
+  }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e, params, packed, g, beta); }
+  static int decoder_bwd(Entry& e, const float* packed, int R, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, R, gm, st); }
+  static int sampler_bwd(Entry& e, const float*, const float* packed, const float*, const float* noise, int B, int nz, GradMap& gm, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int R = B * nz;
+    // ---- sampler backward -> W.dinp [B, cdim]
+    WgradList wl(gm.grads);              // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
+    if (P.kind == 5) {
+      // encode.fc backwards, operator by operator: g = dL/d(output of the operator) [R, out]
+      auto pw = [&](int M, int O, int I, const float* G, const float* X, int ldX, const WnGrad& g, int col0, int ldout, bool bias) {
+        wl.push(M, O, I, G, X, ldX, g.dW + col0, ldout, bias ? g.db : nullptr).beta = g.beta;
+      };
+      float* g = W.dzq;
+      float* pp[2] = {W.dR0, W.dR1};
+      for (int i = (int)P.head.size() - 1; i >= 0; --i) {
+        const HeadOp& o = P.head[i];
+        const ResPacked::HeadPk& hk = K.head[i];
+        const ResWs::HeadBuf& u = W.hb[i];
+        const float* out = i + 1 == (int)P.head.size() ? W.z : u.out;
+        const float* x = i == 0 ? nullptr : W.hb[i - 1].out;        // the operator's input (post-activation output of its predecessor)
+        float* dx = pp[i & 1];
+        if (o.act != ACT_NONE) ARDAE_TRY(launch_mul_dact(g, out, o.act, g, (int64_t)R * o.out, st));
+        if (o.res) {
+          const Blk& b = o.b; const BlkPk& k = hk.k;
+          const BlkGrad gr = gm.blk(b, k);
+          float* dh = W.sc.dh;       // [R, out]: d hmid = (g W_h1) relu'(hmid)
+          ARDAE_TRY(dense_bwd(ACT_RELU, R, o.out, g, o.out, packed + k.h.b, u.hmid, dh, st));
+          pw(R, o.out, o.out, g, u.hmid, o.out, gr.h, 0, o.out, true);
+          if (o.concat) {
+            const int I0 = P.cdim + P.nd;
+            ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rbs [B, out]
+            ARDAE_TRY(launch_segment_sum(dh, o.out, B, nz, o.out, 1.f, W.dB1, o.out, st));      // d rba [B, out]
+            pw(R, o.out, P.nd, g, noise, P.nd, gr.s, P.cdim, I0, true);                           // noise columns of W_01 (+ its bias)
+            pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gr.s, 0, I0, false);                       // image columns of W_01
+            pw(R, o.out, P.nd, dh, noise, P.nd, gr.a, P.cdim, I0, true);
+            pw(B, o.out, P.cdim, W.dB1, W.inp, P.cdim, gr.a, 0, I0, false);
+            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+            LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
+            ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.s_bi, W.dB1, o.out, o.out, packed + k.a_bi, A, st));
+          } else {
+            if (!b.same) pw(R, o.out, o.in, g, x, o.in, gr.s, 0, o.in, true);
+            pw(R, o.out, o.in, dh, x, o.in, gr.a, 0, o.in, true);
+            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+            if (!b.same) {
+              LinArgs A{}; A.Y = dx; A.ldY = o.in;
+              ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.s.b, dh, o.out, o.out, packed + k.a.b, A, st));
+            } else {   // identity skip: dx = dh W_0h + g
+              ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, dh, o.out, o.out, packed + k.a.b, nullptr, dx, st));
+              ARDAE_TRY(launch_axpy(g, (int64_t)R * o.in, 1.f, dx, st));
+            }
+          }
         } else {
-          if (!b.same) pw(R, o.out, o.in, g, x, o.in, gr.s, 0, o.in, true);
-          pw(R, o.out, o.in, dh, x, o.in, gr.a, 0, o.in, true);
-          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          if (!b.same) {
-            LinArgs A{}; A.Y = dx; A.ldY = o.in;
-            ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.s.b, dh, o.out, o.out, packed + k.a.b, A, st));
-          } else {   // identity skip: dx = dh W_0h + g
-            ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, dh, o.out, o.out, packed + k.a.b, nullptr, dx, st));
-            ARDAE_TRY(launch_axpy(g, (int64_t)R * o.in, 1.f, dx, st));
+          const Lin& l = o.l; const LinPk& k = hk.lk;
+          const WnGrad gl{gm.grads + l.w, gm.grads + l.b, gm.grads_beta};
+          if (o.concat) {
+            ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rba [B, out]
+            pw(R, o.out, P.nd, g, noise, P.nd, gl, P.cdim, l.in, true);
+            pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gl, 0, l.in, false);
+            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+            ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, nullptr, W.dinp, st));
+          } else {
+            pw(R, o.out, o.in, g, x, o.in, gl, 0, l.in, true);
+            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+            ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, nullptr, dx, st));
           }
         }
-      } else {
-        const Lin& l = o.l; const LinPk& k = hk.lk;
-        const WnGrad gl{grads + l.w, grads + l.b, grads_beta};
-        if (o.concat) {
-          ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rba [B, out]
-          pw(R, o.out, P.nd, g, noise, P.nd, gl, P.cdim, l.in, true);
-          pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gl, 0, l.in, false);
-          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, nullptr, W.dinp, st));
-        } else {
-          pw(R, o.out, o.in, g, x, o.in, gl, 0, l.in, true);
-          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-          ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, nullptr, dx, st));
-        }
+        g = dx;
       }
-      g = dx;
+    } else {
+      const int ldn = P.nd + P.zd;
+      auto plain_wgrad = [&](int M, const Lin& l, const float* G, const float* X, int ldX, int col0, int I, bool bias) {
+        wl.push(M, l.out, I, G, X, ldX, gm.grads + l.w + col0, l.in, bias ? gm.grads + l.b : nullptr).beta = gm.grads_beta;
+      };
+      // z = mu + exp(lv/2) eps,  lv = spm4(lvr)
+      float* dlv = W.sc.g;           // [R, zd]
+      ARDAE_TRY(launch_reparam_bwd(W.dzq, W.z, W.mu, R, P.zd, 1, dlv, st));
+      RES_LAUNCH(spm4_kernel, (int64_t)R * P.zd, W.lvr, (const float*)dlv, dlv, (int64_t)R * P.zd, (int)P.clipped);
+      plain_wgrad(R, P.mu, W.dzq, W.hh, P.cdim, 0, P.cdim, true);
+      plain_wgrad(R, P.lv, dlv, W.hh, P.cdim, 0, P.cdim, true);
+      float* dhh = W.dR0;            // [R, cdim]
+      { LinArgs A{}; A.Y = dhh; A.ldY = P.cdim; ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, P.cdim, W.dzq, P.zd, P.zd, packed + K.mu.b, dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
+      ARDAE_TRY(launch_mul_dact(dhh, W.hh, ACT_ELU, dhh, (int64_t)R * P.cdim, st));
+      ARDAE_TRY(launch_segment_sum(dhh, P.cdim, B, nz, P.cdim, 1.f, W.dB0, P.cdim, st));      // d rbh [B, cdim]
+      plain_wgrad(R, P.efc, dhh, W.z0, P.nd, P.cdim, P.nd, true);                              // z0 columns + bias
+      plain_wgrad(B, P.efc, W.dB0, W.inp, P.cdim, 0, P.cdim, false);                           // image columns
+      float* dz0 = W.dR1;            // [R, nd] = dhh W_fc[:, cdim:]
+      ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, dhh, P.cdim, P.cdim, packed + K.efc.bn, nullptr, dz0, st));
+      // z0 = mu0[b] + exp(lv0[b] / 2) eps0,  lv0 = spm4(lv0r): reduce over the nz rows of an image first
+      float* dlv0_rows = W.sc.dh;    // [R, nd]
+      ARDAE_TRY(launch_reparam_bwd(dz0, W.z0, W.mu0, R, P.nd, nz, dlv0_rows, st, P.clipped ? 1.f : 0.f, noise, ldn));
+      ARDAE_TRY(launch_segment_sum(dz0, P.nd, B, nz, P.nd, 1.f, W.dB1, P.nd, st));            // d mu0 [B, nd]
+      ARDAE_TRY(launch_segment_sum(dlv0_rows, P.nd, B, nz, P.nd, 1.f, W.dB2, P.nd, st));      // d lv0 [B, nd]
+      RES_LAUNCH(spm4_kernel, (int64_t)B * P.nd, W.lv0r, (const float*)W.dB2, W.dB2, (int64_t)B * P.nd, (int)P.clipped);
+      plain_wgrad(B, P.mu0, W.dB1, W.inp, P.cdim, 0, P.cdim, true);
+      plain_wgrad(B, P.lv0, W.dB2, W.inp, P.cdim, 0, P.cdim, true);
+      ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+      // d inp = d rbh W_fc[:, :cdim] + d mu0 W_mu0 + d lv0r W_lv0
+      float* part = W.dflat;         // [B, cdim] scratch (cdim <= 512)
+      { LinArgs A{}; A.Y = part; A.ldY = P.cdim;
+        ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, P.cdim, P.cdim, packed + K.efc.bi, W.dB1, P.nd, P.nd, packed + K.mu0.b, A, st)); }
+      ARDAE_TRY(dense_bwd(ACT_NONE, B, P.cdim, W.dB2, P.nd, packed + K.lv0.b, part, W.dinp, st, part));       // V * 1 + Q
     }
-  } else {
-    const int ldn = P.nd + P.zd;
-    auto plain_wgrad = [&](int M, const Lin& l, const float* G, const float* X, int ldX, int col0, int I, bool bias) {
-      wl.push(M, l.out, I, G, X, ldX, grads + l.w + col0, l.in, bias ? grads + l.b : nullptr).beta = grads_beta;
-    };
-    // z = mu + exp(lv/2) eps,  lv = spm4(lvr)
-    float* dlv = W.sc.g;           // [R, zd]
-    ARDAE_TRY(launch_reparam_bwd(W.dzq, W.z, W.mu, R, P.zd, 1, dlv, st));
-    RES_LAUNCH(spm4_kernel, (int64_t)R * P.zd, W.lvr, (const float*)dlv, dlv, (int64_t)R * P.zd, (int)P.clipped);
-    plain_wgrad(R, P.mu, W.dzq, W.hh, P.cdim, 0, P.cdim, true);
-    plain_wgrad(R, P.lv, dlv, W.hh, P.cdim, 0, P.cdim, true);
-    float* dhh = W.dR0;            // [R, cdim]
-    { LinArgs A{}; A.Y = dhh; A.ldY = P.cdim; ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, P.cdim, W.dzq, P.zd, P.zd, packed + K.mu.b, dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
-    ARDAE_TRY(launch_mul_dact(dhh, W.hh, ACT_ELU, dhh, (int64_t)R * P.cdim, st));
-    ARDAE_TRY(launch_segment_sum(dhh, P.cdim, B, nz, P.cdim, 1.f, W.dB0, P.cdim, st));      // d rbh [B, cdim]
-    plain_wgrad(R, P.efc, dhh, W.z0, P.nd, P.cdim, P.nd, true);                              // z0 columns + bias
-    plain_wgrad(B, P.efc, W.dB0, W.inp, P.cdim, 0, P.cdim, false);                           // image columns
-    float* dz0 = W.dR1;            // [R, nd] = dhh W_fc[:, cdim:]
-    ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, dhh, P.cdim, P.cdim, packed + K.efc.bn, nullptr, dz0, st));
-    // z0 = mu0[b] + exp(lv0[b] / 2) eps0,  lv0 = spm4(lv0r): reduce over the nz rows of an image first
-    float* dlv0_rows = W.sc.dh;    // [R, nd]
-    ARDAE_TRY(launch_reparam_bwd(dz0, W.z0, W.mu0, R, P.nd, nz, dlv0_rows, st, P.clipped ? 1.f : 0.f, noise, ldn));
-    ARDAE_TRY(launch_segment_sum(dz0, P.nd, B, nz, P.nd, 1.f, W.dB1, P.nd, st));            // d mu0 [B, nd]
-    ARDAE_TRY(launch_segment_sum(dlv0_rows, P.nd, B, nz, P.nd, 1.f, W.dB2, P.nd, st));      // d lv0 [B, nd]
-    RES_LAUNCH(spm4_kernel, (int64_t)B * P.nd, W.lv0r, (const float*)W.dB2, W.dB2, (int64_t)B * P.nd, (int)P.clipped);
-    plain_wgrad(B, P.mu0, W.dB1, W.inp, P.cdim, 0, P.cdim, true);
-    plain_wgrad(B, P.lv0, W.dB2, W.inp, P.cdim, 0, P.cdim, true);
-    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-    // d inp = d rbh W_fc[:, :cdim] + d mu0 W_mu0 + d lv0r W_lv0
-    float* part = W.dflat;         // [B, cdim] scratch (cdim <= 512)
-    { LinArgs A{}; A.Y = part; A.ldY = P.cdim;
-      ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, P.cdim, P.cdim, packed + K.efc.bi, W.dB1, P.nd, P.nd, packed + K.mu0.b, A, st)); }
-    ARDAE_TRY(dense_bwd(ACT_NONE, B, P.cdim, W.dB2, P.nd, packed + K.lv0.b, part, W.dinp, st, part));       // V * 1 + Q
+    return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
   }
-  return trunk_wn_bwd(P, K, packed, W, B, gm, grads_beta, st);
-}
+};
 
 // ------------------------------------------------------------------------------------------------ kind 12: the Gaussian-posterior baseline
 // one draw per image; there is no sampler pair.  mode 2: B * nz decoded rows
 size_t resvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  if (res_desc_ok(d)) return 0;
   if (mode != 2 && (nz != 1 || mode == 3)) return 0;
-  return res_workspace(ResLayout(d), mode == 2 ? B * nz : B, 1, mode);
+  const ResLayout P(d);
+  Bump ws;
+  ResWs W;
+  carve(P, ResPacked(P), ws, mode == 2 ? B * nz : B, 1, mode, W);
+  return ws.off;
 }
 
 int resvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
@@ -1104,11 +1081,7 @@ struct ResVaeTraits {
   static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
     return ardae::decoder_fwd(e.P, e.K, params, packed, e.W.z, B, e.W, nullptr, st);
   }
-  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* grads, float grads_beta) {
-    GradMap gm{e.P, e.W.dweff, e.W.dbias, 0, {}, params, packed, grads};
-    gm.grads_beta = grads_beta;
-    return gm;
-  }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e, params, packed, g, beta); }
   static int decoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, B, gm, st); }
   static int encoder_bwd(Entry& e, const float* packed, const float*, int B, GradMap& gm, hipStream_t st) {
     auto& [P, K, ws, W] = e;
@@ -1127,10 +1100,10 @@ struct ResVaeTraits {
 
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
 #ifndef __HIP_DEVICE_COMPILE__
-const Family RES_FAMILY = {res_param_floats, res_packed_floats, res_workspace_floats, res_pack, res_encode, res_decode, res_vae_forward, res_vae_backward};
-static const GaussFamily RESVAE_GAUSS = gauss_family<ResVaeTraits>(resvae_desc_check);
-const Family RESVAE_FAMILY = {res_param_floats, res_packed_floats, resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward,
-                              vae_no_backward, &RESVAE_GAUSS};
+const Family RES_FAMILY = ip_family<ResTraits>(res_pack);
+static const GaussFamily RESVAE_GAUSS = gauss_family<ResVaeTraits>();
+const Family RESVAE_FAMILY = {resvae_desc_check, no_caps, family_param_floats<ResLayout, ResPacked>, family_packed_floats<ResLayout, ResPacked>,
+                              resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward, vae_no_backward, &RESVAE_GAUSS};
 #endif
 
 }  // namespace ardae

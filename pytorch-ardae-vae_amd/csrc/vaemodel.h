@@ -30,10 +30,9 @@ int vae_no_forward(const ardae_model_desc&, const float*, const float*, const fl
 int vae_no_backward(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, DevFloat, float, const float*, float*,
                     size_t, float*, float, hipStream_t);
 
-// What a Gaussian family adds to its Family row: its descriptor rules (0, or -1 with the message set) and the bodies of ardae_vae_head_fused_ok /
+// What a Gaussian family adds to its Family row (whose desc_check holds its descriptor rules): the bodies of ardae_vae_head_fused_ok /
 // _forward / _backward / _encode_stats / _head, whose arguments the entry points have validated.
 struct GaussFamily {
-  int (*desc_check)(const ardae_model_desc* d);
   bool (*head_fused_ok)(const ardae_model_desc& d);
   int (*forward)(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, DevFloat beta,
                  uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t wsf, float* z_out, float* eps_out, float* losses,
@@ -118,8 +117,8 @@ template <class F> int gauss_vae_head(const ardae_model_desc& d, const float* pa
   return gauss_head_fwd(gauss_head_of<F>(d), params, packed, hid, eps, B, seed, offset, state, variant, mu, lv, z, eps_out, kld, st);
 }
 
-// the family's row: its descriptor rules and the bodies above over its traits
-template <class F> constexpr GaussFamily gauss_family(int (*desc_check)(const ardae_model_desc*)) {
-  return {desc_check, gauss_vae_head_fused_ok<F>, gauss_vae_forward<F>, gauss_vae_backward<F>, gauss_vae_encode_stats<F>, gauss_vae_head<F>};
+// the family's row: the bodies above over its traits
+template <class F> constexpr GaussFamily gauss_family() {
+  return {gauss_vae_head_fused_ok<F>, gauss_vae_forward<F>, gauss_vae_backward<F>, gauss_vae_encode_stats<F>, gauss_vae_head<F>};
 }
 }  // namespace ardae

@@ -413,9 +413,10 @@ int vae_desc_check(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
   return 0;
 }
+unsigned vae_caps(const ardae_model_desc& d) { return d.kind == 9 ? CAP_GAUSS_DECODER : 0; }      // ToyVAE: mean and logvar heads
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
-const GaussFamily VAE_GAUSS = gauss_family<VaeTraits>(vae_desc_check);
+const GaussFamily VAE_GAUSS = gauss_family<VaeTraits>();
 #endif
 
 // ------------------------------------------------------------------------------------------------ the ardae_vae_* entry points, every Gaussian kind
@@ -424,7 +425,7 @@ int vae_kind_check(const ardae_model_desc* d, const char* who) {
   ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
   ARDAE_CHECK_ARG(family_of(d->kind) && family(d).gauss,
                   "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), or 12 (MNISTResConvVAE), got %d", who, d->kind);
-  return family(d).gauss->desc_check(d);
+  return family(d).desc_check(d);
 }
 
 // what every ardae_vae_* entry point checks before anything is launched
@@ -459,7 +460,7 @@ int vae_backward_entry(const ardae_model_desc* d, const float* params, const flo
 
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
-const Family VAE_FAMILY = {family_param_floats<VaeLayout, VaePacked>, family_packed_floats<VaeLayout, VaePacked>, vae_workspace_floats,
+const Family VAE_FAMILY = {vae_desc_check, vae_caps, family_param_floats<VaeLayout, VaePacked>, family_packed_floats<VaeLayout, VaePacked>, vae_workspace_floats,
                            family_pack<VaeLayout, VaePacked>, vae_no_encode, mlp_decode<VaeLayout, VaePacked>, vae_no_forward, vae_no_backward,
                            &VAE_GAUSS};
 #endif
