@@ -376,7 +376,8 @@ int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, doubl
  *                        noise of such a call = [eps0: B q x noise_dim | eps: B q q x z_dim], two consecutive blocks; hidden1a context
  *                        cat(h0, h) [B, 2 h_dim] */
 typedef struct ardae_model_desc {
-  int kind;     /* 0 .. 7 above; 8 / 9 / 11 / 12: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0).
+  int kind;     /* 0 .. 7 above; 8 / 9 / 11 / 12: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0);
+                 * 14 / 15: the auxiliary-variable baselines (see "Auxiliary-variable Gaussian baselines" below).
                  * 10 is not a kind */
   int input_dim, noise_dim, h_dim, z_dim;
   int n_layers; /* --model-n-layers */
@@ -399,7 +400,8 @@ enum { ARDAE_MODEL_NO_CENTER = 1,
        ARDAE_MODEL_CLIP_Z0_SHIFT = 8, ARDAE_MODEL_CLIP_Z_SHIFT = 12, ARDAE_MODEL_CLIP_MASK = 0xff00 };
 size_t ardae_model_param_floats(const ardae_model_desc* d);
 size_t ardae_model_packed_floats(const ardae_model_desc* d);
-/* mode 0: encode only; mode 1: vae_forward + vae_backward; mode 2: decode only (B = rows, nz = 1); mode 3: encode_pair */
+/* mode 0: encode only; mode 1: vae_forward + vae_backward; mode 2: decode only (B = rows, nz = 1); mode 3: encode_pair; mode 4: kinds 14 / 15 only,
+ * ardae_vae_aux_iwae_draw on B images x nz samples */
 size_t ardae_model_workspace_floats(const ardae_model_desc* d, int B, int nz, int mode);
 int ardae_model_pack(const ardae_model_desc* d, const float* params, float* packed, void* stream);
 /* Encoder.forward (ivae/mnist.py:102-121): z[B*nz, z] = f(x[B, input_dim], noise[B*nz, noise_dim]); noise NULL = zeros,
@@ -535,6 +537,53 @@ int ardae_vae_encode_stats(const ardae_model_desc* d, const float* params, const
  * decoder, the row losses and the log-mean-exp are ardae_model_decode, ardae_model_loss_rows and ardae_iwae_reduce. */
 int ardae_vae_iwae_draw(const float* mu, const float* lv, const float* eps, int B, int k, int z, uint64_t seed, uint64_t offset,
                         uint64_t first_element, float* z_out, float* logq, float* eps_out, void* stream);
+
+/* ---- Auxiliary-variable Gaussian baselines (vae.py --model auxmnist | auxtoy; models/vae/auxmnist.py, auxtoy.py; csrc/auxvae.hip):
+ * ardae_model_desc.kind 14 / 15 ------
+ * The Gaussian counterparts of kinds 3 / 7: q(z0 | x) q(z | z0, x) with an auxiliary decoder r(z0 | z, x).  13 is not a kind.
+ *   kind 14 (MNISTAuxVAE, `vae.py --model auxmnist`, the "# hierarchical mlp" baseline of run_vae_dbmnist.sh): aux_encode.main.{layers.0..n_layers-2, fc},
+ *                        aux_encode.reparam.{mean_fn, logvar_fn} [noise_dim, h]; encode.fc.{layers.*, fc} (first weight [h, input_dim + noise_dim]),
+ *                        encode.reparam.{mean_fn, logvar_fn} [z_dim, h]; decode.main.*, decode.reparam.logit_fn; aux_decode.fc.{layers.*, fc} (first weight
+ *                        [h, input_dim + z_dim]), aux_decode.reparam.{mean_fn, logvar_fn} [noise_dim, h].  x rescaled to 2x - 1 in all three encoders.
+ *   kind 15 (ToyAuxVAE, `vae.py --model auxtoy`): the same without the rescale, decode.reparam.{mean_fn, logvar_fn}: Gaussian decoder.
+ * 1 <= noise_dim <= 128 (the width of z0), z_dim >= 1 (<= 128 for ardae_vae_aux_iwae_draw), n_layers 1 .. 4; flags: only the ARDAE_MODEL_CLIP_Z0 code
+ * (aux_encode's clip_logvar, codes 0 .. 10 as for kinds 3 / 7) - the other two heads take no clip.  ardae_model_param_floats / packed_floats /
+ * workspace_floats (mode 0: encode_stats, 1: forward + backward, 2: decode - nz = 1 each - and mode 4: ardae_vae_aux_iwae_draw on B images x nz samples)
+ * / pack / decode / loss_rows take these kinds; ardae_model_encode and ardae_model_vae_* refuse them.  The ardae_vae_* entry points above take them with
+ * these meanings:
+ * ardae_vae_forward: eps is ONE tensor [B, noise_dim + z_dim], row = [eps0 | eps] (kind 3's layout), or NULL: with q = (B noise_dim + 3) / 4 * 4,
+ *   eps0 element i = element i and eps element j = element q + j of the draw (seed, offset [+ state.rng_offset]) - what
+ *   ardae_philox_normal_at(out, B noise_dim, seed, offset, state, 0) and ardae_philox_normal_at(out, B z_dim, seed, offset, state, q) write.  eps_out has
+ *   eps' shape, z_out is [B, z_dim], losses[3] = {mean_b(recon_b + beta (kld_b + aux_kld_b)), mean recon, mean (kld + aux_kld)} with
+ *   aux_kld_b = -0.5 sum_c (1 - lvp + lv0 - (exp(lv0) + (mu0 - mup)^2) / exp(lvp)) (utils/vae.py:94-114; one launch, added into the head's KL rows).
+ * ardae_vae_backward: with c = loss_scale / B the auxiliary decoder's head is seeded in closed form, dmup = c beta (mup - mu0) / exp(lvp),
+ *   dlvp = c beta (1 - (exp(lv0) + (mu0 - mup)^2) / exp(lvp)) / 2, the first head gets dmu0 = dz0 + c beta (mu0 - mup) / exp(lvp),
+ *   dlv0 = dz0 (z0 - mu0) / 2 + c beta (exp(lv0) / exp(lvp) - 1) / 2 and then the clip's derivative, and dz is the decoder's part + the auxiliary
+ *   decoder's + the head seed of kinds 8 / 9.  One ardae_wgrad_batch problem list.
+ * ardae_vae_encode_stats: mu0, lv0 (clipped) [B, noise_dim] of q(z0 | x).  ardae_vae_head / ardae_vae_head_fused_ok: the encode.reparam head on encode.fc's
+ *   hidden rows, with kind 8's variants and policy.
+ * ardae_vae_pair_kld_rows: kld[b] = -0.5 sum_c (1 - lv2 + lv1 - (exp(lv1) + (mu1 - mu2)^2) / exp(lv2)) from [B, n] statistics, n <= 128: the row values of
+ *   loss_kld_gaussian_vs_gaussian, the terms in double and added over ascending c (a row's bits do not depend on B); it mirrors ardae_vae_kld_rows.
+ * ardae_vae_aux_iwae_draw: VAE.logprob's three stochastic stages (vae/auxmnist.py:381-451, sample_size2 = 1) for B images x k samples: k z0's per image
+ *   from mu0, lv0 [B, noise_dim] (ardae_vae_encode_stats), one z per z0 from q(z | z0, x), and ONE combined row
+ *   logq [B, k] = log q(z0 | x) + log q(z | z0, x) - log r(z0 | z, x) - each a sum in double over ascending c (utils/stat.py:65-85), combined in double
+ *   in that order.  z_out [B, k, z_dim].  The caller goes on with ardae_model_decode, ardae_model_loss_rows and ardae_iwae_reduce as for kind 8.
+ *   eps [B, k, noise_dim + z_dim] (rows [eps0 | eps]) or NULL: with g = first_image + b, eps0 of (b, s, c) is element (g k + s) noise_dim + c of the
+ *   draw (seed, offset0) and eps of (b, s, c) element (g k + s) z_dim + c of the draw (seed, offset1) - so a set walked in chunks draws the same
+ *   numbers whatever the chunk length; first_image k noise_dim and first_image k z_dim must be multiples of 4.  eps_out: eps' shape, or NULL.
+ *   Workspace: mode 4 with nz = k.  (ARDAE_AUX_DRAW_STAGES=1 | 2 under ARDAE_DEBUG_KNOBS=1 stops the call after that stage and leaves logq unwritten:
+ *   tools/time_vae_aux_baseline.py times the stages that way.)
+ * ardae_vae_aux_elbo_rows: the rows of one forward at beta = 1 (evaluate_iws' ELBO, vae.py:360): recon_rows [B] and kld_rows [B] = kld_b + aux_kld_b, the
+ *   values ardae_vae_forward averages.  eps [B, noise_dim + z_dim] or NULL: eps0 of (b, c) is element (first_image + b) noise_dim + c of the draw
+ *   (seed, offset0), eps of (b, c) element (first_image + b) z_dim + c of the draw (seed, offset1); first_image noise_dim and first_image z_dim must be
+ *   multiples of 4.  Workspace: mode 1. */
+int ardae_vae_aux_elbo_rows(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* eps, int B, uint64_t seed,
+                            uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace, size_t workspace_floats, float* recon_rows,
+                            float* kld_rows, void* stream);
+int ardae_vae_pair_kld_rows(const float* mu1, const float* lv1, const float* mu2, const float* lv2, int B, int n, float* kld, void* stream);
+int ardae_vae_aux_iwae_draw(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* mu0, const float* lv0,
+                            const float* eps, int B, int k, uint64_t seed, uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace,
+                            size_t workspace_floats, float* z_out, float* logq, float* eps_out, void* stream);
 
 /* The last stage of the residual-conv decoder on its own (kind 12; csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
  * -> bilinear x2 upsampling (align_corners) -> decode.dec.17 = ResConv2d(16 -> 1) -> logits [R, 784].  It reads the effective weights ardae_model_pack

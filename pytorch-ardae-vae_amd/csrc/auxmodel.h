@@ -14,4 +14,7 @@ int launch_reparam_fwd(const float* mu, const float* lv, const float* eps, int l
 // dlv = dz (z - mu - min_std eps) / 2   (eps: the draw of the forward call, needed only with min_std != 0)
 int launch_reparam_bwd(const float* dz, const float* z, const float* mu, int64_t rows, int cols, int rows_per_group, float* dlv, hipStream_t st,
                        float min_std = 0.f, const float* eps = nullptr, int ld_eps = 0);
+// NormalDistribution.clip_logvar (models/reparam.py:17-41; code: ardae_hip.h's ARDAE_MODEL_CLIP_*, 0 = none: no launch) on n raw head outputs x:
+// y = c(x), or (dy given) the backward y = dy c'(x); y may be dy.  Shared with the auxiliary-variable baselines (csrc/auxvae.hip).
+int launch_logvar_clip(const float* x, const float* dy, float* y, int64_t n, int code, hipStream_t st);
 }  // namespace ardae

@@ -132,6 +132,27 @@ def vae_spec(kind, input_dim, h_dim, z_dim, n_layers):
                 ("decode.reparam.logvar_fn.weight", (input_dim, h_dim)), ("decode.reparam.logvar_fn.bias", (input_dim,))]
 
 
+def aux_vae_spec(kind, input_dim, noise_dim, h_dim, z_dim, n_layers):
+    """The auxiliary-variable Gaussian baselines of vae.py (models/vae/auxmnist.py:268-311 'mnist', models/vae/auxtoy.py 'toy'): AuxEncoder (an MLP and a
+    NormalDistributionLinear head on z0), SimpleEncoder (`fc` on cat[x, z0], a head on z), the decoder of 'mnist' / 'toy' above and AuxDecoder (`fc` on
+    cat[x, z], a head on z0), in the order the reference assigns them; inp_encode / nos_encode / ltt_encode are Identity and own nothing.
+    ardae_model_desc.kind 14 ('mnist') / 15 ('toy')."""
+    if kind not in ("mnist", "toy"):
+        raise NotImplementedError(kind)
+
+    def head(prefix, out):
+        return [(prefix + "mean_fn.weight", (out, h_dim)), (prefix + "mean_fn.bias", (out,)),
+                (prefix + "logvar_fn.weight", (out, h_dim)), (prefix + "logvar_fn.bias", (out,))]
+    s = _mlp("aux_encode.main.", input_dim, h_dim, h_dim, n_layers - 1) + head("aux_encode.reparam.", noise_dim)
+    s += _mlp("encode.fc.", input_dim + noise_dim, h_dim, h_dim, n_layers - 1) + head("encode.reparam.", z_dim)
+    s += _mlp("decode.main.", z_dim, h_dim, h_dim, n_layers - 1)
+    if kind == "mnist":
+        s += [("decode.reparam.logit_fn.weight", (input_dim, h_dim)), ("decode.reparam.logit_fn.bias", (input_dim,))]
+    else:
+        s += head("decode.reparam.", input_dim)
+    return s + _mlp("aux_decode.fc.", input_dim + z_dim, h_dim, h_dim, n_layers - 1) + head("aux_decode.reparam.", noise_dim)
+
+
 def conv_vae_spec(z_dim):
     """The conv Gaussian-posterior baseline of vae.py (models/vae/conv.py:29-168, `--model conv`; 28 x 28 x 1, fixed architecture): the conv
     trunk of the 'conv' implicit model, `encode.fc` 512 -> 800, a NormalDistributionLinear head and that model's decoder.  ardae_model_desc.kind 11."""

@@ -7,6 +7,7 @@
     net.MNISTVAE / net.ToyVAE            <- models/vae/mnist.py:99-220, models/vae/toy.py:99-213 (the Gaussian-posterior baselines of vae.py)
     net.MNISTConvVAE                     <- models/vae/conv.py:138-260 (`vae.py --model conv`)
     net.MNISTResConvVAE                  <- models/vae/resconv.py:122-240 (`vae.py --model resconv`)
+    net.MNISTAuxVAE / net.ToyAuxVAE      <- models/vae/auxmnist.py:268-451, models/vae/auxtoy.py (`vae.py --model auxmnist | auxtoy`)
 
 Same constructor kwargs, same `state_dict()` keys and `[out, in]` layouts (reference checkpoints load), same method
 names and argument meaning, same exception types.  Parameters are `nn.Parameter` views into ONE flat fp32 buffer
@@ -150,9 +151,10 @@ def _f32c(t):
 
 
 KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7,      # ardae_model_desc.kind
-            "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11, "vae_resconv": 12}                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
+            "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11, "vae_resconv": 12,                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
+            "vae_auxmnist": 14, "vae_auxtoy": 15}                                                                               # (its auxiliary-variable baselines; 13 is not a kind)
 AUX_KINDS = ("auxmnist", "auxconv", "auxresconv", "auxtoy")                                                 # hierarchical samplers
-GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
+GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy", "vae_auxtoy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -879,7 +881,7 @@ class _GaussVaeFn(torch.autograd.Function):
     def forward(ctx, mod, x, eps, beta, *params):
         d, B = mod._desc, x.size(0)
         ws = mod._ws(L.query("ardae_model_workspace_floats", d, B, 1, 1))
-        z, eps_out = torch.empty(B, mod.z_dim, device=x.device), torch.empty(B, mod.z_dim, device=x.device)
+        z, eps_out = torch.empty(B, mod.z_dim, device=x.device), torch.empty(B, mod._eps_width, device=x.device)
         losses = torch.empty(3, device=x.device)
         seed, offset = rng.get_state()["seed"], (rng._next_offset() if eps is None else 0)
         L.call("ardae_vae_forward", d, mod._flat, mod._packed_weights(), x, eps, B, float(beta), 1.0, seed, offset, None, ws, ws.numel(), z, eps_out,
@@ -924,9 +926,10 @@ class GaussianVAE(FlatParamModule):
     _packed_floats_fn, _pack_fn = "ardae_model_packed_floats", "ardae_model_pack"
     return_samples = True        # forward() also returns the decoder sample / mean (one extra decoder pass); False: (None, None)
     noise_dim = 0
+    _eps_width = property(lambda self: self.z_dim)      # floats per image of forward()'s draw (the auxiliary-variable models: noise_dim + z_dim)
     _eval_groups = None          # GaussianIwaeEvaluator: (images per encoder / ELBO-decoder call, images per importance-sample decoder call); None: a chunk at once
 
-    def _build(self, energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, flags=0):
+    def _build(self, energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, flags=0, noise_dim=0, boxes=None):
         if energy_func is not normal_energy_func:
             raise NotImplementedError("only utils.normal_energy_func is implemented on the HIP path")
         if nonlinearity not in L.ACT or nonlinearity in ("none", None):
@@ -938,9 +941,9 @@ class GaussianVAE(FlatParamModule):
         self.input_dim, self.h_dim, self.z_dim = int(input_dim), int(h_dim), int(z_dim)
         self.latent_dim = self.z_dim
         self.nonlinearity, self.num_hidden_layers = nonlinearity, int(num_hidden_layers)
-        self._desc = L.ModelDesc(KIND_IDS[self._kind], self.input_dim, 0, self.h_dim, self.z_dim, self.num_hidden_layers, L.ACT[nonlinearity], flags)
+        self._desc = L.ModelDesc(KIND_IDS[self._kind], self.input_dim, int(noise_dim), self.h_dim, self.z_dim, self.num_hidden_layers, L.ACT[nonlinearity], flags)
         self._abi = (self._desc,)
-        self._build_params(self._param_spec(), {"encode": _GaussEncodeBox})
+        self._build_params(self._param_spec(), {"encode": _GaussEncodeBox} if boxes is None else boxes)
         object.__setattr__(self.encode, "_owner_ref", weakref.ref(self))
         self.reset_parameters()
 
@@ -973,7 +976,7 @@ class GaussianVAE(FlatParamModule):
         B = x.size(0)
         if eps is not None:
             self._require_gpu(eps)
-            eps = _f32c(eps).view(B, self.z_dim)
+            eps = _f32c(eps).view(B, self._eps_width)
         loss, z, _, losses = _GaussVaeFn.apply(self, x, eps, beta, *self.parameters())
         xs, xm = (None, None)
         if self.return_samples:
@@ -1113,3 +1116,87 @@ class ToyVAE(GaussianVAE):
         if self.init == "gaussian":                         # Decoder.reset_parameters (vae/toy.py:75-81)
             with torch.no_grad():
                 dict(self.named_parameters())["decode.reparam.mean_fn.weight"].normal_()
+
+
+class _AuxGaussianVAE(GaussianVAE):
+    """What MNISTAuxVAE and ToyAuxVAE share (ardae_model_desc kinds 14 / 15): q(z0 | x) q(z | z0, x) with an auxiliary decoder r(z0 | z, x).  forward()'s
+    `eps` is [B, noise_dim + z_dim], rows [eps0 | eps]; encode_stats() returns the statistics of q(z0 | x); logprob's `eps` is
+    [B, sample_size, noise_dim + z_dim].  `model.encode` / `model.aux_encode` / `model.aux_decode` only name parameters: the three networks run inside
+    forward() and logprob()."""
+    _eps_width = property(lambda self: self.noise_dim + self.z_dim)
+
+    def _build_aux(self, energy_func, input_dim, noise_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, enc_type, clip_logvar):
+        if enc_type != "simple":
+            raise NotImplementedError(f"enc_type {enc_type!r}: the reference builds 'simple' only (models/vae/auxmnist.py:294-302)")
+        if clip_logvar not in L.LOGVAR_CLIP:
+            raise NotImplementedError(f"clip_logvar {clip_logvar!r}: models/reparam.py:17-41 knows {sorted(k for k in L.LOGVAR_CLIP if k)}")
+        if not 1 <= int(noise_dim) <= 128:
+            raise ValueError(f"{type(self).__name__}: noise_dim must be 1 .. 128 (got {noise_dim})")
+        self.noise_dim, self.enc_type = int(noise_dim), enc_type
+        self.clip_logvar = None if clip_logvar == "none" else clip_logvar                       # vae/auxmnist.py:291
+        self._build(energy_func, input_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, L.LOGVAR_CLIP[clip_logvar] << L.MODEL_CLIP_Z0_SHIFT,
+                    noise_dim=self.noise_dim, boxes={})
+
+    def _param_spec(self):
+        return layout.aux_vae_spec(self._kind[len("vae_aux"):], self.input_dim, self.noise_dim, self.h_dim, self.z_dim, self.num_hidden_layers)
+
+    def encode_stats(self, input):
+        """(mu0, logvar0) [B, noise_dim] of q(z0 | x), the log-variance clipped, no draw (ardae_vae_encode_stats)."""
+        x = self._x(input)
+        B = x.size(0)
+        ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, B, 1, 0))
+        mu, lv = torch.empty(B, self.noise_dim, device=x.device), torch.empty(B, self.noise_dim, device=x.device)
+        L.call("ardae_vae_encode_stats", self._desc, self._flat, self._packed_weights(), x, B, ws, ws.numel(), mu, lv)
+        return mu, lv
+
+    def logprob_rows(self, input, sample_size=128, eps=None):
+        """The IWAE-`sample_size` bound of every image, [B] on the device (VAE.logprob before its mean, vae/auxmnist.py:381-451 with
+        sample_size2 = 1): the statistics of q(z0 | x), ardae_vae_aux_iwae_draw (k z0's, one z per z0, and log q(z0|x) + log q(z|z0,x) - log r(z0|z,x)
+        as one row), decoder, row losses, log-mean-exp.  eps [B, sample_size, noise_dim + z_dim] injects the draws."""
+        x = self._x(input)
+        B, k, zd = x.size(0), int(sample_size), self.z_dim
+        if zd > 128:
+            raise NotImplementedError(f"{type(self).__name__}.logprob: z_dim {zd} > 128: ardae_vae_aux_iwae_draw takes latent widths up to 128")
+        with torch.no_grad():
+            mu0, lv0 = self.encode_stats(x)
+            if eps is not None:
+                self._require_gpu(eps)
+                eps = _f32c(eps).view(B, k, self._eps_width)
+            z, logq = torch.empty(B * k, zd, device=x.device), torch.empty(B * k, device=x.device)
+            ws = self._ws(L.query("ardae_model_workspace_floats", self._desc, B, k, 4))
+            seed = rng.get_state()["seed"]
+            off0, off1 = (rng._next_offset(), rng._next_offset()) if eps is None else (0, 0)
+            L.call("ardae_vae_aux_iwae_draw", self._desc, self._flat, self._packed_weights(), x, mu0, lv0, eps, B, k, seed, off0, off1, 0, ws, ws.numel(),
+                   z, logq, None)
+            out = self.decode_params(z)
+            rec, pri, res = torch.empty(B * k, device=x.device), torch.empty(B * k, device=x.device), torch.empty(B, device=x.device)
+            L.call("ardae_model_loss_rows", self._desc, out[0], out[1] if len(out) > 1 else None, x, z, B * k, k, rec, pri)
+            L.call("ardae_iwae_reduce", rec, pri, logq, B, k, res)
+        return res
+
+
+class MNISTAuxVAE(_AuxGaussianVAE):
+    """models/vae/auxmnist.py::VAE (`vae.py --model auxmnist`, the "# hierarchical mlp" baseline of run_vae_dbmnist.sh): the Gaussian counterpart of
+    MNISTAuxIPVAE.  x -> 2x - 1 inside the three encoders, Bernoulli decoder; `clip_logvar` is aux_encode's."""
+    _kind = "vae_auxmnist"
+
+    def __init__(self, energy_func=normal_energy_func, input_dim=784, noise_dim=100, h_dim=300, z_dim=32, nonlinearity="softplus", num_hidden_layers=2,
+                 enc_type="simple", clip_logvar=None, do_xavier=True, do_m5bias=False):
+        super().__init__()
+        self.do_xavier, self.do_m5bias = do_xavier, do_m5bias
+        self._build_aux(energy_func, input_dim, noise_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, enc_type, clip_logvar)
+
+    reset_parameters = MNISTVAE.reset_parameters        # weight_init where do_xavier, the -5 logit bias where do_m5bias (vae/auxmnist.py:307-311)
+
+
+class ToyAuxVAE(_AuxGaussianVAE):
+    """models/vae/auxtoy.py::VAE (`vae.py --model auxtoy`): the same networks without the rescale, the Gaussian decoder of models/vae/toy.py."""
+    _kind = "vae_auxtoy"
+
+    def __init__(self, energy_func=normal_energy_func, input_dim=2, noise_dim=2, h_dim=64, z_dim=2, nonlinearity="tanh", num_hidden_layers=1,
+                 init="gaussian", enc_type="simple", clip_logvar=None):
+        super().__init__()
+        self.init = init
+        self._build_aux(energy_func, input_dim, noise_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, enc_type, clip_logvar)
+
+    reset_parameters = ToyVAE.reset_parameters          # Decoder.reset_parameters (vae/toy.py:75-81)

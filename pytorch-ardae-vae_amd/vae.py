@@ -1,7 +1,7 @@
 """The Gaussian-posterior baselines of the reference's second trainer, vae.py, on the device: one iteration of its loop (vae.py:396-417)
 as one captured unit, and its evaluate_iws (vae.py:342-377) in large chunks.
 
-    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE
+    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE, net.MNISTAuxVAE, net.ToyAuxVAE
     eng = net.VaeEngine(model, net.VaeConfig(lr=1e-3, beta_init=1e-4, beta_annealing=50000), batch_size=128)
     for x in loader: eng.step(x)
     elbo, logprob = eng.evaluate_iws(x_valid, sample_size=512)
@@ -20,7 +20,7 @@ from . import rng
 from .engine import ArdaeEngine, annealing_func
 from .engine_common import CaptureLadder, _FlatOpt, bump_versions, check_batch, check_tensor, rebuild_step_state
 from .iwae import _check, plan_chunks
-from .modules import GaussianVAE
+from .modules import GAUSSIAN_DECODERS, GaussianVAE, _AuxGaussianVAE
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
 
@@ -61,6 +61,7 @@ class VaeConfig:
 
 
 MAX_Z = 64                      # ardae_vae_iwae_draw holds one sample's terms per column in LDS
+MAX_AUX = 128                   # ... and ardae_vae_aux_iwae_draw's stages (noise_dim and z_dim)
 
 
 class GaussianIwaeEvaluator:
@@ -78,14 +79,18 @@ class GaussianIwaeEvaluator:
 
     def __init__(self, model, sample_size, max_workspace_floats=1 << 28):
         if not isinstance(model, GaussianVAE):
-            raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE (the implicit models: "
-                            "net.IwaeEvaluator)")
+            raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE / net.MNISTAuxVAE / "
+                            "net.ToyAuxVAE (the implicit models: net.IwaeEvaluator)")
         self.model, self.k, self.budget = model, int(sample_size), int(max_workspace_floats)
         if self.k < 1:
             raise ValueError(f"sample_size must be positive (got {sample_size})")
-        if model.z_dim > MAX_Z:
-            raise NotImplementedError(f"GaussianIwaeEvaluator: z_dim {model.z_dim} > {MAX_Z}: ardae_vae_iwae_draw takes latent widths up to {MAX_Z}")
-        self.gaussian = model._kind == "vae_toy"
+        self.aux = isinstance(model, _AuxGaussianVAE)      # MNISTAuxVAE / ToyAuxVAE: two draws per sample, ardae_vae_aux_* in place of the head's calls
+        if model.z_dim > (MAX_AUX if self.aux else MAX_Z):
+            raise NotImplementedError(f"GaussianIwaeEvaluator: z_dim {model.z_dim} > {MAX_AUX if self.aux else MAX_Z}: "
+                                      f"{'ardae_vae_aux_iwae_draw' if self.aux else 'ardae_vae_iwae_draw'} takes latent widths up to "
+                                      f"{MAX_AUX if self.aux else MAX_Z}")
+        self.gaussian = model._kind in GAUSSIAN_DECODERS
+        self.sd = model.noise_dim if self.aux else model.z_dim      # width of the statistics ardae_vae_encode_stats returns
         # images per encoder / ELBO-decoder call and per importance-sample decoder call (None: a chunk at once)
         self.image_group, self.group = model._eval_groups or (None, None)
         self._bufs = None
@@ -93,12 +98,13 @@ class GaussianIwaeEvaluator:
     def _workspace_floats(self, c):
         d = self.model._desc
         G, g = min(c, self.image_group or c), min(c, self.group or c)
+        aux = (L.query("ardae_model_workspace_floats", d, c, 1, 1), L.query("ardae_model_workspace_floats", d, c, self.k, 4)) if self.aux else ()
         return max(L.query("ardae_model_workspace_floats", d, G, 1, 0), L.query("ardae_model_workspace_floats", d, G, 1, 2),
-                   L.query("ardae_model_workspace_floats", d, g * self.k, 1, 2))
+                   L.query("ardae_model_workspace_floats", d, g * self.k, 1, 2), *aux)
 
     def _encode_stats(self, b, xc, c):
         """b["mu"], b["lv"] [c, z_dim] of the chunk xc, `self.image_group` images per encoder call"""
-        m, zd = self.model, self.model.z_dim
+        m, zd = self.model, self.sd
         G = self.image_group or c
         for j in range(0, c, G):
             n = min(G, c - j)
@@ -118,11 +124,17 @@ class GaussianIwaeEvaluator:
 
     def floats_per_chunk(self, c):
         m, k = self.model, self.k
-        own = 4 * m.z_dim + k * m.z_dim + 3 * k + (2 if self.gaussian else 1) * k * m.input_dim
+        own = 2 * m.z_dim + 2 * self.sd + k * m.z_dim + 3 * k + (2 if self.gaussian else 1) * k * m.input_dim
         return self._workspace_floats(c) + c * own
 
     def plan(self, N):
         chunks = plan_chunks(N, self.k, self.floats_per_chunk, self.budget)
+        if self.aux and len(chunks) > 1:
+            # own draws are keyed by a chunk's first image, and a Philox counter holds 4 normals: chunks start at multiples of 4 images
+            C = (chunks[0][1] - chunks[0][0]) // 4 * 4
+            if C == 0:
+                raise ValueError(f"GaussianIwaeEvaluator: the budget of {self.budget} floats is below 4 images ({self.floats_per_chunk(4)} floats)")
+            return [(s, min(s + C, N)) for s in range(0, N, C)]
         G = self.image_group
         if G is None or len(chunks) == 1:
             return chunks
@@ -136,7 +148,7 @@ class GaussianIwaeEvaluator:
         if self._bufs is None or self._bufs["c"] < c or self._bufs["ws"].device != device:
             m, k = self.model, self.k
             new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)      # noqa: E731
-            self._bufs = dict(c=c, ws=new(self._workspace_floats(c)), feps=new(c * m.z_dim), fz=new(c * m.z_dim), mu=new(c * m.z_dim), lv=new(c * m.z_dim),
+            self._bufs = dict(c=c, ws=new(self._workspace_floats(c)), feps=new(c * m.z_dim), fz=new(c * m.z_dim), mu=new(c * self.sd), lv=new(c * self.sd),
                               z=new(c * k * m.z_dim), logq=new(c * k), rec=new(c * k), pri=new(c * k), out0=new(c * k * m.input_dim),
                               out1=new(c * k * m.input_dim) if self.gaussian else None)
         return self._bufs
@@ -149,9 +161,11 @@ class GaussianIwaeEvaluator:
         _check(x_all, "x_all", (max(N, 1), 1, m.input_dim), who)
         m._require_gpu(x_all)
         if eps is not None:
-            eps = _check(eps, "eps", (N, k, zd), who)
+            eps = _check(eps, "eps", (N, k, m._eps_width), who)
         if fwd_eps is not None:
-            fwd_eps = _check(fwd_eps, "fwd_eps", (N, 1, zd), who)
+            fwd_eps = _check(fwd_eps, "fwd_eps", (N, 1, m._eps_width), who)
+        if self.aux:
+            return self._evaluate_rows_aux(x_all.view(N, m.input_dim), N, eps, fwd_eps)
         x = x_all.view(N, m.input_dim)
         chunks = self.plan(N)
         with torch.no_grad():
@@ -181,6 +195,32 @@ class GaussianIwaeEvaluator:
                 L.call("ardae_iwae_reduce", b["rec"], b["pri"], b["logq"], c, k, out[i0:i1])
         return recon, kld, out
 
+    def _evaluate_rows_aux(self, x, N, eps, fwd_eps):
+        """evaluate_rows for MNISTAuxVAE / ToyAuxVAE: per chunk the statistics of q(z0 | x), the ELBO rows of a forward at beta = 1
+        (ardae_vae_aux_elbo_rows: recon and kld + aux_kld), then VAE.logprob - ardae_vae_aux_iwae_draw, decoder, row losses, log-mean-exp.  Own draws
+        take four Philox offsets per call (two per pass: z0's and z's), each keyed by the chunk's first image.  Injected: fwd_eps
+        [N, noise_dim + z_dim], eps [N, k, noise_dim + z_dim]."""
+        m, k, w = self.model, self.k, self.model._eps_width
+        chunks = self.plan(N)
+        with torch.no_grad():
+            b = self._buffers(chunks[0][1] - chunks[0][0], x.device)
+            seed = rng.get_state()["seed"]
+            f0, f1 = (rng._next_offset(), rng._next_offset()) if fwd_eps is None else (0, 0)
+            o0, o1 = (rng._next_offset(), rng._next_offset()) if eps is None else (0, 0)
+            d, flat, packed, ws = m._desc, m._flat, m._packed_weights(), b["ws"]
+            recon, kld, out = (torch.empty(N, device=x.device, dtype=torch.float32) for _ in range(3))
+            for i0, i1 in chunks:
+                c = i1 - i0
+                xc = x[i0:i1]
+                self._encode_stats(b, xc, c)
+                L.call("ardae_vae_aux_elbo_rows", d, flat, packed, xc, None if fwd_eps is None else fwd_eps.view(N, w)[i0:i1], c, seed, f0, f1, i0, ws,
+                       ws.numel(), recon[i0:i1], kld[i0:i1])
+                L.call("ardae_vae_aux_iwae_draw", d, flat, packed, xc, b["mu"], b["lv"], None if eps is None else eps[i0:i1], c, k, seed, o0, o1, i0, ws,
+                       ws.numel(), b["z"], b["logq"], None)
+                self._decode_rows(b, xc, b["z"], c, k, b["rec"], self.group)
+                L.call("ardae_iwae_reduce", b["rec"], b["pri"], b["logq"], c, k, out[i0:i1])
+        return recon, kld, out
+
     def evaluate(self, x_all, eps=None, fwd_eps=None):
         """-> (elbo, logprob): the means over x_all of -(recon + kld) at beta = 1 and of the IWAE bound (evaluate_iws' `total_elbo / num_data`,
         `total_logprob / num_data`), each one reduction of an [N] buffer in double; one host synchronisation."""
@@ -202,8 +242,8 @@ class VaeEngine:
 
     def __init__(self, model, cfg: VaeConfig, batch_size, graph=True):
         if not isinstance(model, GaussianVAE):
-            raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE); the "
-                            "implicit models take net.ArdaeEngine")
+            raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE / "
+                            "net.MNISTAuxVAE / net.ToyAuxVAE); the implicit models take net.ArdaeEngine")
         if not isinstance(cfg, VaeConfig):
             raise TypeError(f"VaeEngine takes a VaeConfig, not a {type(cfg).__name__}")
         model._require_gpu()
@@ -215,7 +255,8 @@ class VaeEngine:
         self.loss_scale = 1.0 / float(self.D) if cfg.loss_scale is None else float(cfg.loss_scale)
         f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
         self.ws = f(L.query("ardae_model_workspace_floats", model._desc, self.B, 1, 1))
-        self.z, self.eps, self.losses = f(self.B, self.zd), f(self.B, self.zd), f(3)
+        self.ew = model._eps_width                              # floats per image of the step's draw (z_dim; the auxiliary-variable models: noise_dim + z_dim)
+        self.z, self.eps, self.losses = f(self.B, self.zd), f(self.B, self.ew), f(3)
         self.grads = torch.zeros_like(model._flat)
         self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self._state_f32 = self.state.view(torch.float32)       # float 6: the block's beta
@@ -264,11 +305,12 @@ class VaeEngine:
         self.opt.advance(self.RNG_STRIDE)      # for the NEXT step: Philox base += stride, t += 1, beta of the next i_ep
 
     def step(self, x, eps=None):
-        """One update on the B images x [B, ...]; eps [B, z_dim] injects the posterior draw (parity tests)."""
+        """One update on the B images x [B, ...]; eps [B, z_dim] injects the posterior draw (parity tests; MNISTAuxVAE / ToyAuxVAE:
+        [B, noise_dim + z_dim], rows [eps0 | eps])."""
         self._require_trained("step()")
         self._check_batch(x, "step(x)")
         if eps is not None:
-            check_tensor(eps, "step(eps)", self.dev, numel=self.B * self.zd)
+            check_tensor(eps, "step(eps)", self.dev, numel=self.B * self.ew)
         if self.use_graph and eps is None and x is not self._x:
             x = self.input_buffer().copy_(x.reshape(self.B, self.D))       # the static batch buffer the captured launches read
         else:

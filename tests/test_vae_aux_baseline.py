@@ -1,0 +1,503 @@
+"""Auxiliary-variable Gaussian baselines (ardae_model_desc.kind 14 / 15, the reference's vae.py --model auxmnist / auxtoy): layout, descriptor rules
+and argument validation through the C ABI, the module surface, and a float64 numpy restatement of the model - forward, both KLs, the closed-form
+backward and the three-stage logprob - that the GPU tests lean on, pinned here to the reference's fp64 fixtures.  No GPU needed."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import ardae_amd as net
+from ardae_amd import _lib as L
+from ardae_amd import layout
+from oracle import ardae_oracle as O
+from test_vae_baseline import load
+
+KIND_ID = {"mnist": 14, "toy": 15}
+CASES = ("auxmnist_n100_z32_b3", "auxmnist_n10_z6_b5_spm6", "auxtoy_n2_z2_b7", "auxtoy_n5_z3_b4_hard")
+TRAJ = ("auxmnist", "auxtoy")
+BETAS = {"b1": 1.0, "b03": 0.3}
+LOG_2PI = math.log(2 * math.pi)
+
+
+def rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-300))
+
+
+def summary(t):
+    t = np.asarray(t).reshape(-1)
+    return np.concatenate([[np.linalg.norm(t), t.sum()], t[:8]])
+
+
+def summary_err(t, want):
+    """The worst of a tensor's three distances to a stored summary: the L2 norm, the sum on the scale of its terms, the first 8 elements"""
+    got, want = summary(t), np.asarray(want, dtype=np.float64)
+    return max(abs(got[0] - want[0]) / want[0], abs(got[1] - want[1]) / (want[0] * math.sqrt(np.asarray(t).size)), rel(got[2:], want[2:]))
+
+
+def shape_of(fx):
+    """-> family, (B, D, h, noise, z, L), act, clip"""
+    return str(fx["family"]), tuple(int(v) for v in fx["shape"]), str(fx["act"]), str(fx["clip"])
+
+
+def aux_params(fx, dtype=torch.float32):
+    """The parameters of a fixture, regenerated as tools/gen_vae_aux_golden.py::aux_params made them"""
+    family, (B, D, h, nd, z, nl), _, _ = shape_of(fx)
+    p = O.init_params(layout.aux_vae_spec(family, D, nd, h, z, nl), int(fx["seed"]), None, dtype)
+    p["aux_encode.reparam.logvar_fn.bias"].add_(torch.linspace(-5.0, 2.5, nd, dtype=dtype))
+    return p
+
+
+def params64(fx):
+    """... as the float64 runs of the generator saw them: the fp32 numbers, widened"""
+    return {k: v.double().numpy() for k, v in aux_params(fx).items()}
+
+
+# ---- the test-side oracle: the model restated in float64 numpy, backward by hand ----------------------------------------------------
+def sigmoid(v):
+    return 0.5 * (1.0 + np.tanh(0.5 * v))
+
+
+def softplus(v):
+    return np.logaddexp(0.0, v)
+
+
+# activation -> (f(v), f'(v)) on the pre-activation v
+ACT = {"relu": (lambda v: np.maximum(v, 0.0), lambda v: (v > 0).astype(v.dtype)),
+       "softplus": (softplus, sigmoid),
+       "elu": (lambda v: np.where(v > 0, v, np.expm1(np.minimum(v, 0.0))), lambda v: np.where(v > 0, 1.0, np.exp(np.minimum(v, 0.0)))),
+       "tanh": (np.tanh, lambda v: 1.0 - np.tanh(v) ** 2),
+       "leaky_relu": (lambda v: np.where(v > 0, v, 0.2 * v), lambda v: np.where(v > 0, 1.0, 0.2)),
+       "swish": (lambda v: v * sigmoid(v), lambda v: sigmoid(v) * (1.0 + v * (1.0 - sigmoid(v))))}
+SPM = {"softplus": 0.0, "spm10": 10.0, "spm6": 6.0, "spm5": 5.0, "spm4": 4.0, "spm3": 3.0, "spm2": 2.0}
+
+
+def clip_logvar(code, v):
+    """NormalDistribution.clip_logvar (models/reparam.py:17-41) -> (c(v), c'(v))"""
+    if code in (None, "none"):
+        return v, np.ones_like(v)
+    if code == "hard":
+        return np.clip(v, -4.0, 2.0), ((v > -4.0) & (v < 2.0)).astype(v.dtype)
+    if code in SPM:
+        return softplus(v + SPM[code]) - SPM[code], sigmoid(v + SPM[code])
+    s = {"tanh": 1.0, "2tanh": 2.0}[code]
+    return s * np.tanh(v), s * (1.0 - np.tanh(v) ** 2)
+
+
+def mlp_names(p, prefix):
+    n = len([k for k in p if k.startswith(prefix + "layers.") and k.endswith("weight")])
+    return [f"{prefix}layers.{i}" for i in range(n)] + [prefix + "fc"]
+
+
+def mlp_fwd(p, prefix, hdn, act):
+    """models/layers.py MLP(..., use_nonlinearity_output=True): `layers.*` then `fc`, every one followed by the activation -> output, cache"""
+    cache = []
+    for name in mlp_names(p, prefix):
+        pre = hdn @ p[name + ".weight"].T + p[name + ".bias"]
+        cache.append((name, hdn, pre))
+        hdn = ACT[act][0](pre)
+    return hdn, cache
+
+
+def mlp_bwd(p, cache, act, dh, grads):
+    """dL/d output -> dL/d input, the layers' gradients into `grads`"""
+    for name, inp, pre in reversed(cache):
+        dpre = dh * ACT[act][1](pre)
+        grads[name + ".weight"], grads[name + ".bias"] = dpre.T @ inp, dpre.sum(0)
+        dh = dpre @ p[name + ".weight"]
+    return dh
+
+
+def lin(p, name, hdn):
+    return hdn @ p[name + ".weight"].T + p[name + ".bias"]
+
+
+def lin_bwd(p, name, hdn, dout, grads):
+    grads[name + ".weight"], grads[name + ".bias"] = dout.T @ hdn, dout.sum(0)
+    return dout @ p[name + ".weight"]
+
+
+def kld_rows(mu, lv):
+    return -0.5 * (1 + lv - mu ** 2 - np.exp(lv)).sum(1)                                            # utils/vae.py:78-92
+
+
+def pair_kld_rows(mu1, lv1, mu2, lv2):
+    return -0.5 * (1 - lv2 + lv1 - (np.exp(lv1) + (mu1 - mu2) ** 2) / np.exp(lv2)).sum(1)           # utils/vae.py:94-114
+
+
+def recon_rows(family, p, act, x, z):
+    """-log p(x | z) per row -> rows, decoder mean, and what the backward needs"""
+    hd, cache = mlp_fwd(p, "decode.main.", z, act)
+    if family == "mnist":
+        logit = lin(p, "decode.reparam.logit_fn", hd)
+        rows = (np.maximum(logit, 0) - logit * x + np.logaddexp(0.0, -np.abs(logit))).sum(1)        # BCE with logits
+        return rows, sigmoid(logit), (hd, cache, logit, None)
+    mx, lvx = lin(p, "decode.reparam.mean_fn", hd), lin(p, "decode.reparam.logvar_fn", hd)
+    return 0.5 * (lvx + (x - mx) ** 2 / np.exp(lvx) + LOG_2PI).sum(1), mx, (hd, cache, mx, lvx)
+
+
+def forward_backward(family, p, act, clip, x, eps, beta, scale):
+    """VAE.forward (vae/auxmnist.py:337-364) and d (scale * loss) / d p in closed form -> dict(mu0, lv0, z, mean, loss, recon, kld), grads"""
+    B, D = x.shape
+    nd = p["aux_encode.reparam.mean_fn.weight"].shape[0]
+    eps0, epsz = eps[:, :nd], eps[:, nd:]
+    xs = 2 * x - 1 if family == "mnist" else x
+    h0, c0 = mlp_fwd(p, "aux_encode.main.", xs, act)
+    mu0, lv0r = lin(p, "aux_encode.reparam.mean_fn", h0), lin(p, "aux_encode.reparam.logvar_fn", h0)
+    lv0, dclip = clip_logvar(clip, lv0r)
+    z0 = mu0 + np.exp(0.5 * lv0) * eps0
+    h, c1 = mlp_fwd(p, "encode.fc.", np.concatenate([xs, z0], 1), act)
+    mu, lv = lin(p, "encode.reparam.mean_fn", h), lin(p, "encode.reparam.logvar_fn", h)
+    z = mu + np.exp(0.5 * lv) * epsz
+    hr, c2 = mlp_fwd(p, "aux_decode.fc.", np.concatenate([xs, z], 1), act)
+    mup, lvp = lin(p, "aux_decode.reparam.mean_fn", hr), lin(p, "aux_decode.reparam.logvar_fn", hr)
+    rec, mean, (hd, c3, o0, o1) = recon_rows(family, p, act, x, z)
+    kld, aux = kld_rows(mu, lv), pair_kld_rows(mu0, lv0, mup, lvp)
+    out = dict(mu0=mu0, lv0=lv0, z=z, mean=mean, loss=(rec + beta * kld + beta * aux).mean(), recon=rec.mean(), kld=(kld + aux).mean())
+    # ---- backward, c = scale / B
+    c, g = scale / B, {}
+    if family == "mnist":
+        dhd = lin_bwd(p, "decode.reparam.logit_fn", hd, c * (sigmoid(o0) - x), g)
+    else:
+        dhd = lin_bwd(p, "decode.reparam.mean_fn", hd, -c * (x - o0) / np.exp(o1), g)
+        dhd = dhd + lin_bwd(p, "decode.reparam.logvar_fn", hd, 0.5 * c * (1 - (x - o0) ** 2 / np.exp(o1)), g)
+    dz = mlp_bwd(p, c3, act, dhd, g)
+    dmup = c * beta * (mup - mu0) / np.exp(lvp)
+    dlvp = c * beta * 0.5 * (1 - (np.exp(lv0) + (mu0 - mup) ** 2) / np.exp(lvp))
+    dhr = lin_bwd(p, "aux_decode.reparam.mean_fn", hr, dmup, g) + lin_bwd(p, "aux_decode.reparam.logvar_fn", hr, dlvp, g)
+    dz = dz + mlp_bwd(p, c2, act, dhr, g)[:, D:]
+    dmu = dz + c * beta * mu
+    dlv = dz * (z - mu) / 2 + c * beta * (np.exp(lv) - 1) / 2
+    dh = lin_bwd(p, "encode.reparam.mean_fn", h, dmu, g) + lin_bwd(p, "encode.reparam.logvar_fn", h, dlv, g)
+    dz0 = mlp_bwd(p, c1, act, dh, g)[:, D:]
+    dmu0 = dz0 + c * beta * (mu0 - mup) / np.exp(lvp)
+    dlv0 = dz0 * (z0 - mu0) / 2 + c * beta * 0.5 * (np.exp(lv0) / np.exp(lvp) - 1)
+    dh0 = lin_bwd(p, "aux_encode.reparam.mean_fn", h0, dmu0, g) + lin_bwd(p, "aux_encode.reparam.logvar_fn", h0, dlv0 * dclip, g)
+    mlp_bwd(p, c0, act, dh0, g)
+    return out, g
+
+
+def log_normal_rows(v, mu, lv):
+    return (-0.5 * ((v - mu) ** 2 / np.exp(lv) + lv + LOG_2PI)).sum(-1)                             # utils/stat.py:65-85
+
+
+def logq_rows(family, p, act, clip, x, eps):
+    """The three stochastic stages of VAE.logprob (vae/auxmnist.py:381-451, sample_size2 = 1) on injected draws eps [B, k, noise + z]
+    -> z [B k, zd], logq [B k] = log q(z0|x) + log q(z|z0,x) - log r(z0|z,x)"""
+    B, k, _ = eps.shape
+    nd = p["aux_encode.reparam.mean_fn.weight"].shape[0]
+    xs = 2 * x - 1 if family == "mnist" else x
+    h0, _ = mlp_fwd(p, "aux_encode.main.", xs, act)
+    mu0 = lin(p, "aux_encode.reparam.mean_fn", h0)
+    lv0, _ = clip_logvar(clip, lin(p, "aux_encode.reparam.logvar_fn", h0))
+    mu0, lv0, xr = (np.repeat(v, k, 0) for v in (mu0, lv0, xs))
+    e = eps.reshape(B * k, -1)
+    z0 = mu0 + np.exp(0.5 * lv0) * e[:, :nd]
+    h, _ = mlp_fwd(p, "encode.fc.", np.concatenate([xr, z0], 1), act)
+    mu, lv = lin(p, "encode.reparam.mean_fn", h), lin(p, "encode.reparam.logvar_fn", h)
+    z = mu + np.exp(0.5 * lv) * e[:, nd:]
+    hr, _ = mlp_fwd(p, "aux_decode.fc.", np.concatenate([xr, z], 1), act)
+    mup, lvp = lin(p, "aux_decode.reparam.mean_fn", hr), lin(p, "aux_decode.reparam.logvar_fn", hr)
+    return z, log_normal_rows(z0, mu0, lv0) + log_normal_rows(z, mu, lv) - log_normal_rows(z0, mup, lvp)
+
+
+def logprob_rows(family, p, act, clip, x, eps):
+    """VAE.logprob before its mean, [B]"""
+    B, k, _ = eps.shape
+    z, logq = logq_rows(family, p, act, clip, x, eps)
+    rec, _, _ = recon_rows(family, p, act, np.repeat(x, k, 0), z)
+    lw = (-rec + log_normal_rows(z, 0.0, 0.0) - logq).reshape(B, k)
+    m = lw.max(1, keepdims=True)
+    return (np.log(np.mean(np.exp(lw - m), 1, keepdims=True) + 1e-10) + m).reshape(B)
+
+
+def adam_step(p, g, st, lr, beta1, t):
+    """The reference's vendored Adam (utils/optim.py:84-106: epsilon before the bias correction), in place"""
+    bc1, bc2 = 1 - beta1 ** t, 1 - 0.999 ** t
+    for k in p:
+        m, v = st.setdefault(k, (np.zeros_like(p[k]), np.zeros_like(p[k])))
+        m *= beta1
+        m += (1 - beta1) * g[k]
+        v *= 0.999
+        v += (1 - 0.999) * g[k] * g[k]
+        p[k] -= lr / bc1 * m / ((np.sqrt(v) + 1e-8) / math.sqrt(bc2))
+
+
+# ---- 1. the restatement, pinned to the reference ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES)
+def test_restatement_is_the_reference_in_float64(golden_dir, case):
+    fx = load(golden_dir, "vae_" + case)
+    family, (B, D, h, nd, z, nl), act, clip = shape_of(fx)
+    p = params64(fx)
+    x, eps = fx["x"].astype(np.float64), fx["eps"].astype(np.float64)
+    for b, beta in BETAS.items():
+        out, grads = forward_backward(family, p, act, clip, x, eps, beta, 1.0 / D)
+        for k in ("z", "mean", "loss", "recon", "kld"):
+            assert rel(out[k], fx[f"{b}/{k}_f64"]) <= 1e-9, (b, k)
+        assert rel(out["mu0"], fx["mu0_f64"]) <= 1e-9 and rel(out["lv0"], fx["lv0_f64"]) <= 1e-9
+        full = {k[len(b) + 7:]: v for k, v in fx.items() if k.startswith(f"{b}/g_f64/")}
+        summ = {k[len(b) + 8:]: v for k, v in fx.items() if k.startswith(f"{b}/gs_f64/")}
+        assert set(grads) == set(full) | set(summ) == set(p)
+        for k, g in grads.items():
+            assert g.shape == p[k].shape
+            e = rel(g, full[k]) if k in full else summary_err(g, summ[k])
+            assert e <= 1e-9, (b, k, e)
+    lp = logprob_rows(family, p, act, clip, x, fx["lp/eps"].astype(np.float64)).mean()
+    assert rel(lp, fx["lp/value_f64"]) <= 1e-9
+    # the fp32 fixture is the same computation at fp32's precision
+    assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
+    if clip != "none":       # the clip acts on part of the elements
+        raw = lin(p, "aux_encode.reparam.logvar_fn", mlp_fwd(p, "aux_encode.main.", 2 * x - 1 if family == "mnist" else x, act)[0])
+        assert 0.0 < np.mean(np.abs(clip_logvar(clip, raw)[1] - 1.0) > 1e-2) < 1.0
+
+
+@pytest.mark.parametrize("name", TRAJ)
+def test_restated_trajectory_is_the_reference_in_float64(golden_dir, name):
+    fx = load(golden_dir, "vae_traj_" + name)
+    family, (B, D, h, nd, z, nl), act, clip = shape_of(fx)
+    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
+                        beta_annealing=int(fx["cfg/beta_annealing"]))
+    p, st = params64(fx), {}
+    for s in range(int(fx["cfg/steps"])):
+        beta = cfg.beta_at(s)
+        assert beta == float(fx[f"{s}/beta"])
+        out, grads = forward_backward(family, p, act, clip, fx[f"{s}/x"].astype(np.float64), fx[f"{s}/eps"].astype(np.float64), beta, 1.0 / D)
+        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
+        assert rel(out["loss"], fx[f"{s}/loss_f64"]) <= 1e-9 and rel(out["kld"], fx[f"{s}/kld_f64"]) <= 1e-9
+        for k, v in p.items():
+            assert summary_err(v, fx[f"{s}/ps_f64/{k}"]) <= 1e-9, (s, k)
+    assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
+
+
+# ---- 2. layout -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", CASES + tuple("traj_" + t for t in TRAJ))
+def test_spec_names_and_shapes_are_the_fixtures(golden_dir, name):
+    fx = load(golden_dir, "vae_" + name)
+    family, (B, D, h, nd, z, nl), act, clip = shape_of(fx)
+    spec = layout.aux_vae_spec(family, D, nd, h, z, nl)
+    assert [n for n, _ in spec] == [str(n) for n in fx["names"]]
+    assert [",".join(str(d) for d in s) for _, s in spec] == [str(s) for s in fx["shapes"]]
+    desc = L.ModelDesc(KIND_ID[family], D, nd, h, z, nl, L.ACT[act], L.LOGVAR_CLIP[clip] << L.MODEL_CLIP_Z0_SHIFT)
+    total = layout.offsets(spec)[1]
+    assert total == L.query("ardae_model_param_floats", desc)
+    assert L.query("ardae_model_packed_floats", desc) > total
+    sizes = [[L.query("ardae_model_workspace_floats", desc, b, 1, mode) for b in (6, 70, 129)] for mode in (0, 1, 2)]
+    sizes.append([L.query("ardae_model_workspace_floats", desc, b, 16, 4) for b in (6, 70, 129)])
+    for per_mode in sizes:
+        assert 0 < per_mode[0] < per_mode[1] < per_mode[2]
+    assert all(a < b for a, b in zip(sizes[0], sizes[1]))               # the training workspace holds aux_encode's and more
+    assert L.query("ardae_model_workspace_floats", desc, 6, 2, 1) == L.query("ardae_model_workspace_floats", desc, 6, 1, 3) == 0
+    # the module's parameters are the spec, in order, with the reference's state_dict names
+    ctor = net.MNISTAuxVAE if family == "mnist" else net.ToyAuxVAE
+    mod = ctor(input_dim=D, noise_dim=nd, h_dim=h, z_dim=z, nonlinearity=act, num_hidden_layers=nl, clip_logvar=clip)
+    assert [(k, tuple(v.shape)) for k, v in mod.state_dict().items()] == [(n, tuple(s)) for n, s in spec]
+    sd = aux_params(fx)
+    mod.load_state_dict(sd)
+    assert torch.equal(mod.flat_params(), torch.cat([v.reshape(-1) for v in sd.values()]))
+    assert mod._desc.flags == desc.flags and mod._desc.kind == desc.kind
+
+
+def test_parameter_counts_at_the_recipe_widths(golden_dir):
+    counts = load(golden_dir, "vae_aux_param_counts")
+    assert sorted(counts) == ["auxmnist_784_100_300_32_2", "auxtoy_2_2_64_2_1"]
+    for key, want in counts.items():
+        family = "mnist" if key.startswith("auxmnist") else "toy"
+        D, nd, h, z, nl = (int(v) for v in key.split("_")[1:])
+        d = L.ModelDesc(KIND_ID[family], D, nd, h, z, nl, L.ACT["softplus"], 0)
+        assert layout.offsets(layout.aux_vae_spec(family, D, nd, h, z, nl))[1] == L.query("ardae_model_param_floats", d) == int(want)
+    assert sum(p.numel() for p in net.MNISTAuxVAE().parameters()) == int(counts["auxmnist_784_100_300_32_2"])
+    assert sum(p.numel() for p in net.ToyAuxVAE().parameters()) == int(counts["auxtoy_2_2_64_2_1"])
+    assert L.query("ardae_vae_head_fused_ok", L.ModelDesc(14, 784, 100, 300, 32, 2, L.ACT["softplus"], 0)) == 1      # the recipe's z head: kind 8's policy
+    assert L.query("ardae_vae_head_fused_ok", L.ModelDesc(15, 2, 2, 64, 2, 1, L.ACT["tanh"], 0)) == 0
+    assert net.modules.KIND_IDS["vae_auxmnist"] == 14 and net.modules.KIND_IDS["vae_auxtoy"] == 15
+    with pytest.raises(NotImplementedError):
+        layout.aux_vae_spec("conv", 784, 100, 300, 32, 2)
+
+
+# ---- 3. descriptor rules and refusals, before any HIP call --------------------------------------------------------------------------
+one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
+ref = ctypes.byref
+
+
+def fails(rc, fragment):
+    lib = L.lib()
+    assert rc < 0
+    assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
+
+
+def accepted(d):
+    lib = L.lib()
+    ok = lib.ardae_model_param_floats(ref(d)) > 0
+    assert ok == (lib.ardae_model_packed_floats(ref(d)) > 0) == (lib.ardae_model_workspace_floats(ref(d), 3, 1, 1) > 0)
+    assert ok == (lib.ardae_model_pack(ref(d), one, None, None) == -1 and b"null pointer" in lib.ardae_last_error())
+    return ok
+
+
+def test_descriptor_rules():
+    for k in (14, 15):
+        assert accepted(L.ModelDesc(k, 1, 1, 1, 1, 1, 1, 0))                                   # the smallest descriptor
+        assert accepted(L.ModelDesc(k, 12, 128, 16, 4, 4, 2, 0)) and not accepted(L.ModelDesc(k, 12, 129, 16, 4, 2, 2, 0))
+        assert not accepted(L.ModelDesc(k, 12, 0, 16, 4, 2, 2, 0)) and not accepted(L.ModelDesc(k, 12, -1, 16, 4, 2, 2, 0))
+        fails(L.lib().ardae_model_pack(ref(L.ModelDesc(k, 12, 0, 16, 4, 2, 2, 0)), one, one, None), "noise_dim must be 1 .. 128")
+        for bad in (L.ModelDesc(k, 12, 3, 16, 0, 2, 2, 0), L.ModelDesc(k, 12, 3, 16, 4, 0, 2, 0), L.ModelDesc(k, 12, 3, 16, 4, 5, 2, 0),
+                    L.ModelDesc(k, 0, 3, 16, 4, 2, 2, 0), L.ModelDesc(k, 12, 3, 0, 4, 2, 2, 0)):
+            assert not accepted(bad)
+            fails(L.lib().ardae_model_pack(ref(bad), one, one, None), "bad dimensions")
+        assert not accepted(L.ModelDesc(k, 12, 3, 16, 4, 2, 0, 0)) and not accepted(L.ModelDesc(k, 12, 3, 16, 4, 2, 7, 0))
+        # flags: aux_encode's clip code 0 .. 10, nothing else
+        for code in range(16):
+            assert accepted(L.ModelDesc(k, 12, 3, 16, 4, 2, 2, code << L.MODEL_CLIP_Z0_SHIFT)) == (code <= 10), code
+        for bit in range(31):
+            if not 8 <= bit <= 11:
+                assert not accepted(L.ModelDesc(k, 12, 3, 16, 4, 2, 2, 1 << bit)), bit
+                assert not accepted(L.ModelDesc(k, 12, 3, 16, 4, 2, 2, (1 << bit) | (4 << L.MODEL_CLIP_Z0_SHIFT))), bit
+        fails(L.lib().ardae_model_pack(ref(L.ModelDesc(k, 12, 3, 16, 4, 2, 2, 1 << L.MODEL_CLIP_Z_SHIFT)), one, one, None), "unknown flags")
+    # 13 stays no kind, as 10 does
+    for k in (10, 13, 16, -1):
+        bad = L.ModelDesc(k, 12, 3, 16, 4, 2, 2, 0)
+        assert L.lib().ardae_model_param_floats(ref(bad)) == 0
+        fails(L.lib().ardae_model_pack(ref(bad), one, one, None), "kind must be")
+        fails(L.lib().ardae_vae_encode_stats(ref(bad), one, one, one, 4, one, big, one, one, None), "kind must be")
+    # kind 15 needs the Gaussian decoder's second output, kind 14 does not
+    assert L.lib().ardae_model_decode(ref(L.ModelDesc(15, 2, 2, 16, 2, 1, 2, 0)), one, one, one, 4, one, small, one, None, None) < 0
+    assert b"needs out1" in L.lib().ardae_last_error()
+    fails(L.lib().ardae_model_decode(ref(L.ModelDesc(14, 12, 3, 16, 4, 2, 2, 0)), one, one, one, 4, one, small, one, None, None), "workspace too small")
+
+
+def test_argument_validation_of_every_entry_point():
+    lib = L.lib()
+    fwd = lambda d, x, B, wsf, z, losses: lib.ardae_vae_forward(ref(d), one, one, x, None, B, 1.0, 1.0, 7, 0, None, one, wsf, z, None, losses, None)
+    fwd_dev = lambda d, st: lib.ardae_vae_forward_dev(ref(d), one, one, one, None, 4, st, 1.0, 7, 0, None, one, big, one, None, one, None)
+    bwd = lambda d, B, wsf, g: lib.ardae_vae_backward(ref(d), one, one, one, B, 1.0, 1.0, one, wsf, g, 0.0, None)
+    bwd_dev = lambda d, st: lib.ardae_vae_backward_dev(ref(d), one, one, one, 4, st, 1.0, one, big, one, 0.0, None)
+    stats = lambda d, B, wsf, mu, lv: lib.ardae_vae_encode_stats(ref(d), one, one, one, B, one, wsf, mu, lv, None)
+    head = lambda d, B, variant, mu, eps_out=one: lib.ardae_vae_head(ref(d), one, one, one, None, B, 7, 0, None, variant, mu, one, one, eps_out, one, None)
+    draw = lambda d, x, B, k, first, wsf, z, lq, eps=None: lib.ardae_vae_aux_iwae_draw(ref(d), one, one, x, one, one, eps, B, k, 7, 0, 1, first, one, wsf, z, lq,
+                                                                                       None, None)
+    elbo = lambda d, x, B, first, wsf, rec, kld, eps=None: lib.ardae_vae_aux_elbo_rows(ref(d), one, one, x, eps, B, 7, 0, 1, first, one, wsf, rec, kld, None)
+    for k in (14, 15):
+        ok = L.ModelDesc(k, 12, 3, 16, 5, 2, 2, 0)
+        assert lib.ardae_model_workspace_floats(ref(ok), 4, 1, 1) > lib.ardae_model_workspace_floats(ref(ok), 4, 1, 0) > 0
+        assert lib.ardae_model_workspace_floats(ref(ok), 4, 16, 4) > lib.ardae_model_workspace_floats(ref(ok), 4, 8, 4) > 0
+        bad = L.ModelDesc(k, 12, 0, 16, 5, 2, 2, 0)
+        why = "noise_dim must be"
+        assert lib.ardae_vae_head_fused_ok(ref(bad)) == 0
+        for rc in (fwd(bad, one, 4, big, one, one), bwd(bad, 4, big, one), stats(bad, 4, big, one, one), head(bad, 4, 0, one)):
+            fails(rc, why)
+        fails(draw(bad, one, 4, 16, 0, big, one, one), why)
+        fails(elbo(bad, one, 4, 0, big, one, one), why)
+        fails(fwd(ok, one, 0, big, one, one), "bad batch")
+        fails(fwd(ok, one, -3, big, one, one), "bad batch")
+        fails(fwd(ok, one, 4, small, one, one), "workspace too small")
+        fails(fwd(ok, None, 4, big, one, one), "null pointer")
+        fails(fwd(ok, one, 4, big, None, one), "null pointer")
+        fails(fwd(ok, one, 4, big, one, None), "null pointer")
+        fails(fwd_dev(ok, None), "beta_state is NULL")
+        fails(bwd(ok, 0, big, one), "bad batch")
+        fails(bwd(ok, 4, small, one), "workspace too small")
+        fails(bwd(ok, 4, big, None), "null pointer")
+        fails(bwd_dev(ok, None), "beta_state is NULL")
+        fails(stats(ok, 0, big, one, one), "bad batch")
+        fails(stats(ok, 4, small, one, one), "workspace too small")
+        fails(stats(ok, 4, big, None, one), "null pointer")
+        fails(stats(ok, 4, big, one, None), "null pointer")
+        fails(head(ok, 0, 1, one), "bad batch")
+        fails(head(ok, 4, 3, one), "variant must be")
+        fails(head(ok, 4, 1, None), "null pointer")
+        fails(head(ok, 4, 2, one, eps_out=None), "null pointer")
+        fails(head(L.ModelDesc(k, 12, 3, 16, 65, 2, 2, 0), 4, 1, one), "the fused head takes")
+        # the two new entry points
+        fails(draw(ok, one, 0, 16, 0, big, one, one), "bad batch")
+        fails(draw(ok, one, 4, 0, 0, big, one, one), "bad batch")
+        fails(draw(ok, one, 1 << 20, 1 << 12, 0, big, one, one), "bad batch")
+        fails(draw(ok, one, 4, 16, 0, small, one, one), "workspace too small")
+        fails(draw(ok, None, 4, 16, 0, big, one, one), "null pointer")
+        fails(draw(ok, one, 4, 16, 0, big, None, one), "null pointer")
+        fails(draw(ok, one, 4, 16, 0, big, one, None), "null pointer")
+        fails(draw(ok, one, 4, 3, 1, big, one, one), "multiples of 4")                        # 1 x 3 x 3 normals before the chunk: no whole counter
+        fails(draw(ok, one, 4, 3, 1, small, one, one, eps=one), "workspace too small")        # ... which injected draws do not need
+        fails(draw(L.ModelDesc(k, 12, 3, 16, 129, 2, 2, 0), one, 4, 16, 0, big, one, one), "z_dim <= 128")
+        fails(elbo(ok, one, 0, 0, big, one, one), "bad batch")
+        fails(elbo(ok, one, 4, 0, small, one, one), "workspace too small")
+        fails(elbo(ok, None, 4, 0, big, one, one), "null pointer")
+        fails(elbo(ok, one, 4, 0, big, None, one), "null pointer")
+        fails(elbo(ok, one, 4, 0, big, one, None), "null pointer")
+        fails(elbo(ok, one, 4, 2, big, one, one), "multiples of 4")
+        # the implicit models' calls refuse the family: there is no sampler
+        fails(lib.ardae_model_encode(ref(ok), one, one, one, None, 4, 1, one, big, one, None), "analytic posterior")
+        fails(lib.ardae_model_vae_forward(ref(ok), one, one, one, one, 4, 1, 1.0, one, big, one, one, None), "ardae_vae_forward")
+        fails(lib.ardae_model_vae_backward(ref(ok), one, one, one, one, 4, 1, 1.0, 1.0, None, one, big, one, 0.0, None), "ardae_vae_backward")
+        fails(lib.ardae_model_vae_backward_decoder(ref(ok), one, one, one, one, 4, 1, 1.0, 1.0, one, big, None), "no split backward")
+        fails(lib.ardae_model_encode_hidden(ref(ok), one, one, one, 4, one, big, one, None, None), "hidden1a context")
+    # the kinds of the other families at the new entry points
+    for k in (8, 3, 13):
+        other = L.ModelDesc(k, 12, 0 if k == 8 else 3, 16, 4, 2, 2, 0)
+        fails(draw(other, one, 4, 16, 0, big, one, one), "kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE)")
+        fails(elbo(other, one, 4, 0, big, one, one), "kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE)")
+    pair = lambda mu, B, n, out: lib.ardae_vae_pair_kld_rows(mu, one, one, one, B, n, out, None)
+    fails(pair(one, 0, 4, one), "bad batch")
+    fails(pair(one, 4, 0, one), "bad batch")
+    fails(pair(one, 4, 129, one), "bad batch")
+    fails(pair(None, 4, 4, one), "null pointer")
+    fails(pair(one, 4, 4, None), "null pointer")
+
+
+# ---- 4. the module surface -----------------------------------------------------------------------------------------------------------
+def test_module_surface_and_refusals():
+    m = net.MNISTAuxVAE()
+    assert (m.input_dim, m.noise_dim, m.h_dim, m.z_dim, m.nonlinearity, m.num_hidden_layers, m.enc_type, m.clip_logvar, m.do_xavier, m.do_m5bias) == \
+        (784, 100, 300, 32, "softplus", 2, "simple", None, True, False)
+    assert isinstance(m, net.GaussianVAE) and m.latent_dim == 32 and m._eps_width == 132
+    p = {k: v.detach() for k, v in m.named_parameters()}
+    assert all(float(v.abs().max()) == 0.0 for k, v in p.items() if k.endswith("bias"))                       # do_xavier: weight_init
+    bound = math.sqrt(6.0 / (884 + 300))
+    assert 0.5 * bound < float(p["encode.fc.layers.0.weight"].abs().max()) <= bound
+    m5 = net.MNISTAuxVAE(input_dim=12, noise_dim=5, h_dim=16, z_dim=4, do_xavier=False, do_m5bias=True, clip_logvar="none")
+    assert m5.clip_logvar is None and m5._desc.flags == 0                                                      # 'none' means None (vae/auxmnist.py:291)
+    b = dict(m5.named_parameters())["decode.reparam.logit_fn.bias"].detach()
+    assert float(b.min()) == float(b.max()) == -5.0
+    assert float(dict(m5.named_parameters())["aux_decode.fc.fc.bias"].detach().abs().max()) > 0.0
+    torch.manual_seed(0)
+    t = net.ToyAuxVAE(h_dim=256)
+    assert (t.input_dim, t.noise_dim, t.h_dim, t.z_dim, t.nonlinearity, t.num_hidden_layers, t.init, t.enc_type, t.clip_logvar) == \
+        (2, 2, 256, 2, "tanh", 1, "gaussian", "simple", None)
+    w = dict(t.named_parameters())["decode.reparam.mean_fn.weight"].detach()
+    assert float(w.abs().max()) > 1.5 and abs(float(w.std()) - 1.0) < 0.15                                     # N(0, 1), not U(+-1/16)
+    assert net.ToyAuxVAE(clip_logvar="spm6")._desc.flags == 4 << L.MODEL_CLIP_Z0_SHIFT
+    for ctor in (net.MNISTAuxVAE, net.ToyAuxVAE):
+        with pytest.raises(NotImplementedError, match="enc_type 'mlp'"):
+            ctor(enc_type="mlp")
+        with pytest.raises(NotImplementedError, match="clip_logvar 'sigmoid'"):
+            ctor(clip_logvar="sigmoid")
+        with pytest.raises(NotImplementedError, match="normal_energy_func"):
+            ctor(energy_func=lambda z: z)
+        with pytest.raises(NotImplementedError, match="gelu"):
+            ctor(nonlinearity="gelu")
+        with pytest.raises(ValueError, match="noise_dim"):
+            ctor(noise_dim=0)
+        with pytest.raises(ValueError, match="noise_dim"):
+            ctor(noise_dim=129)
+    for mod in (m5, t):       # execution on the CPU is refused
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            mod(torch.zeros(3, mod.input_dim))
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            mod.logprob(torch.zeros(3, mod.input_dim), sample_size=4)
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            mod.encode_stats(torch.zeros(3, mod.input_dim))
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            mod.generate(2)
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            net.VaeEngine(mod, net.VaeConfig(), batch_size=4)
+    # the engine / evaluator type checks keep naming the existing classes, and name the new ones
+    with pytest.raises(TypeError, match="VaeEngine drives.*net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE.*net.MNISTAuxVAE"):
+        net.VaeEngine(net.MNISTAuxIPVAE(input_dim=12, noise_dim=4, h_dim=16, z_dim=4), net.VaeConfig(), batch_size=4)
+    with pytest.raises(TypeError, match="net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE.*net.ToyAuxVAE"):
+        net.GaussianIwaeEvaluator(net.ToyAuxIPVAE(), 16)
+    ev = net.GaussianIwaeEvaluator(m5, 16)
+    assert ev.aux and ev.sd == 5 and not ev.gaussian and net.GaussianIwaeEvaluator(t, 16).gaussian
+    with pytest.raises(NotImplementedError, match="z_dim 129 > 128"):
+        net.GaussianIwaeEvaluator(net.MNISTAuxVAE(input_dim=12, noise_dim=5, h_dim=16, z_dim=129), 16)
+    wide = net.MNISTAuxVAE(input_dim=12, noise_dim=5, h_dim=16, z_dim=100)      # wider than kind 8's draw takes: the aux draw's own limit holds
+    assert net.GaussianIwaeEvaluator(wide, 16).plan(5) == [(0, 5)]
