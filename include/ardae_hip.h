@@ -377,8 +377,8 @@ int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, doubl
  *                        cat(h0, h) [B, 2 h_dim] */
 typedef struct ardae_model_desc {
   int kind;     /* 0 .. 7 above; 8 / 9 / 11 / 12: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0);
-                 * 14 / 15: the auxiliary-variable baselines (see "Auxiliary-variable Gaussian baselines" below).
-                 * 10 is not a kind */
+                 * 14 / 15 / 17: the auxiliary-variable baselines (see "Auxiliary-variable Gaussian baselines" and "the hierarchical conv baseline" below).
+                 * 10, 13 and 16 are not kinds */
   int input_dim, noise_dim, h_dim, z_dim;
   int n_layers; /* --model-n-layers */
   int act;      /* any ARDAE_ACT_* but NONE; kinds 5 / 6: ARDAE_ACT_ELU */
@@ -400,7 +400,7 @@ enum { ARDAE_MODEL_NO_CENTER = 1,
        ARDAE_MODEL_CLIP_Z0_SHIFT = 8, ARDAE_MODEL_CLIP_Z_SHIFT = 12, ARDAE_MODEL_CLIP_MASK = 0xff00 };
 size_t ardae_model_param_floats(const ardae_model_desc* d);
 size_t ardae_model_packed_floats(const ardae_model_desc* d);
-/* mode 0: encode only; mode 1: vae_forward + vae_backward; mode 2: decode only (B = rows, nz = 1); mode 3: encode_pair; mode 4: kinds 14 / 15 only,
+/* mode 0: encode only; mode 1: vae_forward + vae_backward; mode 2: decode only (B = rows, nz = 1); mode 3: encode_pair; mode 4: kinds 14 / 15 / 17 only,
  * ardae_vae_aux_iwae_draw on B images x nz samples */
 size_t ardae_model_workspace_floats(const ardae_model_desc* d, int B, int nz, int mode);
 int ardae_model_pack(const ardae_model_desc* d, const float* params, float* packed, void* stream);
@@ -584,6 +584,32 @@ int ardae_vae_pair_kld_rows(const float* mu1, const float* lv1, const float* mu2
 int ardae_vae_aux_iwae_draw(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* mu0, const float* lv0,
                             const float* eps, int B, int k, uint64_t seed, uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace,
                             size_t workspace_floats, float* z_out, float* logq, float* eps_out, void* stream);
+
+/* ---- the hierarchical conv baseline of vae.py (models/vae/auxconv.py; csrc/auxconvvae.hip): ardae_model_desc.kind 17 ------
+ * The Gaussian counterpart of kind 4, `vae.py --model auxconv` (the "# hierarchical conv" baseline of run_vae_dbmnist.sh).  16 is not a kind.
+ *   kind 17 (MNISTConvAuxVAE; 28 x 28 x 1 only): aux_encode.{conv1,2,3, fc 512 -> 800, reparam.{mean_fn, logvar_fn} [noise_dim, 800]},
+ *                        encode.{conv1,2,3, fc (512 + noise_dim) -> 800, reparam.* [z_dim, 800]}, kind 11's decoder, aux_decode.{conv1,2,3,
+ *                        fc (512 + z_dim) -> 800, reparam.* [noise_dim, 800]}: three conv trunks on the same 2x - 1, each with its own weights; the trunk
+ *                        output comes FIRST in both concatenations; no log-variance clip.
+ * input_dim 784, h_dim 800, n_layers 1, 1 <= noise_dim <= 128 (the width of z0), z_dim >= 1 (<= 128 for ardae_vae_aux_iwae_draw), flags 0, any activation
+ * but NONE.  Workspace modes as for kinds 14 / 15 (0: encode_stats, which returns mu0, lv0; 1: forward + backward; 2: decode; 4: ardae_vae_aux_iwae_draw).
+ * Every ardae_vae_* entry point takes it with kind 14's conventions (eps rows [eps0 | eps], the Philox elements of an own draw, losses[2] = mean(kld +
+ * aux_kld)); the z head has kind 11's variants and policy; ardae_vae_aux_elbo_rows and ardae_vae_aux_iwae_draw take it unchanged.
+ *
+ * The decoder's last two stages on their own: u1 [R, 8, 8, 32] NHWC - decode.deconv1's activated output with its zero pad - -> decode.deconv2
+ * (ConvTranspose2d 32 -> 16, k5 s2 p2, 8 x 8 -> 15 x 15) + bias + activation -> decode.reparam.logit_fn (16 -> 1, 15 x 15 -> 29 x 29, cropped) + bias
+ * -> logits [R, 784].
+ *   variant 1: conv_tail_kernel, ONE launch, a workgroup per image: u1 and the 15 x 15 x 16 map stay in LDS, the weights come from `packed` (re-laid by
+ *              ardae_model_pack) by scalar loads; every output is one FP32 FMA chain in a fixed order (input channel ascending, within it the taps
+ *              ascending; then bias and activation), so a row's bits do not depend on R.  Needs no workspace (it may be NULL).
+ *   variant 2: the four launches the training forward runs (linear, col2im, linear, col2im); workspace: ardae_conv_tail_workspace_floats(d, R, 2) floats.
+ *   variant 0: what ardae_model_decode runs for kind 17: variant 1, unless ARDAE_CONV_TAIL_UNFUSED=1 is set under ARDAE_DEBUG_KNOBS=1 (then the mode-2
+ *              workspace of the kind grows by c2, u2, c3 and the logits: ~5.2e4 floats per decoded row in place of ~1.6e4).
+ * Kinds 2 / 4 / 11 and kind 17's training forward run the unfused launches.
+ * ardae_conv_tail_workspace_floats: the floats `variant` needs at R rows (0 for the fused kernel, and for bad arguments). */
+size_t ardae_conv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant);
+int ardae_conv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* u1, int R, int variant, float* workspace,
+                    size_t workspace_floats, float* logits, void* stream);
 
 /* The last stage of the residual-conv decoder on its own (kind 12; csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
  * -> bilinear x2 upsampling (align_corners) -> decode.dec.17 = ResConv2d(16 -> 1) -> logits [R, 784].  It reads the effective weights ardae_model_pack

@@ -1,0 +1,400 @@
+// The hierarchical conv Gaussian baseline (vae.py --model auxconv; ardae_model_desc.kind 17: models/vae/auxconv.py::VAE, the "# hierarchical conv"
+// baseline of run_vae_dbmnist.sh) - the Gaussian counterpart of kind 4, joined from pieces the other families own: the conv trunk and the decoder of
+// csrc/convmodel.hip, the Gaussian head (csrc/vaemodel.h), the pair KL, its seed and the evaluation's row kernel (csrc/auxvae.hip).
+//
+//   per image (B rows):  x2 = 2x - 1; three trunks (conv 1 -> 16 -> 32 -> 32, k5 s2 p2) on the SAME x2, each with its own weights, one im2col of x2
+//     aux_encode   h3a = trunk_a(x2);  h4a = act(Fa h3a + fa)  [B, 800];  mu0 = M0 h4a + m0;  lv0 = L0 h4a + l0 (no clip);  z0 = mu0 + exp(lv0 / 2) eps0
+//     encode       h4 = act(Fe [h3e | z0] + fe);  mu, lv, z, kld: the Gaussian head on h4 (kind 11's policy: the tail form)
+//     aux_decode   h4r = act(Fr [h3r | z] + fr);  mup = Mp h4r + mp;  lvp = Lp h4r + lp;  aux_kld = KL(N(mu0, exp lv0) || N(mup, exp lvp)), added into kld
+//     decode       kind 11's decoder (models/vae/conv.py::Decoder), Bernoulli reconstruction rows
+//   losses = {mean_b(recon_b + beta (kld_b + aux_kld_b)), mean recon, mean (kld + aux_kld)}
+//   (the trunk half of Fe / Fr enters as a row bias, computed once per image: the same code serves the evaluation's k rows per image)
+// Backward (c = loss_scale / B), every reparameterisation and both KLs in closed form, as csrc/auxvae.hip's: the reconstruction seed and the decoder; the
+// pair KL's seed; aux_decode back into its z columns (dz = the decoder's + the auxiliary decoder's) and into h3r; the head's seed; encode back into z0
+// and h3e; the first head's seed; aux_encode; the three trunks; every weight gradient - 28 problems - in one list.
+// Decode-only (ardae_model_decode: the importance samples, generate, decode_params): the decoder up to u1, then conv_tail_kernel - unless
+// ARDAE_CONV_TAIL_UNFUSED=1 under ARDAE_DEBUG_KNOBS=1.  The training forward keeps the unfused launches.
+#include <cmath>
+
+#include "ardae_hip.h"
+#include "auxconvvae.h"
+#include "auxvae.h"
+#include "common.h"
+#include "convmodel.h"
+#include "vaemodel.h"
+
+namespace ardae {
+namespace {
+
+enum { TR_A = 0, TR_E = 1, TR_R = 2 };      // the three trunks: aux_encode, encode, aux_decode
+
+struct AuxConvVaeLayout {
+  int nd, zd, act, h = 800;
+  Lin conv[3][3], afc, mean0, logvar0, efc, mean, logvar, rfc, meanp, logvarp;
+  ConvLayout dec;                  // dfc / dcv only
+  size_t total;
+  explicit AuxConvVaeLayout(const ardae_model_desc& d) : nd(d.noise_dim), zd(d.z_dim), act(d.act) {
+    size_t off = 0;
+    auto trunk = [&](Lin* c) { c[0] = next_lin(off, 16, 1 * 25); c[1] = next_lin(off, 32, 16 * 25); c[2] = next_lin(off, 32, 32 * 25); };
+    trunk(conv[TR_A]); afc = next_lin(off, 800, 512); mean0 = next_lin(off, nd, 800); logvar0 = next_lin(off, nd, 800);
+    trunk(conv[TR_E]); efc = next_lin(off, 800, 512 + nd); mean = next_lin(off, zd, 800); logvar = next_lin(off, zd, 800);
+    dec.zd = zd; dec.act = act;
+    dec.decoder(off);
+    trunk(conv[TR_R]); rfc = next_lin(off, 800, 512 + zd); meanp = next_lin(off, nd, 800); logvarp = next_lin(off, nd, 800);
+    total = off;
+  }
+};
+
+// Linear on cat[h3, s] (h3 [B, 512] a trunk's output, FIRST in the concat; s [R, sd]): both halves forward and backward-data - unlike csrc/auxvae.hip's
+// CondStack, whose first half is the image and takes no gradient
+struct CatLin { size_t i_f, i_b, s_f, s_b; };
+
+struct AuxConvVaePacked {
+  size_t conv_f[3][3], conv_b[3][3], afc_f, afc_b, mean0_f, mean0_b, logvar0_f, logvar0_b, mean_f, mean_b, logvar_f, logvar_b, meanp_f, meanp_b, logvarp_f,
+      logvarp_b;
+  CatLin efc, rfc;
+  ConvPacked dec;
+  size_t tail_w2, tail_w3;         // conv_tail_kernel's weights (launch_conv_tail_pack fills them after the pack launch)
+  AuxConvVaePacked(const AuxConvVaeLayout& P, PackList& pl) {
+    auto trunk = [&](int k) { for (int i = 0; i < 3; ++i) pl.pair(P.conv[k][i], conv_f[k][i], conv_b[k][i]); };
+    auto cat = [&](const Lin& l, CatLin& c) { pl.pair(l, c.i_f, c.i_b, 0, 512); pl.pair(l, c.s_f, c.s_b, 512, l.in - 512); };
+    trunk(TR_A); pl.pair(P.afc, afc_f, afc_b); pl.pair(P.mean0, mean0_f, mean0_b); pl.pair(P.logvar0, logvar0_f, logvar0_b);
+    trunk(TR_E); cat(P.efc, efc); pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
+    dec.decoder_panels(P.dec, pl);
+    trunk(TR_R); cat(P.rfc, rfc); pl.pair(P.meanp, meanp_f, meanp_b); pl.pair(P.logvarp, logvarp_f, logvarp_b);
+    tail_w2 = pl.take(CT_W2); tail_w3 = pl.take(CT_W3);
+  }
+  explicit AuxConvVaePacked(const AuxConvVaeLayout& P, PackList&& sizing = PackList()) : AuxConvVaePacked(P, sizing) {}   // offsets only
+};
+
+// one trunk's buffers on B images; cols[0], the im2col rows of x2, is the same buffer in all three
+struct TrunkBuf { float *cols[3], *hcv[3], *inp, *dinp, *dh3, *dh2, *dh1; };
+
+struct AuxConvVaeWs {
+  ConvWs C;                        // x2, the decoder's buffers, t1 = h4 [B, 800] and dt1, z, dzq / dz (the decoder's), dinp_t / dcols3 / dcols2 (trunk_bwd's scratch)
+  TrunkBuf T[3];
+  float *h4a, *mu0, *lv0, *eps0, *epsz, *z0, *rb, *mu, *lv, *z, *eps, *kld, *rb2, *h4r, *mup, *lvp;
+  float *dmu, *dlv, *dz, *dz0, *dmu0, *dlv0, *dmup, *dlvp, *dh4r, *dh4a;      // dz: the decoder's + the auxiliary decoder's
+};
+
+void trunk_carve(Bump& ws, size_t b, float* cols0, TrunkBuf& T) {
+  for (int i = 0; i < 3; ++i) {
+    T.cols[i] = i == 0 ? cols0 : ws.take(b * EH[i + 1] * EH[i + 1] * ECH[i] * 25);
+    T.hcv[i] = ws.take(b * EH[i + 1] * EH[i + 1] * ECH[i + 1]);
+  }
+  T.inp = ws.take(b * 512);
+}
+
+// which tail the decode-only path runs (ardae_conv_tail's variant 0; the mode-2 workspace is sized for the answer): conv_tail_kernel, unless
+// ARDAE_CONV_TAIL_UNFUSED=1 under ARDAE_DEBUG_KNOBS=1
+bool tail_fused_default() {
+  const char* knob = debug_knob("ARDAE_CONV_TAIL_UNFUSED");
+  return !(knob && knob[0] == '1');
+}
+// the decode-only buffers on R rows: the decoder up to u1, and for the unfused tail c2, u2, c3 and the logits (the fused kernel writes the caller's)
+void decode_carve(Bump& ws, size_t R, bool fused, ConvWs& C) {
+  C.d1 = ws.take(R * 300); C.d2 = ws.take(R * 512); C.g0 = ws.take(R * 512); C.c1 = ws.take(R * 16 * 800); C.u1 = ws.take(R * 64 * 32);
+  if (fused) return;
+  C.c2 = ws.take(R * 64 * 400); C.u2 = ws.take(R * 225 * 16); C.c3 = ws.take(R * 225 * 25); C.logit = ws.take(R * 784);
+}
+
+// mode 0: aux_encode up to h4a (encode_stats writes mu0, lv0 to the caller); 1: forward + backward; 2: the decoder's forward on B rows of z
+void carve(const AuxConvVaeLayout& P, const AuxConvVaePacked&, Bump& ws, int B, int mode, AuxConvVaeWs& W) {
+  const size_t b = (size_t)B;
+  ConvWs& C = W.C;
+  if (mode == 2) return decode_carve(ws, b, tail_fused_default(), C);
+  C.x2 = ws.take(b * 784);
+  float* cols0 = ws.take(b * 196 * 25);
+  trunk_carve(ws, b, cols0, W.T[TR_A]);
+  W.h4a = ws.take(b * 800);
+  if (mode == 0) return;
+  trunk_carve(ws, b, cols0, W.T[TR_E]); trunk_carve(ws, b, cols0, W.T[TR_R]);
+  W.mu0 = ws.take(b * P.nd); W.lv0 = ws.take(b * P.nd); W.eps0 = ws.take(b * P.nd); W.epsz = ws.take(b * P.zd); W.z0 = ws.take(b * P.nd);
+  W.rb = ws.take(b * 800); C.t1 = ws.take(b * 800);
+  W.mu = ws.take(b * P.zd); W.lv = ws.take(b * P.zd); W.z = C.z = ws.take(b * P.zd); W.eps = ws.take(b * P.zd); W.kld = ws.take(b);
+  W.rb2 = ws.take(b * 800); W.h4r = ws.take(b * 800); W.mup = ws.take(b * P.nd); W.lvp = ws.take(b * P.nd);
+  conv_decoder_carve(ws, b, P.zd, false, C);
+  W.dmu = ws.take(b * P.zd); W.dlv = ws.take(b * P.zd); W.dz = ws.take(b * P.zd);
+  W.dz0 = ws.take(b * P.nd); W.dmu0 = ws.take(b * P.nd); W.dlv0 = ws.take(b * P.nd); W.dmup = ws.take(b * P.nd); W.dlvp = ws.take(b * P.nd);
+  W.dh4r = ws.take(b * 800); C.dt1 = ws.take(b * 800); W.dh4a = ws.take(b * 800);
+  C.dinp_t = ws.take(b * 512); C.dcols3 = ws.take(b * 16 * 800); C.dcols2 = ws.take(b * 49 * 400);
+  for (TrunkBuf& T : W.T) { T.dinp = ws.take(b * 512); T.dh3 = ws.take(b * 512); T.dh2 = ws.take(b * 49 * 32); T.dh1 = ws.take(b * 196 * 16); }
+}
+using AuxConvVaeEntry = Entry<AuxConvVaeLayout, AuxConvVaePacked, AuxConvVaeWs>;
+
+// wgrad_splits hint of the backward (a tuning value, as CONV_WGRAD_HINT), and the size of its first batch: the 28 problems go out as 14 + 14
+constexpr int ACV_WGRAD_HINT = 14;
+
+// every weight-gradient problem of the backward: the decoder's eight, the z head, encode.fc's two halves and trunk, the z0 head, aux_encode.fc and
+// trunk, the auxiliary decoder's head, its fc's two halves and trunk
+void auxconvvae_wgrads(const AuxConvVaeLayout& P, const AuxConvVaeWs& W, int B, WgradList& wl, Bump& ws) {
+  const ConvWs& C = W.C;
+  auto trunk = [&](int k) { conv_trunk_wgrads(P.conv[k], W.T[k].cols, W.T[k].dh3, W.T[k].dh2, W.T[k].dh1, B, wl); };
+  // cat[h3, s]: the s half (+ bias), then the trunk half
+  auto cat = [&](const Lin& l, const float* dpre, const float* s, const float* inp) {
+    wl.push(B, 800, l.in - 512, dpre, s, l.in - 512, wl.g(l.w + 512), l.in, wl.g(l.b));
+    wl.push(B, 800, 512, dpre, inp, 512, wl.g(l.w), l.in, nullptr);
+  };
+  conv_decoder_wgrads(P.dec, C, B, wl);
+  wl.push(B, P.zd, 800, W.dmu, C.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
+  wl.push(B, P.zd, 800, W.dlv, C.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
+  cat(P.efc, C.dt1, W.z0, W.T[TR_E].inp);
+  trunk(TR_E);
+  wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
+  wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
+  wl.push(B, 800, 512, W.dh4a, W.T[TR_A].inp, 512, wl.g(P.afc.w), 512, wl.g(P.afc.b));
+  trunk(TR_A);
+  wl.push(B, P.nd, 800, W.dmup, W.h4r, 800, wl.g(P.meanp.w), 800, wl.g(P.meanp.b));
+  wl.push(B, P.nd, 800, W.dlvp, W.h4r, 800, wl.g(P.logvarp.w), 800, wl.g(P.logvarp.b));
+  cat(P.rfc, W.dh4r, W.z, W.T[TR_R].inp);
+  trunk(TR_R);
+  wl.assign(ws, ACV_WGRAD_HINT);
+}
+
+// h4 [B rpg, 800] = act(F [h3 | s] + f): the trunk half once per image as a row bias rb [B, 800], shared by the image's rpg rows
+int cat_fwd(const Lin& l, const CatLin& k, const float* params, const float* packed, int act, int B, int rpg, const float* inp, const float* s, float* rb,
+            float* h4, hipStream_t st) {
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, inp, 512, 512, packed + k.i_f, params + l.b, rb, st));
+  LinArgs A{}; A.Y = h4; A.ldY = 800; A.rowbias = rb; A.rowbias_ld = 800; A.rows_per_group = rpg;
+  return lin1(EPI_ACT, act, B * rpg, 800, s, l.in - 512, l.in - 512, packed + k.s_f, A, st);
+}
+// from dpre [B, 800] = d(pre-activation): ds [B, sd] = dpre Ws (+ q: what else arrives at s) and dinp [B, 512] = dpre Wi (the trunk applies conv3's act')
+int cat_bwd(const Lin& l, const CatLin& k, const float* packed, int B, const float* dpre, float* ds, const float* q, float* dinp, hipStream_t st) {
+  const int sd = l.in - 512;
+  if (q) ARDAE_TRY(dense_bwd(ACT_NONE, B, sd, dpre, 800, packed + k.s_b, q, ds, st, q));      // act' == 1: S is only a placeholder
+  else ARDAE_TRY(dense_fwd(ACT_NONE, B, sd, dpre, 800, 800, packed + k.s_b, nullptr, ds, st));
+  return dense_fwd(ACT_NONE, B, 512, dpre, 800, 800, packed + k.i_b, nullptr, dinp, st);
+}
+
+// The evaluation pass (mode 4): B images x k samples, R = B k rows.  One trunk's buffers serve encode's and aux_decode's trunk in turn, and the
+// auxiliary decoder reuses encode.fc's row buffer and row bias.
+struct AuxConvEvalWs {
+  float* x2;
+  TrunkBuf T;
+  float *rb, *z0, *t, *mu, *lv, *mup, *lvp;
+  double* acc;                               // the row's log-density so far [R]
+};
+
+struct AuxConvVaeTraits {
+  using Layout = AuxConvVaeLayout; using Packed = AuxConvVaePacked; using Entry = AuxConvVaeEntry;
+  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, mode); }
+  // encode.reparam on h4: kind 11's head and policy (the tail form, the default for z <= 64)
+  static GaussHead head_of(const AuxConvVaeLayout& P, const AuxConvVaePacked& K) {
+    return GaussHead{800, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f, true, P.zd >= 1 && P.zd <= 64};
+  }
+  static const float* hid(const AuxConvVaeWs& W) { return W.C.t1; }
+  static GaussBufs bufs(const AuxConvVaeWs& W) {
+    const ConvWs& C = W.C;
+    return {W.mu, W.lv, W.z, W.eps, W.kld, C.rec_row, C.pri_row, C.logit, nullptr, C.dlogit, nullptr, C.dzq, C.dz, W.dmu, W.dlv};
+  }
+  // x2 and aux_encode up to (mu0, lv0); its trunk fills the im2col rows of x2 the other two read
+  static int stats_fwd(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, const float* x, int B, float* x2,
+                       const TrunkBuf& T, float* h4a, float* mu0, float* lv0, hipStream_t st) {
+    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, x2, st));
+    ARDAE_TRY(trunk_fwd(P.conv[TR_A], K.conv_f[TR_A], params, packed, x2, T.cols, T.hcv, T.inp, B, P.act, st));
+    ARDAE_TRY(dense_fwd(P.act, B, 800, T.inp, 512, 512, packed + K.afc_f, params + P.afc.b, h4a, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, h4a, 800, 800, packed + K.mean0_f, params + P.mean0.b, mu0, st));
+    return dense_fwd(ACT_NONE, B, P.nd, h4a, 800, 800, packed + K.logvar0_f, params + P.logvar0.b, lv0, st);
+  }
+  // (the two draws are in W.eps0 / W.epsz: aux_vae_forward)  aux_encode, z0, encode's trunk and fc
+  static int encoder_fwd(Entry& en, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    const TrunkBuf& T = W.T[TR_E];
+    ARDAE_TRY(stats_fwd(P, K, params, packed, x, B, W.C.x2, W.T[TR_A], W.h4a, W.mu0, W.lv0, st));
+    ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
+    ARDAE_TRY(trunk_fwd(P.conv[TR_E], K.conv_f[TR_E], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st, true));
+    return cat_fwd(P.efc, K.efc, params, packed, P.act, B, 1, T.inp, W.z0, W.rb, W.C.t1, st);
+  }
+  // the auxiliary decoder on [h3r | z] and the pair KL, added into the head's KL rows; then the decoder
+  static int decoder_fwd(Entry& en, const float* params, const float* packed, int B, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    const TrunkBuf& T = W.T[TR_R];
+    ARDAE_TRY(trunk_fwd(P.conv[TR_R], K.conv_f[TR_R], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st, true));
+    ARDAE_TRY(cat_fwd(P.rfc, K.rfc, params, packed, P.act, B, 1, T.inp, W.z, W.rb2, W.h4r, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4r, 800, 800, packed + K.meanp_f, params + P.meanp.b, W.mup, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4r, 800, 800, packed + K.logvarp_f, params + P.logvarp.b, W.lvp, st));
+    ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
+    return conv_decode_fwd(P.dec, K.dec, params, packed, W.z, B, W.C, st);
+  }
+  // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h)
+  using EvalWs = AuxConvEvalWs;
+  static void carve_eval(const AuxConvVaeLayout& P, const AuxConvVaePacked&, Bump& ws, int B, int k, AuxConvEvalWs& W) {
+    const size_t b = (size_t)B, R = b * (size_t)k;
+    W.x2 = ws.take(b * 784);
+    trunk_carve(ws, b, ws.take(b * 196 * 25), W.T);
+    W.rb = ws.take(b * 800);
+    W.z0 = ws.take(R * P.nd); W.t = ws.take(R * 800);
+    W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
+    W.acc = reinterpret_cast<double*>(ws.take(2 * R));
+  }
+  static int eval_prepare(const AuxConvVaeLayout&, const float* x, int B, AuxConvEvalWs& W, const float*& xs, hipStream_t st) {
+    xs = W.x2;
+    return launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st);
+  }
+  static int eval_hidden(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, int stage, const float* xs,
+                         const float* s, int B, int k, AuxConvEvalWs& W, const float*& hid, hipStream_t st) {
+    const int tr = stage == 2 ? TR_E : TR_R;
+    hid = W.t;
+    ARDAE_TRY(trunk_fwd(P.conv[tr], K.conv_f[tr], params, packed, xs, W.T.cols, W.T.hcv, W.T.inp, B, P.act, st, stage == 3));
+    return cat_fwd(stage == 2 ? P.efc : P.rfc, stage == 2 ? K.efc : K.rfc, params, packed, P.act, B, k, W.T.inp, s, W.rb, W.t, st);
+  }
+};
+
+size_t auxconvvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+  const AuxConvVaeLayout P(d);
+  const AuxConvVaePacked K(P);
+  Bump ws;
+  if (mode == 4) {
+    if ((int64_t)B * nz >= (int64_t)1 << 30) return 0;
+    AuxConvEvalWs W;
+    AuxConvVaeTraits::carve_eval(P, K, ws, B, nz, W);
+    return ws.off;
+  }
+  if (mode != 2 && (nz != 1 || (mode != 0 && mode != 1))) return 0;      // one draw per image; there is no sampler pair
+  AuxConvVaeWs W;
+  carve(P, K, ws, mode == 2 ? B * nz : B, mode, W);
+  if (mode == 1) {
+    WgradList wl(nullptr);
+    auxconvvae_wgrads(P, W, B, wl, ws);
+  }
+  return ws.off;
+}
+
+int auxconvvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
+                        float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
+  AuxConvVaeEntry entry(d, workspace, wsf, B, 1);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+  ConvWs& C = W.C;
+  const float c = loss_scale / (float)B;
+  const int act = P.act;
+  const int64_t n0 = (int64_t)B * P.nd;
+  // reconstruction gradients at the logits (beta 0, no seed: dzq gets the zeros of the switched-off energy), the decoder down to C.dz
+  ARDAE_TRY(launch_vae_loss(0, C.logit, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, C.rec_row, C.pri_row, C.dlogit, nullptr, C.dzq, st));
+  ARDAE_TRY(conv_decoder_bwd(P.dec, K.dec, packed, C, B, st));
+  // the pair KL's seed at the auxiliary decoder's head and at the first head; the auxiliary decoder back into its z columns (dz = C.dz + dh4r Wz) and h3r
+  ARDAE_TRY(launch_pair_kld_seed(W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta, W.dmup, W.dlvp, W.dmu0, W.dlv0, st));
+  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.h4r, W.dh4r, st));
+  ARDAE_TRY(cat_bwd(P.rfc, K.rfc, packed, B, W.dh4r, W.dz, C.dz, W.T[TR_R].dinp, st));
+  // the z head, encode.fc back into its z0 columns and h3e
+  ARDAE_TRY(gauss_head_seed(W.dz, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
+  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, C.t1, C.dt1, st));
+  ARDAE_TRY(cat_bwd(P.efc, K.efc, packed, B, C.dt1, W.dz0, nullptr, W.T[TR_E].dinp, st));
+  // the first head: the reparameterisation through z0 joins the pair KL's part (there is no clip in this family); aux_encode.fc
+  ARDAE_TRY(launch_z0_seed(W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0, st));
+  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.T[TR_A].dinp, st));
+  for (int k = 0; k < 3; ++k) {
+    TrunkBuf& T = W.T[k];
+    ARDAE_TRY(trunk_bwd(K.conv_b[k], packed, T.dinp, C.dinp_t, T.hcv, T.dh3, C.dcols3, T.dh2, C.dcols2, T.dh1, B, act, st));
+  }
+  WgradList wl(grads, grads_beta);
+  auxconvvae_wgrads(P, W, B, wl, ws);
+  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+  ARDAE_TRY(wl.launch(st, ACV_WGRAD_HINT));
+  return wl.launch(st);
+}
+
+// mu0, lv0 of q(z0 | x): what the evaluation needs first
+int auxconvvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
+                            float* mu_out, float* lv_out, hipStream_t st) {
+  AuxConvVaeEntry entry(d, workspace, wsf, B, 0);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
+  return AuxConvVaeTraits::stats_fwd(P, K, params, packed, x, B, W.C.x2, W.T[TR_A], W.h4a, mu_out, lv_out, st);
+}
+
+// u1 [R, 8, 8, 32] -> logits [R, 784]; fused: conv_tail_kernel, else the four unfused launches on c2 / u2 / c3 / logit (then copied out)
+int tail_fwd(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, const float* u1, int R, bool fused, ConvWs& C,
+             float* logits, hipStream_t st) {
+  if (fused)
+    return launch_conv_tail(u1, packed + K.tail_w2, params + P.dec.dcv[1].b, packed + K.tail_w3, params + P.dec.dcv[2].b, R, P.act, logits, st);
+  ARDAE_TRY(conv_decode_tail_fwd(P.dec, K.dec, params, packed, u1, R, C.c2, C.u2, C.c3, C.logit, st));
+  return launch_copy(C.logit, (int64_t)R * 784, logits, st);
+}
+
+int auxconvvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf,
+                      float* out0, hipStream_t st, float*) {
+  AuxConvVaeEntry entry(d, workspace, wsf, R, 2);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
+  ARDAE_TRY(conv_decode_head_fwd(P.dec, K.dec, params, packed, z, R, W.C, st));
+  return tail_fwd(P, K, params, packed, W.C.u1, R, tail_fused_default(), W.C, out0, st);
+}
+
+// the pack launch, then the fused tail's two weights
+int auxconvvae_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
+  const AuxConvVaeLayout P(d);
+  PackList pl(params, packed);
+  const AuxConvVaePacked K(P, pl);
+  ARDAE_TRY(pl.launch(st));
+  return launch_conv_tail_pack(params + P.dec.dcv[1].w, params + P.dec.dcv[2].w, packed + K.tail_w2, packed + K.tail_w3, st);
+}
+
+// the descriptor rules of kind 17 (input_dim 784, h_dim 800, n_layers 1, 1 <= noise_dim <= AV_NMAX, flags 0, z_dim >= 1, any activation but NONE)
+int auxconvvae_desc_check(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d->noise_dim >= 1 && d->noise_dim <= AV_NMAX, "model: noise_dim must be 1 .. %d for kind 17 (the width of z0), got %d", AV_NMAX,
+                  d->noise_dim);
+  ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kind 17, got %d", d->flags);
+  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTConvAuxVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
+  ARDAE_CHECK_ARG(d->h_dim == 800, "model: h_dim must be 800 for kind 17 (the width of the three fc layers), got %d", d->h_dim);
+  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 17, got %d", d->n_layers);
+  ARDAE_CHECK_ARG(d->z_dim >= 1, "model: bad dimensions (z_dim %d)", d->z_dim);
+  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
+  return 0;
+}
+
+// (host pass only, as in csrc/auxmodel.hip)
+#ifndef __HIP_DEVICE_COMPILE__
+const GaussFamily AUXCONVVAE_GAUSS = {gauss_vae_head_fused_ok<AuxConvVaeTraits>, aux_vae_forward<AuxConvVaeTraits>, auxconvvae_backward,
+                                      auxconvvae_encode_stats, gauss_vae_head<AuxConvVaeTraits>, aux_vae_elbo_rows<AuxConvVaeTraits>,
+                                      aux_vae_iwae_draw<AuxConvVaeTraits>};
+#endif
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__
+const Family AUXCONVVAE_FAMILY = {auxconvvae_desc_check, no_caps, family_param_floats<AuxConvVaeLayout, AuxConvVaePacked>,
+                                  family_packed_floats<AuxConvVaeLayout, AuxConvVaePacked>, auxconvvae_workspace_floats,
+                                  auxconvvae_pack, vae_no_encode, auxconvvae_decode, vae_no_forward, vae_no_backward,
+                                  &AUXCONVVAE_GAUSS};
+#endif
+
+}  // namespace ardae
+
+using namespace ardae;
+
+extern "C" {
+
+// floats of the buffers the unfused launches keep: c2, u2, c3 and the logits
+size_t ardae_conv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant) {
+  if (!d || d->kind != 17 || auxconvvae_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
+  if (variant == 1 || (variant == 0 && tail_fused_default())) return 0;
+  Bump ws;
+  ws.take((size_t)R * 64 * 400); ws.take((size_t)R * 225 * 16); ws.take((size_t)R * 225 * 25); ws.take((size_t)R * 784);
+  return ws.off;
+}
+
+int ardae_conv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* u1, int R, int variant, float* workspace,
+                    size_t workspace_floats, float* logits, void* stream) {
+  ARDAE_CHECK_ARG(d != nullptr, "conv_tail: desc is NULL");
+  ARDAE_CHECK_ARG(d->kind == 17, "conv_tail: kind must be 17 (MNISTConvAuxVAE), got %d", d->kind);
+  ARDAE_TRY(auxconvvae_desc_check(d));
+  ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "conv_tail: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
+  ARDAE_CHECK_ARG(params && packed && u1 && logits, "conv_tail: null pointer argument");
+  ARDAE_CHECK_ARG(R > 0 && R < (1 << 20), "conv_tail: bad batch (R=%d)", R);
+  if (variant == 0) variant = tail_fused_default() ? 1 : 2;
+  const AuxConvVaeLayout P(*d);
+  const AuxConvVaePacked K(P);
+  ConvWs C{};
+  if (variant == 2) {
+    const size_t need = ardae_conv_tail_workspace_floats(d, R, 2);
+    ARDAE_CHECK_ARG(workspace, "conv_tail: null pointer argument (the unfused launches need a workspace)");
+    ARDAE_CHECK_ARG(workspace_floats >= need, "conv_tail: workspace too small (%zu < %zu floats)", workspace_floats, need);
+    Bump ws(workspace, workspace_floats);
+    C.c2 = ws.take((size_t)R * 64 * 400); C.u2 = ws.take((size_t)R * 225 * 16); C.c3 = ws.take((size_t)R * 225 * 25); C.logit = ws.take((size_t)R * 784);
+  }
+  return tail_fwd(P, K, params, packed, u1, R, variant == 1, C, logits, (hipStream_t)stream);
+}
+
+}  // extern "C"

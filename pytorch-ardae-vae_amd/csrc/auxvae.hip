@@ -33,8 +33,6 @@
 namespace ardae {
 namespace {
 
-constexpr int AV_NMAX = 128;       // widest noise_dim (and, in the evaluation, z_dim) the row kernels hold in LDS
-
 // A stack of Linear -> act layers whose first layer reads cat[xs, s]: xs [B, D] once per image (a row bias, with the layer's bias), s [R, sd] per row
 // (R = B rows_per_group).  t[1 .. nl] are the layer outputs [R, h].
 struct CondStack {
@@ -284,15 +282,7 @@ __global__ void z0_seed_kernel(const float* __restrict__ dz0, const float* __res
 // the auxiliary decoder's statistics).  The row's log-density -0.5 sum_c ((v - mu)^2 / exp(lv) + lv + log 2 pi) (utils/stat.py:65-85) is formed
 // like vae_iwae_draw_kernel's - terms in double in LDS, ONE thread adds them over ascending c - and enters the row's double accumulator:
 // acc_mode 0: acc = lp;  1: acc += lp;  2: logq = (float)(acc - lp).  So logq = (log q(z0|x) + log q(z|z0,x)) - log r(z0|z,x), in that order.
-struct RowsArgs {
-  const float *mu, *lv; int rpg;
-  const float* eps_in; int ld_eps;
-  uint64_t seed, offset, first;
-  const float* sample_in;
-  int64_t R; int n;
-  float *sample_out, *eps_out; int ld_eps_out;
-  double* acc; int acc_mode; float* logq;
-};
+// (RowsArgs: csrc/auxvae.h)
 __global__ __launch_bounds__(AV_THREADS) void aux_rows_kernel(const RowsArgs a) {
   __shared__ double term[AR_ROWS][AV_NMAX + 1];
   const int t = threadIdx.x, n = a.n;
@@ -327,8 +317,22 @@ __global__ __launch_bounds__(AV_THREADS) void aux_rows_kernel(const RowsArgs a) 
   }
 }
 
+}  // namespace
+
+// the launchers the auxiliary families share (csrc/auxvae.h)
 int launch_pair_kld_rows(const float* mu1, const float* lv1, const float* mu2, const float* lv2, int B, int n, float* kld, int accumulate, hipStream_t st) {
   hipLaunchKernelGGL(pair_kld_rows_kernel, dim3((unsigned)ceil_div(B, PK_ROWS)), dim3(AV_THREADS), 0, st, mu1, lv1, mu2, lv2, B, n, kld, accumulate);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+int launch_pair_kld_seed(const float* mu0, const float* lv0, const float* mup, const float* lvp, int64_t n, float c, DevFloat beta, float* dmup, float* dlvp,
+                         float* dmu0, float* dlv0, hipStream_t st) {
+  hipLaunchKernelGGL(pair_kld_seed_kernel, dim3(nblk(n)), dim3(256), 0, st, mu0, lv0, mup, lvp, n, c, beta.v, beta.p, dmup, dlvp, dmu0, dlv0);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+int launch_z0_seed(const float* dz0, const float* z0, const float* mu0, int64_t n, float* dmu0, float* dlv0, hipStream_t st) {
+  hipLaunchKernelGGL(z0_seed_kernel, dim3(nblk(n)), dim3(256), 0, st, dz0, z0, mu0, n, dmu0, dlv0);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
@@ -338,9 +342,9 @@ int launch_aux_rows(const RowsArgs& a, hipStream_t st) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ kinds 14 / 15: the traits and the family row
-size_t roundup4(size_t n) { return (n + 3) & ~size_t(3); }
+namespace {
 
+// ------------------------------------------------------------------------------------------------ kinds 14 / 15: the traits and the family row
 struct AuxVaeTraits {
   using Layout = AuxVaeLayout; using Packed = AuxVaePacked; using Entry = AuxVaeEntry;
   static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, mode); }
@@ -380,31 +384,21 @@ struct AuxVaeTraits {
     ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
     return K.dec.fwd(params, packed, P.act, B, W.z, W.D.hid.data(), W.D.o, st);
   }
+  // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h): the stages read xs; the auxiliary decoder reuses encode.fc's row buffers and row bias
+  using EvalWs = AuxEvalWs;
+  static void carve_eval(const AuxVaeLayout& P, const AuxVaePacked& K, Bump& ws, int B, int k, AuxEvalWs& W) { ardae::carve_eval(P, K, ws, B, k, W); }
+  static int eval_prepare(const AuxVaeLayout& P, const float* x, int B, AuxEvalWs& W, const float*& xs, hipStream_t st) {
+    xs = x;
+    if (P.toy) return 0;
+    xs = W.xs;
+    return launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.xs, st);
+  }
+  static int eval_hidden(const AuxVaeLayout& P, const AuxVaePacked& K, const float* params, const float* packed, int stage, const float* xs, const float* s,
+                         int B, int k, AuxEvalWs& W, const float*& hid, hipStream_t st) {
+    hid = W.t[P.nl];
+    return (stage == 2 ? K.ef : K.ad).fwd(params, packed, P.act, B, k, xs, s, W.rb, W.t.data(), st);
+  }
 };
-
-// ardae_vae_forward: the two draws go into the workspace first - the caller's rows [eps0 | eps], or elements [0, B nd) and
-// [roundup4(B nd), roundup4(B nd) + B zd) of the draw (seed, offset [+ state.rng_offset]) - then the shared algorithm runs on an injected draw.
-int aux_forward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, DevFloat beta,
-                uint64_t seed, uint64_t offset, const void* state, float* workspace, size_t wsf, float* z_out, float* eps_out, float* losses,
-                hipStream_t st) {
-  AuxVaeEntry entry(d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_forward: internal workspace accounting error");
-  const int ld = P.nd + P.zd;
-  if (eps) {
-    ARDAE_TRY(launch_copy2d(eps, ld, W.eps0, P.nd, B, P.nd, st));
-    ARDAE_TRY(launch_copy2d(eps + P.nd, ld, W.epsz, P.zd, B, P.zd, st));
-  } else {
-    ARDAE_TRY(launch_philox_normal_at(W.eps0, (int64_t)B * P.nd, seed, offset, state, 0, st));
-    ARDAE_TRY(launch_philox_normal_at(W.epsz, (int64_t)B * P.zd, seed, offset, state, roundup4((size_t)B * P.nd), st));
-  }
-  ARDAE_TRY(gauss_vae_forward<AuxVaeTraits>(d, params, packed, x, W.epsz, B, beta, seed, offset, state, workspace, wsf, z_out, nullptr, losses, st));
-  if (eps_out) {
-    ARDAE_TRY(launch_copy2d(W.eps0, P.nd, eps_out, ld, B, P.nd, st));
-    ARDAE_TRY(launch_copy2d(W.epsz, P.zd, eps_out + P.nd, ld, B, P.zd, st));
-  }
-  return 0;
-}
 
 int aux_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
                  float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
@@ -419,9 +413,7 @@ int aux_backward(const ardae_model_desc& d, const float* params, const float* pa
                             W.D.dzq, st));
   ARDAE_TRY(K.dec.bwd(packed, act, B, W.D, st));
   // the pair KL's seed at the auxiliary decoder's head and at the first head, the auxiliary decoder back into its z columns: dz = D.dz + du_1 Wz
-  hipLaunchKernelGGL(pair_kld_seed_kernel, dim3(nblk(n0)), dim3(256), 0, st, W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta.v, beta.p, W.dmup, W.dlvp, W.dmu0,
-                     W.dlv0);
-  ARDAE_LAUNCH_CHECK();
+  ARDAE_TRY(launch_pair_kld_seed(W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta, W.dmup, W.dlvp, W.dmu0, W.dlv0, st));
   ARDAE_TRY(dense_bwd2(act, B, h, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.u[nl], W.du[nl], st));
   ARDAE_TRY(K.ad.bwd(packed, act, B, W.u.data(), W.du.data(), W.dz, W.D.dz, st));
   // the z head, encode.fc back into its z0 columns
@@ -429,8 +421,7 @@ int aux_backward(const ardae_model_desc& d, const float* params, const float* pa
   ARDAE_TRY(dense_bwd2(act, B, h, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.t[nl], W.dt[nl], st));
   ARDAE_TRY(K.ef.bwd(packed, act, B, W.t.data(), W.dt.data(), W.dz0, nullptr, st));
   // the first head: the reparameterisation through z0 joins the pair KL's part, then the clip's derivative on the raw log-variance
-  hipLaunchKernelGGL(z0_seed_kernel, dim3(nblk(n0)), dim3(256), 0, st, W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0);
-  ARDAE_LAUNCH_CHECK();
+  ARDAE_TRY(launch_z0_seed(W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0, st));
   ARDAE_TRY(launch_logvar_clip(W.lv0r, W.dlv0, W.dlv0, n0, P.clip0, st));
   ARDAE_TRY(dense_bwd2(act, B, h, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.e[nl], W.de[nl], st));
   ARDAE_TRY(K.am.bwd(packed, act, B, W.e.data(), W.de.data(), st));
@@ -464,7 +455,8 @@ unsigned auxvae_caps(const ardae_model_desc& d) { return d.kind == 15 ? CAP_GAUS
 
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
-const GaussFamily AUXVAE_GAUSS = {gauss_vae_head_fused_ok<AuxVaeTraits>, aux_forward, aux_backward, aux_encode_stats, gauss_vae_head<AuxVaeTraits>};
+const GaussFamily AUXVAE_GAUSS = {gauss_vae_head_fused_ok<AuxVaeTraits>, aux_vae_forward<AuxVaeTraits>, aux_backward, aux_encode_stats,
+                                   gauss_vae_head<AuxVaeTraits>, aux_vae_elbo_rows<AuxVaeTraits>, aux_vae_iwae_draw<AuxVaeTraits>};
 #endif
 
 }  // namespace
@@ -487,89 +479,41 @@ int ardae_vae_pair_kld_rows(const float* mu1, const float* lv1, const float* mu2
   return launch_pair_kld_rows(mu1, lv1, mu2, lv2, B, n, kld, 0, (hipStream_t)stream);
 }
 
+// the kinds the two aux entry points take: the rows of the table whose GaussFamily has the aux bodies; then the kind's descriptor rules
+static int aux_kind_check(const ardae_model_desc* d, const char* who) {
+  ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
+  const Family* f = family_of(d->kind);
+  ARDAE_CHECK_ARG(f && f->gauss && f->gauss->aux_elbo_rows, "%s: kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE) or 17 (MNISTConvAuxVAE), got %d", who, d->kind);
+  return f->desc_check(d);
+}
+
 int ardae_vae_aux_elbo_rows(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* eps, int B, uint64_t seed,
                             uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace, size_t workspace_floats_, float* recon_rows,
                             float* kld_rows, void* stream) {
-  ARDAE_CHECK_ARG(d != nullptr, "vae_aux_elbo_rows: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind == 14 || d->kind == 15, "vae_aux_elbo_rows: kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE), got %d", d->kind);
-  ARDAE_TRY(auxvae_desc_check(d));
+  ARDAE_TRY(aux_kind_check(d, "vae_aux_elbo_rows"));
   ARDAE_CHECK_ARG(params && packed && x && workspace && recon_rows && kld_rows, "vae_aux_elbo_rows: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && B < (1 << 24), "vae_aux_elbo_rows: bad batch (B=%d)", B);
   ARDAE_CHECK_ARG(eps || (((first_image * (uint64_t)d->noise_dim) & 3) == 0 && ((first_image * (uint64_t)d->z_dim) & 3) == 0),
                   "vae_aux_elbo_rows: first_image noise_dim and first_image z_dim must be multiples of 4 (one Philox counter = 4 normals)");
-  const size_t need = auxvae_workspace_floats(*d, B, 1, 1);
+  const size_t need = family(d).workspace_floats(*d, B, 1, 1);
   ARDAE_CHECK_ARG(workspace_floats_ >= need, "vae_aux_elbo_rows: workspace too small (%zu < %zu floats)", workspace_floats_, need);
-  hipStream_t st = (hipStream_t)stream;
-  AuxVaeEntry entry(*d, workspace, workspace_floats_, B, 1);
-  auto& [P, K, ws, W] = entry;
-  const int ld = P.nd + P.zd;
-  if (eps) {
-    ARDAE_TRY(launch_copy2d(eps, ld, W.eps0, P.nd, B, P.nd, st));
-    ARDAE_TRY(launch_copy2d(eps + P.nd, ld, W.epsz, P.zd, B, P.zd, st));
-  } else {
-    ARDAE_TRY(launch_philox_normal_at(W.eps0, (int64_t)B * P.nd, seed, offset0, nullptr, first_image * (uint64_t)P.nd, st));
-    ARDAE_TRY(launch_philox_normal_at(W.epsz, (int64_t)B * P.zd, seed, offset1, nullptr, first_image * (uint64_t)P.zd, st));
-  }
-  ARDAE_TRY(AuxVaeTraits::encoder_fwd(entry, params, packed, x, B, st));
-  ARDAE_TRY(gauss_head_fwd(AuxVaeTraits::head_of(P, K), params, packed, W.t[P.nl], W.epsz, B, seed, 0, nullptr, 0, W.mu, W.lv, W.z, W.eps, kld_rows, st));
-  W.kld = kld_rows;      // the pair KL is added into the caller's rows
-  ARDAE_TRY(AuxVaeTraits::decoder_fwd(entry, params, packed, B, st));
-  return launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, B, 1, P.D, P.zd, 0.f, 0, 0.f, nullptr, recon_rows, W.pri_row, nullptr, nullptr, nullptr, st);
+  return family(d).gauss->aux_elbo_rows(*d, params, packed, x, eps, B, seed, offset0, offset1, first_image, workspace, workspace_floats_, recon_rows,
+                                        kld_rows, (hipStream_t)stream);
 }
 
 int ardae_vae_aux_iwae_draw(const ardae_model_desc* d, const float* params, const float* packed, const float* x, const float* mu0, const float* lv0,
                             const float* eps, int B, int k, uint64_t seed, uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace,
                             size_t workspace_floats_, float* z_out, float* logq, float* eps_out, void* stream) {
-  ARDAE_CHECK_ARG(d != nullptr, "vae_aux_iwae_draw: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind == 14 || d->kind == 15, "vae_aux_iwae_draw: kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE), got %d", d->kind);
-  ARDAE_TRY(auxvae_desc_check(d));
+  ARDAE_TRY(aux_kind_check(d, "vae_aux_iwae_draw"));
   ARDAE_CHECK_ARG(params && packed && x && mu0 && lv0 && workspace && z_out && logq, "vae_aux_iwae_draw: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && k > 0 && (int64_t)B * k < (int64_t)1 << 30, "vae_aux_iwae_draw: bad batch (B=%d, k=%d)", B, k);
   ARDAE_CHECK_ARG(d->z_dim <= AV_NMAX, "vae_aux_iwae_draw: need z_dim <= %d (got %d)", AV_NMAX, d->z_dim);
-  const AuxVaeLayout P(*d);
-  ARDAE_CHECK_ARG(eps || (((first_image * (uint64_t)k * P.nd) & 3) == 0 && ((first_image * (uint64_t)k * P.zd) & 3) == 0),
+  ARDAE_CHECK_ARG(eps || (((first_image * (uint64_t)k * d->noise_dim) & 3) == 0 && ((first_image * (uint64_t)k * d->z_dim) & 3) == 0),
                   "vae_aux_iwae_draw: first_image k noise_dim and first_image k z_dim must be multiples of 4 (one Philox counter = 4 normals)");
-  const size_t need = auxvae_workspace_floats(*d, B, k, 4);
+  const size_t need = family(d).workspace_floats(*d, B, k, 4);
   ARDAE_CHECK_ARG(workspace_floats_ >= need, "vae_aux_iwae_draw: workspace too small (%zu < %zu floats)", workspace_floats_, need);
-  const AuxVaePacked K(P);
-  Bump ws(workspace, workspace_floats_);
-  AuxEvalWs W;
-  carve_eval(P, K, ws, B, k, W);
-  ARDAE_CHECK_ARG(ws.ok, "vae_aux_iwae_draw: internal workspace accounting error");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t R = (int64_t)B * k;
-  const int ld = P.nd + P.zd, nl = P.nl;
-  const float* xs = x;
-  if (!P.toy) {
-    ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.xs, st));
-    xs = W.xs;
-  }
-  // stage 1: k z0's per image from q(z0 | x), log q(z0 | x)
-  RowsArgs a{};
-  a.mu = mu0; a.lv = lv0; a.rpg = k; a.eps_in = eps; a.ld_eps = ld; a.seed = seed; a.offset = offset0; a.first = first_image * (uint64_t)k * P.nd;
-  a.R = R; a.n = P.nd; a.sample_out = W.z0; a.eps_out = eps_out; a.ld_eps_out = ld; a.acc = W.acc; a.acc_mode = 0;
-  ARDAE_TRY(launch_aux_rows(a, st));
-  // (the timing tool's per-stage split: ARDAE_AUX_DRAW_STAGES=1 | 2 under ARDAE_DEBUG_KNOBS=1 stops after that stage; logq is then not written)
-  int stages = 3;
-  if (const char* knob = debug_knob("ARDAE_AUX_DRAW_STAGES")) stages = knob[0] == '1' ? 1 : knob[0] == '2' ? 2 : 3;
-  if (stages < 2) return 0;
-  // stage 2: encode.fc on [xs | z0], one z per row from q(z | z0, x), + log q(z | z0, x)
-  ARDAE_TRY(K.ef.fwd(params, packed, P.act, B, k, xs, W.z0, W.rb, W.t.data(), st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, (int)R, P.zd, W.t[nl], P.h, P.h, packed + K.mean_f, params + P.mean.b, W.mu, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, (int)R, P.zd, W.t[nl], P.h, P.h, packed + K.logvar_f, params + P.logvar.b, W.lv, st));
-  RowsArgs b{};
-  b.mu = W.mu; b.lv = W.lv; b.rpg = 1; b.eps_in = eps ? eps + P.nd : nullptr; b.ld_eps = ld; b.seed = seed; b.offset = offset1;
-  b.first = first_image * (uint64_t)k * P.zd; b.R = R; b.n = P.zd; b.sample_out = z_out; b.eps_out = eps_out ? eps_out + P.nd : nullptr;
-  b.ld_eps_out = ld; b.acc = W.acc; b.acc_mode = 1;
-  ARDAE_TRY(launch_aux_rows(b, st));
-  if (stages < 3) return 0;
-  // stage 3: aux_decode.fc on [xs | z] (in encode.fc's buffers), - log r(z0 | z, x) on the stored z0
-  ARDAE_TRY(K.ad.fwd(params, packed, P.act, B, k, xs, z_out, W.rb, W.t.data(), st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, (int)R, P.nd, W.t[nl], P.h, P.h, packed + K.meanp_f, params + P.meanp.b, W.mup, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, (int)R, P.nd, W.t[nl], P.h, P.h, packed + K.logvarp_f, params + P.logvarp.b, W.lvp, st));
-  RowsArgs r{};
-  r.mu = W.mup; r.lv = W.lvp; r.rpg = 1; r.sample_in = W.z0; r.R = R; r.n = P.nd; r.acc = W.acc; r.acc_mode = 2; r.logq = logq;
-  return launch_aux_rows(r, st);
+  return family(d).gauss->aux_iwae_draw(*d, params, packed, x, mu0, lv0, eps, B, k, seed, offset0, offset1, first_image, workspace, workspace_floats_,
+                                        z_out, logq, eps_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -71,8 +71,9 @@ void conv_decoder_carve(Bump& ws, size_t R, int zd, bool decode_only, ConvWs& W)
 
 // conv trunk 1 -> 16 -> 32 -> 32 (k5 s2 p2, 28 -> 14 -> 7 -> 4) on the rescaled images x2 [B, 784]: fills cols / hcv and the
 // NCHW-flattened output inp [B, 512]
+// (cols0_ready: cols[0], the im2col rows of x2, were filled by an earlier trunk on the same x2 - the three trunks of kind 17 share them)
 int trunk_fwd(const Lin* conv, const size_t* conv_f, const float* params, const float* packed, const float* x2, float* const* cols,
-              float* const* hcv, float* inp, int B, int act, hipStream_t st);
+              float* const* hcv, float* inp, int B, int act, hipStream_t st, bool cols0_ready = false);
 // backward of the trunk from d(inp) [B, 512] (NCHW-flat): dh3 / dh2 / dh1 = d(pre-activation) of conv3 / conv2 / conv1 (NHWC rows)
 int trunk_bwd(const size_t* conv_b, const float* packed, const float* dinp, float* dinp_t, float* const* hcv, float* dh3, float* dcols3,
               float* dh2, float* dcols2, float* dh1, int B, int act, hipStream_t st);
@@ -81,6 +82,18 @@ void conv_trunk_wgrads(const Lin* conv, float* const* cols, const float* dh3, co
 // models/vae/conv.py::Decoder on R rows of z (P, K: the dfc / dcv members): fills W.d1 .. W.logit [R, 784]
 int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
                     hipStream_t st);
+// its two halves: up to W.u1 [R, 8, 8, 32] (decode.fc, deconv1 with its activation and zero pad: fills W.d1, d2, g0, c1, u1), and the last two stages
+// from u1 as the four unfused launches (deconv2, logit_fn)
+int conv_decode_head_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
+                         hipStream_t st);
+int conv_decode_tail_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* u1, int R, float* c2, float* u2,
+                         float* c3, float* logit, hipStream_t st);
+// the same two stages as ONE launch (conv_tail_kernel, csrc/convmodel.hip): u1 [R, 8, 8, 32] -> logit [R, 784]; b2 / b3: the biases of decode.deconv2 and
+// decode.reparam.logit_fn in the parameter buffer, wt2 [CT_W2] / wt3 [CT_W3]: their weights (ConvTranspose2d layout [in, out, 5, 5]) as
+// launch_conv_tail_pack re-lays them, on 16-byte boundaries of the packed buffer
+constexpr size_t CT_W2 = 32 * 25 * 16, CT_W3 = 16 * 32;
+int launch_conv_tail(const float* u1, const float* wt2, const float* b2, const float* wt3, const float* b3, int R, int act, float* logit, hipStream_t st);
+int launch_conv_tail_pack(const float* w2, const float* w3, float* wt2, float* wt3, hipStream_t st);
 // decoder backward from W.dlogit (and W.dzq = the part of dL/dz that does not pass through the decoder): fills dc3 / dp2 / dc2 / dp1 / dc1 / dg0 /
 // dd2 / dd1 and W.dz
 int conv_decoder_bwd(const ConvLayout& P, const ConvPacked& K, const float* packed, ConvWs& W, int R, hipStream_t st);

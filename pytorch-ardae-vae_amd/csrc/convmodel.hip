@@ -118,11 +118,11 @@ void conv_decoder_carve(Bump& ws, size_t R, int zd, bool decode_only, ConvWs& W)
 // conv trunk 1 -> 16 -> 32 -> 32 (k5 s2 p2, 28 -> 14 -> 7 -> 4) on the rescaled images x2 [B, 784]: fills cols / hcv and the
 // NCHW-flattened output inp [B, 512] (shared by ConvIPVAE, the two trunks of the hierarchical conv model and the conv baseline)
 int trunk_fwd(const Lin* conv, const size_t* conv_f, const float* params, const float* packed, const float* x2, float* const* cols,
-              float* const* hcv, float* inp, int B, int act, hipStream_t st) {
+              float* const* hcv, float* inp, int B, int act, hipStream_t st, bool cols0_ready) {
   const float* cur = x2;
   for (int i = 0; i < 3; ++i) {                                                 // conv_i = im2col + Linear([O, C*25]) + act
     const int OH = EH[i + 1], Kc = ECH[i] * 25;
-    ARDAE_TRY(im2col(cur, B, EH[i], EH[i], ECH[i], OH, OH, cols[i], st));
+    if (i > 0 || !cols0_ready) ARDAE_TRY(im2col(cur, B, EH[i], EH[i], ECH[i], OH, OH, cols[i], st));
     ARDAE_TRY(dense_fwd(act, B * OH * OH, ECH[i + 1], cols[i], Kc, Kc, packed + conv_f[i], params + conv[i].b, hcv[i], st));
     cur = hcv[i];
   }
@@ -140,22 +140,34 @@ int trunk_bwd(const size_t* conv_b, const float* packed, const float* dinp, floa
   return col2im(dcols2, B, 7, 7, 16, 14, 14, 14, 14, nullptr, act, hcv[0], dh1, st);
 }
 
-int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
-                    hipStream_t st) {
+// the decoder up to u1 [R, 8, 8, 32]: decode.fc and deconv1 with its activation and zero pad
+int conv_decode_head_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
+                         hipStream_t st) {
   const int act = P.act;
   ARDAE_TRY(dense_fwd(act, R, 300, z, P.zd, P.zd, packed + K.dfc_f[0], params + P.dfc[0].b, W.d1, st));
   ARDAE_TRY(dense_fwd(act, R, 512, W.d1, 300, 300, packed + K.dfc_f[1], params + P.dfc[1].b, W.d2, st));
   ARDAE_TRY(launch_nhwc_nchw(W.d2, R, 16, 32, W.g0, true, st));                  // h1.view(R,32,4,4) -> NHWC rows
   // deconv1 32->32: 4x4 -> 7x7, activation, zero-pad to 8x8
   ARDAE_TRY(dense_fwd(ACT_NONE, R * 16, 800, W.g0, 32, 32, packed + K.dcv_f[0], nullptr, W.c1, st));
-  ARDAE_TRY(col2im(W.c1, R, 4, 4, 32, 8, 8, 7, 7, params + P.dcv[0].b, act, nullptr, W.u1, st));
+  return col2im(W.c1, R, 4, 4, 32, 8, 8, 7, 7, params + P.dcv[0].b, act, nullptr, W.u1, st);
+}
+
+// the decoder's last two stages as the four unfused launches: u1 -> c2, u2, c3 -> logit [R, 784]
+int conv_decode_tail_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* u1, int R, float* c2, float* u2,
+                         float* c3, float* logit, hipStream_t st) {
+  const int act = P.act;
   // deconv2 32->16: 8x8 -> 15x15, activation
-  ARDAE_TRY(dense_fwd(ACT_NONE, R * 64, 400, W.u1, 32, 32, packed + K.dcv_f[1], nullptr, W.c2, st));
-  ARDAE_TRY(col2im(W.c2, R, 8, 8, 16, 15, 15, 15, 15, params + P.dcv[1].b, act, nullptr, W.u2, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, R * 64, 400, u1, 32, 32, packed + K.dcv_f[1], nullptr, c2, st));
+  ARDAE_TRY(col2im(c2, R, 8, 8, 16, 15, 15, 15, 15, params + P.dcv[1].b, act, nullptr, u2, st));
   // logit deconv 16->1: 15x15 -> 29x29, cropped to 28x28
-  ARDAE_TRY(dense_fwd(ACT_NONE, R * 225, 25, W.u2, 16, 16, packed + K.dcv_f[2], nullptr, W.c3, st));
-  ARDAE_TRY(col2im(W.c3, R, 15, 15, 1, 28, 28, 28, 28, params + P.dcv[2].b, ACT_NONE, nullptr, W.logit, st));
-  return 0;
+  ARDAE_TRY(dense_fwd(ACT_NONE, R * 225, 25, u2, 16, 16, packed + K.dcv_f[2], nullptr, c3, st));
+  return col2im(c3, R, 15, 15, 1, 28, 28, 28, 28, params + P.dcv[2].b, ACT_NONE, nullptr, logit, st);
+}
+
+int conv_decode_fwd(const ConvLayout& P, const ConvPacked& K, const float* params, const float* packed, const float* z, int R, ConvWs& W,
+                    hipStream_t st) {
+  ARDAE_TRY(conv_decode_head_fwd(P, K, params, packed, z, R, W, st));
+  return conv_decode_tail_fwd(P, K, params, packed, W.u1, R, W.c2, W.u2, W.c3, W.logit, st);
 }
 
 // decoder backward from W.dlogit (and W.dzq = prior + seed part of dL/dz): fills dc3/dp2/dc2/dp1/dc1/dg0/dd2/dd1 and W.dz
@@ -196,6 +208,123 @@ void conv_trunk_wgrads(const Lin* conv, float* const* cols, const float* dh3, co
   wl.push(B * 16, 32, 800, dh3, cols[2], 800, wl.g(conv[2].w), 800, wl.g(conv[2].b));
   wl.push(B * 49, 32, 400, dh2, cols[1], 400, wl.g(conv[1].w), 400, wl.g(conv[1].b));
   wl.push(B * 196, 16, 25, dh1, cols[0], 25, wl.g(conv[0].w), 25, wl.g(conv[0].b));
+}
+
+// ------------------------------------------------------------------------------------------------ the decoder's last two stages as one launch
+// conv_tail_kernel (kind 17's decode-only path; ardae_conv_tail variant 1): u1 [R, 8, 8, 32] NHWC - deconv1's activated output with its zero pad ->
+//   stage A  u2[oh][ow][o] = act(b2[o] + sum_{kh, kw: (oh+2-kh) even, ih = (oh+2-kh)/2 in [0, 8), same for w} sum_c u1[ih][iw][c] W2[c][o][kh][kw])   15 x 15 x 16
+//   stage B  logit[oh][ow] = b3 + the same sum over u2 and W3[c][0][kh][kw], 29 x 29 cropped to 28 x 28
+// ONE workgroup of 256 threads per image; u1 and u2 live in LDS, channel-major with a zero halo of one position (c2, u2, c3 never reach global
+// memory: 32 x 101 + 16 x 290 floats = 31.5 KiB, five workgroups per CU).  A stride-2 transposed convolution sends tap (kh, kw) to the outputs of
+// parity (kh & 1, kw & 1) only, so a thread owns the 2 x 2 output quad (2a + ph, 2b + pw) of input position (a, b): tap kh reads input row
+// a + 1 - (kh >> 1) for every thread alike, the 25 taps of a quad are the 25 weights W[c][o][.][.] - the same address in every lane, so they arrive
+// by scalar loads and cost no LDS or vector-memory traffic - and out-of-range rows are the halo's zeros.  Stage A: lane = (a, b) of the 8 x 8 grid,
+// wave w owns output channels 4w .. 4w + 3 (16 accumulators); stage B: thread = (a, b) of the 15 x 15 grid (4 accumulators).
+// The weights come from the packed buffer, re-laid at pack time on 16-byte boundaries (conv_tail_pack_kernel): wt2[c][tap][o] (a wave's four
+// channels of a tap are one 16-byte scalar load) and wt3[c][32] (25 taps, padded).
+// Summation order of every output, in FP32 FMAs from 0: c ascending, within c the taps (kh, kw) ascending (taps that fall outside are exact zeros);
+// then + bias, then the activation.  A row's bits depend on that row alone.
+constexpr int CT_THREADS = 256, CT_S1 = 101, CT_S2 = 290;      // strides of a channel's 10 x 10 / 17 x 17 halo grid (odd multiples keep lanes on distinct banks)
+// wt2[c][tap][o] = W2[c][o][tap] (12 800 floats), wt3[c][32] = W3[c][0][tap], zero beyond tap 24 (512 floats)
+__global__ void conv_tail_pack_kernel(const float* __restrict__ w2, const float* __restrict__ w3, float* __restrict__ wt2, float* __restrict__ wt3) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < 12800) {
+    const int o = e & 15, tap = (e >> 4) % 25, c = e / 400;
+    wt2[e] = w2[(c * 16 + o) * 25 + tap];
+  } else if (e < 12800 + 512) {
+    const int i = e - 12800, tap = i & 31, c = i >> 5;
+    wt3[i] = tap < 25 ? w3[c * 25 + tap] : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(CT_THREADS) void conv_tail_kernel(const float* __restrict__ u1, const float* __restrict__ wt2, const float* __restrict__ b2,
+                                                               const float* __restrict__ wt3, const float* __restrict__ b3, int act,
+                                                               float* __restrict__ logit) {
+  __shared__ float s1[32 * CT_S1];
+  __shared__ float s2[16 * CT_S2];
+  const int t = threadIdx.x;
+  const size_t r = blockIdx.x;
+  for (int i = t; i < 32 * CT_S1; i += CT_THREADS) s1[i] = 0.f;
+  for (int i = t; i < 16 * CT_S2; i += CT_THREADS) s2[i] = 0.f;
+  __syncthreads();
+  const float* src = u1 + r * 2048;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {      // coalesced NHWC reads; element e = (position, channel)
+    const int e = t + i * CT_THREADS, pos = e >> 5, c = e & 31;
+    s1[c * CT_S1 + ((pos >> 3) + 1) * 10 + (pos & 7) + 1] = src[e];
+  }
+  __syncthreads();
+  {      // ---- stage A
+    const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), o0 = wv * 4, a = lane >> 3, b = lane & 7;      // wv: the same in every lane
+    const float4* wq = reinterpret_cast<const float4*>(wt2) + wv;
+    float acc[4][2][2] = {};
+    for (int c = 0; c < 32; ++c) {
+      float v[3][3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v[i][j] = s1[c * CT_S1 + (a + i) * 10 + b + j];      // input rows a - 1 .. a + 1
+#pragma unroll
+      for (int kh = 0; kh < 5; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 5; ++kw) {
+          const float4 w = wq[(c * 25 + kh * 5 + kw) * 4];
+          const float x = v[2 - (kh >> 1)][2 - (kw >> 1)];
+          acc[0][kh & 1][kw & 1] = __builtin_fmaf(x, w.x, acc[0][kh & 1][kw & 1]);
+          acc[1][kh & 1][kw & 1] = __builtin_fmaf(x, w.y, acc[1][kh & 1][kw & 1]);
+          acc[2][kh & 1][kw & 1] = __builtin_fmaf(x, w.z, acc[2][kh & 1][kw & 1]);
+          acc[3][kh & 1][kw & 1] = __builtin_fmaf(x, w.w, acc[3][kh & 1][kw & 1]);
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      const float bias = b2[o0 + o];
+#pragma unroll
+      for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+        for (int pw = 0; pw < 2; ++pw) {
+          const int oh = 2 * a + ph, ow = 2 * b + pw;
+          if (oh < 15 && ow < 15) s2[(o0 + o) * CT_S2 + (oh + 1) * 17 + ow + 1] = act_fwd_rt(act, acc[o][ph][pw] + bias);
+        }
+    }
+  }
+  __syncthreads();
+  if (t < 225) {      // ---- stage B
+    const int a = t / 15, b = t - a * 15;
+    float acc[2][2] = {};
+    for (int c = 0; c < 16; ++c) {
+      float v[3][3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v[i][j] = s2[c * CT_S2 + (a + i) * 17 + b + j];
+      const float* w = wt3 + c * 32;
+#pragma unroll
+      for (int kh = 0; kh < 5; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 5; ++kw) acc[kh & 1][kw & 1] = __builtin_fmaf(v[2 - (kh >> 1)][2 - (kw >> 1)], w[kh * 5 + kw], acc[kh & 1][kw & 1]);
+    }
+    const float bias = b3[0];
+    float* dst = logit + r * 784;
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+      for (int pw = 0; pw < 2; ++pw) {
+        const int oh = 2 * a + ph, ow = 2 * b + pw;
+        if (oh < 28 && ow < 28) dst[oh * 28 + ow] = acc[ph][pw] + bias;
+      }
+  }
+}
+
+int launch_conv_tail(const float* u1, const float* wt2, const float* b2, const float* wt3, const float* b3, int R, int act, float* logit, hipStream_t st) {
+  hipLaunchKernelGGL(conv_tail_kernel, dim3((unsigned)R), dim3(CT_THREADS), 0, st, u1, wt2, b2, wt3, b3, act, logit);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+int launch_conv_tail_pack(const float* w2, const float* w3, float* wt2, float* wt3, hipStream_t st) {
+  hipLaunchKernelGGL(conv_tail_pack_kernel, dim3(nblk(CT_W2 + CT_W3)), dim3(256), 0, st, w2, w3, wt2, wt3);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ ConvIPVAE (kind == 2)

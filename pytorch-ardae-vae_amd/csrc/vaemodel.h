@@ -43,6 +43,13 @@ struct GaussFamily {
                       float* mu_out, float* lv_out, hipStream_t st);
   int (*head)(const ardae_model_desc& d, const float* params, const float* packed, const float* hid, const float* eps, int B, uint64_t seed,
               uint64_t offset, const void* state, int variant, float* mu, float* lv, float* z, float* eps_out, float* kld, hipStream_t st);
+  // the auxiliary-variable families only (kinds 14 / 15 / 17; null elsewhere): the bodies of ardae_vae_aux_elbo_rows / ardae_vae_aux_iwae_draw
+  int (*aux_elbo_rows)(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* eps, int B, uint64_t seed,
+                       uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace, size_t wsf, float* recon_rows, float* kld_rows,
+                       hipStream_t st);
+  int (*aux_iwae_draw)(const ardae_model_desc& d, const float* params, const float* packed, const float* x, const float* mu0, const float* lv0,
+                       const float* eps, int B, int k, uint64_t seed, uint64_t offset0, uint64_t offset1, uint64_t first_image, float* workspace,
+                       size_t wsf, float* z_out, float* logq, float* eps_out, hipStream_t st);
 };
 
 // The buffers of a family's workspace that the shared algorithm names (out1 / dout1: the second head of a Gaussian decoder - kind 9 - else null; dzq: the
@@ -119,6 +126,6 @@ template <class F> int gauss_vae_head(const ardae_model_desc& d, const float* pa
 
 // the family's row: the bodies above over its traits
 template <class F> constexpr GaussFamily gauss_family() {
-  return {gauss_vae_head_fused_ok<F>, gauss_vae_forward<F>, gauss_vae_backward<F>, gauss_vae_encode_stats<F>, gauss_vae_head<F>};
+  return {gauss_vae_head_fused_ok<F>, gauss_vae_forward<F>, gauss_vae_backward<F>, gauss_vae_encode_stats<F>, gauss_vae_head<F>, nullptr, nullptr};
 }
 }  // namespace ardae

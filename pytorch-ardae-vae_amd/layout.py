@@ -168,6 +168,22 @@ def conv_vae_spec(z_dim):
                 ("decode.reparam.logit_fn.weight", (16, 1, 5, 5)), ("decode.reparam.logit_fn.bias", (1,))]
 
 
+def aux_conv_vae_spec(noise_dim, z_dim):
+    """The hierarchical conv Gaussian baseline of vae.py (models/vae/auxconv.py, `--model auxconv`; 28 x 28 x 1, fixed architecture): AuxEncoder (a conv
+    trunk, `fc` 512 -> 800, a NormalDistributionLinear head on z0 of width noise_dim), Encoder (its own trunk, `fc` on cat[h3, z0], a head on z), the
+    decoder of conv_vae_spec and AuxDecoder (its own trunk, `fc` on cat[h3, z], a head on z0), in the order the reference assigns them.
+    ardae_model_desc.kind 17."""
+    def net(prefix, extra, out):
+        return [(prefix + "conv1.weight", (16, 1, 5, 5)), (prefix + "conv1.bias", (16,)),
+                (prefix + "conv2.weight", (32, 16, 5, 5)), (prefix + "conv2.bias", (32,)),
+                (prefix + "conv3.weight", (32, 32, 5, 5)), (prefix + "conv3.bias", (32,)),
+                (prefix + "fc.weight", (800, 512 + extra)), (prefix + "fc.bias", (800,)),
+                (prefix + "reparam.mean_fn.weight", (out, 800)), (prefix + "reparam.mean_fn.bias", (out,)),
+                (prefix + "reparam.logvar_fn.weight", (out, 800)), (prefix + "reparam.logvar_fn.bias", (out,))]
+    decoder = [(n, s) for n, s in conv_vae_spec(z_dim) if n.startswith("decode.")]
+    return net("aux_encode.", 0, noise_dim) + net("encode.", noise_dim, z_dim) + decoder + net("aux_decode.", z_dim, noise_dim)
+
+
 def resconv_vae_spec(z_dim, c_dim):
     """The residual-conv Gaussian-posterior baseline of vae.py (models/vae/resconv.py:26-148, `--model resconv`; 28 x 28 x 1): the weight-normalised
     trunk of the 'auxresconv' implicit model as `encode.enc.*` (width c_dim), a NormalDistributionLinear head and that model's decoder.

@@ -152,7 +152,8 @@ def _f32c(t):
 
 KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7,      # ardae_model_desc.kind
             "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11, "vae_resconv": 12,                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
-            "vae_auxmnist": 14, "vae_auxtoy": 15}                                                                               # (its auxiliary-variable baselines; 13 is not a kind)
+            "vae_auxmnist": 14, "vae_auxtoy": 15,                                                                               # (its auxiliary-variable baselines; 13 is not a kind)
+            "vae_auxconv": 17}                                                                                                  # (16 is not a kind)
 AUX_KINDS = ("auxmnist", "auxconv", "auxresconv", "auxtoy")                                                 # hierarchical samplers
 GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy", "vae_auxtoy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
 
@@ -1119,7 +1120,7 @@ class ToyVAE(GaussianVAE):
 
 
 class _AuxGaussianVAE(GaussianVAE):
-    """What MNISTAuxVAE and ToyAuxVAE share (ardae_model_desc kinds 14 / 15): q(z0 | x) q(z | z0, x) with an auxiliary decoder r(z0 | z, x).  forward()'s
+    """What MNISTAuxVAE, ToyAuxVAE and MNISTConvAuxVAE share (ardae_model_desc kinds 14 / 15 / 17): q(z0 | x) q(z | z0, x) with an auxiliary decoder r(z0 | z, x).  forward()'s
     `eps` is [B, noise_dim + z_dim], rows [eps0 | eps]; encode_stats() returns the statistics of q(z0 | x); logprob's `eps` is
     [B, sample_size, noise_dim + z_dim].  `model.encode` / `model.aux_encode` / `model.aux_decode` only name parameters: the three networks run inside
     forward() and logprob()."""
@@ -1200,3 +1201,31 @@ class ToyAuxVAE(_AuxGaussianVAE):
         self._build_aux(energy_func, input_dim, noise_dim, h_dim, z_dim, nonlinearity, num_hidden_layers, enc_type, clip_logvar)
 
     reset_parameters = ToyVAE.reset_parameters          # Decoder.reset_parameters (vae/toy.py:75-81)
+
+
+class MNISTConvAuxVAE(_AuxGaussianVAE):
+    """models/vae/auxconv.py::VAE (`vae.py --model auxconv`, the "# hierarchical conv" baseline of run_vae_dbmnist.sh): the Gaussian counterpart of
+    MNISTConvAuxIPVAE.  Three conv trunks on 2x - 1 (aux_encode, encode, aux_decode), each followed by an `fc` to 800 and a Gaussian head; z0 has width
+    z0_dim (`noise_dim`), there is no log-variance clip; MNISTConvVAE's decoder.  28x28x1 only.  forward() takes x as [B, 784] or [B, 1, 28, 28] and
+    returns the decoder sample / mean as [B, 784]."""
+    _kind = "vae_auxconv"
+    # As for MNISTConvVAE the library picks the kernel of every conv-as-linear (and of the stage linears) by the row count, so the evaluator runs fixed
+    # groups: the statistics and the ELBO pass on 64 images per call, the three stages and the importance samples' decoder on 32.  The decode-only
+    # workspace of this kind (the last two stages fused: no c2 / u2 / c3) takes ~1.62e4 floats per decoded row against ~5.18e4 for MNISTConvVAE's: at
+    # k = 256 the 8192 rows of a call need 0.13 G floats, inside the default budget of 2^28 (64 images would need 0.27 G).  Chunks are cut at multiples
+    # of 64 images.
+    _eval_groups = (64, 32)
+
+    def __init__(self, energy_func=normal_energy_func, input_height=28, input_channels=1, z0_dim=100, z_dim=32, nonlinearity="softplus", do_xavier=True,
+                 do_m5bias=False):
+        if input_height != 28 or input_channels != 1:
+            raise NotImplementedError("MNISTConvAuxVAE: the reference decoder (models/vae/conv.py:79-136) is hard-wired to 28x28x1")
+        super().__init__()
+        self.input_height, self.input_channels, self.do_xavier, self.do_m5bias = input_height, input_channels, do_xavier, do_m5bias
+        self.z0_dim = int(z0_dim)
+        self._build_aux(energy_func, input_height * input_height * input_channels, z0_dim, 800, z_dim, nonlinearity, 1, "simple", None)
+
+    def _param_spec(self):
+        return layout.aux_conv_vae_spec(self.noise_dim, self.z_dim)
+
+    reset_parameters = MNISTConvVAE.reset_parameters    # weight_init on Conv2d / Linear where do_xavier (ConvTranspose2d keeps torch's init), the -5 logit bias where do_m5bias (vae/auxconv.py:18-23,231-235)

@@ -1,7 +1,7 @@
 """The Gaussian-posterior baselines of the reference's second trainer, vae.py, on the device: one iteration of its loop (vae.py:396-417)
 as one captured unit, and its evaluate_iws (vae.py:342-377) in large chunks.
 
-    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE, net.MNISTAuxVAE, net.ToyAuxVAE
+    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE, net.MNISTAuxVAE, net.ToyAuxVAE, net.MNISTConvAuxVAE
     eng = net.VaeEngine(model, net.VaeConfig(lr=1e-3, beta_init=1e-4, beta_annealing=50000), batch_size=128)
     for x in loader: eng.step(x)
     elbo, logprob = eng.evaluate_iws(x_valid, sample_size=512)
@@ -80,11 +80,11 @@ class GaussianIwaeEvaluator:
     def __init__(self, model, sample_size, max_workspace_floats=1 << 28):
         if not isinstance(model, GaussianVAE):
             raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE / net.MNISTAuxVAE / "
-                            "net.ToyAuxVAE (the implicit models: net.IwaeEvaluator)")
+                            "net.ToyAuxVAE / net.MNISTConvAuxVAE (the implicit models: net.IwaeEvaluator)")
         self.model, self.k, self.budget = model, int(sample_size), int(max_workspace_floats)
         if self.k < 1:
             raise ValueError(f"sample_size must be positive (got {sample_size})")
-        self.aux = isinstance(model, _AuxGaussianVAE)      # MNISTAuxVAE / ToyAuxVAE: two draws per sample, ardae_vae_aux_* in place of the head's calls
+        self.aux = isinstance(model, _AuxGaussianVAE)      # MNISTAuxVAE / ToyAuxVAE / MNISTConvAuxVAE: two draws per sample, ardae_vae_aux_* in place of the head's calls
         if model.z_dim > (MAX_AUX if self.aux else MAX_Z):
             raise NotImplementedError(f"GaussianIwaeEvaluator: z_dim {model.z_dim} > {MAX_AUX if self.aux else MAX_Z}: "
                                       f"{'ardae_vae_aux_iwae_draw' if self.aux else 'ardae_vae_iwae_draw'} takes latent widths up to "
@@ -98,7 +98,7 @@ class GaussianIwaeEvaluator:
     def _workspace_floats(self, c):
         d = self.model._desc
         G, g = min(c, self.image_group or c), min(c, self.group or c)
-        aux = (L.query("ardae_model_workspace_floats", d, c, 1, 1), L.query("ardae_model_workspace_floats", d, c, self.k, 4)) if self.aux else ()
+        aux = (L.query("ardae_model_workspace_floats", d, G, 1, 1), L.query("ardae_model_workspace_floats", d, g, self.k, 4)) if self.aux else ()
         return max(L.query("ardae_model_workspace_floats", d, G, 1, 0), L.query("ardae_model_workspace_floats", d, G, 1, 2),
                    L.query("ardae_model_workspace_floats", d, g * self.k, 1, 2), *aux)
 
@@ -129,7 +129,7 @@ class GaussianIwaeEvaluator:
 
     def plan(self, N):
         chunks = plan_chunks(N, self.k, self.floats_per_chunk, self.budget)
-        if self.aux and len(chunks) > 1:
+        if self.aux and self.image_group is None and len(chunks) > 1:
             # own draws are keyed by a chunk's first image, and a Philox counter holds 4 normals: chunks start at multiples of 4 images
             C = (chunks[0][1] - chunks[0][0]) // 4 * 4
             if C == 0:
@@ -213,10 +213,18 @@ class GaussianIwaeEvaluator:
                 c = i1 - i0
                 xc = x[i0:i1]
                 self._encode_stats(b, xc, c)
-                L.call("ardae_vae_aux_elbo_rows", d, flat, packed, xc, None if fwd_eps is None else fwd_eps.view(N, w)[i0:i1], c, seed, f0, f1, i0, ws,
-                       ws.numel(), recon[i0:i1], kld[i0:i1])
-                L.call("ardae_vae_aux_iwae_draw", d, flat, packed, xc, b["mu"], b["lv"], None if eps is None else eps[i0:i1], c, k, seed, o0, o1, i0, ws,
-                       ws.numel(), b["z"], b["logq"], None)
+                # (a model with fixed groups: the ELBO pass on image_group images per call, the three stages on group images per call - whole groups
+                # start at multiples of 4 images, as the draws' keying asks)
+                G, g = self.image_group or c, self.group or c
+                for j in range(0, c, G):
+                    n, a = min(G, c - j), i0 + j
+                    L.call("ardae_vae_aux_elbo_rows", d, flat, packed, x[a:a + n], None if fwd_eps is None else fwd_eps.view(N, w)[a:a + n], n, seed, f0, f1,
+                           a, ws, ws.numel(), recon[a:a + n], kld[a:a + n])
+                for j in range(0, c, g):
+                    n, a = min(g, c - j), i0 + j
+                    L.call("ardae_vae_aux_iwae_draw", d, flat, packed, x[a:a + n], b["mu"][j * self.sd:(j + n) * self.sd], b["lv"][j * self.sd:(j + n) * self.sd],
+                           None if eps is None else eps[a:a + n], n, k, seed, o0, o1, a, ws, ws.numel(), b["z"][j * k * m.z_dim:(j + n) * k * m.z_dim],
+                           b["logq"][j * k:(j + n) * k], None)
                 self._decode_rows(b, xc, b["z"], c, k, b["rec"], self.group)
                 L.call("ardae_iwae_reduce", b["rec"], b["pri"], b["logq"], c, k, out[i0:i1])
         return recon, kld, out
@@ -243,7 +251,7 @@ class VaeEngine:
     def __init__(self, model, cfg: VaeConfig, batch_size, graph=True):
         if not isinstance(model, GaussianVAE):
             raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE / "
-                            "net.MNISTAuxVAE / net.ToyAuxVAE); the implicit models take net.ArdaeEngine")
+                            "net.MNISTAuxVAE / net.ToyAuxVAE / net.MNISTConvAuxVAE); the implicit models take net.ArdaeEngine")
         if not isinstance(cfg, VaeConfig):
             raise TypeError(f"VaeEngine takes a VaeConfig, not a {type(cfg).__name__}")
         model._require_gpu()
