@@ -377,8 +377,8 @@ int ardae_fit_state_advance(void* fit_state, uint64_t rng_inc, double lr0, doubl
  *                        cat(h0, h) [B, 2 h_dim] */
 typedef struct ardae_model_desc {
   int kind;     /* 0 .. 7 above; 8 / 9 / 11 / 12: the Gaussian-posterior baselines of vae.py (see "Gaussian-posterior VAE baselines" below; noise_dim 0);
-                 * 14 / 15 / 17: the auxiliary-variable baselines (see "Auxiliary-variable Gaussian baselines" and "the hierarchical conv baseline" below).
-                 * 10, 13 and 16 are not kinds */
+                 * 14 / 15 / 17 / 19: the auxiliary-variable baselines (see "Auxiliary-variable Gaussian baselines", "the hierarchical conv baseline" and
+                 * "the hierarchical resconv baseline" below).  10, 13, 16 and 18 are not kinds */
   int input_dim, noise_dim, h_dim, z_dim;
   int n_layers; /* --model-n-layers */
   int act;      /* any ARDAE_ACT_* but NONE; kinds 5 / 6: ARDAE_ACT_ELU */
@@ -611,7 +611,7 @@ size_t ardae_conv_tail_workspace_floats(const ardae_model_desc* d, int R, int va
 int ardae_conv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* u1, int R, int variant, float* workspace,
                     size_t workspace_floats, float* logits, void* stream);
 
-/* The last stage of the residual-conv decoder on its own (kind 12; csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
+/* The last stage of the residual-conv decoder on its own (kinds 12 and 19; csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
  * -> bilinear x2 upsampling (align_corners) -> decode.dec.17 = ResConv2d(16 -> 1) -> logits [R, 784].  It reads the effective weights ardae_model_pack
  * composed into `packed`.
  *   variant 1: resconv_tail_kernel, ONE launch, a workgroup per image: the interpolation, hmid = ELU(conv3x3_0h(u28) + b) and
@@ -625,6 +625,35 @@ int ardae_conv_tail(const ardae_model_desc* d, const float* params, const float*
 size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant);
 int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* y14, int R, int variant, float* workspace,
                        size_t workspace_floats, float* logits, void* stream);
+
+/* ---- the hierarchical resconv baseline of vae.py (models/vae/auxresconv.py; csrc/resmodel.hip): ardae_model_desc.kind 19 ------
+ * The Gaussian counterpart of kind 6, `vae.py --model auxresconv` / `auxresconvct` (do_center False / True).  18 is not a kind.
+ *   kind 19 (MNISTResConvAuxVAE; 28 x 28 x 1 and ELU only): ONE weight-normalised residual trunk inp_encode.enc.* (the trunk of kinds 5 / 6 / 12, on 2x - 1
+ *                        unless ARDAE_MODEL_NO_CENTER) -> ctx [B, c_dim]; aux_encode.reparam.{mean_fn, logvar_fn} [noise_dim, c_dim] on ctx;
+ *                        encode.fc.0 (c_dim + noise_dim) -> c_dim + ELU on cat[ctx, z0], encode.reparam.* [z_dim, c_dim]; kind 12's decoder;
+ *                        aux_decode.fc.0 (c_dim + z_dim) -> c_dim + ELU on cat[ctx, z], aux_decode.reparam.* [noise_dim, c_dim].  ctx comes FIRST in
+ *                        both concatenations; no log-variance clip.
+ * input_dim 784, h_dim = c_dim >= 1, n_layers 1, 1 <= noise_dim <= 128 (the width of z0), z_dim >= 1 (<= 128 for ardae_vae_aux_iwae_draw), flags 0 or
+ * ARDAE_MODEL_NO_CENTER, ARDAE_ACT_ELU.  Workspace modes as for kind 17 (0: encode_stats, which returns mu0, lv0; 1: forward + backward; 2: decode;
+ * 4: ardae_vae_aux_iwae_draw).  Every ardae_vae_* entry point takes it with kind 14's conventions (eps rows [eps0 | eps], the Philox elements of an own
+ * draw, losses[2] = mean(kld + aux_kld)); the z head has kind 12's variants and policy (ardae_vae_head_fused_ok is 0); ardae_vae_aux_elbo_rows and
+ * ardae_vae_aux_iwae_draw take it unchanged; ardae_resconv_tail takes it as it takes kind 12.
+ *
+ * The decoder's 14 x 14 stage on its own: y8 [R, 8, 8, 32] NHWC - the output of decode.dec.8 after its ELU - -> crop to 7 x 7 -> bilinear x2 upsampling
+ * (align_corners) -> decode.dec.12 = ResConv2d(32 -> 16) + ELU -> decode.dec.14 = ResConv2d(16 -> 16) + ELU -> y14 [R, 14, 14, 16] NHWC, which
+ * ardae_resconv_tail reads.  It reads the effective weights and the re-laid copy ardae_model_pack left in `packed`.
+ *   variant 1: resconv_mid_kernel, ONE launch, a workgroup per image: the interpolated map, both hidden maps and dec.12's output stay in LDS, the six
+ *              3 x 3 convolutions run on v_mfma_f32_16x16x4_f32 in a fixed order inside the image's workgroup, so a row's bits do not depend on R.
+ *              Needs no workspace (it may be NULL).
+ *   variant 2: the ten launches the training forward runs (crop, upsample, and per block im2col, linear, im2col, two-source linear); workspace:
+ *              ardae_resconv_mid_workspace_floats(d, R, 2) floats.
+ *   variant 0: what ardae_model_decode runs for kind 19: variant 1, unless ARDAE_RESCONV_MID_UNFUSED=1 is set under ARDAE_DEBUG_KNOBS=1 (then the mode-2
+ *              workspace of the kind grows by c7, u14 and the two blocks' buffers, and its columns scratch to the 14 x 14 blocks').
+ * Kinds 5 / 6 / 12 and kind 19's training forward run the unfused launches.
+ * ardae_resconv_mid_workspace_floats: the floats `variant` needs at R rows (0 for the fused kernel, and for bad arguments). */
+size_t ardae_resconv_mid_workspace_floats(const ardae_model_desc* d, int R, int variant);
+int ardae_resconv_mid(const ardae_model_desc* d, const float* params, const float* packed, const float* y8, int R, int variant, float* workspace,
+                      size_t workspace_floats, float* y14, void* stream);
 
 /* ---- evaluation / visualisation side of the model surface (csrc/eval_kernels.hip) ----------------------------
  * Decoder samples that ImplicitPosteriorVAE.forward / .generate return next to the losses (ivae/mnist.py:188-199,300,316):

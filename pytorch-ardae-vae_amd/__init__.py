@@ -14,7 +14,7 @@ Fused path:
     PosteriorDiagnostics, ArdaeEngine.diagnostics -- the visualisation block's numbers (ivae_ardae.py:952-1111): 2-D histograms of the latents at
                                  every noise level from one sampler pass, the data-recon-gen histograms of the 2-D problems, log var q(z); all on
                                  the device, one host synchronisation per pass
-    MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE, VaeEngine, VaeConfig, GaussianIwaeEvaluator -- the Gaussian-posterior baselines of the reference's second trainer, vae.py
+    MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE, MNISTResConvAuxVAE, VaeEngine, VaeConfig, GaussianIwaeEvaluator -- the Gaussian-posterior baselines of the reference's second trainer, vae.py
                                  (`--model mnist` / `--model toy` / `--model conv` / `--model resconv` / `--model auxmnist` / `--model auxtoy` / `--model auxconv`): drop-in modules, one iteration of its loop as one captured unit with the posterior
                                  draw, the reparameterisation and the analytic KL fused into the head kernel, and its evaluate_iws under the analytic posterior
     ScalarLog                 -- the reference's per-step scalars through a device ring buffer (no host sync in the step)
@@ -26,7 +26,7 @@ from . import data  # noqa: F401
 from . import energy  # noqa: F401
 from .rng import manual_seed  # noqa: F401
 from .modules import (MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVAE, MNISTConvAuxIPVAE, ResConvIPVAE, MNISTResConvAuxIPVAE, MNISTResConvAuxIPVAEClipped, MLPGradCARDAE, MLPResCARDAE, MLPGradARDAE, MLPResARDAE, MLPGradDAE, MLPResDAE, ARDAE, DAE, Generator, ImplicitPosteriorVAE, ConditionalARDAE,  # noqa: F401
-                      normal_energy_func, GaussianVAE, MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE)
+                      normal_energy_func, GaussianVAE, MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE, MNISTResConvAuxVAE)
 from .optim import Adam, RMSprop, Polyak, SWA  # noqa: F401
 from .engine import ArdaeEngine, ArdaeScoreEngine, DaeConfig, ScoreConfig, TrainConfig, annealing_func, dae_sigma  # noqa: F401
 from .fit import ArdaeFitEngine, FitConfig  # noqa: F401

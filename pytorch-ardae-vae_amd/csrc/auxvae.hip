@@ -483,7 +483,7 @@ int ardae_vae_pair_kld_rows(const float* mu1, const float* lv1, const float* mu2
 static int aux_kind_check(const ardae_model_desc* d, const char* who) {
   ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
   const Family* f = family_of(d->kind);
-  ARDAE_CHECK_ARG(f && f->gauss && f->gauss->aux_elbo_rows, "%s: kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE) or 17 (MNISTConvAuxVAE), got %d", who, d->kind);
+  ARDAE_CHECK_ARG(f && f->gauss && f->gauss->aux_elbo_rows, "%s: kind must be 14 (MNISTAuxVAE) or 15 (ToyAuxVAE) or 17 (MNISTConvAuxVAE) or 19 (MNISTResConvAuxVAE), got %d", who, d->kind);
   return f->desc_check(d);
 }
 

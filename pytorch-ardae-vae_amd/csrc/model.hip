@@ -239,10 +239,10 @@ const Family MLP_FAMILY = mlp_family();
 // ------------------------------------------------------------------------------------------------ the families, by kind
 // (host_util.h) the one table by kind; desc_ok() checks the kind against it
 const Family* family_of(int kind) {
-  static const Family* const by_kind[18] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY,
+  static const Family* const by_kind[20] = {&MLP_FAMILY, &MLP_FAMILY, &CONV_FAMILY, &AUX_FAMILY, &AUXCONV_FAMILY, &RES_FAMILY, &RES_FAMILY, &AUX_FAMILY,
                                             &VAE_FAMILY, &VAE_FAMILY, nullptr, &CONVVAE_FAMILY, &RESVAE_FAMILY, nullptr, &AUXVAE_FAMILY,
-                                            &AUXVAE_FAMILY, nullptr, &AUXCONVVAE_FAMILY};      // 10, 13 and 16 are not kinds
-  return kind >= 0 && kind <= 17 ? by_kind[kind] : nullptr;
+                                            &AUXVAE_FAMILY, nullptr, &AUXCONVVAE_FAMILY, nullptr, &AUXRESVAE_FAMILY};      // 10, 13, 16 and 18 are not kinds
+  return kind >= 0 && kind <= 19 ? by_kind[kind] : nullptr;
 }
 
 }  // namespace ardae
@@ -254,7 +254,7 @@ static int desc_ok(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "model: desc is NULL");
   ARDAE_CHECK_ARG(family_of(d->kind) != nullptr,
                   "model: kind must be 0 (MNISTIPVAE), 1 (ToyIPVAE concat), 2 (ConvIPVAE), 3 (MNISTAuxIPVAE), 4 (MNISTConvAuxIPVAE), 5 (ResConvIPVAE), "
-                  "6 (MNISTResConvAuxIPVAE), 7 (ToyAuxIPVAE), 8 (MNISTVAE), 9 (ToyVAE), 11 (MNISTConvVAE) or 12 (MNISTResConvVAE), or 14 (MNISTAuxVAE) or 15 (ToyAuxVAE), or 17 (MNISTConvAuxVAE)");
+                  "6 (MNISTResConvAuxIPVAE), 7 (ToyAuxIPVAE), 8 (MNISTVAE), 9 (ToyVAE), 11 (MNISTConvVAE) or 12 (MNISTResConvVAE), or 14 (MNISTAuxVAE) or 15 (ToyAuxVAE), or 17 (MNISTConvAuxVAE), or 19 (MNISTResConvAuxVAE)");
   return family(d).desc_check(d);
 }
 

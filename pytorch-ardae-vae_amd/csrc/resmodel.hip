@@ -1,9 +1,12 @@
-// Weight-normalised residual-conv VAEs on gfx950 (ardae_model_desc.kind 5, 6 and 12):
+// Weight-normalised residual-conv VAEs on gfx950 (ardae_model_desc.kind 5, 6, 12 and 19):
 //   kind 5  ResConvIPVAE           models/ivae/resconv.py:53-245 (`--model resconvct-res`: do_center, enc_type 'res-wn-mlp')
 //   kind 6  MNISTResConvAuxIPVAE   models/ivae/auxresconv.py:48-255 + models/vae/auxresconv.py:26-185 (`--model auxresconvct`)
 //   kind 12 MNISTResConvVAE        models/vae/resconv.py:26-241 (`vae.py --model resconv`): the same trunk (width c_dim = h_dim), a plain Gaussian head
 //                                  encode.reparam.{mean_fn, logvar_fn} on it (no clip, one draw per image, the analytic KL of kinds 8 / 9 / 11) - driven
 //                                  by the ardae_vae_* entry points (csrc/vaemodel.hip dispatches here), not by the sampler calls
+//   kind 19 MNISTResConvAuxVAE     models/vae/auxresconv.py:254-424 (`vae.py --model auxresconv` / `auxresconvct`): the Gaussian counterpart of kind 6, joined
+//                                  from kind 12's trunk, head policy, decoder and weight-norm backward and the pair KL, seeds and evaluation bodies of
+//                                  csrc/auxvae.h (the section "kind 19" below)
 // all with the decoder of models/vae/resconv.py:79-136.  The shipped "implicit resconv" / "hierarchical resconv" recipes
 // (run_vae_dbmnist.sh) train them with ELU, an mlp-res cDAE, --std-scale 100.
 //
@@ -20,6 +23,7 @@
 
 #include "ardae_hip.h"
 #include "auxmodel.h"
+#include "auxvae.h"
 #include "common.h"
 #include "resmodel.h"
 #include "vaemodel.h"
@@ -307,7 +311,141 @@ __global__ __launch_bounds__(RT_THREADS) void resconv_tail_kernel(const float* _
   }
 }
 
-#define RES_LAUNCH(kernel, n, ...)                                                            \
+// The decoder's 14 x 14 stage as ONE launch (kind 19's decode-only path; ardae_resconv_mid variant 1): crop dec[3]'s output y8 [R, 8, 8, 32] to 7 x 7
+// (slicer[:, :, :-1, :-1]), upsample 7 -> 14 (up_src and the expression of upsample2_fwd_kernel), dec[4] = ResConv2d(32 -> 16) + ELU and
+// dec[5] = ResConv2d(16 -> 16) + ELU; writes y14 [R, 14, 14, 16], which resconv_tail_kernel reads.  One workgroup of four waves per image, so a row's
+// bits do not depend on the rows of the call; per row 8 KiB come in and 12.25 KiB go out (the unfused launches write and re-read ~141k column floats).
+//   Products: v_mfma_f32_16x16x4_f32, M = 16 output positions (p = 14 oh + ow; 196 = 12 tiles + one of 4), N = the 16 output channels, K walking
+//        c * 9 + kh * 3 + kw in the order of the effective weights, four per instruction.  Lane l holds A[m = l & 15][k = l >> 4], gathered from the
+//        planes by one ds_read_b32, B[k = l >> 4][n = l & 15] and D[m = 4 (l >> 4) + i][n = l & 15], i < 4.  conv_0h and conv_01 of a block read the
+//        same A: one gather feeds two MFMAs.  Wave w owns tiles w, w + 4, w + 8 (wave 0 also tile 12) and reads a k-step's B once for all of them;
+//        the pad lanes of tile 12 gather position 195 again (inside LDS) and their results are never stored.  conv_01's sums stay in registers and
+//        seed conv_h1's accumulators; the block's bias sum and the ELU come last.
+//   B:   resconv_mid_pack_kernel lays the six effective weights out so that lane l's values of four consecutive k-steps are one float4:
+//        wp[(g * 64 + l) * 4 + j] = weff[n = l & 15][k = 16 g + 4 j + (l >> 4)] - a wave reads 1 KiB per load, coalesced, the four waves the same lines.
+//   LDS: channel planes of 16 x 16 (position (oh, ow) at (oh + 1, ow + 1); the zero halo is what the padding taps read) at a plane stride of 272
+//        floats: u14 32 planes (34 KiB); dec[4]'s hidden map 16 planes (17 KiB); dec[4]'s output goes where u14's first 16 planes were once dec[4]
+//        has read them, dec[5]'s hidden map where dec[4]'s was; y8 staged as [64][33] (8.25 KiB) - 59.25 KiB, two workgroups a CU.
+//        Banks (word % 32, conflicts counted within a 32-lane half): in a gather lanes 0 .. 15 read one tap at 16 consecutive positions, words
+//        a .. a + 13, a + 16, a + 17 (the tile crosses one image row); lanes 16 .. 31 read the next k: the same words shifted by 1 (next kw) or 14 (next
+//        kh) - 32 consecutive words, shared ones broadcast - or by 272 - 34 = 14 mod 32 (next channel): no conflict, which is what the stride is for.
+//        The epilogue's plane writes have lanes 0 .. 15 on 16 planes, stride 272 = 16 mod 32: 8-way, 12 .. 16 such writes a wave and stage against
+//        ~300 MFMAs.  The interpolation walks (channel, pixel) with the pixel fastest: plane writes on consecutive words, y8's stage read at
+//        (pos * 33 + c), pos within 9 of each other in a half: distinct banks or the same word.
+constexpr int RM_THREADS = 256, RM_STRIDE = 272, RM_U = 32 * RM_STRIDE, RM_H = 16 * RM_STRIDE, RM_Y8 = 64 * 33;
+// offsets of the six operators in the packed mid weights: dec[4].a, dec[4].s (K = 288), dec[4].h, dec[5].a, dec[5].s, dec[5].h (K = 144)
+constexpr int RM_W4A = 0, RM_W4S = 16 * 288, RM_W4H = 2 * 16 * 288, RM_W5A = RM_W4H + 16 * 144, RM_W5S = RM_W5A + 16 * 144, RM_W5H = RM_W5S + 16 * 144,
+              RM_WTOTAL = RM_W5H + 16 * 144;
+using f32x4 = float __attribute__((ext_vector_type(4)));
+
+struct MidPackArgs { const float* weff[6]; int K[6], off[6]; };
+__global__ void resconv_mid_pack_kernel(const MidPackArgs a, float* __restrict__ wp) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= RM_WTOTAL) return;
+  int o = 5;
+  while (o > 0 && e < a.off[o]) --o;
+  const int i = e - a.off[o], g = i >> 8, l = (i >> 2) & 63, j = i & 3;
+  wp[e] = a.weff[o][(l & 15) * a.K[o] + 16 * g + 4 * j + (l >> 4)];
+}
+
+// acc0[t] (+ acc1[t] where DUAL) += the 3 x 3 convolution of the CIN planes at src with the packed weights w0 (w1), for the wave's tiles t
+template <int CIN, bool DUAL>
+__device__ __forceinline__ void rm_conv(const float* src, const float4* __restrict__ w0, const float4* __restrict__ w1, int lane, int wave,
+                                        const int (&base)[4], f32x4 (&acc0)[4], f32x4 (&acc1)[4]) {
+  const int kq = lane >> 4;
+#pragma unroll 1
+  for (int g = 0; g < CIN * 9 / 16; ++g) {
+    const float4 f0 = w0[g * 64 + lane];
+    float4 f1 = f0;
+    if (DUAL) f1 = w1[g * 64 + lane];
+    const float b0[4] = {f0.x, f0.y, f0.z, f0.w}, b1[4] = {f1.x, f1.y, f1.z, f1.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = 16 * g + 4 * j + kq, c = k / 9, r = k - 9 * c, kh = r / 3, kw = r - 3 * kh;
+      const float* p = src + c * RM_STRIDE + kh * 16 + kw;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (t < 3 || wave == 0) {          // wave-uniform: tile wave + 4 t < 13
+          const float a = p[base[t]];
+          acc0[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0[j], acc0[t], 0, 0, 0);
+          if (DUAL) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1[j], acc1[t], 0, 0, 0);
+        }
+      }
+    }
+  }
+}
+// ELU(acc + bias[n]) of the wave's tiles into the planes at dst, or (GLOBAL) into the image's NHWC rows [196, 16]
+template <bool GLOBAL>
+__device__ __forceinline__ void rm_store(const f32x4 (&acc)[4], const float* __restrict__ bias, int lane, int wave, float* dst) {
+  const int n = lane & 15, m0 = 4 * (lane >> 4);
+  const float b = bias[n];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t < 3 || wave == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int p = 16 * (wave + 4 * t) + m0 + i;
+        if (p < 196) {
+          const float v = act_fwd_rt(ACT_ELU, acc[t][i] + b);
+          if (GLOBAL) dst[p * 16 + n] = v;
+          else dst[n * RM_STRIDE + (p / 14 + 1) * 16 + p % 14 + 1] = v;
+        }
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(RM_THREADS) void resconv_mid_kernel(const float* __restrict__ y8, const float* __restrict__ wp, const float* __restrict__ ba4,
+                                                                 const float* __restrict__ bs4, const float* __restrict__ ba5,
+                                                                 const float* __restrict__ bs5, float* __restrict__ y14) {
+  __shared__ float u[RM_U];          // u14; then dec[4]'s output in its first 16 planes
+  __shared__ float hm[RM_H];         // dec[4]'s hidden map, then dec[5]'s
+  __shared__ float y8s[RM_Y8];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const float* __restrict__ yb = y8 + (size_t)blockIdx.x * 2048;
+  for (int i = t; i < RM_U; i += RM_THREADS) u[i] = 0.f;
+  for (int i = t; i < RM_H; i += RM_THREADS) hm[i] = 0.f;
+  for (int e = t; e < 2048; e += RM_THREADS) y8s[(e >> 5) * 33 + (e & 31)] = yb[e];
+  __syncthreads();
+  // crop + upsample: source rows / columns 0 .. 6 only (IH = 7 on the stride-8 map)
+  for (int e = t; e < 196 * 32; e += RM_THREADS) {
+    const int c = e / 196, pix = e - c * 196, oh = pix / 14, ow = pix - oh * 14;
+    int h0, h1, w0, w1; float fh, fw;
+    up_src(oh, 7, 14, h0, h1, fh); up_src(ow, 7, 14, w0, w1, fw);
+    const float* xb = y8s + c;
+    const float v00 = xb[(h0 * 8 + w0) * 33], v01 = xb[(h0 * 8 + w1) * 33], v10 = xb[(h1 * 8 + w0) * 33], v11 = xb[(h1 * 8 + w1) * 33];
+    u[c * RM_STRIDE + (oh + 1) * 16 + ow + 1] = (1.f - fh) * ((1.f - fw) * v00 + fw * v01) + fh * ((1.f - fw) * v10 + fw * v11);
+  }
+  int base[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int p = 16 * (wave + 4 * j) + (lane & 15);
+    if (p > 195) p = 195;
+    base[j] = (p / 14) * 16 + p % 14;
+  }
+  const float4* __restrict__ w4 = reinterpret_cast<const float4*>(wp);
+  f32x4 aa[4], as[4];
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) aa[j] = as[j] = zero;
+  __syncthreads();
+  // dec[4]: hidden = ELU(conv_0h(u14) + b_0h), skip = conv_01(u14); out = ELU(conv_h1(hidden) + skip + (b_h1 + b_01))
+  rm_conv<32, true>(u, w4 + RM_W4A / 4, w4 + RM_W4S / 4, lane, wave, base, aa, as);
+  rm_store<false>(aa, ba4, lane, wave, hm);
+  __syncthreads();                   // every wave has read u14 and written its part of the hidden map
+  rm_conv<16, false>(hm, w4 + RM_W4H / 4, nullptr, lane, wave, base, as, aa);
+  rm_store<false>(as, bs4, lane, wave, u);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) aa[j] = as[j] = zero;
+  __syncthreads();
+  // dec[5] on dec[4]'s output
+  rm_conv<16, true>(u, w4 + RM_W5A / 4, w4 + RM_W5S / 4, lane, wave, base, aa, as);
+  rm_store<false>(aa, ba5, lane, wave, hm);
+  __syncthreads();
+  rm_conv<16, false>(hm, w4 + RM_W5H / 4, nullptr, lane, wave, base, as, aa);
+  rm_store<true>(as, bs5, lane, wave, y14 + (size_t)blockIdx.x * (196 * 16));
+}
+
+#define RES_LAUNCH(kernel, n, ...)                                                          \
   do {                                                                                        \
     hipLaunchKernelGGL(kernel, dim3(nblk(n)), dim3(256), 0, st, __VA_ARGS__);                 \
     ARDAE_LAUNCH_CHECK();                                                                     \
@@ -329,7 +467,8 @@ struct ResLayout {
   bool clipped;                  // kind 6 + ARDAE_MODEL_CLIPPED: MNISTResConvAuxIPVAEClipped (no 'spm4' clip, z0 keeps an unscaled eps0)
   std::vector<Blk> trunk, dec;   // trunk: 5 conv + ResLinear(512 -> cdim); dec: 2 ResLinear + 5 conv
   std::vector<HeadOp> head;      // kind 5: encode.fc (the shipped recipe: ResLinear(cdim + nd -> hdim), ELU, ResLinear(hdim -> zd), un-normalised WN operators)
-  Lin mu0{}, lv0{}, efc{}, mu{}, lv{};   // kind 6: aux_encode.reparam.{mean,logvar}_fn, encode.fc.0, encode.reparam.{mean,logvar}_fn; kind 12: the last two
+  Lin mu0{}, lv0{}, efc{}, mu{}, lv{};   // kinds 6 / 19: aux_encode.reparam.{mean,logvar}_fn, encode.fc.0, encode.reparam.{mean,logvar}_fn; kind 12: the last two
+  Lin rfc{}, mup{}, lvp{};               // kind 19: aux_decode.fc.0 on cat[ctx, z], aux_decode.reparam.{mean,logvar}_fn (behind the decoder)
   size_t total = 0;
 
   explicit ResLayout(const ardae_model_desc& d)
@@ -393,6 +532,7 @@ struct ResLayout {
     dec.push_back(block(16, 32, true, 1, 14, true));
     dec.push_back(block(16, 16, true, 1, 14, true));
     dec.push_back(block(1, 16, true, 1, 28, true));
+    if (kind == 19) { rfc = lin(cdim, cdim + zd); mup = lin(nd, cdim); lvp = lin(nd, cdim); }
     total = off;
   }
 };
@@ -405,7 +545,8 @@ struct ResPacked {
   std::vector<BlkPk> trunk, dec;
   struct HeadPk { BlkPk k; LinPk lk; };
   std::vector<HeadPk> head;
-  LinPk mu0{}, lv0{}, efc{}, mu{}, lv{};
+  LinPk mu0{}, lv0{}, efc{}, mu{}, lv{}, rfc{}, mup{}, lvp{};
+  size_t mid_w = 0;              // kind 19: resconv_mid_kernel's weights (res_pack fills them after the pack launch)
   ResPacked(const ResLayout& P, PackList& pl) {
     // an operator's panels are packed from its effective weight: composed into the packed buffer at k.weff by res_pack's
     // compose launch (weight norm), or the parameter itself (plain nn.Linear operator, whose weff / inv stay unused)
@@ -445,6 +586,7 @@ struct ResPacked {
     } else if (P.kind == 12) { mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
     else { mu0 = lin(P.mu0, 0); lv0 = lin(P.lv0, 0); efc = lin(P.efc, P.cdim); mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
     for (auto& b : P.dec) dec.push_back(blk(b, 0));
+    if (P.kind == 19) { rfc = lin(P.rfc, P.cdim); mup = lin(P.mup, 0); lvp = lin(P.lvp, 0); mid_w = pl.take(RM_WTOTAL); }
   }
   explicit ResPacked(const ResLayout& P, PackList&& sizing = PackList()) : ResPacked(P, sizing) {}   // offsets only
 };
@@ -457,6 +599,18 @@ int resvae_desc_check(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 12, got %d", d->n_layers);
   ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
   ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 12 takes ELU only (--model-nonlin elu; models/vae/resconv.py:145 asserts it), got activation %d", d->act);
+  return 0;
+}
+
+// the descriptor rules of kind 19 (input_dim 784, 1 <= noise_dim <= AV_NMAX, h_dim = c_dim >= 1, z_dim >= 1, n_layers 1, ELU, flags within ARDAE_MODEL_NO_CENTER)
+int auxresvae_desc_check(const ardae_model_desc* d) {
+  ARDAE_CHECK_ARG(d->noise_dim >= 1 && d->noise_dim <= AV_NMAX, "model: noise_dim must be 1 .. %d for kind 19 (the width of z0), got %d", AV_NMAX,
+                  d->noise_dim);
+  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind 19, got %d", d->flags);
+  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTResConvAuxVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
+  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 19, got %d", d->n_layers);
+  ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
+  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 19 takes ELU only (--model-nonlin elu; models/vae/auxresconv.py:278 asserts it), got activation %d", d->act);
   return 0;
 }
 
@@ -518,10 +672,23 @@ int tail_fused(const Blk& b, const BlkPk& k, const float* params, const float* p
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
-// which tail the decode-only path of kind 12 runs (ardae_resconv_tail's variant 0): the fused kernel, unless ARDAE_RESCONV_TAIL_UNFUSED=1 under
-// ARDAE_DEBUG_KNOBS=1.  The mode-2 workspace of kind 12 is sized for the answer.
+// which tail the decode-only path of kinds 12 / 19 runs (ardae_resconv_tail's variant 0): the fused kernel, unless ARDAE_RESCONV_TAIL_UNFUSED=1 under
+// ARDAE_DEBUG_KNOBS=1.  The mode-2 workspace of kinds 12 / 19 is sized for the answer.
 bool tail_fused_default() {
   const char* knob = debug_knob("ARDAE_RESCONV_TAIL_UNFUSED");
+  return !(knob && knob[0] == '1');
+}
+// crop + upsample + dec[4] + dec[5] on R images in one launch: y8 [R, 8, 8, 32] (dec[3]'s output after its ELU) -> y14 [R, 14, 14, 16]
+int mid_fused(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* y8, int R, float* y14, hipStream_t st) {
+  hipLaunchKernelGGL(resconv_mid_kernel, dim3((unsigned)R), dim3(RM_THREADS), 0, st, y8, packed + K.mid_w, params + P.dec[4].a.bias, packed + K.dec[4].bsum,
+                     params + P.dec[5].a.bias, packed + K.dec[5].bsum, y14);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+// which 14 x 14 stage the decode-only path of kind 19 runs (ardae_resconv_mid's variant 0; its mode-2 workspace is sized for the answer):
+// resconv_mid_kernel, unless ARDAE_RESCONV_MID_UNFUSED=1 under ARDAE_DEBUG_KNOBS=1
+bool mid_fused_default() {
+  const char* knob = debug_knob("ARDAE_RESCONV_MID_UNFUSED");
   return !(knob && knob[0] == '1');
 }
 
@@ -597,7 +764,9 @@ struct ResWs {
   struct HeadBuf { float *rba, *rbs, *hmid, *out; };                // kind 5, per head operator: per-image row biases [B,out] (concat), ResLinear hidden [R,out], output [R,out]
   std::vector<HeadBuf> hb; float* z;                                // z [R,zd]
   float *mu0, *lv0r, *lv0, *z0, *rbh, *hh, *mu, *lvr, *lv;          // kind 6 (kind 12: mu, lv [B, zd])
-  float *eps, *kld, *dmu, *dlv;                                     // kind 12: the draw used, the KL rows [B], the head's backward seed
+  float *eps, *kld, *dmu, *dlv;                                     // kinds 12 / 19: the draw used, the KL rows [B], the head's backward seed
+  // kind 19 (B rows; mu0, lv0, z0, rbh, hh, mu, lv, z as above): the two draws, aux_decode.fc's row bias and rows, its head, and the backward's seeds
+  float *eps0, *epsz, *rb2, *hr, *mup, *lvp, *dz, *dz0, *dmu0, *dlv0, *dmup, *dlvp, *dhr, *dhh;
   // decoder (R images)
   std::vector<BlkBuf> db; float *d4, *u8, *c7, *u14, *u28;          // block buffers; NHWC 4x4x32, upsampled / cropped maps
   float *rec_row, *pri_row, *dlogit, *dzq;
@@ -618,8 +787,18 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
     for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.tb[i], bwd);
     W.flat = ws.take((size_t)B * 512);
     W.inp = W.tb.back().out;
-    if (P.kind != 12) W.zero = ws.take(R * (P.nd + P.zd));
-    if (P.kind == 12) {          // one draw per image (nz = 1); mode 0 ends at the trunk: encode_stats writes the caller's mu, lv
+    if (P.kind != 12 && P.kind != 19) W.zero = ws.take(R * (P.nd + P.zd));
+    if (P.kind == 19) {          // one draw pair per image (nz = 1); mode 0 ends at the trunk: encode_stats writes the caller's mu0, lv0
+      if (mode == 1) {
+        W.mu0 = ws.take(R * P.nd); W.lv0 = ws.take(R * P.nd); W.eps0 = ws.take(R * P.nd); W.epsz = ws.take(R * P.zd); W.z0 = ws.take(R * P.nd);
+        W.rbh = ws.take(R * P.cdim); W.hh = ws.take(R * P.cdim);
+        W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.z = ws.take(R * P.zd); W.eps = ws.take(R * P.zd); W.kld = ws.take(R);
+        W.rb2 = ws.take(R * P.cdim); W.hr = ws.take(R * P.cdim); W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
+        W.dmu = ws.take(R * P.zd); W.dlv = ws.take(R * P.zd); W.dz = ws.take(R * P.zd);
+        W.dz0 = ws.take(R * P.nd); W.dmu0 = ws.take(R * P.nd); W.dlv0 = ws.take(R * P.nd); W.dmup = ws.take(R * P.nd); W.dlvp = ws.take(R * P.nd);
+        W.dhr = ws.take(R * P.cdim); W.dhh = ws.take(R * P.cdim);
+      }
+    } else if (P.kind == 12) {          // one draw per image (nz = 1); mode 0 ends at the trunk: encode_stats writes the caller's mu, lv
       if (mode == 1) {
         W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.z = ws.take(R * P.zd); W.eps = ws.take(R * P.zd); W.kld = ws.take(R);
         W.dmu = ws.take(R * P.zd); W.dlv = ws.take(R * P.zd);
@@ -640,7 +819,28 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
       W.z = ws.take(R * P.zd);
     }
   }
-  if (dec && P.kind == 12 && mode == 2) {
+  if (dec && P.kind == 19 && mode == 2) {
+    // decode only with resconv_mid_kernel (unless the knob switches back): the kernel stands for c7, u14 and the buffers of dec[4] / dec[5] but
+    // dec[5]'s output, which it writes; the one columns scratch is sized from the 8 x 8 blocks
+    const bool mid = mid_fused_default(), tail = tail_fused_default();
+    size_t cx = 0, ch = 0;
+    auto runs = [&](size_t i) { return i < 4 || (i < 6 ? !mid : !tail); };
+    for (size_t i = 0; i < P.dec.size(); ++i)
+      if (runs(i) && P.dec[i].conv) { cx = max_sz(cx, blk_rows(P.dec[i], (int)R) * P.dec[i].a.I); ch = max_sz(ch, blk_rows(P.dec[i], (int)R) * P.dec[i].h.I); }
+    float* colsx = ws.take(cx); float* colsh = ws.take(ch);
+    W.db.assign(P.dec.size(), BlkBuf{nullptr, nullptr, nullptr, nullptr});
+    for (size_t i = 0; i < P.dec.size(); ++i) {
+      const Blk& b = P.dec[i];
+      if (runs(i)) {
+        W.db[i].colsx = b.conv ? colsx : nullptr; W.db[i].colsh = b.conv ? colsh : nullptr;
+        W.db[i].hmid = ws.take(blk_rows(b, (int)R) * b.Cout);
+      }
+      if (runs(i) || i == 5) W.db[i].out = ws.take(blk_rows(b, (int)R) * b.Cout);
+    }
+    W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32);
+    if (!mid) { W.c7 = ws.take(R * 49 * 32); W.u14 = ws.take(R * 196 * 32); }
+    W.u28 = tail ? nullptr : ws.take(R * 784 * 16);
+  } else if (dec && P.kind == 12 && mode == 2) {
     // decode only, nothing is saved for a backward: ONE columns scratch (the widest block's) serves every conv block in turn, and with the fused
     // tail neither u28 nor dec[6]'s buffers exist
     const size_t nb = tail_fused_default() ? P.dec.size() - 1 : P.dec.size();
@@ -695,6 +895,9 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
       wsf = max_sz(wsf, need);
     }
     if (P.kind == 12) wsf = max_sz(wsf, 2 * wgrad_scratch_floats(Ri, P.zd, P.cdim));      // the two heads, one batch
+    else if (P.kind == 19)       // the ten plain-Linear problems, one list
+      wsf = max_sz(wsf, 2 * wgrad_scratch_floats(B, P.zd, P.cdim) + 4 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.cdim, P.cdim) +
+                            wgrad_scratch_floats(B, P.cdim, P.nd) + wgrad_scratch_floats(B, P.cdim, P.zd));
     else
       wsf = max_sz(wsf, 2 * (wgrad_scratch_floats(Ri, P.hdim, P.hdim) + wgrad_scratch_floats(Ri, P.hdim, P.cdim + P.nd) + wgrad_scratch_floats(Ri, P.zd, P.hdim)) +
                             3 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.hdim, P.cdim));
@@ -784,20 +987,28 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
   return launch_reparam_fwd(W.mu, W.lv, noise + P.nd, ldn, R, P.zd, 1, z_out, st);
 }
 
+// the 14 x 14 stage as its launches: y8 [R, 8, 8, 32] -> u5.out [R, 14, 14, 16]
+int mid_unfused(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* y8, int R, float* c7, float* u14, BlkBuf& u4,
+                BlkBuf& u5, hipStream_t st) {
+  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 49 * 32, y8, 8, 7, 32, c7, (int64_t)R * 49 * 32);    // slicer[:, :, :-1, :-1]
+  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 196 * 32, (const float*)c7, 7, 32, u14, (int64_t)R * 196 * 32);
+  ARDAE_TRY(blk_fwd(P.dec[4], K.dec[4], params, packed, u14, R, ACT_ELU, u4, st));
+  return blk_fwd(P.dec[5], K.dec[5], params, packed, u4.out, R, ACT_ELU, u5, st);
+}
+
 // decoder on R rows: z [R, zd] -> logits [R, 784]
 // fused_tail (kind 12's decode-only path): the last upsampling and dec[6] as resconv_tail_kernel, which writes `logits` itself
+// fused_mid (kind 19's decode-only path): the crop, the 7 -> 14 upsampling, dec[4] and dec[5] as resconv_mid_kernel
 int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* z, int R, ResWs& W, float* logits, hipStream_t st,
-                bool fused_tail = false) {
+                bool fused_tail = false, bool fused_mid = false) {
   ARDAE_TRY(blk_fwd(P.dec[0], K.dec[0], params, packed, z, R, ACT_ELU, W.db[0], st));
   ARDAE_TRY(blk_fwd(P.dec[1], K.dec[1], params, packed, W.db[0].out, R, ACT_ELU, W.db[1], st));
   ARDAE_TRY(launch_nhwc_nchw(W.db[1].out, R, 16, 32, W.d4, true, st));                                    // view(-1, 32, 4, 4) -> NHWC
   RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 64 * 32, W.d4, 4, 32, W.u8, (int64_t)R * 64 * 32);
   ARDAE_TRY(blk_fwd(P.dec[2], K.dec[2], params, packed, W.u8, R, ACT_ELU, W.db[2], st));
   ARDAE_TRY(blk_fwd(P.dec[3], K.dec[3], params, packed, W.db[2].out, R, ACT_ELU, W.db[3], st));
-  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 49 * 32, W.db[3].out, 8, 7, 32, W.c7, (int64_t)R * 49 * 32);    // slicer[:, :, :-1, :-1]
-  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 196 * 32, W.c7, 7, 32, W.u14, (int64_t)R * 196 * 32);
-  ARDAE_TRY(blk_fwd(P.dec[4], K.dec[4], params, packed, W.u14, R, ACT_ELU, W.db[4], st));
-  ARDAE_TRY(blk_fwd(P.dec[5], K.dec[5], params, packed, W.db[4].out, R, ACT_ELU, W.db[5], st));
+  if (fused_mid) ARDAE_TRY(mid_fused(P, K, params, packed, W.db[3].out, R, W.db[5].out, st));
+  else ARDAE_TRY(mid_unfused(P, K, params, packed, W.db[3].out, R, W.c7, W.u14, W.db[4], W.db[5], st));
   if (fused_tail) return tail_fused(P.dec[6], K.dec[6], params, packed, W.db[5].out, R, logits, st);
   RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, W.db[5].out, 14, 16, W.u28, (int64_t)R * 784 * 16);
   ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, W.u28, R, ACT_NONE, W.db[6], st));
@@ -901,11 +1112,20 @@ int res_pack(const ardae_model_desc& d, const float* params, float* packed, hipS
     hipLaunchKernelGGL(wn_compose_batch_kernel, dim3(maxo, cb.n), dim3(256), 0, st, cb);
     ARDAE_LAUNCH_CHECK();
   }
-  return pl.launch(st);
+  ARDAE_TRY(pl.launch(st));
+  if (P.kind != 19) return 0;
+  // resconv_mid_kernel's B operands, from the effective weights the compose launch has written
+  MidPackArgs a;
+  const WNPk* ops[6] = {&K.dec[4].a, &K.dec[4].s, &K.dec[4].h, &K.dec[5].a, &K.dec[5].s, &K.dec[5].h};
+  const int off[6] = {RM_W4A, RM_W4S, RM_W4H, RM_W5A, RM_W5S, RM_W5H};
+  for (int i = 0; i < 6; ++i) { a.weff[i] = packed + ops[i]->weff; a.K[i] = i < 2 ? 288 : 144; a.off[i] = off[i]; }
+  hipLaunchKernelGGL(resconv_mid_pack_kernel, dim3(nblk(RM_WTOTAL)), dim3(256), 0, st, a, packed + K.mid_w);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
 }
 
-GradMap grad_map(ResEntry& e, const float* params, const float* packed, float* grads, float grads_beta) {
-  GradMap gm{e.P, e.W.dweff, e.W.dbias, 0, {}, params, packed, grads};
+GradMap grad_map(const ResLayout& P, ResWs& W, const float* params, const float* packed, float* grads, float grads_beta) {
+  GradMap gm{P, W.dweff, W.dbias, 0, {}, params, packed, grads};
   gm.grads_beta = grads_beta;
   return gm;
 }
@@ -937,7 +1157,7 @@ struct ResTraits : IpTraitsBase {
   static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {
     return ardae::decoder_fwd(e.P, e.K, params, packed, z, R, e.W, nullptr, st);
   }
-  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e, params, packed, g, beta); }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.P, e.W, params, packed, g, beta); }
   static int decoder_bwd(Entry& e, const float* packed, int R, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, R, gm, st); }
   static int sampler_bwd(Entry& e, const float*, const float* packed, const float*, const float* noise, int B, int nz, GradMap& gm, hipStream_t st) {
     auto& [P, K, ws, W] = e;
@@ -1081,7 +1301,7 @@ struct ResVaeTraits {
   static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
     return ardae::decoder_fwd(e.P, e.K, params, packed, e.W.z, B, e.W, nullptr, st);
   }
-  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e, params, packed, g, beta); }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.P, e.W, params, packed, g, beta); }
   static int decoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, B, gm, st); }
   static int encoder_bwd(Entry& e, const float* packed, const float*, int B, GradMap& gm, hipStream_t st) {
     auto& [P, K, ws, W] = e;
@@ -1096,6 +1316,183 @@ struct ResVaeTraits {
   }
 };
 
+// ------------------------------------------------------------------------------------------------ kind 19: the hierarchical resconv Gaussian baseline
+//   per image (B rows):  ctx = trunk(x or 2x - 1)  [B, c]  - ONE trunk, read by the three networks
+//     aux_encode   mu0 = M0 ctx + m0;  lv0 = L0 ctx + l0 (no clip);  z0 = mu0 + exp(lv0 / 2) eps0
+//     encode       h = ELU(Fe [ctx | z0] + fe);  mu, lv, z, kld: the Gaussian head on h (kind 12's policy: the unfused launches)
+//     aux_decode   hr = ELU(Fr [ctx | z] + fr);  mup = Mp hr + mp;  lvp = Lp hr + lp;  aux_kld = KL(N(mu0, exp lv0) || N(mup, exp lvp)), added into kld
+//     decode       kind 12's decoder, Bernoulli reconstruction rows
+//   losses = {mean_b(recon_b + beta (kld_b + aux_kld_b)), mean recon, mean (kld + aux_kld)}
+//   (the ctx half of Fe / Fr enters as a row bias, computed once per image: the same code serves the evaluation's k rows per image)
+// Backward (c = loss_scale / B), every reparameterisation and both KLs in closed form as csrc/auxvae.hip's: the reconstruction seed and the decoder; the
+// pair KL's seed; aux_decode back into its z columns (dz = the decoder's + the auxiliary decoder's) and into ctx; the head's seed; encode back into z0 and
+// ctx; the first head's seed; aux_encode back into ctx - d ctx is the SUM of the three, made before the trunk's backward.  The ten plain-Linear weight
+// gradients go out as one list; the weight-normalised operators' block by block through wn_backward_kernel, as kind 12's.
+// The names csrc/auxvae.h's bodies read, over the shared layout
+struct AuxResLayout : ResLayout {
+  int h; Lin mean, logvar, meanp, logvarp;
+  explicit AuxResLayout(const ardae_model_desc& d) : ResLayout(d), h(cdim), mean(mu), logvar(lv), meanp(mup), logvarp(lvp) {}
+};
+struct AuxResPacked : ResPacked {
+  size_t mean_f, logvar_f, meanp_f, logvarp_f;
+  AuxResPacked(const AuxResLayout& P, PackList& pl) : ResPacked(P, pl), mean_f(mu.f), logvar_f(lv.f), meanp_f(mup.f), logvarp_f(lvp.f) {}
+  explicit AuxResPacked(const AuxResLayout& P, PackList&& sizing = PackList()) : AuxResPacked(P, sizing) {}   // offsets only
+};
+using AuxResEntry = Entry<AuxResLayout, AuxResPacked, ResWs>;
+
+// h [B rpg, c] = ELU(F [ctx | s] + f): the ctx half once per image as a row bias rb [B, c], shared by the image's rpg rows
+int ctx_cat_fwd(const ResLayout& P, const Lin& l, const LinPk& k, const float* params, const float* packed, int B, int rpg, const float* ctx, const float* s,
+                float* rb, float* h, hipStream_t st) {
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, ctx, P.cdim, P.cdim, packed + k.fi, params + l.b, rb, st));
+  LinArgs A{}; A.Y = h; A.ldY = P.cdim; A.rowbias = rb; A.rowbias_ld = P.cdim; A.rows_per_group = rpg;
+  return lin1(EPI_ACT, ACT_ELU, B * rpg, P.cdim, s, l.in - P.cdim, l.in - P.cdim, packed + k.fn, A, st);
+}
+
+// The evaluation pass (mode 4): B images x k samples, R = B k rows.  The trunk runs once (eval_prepare); the auxiliary decoder reuses encode.fc's row
+// buffer and row bias.
+struct AuxResEvalWs {
+  ResWs T;                                   // x2, the trunk's block buffers, flat; T.inp = ctx [B, c]
+  float *rb, *z0, *t, *mu, *lv, *mup, *lvp;
+  double* acc;                               // the row's log-density so far [R]
+};
+
+struct AuxResVaeTraits {
+  using Layout = AuxResLayout; using Packed = AuxResPacked; using Entry = AuxResEntry;
+  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, 1, mode); }
+  // encode.reparam on h [B, c]: kind 12's head and policy
+  static GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f, false, false}; }
+  static const float* hid(const ResWs& W) { return W.hh; }
+  static GaussBufs bufs(const ResWs& W) {
+    return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dz, W.dmu, W.dlv};
+  }
+  // (the two draws are in W.eps0 / W.epsz: aux_vae_forward)  the trunk, aux_encode, z0, encode.fc
+  static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, W.mu0, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, W.lv0, st));
+    ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
+    return ctx_cat_fwd(P, P.efc, K.efc, params, packed, B, 1, W.inp, W.z0, W.rbh, W.hh, st);
+  }
+  // the auxiliary decoder on [ctx | z] and the pair KL, added into the head's KL rows; then the decoder (unfused: the backward reads its columns)
+  static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(ctx_cat_fwd(P, P.rfc, K.rfc, params, packed, B, 1, W.inp, W.z, W.rb2, W.hr, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.hr, P.cdim, P.cdim, packed + K.mup.f, params + P.mup.b, W.mup, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.hr, P.cdim, P.cdim, packed + K.lvp.f, params + P.lvp.b, W.lvp, st));
+    ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
+    return ardae::decoder_fwd(P, K, params, packed, W.z, B, W, nullptr, st);
+  }
+  // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h)
+  using EvalWs = AuxResEvalWs;
+  static void carve_eval(const AuxResLayout& P, const AuxResPacked&, Bump& ws, int B, int k, AuxResEvalWs& W) {
+    const size_t b = (size_t)B, R = b * (size_t)k;
+    W.T.x2 = ws.take(b * 784);
+    W.T.tb.resize(P.trunk.size());
+    for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.T.tb[i], false);
+    W.T.flat = ws.take(b * 512);
+    W.T.inp = W.T.tb.back().out;
+    W.rb = ws.take(b * P.cdim);
+    W.z0 = ws.take(R * P.nd); W.t = ws.take(R * P.cdim);
+    W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
+    W.acc = reinterpret_cast<double*>(ws.take(2 * R));
+  }
+  static int eval_prepare(const AuxResLayout& P, const float* x, int B, AuxResEvalWs& W, const float*& xs, hipStream_t st) {
+    xs = x;
+    (void)P; (void)B; (void)W; (void)st;
+    return 0;
+  }
+  // stage 2 runs the trunk (params and packed are first at hand here); stage 3 reads its ctx again
+  static int eval_hidden(const AuxResLayout& P, const AuxResPacked& K, const float* params, const float* packed, int stage, const float* xs, const float* s,
+                         int B, int k, AuxResEvalWs& W, const float*& hid, hipStream_t st) {
+    hid = W.t;
+    if (stage == 2) ARDAE_TRY(trunk_fwd(P, K, params, packed, xs, B, W.T, st));
+    return ctx_cat_fwd(P, stage == 2 ? P.efc : P.rfc, stage == 2 ? K.efc : K.rfc, params, packed, B, k, W.T.inp, s, W.rb, W.t, st);
+  }
+};
+
+size_t auxresvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+  const AuxResLayout P(d);
+  const AuxResPacked K(P);
+  Bump ws;
+  if (mode == 4) {
+    if ((int64_t)B * nz >= (int64_t)1 << 30) return 0;
+    AuxResEvalWs W;
+    AuxResVaeTraits::carve_eval(P, K, ws, B, nz, W);
+    return ws.off;
+  }
+  if (mode != 2 && (nz != 1 || (mode != 0 && mode != 1))) return 0;      // one draw per image; there is no sampler pair
+  ResWs W;
+  carve(P, K, ws, mode == 2 ? B * nz : B, 1, mode, W);
+  return ws.off;
+}
+
+int auxresvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
+                       float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
+  AuxResEntry entry(d, workspace, wsf, B, 1, 1);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+  const float c = loss_scale / (float)B;
+  const int cd = P.cdim;
+  const int64_t n0 = (int64_t)B * P.nd;
+  GradMap gm = grad_map(entry.P, entry.W, params, packed, grads, grads_beta);
+  // reconstruction gradients at the logits (beta 0, no seed: dzq gets the zeros of the switched-off energy), the decoder down to W.dzq
+  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.dlogit, nullptr, W.dzq, st));
+  ARDAE_TRY(decoder_bwd(P, K, packed, W, B, gm, st));
+  // the pair KL's seed at the auxiliary decoder's head and at the first head; the auxiliary decoder back into its z columns (dz = W.dzq + dhr Wz) and
+  // into ctx (dB0)
+  ARDAE_TRY(launch_pair_kld_seed(W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta, W.dmup, W.dlvp, W.dmu0, W.dlv0, st));
+  ARDAE_TRY(dense_bwd2(ACT_ELU, B, cd, W.dmup, packed + K.mup.b, W.dlvp, packed + K.lvp.b, P.nd, W.hr, W.dhr, st));
+  ARDAE_TRY(dense_bwd(ACT_NONE, B, P.zd, W.dhr, cd, packed + K.rfc.bn, W.dzq, W.dz, st, W.dzq));      // act' == 1: S is only a placeholder
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, cd, W.dhr, cd, cd, packed + K.rfc.bi, nullptr, W.dB0, st));
+  // the z head, encode.fc back into its z0 columns and into ctx (dB1 = dB0 + dhh Wc)
+  ARDAE_TRY(gauss_head_seed(W.dz, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
+  ARDAE_TRY(dense_bwd2(ACT_ELU, B, cd, W.dmu, packed + K.mu.b, W.dlv, packed + K.lv.b, P.zd, W.hh, W.dhh, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.dhh, cd, cd, packed + K.efc.bn, nullptr, W.dz0, st));
+  ARDAE_TRY(dense_bwd(ACT_NONE, B, cd, W.dhh, cd, packed + K.efc.bi, W.dB0, W.dB1, st, W.dB0));
+  // the first head: the reparameterisation through z0 joins the pair KL's part (there is no clip in this family); its two Linears back into ctx
+  ARDAE_TRY(launch_z0_seed(W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0, st));
+  { LinArgs A{}; A.Y = W.dinp; A.ldY = cd;
+    ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, cd, W.dmu0, P.nd, P.nd, packed + K.mu0.b, W.dlv0, P.nd, P.nd, packed + K.lv0.b, A, st)); }
+  ARDAE_TRY(launch_axpy(W.dB1, (int64_t)B * cd, 1.f, W.dinp, st));                                  // d ctx, all three contributions
+  // the plain Linears' weight gradients, written in place (no weight norm)
+  WgradList wl(gm.grads, gm.grads_beta);
+  const float* ctx = W.inp;
+  auto cat = [&](const Lin& l, const float* dpre, const float* s) {      // cat[ctx, s]: the s half (+ bias), then the ctx half
+    wl.push(B, cd, l.in - cd, dpre, s, l.in - cd, wl.g(l.w + cd), l.in, wl.g(l.b));
+    wl.push(B, cd, cd, dpre, ctx, cd, wl.g(l.w), l.in, nullptr);
+  };
+  wl.push(B, P.zd, cd, W.dmu, W.hh, cd, wl.g(P.mu.w), cd, wl.g(P.mu.b));
+  wl.push(B, P.zd, cd, W.dlv, W.hh, cd, wl.g(P.lv.w), cd, wl.g(P.lv.b));
+  cat(P.efc, W.dhh, W.z0);
+  wl.push(B, P.nd, cd, W.dmu0, W.inp, cd, wl.g(P.mu0.w), cd, wl.g(P.mu0.b));
+  wl.push(B, P.nd, cd, W.dlv0, W.inp, cd, wl.g(P.lv0.w), cd, wl.g(P.lv0.b));
+  wl.push(B, P.nd, cd, W.dmup, W.hr, cd, wl.g(P.mup.w), cd, wl.g(P.mup.b));
+  wl.push(B, P.nd, cd, W.dlvp, W.hr, cd, wl.g(P.lvp.w), cd, wl.g(P.lvp.b));
+  cat(P.rfc, W.dhr, W.z);
+  ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+  return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
+}
+
+// mu0, lv0 of q(z0 | x): what the evaluation needs first
+int auxresvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
+                           float* mu_out, float* lv_out, hipStream_t st) {
+  AuxResEntry entry(d, workspace, wsf, B, 1, 0);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
+  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, mu_out, st));
+  return dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, lv_out, st);
+}
+
+int auxresvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
+                     hipStream_t st, float*) {
+  AuxResEntry entry(d, workspace, wsf, R, 1, 2);
+  auto& [P, K, ws, W] = entry;
+  ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
+  return decoder_fwd(P, K, params, packed, z, R, W, out0, st, tail_fused_default(), mid_fused_default());
+}
+
 }  // namespace
 
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
@@ -1104,17 +1501,26 @@ const Family RES_FAMILY = ip_family<ResTraits>(res_pack);
 static const GaussFamily RESVAE_GAUSS = gauss_family<ResVaeTraits>();
 const Family RESVAE_FAMILY = {resvae_desc_check, no_caps, family_param_floats<ResLayout, ResPacked>, family_packed_floats<ResLayout, ResPacked>,
                               resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward, vae_no_backward, &RESVAE_GAUSS};
+static const GaussFamily AUXRESVAE_GAUSS = {gauss_vae_head_fused_ok<AuxResVaeTraits>, aux_vae_forward<AuxResVaeTraits>, auxresvae_backward,
+                                            auxresvae_encode_stats, gauss_vae_head<AuxResVaeTraits>, aux_vae_elbo_rows<AuxResVaeTraits>,
+                                            aux_vae_iwae_draw<AuxResVaeTraits>};
+const Family AUXRESVAE_FAMILY = {auxresvae_desc_check, no_caps, family_param_floats<AuxResLayout, AuxResPacked>,
+                                 family_packed_floats<AuxResLayout, AuxResPacked>, auxresvae_workspace_floats, res_pack, vae_no_encode,
+                                 auxresvae_decode, vae_no_forward, vae_no_backward, &AUXRESVAE_GAUSS};
 #endif
 
 }  // namespace ardae
 
 using namespace ardae;
 
+// the descriptor rules of the two kinds ardae_resconv_tail takes
+static int tail_desc_check(const ardae_model_desc* d) { return d->kind == 19 ? auxresvae_desc_check(d) : resvae_desc_check(d); }
+
 extern "C" {
 
 // floats of the buffers the unfused launches keep: u28 and dec[6]'s columns, hidden map and output
 size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant) {
-  if (!d || d->kind != 12 || resvae_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
+  if (!d || (d->kind != 12 && d->kind != 19) || tail_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
   if (variant == 1 || (variant == 0 && tail_fused_default())) return 0;
   const ResLayout P(*d);
   Bump ws;
@@ -1127,8 +1533,8 @@ size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int
 int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* y14, int R, int variant, float* workspace,
                        size_t workspace_floats, float* logits, void* stream) {
   ARDAE_CHECK_ARG(d != nullptr, "resconv_tail: desc is NULL");
-  ARDAE_CHECK_ARG(d->kind == 12, "resconv_tail: kind must be 12 (MNISTResConvVAE), got %d", d->kind);
-  ARDAE_TRY(resvae_desc_check(d));
+  ARDAE_CHECK_ARG(d->kind == 12 || d->kind == 19, "resconv_tail: kind must be 12 (MNISTResConvVAE) or 19 (MNISTResConvAuxVAE), got %d", d->kind);
+  ARDAE_TRY(tail_desc_check(d));
   ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "resconv_tail: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
   ARDAE_CHECK_ARG(params && packed && y14 && logits, "resconv_tail: null pointer argument");
   ARDAE_CHECK_ARG(R > 0 && R < (1 << 20), "resconv_tail: bad batch (R=%d)", R);
@@ -1147,6 +1553,43 @@ int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const flo
   RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, y14, 14, 16, u28, (int64_t)R * 784 * 16);
   ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, u28, R, ACT_NONE, u, st));
   return launch_copy(u.out, (size_t)R * 784, logits, st);
+}
+
+// floats of the buffers the unfused launches keep: c7, u14 and the columns, hidden maps and outputs of dec[4] / dec[5]
+size_t ardae_resconv_mid_workspace_floats(const ardae_model_desc* d, int R, int variant) {
+  if (!d || d->kind != 19 || auxresvae_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
+  if (variant == 1 || (variant == 0 && mid_fused_default())) return 0;
+  const ResLayout P(*d);
+  Bump ws;
+  BlkBuf u;
+  ws.take((size_t)R * 49 * 32); ws.take((size_t)R * 196 * 32);
+  blk_carve(P.dec[4], R, ws, u, false); blk_carve(P.dec[5], R, ws, u, false);
+  return ws.off;
+}
+
+int ardae_resconv_mid(const ardae_model_desc* d, const float* params, const float* packed, const float* y8, int R, int variant, float* workspace,
+                      size_t workspace_floats, float* y14, void* stream) {
+  ARDAE_CHECK_ARG(d != nullptr, "resconv_mid: desc is NULL");
+  ARDAE_CHECK_ARG(d->kind == 19, "resconv_mid: kind must be 19 (MNISTResConvAuxVAE), got %d", d->kind);
+  ARDAE_TRY(auxresvae_desc_check(d));
+  ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "resconv_mid: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
+  ARDAE_CHECK_ARG(params && packed && y8 && y14, "resconv_mid: null pointer argument");
+  ARDAE_CHECK_ARG(R > 0 && R < (1 << 20), "resconv_mid: bad batch (R=%d)", R);
+  if (variant == 0) variant = mid_fused_default() ? 1 : 2;
+  hipStream_t st = (hipStream_t)stream;
+  const ResLayout P(*d);
+  const ResPacked K(P);
+  if (variant == 1) return mid_fused(P, K, params, packed, y8, R, y14, st);
+  const size_t need = ardae_resconv_mid_workspace_floats(d, R, 2);
+  ARDAE_CHECK_ARG(workspace, "resconv_mid: null pointer argument (the unfused launches need a workspace)");
+  ARDAE_CHECK_ARG(workspace_floats >= need, "resconv_mid: workspace too small (%zu < %zu floats)", workspace_floats, need);
+  Bump ws(workspace, workspace_floats);
+  float* c7 = ws.take((size_t)R * 49 * 32);
+  float* u14 = ws.take((size_t)R * 196 * 32);
+  BlkBuf u4, u5;
+  blk_carve(P.dec[4], R, ws, u4, false); blk_carve(P.dec[5], R, ws, u5, false);
+  ARDAE_TRY(mid_unfused(P, K, params, packed, y8, R, c7, u14, u4, u5, st));
+  return launch_copy(u5.out, (size_t)R * 196 * 16, y14, st);
 }
 
 }  // extern "C"

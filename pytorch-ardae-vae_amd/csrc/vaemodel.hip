@@ -344,7 +344,7 @@ int gauss_head_seed(const float* dz, const float* z, const float* mu, const floa
 }
 
 // what ardae_model_encode / ardae_model_vae_* answer for the Gaussian-posterior kinds (Family members)
-#define GAUSS_KINDS "kinds 8 / 9 / 11 / 12 / 14 / 15 / 17"
+#define GAUSS_KINDS "kinds 8 / 9 / 11 / 12 / 14 / 15 / 17 / 19"
 int vae_no_encode(const ardae_model_desc&, const float*, const float*, const float*, const float*, int, int, float*, size_t, float*, float*, hipStream_t,
                   const float*) {
   set_last_error("model_encode: " GAUSS_KINDS " have an analytic posterior, not a sampler (ardae_vae_encode_stats, ardae_vae_forward)");
@@ -424,7 +424,7 @@ const GaussFamily VAE_GAUSS = gauss_family<VaeTraits>();
 int vae_kind_check(const ardae_model_desc* d, const char* who) {
   ARDAE_CHECK_ARG(d != nullptr, "%s: desc is NULL", who);
   ARDAE_CHECK_ARG(family_of(d->kind) && family(d).gauss,
-                  "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), or 12 (MNISTResConvVAE), or 14 (MNISTAuxVAE) or 15 (ToyAuxVAE), or 17 (MNISTConvAuxVAE), got %d", who, d->kind);
+                  "%s: kind must be 8 (MNISTVAE), 9 (ToyVAE) or 11 (MNISTConvVAE), or 12 (MNISTResConvVAE), or 14 (MNISTAuxVAE) or 15 (ToyAuxVAE), or 17 (MNISTConvAuxVAE), or 19 (MNISTResConvAuxVAE), got %d", who, d->kind);
   return family(d).desc_check(d);
 }
 

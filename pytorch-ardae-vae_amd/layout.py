@@ -194,6 +194,21 @@ def resconv_vae_spec(z_dim, c_dim):
             + _resconv_decoder(z_dim, c_dim))
 
 
+def aux_resconv_vae_spec(noise_dim, z_dim, c_dim):
+    """The hierarchical residual-conv Gaussian baseline of vae.py (models/vae/auxresconv.py:254-284, `--model auxresconv` / `auxresconvct`; 28 x 28 x 1):
+    ONE weight-normalised trunk `inp_encode.enc.*` (width c_dim), AuxEncoder (a NormalDistributionLinear head on z0 of width noise_dim), Encoder
+    (`fc.0` on cat[ctx, z0], a head on z), the decoder of resconv_vae_spec and AuxDecoder (`fc.0` on cat[ctx, z], a head on z0), in the order the
+    reference assigns them.  ardae_model_desc.kind 19."""
+    def head(prefix, out):
+        return [(prefix + "reparam.mean_fn.weight", (out, c_dim)), (prefix + "reparam.mean_fn.bias", (out,)),
+                (prefix + "reparam.logvar_fn.weight", (out, c_dim)), (prefix + "reparam.logvar_fn.bias", (out,))]
+
+    def fc(prefix, extra):
+        return [(prefix + "fc.0.weight", (c_dim, c_dim + extra)), (prefix + "fc.0.bias", (c_dim,))]
+    return (_resconv_trunk("inp_encode.enc.", c_dim) + head("aux_encode.", noise_dim) + fc("encode.", noise_dim) + head("encode.", z_dim)
+            + _resconv_decoder(z_dim, c_dim) + fc("aux_decode.", z_dim) + head("aux_decode.", noise_dim))
+
+
 def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):
     s = _mlp("ctx_encode.", context_dim, h_dim, h_dim, n_layers - 1)
     s += _mlp("inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)

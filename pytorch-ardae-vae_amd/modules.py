@@ -153,7 +153,8 @@ def _f32c(t):
 KIND_IDS = {"mnist": 0, "toy": 1, "conv": 2, "auxmnist": 3, "auxconv": 4, "resconv": 5, "auxresconv": 6, "auxtoy": 7,      # ardae_model_desc.kind
             "vae_mnist": 8, "vae_toy": 9, "vae_conv": 11, "vae_resconv": 12,                                                    # (vae.py's baselines: GaussianVAE below; 10 is not a kind)
             "vae_auxmnist": 14, "vae_auxtoy": 15,                                                                               # (its auxiliary-variable baselines; 13 is not a kind)
-            "vae_auxconv": 17}                                                                                                  # (16 is not a kind)
+            "vae_auxconv": 17,                                                                                                  # (16 is not a kind)
+            "vae_auxresconv": 19}                                                                                               # (18 is not a kind)
 AUX_KINDS = ("auxmnist", "auxconv", "auxresconv", "auxtoy")                                                 # hierarchical samplers
 GAUSSIAN_DECODERS = ("toy", "auxtoy", "vae_toy", "vae_auxtoy")                                                                     # decode.reparam.{mean_fn, logvar_fn}
 
@@ -1120,7 +1121,7 @@ class ToyVAE(GaussianVAE):
 
 
 class _AuxGaussianVAE(GaussianVAE):
-    """What MNISTAuxVAE, ToyAuxVAE and MNISTConvAuxVAE share (ardae_model_desc kinds 14 / 15 / 17): q(z0 | x) q(z | z0, x) with an auxiliary decoder r(z0 | z, x).  forward()'s
+    """What MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE and MNISTResConvAuxVAE share (ardae_model_desc kinds 14 / 15 / 17 / 19): q(z0 | x) q(z | z0, x) with an auxiliary decoder r(z0 | z, x).  forward()'s
     `eps` is [B, noise_dim + z_dim], rows [eps0 | eps]; encode_stats() returns the statistics of q(z0 | x); logprob's `eps` is
     [B, sample_size, noise_dim + z_dim].  `model.encode` / `model.aux_encode` / `model.aux_decode` only name parameters: the three networks run inside
     forward() and logprob()."""
@@ -1229,3 +1230,41 @@ class MNISTConvAuxVAE(_AuxGaussianVAE):
         return layout.aux_conv_vae_spec(self.noise_dim, self.z_dim)
 
     reset_parameters = MNISTConvVAE.reset_parameters    # weight_init on Conv2d / Linear where do_xavier (ConvTranspose2d keeps torch's init), the -5 logit bias where do_m5bias (vae/auxconv.py:18-23,231-235)
+
+
+class MNISTResConvAuxVAE(_AuxGaussianVAE):
+    """models/vae/auxresconv.py::VAE (`vae.py --model auxresconv` / `auxresconvct`): the Gaussian counterpart of MNISTResConvAuxIPVAE.  ONE
+    weight-normalised residual-conv trunk `inp_encode.enc.*` (width c_dim, on 2x - 1 where do_center) gives ctx; aux_encode is a Gaussian head on ctx
+    (z0 of width z0_dim = `noise_dim`, no log-variance clip), encode `fc.0` + ELU on cat[ctx, z0] and a head on z, aux_decode `fc.0` + ELU on cat[ctx, z]
+    and a head on z0; MNISTResConvVAE's decoder.  ELU only (vae/auxresconv.py:278), 28x28x1 only.  forward() takes x as [B, 784] or [B, 1, 28, 28] and
+    returns the decoder sample / mean as [B, 784]."""
+    _kind = "vae_auxresconv"
+    # As for MNISTResConvVAE the library picks the kernel of every conv-as-linear by the row count, so the evaluator runs fixed groups: the statistics and
+    # the ELBO pass on 64 images per call, the three stages and the importance samples' decoder on 16.  The decode-only workspace of this kind (one
+    # columns scratch sized from the 8 x 8 blocks, the 14 x 14 stage and the last stage fused) takes ~5.3e4 floats per decoded row against ~1.18e5
+    # for MNISTResConvVAE's: at k = 256 the 4096 rows of a call need 0.22 G floats, inside the default budget of 2^28 (32 images would need 0.43 G).
+    # Chunks are cut at multiples of 64 images.
+    _eval_groups = (64, 16)
+
+    def __init__(self, energy_func=normal_energy_func, input_height=28, input_channels=1, z0_dim=100, z_dim=32, c_dim=450, nonlinearity="elu",
+                 do_center=False):
+        if input_height != 28 or input_channels != 1:
+            raise NotImplementedError("MNISTResConvAuxVAE: the reference asserts 28x28x1 (models/vae/auxresconv.py:276-277)")
+        if nonlinearity != "elu":
+            raise NotImplementedError(f"MNISTResConvAuxVAE: nonlinearity {nonlinearity!r}: the reference asserts 'elu' (models/vae/auxresconv.py:278)")
+        super().__init__()
+        self.input_height, self.input_channels, self.c_dim, self.z0_dim = input_height, input_channels, int(c_dim), int(z0_dim)
+        self.do_center = bool(do_center)
+        if not 1 <= int(z0_dim) <= 128:
+            raise ValueError(f"MNISTResConvAuxVAE: noise_dim must be 1 .. 128 (got {z0_dim})")
+        self.noise_dim, self.enc_type, self.clip_logvar = int(z0_dim), "simple", None
+        self._build(energy_func, input_height * input_height * input_channels, c_dim, z_dim, nonlinearity, 1, 0 if do_center else L.MODEL_NO_CENTER,
+                    noise_dim=self.noise_dim, boxes={})
+
+    def _param_spec(self):
+        return layout.aux_resconv_vae_spec(self.noise_dim, self.z_dim, self.c_dim)
+
+    def reset_parameters(self):
+        self._default_init()                                # the two fc.0 and the six heads: nn.Linear's default
+        with torch.no_grad():
+            _weight_norm_init(dict(self._spec), dict(self.named_parameters()))

@@ -1,7 +1,7 @@
 """The Gaussian-posterior baselines of the reference's second trainer, vae.py, on the device: one iteration of its loop (vae.py:396-417)
 as one captured unit, and its evaluate_iws (vae.py:342-377) in large chunks.
 
-    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE, net.MNISTAuxVAE, net.ToyAuxVAE, net.MNISTConvAuxVAE
+    model = net.MNISTVAE(...).cuda()          # or net.ToyVAE, net.MNISTConvVAE, net.MNISTResConvVAE, net.MNISTAuxVAE, net.ToyAuxVAE, net.MNISTConvAuxVAE, net.MNISTResConvAuxVAE
     eng = net.VaeEngine(model, net.VaeConfig(lr=1e-3, beta_init=1e-4, beta_annealing=50000), batch_size=128)
     for x in loader: eng.step(x)
     elbo, logprob = eng.evaluate_iws(x_valid, sample_size=512)
@@ -80,11 +80,11 @@ class GaussianIwaeEvaluator:
     def __init__(self, model, sample_size, max_workspace_floats=1 << 28):
         if not isinstance(model, GaussianVAE):
             raise TypeError("GaussianIwaeEvaluator evaluates net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE / net.MNISTAuxVAE / "
-                            "net.ToyAuxVAE / net.MNISTConvAuxVAE (the implicit models: net.IwaeEvaluator)")
+                            "net.ToyAuxVAE / net.MNISTConvAuxVAE / net.MNISTResConvAuxVAE (the implicit models: net.IwaeEvaluator)")
         self.model, self.k, self.budget = model, int(sample_size), int(max_workspace_floats)
         if self.k < 1:
             raise ValueError(f"sample_size must be positive (got {sample_size})")
-        self.aux = isinstance(model, _AuxGaussianVAE)      # MNISTAuxVAE / ToyAuxVAE / MNISTConvAuxVAE: two draws per sample, ardae_vae_aux_* in place of the head's calls
+        self.aux = isinstance(model, _AuxGaussianVAE)      # MNISTAuxVAE / ToyAuxVAE / MNISTConvAuxVAE / MNISTResConvAuxVAE: two draws per sample, ardae_vae_aux_* in place of the head's calls
         if model.z_dim > (MAX_AUX if self.aux else MAX_Z):
             raise NotImplementedError(f"GaussianIwaeEvaluator: z_dim {model.z_dim} > {MAX_AUX if self.aux else MAX_Z}: "
                                       f"{'ardae_vae_aux_iwae_draw' if self.aux else 'ardae_vae_iwae_draw'} takes latent widths up to "
@@ -251,7 +251,7 @@ class VaeEngine:
     def __init__(self, model, cfg: VaeConfig, batch_size, graph=True):
         if not isinstance(model, GaussianVAE):
             raise TypeError("VaeEngine drives the Gaussian-posterior baselines (net.MNISTVAE / net.ToyVAE / net.MNISTConvVAE / net.MNISTResConvVAE / "
-                            "net.MNISTAuxVAE / net.ToyAuxVAE / net.MNISTConvAuxVAE); the implicit models take net.ArdaeEngine")
+                            "net.MNISTAuxVAE / net.ToyAuxVAE / net.MNISTConvAuxVAE / net.MNISTResConvAuxVAE); the implicit models take net.ArdaeEngine")
         if not isinstance(cfg, VaeConfig):
             raise TypeError(f"VaeEngine takes a VaeConfig, not a {type(cfg).__name__}")
         model._require_gpu()
