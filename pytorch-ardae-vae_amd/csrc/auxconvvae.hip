@@ -130,15 +130,10 @@ constexpr int ACV_WGRAD_HINT = 14;
 void auxconvvae_wgrads(const AuxConvVaeLayout& P, const AuxConvVaeWs& W, int B, WgradList& wl, Bump& ws) {
   const ConvWs& C = W.C;
   auto trunk = [&](int k) { conv_trunk_wgrads(P.conv[k], W.T[k].cols, W.T[k].dh3, W.T[k].dh2, W.T[k].dh1, B, wl); };
-  // cat[h3, s]: the s half (+ bias), then the trunk half
-  auto cat = [&](const Lin& l, const float* dpre, const float* s, const float* inp) {
-    wl.push(B, 800, l.in - 512, dpre, s, l.in - 512, wl.g(l.w + 512), l.in, wl.g(l.b));
-    wl.push(B, 800, 512, dpre, inp, 512, wl.g(l.w), l.in, nullptr);
-  };
   conv_decoder_wgrads(P.dec, C, B, wl);
   wl.push(B, P.zd, 800, W.dmu, C.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
   wl.push(B, P.zd, 800, W.dlv, C.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
-  cat(P.efc, C.dt1, W.z0, W.T[TR_E].inp);
+  cat_wgrads(wl, B, P.efc, 512, C.dt1, W.z0, W.T[TR_E].inp);
   trunk(TR_E);
   wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
   wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
@@ -146,33 +141,15 @@ void auxconvvae_wgrads(const AuxConvVaeLayout& P, const AuxConvVaeWs& W, int B, 
   trunk(TR_A);
   wl.push(B, P.nd, 800, W.dmup, W.h4r, 800, wl.g(P.meanp.w), 800, wl.g(P.meanp.b));
   wl.push(B, P.nd, 800, W.dlvp, W.h4r, 800, wl.g(P.logvarp.w), 800, wl.g(P.logvarp.b));
-  cat(P.rfc, W.dh4r, W.z, W.T[TR_R].inp);
+  cat_wgrads(wl, B, P.rfc, 512, W.dh4r, W.z, W.T[TR_R].inp);
   trunk(TR_R);
   wl.assign(ws, ACV_WGRAD_HINT);
 }
 
-// h4 [B rpg, 800] = act(F [h3 | s] + f): the trunk half once per image as a row bias rb [B, 800], shared by the image's rpg rows
-int cat_fwd(const Lin& l, const CatLin& k, const float* params, const float* packed, int act, int B, int rpg, const float* inp, const float* s, float* rb,
-            float* h4, hipStream_t st) {
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, inp, 512, 512, packed + k.i_f, params + l.b, rb, st));
-  LinArgs A{}; A.Y = h4; A.ldY = 800; A.rowbias = rb; A.rowbias_ld = 800; A.rows_per_group = rpg;
-  return lin1(EPI_ACT, act, B * rpg, 800, s, l.in - 512, l.in - 512, packed + k.s_f, A, st);
-}
-// from dpre [B, 800] = d(pre-activation): ds [B, sd] = dpre Ws (+ q: what else arrives at s) and dinp [B, 512] = dpre Wi (the trunk applies conv3's act')
-int cat_bwd(const Lin& l, const CatLin& k, const float* packed, int B, const float* dpre, float* ds, const float* q, float* dinp, hipStream_t st) {
-  const int sd = l.in - 512;
-  if (q) ARDAE_TRY(dense_bwd(ACT_NONE, B, sd, dpre, 800, packed + k.s_b, q, ds, st, q));      // act' == 1: S is only a placeholder
-  else ARDAE_TRY(dense_fwd(ACT_NONE, B, sd, dpre, 800, 800, packed + k.s_b, nullptr, ds, st));
-  return dense_fwd(ACT_NONE, B, 512, dpre, 800, 800, packed + k.i_b, nullptr, dinp, st);
-}
-
-// The evaluation pass (mode 4): B images x k samples, R = B k rows.  One trunk's buffers serve encode's and aux_decode's trunk in turn, and the
-// auxiliary decoder reuses encode.fc's row buffer and row bias.
-struct AuxConvEvalWs {
+// The evaluation pass (mode 4): x2 and ONE trunk's buffers, which serve encode's and aux_decode's trunk in turn, in front of the shared rows
+struct AuxConvEvalWs : AuxEvalRows {
   float* x2;
   TrunkBuf T;
-  float *rb, *z0, *t, *mu, *lv, *mup, *lvp;
-  double* acc;                               // the row's log-density so far [R]
 };
 
 struct AuxConvVaeTraits {
@@ -188,44 +165,77 @@ struct AuxConvVaeTraits {
     return {W.mu, W.lv, W.z, W.eps, W.kld, C.rec_row, C.pri_row, C.logit, nullptr, C.dlogit, nullptr, C.dzq, C.dz, W.dmu, W.dlv};
   }
   // x2 and aux_encode up to (mu0, lv0); its trunk fills the im2col rows of x2 the other two read
-  static int stats_fwd(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, const float* x, int B, float* x2,
-                       const TrunkBuf& T, float* h4a, float* mu0, float* lv0, hipStream_t st) {
-    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, x2, st));
-    ARDAE_TRY(trunk_fwd(P.conv[TR_A], K.conv_f[TR_A], params, packed, x2, T.cols, T.hcv, T.inp, B, P.act, st));
-    ARDAE_TRY(dense_fwd(P.act, B, 800, T.inp, 512, 512, packed + K.afc_f, params + P.afc.b, h4a, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, h4a, 800, 800, packed + K.mean0_f, params + P.mean0.b, mu0, st));
-    return dense_fwd(ACT_NONE, B, P.nd, h4a, 800, 800, packed + K.logvar0_f, params + P.logvar0.b, lv0, st);
+  static int stats_fwd(Entry& en, const float* params, const float* packed, const float* x, int B, float* mu0, float* lv0, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    const TrunkBuf& T = W.T[TR_A];
+    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.C.x2, st));
+    ARDAE_TRY(trunk_fwd(P.conv[TR_A], K.conv_f[TR_A], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st));
+    ARDAE_TRY(dense_fwd(P.act, B, 800, T.inp, 512, 512, packed + K.afc_f, params + P.afc.b, W.h4a, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.mean0_f, params + P.mean0.b, mu0, st));
+    return dense_fwd(ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.logvar0_f, params + P.logvar0.b, lv0, st);
   }
   // (the two draws are in W.eps0 / W.epsz: aux_vae_forward)  aux_encode, z0, encode's trunk and fc
   static int encoder_fwd(Entry& en, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
     auto& [P, K, ws, W] = en;
     const TrunkBuf& T = W.T[TR_E];
-    ARDAE_TRY(stats_fwd(P, K, params, packed, x, B, W.C.x2, W.T[TR_A], W.h4a, W.mu0, W.lv0, st));
+    ARDAE_TRY(stats_fwd(en, params, packed, x, B, W.mu0, W.lv0, st));
     ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
     ARDAE_TRY(trunk_fwd(P.conv[TR_E], K.conv_f[TR_E], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st, true));
-    return cat_fwd(P.efc, K.efc, params, packed, P.act, B, 1, T.inp, W.z0, W.rb, W.C.t1, st);
+    return cat_fwd(P.act, B, 1, 800, T.inp, 512, packed + K.efc.i_f, params + P.efc.b, W.z0, P.nd, packed + K.efc.s_f, W.rb, W.C.t1, st);
   }
   // the auxiliary decoder on [h3r | z] and the pair KL, added into the head's KL rows; then the decoder
   static int decoder_fwd(Entry& en, const float* params, const float* packed, int B, hipStream_t st) {
     auto& [P, K, ws, W] = en;
     const TrunkBuf& T = W.T[TR_R];
     ARDAE_TRY(trunk_fwd(P.conv[TR_R], K.conv_f[TR_R], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st, true));
-    ARDAE_TRY(cat_fwd(P.rfc, K.rfc, params, packed, P.act, B, 1, T.inp, W.z, W.rb2, W.h4r, st));
+    ARDAE_TRY(cat_fwd(P.act, B, 1, 800, T.inp, 512, packed + K.rfc.i_f, params + P.rfc.b, W.z, P.zd, packed + K.rfc.s_f, W.rb2, W.h4r, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4r, 800, 800, packed + K.meanp_f, params + P.meanp.b, W.mup, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4r, 800, 800, packed + K.logvarp_f, params + P.logvarp.b, W.lvp, st));
     ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
     return conv_decode_fwd(P.dec, K.dec, params, packed, W.z, B, W.C, st);
   }
+  struct Grads { float* grads; float beta; };
+  static Grads grads_of(Entry&, const float*, const float*, float* grads, float grads_beta) { return {grads, grads_beta}; }
+  static int decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) { return conv_decoder_bwd(en.P.dec, en.K.dec, packed, en.W.C, B, st); }
+  // the auxiliary decoder back into its z columns (dz = C.dz + dh4r Wz) and into h3r (the trunk applies conv3's act')
+  static int aux_decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.h4r, W.dh4r, st));
+    return cat_bwd(B, 800, W.dh4r, P.zd, packed + K.rfc.s_b, W.C.dz, W.dz, 512, packed + K.rfc.i_b, nullptr, W.T[TR_R].dinp, st);
+  }
+  // encode.fc back into its z0 columns and into h3e
+  static int encode_fc_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.C.t1, W.C.dt1, st));
+    return cat_bwd(B, 800, W.C.dt1, P.nd, packed + K.efc.s_b, nullptr, W.dz0, 512, packed + K.efc.i_b, nullptr, W.T[TR_E].dinp, st);
+  }
+  // the first head (there is no clip in this family), aux_encode.fc, the three trunks; the 28 weight gradients as two batches
+  static int aux_encoder_bwd(Entry& en, const float* packed, int B, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    ConvWs& C = W.C;
+    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.T[TR_A].dinp, st));
+    for (int k = 0; k < 3; ++k) {
+      TrunkBuf& T = W.T[k];
+      ARDAE_TRY(trunk_bwd(K.conv_b[k], packed, T.dinp, C.dinp_t, T.hcv, T.dh3, C.dcols3, T.dh2, C.dcols2, T.dh1, B, P.act, st));
+    }
+    WgradList wl(g.grads, g.beta);
+    auxconvvae_wgrads(P, W, B, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+    ARDAE_TRY(wl.launch(st, ACV_WGRAD_HINT));
+    return wl.launch(st);
+  }
+  static void size_wgrads(Entry& en, int B) {
+    WgradList wl(nullptr);
+    auxconvvae_wgrads(en.P, en.W, B, wl, en.ws);
+  }
   // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h)
   using EvalWs = AuxConvEvalWs;
   static void carve_eval(const AuxConvVaeLayout& P, const AuxConvVaePacked&, Bump& ws, int B, int k, AuxConvEvalWs& W) {
-    const size_t b = (size_t)B, R = b * (size_t)k;
+    const size_t b = (size_t)B;
     W.x2 = ws.take(b * 784);
     trunk_carve(ws, b, ws.take(b * 196 * 25), W.T);
-    W.rb = ws.take(b * 800);
-    W.z0 = ws.take(R * P.nd); W.t = ws.take(R * 800);
-    W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
-    W.acc = reinterpret_cast<double*>(ws.take(2 * R));
+    W.carve_rows(ws, B, k, P.nd, P.zd, 800, 1);
   }
   static int eval_prepare(const AuxConvVaeLayout&, const float* x, int B, AuxConvEvalWs& W, const float*& xs, hipStream_t st) {
     xs = W.x2;
@@ -234,75 +244,13 @@ struct AuxConvVaeTraits {
   static int eval_hidden(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, int stage, const float* xs,
                          const float* s, int B, int k, AuxConvEvalWs& W, const float*& hid, hipStream_t st) {
     const int tr = stage == 2 ? TR_E : TR_R;
-    hid = W.t;
+    const Lin& l = stage == 2 ? P.efc : P.rfc;
+    const CatLin& c = stage == 2 ? K.efc : K.rfc;
+    hid = W.t[1];
     ARDAE_TRY(trunk_fwd(P.conv[tr], K.conv_f[tr], params, packed, xs, W.T.cols, W.T.hcv, W.T.inp, B, P.act, st, stage == 3));
-    return cat_fwd(stage == 2 ? P.efc : P.rfc, stage == 2 ? K.efc : K.rfc, params, packed, P.act, B, k, W.T.inp, s, W.rb, W.t, st);
+    return cat_fwd(P.act, B, k, 800, W.T.inp, 512, packed + c.i_f, params + l.b, s, l.in - 512, packed + c.s_f, W.rb, W.t[1], st);
   }
 };
-
-size_t auxconvvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  const AuxConvVaeLayout P(d);
-  const AuxConvVaePacked K(P);
-  Bump ws;
-  if (mode == 4) {
-    if ((int64_t)B * nz >= (int64_t)1 << 30) return 0;
-    AuxConvEvalWs W;
-    AuxConvVaeTraits::carve_eval(P, K, ws, B, nz, W);
-    return ws.off;
-  }
-  if (mode != 2 && (nz != 1 || (mode != 0 && mode != 1))) return 0;      // one draw per image; there is no sampler pair
-  AuxConvVaeWs W;
-  carve(P, K, ws, mode == 2 ? B * nz : B, mode, W);
-  if (mode == 1) {
-    WgradList wl(nullptr);
-    auxconvvae_wgrads(P, W, B, wl, ws);
-  }
-  return ws.off;
-}
-
-int auxconvvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
-                        float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  AuxConvVaeEntry entry(d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  ConvWs& C = W.C;
-  const float c = loss_scale / (float)B;
-  const int act = P.act;
-  const int64_t n0 = (int64_t)B * P.nd;
-  // reconstruction gradients at the logits (beta 0, no seed: dzq gets the zeros of the switched-off energy), the decoder down to C.dz
-  ARDAE_TRY(launch_vae_loss(0, C.logit, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, C.rec_row, C.pri_row, C.dlogit, nullptr, C.dzq, st));
-  ARDAE_TRY(conv_decoder_bwd(P.dec, K.dec, packed, C, B, st));
-  // the pair KL's seed at the auxiliary decoder's head and at the first head; the auxiliary decoder back into its z columns (dz = C.dz + dh4r Wz) and h3r
-  ARDAE_TRY(launch_pair_kld_seed(W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta, W.dmup, W.dlvp, W.dmu0, W.dlv0, st));
-  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.h4r, W.dh4r, st));
-  ARDAE_TRY(cat_bwd(P.rfc, K.rfc, packed, B, W.dh4r, W.dz, C.dz, W.T[TR_R].dinp, st));
-  // the z head, encode.fc back into its z0 columns and h3e
-  ARDAE_TRY(gauss_head_seed(W.dz, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
-  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, C.t1, C.dt1, st));
-  ARDAE_TRY(cat_bwd(P.efc, K.efc, packed, B, C.dt1, W.dz0, nullptr, W.T[TR_E].dinp, st));
-  // the first head: the reparameterisation through z0 joins the pair KL's part (there is no clip in this family); aux_encode.fc
-  ARDAE_TRY(launch_z0_seed(W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0, st));
-  ARDAE_TRY(dense_bwd2(act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.T[TR_A].dinp, st));
-  for (int k = 0; k < 3; ++k) {
-    TrunkBuf& T = W.T[k];
-    ARDAE_TRY(trunk_bwd(K.conv_b[k], packed, T.dinp, C.dinp_t, T.hcv, T.dh3, C.dcols3, T.dh2, C.dcols2, T.dh1, B, act, st));
-  }
-  WgradList wl(grads, grads_beta);
-  auxconvvae_wgrads(P, W, B, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  ARDAE_TRY(wl.launch(st, ACV_WGRAD_HINT));
-  return wl.launch(st);
-}
-
-// mu0, lv0 of q(z0 | x): what the evaluation needs first
-int auxconvvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
-                            float* mu_out, float* lv_out, hipStream_t st) {
-  AuxConvVaeEntry entry(d, workspace, wsf, B, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
-  return AuxConvVaeTraits::stats_fwd(P, K, params, packed, x, B, W.C.x2, W.T[TR_A], W.h4a, mu_out, lv_out, st);
-}
 
 // u1 [R, 8, 8, 32] -> logits [R, 784]; fused: conv_tail_kernel, else the four unfused launches on c2 / u2 / c3 / logit (then copied out)
 int tail_fwd(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, const float* u1, int R, bool fused, ConvWs& C,
@@ -346,16 +294,14 @@ int auxconvvae_desc_check(const ardae_model_desc* d) {
 
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
-const GaussFamily AUXCONVVAE_GAUSS = {gauss_vae_head_fused_ok<AuxConvVaeTraits>, aux_vae_forward<AuxConvVaeTraits>, auxconvvae_backward,
-                                      auxconvvae_encode_stats, gauss_vae_head<AuxConvVaeTraits>, aux_vae_elbo_rows<AuxConvVaeTraits>,
-                                      aux_vae_iwae_draw<AuxConvVaeTraits>};
+const GaussFamily AUXCONVVAE_GAUSS = aux_gauss_family<AuxConvVaeTraits>();
 #endif
 
 }  // namespace
 
 #ifndef __HIP_DEVICE_COMPILE__
 const Family AUXCONVVAE_FAMILY = {auxconvvae_desc_check, no_caps, family_param_floats<AuxConvVaeLayout, AuxConvVaePacked>,
-                                  family_packed_floats<AuxConvVaeLayout, AuxConvVaePacked>, auxconvvae_workspace_floats,
+                                  family_packed_floats<AuxConvVaeLayout, AuxConvVaePacked>, aux_workspace_floats<AuxConvVaeTraits>,
                                   auxconvvae_pack, vae_no_encode, auxconvvae_decode, vae_no_forward, vae_no_backward,
                                   &AUXCONVVAE_GAUSS};
 #endif

@@ -48,17 +48,14 @@ struct CondStack {
   }
   int fwd(const float* params, const float* packed, int act, int B, int rpg, const float* xs, const float* s, float* rb, float* const* t,
           hipStream_t st) const {
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, h, xs, D, D, packed + x_f, params + first.b, rb, st));
-    LinArgs A{}; A.Y = t[1]; A.ldY = h; A.rowbias = rb; A.rowbias_ld = h; A.rows_per_group = rpg;
-    ARDAE_TRY(lin1(EPI_ACT, act, B * rpg, h, s, sd, sd, packed + s_f, A, st));
+    ARDAE_TRY(cat_fwd(act, B, rpg, h, xs, D, packed + x_f, params + first.b, s, sd, packed + s_f, rb, t[1], st));
     return rest.fwd(params, packed, act, B * rpg, t[1], t + 1, st);
   }
   // from dt[nl] down to dt[1], then ds [R, sd] = dt[1] Ws (+ q: what else arrives at s; ds must not be q)
   int bwd(const float* packed, int act, int R, float* const* t, float* const* dt, float* ds, const float* q, hipStream_t st) const {
     ARDAE_TRY(rest.bwd(packed, act, R, t + 1, dt + 1, st));
     if (nl >= 2) ARDAE_TRY(dense_bwd(act, R, h, dt[2], h, packed + rest.b[0], t[1], dt[1], st));
-    if (q) return dense_bwd(ACT_NONE, R, sd, dt[1], h, packed + s_b, q, ds, st, q);      // act' == 1: S is only a placeholder
-    return dense_fwd(ACT_NONE, R, sd, dt[1], h, h, packed + s_b, nullptr, ds, st);
+    return cat_bwd(R, h, dt[1], sd, packed + s_b, q, ds, D, nullptr, nullptr, nullptr, st);
   }
   // layers nl .. 2, the first layer's s half (+ bias), its image half (training: one row per image, so dt[1] is the row bias' gradient too)
   void wgrads(WgradList& wl, int B, const float* xs, const float* s, float* const* t, float* const* dt) const {
@@ -66,8 +63,7 @@ struct CondStack {
       const Lin& L = rest.lin[l - 2];
       wl.push(B, h, h, dt[l], t[l - 1], h, wl.g(L.w), h, wl.g(L.b));
     }
-    wl.push(B, h, sd, dt[1], s, sd, wl.g(first.w + D), first.in, wl.g(first.b));
-    wl.push(B, h, D, dt[1], xs, D, wl.g(first.w), first.in, nullptr);
+    cat_wgrads(wl, B, first, D, dt[1], s, xs);
   }
   void carve(Bump& ws, size_t R, std::vector<float*>& t) const {
     t.assign(nl + 1, nullptr);
@@ -171,44 +167,8 @@ void auxvae_wgrads(const AuxVaeLayout& P, const AuxVaePacked& K, const AuxVaeWs&
   wl.assign(ws, wgrad_nprob(P));
 }
 
-// The evaluation pass (mode 4): B images x k samples, R = B k rows.  The auxiliary decoder reuses encode.fc's row buffers and row bias.
-struct AuxEvalWs {
-  float *xs, *rb, *z0;
-  std::vector<float*> t;
-  float *mu, *lv, *mup, *lvp;
-  double* acc;                               // the row's log-density so far [R]
-};
-void carve_eval(const AuxVaeLayout& P, const AuxVaePacked& K, Bump& ws, int B, int k, AuxEvalWs& W) {
-  const size_t b = (size_t)B, R = b * (size_t)k;
-  W.xs = ws.take(b * P.D);
-  W.rb = ws.take(b * P.h);
-  W.z0 = ws.take(R * P.nd);
-  K.ef.carve(ws, R, W.t);
-  W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd);
-  W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
-  W.acc = reinterpret_cast<double*>(ws.take(2 * R));
-}
-
-size_t auxvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  const AuxVaeLayout P(d);
-  const AuxVaePacked K(P);
-  if (mode == 2) return K.dec.decode_floats((size_t)B * nz);
-  Bump ws;
-  if (mode == 4) {
-    if ((int64_t)B * nz >= (int64_t)1 << 30) return 0;
-    AuxEvalWs W;
-    carve_eval(P, K, ws, B, nz, W);
-    return ws.off;
-  }
-  if (nz != 1 || (mode != 0 && mode != 1)) return 0;      // one draw per image; there is no sampler pair
-  AuxVaeWs W;
-  carve(P, K, ws, B, mode, W);
-  if (mode == 1) {
-    WgradList wl(nullptr);
-    auxvae_wgrads(P, K, W, B, wl, ws);
-  }
-  return ws.off;
-}
+// The evaluation pass (mode 4): xs [B, D] in front of the shared rows
+struct AuxEvalWs : AuxEvalRows { float* xs; };
 
 // ------------------------------------------------------------------------------------------------ kernels
 constexpr int AV_THREADS = 256;    // 4 waves of 64
@@ -358,20 +318,21 @@ struct AuxVaeTraits {
   static GaussBufs bufs(const AuxVaeWs& W) {
     return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.D.o[0], W.D.o[1], W.D.dox[0], W.D.dox[1], W.D.dzq, W.D.dz, W.dmu, W.dlv};
   }
-  // xs, aux_encode.main and its head: mu0, lv0 (clipped; lv0r the raw values)
-  static int stats_fwd(const AuxVaeLayout& P, const AuxVaePacked& K, const float* params, const float* packed, const float* x, int B, float* xs,
-                       float* const* e, float* mu0, float* lv0r, float* lv0, hipStream_t st) {
-    if (P.toy) ARDAE_TRY(launch_copy(x, (int64_t)B * P.D, xs, st));      // no rescale (vae/auxtoy.py); the later stages read xs, not the caller's x
-    else ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, xs, st));      // vae/auxmnist.py:56
-    ARDAE_TRY(K.am.fwd(params, packed, P.act, B, xs, e, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, e[P.nl], P.h, P.h, packed + K.mean0_f, params + P.mean0.b, mu0, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, e[P.nl], P.h, P.h, packed + K.logvar0_f, params + P.logvar0.b, lv0r, st));
+  // xs, aux_encode.main and its head: mu0, lv0 (clipped; where a clip is on, W.lv0r keeps the raw values)
+  static int stats_fwd(Entry& en, const float* params, const float* packed, const float* x, int B, float* mu0, float* lv0, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    float* lv0r = P.clip0 ? W.lv0r : lv0;
+    if (P.toy) ARDAE_TRY(launch_copy(x, (int64_t)B * P.D, W.xs, st));      // no rescale (vae/auxtoy.py); the later stages read xs, not the caller's x
+    else ARDAE_TRY(launch_affine(x, (int64_t)B * P.D, 2.f, -1.f, W.xs, st));      // vae/auxmnist.py:56
+    ARDAE_TRY(K.am.fwd(params, packed, P.act, B, W.xs, W.e.data(), st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.e[P.nl], P.h, P.h, packed + K.mean0_f, params + P.mean0.b, mu0, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.e[P.nl], P.h, P.h, packed + K.logvar0_f, params + P.logvar0.b, lv0r, st));
     return launch_logvar_clip(lv0r, nullptr, lv0, (int64_t)B * P.nd, P.clip0, st);
   }
-  // (the two draws are in W.eps0 / W.epsz: aux_forward below)  aux_encode, z0, encode.fc
+  // (the two draws are in W.eps0 / W.epsz: aux_vae_forward)  aux_encode, z0, encode.fc
   static int encoder_fwd(Entry& en, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
     auto& [P, K, ws, W] = en;
-    ARDAE_TRY(stats_fwd(P, K, params, packed, x, B, W.xs, W.e.data(), W.mu0, W.lv0r, W.lv0, st));
+    ARDAE_TRY(stats_fwd(en, params, packed, x, B, W.mu0, W.lv0, st));
     ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
     return K.ef.fwd(params, packed, P.act, B, 1, W.xs, W.z0, W.rb, W.t.data(), st);
   }
@@ -384,9 +345,37 @@ struct AuxVaeTraits {
     ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
     return K.dec.fwd(params, packed, P.act, B, W.z, W.D.hid.data(), W.D.o, st);
   }
-  // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h): the stages read xs; the auxiliary decoder reuses encode.fc's row buffers and row bias
+  struct Grads { float* grads; float beta; };
+  static Grads grads_of(Entry&, const float*, const float*, float* grads, float grads_beta) { return {grads, grads_beta}; }
+  static int decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) { return en.K.dec.bwd(packed, en.P.act, B, en.W.D, st); }
+  // the auxiliary decoder back into its z columns: dz = D.dz + du_1 Wz (xs takes no gradient)
+  static int aux_decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    ARDAE_TRY(dense_bwd2(P.act, B, P.h, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.u[P.nl], W.du[P.nl], st));
+    return K.ad.bwd(packed, P.act, B, W.u.data(), W.du.data(), W.dz, W.D.dz, st);
+  }
+  static int encode_fc_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    ARDAE_TRY(dense_bwd2(P.act, B, P.h, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.t[P.nl], W.dt[P.nl], st));
+    return K.ef.bwd(packed, P.act, B, W.t.data(), W.dt.data(), W.dz0, nullptr, st);
+  }
+  // the clip's derivative on the raw log-variance, the first head, aux_encode.main; every weight gradient in one list
+  static int aux_encoder_bwd(Entry& en, const float* packed, int B, Grads& g, hipStream_t st) {
+    auto& [P, K, ws, W] = en;
+    ARDAE_TRY(launch_logvar_clip(W.lv0r, W.dlv0, W.dlv0, (int64_t)B * P.nd, P.clip0, st));
+    ARDAE_TRY(dense_bwd2(P.act, B, P.h, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.e[P.nl], W.de[P.nl], st));
+    ARDAE_TRY(K.am.bwd(packed, P.act, B, W.e.data(), W.de.data(), st));
+    WgradList wl(g.grads, g.beta);
+    auxvae_wgrads(P, K, W, B, wl, ws);
+    ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
+    return wl.launch(st);
+  }
+  // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h): the stages read xs
   using EvalWs = AuxEvalWs;
-  static void carve_eval(const AuxVaeLayout& P, const AuxVaePacked& K, Bump& ws, int B, int k, AuxEvalWs& W) { ardae::carve_eval(P, K, ws, B, k, W); }
+  static void carve_eval(const AuxVaeLayout& P, const AuxVaePacked&, Bump& ws, int B, int k, AuxEvalWs& W) {
+    W.xs = ws.take((size_t)B * P.D);
+    W.carve_rows(ws, B, k, P.nd, P.zd, P.h, P.nl);
+  }
   static int eval_prepare(const AuxVaeLayout& P, const float* x, int B, AuxEvalWs& W, const float*& xs, hipStream_t st) {
     xs = x;
     if (P.toy) return 0;
@@ -400,44 +389,20 @@ struct AuxVaeTraits {
   }
 };
 
-int aux_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
-                 float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  AuxVaeEntry entry(d, workspace, wsf, B, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  const float c = loss_scale / (float)B;
-  const int h = P.h, act = P.act, nl = P.nl;
-  const int64_t n0 = (int64_t)B * P.nd;
-  // reconstruction gradients at the decoder's outputs (beta 0, no seed: dzq gets the zeros of the switched-off energy), the decoder down to D.dz
-  ARDAE_TRY(launch_vae_loss(P.toy ? 1 : 0, W.D.o[0], W.D.o[1], x, W.z, B, 1, P.D, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.D.dox[0], W.D.dox[1],
-                            W.D.dzq, st));
-  ARDAE_TRY(K.dec.bwd(packed, act, B, W.D, st));
-  // the pair KL's seed at the auxiliary decoder's head and at the first head, the auxiliary decoder back into its z columns: dz = D.dz + du_1 Wz
-  ARDAE_TRY(launch_pair_kld_seed(W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta, W.dmup, W.dlvp, W.dmu0, W.dlv0, st));
-  ARDAE_TRY(dense_bwd2(act, B, h, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.u[nl], W.du[nl], st));
-  ARDAE_TRY(K.ad.bwd(packed, act, B, W.u.data(), W.du.data(), W.dz, W.D.dz, st));
-  // the z head, encode.fc back into its z0 columns
-  ARDAE_TRY(gauss_head_seed(W.dz, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
-  ARDAE_TRY(dense_bwd2(act, B, h, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.t[nl], W.dt[nl], st));
-  ARDAE_TRY(K.ef.bwd(packed, act, B, W.t.data(), W.dt.data(), W.dz0, nullptr, st));
-  // the first head: the reparameterisation through z0 joins the pair KL's part, then the clip's derivative on the raw log-variance
-  ARDAE_TRY(launch_z0_seed(W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0, st));
-  ARDAE_TRY(launch_logvar_clip(W.lv0r, W.dlv0, W.dlv0, n0, P.clip0, st));
-  ARDAE_TRY(dense_bwd2(act, B, h, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.e[nl], W.de[nl], st));
-  ARDAE_TRY(K.am.bwd(packed, act, B, W.e.data(), W.de.data(), st));
-  WgradList wl(grads, grads_beta);
-  auxvae_wgrads(P, K, W, B, wl, ws);
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  return wl.launch(st);
-}
-
-// mu0, lv0 (clipped) of q(z0 | x): what the evaluation needs first
-int aux_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
-                     float* mu_out, float* lv_out, hipStream_t st) {
-  AuxVaeEntry entry(d, workspace, wsf, B, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
-  return AuxVaeTraits::stats_fwd(P, K, params, packed, x, B, W.xs, W.e.data(), mu_out, P.clip0 ? W.lv0r : lv_out, lv_out, st);
+size_t auxvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
+  if (mode == 4) return aux_eval_floats<AuxVaeTraits>(d, B, nz);
+  const AuxVaeLayout P(d);
+  const AuxVaePacked K(P);
+  if (mode == 2) return K.dec.decode_floats((size_t)B * nz);
+  if (nz != 1 || (mode != 0 && mode != 1)) return 0;      // one draw per image; there is no sampler pair
+  Bump ws;
+  AuxVaeWs W;
+  carve(P, K, ws, B, mode, W);
+  if (mode == 1) {
+    WgradList wl(nullptr);
+    auxvae_wgrads(P, K, W, B, wl, ws);
+  }
+  return ws.off;
 }
 
 // the descriptor rules of kinds 14 / 15: 1 <= noise_dim <= AV_NMAX, flags: only aux_encode's clip_logvar code (0 .. 10), 1 .. 4 layers
@@ -455,8 +420,7 @@ unsigned auxvae_caps(const ardae_model_desc& d) { return d.kind == 15 ? CAP_GAUS
 
 // (host pass only, as in csrc/auxmodel.hip)
 #ifndef __HIP_DEVICE_COMPILE__
-const GaussFamily AUXVAE_GAUSS = {gauss_vae_head_fused_ok<AuxVaeTraits>, aux_vae_forward<AuxVaeTraits>, aux_backward, aux_encode_stats,
-                                   gauss_vae_head<AuxVaeTraits>, aux_vae_elbo_rows<AuxVaeTraits>, aux_vae_iwae_draw<AuxVaeTraits>};
+const GaussFamily AUXVAE_GAUSS = aux_gauss_family<AuxVaeTraits>();
 #endif
 
 }  // namespace

@@ -380,11 +380,8 @@ struct ConvTraits : IpTraitsBase {
     const int R = B * nz, act = P.act;
     ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // ivae/conv.py:81
     ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.cols, W.hcv, W.inp, B, act, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, 800, W.inp, 512, 512, packed + K.fc4i_f, params + P.fc4.b, W.rb, st));   // image half of fc4, once per image
-    {
-      LinArgs A{}; A.rowbias = W.rb; A.rowbias_ld = 800; A.rows_per_group = nz; A.Y = W.t1; A.ldY = 800;
-      ARDAE_TRY(lin1(EPI_ACT, act, R, 800, noise, P.nd, P.nd, packed + K.fc4n_f, A, st));
-    }
+    // fc4 on cat[h3 | noise]: the image half once per image
+    ARDAE_TRY(cat_fwd(act, B, nz, 800, W.inp, 512, packed + K.fc4i_f, params + P.fc4.b, noise, P.nd, packed + K.fc4n_f, W.rb, W.t1, st));
     return dense_fwd(ACT_NONE, R, P.zd, W.t1, 800, 800, packed + K.fc5_f, params + P.fc5.b, W.z, st);
   }
   static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {

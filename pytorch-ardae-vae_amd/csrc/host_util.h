@@ -1,6 +1,7 @@
 // Host-side helpers shared by the model families (model / convmodel / auxmodel / resmodel .hip) and cdae.hip: the bump
 // allocator that carves a workspace arena, one-/two-source linear launches and the dense-layer calls written with them, the
-// list of weight-gradient problems a backward pass hands to launch_wgrad_batch, the list of weight panels a network's packed
+// list of weight-gradient problems a backward pass hands to launch_wgrad_batch, the Linear on a concat whose first half is
+// per image (forward, backward-data, weight-gradient problems), the list of weight panels a network's packed
 // buffer is made of, and what every model family is made of (the Family table row, its sizing / pack triple, the prologue of
 // an entry point).
 #pragma once
@@ -166,6 +167,32 @@ struct WgradList {
     return 0;
   }
 };
+
+// Linear on cat[ctx | s] -> [B rpg, n]: ctx [B, cw], the first cw columns of the weight, is per image - its product (+ the bias) is made once as the row
+// bias rb [B, n], which the s half's launch on the rows s [B rpg, sd] adds to each group of rpg rows.  wp_*: the forward panels of the two halves.
+inline int cat_fwd(int act, int B, int rpg, int n, const float* ctx, int cw, const float* wp_ctx, const float* bias, const float* s, int sd, const float* wp_s,
+                   float* rb, float* y, hipStream_t st) {
+  ARDAE_TRY(dense_fwd(ACT_NONE, B, n, ctx, cw, cw, wp_ctx, bias, rb, st));
+  LinArgs A{}; A.Y = y; A.ldY = n; A.rowbias = rb; A.rowbias_ld = n; A.rows_per_group = rpg;
+  return lin1(EPI_ACT, act, B * rpg, n, s, sd, sd, wp_s, A, st);
+}
+// its backward-data from dpre [M, n] = d(pre-activation), one row per image: ds [M, sd] = dpre Ws (+ qs), then dctx [M, cw] = dpre Wc (+ qc) unless dctx
+// is null (a ctx that takes no gradient).  q: what else arrives there; the output must not be its q.  wb_*: the backward panels.
+inline int cat_bwd(int M, int n, const float* dpre, int sd, const float* wb_s, const float* qs, float* ds, int cw, const float* wb_ctx, const float* qc,
+                   float* dctx, hipStream_t st) {
+  auto half = [&](int k, const float* wb, const float* q, float* y) {
+    if (q) return dense_bwd(ACT_NONE, M, k, dpre, n, wb, q, y, st, q);      // act' == 1: S is only a placeholder
+    return dense_fwd(ACT_NONE, M, k, dpre, n, n, wb, nullptr, y, st);
+  };
+  ARDAE_TRY(half(sd, wb_s, qs, ds));
+  return dctx ? half(cw, wb_ctx, qc, dctx) : 0;
+}
+// its two weight-gradient problems on M rows (one per image): the s half (+ bias), then the ctx half
+inline void cat_wgrads(WgradList& wl, int M, const Lin& l, int cw, const float* dpre, const float* s, const float* ctx) {
+  const int sd = l.in - cw;
+  wl.push(M, l.out, sd, dpre, s, sd, wl.g(l.w + cw), l.in, wl.g(l.b));
+  wl.push(M, l.out, cw, dpre, ctx, cw, wl.g(l.w), l.in, nullptr);
+}
 
 // the caller's noise, or (null: a std = 0 pass, the reference multiplies its draw by 0) the n floats at `zero`, filled with zeros
 inline int noise_or_zero(const float*& noise, float* zero, size_t n, hipStream_t st) {

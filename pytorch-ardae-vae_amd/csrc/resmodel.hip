@@ -957,9 +957,7 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
       } else {
         const Lin& l = o.l; const LinPk& k = hk.lk;
         if (o.concat) {
-          ARDAE_TRY(dense_fwd(ACT_NONE, B, o.out, W.inp, P.cdim, P.cdim, packed + k.fi, params + l.b, u.rba, st));
-          { LinArgs A{}; A.rowbias = u.rba; A.rowbias_ld = o.out; A.rows_per_group = nz; A.Y = out; A.ldY = o.out;
-            ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, o.out, noise, P.nd, P.nd, packed + k.fn, A, st)); }
+          ARDAE_TRY(cat_fwd(ACT_NONE, B, nz, o.out, W.inp, P.cdim, packed + k.fi, params + l.b, noise, P.nd, packed + k.fn, u.rba, out, st));
         } else {
           ARDAE_TRY(dense_fwd(ACT_NONE, R, o.out, x, o.in, o.in, packed + k.f, params + l.b, out, st));
         }
@@ -976,9 +974,7 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
   // clipped: z0 = mu0 + (std exp(lv0 / 2) + 1) eps0; the std = 0 pass (noise = zeros) takes its unscaled draw from raw0 (none: z0 = mu0)
   if (P.clipped && !(std0 && !raw0)) ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, noise, ldn, R, P.nd, nz, W.z0, st, 1.f, std0 ? raw0 : nullptr, P.nd));
   else ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, noise, ldn, R, P.nd, nz, W.z0, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.inp, P.cdim, P.cdim, packed + K.efc.fi, params + P.efc.b, W.rbh, st));
-  { LinArgs A{}; A.rowbias = W.rbh; A.rowbias_ld = P.cdim; A.rows_per_group = nz; A.Y = W.hh; A.ldY = P.cdim;
-    ARDAE_TRY(lin1(EPI_ACT, ACT_NONE, R, P.cdim, W.z0, P.nd, P.nd, packed + K.efc.fn, A, st)); }
+  ARDAE_TRY(cat_fwd(ACT_NONE, B, nz, P.cdim, W.inp, P.cdim, packed + K.efc.fi, params + P.efc.b, W.z0, P.nd, packed + K.efc.fn, W.rbh, W.hh, st));
   RES_LAUNCH(act_inplace_kernel, (int64_t)R * P.cdim, W.hh, (int)ACT_ELU, (int64_t)R * P.cdim);
   if (hidden_out) ARDAE_TRY(launch_copy(W.hh, (size_t)R * P.cdim, hidden_out, st));
   ARDAE_TRY(dense_fwd(ACT_NONE, R, P.zd, W.hh, P.cdim, P.cdim, packed + K.mu.f, params + P.mu.b, W.mu, st));
@@ -1324,9 +1320,9 @@ struct ResVaeTraits {
 //     decode       kind 12's decoder, Bernoulli reconstruction rows
 //   losses = {mean_b(recon_b + beta (kld_b + aux_kld_b)), mean recon, mean (kld + aux_kld)}
 //   (the ctx half of Fe / Fr enters as a row bias, computed once per image: the same code serves the evaluation's k rows per image)
-// Backward (c = loss_scale / B), every reparameterisation and both KLs in closed form as csrc/auxvae.hip's: the reconstruction seed and the decoder; the
-// pair KL's seed; aux_decode back into its z columns (dz = the decoder's + the auxiliary decoder's) and into ctx; the head's seed; encode back into z0 and
-// ctx; the first head's seed; aux_encode back into ctx - d ctx is the SUM of the three, made before the trunk's backward.  The ten plain-Linear weight
+// Forward, backward, encode_stats, the evaluation passes and the workspace sizes are csrc/auxvae.h's bodies over AuxResVaeTraits; the backward's seeds
+// and their order are aux_vae_backward's, and the traits' three hooks carry d ctx between them: aux_decode back into its z columns and into ctx, encode
+// back into z0 and ctx, aux_encode back into ctx - d ctx is the SUM of the three, made before the trunk's backward.  The ten plain-Linear weight
 // gradients go out as one list; the weight-normalised operators' block by block through wn_backward_kernel, as kind 12's.
 // The names csrc/auxvae.h's bodies read, over the shared layout
 struct AuxResLayout : ResLayout {
@@ -1340,24 +1336,15 @@ struct AuxResPacked : ResPacked {
 };
 using AuxResEntry = Entry<AuxResLayout, AuxResPacked, ResWs>;
 
-// h [B rpg, c] = ELU(F [ctx | s] + f): the ctx half once per image as a row bias rb [B, c], shared by the image's rpg rows
-int ctx_cat_fwd(const ResLayout& P, const Lin& l, const LinPk& k, const float* params, const float* packed, int B, int rpg, const float* ctx, const float* s,
-                float* rb, float* h, hipStream_t st) {
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, ctx, P.cdim, P.cdim, packed + k.fi, params + l.b, rb, st));
-  LinArgs A{}; A.Y = h; A.ldY = P.cdim; A.rowbias = rb; A.rowbias_ld = P.cdim; A.rows_per_group = rpg;
-  return lin1(EPI_ACT, ACT_ELU, B * rpg, P.cdim, s, l.in - P.cdim, l.in - P.cdim, packed + k.fn, A, st);
-}
-
-// The evaluation pass (mode 4): B images x k samples, R = B k rows.  The trunk runs once (eval_prepare); the auxiliary decoder reuses encode.fc's row
-// buffer and row bias.
-struct AuxResEvalWs {
+// The evaluation pass (mode 4): the trunk's buffers in front of the shared rows; the trunk runs once, in stage 2
+struct AuxResEvalWs : AuxEvalRows {
   ResWs T;                                   // x2, the trunk's block buffers, flat; T.inp = ctx [B, c]
-  float *rb, *z0, *t, *mu, *lv, *mup, *lvp;
-  double* acc;                               // the row's log-density so far [R]
 };
 
+// What the bodies of csrc/auxvae.h need to know of kind 19.  Linear on cat[ctx | s]: cat_fwd / cat_bwd / cat_wgrads (host_util.h) at width c.
 struct AuxResVaeTraits {
   using Layout = AuxResLayout; using Packed = AuxResPacked; using Entry = AuxResEntry;
+  using Grads = GradMap;      // built before the decoder's backward, used again by the trunk's
   static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, 1, mode); }
   // encode.reparam on h [B, c]: kind 12's head and policy
   static GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f, false, false}; }
@@ -1365,125 +1352,88 @@ struct AuxResVaeTraits {
   static GaussBufs bufs(const ResWs& W) {
     return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dz, W.dmu, W.dlv};
   }
+  // the trunk and aux_encode's two Linears on ctx: mu0, lv0 (no clip)
+  static int stats_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, float* mu0, float* lv0, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, mu0, st));
+    return dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, lv0, st);
+  }
   // (the two draws are in W.eps0 / W.epsz: aux_vae_forward)  the trunk, aux_encode, z0, encode.fc
   static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
     auto& [P, K, ws, W] = e;
-    ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, W.mu0, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, W.lv0, st));
+    ARDAE_TRY(stats_fwd(e, params, packed, x, B, W.mu0, W.lv0, st));
     ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
-    return ctx_cat_fwd(P, P.efc, K.efc, params, packed, B, 1, W.inp, W.z0, W.rbh, W.hh, st);
+    return cat_fwd(ACT_ELU, B, 1, P.cdim, W.inp, P.cdim, packed + K.efc.fi, params + P.efc.b, W.z0, P.nd, packed + K.efc.fn, W.rbh, W.hh, st);
   }
   // the auxiliary decoder on [ctx | z] and the pair KL, added into the head's KL rows; then the decoder (unfused: the backward reads its columns)
   static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
     auto& [P, K, ws, W] = e;
-    ARDAE_TRY(ctx_cat_fwd(P, P.rfc, K.rfc, params, packed, B, 1, W.inp, W.z, W.rb2, W.hr, st));
+    ARDAE_TRY(cat_fwd(ACT_ELU, B, 1, P.cdim, W.inp, P.cdim, packed + K.rfc.fi, params + P.rfc.b, W.z, P.zd, packed + K.rfc.fn, W.rb2, W.hr, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.hr, P.cdim, P.cdim, packed + K.mup.f, params + P.mup.b, W.mup, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.hr, P.cdim, P.cdim, packed + K.lvp.f, params + P.lvp.b, W.lvp, st));
     ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
     return ardae::decoder_fwd(P, K, params, packed, W.z, B, W, nullptr, st);
   }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.P, e.W, params, packed, g, beta); }
+  static int decoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, B, gm, st); }
+  // d ctx is the SUM of the three networks' parts, made before the trunk's backward: the auxiliary decoder's goes to dB0 (and dz = W.dzq + dhr Wz) ...
+  static int aux_decoder_bwd(Entry& e, const float* packed, int B, GradMap&, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(dense_bwd2(ACT_ELU, B, P.cdim, W.dmup, packed + K.mup.b, W.dlvp, packed + K.lvp.b, P.nd, W.hr, W.dhr, st));
+    return cat_bwd(B, P.cdim, W.dhr, P.zd, packed + K.rfc.bn, W.dzq, W.dz, P.cdim, packed + K.rfc.bi, nullptr, W.dB0, st);
+  }
+  // ... encode.fc's joins it: dB1 = dB0 + dhh Wc ...
+  static int encode_fc_bwd(Entry& e, const float* packed, int B, GradMap&, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(dense_bwd2(ACT_ELU, B, P.cdim, W.dmu, packed + K.mu.b, W.dlv, packed + K.lv.b, P.zd, W.hh, W.dhh, st));
+    return cat_bwd(B, P.cdim, W.dhh, P.nd, packed + K.efc.bn, nullptr, W.dz0, P.cdim, packed + K.efc.bi, W.dB0, W.dB1, st);
+  }
+  // ... and the first head's two Linears (there is no clip in this family) go straight back into ctx.  The ten plain-Linear weight gradients, written
+  // in place (no weight norm), go out as one list; the weight-normalised operators' block by block in the trunk's backward.
+  static int aux_encoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int cd = P.cdim;
+    { LinArgs A{}; A.Y = W.dinp; A.ldY = cd;
+      ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, cd, W.dmu0, P.nd, P.nd, packed + K.mu0.b, W.dlv0, P.nd, P.nd, packed + K.lv0.b, A, st)); }
+    ARDAE_TRY(launch_axpy(W.dB1, (int64_t)B * cd, 1.f, W.dinp, st));
+    WgradList wl(gm.grads, gm.grads_beta);
+    wl.push(B, P.zd, cd, W.dmu, W.hh, cd, wl.g(P.mu.w), cd, wl.g(P.mu.b));
+    wl.push(B, P.zd, cd, W.dlv, W.hh, cd, wl.g(P.lv.w), cd, wl.g(P.lv.b));
+    cat_wgrads(wl, B, P.efc, cd, W.dhh, W.z0, W.inp);
+    wl.push(B, P.nd, cd, W.dmu0, W.inp, cd, wl.g(P.mu0.w), cd, wl.g(P.mu0.b));
+    wl.push(B, P.nd, cd, W.dlv0, W.inp, cd, wl.g(P.lv0.w), cd, wl.g(P.lv0.b));
+    wl.push(B, P.nd, cd, W.dmup, W.hr, cd, wl.g(P.mup.w), cd, wl.g(P.mup.b));
+    wl.push(B, P.nd, cd, W.dlvp, W.hr, cd, wl.g(P.lvp.w), cd, wl.g(P.lvp.b));
+    cat_wgrads(wl, B, P.rfc, cd, W.dhr, W.z, W.inp);
+    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+    return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
+  }
+  static void size_wgrads(Entry&, int) {}      // the carve has taken the weight-gradient scratch
   // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h)
   using EvalWs = AuxResEvalWs;
   static void carve_eval(const AuxResLayout& P, const AuxResPacked&, Bump& ws, int B, int k, AuxResEvalWs& W) {
-    const size_t b = (size_t)B, R = b * (size_t)k;
-    W.T.x2 = ws.take(b * 784);
+    W.T.x2 = ws.take((size_t)B * 784);
     W.T.tb.resize(P.trunk.size());
     for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.T.tb[i], false);
-    W.T.flat = ws.take(b * 512);
+    W.T.flat = ws.take((size_t)B * 512);
     W.T.inp = W.T.tb.back().out;
-    W.rb = ws.take(b * P.cdim);
-    W.z0 = ws.take(R * P.nd); W.t = ws.take(R * P.cdim);
-    W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
-    W.acc = reinterpret_cast<double*>(ws.take(2 * R));
+    W.carve_rows(ws, B, k, P.nd, P.zd, P.cdim, 1);
   }
-  static int eval_prepare(const AuxResLayout& P, const float* x, int B, AuxResEvalWs& W, const float*& xs, hipStream_t st) {
+  static int eval_prepare(const AuxResLayout&, const float* x, int, AuxResEvalWs&, const float*& xs, hipStream_t) {
     xs = x;
-    (void)P; (void)B; (void)W; (void)st;
     return 0;
   }
   // stage 2 runs the trunk (params and packed are first at hand here); stage 3 reads its ctx again
   static int eval_hidden(const AuxResLayout& P, const AuxResPacked& K, const float* params, const float* packed, int stage, const float* xs, const float* s,
                          int B, int k, AuxResEvalWs& W, const float*& hid, hipStream_t st) {
-    hid = W.t;
+    const Lin& l = stage == 2 ? P.efc : P.rfc;
+    const LinPk& c = stage == 2 ? K.efc : K.rfc;
+    hid = W.t[1];
     if (stage == 2) ARDAE_TRY(trunk_fwd(P, K, params, packed, xs, B, W.T, st));
-    return ctx_cat_fwd(P, stage == 2 ? P.efc : P.rfc, stage == 2 ? K.efc : K.rfc, params, packed, B, k, W.T.inp, s, W.rb, W.t, st);
+    return cat_fwd(ACT_ELU, B, k, P.cdim, W.T.inp, P.cdim, packed + c.fi, params + l.b, s, l.in - P.cdim, packed + c.fn, W.rb, W.t[1], st);
   }
 };
-
-size_t auxresvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  const AuxResLayout P(d);
-  const AuxResPacked K(P);
-  Bump ws;
-  if (mode == 4) {
-    if ((int64_t)B * nz >= (int64_t)1 << 30) return 0;
-    AuxResEvalWs W;
-    AuxResVaeTraits::carve_eval(P, K, ws, B, nz, W);
-    return ws.off;
-  }
-  if (mode != 2 && (nz != 1 || (mode != 0 && mode != 1))) return 0;      // one draw per image; there is no sampler pair
-  ResWs W;
-  carve(P, K, ws, mode == 2 ? B * nz : B, 1, mode, W);
-  return ws.off;
-}
-
-int auxresvae_backward(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, DevFloat beta, float loss_scale,
-                       float* workspace, size_t wsf, float* grads, float grads_beta, hipStream_t st) {
-  AuxResEntry entry(d, workspace, wsf, B, 1, 1);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
-  const float c = loss_scale / (float)B;
-  const int cd = P.cdim;
-  const int64_t n0 = (int64_t)B * P.nd;
-  GradMap gm = grad_map(entry.P, entry.W, params, packed, grads, grads_beta);
-  // reconstruction gradients at the logits (beta 0, no seed: dzq gets the zeros of the switched-off energy), the decoder down to W.dzq
-  ARDAE_TRY(launch_vae_loss(0, W.db[6].out, nullptr, x, W.z, B, 1, 784, P.zd, 0.f, 1, c, nullptr, W.rec_row, W.pri_row, W.dlogit, nullptr, W.dzq, st));
-  ARDAE_TRY(decoder_bwd(P, K, packed, W, B, gm, st));
-  // the pair KL's seed at the auxiliary decoder's head and at the first head; the auxiliary decoder back into its z columns (dz = W.dzq + dhr Wz) and
-  // into ctx (dB0)
-  ARDAE_TRY(launch_pair_kld_seed(W.mu0, W.lv0, W.mup, W.lvp, n0, c, beta, W.dmup, W.dlvp, W.dmu0, W.dlv0, st));
-  ARDAE_TRY(dense_bwd2(ACT_ELU, B, cd, W.dmup, packed + K.mup.b, W.dlvp, packed + K.lvp.b, P.nd, W.hr, W.dhr, st));
-  ARDAE_TRY(dense_bwd(ACT_NONE, B, P.zd, W.dhr, cd, packed + K.rfc.bn, W.dzq, W.dz, st, W.dzq));      // act' == 1: S is only a placeholder
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, cd, W.dhr, cd, cd, packed + K.rfc.bi, nullptr, W.dB0, st));
-  // the z head, encode.fc back into its z0 columns and into ctx (dB1 = dB0 + dhh Wc)
-  ARDAE_TRY(gauss_head_seed(W.dz, W.z, W.mu, W.lv, (int64_t)B * P.zd, c, beta, W.dmu, W.dlv, st));
-  ARDAE_TRY(dense_bwd2(ACT_ELU, B, cd, W.dmu, packed + K.mu.b, W.dlv, packed + K.lv.b, P.zd, W.hh, W.dhh, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.dhh, cd, cd, packed + K.efc.bn, nullptr, W.dz0, st));
-  ARDAE_TRY(dense_bwd(ACT_NONE, B, cd, W.dhh, cd, packed + K.efc.bi, W.dB0, W.dB1, st, W.dB0));
-  // the first head: the reparameterisation through z0 joins the pair KL's part (there is no clip in this family); its two Linears back into ctx
-  ARDAE_TRY(launch_z0_seed(W.dz0, W.z0, W.mu0, n0, W.dmu0, W.dlv0, st));
-  { LinArgs A{}; A.Y = W.dinp; A.ldY = cd;
-    ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, cd, W.dmu0, P.nd, P.nd, packed + K.mu0.b, W.dlv0, P.nd, P.nd, packed + K.lv0.b, A, st)); }
-  ARDAE_TRY(launch_axpy(W.dB1, (int64_t)B * cd, 1.f, W.dinp, st));                                  // d ctx, all three contributions
-  // the plain Linears' weight gradients, written in place (no weight norm)
-  WgradList wl(gm.grads, gm.grads_beta);
-  const float* ctx = W.inp;
-  auto cat = [&](const Lin& l, const float* dpre, const float* s) {      // cat[ctx, s]: the s half (+ bias), then the ctx half
-    wl.push(B, cd, l.in - cd, dpre, s, l.in - cd, wl.g(l.w + cd), l.in, wl.g(l.b));
-    wl.push(B, cd, cd, dpre, ctx, cd, wl.g(l.w), l.in, nullptr);
-  };
-  wl.push(B, P.zd, cd, W.dmu, W.hh, cd, wl.g(P.mu.w), cd, wl.g(P.mu.b));
-  wl.push(B, P.zd, cd, W.dlv, W.hh, cd, wl.g(P.lv.w), cd, wl.g(P.lv.b));
-  cat(P.efc, W.dhh, W.z0);
-  wl.push(B, P.nd, cd, W.dmu0, W.inp, cd, wl.g(P.mu0.w), cd, wl.g(P.mu0.b));
-  wl.push(B, P.nd, cd, W.dlv0, W.inp, cd, wl.g(P.lv0.w), cd, wl.g(P.lv0.b));
-  wl.push(B, P.nd, cd, W.dmup, W.hr, cd, wl.g(P.mup.w), cd, wl.g(P.mup.b));
-  wl.push(B, P.nd, cd, W.dlvp, W.hr, cd, wl.g(P.lvp.w), cd, wl.g(P.lvp.b));
-  cat(P.rfc, W.dhr, W.z);
-  ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-  return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
-}
-
-// mu0, lv0 of q(z0 | x): what the evaluation needs first
-int auxresvae_encode_stats(const ardae_model_desc& d, const float* params, const float* packed, const float* x, int B, float* workspace, size_t wsf,
-                           float* mu_out, float* lv_out, hipStream_t st) {
-  AuxResEntry entry(d, workspace, wsf, B, 1, 0);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "vae_encode_stats: internal workspace accounting error");
-  ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-  ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, mu_out, st));
-  return dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, lv_out, st);
-}
 
 int auxresvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
                      hipStream_t st, float*) {
@@ -1501,11 +1451,9 @@ const Family RES_FAMILY = ip_family<ResTraits>(res_pack);
 static const GaussFamily RESVAE_GAUSS = gauss_family<ResVaeTraits>();
 const Family RESVAE_FAMILY = {resvae_desc_check, no_caps, family_param_floats<ResLayout, ResPacked>, family_packed_floats<ResLayout, ResPacked>,
                               resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward, vae_no_backward, &RESVAE_GAUSS};
-static const GaussFamily AUXRESVAE_GAUSS = {gauss_vae_head_fused_ok<AuxResVaeTraits>, aux_vae_forward<AuxResVaeTraits>, auxresvae_backward,
-                                            auxresvae_encode_stats, gauss_vae_head<AuxResVaeTraits>, aux_vae_elbo_rows<AuxResVaeTraits>,
-                                            aux_vae_iwae_draw<AuxResVaeTraits>};
+static const GaussFamily AUXRESVAE_GAUSS = aux_gauss_family<AuxResVaeTraits>();
 const Family AUXRESVAE_FAMILY = {auxresvae_desc_check, no_caps, family_param_floats<AuxResLayout, AuxResPacked>,
-                                 family_packed_floats<AuxResLayout, AuxResPacked>, auxresvae_workspace_floats, res_pack, vae_no_encode,
+                                 family_packed_floats<AuxResLayout, AuxResPacked>, aux_workspace_floats<AuxResVaeTraits>, res_pack, vae_no_encode,
                                  auxresvae_decode, vae_no_forward, vae_no_backward, &AUXRESVAE_GAUSS};
 #endif
 
