@@ -704,6 +704,15 @@ int ardae_sample_logvar(const float* z, int B, int nz, int zd, float eps, float*
  * order). */
 int ardae_hist2d(const float* pts, int64_t n, int64_t row_stride, int nslots, int64_t slot_stride, int col_x, int col_y, double lo, double hi,
                  int bins, int64_t* counts, void* stream);
+/* ardae_hist2d for tables wider than one workgroup's LDS: the 256-bin heat maps of the scripts' `''' test visualize '''` blocks
+ * (ivae_ardae.py:1224-1290, vae.py:677-720).  Same arguments, same contract in every respect above (np.linspace's edges, the comparison in double,
+ * v == hi in the last bin, outside / +-inf / NaN dropped, counts [nslots, bins, bins] ADDED to, first index x, integer sums), with 1 <= bins <= 512.
+ * The table is cut into bands of 16384 / bins x-bin rows (64 KiB of 32-bit counters: 2 bands at 129 bins, 4 at 256, 16 at 512); a workgroup owns one
+ * (share of the points, slot, band), looks up the y bin of the points whose x bin falls into its band and flushes its non-zero cells with 64-bit
+ * atomic adds - every point is counted by exactly one band, and the points are read once per band.  For bins <= 128 it is ardae_hist2d's result at
+ * ardae_hist2d's cost (one band); callers with such tables call ardae_hist2d. */
+int ardae_hist2d_wide(const float* pts, int64_t n, int64_t row_stride, int nslots, int64_t slot_stride, int col_x, int col_y, double lo, double hi,
+                      int bins, int64_t* counts, void* stream);
 
 
 /* ---- scalar log channel + static-binarised batches ------------------------------------------------

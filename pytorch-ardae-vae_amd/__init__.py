@@ -17,6 +17,9 @@ Fused path:
     MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE, MNISTResConvAuxVAE, VaeEngine, VaeConfig, GaussianIwaeEvaluator -- the Gaussian-posterior baselines of the reference's second trainer, vae.py
                                  (`--model mnist` / `--model toy` / `--model conv` / `--model resconv` / `--model auxmnist` / `--model auxtoy` / `--model auxconv`): drop-in modules, one iteration of its loop as one captured unit with the posterior
                                  draw, the reparameterisation and the analytic KL fused into the head kernel, and its evaluate_iws under the analytic posterior
+    GaussianDiagnostics, VaeEngine.diagnostics, PosteriorDiagnostics.final_pass -- vae.py's visualisation block for the Gaussian baselines (2-D histograms
+                                 of the latents of model(x), data | recon | gen of the 2-D problems; no host synchronisation) and both scripts' last
+                                 block, the 256-bin heat maps of 1 000 000 points, through ardae_hist2d_wide (tables of up to 512 bins, cut into bands)
     ScalarLog                 -- the reference's per-step scalars through a device ring buffer (no host sync in the step)
 The compute is libardae_hip.so (hand-written HIP for gfx950, C ABI in include/ardae_hip.h); there is no fallback.
 """
@@ -33,4 +36,5 @@ from .fit import ArdaeFitEngine, FitConfig  # noqa: F401
 from .iwae import IwaeEvaluator, plan_chunks  # noqa: F401
 from .diagnostics import PosteriorDiagnostics  # noqa: F401
 from .vae import GaussianIwaeEvaluator, VaeConfig, VaeEngine  # noqa: F401
+from .vae_diagnostics import GaussianDiagnostics  # noqa: F401
 from .scalar_log import ScalarLog  # noqa: F401

@@ -4,7 +4,9 @@
 //   * sample_logvar_kernel          log(var(z, dim=1) + eps) of an image's nz sampler rows (ivae_ardae.py:956-957), centred two-pass in fp64
 //   * hist2d_kernel                 np.histogram2d (utils/visualization.py:193-204) of two columns of a strided point set, several slots
 //                                   per launch: one bins x bins table of 32-bit counters per workgroup in LDS, flushed with 64-bit global adds
-// All three are stream-ordered, read nothing on the host and keep no state.  The histogram's sums are integers, so the order of the
+//   * hist2d_wide_kernel            the same histogram for tables wider than one workgroup's LDS (the 256-bin heat maps of the final pass,
+//                                   ivae_ardae.py:1224-1290, vae.py:677-720): the table is cut into bands of x-bin rows, a workgroup owns one band
+// All four are stream-ordered, read nothing on the host and keep no state.  The histogram's sums are integers, so the order of the
 // atomic adds does not show in the result; the other two use no atomics and a fixed order.
 #include "ardae_hip.h"
 #include "common.h"
@@ -15,6 +17,8 @@ namespace {
 
 constexpr int DG_THREADS = 256;
 constexpr int HIST_MAX_BINS = 128;                         // 128 x 128 x 4 B = 64 KiB of LDS per workgroup
+constexpr int HIST_WIDE_MAX_BINS = 512;                    // hist2d_wide_kernel: bands of x-bin rows, each at most ...
+constexpr int HIST_BAND_CELLS = HIST_MAX_BINS * HIST_MAX_BINS;      // ... 16384 cells: the same 64 KiB of LDS, two workgroups per CU
 constexpr int64_t HIST_POINTS_PER_WG = 8192;               // a workgroup's share while the grid stays below HIST_MAX_WGS
 constexpr int64_t HIST_MAX_WGS = 2048;                     // per slot; beyond it the shares grow ...
 constexpr int64_t HIST_MAX_SHARE = 0x7fffffff;             // ... up to what a 32-bit bin can count
@@ -128,6 +132,45 @@ __global__ __launch_bounds__(DG_THREADS) void hist2d_kernel(const float* __restr
   }
 }
 
+// The table of hist2d_kernel cut into bands of `band_rows` x-bin rows (band_rows * bins <= HIST_BAND_CELLS): blockIdx.z = band, and a
+// workgroup counts the points of its share whose x bin falls into its band - every point is counted by exactly one band, the y bin is
+// looked up for those points only.  A dropped x (bin -1) lies in no band.  Shares, counters and the flush are hist2d_kernel's.
+__global__ __launch_bounds__(DG_THREADS) void hist2d_wide_kernel(const float* __restrict__ pts, int64_t n, int64_t row_stride, int64_t slot_stride,
+                                                                 int col_x, int col_y, double lo, double hi, double step, int bins, int band_rows,
+                                                                 int64_t share, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int table[HIST_BAND_CELLS];
+  const int t = threadIdx.x;
+  const int r0 = (int)blockIdx.z * band_rows, rows = min(band_rows, bins - r0), cells = rows * bins;
+  for (int i = t; i < cells; i += DG_THREADS) table[i] = 0u;
+  __syncthreads();
+  const int64_t i0 = (int64_t)blockIdx.x * share, i1 = min(n, i0 + share);
+  const float* base = pts + (int64_t)blockIdx.y * slot_stride;
+  for (int64_t i = i0 + t; i < i1; i += DG_THREADS) {
+    const float* p = base + i * row_stride;
+    const int r = hist_bin(p[col_x], bins, lo, hi, step) - r0;
+    if (r < 0 || r >= rows) continue;
+    const int by = hist_bin(p[col_y], bins, lo, hi, step);
+    if (by >= 0) atomicAdd(&table[r * bins + by], 1u);
+  }
+  __syncthreads();
+  unsigned long long* out = counts + ((size_t)blockIdx.y * bins + r0) * bins;
+  for (int i = t; i < cells; i += DG_THREADS) {
+    const unsigned int c = table[i];
+    if (c) atomicAdd(&out[i], (unsigned long long)c);
+  }
+}
+
+// the grid of both histogram kernels along the points: `wgs` shares of `share` points, no share beyond what a 32-bit bin can count
+static void hist_shares(int64_t n, int64_t* wgs, int64_t* share) {
+  *wgs = ceil_div64(n, HIST_POINTS_PER_WG);
+  if (*wgs > HIST_MAX_WGS) *wgs = HIST_MAX_WGS;
+  *share = ceil_div64(n, *wgs);
+  if (*share > HIST_MAX_SHARE) {
+    *share = HIST_MAX_SHARE;
+    *wgs = ceil_div64(n, *share);
+  }
+}
+
 }  // namespace
 }  // namespace ardae
 
@@ -167,17 +210,34 @@ int ardae_hist2d(const float* pts, int64_t n, int64_t row_stride, int nslots, in
                   "hist2d: need row_stride >= 1, slot_stride >= 0, col_x >= 0, col_y >= 0 (got %lld, %lld, %d, %d)", (long long)row_stride,
                   (long long)slot_stride, col_x, col_y);
   ARDAE_CHECK_ARG(pts && counts, "hist2d: pts and counts must not be NULL");
-  int64_t wgs = ceil_div64(n, HIST_POINTS_PER_WG);
-  if (wgs > HIST_MAX_WGS) wgs = HIST_MAX_WGS;
-  int64_t share = ceil_div64(n, wgs);
-  if (share > HIST_MAX_SHARE) {
-    share = HIST_MAX_SHARE;
-    wgs = ceil_div64(n, share);
-  }
+  int64_t wgs, share;
+  hist_shares(n, &wgs, &share);
   ARDAE_CHECK_ARG(wgs <= INT32_MAX, "hist2d: n=%lld points are more than one launch takes", (long long)n);
   const double step = (hi - lo) / (double)bins;                 // np.linspace: delta / div
   hipLaunchKernelGGL(hist2d_kernel, dim3((unsigned)wgs, (unsigned)nslots), dim3(DG_THREADS), 0, (hipStream_t)stream, pts, n, row_stride, slot_stride,
                      col_x, col_y, lo, hi, step, bins, share, reinterpret_cast<unsigned long long*>(counts));
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int ardae_hist2d_wide(const float* pts, int64_t n, int64_t row_stride, int nslots, int64_t slot_stride, int col_x, int col_y, double lo, double hi,
+                      int bins, int64_t* counts, void* stream) {
+  ARDAE_CHECK_ARG(bins >= 1 && bins <= HIST_WIDE_MAX_BINS, "hist2d_wide: need 1 <= bins <= 512 (got bins=%d)", bins);
+  ARDAE_CHECK_ARG(hi > lo && lo > -INFINITY && hi < INFINITY, "hist2d_wide: need finite lo < hi (got lo=%g, hi=%g)", lo, hi);
+  ARDAE_CHECK_ARG(n > 0 && nslots >= 1 && nslots <= 65535, "hist2d_wide: need n > 0 and 1 <= nslots <= 65535 (got n=%lld, nslots=%d)", (long long)n,
+                  nslots);
+  ARDAE_CHECK_ARG(row_stride >= 1 && slot_stride >= 0 && col_x >= 0 && col_y >= 0,
+                  "hist2d_wide: need row_stride >= 1, slot_stride >= 0, col_x >= 0, col_y >= 0 (got %lld, %lld, %d, %d)", (long long)row_stride,
+                  (long long)slot_stride, col_x, col_y);
+  ARDAE_CHECK_ARG(pts && counts, "hist2d_wide: pts and counts must not be NULL");
+  int64_t wgs, share;
+  hist_shares(n, &wgs, &share);
+  ARDAE_CHECK_ARG(wgs <= INT32_MAX, "hist2d_wide: n=%lld points are more than one launch takes", (long long)n);
+  const int band_rows = min(bins, HIST_BAND_CELLS / bins);      // 129 bins: 127 rows, 2 bands; 256: 64 rows, 4 bands; 512: 32 rows, 16 bands
+  const int nbands = (bins + band_rows - 1) / band_rows;
+  const double step = (hi - lo) / (double)bins;                 // np.linspace: delta / div
+  hipLaunchKernelGGL(hist2d_wide_kernel, dim3((unsigned)wgs, (unsigned)nslots, (unsigned)nbands), dim3(DG_THREADS), 0, (hipStream_t)stream, pts, n,
+                     row_stride, slot_stride, col_x, col_y, lo, hi, step, bins, band_rows, share, reinterpret_cast<unsigned long long*>(counts));
   ARDAE_LAUNCH_CHECK();
   return 0;
 }

@@ -9,6 +9,9 @@ s = 0, 0.1, 0.5, 0.8, `model(x)` and `model.generate`, copies every latent to th
     data_histograms     data | reconstruction | generation of the 2-D problems (Gaussian decoders), three ardae_hist2d per chunk
     logvar_qz           a sampler pass with nz rows per image + ardae_sample_logvar
     run                 the reference's pass: all three, ONE host synchronisation
+    final_pass          the script's last block, `''' test visualize '''` (ivae_ardae.py:1224-1290): the two histograms at 256 bins through
+                        ardae_hist2d_wide, whose table is cut into bands of x-bin rows (up to 512 bins)
+The Gaussian-posterior baselines of vae.py have their own class on the same kernels: vae_diagnostics.GaussianDiagnostics.
 
 Plots, image grids and the event file stay with the caller; these are the arrays they are drawn from.
 """
@@ -25,13 +28,42 @@ STDS = (None, 0.8, 0.5, 0.1, 0.0)                # the `alllatent` panel, left t
 TAG_MEAN, TAG_MEDIAN = "enc/logvar_qz/mean/step", "enc/logvar_qz/median/step"      # ivae_ardae.py:961-962, behind `{train_mode}/`
 
 
-def _check_range(lo, hi, bins):
+MAX_BINS_WIDE = 512                              # ardae_hist2d_wide cuts the table into bands of x-bin rows, one band per workgroup
+
+
+def _check_range(lo, hi, bins, max_bins=MAX_BINS, who=WHO):
     lo, hi, bins = float(lo), float(hi), int(bins)
-    if not 1 <= bins <= MAX_BINS:
-        raise ValueError(f"{WHO}: bins must be 1 .. {MAX_BINS} (got {bins}): the kernel keeps the table in one workgroup's LDS")
+    if not 1 <= bins <= max_bins:
+        why = "the kernel keeps the table in one workgroup's LDS" if max_bins == MAX_BINS else "ardae_hist2d_wide takes tables up to that width"
+        raise ValueError(f"{who}: bins must be 1 .. {max_bins} (got {bins}): {why}")
     if not (hi > lo and lo > float("-inf") and hi < float("inf")):
-        raise ValueError(f"{WHO}: the range needs finite lo < hi (got lo={lo}, hi={hi})")
+        raise ValueError(f"{who}: the range needs finite lo < hi (got lo={lo}, hi={hi})")
     return lo, hi, bins
+
+
+def _val_range(val):
+    """val -> (lo, hi): a half-width, or the pair itself"""
+    return val if isinstance(val, (tuple, list)) else (-float(val), float(val))
+
+
+def hist2d_lds(*args):
+    """ardae_hist2d: tables of up to MAX_BINS bins"""
+    L.call("ardae_hist2d", *args)
+
+
+def hist2d(pts, n, row_stride, nslots, slot_stride, col_x, col_y, lo, hi, bins, counts):
+    """The histogram entry point for tables of up to MAX_BINS_WIDE bins: ardae_hist2d where its table fits, ardae_hist2d_wide above."""
+    L.call("ardae_hist2d" if bins <= MAX_BINS else "ardae_hist2d_wide", pts, n, row_stride, nslots, slot_stride, col_x, col_y, lo, hi, bins, counts)
+
+
+def cached_buffers(cache, what, device, sizes):
+    """name -> float buffer of at least sizes[name] floats; kept in `cache` per `what` until a call needs a longer one."""
+    b = cache.get(what)
+    if b is None or b["device"] != device or any(k not in b or b[k].numel() < n for k, n in sizes.items()):
+        b = dict(device=device)
+        b.update({k: torch.empty(n, device=device, dtype=torch.float32) for k, n in sizes.items()})
+        cache[what] = b
+    return b
 
 
 class PosteriorDiagnostics:
@@ -97,13 +129,7 @@ class PosteriorDiagnostics:
         return plan_chunks(N, nz, lambda c: self.logvar_floats_per_chunk(c, nz), self.budget)
 
     def _buffers(self, what, device, sizes):
-        """name -> float buffer of at least sizes[name] floats; kept per `what` until a call needs a longer one."""
-        b = self._bufs.get(what)
-        if b is None or b["device"] != device or any(k not in b or b[k].numel() < n for k, n in sizes.items()):
-            b = dict(device=device)
-            b.update({k: torch.empty(n, device=device, dtype=torch.float32) for k, n in sizes.items()})
-            self._bufs[what] = b
-        return b
+        return cached_buffers(self._bufs, what, device, sizes)
 
     # ---- checks (all before the first launch) --------------------------------------------------------------------------------------
     def _check_x(self, x, what):
@@ -142,13 +168,16 @@ class PosteriorDiagnostics:
         z = model.encode(x_all, std=s), one slot per entry of `stds` (None: the plain pass, forward_hidden(x)); first index the bin of
         latent column 0.  val: 4 for the 2-D problems, 6 for the image models (ivae_ardae.py:1030,1049), or a pair (lo, hi).
         return_latents: -> (counts, latents [N, S, z_dim]).  Nothing is read back."""
+        return self._latent(x_all, stds, val, bins, noise, return_latents, MAX_BINS, hist2d_lds)
+
+    def _latent(self, x_all, stds, val, bins, noise, return_latents, max_bins, hist):
+        """latent_histograms with the caller's bin cap and histogram entry point"""
         m = self.model
         scales = self._scales(stds)
         S, W, zd = len(scales), m._noise_width, m.z_dim
         if val is None:
             val = 4.0 if self.gaussian else 6.0
-        lo, hi = (val if isinstance(val, (tuple, list)) else (-float(val), float(val)))
-        lo, hi, bins = _check_range(lo, hi, bins)
+        lo, hi, bins = _check_range(*_val_range(val), bins, max_bins)
         x, N = self._check_x(x_all, "x_all")
         if zd < 2:
             raise ValueError(f"{WHO}: a 2-D histogram needs z_dim >= 2 (got {zd})")
@@ -183,14 +212,14 @@ class PosteriorDiagnostics:
                 if self.stacked:
                     zs = bufs["zs"][:c * S * zd].view(c, S, zd)
                     L.call("ardae_model_encode", d, flat, packed, xc, rows, c, S, ws, ws.numel(), zs)
-                    L.call("ardae_hist2d", zs, c, S * zd, S, zd, 0, 1, lo, hi, bins, counts)
+                    hist(zs, c, S * zd, S, zd, 0, 1, lo, hi, bins, counts)
                     if return_latents:
                         latents[i0:i1].copy_(zs)
                 else:
                     zs = bufs["zs"][:S * c * zd].view(S, c, zd)                  # slot-major: every call writes its own [c, z] block
                     for s in range(S):
                         self._encode_slot(xc, rows, s, scales[s], bufs["slot"], ws, zs[s])
-                    L.call("ardae_hist2d", zs, c, zd, S, c * zd, 0, 1, lo, hi, bins, counts)
+                    hist(zs, c, zd, S, c * zd, 0, 1, lo, hi, bins, counts)
                     if return_latents:
                         latents[i0:i1].copy_(zs.permute(1, 0, 2))
         return (counts, latents) if return_latents else counts
@@ -218,12 +247,15 @@ class PosteriorDiagnostics:
         """counts [3, bins, bins] of the 2-D problems' data-recon-gen heat maps (ivae_ardae.py:1019-1021): slot 0 x, slot 1 the decoder
         sample of model(x) (a std = 1 latent), slot 2 the decoder sample of model.generate (z ~ N(0, I)); columns 0 and 1.  Four
         Philox offsets per call (sampler, decoder, z, decoder).  return_samples: -> (counts, recon [N, D], gen [N, D])."""
+        return self._data(x_all, val, bins, return_samples, MAX_BINS, hist2d_lds)
+
+    def _data(self, x_all, val, bins, return_samples, max_bins, hist):
+        """data_histograms with the caller's bin cap and histogram entry point"""
         m = self.model
         if not self.gaussian:
             raise NotImplementedError(f"{WHO}: data_histograms is for the Gaussian-decoder kinds (toy, auxtoy): {type(m).__name__} has a Bernoulli "
                                       "decoder, and the reference histograms data, reconstruction and generation for 2-D data only")
-        lo, hi = (val if isinstance(val, (tuple, list)) else (-float(val), float(val)))
-        lo, hi, bins = _check_range(lo, hi, bins)
+        lo, hi, bins = _check_range(*_val_range(val), bins, max_bins)
         x, N = self._check_x(x_all, "x_all")
         D, W, zd = m.input_dim, m._noise_width, m.z_dim
         if D < 2:
@@ -249,7 +281,7 @@ class PosteriorDiagnostics:
                 for per_image, offset in zip(blocks, enc_offsets):
                     L.call("ardae_philox_normal_at", noise[at:], c * per_image, seed, offset, None, i0 * per_image)
                     at += c * per_image
-                L.call("ardae_hist2d", xc, c, D, 1, 0, 0, 1, lo, hi, bins, counts[0])
+                hist(xc, c, D, 1, 0, 0, 1, lo, hi, bins, counts[0])
                 L.call("ardae_model_encode", d, flat, packed, xc, noise, c, 1, ws, ws.numel(), bufs["z"])
                 for slot, z, offset, out, keep in ((1, bufs["z"], dec_offset, bufs["xs"], recon), (2, bufs["zg"], gen_offset, bufs["xg"], gen)):
                     if slot == 2:
@@ -257,7 +289,7 @@ class PosteriorDiagnostics:
                     L.call("ardae_model_decode", d, flat, packed, z, c, ws, ws.numel(), bufs["mu"], bufs["lv"])
                     L.call("ardae_philox_normal_at", bufs["eps"], c * D, seed, offset, None, i0 * D)
                     L.call("ardae_gaussian_sample", bufs["mu"], bufs["lv"], bufs["eps"], c * D, out)
-                    L.call("ardae_hist2d", out, c, D, 1, 0, 0, 1, lo, hi, bins, counts[slot])
+                    hist(out, c, D, 1, 0, 0, 1, lo, hi, bins, counts[slot])
                     if keep is not None:
                         keep[i0:i1].copy_(out[:c * D].view(c, D))
         return (counts, recon, gen) if return_samples else counts
@@ -320,3 +352,18 @@ class PosteriorDiagnostics:
         mean, median = float(host[-2]), float(host[-1])
         return {"latent_counts": latent, "data_counts": data, "logvar_qz": host[:-2].view(lv.shape).numpy(), "logvar_qz_mean": mean,
                 "logvar_qz_median": median, TAG_MEAN: mean, TAG_MEDIAN: median}
+
+    # ---- the script's last block -----------------------------------------------------------------------------------------------------
+    def final_pass(self, x_all, bins=256, return_arrays=False):
+        """The `''' test visualize '''` block (ivae_ardae.py:1224-1290; the reference walks 1 000 000 points at num=256): the latent histograms
+        of every noise level at val 4 and, for 2-D data under a Gaussian decoder, data | reconstruction | generation at val 6.  bins 1 .. 512:
+        up to 128 through ardae_hist2d, above through ardae_hist2d_wide.  The clipped aux-resconv class takes its three levels, stds
+        (None, 1, 0).  -> dict: latent_counts [S, bins, bins], data_counts [3, bins, bins] or None (int64, on the device; no host
+        synchronisation); return_arrays adds latents [N, S, z_dim], recon and gen [N, D] (None without data_counts)."""
+        stds = (None, 1, 0) if self.clipped else STDS
+        with_data = self.gaussian and self.model.input_dim == 2
+        latent = self._latent(x_all, stds, 4.0, bins, None, return_arrays, MAX_BINS_WIDE, hist2d)
+        data = self._data(x_all, 6.0, bins, return_arrays, MAX_BINS_WIDE, hist2d) if with_data else None
+        if not return_arrays:
+            return {"latent_counts": latent, "data_counts": data}
+        return {"latent_counts": latent[0], "data_counts": data and data[0], "latents": latent[1], "recon": data and data[1], "gen": data and data[2]}

@@ -5,6 +5,7 @@ as one captured unit, and its evaluate_iws (vae.py:342-377) in large chunks.
     eng = net.VaeEngine(model, net.VaeConfig(lr=1e-3, beta_init=1e-4, beta_annealing=50000), batch_size=128)
     for x in loader: eng.step(x)
     elbo, logprob = eng.evaluate_iws(x_valid, sample_size=512)
+    panels = eng.diagnostics(x_vis)           # its `''' visualize '''` block: 2-D histograms of the latents (and data | recon | gen), on the device
 
 There is one network, one stream and one linear graph per step.  There is no data parallelism here: the batch is 128 rows, the whole step
 is a few dozen per-image launches, and there is nothing to shard.
@@ -277,6 +278,7 @@ class VaeEngine:
         self._avg_origin = int(cfg.weight_avg_start) + 1
         self._avg_swap = None
         self._iwae = None
+        self._diag = None
         self._ladder = CaptureLadder(self.dev, graph)
         self._x = None
         self.step_count = 0
@@ -458,3 +460,13 @@ class VaeEngine:
             return ev.evaluate(x_all, eps, fwd_eps)
         with self.averaged_weights():
             return ev.evaluate(x_all, eps, fwd_eps)
+
+    def diagnostics(self, x_all):
+        """The visualisation block (vae.py:497-593) on the device: vae_diagnostics.GaussianDiagnostics.run on the engine's model with the LIVE
+        weights, as the reference's block reads them (the averaged weights are swapped in for evaluate_iws only; while they are in, this is
+        refused like step()).  It consumes host-stream Philox offsets and nothing of the step's state, graph or in-step Philox base."""
+        self._require_trained("diagnostics()")
+        if self._diag is None:
+            from .vae_diagnostics import GaussianDiagnostics      # (that module reads this one's width limits)
+            self._diag = GaussianDiagnostics(self.model)
+        return self._diag.run(x_all)
