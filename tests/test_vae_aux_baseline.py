@@ -12,29 +12,14 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
-from test_vae_baseline import load
+import vae_restate as R
+from vae_restate import BETAS, TOL64, clip_logvar, fails, lin, load, mlp_fwd, rel
+from vae_restate import aux_forward_backward as forward_backward      # the family's restatement, in float64 numpy with the backward by hand
+from vae_restate import aux_logprob_rows as logprob_rows
 
 KIND_ID = {"mnist": 14, "toy": 15}
 CASES = ("auxmnist_n100_z32_b3", "auxmnist_n10_z6_b5_spm6", "auxtoy_n2_z2_b7", "auxtoy_n5_z3_b4_hard")
 TRAJ = ("auxmnist", "auxtoy")
-BETAS = {"b1": 1.0, "b03": 0.3}
-LOG_2PI = math.log(2 * math.pi)
-
-
-def rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-300))
-
-
-def summary(t):
-    t = np.asarray(t).reshape(-1)
-    return np.concatenate([[np.linalg.norm(t), t.sum()], t[:8]])
-
-
-def summary_err(t, want):
-    """The worst of a tensor's three distances to a stored summary: the L2 norm, the sum on the scale of its terms, the first 8 elements"""
-    got, want = summary(t), np.asarray(want, dtype=np.float64)
-    return max(abs(got[0] - want[0]) / want[0], abs(got[1] - want[1]) / (want[0] * math.sqrt(np.asarray(t).size)), rel(got[2:], want[2:]))
 
 
 def shape_of(fx):
@@ -55,174 +40,10 @@ def params64(fx):
     return {k: v.double().numpy() for k, v in aux_params(fx).items()}
 
 
-# ---- the test-side oracle: the model restated in float64 numpy, backward by hand ----------------------------------------------------
-def sigmoid(v):
-    return 0.5 * (1.0 + np.tanh(0.5 * v))
-
-
-def softplus(v):
-    return np.logaddexp(0.0, v)
-
-
-# activation -> (f(v), f'(v)) on the pre-activation v
-ACT = {"relu": (lambda v: np.maximum(v, 0.0), lambda v: (v > 0).astype(v.dtype)),
-       "softplus": (softplus, sigmoid),
-       "elu": (lambda v: np.where(v > 0, v, np.expm1(np.minimum(v, 0.0))), lambda v: np.where(v > 0, 1.0, np.exp(np.minimum(v, 0.0)))),
-       "tanh": (np.tanh, lambda v: 1.0 - np.tanh(v) ** 2),
-       "leaky_relu": (lambda v: np.where(v > 0, v, 0.2 * v), lambda v: np.where(v > 0, 1.0, 0.2)),
-       "swish": (lambda v: v * sigmoid(v), lambda v: sigmoid(v) * (1.0 + v * (1.0 - sigmoid(v))))}
-SPM = {"softplus": 0.0, "spm10": 10.0, "spm6": 6.0, "spm5": 5.0, "spm4": 4.0, "spm3": 3.0, "spm2": 2.0}
-
-
-def clip_logvar(code, v):
-    """NormalDistribution.clip_logvar (models/reparam.py:17-41) -> (c(v), c'(v))"""
-    if code in (None, "none"):
-        return v, np.ones_like(v)
-    if code == "hard":
-        return np.clip(v, -4.0, 2.0), ((v > -4.0) & (v < 2.0)).astype(v.dtype)
-    if code in SPM:
-        return softplus(v + SPM[code]) - SPM[code], sigmoid(v + SPM[code])
-    s = {"tanh": 1.0, "2tanh": 2.0}[code]
-    return s * np.tanh(v), s * (1.0 - np.tanh(v) ** 2)
-
-
-def mlp_names(p, prefix):
-    n = len([k for k in p if k.startswith(prefix + "layers.") and k.endswith("weight")])
-    return [f"{prefix}layers.{i}" for i in range(n)] + [prefix + "fc"]
-
-
-def mlp_fwd(p, prefix, hdn, act):
-    """models/layers.py MLP(..., use_nonlinearity_output=True): `layers.*` then `fc`, every one followed by the activation -> output, cache"""
-    cache = []
-    for name in mlp_names(p, prefix):
-        pre = hdn @ p[name + ".weight"].T + p[name + ".bias"]
-        cache.append((name, hdn, pre))
-        hdn = ACT[act][0](pre)
-    return hdn, cache
-
-
-def mlp_bwd(p, cache, act, dh, grads):
-    """dL/d output -> dL/d input, the layers' gradients into `grads`"""
-    for name, inp, pre in reversed(cache):
-        dpre = dh * ACT[act][1](pre)
-        grads[name + ".weight"], grads[name + ".bias"] = dpre.T @ inp, dpre.sum(0)
-        dh = dpre @ p[name + ".weight"]
-    return dh
-
-
-def lin(p, name, hdn):
-    return hdn @ p[name + ".weight"].T + p[name + ".bias"]
-
-
-def lin_bwd(p, name, hdn, dout, grads):
-    grads[name + ".weight"], grads[name + ".bias"] = dout.T @ hdn, dout.sum(0)
-    return dout @ p[name + ".weight"]
-
-
-def kld_rows(mu, lv):
-    return -0.5 * (1 + lv - mu ** 2 - np.exp(lv)).sum(1)                                            # utils/vae.py:78-92
-
-
-def pair_kld_rows(mu1, lv1, mu2, lv2):
-    return -0.5 * (1 - lv2 + lv1 - (np.exp(lv1) + (mu1 - mu2) ** 2) / np.exp(lv2)).sum(1)           # utils/vae.py:94-114
-
-
-def recon_rows(family, p, act, x, z):
-    """-log p(x | z) per row -> rows, decoder mean, and what the backward needs"""
-    hd, cache = mlp_fwd(p, "decode.main.", z, act)
-    if family == "mnist":
-        logit = lin(p, "decode.reparam.logit_fn", hd)
-        rows = (np.maximum(logit, 0) - logit * x + np.logaddexp(0.0, -np.abs(logit))).sum(1)        # BCE with logits
-        return rows, sigmoid(logit), (hd, cache, logit, None)
-    mx, lvx = lin(p, "decode.reparam.mean_fn", hd), lin(p, "decode.reparam.logvar_fn", hd)
-    return 0.5 * (lvx + (x - mx) ** 2 / np.exp(lvx) + LOG_2PI).sum(1), mx, (hd, cache, mx, lvx)
-
-
-def forward_backward(family, p, act, clip, x, eps, beta, scale):
-    """VAE.forward (vae/auxmnist.py:337-364) and d (scale * loss) / d p in closed form -> dict(mu0, lv0, z, mean, loss, recon, kld), grads"""
-    B, D = x.shape
-    nd = p["aux_encode.reparam.mean_fn.weight"].shape[0]
-    eps0, epsz = eps[:, :nd], eps[:, nd:]
-    xs = 2 * x - 1 if family == "mnist" else x
-    h0, c0 = mlp_fwd(p, "aux_encode.main.", xs, act)
-    mu0, lv0r = lin(p, "aux_encode.reparam.mean_fn", h0), lin(p, "aux_encode.reparam.logvar_fn", h0)
-    lv0, dclip = clip_logvar(clip, lv0r)
-    z0 = mu0 + np.exp(0.5 * lv0) * eps0
-    h, c1 = mlp_fwd(p, "encode.fc.", np.concatenate([xs, z0], 1), act)
-    mu, lv = lin(p, "encode.reparam.mean_fn", h), lin(p, "encode.reparam.logvar_fn", h)
-    z = mu + np.exp(0.5 * lv) * epsz
-    hr, c2 = mlp_fwd(p, "aux_decode.fc.", np.concatenate([xs, z], 1), act)
-    mup, lvp = lin(p, "aux_decode.reparam.mean_fn", hr), lin(p, "aux_decode.reparam.logvar_fn", hr)
-    rec, mean, (hd, c3, o0, o1) = recon_rows(family, p, act, x, z)
-    kld, aux = kld_rows(mu, lv), pair_kld_rows(mu0, lv0, mup, lvp)
-    out = dict(mu0=mu0, lv0=lv0, z=z, mean=mean, loss=(rec + beta * kld + beta * aux).mean(), recon=rec.mean(), kld=(kld + aux).mean())
-    # ---- backward, c = scale / B
-    c, g = scale / B, {}
-    if family == "mnist":
-        dhd = lin_bwd(p, "decode.reparam.logit_fn", hd, c * (sigmoid(o0) - x), g)
-    else:
-        dhd = lin_bwd(p, "decode.reparam.mean_fn", hd, -c * (x - o0) / np.exp(o1), g)
-        dhd = dhd + lin_bwd(p, "decode.reparam.logvar_fn", hd, 0.5 * c * (1 - (x - o0) ** 2 / np.exp(o1)), g)
-    dz = mlp_bwd(p, c3, act, dhd, g)
-    dmup = c * beta * (mup - mu0) / np.exp(lvp)
-    dlvp = c * beta * 0.5 * (1 - (np.exp(lv0) + (mu0 - mup) ** 2) / np.exp(lvp))
-    dhr = lin_bwd(p, "aux_decode.reparam.mean_fn", hr, dmup, g) + lin_bwd(p, "aux_decode.reparam.logvar_fn", hr, dlvp, g)
-    dz = dz + mlp_bwd(p, c2, act, dhr, g)[:, D:]
-    dmu = dz + c * beta * mu
-    dlv = dz * (z - mu) / 2 + c * beta * (np.exp(lv) - 1) / 2
-    dh = lin_bwd(p, "encode.reparam.mean_fn", h, dmu, g) + lin_bwd(p, "encode.reparam.logvar_fn", h, dlv, g)
-    dz0 = mlp_bwd(p, c1, act, dh, g)[:, D:]
-    dmu0 = dz0 + c * beta * (mu0 - mup) / np.exp(lvp)
-    dlv0 = dz0 * (z0 - mu0) / 2 + c * beta * 0.5 * (np.exp(lv0) / np.exp(lvp) - 1)
-    dh0 = lin_bwd(p, "aux_encode.reparam.mean_fn", h0, dmu0, g) + lin_bwd(p, "aux_encode.reparam.logvar_fn", h0, dlv0 * dclip, g)
-    mlp_bwd(p, c0, act, dh0, g)
-    return out, g
-
-
-def log_normal_rows(v, mu, lv):
-    return (-0.5 * ((v - mu) ** 2 / np.exp(lv) + lv + LOG_2PI)).sum(-1)                             # utils/stat.py:65-85
-
-
-def logq_rows(family, p, act, clip, x, eps):
-    """The three stochastic stages of VAE.logprob (vae/auxmnist.py:381-451, sample_size2 = 1) on injected draws eps [B, k, noise + z]
-    -> z [B k, zd], logq [B k] = log q(z0|x) + log q(z|z0,x) - log r(z0|z,x)"""
-    B, k, _ = eps.shape
-    nd = p["aux_encode.reparam.mean_fn.weight"].shape[0]
-    xs = 2 * x - 1 if family == "mnist" else x
-    h0, _ = mlp_fwd(p, "aux_encode.main.", xs, act)
-    mu0 = lin(p, "aux_encode.reparam.mean_fn", h0)
-    lv0, _ = clip_logvar(clip, lin(p, "aux_encode.reparam.logvar_fn", h0))
-    mu0, lv0, xr = (np.repeat(v, k, 0) for v in (mu0, lv0, xs))
-    e = eps.reshape(B * k, -1)
-    z0 = mu0 + np.exp(0.5 * lv0) * e[:, :nd]
-    h, _ = mlp_fwd(p, "encode.fc.", np.concatenate([xr, z0], 1), act)
-    mu, lv = lin(p, "encode.reparam.mean_fn", h), lin(p, "encode.reparam.logvar_fn", h)
-    z = mu + np.exp(0.5 * lv) * e[:, nd:]
-    hr, _ = mlp_fwd(p, "aux_decode.fc.", np.concatenate([xr, z], 1), act)
-    mup, lvp = lin(p, "aux_decode.reparam.mean_fn", hr), lin(p, "aux_decode.reparam.logvar_fn", hr)
-    return z, log_normal_rows(z0, mu0, lv0) + log_normal_rows(z, mu, lv) - log_normal_rows(z0, mup, lvp)
-
-
-def logprob_rows(family, p, act, clip, x, eps):
-    """VAE.logprob before its mean, [B]"""
-    B, k, _ = eps.shape
-    z, logq = logq_rows(family, p, act, clip, x, eps)
-    rec, _, _ = recon_rows(family, p, act, np.repeat(x, k, 0), z)
-    lw = (-rec + log_normal_rows(z, 0.0, 0.0) - logq).reshape(B, k)
-    m = lw.max(1, keepdims=True)
-    return (np.log(np.mean(np.exp(lw - m), 1, keepdims=True) + 1e-10) + m).reshape(B)
-
-
-def adam_step(p, g, st, lr, beta1, t):
-    """The reference's vendored Adam (utils/optim.py:84-106: epsilon before the bias correction), in place"""
-    bc1, bc2 = 1 - beta1 ** t, 1 - 0.999 ** t
-    for k in p:
-        m, v = st.setdefault(k, (np.zeros_like(p[k]), np.zeros_like(p[k])))
-        m *= beta1
-        m += (1 - beta1) * g[k]
-        v *= 0.999
-        v += (1 - 0.999) * g[k] * g[k]
-        p[k] -= lr / bc1 * m / ((np.sqrt(v) + 1e-8) / math.sqrt(bc2))
+def restate(fx):
+    """-> the fixture's parameters as float64 numpy, cfg = (family, activation, clip) of vae_restate's aux_* functions"""
+    family, _, act, clip = shape_of(fx)
+    return params64(fx), (family, act, clip)
 
 
 # ---- 1. the restatement, pinned to the reference ------------------------------------------------------------------------------------
@@ -230,22 +51,17 @@ def adam_step(p, g, st, lr, beta1, t):
 def test_restatement_is_the_reference_in_float64(golden_dir, case):
     fx = load(golden_dir, "vae_" + case)
     family, (B, D, h, nd, z, nl), act, clip = shape_of(fx)
-    p = params64(fx)
+    p, cfg = restate(fx)
     x, eps = fx["x"].astype(np.float64), fx["eps"].astype(np.float64)
     for b, beta in BETAS.items():
-        out, grads = forward_backward(family, p, act, clip, x, eps, beta, 1.0 / D)
+        out, grads = forward_backward(p, cfg, x, eps, beta, 1.0 / D)
         for k in ("z", "mean", "loss", "recon", "kld"):
-            assert rel(out[k], fx[f"{b}/{k}_f64"]) <= 1e-9, (b, k)
-        assert rel(out["mu0"], fx["mu0_f64"]) <= 1e-9 and rel(out["lv0"], fx["lv0_f64"]) <= 1e-9
-        full = {k[len(b) + 7:]: v for k, v in fx.items() if k.startswith(f"{b}/g_f64/")}
-        summ = {k[len(b) + 8:]: v for k, v in fx.items() if k.startswith(f"{b}/gs_f64/")}
-        assert set(grads) == set(full) | set(summ) == set(p)
-        for k, g in grads.items():
-            assert g.shape == p[k].shape
-            e = rel(g, full[k]) if k in full else summary_err(g, summ[k])
-            assert e <= 1e-9, (b, k, e)
-    lp = logprob_rows(family, p, act, clip, x, fx["lp/eps"].astype(np.float64)).mean()
-    assert rel(lp, fx["lp/value_f64"]) <= 1e-9
+            assert rel(out[k], fx[f"{b}/{k}_f64"]) <= TOL64, (b, k)
+        assert rel(out["mu0"], fx["mu0_f64"]) <= TOL64 and rel(out["lv0"], fx["lv0_f64"]) <= TOL64
+        assert all(g.shape == p[k].shape for k, g in grads.items())
+        R.check_grads_f64(grads, fx, b, TOL64, params=p)
+    lp = logprob_rows(p, cfg, x, fx["lp/eps"].astype(np.float64)).mean()
+    assert rel(lp, fx["lp/value_f64"]) <= TOL64
     # the fp32 fixture is the same computation at fp32's precision
     assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
     if clip != "none":       # the clip acts on part of the elements
@@ -256,18 +72,10 @@ def test_restatement_is_the_reference_in_float64(golden_dir, case):
 @pytest.mark.parametrize("name", TRAJ)
 def test_restated_trajectory_is_the_reference_in_float64(golden_dir, name):
     fx = load(golden_dir, "vae_traj_" + name)
-    family, (B, D, h, nd, z, nl), act, clip = shape_of(fx)
-    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
-                        beta_annealing=int(fx["cfg/beta_annealing"]))
-    p, st = params64(fx), {}
-    for s in range(int(fx["cfg/steps"])):
-        beta = cfg.beta_at(s)
-        assert beta == float(fx[f"{s}/beta"])
-        out, grads = forward_backward(family, p, act, clip, fx[f"{s}/x"].astype(np.float64), fx[f"{s}/eps"].astype(np.float64), beta, 1.0 / D)
-        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
-        assert rel(out["loss"], fx[f"{s}/loss_f64"]) <= 1e-9 and rel(out["kld"], fx[f"{s}/kld_f64"]) <= 1e-9
-        for k, v in p.items():
-            assert summary_err(v, fx[f"{s}/ps_f64/{k}"]) <= 1e-9, (s, k)
+    D = shape_of(fx)[1][1]
+    p, cfg = restate(fx)
+    steps = R.trajectory(fx, p, lambda p, x, eps, beta: forward_backward(p, cfg, x.astype(np.float64), eps.astype(np.float64), beta, 1.0 / D))
+    R.check_traj_f64(steps, fx, TOL64, keys=("loss", "kld"))
     assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
 
 
@@ -319,12 +127,6 @@ def test_parameter_counts_at_the_recipe_widths(golden_dir):
 # ---- 3. descriptor rules and refusals, before any HIP call --------------------------------------------------------------------------
 one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
 ref = ctypes.byref
-
-
-def fails(rc, fragment):
-    lib = L.lib()
-    assert rc < 0
-    assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
 
 
 def accepted(d):

@@ -6,6 +6,7 @@ reference's float64 fixtures.  No GPU needed.
 The fixtures (tools/gen_vae_auxconv_golden.py) do not store the parameters: `auxconv_params` regenerates them from the stored seed with the oracle's
 platform-independent initialiser, exactly as the tool did."""
 import ctypes
+import functools
 import math
 
 import pytest
@@ -16,14 +17,11 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
-from test_ardae_uncond import ACTS, rel
-from test_vae_baseline import BETAS, adam_step, lin, load
-from test_vae_conv_baseline import recon_rows, relaxed_sample, summary
+import vae_restate as R
+from vae_restate import ACTS, BETAS, TOL64, fails, kld_rows, lin, load, log_normal_rows, pair_kld_rows, rel, relaxed_sample
 
 CASES = ("auxconv_n100_z32_b3", "auxconv_n10_z6_b5_elu")
 D = 784
-TOL64 = 1e-9          # float64 restatement against the reference's float64 outputs: losses, full tensors and summaries
-LOG_2PI = math.log(2 * math.pi)
 
 
 def shape_of(fx):
@@ -37,37 +35,15 @@ def auxconv_params(fx, dtype=torch.float32):
     return {k: v.to(dtype) for k, v in O.init_params(layout.aux_conv_vae_spec(nd, z), int(fx["seed"])).items()}
 
 
-# ---- the test-side oracle: the family restated in plain torch ----------------------------------------------------------------------
-def trunk(p, prefix, act, x):
-    """conv1 .. conv3 of one of the three networks on 2x - 1 -> h3 [B, 512] (NCHW-flat; vae/auxconv.py:61-72)"""
-    a = ACTS[act]
-    hdn = (2 * x - 1).view(-1, 1, 28, 28)
-    for i in (1, 2, 3):
-        hdn = a(F.conv2d(hdn, p[f"{prefix}conv{i}.weight"], p[f"{prefix}conv{i}.bias"], stride=2, padding=2))
-    return hdn.reshape(hdn.size(0), -1)
-
-
+# ---- the test-side oracle: the family restated in plain torch (trunk and decoder: vae_restate) ---------------------------------------
 def stats(p, prefix, act, x, s=None, k=1):
     """-> (mean, logvar) of the network `prefix`: fc on h3 (aux_encode) or on cat[h3, s] with the trunk output first and each image's h3 repeated for
     its k rows of s (encode, aux_decode)"""
-    h3 = trunk(p, prefix, act, x)
+    h3 = R.conv_trunk(p, prefix, act, x)
     if s is not None:
         h3 = torch.cat([h3.repeat_interleave(k, 0), s], 1)
     h4 = ACTS[act](lin(p, prefix + "fc", h3))
     return lin(p, prefix + "reparam.mean_fn", h4), lin(p, prefix + "reparam.logvar_fn", h4)
-
-
-def kld_rows(mu, lv):
-    return -0.5 * (1 + lv - mu ** 2 - lv.exp()).sum(1)                                              # utils/vae.py:78-92
-
-
-def pair_kld_rows(mu1, lv1, mu2, lv2):
-    """tests/test_vae_aux_baseline.py::pair_kld_rows on torch tensors (that one is numpy's, without autograd)"""
-    return -0.5 * (1 - lv2 + lv1 - (lv1.exp() + (mu1 - mu2) ** 2) / lv2.exp()).sum(1)               # utils/vae.py:94-114
-
-
-def log_normal_rows(v, mu, lv):
-    return (-0.5 * ((v - mu) ** 2 / lv.exp() + lv + LOG_2PI)).sum(-1)                               # utils/stat.py:65-85
 
 
 def forward(p, act, x, eps, beta):
@@ -78,18 +54,13 @@ def forward(p, act, x, eps, beta):
     mu, lv = stats(p, "encode.", act, x, z0)
     z = mu + torch.exp(0.5 * lv) * eps[:, nd:]
     mup, lvp = stats(p, "aux_decode.", act, x, z)
-    rec, logit = recon_rows(p, act, x, z)
+    rec, logit = R.conv_recon_rows(p, act, x, z)
     kld, aux = kld_rows(mu, lv), pair_kld_rows(mu0, lv0, mup, lvp)
     return dict(mu0=mu0, lv0=lv0, z=z, mean=torch.sigmoid(logit), logit=logit, loss=(rec + beta * kld + beta * aux).mean(), recon=rec.mean(),
                 kld=(kld + aux).mean())
 
 
-def loss_and_grads(p, act, x, eps, beta, scale):
-    """-> forward's dict (detached) and {name: d (scale * loss) / d p}"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    out = forward(p, act, x, eps, beta)
-    grads = dict(zip(p, torch.autograd.grad(scale * out["loss"], list(p.values()))))
-    return {k: v.detach() for k, v in out.items()}, grads
+loss_and_grads = functools.partial(R.loss_and_grads, forward)      # (p, act, x, eps, beta, scale=) -> forward's dict (detached), {name: gradient}
 
 
 def logq_rows(p, act, x, eps):
@@ -110,10 +81,8 @@ def logprob_rows(p, act, x, eps):
     """VAE.logprob before its mean, [B]"""
     B, k, _ = eps.shape
     z, logq = logq_rows(p, act, x, eps)
-    rec, _ = recon_rows(p, act, x.repeat_interleave(k, 0), z)
-    lw = (-rec + log_normal_rows(z, torch.zeros_like(z), torch.zeros_like(z)) - logq).view(B, k)
-    m = lw.max(1, keepdim=True)[0]
-    return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).view(B)
+    rec, _ = R.conv_recon_rows(p, act, x.repeat_interleave(k, 0), z)
+    return R.iw_logsumexp((-rec + log_normal_rows(z, torch.zeros_like(z), torch.zeros_like(z)) - logq).view(B, k))
 
 
 def tail_logit(p, act, u1):
@@ -124,47 +93,31 @@ def tail_logit(p, act, u1):
     return logit[:, :, :28, :28].reshape(-1, D)
 
 
-def summary_err(t, want):
-    """The worst of a tensor's three distances to a stored summary: the L2 norm, the sum on the scale of its terms, the first 8 elements"""
-    got, want = summary(t).double(), torch.as_tensor(want).double()
-    return max(abs(float(got[0]) - float(want[0])) / float(want[0]), abs(float(got[1]) - float(want[1])) / (float(want[0]) * math.sqrt(t.numel())),
-               rel(got[2:], want[2:]))
+def restate(fx):
+    """-> the fixture's parameters in float64, cfg (the activation)"""
+    return auxconv_params(fx, torch.float64), str(fx["act"])
 
 
 def trajectory(fx):
     """The fixture's loop restated in float64: yields (step, forward's dict, the parameters after the vendored Adam's step)"""
-    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
-                        beta_annealing=int(fx["cfg/beta_annealing"]))
-    p, st, act = auxconv_params(fx, torch.float64), {}, str(fx["act"])
-    for s in range(int(fx["cfg/steps"])):
-        beta = cfg.beta_at(s)
-        assert beta == float(fx[f"{s}/beta"])
-        out, grads = loss_and_grads(p, act, torch.tensor(fx[f"{s}/x"]).double(), torch.tensor(fx[f"{s}/eps"]).double(), beta, 1.0 / D)
-        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
-        yield s, out, p
+    p, act = restate(fx)
+    return R.trajectory(fx, p, lambda p, x, eps, beta: loss_and_grads(p, act, R.t64(x), R.t64(eps), beta, scale=1.0 / D))
 
 
 # ---- 1. the restatement, pinned to the reference -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", CASES)
 def test_restatement_is_the_reference_in_float64(golden_dir, case):
     fx = load(golden_dir, "vae_" + case)
-    _, act = shape_of(fx)
-    p = auxconv_params(fx, torch.float64)
-    x, eps, dec = (torch.tensor(fx[k]).double() for k in ("x", "eps", "dec_noise"))
+    p, act = restate(fx)
+    x, eps, dec = (R.t64(fx[k]) for k in ("x", "eps", "dec_noise"))
     for b, beta in BETAS.items():
-        out, grads = loss_and_grads(p, act, x, eps, beta, 1.0 / D)
+        out, grads = loss_and_grads(p, act, x, eps, beta, scale=1.0 / D)
         for k in ("z", "mean", "loss", "recon", "kld"):
             assert rel(out[k], fx[f"{b}/{k}_f64"]) <= TOL64, (b, k)
         assert rel(relaxed_sample(out["logit"], dec), fx[f"{b}/x_sample_f64"]) <= TOL64
         assert rel(out["mu0"], fx["mu0_f64"]) <= TOL64 and rel(out["lv0"], fx["lv0_f64"]) <= TOL64
-        full = {k[len(b) + 7:]: v for k, v in fx.items() if k.startswith(f"{b}/g_f64/")}
-        summ = {k[len(b) + 8:]: v for k, v in fx.items() if k.startswith(f"{b}/gs_f64/")}
-        assert set(grads) == set(full) | set(summ) == set(p) and not set(full) & set(summ)
-        for k, g in grads.items():
-            assert (g.numel() <= 16384) == (k in full), k
-            e = rel(g, full[k]) if k in full else summary_err(g, summ[k])
-            assert e <= TOL64, (b, k, e)
-    lp = logprob_rows(p, act, x, torch.tensor(fx["lp/eps"]).double()).mean()
+        R.check_grads_f64(grads, fx, b, TOL64, params=p)
+    lp = logprob_rows(p, act, x, R.t64(fx["lp/eps"])).mean()
     assert rel(lp, fx["lp/value_f64"]) <= TOL64
     # the fp32 fixture is the same computation at fp32's precision
     assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
@@ -173,11 +126,7 @@ def test_restatement_is_the_reference_in_float64(golden_dir, case):
 def test_restated_trajectory_is_the_reference_in_float64(golden_dir):
     fx = load(golden_dir, "vae_traj_auxconv")
     assert int(fx["cfg/steps"]) == 4
-    for s, out, p in trajectory(fx):
-        for k in ("loss", "recon", "kld"):
-            assert rel(out[k], fx[f"{s}/{k}_f64"]) <= TOL64, (s, k)
-        for k, v in p.items():
-            assert summary_err(v, fx[f"{s}/ps_f64/{k}"]) <= TOL64, (s, k)
+    R.check_traj_f64(trajectory(fx), fx, TOL64)
     assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
 
 
@@ -218,12 +167,6 @@ def test_parameter_count_at_the_recipe_widths(golden_dir):
 # ---- 3. descriptor rules and refusals, before any HIP call --------------------------------------------------------------------------
 one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
 ref = ctypes.byref
-
-
-def fails(rc, fragment):
-    lib = L.lib()
-    assert rc < 0
-    assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
 
 
 def desc(**kw):

@@ -6,6 +6,7 @@ the decoder's 14 x 14 stage on its own - that the GPU tests lean on, pinned here
 The fixtures (tools/gen_vae_auxresconv_golden.py) do not store the parameters: `auxres_params` regenerates them from the stored seed with the oracle's
 platform-independent initialiser, exactly as the tool did."""
 import ctypes
+import functools
 import math
 
 import pytest
@@ -16,16 +17,14 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
-from test_ardae_uncond import rel
-from test_vae_baseline import BETAS, adam_step, lin, load
-from test_vae_conv_baseline import relaxed_sample
-from test_vae_auxconv_baseline import fails, kld_rows, log_normal_rows, pair_kld_rows, summary_err
-from test_vae_resconv_baseline import decode_logit, tail_logit
+import vae_restate as R
+from vae_restate import BETAS, TOL64, fails, kld_rows, lin, load, log_normal_rows, pair_kld_rows, rel, relaxed_sample
+from vae_restate import resconv_decode_logit as decode_logit
+from vae_restate import resconv_tail_logit as tail_logit
 
 CASES = ("auxresconv_n100_z32_c450_b3", "auxresconv_n10_z6_c42_b5")
 D = 784
 ELU = 3               # ARDAE_ACT_ELU
-TOL64 = 1e-9          # float64 restatement against the reference's float64 outputs: losses, full tensors and summaries
 
 
 def shape_of(fx):
@@ -44,13 +43,10 @@ def desc_of(nd, z, c, center):
     return L.ModelDesc(19, D, nd, c, z, 1, ELU, 0 if center else L.MODEL_NO_CENTER)
 
 
-# ---- the test-side oracle: the family restated in plain torch ----------------------------------------------------------------------
+# ---- the test-side oracle: the family restated in plain torch (trunk and decoder: vae_restate) ---------------------------------------
 def trunk(p, center, x):
     """InputEncoder.forward (vae/auxresconv.py:52-63) -> ctx [B, c_dim]"""
-    h = (2 * x - 1 if center else x).view(-1, 1, 28, 28)
-    for i, st in zip((0, 2, 4, 6, 8), (2, 1, 2, 1, 2)):
-        h = F.elu(O.res_conv(p, f"inp_encode.enc.{i}.", h, st, F.elu))
-    return F.elu(O.res_linear(p, "inp_encode.enc.11.", h.reshape(h.size(0), 512), True))
+    return R.resconv_trunk(p, "inp_encode.enc.", center, x)
 
 
 def head(p, prefix, h):
@@ -62,11 +58,6 @@ def cat_stats(p, prefix, ctx, s, k=1):
     return head(p, prefix, F.elu(lin(p, prefix + "fc.0", torch.cat([ctx.repeat_interleave(k, 0), s], 1))))
 
 
-def recon_rows(p, x, z):
-    logit = decode_logit(p, z)
-    return F.binary_cross_entropy_with_logits(logit, x, reduction="none").sum(1), logit
-
-
 def forward(p, center, x, eps, beta):
     """-> dict(mu0, lv0, z, mean, logit, loss, recon, kld): VAE.forward (vae/auxresconv.py:310-340); kld = kld + aux_kld"""
     nd = p["aux_encode.reparam.mean_fn.weight"].size(0)
@@ -76,18 +67,13 @@ def forward(p, center, x, eps, beta):
     mu, lv = cat_stats(p, "encode.", ctx, z0)
     z = mu + torch.exp(0.5 * lv) * eps[:, nd:]
     mup, lvp = cat_stats(p, "aux_decode.", ctx, z)
-    rec, logit = recon_rows(p, x, z)
+    rec, logit = R.resconv_recon_rows(p, x, z)
     kld, aux = kld_rows(mu, lv), pair_kld_rows(mu0, lv0, mup, lvp)
     return dict(mu0=mu0, lv0=lv0, z=z, mean=torch.sigmoid(logit), logit=logit, loss=(rec + beta * kld + beta * aux).mean(), recon=rec.mean(),
                 kld=(kld + aux).mean())
 
 
-def loss_and_grads(p, center, x, eps, beta, scale):
-    """-> forward's dict (detached) and {name: d (scale * loss) / d p}"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    out = forward(p, center, x, eps, beta)
-    grads = dict(zip(p, torch.autograd.grad(scale * out["loss"], list(p.values()))))
-    return {k: v.detach() for k, v in out.items()}, grads
+loss_and_grads = functools.partial(R.loss_and_grads, forward)      # (p, center, x, eps, beta, scale=) -> forward's dict (detached), {name: gradient}
 
 
 def logq_rows(p, center, x, eps):
@@ -109,10 +95,8 @@ def logprob_rows(p, center, x, eps):
     """VAE.logprob before its mean, [B]"""
     B, k, _ = eps.shape
     z, logq = logq_rows(p, center, x, eps)
-    rec, _ = recon_rows(p, x.repeat_interleave(k, 0), z)
-    lw = (-rec + log_normal_rows(z, torch.zeros_like(z), torch.zeros_like(z)) - logq).view(B, k)
-    m = lw.max(1, keepdim=True)[0]
-    return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).view(B)
+    rec, _ = R.resconv_recon_rows(p, x.repeat_interleave(k, 0), z)
+    return R.iw_logsumexp((-rec + log_normal_rows(z, torch.zeros_like(z), torch.zeros_like(z)) - logq).view(B, k))
 
 
 def head_map(p, z):
@@ -132,41 +116,31 @@ def mid_map(p, y8):
     return F.elu(O.res_conv(p, "decode.dec.14.", h, 1, F.elu)).permute(0, 2, 3, 1)
 
 
+def restate(fx):
+    """-> the fixture's parameters in float64, cfg (do_center)"""
+    return auxres_params(fx, torch.float64), shape_of(fx)[1]
+
+
 def trajectory(fx):
     """The fixture's loop restated in float64: yields (step, forward's dict, the parameters after the vendored Adam's step)"""
-    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
-                        beta_annealing=int(fx["cfg/beta_annealing"]))
-    p, st = auxres_params(fx, torch.float64), {}
-    _, center = shape_of(fx)
-    for s in range(int(fx["cfg/steps"])):
-        beta = cfg.beta_at(s)
-        assert beta == float(fx[f"{s}/beta"])
-        out, grads = loss_and_grads(p, center, torch.tensor(fx[f"{s}/x"]).double(), torch.tensor(fx[f"{s}/eps"]).double(), beta, 1.0 / D)
-        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
-        yield s, out, p
+    p, center = restate(fx)
+    return R.trajectory(fx, p, lambda p, x, eps, beta: loss_and_grads(p, center, R.t64(x), R.t64(eps), beta, scale=1.0 / D))
 
 
 # ---- 1. the restatement, pinned to the reference -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", CASES)
 def test_restatement_is_the_reference_in_float64(golden_dir, case):
     fx = load(golden_dir, "vae_" + case)
-    _, center = shape_of(fx)
-    p = auxres_params(fx, torch.float64)
-    x, eps, dec = (torch.tensor(fx[k]).double() for k in ("x", "eps", "dec_noise"))
+    p, center = restate(fx)
+    x, eps, dec = (R.t64(fx[k]) for k in ("x", "eps", "dec_noise"))
     for b, beta in BETAS.items():
-        out, grads = loss_and_grads(p, center, x, eps, beta, 1.0 / D)
+        out, grads = loss_and_grads(p, center, x, eps, beta, scale=1.0 / D)
         for k in ("z", "mean", "loss", "recon", "kld"):
             assert rel(out[k], fx[f"{b}/{k}_f64"]) <= TOL64, (b, k)
         assert rel(relaxed_sample(out["logit"], dec), fx[f"{b}/x_sample_f64"]) <= TOL64
         assert rel(out["mu0"], fx["mu0_f64"]) <= TOL64 and rel(out["lv0"], fx["lv0_f64"]) <= TOL64
-        full = {k[len(b) + 7:]: v for k, v in fx.items() if k.startswith(f"{b}/g_f64/")}
-        summ = {k[len(b) + 8:]: v for k, v in fx.items() if k.startswith(f"{b}/gs_f64/")}
-        assert set(grads) == set(full) | set(summ) == set(p) and not set(full) & set(summ)
-        for k, g in grads.items():
-            assert (g.numel() <= 16384) == (k in full), k
-            e = rel(g, full[k]) if k in full else summary_err(g, summ[k])
-            assert e <= TOL64, (b, k, e)
-    lp = logprob_rows(p, center, x, torch.tensor(fx["lp/eps"]).double()).mean()
+        R.check_grads_f64(grads, fx, b, TOL64, params=p)
+    lp = logprob_rows(p, center, x, R.t64(fx["lp/eps"])).mean()
     assert rel(lp, fx["lp/value_f64"]) <= TOL64
     # the fp32 fixture is the same computation at fp32's precision
     assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
@@ -175,11 +149,7 @@ def test_restatement_is_the_reference_in_float64(golden_dir, case):
 def test_restated_trajectory_is_the_reference_in_float64(golden_dir):
     fx = load(golden_dir, "vae_traj_auxresconv")
     assert int(fx["cfg/steps"]) == 4
-    for s, out, p in trajectory(fx):
-        for k in ("loss", "recon", "kld"):
-            assert rel(out[k], fx[f"{s}/{k}_f64"]) <= TOL64, (s, k)
-        for k, v in p.items():
-            assert summary_err(v, fx[f"{s}/ps_f64/{k}"]) <= TOL64, (s, k)
+    R.check_traj_f64(trajectory(fx), fx, TOL64)
     assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
 
 

@@ -2,31 +2,20 @@
 of every new entry point, the beta schedule on the host, and the float64 restatement of the two families that the GPU tests lean on -
 pinned here to the reference's fp64 fixtures.  No GPU needed."""
 import ctypes
-import glob
+import functools
 import math
-import os
 
-import numpy as np
 import pytest
 import torch
 
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
-from test_ardae_uncond import ACTS, rel
+import vae_restate as R
+from vae_restate import ACTS, BETAS, fails, lin, load, rel
 
 KIND_ID = {"mnist": 8, "toy": 9}
 CASES = {"mnist": ("d64_h40_z6", "d36_h300_z32"), "toy": ("h40_relu", "h40_tanh")}
-BETAS = {"b1": 1.0, "b03": 0.3}
-
-
-def load(golden_dir, name):
-    """A fixture and its parts (<name>.npz, <name>.p1.npz, ...: tools/gen_vae_golden.py::save_split) as one dict."""
-    paths = [os.path.join(golden_dir, name + ".npz")] + sorted(glob.glob(os.path.join(golden_dir, name + ".p*.npz")))
-    fx = {}
-    for p in paths:
-        fx.update(np.load(p))
-    return fx
 
 
 def case_names():
@@ -46,10 +35,6 @@ def mlp_act(p, prefix, hdn, act):
     return hdn
 
 
-def lin(p, name, hdn):
-    return hdn @ p[name + ".weight"].t() + p[name + ".bias"]
-
-
 def encode(family, p, act, x):
     hdn = mlp_act(p, "encode.main.", 2 * x - 1 if family == "mnist" else x, act)
     return lin(p, "encode.reparam.mean_fn", hdn), lin(p, "encode.reparam.logvar_fn", hdn)
@@ -65,46 +50,28 @@ def recon_rows(family, p, act, x, z):
     return 0.5 * (lv + (x - mu) ** 2 / lv.exp() + math.log(2 * math.pi)).sum(1), mu
 
 
-def forward(family, p, act, x, eps, beta):
-    """-> dict(mu, lv, z, mean, loss, recon, kld): VAE.forward (vae/mnist.py:142-162, vae/toy.py:133-152)"""
+def forward(p, cfg, x, eps, beta):
+    """-> dict(mu, lv, z, mean, loss, recon, kld): VAE.forward (vae/mnist.py:142-162, vae/toy.py:133-152); cfg = (family, activation)"""
+    family, act = cfg
     mu, lv = encode(family, p, act, x)
     z = mu + torch.exp(0.5 * lv) * eps
-    kld = -0.5 * (1 + lv - mu ** 2 - lv.exp()).sum(1)
+    kld = R.kld_rows(mu, lv)
     rec, mean = recon_rows(family, p, act, x, z)
     return dict(mu=mu, lv=lv, z=z, mean=mean, loss=(rec + beta * kld).mean(), recon=rec.mean(), kld=kld.mean())
 
 
-def loss_and_grads(family, p, act, x, eps, beta, scale):
-    """-> forward's dict (detached) and {name: d (scale * loss) / d p}"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    out = forward(family, p, act, x, eps, beta)
-    grads = dict(zip(p, torch.autograd.grad(scale * out["loss"], list(p.values()))))
-    return {k: v.detach() for k, v in out.items()}, grads
+loss_and_grads = functools.partial(R.loss_and_grads, forward)      # (p, cfg, x, eps, beta, scale=) -> forward's dict (detached), {name: gradient}
 
 
-def logprob_rows(family, p, act, x, eps):
+def logprob_rows(p, cfg, x, eps):
     """VAE.logprob before its mean (vae/mnist.py:179-217) on injected draws eps [B, k, zd]"""
-    B, k, zd = eps.shape
-    mu, lv = encode(family, p, act, x)
-    mu, lv = mu[:, None, :], lv[:, None, :]
-    z = mu + torch.exp(0.5 * lv) * eps
-    c = math.log(2 * math.pi)
-    logq = (-0.5 * ((z - mu) ** 2 / lv.exp() + lv + c)).sum(2)
-    logprior = (-0.5 * (z ** 2 + c)).sum(2)
-    rec, _ = recon_rows(family, p, act, x[:, None, :].expand(B, k, x.size(1)).reshape(B * k, -1), z.reshape(B * k, zd))
-    lw = -rec.view(B, k) + logprior - logq
-    m = lw.max(1, keepdim=True)[0]
-    return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).view(B)
+    family, act = cfg
+    return R.gaussian_logprob_rows(*encode(family, p, act, x), x, eps, lambda xr, zr: recon_rows(family, p, act, xr, zr)[0])
 
 
-def adam_step(p, g, st, lr, beta1, t):
-    """The reference's vendored Adam (utils/optim.py:84-106: epsilon before the bias correction), in place"""
-    bc1, bc2 = 1 - beta1 ** t, 1 - 0.999 ** t
-    for k in p:
-        m, v = st.setdefault(k, (torch.zeros_like(p[k]), torch.zeros_like(p[k])))
-        m.mul_(beta1).add_(g[k], alpha=1 - beta1)
-        v.mul_(0.999).addcmul_(g[k], g[k], value=1 - 0.999)
-        p[k].addcdiv_(m, (v.sqrt().add_(1e-8) / math.sqrt(bc2)), value=-lr / bc1)
+def restate(fx):
+    """-> the fixture's parameters in float64, cfg"""
+    return state_dict_of(fx, torch.float64), (str(fx["family"]), str(fx["act"]))
 
 
 # ---- 1. layout ---------------------------------------------------------------------------------------------------------------------
@@ -191,10 +158,6 @@ def test_argument_validation_of_every_new_entry_point():
     one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
     ref = ctypes.byref
 
-    def fails(rc, fragment):
-        assert rc < 0
-        assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
-
     fwd = lambda d, x, B, wsf, z, losses: lib.ardae_vae_forward(ref(d), one, one, x, None, B, 1.0, 1.0, 7, 0, None, one, wsf, z, None, losses, None)
     fwd_dev = lambda d, st: lib.ardae_vae_forward_dev(ref(d), one, one, one, None, 4, st, 1.0, 7, 0, None, one, big, one, None, one, None)
     bwd = lambda d, B, wsf, g: lib.ardae_vae_backward(ref(d), one, one, one, B, 1.0, 1.0, one, wsf, g, 0.0, None)
@@ -272,18 +235,17 @@ def test_argument_validation_of_every_new_entry_point():
 @pytest.mark.parametrize("family,case", case_names())
 def test_restatement_is_the_reference_in_float64(golden_dir, family, case):
     fx = load(golden_dir, f"vae_{family}_{case}")
-    act, D = str(fx["act"]), int(fx["shape"][1])
-    p = state_dict_of(fx, torch.float64)
-    x, eps = torch.tensor(fx["x"]).double(), torch.tensor(fx["eps"]).double()
+    D = int(fx["shape"][1])
+    p, cfg = restate(fx)
+    assert cfg[0] == family
+    x, eps = R.t64(fx["x"]), R.t64(fx["eps"])
     for b, beta in BETAS.items():
-        out, grads = loss_and_grads(family, p, act, x, eps, beta, 1.0 / D)
+        out, grads = loss_and_grads(p, cfg, x, eps, beta, scale=1.0 / D)
         for k in ("z", "mean", "loss", "recon", "kld"):
             assert rel(out[k], fx[f"{b}/{k}_f64"]) <= 1e-12, (b, k)
         assert rel(out["mu"], fx["mu_f64"]) <= 1e-12 and rel(out["lv"], fx["lv_f64"]) <= 1e-12
-        assert set(grads) == {k[len(b) + 7:] for k in fx if k.startswith(f"{b}/g_f64/")}
-        for k, g in grads.items():
-            assert rel(g, fx[f"{b}/g_f64/{k}"]) <= 1e-12, (b, k)
-    lp = logprob_rows(family, p, act, x, torch.tensor(fx["lp/eps"]).double()).mean()
+        R.check_grads_f64(grads, fx, b, 1e-12)
+    lp = logprob_rows(p, cfg, x, R.t64(fx["lp/eps"])).mean()
     assert rel(lp, fx["lp/value_f64"]) <= 1e-12
     # the fp32 fixture is the same computation at fp32's precision
     assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
@@ -292,18 +254,10 @@ def test_restatement_is_the_reference_in_float64(golden_dir, family, case):
 @pytest.mark.parametrize("family", ["mnist", "toy"])
 def test_restated_trajectory_is_the_reference_in_float64(golden_dir, family):
     fx = load(golden_dir, f"vae_traj_{family}")
-    act, D = str(fx["act"]), int(fx["shape"][1])
-    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
-                        beta_annealing=int(fx["cfg/beta_annealing"]))
-    p, st = state_dict_of(fx, torch.float64), {}
-    for s in range(int(fx["cfg/steps"])):
-        beta = cfg.beta_at(s)
-        assert beta == float(fx[f"{s}/beta"])
-        out, grads = loss_and_grads(family, p, act, torch.tensor(fx[f"{s}/x"]).double(), torch.tensor(fx[f"{s}/eps"]).double(), beta, 1.0 / D)
-        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
-        assert rel(out["loss"], fx[f"{s}/loss_f64"]) <= 1e-10
-        for k, v in p.items():
-            assert rel(v, fx[f"{s}/p_f64/{k}"]) <= 1e-10, (s, k)
+    p, cfg = restate(fx)
+    D = int(fx["shape"][1])
+    steps = R.trajectory(fx, p, lambda p, x, eps, beta: loss_and_grads(p, cfg, R.t64(x), R.t64(eps), beta, scale=1.0 / D))
+    R.check_traj_f64(steps, fx, 1e-10, keys=("loss",))
     assert float(fx["2/beta"]) < 1.0 == float(fx["3/beta"]) == float(fx["4/beta"])          # the ramp ends inside the run
 
 

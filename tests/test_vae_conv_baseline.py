@@ -5,23 +5,21 @@ padding and crop as models/vae/conv.py) that the GPU tests lean on - pinned here
 The fixtures (tools/gen_vae_conv_golden.py) do not store the 703 405 parameters: `conv_params` regenerates them from the stored seed with the
 oracle's platform-independent initialiser, exactly as the tool did."""
 import ctypes
+import functools
 import math
 
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
-from test_ardae_uncond import ACTS, rel
-from test_vae_baseline import BETAS, adam_step, lin, load
+import vae_restate as R
+from vae_restate import BETAS, TOL64, fails, lin, load, rel, relaxed_sample
 
 CASES = ("z32_b3", "z6_b5")
 D = 784
-TOL64 = 1e-9          # float64 restatement against the reference's float64 outputs: losses, full tensors and summaries
 
 
 def conv_params(z, seed, special, dtype=torch.float32):
@@ -41,85 +39,39 @@ def fixture_params(fx, dtype=torch.float32):
     return {k: v.to(dtype) for k, v in conv_params(int(fx["shape"][1]), int(fx["seed"]), bool(int(fx["special"]))).items()}
 
 
-def summary(t):
-    t = t.detach().reshape(-1)
-    return torch.cat([torch.stack([t.norm(), t.sum()]), t[:8]])
-
-
-# ---- the test-side oracle: the family restated in plain torch ----------------------------------------------------------------------
+# ---- the test-side oracle: the family restated in plain torch (trunk and decoder: vae_restate) ---------------------------------------
 def encode(p, act, x):
     """Encoder.forward up to the statistics (vae/conv.py:59-72)"""
-    a = ACTS[act]
-    hdn = (2 * x - 1).view(-1, 1, 28, 28)
-    for i in (1, 2, 3):
-        hdn = a(F.conv2d(hdn, p[f"encode.conv{i}.weight"], p[f"encode.conv{i}.bias"], stride=2, padding=2))
-    hdn = a(lin(p, "encode.fc", hdn.reshape(hdn.size(0), -1)))
+    hdn = R.ACTS[act](lin(p, "encode.fc", R.conv_trunk(p, "encode.", act, x)))
     return lin(p, "encode.reparam.mean_fn", hdn), lin(p, "encode.reparam.logvar_fn", hdn)
-
-
-def decode_logit(p, act, z):
-    """Decoder.forward's logits as [R, 784] (vae/conv.py:121-131): ZeroPad2d((0, 1, 0, 1)) after deconv1, the 29 x 29 output cropped to 28 x 28"""
-    a = ACTS[act]
-    hdn = a(lin(p, "decode.fc.fc", a(lin(p, "decode.fc.layers.0", z)))).view(-1, 32, 4, 4)
-    hdn = F.pad(a(F.conv_transpose2d(hdn, p["decode.deconv1.weight"], p["decode.deconv1.bias"], stride=2, padding=2)), (0, 1, 0, 1))
-    hdn = a(F.conv_transpose2d(hdn, p["decode.deconv2.weight"], p["decode.deconv2.bias"], stride=2, padding=2))
-    logit = F.conv_transpose2d(hdn, p["decode.reparam.logit_fn.weight"], p["decode.reparam.logit_fn.bias"], stride=2, padding=2)
-    return logit[:, :, :28, :28].reshape(-1, D)
-
-
-def recon_rows(p, act, x, z):
-    logit = decode_logit(p, act, z)
-    return F.binary_cross_entropy_with_logits(logit, x, reduction="none").sum(1), logit
 
 
 def forward(p, act, x, eps, beta):
     """-> dict(mu, lv, z, mean, logit, loss, recon, kld): VAE.forward (vae/conv.py:170-201)"""
     mu, lv = encode(p, act, x)
     z = mu + torch.exp(0.5 * lv) * eps
-    kld = -0.5 * (1 + lv - mu ** 2 - lv.exp()).sum(1)
-    rec, logit = recon_rows(p, act, x, z)
+    kld = R.kld_rows(mu, lv)
+    rec, logit = R.conv_recon_rows(p, act, x, z)
     return dict(mu=mu, lv=lv, z=z, mean=torch.sigmoid(logit), logit=logit, loss=(rec + beta * kld).mean(), recon=rec.mean(), kld=kld.mean())
 
 
-def loss_and_grads(p, act, x, eps, beta, scale):
-    """-> forward's dict (detached) and {name: d (scale * loss) / d p}"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    out = forward(p, act, x, eps, beta)
-    grads = dict(zip(p, torch.autograd.grad(scale * out["loss"], list(p.values()))))
-    return {k: v.detach() for k, v in out.items()}, grads
-
-
-def relaxed_sample(logit, u):
-    """BernoulliDistribution.sample_logistic_sigmoid at temperature 1 on the uniform draw u (models/reparam.py:111-120)"""
-    return torch.sigmoid(logit + torch.log(u + 1e-20) - torch.log(1 - u + 1e-20))
+loss_and_grads = functools.partial(R.loss_and_grads, forward)      # (p, act, x, eps, beta, scale=) -> forward's dict (detached), {name: gradient}
 
 
 def logprob_rows(p, act, x, eps):
     """VAE.logprob before its mean (vae/conv.py:218-257) on injected draws eps [B, k, zd]"""
-    B, k, zd = eps.shape
-    mu, lv = encode(p, act, x)
-    mu, lv = mu[:, None, :], lv[:, None, :]
-    z = mu + torch.exp(0.5 * lv) * eps
-    c = math.log(2 * math.pi)
-    logq = (-0.5 * ((z - mu) ** 2 / lv.exp() + lv + c)).sum(2)
-    logprior = (-0.5 * (z ** 2 + c)).sum(2)
-    rec, _ = recon_rows(p, act, x[:, None, :].expand(B, k, D).reshape(B * k, D), z.reshape(B * k, zd))
-    lw = -rec.view(B, k) + logprior - logq
-    m = lw.max(1, keepdim=True)[0]
-    return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).view(B)
+    return R.gaussian_logprob_rows(*encode(p, act, x), x, eps, lambda xr, zr: R.conv_recon_rows(p, act, xr, zr)[0])
+
+
+def restate(fx):
+    """-> the fixture's parameters in float64, cfg (the activation)"""
+    return fixture_params(fx, torch.float64), str(fx["act"])
 
 
 def trajectory(fx):
     """The fixture's loop restated in float64: yields (step, forward's dict, the parameters after the vendored Adam's step)"""
-    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
-                        beta_annealing=int(fx["cfg/beta_annealing"]))
-    p, st, act = fixture_params(fx, torch.float64), {}, str(fx["act"])
-    for s in range(int(fx["cfg/steps"])):
-        beta = cfg.beta_at(s)
-        assert beta == float(fx[f"{s}/beta"])
-        out, grads = loss_and_grads(p, act, torch.tensor(fx[f"{s}/x"]).double(), torch.tensor(fx[f"{s}/eps"]).double(), beta, 1.0 / D)
-        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
-        yield s, out, p
+    p, act = restate(fx)
+    return R.trajectory(fx, p, lambda p, x, eps, beta: loss_and_grads(p, act, R.t64(x), R.t64(eps), beta, scale=1.0 / D))
 
 
 # ---- 1. layout, initialisation -----------------------------------------------------------------------------------------------------
@@ -177,29 +129,16 @@ def test_initialisation_of_do_xavier_and_do_m5bias():
 @pytest.mark.parametrize("case", CASES)
 def test_restatement_is_the_reference_in_float64(golden_dir, case):
     fx = load(golden_dir, f"vae_conv_{case}")
-    act = str(fx["act"])
-    p = fixture_params(fx, torch.float64)
-    x, eps, dec = (torch.tensor(fx[k]).double() for k in ("x", "eps", "dec_noise"))
+    p, act = restate(fx)
+    x, eps, dec = (R.t64(fx[k]) for k in ("x", "eps", "dec_noise"))
     for b, beta in BETAS.items():
-        out, grads = loss_and_grads(p, act, x, eps, beta, 1.0 / D)
+        out, grads = loss_and_grads(p, act, x, eps, beta, scale=1.0 / D)
         for k in ("z", "mean", "loss", "recon", "kld"):
             assert rel(out[k], fx[f"{b}/{k}_f64"]) <= TOL64, (b, k)
         assert rel(relaxed_sample(out["logit"], dec), fx[f"{b}/x_sample_f64"]) <= TOL64
         assert rel(out["mu"], fx["mu_f64"]) <= TOL64 and rel(out["lv"], fx["lv_f64"]) <= TOL64
-        full = {k[len(b) + 7:] for k in fx if k.startswith(f"{b}/g_f64/")}
-        summed = {k[len(b) + 8:] for k in fx if k.startswith(f"{b}/gs_f64/")}
-        assert full | summed == set(grads) and not full & summed
-        for k, g in grads.items():
-            assert (g.numel() <= 16384) == (k in full), k
-            if k in full:
-                assert rel(g, fx[f"{b}/g_f64/{k}"]) <= TOL64, (b, k)
-            else:
-                want = torch.tensor(fx[f"{b}/gs_f64/{k}"])
-                got = summary(g)
-                assert abs(float(got[0]) - float(want[0])) <= TOL64 * float(want[0]), (b, k)                 # L2 norm
-                assert abs(float(got[1]) - float(want[1])) <= TOL64 * float(want[0]) * math.sqrt(g.numel()), (b, k)   # the sum, on the scale of its terms
-                assert rel(got[2:], want[2:]) <= TOL64, (b, k)
-    lp = logprob_rows(p, act, x, torch.tensor(fx["lp/eps"]).double()).mean()
+        R.check_grads_f64(grads, fx, b, TOL64)
+    lp = logprob_rows(p, act, x, R.t64(fx["lp/eps"])).mean()
     assert rel(lp, fx["lp/value_f64"]) <= TOL64
     # the fp32 fixture is the same computation at fp32's precision
     assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
@@ -208,15 +147,7 @@ def test_restatement_is_the_reference_in_float64(golden_dir, case):
 def test_restated_trajectory_is_the_reference_in_float64(golden_dir):
     fx = load(golden_dir, "vae_traj_conv")
     assert int(fx["special"]) == 1 and int(fx["cfg/steps"]) == 4                # the run starts from the do_xavier / do_m5bias init
-    for s, out, p in trajectory(fx):
-        for k in ("loss", "recon", "kld"):
-            assert rel(out[k], fx[f"{s}/{k}_f64"]) <= TOL64, (s, k)
-        for k, v in p.items():
-            want = torch.tensor(fx[f"{s}/ps_f64/{k}"])
-            got = summary(v)
-            assert abs(float(got[0]) - float(want[0])) <= TOL64 * float(want[0]), (s, k)
-            assert abs(float(got[1]) - float(want[1])) <= TOL64 * float(want[0]) * math.sqrt(v.numel()), (s, k)
-            assert rel(got[2:], want[2:]) <= TOL64, (s, k)
+    R.check_traj_f64(trajectory(fx), fx, TOL64)
     assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
 
 
@@ -225,10 +156,6 @@ def test_argument_validation_of_kind_11_at_every_entry_point():
     lib = L.lib()
     one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
     ref = ctypes.byref
-
-    def fails(rc, fragment):
-        assert rc < 0
-        assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
 
     fwd = lambda d, x, B, wsf, z, losses: lib.ardae_vae_forward(ref(d), one, one, x, None, B, 1.0, 1.0, 7, 0, None, one, wsf, z, None, losses, None)
     fwd_dev = lambda d, st: lib.ardae_vae_forward_dev(ref(d), one, one, one, None, 4, st, 1.0, 7, 0, None, one, big, one, None, one, None)

@@ -1,7 +1,7 @@
 """GaussianDiagnostics, VaeEngine.diagnostics and PosteriorDiagnostics.final_pass on the device, at the smallest widths of each family.
 
 Criteria: histogram counts are EQUAL to numpy's on the returned arrays; latents of the non-auxiliary kinds are BIT-EQUAL to model.encode's (the same
-entry points on the same rows); MNISTAuxVAE / ToyAuxVAE latents meet TOL_LATENT (1e-5 relative L2, the bar tests/test_vae_baseline_gpu.py sets and
+entry points on the same rows); MNISTAuxVAE / ToyAuxVAE latents meet TOL_LATENT (1e-5 relative L2, the bar tests/vae_gpu_checks.py sets and
 tests/test_vae_aux_baseline_gpu.py holds ardae_vae_aux_iwae_draw's z to) against the float64 restatement; the two auxiliary conv kinds meet
 2 x TOL_LATENT against model(x, eps)[2] - each of the two routes is held to TOL_LATENT against float64 by those files, so they differ by at most twice
 that; results under different budgets are bit-equal."""
@@ -14,8 +14,8 @@ from ardae_amd import _lib as L
 from ardae_amd import rng
 from test_diagnostics_gpu import _images as ip_images
 from test_diagnostics_gpu import _model as ip_model
-from test_vae_aux_baseline_gpu import logq_rows, np64, rel
-from test_vae_baseline_gpu import TOL_LATENT
+from vae_gpu_checks import TOL_LATENT, np64, rel
+from vae_restate import aux_logq_rows as logq_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -26,7 +26,7 @@ BUILD = {"mnist": lambda: net.MNISTVAE(input_dim=24, h_dim=32, z_dim=8, nonlinea
          "auxmnist": lambda: net.MNISTAuxVAE(input_dim=24, noise_dim=10, h_dim=32, z_dim=8, nonlinearity="softplus", num_hidden_layers=2, clip_logvar="spm4"),
          "auxtoy": lambda: net.ToyAuxVAE(input_dim=2, noise_dim=2, h_dim=32, z_dim=2, nonlinearity="tanh", num_hidden_layers=1),
          "auxconv": lambda: net.MNISTConvAuxVAE(z0_dim=12, z_dim=8), "auxresconv": lambda: net.MNISTResConvAuxVAE(z0_dim=12, z_dim=8, c_dim=40)}
-AUX_MLP = {"auxmnist": ("mnist", "softplus", "spm4"), "auxtoy": ("toy", "tanh", None)}      # logq_rows' family, activation, clip
+AUX_MLP = {"auxmnist": ("mnist", "softplus", "spm4"), "auxtoy": ("toy", "tanh", None)}      # logq_rows' cfg: family, activation, clip
 _BUILT = {}
 
 
@@ -74,8 +74,7 @@ def test_latents_are_the_models_and_counts_are_numpys(kind):
     if not gd.aux:
         assert torch.equal(lat, m.encode(x, eps=eps)[0])                        # the same entry points on the same rows
     elif kind in AUX_MLP:
-        family, act, clip = AUX_MLP[kind]
-        want, _ = logq_rows(family, {n: np64(v) for n, v in m.named_parameters()}, act, clip, np64(x), np64(eps).reshape(N, 1, -1))
+        want, _ = logq_rows({n: np64(v) for n, v in m.named_parameters()}, AUX_MLP[kind], np64(x), np64(eps).reshape(N, 1, -1))
         err = rel(np64(lat), want)
         print(f"{kind}: latents against float64: rel L2 {err:.3e}")
         assert err <= TOL_LATENT

@@ -6,6 +6,7 @@ reference's float64 fixtures.  No GPU needed.
 The fixtures (tools/gen_vae_resconv_golden.py) do not store the parameters: `resconv_params` regenerates them from the stored seed with the
 oracle's platform-independent initialiser, exactly as the tool did."""
 import ctypes
+import functools
 import math
 
 import pytest
@@ -16,14 +17,12 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
-from test_ardae_uncond import rel
-from test_vae_baseline import BETAS, adam_step, lin, load
-from test_vae_conv_baseline import relaxed_sample, summary
+import vae_restate as R
+from vae_restate import BETAS, TOL64, fails, lin, load, rel, relaxed_sample
 
 CASES = ("z32_b3", "z6_c42_b5_ct")
 D = 784
 ELU = 3               # ARDAE_ACT_ELU
-TOL64 = 1e-9          # float64 restatement against the reference's float64 outputs: losses, full tensors and summaries (the conv file's value)
 
 
 def resconv_params(z, c_dim, seed, special, dtype=torch.float32):
@@ -43,82 +42,39 @@ def desc_of(z, c_dim, center):
     return L.ModelDesc(12, D, 0, c_dim, z, 1, ELU, 0 if center else L.MODEL_NO_CENTER)
 
 
-# ---- the test-side oracle: the family restated in plain torch ----------------------------------------------------------------------
+# ---- the test-side oracle: the family restated in plain torch (trunk and decoder: vae_restate) ---------------------------------------
 def encode(p, center, x):
     """Encoder.forward up to the statistics (vae/resconv.py:58-68)"""
-    h = (2 * x - 1 if center else x).view(-1, 1, 28, 28)
-    for i, st in zip((0, 2, 4, 6, 8), (2, 1, 2, 1, 2)):
-        h = F.elu(O.res_conv(p, f"encode.enc.{i}.", h, st, F.elu))
-    h = F.elu(O.res_linear(p, "encode.enc.11.", h.reshape(h.size(0), 512), True))
+    h = R.resconv_trunk(p, "encode.enc.", center, x)
     return lin(p, "encode.reparam.mean_fn", h), lin(p, "encode.reparam.logvar_fn", h)
-
-
-def decode_logit(p, z):
-    return O.resconv_decode(None, p, z)
-
-
-def tail_logit(p, y14):
-    """the decoder's last stage on y14 [R, 14, 14, 16] (NHWC): the x2 upsampling, then decode.dec.17 -> [R, 784]"""
-    u = F.interpolate(y14.permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=True)
-    return O.res_conv(p, "decode.dec.17.", u, 1, F.elu).reshape(y14.size(0), D)
-
-
-def recon_rows(p, x, z):
-    logit = decode_logit(p, z)
-    return F.binary_cross_entropy_with_logits(logit, x, reduction="none").sum(1), logit
 
 
 def forward(p, center, x, eps, beta):
     """-> dict(mu, lv, z, mean, logit, loss, recon, kld): VAE.forward (vae/resconv.py:161-181)"""
     mu, lv = encode(p, center, x)
     z = mu + torch.exp(0.5 * lv) * eps
-    kld = -0.5 * (1 + lv - mu ** 2 - lv.exp()).sum(1)
-    rec, logit = recon_rows(p, x, z)
+    kld = R.kld_rows(mu, lv)
+    rec, logit = R.resconv_recon_rows(p, x, z)
     return dict(mu=mu, lv=lv, z=z, mean=torch.sigmoid(logit), logit=logit, loss=(rec + beta * kld).mean(), recon=rec.mean(), kld=kld.mean())
 
 
-def loss_and_grads(p, center, x, eps, beta, scale):
-    """-> forward's dict (detached) and {name: d (scale * loss) / d p}"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    out = forward(p, center, x, eps, beta)
-    grads = dict(zip(p, torch.autograd.grad(scale * out["loss"], list(p.values()))))
-    return {k: v.detach() for k, v in out.items()}, grads
+loss_and_grads = functools.partial(R.loss_and_grads, forward)      # (p, center, x, eps, beta, scale=) -> forward's dict (detached), {name: gradient}
 
 
 def logprob_rows(p, center, x, eps):
     """VAE.logprob before its mean (vae/resconv.py:198-240) on injected draws eps [B, k, zd]"""
-    B, k, zd = eps.shape
-    mu, lv = encode(p, center, x)
-    mu, lv = mu[:, None, :], lv[:, None, :]
-    z = mu + torch.exp(0.5 * lv) * eps
-    c = math.log(2 * math.pi)
-    logq = (-0.5 * ((z - mu) ** 2 / lv.exp() + lv + c)).sum(2)
-    logprior = (-0.5 * (z ** 2 + c)).sum(2)
-    rec, _ = recon_rows(p, x[:, None, :].expand(B, k, D).reshape(B * k, D), z.reshape(B * k, zd))
-    lw = -rec.view(B, k) + logprior - logq
-    m = lw.max(1, keepdim=True)[0]
-    return (torch.log(torch.mean((lw - m).exp(), 1, keepdim=True) + 1e-10) + m).view(B)
+    return R.gaussian_logprob_rows(*encode(p, center, x), x, eps, lambda xr, zr: R.resconv_recon_rows(p, xr, zr)[0])
+
+
+def restate(fx):
+    """-> the fixture's parameters in float64, cfg (do_center)"""
+    return fixture_params(fx, torch.float64), bool(int(fx["do_center"]))
 
 
 def trajectory(fx):
     """The fixture's loop restated in float64: yields (step, forward's dict, the parameters after the vendored Adam's step)"""
-    cfg = net.VaeConfig(lr=float(fx["cfg/lr"]), beta1=float(fx["cfg/beta1"]), beta_init=float(fx["cfg/beta_init"]), beta_fin=float(fx["cfg/beta_fin"]),
-                        beta_annealing=int(fx["cfg/beta_annealing"]))
-    p, st, center = fixture_params(fx, torch.float64), {}, bool(int(fx["do_center"]))
-    for s in range(int(fx["cfg/steps"])):
-        beta = cfg.beta_at(s)
-        assert beta == float(fx[f"{s}/beta"])
-        out, grads = loss_and_grads(p, center, torch.tensor(fx[f"{s}/x"]).double(), torch.tensor(fx[f"{s}/eps"]).double(), beta, 1.0 / D)
-        adam_step(p, grads, st, cfg.lr, cfg.beta1, s + 1)
-        yield s, out, p
-
-
-def check_summary(got_t, want, what):
-    want = torch.tensor(want)
-    got = summary(got_t)
-    assert abs(float(got[0]) - float(want[0])) <= TOL64 * float(want[0]), what                                  # L2 norm
-    assert abs(float(got[1]) - float(want[1])) <= TOL64 * float(want[0]) * math.sqrt(got_t.numel()), what       # the sum, on the scale of its terms
-    assert rel(got[2:], want[2:]) <= TOL64, what
+    p, center = restate(fx)
+    return R.trajectory(fx, p, lambda p, x, eps, beta: loss_and_grads(p, center, R.t64(x), R.t64(eps), beta, scale=1.0 / D))
 
 
 # ---- 1. layout, initialisation, workspace sizes ------------------------------------------------------------------------------------
@@ -191,25 +147,16 @@ def test_initialisation_follows_the_weight_norm_init_and_do_m5bias():
 @pytest.mark.parametrize("case", CASES)
 def test_restatement_is_the_reference_in_float64(golden_dir, case):
     fx = load(golden_dir, f"vae_resconv_{case}")
-    center = bool(int(fx["do_center"]))
-    p = fixture_params(fx, torch.float64)
-    x, eps, dec = (torch.tensor(fx[k]).double() for k in ("x", "eps", "dec_noise"))
+    p, center = restate(fx)
+    x, eps, dec = (R.t64(fx[k]) for k in ("x", "eps", "dec_noise"))
     for b, beta in BETAS.items():
-        out, grads = loss_and_grads(p, center, x, eps, beta, 1.0 / D)
+        out, grads = loss_and_grads(p, center, x, eps, beta, scale=1.0 / D)
         for k in ("z", "mean", "loss", "recon", "kld"):
             assert rel(out[k], fx[f"{b}/{k}_f64"]) <= TOL64, (b, k)
         assert rel(relaxed_sample(out["logit"], dec), fx[f"{b}/x_sample_f64"]) <= TOL64
         assert rel(out["mu"], fx["mu_f64"]) <= TOL64 and rel(out["lv"], fx["lv_f64"]) <= TOL64
-        full = {k[len(b) + 7:] for k in fx if k.startswith(f"{b}/g_f64/")}
-        summed = {k[len(b) + 8:] for k in fx if k.startswith(f"{b}/gs_f64/")}
-        assert full | summed == set(grads) and not full & summed
-        for k, g in grads.items():
-            assert (g.numel() <= 16384) == (k in full), k
-            if k in full:
-                assert rel(g, fx[f"{b}/g_f64/{k}"]) <= TOL64, (b, k)
-            else:
-                check_summary(g, fx[f"{b}/gs_f64/{k}"], (b, k))
-    lp = logprob_rows(p, center, x, torch.tensor(fx["lp/eps"]).double()).mean()
+        R.check_grads_f64(grads, fx, b, TOL64)
+    lp = logprob_rows(p, center, x, R.t64(fx["lp/eps"])).mean()
     assert rel(lp, fx["lp/value_f64"]) <= TOL64
     # the last stage on its own is the decoder's last stage
     z = out["z"][:2]
@@ -217,7 +164,7 @@ def test_restatement_is_the_reference_in_float64(golden_dir, case):
     up = lambda t: F.interpolate(t, scale_factor=2, mode="bilinear", align_corners=True)      # noqa: E731
     h = F.elu(O.res_conv(p, "decode.dec.8.", F.elu(O.res_conv(p, "decode.dec.6.", up(h), 1, F.elu)), 1, F.elu))[:, :, :-1, :-1]
     h = F.elu(O.res_conv(p, "decode.dec.14.", F.elu(O.res_conv(p, "decode.dec.12.", up(h), 1, F.elu)), 1, F.elu))
-    assert rel(tail_logit(p, h.permute(0, 2, 3, 1)), out["logit"][:2]) <= TOL64
+    assert rel(R.resconv_tail_logit(p, h.permute(0, 2, 3, 1)), out["logit"][:2]) <= TOL64
     # the fp32 fixture is the same computation at fp32's precision
     assert rel(fx["b1/loss"], fx["b1/loss_f64"]) <= 1e-5 and rel(fx["lp/value"], fx["lp/value_f64"]) <= 1e-5
 
@@ -225,11 +172,7 @@ def test_restatement_is_the_reference_in_float64(golden_dir, case):
 def test_restated_trajectory_is_the_reference_in_float64(golden_dir):
     fx = load(golden_dir, "vae_traj_resconv")
     assert int(fx["special"]) == 1 and int(fx["cfg/steps"]) == 4 and float(fx["cfg/beta1"]) == 0.9        # the recipe's Adam, from the do_m5bias setting
-    for s, out, p in trajectory(fx):
-        for k in ("loss", "recon", "kld"):
-            assert rel(out[k], fx[f"{s}/{k}_f64"]) <= TOL64, (s, k)
-        for k, v in p.items():
-            check_summary(v, fx[f"{s}/ps_f64/{k}"], (s, k))
+    R.check_traj_f64(trajectory(fx), fx, TOL64)
     assert float(fx["1/beta"]) < 1.0 == float(fx["2/beta"]) == float(fx["3/beta"])          # the ramp ends inside the run
 
 
@@ -238,10 +181,6 @@ def test_argument_validation_of_kind_12_at_every_entry_point():
     lib = L.lib()
     one, big, small = ctypes.c_void_p(64), ctypes.c_size_t(1 << 40), ctypes.c_size_t(16)      # any non-null address: validation fails before it is read
     ref = ctypes.byref
-
-    def fails(rc, fragment):
-        assert rc < 0
-        assert fragment.encode() in lib.ardae_last_error(), lib.ardae_last_error()
 
     fwd = lambda d, x, B, wsf, z, losses: lib.ardae_vae_forward(ref(d), one, one, x, None, B, 1.0, 1.0, 7, 0, None, one, wsf, z, None, losses, None)
     fwd_dev = lambda d, st: lib.ardae_vae_forward_dev(ref(d), one, one, one, None, 4, st, 1.0, 7, 0, None, one, big, one, None, one, None)
