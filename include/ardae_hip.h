@@ -469,7 +469,7 @@ int ardae_model_vae_backward_sampler_dev(const ardae_model_desc* d, const float*
                                          float* workspace, size_t workspace_floats, float* grads, float grads_beta, void* stream);
 
 
-/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, toy.py, conv.py, resconv.py; csrc/vaemodel.hip, csrc/convvae.hip, csrc/resmodel.hip):
+/* ---- Gaussian-posterior VAE baselines (vae.py; models/vae/mnist.py, toy.py, conv.py, resconv.py; csrc/vaemodel.hip, csrc/convvae.hip, csrc/resvae.hip):
  * ardae_model_desc.kind 8 / 9 / 11 / 12 ------
  * The second trainer of the reference: an encoder MLP with a Gaussian head and its analytic KL, no sampler noise, no score network.
  *   kind 8 (MNISTVAE, `vae.py --model mnist`): encode.main.{layers.0..n_layers-2, fc}, encode.reparam.{mean_fn, logvar_fn}, decode.main.{layers.*, fc},
@@ -611,7 +611,7 @@ size_t ardae_conv_tail_workspace_floats(const ardae_model_desc* d, int R, int va
 int ardae_conv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* u1, int R, int variant, float* workspace,
                     size_t workspace_floats, float* logits, void* stream);
 
-/* The last stage of the residual-conv decoder on its own (kinds 12 and 19; csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
+/* The last stage of the residual-conv decoder on its own (kinds 12 and 19: csrc/resvae.hip, csrc/auxresvae.hip; the kernels and this entry point: csrc/resmodel.hip): y14 [R, 14, 14, 16] NHWC - the output of decode.dec.14 after its ELU -
  * -> bilinear x2 upsampling (align_corners) -> decode.dec.17 = ResConv2d(16 -> 1) -> logits [R, 784].  It reads the effective weights ardae_model_pack
  * composed into `packed`.
  *   variant 1: resconv_tail_kernel, ONE launch, a workgroup per image: the interpolation, hmid = ELU(conv3x3_0h(u28) + b) and
@@ -626,7 +626,7 @@ size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int
 int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const float* packed, const float* y14, int R, int variant, float* workspace,
                        size_t workspace_floats, float* logits, void* stream);
 
-/* ---- the hierarchical resconv baseline of vae.py (models/vae/auxresconv.py; csrc/resmodel.hip): ardae_model_desc.kind 19 ------
+/* ---- the hierarchical resconv baseline of vae.py (models/vae/auxresconv.py; csrc/auxresvae.hip): ardae_model_desc.kind 19 ------
  * The Gaussian counterpart of kind 6, `vae.py --model auxresconv` / `auxresconvct` (do_center False / True).  18 is not a kind.
  *   kind 19 (MNISTResConvAuxVAE; 28 x 28 x 1 and ELU only): ONE weight-normalised residual trunk inp_encode.enc.* (the trunk of kinds 5 / 6 / 12, on 2x - 1
  *                        unless ARDAE_MODEL_NO_CENTER) -> ctx [B, c_dim]; aux_encode.reparam.{mean_fn, logvar_fn} [noise_dim, c_dim] on ctx;

@@ -1,5 +1,5 @@
 // The auxiliary-variable Gaussian baselines of vae.py (ardae_model_desc.kind 14: MNISTAuxVAE `--model auxmnist`, 15: ToyAuxVAE `--model auxtoy`,
-// 17: MNISTConvAuxVAE `--model auxconv`, csrc/auxconvvae.hip, 19: MNISTResConvAuxVAE `--model auxresconv`, csrc/resmodel.hip); csrc/model.hip dispatches
+// 17: MNISTConvAuxVAE `--model auxconv`, csrc/auxconvvae.hip, 19: MNISTResConvAuxVAE `--model auxresconv`, csrc/auxresvae.hip); csrc/model.hip dispatches
 // to the families, the ardae_vae_* entry points of csrc/vaemodel.hip and the two ardae_vae_aux_* entry points of csrc/auxvae.hip through a family's
 // GaussFamily row.  What the auxiliary families share is declared here: the row kernels' launchers (csrc/auxvae.hip) and their algorithm - forward,
 // backward, encode_stats, the two evaluation passes, the mode-4 workspace - written once over a family's traits.

@@ -1,14 +1,10 @@
-// Weight-normalised residual-conv VAEs on gfx950 (ardae_model_desc.kind 5, 6, 12 and 19):
+// Weight-normalised residual-conv VAEs on gfx950: every kernel of the residual-conv kinds, what they share (csrc/resmodel.h: the residual block, the
+// trunk, the decoder of models/vae/resconv.py:79-136, the weight-norm pack and backward, the workspace pieces), the implicit kinds
 //   kind 5  ResConvIPVAE           models/ivae/resconv.py:53-245 (`--model resconvct-res`: do_center, enc_type 'res-wn-mlp')
 //   kind 6  MNISTResConvAuxIPVAE   models/ivae/auxresconv.py:48-255 + models/vae/auxresconv.py:26-185 (`--model auxresconvct`)
-//   kind 12 MNISTResConvVAE        models/vae/resconv.py:26-241 (`vae.py --model resconv`): the same trunk (width c_dim = h_dim), a plain Gaussian head
-//                                  encode.reparam.{mean_fn, logvar_fn} on it (no clip, one draw per image, the analytic KL of kinds 8 / 9 / 11) - driven
-//                                  by the ardae_vae_* entry points (csrc/vaemodel.hip dispatches here), not by the sampler calls
-//   kind 19 MNISTResConvAuxVAE     models/vae/auxresconv.py:254-424 (`vae.py --model auxresconv` / `auxresconvct`): the Gaussian counterpart of kind 6, joined
-//                                  from kind 12's trunk, head policy, decoder and weight-norm backward and the pair KL, seeds and evaluation bodies of
-//                                  csrc/auxvae.h (the section "kind 19" below)
-// all with the decoder of models/vae/resconv.py:79-136.  The shipped "implicit resconv" / "hierarchical resconv" recipes
-// (run_vae_dbmnist.sh) train them with ELU, an mlp-res cDAE, --std-scale 100.
+// and the entry points ardae_resconv_tail / ardae_resconv_mid.  The Gaussian kinds on the same trunk and decoder are files of their own: kind 12 in
+// csrc/resvae.hip, kind 19 in csrc/auxresvae.hip.  The shipped "implicit resconv" / "hierarchical resconv" recipes (run_vae_dbmnist.sh) train kinds
+// 5 / 6 with ELU, an mlp-res cDAE, --std-scale 100.
 //
 // Every residual block (models/layers2.py:305-352, models/layers.py:66-85) is
 //     out = W_h1 f(W_0h x + b_0h) + W_01 x + (b_h1 + b_01)           f = ELU inside ResConv2d, ReLU inside ResLinear
@@ -23,10 +19,8 @@
 
 #include "ardae_hip.h"
 #include "auxmodel.h"
-#include "auxvae.h"
 #include "common.h"
 #include "resmodel.h"
-#include "vaemodel.h"
 #include "ipmodel.h"
 
 namespace ardae {
@@ -69,11 +63,6 @@ __global__ __launch_bounds__(256) void wn_compose_batch_kernel(const WnComposeBa
 
 // dL/dW [O, I] -> dL/ddir, dL/dscale (and the bias gradients, plain copies) for up to WNB_MAX operators in one launch
 constexpr int WNB_MAX = 48;
-struct WnBwdItem {
-  const float* dW; const float* dir; const float* scale; const float* inv; const float* db;   // db: [O] bias gradient (scratch)
-  float* gdir; float* gscale; float* gbias;
-  int O, I, norm;
-};
 struct WnBwdBatch { int n; float beta; WnBwdItem it[WNB_MAX]; };
 __global__ __launch_bounds__(256) void wn_backward_kernel(const WnBwdBatch b) {
   __shared__ float red[256];
@@ -334,8 +323,8 @@ __global__ __launch_bounds__(RT_THREADS) void resconv_tail_kernel(const float* _
 //        (pos * 33 + c), pos within 9 of each other in a half: distinct banks or the same word.
 constexpr int RM_THREADS = 256, RM_STRIDE = 272, RM_U = 32 * RM_STRIDE, RM_H = 16 * RM_STRIDE, RM_Y8 = 64 * 33;
 // offsets of the six operators in the packed mid weights: dec[4].a, dec[4].s (K = 288), dec[4].h, dec[5].a, dec[5].s, dec[5].h (K = 144)
-constexpr int RM_W4A = 0, RM_W4S = 16 * 288, RM_W4H = 2 * 16 * 288, RM_W5A = RM_W4H + 16 * 144, RM_W5S = RM_W5A + 16 * 144, RM_W5H = RM_W5S + 16 * 144,
-              RM_WTOTAL = RM_W5H + 16 * 144;
+constexpr int RM_W4A = 0, RM_W4S = 16 * 288, RM_W4H = 2 * 16 * 288, RM_W5A = RM_W4H + 16 * 144, RM_W5S = RM_W5A + 16 * 144, RM_W5H = RM_W5S + 16 * 144;
+static_assert(RM_W5H + 16 * 144 == RM_WTOTAL, "csrc/resmodel.h reserves the packed mid weights");
 using f32x4 = float __attribute__((ext_vector_type(4)));
 
 struct MidPackArgs { const float* weff[6]; int K[6], off[6]; };
@@ -451,197 +440,93 @@ __global__ __launch_bounds__(RM_THREADS) void resconv_mid_kernel(const float* __
     ARDAE_LAUNCH_CHECK();                                                                     \
   } while (0)
 
-// ------------------------------------------------------------------------------------------------ layout
-// plain: the operator is an nn.Linear (weight at `dir`, no scale, effective weight = weight): ResMLP(layer='linear')
-struct WN { size_t dir, scale, bias; int O, I; bool norm; bool plain; };          // flat-parameter offsets; I = fan-in (C*9 for a conv)
-struct Blk { WN a, h, s; bool conv; int Cin, Cout, stride, Hin, Hout; bool same; };   // a = *_0h, h = *_h1, s = *_01 (skip; absent when same: identity)
-// One operator of ResConvIPVAE's sampler head `encode.fc` (models/ivae/resconv.py:101-116) on the B nz rows: a ResLinear (inner ReLU) or a
-// plain Linear, reading [trunk output | noise] (concat: the first one) or its predecessor's output, with ELU behind it or not
-struct HeadOp { bool res; Blk b; Lin l; int in, out; bool concat; int act; };
-// desc.flags bits 1-3 of kind 5: which head (ivae_ardae.py:323-442)
-enum { HEAD_RES_WN_MLP = 0, HEAD_MLP = 1, HEAD_RES_MLP = 2, HEAD_RES_WN_MLP_LIN = 3, HEAD_RES_MLP_LIN = 4 };
+}  // namespace
 
-struct ResLayout {
-  int kind, nd, zd, cdim, hdim;
-  bool center;                   // do_center: the trunk sees 2x - 1 (desc.flags without ARDAE_MODEL_NO_CENTER)
-  bool clipped;                  // kind 6 + ARDAE_MODEL_CLIPPED: MNISTResConvAuxIPVAEClipped (no 'spm4' clip, z0 keeps an unscaled eps0)
-  std::vector<Blk> trunk, dec;   // trunk: 5 conv + ResLinear(512 -> cdim); dec: 2 ResLinear + 5 conv
-  std::vector<HeadOp> head;      // kind 5: encode.fc (the shipped recipe: ResLinear(cdim + nd -> hdim), ELU, ResLinear(hdim -> zd), un-normalised WN operators)
-  Lin mu0{}, lv0{}, efc{}, mu{}, lv{};   // kinds 6 / 19: aux_encode.reparam.{mean,logvar}_fn, encode.fc.0, encode.reparam.{mean,logvar}_fn; kind 12: the last two
-  Lin rfc{}, mup{}, lvp{};               // kind 19: aux_decode.fc.0 on cat[ctx, z], aux_decode.reparam.{mean,logvar}_fn (behind the decoder)
-  size_t total = 0;
-
-  explicit ResLayout(const ardae_model_desc& d)
-      : kind(d.kind), nd(d.noise_dim), zd(d.z_dim), cdim(d.kind == 5 ? 512 : d.h_dim), hdim(d.h_dim), center(!(d.flags & ARDAE_MODEL_NO_CENTER)),
-        clipped(d.kind == 6 && (d.flags & ARDAE_MODEL_CLIPPED)) {
-    size_t off = 0;
-    auto wn = [&](int O, int I, bool norm, bool plain = false) {
-      WN w; w.O = O; w.I = I; w.norm = norm; w.plain = plain;
-      w.dir = off; off += (size_t)O * I; w.scale = off; if (!plain) off += O; w.bias = off; off += O;
-      return w;
-    };
-    auto block = [&](int Cout, int Cin, bool conv, int stride, int Hin, bool norm, bool plain = false, bool same = false) {
-      Blk b; b.conv = conv; b.Cin = Cin; b.Cout = Cout; b.stride = stride; b.Hin = Hin; b.same = same;
-      b.Hout = conv ? (Hin + 2 - 3) / stride + 1 : 1;
-      const int I = conv ? Cin * 9 : Cin, Ih = conv ? Cout * 9 : Cout;
-      b.a = wn(Cout, I, norm, plain); b.h = wn(Cout, Ih, norm, plain);
-      if (same) { b.s = b.h; b.s.O = 0; } else b.s = wn(Cout, I, norm, plain);
-      return b;
-    };
-    auto lin = [&](int out, int in) { return next_lin(off, out, in); };
-    trunk.push_back(block(16, 1, true, 2, 28, true));    // 28 -> 14
-    trunk.push_back(block(16, 16, true, 1, 14, true));
-    trunk.push_back(block(32, 16, true, 2, 14, true));   // 14 -> 7
-    trunk.push_back(block(32, 32, true, 1, 7, true));
-    trunk.push_back(block(32, 32, true, 2, 7, true));    // 7 -> 4
-    trunk.push_back(block(cdim, 512, false, 1, 1, true));
-    if (kind == 5) {
-      // encode.fc in the reference's parameter order (models/ivae/resconv.py:101-116, models/layers.py:477-515,559-622)
-      const int ht = (d.flags >> 1) & 7, nl = d.n_layers, cin = cdim + nd;
-      auto res_op = [&](int out, int in, bool plain, int act, bool concat) {
-        HeadOp o; o.res = true; o.b = block(out, in, false, 1, 1, false, plain, in == out); o.in = in; o.out = out; o.concat = concat; o.act = act;
-        o.l = Lin{0, 0, 0, 0};
-        head.push_back(o);
-      };
-      auto lin_op = [&](int out, int in, int act, bool concat) {
-        HeadOp o; o.res = false; o.l = lin(out, in); o.in = in; o.out = out; o.concat = concat; o.act = act; o.b = Blk{};
-        head.push_back(o);
-      };
-      if (ht == HEAD_MLP) {                       // MLP(cin -> hdim x nl -> zd), ELU after the hidden layers
-        for (int i = 0; i < nl; ++i) lin_op(hdim, i == 0 ? cin : hdim, ACT_ELU, i == 0);
-        lin_op(zd, hdim, ACT_NONE, false);
-      } else if (ht == HEAD_RES_WN_MLP || ht == HEAD_RES_MLP) {   // ResMLP(cin -> hdim x nl -> zd): ResLinear blocks, ELU between them
-        const bool plain = ht == HEAD_RES_MLP;
-        for (int i = 0; i < nl; ++i) res_op(hdim, i == 0 ? cin : hdim, plain, ACT_ELU, i == 0);
-        res_op(zd, hdim, plain, ACT_NONE, false);
-      } else {                                    // Sequential(ResMLP(cin -> hdim x (nl - 1) -> hdim, ELU on its output), Linear(hdim -> zd))
-        const bool plain = ht == HEAD_RES_MLP_LIN;
-        for (int i = 0; i < nl - 1; ++i) res_op(hdim, i == 0 ? cin : hdim, plain, ACT_ELU, i == 0);
-        res_op(hdim, nl - 1 == 0 ? cin : hdim, plain, ACT_ELU, nl - 1 == 0);
-        lin_op(zd, hdim, ACT_NONE, false);
-      }
-    } else if (kind == 12) {
-      mu = lin(zd, cdim); lv = lin(zd, cdim);
-    } else {
-      mu0 = lin(nd, cdim); lv0 = lin(nd, cdim); efc = lin(cdim, cdim + nd); mu = lin(zd, cdim); lv = lin(zd, cdim);
-    }
-    dec.push_back(block(cdim, zd, false, 1, 1, true));
-    dec.push_back(block(512, cdim, false, 1, 1, true));
-    dec.push_back(block(32, 32, true, 1, 8, true));
-    dec.push_back(block(32, 32, true, 1, 8, true));
-    dec.push_back(block(16, 32, true, 1, 14, true));
-    dec.push_back(block(16, 16, true, 1, 14, true));
-    dec.push_back(block(1, 16, true, 1, 28, true));
-    if (kind == 19) { rfc = lin(cdim, cdim + zd); mup = lin(nd, cdim); lvp = lin(nd, cdim); }
-    total = off;
-  }
-};
-
-// offsets into the packed buffer
-struct WNPk { size_t weff, inv, f, b; };
-struct BlkPk { WNPk a, h, s; size_t bsum; size_t a_fi, a_fn, a_bi, s_fi, s_fn, s_bi; };   // *_fi / *_fn / *_bi: image half / noise half of a concat-input operator
-struct LinPk { size_t f, b, fi, fn, bi, bn; };   // fi / fn: image / noise columns forward; bi / bn: their transposes
-struct ResPacked {
-  std::vector<BlkPk> trunk, dec;
-  struct HeadPk { BlkPk k; LinPk lk; };
-  std::vector<HeadPk> head;
-  LinPk mu0{}, lv0{}, efc{}, mu{}, lv{}, rfc{}, mup{}, lvp{};
-  size_t mid_w = 0;              // kind 19: resconv_mid_kernel's weights (res_pack fills them after the pack launch)
-  ResPacked(const ResLayout& P, PackList& pl) {
-    // an operator's panels are packed from its effective weight: composed into the packed buffer at k.weff by res_pack's
-    // compose launch (weight norm), or the parameter itself (plain nn.Linear operator, whose weff / inv stay unused)
-    auto wn_panel = [&](const WN& w, const WNPk& k, int col0, int nout, int kk, bool tr) {
-      return pl.panel((w.plain ? w.dir : k.weff) + col0, w.I, nout, kk, tr, !w.plain);
-    };
-    auto wn = [&](const WN& w) {
-      WNPk k; k.weff = pl.take((size_t)w.O * w.I); k.inv = pl.take(w.O);
-      k.f = wn_panel(w, k, 0, w.O, w.I, false); k.b = wn_panel(w, k, 0, w.I, w.O, true);
-      return k;
-    };
-    auto blk = [&](const Blk& b, int split) {
-      BlkPk k; k.a = wn(b.a); k.h = wn(b.h); k.s = b.same ? k.h : wn(b.s); k.bsum = pl.take(b.Cout);
-      k.a_fi = k.a_fn = k.a_bi = k.s_fi = k.s_fn = k.s_bi = 0;
-      if (split) {   // concat input [image part (split columns) | noise part]  (a concat block always has its projected skip: cdim + nd != Cout)
-        const int nn = b.a.I - split;
-        k.a_fi = wn_panel(b.a, k.a, 0, b.a.O, split, false); k.a_fn = wn_panel(b.a, k.a, split, b.a.O, nn, false); k.a_bi = wn_panel(b.a, k.a, 0, split, b.a.O, true);
-        k.s_fi = wn_panel(b.s, k.s, 0, b.s.O, split, false); k.s_fn = wn_panel(b.s, k.s, split, b.s.O, nn, false); k.s_bi = wn_panel(b.s, k.s, 0, split, b.s.O, true);
-      }
-      return k;
-    };
-    auto lin = [&](const Lin& l, int split) {
-      LinPk k; pl.pair(l, k.f, k.b); k.fi = k.fn = k.bi = k.bn = 0;
-      if (split) {
-        k.fi = pl.panel(l.w, l.in, l.out, split, false); k.fn = pl.panel(l.w + split, l.in, l.out, l.in - split, false);
-        k.bi = pl.panel(l.w, l.in, split, l.out, true); k.bn = pl.panel(l.w + split, l.in, l.in - split, l.out, true);
-      }
-      return k;
-    };
-    for (auto& b : P.trunk) trunk.push_back(blk(b, 0));
-    if (P.kind == 5) {
-      for (auto& o : P.head) {
-        HeadPk hp{};
-        if (o.res) hp.k = blk(o.b, o.concat ? P.cdim : 0); else hp.lk = lin(o.l, o.concat ? P.cdim : 0);
-        head.push_back(hp);
-      }
-    } else if (P.kind == 12) { mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
-    else { mu0 = lin(P.mu0, 0); lv0 = lin(P.lv0, 0); efc = lin(P.efc, P.cdim); mu = lin(P.mu, 0); lv = lin(P.lv, 0); }
-    for (auto& b : P.dec) dec.push_back(blk(b, 0));
-    if (P.kind == 19) { rfc = lin(P.rfc, P.cdim); mup = lin(P.mup, 0); lvp = lin(P.lvp, 0); mid_w = pl.take(RM_WTOTAL); }
-  }
-  explicit ResPacked(const ResLayout& P, PackList&& sizing = PackList()) : ResPacked(P, sizing) {}   // offsets only
-};
-
-// the descriptor rules of kind 12 (input_dim 784, noise_dim 0, h_dim = c_dim >= 1, z_dim >= 1, n_layers 1, ELU, flags within ARDAE_MODEL_NO_CENTER)
-int resvae_desc_check(const ardae_model_desc* d) {
-  ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 12 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
-  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind 12, got %d", d->flags);
-  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTResConvVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
-  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 12, got %d", d->n_layers);
+// ================================================================================================ what the residual-conv kinds share (csrc/resmodel.h)
+int res_gauss_desc_check(const ardae_model_desc* d, const char* cls, const char* elu_assert) {
+  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind %d, got %d", d->kind, d->flags);
+  ARDAE_CHECK_ARG(d->input_dim == 784, "model: %s is hard-wired to 28x28x1 inputs (input_dim 784), got %d", cls, d->input_dim);
+  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind %d, got %d", d->kind, d->n_layers);
   ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
-  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 12 takes ELU only (--model-nonlin elu; models/vae/resconv.py:145 asserts it), got activation %d", d->act);
+  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind %d takes ELU only (--model-nonlin elu; %s asserts it), got activation %d", d->kind, elu_assert, d->act);
   return 0;
 }
 
-// the descriptor rules of kind 19 (input_dim 784, 1 <= noise_dim <= AV_NMAX, h_dim = c_dim >= 1, z_dim >= 1, n_layers 1, ELU, flags within ARDAE_MODEL_NO_CENTER)
-int auxresvae_desc_check(const ardae_model_desc* d) {
-  ARDAE_CHECK_ARG(d->noise_dim >= 1 && d->noise_dim <= AV_NMAX, "model: noise_dim must be 1 .. %d for kind 19 (the width of z0), got %d", AV_NMAX,
-                  d->noise_dim);
-  ARDAE_CHECK_ARG((d->flags & ~ARDAE_MODEL_NO_CENTER) == 0, "model: flags must be 0 or ARDAE_MODEL_NO_CENTER for kind 19, got %d", d->flags);
-  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTResConvAuxVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
-  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 19, got %d", d->n_layers);
-  ARDAE_CHECK_ARG(d->h_dim >= 1 && d->z_dim >= 1, "model: bad dimensions (h_dim = c_dim %d, z_dim %d)", d->h_dim, d->z_dim);
-  ARDAE_CHECK_ARG(d->act == ACT_ELU, "model: kind 19 takes ELU only (--model-nonlin elu; models/vae/auxresconv.py:278 asserts it), got activation %d", d->act);
-  return 0;
-}
-
-// the descriptor rules of kinds 5 / 6
-int res_desc_check(const ardae_model_desc* d) {
-  ARDAE_TRY(desc_flags_ok(d, ARDAE_MODEL_NO_CENTER | ARDAE_MODEL_HEAD_MASK | ARDAE_MODEL_CLIPPED));
-  ARDAE_CHECK_ARG(d->input_dim == 784 && d->noise_dim >= 1 && d->z_dim >= 1 && d->h_dim >= 1 && d->act == ACT_ELU && (d->kind == 6 || (d->n_layers >= 1 && d->n_layers <= 4)),
-                  "model: the residual-conv models are 28x28x1, ELU, and (kind 5) 1 .. 4 hidden layers in the sampler head");
-  const int ht = (d->flags >> 1) & 7;
-  ARDAE_CHECK_ARG(d->kind != 5 || ht <= HEAD_RES_MLP_LIN, "model: unknown sampler head %d (desc.flags bits 1-3)", ht);
-  ARDAE_CHECK_ARG(d->kind == 5 || ht == 0, "model: the sampler-head bits of desc.flags belong to kind 5");
-  ARDAE_CHECK_ARG(d->kind == 6 || !(d->flags & ARDAE_MODEL_CLIPPED), "model: ARDAE_MODEL_CLIPPED belongs to kind 6");
-  // a concat block needs its projected skip (same_dim would make the skip the 612-wide concat itself)
-  ARDAE_CHECK_ARG(d->kind != 5 || ht == HEAD_MLP || 512 + d->noise_dim != d->h_dim,
-                  "model: ResConvIPVAE with c_dim + noise_dim == h_dim (identity skip over the concat input) is not built");
-  return 0;
-}
-
-// saved activations of one block
-struct BlkBuf { float *colsx, *hmid, *colsh, *out; };
+// ------------------------------------------------------------------------------------------------ workspace carving
 size_t blk_rows(const Blk& b, int images) { return (size_t)images * b.Hout * b.Hout; }
-void blk_carve(const Blk& b, int images, Bump& ws, BlkBuf& u, bool keep_cols) {
+void blk_carve(const Blk& b, int images, Bump& ws, BlkBuf& u) {
   const size_t R = blk_rows(b, images);
   u.colsx = b.conv ? ws.take(R * b.a.I) : nullptr;
   u.hmid = ws.take(R * b.Cout);
   u.colsh = b.conv ? ws.take(R * b.h.I) : nullptr;
   u.out = ws.take(R * b.Cout);
-  (void)keep_cols;
+}
+static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+void res_trunk_carve(const ResLayout& P, Bump& ws, int B, ResWs& W) {
+  W.x2 = ws.take((size_t)B * 784);
+  W.tb.resize(P.trunk.size());
+  for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.tb[i]);
+  W.flat = ws.take((size_t)B * 512);
+  W.inp = W.tb.back().out;
 }
 
-// forward of a residual block on `images` images (conv) / rows (linear); x: [images*Hin*Hin, Cin]; act_out: ELU after the block or none
+void res_decoder_carve(const ResLayout& P, Bump& ws, size_t R, DecRuns runs, ResWs& W) {
+  auto on = [&](size_t i) { return i < 4 || (i < 6 ? runs.mid : runs.tail); };
+  float *colsx = nullptr, *colsh = nullptr;
+  if (!runs.keep) {
+    size_t cx = 0, ch = 0;
+    for (size_t i = 0; i < P.dec.size(); ++i)
+      if (on(i) && P.dec[i].conv) { cx = max_sz(cx, blk_rows(P.dec[i], (int)R) * P.dec[i].a.I); ch = max_sz(ch, blk_rows(P.dec[i], (int)R) * P.dec[i].h.I); }
+    colsx = ws.take(cx); colsh = ws.take(ch);
+  }
+  W.db.assign(P.dec.size(), BlkBuf{nullptr, nullptr, nullptr, nullptr});
+  for (size_t i = 0; i < P.dec.size(); ++i) {
+    const Blk& b = P.dec[i];
+    const size_t rows = blk_rows(b, (int)R);
+    BlkBuf& u = W.db[i];
+    if (on(i)) {          // blk_carve's order
+      u.colsx = !b.conv ? nullptr : runs.keep ? ws.take(rows * b.a.I) : colsx;
+      u.hmid = ws.take(rows * b.Cout);
+      u.colsh = !b.conv ? nullptr : runs.keep ? ws.take(rows * b.h.I) : colsh;
+    }
+    if (on(i) || i == 5) u.out = ws.take(rows * b.Cout);
+  }
+  W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32);
+  W.c7 = runs.mid ? ws.take(R * 49 * 32) : nullptr; W.u14 = runs.mid ? ws.take(R * 196 * 32) : nullptr;
+  W.u28 = runs.tail ? ws.take(R * 784 * 16) : nullptr;
+}
+
+void res_bwd_carve(const ResLayout& P, Bump& ws, int B, size_t R, size_t head_wgrad_floats, ResWs& W) {
+  W.rec_row = ws.take(R); W.pri_row = ws.take(R); W.dlogit = ws.take(R * 784); W.dzq = ws.take(R * P.zd);
+  // the largest per-block scratch: decoder convs at 28 x 28 (R images) and the trunk's first convs (B images)
+  size_t mg = 0, mc = 0;
+  auto upd = [&](const Blk& b, size_t images) {
+    const size_t rows = images * b.Hout * b.Hout;
+    mg = max_sz(mg, rows * b.Cout);
+    mc = max_sz(mc, rows * max_sz(b.h.I, b.a.I));
+  };
+  for (auto& b : P.trunk) upd(b, B);
+  for (auto& b : P.dec) upd(b, R);
+  W.sc.g = ws.take(mg); W.sc.dh = ws.take(mg); W.sc.dcols = ws.take(mc);
+  const size_t act_max = max_sz(R * 784 * 16, (size_t)B * 196 * 16);     // largest activation map (decoder 28 x 28 x 16)
+  W.da = ws.take(act_max); W.dbuf = ws.take(act_max);
+  W.dflat = ws.take((size_t)B * 512); W.dinp = ws.take((size_t)B * P.cdim);
+  W.dR0 = ws.take(R * max_sz(P.hdim, P.cdim)); W.dR1 = ws.take(R * max_sz(P.hdim, P.cdim));
+  W.dB0 = ws.take((size_t)B * max_sz(P.hdim, P.cdim)); W.dB1 = ws.take((size_t)B * max_sz(P.hdim, P.cdim)); W.dB2 = ws.take((size_t)B * max_sz(P.hdim, P.cdim));
+  W.dweff = ws.take(P.total); W.dbias = ws.take(P.total / 8 + 4096);
+  size_t wsf = head_wgrad_floats;
+  auto wupd = [&](const Blk& b, size_t images) {
+    const int rows = (int)(images * b.Hout * b.Hout);
+    wsf = max_sz(wsf, wgrad_scratch_floats(rows, b.Cout, b.h.I) + wgrad_scratch_floats(rows, b.Cout, b.s.I) + wgrad_scratch_floats(rows, b.Cout, b.a.I));
+  };
+  for (auto& b : P.trunk) wupd(b, B);
+  for (auto& b : P.dec) wupd(b, R);
+  W.wscratch_floats = wsf + 1024;
+  W.wscratch = ws.take(W.wscratch_floats);
+}
+
+// ------------------------------------------------------------------------------------------------ forward pieces
 int blk_fwd(const Blk& b, const BlkPk& k, const float* params, const float* packed, const float* x, int images, int act_out, BlkBuf& u, hipStream_t st) {
   const int R = (int)blk_rows(b, images);
   const float* cx = x;
@@ -665,40 +550,63 @@ int blk_fwd(const Blk& b, const BlkPk& k, const float* params, const float* pack
   return 0;
 }
 
-// upsample x2 + dec[6] on R images in one launch: y14 [R, 14, 14, 16] (dec[5]'s output after its ELU) -> logits [R, 784]
 int tail_fused(const Blk& b, const BlkPk& k, const float* params, const float* packed, const float* y14, int R, float* logits, hipStream_t st) {
   hipLaunchKernelGGL(resconv_tail_kernel, dim3((unsigned)R), dim3(RT_THREADS), 0, st, y14, packed + k.a.weff, params + b.a.bias, packed + k.h.weff,
                      packed + k.s.weff, packed + k.bsum, logits);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
-// which tail the decode-only path of kinds 12 / 19 runs (ardae_resconv_tail's variant 0): the fused kernel, unless ARDAE_RESCONV_TAIL_UNFUSED=1 under
-// ARDAE_DEBUG_KNOBS=1.  The mode-2 workspace of kinds 12 / 19 is sized for the answer.
-bool tail_fused_default() {
-  const char* knob = debug_knob("ARDAE_RESCONV_TAIL_UNFUSED");
+static bool knob_off(const char* name) {
+  const char* knob = debug_knob(name);
   return !(knob && knob[0] == '1');
 }
-// crop + upsample + dec[4] + dec[5] on R images in one launch: y8 [R, 8, 8, 32] (dec[3]'s output after its ELU) -> y14 [R, 14, 14, 16]
-int mid_fused(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* y8, int R, float* y14, hipStream_t st) {
-  hipLaunchKernelGGL(resconv_mid_kernel, dim3((unsigned)R), dim3(RM_THREADS), 0, st, y8, packed + K.mid_w, params + P.dec[4].a.bias, packed + K.dec[4].bsum,
+bool tail_fused_default() { return knob_off("ARDAE_RESCONV_TAIL_UNFUSED"); }
+bool mid_fused_default() { return knob_off("ARDAE_RESCONV_MID_UNFUSED"); }
+int mid_fused(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* mid_w, const float* y8, int R, float* y14,
+              hipStream_t st) {
+  hipLaunchKernelGGL(resconv_mid_kernel, dim3((unsigned)R), dim3(RM_THREADS), 0, st, y8, mid_w, params + P.dec[4].a.bias, packed + K.dec[4].bsum,
                      params + P.dec[5].a.bias, packed + K.dec[5].bsum, y14);
   ARDAE_LAUNCH_CHECK();
   return 0;
 }
-// which 14 x 14 stage the decode-only path of kind 19 runs (ardae_resconv_mid's variant 0; its mode-2 workspace is sized for the answer):
-// resconv_mid_kernel, unless ARDAE_RESCONV_MID_UNFUSED=1 under ARDAE_DEBUG_KNOBS=1
-bool mid_fused_default() {
-  const char* knob = debug_knob("ARDAE_RESCONV_MID_UNFUSED");
-  return !(knob && knob[0] == '1');
+int mid_unfused(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* y8, int R, float* c7, float* u14, BlkBuf& u4,
+                BlkBuf& u5, hipStream_t st) {
+  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 49 * 32, y8, 8, 7, 32, c7, (int64_t)R * 49 * 32);    // slicer[:, :, :-1, :-1]
+  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 196 * 32, (const float*)c7, 7, 32, u14, (int64_t)R * 196 * 32);
+  ARDAE_TRY(blk_fwd(P.dec[4], K.dec[4], params, packed, u14, R, ACT_ELU, u4, st));
+  return blk_fwd(P.dec[5], K.dec[5], params, packed, u4.out, R, ACT_ELU, u5, st);
 }
 
-// scratch of one block's backward (reused from block to block) and the gradient destinations of its three operators
-struct BwdScratch { float *g, *dh, *dcols; };
-struct WnGrad { float* dW; float* db; float beta; };   // beta: accumulate into the destination (plain operators write the gradient buffer itself)
-struct BlkGrad { WnGrad a, h, s; };
+int res_trunk_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* x, int B, ResWs& W, hipStream_t st) {
+  if (P.center) ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));       // do_center (ivae/resconv.py:131-132)
+  else ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 1.f, 0.f, W.x2, st));
+  const float* cur = W.x2;
+  for (size_t i = 0; i < 5; ++i) {
+    ARDAE_TRY(blk_fwd(P.trunk[i], K.trunk[i], params, packed, cur, B, ACT_ELU, W.tb[i], st));
+    cur = W.tb[i].out;
+  }
+  ARDAE_TRY(launch_nhwc_nchw(cur, B, 16, 32, W.flat, false, st));
+  return blk_fwd(P.trunk[5], K.trunk[5], params, packed, W.flat, B, ACT_ELU, W.tb[5], st);
+}
 
-// assign splits + scratch (the scratch is reused from batch to batch; the batch size is the wgrad_splits hint) and launch,
-// at most ARDAE_WGRAD_MAX_PROBLEMS per batch
+int res_decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* z, int R, ResWs& W, float* logits,
+                    hipStream_t st, bool fused_tail, const float* fused_mid_w) {
+  ARDAE_TRY(blk_fwd(P.dec[0], K.dec[0], params, packed, z, R, ACT_ELU, W.db[0], st));
+  ARDAE_TRY(blk_fwd(P.dec[1], K.dec[1], params, packed, W.db[0].out, R, ACT_ELU, W.db[1], st));
+  ARDAE_TRY(launch_nhwc_nchw(W.db[1].out, R, 16, 32, W.d4, true, st));                                    // view(-1, 32, 4, 4) -> NHWC
+  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 64 * 32, W.d4, 4, 32, W.u8, (int64_t)R * 64 * 32);
+  ARDAE_TRY(blk_fwd(P.dec[2], K.dec[2], params, packed, W.u8, R, ACT_ELU, W.db[2], st));
+  ARDAE_TRY(blk_fwd(P.dec[3], K.dec[3], params, packed, W.db[2].out, R, ACT_ELU, W.db[3], st));
+  if (fused_mid_w) ARDAE_TRY(mid_fused(P, K, params, packed, fused_mid_w, W.db[3].out, R, W.db[5].out, st));
+  else ARDAE_TRY(mid_unfused(P, K, params, packed, W.db[3].out, R, W.c7, W.u14, W.db[4], W.db[5], st));
+  if (fused_tail) return tail_fused(P.dec[6], K.dec[6], params, packed, W.db[5].out, R, logits, st);
+  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, W.db[5].out, 14, 16, W.u28, (int64_t)R * 784 * 16);
+  ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, W.u28, R, ACT_NONE, W.db[6], st));
+  if (logits && logits != W.db[6].out) ARDAE_TRY(launch_copy(W.db[6].out, (size_t)R * 784, logits, st));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ backward pieces
 int flush_wgrad(WgradList& wl, float* scratch, size_t scratch_floats, hipStream_t st) {
   while (wl.pending()) {
     const size_t n = std::min<size_t>(wl.pending(), ARDAE_WGRAD_MAX_PROBLEMS);
@@ -716,7 +624,6 @@ size_t wgrad_scratch_floats(int M, int O, int I) {
   return al64((size_t)sm * O * I) + al64((size_t)sm * 2 * O);
 }
 
-// backward of a block: d_out [R, Cout] (gradient w.r.t. the block's output AFTER act_out) -> d_x [rows_in, Cin] (may be null)
 int blk_bwd(const Blk& b, const BlkPk& k, const float* packed, const float* x, int images, int act_out, const BlkBuf& u, const float* d_out, float* d_x,
             const BwdScratch& sc, const BlkGrad& gr, float* wscratch, size_t wscratch_floats, hipStream_t st) {
   const int R = (int)blk_rows(b, images);
@@ -755,55 +662,203 @@ int blk_bwd(const Blk& b, const BlkPk& k, const float* packed, const float* x, i
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ workspace carving
-struct ResWs {
-  // trunk (B images)
-  float* x2; std::vector<BlkBuf> tb; float *flat, *inp;             // 2x-1, block buffers, NCHW-flattened conv output [B,512], trunk output [B,cdim]
-  // sampler (R = B*nz rows)
+WnGrad GradMap::wn(const WN& w, const WNPk& k) {
+  if (w.plain) return WnGrad{grads + w.dir, grads + w.bias, grads_beta};     // nn.Linear operator: the weight gradient IS the parameter gradient
+  WnGrad g; g.dW = dweff + w.dir; g.db = dbias + boff; g.beta = 0.f; boff += al64(w.O);
+  WnBwdItem it; it.dW = g.dW; it.dir = params + w.dir; it.scale = params + w.scale; it.inv = packed + k.inv; it.db = g.db;
+  it.gdir = grads + w.dir; it.gscale = grads + w.scale; it.gbias = grads + w.bias; it.O = w.O; it.I = w.I; it.norm = w.norm ? 1 : 0;
+  items.push_back(it);
+  return g;
+}
+GradMap grad_map(ResWs& W, const float* params, const float* packed, float* grads, float grads_beta) {
+  return GradMap{W.dweff, W.dbias, 0, {}, params, packed, grads, grads_beta};
+}
+
+int res_decoder_bwd(const ResLayout& P, const ResPacked& K, const float* packed, const float* z, ResWs& W, int R, GradMap& gm, hipStream_t st) {
+  // ---- decoder backward (d_out ping-pongs between W.da and W.dbuf)
+  std::vector<BlkGrad> gd(P.dec.size());
+  for (size_t i = 0; i < P.dec.size(); ++i) gd[i] = gm.blk(P.dec[i], K.dec[i]);
+  ARDAE_TRY(blk_bwd(P.dec[6], K.dec[6], packed, W.u28, R, ACT_NONE, W.db[6], W.dlogit, W.da, W.sc, gd[6], W.wscratch, W.wscratch_floats, st));      // -> d u28 [R,28,28,16]
+  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 196 * 16, W.da, 14, 16, W.dbuf, (int64_t)R * 196 * 16);
+  ARDAE_TRY(blk_bwd(P.dec[5], K.dec[5], packed, W.db[4].out, R, ACT_ELU, W.db[5], W.dbuf, W.da, W.sc, gd[5], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(blk_bwd(P.dec[4], K.dec[4], packed, W.u14, R, ACT_ELU, W.db[4], W.da, W.dbuf, W.sc, gd[4], W.wscratch, W.wscratch_floats, st));          // -> d u14 [R,14,14,32]
+  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 49 * 32, W.dbuf, 7, 32, W.da, (int64_t)R * 49 * 32);                                                 // -> d c7
+  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 64 * 32, W.da, 7, 8, 32, W.dbuf, (int64_t)R * 64 * 32);                                                    // -> d (block 3 out) [R,8,8,32]
+  ARDAE_TRY(blk_bwd(P.dec[3], K.dec[3], packed, W.db[2].out, R, ACT_ELU, W.db[3], W.dbuf, W.da, W.sc, gd[3], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(blk_bwd(P.dec[2], K.dec[2], packed, W.u8, R, ACT_ELU, W.db[2], W.da, W.dbuf, W.sc, gd[2], W.wscratch, W.wscratch_floats, st));            // -> d u8
+  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 16 * 32, W.dbuf, 4, 32, W.da, (int64_t)R * 16 * 32);                                                 // -> d d4 (NHWC)
+  ARDAE_TRY(launch_nhwc_nchw(W.da, R, 16, 32, W.dbuf, false, st));                                                                                    // -> NCHW-flat [R,512]
+  ARDAE_TRY(blk_bwd(P.dec[1], K.dec[1], packed, W.db[0].out, R, ACT_ELU, W.db[1], W.dbuf, W.da, W.sc, gd[1], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(blk_bwd(P.dec[0], K.dec[0], packed, z, R, ACT_ELU, W.db[0], W.da, W.dbuf, W.sc, gd[0], W.wscratch, W.wscratch_floats, st));               // -> dz (decoder part) [R,zd]
+  ARDAE_TRY(launch_axpy(W.dbuf, (int64_t)R * P.zd, 1.f, W.dzq, st));                                                                                 // dz total in W.dzq
+  return 0;
+}
+
+int res_trunk_wn_bwd(const ResLayout& P, const ResPacked& K, const float* packed, ResWs& W, int B, GradMap& gm, float grads_beta, hipStream_t st) {
+  // ---- trunk backward
+  std::vector<BlkGrad> gt(P.trunk.size());
+  for (size_t i = 0; i < P.trunk.size(); ++i) gt[i] = gm.blk(P.trunk[i], K.trunk[i]);
+  ARDAE_TRY(blk_bwd(P.trunk[5], K.trunk[5], packed, W.flat, B, ACT_ELU, W.tb[5], W.dinp, W.dflat, W.sc, gt[5], W.wscratch, W.wscratch_floats, st));
+  ARDAE_TRY(launch_nhwc_nchw(W.dflat, B, 16, 32, W.da, true, st));                                  // NCHW-flat gradient -> NHWC [B,4,4,32]
+  float *cur = W.da, *nxt = W.dbuf;
+  for (int i = 4; i >= 0; --i) {
+    const float* xin = i == 0 ? W.x2 : W.tb[i - 1].out;
+    ARDAE_TRY(blk_bwd(P.trunk[i], K.trunk[i], packed, xin, B, ACT_ELU, W.tb[i], cur, i == 0 ? nullptr : nxt, W.sc, gt[i], W.wscratch, W.wscratch_floats, st));
+    std::swap(cur, nxt);
+  }
+  // ---- dL/dW -> dL/d(direction, scale), bias gradients
+  for (size_t i0 = 0; i0 < gm.items.size(); i0 += WNB_MAX) {
+    WnBwdBatch bt;
+    bt.n = (int)std::min<size_t>(WNB_MAX, gm.items.size() - i0);
+    bt.beta = grads_beta;
+    for (int i = 0; i < bt.n; ++i) bt.it[i] = gm.items[i0 + i];
+    hipLaunchKernelGGL(wn_backward_kernel, dim3(32, bt.n), dim3(256), 0, st, bt);
+    ARDAE_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ pack
+int res_pack(const ResLayout& P, const ResPacked& K, const HeadBlks& head, PackList& pl, hipStream_t st) {
+  const float* params = pl.params; float* packed = pl.packed;
+  // what the panels are packed FROM: the weight-normalised operators' effective weights and every projected-skip block's bias sum,
+  // composed into the packed buffer ahead of the pack launch
+  std::vector<WnComposeItem> comp;
+  auto wn = [&](const WN& w, const WNPk& k) {
+    if (!w.plain) comp.push_back(WnComposeItem{params + w.dir, params + w.scale, packed + k.weff, packed + k.inv, w.O, w.I, w.norm ? 1 : 0, nullptr, nullptr});
+  };
+  auto blk = [&](const Blk& b, const BlkPk& k) {
+    wn(b.a, k.a); wn(b.h, k.h);
+    if (b.same) return;          // identity skip: no third operator, the block's bias is b_h1
+    wn(b.s, k.s);
+    comp.push_back(WnComposeItem{nullptr, nullptr, packed + k.bsum, nullptr, b.Cout, 0, 0, params + b.h.bias, params + b.s.bias});   // bsum = b_h + b_s
+  };
+  for (size_t i = 0; i < P.trunk.size(); ++i) blk(P.trunk[i], K.trunk[i]);
+  for (auto& h : head) blk(*h.first, *h.second);
+  for (size_t i = 0; i < P.dec.size(); ++i) blk(P.dec[i], K.dec[i]);
+  for (size_t i0 = 0; i0 < comp.size(); i0 += WNC_MAX) {
+    WnComposeBatch cb;
+    cb.n = (int)std::min<size_t>(WNC_MAX, comp.size() - i0);
+    int maxo = 1;
+    for (int i = 0; i < cb.n; ++i) {
+      cb.it[i] = comp[i0 + i];
+      maxo = std::max(maxo, cb.it[i].dir ? cb.it[i].O : ceil_div(cb.it[i].O, 256));
+    }
+    hipLaunchKernelGGL(wn_compose_batch_kernel, dim3(maxo, cb.n), dim3(256), 0, st, cb);
+    ARDAE_LAUNCH_CHECK();
+  }
+  return pl.launch(st);
+}
+int launch_mid_pack(const ResPacked& K, float* packed, size_t mid_w, hipStream_t st) {
+  MidPackArgs a;
+  const WNPk* ops[6] = {&K.dec[4].a, &K.dec[4].s, &K.dec[4].h, &K.dec[5].a, &K.dec[5].s, &K.dec[5].h};
+  const int off[6] = {RM_W4A, RM_W4S, RM_W4H, RM_W5A, RM_W5S, RM_W5H};
+  for (int i = 0; i < 6; ++i) { a.weff[i] = packed + ops[i]->weff; a.K[i] = i < 2 ? 288 : 144; a.off[i] = off[i]; }
+  hipLaunchKernelGGL(resconv_mid_pack_kernel, dim3(nblk(RM_WTOTAL)), dim3(256), 0, st, a, packed + mid_w);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ================================================================================================ kinds 5 / 6: the implicit-posterior families
+namespace {
+
+// One operator of ResConvIPVAE's sampler head `encode.fc` (models/ivae/resconv.py:101-116) on the B nz rows: a ResLinear (inner ReLU) or a
+// plain Linear, reading [trunk output | noise] (concat: the first one) or its predecessor's output, with ELU behind it or not
+struct HeadOp { bool res; Blk b; Lin l; int in, out; bool concat; int act; };
+// desc.flags bits 1-3 of kind 5: which head (ivae_ardae.py:323-442)
+enum { HEAD_RES_WN_MLP = 0, HEAD_MLP = 1, HEAD_RES_MLP = 2, HEAD_RES_WN_MLP_LIN = 3, HEAD_RES_MLP_LIN = 4 };
+
+struct IpResLayout : ResLayout {
+  int kind;
+  bool clipped;                  // kind 6 + ARDAE_MODEL_CLIPPED: MNISTResConvAuxIPVAEClipped (no 'spm4' clip, z0 keeps an unscaled eps0)
+  std::vector<HeadOp> head;      // kind 5: encode.fc (the shipped recipe: ResLinear(cdim + nd -> hdim), ELU, ResLinear(hdim -> zd), un-normalised WN operators)
+  Lin mu0{}, lv0{}, efc{}, mu{}, lv{};   // kind 6: aux_encode.reparam.{mean,logvar}_fn, encode.fc.0, encode.reparam.{mean,logvar}_fn
+  explicit IpResLayout(const ardae_model_desc& d)
+      : ResLayout(d, d.kind == 5 ? 512 : d.h_dim), kind(d.kind), clipped(d.kind == 6 && (d.flags & ARDAE_MODEL_CLIPPED)) {
+    ResWalk w;
+    trunk_blocks(w);
+    if (kind == 5) {
+      // encode.fc in the reference's parameter order (models/ivae/resconv.py:101-116, models/layers.py:477-515,559-622)
+      const int ht = (d.flags >> 1) & 7, nl = d.n_layers, cin = cdim + nd;
+      auto res_op = [&](int out, int in, bool plain, int act, bool concat) {
+        HeadOp o; o.res = true; o.b = w.block(out, in, false, 1, 1, false, plain, in == out); o.in = in; o.out = out; o.concat = concat; o.act = act;
+        o.l = Lin{0, 0, 0, 0};
+        head.push_back(o);
+      };
+      auto lin_op = [&](int out, int in, int act, bool concat) {
+        HeadOp o; o.res = false; o.l = w.lin(out, in); o.in = in; o.out = out; o.concat = concat; o.act = act; o.b = Blk{};
+        head.push_back(o);
+      };
+      if (ht == HEAD_MLP) {                       // MLP(cin -> hdim x nl -> zd), ELU after the hidden layers
+        for (int i = 0; i < nl; ++i) lin_op(hdim, i == 0 ? cin : hdim, ACT_ELU, i == 0);
+        lin_op(zd, hdim, ACT_NONE, false);
+      } else if (ht == HEAD_RES_WN_MLP || ht == HEAD_RES_MLP) {   // ResMLP(cin -> hdim x nl -> zd): ResLinear blocks, ELU between them
+        const bool plain = ht == HEAD_RES_MLP;
+        for (int i = 0; i < nl; ++i) res_op(hdim, i == 0 ? cin : hdim, plain, ACT_ELU, i == 0);
+        res_op(zd, hdim, plain, ACT_NONE, false);
+      } else {                                    // Sequential(ResMLP(cin -> hdim x (nl - 1) -> hdim, ELU on its output), Linear(hdim -> zd))
+        const bool plain = ht == HEAD_RES_MLP_LIN;
+        for (int i = 0; i < nl - 1; ++i) res_op(hdim, i == 0 ? cin : hdim, plain, ACT_ELU, i == 0);
+        res_op(hdim, nl - 1 == 0 ? cin : hdim, plain, ACT_ELU, nl - 1 == 0);
+        lin_op(zd, hdim, ACT_NONE, false);
+      }
+    } else {
+      mu0 = w.lin(nd, cdim); lv0 = w.lin(nd, cdim); efc = w.lin(cdim, cdim + nd); mu = w.lin(zd, cdim); lv = w.lin(zd, cdim);
+    }
+    decoder_blocks(w);
+    total = w.off;
+  }
+};
+
+struct IpResPacked : ResPacked {
+  struct HeadPk { BlkPk k; LinPk lk; };
+  std::vector<HeadPk> head;
+  LinPk mu0{}, lv0{}, efc{}, mu{}, lv{};
+  IpResPacked(const IpResLayout& P, PackList& pl) {
+    ResPackWalk w{pl};
+    trunk_panels(P, w);
+    if (P.kind == 5) {
+      for (auto& o : P.head) {
+        HeadPk hp{};
+        if (o.res) hp.k = w.blk(o.b, o.concat ? P.cdim : 0); else hp.lk = w.lin(o.l, o.concat ? P.cdim : 0);
+        head.push_back(hp);
+      }
+    } else { mu0 = w.lin(P.mu0, 0); lv0 = w.lin(P.lv0, 0); efc = w.lin(P.efc, P.cdim); mu = w.lin(P.mu, 0); lv = w.lin(P.lv, 0); }
+    decoder_panels(P, w);
+  }
+  explicit IpResPacked(const IpResLayout& P, PackList&& sizing = PackList()) : IpResPacked(P, sizing) {}   // offsets only
+};
+
+// the descriptor rules of kinds 5 / 6
+int res_desc_check(const ardae_model_desc* d) {
+  ARDAE_TRY(desc_flags_ok(d, ARDAE_MODEL_NO_CENTER | ARDAE_MODEL_HEAD_MASK | ARDAE_MODEL_CLIPPED));
+  ARDAE_CHECK_ARG(d->input_dim == 784 && d->noise_dim >= 1 && d->z_dim >= 1 && d->h_dim >= 1 && d->act == ACT_ELU && (d->kind == 6 || (d->n_layers >= 1 && d->n_layers <= 4)),
+                  "model: the residual-conv models are 28x28x1, ELU, and (kind 5) 1 .. 4 hidden layers in the sampler head");
+  const int ht = (d->flags >> 1) & 7;
+  ARDAE_CHECK_ARG(d->kind != 5 || ht <= HEAD_RES_MLP_LIN, "model: unknown sampler head %d (desc.flags bits 1-3)", ht);
+  ARDAE_CHECK_ARG(d->kind == 5 || ht == 0, "model: the sampler-head bits of desc.flags belong to kind 5");
+  ARDAE_CHECK_ARG(d->kind == 6 || !(d->flags & ARDAE_MODEL_CLIPPED), "model: ARDAE_MODEL_CLIPPED belongs to kind 6");
+  // a concat block needs its projected skip (same_dim would make the skip the 612-wide concat itself)
+  ARDAE_CHECK_ARG(d->kind != 5 || ht == HEAD_MLP || 512 + d->noise_dim != d->h_dim,
+                  "model: ResConvIPVAE with c_dim + noise_dim == h_dim (identity skip over the concat input) is not built");
+  return 0;
+}
+
+// the sampler's rows (R = B*nz) beside the shared buffers
+struct IpResWs : ResWs {
   float *zero;                                                      // zero noise for encode(std=0)
   struct HeadBuf { float *rba, *rbs, *hmid, *out; };                // kind 5, per head operator: per-image row biases [B,out] (concat), ResLinear hidden [R,out], output [R,out]
   std::vector<HeadBuf> hb; float* z;                                // z [R,zd]
-  float *mu0, *lv0r, *lv0, *z0, *rbh, *hh, *mu, *lvr, *lv;          // kind 6 (kind 12: mu, lv [B, zd])
-  float *eps, *kld, *dmu, *dlv;                                     // kinds 12 / 19: the draw used, the KL rows [B], the head's backward seed
-  // kind 19 (B rows; mu0, lv0, z0, rbh, hh, mu, lv, z as above): the two draws, aux_decode.fc's row bias and rows, its head, and the backward's seeds
-  float *eps0, *epsz, *rb2, *hr, *mup, *lvp, *dz, *dz0, *dmu0, *dlv0, *dmup, *dlvp, *dhr, *dhh;
-  // decoder (R images)
-  std::vector<BlkBuf> db; float *d4, *u8, *c7, *u14, *u28;          // block buffers; NHWC 4x4x32, upsampled / cropped maps
-  float *rec_row, *pri_row, *dlogit, *dzq;
-  // backward scratch
-  BwdScratch sc; float *da, *dbuf, *dflat, *dinp, *dR0, *dR1, *dB0, *dB1, *dB2;
-  float* dweff; float* dbias; float* wscratch; size_t wscratch_floats;
+  float *mu0, *lv0r, *lv0, *z0, *rbh, *hh, *mu, *lvr, *lv;          // kind 6
 };
 
-size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
 // mode 0: encode (trunk + sampler forward), 1: vae forward + backward, 2: decode only (B = rows, nz = 1)
-void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mode, ResWs& W) {
+void carve(const IpResLayout& P, const IpResPacked&, Bump& ws, int B, int nz, int mode, IpResWs& W) {
   const size_t R = (size_t)B * nz;
-  const bool enc = mode != 2, dec = mode != 0, bwd = mode == 1;
-  if (enc) {
-    W.x2 = ws.take((size_t)B * 784);
-    W.tb.resize(P.trunk.size());
-    for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.tb[i], bwd);
-    W.flat = ws.take((size_t)B * 512);
-    W.inp = W.tb.back().out;
-    if (P.kind != 12 && P.kind != 19) W.zero = ws.take(R * (P.nd + P.zd));
-    if (P.kind == 19) {          // one draw pair per image (nz = 1); mode 0 ends at the trunk: encode_stats writes the caller's mu0, lv0
-      if (mode == 1) {
-        W.mu0 = ws.take(R * P.nd); W.lv0 = ws.take(R * P.nd); W.eps0 = ws.take(R * P.nd); W.epsz = ws.take(R * P.zd); W.z0 = ws.take(R * P.nd);
-        W.rbh = ws.take(R * P.cdim); W.hh = ws.take(R * P.cdim);
-        W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.z = ws.take(R * P.zd); W.eps = ws.take(R * P.zd); W.kld = ws.take(R);
-        W.rb2 = ws.take(R * P.cdim); W.hr = ws.take(R * P.cdim); W.mup = ws.take(R * P.nd); W.lvp = ws.take(R * P.nd);
-        W.dmu = ws.take(R * P.zd); W.dlv = ws.take(R * P.zd); W.dz = ws.take(R * P.zd);
-        W.dz0 = ws.take(R * P.nd); W.dmu0 = ws.take(R * P.nd); W.dlv0 = ws.take(R * P.nd); W.dmup = ws.take(R * P.nd); W.dlvp = ws.take(R * P.nd);
-        W.dhr = ws.take(R * P.cdim); W.dhh = ws.take(R * P.cdim);
-      }
-    } else if (P.kind == 12) {          // one draw per image (nz = 1); mode 0 ends at the trunk: encode_stats writes the caller's mu, lv
-      if (mode == 1) {
-        W.mu = ws.take(R * P.zd); W.lv = ws.take(R * P.zd); W.z = ws.take(R * P.zd); W.eps = ws.take(R * P.zd); W.kld = ws.take(R);
-        W.dmu = ws.take(R * P.zd); W.dlv = ws.take(R * P.zd);
-      }
-    } else if (P.kind == 5) {
+  if (mode != 2) {
+    res_trunk_carve(P, ws, B, W);
+    W.zero = ws.take(R * (P.nd + P.zd));
+    if (P.kind == 5) {
       W.hb.resize(P.head.size());
       for (size_t i = 0; i < P.head.size(); ++i) {
         const HeadOp& o = P.head[i];
@@ -819,120 +874,35 @@ void carve(const ResLayout& P, const ResPacked&, Bump& ws, int B, int nz, int mo
       W.z = ws.take(R * P.zd);
     }
   }
-  if (dec && P.kind == 19 && mode == 2) {
-    // decode only with resconv_mid_kernel (unless the knob switches back): the kernel stands for c7, u14 and the buffers of dec[4] / dec[5] but
-    // dec[5]'s output, which it writes; the one columns scratch is sized from the 8 x 8 blocks
-    const bool mid = mid_fused_default(), tail = tail_fused_default();
-    size_t cx = 0, ch = 0;
-    auto runs = [&](size_t i) { return i < 4 || (i < 6 ? !mid : !tail); };
-    for (size_t i = 0; i < P.dec.size(); ++i)
-      if (runs(i) && P.dec[i].conv) { cx = max_sz(cx, blk_rows(P.dec[i], (int)R) * P.dec[i].a.I); ch = max_sz(ch, blk_rows(P.dec[i], (int)R) * P.dec[i].h.I); }
-    float* colsx = ws.take(cx); float* colsh = ws.take(ch);
-    W.db.assign(P.dec.size(), BlkBuf{nullptr, nullptr, nullptr, nullptr});
-    for (size_t i = 0; i < P.dec.size(); ++i) {
-      const Blk& b = P.dec[i];
-      if (runs(i)) {
-        W.db[i].colsx = b.conv ? colsx : nullptr; W.db[i].colsh = b.conv ? colsh : nullptr;
-        W.db[i].hmid = ws.take(blk_rows(b, (int)R) * b.Cout);
-      }
-      if (runs(i) || i == 5) W.db[i].out = ws.take(blk_rows(b, (int)R) * b.Cout);
-    }
-    W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32);
-    if (!mid) { W.c7 = ws.take(R * 49 * 32); W.u14 = ws.take(R * 196 * 32); }
-    W.u28 = tail ? nullptr : ws.take(R * 784 * 16);
-  } else if (dec && P.kind == 12 && mode == 2) {
-    // decode only, nothing is saved for a backward: ONE columns scratch (the widest block's) serves every conv block in turn, and with the fused
-    // tail neither u28 nor dec[6]'s buffers exist
-    const size_t nb = tail_fused_default() ? P.dec.size() - 1 : P.dec.size();
-    size_t cx = 0, ch = 0;
-    for (size_t i = 0; i < nb; ++i)
-      if (P.dec[i].conv) { cx = max_sz(cx, blk_rows(P.dec[i], (int)R) * P.dec[i].a.I); ch = max_sz(ch, blk_rows(P.dec[i], (int)R) * P.dec[i].h.I); }
-    float* colsx = ws.take(cx); float* colsh = ws.take(ch);
-    W.db.assign(P.dec.size(), BlkBuf{nullptr, nullptr, nullptr, nullptr});
-    for (size_t i = 0; i < nb; ++i) {
-      const Blk& b = P.dec[i];
-      W.db[i].colsx = b.conv ? colsx : nullptr; W.db[i].colsh = b.conv ? colsh : nullptr;
-      W.db[i].hmid = ws.take(blk_rows(b, (int)R) * b.Cout); W.db[i].out = ws.take(blk_rows(b, (int)R) * b.Cout);
-    }
-    W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32); W.c7 = ws.take(R * 49 * 32); W.u14 = ws.take(R * 196 * 32);
-    W.u28 = nb == P.dec.size() ? ws.take(R * 784 * 16) : nullptr;
-  } else if (dec) {
-    W.db.resize(P.dec.size());
-    for (size_t i = 0; i < P.dec.size(); ++i) blk_carve(P.dec[i], (int)R, ws, W.db[i], bwd);
-    W.d4 = ws.take(R * 512); W.u8 = ws.take(R * 64 * 32); W.c7 = ws.take(R * 49 * 32); W.u14 = ws.take(R * 196 * 32); W.u28 = ws.take(R * 784 * 16);
+  if (mode != 0) res_decoder_carve(P, ws, R, DecRuns{true, true, true}, W);
+  if (mode != 1) return;
+  // the sampler tail's weight gradients: all problems of a head operator in one batch (kind 5); kind 6's nine in one list
+  const int Ri = (int)R;
+  size_t need = 2 * (wgrad_scratch_floats(Ri, P.hdim, P.hdim) + wgrad_scratch_floats(Ri, P.hdim, P.cdim + P.nd) + wgrad_scratch_floats(Ri, P.zd, P.hdim)) +
+                3 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.hdim, P.cdim);
+  for (auto& o : P.head) {
+    const int cin = o.concat ? P.nd : o.in;
+    size_t op = 3 * wgrad_scratch_floats(Ri, o.out, std::max(cin, o.out));
+    if (o.concat) op += 2 * wgrad_scratch_floats(B, o.out, P.cdim);
+    need = max_sz(need, op);
   }
-  if (mode == 1) { W.rec_row = ws.take(R); W.pri_row = ws.take(R); W.dlogit = ws.take(R * 784); W.dzq = ws.take(R * P.zd); }
-  if (bwd) {
-    // the largest per-block scratch: decoder convs at 28 x 28 (R images) and the trunk's first convs (B images)
-    size_t mg = 0, mc = 0;
-    auto upd = [&](const Blk& b, size_t images) {
-      const size_t rows = images * b.Hout * b.Hout;
-      mg = max_sz(mg, rows * b.Cout);
-      mc = max_sz(mc, rows * max_sz(b.h.I, b.a.I));
-    };
-    for (auto& b : P.trunk) upd(b, B);
-    for (auto& b : P.dec) upd(b, R);
-    W.sc.g = ws.take(mg); W.sc.dh = ws.take(mg); W.sc.dcols = ws.take(mc);
-    const size_t act_max = max_sz(R * 784 * 16, (size_t)B * 196 * 16);     // largest activation map (decoder 28 x 28 x 16)
-    W.da = ws.take(act_max); W.dbuf = ws.take(act_max);
-    W.dflat = ws.take((size_t)B * 512); W.dinp = ws.take((size_t)B * P.cdim);
-    W.dR0 = ws.take(R * max_sz(P.hdim, P.cdim)); W.dR1 = ws.take(R * max_sz(P.hdim, P.cdim));
-    W.dB0 = ws.take((size_t)B * max_sz(P.hdim, P.cdim)); W.dB1 = ws.take((size_t)B * max_sz(P.hdim, P.cdim)); W.dB2 = ws.take((size_t)B * max_sz(P.hdim, P.cdim));
-    W.dweff = ws.take(P.total); W.dbias = ws.take(P.total / 8 + 4096);
-    size_t wsf = 0;
-    auto wupd = [&](const Blk& b, size_t images) {
-      const int rows = (int)(images * b.Hout * b.Hout);
-      wsf = max_sz(wsf, wgrad_scratch_floats(rows, b.Cout, b.h.I) + wgrad_scratch_floats(rows, b.Cout, b.s.I) + wgrad_scratch_floats(rows, b.Cout, b.a.I));
-    };
-    for (auto& b : P.trunk) wupd(b, B);
-    for (auto& b : P.dec) wupd(b, R);
-    // sampler tail: all problems of a head operator in one batch
-    const int Ri = (int)R;
-    for (auto& o : P.head) {
-      const int cin = o.concat ? P.nd : o.in;
-      size_t need = 3 * wgrad_scratch_floats(Ri, o.out, std::max(cin, o.out));
-      if (o.concat) need += 2 * wgrad_scratch_floats(B, o.out, P.cdim);
-      wsf = max_sz(wsf, need);
-    }
-    if (P.kind == 12) wsf = max_sz(wsf, 2 * wgrad_scratch_floats(Ri, P.zd, P.cdim));      // the two heads, one batch
-    else if (P.kind == 19)       // the ten plain-Linear problems, one list
-      wsf = max_sz(wsf, 2 * wgrad_scratch_floats(B, P.zd, P.cdim) + 4 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.cdim, P.cdim) +
-                            wgrad_scratch_floats(B, P.cdim, P.nd) + wgrad_scratch_floats(B, P.cdim, P.zd));
-    else
-      wsf = max_sz(wsf, 2 * (wgrad_scratch_floats(Ri, P.hdim, P.hdim) + wgrad_scratch_floats(Ri, P.hdim, P.cdim + P.nd) + wgrad_scratch_floats(Ri, P.zd, P.hdim)) +
-                            3 * wgrad_scratch_floats(B, P.nd, P.cdim) + 2 * wgrad_scratch_floats(B, P.hdim, P.cdim));
-    W.wscratch_floats = wsf + 1024;
-    W.wscratch = ws.take(W.wscratch_floats);
-  }
+  res_bwd_carve(P, ws, B, R, need, W);
 }
 
-using ResEntry = Entry<ResLayout, ResPacked, ResWs>;
-
-// ------------------------------------------------------------------------------------------------ forward pieces
-int trunk_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* x, int B, ResWs& W, hipStream_t st) {
-  if (P.center) ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));       // do_center (ivae/resconv.py:131-132)
-  else ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 1.f, 0.f, W.x2, st));
-  const float* cur = W.x2;
-  for (size_t i = 0; i < 5; ++i) {
-    ARDAE_TRY(blk_fwd(P.trunk[i], K.trunk[i], params, packed, cur, B, ACT_ELU, W.tb[i], st));
-    cur = W.tb[i].out;
-  }
-  ARDAE_TRY(launch_nhwc_nchw(cur, B, 16, 32, W.flat, false, st));
-  return blk_fwd(P.trunk[5], K.trunk[5], params, packed, W.flat, B, ACT_ELU, W.tb[5], st);
-}
+using ResEntry = Entry<IpResLayout, IpResPacked, IpResWs>;
 
 // sampler tail on R = B*nz rows; noise [R, nd] (kind 5) or [R, nd + zd] rows [eps0 | eps] (kind 6); z -> z_out
 // raw0 (clipped class, std = 0 pass only - `noise` is then the zero block): the unscaled eps0 [R, nd] z0 keeps, or NULL (zeros)
-int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* noise, int B, int nz, ResWs& W, float* z_out,
-                float* hidden_out, hipStream_t st, const float* raw0 = nullptr, bool std0 = false) {
+int sampler_fwd(const IpResLayout& P, const IpResPacked& K, const float* params, const float* packed, const float* noise, int B, int nz, IpResWs& W,
+                float* z_out, float* hidden_out, hipStream_t st, const float* raw0 = nullptr, bool std0 = false) {
   const int R = B * nz;
   if (P.kind == 5) {
     // encode.fc operator by operator; the per-image half of a concat input enters as a row bias (computed once per image)
     const float* x = nullptr;
     for (size_t i = 0; i < P.head.size(); ++i) {
       const HeadOp& o = P.head[i];
-      const ResPacked::HeadPk& hk = K.head[i];
-      ResWs::HeadBuf& u = W.hb[i];
+      const IpResPacked::HeadPk& hk = K.head[i];
+      IpResWs::HeadBuf& u = W.hb[i];
       float* out = i + 1 == P.head.size() ? z_out : u.out;
       if (o.res) {
         const Blk& b = o.b; const BlkPk& k = hk.k;
@@ -983,498 +953,192 @@ int sampler_fwd(const ResLayout& P, const ResPacked& K, const float* params, con
   return launch_reparam_fwd(W.mu, W.lv, noise + P.nd, ldn, R, P.zd, 1, z_out, st);
 }
 
-// the 14 x 14 stage as its launches: y8 [R, 8, 8, 32] -> u5.out [R, 14, 14, 16]
-int mid_unfused(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* y8, int R, float* c7, float* u14, BlkBuf& u4,
-                BlkBuf& u5, hipStream_t st) {
-  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 49 * 32, y8, 8, 7, 32, c7, (int64_t)R * 49 * 32);    // slicer[:, :, :-1, :-1]
-  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 196 * 32, (const float*)c7, 7, 32, u14, (int64_t)R * 196 * 32);
-  ARDAE_TRY(blk_fwd(P.dec[4], K.dec[4], params, packed, u14, R, ACT_ELU, u4, st));
-  return blk_fwd(P.dec[5], K.dec[5], params, packed, u4.out, R, ACT_ELU, u5, st);
-}
-
-// decoder on R rows: z [R, zd] -> logits [R, 784]
-// fused_tail (kind 12's decode-only path): the last upsampling and dec[6] as resconv_tail_kernel, which writes `logits` itself
-// fused_mid (kind 19's decode-only path): the crop, the 7 -> 14 upsampling, dec[4] and dec[5] as resconv_mid_kernel
-int decoder_fwd(const ResLayout& P, const ResPacked& K, const float* params, const float* packed, const float* z, int R, ResWs& W, float* logits, hipStream_t st,
-                bool fused_tail = false, bool fused_mid = false) {
-  ARDAE_TRY(blk_fwd(P.dec[0], K.dec[0], params, packed, z, R, ACT_ELU, W.db[0], st));
-  ARDAE_TRY(blk_fwd(P.dec[1], K.dec[1], params, packed, W.db[0].out, R, ACT_ELU, W.db[1], st));
-  ARDAE_TRY(launch_nhwc_nchw(W.db[1].out, R, 16, 32, W.d4, true, st));                                    // view(-1, 32, 4, 4) -> NHWC
-  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 64 * 32, W.d4, 4, 32, W.u8, (int64_t)R * 64 * 32);
-  ARDAE_TRY(blk_fwd(P.dec[2], K.dec[2], params, packed, W.u8, R, ACT_ELU, W.db[2], st));
-  ARDAE_TRY(blk_fwd(P.dec[3], K.dec[3], params, packed, W.db[2].out, R, ACT_ELU, W.db[3], st));
-  if (fused_mid) ARDAE_TRY(mid_fused(P, K, params, packed, W.db[3].out, R, W.db[5].out, st));
-  else ARDAE_TRY(mid_unfused(P, K, params, packed, W.db[3].out, R, W.c7, W.u14, W.db[4], W.db[5], st));
-  if (fused_tail) return tail_fused(P.dec[6], K.dec[6], params, packed, W.db[5].out, R, logits, st);
-  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, W.db[5].out, 14, 16, W.u28, (int64_t)R * 784 * 16);
-  ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, W.u28, R, ACT_NONE, W.db[6], st));
-  if (logits && logits != W.db[6].out) ARDAE_TRY(launch_copy(W.db[6].out, (size_t)R * 784, logits, st));
-  return 0;
-}
-
-// gradient destinations of a WN operator inside the dweff / dbias scratch
-struct GradMap {
-  const ResLayout& P; float* dweff; float* dbias; size_t boff = 0;
-  std::vector<WnBwdItem> items;
-  const float* params; const float* packed; float* grads;
-  float grads_beta = 0.f;
-  WnGrad wn(const WN& w, const WNPk& k) {
-    if (w.plain) return WnGrad{grads + w.dir, grads + w.bias, grads_beta};     // nn.Linear operator: the weight gradient IS the parameter gradient
-    WnGrad g; g.dW = dweff + w.dir; g.db = dbias + boff; g.beta = 0.f; boff += al64(w.O);
-    WnBwdItem it; it.dW = g.dW; it.dir = params + w.dir; it.scale = params + w.scale; it.inv = packed + k.inv; it.db = g.db;
-    it.gdir = grads + w.dir; it.gscale = grads + w.scale; it.gbias = grads + w.bias; it.O = w.O; it.I = w.I; it.norm = w.norm ? 1 : 0;
-    items.push_back(it);
-    return g;
-  }
-  BlkGrad blk(const Blk& b, const BlkPk& k) { BlkGrad g; g.a = wn(b.a, k.a); g.h = wn(b.h, k.h); g.s = b.same ? g.h : wn(b.s, k.s); return g; }
-};
-
-// the decoder's backward on R rows from W.dlogit: every block's weight gradients into gm's scratch, dz (added to what the loss kernel left) in W.dzq
-int decoder_bwd(const ResLayout& P, const ResPacked& K, const float* packed, ResWs& W, int R, GradMap& gm, hipStream_t st) {
-  // ---- decoder backward (d_out ping-pongs between W.da and W.dbuf)
-  std::vector<BlkGrad> gd(P.dec.size());
-  for (size_t i = 0; i < P.dec.size(); ++i) gd[i] = gm.blk(P.dec[i], K.dec[i]);
-  ARDAE_TRY(blk_bwd(P.dec[6], K.dec[6], packed, W.u28, R, ACT_NONE, W.db[6], W.dlogit, W.da, W.sc, gd[6], W.wscratch, W.wscratch_floats, st));      // -> d u28 [R,28,28,16]
-  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 196 * 16, W.da, 14, 16, W.dbuf, (int64_t)R * 196 * 16);
-  ARDAE_TRY(blk_bwd(P.dec[5], K.dec[5], packed, W.db[4].out, R, ACT_ELU, W.db[5], W.dbuf, W.da, W.sc, gd[5], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(blk_bwd(P.dec[4], K.dec[4], packed, W.u14, R, ACT_ELU, W.db[4], W.da, W.dbuf, W.sc, gd[4], W.wscratch, W.wscratch_floats, st));          // -> d u14 [R,14,14,32]
-  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 49 * 32, W.dbuf, 7, 32, W.da, (int64_t)R * 49 * 32);                                                 // -> d c7
-  RES_LAUNCH(crop_pad_kernel, (int64_t)R * 64 * 32, W.da, 7, 8, 32, W.dbuf, (int64_t)R * 64 * 32);                                                    // -> d (block 3 out) [R,8,8,32]
-  ARDAE_TRY(blk_bwd(P.dec[3], K.dec[3], packed, W.db[2].out, R, ACT_ELU, W.db[3], W.dbuf, W.da, W.sc, gd[3], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(blk_bwd(P.dec[2], K.dec[2], packed, W.u8, R, ACT_ELU, W.db[2], W.da, W.dbuf, W.sc, gd[2], W.wscratch, W.wscratch_floats, st));            // -> d u8
-  RES_LAUNCH(upsample2_bwd_kernel, (int64_t)R * 16 * 32, W.dbuf, 4, 32, W.da, (int64_t)R * 16 * 32);                                                 // -> d d4 (NHWC)
-  ARDAE_TRY(launch_nhwc_nchw(W.da, R, 16, 32, W.dbuf, false, st));                                                                                    // -> NCHW-flat [R,512]
-  ARDAE_TRY(blk_bwd(P.dec[1], K.dec[1], packed, W.db[0].out, R, ACT_ELU, W.db[1], W.dbuf, W.da, W.sc, gd[1], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(blk_bwd(P.dec[0], K.dec[0], packed, W.z, R, ACT_ELU, W.db[0], W.da, W.dbuf, W.sc, gd[0], W.wscratch, W.wscratch_floats, st));             // -> dz (decoder part) [R,zd]
-  ARDAE_TRY(launch_axpy(W.dbuf, (int64_t)R * P.zd, 1.f, W.dzq, st));                                                                                 // dz total in W.dzq
-  return 0;
-}
-
-// the trunk's backward on B images from W.dinp (the gradient at its output, after the ELU), then dL/dW -> dL/d(direction, scale) and the bias
-// gradients of every weight-normalised operator gm has handed out
-int trunk_wn_bwd(const ResLayout& P, const ResPacked& K, const float* packed, ResWs& W, int B, GradMap& gm, float grads_beta, hipStream_t st) {
-  // ---- trunk backward
-  std::vector<BlkGrad> gt(P.trunk.size());
-  for (size_t i = 0; i < P.trunk.size(); ++i) gt[i] = gm.blk(P.trunk[i], K.trunk[i]);
-  ARDAE_TRY(blk_bwd(P.trunk[5], K.trunk[5], packed, W.flat, B, ACT_ELU, W.tb[5], W.dinp, W.dflat, W.sc, gt[5], W.wscratch, W.wscratch_floats, st));
-  ARDAE_TRY(launch_nhwc_nchw(W.dflat, B, 16, 32, W.da, true, st));                                  // NCHW-flat gradient -> NHWC [B,4,4,32]
-  float *cur = W.da, *nxt = W.dbuf;
-  for (int i = 4; i >= 0; --i) {
-    const float* xin = i == 0 ? W.x2 : W.tb[i - 1].out;
-    ARDAE_TRY(blk_bwd(P.trunk[i], K.trunk[i], packed, xin, B, ACT_ELU, W.tb[i], cur, i == 0 ? nullptr : nxt, W.sc, gt[i], W.wscratch, W.wscratch_floats, st));
-    std::swap(cur, nxt);
-  }
-  // ---- dL/dW -> dL/d(direction, scale), bias gradients
-  for (size_t i0 = 0; i0 < gm.items.size(); i0 += WNB_MAX) {
-    WnBwdBatch bt;
-    bt.n = (int)std::min<size_t>(WNB_MAX, gm.items.size() - i0);
-    bt.beta = grads_beta;
-    for (int i = 0; i < bt.n; ++i) bt.it[i] = gm.items[i0 + i];
-    hipLaunchKernelGGL(wn_backward_kernel, dim3(32, bt.n), dim3(256), 0, st, bt);
-    ARDAE_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// ================================================================================================ entry points
-int res_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
-  const ResLayout P(d);
+// ardae_model_pack: the head's ResLinear blocks are composed with the trunk's and the decoder's
+int ipres_pack(const ardae_model_desc& d, const float* params, float* packed, hipStream_t st) {
+  const IpResLayout P(d);
   PackList pl(params, packed);
-  const ResPacked K(P, pl);
-  // what the panels are packed FROM: the weight-normalised operators' effective weights and every projected-skip block's bias sum,
-  // composed into the packed buffer ahead of the pack launch
-  std::vector<WnComposeItem> comp;
-  auto wn = [&](const WN& w, const WNPk& k) {
-    if (!w.plain) comp.push_back(WnComposeItem{params + w.dir, params + w.scale, packed + k.weff, packed + k.inv, w.O, w.I, w.norm ? 1 : 0, nullptr, nullptr});
-  };
-  auto blk = [&](const Blk& b, const BlkPk& k) {
-    wn(b.a, k.a); wn(b.h, k.h);
-    if (b.same) return;          // identity skip: no third operator, the block's bias is b_h1
-    wn(b.s, k.s);
-    comp.push_back(WnComposeItem{nullptr, nullptr, packed + k.bsum, nullptr, b.Cout, 0, 0, params + b.h.bias, params + b.s.bias});   // bsum = b_h + b_s
-  };
-  for (size_t i = 0; i < P.trunk.size(); ++i) blk(P.trunk[i], K.trunk[i]);
+  const IpResPacked K(P, pl);
+  HeadBlks head;
   for (size_t i = 0; i < P.head.size(); ++i)
-    if (P.head[i].res) blk(P.head[i].b, K.head[i].k);
-  for (size_t i = 0; i < P.dec.size(); ++i) blk(P.dec[i], K.dec[i]);
-  for (size_t i0 = 0; i0 < comp.size(); i0 += WNC_MAX) {
-    WnComposeBatch cb;
-    cb.n = (int)std::min<size_t>(WNC_MAX, comp.size() - i0);
-    int maxo = 1;
-    for (int i = 0; i < cb.n; ++i) {
-      cb.it[i] = comp[i0 + i];
-      maxo = std::max(maxo, cb.it[i].dir ? cb.it[i].O : ceil_div(cb.it[i].O, 256));
-    }
-    hipLaunchKernelGGL(wn_compose_batch_kernel, dim3(maxo, cb.n), dim3(256), 0, st, cb);
-    ARDAE_LAUNCH_CHECK();
-  }
-  ARDAE_TRY(pl.launch(st));
-  if (P.kind != 19) return 0;
-  // resconv_mid_kernel's B operands, from the effective weights the compose launch has written
-  MidPackArgs a;
-  const WNPk* ops[6] = {&K.dec[4].a, &K.dec[4].s, &K.dec[4].h, &K.dec[5].a, &K.dec[5].s, &K.dec[5].h};
-  const int off[6] = {RM_W4A, RM_W4S, RM_W4H, RM_W5A, RM_W5S, RM_W5H};
-  for (int i = 0; i < 6; ++i) { a.weff[i] = packed + ops[i]->weff; a.K[i] = i < 2 ? 288 : 144; a.off[i] = off[i]; }
-  hipLaunchKernelGGL(resconv_mid_pack_kernel, dim3(nblk(RM_WTOTAL)), dim3(256), 0, st, a, packed + K.mid_w);
-  ARDAE_LAUNCH_CHECK();
-  return 0;
-}
-
-GradMap grad_map(const ResLayout& P, ResWs& W, const float* params, const float* packed, float* grads, float grads_beta) {
-  GradMap gm{P, W.dweff, W.dbias, 0, {}, params, packed, grads};
-  gm.grads_beta = grads_beta;
-  return gm;
+    if (P.head[i].res) head.push_back({&P.head[i].b, &K.head[i].k});
+  return res_pack(P, K, head, pl, st);
 }
 
 // What the shared algorithm (csrc/ipmodel.h) needs to know of the residual-conv models (the weight gradients go out block by block through
 // flush_wgrad, their scratch carved up front: there is no list to size)
 struct ResTraits : IpTraitsBase {
-  using Layout = ResLayout; using Packed = ResPacked; using Ws = ResWs; using Entry = ResEntry;
+  using Layout = IpResLayout; using Packed = IpResPacked; using Ws = IpResWs; using Entry = ResEntry;
   using Grads = GradMap;      // built before the decoder's backward, used again by the sampler's and the trunk's
   [[maybe_unused]] static constexpr bool direct_z = true;      // a forward-only encode: the last launch of the sampler writes the caller's buffer itself
   static int desc_check(const ardae_model_desc* d) { return res_desc_check(d); }
   // the hidden1a context is the aux model's h; the raw form belongs to its clipped class
   static unsigned caps(const ardae_model_desc& d) { return d.kind != 6 ? 0 : (d.flags & ARDAE_MODEL_CLIPPED) ? CAP_HIDDEN | CAP_HIDDEN_RAW : CAP_HIDDEN; }
-  static IpBufs bufs(const ResWs& W) {      // the decoder's backward adds its dz to what the loss kernel left in dzq
+  static IpBufs bufs(const IpResWs& W) {      // the decoder's backward adds its dz to what the loss kernel left in dzq
     return {W.z, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dzq, W.rec_row, W.pri_row};
   }
-  static void wgrads(const ResLayout&, const ResPacked&, const ResWs&, const float*, const float*, int, int, WgradList&, Bump&) {}
-  static size_t noise_floats(const ResLayout& P, int B, int nz) { return (size_t)B * nz * (P.nd + P.zd); }
+  static void wgrads(const IpResLayout&, const IpResPacked&, const IpResWs&, const float*, const float*, int, int, WgradList&, Bump&) {}
+  static size_t noise_floats(const IpResLayout& P, int B, int nz) { return (size_t)B * nz * (P.nd + P.zd); }
   static float* zero_noise(Entry& e, size_t) { return e.W.zero; }
   // (a forward-only pass copies the hidden context out in passing)
   static int sampler_fwd(Entry& e, const float* params, const float* packed, const float* x, const float* noise, int B, int nz, const IpEncodeOut* enc,
                          hipStream_t st) {
     auto& [P, K, ws, W] = e;
-    ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
+    ARDAE_TRY(res_trunk_fwd(P, K, params, packed, x, B, W, st));
     if (!enc) return ardae::sampler_fwd(P, K, params, packed, noise, B, nz, W, W.z, nullptr, st);
     ARDAE_CHECK_ARG(!enc->raw0 || (P.clipped && enc->std0), "res model: raw0 is the clipped class's unscaled eps0 of a std = 0 pass (noise NULL)");
     return ardae::sampler_fwd(P, K, params, packed, noise, B, nz, W, enc->z_out ? enc->z_out : W.z, enc->hidden_out, st, enc->raw0, enc->std0);
   }
   static int decoder_fwd(Entry& e, const float* params, const float* packed, const float* z, int R, hipStream_t st) {
-    return ardae::decoder_fwd(e.P, e.K, params, packed, z, R, e.W, nullptr, st);
+    return res_decoder_fwd(e.P, e.K, params, packed, z, R, e.W, nullptr, st);
   }
-  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.P, e.W, params, packed, g, beta); }
-  static int decoder_bwd(Entry& e, const float* packed, int R, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, R, gm, st); }
+  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.W, params, packed, g, beta); }
+  static int decoder_bwd(Entry& e, const float* packed, int R, GradMap& gm, hipStream_t st) { return res_decoder_bwd(e.P, e.K, packed, e.W.z, e.W, R, gm, st); }
+  // the sampler's backward -> W.dinp [B, cdim], then the trunk's
   static int sampler_bwd(Entry& e, const float*, const float* packed, const float*, const float* noise, int B, int nz, GradMap& gm, hipStream_t st) {
+    ARDAE_TRY(e.P.kind == 5 ? head_bwd(e, packed, noise, B, nz, gm, st) : aux_bwd(e, packed, noise, B, nz, gm, st));
+    return res_trunk_wn_bwd(e.P, e.K, packed, e.W, B, gm, gm.grads_beta, st);
+  }
+  // kind 5: encode.fc backwards, operator by operator: g = dL/d(output of the operator) [R, out]
+  static int head_bwd(Entry& e, const float* packed, const float* noise, int B, int nz, GradMap& gm, hipStream_t st) {
     auto& [P, K, ws, W] = e;
     const int R = B * nz;
-    // ---- sampler backward -> W.dinp [B, cdim]
     WgradList wl(gm.grads);              // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
-    if (P.kind == 5) {
-      // encode.fc backwards, operator by operator: g = dL/d(output of the operator) [R, out]
-      auto pw = [&](int M, int O, int I, const float* G, const float* X, int ldX, const WnGrad& g, int col0, int ldout, bool bias) {
-        wl.push(M, O, I, G, X, ldX, g.dW + col0, ldout, bias ? g.db : nullptr).beta = g.beta;
-      };
-      float* g = W.dzq;
-      float* pp[2] = {W.dR0, W.dR1};
-      for (int i = (int)P.head.size() - 1; i >= 0; --i) {
-        const HeadOp& o = P.head[i];
-        const ResPacked::HeadPk& hk = K.head[i];
-        const ResWs::HeadBuf& u = W.hb[i];
-        const float* out = i + 1 == (int)P.head.size() ? W.z : u.out;
-        const float* x = i == 0 ? nullptr : W.hb[i - 1].out;        // the operator's input (post-activation output of its predecessor)
-        float* dx = pp[i & 1];
-        if (o.act != ACT_NONE) ARDAE_TRY(launch_mul_dact(g, out, o.act, g, (int64_t)R * o.out, st));
-        if (o.res) {
-          const Blk& b = o.b; const BlkPk& k = hk.k;
-          const BlkGrad gr = gm.blk(b, k);
-          float* dh = W.sc.dh;       // [R, out]: d hmid = (g W_h1) relu'(hmid)
-          ARDAE_TRY(dense_bwd(ACT_RELU, R, o.out, g, o.out, packed + k.h.b, u.hmid, dh, st));
-          pw(R, o.out, o.out, g, u.hmid, o.out, gr.h, 0, o.out, true);
-          if (o.concat) {
-            const int I0 = P.cdim + P.nd;
-            ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rbs [B, out]
-            ARDAE_TRY(launch_segment_sum(dh, o.out, B, nz, o.out, 1.f, W.dB1, o.out, st));      // d rba [B, out]
-            pw(R, o.out, P.nd, g, noise, P.nd, gr.s, P.cdim, I0, true);                           // noise columns of W_01 (+ its bias)
-            pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gr.s, 0, I0, false);                       // image columns of W_01
-            pw(R, o.out, P.nd, dh, noise, P.nd, gr.a, P.cdim, I0, true);
-            pw(B, o.out, P.cdim, W.dB1, W.inp, P.cdim, gr.a, 0, I0, false);
-            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-            LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
-            ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.s_bi, W.dB1, o.out, o.out, packed + k.a_bi, A, st));
-          } else {
-            if (!b.same) pw(R, o.out, o.in, g, x, o.in, gr.s, 0, o.in, true);
-            pw(R, o.out, o.in, dh, x, o.in, gr.a, 0, o.in, true);
-            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-            if (!b.same) {
-              LinArgs A{}; A.Y = dx; A.ldY = o.in;
-              ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.s.b, dh, o.out, o.out, packed + k.a.b, A, st));
-            } else {   // identity skip: dx = dh W_0h + g
-              ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, dh, o.out, o.out, packed + k.a.b, nullptr, dx, st));
-              ARDAE_TRY(launch_axpy(g, (int64_t)R * o.in, 1.f, dx, st));
-            }
-          }
+    auto pw = [&](int M, int O, int I, const float* G, const float* X, int ldX, const WnGrad& g, int col0, int ldout, bool bias) {
+      wl.push(M, O, I, G, X, ldX, g.dW + col0, ldout, bias ? g.db : nullptr).beta = g.beta;
+    };
+    float* g = W.dzq;
+    float* pp[2] = {W.dR0, W.dR1};
+    for (int i = (int)P.head.size() - 1; i >= 0; --i) {
+      const HeadOp& o = P.head[i];
+      const IpResPacked::HeadPk& hk = K.head[i];
+      const IpResWs::HeadBuf& u = W.hb[i];
+      const float* out = i + 1 == (int)P.head.size() ? W.z : u.out;
+      const float* x = i == 0 ? nullptr : W.hb[i - 1].out;        // the operator's input (post-activation output of its predecessor)
+      float* dx = pp[i & 1];
+      if (o.act != ACT_NONE) ARDAE_TRY(launch_mul_dact(g, out, o.act, g, (int64_t)R * o.out, st));
+      if (o.res) {
+        const Blk& b = o.b; const BlkPk& k = hk.k;
+        const BlkGrad gr = gm.blk(b, k);
+        float* dh = W.sc.dh;       // [R, out]: d hmid = (g W_h1) relu'(hmid)
+        ARDAE_TRY(dense_bwd(ACT_RELU, R, o.out, g, o.out, packed + k.h.b, u.hmid, dh, st));
+        pw(R, o.out, o.out, g, u.hmid, o.out, gr.h, 0, o.out, true);
+        if (o.concat) {
+          const int I0 = P.cdim + P.nd;
+          ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rbs [B, out]
+          ARDAE_TRY(launch_segment_sum(dh, o.out, B, nz, o.out, 1.f, W.dB1, o.out, st));      // d rba [B, out]
+          pw(R, o.out, P.nd, g, noise, P.nd, gr.s, P.cdim, I0, true);                           // noise columns of W_01 (+ its bias)
+          pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gr.s, 0, I0, false);                       // image columns of W_01
+          pw(R, o.out, P.nd, dh, noise, P.nd, gr.a, P.cdim, I0, true);
+          pw(B, o.out, P.cdim, W.dB1, W.inp, P.cdim, gr.a, 0, I0, false);
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+          LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
+          ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.s_bi, W.dB1, o.out, o.out, packed + k.a_bi, A, st));
         } else {
-          const Lin& l = o.l; const LinPk& k = hk.lk;
-          const WnGrad gl{gm.grads + l.w, gm.grads + l.b, gm.grads_beta};
-          if (o.concat) {
-            ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rba [B, out]
-            pw(R, o.out, P.nd, g, noise, P.nd, gl, P.cdim, l.in, true);
-            pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gl, 0, l.in, false);
-            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-            ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, nullptr, W.dinp, st));
-          } else {
-            pw(R, o.out, o.in, g, x, o.in, gl, 0, l.in, true);
-            ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-            ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, nullptr, dx, st));
+          if (!b.same) pw(R, o.out, o.in, g, x, o.in, gr.s, 0, o.in, true);
+          pw(R, o.out, o.in, dh, x, o.in, gr.a, 0, o.in, true);
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+          if (!b.same) {
+            LinArgs A{}; A.Y = dx; A.ldY = o.in;
+            ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, o.in, g, o.out, o.out, packed + k.s.b, dh, o.out, o.out, packed + k.a.b, A, st));
+          } else {   // identity skip: dx = dh W_0h + g
+            ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, dh, o.out, o.out, packed + k.a.b, nullptr, dx, st));
+            ARDAE_TRY(launch_axpy(g, (int64_t)R * o.in, 1.f, dx, st));
           }
         }
-        g = dx;
+      } else {
+        const Lin& l = o.l; const LinPk& k = hk.lk;
+        const WnGrad gl{gm.grads + l.w, gm.grads + l.b, gm.grads_beta};
+        if (o.concat) {
+          ARDAE_TRY(launch_segment_sum(g, o.out, B, nz, o.out, 1.f, W.dB0, o.out, st));       // d rba [B, out]
+          pw(R, o.out, P.nd, g, noise, P.nd, gl, P.cdim, l.in, true);
+          pw(B, o.out, P.cdim, W.dB0, W.inp, P.cdim, gl, 0, l.in, false);
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+          ARDAE_TRY(dense_fwd(ACT_NONE, B, P.cdim, W.dB0, o.out, o.out, packed + k.bi, nullptr, W.dinp, st));
+        } else {
+          pw(R, o.out, o.in, g, x, o.in, gl, 0, l.in, true);
+          ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+          ARDAE_TRY(dense_fwd(ACT_NONE, R, o.in, g, o.out, o.out, packed + k.b, nullptr, dx, st));
+        }
       }
-    } else {
-      const int ldn = P.nd + P.zd;
-      auto plain_wgrad = [&](int M, const Lin& l, const float* G, const float* X, int ldX, int col0, int I, bool bias) {
-        wl.push(M, l.out, I, G, X, ldX, gm.grads + l.w + col0, l.in, bias ? gm.grads + l.b : nullptr).beta = gm.grads_beta;
-      };
-      // z = mu + exp(lv/2) eps,  lv = spm4(lvr)
-      float* dlv = W.sc.g;           // [R, zd]
-      ARDAE_TRY(launch_reparam_bwd(W.dzq, W.z, W.mu, R, P.zd, 1, dlv, st));
-      RES_LAUNCH(spm4_kernel, (int64_t)R * P.zd, W.lvr, (const float*)dlv, dlv, (int64_t)R * P.zd, (int)P.clipped);
-      plain_wgrad(R, P.mu, W.dzq, W.hh, P.cdim, 0, P.cdim, true);
-      plain_wgrad(R, P.lv, dlv, W.hh, P.cdim, 0, P.cdim, true);
-      float* dhh = W.dR0;            // [R, cdim]
-      { LinArgs A{}; A.Y = dhh; A.ldY = P.cdim; ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, P.cdim, W.dzq, P.zd, P.zd, packed + K.mu.b, dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
-      ARDAE_TRY(launch_mul_dact(dhh, W.hh, ACT_ELU, dhh, (int64_t)R * P.cdim, st));
-      ARDAE_TRY(launch_segment_sum(dhh, P.cdim, B, nz, P.cdim, 1.f, W.dB0, P.cdim, st));      // d rbh [B, cdim]
-      plain_wgrad(R, P.efc, dhh, W.z0, P.nd, P.cdim, P.nd, true);                              // z0 columns + bias
-      plain_wgrad(B, P.efc, W.dB0, W.inp, P.cdim, 0, P.cdim, false);                           // image columns
-      float* dz0 = W.dR1;            // [R, nd] = dhh W_fc[:, cdim:]
-      ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, dhh, P.cdim, P.cdim, packed + K.efc.bn, nullptr, dz0, st));
-      // z0 = mu0[b] + exp(lv0[b] / 2) eps0,  lv0 = spm4(lv0r): reduce over the nz rows of an image first
-      float* dlv0_rows = W.sc.dh;    // [R, nd]
-      ARDAE_TRY(launch_reparam_bwd(dz0, W.z0, W.mu0, R, P.nd, nz, dlv0_rows, st, P.clipped ? 1.f : 0.f, noise, ldn));
-      ARDAE_TRY(launch_segment_sum(dz0, P.nd, B, nz, P.nd, 1.f, W.dB1, P.nd, st));            // d mu0 [B, nd]
-      ARDAE_TRY(launch_segment_sum(dlv0_rows, P.nd, B, nz, P.nd, 1.f, W.dB2, P.nd, st));      // d lv0 [B, nd]
-      RES_LAUNCH(spm4_kernel, (int64_t)B * P.nd, W.lv0r, (const float*)W.dB2, W.dB2, (int64_t)B * P.nd, (int)P.clipped);
-      plain_wgrad(B, P.mu0, W.dB1, W.inp, P.cdim, 0, P.cdim, true);
-      plain_wgrad(B, P.lv0, W.dB2, W.inp, P.cdim, 0, P.cdim, true);
-      ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-      // d inp = d rbh W_fc[:, :cdim] + d mu0 W_mu0 + d lv0r W_lv0
-      float* part = W.dflat;         // [B, cdim] scratch (cdim <= 512)
-      { LinArgs A{}; A.Y = part; A.ldY = P.cdim;
-        ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, P.cdim, P.cdim, packed + K.efc.bi, W.dB1, P.nd, P.nd, packed + K.mu0.b, A, st)); }
-      ARDAE_TRY(dense_bwd(ACT_NONE, B, P.cdim, W.dB2, P.nd, packed + K.lv0.b, part, W.dinp, st, part));       // V * 1 + Q
+      g = dx;
     }
-    return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
-  }
-};
-
-// ------------------------------------------------------------------------------------------------ kind 12: the Gaussian-posterior baseline
-// one draw per image; there is no sampler pair.  mode 2: B * nz decoded rows
-size_t resvae_workspace_floats(const ardae_model_desc& d, int B, int nz, int mode) {
-  if (mode != 2 && (nz != 1 || mode == 3)) return 0;
-  const ResLayout P(d);
-  Bump ws;
-  ResWs W;
-  carve(P, ResPacked(P), ws, mode == 2 ? B * nz : B, 1, mode, W);
-  return ws.off;
-}
-
-int resvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
-                  hipStream_t st, float*) {
-  ResEntry entry(d, workspace, wsf, R, 1, 2);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
-  return decoder_fwd(P, K, params, packed, z, R, W, out0, st, tail_fused_default());
-}
-
-// What gauss_vae_forward / _backward / _encode_stats (csrc/vaemodel.h) need to know of kind 12.
-struct ResVaeTraits {
-  using Layout = ResLayout; using Packed = ResPacked; using Entry = ResEntry;
-  using Grads = GradMap;      // built before the decoder's backward, used again by the trunk's
-  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, 1, mode); }
-  // The head at h = c_dim.  The recipe's 450 is no multiple of 4, so gauss_head_kernel reads its rows float by float there: measured at
-  // 128 x 450 -> 2 x 32 it loses to the unfused launches (README), which are this kind's default; variant 1 stays callable.
-  static GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f, false, false}; }
-  static const float* hid(const ResWs& W) { return W.inp; }
-  static GaussBufs bufs(const ResWs& W) {      // the decoder's backward adds its dz to what the loss kernel left in dzq
-    return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dzq, W.dmu, W.dlv};
-  }
-  static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
-    return trunk_fwd(e.P, e.K, params, packed, x, B, e.W, st);
-  }
-  // the training forward keeps the unfused tail: the backward reads the columns it saves
-  static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
-    return ardae::decoder_fwd(e.P, e.K, params, packed, e.W.z, B, e.W, nullptr, st);
-  }
-  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.P, e.W, params, packed, g, beta); }
-  static int decoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, B, gm, st); }
-  static int encoder_bwd(Entry& e, const float* packed, const float*, int B, GradMap& gm, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    // the two heads: plain Linears, their gradients go to the gradient buffer itself; then both back into the trunk's output rows
-    WgradList wl(gm.grads, gm.grads_beta);
-    wl.push(B, P.zd, P.cdim, W.dmu, W.inp, P.cdim, gm.grads + P.mu.w, P.cdim, gm.grads + P.mu.b);
-    wl.push(B, P.zd, P.cdim, W.dlv, W.inp, P.cdim, gm.grads + P.lv.w, P.cdim, gm.grads + P.lv.b);
-    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-    { LinArgs A{}; A.Y = W.dinp; A.ldY = P.cdim;
-      ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dmu, P.zd, P.zd, packed + K.mu.b, W.dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
-    return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
-  }
-};
-
-// ------------------------------------------------------------------------------------------------ kind 19: the hierarchical resconv Gaussian baseline
-//   per image (B rows):  ctx = trunk(x or 2x - 1)  [B, c]  - ONE trunk, read by the three networks
-//     aux_encode   mu0 = M0 ctx + m0;  lv0 = L0 ctx + l0 (no clip);  z0 = mu0 + exp(lv0 / 2) eps0
-//     encode       h = ELU(Fe [ctx | z0] + fe);  mu, lv, z, kld: the Gaussian head on h (kind 12's policy: the unfused launches)
-//     aux_decode   hr = ELU(Fr [ctx | z] + fr);  mup = Mp hr + mp;  lvp = Lp hr + lp;  aux_kld = KL(N(mu0, exp lv0) || N(mup, exp lvp)), added into kld
-//     decode       kind 12's decoder, Bernoulli reconstruction rows
-//   losses = {mean_b(recon_b + beta (kld_b + aux_kld_b)), mean recon, mean (kld + aux_kld)}
-//   (the ctx half of Fe / Fr enters as a row bias, computed once per image: the same code serves the evaluation's k rows per image)
-// Forward, backward, encode_stats, the evaluation passes and the workspace sizes are csrc/auxvae.h's bodies over AuxResVaeTraits; the backward's seeds
-// and their order are aux_vae_backward's, and the traits' three hooks carry d ctx between them: aux_decode back into its z columns and into ctx, encode
-// back into z0 and ctx, aux_encode back into ctx - d ctx is the SUM of the three, made before the trunk's backward.  The ten plain-Linear weight
-// gradients go out as one list; the weight-normalised operators' block by block through wn_backward_kernel, as kind 12's.
-// The names csrc/auxvae.h's bodies read, over the shared layout
-struct AuxResLayout : ResLayout {
-  int h; Lin mean, logvar, meanp, logvarp;
-  explicit AuxResLayout(const ardae_model_desc& d) : ResLayout(d), h(cdim), mean(mu), logvar(lv), meanp(mup), logvarp(lvp) {}
-};
-struct AuxResPacked : ResPacked {
-  size_t mean_f, logvar_f, meanp_f, logvarp_f;
-  AuxResPacked(const AuxResLayout& P, PackList& pl) : ResPacked(P, pl), mean_f(mu.f), logvar_f(lv.f), meanp_f(mup.f), logvarp_f(lvp.f) {}
-  explicit AuxResPacked(const AuxResLayout& P, PackList&& sizing = PackList()) : AuxResPacked(P, sizing) {}   // offsets only
-};
-using AuxResEntry = Entry<AuxResLayout, AuxResPacked, ResWs>;
-
-// The evaluation pass (mode 4): the trunk's buffers in front of the shared rows; the trunk runs once, in stage 2
-struct AuxResEvalWs : AuxEvalRows {
-  ResWs T;                                   // x2, the trunk's block buffers, flat; T.inp = ctx [B, c]
-};
-
-// What the bodies of csrc/auxvae.h need to know of kind 19.  Linear on cat[ctx | s]: cat_fwd / cat_bwd / cat_wgrads (host_util.h) at width c.
-struct AuxResVaeTraits {
-  using Layout = AuxResLayout; using Packed = AuxResPacked; using Entry = AuxResEntry;
-  using Grads = GradMap;      // built before the decoder's backward, used again by the trunk's
-  static Entry open(const ardae_model_desc& d, float* workspace, size_t wsf, int B, int mode) { return Entry(d, workspace, wsf, B, 1, mode); }
-  // encode.reparam on h [B, c]: kind 12's head and policy
-  static GaussHead head_of(const ResLayout& P, const ResPacked& K) { return GaussHead{P.cdim, P.zd, P.mu, P.lv, K.mu.f, K.lv.f, false, false}; }
-  static const float* hid(const ResWs& W) { return W.hh; }
-  static GaussBufs bufs(const ResWs& W) {
-    return {W.mu, W.lv, W.z, W.eps, W.kld, W.rec_row, W.pri_row, W.db[6].out, nullptr, W.dlogit, nullptr, W.dzq, W.dz, W.dmu, W.dlv};
-  }
-  // the trunk and aux_encode's two Linears on ctx: mu0, lv0 (no clip)
-  static int stats_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, float* mu0, float* lv0, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    ARDAE_TRY(trunk_fwd(P, K, params, packed, x, B, W, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.mu0.f, params + P.mu0.b, mu0, st));
-    return dense_fwd(ACT_NONE, B, P.nd, W.inp, P.cdim, P.cdim, packed + K.lv0.f, params + P.lv0.b, lv0, st);
-  }
-  // (the two draws are in W.eps0 / W.epsz: aux_vae_forward)  the trunk, aux_encode, z0, encode.fc
-  static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    ARDAE_TRY(stats_fwd(e, params, packed, x, B, W.mu0, W.lv0, st));
-    ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
-    return cat_fwd(ACT_ELU, B, 1, P.cdim, W.inp, P.cdim, packed + K.efc.fi, params + P.efc.b, W.z0, P.nd, packed + K.efc.fn, W.rbh, W.hh, st);
-  }
-  // the auxiliary decoder on [ctx | z] and the pair KL, added into the head's KL rows; then the decoder (unfused: the backward reads its columns)
-  static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    ARDAE_TRY(cat_fwd(ACT_ELU, B, 1, P.cdim, W.inp, P.cdim, packed + K.rfc.fi, params + P.rfc.b, W.z, P.zd, packed + K.rfc.fn, W.rb2, W.hr, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.hr, P.cdim, P.cdim, packed + K.mup.f, params + P.mup.b, W.mup, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.hr, P.cdim, P.cdim, packed + K.lvp.f, params + P.lvp.b, W.lvp, st));
-    ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
-    return ardae::decoder_fwd(P, K, params, packed, W.z, B, W, nullptr, st);
-  }
-  static GradMap grads_of(Entry& e, const float* params, const float* packed, float* g, float beta) { return grad_map(e.P, e.W, params, packed, g, beta); }
-  static int decoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) { return ardae::decoder_bwd(e.P, e.K, packed, e.W, B, gm, st); }
-  // d ctx is the SUM of the three networks' parts, made before the trunk's backward: the auxiliary decoder's goes to dB0 (and dz = W.dzq + dhr Wz) ...
-  static int aux_decoder_bwd(Entry& e, const float* packed, int B, GradMap&, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    ARDAE_TRY(dense_bwd2(ACT_ELU, B, P.cdim, W.dmup, packed + K.mup.b, W.dlvp, packed + K.lvp.b, P.nd, W.hr, W.dhr, st));
-    return cat_bwd(B, P.cdim, W.dhr, P.zd, packed + K.rfc.bn, W.dzq, W.dz, P.cdim, packed + K.rfc.bi, nullptr, W.dB0, st);
-  }
-  // ... encode.fc's joins it: dB1 = dB0 + dhh Wc ...
-  static int encode_fc_bwd(Entry& e, const float* packed, int B, GradMap&, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    ARDAE_TRY(dense_bwd2(ACT_ELU, B, P.cdim, W.dmu, packed + K.mu.b, W.dlv, packed + K.lv.b, P.zd, W.hh, W.dhh, st));
-    return cat_bwd(B, P.cdim, W.dhh, P.nd, packed + K.efc.bn, nullptr, W.dz0, P.cdim, packed + K.efc.bi, W.dB0, W.dB1, st);
-  }
-  // ... and the first head's two Linears (there is no clip in this family) go straight back into ctx.  The ten plain-Linear weight gradients, written
-  // in place (no weight norm), go out as one list; the weight-normalised operators' block by block in the trunk's backward.
-  static int aux_encoder_bwd(Entry& e, const float* packed, int B, GradMap& gm, hipStream_t st) {
-    auto& [P, K, ws, W] = e;
-    const int cd = P.cdim;
-    { LinArgs A{}; A.Y = W.dinp; A.ldY = cd;
-      ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, cd, W.dmu0, P.nd, P.nd, packed + K.mu0.b, W.dlv0, P.nd, P.nd, packed + K.lv0.b, A, st)); }
-    ARDAE_TRY(launch_axpy(W.dB1, (int64_t)B * cd, 1.f, W.dinp, st));
-    WgradList wl(gm.grads, gm.grads_beta);
-    wl.push(B, P.zd, cd, W.dmu, W.hh, cd, wl.g(P.mu.w), cd, wl.g(P.mu.b));
-    wl.push(B, P.zd, cd, W.dlv, W.hh, cd, wl.g(P.lv.w), cd, wl.g(P.lv.b));
-    cat_wgrads(wl, B, P.efc, cd, W.dhh, W.z0, W.inp);
-    wl.push(B, P.nd, cd, W.dmu0, W.inp, cd, wl.g(P.mu0.w), cd, wl.g(P.mu0.b));
-    wl.push(B, P.nd, cd, W.dlv0, W.inp, cd, wl.g(P.lv0.w), cd, wl.g(P.lv0.b));
-    wl.push(B, P.nd, cd, W.dmup, W.hr, cd, wl.g(P.mup.w), cd, wl.g(P.mup.b));
-    wl.push(B, P.nd, cd, W.dlvp, W.hr, cd, wl.g(P.lvp.w), cd, wl.g(P.lvp.b));
-    cat_wgrads(wl, B, P.rfc, cd, W.dhr, W.z, W.inp);
-    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
-    return trunk_wn_bwd(P, K, packed, W, B, gm, gm.grads_beta, st);
-  }
-  static void size_wgrads(Entry&, int) {}      // the carve has taken the weight-gradient scratch
-  // the evaluation pass (aux_vae_iwae_draw, csrc/auxvae.h)
-  using EvalWs = AuxResEvalWs;
-  static void carve_eval(const AuxResLayout& P, const AuxResPacked&, Bump& ws, int B, int k, AuxResEvalWs& W) {
-    W.T.x2 = ws.take((size_t)B * 784);
-    W.T.tb.resize(P.trunk.size());
-    for (size_t i = 0; i < P.trunk.size(); ++i) blk_carve(P.trunk[i], B, ws, W.T.tb[i], false);
-    W.T.flat = ws.take((size_t)B * 512);
-    W.T.inp = W.T.tb.back().out;
-    W.carve_rows(ws, B, k, P.nd, P.zd, P.cdim, 1);
-  }
-  static int eval_prepare(const AuxResLayout&, const float* x, int, AuxResEvalWs&, const float*& xs, hipStream_t) {
-    xs = x;
     return 0;
   }
-  // stage 2 runs the trunk (params and packed are first at hand here); stage 3 reads its ctx again
-  static int eval_hidden(const AuxResLayout& P, const AuxResPacked& K, const float* params, const float* packed, int stage, const float* xs, const float* s,
-                         int B, int k, AuxResEvalWs& W, const float*& hid, hipStream_t st) {
-    const Lin& l = stage == 2 ? P.efc : P.rfc;
-    const LinPk& c = stage == 2 ? K.efc : K.rfc;
-    hid = W.t[1];
-    if (stage == 2) ARDAE_TRY(trunk_fwd(P, K, params, packed, xs, B, W.T, st));
-    return cat_fwd(ACT_ELU, B, k, P.cdim, W.T.inp, P.cdim, packed + c.fi, params + l.b, s, l.in - P.cdim, packed + c.fn, W.rb, W.t[1], st);
+  // kind 6: the two reparameterisations and their heads backwards
+  static int aux_bwd(Entry& e, const float* packed, const float* noise, int B, int nz, GradMap& gm, hipStream_t st) {
+    auto& [P, K, ws, W] = e;
+    const int R = B * nz, ldn = P.nd + P.zd;
+    WgradList wl(gm.grads);              // plain nn.Linear gradients are written in place by the wgrad kernel (no weight norm)
+    auto plain_wgrad = [&](int M, const Lin& l, const float* G, const float* X, int ldX, int col0, int I, bool bias) {
+      wl.push(M, l.out, I, G, X, ldX, gm.grads + l.w + col0, l.in, bias ? gm.grads + l.b : nullptr).beta = gm.grads_beta;
+    };
+    // z = mu + exp(lv/2) eps,  lv = spm4(lvr)
+    float* dlv = W.sc.g;           // [R, zd]
+    ARDAE_TRY(launch_reparam_bwd(W.dzq, W.z, W.mu, R, P.zd, 1, dlv, st));
+    RES_LAUNCH(spm4_kernel, (int64_t)R * P.zd, W.lvr, (const float*)dlv, dlv, (int64_t)R * P.zd, (int)P.clipped);
+    plain_wgrad(R, P.mu, W.dzq, W.hh, P.cdim, 0, P.cdim, true);
+    plain_wgrad(R, P.lv, dlv, W.hh, P.cdim, 0, P.cdim, true);
+    float* dhh = W.dR0;            // [R, cdim]
+    { LinArgs A{}; A.Y = dhh; A.ldY = P.cdim; ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, R, P.cdim, W.dzq, P.zd, P.zd, packed + K.mu.b, dlv, P.zd, P.zd, packed + K.lv.b, A, st)); }
+    ARDAE_TRY(launch_mul_dact(dhh, W.hh, ACT_ELU, dhh, (int64_t)R * P.cdim, st));
+    ARDAE_TRY(launch_segment_sum(dhh, P.cdim, B, nz, P.cdim, 1.f, W.dB0, P.cdim, st));      // d rbh [B, cdim]
+    plain_wgrad(R, P.efc, dhh, W.z0, P.nd, P.cdim, P.nd, true);                              // z0 columns + bias
+    plain_wgrad(B, P.efc, W.dB0, W.inp, P.cdim, 0, P.cdim, false);                           // image columns
+    float* dz0 = W.dR1;            // [R, nd] = dhh W_fc[:, cdim:]
+    ARDAE_TRY(dense_fwd(ACT_NONE, R, P.nd, dhh, P.cdim, P.cdim, packed + K.efc.bn, nullptr, dz0, st));
+    // z0 = mu0[b] + exp(lv0[b] / 2) eps0,  lv0 = spm4(lv0r): reduce over the nz rows of an image first
+    float* dlv0_rows = W.sc.dh;    // [R, nd]
+    ARDAE_TRY(launch_reparam_bwd(dz0, W.z0, W.mu0, R, P.nd, nz, dlv0_rows, st, P.clipped ? 1.f : 0.f, noise, ldn));
+    ARDAE_TRY(launch_segment_sum(dz0, P.nd, B, nz, P.nd, 1.f, W.dB1, P.nd, st));            // d mu0 [B, nd]
+    ARDAE_TRY(launch_segment_sum(dlv0_rows, P.nd, B, nz, P.nd, 1.f, W.dB2, P.nd, st));      // d lv0 [B, nd]
+    RES_LAUNCH(spm4_kernel, (int64_t)B * P.nd, W.lv0r, (const float*)W.dB2, W.dB2, (int64_t)B * P.nd, (int)P.clipped);
+    plain_wgrad(B, P.mu0, W.dB1, W.inp, P.cdim, 0, P.cdim, true);
+    plain_wgrad(B, P.lv0, W.dB2, W.inp, P.cdim, 0, P.cdim, true);
+    ARDAE_TRY(flush_wgrad(wl, W.wscratch, W.wscratch_floats, st));
+    // d inp = d rbh W_fc[:, :cdim] + d mu0 W_mu0 + d lv0r W_lv0
+    float* part = W.dflat;         // [B, cdim] scratch (cdim <= 512)
+    { LinArgs A{}; A.Y = part; A.ldY = P.cdim;
+      ARDAE_TRY(lin2(EPI_ACT, ACT_NONE, B, P.cdim, W.dB0, P.cdim, P.cdim, packed + K.efc.bi, W.dB1, P.nd, P.nd, packed + K.mu0.b, A, st)); }
+    return dense_bwd(ACT_NONE, B, P.cdim, W.dB2, P.nd, packed + K.lv0.b, part, W.dinp, st, part);       // V * 1 + Q
   }
 };
-
-int auxresvae_decode(const ardae_model_desc& d, const float* params, const float* packed, const float* z, int R, float* workspace, size_t wsf, float* out0,
-                     hipStream_t st, float*) {
-  AuxResEntry entry(d, workspace, wsf, R, 1, 2);
-  auto& [P, K, ws, W] = entry;
-  ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
-  return decoder_fwd(P, K, params, packed, z, R, W, out0, st, tail_fused_default(), mid_fused_default());
-}
 
 }  // namespace
 
 // (host pass only: a const object with a constant initialiser is otherwise emitted for the device too, where no entry point exists)
 #ifndef __HIP_DEVICE_COMPILE__
-const Family RES_FAMILY = ip_family<ResTraits>(res_pack);
-static const GaussFamily RESVAE_GAUSS = gauss_family<ResVaeTraits>();
-const Family RESVAE_FAMILY = {resvae_desc_check, no_caps, family_param_floats<ResLayout, ResPacked>, family_packed_floats<ResLayout, ResPacked>,
-                              resvae_workspace_floats, res_pack, vae_no_encode, resvae_decode, vae_no_forward, vae_no_backward, &RESVAE_GAUSS};
-static const GaussFamily AUXRESVAE_GAUSS = aux_gauss_family<AuxResVaeTraits>();
-const Family AUXRESVAE_FAMILY = {auxresvae_desc_check, no_caps, family_param_floats<AuxResLayout, AuxResPacked>,
-                                 family_packed_floats<AuxResLayout, AuxResPacked>, aux_workspace_floats<AuxResVaeTraits>, res_pack, vae_no_encode,
-                                 auxresvae_decode, vae_no_forward, vae_no_backward, &AUXRESVAE_GAUSS};
+const Family RES_FAMILY = ip_family<ResTraits>(ipres_pack);
 #endif
 
 }  // namespace ardae
 
 using namespace ardae;
 
-// the descriptor rules of the two kinds ardae_resconv_tail takes
-static int tail_desc_check(const ardae_model_desc* d) { return d->kind == 19 ? auxresvae_desc_check(d) : resvae_desc_check(d); }
+// ================================================================================================ ardae_resconv_tail / ardae_resconv_mid
+// what the unfused launches keep, carved once for the call and for its *_workspace_floats: u28 and dec[6]'s columns, hidden map and output ...
+struct TailBufs { float* u28; BlkBuf u; };
+static TailBufs tail_carve(const ResLayout& P, int R, Bump& ws) {
+  TailBufs t{ws.take((size_t)R * 784 * 16), {}};
+  blk_carve(P.dec[6], R, ws, t.u);
+  return t;
+}
+// ... c7, u14 and the columns, hidden maps and outputs of dec[4] / dec[5]
+struct MidBufs { float *c7, *u14; BlkBuf u4, u5; };
+static MidBufs mid_carve(const ResLayout& P, int R, Bump& ws) {
+  MidBufs m{ws.take((size_t)R * 49 * 32), ws.take((size_t)R * 196 * 32), {}, {}};
+  blk_carve(P.dec[4], R, ws, m.u4); blk_carve(P.dec[5], R, ws, m.u5);
+  return m;
+}
+// the decoder's blocks of the two kinds ardae_resconv_tail takes (their descriptor rules: the Family row's)
+static ResDecoderView decoder_view(const ardae_model_desc* d) { return d->kind == 19 ? auxresvae_decoder_view(*d) : resvae_decoder_view(*d); }
 
 extern "C" {
 
-// floats of the buffers the unfused launches keep: u28 and dec[6]'s columns, hidden map and output
 size_t ardae_resconv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant) {
-  if (!d || (d->kind != 12 && d->kind != 19) || tail_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
+  if (!d || (d->kind != 12 && d->kind != 19) || family(d).desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
   if (variant == 1 || (variant == 0 && tail_fused_default())) return 0;
-  const ResLayout P(*d);
   Bump ws;
-  BlkBuf u;
-  ws.take((size_t)R * 784 * 16);
-  blk_carve(P.dec[6], R, ws, u, false);
+  tail_carve(decoder_view(d).P, R, ws);
   return ws.off;
 }
 
@@ -1482,36 +1146,29 @@ int ardae_resconv_tail(const ardae_model_desc* d, const float* params, const flo
                        size_t workspace_floats, float* logits, void* stream) {
   ARDAE_CHECK_ARG(d != nullptr, "resconv_tail: desc is NULL");
   ARDAE_CHECK_ARG(d->kind == 12 || d->kind == 19, "resconv_tail: kind must be 12 (MNISTResConvVAE) or 19 (MNISTResConvAuxVAE), got %d", d->kind);
-  ARDAE_TRY(tail_desc_check(d));
+  ARDAE_TRY(family(d).desc_check(d));
   ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "resconv_tail: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
   ARDAE_CHECK_ARG(params && packed && y14 && logits, "resconv_tail: null pointer argument");
   ARDAE_CHECK_ARG(R > 0 && R < (1 << 20), "resconv_tail: bad batch (R=%d)", R);
   if (variant == 0) variant = tail_fused_default() ? 1 : 2;
   hipStream_t st = (hipStream_t)stream;
-  const ResLayout P(*d);
-  const ResPacked K(P);
+  const auto [P, K, mid_w] = decoder_view(d);
   if (variant == 1) return tail_fused(P.dec[6], K.dec[6], params, packed, y14, R, logits, st);
   const size_t need = ardae_resconv_tail_workspace_floats(d, R, 2);
   ARDAE_CHECK_ARG(workspace, "resconv_tail: null pointer argument (the unfused launches need a workspace)");
   ARDAE_CHECK_ARG(workspace_floats >= need, "resconv_tail: workspace too small (%zu < %zu floats)", workspace_floats, need);
   Bump ws(workspace, workspace_floats);
-  float* u28 = ws.take((size_t)R * 784 * 16);
-  BlkBuf u;
-  blk_carve(P.dec[6], R, ws, u, false);
-  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, y14, 14, 16, u28, (int64_t)R * 784 * 16);
-  ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, u28, R, ACT_NONE, u, st));
-  return launch_copy(u.out, (size_t)R * 784, logits, st);
+  TailBufs t = tail_carve(P, R, ws);
+  RES_LAUNCH(upsample2_fwd_kernel, (int64_t)R * 784 * 16, y14, 14, 16, t.u28, (int64_t)R * 784 * 16);
+  ARDAE_TRY(blk_fwd(P.dec[6], K.dec[6], params, packed, t.u28, R, ACT_NONE, t.u, st));
+  return launch_copy(t.u.out, (size_t)R * 784, logits, st);
 }
 
-// floats of the buffers the unfused launches keep: c7, u14 and the columns, hidden maps and outputs of dec[4] / dec[5]
 size_t ardae_resconv_mid_workspace_floats(const ardae_model_desc* d, int R, int variant) {
-  if (!d || d->kind != 19 || auxresvae_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
+  if (!d || d->kind != 19 || family(d).desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
   if (variant == 1 || (variant == 0 && mid_fused_default())) return 0;
-  const ResLayout P(*d);
   Bump ws;
-  BlkBuf u;
-  ws.take((size_t)R * 49 * 32); ws.take((size_t)R * 196 * 32);
-  blk_carve(P.dec[4], R, ws, u, false); blk_carve(P.dec[5], R, ws, u, false);
+  mid_carve(auxresvae_decoder_view(*d).P, R, ws);
   return ws.off;
 }
 
@@ -1519,25 +1176,22 @@ int ardae_resconv_mid(const ardae_model_desc* d, const float* params, const floa
                       size_t workspace_floats, float* y14, void* stream) {
   ARDAE_CHECK_ARG(d != nullptr, "resconv_mid: desc is NULL");
   ARDAE_CHECK_ARG(d->kind == 19, "resconv_mid: kind must be 19 (MNISTResConvAuxVAE), got %d", d->kind);
-  ARDAE_TRY(auxresvae_desc_check(d));
+  ARDAE_TRY(family(d).desc_check(d));
   ARDAE_CHECK_ARG(variant >= 0 && variant <= 2, "resconv_mid: variant must be 0 (the library's choice), 1 (fused) or 2 (unfused), got %d", variant);
   ARDAE_CHECK_ARG(params && packed && y8 && y14, "resconv_mid: null pointer argument");
   ARDAE_CHECK_ARG(R > 0 && R < (1 << 20), "resconv_mid: bad batch (R=%d)", R);
   if (variant == 0) variant = mid_fused_default() ? 1 : 2;
   hipStream_t st = (hipStream_t)stream;
-  const ResLayout P(*d);
-  const ResPacked K(P);
-  if (variant == 1) return mid_fused(P, K, params, packed, y8, R, y14, st);
+  const auto [P, K, mid_w] = auxresvae_decoder_view(*d);
+  if (variant == 1) return mid_fused(P, K, params, packed, packed + mid_w, y8, R, y14, st);
   const size_t need = ardae_resconv_mid_workspace_floats(d, R, 2);
   ARDAE_CHECK_ARG(workspace, "resconv_mid: null pointer argument (the unfused launches need a workspace)");
   ARDAE_CHECK_ARG(workspace_floats >= need, "resconv_mid: workspace too small (%zu < %zu floats)", workspace_floats, need);
   Bump ws(workspace, workspace_floats);
-  float* c7 = ws.take((size_t)R * 49 * 32);
-  float* u14 = ws.take((size_t)R * 196 * 32);
-  BlkBuf u4, u5;
-  blk_carve(P.dec[4], R, ws, u4, false); blk_carve(P.dec[5], R, ws, u5, false);
-  ARDAE_TRY(mid_unfused(P, K, params, packed, y8, R, c7, u14, u4, u5, st));
-  return launch_copy(u5.out, (size_t)R * 196 * 16, y14, st);
+  MidBufs m = mid_carve(P, R, ws);
+  ARDAE_TRY(mid_unfused(P, K, params, packed, y8, R, m.c7, m.u14, m.u4, m.u5, st));
+  return launch_copy(m.u5.out, (size_t)R * 196 * 16, y14, st);
 }
 
 }  // extern "C"
+

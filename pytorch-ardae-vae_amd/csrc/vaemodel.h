@@ -1,6 +1,6 @@
 // The Gaussian-posterior VAE baselines of vae.py (ardae_model_desc.kind 8: MNISTVAE `--model mnist`, 9: ToyVAE `--model toy`, 11: MNISTConvVAE
 // `--model conv`, 12: MNISTResConvVAE `--model resconv`).  Their algorithm is written ONCE, here, as templates over a family's traits
-// (gauss_vae_forward / _backward / _encode_stats); each family file (csrc/vaemodel.hip: kinds 8 / 9, csrc/convvae.hip, csrc/resmodel.hip) supplies
+// (gauss_vae_forward / _backward / _encode_stats); each family file (csrc/vaemodel.hip: kinds 8 / 9, csrc/convvae.hip, csrc/resvae.hip) supplies
 // its traits and one GaussFamily row of the instantiated bodies, which hangs off its Family row (host_util.h).  The ardae_vae_* entry points of
 // csrc/vaemodel.hip validate and dispatch through family(d).gauss; they know no family by name.
 #pragma once

@@ -1,6 +1,6 @@
 // Gaussian-posterior VAE baselines (vae.py; ardae_model_desc.kind 8: models/vae/mnist.py::VAE, 9: models/vae/toy.py::VAE), orchestrated
 // from the K1 / K6w kernels like csrc/model.hip, plus the one kernel the family adds: the fused Gaussian head.  Also here, for every Gaussian kind
-// (11: csrc/convvae.hip, 12: csrc/resmodel.hip): the head's kernels and its one policy (gauss_head_fwd), and the ardae_vae_* entry points, which
+// (11: csrc/convvae.hip, 12: csrc/resvae.hip): the head's kernels and its one policy (gauss_head_fwd), and the ardae_vae_* entry points, which
 // validate and dispatch through the table's row (family(d).gauss); the algorithm they run is csrc/vaemodel.h's, over each family's traits.
 //
 //   per image (B rows):  xs = 2x - 1 (kind 8) | x (kind 9);  h = MLP_enc(xs)  (n_layers Linear -> act: layers.0 .. n-2, fc)
