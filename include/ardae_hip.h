@@ -201,9 +201,10 @@ typedef struct ardae_cdae_desc {
   int kind;        /* 0 = mlp-grad (MLPGradCARDAE: score = input-gradient of an energy MLP), 1 = mlp-res (direct score);
                     * 2 / 3 = the same two WITHOUT a context (MLPGradARDAE / MLPResARDAE, see "unconditional AR-DAE" below);
                     * 6 / 7 = the plain DAEs, without a context and without the sigma input (MLPGradDAE / MLPResDAE, see "plain DAE"
-                    * below).  4 and 5 are not kinds */
+                    * below); 10 / 11 = the plain CONDITIONAL DAEs, kinds 0 / 1 without the sigma input (MLPGradCDAE / MLPResCDAE, see
+                    * "plain conditional DAE" below).  4, 5, 8 and 9 are not kinds */
   int input_dim;   /* z */
-  int context_dim; /* c  (kinds 0 / 1: >= 1; kinds 2 / 3 / 6 / 7: 0) */
+  int context_dim; /* c  (kinds 0 / 1 / 10 / 11: >= 1; kinds 2 / 3 / 6 / 7: 0) */
   int h_dim;
   int n_layers;    /* --cdae-n-layers */
   int act;         /* any ARDAE_ACT_* but NONE (with a piecewise linear one mlp-grad's second-order terms are zero)  */
@@ -226,7 +227,8 @@ int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const f
  * a_1 = act(xbar A_1^T + b_1) (graddae/mlp.py:414-434), written into the cDAE workspace; the rest is ardae_cdae_loss_grads from layer 2 on.
  * xbar / sigma / eps_out / std_b are written as by ardae_latent_perturb_draw (the weight gradient of A_1 and the DAE-loss layer read them).
  * ardae_cdae_perturb_fused_ok: 1 if the shape qualifies (nstd == 1, the draw kernel's conditions, z % 8 == 0, z <= 64, nz % 32 == 0,
- * h % 32 == 0, relu / softplus); otherwise call ardae_latent_perturb* and ardae_cdae_loss_grads. */
+ * h % 32 == 0, relu / softplus; kinds 0 / 1 - the kernel draws sigma, so 0 for kinds 10 / 11); otherwise call ardae_latent_perturb* and
+ * ardae_cdae_loss_grads. */
 int ardae_cdae_perturb_fused_ok(const ardae_cdae_desc* d, int nz, int nstd);
 int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* latent, const float* z0,
                                   const float* ctx, int B, int nz, float std_scale, float delta, uint64_t seed, uint64_t offset_xi,
@@ -289,6 +291,34 @@ int ardae_dae_noise_perturb(const float* x /* [B, d] */, const float* eps /* [B*
  * sigma_annealing <= 0: the constant sigma_min. */
 int ardae_dae_state_advance(void* state, uint64_t rng_inc, double lr, double beta1, double beta2, double sigma_max, double sigma_min,
                             int64_t sigma_annealing, void* stream);
+
+/* ---- plain conditional DAE (models/graddae/mlp.py:210-339, models/resdae/mlp.py:170-284): ardae_cdae_desc.kind 10 / 11 ----------------
+ * ConditionalDAE, the conditional score network that is NOT amortised over the noise level (MLPGradCDAE, kind 10: score = input-gradient
+ * of an energy MLP; MLPResCDAE, kind 11: the MLP's output is the score).  Parameters in the order of kinds 0 / 1 - ctx_encode.*,
+ * inp_encode.*, neglogprob.* (kind 10) / dae.* (kind 11) - but layers.0.weight is [h, 2h] = [W1a | W1c]: there is no sigma column,
+ * h_1 = act(W1a a_L + [W1c c_L + d_1](b)).  context_dim >= 1 and ctx non-NULL, as for kinds 0 / 1.  ardae_cdae_param_floats /
+ * packed_floats / workspace_floats / pack / loss_grads / score take these kinds; the update is the one of kinds 0 / 1 with every
+ * sigma-column term removed, and every launch decision is the sibling's (kind 10: kind 0's, the one-launch chain of the N == B score pass
+ * included; kind 11: kind 1's).  The loss is unchanged, mean((sigma[r] g + eps)^2) with a per-row sigma [N]; ardae_cdae_score ignores
+ * `sigma` (NULL allowed), as ConditionalDAE.glogprob never reads std.  Kind 10 leaves neglogprob.fc.bias's gradient untouched.
+ * ardae_cdae_perturb_fused_ok and ardae_dae_perturb_fused_ok are 0 for these kinds (those kernels draw sigma); a fused first-layer kernel
+ * did not pay for kinds 6 / 7 and none is built here.
+ *
+ * ardae_latent_noise_perturb: ivae_ardae.py:753-767 with ONE noise level, the counterpart of ardae_latent_perturb_nstd:
+ * u = std_scale (latent[b, i] - z0[b]), rounded as ardae_center_scale rounds it; xbar[(b, i, j)] = fma(s, eps[(b, i, j)], u) and
+ * sigma_out[r] = s for all N = B * nz * nstd rows, where s is the f32 in bytes 24..27 of `dae_state` (ardae_dae_state_advance) when
+ * that is non-NULL, else the argument `sigma`.  latent [B, nz, z], z0 [B, z], eps / xbar [N, z]; the broadcast over j is never written.
+ * ardae_latent_noise_perturb_draw: the same with eps made in the kernel, the counterpart of ardae_latent_perturb_draw: element i of the
+ * call's rows = element first_row * z + i of the draw (seed, offset_eps [+ dae_state's rng_offset]), keyed exactly like
+ * ardae_philox_normal_at (first_row a multiple of 4), written to eps_out; xbar / sigma_out / eps_out hold the bits of
+ * ardae_philox_normal_at followed by ardae_latent_noise_perturb.  64-row tiles, a last partial tile is masked.
+ * ardae_latent_noise_perturb_draw_ok: 1 for every positive (nz, nstd, z). */
+int ardae_latent_noise_perturb(const float* latent, const float* z0, const float* eps, int B, int nz, int nstd, int z, float std_scale, float sigma,
+                               const void* dae_state, float* xbar, float* sigma_out, void* stream);
+int ardae_latent_noise_perturb_draw_ok(int nz, int nstd, int z);
+int ardae_latent_noise_perturb_draw(const float* latent, const float* z0, int B, int nz, int nstd, int z, float std_scale, float sigma,
+                                    const void* dae_state, uint64_t seed, uint64_t offset_eps, uint64_t first_row, float* xbar, float* sigma_out,
+                                    float* eps_out, void* stream);
 
 /* ---- energy-function fitting (notebooks/ardae_fit.ipynb): energies, the implicit generator, torch.optim.Adam + StepLR -------------
  * One iteration of the notebook: num_dae_updates AR-DAE updates, each on a fresh sample of the generator, then one generator update

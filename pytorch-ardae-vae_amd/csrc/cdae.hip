@@ -1,5 +1,5 @@
-// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1), unconditional (kind 2 / 3) and plain DAE (kind 6 / 7): forward, score pass, DAE loss,
-// double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
+// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1), unconditional (kind 2 / 3), plain DAE (kind 6 / 7) and plain conditional DAE
+// (kind 10 / 11): forward, score pass, DAE loss, double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
 //
 // Maths: SURVEY.md Appendix A (closed form of models/graddae/mlp.py:400-444 under autograd), notation below.
 //   rows i=1..N (N = B*S), image b(i) = i / S
@@ -25,8 +25,10 @@
 //   g = e_1 W1x;  eb_1 = gbar W1x^T;  W1x's gradient = e_1 (x) gbar + qhat_1 (x) xbar.
 // The plain DAEs (kinds 6 / 7; models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90) are the unconditional kinds whose network does not see
 // sigma: W1 = W1x [h, z], no w1s, h_1 = sp(W1x xbar + d_1).  The loss keeps its per-row sigma.
-// In the code: `cond` marks what exists for kinds 0 / 1 only, `grad` what the energy kinds (0 / 2 / 6) add to the res kinds, `has_sigma`
-// the sigma column of W1 (every kind but 6 / 7).
+// The plain conditional DAEs (kinds 10 / 11; models/graddae/mlp.py:210-339, models/resdae/mlp.py:170-284) relate to kinds 0 / 1 as 6 / 7 do to 2 / 3:
+// W1 = [W1a | W1c] [h, 2h], no w1s, h_1 = sp(W1a a_L + [W1c c_L + d_1](b)).  The loss keeps its per-row sigma.
+// In the code: `cond` marks what exists for kinds 0 / 1 / 10 / 11 only, `grad` what the energy kinds (0 / 2 / 6 / 10) add to the res kinds,
+// `has_sigma` the sigma column of W1 (kinds 0 - 3).
 #include <vector>
 
 #include "ardae_hip.h"
@@ -36,6 +38,8 @@
 
 namespace ardae {
 namespace {
+
+bool cond_kind(int kind) { return kind < 2 || kind == 10 || kind == 11; }
 
 struct CdaeLayout {
   int kind, z, c, h, L, act;
@@ -47,7 +51,7 @@ struct CdaeLayout {
   int sigma_col() const { return cond ? 2 * h : z; }
 
   explicit CdaeLayout(const ardae_cdae_desc& d)
-      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(d.kind < 2), grad(d.kind % 2 == 0), has_sigma(d.kind < 6) {
+      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(cond_kind(d.kind)), grad(d.kind % 2 == 0), has_sigma(d.kind < 6) {
     size_t off = 0;
     auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
     if (cond) {
@@ -84,10 +88,11 @@ struct PackedLayout {
 
 int desc_ok(const ardae_cdae_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "cdae: desc is NULL");
-  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7,
-                  "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad), 3 (unconditional res), 6 (plain DAE grad) or 7 (plain DAE res)");
-  ARDAE_CHECK_ARG(d->kind >= 2 || d->context_dim >= 1, "cdae: kinds 0 / 1 need context_dim >= 1 (got %d)", d->context_dim);
-  ARDAE_CHECK_ARG(d->kind < 2 || d->context_dim == 0, "cdae: kinds 2 / 3 have no context: context_dim must be 0 (got %d)", d->context_dim);
+  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7 || d->kind == 10 || d->kind == 11,
+                  "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad), 3 (unconditional res), 6 (plain DAE grad), 7 (plain DAE res), "
+                  "10 (plain conditional DAE grad) or 11 (plain conditional DAE res)");
+  ARDAE_CHECK_ARG(!cond_kind(d->kind) || d->context_dim >= 1, "cdae: kinds 0 / 1 / 10 / 11 need context_dim >= 1 (got %d)", d->context_dim);
+  ARDAE_CHECK_ARG(cond_kind(d->kind) || d->context_dim == 0, "cdae: kinds 2 / 3 / 6 / 7 have no context: context_dim must be 0 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->n_layers >= 1, "cdae: bad dimensions");
   ARDAE_CHECK_ARG(d->n_layers <= 6, "cdae: n_layers <= 6 supported (3L+1 gradient problems per batch)");
   // every activation of get_nonlinear_func; with a piecewise linear one mlp-grad's second-order terms vanish, as
@@ -103,7 +108,7 @@ struct CdaeWs {
   int ltiles, ctiles;
 };
 
-// The conditional kinds take every buffer whichever of the two reads it (kind 1 leaves e, r, tau, tau', pbar and cs_taup unused); the
+// The conditional kinds take every buffer whichever of the two reads it (kinds 1 / 11 leave e, r, tau, tau', pbar and cs_taup unused); the
 // unconditional kinds take what they read, so hh[1] is the arena's first piece (the fused front end of dae_perturb.hip fills it).
 void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, CdaeWs& W) {
   const int N = B * S, h = P.h, L = P.L, z = P.z;
@@ -202,7 +207,7 @@ LinArgs lin_args(int act, int M, int Nout, const float* x, int ldx, int K, const
 
 // A run of consecutive N-row layers of one epilogue kind, each reading its predecessor's output: the longest prefixes that
 // qualify go out as ONE launch each (linear_chain.hip: the small-shard regime), the rest layer by layer.
-// one_by_one: no grouping, every layer is a launch of its own (kind 1's backward: moving it onto grouped launches is a change of its own, to be measured).
+// one_by_one: no grouping, every layer is a launch of its own (the backward of kinds 1 / 11: moving it onto grouped launches is a change of its own, to be measured).
 struct LayerRun {
   int epi;
   hipStream_t st;
@@ -243,8 +248,8 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   ARDAE_TRY(desc_ok(d));
   const CdaeLayout P(*d);
   const bool cond = P.cond, grad = P.grad;
-  ARDAE_CHECK_ARG(cond || ctx == nullptr, "cdae: kinds 2 / 3 take no context: ctx must be NULL");
-  // the plain DAEs' score does not read sigma (DAE.glogprob ignores std); their loss layer does
+  ARDAE_CHECK_ARG(cond || ctx == nullptr, "cdae: kinds 2 / 3 / 6 / 7 take no context: ctx must be NULL");
+  // the plain DAEs' score does not read sigma (DAE.glogprob / ConditionalDAE.glogprob ignore std); their loss layer does
   ARDAE_CHECK_ARG(params && packed && xbar && (sigma || (!P.has_sigma && !need_grads)) && (ctx || !cond) && workspace, "cdae: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S < (int64_t)1 << 30, "cdae: bad batch (B=%d, S=%d)", B, S);
   ARDAE_CHECK_ARG(!need_grads || (eps && loss && grads), "cdae: loss/grads/eps must be given");
@@ -296,7 +301,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   };
 
   // ------------------------------------------------------------------ forward: ctx (B rows, once per image), inp and energy (N rows)
-  if (!need_grads && P.kind == 0 && N == B && linear_small_eligible(inp_layer(1), EPI_ACT)) {
+  if (!need_grads && cond && grad && N == B && linear_small_eligible(inp_layer(1), EPI_ACT)) {
     // The sigma = 0 score pass of the VAE update (glogprob on B rows, models/graddae/mlp.py:446-483): 4 L + 2 per-image problems, every one
     // a link of a dependent chain - ONE launch walks them level by level (linear_small_chain_kernel): [ctx_l | inp_l] l = 1..L, the
     // per-image bias of the first energy layer, the energy layers, the score layers, g.
@@ -367,7 +372,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   }
   {
     // ordinary backward of the energy chain and (cond) the input encoder; the grad kinds seed every layer with its qbar_l / pbar_l
-    LayerRun run(EPI_DACT, st, P.kind == 1);
+    LayerRun run(EPI_DACT, st, cond && !grad);
     for (int l = L; l >= 2; --l) {
       LinArgs A{}; A.S = hh[l - 1]; A.ldS = h; A.Y = qhat[l - 1]; A.ldY = h;
       if (grad) { A.Q = qbar[l - 1]; A.ldQ = h; }
@@ -399,8 +404,8 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
 // what the fused front end of dae_perturb.hip needs of an unconditional network: where W1 / d_1 live, and the carved h_1 it writes
 int dae_front_slots(const ardae_cdae_desc* d, int N, float* workspace, size_t ws_floats, size_t* w1, size_t* b1, float** h1) {
   ARDAE_TRY(desc_ok(d));
-  ARDAE_CHECK_ARG(d->kind >= 2, "dae_perturb_loss_grads: the network must be unconditional");
   const CdaeLayout P(*d);
+  ARDAE_CHECK_ARG(!P.cond, "dae_perturb_loss_grads: the network must be unconditional");
   const size_t need = workspace_floats(P, N, 1, true);
   ARDAE_CHECK_ARG(ws_floats >= need, "dae_perturb_loss_grads: workspace too small (%zu < %zu floats)", ws_floats, need);
   Bump ws(workspace, ws_floats);
@@ -447,8 +452,8 @@ int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const f
 }
 int ardae_cdae_perturb_fused_ok(const ardae_cdae_desc* d, int nz, int nstd) {
   if (desc_ok(d) != 0) return 0;
-  const CdaeLayout P(*d);   // the fused draw + A_1 kernel is the conditional kinds'
-  return P.cond && nstd == 1 && P.inp[0].in == P.z && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
+  const CdaeLayout P(*d);   // the fused draw + A_1 kernel is the conditional AR-DAE kinds' (it draws sigma)
+  return P.cond && P.has_sigma && nstd == 1 && P.inp[0].in == P.z && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
 }
 int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* latent, const float* z0,
                                   const float* ctx, int B, int nz, float std_scale, float delta, uint64_t seed, uint64_t offset_xi,

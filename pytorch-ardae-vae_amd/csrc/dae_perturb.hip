@@ -1,6 +1,7 @@
 // Front end of the unconditional AR-DAE update (ardae_cdae_desc.kind 2 / 3): the perturbation of a broadcast batch, and the same with
 // its two draws and the score network's first layer in one kernel.  And the plain DAE's perturbation (kind 6 / 7, notebooks/dae_toy.ipynb):
-// one noise level for the whole batch, a value or the DAE state's.
+// one noise level for the whole batch, a value or the DAE state's.  And the plain conditional DAE's (kind 10 / 11): the same one noise level on
+// the centred, scaled latent samples of ivae_ardae.py:753-767, with the eps draw read or made in the kernel.
 //
 // Reference: the training cells of notebooks/ardae_toy.ipynb / ardae_fit.ipynb (x.unsqueeze(1).expand(B, nsigma, d).contiguous(),
 // std = delta * randn) and add_gaussian_noise (models/graddae/mlp.py:21-23).  Row (b, j) reads x[b]: the broadcast is never written.
@@ -44,6 +45,63 @@ __global__ __launch_bounds__(256) void dae_noise_perturb_kernel(const float* __r
     const int k = (int)(e - row * d);
     xbar[e] = __builtin_fmaf(s, eps[e], x[(row / nsigma) * d + k]);
     if (k == 0) sigma_out[row] = s;
+  }
+}
+
+// The plain conditional DAE's perturbation (the one-noise-level counterpart of latent_perturb_kernel): row (b, i, j) of the B * nz * nstd rows reads
+// latent[b, i]; u = std_scale (latent - z0[b]) is rounded as center_scale_kernel rounds it, then xbar = fma(s, eps, u).
+__device__ __forceinline__ float latent_noise_xbar(const float* __restrict__ latent, const float* __restrict__ z0, int64_t row, int k, int nz, int nstd,
+                                                   int zd, float std_scale, float s, float ep) {
+  const int64_t src = row / nstd;
+  const float u = std_scale * (latent[src * zd + k] - z0[(src / nz) * zd + k]);
+  return __builtin_fmaf(s, ep, u);
+}
+
+__global__ __launch_bounds__(256) void latent_noise_perturb_kernel(const float* __restrict__ latent, const float* __restrict__ z0,
+                                                                   const float* __restrict__ eps, int64_t n, int nz, int nstd, int zd, float std_scale,
+                                                                   float sv, const float* __restrict__ sp, float* __restrict__ xbar,
+                                                                   float* __restrict__ sigma_out) {
+  const float s = sp ? *sp : sv;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = e / zd;
+    const int k = (int)(e - row * zd);
+    xbar[e] = latent_noise_xbar(latent, z0, row, k, nz, nstd, zd, std_scale, s, eps[e]);
+    if (k == 0) sigma_out[row] = s;
+  }
+}
+
+// The same with eps made here.  One workgroup per tile of LN_ROWS rows = 16 zd Philox counters; a thread takes counters t, t + 256, ... of its
+// tile, i.e. four consecutive elements of the [N, zd] draw each, keyed exactly like ardae_philox_normal_at (element i of the call's rows = element
+// first_row zd + i of the draw (seed, off_eps + the block's base offset)).  Rows at or beyond N (a last partial tile) draw and write nothing.
+constexpr int LN_ROWS = 64;
+__global__ __launch_bounds__(256) void latent_noise_perturb_draw_kernel(const float* __restrict__ latent, const float* __restrict__ z0, int N, int nz,
+                                                                        int nstd, int zd, float std_scale, float sv, const DaeState* __restrict__ state,
+                                                                        uint64_t seed, uint64_t off_eps, uint64_t first_row,
+                                                                        float* __restrict__ xbar, float* __restrict__ sigma_out,
+                                                                        float* __restrict__ eps_out, int vec_ok) {
+  const float s = state ? state->sigma : sv;
+  const uint64_t base_off = state ? state->step.rng_offset : 0;
+  const int64_t row0 = (int64_t)blockIdx.x * LN_ROWS;
+  const int64_t n = (int64_t)N * zd, e0 = row0 * zd;
+  const uint64_t q0 = ((first_row + (uint64_t)row0) * (uint64_t)zd) >> 2;     // first_row and LN_ROWS are multiples of 4
+  for (int c = threadIdx.x; c < (LN_ROWS / 4) * zd; c += 256) {
+    const int64_t e = e0 + 4 * (int64_t)c;
+    if (e >= n) break;
+    float v[4], xb[4];
+    philox_normal4(seed, off_eps + base_off, q0 + (uint64_t)c, v);
+    const int lim = n - e < 4 ? (int)(n - e) : 4;
+    for (int i = 0; i < lim; ++i) {
+      const int64_t row = (e + i) / zd;
+      const int k = (int)(e + i - row * zd);
+      xb[i] = latent_noise_xbar(latent, z0, row, k, nz, nstd, zd, std_scale, s, v[i]);
+      if (k == 0) sigma_out[row] = s;
+    }
+    if (lim == 4 && vec_ok) {
+      *reinterpret_cast<f32x4*>(xbar + e) = f32x4{xb[0], xb[1], xb[2], xb[3]};
+      *reinterpret_cast<f32x4*>(eps_out + e) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+      for (int i = 0; i < lim; ++i) { xbar[e + i] = xb[i]; eps_out[e + i] = v[i]; }
+    }
   }
 }
 
@@ -159,6 +217,42 @@ int ardae_dae_noise_perturb(const float* x, const float* eps, int B, int nsigma,
   prof_begin(st, "dae_noise_perturb_kernel", 2.0 * (double)n, 4.0 * (2.0 * (double)n + (double)B * nsigma + (double)B * d));
   hipLaunchKernelGGL(dae_noise_perturb_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, x, eps, n, nsigma, d, s.v,
                      s.p, xbar, sigma_out);
+  prof_end(st);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int ardae_latent_noise_perturb(const float* latent, const float* z0, const float* eps, int B, int nz, int nstd, int z, float std_scale, float sigma,
+                               const void* dae_state, float* xbar, float* sigma_out, void* stream) {
+  ARDAE_CHECK_ARG(latent && z0 && eps && xbar && sigma_out, "latent_noise_perturb: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && nz > 0 && nstd > 0 && z > 0 && (int64_t)B * nz * nstd * z < (int64_t)1 << 31,
+                  "latent_noise_perturb: bad batch (B=%d, nz=%d, nstd=%d, z=%d)", B, nz, nstd, z);
+  const int64_t n = (int64_t)B * nz * nstd * z;
+  const hipStream_t st = (hipStream_t)stream;
+  const DevFloat s = dae_state ? dae_state_sigma(dae_state) : DevFloat(sigma);
+  prof_begin(st, "latent_noise_perturb_kernel", 3.0 * (double)n, 4.0 * (2.0 * (double)n + (double)B * nz * (nstd + z) + (double)B * z));
+  hipLaunchKernelGGL(latent_noise_perturb_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, latent, z0, eps, n, nz,
+                     nstd, z, std_scale, s.v, s.p, xbar, sigma_out);
+  prof_end(st);
+  ARDAE_LAUNCH_CHECK();
+  return 0;
+}
+
+int ardae_latent_noise_perturb_draw_ok(int nz, int nstd, int z) { return nz > 0 && nstd > 0 && z > 0 ? 1 : 0; }
+
+int ardae_latent_noise_perturb_draw(const float* latent, const float* z0, int B, int nz, int nstd, int z, float std_scale, float sigma,
+                                    const void* dae_state, uint64_t seed, uint64_t offset_eps, uint64_t first_row, float* xbar, float* sigma_out,
+                                    float* eps_out, void* stream) {
+  ARDAE_CHECK_ARG(latent && z0 && xbar && sigma_out && eps_out, "latent_noise_perturb_draw: null pointer argument");
+  ARDAE_CHECK_ARG(B > 0 && nz > 0 && nstd > 0 && z > 0 && (int64_t)B * nz * nstd * z < (int64_t)1 << 31,
+                  "latent_noise_perturb_draw: bad batch (B=%d, nz=%d, nstd=%d, z=%d)", B, nz, nstd, z);
+  ARDAE_CHECK_ARG((first_row & 3) == 0, "latent_noise_perturb_draw: first_row must be a multiple of 4 (one Philox counter = 4 normals)");
+  const int N = B * nz * nstd;
+  const hipStream_t st = (hipStream_t)stream;
+  const int vec_ok = ((reinterpret_cast<uintptr_t>(xbar) | reinterpret_cast<uintptr_t>(eps_out)) & 15) == 0 ? 1 : 0;
+  prof_begin(st, "latent_noise_perturb_draw_kernel", 3.0 * (double)N * z, 4.0 * (2.0 * (double)N * z + (double)B * nz * (nstd + z) + (double)B * z));
+  hipLaunchKernelGGL(latent_noise_perturb_draw_kernel, dim3((unsigned)ceil_div(N, LN_ROWS)), dim3(256), 0, st, latent, z0, N, nz, nstd, z, std_scale,
+                     sigma, (const DaeState*)dae_state, seed, offset_eps, first_row, xbar, sigma_out, eps_out, vec_ok);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
   return 0;

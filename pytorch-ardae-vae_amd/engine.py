@@ -99,6 +99,9 @@ class ArdaeEngine:
     def __init__(self, model, cdae, cfg: TrainConfig, batch_size, process_group=None, graph=True, force_dp=False, dp_comm="auto"):
         model._require_gpu()
         cdae._require_gpu()
+        if int(cdae._desc.kind) not in (0, 1):
+            raise TypeError(f"ArdaeEngine trains a conditional AR-DAE (net.MLPGradCARDAE / net.MLPResCARDAE), not a {type(cdae).__name__}: its step "
+                            "block has no slot for a noise level beside beta (a plain conditional DAE runs in ArdaeCondScoreEngine)")
         self.model, self.cdae, self.cfg = model, cdae, cfg
         self.B = int(batch_size)                       # per-rank image batch
         self.dev = model._flat.device
@@ -1042,4 +1045,215 @@ class ArdaeScoreEngine:
             self.opt.advance(self.RNG_STRIDE)
         self._ladder.reset()                    # parameters were rewritten outside of the captured step
         bump_versions(self.dae)
+        self.repack()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Conditional score networks outside the VAE loop: the cDAE update of ivae_ardae.py:743-779 on the caller's samples
+# ---------------------------------------------------------------------------------------------------------------
+class ArdaeCondScoreEngine:
+    """One update of a CONDITIONAL score network on samples of the caller's own amortised sampler (ivae_ardae.py:752-779), as ONE captured
+    unit: centre and scale the samples, perturb them, loss and gradients on B * S * nsigma rows, optimiser, re-pack, advance the step
+    state.  `step(latent [B, S, z], ctx [B, c] | [B, 1, c], latent_mean=None ([B, z] | [B, 1, z]; None: zeros), noise=None)`;
+    `cfg.nsigma` plays the role of --train-nstd-cdae.  The rules are ArdaeScoreEngine's: eager twice, captured at the third call, replayed
+    afterwards (replayed == eager bit for bit), injected noise runs the same launches eagerly, batches are validated before any pointer
+    reaches a kernel.  One stream, one linear graph; there is no data parallelism here.
+
+    A conditional AR-DAE (`net.MLPGradCARDAE` / `net.MLPResCARDAE`) takes a `ScoreConfig`: the launches and selection rules of
+    ArdaeEngine's cDAE phase behind its sampler - `ardae_cdae_perturb_loss_grads` where the shape allows, else `ardae_latent_perturb_draw`,
+    else two draws and `ardae_latent_perturb_nstd` - with sigma = delta * mean_d std_S(u) * xi; `noise={'sigma': xi [N], 'eps': [N, z]}`;
+    in-step Philox offsets RNG_STRIDE * step + {0 (xi), 1 (eps)}; `stats()` reports `loss` and `std_mean / std_max / std_min`.
+
+    A plain conditional DAE (`net.MLPGradCDAE` / `net.MLPResCDAE`) takes a `DaeConfig`: one noise level per step, read from the device
+    block where `ardae_dae_state_advance` leaves the annealed value, so the replay runs through the ramp; the launches are
+    `ardae_latent_noise_perturb_draw` (`draw_form=False`, or injected eps: `ardae_philox_normal_at` and `ardae_latent_noise_perturb`, the same
+    bits) and `ardae_cdae_loss_grads`; `noise={'eps'}` alone, offset RNG_STRIDE * step + 1; `stats()` reports `loss` and `sigma`.
+
+    `score(latent, ctx, latent_mean=None)` is glogprob(std_scale (latent - mean), ctx, sigma = 0) with the engine's weight image, for any
+    batch and sample size: a sampler that stays the caller's torch module takes its entropy gradient as
+    `(std_scale * (latent - mean)).backward(beta * engine.score(latent.detach(), ctx, mean.detach()) / (B * S))` (ivae_ardae.py:826-834)."""
+
+    RNG_STRIDE = ArdaeEngine.RNG_STRIDE
+    DRAW_FORM_DEFAULT = True       # plain kinds: ardae_latent_noise_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
+
+    def __init__(self, cdae, cfg, batch_size, sample_size, std_scale=1.0, graph=True, draw_form=None):
+        cdae._require_gpu()
+        kind = int(cdae._desc.kind)
+        if kind not in (0, 1, 10, 11):
+            raise TypeError("ArdaeCondScoreEngine drives the conditional networks (net.MLPGradCARDAE / net.MLPResCARDAE with a ScoreConfig, "
+                            "net.MLPGradCDAE / net.MLPResCDAE with a DaeConfig); the unconditional ones run in ArdaeScoreEngine")
+        self.plain = kind >= 10
+        if not isinstance(cfg, DaeConfig if self.plain else ScoreConfig):
+            raise TypeError(f"{type(cdae).__name__} takes a {'DaeConfig' if self.plain else 'ScoreConfig'}, not a {type(cfg).__name__}: ScoreConfig "
+                            "(a sigma draw per row) belongs to the AR-DAE networks, DaeConfig (one annealed sigma per step) to the plain DAEs")
+        if int(cfg.nsigma) < 1 or int(batch_size) < 1 or int(sample_size) < 1:
+            raise ValueError(f"nsigma, batch_size and sample_size must be positive (got {cfg.nsigma}, {batch_size}, {sample_size})")
+        if not self.plain and int(sample_size) < 2:
+            raise ValueError("a conditional AR-DAE scales its noise by the unbiased std over the samples: sample_size >= 2")
+        self.cdae, self.cfg, self.std_scale = cdae, cfg, float(std_scale)
+        self.B, self.S, self.nstd = int(batch_size), int(sample_size), int(cfg.nsigma)
+        self.z, self.c = int(cdae.input_dim), int(cdae.context_dim)
+        self.N = self.B * self.S * self.nstd
+        self.dev = cdae._flat.device
+        f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
+        self.ws = f(L.query("ardae_cdae_workspace_floats", cdae._desc, self.B, self.S * self.nstd, 1))
+        self.xbar, self.sigma, self.eps, self.xi = f(self.N, self.z), f(self.N), f(self.N, self.z), f(self.N)
+        self.std_b = f(self.B)
+        self._latent, self._z0, self._ctx = f(self.B, self.S, self.z), torch.zeros(self.B, self.z, device=self.dev), f(self.B, self.c)
+        self.loss = f(1)
+        self.grads = torch.zeros_like(cdae._flat)
+        self.n_grad = cdae._flat.numel() - (1 if cdae._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
+        self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        self.sched = (float(cfg.sigma_max), float(cfg.sigma_min), int(cfg.sigma_annealing)) if self.plain else None
+        self.opt = _FlatOpt(cfg.optimizer, cdae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state, dae=self.sched)
+        self._ladder = CaptureLadder(self.dev, graph)
+        if self.plain:
+            want = self.DRAW_FORM_DEFAULT if draw_form is None else bool(draw_form)
+            self.draw_form = want and bool(L.query("ardae_latent_noise_perturb_draw_ok", self.S, self.nstd, self.z))
+            self.fused_first = self.fused_draw = False
+        else:
+            self.draw_form = False
+            self.fused_draw = L.debug_knob("ARDAE_FUSED_DRAW", "1") != "0" and bool(L.query("ardae_latent_perturb_draw_ok", self.S, self.nstd, self.z))
+            self.fused_first = (self.fused_draw and L.debug_knob("ARDAE_FUSED_A1", "1") != "0"
+                                and bool(L.query("ardae_cdae_perturb_fused_ok", cdae._desc, self.S, self.nstd)))
+        self._score_ws = {}
+        self.step_count = 0
+        self.opt.advance(self.RNG_STRIDE)      # the step state always describes the COMING step
+        self.repack()
+
+    def repack(self):
+        self.cdae._packed = None
+        self.pk = self.cdae._packed_weights()
+
+    _graph = property(lambda self: self._ladder.graph)          # None until the step has been captured
+    use_graph = property(lambda self: self._ladder.on, lambda self, on: setattr(self._ladder, "on", bool(on)))
+
+    def _loss_grads(self):
+        L.call("ardae_cdae_loss_grads", self.cdae._desc, self.cdae._flat, self.pk, self.xbar, self.sigma, self.eps, self._ctx, self.B,
+               self.S * self.nstd, self.ws, self.ws.numel(), self.loss, self.grads, None)
+
+    def _body(self, drawn):
+        """The launches of one update on the static buffers; drawn: the step makes its own draws (else xi / eps hold injected ones)."""
+        d, seed, cfg = self.cdae._desc, rng.get_state()["seed"], self.cfg
+        lat, z0, B, S, nstd, z = self._latent, self._z0, self.B, self.S, self.nstd, self.z
+        if self.plain:             # sigma: the device block's in every form of the step
+            if drawn and self.draw_form:
+                L.call("ardae_latent_noise_perturb_draw", lat, z0, B, S, nstd, z, self.std_scale, 0.0, self.state, seed, 1, 0, self.xbar, self.sigma,
+                       self.eps)
+            else:
+                if drawn:
+                    L.call("ardae_philox_normal_at", self.eps, self.N * z, seed, 1, self.state, 0)
+                L.call("ardae_latent_noise_perturb", lat, z0, self.eps, B, S, nstd, z, self.std_scale, 0.0, self.state, self.xbar, self.sigma)
+            self._loss_grads()
+        elif drawn and self.fused_first:
+            L.call("ardae_cdae_perturb_loss_grads", d, self.cdae._flat, self.pk, lat, z0, self._ctx, B, S, self.std_scale, float(cfg.delta), seed, 0, 1,
+                   self.state, 0, self.xbar, self.sigma, self.eps, self.std_b, self.ws, self.ws.numel(), self.loss, self.grads)
+        elif drawn and self.fused_draw:
+            L.call("ardae_latent_perturb_draw", lat, z0, B, S, z, self.std_scale, float(cfg.delta), seed, 0, 1, self.state, 0, self.xbar, self.sigma,
+                   self.eps, self.std_b)
+            self._loss_grads()
+        else:
+            if drawn:
+                L.call("ardae_philox_normal_at", self.xi, self.N, seed, 0, self.state, 0)
+                L.call("ardae_philox_normal_at", self.eps, self.N * z, seed, 1, self.state, 0)
+            L.call("ardae_latent_perturb_nstd", lat, z0, self.xi, self.eps, B, S, nstd, z, self.std_scale, float(cfg.delta), self.xbar, self.sigma,
+                   self.std_b)
+            self._loss_grads()
+        self.opt.apply(self.grads, True)      # Adam's t and bias corrections come from the device block
+        L.call("ardae_cdae_pack", d, self.cdae._flat, self.pk)
+        self.opt.advance(self.RNG_STRIDE)     # for the NEXT step: Philox base += stride, t += 1
+
+    def step(self, latent, ctx, latent_mean=None, noise=None, sigma=None):
+        """One update on the samples latent [B, S, z] of the B contexts ctx (each sample used with nsigma noise draws)."""
+        if sigma is not None:
+            raise ValueError(f"sigma={sigma!r}: " + (f"this engine computes sigma on the device (DaeConfig(sigma_max={self.cfg.sigma_max}, sigma_min="
+                             f"{self.cfg.sigma_min}, sigma_annealing={self.cfg.sigma_annealing})); a second source is refused" if self.plain else
+                             "the AR-DAE update draws its noise levels; inject them through noise={'sigma', 'eps'}"))
+        check_batch(latent, "step(latent)", self.dev, self.B, self.S * self.z)
+        check_batch(ctx, "step(ctx)", self.dev, self.B, self.c, rows="contexts")
+        if latent_mean is not None:
+            check_batch(latent_mean, "step(latent_mean)", self.dev, self.B, self.z, rows="means")
+        if noise is not None:
+            if not self.plain:
+                check_tensor(noise["sigma"], "step(noise): sigma", self.dev, numel=self.N)
+            check_tensor(noise["eps"], "step(noise): eps", self.dev, numel=self.N * self.z)
+            # into the engine's own buffers: the launches (and stats()) then read what a drawn step would have left there
+            if not self.plain:
+                self.xi.copy_(noise["sigma"].reshape(-1))
+            self.eps.copy_(noise["eps"].reshape(self.N, self.z))
+        # the static buffers the (captured) launches read; a caller that filled input_buffers() passes the same tensors and saves the copies
+        if latent is not self._latent:
+            self._latent.copy_(latent.view(self.B, self.S, self.z))
+        if ctx is not self._ctx:
+            self._ctx.copy_(ctx.view(self.B, self.c))
+        if latent_mean is None:
+            self._z0.zero_()
+        elif latent_mean is not self._z0:
+            self._z0.copy_(latent_mean.view(self.B, self.z))
+        self._ladder.run(lambda: self._body(noise is None), eager=noise is not None)
+        self.step_count += 1
+        self.opt.steps = self.step_count
+        bump_versions(self.cdae)
+
+    def input_buffers(self):
+        """The static (latent [B, S, z], latent_mean [B, z], ctx [B, c]) buffers: a sampler that writes there and passes the same tensors to
+        step() saves the copies."""
+        return self._latent, self._z0, self._ctx
+
+    def score(self, latent, ctx, latent_mean=None):
+        """glogprob(std_scale (latent - latent_mean), ctx, sigma = 0) with the engine's weight image: latent [B', S', z], ctx [B', c] | [B', 1, c],
+        latent_mean [B', z] | [B', 1, z] or None = zeros -> [B', S', z]."""
+        check_tensor(latent, "score(latent)", self.dev, shape=(None, None, self.z))
+        Bq, Sq = latent.size(0), latent.size(1)
+        check_batch(ctx, "score(ctx)", self.dev, Bq, self.c, rows="contexts")
+        if latent_mean is not None:
+            check_batch(latent_mean, "score(latent_mean)", self.dev, Bq, self.z, rows="means")
+        bufs = self._score_ws.get((Bq, Sq))
+        if bufs is None:
+            bufs = self._score_ws[(Bq, Sq)] = (torch.empty(L.query("ardae_cdae_workspace_floats", self.cdae._desc, Bq, Sq, 0), device=self.dev),
+                                               torch.zeros(Bq * Sq, device=self.dev), torch.zeros(Bq, self.z, device=self.dev))
+        ws, sigma0, zeros = bufs
+        u = torch.empty(Bq * Sq, self.z, device=self.dev)
+        L.call("ardae_center_scale", latent.detach(), zeros if latent_mean is None else latent_mean.detach(), Bq, Sq, self.z, self.std_scale, u)
+        out = torch.empty(Bq, Sq, self.z, device=self.dev)
+        L.call("ardae_cdae_score", self.cdae._desc, self.cdae._flat, self.pk, u, None if self.plain else sigma0, ctx.detach(), Bq, Sq, ws, ws.numel(), out)
+        return out
+
+    def stats(self):
+        """Host copy of the last step's loss and (AR kinds) the per-context noise scale delta * mean_d std_S(u) - the loop's cur_mean_std* - or
+        (plain kinds) the finished step's sigma, recomputed on the host from the step count.  The only synchronising call."""
+        if self.plain:
+            sigma = float(np.float32(dae_sigma(*self.sched, self.step_count - 1))) if self.step_count else float("nan")
+            return dict(loss=float(self.loss), sigma=sigma)
+        v = torch.cat([self.loss, self.std_b.mean().reshape(1), self.std_b.max().reshape(1), self.std_b.min().reshape(1)]).tolist()
+        return dict(loss=v[0], std_mean=v[1], std_max=v[2], std_min=v[3])
+
+    # ------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """The network, its optimiser in torch.optim's layout, and the step count, step-state block and RNG state: everything a resumed
+        run needs to continue bit-identically."""
+        return {"cdae": {k: v.clone() for k, v in self.cdae.state_dict().items()},
+                "optimizer": self.opt.state_dict(self.cdae),
+                "engine": {"step_count": self.step_count, "rng_seed": rng.get_state()["seed"], "rng_host_offset": rng.get_state()["offset"],
+                           "step_state": self.state.cpu().clone()}}
+
+    def load_state_dict(self, sd, default_steps=0):
+        """Inverse of state_dict().  Without the "engine" entry (a checkpoint assembled from torch objects) the step count is the optimiser
+        state's (default_steps where that is empty: SGD) and the block is rebuilt for it.  The plain kinds' noise level is recomputed from the
+        step count under THIS engine's schedule, as ArdaeScoreEngine does."""
+        self.cdae.load_state_dict(sd["cdae"])
+        steps = self.opt.load_state_dict(self.cdae, sd["optimizer"], "cDAE checkpoint")
+        eng = sd.get("engine")
+        self.step_count = self.opt.steps = int(eng["step_count"]) if eng is not None else (steps or int(default_steps))
+        if eng is not None:
+            rng.manual_seed(eng["rng_seed"], eng["rng_host_offset"])
+            self.state.copy_(eng["step_state"].to(self.dev))
+        else:
+            rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt.advance(self.RNG_STRIDE))
+        if self.plain and eng is not None:
+            self.state[0] -= self.RNG_STRIDE
+            self.state[1] -= 1
+            self.opt.advance(self.RNG_STRIDE)
+        self._ladder.reset()                    # parameters were rewritten outside of the captured step
+        bump_versions(self.cdae)
         self.repack()

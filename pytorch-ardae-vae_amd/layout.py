@@ -221,6 +221,18 @@ def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):
     return s
 
 
+def cdae_plain_spec(kind, input_dim, context_dim, h_dim, n_layers):
+    """The plain conditional DAE (models/graddae/mlp.py:243-247, models/resdae/mlp.py:203-207): cdae_spec without the sigma column,
+    `layers.0.weight` is [h, 2h] = [W1a | W1c].  ardae_cdae_desc.kind 10 ('grad') / 11 ('res')."""
+    s = _mlp("ctx_encode.", context_dim, h_dim, h_dim, n_layers - 1)
+    s += _mlp("inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)
+    if kind == "grad":
+        return s + _mlp("neglogprob.", 2 * h_dim, h_dim, 1, n_layers)
+    if kind == "res":
+        return s + _mlp("dae.", 2 * h_dim, h_dim, input_dim, n_layers)
+    raise NotImplementedError(kind)
+
+
 def dae_spec(kind, input_dim, h_dim, n_layers):
     """The unconditional AR-DAE (models/graddae/mlp.py:137, models/resdae/mlp.py:111): one MLP on [x_bar | sigma]; `layers.0.weight`
     is [h, d + 1] = [W1x | w1s].  ardae_cdae_desc.kind 2 ('grad') / 3 ('res')."""

@@ -4,6 +4,7 @@
     net.MLPGradCARDAE / net.MLPResCARDAE <- models/graddae/mlp.py:341-483, models/resdae/mlp.py:286-413
     net.MLPGradARDAE / net.MLPResARDAE   <- models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167
     net.MLPGradDAE / net.MLPResDAE       <- models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90
+    net.MLPGradCDAE / net.MLPResCDAE     <- models/graddae/mlp.py:210-339, models/resdae/mlp.py:170-284
     net.MNISTVAE / net.ToyVAE            <- models/vae/mnist.py:99-220, models/vae/toy.py:99-213 (the Gaussian-posterior baselines of vae.py)
     net.MNISTConvVAE                     <- models/vae/conv.py:138-260 (`vae.py --model conv`)
     net.MNISTResConvVAE                  <- models/vae/resconv.py:122-240 (`vae.py --model resconv`)
@@ -197,7 +198,7 @@ class _ScoreNet(FlatParamModule):
             raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
 
     def _build_net(self, first_kind, spec, input_dim, context_dim, h_dim, std, num_hidden_layers, nonlinearity, noise_type):
-        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional, 6 plain DAE); its res sibling is the next."""
+        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional, 6 plain DAE, 10 plain conditional DAE); its res sibling is the next."""
         self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
         self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
         self._desc = L.CdaeDesc(first_kind if self._kind == "grad" else first_kind + 1, input_dim, context_dim, h_dim, num_hidden_layers, L.ACT[nonlinearity])
@@ -258,6 +259,64 @@ class MLPGradCARDAE(ConditionalARDAE):
 
 class MLPResCARDAE(ConditionalARDAE):
     """models/resdae/mlp.py::ConditionalARDAE (`--cdae mlp-res`)."""
+    _kind = "res"
+
+
+class ConditionalDAE(_ScoreNet):
+    """models/graddae/mlp.py:210-339 / models/resdae/mlp.py:170-284: the conditional score network that is not amortised over the noise level -
+    ConditionalARDAE without the sigma input: one noise level per call (`std`, default `self.std`), not an input of the network."""
+
+    def __init__(self, input_dim=2, h_dim=128, context_dim=2, std=0.01, num_hidden_layers=1, nonlinearity="tanh", noise_type="gaussian",
+                 enc_input=True, enc_ctx=True):
+        super().__init__()
+        self._check(noise_type, nonlinearity, None if enc_input and enc_ctx else
+                    "enc_input=enc_ctx=True is the only configuration built (the sibling ConditionalARDAE's)")
+        self.context_dim, self.enc_input, self.enc_ctx = context_dim, enc_input, enc_ctx
+        self._build_net(10, layout.cdae_plain_spec(self._kind, input_dim, context_dim, h_dim, num_hidden_layers), input_dim, context_dim, h_dim,
+                        std, num_hidden_layers, nonlinearity, noise_type)
+
+    def _prep(self, input, context):
+        assert input.dim() == 3      # bsz x ssz x x_dim   (graddae/mlp.py:271)
+        assert context.dim() == 3    # bsz x 1 x ctx_dim   (graddae/mlp.py:272)
+        B, S = input.size(0), input.size(1)
+        self._require_gpu(input, context)
+        return B, S, _f32c(input).view(B * S, self.input_dim), _f32c(context).view(B, self.context_dim)
+
+    def forward(self, input, context, std=None, eps=None):
+        """-> (None, loss) like the reference.  `std`: None (self.std), a Python number, or a tensor that broadcasts to [B*S, 1]
+        (graddae/mlp.py:273,304).  `eps` injects the Gaussian perturbation draw ([B*S, x_dim]); default: the library's Philox stream."""
+        B, S, x, c = self._prep(input, context)
+        N = B * S
+        std = self.std if std is None else std
+        if torch.is_tensor(std):
+            self._require_gpu(std)
+            s = torch.broadcast_to(_f32c(std), (N, 1)).reshape(-1).contiguous()
+        else:
+            s = torch.full((N,), float(std), device=x.device, dtype=torch.float32)
+        if eps is None:
+            eps = rng.normal((N, self.input_dim), x.device)
+        eps = _f32c(eps).view(N, self.input_dim)
+        xbar = torch.empty_like(x)
+        L.call("ardae_dae_perturb", x, s, eps, N, 1, self.input_dim, xbar)      # add_gaussian_noise (graddae/mlp.py:21-23)
+        loss = _ArdaeLossFn.apply(self, xbar, s, eps, c, B, S, *self.parameters())
+        return None, loss
+
+    def glogprob(self, input, context, std=None):
+        """The score at `input` given `context`; `std` is accepted and ignored, as in the reference (graddae/mlp.py:309-339)."""
+        B, S, x, c = self._prep(input, context)
+        ws = self._ws(L.query("ardae_cdae_workspace_floats", self._desc, B, S, 0))
+        out = torch.empty(B * S, self.input_dim, device=x.device)
+        L.call("ardae_cdae_score", self._desc, self._flat, self._packed_weights(), x, None, c, B, S, ws, ws.numel(), out)
+        return out.view(B, S, self.input_dim)
+
+
+class MLPGradCDAE(ConditionalDAE):
+    """models/graddae/mlp.py::ConditionalDAE (exported as MLPGradCDAE, models/__init__.py:12): score = input-gradient of an energy MLP."""
+    _kind = "grad"
+
+
+class MLPResCDAE(ConditionalDAE):
+    """models/resdae/mlp.py::ConditionalDAE (exported as MLPResCDAE, models/__init__.py:7): the MLP's output is the score."""
     _kind = "res"
 
 
