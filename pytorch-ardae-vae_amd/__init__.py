@@ -33,7 +33,8 @@ from .rng import manual_seed  # noqa: F401
 from .modules import (MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVAE, MNISTConvAuxIPVAE, ResConvIPVAE, MNISTResConvAuxIPVAE, MNISTResConvAuxIPVAEClipped, MLPGradCARDAE, MLPResCARDAE, MLPGradARDAE, MLPResARDAE, MLPGradDAE, MLPResDAE, MLPGradCDAE, MLPResCDAE, ARDAE, DAE, ConditionalDAE, Generator, ImplicitPosteriorVAE, ConditionalARDAE,  # noqa: F401
                       normal_energy_func, GaussianVAE, MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE, MNISTResConvAuxVAE)
 from .optim import Adam, RMSprop, Polyak, SWA  # noqa: F401
-from .engine import ArdaeCondScoreEngine, ArdaeEngine, ArdaeScoreEngine, DaeConfig, ScoreConfig, TrainConfig, annealing_func, dae_sigma  # noqa: F401
+from .engine import ArdaeEngine, TrainConfig, annealing_func  # noqa: F401
+from .score_engine import ArdaeCondScoreEngine, ArdaeScoreEngine, DaeConfig, ScoreConfig, dae_sigma  # noqa: F401
 from .fit import ArdaeFitEngine, FitConfig  # noqa: F401
 from .iwae import IwaeEvaluator, plan_chunks  # noqa: F401
 from .diagnostics import PosteriorDiagnostics  # noqa: F401

@@ -8,7 +8,6 @@ buffers are all-reduced (RCCL over xGMI via torch.distributed backend "nccl") be
 import contextlib
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from . import _lib as L
@@ -16,7 +15,7 @@ from . import dist
 from . import rng
 from .iwae import IwaeEvaluator
 from .diagnostics import PosteriorDiagnostics
-from .engine_common import CaptureLadder, _FlatOpt, bump_versions, capture_linear, check_batch, check_tensor, rebuild_step_state  # noqa: F401
+from .engine_common import RNG_STRIDE, CaptureLadder, _FlatOpt, bump_versions, capture_linear, check_batch, check_tensor, rebuild_step_state  # noqa: F401
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
 
@@ -94,7 +93,7 @@ class ArdaeEngine:
     replayed == eager bit for bit, for any world size and any backend (RCCL over xGMI in `bench.py --gpus N`, gloo in the
     rehearsal tests).  `graph=True` makes a refused capture an error; `graph="auto"` falls back to eager launches with a warning."""
 
-    RNG_STRIDE = 16   # Philox offsets reserved per step (draws use base + 0, 1, 2, ...)
+    RNG_STRIDE = RNG_STRIDE
 
     def __init__(self, model, cdae, cfg: TrainConfig, batch_size, process_group=None, graph=True, force_dp=False, dp_comm="auto"):
         model._require_gpu()
@@ -828,432 +827,3 @@ class ArdaeEngine:
         """Host copy of the logged scalars of ivae_ardae.py:756-758,774,837-841 (this is the only synchronising call)."""
         v = torch.cat([self.loss_c, self.losses_m, self.std_b.mean().reshape(1), self.std_b.max().reshape(1), self.std_b.min().reshape(1)]).tolist()
         return dict(cdae_loss=v[0], model_loss=v[1], recon=v[2], prior=v[3], std_mean=v[4], std_max=v[5], std_min=v[6])
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# Unconditional AR-DAE: the score-estimator half of notebooks/ardae_toy.ipynb / ardae_fit.ipynb
-# ---------------------------------------------------------------------------------------------------------------
-@dataclass
-class ScoreConfig:
-    """Constants of the notebooks' AR-DAE update (ardae_toy.ipynb: delta 1, num_sigma 10, lr 5e-3; ardae_fit.ipynb: lr 1e-3)."""
-    delta: float = 1.0            # sigma = delta * randn per row
-    nsigma: int = 10              # noise levels per sample (`num_sigma`): a batch of B samples is B * nsigma rows
-    lr: float = 1e-3
-    optimizer: str = "rmsprop"    # sgd | adam | amsgrad | rmsprop (_FlatOpt).  "adam" is the reference's VENDORED Adam (utils/optim.py:
-    beta1: float = 0.5            # epsilon before the bias correction), not the torch.optim.Adam the notebooks construct; for that one
-    momentum: float = 0.5         # use the module path (MLPGradARDAE + torch.optim.Adam).  rmsprop and sgd coincide with torch's.
-
-
-@dataclass
-class DaeConfig:
-    """Constants of notebooks/dae_toy.ipynb's training cell: one noise level per step, annealed linearly from sigma_max to sigma_min over
-    sigma_annealing steps and computed on the device (ardae_dae_state_advance); torch.optim.Adam(lr=0.005)."""
-    sigma_max: float = 5.0
-    sigma_min: float = 0.05
-    sigma_annealing: int = 4000   # steps of the ramp; 0 or below: the constant sigma_min
-    nsigma: int = 10              # `num_sigma`: a batch of B samples is B * nsigma rows (each with its own eps)
-    lr: float = 5e-3
-    optimizer: str = "adam_torch"  # torch.optim.Adam, the notebook's (_FlatOpt; sgd | adam | amsgrad | rmsprop as for ScoreConfig)
-    beta1: float = 0.9
-    momentum: float = 0.0
-
-    def __post_init__(self):
-        if int(self.sigma_annealing) != self.sigma_annealing:
-            raise ValueError(f"sigma_annealing must be a whole number of steps (got {self.sigma_annealing!r})")
-
-
-def dae_sigma(sigma_max, sigma_min, sigma_annealing, step):
-    """The noise level of 0-based step `step` (the notebook's i_ep), in the notebook's operation order; numpy.float32 of it is what
-    ardae_dae_state_advance writes for t = step + 1."""
-    if sigma_annealing <= 0:
-        return float(sigma_min)
-    perc = min((step + 1) / float(sigma_annealing), 1.0)
-    return sigma_max * (1 - perc) + sigma_min * perc
-
-
-class ArdaeScoreEngine:
-    """One AR-DAE update of an unconditional score network (`net.MLPGradARDAE` / `net.MLPResARDAE`) as ONE captured unit:
-    advance the step state, draw sigma and eps, perturb the broadcast batch, loss and gradients on B * nsigma rows, optimiser,
-    re-pack.  The rules are ArdaeEngine's: `step()` is captured at its third call and replayed afterwards (replayed == eager bit for
-    bit), `noise={'sigma' [B * nsigma], 'eps' [B * nsigma, d]}` runs the same launches eagerly on injected draws, batches are
-    validated before any pointer reaches a kernel, in-step Philox offsets are RNG_STRIDE * step + {0 (sigma), 1 (eps)} - below
-    rng.HOST_STREAM.  One stream, one linear graph; there is no data parallelism here.
-
-    With a plain DAE (`net.MLPGradDAE` / `net.MLPResDAE`) and a `DaeConfig` the same engine runs notebooks/dae_toy.ipynb's update: no
-    sigma draw - the step's one noise level is read from the device block, where `ardae_dae_state_advance` leaves the annealed value -
-    so `noise` is {'eps'} alone, the in-step Philox offset RNG_STRIDE * step + 1 (eps; slot 0 stays unused), and `stats()` reports
-    `loss` and `sigma`.
-
-    A sampler that stays the caller's torch module takes its entropy gradient as `output.backward(engine.score(output.detach()) / B)`;
-    the whole iteration of ardae_fit.ipynb on the device - generator, energy, this update - is `ArdaeFitEngine` (fit.py)."""
-
-    RNG_STRIDE = ArdaeEngine.RNG_STRIDE
-
-    def __init__(self, dae, cfg: ScoreConfig, batch_size, graph=True):
-        dae._require_gpu()
-        kind = int(dae._desc.kind)
-        if kind not in (2, 3, 6, 7):
-            raise TypeError("ArdaeScoreEngine drives the unconditional networks (net.MLPGradARDAE / net.MLPResARDAE with a ScoreConfig, "
-                            "net.MLPGradDAE / net.MLPResDAE with a DaeConfig)")
-        self.plain = kind >= 6
-        if not isinstance(cfg, DaeConfig if self.plain else ScoreConfig):
-            raise TypeError(f"{type(dae).__name__} takes a {'DaeConfig' if self.plain else 'ScoreConfig'}, not a {type(cfg).__name__}: ScoreConfig "
-                            "(a sigma draw per row) belongs to the AR-DAE networks, DaeConfig (one annealed sigma per step) to the plain DAEs")
-        if int(cfg.nsigma) < 1 or int(batch_size) < 1:
-            raise ValueError(f"nsigma and batch_size must be positive (got {cfg.nsigma}, {batch_size})")
-        self.dae, self.cfg = dae, cfg
-        self.B, self.S, self.d = int(batch_size), int(cfg.nsigma), int(dae.input_dim)
-        self.N = self.B * self.S
-        self.dev = dae._flat.device
-        f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
-        self.ws = f(L.query("ardae_cdae_workspace_floats", dae._desc, self.N, 1, 1))
-        self.xbar, self.sigma, self.eps, self.nrm = f(self.N, self.d), f(self.N), f(self.N, self.d), f(self.N)
-        self._zero = torch.zeros(self.N, device=self.dev)
-        self.loss = f(1)
-        self.grads = torch.zeros_like(dae._flat)
-        self.n_grad = dae._flat.numel() - (1 if dae._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
-        self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.sched = (float(cfg.sigma_max), float(cfg.sigma_min), int(cfg.sigma_annealing)) if self.plain else None
-        self.opt = _FlatOpt(cfg.optimizer, dae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state, dae=self.sched)
-        self._ladder = CaptureLadder(self.dev, graph)
-        self.fused_front = (not self.plain and L.debug_knob("ARDAE_FUSED_DAE_FRONT", "1") != "0"       # (the plain DAEs have no fused front end)
-                            and bool(L.query("ardae_dae_perturb_fused_ok", dae._desc, self.S)))
-        self._x = None
-        self._score_ws = {}
-        self.step_count = 0
-        self.opt.advance(self.RNG_STRIDE)      # the step state always describes the COMING step
-        self.repack()
-
-    def repack(self):
-        self.dae._packed = None
-        self.pk = self.dae._packed_weights()
-
-    _graph = property(lambda self: self._ladder.graph)          # None until the step has been captured
-    use_graph = property(lambda self: self._ladder.on, lambda self, on: setattr(self._ladder, "on", bool(on)))
-
-    def _check_batch(self, x, what):
-        check_batch(x, what, self.dev, self.B, self.d)
-
-    def _body(self, x, noise):
-        d, seed = self.dae._desc, rng.get_state()["seed"]
-        if self.plain:             # sigma: the device block's in every form of the step
-            if noise is None:
-                L.call("ardae_philox_normal_at", self.eps, self.N * self.d, seed, 1, self.state, 0)
-            L.call("ardae_dae_noise_perturb", x, self.eps, self.B, self.S, self.d, 0.0, self.state, self.xbar, self.sigma)
-            L.call("ardae_cdae_loss_grads", d, self.dae._flat, self.pk, self.xbar, self.sigma, self.eps, None, self.N, 1, self.ws, self.ws.numel(),
-                   self.loss, self.grads, None)
-        elif noise is None and self.fused_front:
-            L.call("ardae_dae_perturb_loss_grads", d, self.dae._flat, self.pk, x, self.B, self.S, float(self.cfg.delta), seed, 0, 1, self.state, 0,
-                   self.xbar, self.sigma, self.eps, self.ws, self.ws.numel(), self.loss, self.grads)
-        else:
-            if noise is None:
-                L.call("ardae_philox_normal_at", self.nrm, self.N, seed, 0, self.state, 0)
-                L.call("ardae_center_scale", self.nrm, self._zero, self.N, 1, 1, float(self.cfg.delta), self.sigma)     # sigma = delta * n
-                L.call("ardae_philox_normal_at", self.eps, self.N * self.d, seed, 1, self.state, 0)
-                sigma, eps = self.sigma, self.eps
-            else:
-                sigma, eps = noise["sigma"], noise["eps"]
-            L.call("ardae_dae_perturb", x, sigma, eps, self.B, self.S, self.d, self.xbar)
-            L.call("ardae_cdae_loss_grads", d, self.dae._flat, self.pk, self.xbar, sigma, eps, None, self.N, 1, self.ws, self.ws.numel(), self.loss,
-                   self.grads, None)
-        self.opt.apply(self.grads, True)      # Adam's t and bias corrections come from the device block
-        L.call("ardae_cdae_pack", d, self.dae._flat, self.pk)
-        self.opt.advance(self.RNG_STRIDE)     # for the NEXT step: Philox base += stride, t += 1
-
-    def step(self, x, noise=None, sigma=None):
-        """One AR-DAE update on the B samples x [B, d] (each used with nsigma noise levels)."""
-        if sigma is not None:
-            raise ValueError(f"sigma={sigma!r}: " + (f"this engine computes sigma on the device (DaeConfig(sigma_max={self.cfg.sigma_max}, sigma_min="
-                             f"{self.cfg.sigma_min}, sigma_annealing={self.cfg.sigma_annealing})); a second source is refused" if self.plain else
-                             "the AR-DAE update draws its noise levels; inject them through noise={'sigma', 'eps'}"))
-        self._check_batch(x, "step(x)")
-        if noise is not None:
-            if not self.plain:
-                check_tensor(noise["sigma"], "step(noise): sigma", self.dev, numel=self.N)
-            check_tensor(noise["eps"], "step(noise): eps", self.dev, numel=self.N * self.d)
-            # into the engine's own buffers: the launches (and stats()) then read what a drawn step would have left there
-            if not self.plain:
-                self.sigma.copy_(noise["sigma"].reshape(-1))
-            self.eps.copy_(noise["eps"].reshape(self.N, self.d))
-            noise = {"sigma": self.sigma, "eps": self.eps}
-        elif self.use_graph and x is not self._x:
-            x = self.input_buffer().copy_(x.view(self.B, self.d))      # the static batch buffer the captured launches read
-        self._ladder.run(lambda: self._body(x, noise), eager=noise is not None)
-        self._count_step()
-
-    def _count_step(self):
-        """Host-side bookkeeping of one update (`_body` itself only launches: ArdaeFitEngine runs it inside its own captured iteration)."""
-        self.step_count += 1
-        self.opt.steps = self.step_count
-        bump_versions(self.dae)
-
-    def input_buffer(self):
-        """The static batch buffer [B, d]: a sampler that writes its batch there and passes the same tensor to step() saves the copy."""
-        if self._x is None:
-            self._x = torch.empty(self.B, self.d, device=self.dev, dtype=torch.float32)
-        return self._x
-
-    def score(self, x, sigma=None):
-        """glogprob(x, sigma) with the engine's weight image: x [R, d] (any R), sigma [R] / [R, 1] or None = zeros."""
-        check_tensor(x, "score(x)", self.dev, shape=(None, self.d))
-        R = x.size(0)
-        s = torch.zeros(R, device=self.dev) if sigma is None else sigma.detach().to(torch.float32).reshape(-1).contiguous()
-        if s.numel() != R:
-            raise ValueError(f"score(sigma): {s.numel()} entries for {R} rows")
-        ws = self._score_ws.get(R)
-        if ws is None:
-            ws = self._score_ws[R] = torch.empty(L.query("ardae_cdae_workspace_floats", self.dae._desc, R, 1, 0), device=self.dev)
-        out = torch.empty(R, self.d, device=self.dev)
-        L.call("ardae_cdae_score", self.dae._desc, self.dae._flat, self.pk, x.detach(), s, None, R, 1, ws, ws.numel(), out)
-        return out
-
-    def stats(self):
-        """Host copy of the last step's loss and mean |sigma| (the only synchronising call); a plain DAE: its loss and the finished step's
-        sigma, recomputed on the host from the step count (nothing is read back for it)."""
-        if self.plain:
-            sigma = float(np.float32(dae_sigma(*self.sched, self.step_count - 1))) if self.step_count else float("nan")
-            return dict(loss=float(self.loss), sigma=sigma)
-        v = torch.cat([self.loss, self.sigma.abs().mean().reshape(1)]).tolist()
-        return dict(loss=v[0], sigma_abs_mean=v[1])
-
-    # ------------------------------------------------------------------------------------------------------------
-    def state_dict(self):
-        """The network, its optimiser in torch.optim's layout, and the step count, step-state block and RNG state: everything a resumed
-        run needs to continue bit-identically."""
-        return {"dae": {k: v.clone() for k, v in self.dae.state_dict().items()},
-                "optimizer": self.opt.state_dict(self.dae),
-                "engine": {"step_count": self.step_count, "rng_seed": rng.get_state()["seed"], "rng_host_offset": rng.get_state()["offset"],
-                           "step_state": self.state.cpu().clone()}}
-
-    def load_state_dict(self, sd, default_steps=0):
-        """Inverse of state_dict().  Without the "engine" entry (a checkpoint assembled from torch objects) the step count is the optimiser
-        state's (default_steps where that is empty: SGD) and the block is rebuilt for it: the run continues with Philox offsets it has not used."""
-        self.dae.load_state_dict(sd["dae"])
-        steps = self.opt.load_state_dict(self.dae, sd["optimizer"], "AR-DAE checkpoint")
-        eng = sd.get("engine")
-        self.step_count = self.opt.steps = int(eng["step_count"]) if eng is not None else (steps or int(default_steps))
-        if eng is not None:
-            rng.manual_seed(eng["rng_seed"], eng["rng_host_offset"])
-            self.state.copy_(eng["step_state"].to(self.dev))
-        else:
-            rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt.advance(self.RNG_STRIDE))
-        if self.plain and eng is not None:
-            # bytes 24..27 recomputed from t (ArdaeEngine._refresh_train_state): step the block back by one and advance it again, so that a
-            # file written under another schedule resumes at THIS engine's sigma
-            self.state[0] -= self.RNG_STRIDE
-            self.state[1] -= 1
-            self.opt.advance(self.RNG_STRIDE)
-        self._ladder.reset()                    # parameters were rewritten outside of the captured step
-        bump_versions(self.dae)
-        self.repack()
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# Conditional score networks outside the VAE loop: the cDAE update of ivae_ardae.py:743-779 on the caller's samples
-# ---------------------------------------------------------------------------------------------------------------
-class ArdaeCondScoreEngine:
-    """One update of a CONDITIONAL score network on samples of the caller's own amortised sampler (ivae_ardae.py:752-779), as ONE captured
-    unit: centre and scale the samples, perturb them, loss and gradients on B * S * nsigma rows, optimiser, re-pack, advance the step
-    state.  `step(latent [B, S, z], ctx [B, c] | [B, 1, c], latent_mean=None ([B, z] | [B, 1, z]; None: zeros), noise=None)`;
-    `cfg.nsigma` plays the role of --train-nstd-cdae.  The rules are ArdaeScoreEngine's: eager twice, captured at the third call, replayed
-    afterwards (replayed == eager bit for bit), injected noise runs the same launches eagerly, batches are validated before any pointer
-    reaches a kernel.  One stream, one linear graph; there is no data parallelism here.
-
-    A conditional AR-DAE (`net.MLPGradCARDAE` / `net.MLPResCARDAE`) takes a `ScoreConfig`: the launches and selection rules of
-    ArdaeEngine's cDAE phase behind its sampler - `ardae_cdae_perturb_loss_grads` where the shape allows, else `ardae_latent_perturb_draw`,
-    else two draws and `ardae_latent_perturb_nstd` - with sigma = delta * mean_d std_S(u) * xi; `noise={'sigma': xi [N], 'eps': [N, z]}`;
-    in-step Philox offsets RNG_STRIDE * step + {0 (xi), 1 (eps)}; `stats()` reports `loss` and `std_mean / std_max / std_min`.
-
-    A plain conditional DAE (`net.MLPGradCDAE` / `net.MLPResCDAE`) takes a `DaeConfig`: one noise level per step, read from the device
-    block where `ardae_dae_state_advance` leaves the annealed value, so the replay runs through the ramp; the launches are
-    `ardae_latent_noise_perturb_draw` (`draw_form=False`, or injected eps: `ardae_philox_normal_at` and `ardae_latent_noise_perturb`, the same
-    bits) and `ardae_cdae_loss_grads`; `noise={'eps'}` alone, offset RNG_STRIDE * step + 1; `stats()` reports `loss` and `sigma`.
-
-    `score(latent, ctx, latent_mean=None)` is glogprob(std_scale (latent - mean), ctx, sigma = 0) with the engine's weight image, for any
-    batch and sample size: a sampler that stays the caller's torch module takes its entropy gradient as
-    `(std_scale * (latent - mean)).backward(beta * engine.score(latent.detach(), ctx, mean.detach()) / (B * S))` (ivae_ardae.py:826-834)."""
-
-    RNG_STRIDE = ArdaeEngine.RNG_STRIDE
-    DRAW_FORM_DEFAULT = True       # plain kinds: ardae_latent_noise_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
-
-    def __init__(self, cdae, cfg, batch_size, sample_size, std_scale=1.0, graph=True, draw_form=None):
-        cdae._require_gpu()
-        kind = int(cdae._desc.kind)
-        if kind not in (0, 1, 10, 11):
-            raise TypeError("ArdaeCondScoreEngine drives the conditional networks (net.MLPGradCARDAE / net.MLPResCARDAE with a ScoreConfig, "
-                            "net.MLPGradCDAE / net.MLPResCDAE with a DaeConfig); the unconditional ones run in ArdaeScoreEngine")
-        self.plain = kind >= 10
-        if not isinstance(cfg, DaeConfig if self.plain else ScoreConfig):
-            raise TypeError(f"{type(cdae).__name__} takes a {'DaeConfig' if self.plain else 'ScoreConfig'}, not a {type(cfg).__name__}: ScoreConfig "
-                            "(a sigma draw per row) belongs to the AR-DAE networks, DaeConfig (one annealed sigma per step) to the plain DAEs")
-        if int(cfg.nsigma) < 1 or int(batch_size) < 1 or int(sample_size) < 1:
-            raise ValueError(f"nsigma, batch_size and sample_size must be positive (got {cfg.nsigma}, {batch_size}, {sample_size})")
-        if not self.plain and int(sample_size) < 2:
-            raise ValueError("a conditional AR-DAE scales its noise by the unbiased std over the samples: sample_size >= 2")
-        self.cdae, self.cfg, self.std_scale = cdae, cfg, float(std_scale)
-        self.B, self.S, self.nstd = int(batch_size), int(sample_size), int(cfg.nsigma)
-        self.z, self.c = int(cdae.input_dim), int(cdae.context_dim)
-        self.N = self.B * self.S * self.nstd
-        self.dev = cdae._flat.device
-        f = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
-        self.ws = f(L.query("ardae_cdae_workspace_floats", cdae._desc, self.B, self.S * self.nstd, 1))
-        self.xbar, self.sigma, self.eps, self.xi = f(self.N, self.z), f(self.N), f(self.N, self.z), f(self.N)
-        self.std_b = f(self.B)
-        self._latent, self._z0, self._ctx = f(self.B, self.S, self.z), torch.zeros(self.B, self.z, device=self.dev), f(self.B, self.c)
-        self.loss = f(1)
-        self.grads = torch.zeros_like(cdae._flat)
-        self.n_grad = cdae._flat.numel() - (1 if cdae._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
-        self.state = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.sched = (float(cfg.sigma_max), float(cfg.sigma_min), int(cfg.sigma_annealing)) if self.plain else None
-        self.opt = _FlatOpt(cfg.optimizer, cdae._flat, self.n_grad, cfg.lr, cfg.beta1, cfg.momentum, state=self.state, dae=self.sched)
-        self._ladder = CaptureLadder(self.dev, graph)
-        if self.plain:
-            want = self.DRAW_FORM_DEFAULT if draw_form is None else bool(draw_form)
-            self.draw_form = want and bool(L.query("ardae_latent_noise_perturb_draw_ok", self.S, self.nstd, self.z))
-            self.fused_first = self.fused_draw = False
-        else:
-            self.draw_form = False
-            self.fused_draw = L.debug_knob("ARDAE_FUSED_DRAW", "1") != "0" and bool(L.query("ardae_latent_perturb_draw_ok", self.S, self.nstd, self.z))
-            self.fused_first = (self.fused_draw and L.debug_knob("ARDAE_FUSED_A1", "1") != "0"
-                                and bool(L.query("ardae_cdae_perturb_fused_ok", cdae._desc, self.S, self.nstd)))
-        self._score_ws = {}
-        self.step_count = 0
-        self.opt.advance(self.RNG_STRIDE)      # the step state always describes the COMING step
-        self.repack()
-
-    def repack(self):
-        self.cdae._packed = None
-        self.pk = self.cdae._packed_weights()
-
-    _graph = property(lambda self: self._ladder.graph)          # None until the step has been captured
-    use_graph = property(lambda self: self._ladder.on, lambda self, on: setattr(self._ladder, "on", bool(on)))
-
-    def _loss_grads(self):
-        L.call("ardae_cdae_loss_grads", self.cdae._desc, self.cdae._flat, self.pk, self.xbar, self.sigma, self.eps, self._ctx, self.B,
-               self.S * self.nstd, self.ws, self.ws.numel(), self.loss, self.grads, None)
-
-    def _body(self, drawn):
-        """The launches of one update on the static buffers; drawn: the step makes its own draws (else xi / eps hold injected ones)."""
-        d, seed, cfg = self.cdae._desc, rng.get_state()["seed"], self.cfg
-        lat, z0, B, S, nstd, z = self._latent, self._z0, self.B, self.S, self.nstd, self.z
-        if self.plain:             # sigma: the device block's in every form of the step
-            if drawn and self.draw_form:
-                L.call("ardae_latent_noise_perturb_draw", lat, z0, B, S, nstd, z, self.std_scale, 0.0, self.state, seed, 1, 0, self.xbar, self.sigma,
-                       self.eps)
-            else:
-                if drawn:
-                    L.call("ardae_philox_normal_at", self.eps, self.N * z, seed, 1, self.state, 0)
-                L.call("ardae_latent_noise_perturb", lat, z0, self.eps, B, S, nstd, z, self.std_scale, 0.0, self.state, self.xbar, self.sigma)
-            self._loss_grads()
-        elif drawn and self.fused_first:
-            L.call("ardae_cdae_perturb_loss_grads", d, self.cdae._flat, self.pk, lat, z0, self._ctx, B, S, self.std_scale, float(cfg.delta), seed, 0, 1,
-                   self.state, 0, self.xbar, self.sigma, self.eps, self.std_b, self.ws, self.ws.numel(), self.loss, self.grads)
-        elif drawn and self.fused_draw:
-            L.call("ardae_latent_perturb_draw", lat, z0, B, S, z, self.std_scale, float(cfg.delta), seed, 0, 1, self.state, 0, self.xbar, self.sigma,
-                   self.eps, self.std_b)
-            self._loss_grads()
-        else:
-            if drawn:
-                L.call("ardae_philox_normal_at", self.xi, self.N, seed, 0, self.state, 0)
-                L.call("ardae_philox_normal_at", self.eps, self.N * z, seed, 1, self.state, 0)
-            L.call("ardae_latent_perturb_nstd", lat, z0, self.xi, self.eps, B, S, nstd, z, self.std_scale, float(cfg.delta), self.xbar, self.sigma,
-                   self.std_b)
-            self._loss_grads()
-        self.opt.apply(self.grads, True)      # Adam's t and bias corrections come from the device block
-        L.call("ardae_cdae_pack", d, self.cdae._flat, self.pk)
-        self.opt.advance(self.RNG_STRIDE)     # for the NEXT step: Philox base += stride, t += 1
-
-    def step(self, latent, ctx, latent_mean=None, noise=None, sigma=None):
-        """One update on the samples latent [B, S, z] of the B contexts ctx (each sample used with nsigma noise draws)."""
-        if sigma is not None:
-            raise ValueError(f"sigma={sigma!r}: " + (f"this engine computes sigma on the device (DaeConfig(sigma_max={self.cfg.sigma_max}, sigma_min="
-                             f"{self.cfg.sigma_min}, sigma_annealing={self.cfg.sigma_annealing})); a second source is refused" if self.plain else
-                             "the AR-DAE update draws its noise levels; inject them through noise={'sigma', 'eps'}"))
-        check_batch(latent, "step(latent)", self.dev, self.B, self.S * self.z)
-        check_batch(ctx, "step(ctx)", self.dev, self.B, self.c, rows="contexts")
-        if latent_mean is not None:
-            check_batch(latent_mean, "step(latent_mean)", self.dev, self.B, self.z, rows="means")
-        if noise is not None:
-            if not self.plain:
-                check_tensor(noise["sigma"], "step(noise): sigma", self.dev, numel=self.N)
-            check_tensor(noise["eps"], "step(noise): eps", self.dev, numel=self.N * self.z)
-            # into the engine's own buffers: the launches (and stats()) then read what a drawn step would have left there
-            if not self.plain:
-                self.xi.copy_(noise["sigma"].reshape(-1))
-            self.eps.copy_(noise["eps"].reshape(self.N, self.z))
-        # the static buffers the (captured) launches read; a caller that filled input_buffers() passes the same tensors and saves the copies
-        if latent is not self._latent:
-            self._latent.copy_(latent.view(self.B, self.S, self.z))
-        if ctx is not self._ctx:
-            self._ctx.copy_(ctx.view(self.B, self.c))
-        if latent_mean is None:
-            self._z0.zero_()
-        elif latent_mean is not self._z0:
-            self._z0.copy_(latent_mean.view(self.B, self.z))
-        self._ladder.run(lambda: self._body(noise is None), eager=noise is not None)
-        self.step_count += 1
-        self.opt.steps = self.step_count
-        bump_versions(self.cdae)
-
-    def input_buffers(self):
-        """The static (latent [B, S, z], latent_mean [B, z], ctx [B, c]) buffers: a sampler that writes there and passes the same tensors to
-        step() saves the copies."""
-        return self._latent, self._z0, self._ctx
-
-    def score(self, latent, ctx, latent_mean=None):
-        """glogprob(std_scale (latent - latent_mean), ctx, sigma = 0) with the engine's weight image: latent [B', S', z], ctx [B', c] | [B', 1, c],
-        latent_mean [B', z] | [B', 1, z] or None = zeros -> [B', S', z]."""
-        check_tensor(latent, "score(latent)", self.dev, shape=(None, None, self.z))
-        Bq, Sq = latent.size(0), latent.size(1)
-        check_batch(ctx, "score(ctx)", self.dev, Bq, self.c, rows="contexts")
-        if latent_mean is not None:
-            check_batch(latent_mean, "score(latent_mean)", self.dev, Bq, self.z, rows="means")
-        bufs = self._score_ws.get((Bq, Sq))
-        if bufs is None:
-            bufs = self._score_ws[(Bq, Sq)] = (torch.empty(L.query("ardae_cdae_workspace_floats", self.cdae._desc, Bq, Sq, 0), device=self.dev),
-                                               torch.zeros(Bq * Sq, device=self.dev), torch.zeros(Bq, self.z, device=self.dev))
-        ws, sigma0, zeros = bufs
-        u = torch.empty(Bq * Sq, self.z, device=self.dev)
-        L.call("ardae_center_scale", latent.detach(), zeros if latent_mean is None else latent_mean.detach(), Bq, Sq, self.z, self.std_scale, u)
-        out = torch.empty(Bq, Sq, self.z, device=self.dev)
-        L.call("ardae_cdae_score", self.cdae._desc, self.cdae._flat, self.pk, u, None if self.plain else sigma0, ctx.detach(), Bq, Sq, ws, ws.numel(), out)
-        return out
-
-    def stats(self):
-        """Host copy of the last step's loss and (AR kinds) the per-context noise scale delta * mean_d std_S(u) - the loop's cur_mean_std* - or
-        (plain kinds) the finished step's sigma, recomputed on the host from the step count.  The only synchronising call."""
-        if self.plain:
-            sigma = float(np.float32(dae_sigma(*self.sched, self.step_count - 1))) if self.step_count else float("nan")
-            return dict(loss=float(self.loss), sigma=sigma)
-        v = torch.cat([self.loss, self.std_b.mean().reshape(1), self.std_b.max().reshape(1), self.std_b.min().reshape(1)]).tolist()
-        return dict(loss=v[0], std_mean=v[1], std_max=v[2], std_min=v[3])
-
-    # ------------------------------------------------------------------------------------------------------------
-    def state_dict(self):
-        """The network, its optimiser in torch.optim's layout, and the step count, step-state block and RNG state: everything a resumed
-        run needs to continue bit-identically."""
-        return {"cdae": {k: v.clone() for k, v in self.cdae.state_dict().items()},
-                "optimizer": self.opt.state_dict(self.cdae),
-                "engine": {"step_count": self.step_count, "rng_seed": rng.get_state()["seed"], "rng_host_offset": rng.get_state()["offset"],
-                           "step_state": self.state.cpu().clone()}}
-
-    def load_state_dict(self, sd, default_steps=0):
-        """Inverse of state_dict().  Without the "engine" entry (a checkpoint assembled from torch objects) the step count is the optimiser
-        state's (default_steps where that is empty: SGD) and the block is rebuilt for it.  The plain kinds' noise level is recomputed from the
-        step count under THIS engine's schedule, as ArdaeScoreEngine does."""
-        self.cdae.load_state_dict(sd["cdae"])
-        steps = self.opt.load_state_dict(self.cdae, sd["optimizer"], "cDAE checkpoint")
-        eng = sd.get("engine")
-        self.step_count = self.opt.steps = int(eng["step_count"]) if eng is not None else (steps or int(default_steps))
-        if eng is not None:
-            rng.manual_seed(eng["rng_seed"], eng["rng_host_offset"])
-            self.state.copy_(eng["step_state"].to(self.dev))
-        else:
-            rebuild_step_state(self.state, self.step_count, self.RNG_STRIDE, lambda: self.opt.advance(self.RNG_STRIDE))
-        if self.plain and eng is not None:
-            self.state[0] -= self.RNG_STRIDE
-            self.state[1] -= 1
-            self.opt.advance(self.RNG_STRIDE)
-        self._ladder.reset()                    # parameters were rewritten outside of the captured step
-        bump_versions(self.cdae)
-        self.repack()

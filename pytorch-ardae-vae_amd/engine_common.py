@@ -1,7 +1,10 @@
-"""Host logic the three engines (engine.py, fit.py) share: argument validation, graph capture, the flat optimiser and its checkpoint."""
+"""Host logic the engines (engine.py, score_engine.py, fit.py, vae.py) share: the Philox stride of a step, argument validation, graph capture,
+the flat optimiser and its checkpoint."""
 import torch
 
 from . import _lib as L
+
+RNG_STRIDE = 16   # Philox offsets reserved per step (draws use base + 0, 1, 2, ...)
 
 
 # ---- validation: nothing unchecked reaches a kernel pointer ---------------------------------------------------------------------------

@@ -13,9 +13,10 @@ import torch
 from . import _lib as L
 from . import energy as E
 from . import rng
-from .engine import ArdaeScoreEngine, ScoreConfig, annealing_func
-from .engine_common import CaptureLadder, bump_versions, check_tensor, rebuild_step_state
+from .engine import annealing_func
+from .engine_common import RNG_STRIDE, CaptureLadder, bump_versions, check_tensor, rebuild_step_state
 from .modules import Generator
+from .score_engine import ArdaeScoreEngine, ScoreConfig
 
 FIT_STATE_WORDS = L.CONSTANTS["ARDAE_FIT_STATE_BYTES"] // 8          # the block as int64 words; floats 8 .. 11 are its tail
 _TAIL = L.CONSTANTS["ARDAE_STEP_STATE_BYTES"] // 4
@@ -45,8 +46,8 @@ class FitConfig:
 
     def __post_init__(self):
         E.kind_of(self.energy)
-        if not 1 <= int(self.num_dae_updates) < ArdaeFitEngine.RNG_STRIDE:
-            raise ValueError(f"num_dae_updates must be in 1 .. {ArdaeFitEngine.RNG_STRIDE - 1} (one Philox offset per generator sample of an "
+        if not 1 <= int(self.num_dae_updates) < RNG_STRIDE:
+            raise ValueError(f"num_dae_updates must be in 1 .. {RNG_STRIDE - 1} (one Philox offset per generator sample of an "
                              f"iteration), got {self.num_dae_updates}")
         if int(self.nsigma) < 1:
             raise ValueError(f"nsigma must be positive, got {self.nsigma}")
@@ -77,7 +78,7 @@ class ArdaeFitEngine:
     Philox offsets: the generator's sample u of iteration i (0-based) is the draw Z_STREAM + RNG_STRIDE (i + 1) + u; the embedded AR-DAE
     update k (1-based) uses RNG_STRIDE k + {0, 1} as in ArdaeScoreEngine; host-side draws (`sample`, net.rng) have the top bit set."""
 
-    RNG_STRIDE = ArdaeScoreEngine.RNG_STRIDE
+    RNG_STRIDE = RNG_STRIDE
     Z_STREAM = 1 << 62
 
     def __init__(self, generator, dae, cfg: FitConfig, batch_size, graph=True):
@@ -161,12 +162,10 @@ class ArdaeFitEngine:
         sc, c = self.score, self.cfg
         for u in range(self.U):
             self._sample_into_x(u, None if noise is None else noise["z"][u])
-            if noise is None:
-                sc._body(self.x, None)
-            else:           # into the score engine's own buffers, as its step(noise=...) does
+            if noise is not None:           # into the score engine's own buffers, as its step(noise=...) does
                 sc.sigma.copy_(noise["sigma"][u].reshape(-1))
                 sc.eps.copy_(noise["eps"][u].reshape(sc.N, self.d))
-                sc._body(self.x, {"sigma": sc.sigma, "eps": sc.eps})
+            sc._body(self.x, noise is None)
         self._sample_into_x(self.U, None if noise is None else noise["z"][self.U])
         L.call("ardae_cdae_score", self.dae._desc, self.dae._flat, sc.pk, self.x, self._zero, None, self.B, 1, self.ws_score, self.ws_score.numel(), self.sc)
         L.call("ardae_energy_seed", self.kind, self.x, self.sc, self.B, self.d, float(c.energy_mu), float(c.energy_logvar), 0.0, self.state, self.seed,

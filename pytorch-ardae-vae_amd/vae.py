@@ -18,8 +18,8 @@ import torch
 
 from . import _lib as L
 from . import rng
-from .engine import ArdaeEngine, annealing_func
-from .engine_common import CaptureLadder, _FlatOpt, bump_versions, check_batch, check_tensor, rebuild_step_state
+from .engine import annealing_func
+from .engine_common import RNG_STRIDE, CaptureLadder, _FlatOpt, bump_versions, check_batch, check_tensor, rebuild_step_state
 from .iwae import _check, plan_chunks
 from .modules import GAUSSIAN_DECODERS, GaussianVAE, _AuxGaussianVAE
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
@@ -247,7 +247,7 @@ class VaeEngine:
     device block (`ardae_train_state_advance`, on the zero-based i_ep like vae.py:394-397) and both passes read it there, so the replay
     runs through the ramp.  There is no data parallelism: the batch is 128 rows and there is nothing to shard."""
 
-    RNG_STRIDE = ArdaeEngine.RNG_STRIDE
+    RNG_STRIDE = RNG_STRIDE
 
     def __init__(self, model, cfg: VaeConfig, batch_size, graph=True):
         if not isinstance(model, GaussianVAE):

@@ -1,67 +1,20 @@
 """Unconditional AR-DAE score networks (ardae_cdae_desc.kind 2 / 3): layout, argument validation, module surface, and the float64
-restatement of the two networks that the GPU tests lean on - pinned here to the reference's fp64 fixtures.  No GPU needed."""
+restatement of the two networks that the GPU tests lean on (tests/score_restate.py) - pinned here to the reference's fp64 fixtures.  No GPU needed."""
 import ctypes
-import glob
-import os
 
-import numpy as np
 import pytest
 import torch
 
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
+from ardae_amd.engine_common import _FlatOpt
+from score_restate import ARDAE, load, loss_and_grads, rel, score, state_dict_of
 
-KIND_ID = {"grad": 2, "res": 3}
+KIND_ID = ARDAE.kind_id
+fixtures = ARDAE.fixtures
 # parameter counts of the reference classes, (d, h, L) -> (grad, res)
 REFERENCE_COUNTS = {(2, 256, 3): (132865, 133122), (32, 256, 3): (140545, 148512), (2, 64, 3): (8641, 8706), (3, 100, 2): (10701, 10903)}
-
-
-def fixtures(golden_dir, kind=None):
-    names = sorted(glob.glob(os.path.join(golden_dir, f"ardae_uncond_{kind or '*'}_n*.npz")))
-    assert len(names) == (5 if kind else 10)
-    return names
-
-
-def load(path):
-    return dict(np.load(path))
-
-
-def state_dict_of(fx):
-    return {k[3:]: torch.tensor(v) for k, v in fx.items() if k.startswith("sd/")}
-
-
-# ---- the test-side oracle: the two networks restated (models/layers.py:477-515 MLP on [x_bar | sigma]) ----------------------------
-ACTS = {"relu": torch.relu, "softplus": torch.nn.functional.softplus, "elu": torch.nn.functional.elu, "tanh": torch.tanh,
-        "leaky_relu": lambda t: torch.nn.functional.leaky_relu(t, 0.2), "swish": lambda t: t * torch.sigmoid(t)}
-
-
-def mlp(p, prefix, hdn, act):
-    n = len([k for k in p if k.startswith(prefix + "layers.") and k.endswith("weight")])
-    for i in range(n):
-        hdn = ACTS[act](hdn @ p[f"{prefix}layers.{i}.weight"].t() + p[f"{prefix}layers.{i}.bias"])
-    return hdn @ p[prefix + "fc.weight"].t() + p[prefix + "fc.bias"]
-
-
-def score(kind, p, act, x, std, create_graph=False):
-    if kind == "res":
-        return mlp(p, "main.", torch.cat([x, std], 1), act)
-    x = x if x.requires_grad else x.clone().requires_grad_(True)
-    logprob = -mlp(p, "neglogprob.", torch.cat([x, std], 1), act).sum()
-    return torch.autograd.grad(logprob, x, create_graph=create_graph)[0]
-
-
-def loss_and_grads(kind, p, act, x, std, eps):
-    """-> loss, {name: grad or None}, with p's tensors as leaves"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    xbar = (x + std * eps).requires_grad_(True)
-    loss = torch.nn.functional.mse_loss(std * score(kind, p, act, xbar, std, create_graph=True), -eps)
-    return loss.detach(), dict(zip(p, torch.autograd.grad(loss, list(p.values()), allow_unused=True)))
-
-
-def rel(a, b):
-    a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
-    return float((a - b).norm() / (b.norm() + 1e-300))
 
 
 # ---- 1. layout ---------------------------------------------------------------------------------------------------------------------
@@ -172,7 +125,7 @@ def test_load_state_dict_keeps_flat_views(golden_dir):
 
 def test_score_engine_refuses_other_networks_and_bad_batches():
     import types
-    from ardae_amd.engine import ArdaeScoreEngine
+    ArdaeScoreEngine = net.ArdaeScoreEngine
     eng = types.SimpleNamespace(B=4, d=2, dev=torch.device("cuda", 0))
     check = lambda x: ArdaeScoreEngine._check_batch(eng, x, "step(x)")
     with pytest.raises(ValueError, match="on cuda:0"):
@@ -197,7 +150,7 @@ def test_restatement_reproduces_the_fp64_fixtures(golden_dir):
         kind, act = str(fx["kind"]), str(fx["act"])
         p = {k: v.double() for k, v in state_dict_of(fx).items()}
         x, std, eps = (torch.tensor(fx[k]).double() for k in ("x", "std", "eps"))
-        loss, grads = loss_and_grads(kind, p, act, x, std, eps)
+        loss, grads = loss_and_grads(kind, p, act, x, std, eps, True)
         assert abs(float(loss) - float(fx["loss64"])) <= 1e-12 * abs(float(fx["loss64"])), path
         for n, g in grads.items():
             if f"g64/{n}/none" in fx:
@@ -235,7 +188,6 @@ def test_param_views_alias_the_parameters_and_name_the_tensor_without_gradient()
 
 
 def _flat_opt(kind, seed=0):
-    from ardae_amd.engine import _FlatOpt
     torch.manual_seed(seed)
     m = net.MLPGradARDAE(input_dim=3, h_dim=16, num_hidden_layers=2, nonlinearity="elu")
     return m, _FlatOpt(kind, m.flat_params(), m.flat_params().numel() - 1, 1e-3, 0.5, 0.5)        # construction launches nothing

@@ -13,6 +13,7 @@ import torch
 import ardae_amd
 from ardae_amd import _lib as L
 from oracle import ardae_oracle as O
+from score_gpu_checks import split_flat
 
 pytestmark = pytest.mark.gpu
 
@@ -60,15 +61,6 @@ class CdaeHarness:
                                      L.ptr(sigma), L.ptr(ctx), B, S, L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()))
         torch.cuda.synchronize()
         return out.cpu()
-
-
-def split_flat(v, spec):
-    out, off = {}, 0
-    for n, shp in spec:
-        k = int(np.prod(shp))
-        out[n] = v[off:off + k].view(*shp)
-        off += k
-    return out
 
 
 def rel_l2(a, b):

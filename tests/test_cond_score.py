@@ -1,8 +1,7 @@
 """Plain conditional DAE score networks (ardae_cdae_desc.kind 10 / 11) and the conditional score engine: layout, argument validation, module
-and engine surface, and the float64 restatement of the two networks that the GPU tests lean on - pinned here to the reference's fp64
+and engine surface, and the float64 restatement of the two networks that the GPU tests lean on (tests/score_restate.py) - pinned here to the reference's fp64
 fixtures.  No GPU needed."""
 import ctypes
-import glob
 import math
 import os
 
@@ -12,10 +11,10 @@ import torch
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
-from test_ardae_uncond import ACTS, load, mlp, rel, state_dict_of
+from score_restate import CDAE, dims, inputs_of, load, loss_and_grads, rel, score, state_dict_of, std_of
 
-KIND_ID = {"grad": 10, "res": 11}
-CLS = {"grad": "MLPGradCDAE", "res": "MLPResCDAE"}
+KIND_ID = CDAE.kind_id
+fixtures = CDAE.fixtures
 # (kind, (d, c, h, L)) -> parameter floats, packed floats, workspace floats at (B, S) = (4, 8) without / with gradients; recorded like DAE_SIZES
 # of test_abi.py (these kinds share the layout, workspace and gradient-list code of kinds 0 / 1: what they do NOT take of it is pinned here)
 CDAE_PLAIN_SIZES = [("grad", (2, 2, 64, 3), 33665, 70656, (25856, 85824)), ("grad", (3, 5, 100, 2), 51501, 141824, (27328, 107264)),
@@ -24,52 +23,9 @@ CDAE_PLAIN_SIZES = [("grad", (2, 2, 64, 3), 33665, 70656, (25856, 85824)), ("gra
                     ("res", (32, 32, 256, 3), 551200, 1097728, (104576, 761280)), ("res", (2, 2, 64, 1), 8770, 24064, (8960, 26880))]
 
 
-def fixtures(golden_dir, kind=None):
-    names = sorted(glob.glob(os.path.join(golden_dir, f"cdae_plain_{kind or '*'}_b*.npz")))
-    assert len(names) == (5 if kind else 10)
-    return names
-
-
-def dims(fx):
-    B, S, d, c, h, nl = (int(v) for v in fx["shape"])
-    return B, S, d, c, h, nl
-
-
 def build(fx, **kw):
     _, _, d, c, h, nl = dims(fx)
-    return getattr(net, CLS[str(fx["kind"])])(input_dim=d, context_dim=c, h_dim=h, num_hidden_layers=nl, nonlinearity=str(fx["act"]), **kw)
-
-
-# ---- the test-side oracle: ConditionalDAE restated (models/graddae/mlp.py:243-247,269-339: two MLPs with an activated output, an MLP on their
-# concatenation; the context row of image b serves its S samples) -------------------------------------------------------------------------
-def score(kind, p, act, x, ctx, S, create_graph=False, sigma=None):
-    """x [B*S, d], ctx [B, c] -> the score [B*S, d].  sigma [B*S, 1]: the AR-DAE sibling (kinds 0 / 1), whose last MLP also reads the noise level."""
-    x = x if (kind == "res" or x.requires_grad) else x.clone().requires_grad_(True)
-    enc_c = ACTS[act](mlp(p, "ctx_encode.", ctx, act)).repeat_interleave(S, 0)
-    enc_x = ACTS[act](mlp(p, "inp_encode.", x, act))
-    hdn = torch.cat([enc_x, enc_c] + ([] if sigma is None else [sigma]), 1)
-    if kind == "res":
-        return mlp(p, "dae.", hdn, act)
-    logprob = -mlp(p, "neglogprob.", hdn, act).sum()
-    return torch.autograd.grad(logprob, x, create_graph=create_graph)[0]
-
-
-def loss_and_grads(kind, p, act, x, ctx, S, std, eps):
-    """-> loss, {name: grad or None}, with p's tensors as leaves; std: a number or a tensor that broadcasts against [B*S, d]"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    xbar = (x + std * eps).requires_grad_(True)
-    loss = torch.nn.functional.mse_loss(std * score(kind, p, act, xbar, ctx, S, create_graph=True), -eps)
-    return loss.detach(), dict(zip(p, torch.autograd.grad(loss, list(p.values()), allow_unused=True)))
-
-
-def std_of(fx, dtype=torch.float32):
-    """The fixture's noise level as the reference took it: a Python float, or a [B*S, 1] tensor."""
-    return float(fx["std"]) if fx["std"].ndim == 0 else torch.tensor(fx["std"]).to(dtype)
-
-
-def inputs_of(fx, dtype):
-    B, S, d, c, _, _ = dims(fx)
-    return torch.tensor(fx["x"]).to(dtype).view(B * S, d), torch.tensor(fx["ctx"]).to(dtype).view(B, c), torch.tensor(fx["eps"]).to(dtype)
+    return CDAE.module(str(fx["kind"]), d, h, nl, str(fx["act"]), c, **kw)
 
 
 # ---- 1. layout ---------------------------------------------------------------------------------------------------------------------
@@ -181,7 +137,7 @@ def test_argument_validation_of_the_plain_conditional_entry_points():
 # ---- 3. modules --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["grad", "res"])
 def test_module_defaults_are_the_references(kind, golden_dir):
-    cls = getattr(net, CLS[kind])
+    cls = CDAE.classes[kind]
     last = "neglogprob" if kind == "grad" else "dae"
     names = ["ctx_encode.fc.weight", "ctx_encode.fc.bias", "inp_encode.fc.weight", "inp_encode.fc.bias",
              f"{last}.layers.0.weight", f"{last}.layers.0.bias", f"{last}.fc.weight", f"{last}.fc.bias"]
@@ -255,14 +211,14 @@ def test_restatement_reproduces_the_fp64_fixtures(golden_dir):
         kind, act, S = str(fx["kind"]), str(fx["act"]), dims(fx)[1]
         p = {k: v.double() for k, v in state_dict_of(fx).items()}
         x, ctx, eps = inputs_of(fx, torch.float64)
-        loss, grads = loss_and_grads(kind, p, act, x, ctx, S, std_of(fx, torch.float64), eps)
+        loss, grads = loss_and_grads(kind, p, act, x, std_of(fx, torch.float64), eps, False, ctx, S)
         assert abs(float(loss) - float(fx["loss_f64"])) <= 1e-12 * abs(float(fx["loss_f64"])), path
         for n, g in grads.items():
             if f"g_f64/{n}/none" in fx:
                 assert g is None and n == "neglogprob.fc.bias", (path, n)
             else:
                 assert rel(g, fx["g_f64/" + n]) <= 1e-12, (path, n, rel(g, fx["g_f64/" + n]))
-        assert rel(score(kind, p, act, x, ctx, S).reshape(fx["glog_f64"].shape), fx["glog_f64"]) <= 1e-12, path
+        assert rel(score(kind, p, act, x, None, ctx, S).reshape(fx["glog_f64"].shape), fx["glog_f64"]) <= 1e-12, path
     assert sorted(load(p)["std"].ndim for p in fixtures(golden_dir)) == [0] * 6 + [2] * 4         # scalar and [B*S, 1] noise levels
 
 
@@ -290,7 +246,7 @@ def test_restatement_reproduces_the_fp64_trajectory(golden_dir):
             sigmas.append(sigma)
             u, ctx, eps = traj_step_inputs(fx, s, torch.float64)
             xbar = (u + sigma * eps).requires_grad_(True)
-            loss = torch.nn.functional.mse_loss(sigma * score(kind, p, act, xbar, ctx, rows_per_ctx, create_graph=True), -eps)
+            loss = torch.nn.functional.mse_loss(sigma * score(kind, p, act, xbar, None, ctx, rows_per_ctx, create_graph=True), -eps)
             opt.zero_grad()
             loss.backward()
             opt.step()

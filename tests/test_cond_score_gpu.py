@@ -2,109 +2,29 @@
 ArdaeCondScoreEngine for both conditional families.
 
 Bars: loss 2e-5 relative, every gradient tensor and glogprob 1e-4 relative L2 against the reference's fp32 fixtures - the bars
-tests/test_cdae_gpu.py and tests/test_dae_plain_gpu.py state.  The float64 oracle is the restatement in tests/test_cond_score.py, which that
-file pins to the reference's fp64 fixtures to 1e-12."""
-import os
-
+tests/test_cdae_gpu.py and tests/test_dae_plain_gpu.py state.  The float64 oracle is the restatement in tests/score_restate.py, which
+tests/test_cond_score.py pins to the reference's fp64 fixtures to 1e-12."""
 import numpy as np
 import pytest
 import torch
 
 import ardae_amd as net
 from ardae_amd import _lib as L
-from ardae_amd import layout
 from oracle import ardae_oracle as O
-from test_ardae_uncond import load, rel, state_dict_of
-from test_ardae_uncond_gpu import assert_matches_reference, flat_of, init_params
-from test_cdae_gpu import split_flat
-from test_cond_score import CLS, KIND_ID, build, dims, inputs_of, score, std_of
+from score_gpu_checks import (STRIDE, Harness, check_abi_against_fixture, check_drop_in_route, check_module_forward_backward, check_recorded_trajectory,
+                              check_refusals, check_replay_equals_eager, check_resume, check_zero_sigma_column, dae_block, flat_of, fresh_module, guarded,
+                              init_params)
+from score_restate import CARDAE, CDAE, LOSS_TOL, TENSOR_TOL, cast, grads_on_xbar, rel, score
 
 pytestmark = pytest.mark.gpu
-LOSS_TOL, TENSOR_TOL = 2e-5, 1e-4
 FIXTURE_IDS = [f"{k}_{c}" for k in ("grad", "res") for c in ("b4_s16_d2_softplus", "b5_s12_d3_elu", "b6_s16_d8_tanh", "b8_s8_d2_relu1", "b4_s16_d2_swish")]
-STRIDE = 16
-
-
-def fixture(golden_dir, fid):
-    return load(os.path.join(golden_dir, f"cdae_plain_{fid}.npz"))
-
-
-def sigma_rows(std, N):
-    """The per-row [N] array the ABI takes for the reference's float or [N, 1] std."""
-    return std.reshape(-1) if torch.is_tensor(std) else torch.full((N,), float(std))
-
-
-def guarded(rows, cols=None):
-    """A NaN-filled buffer of rows + 1 rows: the first `rows` are the output, the last one must stay NaN."""
-    full = torch.full((rows + 1,) if cols is None else (rows + 1, cols), float("nan"), device="cuda")
-    return full, full[:rows]
-
-
-def dae_block(t, smax, smin, ann, lr=5e-3, beta1=0.9):
-    """A DAE state block that describes step t (t >= 1): written for t - 1, advanced once."""
-    st = torch.zeros(4, dtype=torch.int64, device="cuda")
-    st[0], st[1] = STRIDE * (t - 1), t - 1
-    L.call("ardae_dae_state_advance", st, STRIDE, lr, beta1, 0.999, smax, smin, ann)
-    return st
-
-
-class Harness:
-    """The C ABI for one conditional network: plain (kind 10 / 11) or, plain=False, its AR-DAE sibling (kind 0 / 1)."""
-
-    def __init__(self, kind, d, c, h, nl, act, flat_params, plain=True):
-        self.kind, self.d_in, self.c, self.h = kind, d, c, h
-        self.spec = (layout.cdae_plain_spec if plain else layout.cdae_spec)(kind, d, c, h, nl)
-        self.d = L.CdaeDesc(KIND_ID[kind] - (0 if plain else 10), d, c, h, nl, L.ACT[act])
-        assert L.query("ardae_cdae_param_floats", self.d) == flat_params.numel()
-        self.params = flat_params.cuda()
-        self.packed = torch.empty(L.query("ardae_cdae_packed_floats", self.d), device="cuda")
-        L.call("ardae_cdae_pack", self.d, self.params, self.packed)
-
-    def loss_grads(self, xbar, sigma, eps, ctx, B, S):
-        assert B * S == xbar.size(0)
-        ws = torch.empty(L.query("ardae_cdae_workspace_floats", self.d, B, S, 1), device="cuda")
-        loss, grads = torch.zeros(1, device="cuda"), torch.full_like(self.params, float("nan"))
-        sc = torch.empty(B * S, self.d_in, device="cuda")
-        xbar, sigma, eps, ctx = (t.contiguous().cuda() for t in (xbar, sigma.reshape(-1), eps, ctx.reshape(B, self.c)))
-        L.call("ardae_cdae_loss_grads", self.d, self.params, self.packed, xbar, sigma, eps, ctx, B, S, ws, ws.numel(), loss, grads, sc)
-        torch.cuda.synchronize()
-        return loss.cpu(), split_flat(grads.cpu(), self.spec), sc.cpu()
-
-    def score(self, x, ctx, B, S, sigma=None):
-        ws = torch.empty(L.query("ardae_cdae_workspace_floats", self.d, B, S, 0), device="cuda")
-        out = torch.empty(B * S, self.d_in, device="cuda")
-        x, ctx = x.contiguous().cuda(), ctx.reshape(B, self.c).contiguous().cuda()
-        L.call("ardae_cdae_score", self.d, self.params, self.packed, x, None if sigma is None else sigma.reshape(-1).contiguous().cuda(), ctx, B, S, ws,
-               ws.numel(), out)
-        torch.cuda.synchronize()
-        return out.cpu()
-
-
-def first_energy_weight(kind):
-    return ("neglogprob." if kind == "grad" else "dae.") + "layers.0.weight"
+FAMILY = {True: CDAE, False: CARDAE}      # by `plain`
 
 
 # ---- 1. C ABI against every fixture ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("fid", FIXTURE_IDS)
 def test_abi_matches_the_reference_fixtures(golden_dir, fid):
-    fx = fixture(golden_dir, fid)
-    (B, S, d, c, h, nl), kind, act = dims(fx), str(fx["kind"]), str(fx["act"])
-    N = B * S
-    x, ctx, eps = inputs_of(fx, torch.float32)
-    std = std_of(fx)
-    s = sigma_rows(std, N)
-    hn = Harness(kind, d, c, h, nl, act, flat_of(state_dict_of(fx), layout.cdae_plain_spec(kind, d, c, h, nl)))
-    xbar = x + std * eps                                        # add_gaussian_noise as the reference evaluates it
-    loss, grads, sc = hn.loss_grads(xbar, s, eps, ctx, B, S)
-    print(f"{fid}: loss {float(loss):.7f} (reference {float(fx['loss']):.7f})")
-    assert abs(float(loss) - float(fx["loss"])) <= LOSS_TOL * abs(float(fx["loss"]))
-    assert_matches_reference(grads, fx, "g", fid)
-    assert [n for n, g in grads.items() if torch.isnan(g).any()] == (["neglogprob.fc.bias"] if kind == "grad" else [])       # the prefill survives there only
-    # score: the same bits whatever sigma is passed
-    glog = hn.score(x, ctx, B, S)
-    assert rel(glog, fx["glog"].reshape(N, d)) <= TENSOR_TOL
-    assert torch.equal(glog, hn.score(x, ctx, B, S, s)) and torch.equal(glog, hn.score(x, ctx, B, S, torch.zeros(N)))
-    assert torch.equal(glog, hn.score(x, ctx, B, S, torch.full((N,), float("nan"))))
+    check_abi_against_fixture(CDAE, golden_dir, fid)
 
 
 # ---- 2. the AR-DAE kinds with a zero sigma column are the same function: existing code as the oracle -------------------------------
@@ -115,32 +35,7 @@ ORACLE_SHAPES = [(1, 1, 2, 2, 64, 1, "tanh"), (5, 20, 3, 5, 100, 2, "elu"), (4, 
 @pytest.mark.parametrize("kind", ["grad", "res"])
 @pytest.mark.parametrize("B,S,d,c,h,nl,act", ORACLE_SHAPES, ids=[f"b{s[0]}_s{s[1]}_d{s[2]}_h{s[4]}" for s in ORACLE_SHAPES])
 def test_plain_kinds_equal_the_ardae_kinds_with_a_zero_sigma_column(kind, B, S, d, c, h, nl, act):
-    N = B * S
-    g = torch.Generator().manual_seed(N + d)
-    x, sigma, eps, ctx = torch.randn(N, d, generator=g), 0.3 * torch.randn(N, generator=g), torch.randn(N, d, generator=g), torch.randn(B, c, generator=g)
-    spec = layout.cdae_plain_spec(kind, d, c, h, nl)
-    p = init_params(spec, 4)
-    first = first_energy_weight(kind)
-    q = dict(p)
-    q[first] = torch.cat([p[first], torch.zeros(h, 1)], 1)                                  # fma(sigma, 0, v) = v
-    xbar = torch.addcmul(x, sigma[:, None], eps)
-    hn = Harness(kind, d, c, h, nl, act, flat_of(p, spec))
-    ar = Harness(kind, d, c, h, nl, act, flat_of(q, layout.cdae_spec(kind, d, c, h, nl)), plain=False)
-    loss, grads, sc = hn.loss_grads(xbar, sigma, eps, ctx, B, S)
-    loss_o, grads_o, sc_o = ar.loss_grads(xbar, sigma, eps, ctx, B, S)
-    grads_o[first] = grads_o[first][:, :2 * h]                                              # all tensors but the sigma column
-    assert abs(float(loss) - float(loss_o)) <= LOSS_TOL * abs(float(loss_o))
-    assert rel(sc, sc_o) <= TENSOR_TOL
-    same, total = int((sc == sc_o).sum()), sc.numel()
-    for n in grads:
-        if torch.isnan(grads_o[n]).all():
-            assert torch.isnan(grads[n]).all() and n == "neglogprob.fc.bias"
-            continue
-        assert not torch.isnan(grads[n]).any(), n
-        assert rel(grads[n], grads_o[n]) <= TENSOR_TOL, (n, rel(grads[n], grads_o[n]))
-        same, total = same + int((grads[n] == grads_o[n]).sum()), total + grads[n].numel()
-    assert rel(hn.score(x, ctx, B, S), ar.score(x, ctx, B, S, sigma)) <= TENSOR_TOL          # (N == B: kind 10 walks kind 0's one-launch chain)
-    print(f"{kind} B={B} S={S} d={d} h={h} L={nl} {act}: {100 * same / total:.3f} % of the score and gradient elements bit-identical, loss {float(loss):.7f} / {float(loss_o):.7f}")
+    check_zero_sigma_column(CDAE, kind, B, S, d, c, h, nl, act)
 
 
 # ---- 3. against float64, with the AR-DAE sibling as the yardstick ------------------------------------------------------------------
@@ -149,12 +44,8 @@ F64_SHAPES = [(16, 64, 32, 32, 256, 3, "softplus"), (10, 30, 3, 5, 100, 2, "elu"
 
 def oracle_grads(kind, p, act, xbar, sigma, eps, ctx, S, dtype, with_sigma_input):
     """The restatement's loss on the SAME fp32 xbar, mse(sigma g(xbar), -eps), and its gradients, in `dtype`"""
-    pp = {k: v.to(dtype).requires_grad_(True) for k, v in p.items()}
-    xb = xbar.to(dtype).requires_grad_(True)
-    sg = sigma.to(dtype).reshape(-1, 1)
-    g = score(kind, pp, act, xb, ctx.to(dtype), S, create_graph=True, sigma=sg if with_sigma_input else None)
-    loss = torch.nn.functional.mse_loss(sg * g, -eps.to(dtype))
-    return loss.detach(), dict(zip(pp, torch.autograd.grad(loss, list(pp.values()), allow_unused=True)))
+    pp, xb, sg, ep, cx = cast(dtype, p, xbar, sigma.reshape(-1, 1), eps, ctx)
+    return grads_on_xbar(kind, pp, act, xb, sg, ep, with_sigma_input, cx, S)
 
 
 @pytest.mark.parametrize("kind", ["grad", "res"])
@@ -166,14 +57,14 @@ def test_gradients_against_float64(kind, B, S, d, c, h, nl, act):
     g = torch.Generator().manual_seed(N + d)
     x, sigma, eps, ctx = torch.randn(N, d, generator=g), 0.1 * torch.randn(N, generator=g), torch.randn(N, d, generator=g), torch.randn(B, c, generator=g)
     xbar = torch.addcmul(x, sigma[:, None], eps)
-    spec, spec_sib = layout.cdae_plain_spec(kind, d, c, h, nl), layout.cdae_spec(kind, d, c, h, nl)
+    spec, spec_sib = CDAE.spec_of(kind, d, h, nl, c), CARDAE.spec_of(kind, d, h, nl, c)
     p, p_sib = init_params(spec, 3), init_params(spec_sib, 11)
     _, g64_sib = oracle_grads(kind, p_sib, act, xbar, sigma, eps, ctx, S, torch.float64, True)
-    _, grads_sib, _ = Harness(kind, d, c, h, nl, act, flat_of(p_sib, spec_sib), plain=False).loss_grads(xbar, sigma, eps, ctx, B, S)
+    _, grads_sib, _ = Harness(CARDAE, kind, d, h, nl, act, flat_of(p_sib, spec_sib), c).loss_grads(xbar, sigma, eps, ctx, B, S)
     E_sib = max(rel(grads_sib[n], g64_sib[n]) for n in grads_sib if g64_sib[n] is not None)
     loss64, g64 = oracle_grads(kind, p, act, xbar, sigma, eps, ctx, S, torch.float64, False)
     _, g32 = oracle_grads(kind, p, act, xbar, sigma, eps, ctx, S, torch.float32, False)
-    loss, grads, _ = Harness(kind, d, c, h, nl, act, flat_of(p, spec)).loss_grads(xbar, sigma, eps, ctx, B, S)
+    loss, grads, _ = Harness(CDAE, kind, d, h, nl, act, flat_of(p, spec), c).loss_grads(xbar, sigma, eps, ctx, B, S)
     assert abs(float(loss) - float(loss64)) <= LOSS_TOL * abs(float(loss64))
     bad = []
     for n in g64:
@@ -228,45 +119,10 @@ def test_latent_noise_perturb_kernels(B, nz, nstd, z):
 # ---- 5. modules --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("fid", FIXTURE_IDS)
 def test_module_forward_backward(golden_dir, fid):
-    fx = fixture(golden_dir, fid)
-    (B, S, d, c, h, nl), kind, act = dims(fx), str(fx["kind"]), str(fx["act"])
-    N = B * S
-    x, ctx, eps = torch.tensor(fx["x"]).cuda(), torch.tensor(fx["ctx"]).cuda(), torch.tensor(fx["eps"]).cuda()
-    std = std_of(fx)
-    std = std.cuda() if torch.is_tensor(std) else std
-    m = build(fx)
-    m.load_state_dict(state_dict_of(fx))
-    m = m.cuda()
-    none, loss = m(x, ctx, std, eps=eps)
-    assert none is None and loss.dim() == 0
-    loss.backward()
-    assert abs(float(loss.detach()) - float(fx["loss"])) <= LOSS_TOL * abs(float(fx["loss"]))
-    for n, p in m.named_parameters():
-        if n == "neglogprob.fc.bias":
-            assert p.grad is None
-        else:
-            assert rel(p.grad.cpu(), fx["g/" + n]) <= TENSOR_TOL, n
-    glog = m.glogprob(x, ctx)
-    assert glog.shape == (B, S, d) and rel(glog.cpu(), fx["glog"]) <= TENSOR_TOL
-    assert torch.equal(glog, m.glogprob(x, ctx, 0.7)) and torch.equal(glog, m.glogprob(x, ctx, torch.ones(N, 1, device="cuda")))
-    # std=None: self.std; a number and the tensors that broadcast to [B*S, 1] are the same call
-    m.std = 0.37
-    a = float(m(x, ctx, eps=eps)[1].detach())
-    assert a == float(m(x, ctx, 0.37, eps=eps)[1].detach()) != float(loss.detach())
-    assert a == float(m(x, ctx, torch.tensor(0.37, device="cuda"), eps=eps)[1].detach()) == float(m(x, ctx, torch.full((N, 1), 0.37, device="cuda"), eps=eps)[1].detach())
-    # eps=None: the module's own Philox draw, a fresh one per call
-    a, b = float(m(x, ctx, std)[1].detach()), float(m(x, ctx, std)[1].detach())
-    assert np.isfinite(a) and np.isfinite(b) and a != b and a != float(loss.detach())
+    check_module_forward_backward(CDAE, golden_dir, fid)
 
 
 # ---- 6. the AR-DAE kinds: ArdaeEngine's cDAE phase behind its sampler --------------------------------------------------------------
-def fresh_module(kind, d, c, h, nl, act, plain, seed=21):
-    cls = getattr(net, CLS[kind]) if plain else (net.MLPGradCARDAE if kind == "grad" else net.MLPResCARDAE)
-    m = cls(input_dim=d, context_dim=c, h_dim=h, num_hidden_layers=nl, nonlinearity=act)
-    m.load_state_dict(init_params((layout.cdae_plain_spec if plain else layout.cdae_spec)(kind, d, c, h, nl), seed))
-    return m.cuda()
-
-
 @pytest.mark.parametrize("kind,nstd", [("grad", 1), ("res", 3)])
 def test_ar_step_is_the_cdae_phase_of_the_vae_engine(kind, nstd):
     """The same ABI calls at the same shapes: with injected noise, a step on the latent / z0 / context that a tiny ArdaeEngine's cdae_phase
@@ -279,7 +135,7 @@ def test_ar_step_is_the_cdae_phase_of_the_vae_engine(kind, nstd):
     model, cdae = build_pair(mc, cc)
     model.load_state_dict(O.init_params(O.model_param_spec(mc), 0, O.model_init_special(mc)))
     cdae.load_state_dict(O.init_params(O.cdae_param_spec(cc), 1))
-    twin = (net.MLPGradCARDAE if kind == "grad" else net.MLPResCARDAE)(input_dim=8, context_dim=8, h_dim=64, num_hidden_layers=3, nonlinearity=cc.nonlin)
+    twin = CARDAE.module(kind, 8, 64, 3, cc.nonlin, 8)
     twin.load_state_dict(cdae.state_dict())
     eng = net.ArdaeEngine(model.cuda(), cdae.cuda(), tcfg, batch_size=B)
     g = torch.Generator().manual_seed(9)
@@ -312,7 +168,7 @@ def test_ar_own_draw_forms_equal_the_unfused_launches(kind):
     runs = {}
     for form in ("first_layer", "draw", "unfused"):
         net.manual_seed(55)
-        eng = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, False), cfg, B, S, std_scale=100.0, graph=False)
+        eng = net.ArdaeCondScoreEngine(fresh_module(CARDAE, kind, z, h, nl, act, c), cfg, B, S, std_scale=100.0, graph=False)
         assert eng.fused_first and eng.fused_draw
         eng.fused_first, eng.fused_draw = form == "first_layer", form != "unfused"
         eng.step(latent, ctx, mean)
@@ -329,10 +185,6 @@ def test_ar_own_draw_forms_equal_the_unfused_launches(kind):
 
 
 # ---- 7. engine ---------------------------------------------------------------------------------------------------------------------
-def sigma32(cfg, i):
-    return float(np.float32(net.dae_sigma(cfg.sigma_max, cfg.sigma_min, cfg.sigma_annealing, i)))
-
-
 def batches(B, S, z, c, n, seed=0):
     g = torch.Generator().manual_seed(seed)
     out = []
@@ -355,29 +207,13 @@ def make_cfg(plain, ns, optimizer):
 @pytest.mark.parametrize("plain,kind,B,S,ns,z,c,h,nl,act,optimizer", ENGINE_CASES, ids=[f"{'plain' if e[0] else 'ar'}_{e[1]}_{e[10]}" for e in ENGINE_CASES])
 def test_engine_replay_equals_eager(plain, kind, B, S, ns, z, c, h, nl, act, optimizer):
     cfg = make_cfg(plain, ns, optimizer)
-    data = batches(B, S, z, c, 6)
-    runs = []
-    for graph in (True, False):
-        net.manual_seed(77)
-        eng = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, plain), cfg, B, S, std_scale=2.0, graph=graph)
-        assert eng.plain == plain and eng.fused_first == (not plain and z == 32) and eng.draw_form == plain
-        trace = []
-        for i, (lat, ctx, mean) in enumerate(data):
-            eng.step(lat, ctx.view(B, 1, c), mean.view(B, 1, z) if i % 2 else mean)
-            trace += [eng.cdae.flat_params().clone(), eng.loss.clone(), eng.sigma.clone(), eng.xbar.clone()] + [b.clone() for b in eng.opt.buffers()]
-            if plain:
-                assert eng.stats()["sigma"] == sigma32(cfg, i) and torch.equal(eng.sigma, torch.full((B * S * ns,), sigma32(cfg, i), device="cuda"))
-        torch.cuda.synchronize()
-        assert (eng._graph is not None) == graph
-        runs.append(trace + [eng.state.clone()])
-    assert len(runs[0]) == len(runs[1]) and all(torch.equal(a, b) for a, b in zip(*runs)), "replayed != eager"
-    losses = torch.cat(runs[0][1::4 + len(eng.opt.buffers())][:6])
-    assert torch.isfinite(losses).all() and len(set(losses.tolist())) == 6
-    s = runs[0][-1]
-    assert int(s[0]) == STRIDE * 7 and int(s[1]) == 7                          # the block describes the coming step
+    raw = batches(B, S, z, c, 6)
+    data = [(lat, ctx.view(B, 1, c), mean.view(B, 1, z) if i % 2 else mean) for i, (lat, ctx, mean) in enumerate(raw)]
+    flags = dict(fused_first=not plain and z == 32, draw_form=plain)
+    eng = check_replay_equals_eager(FAMILY[plain], lambda: fresh_module(FAMILY[plain], kind, z, h, nl, act, c), cfg, B, (S,), data, flags, std_scale=2.0)
     lat_b, mean_b, ctx_b = eng.input_buffers()
     assert lat_b.shape == (B, S, z) and mean_b.shape == (B, z) and ctx_b.shape == (B, c)
-    assert torch.equal(lat_b, data[-1][0]) and torch.equal(ctx_b, data[-1][1]) and torch.equal(mean_b, data[-1][2])
+    assert torch.equal(lat_b, raw[-1][0]) and torch.equal(ctx_b, raw[-1][1]) and torch.equal(mean_b, raw[-1][2])
     eng.step(lat_b, ctx_b, mean_b)                                              # the static buffers themselves: no copies
     eng.step(lat_b, ctx_b)                                                      # latent_mean=None: zeros
     assert eng.step_count == 8 and not mean_b.any()
@@ -398,7 +234,7 @@ def test_plain_engine_draw_form_equals_its_two_launches(kind):
     runs = []
     for draw_form in (None, False):
         net.manual_seed(31)
-        eng = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, True), cfg, B, S, std_scale=2.0, draw_form=draw_form)
+        eng = net.ArdaeCondScoreEngine(fresh_module(CDAE, kind, z, h, nl, act, c), cfg, B, S, std_scale=2.0, draw_form=draw_form)
         assert eng.draw_form == (draw_form is None)
         trace = []
         for lat, ctx, mean in batches(B, S, z, c, 4):
@@ -413,65 +249,16 @@ def test_plain_engine_draw_form_equals_its_two_launches(kind):
 
 @pytest.mark.parametrize("kind", ["grad", "res"])
 def test_plain_engine_follows_the_recorded_trajectory(golden_dir, kind):
-    """The update on the fixture's samples / eps: every parameter after every step against the reference's fp32 run, and no further from its
-    float64 run than max(2 x the fp32 reference's own distance, 2e-6)."""
-    fx = load(os.path.join(golden_dir, f"cdae_plain_traj_{kind}.npz"))
-    c = {k[4:]: v for k, v in fx.items() if k.startswith("cfg/")}
-    B, S, ns, d, cd, h, nl, act, steps = int(c["B"]), int(c["S"]), int(c["nsigma"]), int(c["d"]), int(c["c"]), int(c["h"]), int(c["L"]), str(c["act"]), int(c["steps"])
-    cfg = net.DaeConfig(sigma_max=float(c["sigma_max"]), sigma_min=float(c["sigma_min"]), sigma_annealing=int(c["sigma_annealing"]), nsigma=ns, lr=float(c["lr"]))
-    m = getattr(net, CLS[kind])(input_dim=d, context_dim=cd, h_dim=h, num_hidden_layers=nl, nonlinearity=act)
-    m.load_state_dict(state_dict_of(fx))
-    eng = net.ArdaeCondScoreEngine(m.cuda(), cfg, B, S, std_scale=float(c["std_scale"]))
-    bad = []
-    for s in range(steps):
-        lat, mean, ctx, eps = (torch.tensor(fx[f"{s}/{k}"]).cuda() for k in ("latent", "mean", "ctx", "eps"))
-        eng.step(lat, ctx, mean, noise={"eps": eps})
-        st = eng.stats()
-        assert st["sigma"] == float(np.float32(float(fx[f"{s}/sigma"])))
-        assert abs(st["loss"] - float(fx[f"{s}/loss"])) <= LOSS_TOL * abs(float(fx[f"{s}/loss"])), (s, st["loss"])
-        for n, p in eng.cdae.named_parameters():
-            p32, p64 = fx[f"{s}/p/{n}"], fx[f"{s}/p_f64/{n}"]
-            e32, e64, ref64 = rel(p.detach().cpu(), p32), rel(p.detach().cpu(), p64), rel(p32, p64)
-            print(f"{kind} step {s} {n}: to fp32 reference {e32:.2e}, to float64 {e64:.2e} (fp32 reference to float64 {ref64:.2e})")
-            if e32 > TENSOR_TOL or e64 > max(2 * ref64, 2e-6):
-                bad.append((s, n, e32, e64, ref64))
-    assert not bad, bad
+    """The update on the fixture's samples / eps."""
+    check_recorded_trajectory(CDAE, golden_dir, kind)
 
 
 @pytest.mark.parametrize("plain,kind", [(True, "grad"), (True, "res"), (False, "grad"), (False, "res")])
 def test_engine_equals_the_drop_in_module_route(plain, kind):
     """The same six steps through the engine and through the module + torch.optim with host-computed noise levels."""
-    B, S, ns, z, c, h, nl, act, scale = 6, 8, 2, 3, 5, 64, 2, "elu", 2.0
-    N = B * S * ns
-    if plain:
-        cfg = net.DaeConfig(sigma_max=1.0, sigma_min=0.1, sigma_annealing=4, nsigma=ns)
-    else:
-        cfg = net.ScoreConfig(delta=0.1, nsigma=ns, lr=1e-3, optimizer="rmsprop", momentum=0.5)
-    eng = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, plain), cfg, B, S, std_scale=scale)
-    m = fresh_module(kind, z, c, h, nl, act, plain)
-    opt = torch.optim.Adam(m.parameters(), lr=cfg.lr) if plain else torch.optim.RMSprop(m.parameters(), lr=cfg.lr, momentum=0.5)
-    g = torch.Generator().manual_seed(5)
-    for i, (lat, ctx, mean) in enumerate(batches(B, S, z, c, 6, seed=1)):
-        xi, eps = torch.randn(N, generator=g).cuda(), torch.randn(N, z, generator=g).cuda()
-        eng.step(lat, ctx, mean, noise={"eps": eps} if plain else {"sigma": xi, "eps": eps})
-        u = scale * (lat - mean[:, None, :])
-        rows = u.unsqueeze(2).expand(B, S, ns, z).reshape(B, S * ns, z)
-        opt.zero_grad()
-        if plain:
-            _, loss = m(rows, ctx.view(B, 1, c), net.dae_sigma(1.0, 0.1, 4, i), eps=eps)
-        else:       # ivae_ardae.py:753-767: std = delta * mean_d std_S(u), one draw per row
-            std = cfg.delta * u.std(dim=1, keepdim=True).mean(dim=2, keepdim=True).expand(B, S * ns, 1) * xi.view(B, S * ns, 1)
-            _, loss = m(rows, ctx.view(B, 1, c), std, eps=eps)
-        loss.backward()
-        opt.step()
-        assert abs(eng.stats()["loss"] - float(loss.detach())) <= LOSS_TOL * abs(float(loss.detach())), i
-        for (n, p), (_, q) in zip(eng.cdae.named_parameters(), m.named_parameters()):
-            assert rel(p.detach().cpu(), q.detach().cpu()) <= TENSOR_TOL, (i, n, rel(p.detach().cpu(), q.detach().cpu()))
-    # the two routes' checkpoints are interchangeable: torch.optim's state loads into the engine
-    eng.load_state_dict({"cdae": m.state_dict(), "optimizer": opt.state_dict()})
-    assert eng.step_count == 6 and eng.state[:2].tolist() == [STRIDE * 7, 7]
-    if plain:
-        assert eng.state[3:].view(torch.float32)[0].item() == sigma32(cfg, 6)
+    B, S, ns, z, c, h, nl, act = 6, 8, 2, 3, 5, 64, 2, "elu"
+    data = iter(batches(B, S, z, c, 6, seed=1))
+    check_drop_in_route(FAMILY[plain], kind, z, h, nl, act, c, B, (S,), ns, lambda g: next(data), scale=2.0)
 
 
 @pytest.mark.parametrize("plain,kind,optimizer", [(True, "grad", "adam_torch"), (True, "res", "amsgrad"), (False, "grad", "rmsprop")])
@@ -479,52 +266,21 @@ def test_engine_resumes_bit_identically_across_the_end_of_the_ramp(plain, kind, 
     """state_dict() after step 2 into a fresh engine under another library seed: steps 3 - 8 (the ramp of 4 steps ends among them; eager,
     eager, captured, replayed there) leave what the uninterrupted run leaves."""
     B, S, ns, z, c, h, nl, act = 6, 8, 2, 3, 5, 64, 2, "elu"
-    cfg = make_cfg(plain, ns, optimizer)
-    data = batches(B, S, z, c, 8)
-    runs, sd = [], None
-    for resumed in (False, True):
-        net.manual_seed(77)
-        eng = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, plain), cfg, B, S)
-        losses = []
-        for i, (lat, ctx, mean) in enumerate(data):
-            if resumed and i == 2:
-                sd = eng.state_dict()
-                net.manual_seed(1)                                 # the checkpoint, not the process, carries the RNG state
-                eng = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, plain, seed=5), cfg, B, S)
-                eng.load_state_dict(sd)
-                assert eng._graph is None and (eng.step_count, eng.opt.steps) == (2, 2)
-            eng.step(lat, ctx, mean)
-            if plain:
-                assert eng.stats()["sigma"] == sigma32(cfg, i)
-            losses.append(eng.loss.clone())
-        torch.cuda.synchronize()
-        assert eng._graph is not None
-        runs.append([eng.cdae.flat_params().clone(), eng.state.clone(), eng.sigma.clone(), torch.cat(losses)[2:]] + [b.clone() for b in eng.opt.buffers()])
-    assert len(runs[0]) == len(runs[1]) == 4 + len(eng.opt.state_names())
-    assert all(torch.equal(a, b) for a, b in zip(*runs)), "the resumed run drifted"
-    assert torch.isfinite(runs[0][3]).all() and len(set(runs[0][3].tolist())) == 6
-    if plain:      # a checkpoint written under another schedule resumes at THIS engine's value: bytes 24..27 are recomputed from t
-        other = net.DaeConfig(sigma_max=5.0, sigma_min=0.05, sigma_annealing=4000, nsigma=ns, optimizer=optimizer, momentum=0.5)
-        new = net.ArdaeCondScoreEngine(fresh_module(kind, z, c, h, nl, act, plain, seed=5), other, B, S)
-        new.load_state_dict(sd)
-        assert torch.equal(new.state[:3].cpu(), sd["engine"]["step_state"][:3]) and new.state[3:].view(torch.float32)[0].item() == sigma32(other, 2)
+    other = net.DaeConfig(sigma_max=5.0, sigma_min=0.05, sigma_annealing=4000, nsigma=ns, optimizer=optimizer, momentum=0.5)
+    check_resume(FAMILY[plain], lambda seed: fresh_module(FAMILY[plain], kind, z, h, nl, act, c, seed=seed), make_cfg(plain, ns, optimizer), other, B, (S,),
+                 batches(B, S, z, c, 8), 2, {})
 
 
 def test_engine_refusals_leave_the_step_count_at_zero():
     z, c = 2, 3
-    with pytest.raises(TypeError, match="(?s)MLPGradCDAE.*DaeConfig.*ScoreConfig"):
-        net.ArdaeCondScoreEngine(fresh_module("grad", z, c, 64, 3, "softplus", True), net.ScoreConfig(), 4, 8)
-    with pytest.raises(TypeError, match="(?s)MLPResCARDAE.*ScoreConfig.*DaeConfig"):
-        net.ArdaeCondScoreEngine(fresh_module("res", z, c, 64, 3, "softplus", False), net.DaeConfig(), 4, 8)
+    fresh = lambda plain: lambda: fresh_module(FAMILY[plain], "grad", z, 64, 3, "softplus", c)
     from test_engine_gpu import build as build_pair
     model, _ = build_pair(O.ModelCfg("mnist", 24, 10, 64, 2, 2, "softplus"), O.CdaeCfg("grad", 2, 2, 64, 3))
     with pytest.raises(TypeError, match="ArdaeCondScoreEngine"):       # the VAE loop's engine has no slot for a noise level beside beta
-        net.ArdaeEngine(model.cuda(), fresh_module("grad", 2, 2, 64, 3, "softplus", True), net.TrainConfig(nz_cdae=8), batch_size=4)
+        net.ArdaeEngine(model.cuda(), fresh_module(CDAE, "grad", 2, 64, 3, "softplus", 2), net.TrainConfig(nz_cdae=8), batch_size=4)
     lat, ctx, mean = torch.zeros(4, 8, z, device="cuda"), torch.zeros(4, c, device="cuda"), torch.zeros(4, z, device="cuda")
-    for plain, cfg in ((True, net.DaeConfig(nsigma=2)), (False, net.ScoreConfig(nsigma=2))):
-        eng = net.ArdaeCondScoreEngine(fresh_module("grad", z, c, 64, 3, "softplus", plain), cfg, 4, 8)
-        with pytest.raises(ValueError, match="batch_size=4"):
-            eng.step(lat[:3], ctx, mean)                                       # a ragged batch
+    for plain in (True, False):
+        eng = check_refusals(FAMILY[plain], fresh(plain), fresh(not plain), 4, (8,), (lat, ctx, mean), lat[:3])
         with pytest.raises(ValueError, match="batch_size=4"):
             eng.step(lat, ctx[:3], mean)
         with pytest.raises(ValueError, match="batch_size=4"):
@@ -533,21 +289,11 @@ def test_engine_refusals_leave_the_step_count_at_zero():
             eng.step(torch.zeros(4, 7, z, device="cuda"), ctx, mean)
         with pytest.raises(ValueError, match="step\\(latent\\)"):
             eng.step(lat.cpu(), ctx, mean)
-        good = {"sigma": torch.zeros(64, device="cuda"), "eps": torch.zeros(64, z, device="cuda")}
-        with pytest.raises(ValueError, match="eps must be"):
-            eng.step(lat, ctx, mean, noise=dict(good, eps=torch.zeros(32, z, device="cuda")))      # nsigma forgotten
-        with pytest.raises(ValueError, match="eps must be"):
-            eng.step(lat, ctx, mean, noise=dict(good, eps=torch.zeros(64, z)))
-        if not plain:
-            with pytest.raises(ValueError, match="sigma must be"):
-                eng.step(lat, ctx, mean, noise=dict(good, sigma=torch.zeros(32, device="cuda")))
-        with pytest.raises(ValueError, match="computes sigma on the device" if plain else "inject them through noise"):
-            eng.step(lat, ctx, mean, sigma=0.5)
         with pytest.raises(ValueError, match="score\\(ctx\\)"):
             eng.score(lat, ctx[:3])
         assert eng.step_count == 0 and eng.opt.steps == 0 and eng.state[:2].tolist() == [STRIDE, 1]
     with pytest.raises(ValueError, match="sample_size >= 2"):
-        net.ArdaeCondScoreEngine(fresh_module("grad", z, c, 64, 3, "softplus", False), net.ScoreConfig(), 4, 1)
+        net.ArdaeCondScoreEngine(fresh(False)(), net.ScoreConfig(), 4, 1)
 
 
 # ---- 8. quality, kept small --------------------------------------------------------------------------------------------------------
@@ -555,7 +301,7 @@ def test_engine_refusals_leave_the_step_count_at_zero():
 def test_learned_conditional_score_points_at_the_context(kind):
     """z | c ~ N(c, 0.25 I_2), sigma 1.0 -> 0.1 over 300 of 400 steps: the learned score(z, c) against the analytic score of the
     sigma-smoothed conditional, -(z - c) / (0.25 + 0.01), by cosine similarity on 1024 fresh pairs - and against the PyTorch autograd
-    restatement (tests/test_cond_score.py) trained with torch.optim.Adam on the same data."""
+    restatement (tests/score_restate.py) trained with torch.optim.Adam on the same data."""
     B, S, d, c, h, nl, act, steps = 64, 8, 2, 2, 64, 3, "softplus", 400
     cfg = net.DaeConfig(sigma_max=1.0, sigma_min=0.1, sigma_annealing=300, nsigma=1)
     g = torch.Generator().manual_seed(2024)
@@ -565,8 +311,8 @@ def test_learned_conditional_score_points_at_the_context(kind):
     pz = (pc + 0.5 * torch.randn(1024, d, generator=g).cuda()).contiguous()
     exact = -(pz - pc) / (0.25 + 0.01)
     net.manual_seed(11)
-    eng = net.ArdaeCondScoreEngine(fresh_module(kind, d, c, h, nl, act, True), cfg, B, S)
-    p = {k: v.cuda().requires_grad_(True) for k, v in init_params(layout.cdae_plain_spec(kind, d, c, h, nl), 21).items()}
+    eng = net.ArdaeCondScoreEngine(fresh_module(CDAE, kind, d, h, nl, act, c), cfg, B, S)
+    p = {k: v.cuda().requires_grad_(True) for k, v in init_params(CDAE.spec_of(kind, d, h, nl, c), 21).items()}
     opt = torch.optim.Adam(list(p.values()), lr=cfg.lr)
     torch.manual_seed(3)
     for i in range(steps):
@@ -574,13 +320,13 @@ def test_learned_conditional_score_points_at_the_context(kind):
         sigma = net.dae_sigma(1.0, 0.1, 300, i)
         eps = torch.randn(B * S, d, device="cuda")
         xbar = (lats[i].view(B * S, d) + sigma * eps).requires_grad_(True)
-        loss = torch.nn.functional.mse_loss(sigma * score(kind, p, act, xbar, ctxs[i], S, create_graph=True), -eps)
+        loss = torch.nn.functional.mse_loss(sigma * score(kind, p, act, xbar, None, ctxs[i], S, create_graph=True), -eps)
         opt.zero_grad()
         loss.backward()
         opt.step()
     cos = torch.nn.functional.cosine_similarity
     with torch.enable_grad():
-        ref_score = score(kind, {k: v.detach() for k, v in p.items()}, act, pz, pc, 1).detach()
+        ref_score = score(kind, {k: v.detach() for k, v in p.items()}, act, pz, None, pc, 1).detach()
     got, ref = float(cos(eng.score(pz.view(1024, 1, d), pc).view(1024, d), exact).mean()), float(cos(ref_score, exact).mean())
     print(f"{kind}: mean cosine similarity with the analytic score: engine {got:.4f}, autograd restatement {ref:.4f}; last losses {eng.stats()['loss']:.4f} / {float(loss.detach()):.4f}")
     assert got > 0 and got > ref - 0.05

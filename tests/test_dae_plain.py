@@ -1,8 +1,7 @@
 """Plain DAE score networks (ardae_cdae_desc.kind 6 / 7, notebooks/dae_toy.ipynb): layout, argument validation, the sigma schedule on
-the host, module and engine surface, and the float64 restatement of the two networks that the GPU tests lean on - pinned here to the
+the host, module and engine surface, and the float64 restatement of the two networks that the GPU tests lean on (tests/score_restate.py) - pinned here to the
 reference's fp64 fixtures.  No GPU needed."""
 import ctypes
-import glob
 import os
 
 import numpy as np
@@ -12,42 +11,16 @@ import torch
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
-from test_ardae_uncond import load, mlp, rel, state_dict_of
+from ardae_amd.engine_common import _FlatOpt
+from score_restate import DAE, load, loss_and_grads, rel, score, state_dict_of, std_of
 
-KIND_ID = {"grad": 6, "res": 7}
+KIND_ID = DAE.kind_id
+fixtures = DAE.fixtures
 # parameter counts of the reference classes, (d, h, L) -> (grad, res)
 REFERENCE_COUNTS = {(2, 128, 3): (33537, 33666), (2, 256, 3): (132609, 132866), (3, 100, 2): (10601, 10803), (2, 64, 3): (8577, 8642)}
 # sigma_max 5.0, sigma_min 0.05, sigma_annealing 4000: i -> (the Python float, numpy.float32 of it)
 SCHEDULE = {0: (4.998762500000001, 4.998762607574463), 1999: (2.525, 2.5250000953674316), 3998: (0.051237499999999866, 0.051237501204013824),
             3999: (0.05, 0.05000000074505806), 4000: (0.05, 0.05000000074505806), 123456: (0.05, 0.05000000074505806)}
-
-
-def fixtures(golden_dir, kind=None):
-    names = sorted(glob.glob(os.path.join(golden_dir, f"dae_plain_{kind or '*'}_n*.npz")))
-    assert len(names) == (5 if kind else 10)
-    return names
-
-
-# ---- the test-side oracle: the two networks restated (models/layers.py:477-515 MLP on x_bar alone) ---------------------------------
-def score(kind, p, act, x, create_graph=False):
-    if kind == "res":
-        return mlp(p, "main.", x, act)
-    x = x if x.requires_grad else x.clone().requires_grad_(True)
-    logprob = -mlp(p, "neglogprob.", x, act).sum()
-    return torch.autograd.grad(logprob, x, create_graph=create_graph)[0]
-
-
-def loss_and_grads(kind, p, act, x, std, eps):
-    """-> loss, {name: grad or None}, with p's tensors as leaves; std: a number or a tensor that broadcasts against [N, d]"""
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    xbar = (x + std * eps).requires_grad_(True)
-    loss = torch.nn.functional.mse_loss(std * score(kind, p, act, xbar, create_graph=True), -eps)
-    return loss.detach(), dict(zip(p, torch.autograd.grad(loss, list(p.values()), allow_unused=True)))
-
-
-def std_of(fx, dtype=torch.float32):
-    """The fixture's noise level as the reference took it: a Python float, or a [N, 1] tensor."""
-    return float(fx["std"]) if fx["std"].ndim == 0 else torch.tensor(fx["std"]).to(dtype)
 
 
 # ---- 1. layout ---------------------------------------------------------------------------------------------------------------------
@@ -197,7 +170,6 @@ def test_config_and_network_must_belong_together():
 
 
 def test_flat_opt_adam_torch_keeps_torchs_checkpoint_layout():
-    from ardae_amd.engine import _FlatOpt
     m = net.MLPGradDAE(input_dim=3, h_dim=16, num_hidden_layers=2, nonlinearity="elu")
     opt = _FlatOpt("adam_torch", m.flat_params(), m.flat_params().numel() - 1, 5e-3, 0.9, 0.0, dae=(5.0, 0.05, 4000))      # construction launches nothing
     assert opt.adam and opt.state_names() == ("exp_avg", "exp_avg_sq") and len(opt.buffers()) == 2
@@ -232,7 +204,7 @@ def test_restatement_reproduces_the_fp64_fixtures(golden_dir):
         kind, act = str(fx["kind"]), str(fx["act"])
         p = {k: v.double() for k, v in state_dict_of(fx).items()}
         x, eps = (torch.tensor(fx[k]).double() for k in ("x", "eps"))
-        loss, grads = loss_and_grads(kind, p, act, x, std_of(fx, torch.float64), eps)
+        loss, grads = loss_and_grads(kind, p, act, x, std_of(fx, torch.float64), eps, False)
         assert abs(float(loss) - float(fx["loss_f64"])) <= 1e-12 * abs(float(fx["loss_f64"])), path
         for n, g in grads.items():
             if f"g_f64/{n}/none" in fx:

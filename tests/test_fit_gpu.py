@@ -12,7 +12,7 @@ import torch
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import fit, layout
-from test_ardae_uncond import rel
+from score_restate import rel
 from test_engine_gpu import assert_update_close
 from test_fit import CASES, case_config, case_networks, load, sd_of
 

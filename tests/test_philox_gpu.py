@@ -13,8 +13,9 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout, rng
 from oracle import philox_ref as P
-from test_ardae_uncond_gpu import Harness, flat_of
-from test_ardae_uncond_gpu import init_params as dae_init_params
+from score_gpu_checks import Harness, flat_of
+from score_gpu_checks import init_params as dae_init_params
+from score_restate import ARDAE
 from test_fit_gpu import GenHarness
 from test_fit_gpu import init_params as gen_init_params
 from test_philox import EDGE_OFFSET, EDGE_SEED, EDGES
@@ -302,7 +303,7 @@ def test_latent_perturb_draw_under_wide_keys():
 def test_dae_perturb_loss_grads_draws_under_wide_keys():
     B, ns, d, h, nl, kind, act = 5, 12, 3, 64, 2, "grad", "softplus"          # 60 rows: one partial 64-row tile
     spec = layout.dae_spec(kind, d, h, nl)
-    hn = Harness(kind, d, h, nl, act, flat_of(dae_init_params(spec, 9), spec))
+    hn = Harness(ARDAE, kind, d, h, nl, act, flat_of(dae_init_params(spec, 9), spec))
     assert L.query("ardae_dae_perturb_fused_ok", hn.d, ns) == 1
     N = B * ns
     x = torch.randn(B, d, generator=torch.Generator().manual_seed(B)).cuda()

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 import ardae_amd as net
 from ardae_amd import _lib as L
 from oracle import ardae_oracle as O
-from test_ardae_uncond import ACTS, rel  # noqa: F401  (re-exported: the family files take them from here)
+from score_restate import ACTS, rel  # noqa: F401  (re-exported: the family files take them from here)
 
 BETAS = {"b1": 1.0, "b03": 0.3}
 TOL64 = 1e-9          # float64 restatement against the reference's float64 outputs: losses, full tensors and summaries
