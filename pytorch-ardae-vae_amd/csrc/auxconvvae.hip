@@ -1,6 +1,6 @@
 // The hierarchical conv Gaussian baseline (vae.py --model auxconv; ardae_model_desc.kind 17: models/vae/auxconv.py::VAE, the "# hierarchical conv"
 // baseline of run_vae_dbmnist.sh) - the Gaussian counterpart of kind 4, joined from pieces the other families own: the conv trunk and the decoder of
-// csrc/convmodel.hip, the Gaussian head (csrc/vaemodel.h), the pair KL, its seed and the evaluation's row kernel (csrc/auxvae.hip).
+// csrc/convmodel.h, the Gaussian head (csrc/vaemodel.h), the pair KL, its seed and the evaluation's row kernel (csrc/auxvae.hip).
 //
 //   per image (B rows):  x2 = 2x - 1; three trunks (conv 1 -> 16 -> 32 -> 32, k5 s2 p2) on the SAME x2, each with its own weights, one im2col of x2
 //     aux_encode   h3a = trunk_a(x2);  h4a = act(Fa h3a + fa)  [B, 800];  mu0 = M0 h4a + m0;  lv0 = L0 h4a + l0 (no clip);  z0 = mu0 + exp(lv0 / 2) eps0
@@ -31,16 +31,14 @@ enum { TR_A = 0, TR_E = 1, TR_R = 2 };      // the three trunks: aux_encode, enc
 struct AuxConvVaeLayout {
   int nd, zd, act, h = 800;
   Lin conv[3][3], afc, mean0, logvar0, efc, mean, logvar, rfc, meanp, logvarp;
-  ConvLayout dec;                  // dfc / dcv only
+  ConvDecLayout dec;
   size_t total;
   explicit AuxConvVaeLayout(const ardae_model_desc& d) : nd(d.noise_dim), zd(d.z_dim), act(d.act) {
     size_t off = 0;
-    auto trunk = [&](Lin* c) { c[0] = next_lin(off, 16, 1 * 25); c[1] = next_lin(off, 32, 16 * 25); c[2] = next_lin(off, 32, 32 * 25); };
-    trunk(conv[TR_A]); afc = next_lin(off, 800, 512); mean0 = next_lin(off, nd, 800); logvar0 = next_lin(off, nd, 800);
-    trunk(conv[TR_E]); efc = next_lin(off, 800, 512 + nd); mean = next_lin(off, zd, 800); logvar = next_lin(off, zd, 800);
-    dec.zd = zd; dec.act = act;
-    dec.decoder(off);
-    trunk(conv[TR_R]); rfc = next_lin(off, 800, 512 + zd); meanp = next_lin(off, nd, 800); logvarp = next_lin(off, nd, 800);
+    trunk_lins(off, conv[TR_A]); afc = next_lin(off, 800, 512); mean0 = next_lin(off, nd, 800); logvar0 = next_lin(off, nd, 800);
+    trunk_lins(off, conv[TR_E]); efc = next_lin(off, 800, 512 + nd); mean = next_lin(off, zd, 800); logvar = next_lin(off, zd, 800);
+    dec = ConvDecLayout(zd, act, off);
+    trunk_lins(off, conv[TR_R]); rfc = next_lin(off, 800, 512 + zd); meanp = next_lin(off, nd, 800); logvarp = next_lin(off, nd, 800);
     total = off;
   }
 };
@@ -53,37 +51,26 @@ struct AuxConvVaePacked {
   size_t conv_f[3][3], conv_b[3][3], afc_f, afc_b, mean0_f, mean0_b, logvar0_f, logvar0_b, mean_f, mean_b, logvar_f, logvar_b, meanp_f, meanp_b, logvarp_f,
       logvarp_b;
   CatLin efc, rfc;
-  ConvPacked dec;
+  ConvDecPacked dec;
   size_t tail_w2, tail_w3;         // conv_tail_kernel's weights (launch_conv_tail_pack fills them after the pack launch)
   AuxConvVaePacked(const AuxConvVaeLayout& P, PackList& pl) {
-    auto trunk = [&](int k) { for (int i = 0; i < 3; ++i) pl.pair(P.conv[k][i], conv_f[k][i], conv_b[k][i]); };
+    auto trunk = [&](int k) { trunk_panels(P.conv[k], pl, conv_f[k], conv_b[k]); };
     auto cat = [&](const Lin& l, CatLin& c) { pl.pair(l, c.i_f, c.i_b, 0, 512); pl.pair(l, c.s_f, c.s_b, 512, l.in - 512); };
     trunk(TR_A); pl.pair(P.afc, afc_f, afc_b); pl.pair(P.mean0, mean0_f, mean0_b); pl.pair(P.logvar0, logvar0_f, logvar0_b);
     trunk(TR_E); cat(P.efc, efc); pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
-    dec.decoder_panels(P.dec, pl);
+    dec = ConvDecPacked(P.dec, pl);
     trunk(TR_R); cat(P.rfc, rfc); pl.pair(P.meanp, meanp_f, meanp_b); pl.pair(P.logvarp, logvarp_f, logvarp_b);
     tail_w2 = pl.take(CT_W2); tail_w3 = pl.take(CT_W3);
   }
   explicit AuxConvVaePacked(const AuxConvVaeLayout& P, PackList&& sizing = PackList()) : AuxConvVaePacked(P, sizing) {}   // offsets only
 };
 
-// one trunk's buffers on B images; cols[0], the im2col rows of x2, is the same buffer in all three
-struct TrunkBuf { float *cols[3], *hcv[3], *inp, *dinp, *dh3, *dh2, *dh1; };
-
 struct AuxConvVaeWs {
-  ConvWs C;                        // x2, the decoder's buffers, t1 = h4 [B, 800] and dt1, z, dzq / dz (the decoder's), dinp_t / dcols3 / dcols2 (trunk_bwd's scratch)
-  TrunkBuf T[3];
-  float *h4a, *mu0, *lv0, *eps0, *epsz, *z0, *rb, *mu, *lv, *z, *eps, *kld, *rb2, *h4r, *mup, *lvp;
-  float *dmu, *dlv, *dz, *dz0, *dmu0, *dlv0, *dmup, *dlvp, *dh4r, *dh4a;      // dz: the decoder's + the auxiliary decoder's
+  float* x2; TrunkBuf T[3]; TrunkScratch S;      // cols[0], the im2col rows of x2, is the same buffer in all three trunks; ONE scratch set
+  float *h4a, *mu0, *lv0, *eps0, *epsz, *z0, *rb, *h4, *mu, *lv, *z, *eps, *kld, *rb2, *h4r, *mup, *lvp;
+  ConvDecWs D;
+  float *dmu, *dlv, *dz, *dz0, *dmu0, *dlv0, *dmup, *dlvp, *dh4r, *dh4, *dh4a;      // dz: the decoder's (D.dz) + the auxiliary decoder's
 };
-
-void trunk_carve(Bump& ws, size_t b, float* cols0, TrunkBuf& T) {
-  for (int i = 0; i < 3; ++i) {
-    T.cols[i] = i == 0 ? cols0 : ws.take(b * EH[i + 1] * EH[i + 1] * ECH[i] * 25);
-    T.hcv[i] = ws.take(b * EH[i + 1] * EH[i + 1] * ECH[i + 1]);
-  }
-  T.inp = ws.take(b * 512);
-}
 
 // which tail the decode-only path runs (ardae_conv_tail's variant 0; the mode-2 workspace is sized for the answer): conv_tail_kernel, unless
 // ARDAE_CONV_TAIL_UNFUSED=1 under ARDAE_DEBUG_KNOBS=1
@@ -91,34 +78,25 @@ bool tail_fused_default() {
   const char* knob = debug_knob("ARDAE_CONV_TAIL_UNFUSED");
   return !(knob && knob[0] == '1');
 }
-// the decode-only buffers on R rows: the decoder up to u1, and for the unfused tail c2, u2, c3 and the logits (the fused kernel writes the caller's)
-void decode_carve(Bump& ws, size_t R, bool fused, ConvWs& C) {
-  C.d1 = ws.take(R * 300); C.d2 = ws.take(R * 512); C.g0 = ws.take(R * 512); C.c1 = ws.take(R * 16 * 800); C.u1 = ws.take(R * 64 * 32);
-  if (fused) return;
-  C.c2 = ws.take(R * 64 * 400); C.u2 = ws.take(R * 225 * 16); C.c3 = ws.take(R * 225 * 25); C.logit = ws.take(R * 784);
-}
 
 // mode 0: aux_encode up to h4a (encode_stats writes mu0, lv0 to the caller); 1: forward + backward; 2: the decoder's forward on B rows of z
 void carve(const AuxConvVaeLayout& P, const AuxConvVaePacked&, Bump& ws, int B, int mode, AuxConvVaeWs& W) {
   const size_t b = (size_t)B;
-  ConvWs& C = W.C;
-  if (mode == 2) return decode_carve(ws, b, tail_fused_default(), C);
-  C.x2 = ws.take(b * 784);
-  float* cols0 = ws.take(b * 196 * 25);
-  trunk_carve(ws, b, cols0, W.T[TR_A]);
+  if (mode == 2) return conv_decoder_carve(ws, b, P.zd, ConvDecRuns{true, !tail_fused_default(), false, false}, W.D);
+  W.x2 = ws.take(b * 784);
+  trunk_carve(ws, b, W.T[TR_A]);
   W.h4a = ws.take(b * 800);
   if (mode == 0) return;
-  trunk_carve(ws, b, cols0, W.T[TR_E]); trunk_carve(ws, b, cols0, W.T[TR_R]);
+  trunk_carve(ws, b, W.T[TR_E], &W.T[TR_A]); trunk_carve(ws, b, W.T[TR_R], &W.T[TR_A]);
   W.mu0 = ws.take(b * P.nd); W.lv0 = ws.take(b * P.nd); W.eps0 = ws.take(b * P.nd); W.epsz = ws.take(b * P.zd); W.z0 = ws.take(b * P.nd);
-  W.rb = ws.take(b * 800); C.t1 = ws.take(b * 800);
-  W.mu = ws.take(b * P.zd); W.lv = ws.take(b * P.zd); W.z = C.z = ws.take(b * P.zd); W.eps = ws.take(b * P.zd); W.kld = ws.take(b);
+  W.rb = ws.take(b * 800); W.h4 = ws.take(b * 800);
+  W.mu = ws.take(b * P.zd); W.lv = ws.take(b * P.zd); W.z = ws.take(b * P.zd); W.eps = ws.take(b * P.zd); W.kld = ws.take(b);
   W.rb2 = ws.take(b * 800); W.h4r = ws.take(b * 800); W.mup = ws.take(b * P.nd); W.lvp = ws.take(b * P.nd);
-  conv_decoder_carve(ws, b, P.zd, false, C);
+  conv_decoder_carve(ws, b, P.zd, CONV_DEC_TRAIN, W.D);
   W.dmu = ws.take(b * P.zd); W.dlv = ws.take(b * P.zd); W.dz = ws.take(b * P.zd);
   W.dz0 = ws.take(b * P.nd); W.dmu0 = ws.take(b * P.nd); W.dlv0 = ws.take(b * P.nd); W.dmup = ws.take(b * P.nd); W.dlvp = ws.take(b * P.nd);
-  W.dh4r = ws.take(b * 800); C.dt1 = ws.take(b * 800); W.dh4a = ws.take(b * 800);
-  C.dinp_t = ws.take(b * 512); C.dcols3 = ws.take(b * 16 * 800); C.dcols2 = ws.take(b * 49 * 400);
-  for (TrunkBuf& T : W.T) { T.dinp = ws.take(b * 512); T.dh3 = ws.take(b * 512); T.dh2 = ws.take(b * 49 * 32); T.dh1 = ws.take(b * 196 * 16); }
+  W.dh4r = ws.take(b * 800); W.dh4 = ws.take(b * 800); W.dh4a = ws.take(b * 800);
+  for (int k = 0; k < 3; ++k) trunk_bwd_carve(ws, b, W.T[k], k == 0 ? &W.S : nullptr);
 }
 using AuxConvVaeEntry = Entry<AuxConvVaeLayout, AuxConvVaePacked, AuxConvVaeWs>;
 
@@ -128,21 +106,19 @@ constexpr int ACV_WGRAD_HINT = 14;
 // every weight-gradient problem of the backward: the decoder's eight, the z head, encode.fc's two halves and trunk, the z0 head, aux_encode.fc and
 // trunk, the auxiliary decoder's head, its fc's two halves and trunk
 void auxconvvae_wgrads(const AuxConvVaeLayout& P, const AuxConvVaeWs& W, int B, WgradList& wl, Bump& ws) {
-  const ConvWs& C = W.C;
-  auto trunk = [&](int k) { conv_trunk_wgrads(P.conv[k], W.T[k].cols, W.T[k].dh3, W.T[k].dh2, W.T[k].dh1, B, wl); };
-  conv_decoder_wgrads(P.dec, C, B, wl);
-  wl.push(B, P.zd, 800, W.dmu, C.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
-  wl.push(B, P.zd, 800, W.dlv, C.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
-  cat_wgrads(wl, B, P.efc, 512, C.dt1, W.z0, W.T[TR_E].inp);
-  trunk(TR_E);
+  conv_decoder_wgrads(P.dec, W.D, W.z, B, wl);
+  wl.push(B, P.zd, 800, W.dmu, W.h4, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
+  wl.push(B, P.zd, 800, W.dlv, W.h4, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
+  cat_wgrads(wl, B, P.efc, 512, W.dh4, W.z0, W.T[TR_E].inp);
+  conv_trunk_wgrads(P.conv[TR_E], W.T[TR_E], B, wl);
   wl.push(B, P.nd, 800, W.dmu0, W.h4a, 800, wl.g(P.mean0.w), 800, wl.g(P.mean0.b));
   wl.push(B, P.nd, 800, W.dlv0, W.h4a, 800, wl.g(P.logvar0.w), 800, wl.g(P.logvar0.b));
   wl.push(B, 800, 512, W.dh4a, W.T[TR_A].inp, 512, wl.g(P.afc.w), 512, wl.g(P.afc.b));
-  trunk(TR_A);
+  conv_trunk_wgrads(P.conv[TR_A], W.T[TR_A], B, wl);
   wl.push(B, P.nd, 800, W.dmup, W.h4r, 800, wl.g(P.meanp.w), 800, wl.g(P.meanp.b));
   wl.push(B, P.nd, 800, W.dlvp, W.h4r, 800, wl.g(P.logvarp.w), 800, wl.g(P.logvarp.b));
   cat_wgrads(wl, B, P.rfc, 512, W.dh4r, W.z, W.T[TR_R].inp);
-  trunk(TR_R);
+  conv_trunk_wgrads(P.conv[TR_R], W.T[TR_R], B, wl);
   wl.assign(ws, ACV_WGRAD_HINT);
 }
 
@@ -159,17 +135,17 @@ struct AuxConvVaeTraits {
   static GaussHead head_of(const AuxConvVaeLayout& P, const AuxConvVaePacked& K) {
     return GaussHead{800, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f, true, P.zd >= 1 && P.zd <= 64};
   }
-  static const float* hid(const AuxConvVaeWs& W) { return W.C.t1; }
+  static const float* hid(const AuxConvVaeWs& W) { return W.h4; }
   static GaussBufs bufs(const AuxConvVaeWs& W) {
-    const ConvWs& C = W.C;
-    return {W.mu, W.lv, W.z, W.eps, W.kld, C.rec_row, C.pri_row, C.logit, nullptr, C.dlogit, nullptr, C.dzq, C.dz, W.dmu, W.dlv};
+    const ConvDecWs& D = W.D;
+    return {W.mu, W.lv, W.z, W.eps, W.kld, D.rec_row, D.pri_row, D.logit, nullptr, D.dlogit, nullptr, D.dzq, D.dz, W.dmu, W.dlv};
   }
   // x2 and aux_encode up to (mu0, lv0); its trunk fills the im2col rows of x2 the other two read
   static int stats_fwd(Entry& en, const float* params, const float* packed, const float* x, int B, float* mu0, float* lv0, hipStream_t st) {
     auto& [P, K, ws, W] = en;
     const TrunkBuf& T = W.T[TR_A];
-    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.C.x2, st));
-    ARDAE_TRY(trunk_fwd(P.conv[TR_A], K.conv_f[TR_A], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st));
+    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));
+    ARDAE_TRY(trunk_fwd(P.conv[TR_A], K.conv_f[TR_A], params, packed, W.x2, T, B, P.act, st));
     ARDAE_TRY(dense_fwd(P.act, B, 800, T.inp, 512, 512, packed + K.afc_f, params + P.afc.b, W.h4a, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.mean0_f, params + P.mean0.b, mu0, st));
     return dense_fwd(ACT_NONE, B, P.nd, W.h4a, 800, 800, packed + K.logvar0_f, params + P.logvar0.b, lv0, st);
@@ -180,45 +156,41 @@ struct AuxConvVaeTraits {
     const TrunkBuf& T = W.T[TR_E];
     ARDAE_TRY(stats_fwd(en, params, packed, x, B, W.mu0, W.lv0, st));
     ARDAE_TRY(launch_reparam_fwd(W.mu0, W.lv0, W.eps0, P.nd, B, P.nd, 1, W.z0, st));
-    ARDAE_TRY(trunk_fwd(P.conv[TR_E], K.conv_f[TR_E], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st, true));
-    return cat_fwd(P.act, B, 1, 800, T.inp, 512, packed + K.efc.i_f, params + P.efc.b, W.z0, P.nd, packed + K.efc.s_f, W.rb, W.C.t1, st);
+    ARDAE_TRY(trunk_fwd(P.conv[TR_E], K.conv_f[TR_E], params, packed, W.x2, T, B, P.act, st, true));
+    return cat_fwd(P.act, B, 1, 800, T.inp, 512, packed + K.efc.i_f, params + P.efc.b, W.z0, P.nd, packed + K.efc.s_f, W.rb, W.h4, st);
   }
   // the auxiliary decoder on [h3r | z] and the pair KL, added into the head's KL rows; then the decoder
   static int decoder_fwd(Entry& en, const float* params, const float* packed, int B, hipStream_t st) {
     auto& [P, K, ws, W] = en;
     const TrunkBuf& T = W.T[TR_R];
-    ARDAE_TRY(trunk_fwd(P.conv[TR_R], K.conv_f[TR_R], params, packed, W.C.x2, T.cols, T.hcv, T.inp, B, P.act, st, true));
+    ARDAE_TRY(trunk_fwd(P.conv[TR_R], K.conv_f[TR_R], params, packed, W.x2, T, B, P.act, st, true));
     ARDAE_TRY(cat_fwd(P.act, B, 1, 800, T.inp, 512, packed + K.rfc.i_f, params + P.rfc.b, W.z, P.zd, packed + K.rfc.s_f, W.rb2, W.h4r, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4r, 800, 800, packed + K.meanp_f, params + P.meanp.b, W.mup, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, P.nd, W.h4r, 800, 800, packed + K.logvarp_f, params + P.logvarp.b, W.lvp, st));
     ARDAE_TRY(launch_pair_kld_rows(W.mu0, W.lv0, W.mup, W.lvp, B, P.nd, W.kld, 1, st));
-    return conv_decode_fwd(P.dec, K.dec, params, packed, W.z, B, W.C, st);
+    return conv_decode_fwd(P.dec, K.dec, params, packed, W.z, B, W.D, st);
   }
   struct Grads { float* grads; float beta; };
   static Grads grads_of(Entry&, const float*, const float*, float* grads, float grads_beta) { return {grads, grads_beta}; }
-  static int decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) { return conv_decoder_bwd(en.P.dec, en.K.dec, packed, en.W.C, B, st); }
-  // the auxiliary decoder back into its z columns (dz = C.dz + dh4r Wz) and into h3r (the trunk applies conv3's act')
+  static int decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) { return conv_decoder_bwd(en.P.dec, en.K.dec, packed, en.W.D, B, st); }
+  // the auxiliary decoder back into its z columns (dz = D.dz + dh4r Wz) and into h3r (the trunk applies conv3's act')
   static int aux_decoder_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) {
     auto& [P, K, ws, W] = en;
     ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmup, packed + K.meanp_b, W.dlvp, packed + K.logvarp_b, P.nd, W.h4r, W.dh4r, st));
-    return cat_bwd(B, 800, W.dh4r, P.zd, packed + K.rfc.s_b, W.C.dz, W.dz, 512, packed + K.rfc.i_b, nullptr, W.T[TR_R].dinp, st);
+    return cat_bwd(B, 800, W.dh4r, P.zd, packed + K.rfc.s_b, W.D.dz, W.dz, 512, packed + K.rfc.i_b, nullptr, W.T[TR_R].dinp, st);
   }
   // encode.fc back into its z0 columns and into h3e
   static int encode_fc_bwd(Entry& en, const float* packed, int B, Grads&, hipStream_t st) {
     auto& [P, K, ws, W] = en;
-    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.C.t1, W.C.dt1, st));
-    return cat_bwd(B, 800, W.C.dt1, P.nd, packed + K.efc.s_b, nullptr, W.dz0, 512, packed + K.efc.i_b, nullptr, W.T[TR_E].dinp, st);
+    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.h4, W.dh4, st));
+    return cat_bwd(B, 800, W.dh4, P.nd, packed + K.efc.s_b, nullptr, W.dz0, 512, packed + K.efc.i_b, nullptr, W.T[TR_E].dinp, st);
   }
   // the first head (there is no clip in this family), aux_encode.fc, the three trunks; the 28 weight gradients as two batches
   static int aux_encoder_bwd(Entry& en, const float* packed, int B, Grads& g, hipStream_t st) {
     auto& [P, K, ws, W] = en;
-    ConvWs& C = W.C;
     ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu0, packed + K.mean0_b, W.dlv0, packed + K.logvar0_b, P.nd, W.h4a, W.dh4a, st));
     ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dh4a, 800, 800, packed + K.afc_b, nullptr, W.T[TR_A].dinp, st));
-    for (int k = 0; k < 3; ++k) {
-      TrunkBuf& T = W.T[k];
-      ARDAE_TRY(trunk_bwd(K.conv_b[k], packed, T.dinp, C.dinp_t, T.hcv, T.dh3, C.dcols3, T.dh2, C.dcols2, T.dh1, B, P.act, st));
-    }
+    for (int k = 0; k < 3; ++k) ARDAE_TRY(trunk_bwd(K.conv_b[k], packed, W.T[k], W.S, B, P.act, st));
     WgradList wl(g.grads, g.beta);
     auxconvvae_wgrads(P, W, B, wl, ws);
     ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");
@@ -234,7 +206,7 @@ struct AuxConvVaeTraits {
   static void carve_eval(const AuxConvVaeLayout& P, const AuxConvVaePacked&, Bump& ws, int B, int k, AuxConvEvalWs& W) {
     const size_t b = (size_t)B;
     W.x2 = ws.take(b * 784);
-    trunk_carve(ws, b, ws.take(b * 196 * 25), W.T);
+    trunk_carve(ws, b, W.T);
     W.carve_rows(ws, B, k, P.nd, P.zd, 800, 1);
   }
   static int eval_prepare(const AuxConvVaeLayout&, const float* x, int B, AuxConvEvalWs& W, const float*& xs, hipStream_t st) {
@@ -247,17 +219,17 @@ struct AuxConvVaeTraits {
     const Lin& l = stage == 2 ? P.efc : P.rfc;
     const CatLin& c = stage == 2 ? K.efc : K.rfc;
     hid = W.t[1];
-    ARDAE_TRY(trunk_fwd(P.conv[tr], K.conv_f[tr], params, packed, xs, W.T.cols, W.T.hcv, W.T.inp, B, P.act, st, stage == 3));
+    ARDAE_TRY(trunk_fwd(P.conv[tr], K.conv_f[tr], params, packed, xs, W.T, B, P.act, st, stage == 3));
     return cat_fwd(P.act, B, k, 800, W.T.inp, 512, packed + c.i_f, params + l.b, s, l.in - 512, packed + c.s_f, W.rb, W.t[1], st);
   }
 };
 
 // u1 [R, 8, 8, 32] -> logits [R, 784]; fused: conv_tail_kernel, else the four unfused launches on c2 / u2 / c3 / logit (then copied out)
-int tail_fwd(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, const float* u1, int R, bool fused, ConvWs& C,
+int tail_fwd(const AuxConvVaeLayout& P, const AuxConvVaePacked& K, const float* params, const float* packed, const float* u1, int R, bool fused, ConvDecWs& C,
              float* logits, hipStream_t st) {
   if (fused)
     return launch_conv_tail(u1, packed + K.tail_w2, params + P.dec.dcv[1].b, packed + K.tail_w3, params + P.dec.dcv[2].b, R, P.act, logits, st);
-  ARDAE_TRY(conv_decode_tail_fwd(P.dec, K.dec, params, packed, u1, R, C.c2, C.u2, C.c3, C.logit, st));
+  ARDAE_TRY(conv_decode_tail_fwd(P.dec, K.dec, params, packed, u1, R, C, st));
   return launch_copy(C.logit, (int64_t)R * 784, logits, st);
 }
 
@@ -266,8 +238,8 @@ int auxconvvae_decode(const ardae_model_desc& d, const float* params, const floa
   AuxConvVaeEntry entry(d, workspace, wsf, R, 2);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
-  ARDAE_TRY(conv_decode_head_fwd(P.dec, K.dec, params, packed, z, R, W.C, st));
-  return tail_fwd(P, K, params, packed, W.C.u1, R, tail_fused_default(), W.C, out0, st);
+  ARDAE_TRY(conv_decode_head_fwd(P.dec, K.dec, params, packed, z, R, W.D, st));
+  return tail_fwd(P, K, params, packed, W.D.u1, R, tail_fused_default(), W.D, out0, st);
 }
 
 // the pack launch, then the fused tail's two weights
@@ -284,12 +256,7 @@ int auxconvvae_desc_check(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d->noise_dim >= 1 && d->noise_dim <= AV_NMAX, "model: noise_dim must be 1 .. %d for kind 17 (the width of z0), got %d", AV_NMAX,
                   d->noise_dim);
   ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kind 17, got %d", d->flags);
-  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTConvAuxVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
-  ARDAE_CHECK_ARG(d->h_dim == 800, "model: h_dim must be 800 for kind 17 (the width of the three fc layers), got %d", d->h_dim);
-  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 17, got %d", d->n_layers);
-  ARDAE_CHECK_ARG(d->z_dim >= 1, "model: bad dimensions (z_dim %d)", d->z_dim);
-  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
-  return 0;
+  return conv_gauss_desc_check(d, "MNISTConvAuxVAE", "the width of the three fc layers");
 }
 
 // (host pass only, as in csrc/auxmodel.hip)
@@ -316,8 +283,8 @@ extern "C" {
 size_t ardae_conv_tail_workspace_floats(const ardae_model_desc* d, int R, int variant) {
   if (!d || d->kind != 17 || auxconvvae_desc_check(d) || R <= 0 || R >= (1 << 20) || variant < 0 || variant > 2) return 0;
   if (variant == 1 || (variant == 0 && tail_fused_default())) return 0;
-  Bump ws;
-  ws.take((size_t)R * 64 * 400); ws.take((size_t)R * 225 * 16); ws.take((size_t)R * 225 * 25); ws.take((size_t)R * 784);
+  Bump ws; ConvDecWs C;
+  conv_decoder_carve(ws, (size_t)R, d->z_dim, CONV_DEC_TAIL, C);
   return ws.off;
 }
 
@@ -332,13 +299,13 @@ int ardae_conv_tail(const ardae_model_desc* d, const float* params, const float*
   if (variant == 0) variant = tail_fused_default() ? 1 : 2;
   const AuxConvVaeLayout P(*d);
   const AuxConvVaePacked K(P);
-  ConvWs C{};
+  ConvDecWs C{};
   if (variant == 2) {
     const size_t need = ardae_conv_tail_workspace_floats(d, R, 2);
     ARDAE_CHECK_ARG(workspace, "conv_tail: null pointer argument (the unfused launches need a workspace)");
     ARDAE_CHECK_ARG(workspace_floats >= need, "conv_tail: workspace too small (%zu < %zu floats)", workspace_floats, need);
     Bump ws(workspace, workspace_floats);
-    C.c2 = ws.take((size_t)R * 64 * 400); C.u2 = ws.take((size_t)R * 225 * 16); C.c3 = ws.take((size_t)R * 225 * 25); C.logit = ws.take((size_t)R * 784);
+    conv_decoder_carve(ws, (size_t)R, d->z_dim, CONV_DEC_TAIL, C);
   }
   return tail_fwd(P, K, params, packed, u1, R, variant == 1, C, logits, (hipStream_t)stream);
 }

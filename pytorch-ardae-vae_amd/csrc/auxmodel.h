@@ -5,7 +5,7 @@
 
 namespace ardae {
 extern const Family AUX_FAMILY;
-// the two reparameterisation steps shared with the hierarchical conv model (csrc/convmodel.hip)
+// the two reparameterisation steps shared with the hierarchical conv model (csrc/auxconvmodel.hip)
 //   out[r][c] = mu[g][c] + exp(lv[g][c] / 2) * eps[r * ld_eps + c],  g = r / rows_per_group   (mu, lv: [rows / rpg, cols])
 // min_std / raw (the clipped aux-resconv class, ivae/auxresconv2.py:29-36,91): out = mu + exp(lv / 2) eps + min_std (raw ? raw : eps) - `eps` carries
 // std * draw, the extra term the UNSCALED draw (raw [rows, cols], row stride ld_raw; NULL: eps itself, i.e. std = 1)

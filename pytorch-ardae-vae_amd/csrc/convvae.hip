@@ -20,59 +20,56 @@ namespace {
 struct ConvVaeLayout {
   int zd, act;
   Lin conv[3], fc, mean, logvar;   // encode.conv{1,2,3}, encode.fc [800, 512], encode.reparam.{mean_fn, logvar_fn} [zd, 800]
-  ConvLayout dec;                  // dfc / dcv only
+  ConvDecLayout dec;
   size_t total;
   explicit ConvVaeLayout(const ardae_model_desc& d) : zd(d.z_dim), act(d.act) {
     size_t off = 0;
-    conv[0] = next_lin(off, 16, 1 * 25); conv[1] = next_lin(off, 32, 16 * 25); conv[2] = next_lin(off, 32, 32 * 25);
+    trunk_lins(off, conv);
     fc = next_lin(off, 800, 512); mean = next_lin(off, zd, 800); logvar = next_lin(off, zd, 800);
-    dec.zd = zd; dec.act = act;
-    dec.decoder(off);
+    dec = ConvDecLayout(zd, act, off);
     total = off;
   }
 };
 
 struct ConvVaePacked {
   size_t conv_f[3], conv_b[3], fc_f, fc_b, mean_f, mean_b, logvar_f, logvar_b;
-  ConvPacked dec;
+  ConvDecPacked dec;
   ConvVaePacked(const ConvVaeLayout& P, PackList& pl) {
-    for (int i = 0; i < 3; ++i) pl.pair(P.conv[i], conv_f[i], conv_b[i]);
+    trunk_panels(P.conv, pl, conv_f, conv_b);
     pl.pair(P.fc, fc_f, fc_b); pl.pair(P.mean, mean_f, mean_b); pl.pair(P.logvar, logvar_f, logvar_b);
-    dec.decoder_panels(P.dec, pl);
+    dec = ConvDecPacked(P.dec, pl);
   }
   explicit ConvVaePacked(const ConvVaeLayout& P, PackList&& sizing = PackList()) : ConvVaePacked(P, sizing) {}   // offsets only
 };
 
 struct ConvVaeWs {
-  ConvWs C;                        // x2, the trunk's and the decoder's buffers; t1 = hid [B, 800], dt1 = its gradient, z, dzq / dz
-  float *mu, *lv, *eps, *kld, *dmu, *dlv;
+  float* x2; TrunkBuf T; TrunkScratch S;
+  float *hid, *mu, *lv, *z, *eps, *kld, *dmu, *dlv, *dhid;      // hid [B, 800] = act(fc(h3))
+  ConvDecWs D;
 };
 
 // mode 0: the encoder up to hid (encode_stats writes mu, lv to the caller); 1: forward + backward; 2: the decoder's forward on B rows of z
 void carve(const ConvVaeLayout& P, const ConvVaePacked&, Bump& ws, int B, int mode, ConvVaeWs& W) {
   const size_t b = (size_t)B;
-  ConvWs& C = W.C;
-  if (mode == 2) return conv_decoder_carve(ws, b, P.zd, true, C);
-  conv_trunk_carve(ws, b, C);
-  C.t1 = ws.take(b * 800);
+  if (mode == 2) return conv_decoder_carve(ws, b, P.zd, CONV_DEC_DECODE, W.D);
+  W.x2 = ws.take(b * 784);
+  trunk_carve(ws, b, W.T);
+  W.hid = ws.take(b * 800);
   if (mode == 0) return;
-  W.mu = ws.take(b * P.zd); W.lv = ws.take(b * P.zd); C.z = ws.take(b * P.zd); W.eps = ws.take(b * P.zd); W.kld = ws.take(b);
-  conv_decoder_carve(ws, b, P.zd, false, C);
-  W.dmu = ws.take(b * P.zd); W.dlv = ws.take(b * P.zd); C.dt1 = ws.take(b * 800);
-  C.dinp = ws.take(b * 512); C.dinp_t = ws.take(b * 512);
-  C.dh3 = ws.take(b * 512); C.dcols3 = ws.take(b * 16 * 800); C.dh2 = ws.take(b * 49 * 32);
-  C.dcols2 = ws.take(b * 49 * 400); C.dh1 = ws.take(b * 196 * 16);
+  W.mu = ws.take(b * P.zd); W.lv = ws.take(b * P.zd); W.z = ws.take(b * P.zd); W.eps = ws.take(b * P.zd); W.kld = ws.take(b);
+  conv_decoder_carve(ws, b, P.zd, CONV_DEC_TRAIN, W.D);
+  W.dmu = ws.take(b * P.zd); W.dlv = ws.take(b * P.zd); W.dhid = ws.take(b * 800);
+  trunk_bwd_carve(ws, b, W.T, &W.S);
 }
 using ConvVaeEntry = Entry<ConvVaeLayout, ConvVaePacked, ConvVaeWs>;
 
 // every weight-gradient problem of the backward: the decoder's eight, the two heads, fc, the three convs
 void convvae_wgrads(const ConvVaeLayout& P, const ConvVaeWs& W, int B, WgradList& wl, Bump& ws) {
-  const ConvWs& C = W.C;
-  conv_decoder_wgrads(P.dec, C, B, wl);
-  wl.push(B, P.zd, 800, W.dmu, C.t1, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
-  wl.push(B, P.zd, 800, W.dlv, C.t1, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
-  wl.push(B, 800, 512, C.dt1, C.inp, 512, wl.g(P.fc.w), 512, wl.g(P.fc.b));
-  conv_trunk_wgrads(P.conv, C.cols, C.dh3, C.dh2, C.dh1, B, wl);
+  conv_decoder_wgrads(P.dec, W.D, W.z, B, wl);
+  wl.push(B, P.zd, 800, W.dmu, W.hid, 800, wl.g(P.mean.w), 800, wl.g(P.mean.b));
+  wl.push(B, P.zd, 800, W.dlv, W.hid, 800, wl.g(P.logvar.w), 800, wl.g(P.logvar.b));
+  wl.push(B, 800, 512, W.dhid, W.T.inp, 512, wl.g(P.fc.w), 512, wl.g(P.fc.b));
+  conv_trunk_wgrads(P.conv, W.T, B, wl);
   wl.assign(ws, CONV_WGRAD_HINT);
 }
 
@@ -94,20 +91,15 @@ int convvae_decode(const ardae_model_desc& d, const float* params, const float* 
   ConvVaeEntry entry(d, workspace, wsf, R, 2);
   auto& [P, K, ws, W] = entry;
   ARDAE_CHECK_ARG(ws.ok, "model_decode: workspace too small");
-  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, z, R, W.C, st));
-  return launch_copy(W.C.logit, (int64_t)R * 784, out0, st);
+  ARDAE_TRY(conv_decode_fwd(P.dec, K.dec, params, packed, z, R, W.D, st));
+  return launch_copy(W.D.logit, (int64_t)R * 784, out0, st);
 }
 
 // the descriptor rules of kind 11 (input_dim 784, h_dim 800, n_layers 1, noise_dim 0, flags 0, z_dim >= 1, any activation but NONE)
 int convvae_desc_check(const ardae_model_desc* d) {
   ARDAE_CHECK_ARG(d->noise_dim == 0, "model: noise_dim must be 0 for kind 11 (the Gaussian posterior takes no noise input), got %d", d->noise_dim);
   ARDAE_CHECK_ARG(d->flags == 0, "model: flags must be 0 for kind 11, got %d", d->flags);
-  ARDAE_CHECK_ARG(d->input_dim == 784, "model: MNISTConvVAE is hard-wired to 28x28x1 inputs (input_dim 784), got %d", d->input_dim);
-  ARDAE_CHECK_ARG(d->h_dim == 800, "model: h_dim must be 800 for kind 11 (the width of encode.fc), got %d", d->h_dim);
-  ARDAE_CHECK_ARG(d->n_layers == 1, "model: n_layers must be 1 for kind 11, got %d", d->n_layers);
-  ARDAE_CHECK_ARG(d->z_dim >= 1, "model: bad dimensions (z_dim %d)", d->z_dim);
-  ARDAE_CHECK_ARG(d->act > ACT_NONE && d->act <= ACT_LAST, "model: unknown activation %d (relu, softplus, elu, tanh, leaky_relu, swish)", d->act);
-  return 0;
+  return conv_gauss_desc_check(d, "MNISTConvVAE", "the width of encode.fc");
 }
 
 // What gauss_vae_forward / _backward / _encode_stats (csrc/vaemodel.h) need to know of this family.
@@ -122,29 +114,28 @@ struct ConvVaeTraits {
   static GaussHead head_of(const ConvVaeLayout& P, const ConvVaePacked& K) {
     return GaussHead{800, P.zd, P.mean, P.logvar, K.mean_f, K.logvar_f, true, P.zd >= 1 && P.zd <= 64};
   }
-  static const float* hid(const ConvVaeWs& W) { return W.C.t1; }
+  static const float* hid(const ConvVaeWs& W) { return W.hid; }
   static GaussBufs bufs(const ConvVaeWs& W) {
-    const ConvWs& C = W.C;
-    return {W.mu, W.lv, C.z, W.eps, W.kld, C.rec_row, C.pri_row, C.logit, nullptr, C.dlogit, nullptr, C.dzq, C.dz, W.dmu, W.dlv};
+    const ConvDecWs& D = W.D;
+    return {W.mu, W.lv, W.z, W.eps, W.kld, D.rec_row, D.pri_row, D.logit, nullptr, D.dlogit, nullptr, D.dzq, D.dz, W.dmu, W.dlv};
   }
   // x2 = 2x - 1, the trunk, hid = act(fc(h3))
   static int encoder_fwd(Entry& e, const float* params, const float* packed, const float* x, int B, hipStream_t st) {
-    const ConvVaeLayout& P = e.P; const ConvVaePacked& K = e.K; ConvWs& C = e.W.C;
-    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, C.x2, st));           // vae/conv.py:64
-    ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, C.x2, C.cols, C.hcv, C.inp, B, P.act, st));
-    return dense_fwd(P.act, B, 800, C.inp, 512, 512, packed + K.fc_f, params + P.fc.b, C.t1, st);
+    auto& [P, K, ws, W] = e;
+    ARDAE_TRY(launch_affine(x, (int64_t)B * 784, 2.f, -1.f, W.x2, st));           // vae/conv.py:64
+    ARDAE_TRY(trunk_fwd(P.conv, K.conv_f, params, packed, W.x2, W.T, B, P.act, st));
+    return dense_fwd(P.act, B, 800, W.T.inp, 512, 512, packed + K.fc_f, params + P.fc.b, W.hid, st);
   }
   static int decoder_fwd(Entry& e, const float* params, const float* packed, int B, hipStream_t st) {
-    return conv_decode_fwd(e.P.dec, e.K.dec, params, packed, e.W.C.z, B, e.W.C, st);
+    return conv_decode_fwd(e.P.dec, e.K.dec, params, packed, e.W.z, B, e.W.D, st);
   }
   static Grads grads_of(Entry&, const float*, const float*, float* grads, float grads_beta) { return {grads, grads_beta}; }
-  static int decoder_bwd(Entry& e, const float* packed, int B, Grads&, hipStream_t st) { return conv_decoder_bwd(e.P.dec, e.K.dec, packed, e.W.C, B, st); }
+  static int decoder_bwd(Entry& e, const float* packed, int B, Grads&, hipStream_t st) { return conv_decoder_bwd(e.P.dec, e.K.dec, packed, e.W.D, B, st); }
   static int encoder_bwd(Entry& e, const float* packed, const float*, int B, Grads& g, hipStream_t st) {
     auto& [P, K, ws, W] = e;
-    ConvWs& C = W.C;
-    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, C.t1, C.dt1, st));
-    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, C.dt1, 800, 800, packed + K.fc_b, nullptr, C.dinp, st));   // fc backward-data; the trunk applies conv3's act'
-    ARDAE_TRY(trunk_bwd(K.conv_b, packed, C.dinp, C.dinp_t, C.hcv, C.dh3, C.dcols3, C.dh2, C.dcols2, C.dh1, B, P.act, st));
+    ARDAE_TRY(dense_bwd2(P.act, B, 800, W.dmu, packed + K.mean_b, W.dlv, packed + K.logvar_b, P.zd, W.hid, W.dhid, st));
+    ARDAE_TRY(dense_fwd(ACT_NONE, B, 512, W.dhid, 800, 800, packed + K.fc_b, nullptr, W.T.dinp, st));   // fc backward-data; the trunk applies conv3's act'
+    ARDAE_TRY(trunk_bwd(K.conv_b, packed, W.T, W.S, B, P.act, st));
     WgradList wl(g.grads, g.beta);
     convvae_wgrads(P, W, B, wl, ws);
     ARDAE_CHECK_ARG(ws.ok, "vae_backward: internal workspace accounting error");

@@ -1,6 +1,6 @@
 // The implicit-posterior VAEs (ardae_model_desc.kind 0 - 7: a sampler z = f(x, noise) on R = B nz rows, a decoder, the ELBO pieces).  Their algorithm
 // is written ONCE, here, as templates over a family's traits (ip_workspace_floats / ip_encode / ip_decode / ip_vae_forward / ip_vae_backward and its two
-// halves); each family file (csrc/model.hip: kinds 0 / 1, csrc/convmodel.hip: 2 and 4, csrc/auxmodel.hip: 3 / 7, csrc/resmodel.hip: 5 / 6) supplies
+// halves); each family file (csrc/model.hip: kinds 0 / 1, csrc/convmodel.hip: 2, csrc/auxconvmodel.hip: 4, csrc/auxmodel.hip: 3 / 7, csrc/resmodel.hip: 5 / 6) supplies
 // its traits and exports one Family row (host_util.h) built by ip_family<F>().  csrc/vaemodel.h is the same for the Gaussian-posterior kinds.
 //
 // The internal arena checks (`ws.ok`) of these bodies carry one text each.  They cannot fire through the ABI: the entry point has sized the arena with
