@@ -202,9 +202,10 @@ typedef struct ardae_cdae_desc {
                     * 2 / 3 = the same two WITHOUT a context (MLPGradARDAE / MLPResARDAE, see "unconditional AR-DAE" below);
                     * 6 / 7 = the plain DAEs, without a context and without the sigma input (MLPGradDAE / MLPResDAE, see "plain DAE"
                     * below); 10 / 11 = the plain CONDITIONAL DAEs, kinds 0 / 1 without the sigma input (MLPGradCDAE / MLPResCDAE, see
-                    * "plain conditional DAE" below).  4, 5, 8 and 9 are not kinds */
+                    * "plain conditional DAE" below); 13 = the conditional DAE WITHOUT an input encoder (MLPCDAE with enc_input=False, see
+                    * "reconstruction DAE" below).  4, 5, 8, 9 and 12 are not kinds */
   int input_dim;   /* z */
-  int context_dim; /* c  (kinds 0 / 1 / 10 / 11: >= 1; kinds 2 / 3 / 6 / 7: 0) */
+  int context_dim; /* c  (kinds 0 / 1 / 10 / 11 / 13: >= 1; kinds 2 / 3 / 6 / 7: 0) */
   int h_dim;
   int n_layers;    /* --cdae-n-layers */
   int act;         /* any ARDAE_ACT_* but NONE (with a piecewise linear one mlp-grad's second-order terms are zero)  */
@@ -319,6 +320,50 @@ int ardae_latent_noise_perturb_draw_ok(int nz, int nstd, int z);
 int ardae_latent_noise_perturb_draw(const float* latent, const float* z0, int B, int nz, int nstd, int z, float std_scale, float sigma,
                                     const void* dae_state, uint64_t seed, uint64_t offset_eps, uint64_t first_row, float* xbar, float* sigma_out,
                                     float* eps_out, void* stream);
+
+/* ---- reconstruction DAE (models/dae/mlp.py: DAE :21-82 = MLPDAE, ConditionalDAE :85-193 = MLPCDAE): kinds 7 / 11 / 13 --------------------
+ * The classical denoising autoencoders: x_recon = main(x_bar), loss = mse(x_recon, x) (dae/mlp.py:49-70,131-165), and the score read off the
+ * residual, glogprob = (main(x) - x) / std^2 (:72-82,167-193).  The loss layer is not new: ardae_cdae_loss_grads forms rho = sigma y + eps, and
+ * with sigma = 1, eps = -x that is y - x exactly, so loss and gradients on a given x_bar are ardae_cdae_loss_grads of the res-kind network on
+ * (x_bar, 1, -x) with score_out = x_recon.  MLPDAE's network is kind 7's (`main.*`), MLPCDAE's with enc_input=True kind 11's.
+ *
+ * ardae_cdae_desc.kind 13: ConditionalDAE with enc_input=False (its default), the conditional direct-output network WITHOUT an input encoder:
+ * the last MLP reads the perturbed sample itself beside the encoded context (dae/mlp.py:116-120,151-159).  Parameters in named_parameters()
+ * order: ctx_encode.*, dae.*, with dae.layers.0.weight [h, z + h] = [W1x | W1c]; no sigma column.  h_1 = act(W1x x_bar + [W1c c_L + d_1](b)): the
+ * context half enters as a row bias, once per context row.  context_dim >= 1, ctx non-NULL, N = B * S rows in the caller's factorisation (one
+ * context per row: B = N, S = 1).  ardae_cdae_param_floats / packed_floats / workspace_floats / pack / loss_grads / score take it; the update is
+ * kind 11's with every inp_encode term removed (k1 = z): one ordinary backward from the seed, W1x's gradient = ghat_1 (x) x_bar, W1c's through the
+ * per-image reduction over S.  ardae_cdae_score gives the network's output and ignores `sigma`.  ardae_cdae_perturb_fused_ok and
+ * ardae_dae_perturb_fused_ok are 0 for it.  12 is not a kind (an even number would be an energy kind).
+ *
+ * ardae_philox_uniform_at: torch.rand_like of add_uniform_noise (dae/mlp.py:16-18): the [0, 1) map of ardae_philox_uniform, (word >> 8) 2^-24,
+ * keyed like ardae_philox_normal_at - elements [first_element, first_element + n) of the draw (seed, offset + state.rng_offset), the same numbers
+ * for any partition.  first_element and n may be any values (a first or last counter may be partial).  state may be NULL. */
+int ardae_philox_uniform_at(float* out, int64_t n, uint64_t seed, uint64_t offset, const void* state, uint64_t first_element, void* stream);
+/* ardae_recon_perturb: add_noise (dae/mlp.py:12-18,40-47) on a broadcast batch with ONE noise level: row (b, j) of the N = B * nsigma rows reads
+ * x[b] (the broadcast is never written).  noise 0 (gaussian): xbar = fma(s, draw, x); noise 1 (uniform, draw in [0, 1)):
+ * xbar = x + ((2 s) draw - s), each operation rounded on its own, the reference's order.  s is the f32 in bytes 24..27 of `dae_state`
+ * (ardae_dae_state_advance) when that is non-NULL, else the argument `sigma`.  It also writes what the loss layer reads: sigma_out[r] = 1 and
+ * target_out[r, k] = -x[b, k].  draw / xbar / target_out [N, d], sigma_out [N].
+ * ardae_recon_perturb_draw: the same with the draw made in the kernel: element i of the call's rows = element first_row * d + i of the draw
+ * (seed, offset [+ dae_state's rng_offset]), keyed exactly like ardae_philox_normal_at / ardae_philox_uniform_at (first_row a multiple of 4),
+ * written to draw_out; xbar / sigma_out / target_out / draw_out hold the bits of the stand-alone draw followed by ardae_recon_perturb.  64-row
+ * tiles, a last partial tile is masked. */
+int ardae_recon_perturb(const float* x /* [B, d] */, const float* draw /* [B*nsigma, d] */, int B, int nsigma, int d, int noise, float sigma,
+                        const void* dae_state, float* xbar, float* sigma_out, float* target_out, void* stream);
+int ardae_recon_perturb_draw(const float* x, int B, int nsigma, int d, int noise, float sigma, const void* dae_state, uint64_t seed, uint64_t offset,
+                             uint64_t first_row, float* xbar, float* sigma_out, float* target_out, float* draw_out, void* stream);
+/* The conditional engine's counterparts, next to ardae_latent_noise_perturb(_draw): u = std_scale (latent[b, i] - z0[b]), rounded as
+ * ardae_center_scale rounds it (ivae_ardae.py:753-767); xbar = perturb(u) as above, target_out = -u, sigma_out = 1; rows (b, i, j) of the
+ * N = B * nz * nstd rows.  latent [B, nz, z], z0 [B, z], draw / xbar / target_out [N, z]. */
+int ardae_latent_recon_perturb(const float* latent, const float* z0, const float* draw, int B, int nz, int nstd, int z, float std_scale, int noise,
+                               float sigma, const void* dae_state, float* xbar, float* sigma_out, float* target_out, void* stream);
+int ardae_latent_recon_perturb_draw(const float* latent, const float* z0, int B, int nz, int nstd, int z, float std_scale, int noise, float sigma,
+                                    const void* dae_state, uint64_t seed, uint64_t offset, uint64_t first_row, float* xbar, float* sigma_out,
+                                    float* target_out, float* draw_out, void* stream);
+/* glogprob's last line (dae/mlp.py:80-81,191-192): out = (recon - x) / s^2 on [n, d]; s from `dae_state` (bytes 24..27) when that is non-NULL,
+ * else `sigma` - read on the device, so the caller needs no host synchronisation.  out may alias recon. */
+int ardae_recon_score(const float* recon, const float* x, int n, int d, float sigma, const void* dae_state, float* out, void* stream);
 
 /* ---- energy-function fitting (notebooks/ardae_fit.ipynb): energies, the implicit generator, torch.optim.Adam + StepLR -------------
  * One iteration of the notebook: num_dae_updates AR-DAE updates, each on a fresh sample of the generator, then one generator update

@@ -1,7 +1,7 @@
 """MI355X-native engine for the AR-DAE-VAE inner training loop (reference: ivae_ardae.py:546-846).
 
 Drop-in surface (same names as the reference's `models` / `utils` re-exports used by ivae_ardae.py):
-    MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVAE, MNISTConvAuxIPVAE, ResConvIPVAE, MNISTResConvAuxIPVAE, MNISTResConvAuxIPVAEClipped, MLPGradCARDAE, MLPResCARDAE, MLPGradARDAE, MLPResARDAE, MLPGradDAE, MLPResDAE, MLPGradCDAE, MLPResCDAE, Adam, RMSprop, normal_energy_func, annealing_func,
+    MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVAE, MNISTConvAuxIPVAE, ResConvIPVAE, MNISTResConvAuxIPVAE, MNISTResConvAuxIPVAEClipped, MLPGradCARDAE, MLPResCARDAE, MLPGradARDAE, MLPResARDAE, MLPGradDAE, MLPResDAE, MLPGradCDAE, MLPResCDAE, MLPDAE, MLPCDAE, Adam, RMSprop, normal_energy_func, annealing_func,
     Polyak, SWA (torchcontrib.optim wrappers of --m-weight-avg: use_buf() / use_sgd() around an evaluation)
 Fused path:
     ArdaeEngine, TrainConfig  -- one train step as a straight line of C-ABI calls (what bench.py times)
@@ -9,6 +9,8 @@ Fused path:
     ArdaeScoreEngine, DaeConfig -- the same engine on a plain DAE (MLPGradDAE / MLPResDAE) with notebooks/dae_toy.ipynb's annealed noise level
     ArdaeCondScoreEngine, ScoreConfig | DaeConfig -- the cDAE update of ivae_ardae.py:752-779 on samples of the caller's own amortised sampler as one captured unit, for a conditional
                                  AR-DAE (MLPGradCARDAE / MLPResCARDAE) or a plain conditional DAE (MLPGradCDAE / MLPResCDAE); score() = the entropy gradient of :826-834
+    ArdaeScoreEngine | ArdaeCondScoreEngine, DaeConfig -- the same two engines on the reconstruction DAEs of models/dae/mlp.py (MLPDAE; MLPCDAE): gaussian or uniform noise at the
+                                 annealed level, loss = mse(x_recon, x) through the same loss layer; score() = (x_recon - x) / sigma^2
     ArdaeFitEngine, FitConfig, Generator, energy -- a whole iteration of notebooks/ardae_fit.ipynb (implicit generator fitted to an energy function, the
                                  AR-DAE score as its entropy gradient) as one captured unit; utils/energy.py's functions on the device
     IwaeEvaluator, ArdaeEngine.evaluate_iws -- evaluate_iws of the recipes: the IWAE bound of a whole set in large chunks, the proposal fused into one
@@ -30,7 +32,7 @@ from . import rng  # noqa: F401
 from . import data  # noqa: F401
 from . import energy  # noqa: F401
 from .rng import manual_seed  # noqa: F401
-from .modules import (MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVAE, MNISTConvAuxIPVAE, ResConvIPVAE, MNISTResConvAuxIPVAE, MNISTResConvAuxIPVAEClipped, MLPGradCARDAE, MLPResCARDAE, MLPGradARDAE, MLPResARDAE, MLPGradDAE, MLPResDAE, MLPGradCDAE, MLPResCDAE, ARDAE, DAE, ConditionalDAE, Generator, ImplicitPosteriorVAE, ConditionalARDAE,  # noqa: F401
+from .modules import (MNISTIPVAE, ToyIPVAE, ToyAuxIPVAE, ConvIPVAE, MNISTAuxIPVAE, MNISTConvAuxIPVAE, ResConvIPVAE, MNISTResConvAuxIPVAE, MNISTResConvAuxIPVAEClipped, MLPGradCARDAE, MLPResCARDAE, MLPGradARDAE, MLPResARDAE, MLPGradDAE, MLPResDAE, MLPGradCDAE, MLPResCDAE, MLPDAE, MLPCDAE, ReconDAE, ReconConditionalDAE, ARDAE, DAE, ConditionalDAE, Generator, ImplicitPosteriorVAE, ConditionalARDAE,  # noqa: F401
                       normal_energy_func, GaussianVAE, MNISTVAE, ToyVAE, MNISTConvVAE, MNISTResConvVAE, MNISTAuxVAE, ToyAuxVAE, MNISTConvAuxVAE, MNISTResConvAuxVAE)
 from .optim import Adam, RMSprop, Polyak, SWA  # noqa: F401
 from .engine import ArdaeEngine, TrainConfig, annealing_func  # noqa: F401

@@ -1,5 +1,5 @@
 // AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1), unconditional (kind 2 / 3), plain DAE (kind 6 / 7) and plain conditional DAE
-// (kind 10 / 11): forward, score pass, DAE loss, double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
+// (kind 10 / 11 / 13): forward, score pass, DAE loss, double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
 //
 // Maths: SURVEY.md Appendix A (closed form of models/graddae/mlp.py:400-444 under autograd), notation below.
 //   rows i=1..N (N = B*S), image b(i) = i / S
@@ -27,8 +27,12 @@
 // sigma: W1 = W1x [h, z], no w1s, h_1 = sp(W1x xbar + d_1).  The loss keeps its per-row sigma.
 // The plain conditional DAEs (kinds 10 / 11; models/graddae/mlp.py:210-339, models/resdae/mlp.py:170-284) relate to kinds 0 / 1 as 6 / 7 do to 2 / 3:
 // W1 = [W1a | W1c] [h, 2h], no w1s, h_1 = sp(W1a a_L + [W1c c_L + d_1](b)).  The loss keeps its per-row sigma.
-// In the code: `cond` marks what exists for kinds 0 / 1 / 10 / 11 only, `grad` what the energy kinds (0 / 2 / 6 / 10) add to the res kinds,
-// `has_sigma` the sigma column of W1 (kinds 0 - 3).
+// The conditional DAE without an input encoder (kind 13; models/dae/mlp.py:85-193 with enc_input=False) is kind 11 whose energy MLP reads the
+// perturbed rows themselves beside the encoded context: a_L := xbar, W1 = [W1x | W1c] [h, z + h], h_1 = sp(W1x xbar + [W1c c_L + d_1](b)).  Every line
+// that names A_l, a_l or phat_l drops out: one ordinary backward from gbar, W1x's gradient = qhat_1 (x) xbar, W1c's through Qsum as before.
+// (Kinds 7 / 11 / 13 also serve the reconstruction DAEs of models/dae/mlp.py: with sigma = 1 and eps = -x the loss layer's rho is y - x.)
+// In the code: `cond` marks what exists for kinds 0 / 1 / 10 / 11 / 13 only, `enc_inp` the input encoder (cond without kind 13), `grad` what the
+// energy kinds (0 / 2 / 6 / 10) add to the res kinds, `has_sigma` the sigma column of W1 (kinds 0 - 3).
 #include <vector>
 
 #include "ardae_hip.h"
@@ -39,25 +43,26 @@
 namespace ardae {
 namespace {
 
-bool cond_kind(int kind) { return kind < 2 || kind == 10 || kind == 11; }
+bool cond_kind(int kind) { return kind < 2 || kind == 10 || kind == 11 || kind == 13; }
 
 struct CdaeLayout {
   int kind, z, c, h, L, act;
-  bool cond, grad, has_sigma;
-  std::vector<Lin> ctx, inp, neg;   // ctx/inp (cond): L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae / main)
+  bool cond, enc_inp, grad, has_sigma;
+  std::vector<Lin> ctx, inp, neg;   // ctx (cond) / inp (enc_inp): L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae / main)
   size_t total = 0;
-  // W1 = neg[0] is [W1a | W1c | w1s] (cond) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then (has_sigma) the sigma column
-  int k1() const { return cond ? h : z; }
-  int sigma_col() const { return cond ? 2 * h : z; }
+  // W1 = neg[0] is [W1a | W1c | w1s] (enc_inp), [W1x | W1c] (kind 13) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then
+  // (has_sigma) the sigma column
+  int k1() const { return enc_inp ? h : z; }
+  int sigma_col() const { return cond ? k1() + h : z; }
 
   explicit CdaeLayout(const ardae_cdae_desc& d)
-      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(cond_kind(d.kind)), grad(d.kind % 2 == 0), has_sigma(d.kind < 6) {
+      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(cond_kind(d.kind)), enc_inp(cond && d.kind != 13), grad(d.kind % 2 == 0), has_sigma(d.kind < 6) {
     size_t off = 0;
     auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
-    if (cond) {
+    if (cond)
       for (int l = 0; l < L; ++l) add(ctx, h, l == 0 ? c : h);
+    if (enc_inp)
       for (int l = 0; l < L; ++l) add(inp, h, l == 0 ? z : h);
-    }
     for (int l = 0; l < L; ++l) add(neg, h, l == 0 ? sigma_col() + (has_sigma ? 1 : 0) : h);
     add(neg, grad ? 1 : z, h);
     total = off;
@@ -66,18 +71,18 @@ struct CdaeLayout {
 
 // offsets into the packed-weight buffer
 struct PackedLayout {
-  std::vector<size_t> ctx_f, ctx_b, inp_f, inp_b, neg_f, neg_b;   // ctx / inp: cond only; neg_*[0] unused (W1 is split below)
+  std::vector<size_t> ctx_f, ctx_b, inp_f, inp_b, neg_f, neg_b;   // ctx: cond only, inp: enc_inp only; neg_*[0] unused (W1 is split below)
   size_t w1_f, w1_b, w1c_f, w1c_b, w1s;                           // w1: W1's N-row panel (W1a | W1x); w1c: cond only; w1s: has_sigma only
   size_t fc_f, fc_b;   // res kinds only (dae.fc / main.fc [z,h])
   PackedLayout(const CdaeLayout& P, PackList& pl) {
     const size_t L = P.L;
     for (auto* v : {&ctx_f, &ctx_b, &inp_f, &inp_b, &neg_f, &neg_b}) v->assign(L, 0);
     if (P.cond)
-      for (size_t l = 0; l < L; ++l) { pl.pair(P.ctx[l], ctx_f[l], ctx_b[l]); pl.pair(P.inp[l], inp_f[l], inp_b[l]); }
+      for (size_t l = 0; l < L; ++l) { pl.pair(P.ctx[l], ctx_f[l], ctx_b[l]); if (P.enc_inp) pl.pair(P.inp[l], inp_f[l], inp_b[l]); }
     const Lin& W1 = P.neg[0];
     pl.pair(W1, w1_f, w1_b, 0, P.k1());
     w1c_f = w1c_b = 0;
-    if (P.cond) pl.pair(W1, w1c_f, w1c_b, P.h, P.h);
+    if (P.cond) pl.pair(W1, w1c_f, w1c_b, P.k1(), P.h);
     w1s = P.has_sigma ? pl.take(P.h) : 0;            // the sigma column, gathered by cdae_pack_impl
     for (size_t l = 1; l < L; ++l) pl.pair(P.neg[l], neg_f[l], neg_b[l]);
     fc_f = fc_b = 0;
@@ -88,10 +93,10 @@ struct PackedLayout {
 
 int desc_ok(const ardae_cdae_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "cdae: desc is NULL");
-  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7 || d->kind == 10 || d->kind == 11,
+  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7 || d->kind == 10 || d->kind == 11 || d->kind == 13,
                   "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad), 3 (unconditional res), 6 (plain DAE grad), 7 (plain DAE res), "
-                  "10 (plain conditional DAE grad) or 11 (plain conditional DAE res)");
-  ARDAE_CHECK_ARG(!cond_kind(d->kind) || d->context_dim >= 1, "cdae: kinds 0 / 1 / 10 / 11 need context_dim >= 1 (got %d)", d->context_dim);
+                  "10 (plain conditional DAE grad), 11 (plain conditional DAE res) or 13 (conditional DAE without an input encoder)");
+  ARDAE_CHECK_ARG(!cond_kind(d->kind) || d->context_dim >= 1, "cdae: kinds 0 / 1 / 10 / 11 / 13 need context_dim >= 1 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(cond_kind(d->kind) || d->context_dim == 0, "cdae: kinds 2 / 3 / 6 / 7 have no context: context_dim must be 0 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->n_layers >= 1, "cdae: bad dimensions");
   ARDAE_CHECK_ARG(d->n_layers <= 6, "cdae: n_layers <= 6 supported (3L+1 gradient problems per batch)");
@@ -108,12 +113,12 @@ struct CdaeWs {
   int ltiles, ctiles;
 };
 
-// The conditional kinds take every buffer whichever of the two reads it (kinds 1 / 11 leave e, r, tau, tau', pbar and cs_taup unused); the
-// unconditional kinds take what they read, so hh[1] is the arena's first piece (the fused front end of dae_perturb.hip fills it).
+// Kinds 0 / 1 / 10 / 11 take every buffer whichever of the two reads it (kinds 1 / 11 leave e, r, tau, tau', pbar and cs_taup unused); kind 13 and
+// the unconditional kinds take what they read, so hh[1] is the arena's first piece (the fused front end of dae_perturb.hip fills it).
 void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, CdaeWs& W) {
   const int N = B * S, h = P.h, L = P.L, z = P.z;
   const size_t Bh = (size_t)B * h, Nh = (size_t)N * h;
-  const bool cond = P.cond, score = P.cond || P.grad;
+  const bool cond = P.cond, enc = P.enc_inp, score = enc || P.grad;
   for (auto* v : {&W.cL, &W.a, &W.hh, &W.e, &W.r, &W.tau, &W.taup, &W.pbar, &W.qbar, &W.chat}) v->assign(L + 1, nullptr);
   W.cb = W.chain_cnt = W.Qsum = W.cs_taup = nullptr;
   if (cond) {
@@ -121,23 +126,23 @@ void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, Cd
     W.cb = ws.take(Bh);
   }
   for (int l = 1; l <= L; ++l) {
-    if (cond) W.a[l] = ws.take(Nh);
+    if (enc) W.a[l] = ws.take(Nh);
     W.hh[l] = ws.take(Nh);
     if (score) W.e[l] = ws.take(Nh);
-    if (cond) W.r[l] = ws.take(Nh);
+    if (enc) W.r[l] = ws.take(Nh);
   }
   if (need_grads)
     for (int l = 1; l <= L; ++l) {
-      if (cond) W.tau[l] = ws.take(Nh);
+      if (enc) W.tau[l] = ws.take(Nh);
       if (score) W.taup[l] = ws.take(Nh);
-      if (cond) W.pbar[l] = ws.take(Nh);
+      if (enc) W.pbar[l] = ws.take(Nh);
       W.qbar[l] = ws.take(Nh);
     }
   W.gbar = ws.take((size_t)N * z);
   W.gbuf = ws.take((size_t)N * z);
   W.ltiles = linear_row_tiles(N, z) * linear_col_panels(N, z);
   W.tile_loss = ws.take(W.ltiles);
-  if (cond) W.chain_cnt = ws.take((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));   // row-block counters of the per-image chain launch (score pass)
+  if (enc) W.chain_cnt = ws.take((size_t)LINEAR_SMALL_CHAIN_COUNTER_WORDS * ((N + 15) / 16));   // row-block counters of the per-image chain launch (score pass)
   W.ctiles = linear_row_tiles(N, h);
   if (!need_grads) return;
   if (cond) {
@@ -164,11 +169,11 @@ void cdae_wgrads(const CdaeLayout& P, const CdaeWs& W, const float* xbar, const 
     if (P.grad) wl.push2(N, h, I, s, t, I, ghat, x, I, 1, rs, wl.g(lin.w), ld, wl.g(lin.b), out_rs, ld_rs);
     else wl.push2(N, h, I, ghat, x, I, nullptr, nullptr, 0, 0, rs, wl.g(lin.w), ld, wl.g(lin.b), out_rs, ld_rs);
   };
-  if (P.cond)
+  if (P.enc_inp)
     for (int l = 1; l <= L; ++l)   // inp A_l: r_l (x) tau_{l-1}  +  phat_l (x) a_{l-1}   (tau_0 = gbar, a_0 = xbar)
       push(P.inp[l - 1], l == 1 ? z : h, r[l], l == 1 ? W.gbar : tau[l - 1], phat[l], l == 1 ? xbar : a[l - 1], false);
-  push(P.neg[0], P.k1(), e[1], P.cond ? tau[L] : W.gbar, qhat[1], P.cond ? a[L] : xbar, true);                                  // W1a | W1x, d_1, w1s
-  if (P.cond) wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + h), ld1, nullptr, nullptr, 0);   // W1c
+  push(P.neg[0], P.k1(), e[1], P.enc_inp ? tau[L] : W.gbar, qhat[1], P.enc_inp ? a[L] : xbar, true);                                  // W1a | W1x, d_1, w1s
+  if (P.cond) wl.push2(B, h, h, W.Qsum, W.cL[L], h, nullptr, nullptr, 0, -1, nullptr, wl.g(gW1 + P.k1()), ld1, nullptr, nullptr, 0);   // W1c
   for (int l = 2; l <= L; ++l)     // W_l: e_l (x) tau'_{l-1} + qhat_l (x) h_{l-1}
     push(P.neg[l - 1], h, e[l], taup[l - 1], qhat[l], hh[l - 1], false);
   if (!P.grad) wl.push2(N, z, h, W.gbar, hh[L], h, nullptr, nullptr, 0, 0, nullptr, wl.g(P.neg[L].w), h, wl.g(P.neg[L].b), nullptr, 0);   // dae.fc / main.fc
@@ -176,7 +181,7 @@ void cdae_wgrads(const CdaeLayout& P, const CdaeWs& W, const float* xbar, const 
     for (int l = 1; l <= L; ++l)   // ctx C_l: chat_l (x) c_{l-1}
       wl.push2(B, h, P.ctx[l - 1].in, W.chat[l], l == 1 ? ctx : W.cL[l - 1], l == 1 ? P.c : h, nullptr, nullptr, 0, 0, nullptr,
                wl.g(P.ctx[l - 1].w), P.ctx[l - 1].in, wl.g(P.ctx[l - 1].b), nullptr, 0);
-  wl.assign(ws, P.cond ? 3 * L + 1 : L + 1);   // the split hint: the list's length (res kinds keep their grad sibling's)
+  wl.assign(ws, P.cond ? 3 * L + 1 : L + 1);   // the split hint: the list's length (res kinds keep their grad sibling's, kind 13 kind 11's)
 }
 
 // dry run of cdae_carve() and the weight-gradient list on a null arena
@@ -248,6 +253,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   ARDAE_TRY(desc_ok(d));
   const CdaeLayout P(*d);
   const bool cond = P.cond, grad = P.grad;
+  const bool enc = P.enc_inp;
   ARDAE_CHECK_ARG(cond || ctx == nullptr, "cdae: kinds 2 / 3 / 6 / 7 take no context: ctx must be NULL");
   // the plain DAEs' score does not read sigma (DAE.glogprob / ConditionalDAE.glogprob ignore std); their loss layer does
   ARDAE_CHECK_ARG(params && packed && xbar && (sigma || (!P.has_sigma && !need_grads)) && (ctx || !cond) && workspace, "cdae: null pointer argument");
@@ -266,7 +272,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   const std::vector<float*>&cL = W.cL, &a = W.a, &hh = W.hh, &e = W.e, &r = W.r, &tau = W.tau, &taup = W.taup, &pbar = W.pbar, &qbar = W.qbar, &chat = W.chat;
   float *cb = W.cb, *gbar = W.gbar, *Qsum = W.Qsum, *cs_taup = W.cs_taup;
   float* g = score_out ? score_out : W.gbuf;
-  const float* x1 = cond ? a[L] : xbar;        // the energy MLP's input rows [N, k1]
+  const float* x1 = enc ? a[L] : xbar;        // the energy MLP's input rows [N, k1]
   const float* wfc = params + P.neg[L].w;      // grad kinds: w [1,h]
 
   // ------------------------------------------------------------------ the layers of the forward and of the score pass
@@ -318,7 +324,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   }
   {
     LayerRun run(EPI_ACT, st);      // the forward N-row layers: A_1 (2) .. A_L, then W_1 (2) .. W_L
-    if (cond && !first_ready && linear_small_eligible(inp_layer(1), EPI_ACT)) {
+    if (enc && !first_ready && linear_small_eligible(inp_layer(1), EPI_ACT)) {
       // few rows: the two encoders are independent chains of per-image launches - level l of both in ONE launch
       for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear_pair(ctx_layer(l), inp_layer(l), EPI_ACT, st));
       ARDAE_TRY(launch_linear(ctx_bias(), EPI_ACT, st));
@@ -327,7 +333,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
       // layers of both networks then form ONE run (round 4: one multi-layer launch instead of two with a per-image launch between them)
       for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear(ctx_layer(l), EPI_ACT, st));
       ARDAE_TRY(launch_linear(ctx_bias(), EPI_ACT, st));
-      for (int l = first_ready ? 2 : 1; l <= L; ++l) run.add(inp_layer(l));
+      if (enc) for (int l = first_ready ? 2 : 1; l <= L; ++l) run.add(inp_layer(l));
     }
     for (int l = !cond && first_ready ? 2 : 1; l <= L; ++l) run.add(energy_layer(l));
     ARDAE_TRY(run.flush());
@@ -378,7 +384,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
       if (grad) { A.Q = qbar[l - 1]; A.ldQ = h; }
       run.add(lin_args(act, N, h, qhat[l], h, h, packed + K.neg_b[l - 1], A));
     }
-    if (cond)
+    if (enc)
       for (int l = L + 1; l >= 2; --l) {   // phat_{l-1} from phat_l, with phat_{L+1} A := qhat_1 W1a
         LinArgs A{}; A.S = a[l - 1]; A.ldS = h; A.Y = phat[l - 1]; A.ldY = h;
         if (grad) { A.Q = pbar[l - 1]; A.ldQ = h; }

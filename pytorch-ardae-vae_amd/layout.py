@@ -233,6 +233,15 @@ def cdae_plain_spec(kind, input_dim, context_dim, h_dim, n_layers):
     raise NotImplementedError(kind)
 
 
+def recon_cdae_spec(input_dim, context_dim, h_dim, n_layers, enc_input):
+    """The reconstruction conditional DAE (models/dae/mlp.py:116-120, enc_ctx=True): ctx_encode.*, inp_encode.* (enc_input only), dae.*.
+    enc_input=True is cdae_plain_spec('res', ...) (ardae_cdae_desc.kind 11); enc_input=False (the reference's default) has no input encoder and
+    `dae.layers.0.weight` is [h, d + h] = [W1x | W1c] (kind 13).  With n_layers = 1 each encoder is a single `fc`."""
+    if enc_input:
+        return cdae_plain_spec("res", input_dim, context_dim, h_dim, n_layers)
+    return _mlp("ctx_encode.", context_dim, h_dim, h_dim, n_layers - 1) + _mlp("dae.", input_dim + h_dim, h_dim, input_dim, n_layers)
+
+
 def dae_spec(kind, input_dim, h_dim, n_layers):
     """The unconditional AR-DAE (models/graddae/mlp.py:137, models/resdae/mlp.py:111): one MLP on [x_bar | sigma]; `layers.0.weight`
     is [h, d + 1] = [W1x | w1s].  ardae_cdae_desc.kind 2 ('grad') / 3 ('res')."""

@@ -5,6 +5,7 @@
     net.MLPGradARDAE / net.MLPResARDAE   <- models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167
     net.MLPGradDAE / net.MLPResDAE       <- models/graddae/mlp.py:39-116, models/resdae/mlp.py:27-90
     net.MLPGradCDAE / net.MLPResCDAE     <- models/graddae/mlp.py:210-339, models/resdae/mlp.py:170-284
+    net.MLPDAE / net.MLPCDAE             <- models/dae/mlp.py:21-82, :85-193 (the reconstruction DAEs: gaussian or uniform noise)
     net.MNISTVAE / net.ToyVAE            <- models/vae/mnist.py:99-220, models/vae/toy.py:99-213 (the Gaussian-posterior baselines of vae.py)
     net.MNISTConvVAE                     <- models/vae/conv.py:138-260 (`vae.py --model conv`)
     net.MNISTResConvVAE                  <- models/vae/resconv.py:122-240 (`vae.py --model resconv`)
@@ -429,6 +430,165 @@ class MLPGradDAE(DAE):
 class MLPResDAE(DAE):
     """models/resdae/mlp.py::DAE (exported as MLPResDAE, models/__init__.py): the MLP's output is the score."""
     _kind = "res"
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The reconstruction DAEs of models/dae/mlp.py: x_recon = net(x_bar), loss = mse(x_recon, x), score = (net(x) - x) / std^2
+# ---------------------------------------------------------------------------------------------------------------
+class _ReconLossFn(torch.autograd.Function):
+    """forward = (loss, x_recon) of DAE.forward / ConditionalDAE.forward (dae/mlp.py:54-70,136-165) on a given x_bar: the res kinds' loss
+    layer on (x_bar, ones, -x) - rho = 1 * y + (-x) is y - x exactly - with the network's output taken as score_out.  The backward runs in
+    the same ABI call, so backward() only scales; x_recon carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, mod, xbar, ones, target, context, B, S, *params):
+        d = mod._desc
+        ws = mod._ws(L.query("ardae_cdae_workspace_floats", d, B, S, 1))
+        loss = torch.empty(1, device=xbar.device)
+        grads = torch.zeros_like(mod._flat)
+        recon = torch.empty_like(xbar)
+        L.call("ardae_cdae_loss_grads", d, mod._flat, mod._packed_weights(), xbar, ones, target, context, B, S, ws, ws.numel(), loss, grads, recon)
+        ctx.mod, ctx.grads = mod, grads
+        ctx.mark_non_differentiable(recon)
+        return loss.reshape(()), recon
+
+    @staticmethod
+    def backward(ctx, gloss, _grecon):
+        return (None,) * 7 + tuple(g * gloss for g in ctx.mod.param_views(ctx.grads))
+
+
+class _ReconNet(_ScoreNet):
+    """What ReconDAE and ReconConditionalDAE share: the refusals, add_noise, and the two calls around the network."""
+    _kind = "res"                # the network's output is a point of the input space: the res kinds' networks (kind 7 / 11 / 13)
+    _recon = True                # the engines tell a reconstruction DAE from a residual one by this: the network kind cannot
+    NOISE = {"gaussian": 0, "uniform": 1}      # ardae_recon_perturb's `noise`
+
+    @classmethod
+    def _check_recon(cls, noise_type, nonlinearity, num_hidden_layers, also=None):
+        if noise_type not in cls.NOISE:
+            raise NotImplementedError(f"noise_type {noise_type!r}: add_noise (dae/mlp.py:40-47) knows 'gaussian' and 'uniform'")
+        cls._check("gaussian", nonlinearity, also)
+        if num_hidden_layers < 1:
+            raise NotImplementedError("num_hidden_layers >= 1 (without a hidden layer the denoiser is linear in its input)")
+
+    def add_noise(self, input, std=None, eps=None):
+        """x_bar of dae/mlp.py:12-18,40-47 for rows [N, d].  `eps`: the raw draw [N, d] - standard normals, or uniforms in [0, 1); default: the
+        library's Philox stream."""
+        return self._perturb(_f32c(input).view(-1, self.input_dim), std, eps)[0]
+
+    def _perturb(self, x, std, eps):
+        """-> x_bar, ones [N], -x: what the loss layer reads.  std: None (self.std), a Python number, or a tensor that broadcasts to [N, 1]."""
+        N, d, noise = x.size(0), self.input_dim, self.NOISE[self.noise_type]
+        std = self.std if std is None else std
+        if eps is None:
+            eps = (rng.uniform if noise else rng.normal)((N, d), x.device)
+        eps = _f32c(eps).view(N, d)
+        xbar = torch.empty_like(x)
+        if not torch.is_tensor(std):
+            ones, target = torch.empty(N, device=x.device), torch.empty_like(x)
+            L.call("ardae_recon_perturb", x, eps, N, 1, d, noise, float(std), None, xbar, ones, target)
+            return xbar, ones, target
+        # a noise level per row (ardae_recon_perturb takes one per call): the same expressions, row by row
+        self._require_gpu(std)
+        s = torch.broadcast_to(_f32c(std), (N, 1)).contiguous()
+        if noise:
+            xbar = x + ((2.0 * s) * eps - s)                                        # add_uniform_noise (dae/mlp.py:16-18), its order
+        else:
+            L.call("ardae_dae_perturb", x, s.view(N), eps, N, 1, d, xbar)           # add_gaussian_noise (dae/mlp.py:12-14)
+        return xbar, torch.ones(N, device=x.device), -x
+
+    def _residual_score(self, recon, x, std):
+        """(recon - x) / std^2 (dae/mlp.py:80-81), in place of recon"""
+        std = self.std if std is None else std
+        if torch.is_tensor(std):
+            self._require_gpu(std)
+            return (recon - x) / torch.broadcast_to(_f32c(std), (x.size(0), 1)) ** 2
+        L.call("ardae_recon_score", recon, x, x.size(0), self.input_dim, float(std), None, recon)
+        return recon
+
+
+class ReconDAE(_ReconNet):
+    """models/dae/mlp.py:21-82 (exported as MLPDAE): the classical denoising autoencoder, `main = MLP(d, h, d)` - the network of MLPResDAE."""
+
+    def __init__(self, input_dim=2, h_dim=1000, std=0.1, num_hidden_layers=1, nonlinearity="tanh", noise_type="gaussian"):
+        super().__init__()
+        self._check_recon(noise_type, nonlinearity, num_hidden_layers)
+        self._build_net(6, layout.dae_plain_spec("res", input_dim, h_dim, num_hidden_layers), input_dim, 0, h_dim, std, num_hidden_layers,
+                        nonlinearity, noise_type)
+
+    def forward(self, input, std=None, eps=None):
+        """-> (x_recon [N, d], loss) like the reference (dae/mlp.py:54-70).  x_recon is returned DETACHED (the reference's is attached to the
+        graph); loss is differentiable with respect to the parameters.  `std`: None (self.std), a Python number, or a tensor that broadcasts
+        to [N, 1].  `eps` injects the raw draw [N, d]: normals, or uniforms in [0, 1); default: the library's Philox stream."""
+        self._require_gpu(input)
+        x = _f32c(input).view(-1, self.input_dim)
+        xbar, ones, target = self._perturb(x, std, eps)
+        loss, recon = _ReconLossFn.apply(self, xbar, ones, target, None, x.size(0), 1, *self.parameters())
+        return recon, loss
+
+    def glogprob(self, input, std=None):
+        """(main(x) - x) / std^2, in the shape of `input` (dae/mlp.py:72-82)."""
+        self._require_gpu(input)
+        x = _f32c(input).view(input.size(0), self.input_dim)
+        N = x.size(0)
+        ws = self._ws(L.query("ardae_cdae_workspace_floats", self._desc, N, 1, 0))
+        out = torch.empty(N, self.input_dim, device=x.device)
+        L.call("ardae_cdae_score", self._desc, self._flat, self._packed_weights(), x, None, None, N, 1, ws, ws.numel(), out)
+        return self._residual_score(out, x, std).view(input.size())
+
+
+class MLPDAE(ReconDAE):
+    """models/dae/mlp.py::DAE (exported as MLPDAE, models/__init__.py)."""
+
+
+class ReconConditionalDAE(_ReconNet):
+    """models/dae/mlp.py:85-193 (exported as MLPCDAE): the conditional denoising autoencoder.  `context` is [B, S, c], one context row PER SAMPLE
+    ROW (:146), so the ABI is called with B = N, S = 1; a [B, 1, c] tensor expanded along dim 1 (stride 0 there) is one context per image and
+    runs as (B, S).  enc_input=False (the default): the last MLP reads x_bar beside the encoded context (ardae_cdae_desc.kind 13);
+    enc_input=True: MLPResCDAE's network (kind 11)."""
+
+    def __init__(self, input_dim=2, h_dim=128, context_dim=2, std=0.1, num_hidden_layers=1, nonlinearity="tanh", noise_type="gaussian",
+                 enc_input=False, enc_ctx=True):
+        super().__init__()
+        self._check_recon(noise_type, nonlinearity, num_hidden_layers, None if enc_ctx else
+                          "enc_ctx=False is not built: the last MLP would read the raw concatenation [x | ctx]")
+        self.context_dim, self.enc_input, self.enc_ctx = context_dim, enc_input, enc_ctx
+        self._build_net(10 if enc_input else 12, layout.recon_cdae_spec(input_dim, context_dim, h_dim, num_hidden_layers, enc_input), input_dim,
+                        context_dim, h_dim, std, num_hidden_layers, nonlinearity, noise_type)
+
+    def _prep(self, input, context):
+        """-> (B, S) of the ABI call, x [N, d], ctx [B, c]"""
+        assert input.dim() == 3      # bsz x ssz x x_dim     (dae/mlp.py:138)
+        assert context.dim() == 3    # bsz x ssz x ctx_dim   (dae/mlp.py:139)
+        self._require_gpu(input, context)
+        B, S = input.size(0), input.size(1)
+        if tuple(context.shape) != (B, S, self.context_dim):
+            raise ValueError(f"context must be [{B}, {S}, {self.context_dim}] (one row per sample row), got {list(context.shape)}")
+        x = _f32c(input).view(B * S, self.input_dim)
+        if S > 1 and context.stride(1) == 0:               # one context per image, expanded over its samples
+            return B, S, x, _f32c(context[:, 0, :])
+        return B * S, 1, x, _f32c(context).view(B * S, self.context_dim)
+
+    def forward(self, input, context, std=None, eps=None):
+        """-> (x_recon [N, d], loss) like the reference (dae/mlp.py:136-165).  x_recon is returned DETACHED (the reference's is attached to the
+        graph); loss is differentiable with respect to the parameters.  `std`: None (self.std), a Python number, or a tensor that broadcasts
+        to [N, 1].  `eps` injects the raw draw [N, d]: normals, or uniforms in [0, 1); default: the library's Philox stream."""
+        B, S, x, c = self._prep(input, context)
+        xbar, ones, target = self._perturb(x, std, eps)
+        loss, recon = _ReconLossFn.apply(self, xbar, ones, target, c, B, S, *self.parameters())
+        return recon, loss
+
+    def glogprob(self, input, context, std=None):
+        """(dae(x, ctx) - x) / std^2 -> [B, S, d] (dae/mlp.py:167-193)."""
+        B, S, x, c = self._prep(input, context)
+        ws = self._ws(L.query("ardae_cdae_workspace_floats", self._desc, B, S, 0))
+        out = torch.empty(B * S, self.input_dim, device=x.device)
+        L.call("ardae_cdae_score", self._desc, self._flat, self._packed_weights(), x, None, c, B, S, ws, ws.numel(), out)
+        return self._residual_score(out, x, std).view(input.size())
+
+
+class MLPCDAE(ReconConditionalDAE):
+    """models/dae/mlp.py::ConditionalDAE (exported as MLPCDAE, models/__init__.py)."""
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -73,6 +73,9 @@ class _ScoreEngine:
         if kind not in self._AR_KINDS + self._PLAIN_KINDS:
             raise TypeError(self._DRIVES)
         self.plain = kind in self._PLAIN_KINDS
+        # a reconstruction DAE (models/dae/mlp.py) shares its network kind with a residual one: the module says which it is
+        self.recon = bool(getattr(net, "_recon", False))
+        self.noise_id = net.NOISE[net.noise_type] if self.recon else 0
         if not isinstance(cfg, DaeConfig if self.plain else ScoreConfig):
             raise TypeError(f"{type(net).__name__} takes a {'DaeConfig' if self.plain else 'ScoreConfig'}, not a {type(cfg).__name__}: ScoreConfig "
                             "(a sigma draw per row) belongs to the AR-DAE networks, DaeConfig (one annealed sigma per step) to the plain DAEs")
@@ -86,6 +89,8 @@ class _ScoreEngine:
         f = self._f
         self.ws = f(L.query("ardae_cdae_workspace_floats", net._desc, B, S, 1))
         self.xbar, self.sigma, self.eps = f(self.N, width), f(self.N), f(self.N, width)
+        # a reconstruction DAE: eps holds the raw draw, and the loss layer reads (sigma = 1, target = -x) in the place of (sigma, eps)
+        self.target = f(self.N, width) if self.recon else self.eps
         self.loss = f(1)
         self.grads = torch.zeros_like(net._flat)
         self.n_grad = net._flat.numel() - (1 if net._kind == "grad" else 0)     # neglogprob.fc.bias gets no gradient and keeps no state
@@ -126,8 +131,17 @@ class _ScoreEngine:
         self.eps.copy_(noise["eps"].reshape(self.eps.shape))
 
     def _loss_grads(self, ctx, B, S):
-        L.call("ardae_cdae_loss_grads", self._net._desc, self._net._flat, self.pk, self.xbar, self.sigma, self.eps, ctx, B, S, self.ws, self.ws.numel(),
+        L.call("ardae_cdae_loss_grads", self._net._desc, self._net._flat, self.pk, self.xbar, self.sigma, self.target, ctx, B, S, self.ws, self.ws.numel(),
                self.loss, self.grads, None)
+
+    def _draw(self, out, n, seed):
+        """The step's eps draw at in-step offset 1: normals, or (a reconstruction DAE with uniform noise) uniforms in [0, 1)"""
+        L.call("ardae_philox_uniform_at" if self.noise_id else "ardae_philox_normal_at", out, n, seed, 1, self.state, 0)
+
+    def _residual_score(self, recon, x, std):
+        """(recon - x) / s^2 in place of recon; s: `std`, or the device block's sigma (the coming step's) - no host synchronisation"""
+        L.call("ardae_recon_score", recon, x, x.size(0), x.size(1), 0.0 if std is None else float(std), self.state if std is None else None, recon)
+        return recon
 
     def _body(self, *front):
         self._front(*front)
@@ -200,16 +214,24 @@ class ArdaeScoreEngine(_ScoreEngine):
     so `noise` is {'eps'} alone, the in-step Philox offset RNG_STRIDE * step + 1 (eps; slot 0 stays unused), and `stats()` reports
     `loss` and `sigma`.
 
+    With a reconstruction DAE (`net.MLPDAE`, models/dae/mlp.py) and a `DaeConfig` it is the same update with the reconstruction loss: the
+    draw (normals, or uniforms in [0, 1) for noise_type='uniform') and `ardae_recon_perturb` at the block's noise level - or, `draw_form=True` (the default),
+    `ardae_recon_perturb_draw`, the same bits in one launch - leave x_bar, ones and -x, on which `ardae_cdae_loss_grads` gives mse(main(x_bar), x);
+    `noise={'eps'}` injects the raw draw; `score(x, std=None)` is (main(x) - x) / std^2 at the block's sigma or at `std`.
+
     A sampler that stays the caller's torch module takes its entropy gradient as `output.backward(engine.score(output.detach()) / B)`;
     the whole iteration of ardae_fit.ipynb on the device - generator, energy, this update - is `ArdaeFitEngine` (fit.py), which runs
     `_body(x, drawn)` inside its own captured iteration and `_count_step()` after it."""
 
     _NET, _AR_KINDS, _PLAIN_KINDS, _CHECKPOINT = "dae", (2, 3), (6, 7), "AR-DAE checkpoint"
     _DRIVES = ("ArdaeScoreEngine drives the unconditional networks (net.MLPGradARDAE / net.MLPResARDAE with a ScoreConfig, "
-               "net.MLPGradDAE / net.MLPResDAE with a DaeConfig)")
+               "net.MLPGradDAE / net.MLPResDAE / net.MLPDAE with a DaeConfig)")
 
-    def __init__(self, dae, cfg: ScoreConfig, batch_size, graph=True):
+    RECON_DRAW_FORM_DEFAULT = True       # reconstruction DAEs: ardae_recon_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
+
+    def __init__(self, dae, cfg: ScoreConfig, batch_size, graph=True, draw_form=None):
         self._pair(dae, cfg)
+        self.draw_form = self.recon and (self.RECON_DRAW_FORM_DEFAULT if draw_form is None else bool(draw_form))
         if int(cfg.nsigma) < 1 or int(batch_size) < 1:
             raise ValueError(f"nsigma and batch_size must be positive (got {cfg.nsigma}, {batch_size})")
         self.B, self.S, self.d = int(batch_size), int(cfg.nsigma), int(dae.input_dim)
@@ -227,7 +249,15 @@ class ArdaeScoreEngine(_ScoreEngine):
     def _front(self, x, drawn):
         """Perturbation, loss and gradients of the rows of x [B, d]; drawn: the step makes its own draws (else sigma / eps hold injected ones)."""
         seed = rng.get_state()["seed"]
-        if self.plain:             # sigma: the device block's in every form of the step
+        if self.recon:             # sigma: the device block's in every form of the step; the loss layer reads (1, -x)
+            if drawn and self.draw_form:
+                L.call("ardae_recon_perturb_draw", x, self.B, self.S, self.d, self.noise_id, 0.0, self.state, seed, 1, 0, self.xbar, self.sigma,
+                       self.target, self.eps)
+            else:
+                if drawn:
+                    self._draw(self.eps, self.N * self.d, seed)
+                L.call("ardae_recon_perturb", x, self.eps, self.B, self.S, self.d, self.noise_id, 0.0, self.state, self.xbar, self.sigma, self.target)
+        elif self.plain:           # sigma: the device block's in every form of the step
             if drawn:
                 L.call("ardae_philox_normal_at", self.eps, self.N * self.d, seed, 1, self.state, 0)
             L.call("ardae_dae_noise_perturb", x, self.eps, self.B, self.S, self.d, 0.0, self.state, self.xbar, self.sigma)
@@ -259,9 +289,12 @@ class ArdaeScoreEngine(_ScoreEngine):
             self._x = self._f(self.B, self.d)
         return self._x
 
-    def score(self, x, sigma=None):
-        """glogprob(x, sigma) with the engine's weight image: x [R, d] (any R), sigma [R] / [R, 1] or None = zeros."""
+    def score(self, x, sigma=None, std=None):
+        """glogprob(x, sigma) with the engine's weight image: x [R, d] (any R), sigma [R] / [R, 1] or None = zeros.  A reconstruction DAE:
+        glogprob(x, std) = (main(x) - x) / std^2, std a number or None = the device block's sigma (the coming step's)."""
         check_tensor(x, "score(x)", self.dev, shape=(None, self.d))
+        if (sigma is not None and self.recon) or (std is not None and not self.recon):
+            raise ValueError("score(): a reconstruction DAE takes std= (one noise level, a number), every other network sigma= (a level per row)")
         R = x.size(0)
         s = torch.zeros(R, device=self.dev) if sigma is None else sigma.detach().to(torch.float32).reshape(-1).contiguous()
         if s.numel() != R:
@@ -271,7 +304,7 @@ class ArdaeScoreEngine(_ScoreEngine):
             ws = self._score_ws[R] = torch.empty(L.query("ardae_cdae_workspace_floats", self.dae._desc, R, 1, 0), device=self.dev)
         out = torch.empty(R, self.d, device=self.dev)
         L.call("ardae_cdae_score", self.dae._desc, self.dae._flat, self.pk, x.detach(), s, None, R, 1, ws, ws.numel(), out)
-        return out
+        return self._residual_score(out, x.detach(), std) if self.recon else out
 
     def _ar_stats(self):
         """The last step's loss and mean |sigma|."""
@@ -300,13 +333,18 @@ class ArdaeCondScoreEngine(_ScoreEngine):
     `ardae_latent_noise_perturb_draw` (`draw_form=False`, or injected eps: `ardae_philox_normal_at` and `ardae_latent_noise_perturb`, the same
     bits) and `ardae_cdae_loss_grads`; `noise={'eps'}` alone, offset RNG_STRIDE * step + 1; `stats()` reports `loss` and `sigma`.
 
+    A reconstruction conditional DAE (`net.MLPCDAE`, models/dae/mlp.py; enc_input False or True) takes a `DaeConfig` too: the draw and
+    `ardae_latent_recon_perturb` (`draw_form=True`, the default: `ardae_latent_recon_perturb_draw`, the same bits in one launch), then `ardae_cdae_loss_grads` on
+    (x_bar, ones, -u) with one context per image; `score(..., std=None)` is (dae(u, ctx) - u) / std^2 at the block's sigma or at `std`.
+
     `score(latent, ctx, latent_mean=None)` is glogprob(std_scale (latent - mean), ctx, sigma = 0) with the engine's weight image, for any
     batch and sample size: a sampler that stays the caller's torch module takes its entropy gradient as
     `(std_scale * (latent - mean)).backward(beta * engine.score(latent.detach(), ctx, mean.detach()) / (B * S))` (ivae_ardae.py:826-834)."""
 
-    _NET, _AR_KINDS, _PLAIN_KINDS, _CHECKPOINT = "cdae", (0, 1), (10, 11), "cDAE checkpoint"
+    _NET, _AR_KINDS, _PLAIN_KINDS, _CHECKPOINT = "cdae", (0, 1), (10, 11, 13), "cDAE checkpoint"
     _DRIVES = ("ArdaeCondScoreEngine drives the conditional networks (net.MLPGradCARDAE / net.MLPResCARDAE with a ScoreConfig, "
-               "net.MLPGradCDAE / net.MLPResCDAE with a DaeConfig); the unconditional ones run in ArdaeScoreEngine")
+               "net.MLPGradCDAE / net.MLPResCDAE / net.MLPCDAE with a DaeConfig); the unconditional ones run in ArdaeScoreEngine")
+    RECON_DRAW_FORM_DEFAULT = True       # reconstruction DAEs: ardae_latent_recon_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
     DRAW_FORM_DEFAULT = True       # plain kinds: ardae_latent_noise_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
 
     def __init__(self, cdae, cfg, batch_size, sample_size, std_scale=1.0, graph=True, draw_form=None):
@@ -324,8 +362,9 @@ class ArdaeCondScoreEngine(_ScoreEngine):
         self.xi, self.std_b = f(self.N), f(self.B)
         self._latent, self._z0, self._ctx = f(self.B, self.S, self.z), torch.zeros(self.B, self.z, device=self.dev), f(self.B, self.c)
         if self.plain:
-            want = self.DRAW_FORM_DEFAULT if draw_form is None else bool(draw_form)
-            self.draw_form = want and bool(L.query("ardae_latent_noise_perturb_draw_ok", self.S, self.nstd, self.z))
+            want = (self.RECON_DRAW_FORM_DEFAULT if self.recon else self.DRAW_FORM_DEFAULT) if draw_form is None else bool(draw_form)
+            # (ardae_latent_recon_perturb_draw takes every positive shape; the query is the residual kinds' kernel's)
+            self.draw_form = want and (self.recon or bool(L.query("ardae_latent_noise_perturb_draw_ok", self.S, self.nstd, self.z)))
             self.fused_first = self.fused_draw = False
         else:
             self.draw_form = False
@@ -337,7 +376,16 @@ class ArdaeCondScoreEngine(_ScoreEngine):
         """Centring, perturbation, loss and gradients on the static buffers; drawn: the step makes its own draws (else xi / eps hold injected ones)."""
         seed, cfg = rng.get_state()["seed"], self.cfg
         lat, z0, B, S, nstd, z = self._latent, self._z0, self.B, self.S, self.nstd, self.z
-        if self.plain:             # sigma: the device block's in every form of the step
+        if self.recon:             # sigma: the device block's in every form of the step; the loss layer reads (1, -u)
+            if drawn and self.draw_form:
+                L.call("ardae_latent_recon_perturb_draw", lat, z0, B, S, nstd, z, self.std_scale, self.noise_id, 0.0, self.state, seed, 1, 0, self.xbar,
+                       self.sigma, self.target, self.eps)
+            else:
+                if drawn:
+                    self._draw(self.eps, self.N * z, seed)
+                L.call("ardae_latent_recon_perturb", lat, z0, self.eps, B, S, nstd, z, self.std_scale, self.noise_id, 0.0, self.state, self.xbar,
+                       self.sigma, self.target)
+        elif self.plain:           # sigma: the device block's in every form of the step
             if drawn and self.draw_form:
                 L.call("ardae_latent_noise_perturb_draw", lat, z0, B, S, nstd, z, self.std_scale, 0.0, self.state, seed, 1, 0, self.xbar, self.sigma,
                        self.eps)
@@ -385,10 +433,13 @@ class ArdaeCondScoreEngine(_ScoreEngine):
         step() saves the copies."""
         return self._latent, self._z0, self._ctx
 
-    def score(self, latent, ctx, latent_mean=None):
+    def score(self, latent, ctx, latent_mean=None, std=None):
         """glogprob(std_scale (latent - latent_mean), ctx, sigma = 0) with the engine's weight image: latent [B', S', z], ctx [B', c] | [B', 1, c],
-        latent_mean [B', z] | [B', 1, z] or None = zeros -> [B', S', z]."""
+        latent_mean [B', z] | [B', 1, z] or None = zeros -> [B', S', z].  A reconstruction DAE: glogprob(u, ctx, std) = (dae(u, ctx) - u) / std^2,
+        std a number or None = the device block's sigma (the coming step's)."""
         check_tensor(latent, "score(latent)", self.dev, shape=(None, None, self.z))
+        if std is not None and not self.recon:
+            raise ValueError("score(std=): only a reconstruction DAE's score reads a noise level")
         Bq, Sq = latent.size(0), latent.size(1)
         check_batch(ctx, "score(ctx)", self.dev, Bq, self.c, rows="contexts")
         if latent_mean is not None:
@@ -402,6 +453,8 @@ class ArdaeCondScoreEngine(_ScoreEngine):
         L.call("ardae_center_scale", latent.detach(), zeros if latent_mean is None else latent_mean.detach(), Bq, Sq, self.z, self.std_scale, u)
         out = torch.empty(Bq, Sq, self.z, device=self.dev)
         L.call("ardae_cdae_score", self.cdae._desc, self.cdae._flat, self.pk, u, None if self.plain else sigma0, ctx.detach(), Bq, Sq, ws, ws.numel(), out)
+        if self.recon:
+            self._residual_score(out.view(Bq * Sq, self.z), u, std)
         return out
 
     def _ar_stats(self):
