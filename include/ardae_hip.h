@@ -203,9 +203,10 @@ typedef struct ardae_cdae_desc {
                     * 6 / 7 = the plain DAEs, without a context and without the sigma input (MLPGradDAE / MLPResDAE, see "plain DAE"
                     * below); 10 / 11 = the plain CONDITIONAL DAEs, kinds 0 / 1 without the sigma input (MLPGradCDAE / MLPResCDAE, see
                     * "plain conditional DAE" below); 13 = the conditional DAE WITHOUT an input encoder (MLPCDAE with enc_input=False, see
-                    * "reconstruction DAE" below).  4, 5, 8, 9 and 12 are not kinds */
+                    * "reconstruction DAE" below); 16 / 17 = kinds 0 / 1 WITHOUT an input encoder (MLPGradCARDAE / MLPResCARDAE with
+                    * enc_input=False, see "conditional AR-DAE without an input encoder" below).  4, 5, 8, 9 and 12 are not kinds */
   int input_dim;   /* z */
-  int context_dim; /* c  (kinds 0 / 1 / 10 / 11 / 13: >= 1; kinds 2 / 3 / 6 / 7: 0) */
+  int context_dim; /* c  (kinds 0 / 1 / 10 / 11 / 13 / 16 / 17: >= 1; kinds 2 / 3 / 6 / 7: 0) */
   int h_dim;
   int n_layers;    /* --cdae-n-layers */
   int act;         /* any ARDAE_ACT_* but NONE (with a piecewise linear one mlp-grad's second-order terms are zero)  */
@@ -228,8 +229,8 @@ int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const f
  * a_1 = act(xbar A_1^T + b_1) (graddae/mlp.py:414-434), written into the cDAE workspace; the rest is ardae_cdae_loss_grads from layer 2 on.
  * xbar / sigma / eps_out / std_b are written as by ardae_latent_perturb_draw (the weight gradient of A_1 and the DAE-loss layer read them).
  * ardae_cdae_perturb_fused_ok: 1 if the shape qualifies (nstd == 1, the draw kernel's conditions, z % 8 == 0, z <= 64, nz % 32 == 0,
- * h % 32 == 0, relu / softplus; kinds 0 / 1 - the kernel draws sigma, so 0 for kinds 10 / 11); otherwise call ardae_latent_perturb* and
- * ardae_cdae_loss_grads. */
+ * h % 32 == 0, relu / softplus; kinds 0 / 1 / 16 / 17 - the kernel draws sigma, so 0 for kinds 10 / 11); otherwise call ardae_latent_perturb* and
+ * ardae_cdae_loss_grads.  Kinds 16 / 17: the layer is the energy MLP's own first one, see below. */
 int ardae_cdae_perturb_fused_ok(const ardae_cdae_desc* d, int nz, int nstd);
 int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* latent, const float* z0,
                                   const float* ctx, int B, int nz, float std_scale, float delta, uint64_t seed, uint64_t offset_xi,
@@ -239,6 +240,27 @@ int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params,
 int ardae_cdae_score(const ardae_cdae_desc* d, const float* params, const float* packed, const float* x,
                      const float* sigma, const float* ctx, int B, int S, float* workspace, size_t workspace_floats,
                      float* score_out, void* stream);
+
+/* ---- conditional AR-DAE without an input encoder (the same classes with enc_input=False): ardae_cdae_desc.kind 16 / 17 -----------
+ * With enc_input=False the reference drops inp_encode and the last MLP reads the perturbed sample itself beside the encoded context and the noise
+ * level: neglogprob / dae = MLP(z + h + 1, h, ...).  Kind 16 (MLPGradCARDAE) is an energy kind: the score is the input-gradient of the energy MLP;
+ * kind 17 (MLPResCARDAE) a direct-score kind.  Parameters in named_parameters() order: ctx_encode.layers.{0..L-2}.{weight,bias}, ctx_encode.fc.*,
+ * then neglogprob.layers.{0..L-1}.*, neglogprob.fc.* (kind 16) or dae.layers.*, dae.fc.* (kind 17); layers.0.weight is [h, z + h + 1] =
+ * [W1x | W1c | w1s], so h_1 = act(W1x x_bar + sigma w1s + [W1c c_L + d_1](b)): the context half enters as a row bias computed once per image, the
+ * sigma column as for kinds 0 / 1.  context_dim >= 1 and ctx non-NULL.  ardae_cdae_param_floats / packed_floats / workspace_floats / pack /
+ * loss_grads / score take the two kinds; the workspace is smaller than kind 0 / 1's at equal shape (no a_l, r_l, tau_l, pbar_l of an input encoder).
+ * The update: kind 17 is kind 1's with every inp_encode term removed (what kind 13 is to kind 11: one ordinary backward from the seed); kind 16 is
+ * the unconditional kind 2's (score pass g = e_1 W1x, tangent chain, backward) with the context bias in layer 1 and the backward of ctx_encode
+ * through the per-image reduction of layer 1's pre-activation gradient, first- and second-order contributions both, as kind 0 forms it for W1c;
+ * it leaves neglogprob.fc.bias's gradient untouched.  Launch decisions: kind 17 follows kind 13, kind 16 kind 0 on the per-image branch and kind 2
+ * on the N-row runs (its N == B score takes the general path).
+ * ardae_cdae_perturb_fused_ok follows the rule above.  ardae_cdae_perturb_loss_grads for these kinds: ctx_encode and the row bias
+ * cb[b] = W1c c_L + d_1 run first (B rows); then one kernel per image draws xi / eps, computes the statistics, sigma and x_bar as for kinds 0 / 1
+ * (the same bits as ardae_latent_perturb_draw) and - the rows still in LDS - writes h_1 = act(x_bar W1x^T + sigma[r] w1s + cb[b]) where
+ * ardae_cdae_loss_grads would have put the first N-row layer's output (with L = 1, kind 16, also the score pass's seed e_1); the rest is
+ * ardae_cdae_loss_grads from layer 2 on, and the context chain does not run a second time.  Measured, the fused form does not beat the draw +
+ * perturb launch followed by the stand-alone layer beyond the run-to-run spread (profiles/noenc_score_timing.json), so the engines do not use
+ * it for these kinds unless asked to. */
 
 /* ---- unconditional AR-DAE (models/graddae/mlp.py:118-207, models/resdae/mlp.py:92-167): ardae_cdae_desc.kind 2 / 3 -------------
  * The score network on [x_bar | sigma] alone: MLP(input_dim + 1, h, 1) whose input-gradient is the score (kind 2, MLPGradARDAE)

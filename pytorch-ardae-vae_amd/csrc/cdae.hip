@@ -1,4 +1,4 @@
-// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1), unconditional (kind 2 / 3), plain DAE (kind 6 / 7) and plain conditional DAE
+// AR-DAE update on gfx950, conditional (ardae_cdae_desc.kind 0 / 1; 16 / 17 without an input encoder), unconditional (kind 2 / 3), plain DAE (kind 6 / 7) and plain conditional DAE
 // (kind 10 / 11 / 13): forward, score pass, DAE loss, double backward and weight gradients, orchestrated on the host from the K1 (linear.hip) / K6w (wgrad.hip) kernels.
 //
 // Maths: SURVEY.md Appendix A (closed form of models/graddae/mlp.py:400-444 under autograd), notation below.
@@ -31,8 +31,16 @@
 // perturbed rows themselves beside the encoded context: a_L := xbar, W1 = [W1x | W1c] [h, z + h], h_1 = sp(W1x xbar + [W1c c_L + d_1](b)).  Every line
 // that names A_l, a_l or phat_l drops out: one ordinary backward from gbar, W1x's gradient = qhat_1 (x) xbar, W1c's through Qsum as before.
 // (Kinds 7 / 11 / 13 also serve the reconstruction DAEs of models/dae/mlp.py: with sigma = 1 and eps = -x the loss layer's rho is y - x.)
-// In the code: `cond` marks what exists for kinds 0 / 1 / 10 / 11 / 13 only, `enc_inp` the input encoder (cond without kind 13), `grad` what the
-// energy kinds (0 / 2 / 6 / 10) add to the res kinds, `has_sigma` the sigma column of W1 (kinds 0 - 3).
+// The conditional AR-DAEs without an input encoder (kinds 16 / 17; models/graddae/mlp.py:341-483, models/resdae/mlp.py:286-413 with enc_input=False)
+// are kinds 0 / 1 whose energy MLP reads the perturbed rows themselves: a_L := xbar, W1 = [W1x | W1c | w1s] [h, z + h + 1],
+// h_1 = sp(W1x xbar + [W1c c_L + d_1](b) + sigma w1s).  Every line that names A_l, a_l (l < L), r_l, tau_l, pbar_l or phat_l drops out.  Kind 17 is to
+// kind 1 what kind 13 is to kind 11: one ordinary backward from gbar.  Kind 16 is the unconditional kind 2's update (g = e_1 W1x, eb_1 = gbar W1x^T,
+// W1x's gradient = e_1 (x) gbar + qhat_1 (x) xbar) with the per-image bias in layer 1 and the ctx branch seeded by Qsum = sum_S qhat_1, which holds
+// the first- and the second-order term as kind 0's does.  Launch decisions: kind 17 follows kind 13 (the backward layer by layer, the split hint
+// 3L + 1), kind 16 kind 0 for the context chain, the ctx branch and the split hint, and kind 2 for the N-row runs; its N == B score takes the
+// general path (the one-launch chain of kind 0 walks the input encoder).
+// In the code: `cond` marks what exists for kinds 0 / 1 / 10 / 11 / 13 / 16 / 17 only, `enc_inp` the input encoder (cond without kinds 13 / 16 / 17),
+// `grad` what the energy kinds (0 / 2 / 6 / 10 / 16) add to the res kinds, `has_sigma` the sigma column of W1 (kinds 0 - 3, 16, 17).
 #include <vector>
 
 #include "ardae_hip.h"
@@ -43,20 +51,22 @@
 namespace ardae {
 namespace {
 
-bool cond_kind(int kind) { return kind < 2 || kind == 10 || kind == 11 || kind == 13; }
+bool cond_kind(int kind) { return kind < 2 || kind == 10 || kind == 11 || kind == 13 || kind == 16 || kind == 17; }
+bool input_encoder_kind(int kind) { return kind < 2 || kind == 10 || kind == 11; }
+bool sigma_column_kind(int kind) { return kind < 4 || kind == 16 || kind == 17; }
 
 struct CdaeLayout {
   int kind, z, c, h, L, act;
   bool cond, enc_inp, grad, has_sigma;
   std::vector<Lin> ctx, inp, neg;   // ctx (cond) / inp (enc_inp): L linears (L-1 hidden + fc); neg: L hidden + fc (= neglogprob / dae / main)
   size_t total = 0;
-  // W1 = neg[0] is [W1a | W1c | w1s] (enc_inp), [W1x | W1c] (kind 13) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then
+  // W1 = neg[0] is [W1a | W1c | w1s] (enc_inp), [W1x | W1c] (kind 13), [W1x | W1c | w1s] (kinds 16 / 17) or [W1x | w1s]: its N-row panel has k1 columns, then (cond) W1c's h, then
   // (has_sigma) the sigma column
   int k1() const { return enc_inp ? h : z; }
   int sigma_col() const { return cond ? k1() + h : z; }
 
   explicit CdaeLayout(const ardae_cdae_desc& d)
-      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(cond_kind(d.kind)), enc_inp(cond && d.kind != 13), grad(d.kind % 2 == 0), has_sigma(d.kind < 6) {
+      : kind(d.kind), z(d.input_dim), c(d.context_dim), h(d.h_dim), L(d.n_layers), act(d.act), cond(cond_kind(d.kind)), enc_inp(input_encoder_kind(d.kind)), grad(d.kind % 2 == 0), has_sigma(sigma_column_kind(d.kind)) {
     size_t off = 0;
     auto add = [&](std::vector<Lin>& v, int out, int in) { v.push_back(next_lin(off, out, in)); };
     if (cond)
@@ -93,10 +103,11 @@ struct PackedLayout {
 
 int desc_ok(const ardae_cdae_desc* d) {
   ARDAE_CHECK_ARG(d != nullptr, "cdae: desc is NULL");
-  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7 || d->kind == 10 || d->kind == 11 || d->kind == 13,
+  ARDAE_CHECK_ARG((d->kind >= 0 && d->kind <= 3) || d->kind == 6 || d->kind == 7 || d->kind == 10 || d->kind == 11 || d->kind == 13 || d->kind == 16 || d->kind == 17,
                   "cdae: kind must be 0 (mlp-grad), 1 (mlp-res), 2 (unconditional grad), 3 (unconditional res), 6 (plain DAE grad), 7 (plain DAE res), "
-                  "10 (plain conditional DAE grad), 11 (plain conditional DAE res) or 13 (conditional DAE without an input encoder)");
-  ARDAE_CHECK_ARG(!cond_kind(d->kind) || d->context_dim >= 1, "cdae: kinds 0 / 1 / 10 / 11 / 13 need context_dim >= 1 (got %d)", d->context_dim);
+                  "10 (plain conditional DAE grad), 11 (plain conditional DAE res), 13 (conditional DAE without an input encoder), "
+                  "16 (mlp-grad without an input encoder) or 17 (mlp-res without an input encoder)");
+  ARDAE_CHECK_ARG(!cond_kind(d->kind) || d->context_dim >= 1, "cdae: kinds 0 / 1 / 10 / 11 / 13 / 16 / 17 need context_dim >= 1 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(cond_kind(d->kind) || d->context_dim == 0, "cdae: kinds 2 / 3 / 6 / 7 have no context: context_dim must be 0 (got %d)", d->context_dim);
   ARDAE_CHECK_ARG(d->input_dim >= 1 && d->h_dim >= 1 && d->n_layers >= 1, "cdae: bad dimensions");
   ARDAE_CHECK_ARG(d->n_layers <= 6, "cdae: n_layers <= 6 supported (3L+1 gradient problems per batch)");
@@ -113,8 +124,8 @@ struct CdaeWs {
   int ltiles, ctiles;
 };
 
-// Kinds 0 / 1 / 10 / 11 take every buffer whichever of the two reads it (kinds 1 / 11 leave e, r, tau, tau', pbar and cs_taup unused); kind 13 and
-// the unconditional kinds take what they read, so hh[1] is the arena's first piece (the fused front end of dae_perturb.hip fills it).
+// Kinds 0 / 1 / 10 / 11 take every buffer whichever of the two reads it (kinds 1 / 11 leave e, r, tau, tau', pbar and cs_taup unused); kinds 13 /
+// 16 / 17 and the unconditional kinds take what they read, so hh[1] is the first N-row piece of the arena (the fused front ends fill it).
 void cdae_carve(const CdaeLayout& P, Bump& ws, int B, int S, bool need_grads, CdaeWs& W) {
   const int N = B * S, h = P.h, L = P.L, z = P.z;
   const size_t Bh = (size_t)B * h, Nh = (size_t)N * h;
@@ -246,7 +257,8 @@ struct LayerRun {
   }
 };
 
-// first_ready: a fused front end has written the first N-row layer's output where the carve puts it (a_1 when cond, else h_1)
+// first_ready: a fused front end has written the first N-row layer's output where the carve puts it (a_1 with an input encoder, else h_1);
+// for kinds 16 / 17 it has also run the context chain (cL, cb), which is then not run again
 int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed, const float* xbar, const float* sigma,
               const float* eps, const float* ctx, int B, int S, float* workspace, size_t ws_floats, float* loss, float* grads,
               float* score_out, bool need_grads, hipStream_t st, bool first_ready = false) {
@@ -255,6 +267,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   const bool cond = P.cond, grad = P.grad;
   const bool enc = P.enc_inp;
   ARDAE_CHECK_ARG(cond || ctx == nullptr, "cdae: kinds 2 / 3 / 6 / 7 take no context: ctx must be NULL");
+  const bool ctx_ready = first_ready && cond && !enc;
   // the plain DAEs' score does not read sigma (DAE.glogprob / ConditionalDAE.glogprob ignore std); their loss layer does
   ARDAE_CHECK_ARG(params && packed && xbar && (sigma || (!P.has_sigma && !need_grads)) && (ctx || !cond) && workspace, "cdae: null pointer argument");
   ARDAE_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S < (int64_t)1 << 30, "cdae: bad batch (B=%d, S=%d)", B, S);
@@ -301,13 +314,13 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   };
   auto g_layer = [&](LinArgs A) {   // the score g [N, z]: the last link of the score pass (r_1 A_1 | e_1 W1x), or fc(h_L) of the res kinds
     A.Y = g; A.ldY = z;
-    if (grad) return lin_args(ACT_NONE, N, z, cond ? r[1] : e[1], h, h, packed + (cond ? K.inp_b[0] : K.w1_b), A);
+    if (grad) return lin_args(ACT_NONE, N, z, enc ? r[1] : e[1], h, h, packed + (enc ? K.inp_b[0] : K.w1_b), A);
     A.bias = params + P.neg[L].b;
     return lin_args(ACT_NONE, N, z, hh[L], h, h, packed + K.fc_f, A);
   };
 
   // ------------------------------------------------------------------ forward: ctx (B rows, once per image), inp and energy (N rows)
-  if (!need_grads && cond && grad && N == B && linear_small_eligible(inp_layer(1), EPI_ACT)) {
+  if (!need_grads && enc && grad && N == B && linear_small_eligible(inp_layer(1), EPI_ACT)) {
     // The sigma = 0 score pass of the VAE update (glogprob on B rows, models/graddae/mlp.py:446-483): 4 L + 2 per-image problems, every one
     // a link of a dependent chain - ONE launch walks them level by level (linear_small_chain_kernel): [ctx_l | inp_l] l = 1..L, the
     // per-image bias of the first energy layer, the energy layers, the score layers, g.
@@ -331,18 +344,20 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     } else if (cond) {
       // the whole per-image branch FIRST (context encoder, then the bias it contributes to the first energy layer): the N-row forward
       // layers of both networks then form ONE run (round 4: one multi-layer launch instead of two with a per-image launch between them)
-      for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear(ctx_layer(l), EPI_ACT, st));
-      ARDAE_TRY(launch_linear(ctx_bias(), EPI_ACT, st));
+      if (!ctx_ready) {
+        for (int l = 1; l <= L; ++l) ARDAE_TRY(launch_linear(ctx_layer(l), EPI_ACT, st));
+        ARDAE_TRY(launch_linear(ctx_bias(), EPI_ACT, st));
+      }
       if (enc) for (int l = first_ready ? 2 : 1; l <= L; ++l) run.add(inp_layer(l));
     }
-    for (int l = !cond && first_ready ? 2 : 1; l <= L; ++l) run.add(energy_layer(l));
+    for (int l = !enc && first_ready ? 2 : 1; l <= L; ++l) run.add(energy_layer(l));
     ARDAE_TRY(run.flush());
   }
   if (grad) {
     // ------------------------------------------------------------------ score pass (input-gradient of the energy)
     LayerRun run(EPI_DACT, st);
     for (int l = L; l >= 2; --l) run.add(e_layer(l));
-    if (cond) for (int l = L + 1; l >= 2; --l) run.add(r_layer(l));
+    if (enc) for (int l = L + 1; l >= 2; --l) run.add(r_layer(l));
     ARDAE_TRY(run.flush());
   }
   if (!need_grads) return launch_linear(g_layer(LinArgs{}), EPI_ACT, st);   // glogprob
@@ -358,7 +373,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
   if (grad) {
     // forward-mode chain through the score pass
     LayerRun run(EPI_CHAIN, st);
-    if (cond)
+    if (enc)
       for (int l = 1; l <= L; ++l) {
         LinArgs A{}; A.S = a[l]; A.ldS = h; A.R = r[l]; A.ldR = h; A.Y = tau[l]; A.ldY = h; A.Y2 = pbar[l]; A.ldY2 = h;
         run.add(l == 1 ? lin_args(act, N, h, gbar, z, z, packed + K.inp_f[0], A) : lin_args(act, N, h, tau[l - 1], h, h, packed + K.inp_f[l - 1], A));
@@ -366,7 +381,7 @@ int cdae_impl(const ardae_cdae_desc* d, const float* params, const float* packed
     for (int l = 1; l <= L; ++l) {
       LinArgs A{}; A.S = hh[l]; A.ldS = h; A.R = e[l]; A.ldR = h; A.Y = taup[l]; A.ldY = h; A.Y2 = qbar[l]; A.ldY2 = h;
       if (l == L) A.colsum = cs_taup;
-      run.add(l == 1 ? lin_args(act, N, h, cond ? tau[L] : gbar, k1, k1, packed + K.w1_f, A) : lin_args(act, N, h, taup[l - 1], h, h, packed + K.neg_f[l - 1], A));
+      run.add(l == 1 ? lin_args(act, N, h, enc ? tau[L] : gbar, k1, k1, packed + K.w1_f, A) : lin_args(act, N, h, taup[l - 1], h, h, packed + K.neg_f[l - 1], A));
     }
     ARDAE_TRY(run.flush());
     // wbar = -colsum(tau'_L)  -> grads of neglogprob.fc.weight [1,h]
@@ -458,8 +473,8 @@ int ardae_cdae_loss_grads(const ardae_cdae_desc* d, const float* params, const f
 }
 int ardae_cdae_perturb_fused_ok(const ardae_cdae_desc* d, int nz, int nstd) {
   if (desc_ok(d) != 0) return 0;
-  const CdaeLayout P(*d);   // the fused draw + A_1 kernel is the conditional AR-DAE kinds' (it draws sigma)
-  return P.cond && P.has_sigma && nstd == 1 && P.inp[0].in == P.z && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
+  const CdaeLayout P(*d);   // the fused draw + first-layer kernel is the conditional AR-DAE kinds' (it draws sigma): A_1, or W1x of kinds 16 / 17
+  return P.cond && P.has_sigma && nstd == 1 && latent_perturb_draw_fwd_ok(nz, P.z, P.h, P.act) ? 1 : 0;
 }
 int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params, const float* packed, const float* latent, const float* z0,
                                   const float* ctx, int B, int nz, float std_scale, float delta, uint64_t seed, uint64_t offset_xi,
@@ -473,7 +488,24 @@ int ardae_cdae_perturb_loss_grads(const ardae_cdae_desc* d, const float* params,
   ARDAE_CHECK_ARG(ws_floats >= workspace_floats(P, B, nz, true), "cdae_perturb_loss_grads: workspace too small");
   Bump ws(workspace, ws_floats);
   CdaeWs W;
-  cdae_carve(P, ws, B, nz, true, W);   // the kernel below leaves a_1 where cdae_impl reads it
+  cdae_carve(P, ws, B, nz, true, W);   // the kernel below leaves a_1 (kinds 16 / 17: h_1) where cdae_impl reads it
+  const hipStream_t st = (hipStream_t)stream;
+  if (!P.enc_inp) {
+    // the per-image branch first, with cdae_impl's own launches: ctx_encode, then cb = W1c c_L + d_1 - the kernel adds it (and sigma w1s) to W1x xbar
+    ARDAE_CHECK_ARG(latent && z0 && ctx && xbar && sigma && eps_out && std_b && loss && grads, "cdae_perturb_loss_grads: null pointer argument");
+    const int h = P.h, L = P.L;
+    for (int l = 1; l <= L; ++l) {
+      LinArgs A{}; A.bias = params + P.ctx[l - 1].b; A.Y = W.cL[l]; A.ldY = h;
+      ARDAE_TRY(launch_linear(lin_args(P.act, B, h, l == 1 ? ctx : W.cL[l - 1], l == 1 ? P.c : h, P.ctx[l - 1].in, packed + K.ctx_f[l - 1], A), EPI_ACT, st));
+    }
+    LinArgs A{}; A.bias = params + P.neg[0].b; A.Y = W.cb; A.ldY = h;
+    ARDAE_TRY(launch_linear(lin_args(ACT_NONE, B, h, W.cL[L], h, h, packed + K.w1c_f, A), EPI_ACT, st));
+    const bool seed_e = P.grad && L == 1;   // the only hidden layer: the score pass's seed e_1 comes with it
+    ARDAE_TRY(launch_latent_perturb_draw_fwd(latent, z0, B, nz, P.z, std_scale, delta, seed, offset_xi, offset_eps, state, first_row, xbar, sigma, eps_out,
+                                             std_b, packed + K.w1_f, W.cb, h, P.act, W.hh[1], st, packed + K.w1s, seed_e ? params + P.neg[L].w : nullptr,
+                                             seed_e ? W.e[1] : nullptr));
+    return cdae_impl(d, params, packed, xbar, sigma, eps_out, ctx, B, nz, workspace, ws_floats, loss, grads, nullptr, true, st, true);
+  }
   ARDAE_TRY(launch_latent_perturb_draw_fwd(latent, z0, B, nz, P.z, std_scale, delta, seed, offset_xi, offset_eps, state, first_row, xbar, sigma,
                                            eps_out, std_b, packed + K.inp_f[0], params + P.inp[0].b, P.h, P.act, W.a[1],
                                            (hipStream_t)stream));

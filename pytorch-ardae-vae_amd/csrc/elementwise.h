@@ -33,7 +33,8 @@ bool latent_perturb_draw_fwd_ok(int nz, int zd, int h, int act);
 int launch_latent_perturb_draw_fwd(const float* latent, const float* z0, int B, int nz, int zd, float std_scale, float delta, uint64_t seed,
                                    uint64_t off_xi, uint64_t off_eps, const void* state, uint64_t first_row, float* xbar, float* sigma,
                                    float* eps_out, float* std_b, const float* wp1, const float* bias1, int h, int act, float* a1_out,
-                                   hipStream_t st);
+                                   hipStream_t st, const float* w1s = nullptr, const float* wfc = nullptr, float* e1_out = nullptr);
+// (w1s: the layer has a sigma column and bias1 is a per-image bias [B, h]; wfc / e1_out: it also seeds the score pass - PerturbDraw in elementwise.hip)
 // u = s (z - z0[b]) only (VAE phase, sigma = 0: ivae_ardae.py:827)
 int launch_center_scale(const float* latent, const float* z0, int B, int nz, int zd, float std_scale, float* u,
                         hipStream_t st);

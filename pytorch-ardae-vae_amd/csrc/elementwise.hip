@@ -177,13 +177,20 @@ struct PerturbDraw {
   const float* bias1;                 // [h]
   float* a1_out;                      // [rows, h]
   int h;
+  // SC (kinds 16 / 17 of cdae.hip: no input encoder): the layer is the energy MLP's own first one, h_1 = act(xbar W1x^T + sigma w1s + cb[b]) - wp1 is
+  // W1x's image, bias1 the per-image bias cb [B, h] = W1c c_L + d_1, a1_out receives h_1
+  const float* w1s;                   // [h]: the sigma column of W1
+  const float* wfc;                   // [h] or null: the energy's output weights w, where this layer is the last hidden one (L = 1, energy kinds) ...
+  float* e1_out;                      // ... and the score pass's seed e_1 = -w (.) act'(h_1) [rows, h] is due with it
 };
 
 // FWD > 0 (the activation id): north star "fused per-sample Gaussian-perturb + sigma-scaling + DAE-forward kernel": after the perturbation the
 // image's rows xbar [nz, z] are still in the workgroup's LDS; its four waves multiply them by A_1 (FP32 MFMA, 32 x 32 blocks, K = z) and write
 // a_1 = act(xbar A_1^T + b_1) [nz, h] (models/graddae/mlp.py:414-434: add_gaussian_noise, then inp_encode's first Linear + activation) - the
 // separate K = z N-row launch and its re-read of xbar are gone.  Same MFMA order over k as the stand-alone layer kernels.
-template <int NV, bool DRAW, int FWD = 0>
+// SC: the FWD layer with a sigma column and a per-image bias (see PerturbDraw): a column's w1s and cb entries live in registers beside the bias of the
+// plain form, sigma[r] = sb * xi[r] is rebuilt from the xi values still in LDS behind the xbar tile (the bits of the value written out).
+template <int NV, bool DRAW, int FWD = 0, bool SC = false>
 __global__ __launch_bounds__(256) void latent_perturb_reg_kernel(const float* __restrict__ latent, const float* __restrict__ z0,
                                                                  const float* __restrict__ xi, const float* __restrict__ eps, int nz,
                                                                  int zd, float std_scale, float delta, float* __restrict__ xbar,
@@ -295,7 +302,8 @@ __global__ __launch_bounds__(256) void latent_perturb_reg_kernel(const float* __
       for (int c = 0; c < 8; ++c)
         if (c < kch) bv[c] = *reinterpret_cast<const f32x4*>(bp + (size_t)c * 256);
       const int col = cb * 32 + l31;
-      const float bc = dr.bias1[col];
+      const float bc = SC ? dr.bias1[(size_t)b * dr.h + col] : dr.bias1[col];
+      const float wsg = SC ? dr.w1s[col] : 0.f, wv = (SC && dr.wfc) ? dr.wfc[col] : 0.f;
       for (int rb = 0; rb < nrb; ++rb) {
         f32x16 acc;
 #pragma unroll
@@ -310,7 +318,16 @@ __global__ __launch_bounds__(256) void latent_perturb_reg_kernel(const float* __
           }
         float* yo = dr.a1_out + ((size_t)b * nz + RG * j0 + rb * 32 + 4 * hh) * dr.h + col;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) yo[(size_t)((r & 3) + 8 * (r >> 2)) * dr.h] = act_fwd<FWD>(acc[r] + bc);
+        for (int r = 0; r < 16; ++r) {
+          const int rr = (r & 3) + 8 * (r >> 2);
+          if (SC) {
+            const float y = act_fwd<FWD>(acc[r] + bc + sb * nbuf[xi_at + rb * 32 + 4 * hh + rr] * wsg);
+            yo[(size_t)rr * dr.h] = y;
+            if (dr.e1_out) dr.e1_out[(yo - dr.a1_out) + (size_t)rr * dr.h] = -wv * act_d1<FWD>(y);
+          } else {
+            yo[(size_t)rr * dr.h] = act_fwd<FWD>(acc[r] + bc);
+          }
+        }
       }
     }
   }
@@ -621,12 +638,13 @@ bool latent_perturb_draw_fwd_ok(int nz, int zd, int h, int act) {
 int launch_latent_perturb_draw_fwd(const float* latent, const float* z0, int B, int nz, int zd, float std_scale, float delta, uint64_t seed,
                                    uint64_t off_xi, uint64_t off_eps, const void* state, uint64_t first_row, float* xbar, float* sigma,
                                    float* eps_out, float* std_b, const float* wp1, const float* bias1, int h, int act, float* a1_out,
-                                   hipStream_t st) {
+                                   hipStream_t st, const float* w1s, const float* wfc, float* e1_out) {
   ARDAE_CHECK_ARG(latent && z0 && xbar && sigma && eps_out && std_b && wp1 && bias1 && a1_out && B > 0, "latent_perturb_draw_fwd: null pointer");
   ARDAE_CHECK_ARG(latent_perturb_draw_fwd_ok(nz, zd, h, act), "latent_perturb_draw_fwd: shape not eligible (nz=%d z=%d h=%d act=%d)", nz, zd, h, act);
   ARDAE_CHECK_ARG((first_row & 3) == 0, "latent_perturb_draw_fwd: first_row must be a multiple of 4 (one Philox counter = 4 normals)");
   const int64_t per_image = (int64_t)nz * zd;
-  const PerturbDraw dr{seed, off_xi, off_eps, (const StepState*)state, first_row, eps_out, wp1, bias1, a1_out, h};
+  ARDAE_CHECK_ARG((wfc != nullptr) == (e1_out != nullptr) && (w1s || !wfc), "latent_perturb_draw_fwd: w1s / wfc / e1_out do not go together");
+  const PerturbDraw dr{seed, off_xi, off_eps, (const StepState*)state, first_row, eps_out, wp1, bias1, a1_out, h, w1s, wfc, e1_out};
   // few images: S workgroups per image, rows split among them (a slice is a whole number of 32-row blocks), until the grid fills the chip
   const int rg = 256 / zd, passes = (int)(per_image >> 8);
   static const int target_wgs = debug_knob("ARDAE_LP_WGS") ? atoi(debug_knob("ARDAE_LP_WGS")) : 256;
@@ -634,9 +652,14 @@ int launch_latent_perturb_draw_fwd(const float* latent, const float* z0, int B, 
   while (B * S < target_wgs && passes % (2 * S) == 0 && (passes / (2 * S)) * rg % 32 == 0) S *= 2;
   const size_t rows_sl = (size_t)(passes / S) * rg;
   const size_t lds = (rows_sl * (zd + LP_XPAD) + rows_sl) * sizeof(float);
+#define ARDAE_LP_FWD_SC(NV_, ACT_, SC_)                                                                                                    \
+  hipLaunchKernelGGL((latent_perturb_reg_kernel<NV_, true, ACT_, SC_>), dim3(B, S), dim3(256), lds, st, latent, z0, nullptr, nullptr, nz,  \
+                     zd, std_scale, delta, xbar, sigma, std_b, dr)
 #define ARDAE_LP_FWD(NV_, ACT_)                                                                                                            \
-  hipLaunchKernelGGL((latent_perturb_reg_kernel<NV_, true, ACT_>), dim3(B, S), dim3(256), lds, st, latent, z0, nullptr, nullptr, nz, zd,    \
-                     std_scale, delta, xbar, sigma, std_b, dr)
+  do {                                                                                                                                     \
+    if (w1s) ARDAE_LP_FWD_SC(NV_, ACT_, true);                                                                                             \
+    else ARDAE_LP_FWD_SC(NV_, ACT_, false);                                                                                                \
+  } while (0)
 #define ARDAE_LP_FWD_NV(ACT_)                                                                                                              \
   do {                                                                                                                                     \
     if (per_image <= 256 * 8) ARDAE_LP_FWD(8, ACT_);                                                                                       \
@@ -647,6 +670,7 @@ int launch_latent_perturb_draw_fwd(const float* latent, const float* z0, int B, 
   else ARDAE_LP_FWD_NV(ACT_SOFTPLUS);
 #undef ARDAE_LP_FWD_NV
 #undef ARDAE_LP_FWD
+#undef ARDAE_LP_FWD_SC
   ARDAE_LAUNCH_CHECK();
   return 0;
 }

@@ -16,6 +16,7 @@ from . import rng
 from .iwae import IwaeEvaluator
 from .diagnostics import PosteriorDiagnostics
 from .engine_common import RNG_STRIDE, CaptureLadder, _FlatOpt, bump_versions, capture_linear, check_batch, check_tensor, rebuild_step_state  # noqa: F401
+from .score_engine import ArdaeCondScoreEngine
 from .optim import WEIGHT_AVG_KINDS, unwrap_state_dict, wrap_state_dict
 
 
@@ -98,7 +99,7 @@ class ArdaeEngine:
     def __init__(self, model, cdae, cfg: TrainConfig, batch_size, process_group=None, graph=True, force_dp=False, dp_comm="auto"):
         model._require_gpu()
         cdae._require_gpu()
-        if int(cdae._desc.kind) not in (0, 1):
+        if int(cdae._desc.kind) not in (0, 1, 16, 17):       # (16 / 17: the same classes with enc_input=False)
             raise TypeError(f"ArdaeEngine trains a conditional AR-DAE (net.MLPGradCARDAE / net.MLPResCARDAE), not a {type(cdae).__name__}: its step "
                             "block has no slot for a noise level beside beta (a plain conditional DAE runs in ArdaeCondScoreEngine)")
         self.model, self.cdae, self.cfg = model, cdae, cfg
@@ -200,7 +201,9 @@ class ArdaeEngine:
         self.split_backward = int(md.kind) < 2 and L.debug_knob("ARDAE_SPLIT_BACKWARD", "1") != "0"
         self._side = torch.cuda.Stream(device=self.dev) if self.overlap else None
         self.fused_draws = L.debug_knob("ARDAE_FUSED_DRAW", "1") != "0"     # sigma / eps draws inside the perturbation kernel
-        self.fused_first_layer = L.debug_knob("ARDAE_FUSED_A1", "1") != "0"   # ... and the score network's first layer on the perturbed rows
+        # ... and the score network's first layer on the perturbed rows: the measured default of the network's kind (ArdaeCondScoreEngine's)
+        self.fused_first_layer = (L.debug_knob("ARDAE_FUSED_A1", "1") != "0"
+                                  and (int(cd.kind) < 2 or ArdaeCondScoreEngine.FUSED_FIRST_NOENC_DEFAULT))
         self._cap_stream = torch.cuda.Stream(device=self.dev)
         self._stamps = None                             # diagnostics: see enable_stamps()
         self._log = None                                # scalar log channel (scalar_log.ScalarLog), one more launch at the end of the step

@@ -209,13 +209,18 @@ def aux_resconv_vae_spec(noise_dim, z_dim, c_dim):
             + _resconv_decoder(z_dim, c_dim) + fc("aux_decode.", z_dim) + head("aux_decode.", noise_dim))
 
 
-def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers):
+def cdae_spec(kind, input_dim, context_dim, h_dim, n_layers, enc_input=True):
+    """The conditional AR-DAE (models/graddae/mlp.py:342-378, models/resdae/mlp.py:287-326): `layers.0.weight` of the last MLP is [h, 2h + 1] =
+    [W1a | W1c | w1s] (ardae_cdae_desc.kind 0 'grad' / 1 'res').  enc_input=False: there is no inp_encode and the last MLP reads x_bar itself,
+    [h, d + h + 1] = [W1x | W1c | w1s] (kind 16 / 17)."""
     s = _mlp("ctx_encode.", context_dim, h_dim, h_dim, n_layers - 1)
-    s += _mlp("inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)
+    if enc_input:
+        s += _mlp("inp_encode.", input_dim, h_dim, h_dim, n_layers - 1)
+    first = (h_dim if enc_input else input_dim) + h_dim + 1
     if kind == "grad":
-        s += _mlp("neglogprob.", 2 * h_dim + 1, h_dim, 1, n_layers)
+        s += _mlp("neglogprob.", first, h_dim, 1, n_layers)
     elif kind == "res":
-        s += _mlp("dae.", 2 * h_dim + 1, h_dim, input_dim, n_layers)
+        s += _mlp("dae.", first, h_dim, input_dim, n_layers)
     else:
         raise NotImplementedError(kind)
     return s

@@ -199,7 +199,8 @@ class _ScoreNet(FlatParamModule):
             raise NotImplementedError(f"nonlinearity {nonlinearity!r}: get_nonlinear_func (utils/models.py:14-32) knows relu, softplus / csoftplus, elu, tanh, leaky_relu and swish")
 
     def _build_net(self, first_kind, spec, input_dim, context_dim, h_dim, std, num_hidden_layers, nonlinearity, noise_type):
-        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional, 6 plain DAE, 10 plain conditional DAE); its res sibling is the next."""
+        """first_kind: ardae_cdae_desc.kind of the grad class (0 conditional, 2 unconditional, 6 plain DAE, 10 plain conditional DAE, 16 conditional
+        without an input encoder); its res sibling is the next."""
         self.input_dim, self.h_dim, self.std = input_dim, h_dim, std
         self.num_hidden_layers, self.nonlinearity, self.noise_type = num_hidden_layers, nonlinearity, noise_type
         self._desc = L.CdaeDesc(first_kind if self._kind == "grad" else first_kind + 1, input_dim, context_dim, h_dim, num_hidden_layers, L.ACT[nonlinearity])
@@ -214,11 +215,13 @@ class ConditionalARDAE(_ScoreNet):
     def __init__(self, input_dim=2, h_dim=128, context_dim=2, std=0.01, num_hidden_layers=1, nonlinearity="tanh",
                  noise_type="gaussian", enc_input=True, enc_ctx=True, std_method="default"):
         super().__init__()
-        self._check(noise_type, nonlinearity, None if enc_input and enc_ctx else
-                    "enc_input=enc_ctx=True is the only configuration ivae_ardae.py:583-606 constructs")
-        self.context_dim, self.enc_input, self.enc_ctx = context_dim, enc_input, enc_ctx
-        self._build_net(0, layout.cdae_spec(self._kind, input_dim, context_dim, h_dim, num_hidden_layers), input_dim, context_dim, h_dim, std,
-                        num_hidden_layers, nonlinearity, noise_type)
+        self._check(noise_type, nonlinearity, None if enc_ctx else
+                    "enc_ctx=False is not built: the last MLP would read the raw concatenation [input | context | std] "
+                    "(enc_input may be False: ardae_cdae_desc.kind 16 / 17)")
+        self.context_dim, self.enc_input, self.enc_ctx = context_dim, bool(enc_input), enc_ctx
+        # enc_input=True: what ivae_ardae.py:583-606 constructs (kind 0 / 1); False: the last MLP reads the perturbed sample itself (kind 16 / 17)
+        self._build_net(0 if enc_input else 16, layout.cdae_spec(self._kind, input_dim, context_dim, h_dim, num_hidden_layers, bool(enc_input)),
+                        input_dim, context_dim, h_dim, std, num_hidden_layers, nonlinearity, noise_type)
 
     def _prep(self, input, context, std):
         assert input.dim() == 3      # bsz x ssz x x_dim   (graddae/mlp.py:402)

@@ -326,7 +326,9 @@ class ArdaeCondScoreEngine(_ScoreEngine):
     A conditional AR-DAE (`net.MLPGradCARDAE` / `net.MLPResCARDAE`) takes a `ScoreConfig`: the launches and selection rules of
     ArdaeEngine's cDAE phase behind its sampler - `ardae_cdae_perturb_loss_grads` where the shape allows, else `ardae_latent_perturb_draw`,
     else two draws and `ardae_latent_perturb_nstd` - with sigma = delta * mean_d std_S(u) * xi; `noise={'sigma': xi [N], 'eps': [N, z]}`;
-    in-step Philox offsets RNG_STRIDE * step + {0 (xi), 1 (eps)}; `stats()` reports `loss` and `std_mean / std_max / std_min`.
+    in-step Philox offsets RNG_STRIDE * step + {0 (xi), 1 (eps)}; `stats()` reports `loss` and `std_mean / std_max / std_min`.  The same
+    classes with `enc_input=False` (ardae_cdae_desc.kind 16 / 17: no input encoder) run the same launches; for them the first-layer form of
+    `ardae_cdae_perturb_loss_grads` is off unless `fused_first=True` asks for it (measured: DESIGN.md section 6).
 
     A plain conditional DAE (`net.MLPGradCDAE` / `net.MLPResCDAE`) takes a `DaeConfig`: one noise level per step, read from the device
     block where `ardae_dae_state_advance` leaves the annealed value, so the replay runs through the ramp; the launches are
@@ -341,13 +343,14 @@ class ArdaeCondScoreEngine(_ScoreEngine):
     batch and sample size: a sampler that stays the caller's torch module takes its entropy gradient as
     `(std_scale * (latent - mean)).backward(beta * engine.score(latent.detach(), ctx, mean.detach()) / (B * S))` (ivae_ardae.py:826-834)."""
 
-    _NET, _AR_KINDS, _PLAIN_KINDS, _CHECKPOINT = "cdae", (0, 1), (10, 11, 13), "cDAE checkpoint"
+    _NET, _AR_KINDS, _PLAIN_KINDS, _CHECKPOINT = "cdae", (0, 1, 16, 17), (10, 11, 13), "cDAE checkpoint"
     _DRIVES = ("ArdaeCondScoreEngine drives the conditional networks (net.MLPGradCARDAE / net.MLPResCARDAE with a ScoreConfig, "
                "net.MLPGradCDAE / net.MLPResCDAE / net.MLPCDAE with a DaeConfig); the unconditional ones run in ArdaeScoreEngine")
     RECON_DRAW_FORM_DEFAULT = True       # reconstruction DAEs: ardae_latent_recon_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
     DRAW_FORM_DEFAULT = True       # plain kinds: ardae_latent_noise_perturb_draw in place of its two launches (measured: DESIGN.md section 6)
+    FUSED_FIRST_NOENC_DEFAULT = False    # kinds 16 / 17 (enc_input=False): the first energy layer inside the perturbation kernel (DESIGN.md section 6)
 
-    def __init__(self, cdae, cfg, batch_size, sample_size, std_scale=1.0, graph=True, draw_form=None):
+    def __init__(self, cdae, cfg, batch_size, sample_size, std_scale=1.0, graph=True, draw_form=None, fused_first=None):
         self._pair(cdae, cfg)
         if int(cfg.nsigma) < 1 or int(batch_size) < 1 or int(sample_size) < 1:
             raise ValueError(f"nsigma, batch_size and sample_size must be positive (got {cfg.nsigma}, {batch_size}, {sample_size})")
@@ -369,7 +372,9 @@ class ArdaeCondScoreEngine(_ScoreEngine):
         else:
             self.draw_form = False
             self.fused_draw = L.debug_knob("ARDAE_FUSED_DRAW", "1") != "0" and bool(L.query("ardae_latent_perturb_draw_ok", self.S, self.nstd, self.z))
-            self.fused_first = (self.fused_draw and L.debug_knob("ARDAE_FUSED_A1", "1") != "0"
+            # fused_first=None: the measured default of the network's kind (on for kinds 0 / 1); a bool asks for it, where the shape allows
+            want = (int(cdae._desc.kind) < 2 or self.FUSED_FIRST_NOENC_DEFAULT) if fused_first is None else bool(fused_first)
+            self.fused_first = (want and self.fused_draw and L.debug_knob("ARDAE_FUSED_A1", "1") != "0"
                                 and bool(L.query("ardae_cdae_perturb_fused_ok", cdae._desc, self.S, self.nstd)))
 
     def _front(self, drawn):
