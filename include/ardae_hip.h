@@ -109,7 +109,9 @@ typedef struct ardae_wgrad_problem {
   const float* X[2]; int ldX[2]; /* [M, I] input-side factors                                                */
   int bias_pair;              /* pair whose G is column-summed into out_bias / out_rowscale, or -1           */
   const float* rowscale;      /* optional [M]: out_rowscale[o] = sum_m rowscale[m] * G[bias_pair][m][o]      */
-  int splits;                 /* row splits, from ardae_wgrad_splits                                         */
+  int splits;                 /* row splits: ardae_wgrad_splits, or any value >= 1 (it sizes partial and
+                               * partial_vec; the launch sizes nothing from it and may use fewer: the tiled
+                               * kernels run min(256 / tiles in their launch, smallest splits in it))       */
   float* partial;             /* scratch [splits, O, I]                                                      */
   float* partial_vec;         /* scratch [splits, 2, O] (needed when bias_pair >= 0)                         */
   float* out; int ldout;      /* [O, I] view of the gradient buffer (row stride ldout)                       */

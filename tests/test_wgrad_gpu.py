@@ -36,7 +36,7 @@ def run_batch(specs, seed, beta=0.0, pad=0):
         p.bias_pair = npairs - 1 if (wb or wr) else -1
         p.rowscale = sig.data_ptr() if wr else None
         p.splits = lib.ardae_wgrad_splits(M, O, I, len(specs))
-        part = torch.empty(p.splits * O * I, device="cuda"); pvec = torch.empty(p.splits * 2 * O, device="cuda")
+        part = torch.full((p.splits * O * I,), float("nan"), device="cuda"); pvec = torch.full((p.splits * 2 * O,), float("nan"), device="cuda")
         out = torch.full((O, I + 3), float("nan"), device="cuda")        # strided output view, like a block of a wider matrix
         ob = torch.full((O,), float("nan"), device="cuda"); ors = torch.full((O, 5), float("nan"), device="cuda")
         p.partial, p.partial_vec = part.data_ptr(), pvec.data_ptr()
@@ -131,7 +131,7 @@ def _x9_problem(G, X, sig=None):
     p.bias_pair = 0
     p.rowscale = sig.data_ptr() if sig is not None else None
     p.splits = lib.ardae_wgrad_splits(M, O, I, 1)
-    part = torch.empty(p.splits * O * I, device="cuda"); pvec = torch.empty(p.splits * 2 * O, device="cuda")
+    part = torch.full((p.splits * O * I,), float("nan"), device="cuda"); pvec = torch.full((p.splits * 2 * O,), float("nan"), device="cuda")
     out = torch.full((O, I), float("nan"), device="cuda"); ob = torch.full((O,), float("nan"), device="cuda"); ors = torch.full((O,), float("nan"), device="cuda")
     p.partial, p.partial_vec, p.out, p.ldout, p.out_bias = part.data_ptr(), pvec.data_ptr(), out.data_ptr(), I, ob.data_ptr()
     p.out_rowscale, p.ld_rowscale = (ors.data_ptr(), 1) if sig is not None else (None, 0)
