@@ -859,7 +859,8 @@ int ardae_dp_allreduce_mean(void* comm, float* buf, size_t n, void* stream);
 
 /* ---- live per-kernel timing (bench.py roofline): HIP events around every launch on the launch stream ---------- */
 typedef struct ardae_profile_entry {
-  char name[96];   /* kernel name as rocprofv3 prints it (template arguments included)                         */
+  char name[96];   /* kernel name as rocprofv3 prints it (template arguments included); a suffix may follow them:
+                      the per-image kernels append the block that ran, " b16" (16 x 16) or " fast" (lean 32 x 32)   */
   int calls;
   double total_ms; /* sum of event-to-event durations                                                         */
   double flops;    /* algorithmic FLOPs (2*MAC) of those launches                                             */

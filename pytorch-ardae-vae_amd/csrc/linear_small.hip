@@ -645,9 +645,11 @@ __global__ __launch_bounds__(256) void linear_small_chain_kernel(const ScArgs c)
 
 template <int EPI, int ACT>
 int launch_small_pair(const LinArgs& a0, const LinArgs& a1, hipStream_t st) {
+  const bool b16 = small_fast_on() && small_regular16(a0) && small_regular16(a1);
+  const bool lean = !b16 && small_fast_on() && small_regular(a0) && small_regular(a1);
   if (g_prof_enabled) {
-    char name[64];
-    snprintf(name, sizeof(name), "linear_small_pair_kernel<%d, %d>", EPI, ACT);
+    char name[64];      // the block that runs follows the template arguments: the family (before '<') stays one
+    snprintf(name, sizeof(name), "linear_small_pair_kernel<%d, %d>%s", EPI, ACT, b16 ? " b16" : lean ? " fast" : "");
     double fl = 0, by = 0;
     for (const LinArgs* a : {&a0, &a1}) {
       double ksum = 0;
@@ -658,9 +660,9 @@ int launch_small_pair(const LinArgs& a0, const LinArgs& a1, hipStream_t st) {
     prof_begin(st, name, fl, by);
   }
   const dim3 grid(std::max(ceil_div(a0.M, 32), ceil_div(a1.M, 32)), std::max(ceil_div(a0.Nout, 32), ceil_div(a1.Nout, 32)), 2);
-  if (small_fast_on() && small_regular16(a0) && small_regular16(a1))
+  if (b16)
     hipLaunchKernelGGL((linear_small16_pair_kernel<EPI, ACT>), dim3(std::max(a0.M, a1.M) / 16, ceil_div(std::max(a0.Nout, a1.Nout), 16), 2), dim3(256), 0, st, a0, a1);
-  else if (small_fast_on() && small_regular(a0) && small_regular(a1))
+  else if (lean)
     hipLaunchKernelGGL((linear_small_fast_pair_kernel<EPI, ACT>), grid, dim3(256), 0, st, a0, a1);
   else
     hipLaunchKernelGGL((linear_small_pair_kernel<EPI, ACT>), grid, dim3(256), 0, st, a0, a1);
@@ -671,18 +673,20 @@ int launch_small_pair(const LinArgs& a0, const LinArgs& a1, hipStream_t st) {
 
 template <int EPI, int ACT>
 int launch_small(const LinArgs& a, hipStream_t st) {
+  const bool b16 = small_fast_on() && small_regular16(a);
+  const bool lean = !b16 && small_fast_on() && small_regular(a);
   if (g_prof_enabled) {
-    char name[64];
-    snprintf(name, sizeof(name), "linear_small_kernel<%d, %d>", EPI, ACT);
+    char name[64];      // the block that runs follows the template arguments: the family (before '<') stays one
+    snprintf(name, sizeof(name), "linear_small_kernel<%d, %d>%s", EPI, ACT, b16 ? " b16" : lean ? " fast" : "");
     double ksum = 0;
     for (int s = 0; s < a.nsrc; ++s) ksum += a.src[s].K;
     const double tensors = 1.0 + (a.Y2 ? 1 : 0) + ((EPI == EPI_DACT || EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_CHAIN) ? 1 : 0) +
                            ((EPI == EPI_DACT && a.Q) ? 1 : 0);
     prof_begin(st, name, 2.0 * a.M * (double)a.Nout * ksum, 4.0 * ((double)a.M * ksum + tensors * a.M * (double)a.Nout + ksum * a.Nout));
   }
-  if (small_fast_on() && small_regular16(a))
+  if (b16)
     hipLaunchKernelGGL((linear_small16_kernel<EPI, ACT>), dim3(a.M / 16, ceil_div(a.Nout, 16)), dim3(256), 0, st, a);
-  else if (small_fast_on() && small_regular(a))
+  else if (lean)
     hipLaunchKernelGGL((linear_small_fast_kernel<EPI, ACT>), dim3(a.M / 32, a.Nout / 32), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((linear_small_kernel<EPI, ACT>), dim3(ceil_div(a.M, 32), ceil_div(a.Nout, 32)), dim3(256), 0, st, a);

@@ -77,6 +77,9 @@ bool linear_wide_eligible(const LinArgs& a, int epi) {
     if ((int64_t)a.src[s].ld * a.M * 4 >= (int64_t)1 << 32) return false;   // 32-bit buffer offsets
   }
   if (epi == EPI_DAE_LOSS) return false;   // Nout = z_dim there (narrow geometry)
+  // per-tile column sums: the caller sizes colsum by linear_row_tiles(), the kernel writes one row per WBM rows - K = 512 with
+  // Nout >= 512 is eligible from 2048 rows, where linear_row_tile() still answers 32 (small-M geometry): leave those to linear_kernel
+  if (a.colsum && linear_row_tile(a.M, a.Nout) != WBM) return false;
   if (a.src[0].K == 1024) {               // the instantiated K = 1024 epilogues: softplus forward layers (no score seed), DACT without Q
     if (a.act != ACT_SOFTPLUS) return false;
     if (!((epi == EPI_ACT && !a.Y2) || (epi == EPI_DACT && !a.Q))) return false;

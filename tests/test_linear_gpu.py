@@ -272,13 +272,50 @@ def test_linear_per_image_blocks_bit_identical(Ks, Nout, epi):
 
     # 512 rows: 32 x 32 blocks (lean where the shape is regular, generic otherwise); 500 / 529: ragged rows, always the generic block;
     # 16 .. 64 rows: 16 x 16 blocks (at most 64 blocks of 32 x 32 in the layer; Nout = 784 only up to 64 rows)
+    def block_of(M):
+        """run(M) with the profile log on: -> (outputs, the per-image block the log names: "b16", "fast" or "" for the generic one)"""
+        L.lib().ardae_profile_enable(1)
+        try:
+            out = run(M)
+            names = [e["name"] for e in L.profile_report(max_entries=8)]
+        finally:
+            L.lib().ardae_profile_enable(0)
+        assert len(names) == 1 and names[0].startswith("linear_small_kernel<"), names
+        return out, names[0].partition(">")[2].strip()
+
+    def want_block(M):      # linear_small.hip: small_regular16, then small_regular (the operands here are 16-byte aligned, ld = K)
+        blocks = -(-M // 32) * -(-Nout // 32)
+        if M % 16 == 0 and blocks <= 64 and all(K >= 4 and K % 4 == 0 for K in Ks):
+            return "b16"
+        return "fast" if len(Ks) == 1 and Ks[0] % 8 == 0 and M % 32 == 0 and Nout % 32 == 0 else ""
+
+    small_on = int(L.debug_knob("ARDAE_SMALL", "1")) != 0        # (the fallback-paths run of this file: everything on linear_kernel)
     ref = run(Mbig)
+    seen = set()
+    if small_on:
+        _, blk = block_of(Mbig)
+        assert blk == want_block(Mbig), (Mbig, blk)
+        seen.add(blk)
     for M in (16, 32, 64, 128, 500, 529):
-        got = run(M)
+        if small_on:
+            got, blk = block_of(M)
+            assert blk == want_block(M), (M, blk)
+            assert blk == "" or M not in (500, 529), (M, blk)             # ragged rows: always the generic block
+            seen.add(blk)
+        else:
+            got = run(M)
         m = min(M, Mbig)
         for r, o in zip(ref, got):
             assert not torch.isnan(o).any()
             assert torch.equal(r[:m], o[:m]), (M, float((r[:m] - o[:m]).abs().max()))
+    if small_on:
+        # "the same bits on all three blocks" needs three blocks: 16 x 16 for 16 / 32 / 64 rows wherever every K is a multiple of 4, the lean
+        # block for 512 rows of a regular shape with more than 64 blocks, the generic one for 500 / 529 rows
+        if all(K % 4 == 0 for K in Ks):
+            assert all(want_block(M) == "b16" for M in (16, 32, 64)) and "b16" in seen
+        if len(Ks) == 1 and Ks[0] % 8 == 0 and Nout % 32 == 0 and Nout > 128:
+            assert want_block(Mbig) == "fast" and seen == {"b16", "fast", ""}, seen
+        assert "" in seen
 
 
 @pytest.mark.parametrize("act", ["relu", "softplus"])

@@ -71,12 +71,14 @@ def _ints(shape, lo, hi, gen):
 
 
 def _full_significands(shape, gen, emax, zeros=0.05):
-    """+-(1 + j 2^-23) 10^e, j in [1, 2^23), e in [-emax, emax], rounded to fp32 once; a fraction `zeros` of exact zeros."""
-    j = torch.randint(1, 1 << 23, shape, device="cuda", generator=gen).double()
-    e = torch.randint(-emax, emax + 1, shape, device="cuda", generator=gen).double()
-    s = torch.randint(0, 2, shape, device="cuda", generator=gen).double() * 2 - 1
-    v = (s * (1 + j * 2.0 ** -23) * torch.pow(torch.tensor(10.0, dtype=torch.float64, device="cuda"), e)).float()
-    v[torch.rand(shape, device="cuda", generator=gen) < zeros] = 0.0
+    """+-(1 + j 2^-23) 10^e, j in [1, 2^23), e in [-emax, emax], rounded to fp32 once; a fraction `zeros` of exact zeros.  On the
+    generator's device (tests/linear_cases.py draws on the CPU)."""
+    dev = gen.device
+    j = torch.randint(1, 1 << 23, shape, device=dev, generator=gen).double()
+    e = torch.randint(-emax, emax + 1, shape, device=dev, generator=gen).double()
+    s = torch.randint(0, 2, shape, device=dev, generator=gen).double() * 2 - 1
+    v = (s * (1 + j * 2.0 ** -23) * torch.pow(torch.tensor(10.0, dtype=torch.float64, device=dev), e)).float()
+    v[torch.rand(shape, device=dev, generator=gen) < zeros] = 0.0
     return v
 
 
