@@ -48,6 +48,18 @@ inline const char* debug_knob(const char* name) {
   static const bool armed = [] { const char* e = getenv("ARDAE_DEBUG_KNOBS"); return e && e[0] == '1' && e[1] == 0; }();
   return armed ? getenv(name) : nullptr;
 }
+// an on/off knob: on unless set to a number that reads as 0;  an integer knob: `dflt` unless set.  Callers keep the result in a
+// `static const`, so that each knob is read once per process.
+inline bool knob_on(const char* name) {
+  const char* v = debug_knob(name);
+  return !(v && atoi(v) == 0);
+}
+inline int knob_int(const char* name, int dflt) {
+  const char* v = debug_knob(name);
+  return v ? atoi(v) : dflt;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ----------------------------------------------------------------------------------------------
 // activations (reference: utils/models.py:14-32; F.softplus beta=1 threshold=20, F.relu)

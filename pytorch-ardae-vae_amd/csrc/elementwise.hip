@@ -647,7 +647,7 @@ int launch_latent_perturb_draw_fwd(const float* latent, const float* z0, int B, 
   const PerturbDraw dr{seed, off_xi, off_eps, (const StepState*)state, first_row, eps_out, wp1, bias1, a1_out, h, w1s, wfc, e1_out};
   // few images: S workgroups per image, rows split among them (a slice is a whole number of 32-row blocks), until the grid fills the chip
   const int rg = 256 / zd, passes = (int)(per_image >> 8);
-  static const int target_wgs = debug_knob("ARDAE_LP_WGS") ? atoi(debug_knob("ARDAE_LP_WGS")) : 256;
+  static const int target_wgs = knob_int("ARDAE_LP_WGS", 256);
   int S = 1;
   while (B * S < target_wgs && passes % (2 * S) == 0 && (passes / (2 * S)) * rg % 32 == 0) S *= 2;
   const size_t rows_sl = (size_t)(passes / S) * rg;

@@ -384,16 +384,8 @@ template <int TM, int TN, int WM, int WN, int KPANEL, int EPI, int ACT, int MINB
 int launch_geo(const LinArgs& a, hipStream_t st) {
   using G = Geo<TM, TN, WM, WN, KPANEL>;
   dim3 grid(ceil_div(a.M, G::BM), ceil_div(a.Nout, G::BN));
-  if (g_prof_enabled) {
-    char name[96];
-    snprintf(name, sizeof(name), "linear_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", TM, TN, WM, WN, KPANEL, EPI, ACT, MINB);
-    double ksum = 0;
-    for (int s = 0; s < a.nsrc; ++s) ksum += a.src[s].K;
-    // algorithmic bytes: X read once, Y (+Y2) written once, S/R/Q read once, weights once
-    double tensors = 1.0 + (a.Y2 ? 1 : 0) + ((EPI == EPI_DACT || EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_CHAIN) ? 1 : 0) +
-                     ((EPI == EPI_DACT && a.Q) ? 1 : 0);
-    prof_begin(st, name, 2.0 * a.M * (double)a.Nout * ksum, 4.0 * ((double)a.M * ksum + tensors * a.M * (double)a.Nout + ksum * a.Nout));
-  }
+  if (g_prof_enabled)
+    prof_begin_named(st, lin_cost(a, epi_tensors(a, EPI)), "linear_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", TM, TN, WM, WN, KPANEL, EPI, ACT, MINB);
   hipLaunchKernelGGL((linear_kernel<TM, TN, WM, WN, KPANEL, EPI, ACT, MINB>), grid, dim3(256), 0, st, a);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
@@ -463,7 +455,8 @@ int launch_pack_batch(const PackItem* items, int n, hipStream_t st) {
   return 0;
 }
 
-// argument validation of launch_linear
+// argument validation of launch_linear: the one place its arguments are checked, before any eligibility rule, so that neither the
+// checks nor their messages depend on the kernel a shape selects
 int validate_linear(const LinArgs& a, int epi) {
   ARDAE_CHECK_ARG(a.M > 0 && a.Nout > 0, "linear: empty problem (M=%d, Nout=%d)", a.M, a.Nout);
   ARDAE_CHECK_ARG(a.nsrc >= 1 && a.nsrc <= 2, "linear: nsrc must be 1 or 2");
@@ -494,67 +487,21 @@ int validate_linear(const LinArgs& a, int epi) {
 }
 
 int launch_linear(const LinArgs& a, int epi, hipStream_t st) {
-  ARDAE_CHECK_ARG(a.M > 0 && a.Nout > 0, "linear: empty problem (M=%d, Nout=%d)", a.M, a.Nout);
-  ARDAE_CHECK_ARG(a.nsrc >= 1 && a.nsrc <= 2, "linear: nsrc must be 1 or 2");
-  for (int s = 0; s < a.nsrc; ++s)
-    ARDAE_CHECK_ARG(a.src[s].x && a.src[s].wp && a.src[s].K > 0 && a.src[s].ld >= a.src[s].K,
-                    "linear: bad source %d (K=%d ld=%d)", s, a.src[s].K, a.src[s].ld);
-  ARDAE_CHECK_ARG(a.Y || epi == EPI_DAE_LOSS, "linear: Y is null");
-  if (linear_small_eligible(a, epi)) {
-    ARDAE_TRY(validate_linear(a, epi));
-    return launch_linear_small(a, epi, st);
-  }
-  if (linear_narrow_eligible(a, epi)) {
-    ARDAE_TRY(validate_linear(a, epi));
-    return launch_linear_narrow(a, epi, st);
-  }
-  if (linear_shortk_eligible(a, epi)) {
-    ARDAE_TRY(validate_linear(a, epi));
-    return launch_linear_shortk(a, epi, st);
-  }
-  static const bool wide_on = !(debug_knob("ARDAE_WIDE") && atoi(debug_knob("ARDAE_WIDE")) == 0);
-  if (wide_on && linear_wide_eligible(a, epi)) {
-    if (epi == EPI_ACT) ARDAE_CHECK_ARG(!a.rowbias || a.rows_per_group > 0, "linear: rows_per_group must be positive");
-    if (epi == EPI_DACT || epi == EPI_CHAIN) ARDAE_CHECK_ARG(a.S, "linear: EPI_DACT/EPI_CHAIN need S");
-    if (epi == EPI_CHAIN) ARDAE_CHECK_ARG(a.R && a.Y2, "linear: EPI_CHAIN needs S, R and Y2");
-    return launch_linear_wide(a, epi, st);
-  }
+  ARDAE_TRY(validate_linear(a, epi));
+  if (linear_small_eligible(a, epi)) return launch_linear_small(a, epi, st);
+  if (linear_narrow_eligible(a, epi)) return launch_linear_narrow(a, epi, st);
+  if (linear_shortk_eligible(a, epi)) return launch_linear_shortk(a, epi, st);
+  static const bool wide_on = knob_on("ARDAE_WIDE");
+  if (wide_on && linear_wide_eligible(a, epi)) return launch_linear_wide(a, epi, st);
+  int rc = ACT_UNLISTED;
   switch (epi) {
-    case EPI_ACT:
-      ARDAE_CHECK_ARG(!a.rowbias || a.rows_per_group > 0, "linear: rows_per_group must be positive");
-      if (a.act == ACT_NONE) return launch_epi<EPI_ACT, ACT_NONE>(a, st);
-      if (a.act == ACT_RELU) return launch_epi<EPI_ACT, ACT_RELU>(a, st);
-      if (a.act == ACT_SOFTPLUS) return launch_epi<EPI_ACT, ACT_SOFTPLUS>(a, st);
-      if (a.act == ACT_ELU) return launch_epi<EPI_ACT, ACT_ELU>(a, st);
-      if (a.act == ACT_TANH) return launch_epi<EPI_ACT, ACT_TANH>(a, st);
-      if (a.act == ACT_LEAKY) return launch_epi<EPI_ACT, ACT_LEAKY>(a, st);
-      if (a.act == ACT_SWISH) return launch_epi<EPI_ACT, ACT_SWISH>(a, st);
-      break;
-    case EPI_DACT:
-      ARDAE_CHECK_ARG(a.S, "linear: EPI_DACT needs S");
-      if (a.act == ACT_NONE) return launch_epi<EPI_DACT, ACT_NONE>(a, st);
-      if (a.act == ACT_RELU) return launch_epi<EPI_DACT, ACT_RELU>(a, st);
-      if (a.act == ACT_SOFTPLUS) return launch_epi<EPI_DACT, ACT_SOFTPLUS>(a, st);
-      if (a.act == ACT_ELU) return launch_epi<EPI_DACT, ACT_ELU>(a, st);
-      if (a.act == ACT_TANH) return launch_epi<EPI_DACT, ACT_TANH>(a, st);
-      if (a.act == ACT_LEAKY) return launch_epi<EPI_DACT, ACT_LEAKY>(a, st);
-      if (a.act == ACT_SWISH) return launch_epi<EPI_DACT, ACT_SWISH>(a, st);
-      break;
-    case EPI_CHAIN:
-      ARDAE_CHECK_ARG(a.S && a.R && a.Y2, "linear: EPI_CHAIN needs S, R and Y2");
-      if (a.act == ACT_SOFTPLUS) return launch_epi<EPI_CHAIN, ACT_SOFTPLUS>(a, st);
-      if (a.act == ACT_RELU) return launch_epi<EPI_CHAIN, ACT_RELU>(a, st);
-      if (a.act == ACT_ELU) return launch_epi<EPI_CHAIN, ACT_ELU>(a, st);
-      if (a.act == ACT_TANH) return launch_epi<EPI_CHAIN, ACT_TANH>(a, st);
-      if (a.act == ACT_LEAKY) return launch_epi<EPI_CHAIN, ACT_LEAKY>(a, st);
-      if (a.act == ACT_SWISH) return launch_epi<EPI_CHAIN, ACT_SWISH>(a, st);
-      break;
-    case EPI_DAE_LOSS:
-      ARDAE_CHECK_ARG(a.sigma && a.eps, "linear: EPI_DAE_LOSS needs sigma and eps");
-      return launch_epi<EPI_DAE_LOSS, ACT_NONE>(a, st);
+    case EPI_ACT: rc = dispatch_act(ActsAll{}, a.act, [&](auto A) { return launch_epi<EPI_ACT, decltype(A)::value>(a, st); }); break;
+    case EPI_DACT: rc = dispatch_act(ActsAll{}, a.act, [&](auto A) { return launch_epi<EPI_DACT, decltype(A)::value>(a, st); }); break;
+    case EPI_CHAIN: rc = dispatch_act(ActsChainEpi{}, a.act, [&](auto A) { return launch_epi<EPI_CHAIN, decltype(A)::value>(a, st); }); break;
+    case EPI_DAE_LOSS: rc = launch_epi<EPI_DAE_LOSS, ACT_NONE>(a, st); break;
   }
-  ARDAE_CHECK_ARG(false, "linear: unsupported epilogue/activation combination (epi=%d act=%d)", epi, a.act);
-  return -1;
+  ARDAE_CHECK_ARG(rc != ACT_UNLISTED, "linear: unsupported epilogue/activation combination (epi=%d act=%d)", epi, a.act);
+  return rc;
 }
 
 }  // namespace ardae

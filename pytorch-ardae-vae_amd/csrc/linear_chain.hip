@@ -11,17 +11,15 @@ int chain_grid(int ntiles) { return ntiles < 256 ? ntiles : 256; }
 using namespace wide;
 
 namespace {
-bool al16c(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // most row tiles per workgroup for which one launch per chain beats one launch per layer (per-layer launches amortise their
 // fixed cost over the tiles and keep the NEXT tile's panel loads in flight; the chain kernel pays an exposed input load per tile)
 int chain_max_tiles() {
-  static const int v = debug_knob("ARDAE_CHAIN_MAX_TILES") ? atoi(debug_knob("ARDAE_CHAIN_MAX_TILES")) : 1024;
+  static const int v = knob_int("ARDAE_CHAIN_MAX_TILES", 1024);
   return v;
 }
 // ... and for the chains whose last layer stages the next tile (EPI_ACT, EPI_DACT without Q: linear_chain_kernel's PF)
 int chain_pf_max_tiles() {
-  static const int v = debug_knob("ARDAE_CHAIN_PF_MAX_TILES") ? atoi(debug_knob("ARDAE_CHAIN_PF_MAX_TILES")) : 1024;
+  static const int v = knob_int("ARDAE_CHAIN_PF_MAX_TILES", 1024);
   return v;
 }
 }  // namespace
@@ -54,7 +52,7 @@ bool linear_chain_eligible(const LinArgs* L, int nl, int epi) {
       if (a.act != ACT_SOFTPLUS || !a.Y2 || !a.R) return false;
       if (a.colsum && l != nl - 1) return false;
     }
-    if (!al16c(a.src[0].wp)) return false;
+    if (!aligned16(a.src[0].wp)) return false;
   }
   return true;
 }
@@ -65,24 +63,24 @@ int launch_linear_chain(const LinArgs* L, int nl, int epi, hipStream_t st) {
   memset(&ca, 0, sizeof(ca));
   ca.nl = nl; ca.M = L[0].M;
   for (int l = 0; l < nl; ++l) ca.L[l] = L[l];
-  const int act = L[0].act;
+  const int act = L[0].act;      // one of its list: the eligibility rule has admitted it
   if (epi == EPI_ACT) {
     const bool f2 = L[0].rowbias != nullptr, f1 = L[nl - 1].Y2 != nullptr;
-    if (act == ACT_SOFTPLUS) {
-      if (f2 && f1) return launch_chain<EPI_ACT, ACT_SOFTPLUS, true, true, false>(ca, st);
-      if (f2) return launch_chain<EPI_ACT, ACT_SOFTPLUS, true, false, false>(ca, st);
-      return launch_chain<EPI_ACT, ACT_SOFTPLUS, false, false, false>(ca, st);
-    }
-    if (f2 && f1) return launch_chain<EPI_ACT, ACT_RELU, true, true, false>(ca, st);
-    if (f2) return launch_chain<EPI_ACT, ACT_RELU, true, false, false>(ca, st);
-    return launch_chain<EPI_ACT, ACT_RELU, false, false, false>(ca, st);
+    return dispatch_act(ActsHidden{}, act, [&](auto A) {
+      constexpr int ACT = decltype(A)::value;
+      if (f2 && f1) return launch_chain<EPI_ACT, ACT, true, true, false>(ca, st);
+      if (f2) return launch_chain<EPI_ACT, ACT, true, false, false>(ca, st);
+      return launch_chain<EPI_ACT, ACT, false, false, false>(ca, st);
+    });
   }
   if (epi == EPI_DACT) {
     const bool fq = L[0].Q != nullptr;
-    if (act == ACT_SOFTPLUS) return fq ? launch_chain<EPI_DACT, ACT_SOFTPLUS, false, false, true>(ca, st) : launch_chain<EPI_DACT, ACT_SOFTPLUS, false, false, false>(ca, st);
-    return fq ? launch_chain<EPI_DACT, ACT_RELU, false, false, true>(ca, st) : launch_chain<EPI_DACT, ACT_RELU, false, false, false>(ca, st);
+    return dispatch_act(ActsHidden{}, act, [&](auto A) {
+      constexpr int ACT = decltype(A)::value;
+      return fq ? launch_chain<EPI_DACT, ACT, false, false, true>(ca, st) : launch_chain<EPI_DACT, ACT, false, false, false>(ca, st);
+    });
   }
-  return launch_chain<EPI_CHAIN, ACT_SOFTPLUS, false, false, false>(ca, st);
+  return dispatch_act(ActsSoftplus{}, act, [&](auto A) { return launch_chain<EPI_CHAIN, decltype(A)::value, false, false, false>(ca, st); });
 }
 
 }  // namespace ardae

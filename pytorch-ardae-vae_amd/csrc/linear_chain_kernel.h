@@ -340,15 +340,12 @@ int launch_chain(const ChainArgs& ca, hipStream_t st) {
     attr_set = true;
   }
   if (g_prof_enabled) {
-    char name[96];
-    snprintf(name, sizeof(name), "linear_chain_kernel<%d, %d, %d, %d, %d> x%d", EPI, ACT, (int)F2F, (int)F1L, (int)FQ, ca.nl);
     double tensors = 0;
-    for (int l = 0; l < ca.nl; ++l) {
-      const LinArgs& a = ca.L[l];
-      tensors += 1.0 + (a.Y2 ? 1 : 0) + ((EPI == EPI_DACT || EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_DACT && a.Q) ? 1 : 0);
-    }
-    // algorithmic bytes: the chain's input once, every layer's operands / results (the weight gradients need them), the weights
-    prof_begin(st, name, ca.nl * 2.0 * ca.M * 256.0 * 256.0, 4.0 * ((double)ca.M * 256.0 * (1.0 + tensors) + ca.nl * 256.0 * 256.0));
+    for (int l = 0; l < ca.nl; ++l) tensors += epi_tensors(ca.L[l], EPI);
+    // algorithmic bytes: the chain's input ONCE (not once per layer, so not lin_cost), every layer's operands / results (the weight
+    // gradients need them), the weights
+    const LinCost cost{ca.nl * 2.0 * ca.M * 256.0 * 256.0, 4.0 * ((double)ca.M * 256.0 * (1.0 + tensors) + ca.nl * 256.0 * 256.0)};
+    prof_begin_named(st, cost, "linear_chain_kernel<%d, %d, %d, %d, %d> x%d", EPI, ACT, (int)F2F, (int)F1L, (int)FQ, ca.nl);
   }
   hipLaunchKernelGGL(kern, dim3(chain_grid(nrt)), dim3(256), lds_bytes, st, ca, nrt);
   prof_end(st);

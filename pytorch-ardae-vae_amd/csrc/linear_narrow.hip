@@ -96,11 +96,9 @@ __global__ __launch_bounds__(256) void linear_narrow_kernel(const LinArgs a) {
 
 template <int EPI>
 int launch_narrow(const LinArgs& a, hipStream_t st) {
-  if (g_prof_enabled) {
-    char name[64];
-    snprintf(name, sizeof(name), "linear_narrow_kernel<%d>", EPI);
+  if (g_prof_enabled) {      // K = 256; the plain layer writes Y, the DAE loss whichever of Y and Y2 it is given and reads eps
     const double tensors = EPI == EPI_DAE_LOSS ? (1.0 + (a.Y ? 1 : 0) + (a.Y2 ? 1 : 0)) : 1.0;
-    prof_begin(st, name, 2.0 * a.M * (double)a.Nout * 256.0, 4.0 * ((double)a.M * 256.0 + tensors * a.M * (double)a.Nout + 256.0 * a.Nout));
+    prof_begin_named(st, lin_cost(a, tensors), "linear_narrow_kernel<%d>", EPI);
   }
   hipLaunchKernelGGL((linear_narrow_kernel<EPI>), dim3(a.M / 128), dim3(256), 0, st, a);
   prof_end(st);
@@ -113,9 +111,9 @@ int launch_narrow(const LinArgs& a, hipStream_t st) {
 // One source of K = 256, Nout <= 32, whole 128-row tiles (the row-tile size the per-tile loss partials are sized for:
 // linear_row_tile() of the narrow geometry), vector-aligned rows; plain bias epilogue or the DAE loss.  ARDAE_NARROW=0: off.
 bool linear_narrow_eligible(const LinArgs& a, int epi) {
-  static const bool on = !(debug_knob("ARDAE_NARROW") && atoi(debug_knob("ARDAE_NARROW")) == 0);
+  static const bool on = knob_on("ARDAE_NARROW");
   if (!on || a.nsrc != 1 || a.src[0].K != 256 || a.Nout <= 0 || a.Nout > 32 || a.M <= 0 || (a.M % 128)) return false;
-  if ((a.src[0].ld & 3) || (reinterpret_cast<uintptr_t>(a.src[0].x) & 15) || a.colsum != nullptr) return false;
+  if ((a.src[0].ld & 3) || !aligned16(a.src[0].x) || a.colsum != nullptr) return false;
   if (epi == EPI_ACT) return a.act == ACT_NONE && !a.rowbias && !a.rowscale && !a.Y2 && a.Y != nullptr;
   if (epi == EPI_DAE_LOSS) return a.tile_loss != nullptr && a.sigma != nullptr && a.eps != nullptr;
   return false;

@@ -385,18 +385,19 @@ __global__ __launch_bounds__(256, 1) void sampler_tail_ws_kernel(const LinArgs a
 }
 
 inline bool tail_ws_eligible(const LinArgs& a, const TailOut& o1) {
-  static const bool on = !(debug_knob("ARDAE_TAIL_WS") && atoi(debug_knob("ARDAE_TAIL_WS")) == 0);
+  static const bool on = knob_on("ARDAE_TAIL_WS");
   return on && !o1.wp && a.Nout == 256 && ((a.src[0].K + 7) >> 3) <= TW_CH && (!a.rowbias || a.rows_per_group >= 32);
+}
+
+// two layers, the hidden rows on chip: X in, the nc latent columns out, both weight matrices once
+inline LinCost tail_cost(const LinArgs& a, int nc) {
+  const double M = a.M, H = a.Nout, K = a.src[0].K;
+  return {2.0 * M * (H * K + H * nc), 4.0 * (M * K + M * nc + K * H + H * nc)};
 }
 
 template <int ACT>
 int launch_tail_ws(const LinArgs& a, const TailOut& o0, int n2, hipStream_t st) {
-  if (g_prof_enabled) {
-    char name[64];
-    snprintf(name, sizeof(name), "sampler_tail_ws_kernel<%d>", ACT);
-    const double K = a.src[0].K, nc = (double)n2;
-    prof_begin(st, name, 2.0 * a.M * ((double)a.Nout * K + (double)a.Nout * nc), 4.0 * ((double)a.M * K + (double)a.M * nc + K * a.Nout + (double)a.Nout * nc));
-  }
+  if (g_prof_enabled) prof_begin_named(st, tail_cost(a, n2), "sampler_tail_ws_kernel<%d>", ACT);
   const int nrb = a.M / 32;
   hipLaunchKernelGGL((sampler_tail_ws_kernel<ACT>), dim3(std::min(nrb, 256)), dim3(256), 0, st, a, o0, n2, nrb);
   prof_end(st);
@@ -406,14 +407,9 @@ int launch_tail_ws(const LinArgs& a, const TailOut& o0, int n2, hipStream_t st) 
 
 template <int ACT, int MAXCH, int NOUT2>
 int launch_tail_ch(const LinArgs& a, const TailOut& o0, const TailOut& o1, int n2, hipStream_t st) {
-  if (g_prof_enabled) {
-    char name[64];
-    snprintf(name, sizeof(name), "sampler_tail_kernel<%d, %d, %d>", ACT, MAXCH, NOUT2);
-    const double K = a.src[0].K, nc = (double)n2 * NOUT2;
-    prof_begin(st, name, 2.0 * a.M * ((double)a.Nout * K + (double)a.Nout * nc), 4.0 * ((double)a.M * K + (double)a.M * nc + K * a.Nout + (double)a.Nout * nc));
-  }
+  if (g_prof_enabled) prof_begin_named(st, tail_cost(a, n2 * NOUT2), "sampler_tail_kernel<%d, %d, %d>", ACT, MAXCH, NOUT2);
   // few rows: split the hidden columns over 2 / 4 waves until the grid fills the chip (ARDAE_TAIL_SPLIT=1: never)
-  static const int max_cs = debug_knob("ARDAE_TAIL_SPLIT") ? atoi(debug_knob("ARDAE_TAIL_SPLIT")) : 4;
+  static const int max_cs = knob_int("ARDAE_TAIL_SPLIT", 4);
   int cs = 1;
   while (cs < max_cs && cs < 4 && (a.M / 128) * (2 * cs) <= 256 && (a.Nout / 32) % (2 * cs) == 0) cs *= 2;
   hipLaunchKernelGGL((sampler_tail_kernel<ACT, MAXCH, NOUT2>), dim3(a.M / 128 * cs), dim3(256), 0, st, a, o0, o1, n2, cs);
@@ -437,12 +433,7 @@ int launch_tail(const LinArgs& a, const TailOut& o0, const TailOut& o1, int n2, 
 
 template <int ACT, int MAXCH>
 int launch_shortk_ch(const LinArgs& a, hipStream_t st) {
-  if (g_prof_enabled) {
-    char name[64];
-    snprintf(name, sizeof(name), "linear_shortk_kernel<%d, %d>", ACT, MAXCH);
-    const double K = a.src[0].K;
-    prof_begin(st, name, 2.0 * a.M * (double)a.Nout * K, 4.0 * ((double)a.M * K + (double)a.M * a.Nout + K * a.Nout));
-  }
+  if (g_prof_enabled) prof_begin_named(st, lin_cost(a, 1.0), "linear_shortk_kernel<%d, %d>", ACT, MAXCH);
   hipLaunchKernelGGL((linear_shortk_kernel<ACT, MAXCH>), dim3(a.M / 128), dim3(256), 0, st, a);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
@@ -463,12 +454,12 @@ int launch_shortk(const LinArgs& a, hipStream_t st) {
 // blocks, >= 8192 rows (64 workgroups: from there on it beats the generic kernel - at the 64-image shard of the 8-GPU run, 16384
 // rows, the fused sampler is 1.7 % of the step); forward epilogue (bias, per-image row bias, activation) only.  ARDAE_SHORTK=0: off.
 bool linear_shortk_eligible(const LinArgs& a, int epi) {
-  static const bool on = !(debug_knob("ARDAE_SHORTK") && atoi(debug_knob("ARDAE_SHORTK")) == 0);
+  static const bool on = knob_on("ARDAE_SHORTK");
   if (!on || epi != EPI_ACT || a.nsrc != 1) return false;
   const int K = a.src[0].K;
   if (K <= 0 || K > SK_MAXK || (K & 3) || K % 32 == 0) return false;
   if (a.M < 128 * 64 || (a.M % 128) || a.Nout <= 0 || (a.Nout % 32)) return false;
-  if ((a.src[0].ld & 3) || (reinterpret_cast<uintptr_t>(a.src[0].x) & 15)) return false;
+  if ((a.src[0].ld & 3) || !aligned16(a.src[0].x)) return false;
   if (a.rowscale || a.Y2 || a.colsum || !a.Y) return false;
   if (a.rowbias && a.rows_per_group <= 0) return false;
   return a.act == ACT_NONE || a.act == ACT_RELU || a.act == ACT_SOFTPLUS;
@@ -477,7 +468,7 @@ bool linear_shortk_eligible(const LinArgs& a, int epi) {
 // `first` is the short-K layer as launch_linear would get it (its Y is ignored), followed by Z = hidden . W2^T + b2 with N2 <= 32
 // columns.  ARDAE_SAMPLER_TAIL=0: off.
 bool sampler_tail_eligible(const LinArgs& first, int n2) {
-  static const bool on = !(debug_knob("ARDAE_SAMPLER_TAIL") && atoi(debug_knob("ARDAE_SAMPLER_TAIL")) == 0);
+  static const bool on = knob_on("ARDAE_SAMPLER_TAIL");
   if (!on || n2 < 1 || n2 > 32) return false;
   LinArgs a = first;
   if (!a.Y) a.Y = const_cast<float*>(a.src[0].x);   // the single-layer rule wants an output pointer; unused here
@@ -489,16 +480,15 @@ int launch_sampler_tail(const LinArgs& first, const float* wp2, const float* bia
                         const float* wp2b, const float* bias2b, float* Zb, int ldzb) {
   ARDAE_CHECK_ARG(sampler_tail_eligible(first, n2) && wp2 && Z && ldz >= n2 && (!wp2b || (Zb && ldzb >= n2)), "sampler tail: shape not eligible");
   const TailOut o0{wp2, bias2, Z, ldz}, o1{wp2b, bias2b, Zb, ldzb};
-  if (first.act == ACT_RELU) return launch_tail<ACT_RELU>(first, o0, o1, n2, st);
-  if (first.act == ACT_SOFTPLUS) return launch_tail<ACT_SOFTPLUS>(first, o0, o1, n2, st);
-  return launch_tail<ACT_NONE>(first, o0, o1, n2, st);
+  const int rc = dispatch_act(ActsShipped{}, first.act, [&](auto A) { return launch_tail<decltype(A)::value>(first, o0, o1, n2, st); });
+  ARDAE_CHECK_ARG(rc != ACT_UNLISTED, "sampler tail: shape not eligible");
+  return rc;
 }
 
 int launch_linear_shortk(const LinArgs& a, int epi, hipStream_t st) {
-  (void)epi;
-  if (a.act == ACT_RELU) return launch_shortk<ACT_RELU>(a, st);
-  if (a.act == ACT_SOFTPLUS) return launch_shortk<ACT_SOFTPLUS>(a, st);
-  return launch_shortk<ACT_NONE>(a, st);
+  const int rc = dispatch_act(ActsShipped{}, a.act, [&](auto A) { return launch_shortk<decltype(A)::value>(a, st); });
+  ARDAE_CHECK_ARG(rc != ACT_UNLISTED, "linear_shortk: shape not eligible (epi=%d act=%d)", epi, a.act);
+  return rc;
 }
 
 }  // namespace ardae

@@ -429,21 +429,39 @@ __device__ __forceinline__ void small_block16(const LinArgs& a, int bx, int by, 
 
 // what small_block_fast assumes (host side)
 inline bool small_fast_on() {     // ARDAE_SMALL_FAST=0: the generic block everywhere (A/B)
-  static const bool on = !(debug_knob("ARDAE_SMALL_FAST") && atoi(debug_knob("ARDAE_SMALL_FAST")) == 0);
+  static const bool on = knob_on("ARDAE_SMALL_FAST");
   return on;
 }
 inline bool small_regular(const LinArgs& a) {
-  return a.nsrc == 1 && a.src[0].K >= 8 && a.src[0].K % 8 == 0 && a.src[0].ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.src[0].x) & 15) == 0 &&
-         a.M % 32 == 0 && a.Nout % 32 == 0;
+  return a.nsrc == 1 && a.src[0].K >= 8 && a.src[0].K % 8 == 0 && a.src[0].ld % 4 == 0 && aligned16(a.src[0].x) && a.M % 32 == 0 && a.Nout % 32 == 0;
 }
 
 // what small_block16 assumes, and when it pays: the layer has few 32 x 32 blocks (ARDAE_SMALL16_MAX_BLOCKS, default 64)
 inline bool small_regular16(const LinArgs& a) {
-  static const int max_blocks = debug_knob("ARDAE_SMALL16_MAX_BLOCKS") ? atoi(debug_knob("ARDAE_SMALL16_MAX_BLOCKS")) : 64;
+  static const int max_blocks = knob_int("ARDAE_SMALL16_MAX_BLOCKS", 64);
   if (a.nsrc < 1 || a.nsrc > 2 || a.M % 16 || a.Nout < 1 || (int64_t)ceil_div(a.M, 32) * ceil_div(a.Nout, 32) > max_blocks) return false;
   for (int s = 0; s < a.nsrc; ++s)      // float4 fragments: rows 16-byte aligned, K a multiple of 4 (a partial last step of 16 k is fine)
-    if (a.src[s].K < 4 || a.src[s].K % 4 || a.src[s].ld % 4 || (reinterpret_cast<uintptr_t>(a.src[s].x) & 15)) return false;
+    if (a.src[s].K < 4 || a.src[s].K % 4 || a.src[s].ld % 4 || !aligned16(a.src[s].x)) return false;
   return true;
+}
+
+// The three per-image blocks, weakest first: small_block (any shape), small_block_fast, small_block16.
+enum SmallBlk { SMALL_GENERIC, SMALL_FAST, SMALL_B16 };
+inline bool small_allows(const LinArgs& a, SmallBlk b) {
+  return b == SMALL_GENERIC || (small_fast_on() && (b == SMALL_B16 ? small_regular16(a) : small_regular(a)));
+}
+// the block of a launch: the strongest one its problem allows - of a pair, both problems
+inline SmallBlk small_pick(const LinArgs& a, const LinArgs* second = nullptr) {
+  for (SmallBlk b : {SMALL_B16, SMALL_FAST})
+    if (small_allows(a, b) && (!second || small_allows(*second, b))) return b;
+  return SMALL_GENERIC;
+}
+// the profile log names the block behind the template arguments: the family (before '<') stays one
+inline const char* small_suffix(SmallBlk b) { return b == SMALL_B16 ? " b16" : b == SMALL_FAST ? " fast" : ""; }
+// one workgroup per block of 16 x 16 (b16) or 32 x 32 outputs; a pair (nz = 2) covers the larger problem
+inline dim3 small_grid(SmallBlk b, int M, int Nout, int nz) {
+  const int edge = b == SMALL_B16 ? 16 : 32;
+  return dim3(ceil_div(M, edge), ceil_div(Nout, edge), nz);
 }
 
 template <int EPI, int ACT>
@@ -645,24 +663,15 @@ __global__ __launch_bounds__(256) void linear_small_chain_kernel(const ScArgs c)
 
 template <int EPI, int ACT>
 int launch_small_pair(const LinArgs& a0, const LinArgs& a1, hipStream_t st) {
-  const bool b16 = small_fast_on() && small_regular16(a0) && small_regular16(a1);
-  const bool lean = !b16 && small_fast_on() && small_regular(a0) && small_regular(a1);
+  const SmallBlk blk = small_pick(a0, &a1);
   if (g_prof_enabled) {
-    char name[64];      // the block that runs follows the template arguments: the family (before '<') stays one
-    snprintf(name, sizeof(name), "linear_small_pair_kernel<%d, %d>%s", EPI, ACT, b16 ? " b16" : lean ? " fast" : "");
-    double fl = 0, by = 0;
-    for (const LinArgs* a : {&a0, &a1}) {
-      double ksum = 0;
-      for (int s = 0; s < a->nsrc; ++s) ksum += a->src[s].K;
-      fl += 2.0 * a->M * (double)a->Nout * ksum;
-      by += 4.0 * ((double)a->M * ksum + 2.0 * a->M * (double)a->Nout + ksum * a->Nout);
-    }
-    prof_begin(st, name, fl, by);
+    const LinArgs both[2] = {a0, a1};      // X, Y and the weights: a pair is two plain forward layers
+    prof_begin_named(st, lin_cost_sum(both, 2, [](const LinArgs&) { return 2.0; }), "linear_small_pair_kernel<%d, %d>%s", EPI, ACT, small_suffix(blk));
   }
-  const dim3 grid(std::max(ceil_div(a0.M, 32), ceil_div(a1.M, 32)), std::max(ceil_div(a0.Nout, 32), ceil_div(a1.Nout, 32)), 2);
-  if (b16)
-    hipLaunchKernelGGL((linear_small16_pair_kernel<EPI, ACT>), dim3(std::max(a0.M, a1.M) / 16, ceil_div(std::max(a0.Nout, a1.Nout), 16), 2), dim3(256), 0, st, a0, a1);
-  else if (lean)
+  const dim3 grid = small_grid(blk, std::max(a0.M, a1.M), std::max(a0.Nout, a1.Nout), 2);
+  if (blk == SMALL_B16)
+    hipLaunchKernelGGL((linear_small16_pair_kernel<EPI, ACT>), grid, dim3(256), 0, st, a0, a1);
+  else if (blk == SMALL_FAST)
     hipLaunchKernelGGL((linear_small_fast_pair_kernel<EPI, ACT>), grid, dim3(256), 0, st, a0, a1);
   else
     hipLaunchKernelGGL((linear_small_pair_kernel<EPI, ACT>), grid, dim3(256), 0, st, a0, a1);
@@ -673,23 +682,15 @@ int launch_small_pair(const LinArgs& a0, const LinArgs& a1, hipStream_t st) {
 
 template <int EPI, int ACT>
 int launch_small(const LinArgs& a, hipStream_t st) {
-  const bool b16 = small_fast_on() && small_regular16(a);
-  const bool lean = !b16 && small_fast_on() && small_regular(a);
-  if (g_prof_enabled) {
-    char name[64];      // the block that runs follows the template arguments: the family (before '<') stays one
-    snprintf(name, sizeof(name), "linear_small_kernel<%d, %d>%s", EPI, ACT, b16 ? " b16" : lean ? " fast" : "");
-    double ksum = 0;
-    for (int s = 0; s < a.nsrc; ++s) ksum += a.src[s].K;
-    const double tensors = 1.0 + (a.Y2 ? 1 : 0) + ((EPI == EPI_DACT || EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_CHAIN) ? 1 : 0) +
-                           ((EPI == EPI_DACT && a.Q) ? 1 : 0);
-    prof_begin(st, name, 2.0 * a.M * (double)a.Nout * ksum, 4.0 * ((double)a.M * ksum + tensors * a.M * (double)a.Nout + ksum * a.Nout));
-  }
-  if (b16)
-    hipLaunchKernelGGL((linear_small16_kernel<EPI, ACT>), dim3(a.M / 16, ceil_div(a.Nout, 16)), dim3(256), 0, st, a);
-  else if (lean)
-    hipLaunchKernelGGL((linear_small_fast_kernel<EPI, ACT>), dim3(a.M / 32, a.Nout / 32), dim3(256), 0, st, a);
+  const SmallBlk blk = small_pick(a);
+  if (g_prof_enabled) prof_begin_named(st, lin_cost(a, epi_tensors(a, EPI)), "linear_small_kernel<%d, %d>%s", EPI, ACT, small_suffix(blk));
+  const dim3 grid = small_grid(blk, a.M, a.Nout, 1);
+  if (blk == SMALL_B16)
+    hipLaunchKernelGGL((linear_small16_kernel<EPI, ACT>), grid, dim3(256), 0, st, a);
+  else if (blk == SMALL_FAST)
+    hipLaunchKernelGGL((linear_small_fast_kernel<EPI, ACT>), grid, dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL((linear_small_kernel<EPI, ACT>), dim3(ceil_div(a.M, 32), ceil_div(a.Nout, 32)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((linear_small_kernel<EPI, ACT>), grid, dim3(256), 0, st, a);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
   return 0;
@@ -700,8 +701,8 @@ int launch_small(const LinArgs& a, hipStream_t st) {
 // Per-image problems only: up to SMALL_MAX_TILES workgroups (beyond that the throughput tilings win), no per-tile side
 // outputs (column sums, DAE-loss partials: those belong to N-row launches).  ARDAE_SMALL=0 switches the kernel off.
 bool linear_small_eligible(const LinArgs& a, int epi) {
-  static const bool on = !(debug_knob("ARDAE_SMALL") && atoi(debug_knob("ARDAE_SMALL")) == 0);
-  static const int max_tiles = debug_knob("ARDAE_SMALL_MAX_TILES") ? atoi(debug_knob("ARDAE_SMALL_MAX_TILES")) : 512;
+  static const bool on = knob_on("ARDAE_SMALL");
+  static const int max_tiles = knob_int("ARDAE_SMALL_MAX_TILES", 512);
   if (!on || epi == EPI_DAE_LOSS || a.colsum != nullptr || a.tile_loss != nullptr) return false;
   if (a.M <= 0 || a.Nout <= 0) return false;
   if (epi == EPI_CHAIN && a.act == ACT_NONE) return false;
@@ -713,7 +714,7 @@ namespace {
 // another value, for the test of the fallback.
 int sc_resident_cap() {
   static const int cap = [] {
-    if (debug_knob("ARDAE_SC_CAP")) return atoi(debug_knob("ARDAE_SC_CAP"));
+    if (debug_knob("ARDAE_SC_CAP")) return knob_int("ARDAE_SC_CAP", 0);
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, linear_small_chain_kernel, 256, 0) != hipSuccess)
@@ -774,7 +775,7 @@ bool sc_fill(const LinArgs& a, int epi, ScProblem& q) {
 // one launch per problem when a problem does not qualify for the split-K kernel.
 int launch_linear_small_chain(const LinArgs* probs, const int* epis, const int* level_of, int nprob, float* counters, hipStream_t st) {
   ARDAE_CHECK_ARG(probs && epis && level_of && nprob >= 1 && counters, "linear_small_chain: bad arguments");
-  static const bool on = !(debug_knob("ARDAE_SMALL_CHAIN") && atoi(debug_knob("ARDAE_SMALL_CHAIN")) == 0);
+  static const bool on = knob_on("ARDAE_SMALL_CHAIN");
   ScArgs c;
   memset(&c, 0, sizeof(c));
   static_assert(sizeof(ScArgs) <= 4096, "kernel arguments");
@@ -782,7 +783,7 @@ int launch_linear_small_chain(const LinArgs* probs, const int* epis, const int* 
   const int M = probs[0].M;
   int nlev = 0;
   bool all16 = small_fast_on();
-  for (int i = 0; all16 && i < nprob; ++i) all16 = small_regular16(probs[i]) || (probs[i].Nout <= 32 && probs[i].Nout % 16 == 0 && probs[i].M % 16 == 0 && probs[i].src[0].K % 16 == 0 && probs[i].nsrc == 1);
+  for (int i = 0; all16 && i < nprob; ++i) all16 = small_pick(probs[i]) == SMALL_B16 || (probs[i].Nout <= 32 && probs[i].Nout % 16 == 0 && probs[i].M % 16 == 0 && probs[i].src[0].K % 16 == 0 && probs[i].nsrc == 1);
   const int blk = all16 ? 16 : 32;
   for (int i = 0; ok && i < nprob; ++i) {
     const int l = level_of[i];
@@ -806,24 +807,13 @@ int launch_linear_small_chain(const LinArgs* probs, const int* epis, const int* 
     return 0;
   }
   c.nlev = nlev; c.M = M; c.cnt = reinterpret_cast<unsigned*>(counters);
-  static const bool fast = !(debug_knob("ARDAE_SMALL_CHAIN_FAST") && atoi(debug_knob("ARDAE_SMALL_CHAIN_FAST")) == 0);
-  static const int dbg = debug_knob("ARDAE_SC_DEBUG") ? atoi(debug_knob("ARDAE_SC_DEBUG")) : 0;     // 2: no compute, 4: no hand-over, 8: cycle stamps of one block (timing only)
+  static const bool fast = knob_on("ARDAE_SMALL_CHAIN_FAST");
+  static const int dbg = knob_int("ARDAE_SC_DEBUG", 0);     // 2: no compute, 4: no hand-over, 8: cycle stamps of one block (timing only)
   c.fast = (fast ? 1 : 0) | (dbg & 30);
   c.nrb = nrb;
   c.blk = blk;
   ARDAE_TRY(launch_fill(counters, (size_t)SC_CNT_STRIDE * nrb, 0.f, st));
-  if (g_prof_enabled) {
-    double fl = 0, by = 0;
-    for (int i = 0; i < nprob; ++i) {
-      double ksum = 0;
-      for (int s = 0; s < probs[i].nsrc; ++s) ksum += probs[i].src[s].K;
-      fl += 2.0 * M * (double)probs[i].Nout * ksum;
-      by += 4.0 * ((double)M * ksum + 2.0 * M * (double)probs[i].Nout + ksum * probs[i].Nout);
-    }
-    char name[64];
-    snprintf(name, sizeof(name), "linear_small_chain_kernel x%d", nlev);
-    prof_begin(st, name, fl, by);
-  }
+  if (g_prof_enabled) prof_begin_named(st, lin_cost_sum(probs, nprob, [](const LinArgs&) { return 2.0; }), "linear_small_chain_kernel x%d", nlev);
   const int groups = ceil_div(nrb, 8);
   hipLaunchKernelGGL(linear_small_chain_kernel, dim3(groups * 8 * c.nj), dim3(256), 0, st, c);
   prof_end(st);
@@ -835,44 +825,22 @@ int launch_linear_small_chain(const LinArgs* probs, const int* epis, const int* 
 // (instantiated for what the score pass needs: forward layers), two launches of launch_linear otherwise
 int launch_linear_pair(const LinArgs& a0, const LinArgs& a1, int epi, hipStream_t st) {
   if (epi == EPI_ACT && a0.act == a1.act && linear_small_eligible(a0, epi) && linear_small_eligible(a1, epi) && !a0.Y2 && !a1.Y2) {
-    if (a0.act == ACT_SOFTPLUS) return launch_small_pair<EPI_ACT, ACT_SOFTPLUS>(a0, a1, st);
-    if (a0.act == ACT_RELU) return launch_small_pair<EPI_ACT, ACT_RELU>(a0, a1, st);
+    const int rc = dispatch_act(ActsHidden{}, a0.act, [&](auto A) { return launch_small_pair<EPI_ACT, decltype(A)::value>(a0, a1, st); });
+    if (rc != ACT_UNLISTED) return rc;
   }
   ARDAE_TRY(launch_linear(a0, epi, st));
   return launch_linear(a1, epi, st);
 }
 
 int launch_linear_small(const LinArgs& a, int epi, hipStream_t st) {
+  int rc = ACT_UNLISTED;
   switch (epi) {
-    case EPI_ACT:
-      if (a.act == ACT_NONE) return launch_small<EPI_ACT, ACT_NONE>(a, st);
-      if (a.act == ACT_RELU) return launch_small<EPI_ACT, ACT_RELU>(a, st);
-      if (a.act == ACT_SOFTPLUS) return launch_small<EPI_ACT, ACT_SOFTPLUS>(a, st);
-      if (a.act == ACT_ELU) return launch_small<EPI_ACT, ACT_ELU>(a, st);
-      if (a.act == ACT_TANH) return launch_small<EPI_ACT, ACT_TANH>(a, st);
-      if (a.act == ACT_LEAKY) return launch_small<EPI_ACT, ACT_LEAKY>(a, st);
-      if (a.act == ACT_SWISH) return launch_small<EPI_ACT, ACT_SWISH>(a, st);
-      break;
-    case EPI_DACT:
-      if (a.act == ACT_NONE) return launch_small<EPI_DACT, ACT_NONE>(a, st);
-      if (a.act == ACT_RELU) return launch_small<EPI_DACT, ACT_RELU>(a, st);
-      if (a.act == ACT_SOFTPLUS) return launch_small<EPI_DACT, ACT_SOFTPLUS>(a, st);
-      if (a.act == ACT_ELU) return launch_small<EPI_DACT, ACT_ELU>(a, st);
-      if (a.act == ACT_TANH) return launch_small<EPI_DACT, ACT_TANH>(a, st);
-      if (a.act == ACT_LEAKY) return launch_small<EPI_DACT, ACT_LEAKY>(a, st);
-      if (a.act == ACT_SWISH) return launch_small<EPI_DACT, ACT_SWISH>(a, st);
-      break;
-    case EPI_CHAIN:
-      if (a.act == ACT_SOFTPLUS) return launch_small<EPI_CHAIN, ACT_SOFTPLUS>(a, st);
-      if (a.act == ACT_RELU) return launch_small<EPI_CHAIN, ACT_RELU>(a, st);
-      if (a.act == ACT_ELU) return launch_small<EPI_CHAIN, ACT_ELU>(a, st);
-      if (a.act == ACT_TANH) return launch_small<EPI_CHAIN, ACT_TANH>(a, st);
-      if (a.act == ACT_LEAKY) return launch_small<EPI_CHAIN, ACT_LEAKY>(a, st);
-      if (a.act == ACT_SWISH) return launch_small<EPI_CHAIN, ACT_SWISH>(a, st);
-      break;
+    case EPI_ACT: rc = dispatch_act(ActsAll{}, a.act, [&](auto A) { return launch_small<EPI_ACT, decltype(A)::value>(a, st); }); break;
+    case EPI_DACT: rc = dispatch_act(ActsAll{}, a.act, [&](auto A) { return launch_small<EPI_DACT, decltype(A)::value>(a, st); }); break;
+    case EPI_CHAIN: rc = dispatch_act(ActsChainEpi{}, a.act, [&](auto A) { return launch_small<EPI_CHAIN, decltype(A)::value>(a, st); }); break;
   }
-  ARDAE_CHECK_ARG(false, "linear_small: unsupported epilogue/activation combination (epi=%d act=%d)", epi, a.act);
-  return -1;
+  ARDAE_CHECK_ARG(rc != ACT_UNLISTED, "linear_small: unsupported epilogue/activation combination (epi=%d act=%d)", epi, a.act);
+  return rc;
 }
 
 }  // namespace ardae

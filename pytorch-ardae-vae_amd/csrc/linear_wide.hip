@@ -8,9 +8,8 @@ namespace ardae {
 namespace wide {
 
 int wide_grid(int ntiles, int ncp) {
-  static const char* genv = debug_knob("ARDAE_WIDE_GRID");   // experiments: resident workgroups
-  int g = genv ? atoi(genv) : 256;
-  g -= g % ncp;
+  static const int resident = knob_int("ARDAE_WIDE_GRID", 256);   // experiments: resident workgroups
+  const int g = resident - resident % ncp;
   return ntiles < g ? ntiles : g;
 }
 
@@ -19,8 +18,6 @@ int wide_grid(int ntiles, int ncp) {
 namespace {
 
 using namespace wide;
-
-bool al16w(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // supported K layouts (the wave's weight slab, 32 NJ columns x K, must fit its 256 AGPRs): one source of K = 256 (four 64-wide
 // panels) or K = 32 (one 32-wide panel) with two column blocks per wave (workgroup = 256 columns), or K = 512 (eight panels)
@@ -73,7 +70,7 @@ bool linear_wide_eligible(const LinArgs& a, int epi) {
   if (a.M <= 0 || (a.M % WBM) || a.Nout <= 0 || (a.Nout % wgcols)) return false;
   if ((int64_t)(a.M / WBM) * (a.Nout / wgcols) < 128) return false;   // small problems: the 32 x 128 tiling fills the chip better
   for (int s = 0; s < a.nsrc; ++s) {
-    if (a.src[s].K % 32 || (a.src[s].ld & 3) || !al16w(a.src[s].x)) return false;
+    if (a.src[s].K % 32 || (a.src[s].ld & 3) || !aligned16(a.src[s].x)) return false;
     if ((int64_t)a.src[s].ld * a.M * 4 >= (int64_t)1 << 32) return false;   // 32-bit buffer offsets
   }
   if (epi == EPI_DAE_LOSS) return false;   // Nout = z_dim there (narrow geometry)
@@ -105,7 +102,7 @@ bool linear_wide_eligible(const LinArgs& a, int epi) {
 // one activation, the same optional operands in every layer (forward: bias only; DACT: all with Q or none; CHAIN), every layer reading
 // its predecessor's Y.  ARDAE_WIDE_LAYERS=0: off (A/B).
 bool linear_wide_layers_eligible(const LinArgs* L, int nl, int epi) {
-  static const bool on = !(debug_knob("ARDAE_WIDE_LAYERS") && atoi(debug_knob("ARDAE_WIDE_LAYERS")) == 0);
+  static const bool on = knob_on("ARDAE_WIDE_LAYERS");
   if (!on || nl < 2 || nl > WIDE_MAXL || !(epi == EPI_ACT || epi == EPI_DACT || epi == EPI_CHAIN)) return false;
   const LinArgs& f = L[0];
   if (f.act != ACT_SOFTPLUS && !(f.act == ACT_RELU && epi != EPI_CHAIN)) return false;
@@ -125,34 +122,22 @@ bool linear_wide_layers_eligible(const LinArgs* L, int nl, int epi) {
 
 int launch_linear_wide_layers(const LinArgs* L, int nl, int epi, hipStream_t st) {
   ARDAE_CHECK_ARG(linear_wide_layers_eligible(L, nl, epi), "linear_wide_layers: run not eligible");
-  const int act = L[0].act;
-  if (epi == EPI_ACT) return act == ACT_SOFTPLUS ? launch_wide_layers<8, 4, 2, EPI_ACT, ACT_SOFTPLUS, false, false>(L, nl, st)
-                                                 : launch_wide_layers<8, 4, 2, EPI_ACT, ACT_RELU, false, false>(L, nl, st);
-  if (epi == EPI_CHAIN) return launch_wide_layers<8, 4, 2, EPI_CHAIN, ACT_SOFTPLUS, false, false>(L, nl, st);
-  if (L[0].Q) return act == ACT_SOFTPLUS ? launch_wide_layers<8, 4, 2, EPI_DACT, ACT_SOFTPLUS, true, false>(L, nl, st)
-                                         : launch_wide_layers<8, 4, 2, EPI_DACT, ACT_RELU, true, false>(L, nl, st);
-  return act == ACT_SOFTPLUS ? launch_wide_layers<8, 4, 2, EPI_DACT, ACT_SOFTPLUS, false, false>(L, nl, st)
-                             : launch_wide_layers<8, 4, 2, EPI_DACT, ACT_RELU, false, false>(L, nl, st);
+  const int act = L[0].act;      // one of its list: the eligibility rule has admitted it
+  if (epi == EPI_ACT) return dispatch_act(ActsHidden{}, act, [&](auto A) { return launch_wide_layers<8, 4, 2, EPI_ACT, decltype(A)::value, false, false>(L, nl, st); });
+  if (epi == EPI_CHAIN) return dispatch_act(ActsSoftplus{}, act, [&](auto A) { return launch_wide_layers<8, 4, 2, EPI_CHAIN, decltype(A)::value, false, false>(L, nl, st); });
+  if (L[0].Q) return dispatch_act(ActsHidden{}, act, [&](auto A) { return launch_wide_layers<8, 4, 2, EPI_DACT, decltype(A)::value, true, false>(L, nl, st); });
+  return dispatch_act(ActsHidden{}, act, [&](auto A) { return launch_wide_layers<8, 4, 2, EPI_DACT, decltype(A)::value, false, false>(L, nl, st); });
 }
 
 int launch_linear_wide(const LinArgs& a, int epi, hipStream_t st) {
+  int rc = ACT_UNLISTED;
   switch (epi) {
-    case EPI_ACT:
-      if (a.act == ACT_NONE) return launch_wide_flags<EPI_ACT, ACT_NONE>(a, st);
-      if (a.act == ACT_RELU) return launch_wide_flags<EPI_ACT, ACT_RELU>(a, st);
-      if (a.act == ACT_SOFTPLUS) return launch_wide_flags<EPI_ACT, ACT_SOFTPLUS>(a, st);
-      break;
-    case EPI_DACT:
-      if (a.act == ACT_NONE) return launch_wide_flags<EPI_DACT, ACT_NONE>(a, st);
-      if (a.act == ACT_RELU) return launch_wide_flags<EPI_DACT, ACT_RELU>(a, st);
-      if (a.act == ACT_SOFTPLUS) return launch_wide_flags<EPI_DACT, ACT_SOFTPLUS>(a, st);
-      break;
-    case EPI_CHAIN:
-      if (a.act == ACT_SOFTPLUS) return launch_wide_flags<EPI_CHAIN, ACT_SOFTPLUS>(a, st);
-      break;
+    case EPI_ACT: rc = dispatch_act(ActsShipped{}, a.act, [&](auto A) { return launch_wide_flags<EPI_ACT, decltype(A)::value>(a, st); }); break;
+    case EPI_DACT: rc = dispatch_act(ActsShipped{}, a.act, [&](auto A) { return launch_wide_flags<EPI_DACT, decltype(A)::value>(a, st); }); break;
+    case EPI_CHAIN: rc = dispatch_act(ActsSoftplus{}, a.act, [&](auto A) { return launch_wide_flags<EPI_CHAIN, decltype(A)::value>(a, st); }); break;
   }
-  ARDAE_CHECK_ARG(false, "linear_wide: unsupported epilogue/activation combination (epi=%d act=%d)", epi, a.act);
-  return -1;
+  ARDAE_CHECK_ARG(rc != ACT_UNLISTED, "linear_wide: unsupported epilogue/activation combination (epi=%d act=%d)", epi, a.act);
+  return rc;
 }
 
 }  // namespace ardae

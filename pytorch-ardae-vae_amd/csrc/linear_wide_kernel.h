@@ -715,16 +715,9 @@ int launch_wide(const LinArgs& a, hipStream_t st) {
   const int nrt = tpg ? (a.M / a.rows_per_group) * tpg : a.M / WBM;
   const int ntiles = nrt * ncp;
   const int grid = wide_grid(ntiles, ncp);
-  if (g_prof_enabled) {
-    char name[96];
-    // spelled as rocprofv3 demangles the instantiation: bench.py joins this log with profiles/pmc_summary.json by name
-    snprintf(name, sizeof(name), "linear_wide_kernel<%d, %d, %d, %d, %d, %s, %s>", NCH, NP, NJ, EPI, ACT, F1 ? "true" : "false", F2 ? "true" : "false");
-    double ksum = 0;
-    for (int s = 0; s < a.nsrc; ++s) ksum += a.src[s].K;
-    double tensors = 1.0 + (a.Y2 ? 1 : 0) + ((EPI == EPI_DACT || EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_CHAIN) ? 1 : 0) +
-                     ((EPI == EPI_DACT && a.Q) ? 1 : 0);
-    prof_begin(st, name, 2.0 * a.M * (double)a.Nout * ksum, 4.0 * ((double)a.M * ksum + tensors * a.M * (double)a.Nout + ksum * a.Nout));
-  }
+  if (g_prof_enabled)      // spelled as rocprofv3 demangles the instantiation: bench.py joins this log with profiles/pmc_summary.json by name
+    prof_begin_named(st, lin_cost(a, epi_tensors(a, EPI)), "linear_wide_kernel<%d, %d, %d, %d, %d, %s, %s>", NCH, NP, NJ, EPI, ACT, F1 ? "true" : "false",
+                     F2 ? "true" : "false");
   hipLaunchKernelGGL((linear_wide_kernel<NCH, NP, NJ, EPI, ACT, F1, F2>), dim3(grid), dim3(256), 0, st, a, nrt, ncp, tpg);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();
@@ -742,18 +735,9 @@ int launch_wide_layers(const LinArgs* L, int nl, hipStream_t st) {
   memset(&c, 0, sizeof(c));
   c.nl = nl;
   for (int l = 0; l < nl; ++l) c.L[l] = L[l];
-  if (g_prof_enabled) {
-    char name[112];
-    snprintf(name, sizeof(name), "linear_wide_layers_kernel<%d, %d, %d, %d, %d, %s, %s> x%d", NCH, NP, NJ, EPI, ACT, F1 ? "true" : "false", F2 ? "true" : "false", nl);
-    double fl = 0, by = 0;
-    for (int l = 0; l < nl; ++l) {
-      const double K = L[l].src[0].K;
-      const double tensors = 1.0 + (L[l].Y2 ? 1 : 0) + ((EPI == EPI_DACT || EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_CHAIN) ? 1 : 0) + ((EPI == EPI_DACT && L[l].Q) ? 1 : 0);
-      fl += 2.0 * a.M * (double)a.Nout * K;
-      by += 4.0 * ((double)a.M * K + tensors * a.M * (double)a.Nout + K * a.Nout);
-    }
-    prof_begin(st, name, fl, by);
-  }
+  if (g_prof_enabled)
+    prof_begin_named(st, lin_cost_sum(L, nl, [](const LinArgs& l) { return epi_tensors(l, EPI); }), "linear_wide_layers_kernel<%d, %d, %d, %d, %d, %s, %s> x%d", NCH,
+                     NP, NJ, EPI, ACT, F1 ? "true" : "false", F2 ? "true" : "false", nl);
   hipLaunchKernelGGL((linear_wide_layers_kernel<NCH, NP, NJ, EPI, ACT, F1, F2>), dim3(grid), dim3(256), 0, st, c, nrt, ncp, 0);
   prof_end(st);
   ARDAE_LAUNCH_CHECK();

@@ -415,7 +415,7 @@ int launch_wgrad_batch(const WgradProblem* probs, int nprob, hipStream_t st) {
     }
   }
   // per-image problems (few rows): one 32 x 32 tile per wave (wgrad_small_kernel).  ARDAE_WGRAD_SMALL=0: off
-  static const bool small_on = !(debug_knob("ARDAE_WGRAD_SMALL") && atoi(debug_knob("ARDAE_WGRAD_SMALL")) == 0);
+  static const bool small_on = knob_on("ARDAE_WGRAD_SMALL");
   bool is_small[WGRAD_MAX_PROBLEMS] = {false};
   WgradBatchDev b;
   {

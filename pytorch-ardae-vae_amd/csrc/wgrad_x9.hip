@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x9_kernel(const WwBatchDev batch
 }  // namespace
 
 bool wgrad_x9_eligible(const WgradProblem& p) {
-  static const bool off = debug_knob("ARDAE_WGRAD_X9") && atoi(debug_knob("ARDAE_WGRAD_X9")) == 0;
+  static const bool off = !knob_on("ARDAE_WGRAD_X9");
   if (off || p.O % XT || p.I % XT || p.M % XRC || p.M < 64 * 32) return false;
   // sigma is read four rows at a time (global_load_dwordx4 at rowscale + m0 + 4 q): a 16-byte aligned base, like G and X, or the
   // problem stays on wgrad_wide_kernel<256x256>, which reads it one dword at a time

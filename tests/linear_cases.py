@@ -1,6 +1,7 @@
 """The harness of tests/test_linear_exact_gpu.py: `ardae_linear`, `ardae_linear_chain` and `ardae_linear_wide_layers` with STRIDED operands in
 GUARDED buffers, on data for which most epilogues have one representable result (torch.equal, no tolerance), and with the kernel that ran
-asserted through the profile log.  tests/test_linear_cases.py runs the same cases through a pure-PyTorch emulator on the CPU (and through
+asserted through the profile log, together with the flops and bytes that log reports for it (tests/golden/linear_profile_costs.json).
+tests/test_linear_cases.py runs the same cases through a pure-PyTorch emulator on the CPU (and through
 deliberately wrong emulators, which check() must refuse).
 
 Layouts, applied to every operand a case has:
@@ -26,7 +27,9 @@ Data (CPU generator; the device gets copies, so the emulator sees the same numbe
               the profile log names the same kernel for both (the three per-image blocks: always - one k order is their stated rule)."""
 import ctypes
 import functools
+import json
 import math
+import os
 import zlib
 from dataclasses import dataclass, replace
 
@@ -380,9 +383,69 @@ def _library(inp, per_layer):
         else:
             assert lib.ardae_linear_wide_layers_eligible(arr, c.nl, epi) == 1, c.tag
             L.check(lib.ardae_linear_wide_layers(arr, c.nl, epi, L.stream_ptr()), "ardae_linear_wide_layers")
-        return {e["name"] for e in L.profile_report(max_entries=64)}
+        return L.profile_report(max_entries=64)
     finally:
         lib.ardae_profile_enable(0)
+
+
+# ---- the cost model: (name, calls, flops, bytes) of the profile log, recorded from a build of the commit BEFORE the launchers' cost
+# expressions were written once (tools/gen_linear_profile_costs.py).  bench.py builds its roofline from these numbers.
+COSTS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "linear_profile_costs.json")
+_LINEAR_FAMILY = ("linear_", "sampler_tail_")
+
+
+@functools.lru_cache(maxsize=1)
+def recorded_costs():
+    with open(COSTS_PATH) as f:
+        return json.load(f)
+
+
+def costs(entries):
+    """The linear family's entries of a profile report as sorted [name, calls, flops, bytes]; flops and bytes are integer-valued doubles
+    far below 2^53 (sums of products of sizes), so the comparison with the fixture is exact whatever the order of summation."""
+    out = []
+    for e in entries:
+        if e["name"].startswith(_LINEAR_FAMILY):
+            assert e["flops"] == int(e["flops"]) and e["bytes"] == int(e["bytes"]) and max(e["flops"], e["bytes"]) < 2 ** 53, e
+            out.append([e["name"], int(e["calls"]), int(e["flops"]), int(e["bytes"])])
+    return sorted(out)
+
+
+def profiled(fn):
+    """fn() with the profile log on -> costs() of what it launched."""
+    lib = L.lib()
+    lib.ardae_profile_enable(1)
+    try:
+        fn()
+        return costs(L.profile_report(max_entries=64))
+    finally:
+        lib.ardae_profile_enable(0)
+
+
+def scene_score_pass(B=64, S=1):
+    """The 64-row cDAE score pass of tests/test_cdae_gpu.py's chain-cap child.  One row per image (64 x 1): the whole pass is ONE launch of
+    the small chain, its two encoders levels of two problems.  Two rows per image (32 x 2): no chain launch (csrc/cdae.hip), the
+    encoders' levels go out as launches of the pair, the rest one launch per layer."""
+    from oracle import ardae_oracle as O
+    from test_cdae_gpu import CdaeHarness
+    cc = O.CdaeCfg("grad", 32, 32, 256, 3, "softplus")
+    pc = O.init_params(O.cdae_param_spec(cc), 3)
+    H = CdaeHarness(cc, torch.cat([pc[n].reshape(-1) for n, _ in O.cdae_param_spec(cc)]))
+    g = torch.Generator().manual_seed(64)
+    x, ctx, sigma = torch.randn(B * S, 32, generator=g) * 30, torch.randn(B, 32, generator=g), torch.zeros(B * S)
+    return profiled(lambda: H.score(x, sigma, ctx, B, S))
+
+
+def scene_forward_hidden():
+    """One forward_hidden of the mnist 784 / 100 / 256 / 32 model at 32 images x nz 256: 8192 rows, the fewest the short-K and tail kernels take."""
+    import ardae_amd as net
+    torch.manual_seed(3)
+    model = net.MNISTIPVAE(input_dim=784, noise_dim=100, h_dim=256, num_hidden_layers=2, nonlinearity="softplus", enc_type="concat", z_dim=32).to("cuda")
+    x, noise = (torch.rand(32, 784) < 0.2).float().cuda(), torch.randn(32 * 256, 100).cuda()
+    return profiled(lambda: model.forward_hidden(x, nz=256, noise=noise))
+
+
+SCENES = dict(score_pass_64=scene_score_pass, score_pass_32x2=functools.partial(scene_score_pass, 32, 2), forward_hidden_8192=scene_forward_hidden)
 
 
 def emulate(inp, bug=None):
@@ -455,11 +518,15 @@ def launch(case, inp, backend="lib"):
     assert replace(inp["case"], layout=case.layout) == case
     if callable(backend):
         return backend(inp)
-    names = _library(inp, backend == "per_layer")
+    entries = _library(inp, backend == "per_layer")
+    names = {e["name"] for e in entries}
     if backend == "lib":
         head, tail = kernel_of(case)
         assert len(names) == 1 and all(n.startswith(head) and n.endswith(tail) for n in names), \
             f"{case.tag}: ran {sorted(names)}, meant for {head}...{tail} under {dict(zip(_KNOBS, knob_env()))}"
+        if knob_env() == ("1", "1", "1", "1"):       # the fixture holds the default environment: a case's cost follows its tag, not its layout or data
+            want = recorded_costs()["cases"][case.tag]
+            assert costs(entries) == want, f"{case.tag}: the profile log reports {costs(entries)}, the recorded cost is {want}"
     return names
 
 

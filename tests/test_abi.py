@@ -187,6 +187,61 @@ def test_abi_version_and_error_channel():
         L.check(lib.ardae_pack_weight(None, 0, 0, 0, 0, None, None))
 
 
+def _linear_args(M, K, Nout, epi):
+    """A valid call of ardae_linear for `epi` on arbitrary non-null, 16-byte aligned addresses (never launched: every use adds a defect)."""
+    a = L.LinearArgs()
+    a.M, a.Nout, a.nsrc, a.act = M, Nout, 1, L.ACT["softplus"]
+    a.src[0].x, a.src[0].ld, a.src[0].K, a.src[0].wp = 1 << 20, K, K, 2 << 20
+    a.Y, a.ldY = 3 << 20, Nout
+    if epi in (L.EPI_DACT, L.EPI_CHAIN):
+        a.S, a.ldS = 4 << 20, Nout
+    if epi == L.EPI_CHAIN:
+        a.R, a.ldR, a.Y2, a.ldY2 = 5 << 20, Nout, 6 << 20, Nout
+    if epi == L.EPI_DAE_LOSS:
+        a.sigma, a.eps, a.ldeps, a.tile_loss = 7 << 20, 8 << 20, Nout, 9 << 20
+    return a
+
+
+LINEAR_DEFECTS = {      # name -> (epilogue, the defect, the validator's message)
+    "empty_M": (0, dict(M=0), "linear: empty problem (M=0"),
+    "nsrc_0": (0, dict(nsrc=0), "linear: nsrc must be 1 or 2"),
+    "nsrc_3": (0, dict(nsrc=3), "linear: nsrc must be 1 or 2"),
+    "ld_below_K": (0, dict(ld=-1), "linear: bad source 0 (K="),
+    "null_Y": (1, dict(Y=None), "linear: Y is null"),
+    "dact_without_S": (1, dict(S=None), "linear: EPI_DACT needs S"),
+    "chain_without_S": (2, dict(S=None), "linear: EPI_CHAIN needs S, R and Y2"),
+    "chain_without_R": (2, dict(R=None), "linear: EPI_CHAIN needs S, R and Y2"),
+    "chain_without_Y2": (2, dict(Y2=None), "linear: EPI_CHAIN needs S, R and Y2"),
+    "chain_act_none": (2, dict(act=0), "linear: unsupported epilogue/activation combination (epi=2 act=0)"),
+    "dae_loss_without_sigma": (3, dict(sigma=None), "linear: EPI_DAE_LOSS needs sigma and eps"),
+    "act_99": (0, dict(act=99), "linear: unknown activation 99"),
+    "dact_act_99": (1, dict(act=99), "linear: unknown activation 99"),
+    "epi_99": (99, {}, "linear: unknown epilogue 99"),
+    "rowbias_group_0": (0, dict(rowbias=10 << 20, rowbias_ld=256, rows_per_group=0), "linear: rows_per_group must be positive"),
+}
+# a per-image shape, a ragged one for linear_kernel, and two the wide kernel takes (whole 64-row tiles, K = Nout = 256, 128 and 256 tiles)
+LINEAR_DEFECT_SHAPES = [(64, 64, 64), (300, 100, 70), (8192, 256, 256), (16384, 256, 256)]
+
+
+@pytest.mark.parametrize("shape", LINEAR_DEFECT_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("defect", sorted(LINEAR_DEFECTS))
+def test_linear_validation_does_not_depend_on_the_kernel_path(defect, shape):
+    """launch_linear validates once, before any eligibility rule (csrc/linear.hip::validate_linear): one defect at a time gives a negative
+    status and the validator's message whichever kernel the shape would have selected; validation precedes every HIP call."""
+    assert (L.EPI_ACT, L.EPI_DACT, L.EPI_CHAIN, L.EPI_DAE_LOSS) == (0, 1, 2, 3)
+    epi, change, message = LINEAR_DEFECTS[defect]
+    M, K, Nout = shape
+    a = _linear_args(M, K, Nout, epi)
+    for k, v in change.items():
+        if k == "ld":
+            a.src[0].ld = K + v
+        else:
+            setattr(a, k, v)
+    lib = L.lib()
+    assert lib.ardae_linear(ctypes.byref(a), epi, None) < 0
+    assert message.encode() in lib.ardae_last_error(), lib.ardae_last_error()
+
+
 # packed floats and workspace floats at (B, nz) = (8, 16) for modes 0 .. 3, as the C side gave them before the packed buffers were laid
 # out from one pack list (the packed-buffer and workspace layouts are part of no interface, but a change of either is a change of every offset)
 MODEL_SIZES = [("mnist", (784, 100, 256, 32, 2), 2, 0, 1656832, [66176, 1735232, 98304, 56256]),

@@ -43,6 +43,21 @@ def test_default_environment_reaches_all_eleven_kernels():
     assert len(heads) >= 14 + 2        # 12 single-launch paths, chain x2 / x3, wide layers x2 / x3
 
 
+def test_profile_costs_of_the_engine_launches():
+    """The launchers that ardae_linear does not reach - the small chain (the 64-row cDAE score pass at one row per image), the per-image
+    pair (the same 64 rows at two rows per image: that pass is not chained), the sampler tail behind the short-K layer (forward_hidden on
+    8192 rows) - report the (name, calls, flops, bytes) recorded from the commit before the cost model was written once; exact, like
+    every case of the table."""
+    if C.knob_env() != ("1", "1", "1", "1"):
+        return
+    reached = set()
+    for scene, run in sorted(C.SCENES.items()):
+        got, want = run(), C.recorded_costs()["scenes"][scene]
+        assert got == want, f"{scene}: the profile log reports {got}, recorded {want}"
+        reached |= {name.split("<")[0].split(" ")[0] for name, *_ in got}
+    assert {"linear_small_pair_kernel", "linear_small_chain_kernel"} <= reached and any(n.startswith("sampler_tail") for n in reached), reached
+
+
 def test_knob_only_generic_kernel_under_the_same_cases():
     """The library reads its knobs once per process: this file again in a fresh child process with the per-image, narrow, short-K and wide
     kernels switched off - every single launch on linear_kernel, in the geometry the table of linear_cases.py expects."""
