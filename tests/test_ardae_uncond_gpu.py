@@ -256,7 +256,7 @@ def test_score_engine_resumes_bit_identically(kind, optimizer):
 @pytest.mark.parametrize("kind", ["grad", "res"])
 def test_training_quality_against_the_reference_seeds(golden_dir, kind):
     """The training cell of notebooks/ardae_toy.ipynb on x ~ N(0, I_2) with the notebook's optimiser (torch.optim.Adam over the module's
-    parameters); every constant comes from the fixture tools/gen_ardae_golden.py wrote with the reference classes."""
+    parameters); every constant comes from the fixture tools/gen_score_golden.py (family ardae) wrote with the reference classes."""
     q = load(os.path.join(golden_dir, "ardae_uncond_quality.npz"))
     B, ns, steps, tail, delta, lr = int(q["B"]), int(q["nsigma"]), int(q["steps"]), int(q["tail"]), float(q["delta"]), float(q["lr"])
     xt = torch.tensor(q["x_t"]).cuda()

@@ -11,7 +11,7 @@ import torch
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
-from oracle import ardae_oracle as O
+from oracle import fixture_params as P
 import vae_restate as R
 from vae_restate import BETAS, TOL64, clip_logvar, fails, lin, load, mlp_fwd, rel
 from vae_restate import aux_forward_backward as forward_backward      # the family's restatement, in float64 numpy with the backward by hand
@@ -28,11 +28,9 @@ def shape_of(fx):
 
 
 def aux_params(fx, dtype=torch.float32):
-    """The parameters of a fixture, regenerated as tools/gen_vae_aux_golden.py::aux_params made them"""
+    """The parameters of a fixture, regenerated with the recipe tools/gen_vae_golden.py called (oracle.fixture_params.aux)"""
     family, (B, D, h, nd, z, nl), _, _ = shape_of(fx)
-    p = O.init_params(layout.aux_vae_spec(family, D, nd, h, z, nl), int(fx["seed"]), None, dtype)
-    p["aux_encode.reparam.logvar_fn.bias"].add_(torch.linspace(-5.0, 2.5, nd, dtype=dtype))
-    return p
+    return P.aux(family, D, nd, h, z, nl, int(fx["seed"]), dtype)
 
 
 def params64(fx):

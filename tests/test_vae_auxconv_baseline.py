@@ -3,8 +3,8 @@ validation through the C ABI (ardae_conv_tail included), the module surface, and
 the same 2x - 1, the two concatenations with the trunk output FIRST, both KLs, the three-stage logprob - that the GPU tests lean on, pinned here to the
 reference's float64 fixtures.  No GPU needed.
 
-The fixtures (tools/gen_vae_auxconv_golden.py) do not store the parameters: `auxconv_params` regenerates them from the stored seed with the oracle's
-platform-independent initialiser, exactly as the tool did."""
+The fixtures (tools/gen_vae_golden.py, family auxconv) do not store the parameters: `auxconv_params` regenerates them from the stored seed with the
+recipe the tool called (oracle.fixture_params.auxconv)."""
 import ctypes
 import functools
 import math
@@ -16,7 +16,7 @@ import torch.nn.functional as F
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
-from oracle import ardae_oracle as O
+from oracle import fixture_params as P
 import vae_restate as R
 from vae_restate import ACTS, BETAS, TOL64, fails, kld_rows, lin, load, log_normal_rows, pair_kld_rows, rel, relaxed_sample
 
@@ -30,9 +30,9 @@ def shape_of(fx):
 
 
 def auxconv_params(fx, dtype=torch.float32):
-    """tools/gen_vae_auxconv_golden.py: oracle.init_params on layout.aux_conv_vae_spec(noise, z) (the float64 runs start from the fp32 numbers, widened)"""
+    """The recipe tools/gen_vae_golden.py called: oracle.fixture_params.auxconv (the float64 runs start from the fp32 numbers, widened)"""
     (_, nd, z), _ = shape_of(fx)
-    return {k: v.to(dtype) for k, v in O.init_params(layout.aux_conv_vae_spec(nd, z), int(fx["seed"])).items()}
+    return {k: v.to(dtype) for k, v in P.auxconv(nd, z, int(fx["seed"])).items()}
 
 
 # ---- the test-side oracle: the family restated in plain torch (trunk and decoder: vae_restate) ---------------------------------------

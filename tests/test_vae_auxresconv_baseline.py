@@ -3,8 +3,8 @@ rules and argument validation through the C ABI (ardae_resconv_mid included), th
 the float64 torch restatement of the family - ONE weight-normalised trunk, the two concatenations with ctx FIRST, both KLs, the three-stage logprob, and
 the decoder's 14 x 14 stage on its own - that the GPU tests lean on, pinned here to the reference's float64 fixtures.  No GPU needed.
 
-The fixtures (tools/gen_vae_auxresconv_golden.py) do not store the parameters: `auxres_params` regenerates them from the stored seed with the oracle's
-platform-independent initialiser, exactly as the tool did."""
+The fixtures (tools/gen_vae_golden.py, family auxresconv) do not store the parameters: `auxres_params` regenerates them from the stored seed with the
+recipe the tool called (oracle.fixture_params.auxresconv)."""
 import ctypes
 import functools
 import math
@@ -17,6 +17,7 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
+from oracle import fixture_params as P
 import vae_restate as R
 from vae_restate import BETAS, TOL64, fails, kld_rows, lin, load, log_normal_rows, pair_kld_rows, rel, relaxed_sample
 from vae_restate import resconv_decode_logit as decode_logit
@@ -33,10 +34,9 @@ def shape_of(fx):
 
 
 def auxres_params(fx, dtype=torch.float32):
-    """tools/gen_vae_auxresconv_golden.py: oracle.init_params on layout.aux_resconv_vae_spec(noise, z, c_dim) (the float64 runs start from the fp32
-    numbers, widened)"""
+    """The recipe tools/gen_vae_golden.py called: oracle.fixture_params.auxresconv (the float64 runs start from the fp32 numbers, widened)"""
     (_, nd, z, c), _ = shape_of(fx)
-    return {k: v.to(dtype) for k, v in O.init_params(layout.aux_resconv_vae_spec(nd, z, c), int(fx["seed"])).items()}
+    return {k: v.to(dtype) for k, v in P.auxresconv(nd, z, c, int(fx["seed"])).items()}
 
 
 def desc_of(nd, z, c, center):

@@ -2,8 +2,8 @@
 validation of kind 11 at every entry point, refusals of the module, and the float64 restatement of the family (F.conv2d / F.conv_transpose2d,
 padding and crop as models/vae/conv.py) that the GPU tests lean on - pinned here to the reference's float64 fixtures.  No GPU needed.
 
-The fixtures (tools/gen_vae_conv_golden.py) do not store the 703 405 parameters: `conv_params` regenerates them from the stored seed with the
-oracle's platform-independent initialiser, exactly as the tool did."""
+The fixtures (tools/gen_vae_golden.py, family conv) do not store the 703 405 parameters: `conv_params` regenerates them from the stored seed
+with the recipe the tool called (oracle.fixture_params.conv)."""
 import ctypes
 import functools
 import math
@@ -14,7 +14,7 @@ import torch
 import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
-from oracle import ardae_oracle as O
+from oracle import fixture_params as P
 import vae_restate as R
 from vae_restate import BETAS, TOL64, fails, lin, load, rel, relaxed_sample
 
@@ -22,16 +22,7 @@ CASES = ("z32_b3", "z6_b5")
 D = 784
 
 
-def conv_params(z, seed, special, dtype=torch.float32):
-    """tools/gen_vae_conv_golden.py::conv_params: oracle.init_params on layout.conv_vae_spec(z); special: the init of do_xavier, do_m5bias"""
-    spec = layout.conv_vae_spec(z)
-    sp = None
-    if special:
-        sp = {n: (("xavier",) if n.endswith("weight") else ("zeros",)) for n, _ in spec if "deconv" not in n and "logit_fn" not in n}
-    p = O.init_params(spec, seed, sp, dtype)
-    if special:
-        p["decode.reparam.logit_fn.bias"].fill_(-5.0)
-    return p
+conv_params = P.conv      # (z, seed, special, dtype=): the recipe tools/gen_vae_golden.py loaded into the reference class
 
 
 def fixture_params(fx, dtype=torch.float32):

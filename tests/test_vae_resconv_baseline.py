@@ -3,8 +3,8 @@ argument validation of kind 12 at every entry point and of ardae_resconv_tail, r
 restatement of the family (F.conv2d, F.interpolate and the oracle's weight-norm block helpers) that the GPU tests lean on - pinned here to the
 reference's float64 fixtures.  No GPU needed.
 
-The fixtures (tools/gen_vae_resconv_golden.py) do not store the parameters: `resconv_params` regenerates them from the stored seed with the
-oracle's platform-independent initialiser, exactly as the tool did."""
+The fixtures (tools/gen_vae_golden.py, family resconv) do not store the parameters: `resconv_params` regenerates them from the stored seed with
+the recipe the tool called (oracle.fixture_params.resconv)."""
 import ctypes
 import functools
 import math
@@ -17,6 +17,7 @@ import ardae_amd as net
 from ardae_amd import _lib as L
 from ardae_amd import layout
 from oracle import ardae_oracle as O
+from oracle import fixture_params as P
 import vae_restate as R
 from vae_restate import BETAS, TOL64, fails, lin, load, rel, relaxed_sample
 
@@ -25,12 +26,7 @@ D = 784
 ELU = 3               # ARDAE_ACT_ELU
 
 
-def resconv_params(z, c_dim, seed, special, dtype=torch.float32):
-    """tools/gen_vae_resconv_golden.py::resconv_params: oracle.init_params on layout.resconv_vae_spec(z, c_dim); special: do_m5bias as a setting"""
-    p = O.init_params(layout.resconv_vae_spec(z, c_dim), seed, None, dtype)
-    if special:
-        p["decode.dec.17.conv_01.bias"].fill_(-3.0)
-    return p
+resconv_params = P.resconv      # (z, c_dim, seed, special, dtype=): the recipe tools/gen_vae_golden.py loaded into the reference class
 
 
 def fixture_params(fx, dtype=torch.float32):

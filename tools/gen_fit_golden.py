@@ -36,7 +36,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 from oracle import gen_golden as G  # noqa: E402
-import gen_ardae_golden as A  # noqa: E402
+import gen_score_golden as A  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 ACTS = {"relu": nn.ReLU, "tanh": nn.Tanh, "softplus": nn.Softplus, "elu": nn.ELU}
@@ -133,7 +133,7 @@ def gen_traj(net, ru, name, case, seed):
     B, ns, U, zd = c["B"], c["nsigma"], c["U"], c["z_dim"]
     torch.manual_seed(seed)
     gen = generator(c)
-    dae = A.build(net, c["dae"], 2, c["dae_h"], c["dae_L"], "softplus")
+    dae = A.build(net, A.score_class(c["dae"], "ARDAE"), (c["B"], 2, c["dae_h"], c["dae_L"], "softplus"))
     sd_gen = {k: v.clone() for k, v in gen.state_dict().items()}
     sd_dae = {k: v.clone() for k, v in dae.state_dict().items()}
     g = torch.Generator().manual_seed(seed + 1)
@@ -182,7 +182,7 @@ def gen_quality(net, ru):
         t0 = time.time()
         torch.manual_seed(3000 + seed)
         gen = generator(q)
-        dae = A.build(net, q["dae"], 2, q["dae_h"], q["dae_L"], "softplus")
+        dae = A.build(net, A.score_class(q["dae"], "ARDAE"), (q["B"], 2, q["dae_h"], q["dae_L"], "softplus"))
         untrained.append(statistics(gen, seed))
         fit_loop(net, ru, q, gen, dae, q["steps"])
         trained.append(statistics(gen, seed))
